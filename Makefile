@@ -10,7 +10,7 @@
 #   make test-gpu         GPU tests (needs a HIP device)
 #   make sanitize         ASan/UBSan build of the host tree + native tests
 #   make tsan             ThreadSanitizer build + native tests
-#   make bench            headline benchmark (bench.py) on this host
+#   make bench            headline benchmark with its direct baseline and curve (bench.py --full) on this host
 #   make serve ROOM=r UPSTREAM=http://127.0.0.1:11434
 #   make proxy ROOM=r [LISTEN=127.0.0.1:8000]
 #   make signal [PORT=8787]
@@ -67,7 +67,7 @@ tsan:
 	$(BUILD)-tsan/bin/native_tests
 
 bench: build
-	$(PY) bench.py
+	$(PY) bench.py --full
 
 serve: build
 	@test -n "$(ROOM)" -a -n "$(UPSTREAM)" || (echo "usage: make serve ROOM=<room> UPSTREAM=<url>"; exit 2)

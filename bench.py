@@ -8,8 +8,8 @@ tokens 100 ms apart, then a stop event and [DONE]; HTTP/1.0, no
 Content-Length), the local signal server, ``tunnel serve`` and ``tunnel proxy``
 (native C++; WebRTC data channel over the host's interfaces by default, on the
 1200-byte SCTP path a reference webrtc-rs peer negotiates — ``--mtu jumbo``
-takes this repo's same-host 16 KiB extension instead, and an untimed jumbo
-point is reported beside the headline as ``jumbo_rank0``).
+takes this repo's same-host 16 KiB extension instead, and with ``--full`` an
+untimed jumbo point is reported beside the headline as ``jumbo_rank0``).
 A *step* = one streamed completion on each of S concurrent keep-alive client
 connections (S = 8 for the headline). ``value`` = whole-job tunneled
 requests/s (weak scaling: S streams per GPU).
@@ -24,9 +24,13 @@ gives every rank its own tunnel (round 1's layout).
 
 The upstream and the client are native by default (``tunnel-mock``,
 ``tunnel-loadgen``) so the TTFT numbers measure the tunnel rather than
-CPython; ``--mock python`` uses the Python mock instead. The untimed tail
-measures the 1/2/4-stream points and the direct (untunneled) baseline that
-"added TTFT" is computed against.
+CPython; ``--mock python`` uses the Python mock instead. A plain run sets up,
+warms up, times the K steps and prints the result line. With ``--full`` an
+untimed tail also measures the 1/2/4-stream points, the direct (untunneled)
+baseline that "added TTFT" is computed against and the jumbo-path point; a
+plain run reports those fields as null / empty. ``--dump-outputs DIR`` writes
+the response bodies the clients received in the last timed step as .npy
+arrays (the request is fixed, so two builds compare byte for byte).
 
 The tunnel has no GPU compute: the measured path is
 host-side networking on the MI355X node, so "dtype" is n/a.
@@ -79,7 +83,37 @@ def parse():
                          "scheduler within it (pinning.l3_set_plan); numa: every process on the CPUs of the idlest "
                          "NUMA node (pinning.numa_plan)")
     ap.add_argument("--out", default=None, help="also write the JSON line here")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure (untimed) the direct baseline of the headline (added p50 / "
+                         "p99 TTFT), the --curve points with their direct legs and the jumbo-path point; a plain run "
+                         "times the headline only and reports those fields as null")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the clients received in the last timed step as DIR/<name>.npy (float32): "
+                         "response_bytes [streams, longest body] (the decoded response bodies, padded with -1) and "
+                         "response_len [streams]")
     return ap.parse_args()
+
+
+def dump_outputs(raw_path, out_dir, rank):
+    """The last timed step's response bodies (tunnel-loadgen --dump-last) as .npy arrays."""
+    import struct
+
+    import numpy as np
+    with open(raw_path, "rb") as f:
+        raw = f.read()
+    os.remove(raw_path)
+    (n,), off, bodies = struct.unpack_from("<I", raw, 0), 4, []
+    for _ in range(n):
+        (k,) = struct.unpack_from("<I", raw, off)
+        bodies.append(np.frombuffer(raw, dtype=np.uint8, count=k, offset=off + 4))
+        off += 4 + k
+    width = min(max((len(b) for b in bodies), default=0), (32 << 20) // (4 * max(1, n)))  # well inside 64 MB
+    arr = np.full((n, width), -1.0, dtype=np.float32)
+    for i, b in enumerate(bodies):
+        arr[i, :min(len(b), width)] = b[:width]
+    sfx = f"_rank{rank}" if rank else ""
+    np.save(os.path.join(out_dir, f"response_bytes{sfx}.npy"), arr)
+    np.save(os.path.join(out_dir, f"response_len{sfx}.npy"), np.array([len(b) for b in bodies], dtype=np.float32))
 
 
 def dist_init():
@@ -181,6 +215,11 @@ def main():
         ensure_native()
     if dist:
         dist.barrier()
+    # The compiled core in this process too (the bindings of the code the
+    # tunnel binaries are built from): an unbuilt or stale tree fails here,
+    # and the upstream URLs below go through the parser `tunnel serve` uses.
+    from p2p_llm_tunnel_amd import native
+    core = native()
 
     global PLAN
     if a.pin != "none" and world == 1:  # one GPU's share of the host; N > 1 ranks leave placement to the scheduler
@@ -202,6 +241,10 @@ def main():
     pin_s = ["--cpu-affinity", PLAN["serve"]] if PLAN else []
     pin_p = ["--cpu-affinity", PLAN["proxy"]] if PLAN else []
     upstreams = ",".join(f"http://127.0.0.1:{p}" for p in ups)
+    for u, p in zip(upstreams.split(","), ups):
+        scheme, host, port, _ = core.parse_url(u)
+        if (scheme, host, port) != ("http", "127.0.0.1", p):
+            raise RuntimeError(f"upstream {u!r} parsed as {scheme}://{host}:{port}")
     if drive:
         tun = Tunnel(upstreams, transport=a.transport, env=log_env, serve_extra=mtu_flags + pin_s,
                      proxy_extra=mtu_flags + pin_p)
@@ -219,9 +262,15 @@ def main():
     # 0.2-0.34 ms for the others on the MI355X host — set the p99.)
     from p2p_llm_tunnel_amd import binary
     lg = None
+    raw_dump = None
     if drive:
+        dump = []
+        if a.dump_outputs:
+            os.makedirs(a.dump_outputs, exist_ok=True)
+            raw_dump = os.path.join(a.dump_outputs, f".last_step_rank{rank}.raw")
+            dump = ["--dump-last", raw_dump]
         lg = subprocess.Popen(taskset("loadgen") + [binary("tunnel-loadgen"), "--target", f"127.0.0.1:{tun.proxy_port}", "--streams",
-                               str(streams), "--steps", str(a.steps), "--warmup", str(max(1, a.warmup)), "--hold", "1"],
+                               str(streams), "--steps", str(a.steps), "--warmup", str(max(1, a.warmup)), "--hold", "1"] + dump,
                               stdin=subprocess.PIPE, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
         ready = lg.stdout.readline()
         if ready.strip() != "READY":
@@ -250,11 +299,13 @@ def main():
     from p2p_llm_tunnel_amd.utils.pinning import where
     placement = {"serve": where(tun.serve.popen.pid), "proxy": where(tun.proxy.popen.pid),
                  "mock": where(mock.popen.pid)} if tun else None
+    if raw_dump:
+        dump_outputs(raw_dump, a.dump_outputs, rank)
 
-    # ---- untimed: curve points + direct baseline (the same load straight to
+    # ---- untimed, --full only: curve points + direct baseline (the same load straight to
     # the upstream; node topology: S x N streams split evenly over the N upstreams)
     curve = {}
-    for s in sorted({int(x) for x in a.curve.split(",") if x} | {a.streams}) if drive else []:
+    for s in sorted({int(x) for x in a.curve.split(",") if x} | {a.streams}) if drive and a.full else []:
         n = s * (world if node else 1)
         c_steps = a.curve_steps or a.steps
         c_warm = max(1, a.warmup if a.curve_steps is None else 1)
@@ -281,7 +332,7 @@ def main():
         tun.stop()
     # Untimed extra: the same headline load on the same-host jumbo path.
     jumbo = None
-    if drive and a.mtu == "std" and a.transport == "webrtc" and not a.no_jumbo_extra:
+    if drive and a.full and a.mtu == "std" and a.transport == "webrtc" and not a.no_jumbo_extra:
         with Tunnel(upstreams, transport=a.transport, env=log_env, serve_extra=pin_s, proxy_extra=pin_p) as tj:
             loadgen(tj.proxy_port, streams, max(1, a.warmup))
             r = loadgen(tj.proxy_port, streams, a.steps)
@@ -299,9 +350,9 @@ def main():
     requests = head["requests"]
     errors = head["errors"]
     dt = dt_wall
-    added = curve[str(a.streams)]["added_p50_ttft_ms"] if drive else 0.0
+    added = curve[str(a.streams)]["added_p50_ttft_ms"] if drive and a.full else 0.0
     added_p99 = (curve[str(a.streams)]["tunneled_p99_ttft_ms"] - curve[str(a.streams)]["direct_p99_ttft_ms"]
-                 if drive else 0.0)
+                 if drive and a.full else 0.0)
     if dist:
         import torch
         t = torch.tensor([dt, added, added_p99], dtype=torch.float64)
@@ -310,6 +361,8 @@ def main():
         r = torch.tensor([requests, errors], dtype=torch.float64)
         dist.all_reduce(r, op=dist.ReduceOp.SUM)
         requests, errors = int(r[0].item()), int(r[1].item())
+    if not a.full:  # no direct leg was run
+        added = added_p99 = None
 
     if rank == 0:
         from p2p_llm_tunnel_amd.utils.boxinfo import identity
@@ -321,6 +374,9 @@ def main():
             "n_gpus": world,
             "steps": a.steps,
             "warmup": a.warmup,
+            "full": a.full,
+            "native_core": {"module": os.path.basename(core.__file__),
+                            "protocol": f"{core.PROTOCOL_NAME}/{core.PROTOCOL_VERSION}"},
             "ms_per_step": dt * 1e3 / a.steps,
             "higher_is_better": True,
             "scaling": "weak",

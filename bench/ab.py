@@ -19,7 +19,7 @@ KIND and what one run is:
          of 1 ms tokens. Key: added p50 TTFT, tunneled / direct p99 TTFT.
   mixed  bench/bench_mixed.py --reps 1: SSE next to 8 x 64 MB downloads.
          Key: SSE TTFT p99 per transport, bulk ratio, proxy RSS.
-  head   bench.py: the headline (8 streams). Key: added p50 / p99 TTFT.
+  head   bench.py --full: the headline (8 streams). Key: added p50 / p99 TTFT.
 
 A variant is "label:VAR=v,VAR2=w" ("label:" for the environment as is). A
 run that fails or times out ends the whole A/B (exit status 1): nothing is
@@ -74,7 +74,7 @@ def command(kind: str, path: str, out_file: str, a, extra: list[str]) -> tuple[l
     if kind == "mixed":
         return [py, "bench/bench_mixed.py", "--reps", "1", "--out", out_file] + extra, False
     if kind == "head":
-        return [py, "bench.py", "--out", out_file] + extra, False
+        return [py, "bench.py", "--full", "--out", out_file] + extra, False
     raise SystemExit(f"unknown kind {kind}")
 
 

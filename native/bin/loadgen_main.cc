@@ -58,6 +58,10 @@ struct Opts {
   char event_sep = 0;     // 0: auto from content-type (SSE "\n\n", NDJSON "\n"); 'n' none
   uint64_t read_rate = 0; // >0: read at most this many body bytes/s per stream (slow client)
   uint64_t duration_us = 0;  // >0: repeat timed steps for this long (--duration-s)
+  // --dump-last FILE: keep the decoded body of each stream's latest response
+  // and write those of the last step to FILE when the run ends (u32 stream
+  // count, then u32 length + bytes per stream, little endian, stream order).
+  std::string dump_last;
 };
 
 struct Result {
@@ -69,6 +73,7 @@ struct Result {
   std::vector<double> step_ttft_max_us;  // per step: the slowest first byte (thread 0)
   size_t step_base = 0;                  // ttft_us entries before the current step
   uint64_t t_start = 0, t_end = 0;
+  std::vector<std::string> last_bodies;  // --dump-last: one per stream of the thread
 };
 
 // LOADGEN_TRACE=path: step boundaries of thread 0 as JSON lines in the
@@ -100,6 +105,7 @@ class Stream : public std::enable_shared_from_this<Stream> {
   Stream(Reactor& r, const Opts& o, const Target& t, Result* res) : r_(r), o_(o), t_(t), res_(res) {}
   std::function<void()> on_done;  // one request finished
   void set_result(Result* r) { res_ = r; }
+  const std::string& last_body() const { return last_body_; }
 
   void request() {
     if (!conn_ || conn_->closed()) {
@@ -152,6 +158,7 @@ class Stream : public std::enable_shared_from_this<Stream> {
     last_ev_ = 0;
     sep_run_ = 0;
     active_ = true;
+    if (capture_) last_body_.clear();
     t0_ = Reactor::now_us();
     conn_->write(std::move(req));
     if (!body.empty()) conn_->write(body);
@@ -183,6 +190,7 @@ class Stream : public std::enable_shared_from_this<Stream> {
         if (!first_ && k) first_ = now;
         res_->body_bytes += k;
         got_ += k;
+        if (capture_) last_body_.append(reinterpret_cast<const char*>(d), k);
         scan_events(d, k, now);
       });
       if (used == SIZE_MAX) {
@@ -226,6 +234,7 @@ class Stream : public std::enable_shared_from_this<Stream> {
       if (!first_ && k) first_ = now;
       res_->body_bytes += k;
       got_ += k;
+      if (capture_) last_body_.append(reinterpret_cast<const char*>(d), k);
       scan_events(d, k, now);
     });
     if (used == SIZE_MAX) {
@@ -314,6 +323,8 @@ class Stream : public std::enable_shared_from_this<Stream> {
   uint64_t t0_ = 0, first_ = 0, last_ev_ = 0, got_ = 0;
   char sep_ = 0;
   int sep_run_ = 0;
+  const bool capture_ = !o_.dump_last.empty();
+  std::string last_body_;
 };
 
 // One reactor thread driving streams [first, first + count).
@@ -381,6 +392,8 @@ void run_thread(const Opts& o, int first, int count, Result& res, Result& warm_r
   if (count == 0) return;
   launch();
   r.run();
+  if (!o.dump_last.empty())
+    for (auto& s : live) res.last_bodies.push_back(s->last_body());
 }
 
 double pct(std::vector<double>& v, double q) {
@@ -429,6 +442,7 @@ int main(int argc, char** argv) {
     else if (a == "--events") o.event_sep = v == "sse" ? 's' : v == "ndjson" ? 'l' : v == "none" ? 'n' : 0;
     else if (a == "--read-rate") o.read_rate = strtoull(v.c_str(), nullptr, 10);
     else if (a == "--duration-s") o.duration_us = uint64_t(atof(v.c_str()) * 1e6);
+    else if (a == "--dump-last") o.dump_last = v;
   }
   signal(SIGPIPE, SIG_IGN);
   int T = std::min(o.threads, std::max(1, o.streams));
@@ -455,6 +469,26 @@ int main(int argc, char** argv) {
     all.t_end = std::max(all.t_end, r.t_end);
   }
   if (all.t_start == UINT64_MAX) all.t_start = all.t_end;
+  if (!o.dump_last.empty()) {
+    FILE* f = fopen(o.dump_last.c_str(), "wb");
+    if (!f) {
+      fprintf(stderr, "loadgen: cannot write %s\n", o.dump_last.c_str());
+      return 2;
+    }
+    auto put32 = [f](size_t v) {
+      uint8_t b[4] = {uint8_t(v), uint8_t(v >> 8), uint8_t(v >> 16), uint8_t(v >> 24)};
+      fwrite(b, 1, 4, f);
+    };
+    size_t n = 0;
+    for (auto& r : res) n += r.last_bodies.size();
+    put32(n);
+    for (auto& r : res)
+      for (auto& b : r.last_bodies) {
+        put32(b.size());
+        fwrite(b.data(), 1, b.size(), f);
+      }
+    fclose(f);
+  }
   double secs = double(all.t_end - all.t_start) / 1e6;
   // Per-step durations (thread 0's steps; every thread runs the same count).
   std::string steps_ms, step_ttft;
