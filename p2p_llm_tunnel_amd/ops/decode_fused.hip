@@ -43,7 +43,6 @@
 #include "bf16_common.h"
 
 #include <algorithm>
-#include <cstdlib>
 
 namespace {
 
@@ -79,29 +78,20 @@ struct GemmArgs {
   float log2_theta;
   float* am_val;  // ARGMAX: [gridDim.x][16]
   int* am_idx;
-  // Split-K over workgroups (ks > 1): the ks workgroups of a column tile each
-  // reduce a K range, publish a 16 x 16*TN fp32 slab write-through, and the
-  // last to arrive sums the slabs in fixed order (deterministic) and runs the
-  // epilogue. Small-N projections (N = d_model) otherwise leave CUs idle.
-  int ks;
-  float* kpart;     // [tiles][ks][TN][4][64]
-  unsigned* kctr;   // [tiles] arrival tickets (self-resetting)
-  // Column-tile width 2^cwl (16, 8 or 4 output columns per 16-lane MFMA
-  // subtile). Narrower tiles put a small-N projection on more workgroups, so
-  // its weight stream spreads over every CU (one CU streams ~10 B/cycle, a
-  // 2048-wide projection in 16-column tiles reached only 128 of the 256 CUs).
-  // Lanes c and c + 2^cwl load the same weight row in the same instruction
-  // (one fetch); their duplicate MFMA columns are dropped in the epilogue.
-  int cwl;
-  // K parts (kpl = log2 P, 0: off; P = 16 >> cwl, TN = 1, M * P <= 16): lanes
-  // past the tile width take the other K parts of the same columns instead of
-  // repeating them, and MFMA rows m * P + p carry activation row m's K part p,
-  // so every lane streams unique weight bytes. The diagonal blocks of the
-  // 16 x 16 accumulator are summed in the epilogue. With spare MFMA rows (a
-  // decode step of <= 16 / P tokens) a 2048-wide projection then spreads
-  // over every CU without the duplicate fetches of narrow tiles.
+  // K parts (kpl = log2 P, 0: off; TN = 1, M * P <= 16). A subtile then holds
+  // 16 / P output columns instead of 16, so a small-N projection lands on P
+  // times the workgroups and its weight stream spreads over every CU (one CU
+  // streams ~10 B/cycle; a 2048-wide projection in 16-column tiles reaches
+  // only 128 of the 256 CUs). Lanes past the tile width take the other K
+  // parts of the same columns, and MFMA rows m * P + p carry activation row
+  // m's K part p, so every lane streams unique weight bytes. The diagonal
+  // blocks of the 16 x 16 accumulator are summed in the epilogue. It needs
+  // spare MFMA rows: a decode step of <= 16 / P tokens.
   int kpl;
 };
+
+// log2 of the output columns per 16-lane subtile: 16, 8 or 4 for 1, 2 or 4 K parts.
+__host__ __device__ __forceinline__ int tile_cwl(int kpl) { return 4 - kpl; }
 
 __device__ __forceinline__ frag8 as_frag(const uint4& v) { return __builtin_bit_cast(frag8, v); }
 
@@ -110,12 +100,6 @@ typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float dot2_bf16(uint32_t a, uint32_t b, float c) {
   return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, a), __builtin_bit_cast(bf16x2_t, b), c, false);
 }
-
-// Weights use the default cache policy on purpose: a decode step replays the
-// same weights back to back, and models up to the 256 MB MALL keep them
-// resident between steps (non-temporal loads measured 1.75x slower on the
-// 4-layer config in round 1; with buffer loads, nt (aux 2) on the weights was
-// 5 % slower on the 0.85 GB config too: profiles/r02/decode/decode_sweep_s9.log).
 
 // Cross-workgroup hand-off without L2 write-back/invalidate fences: payload
 // stores are agent-scope relaxed atomics (write-through, `sc1`), drained with
@@ -137,7 +121,7 @@ __device__ __forceinline__ unsigned arrive(unsigned* ctr) {
 }
 
 // Output column of lane column c (0..15) in subtile t of block bx, for
-// subtiles of 2^cwl distinct columns (lanes past 2^cwl repeat them).
+// subtiles of 2^cwl columns (lanes past 2^cwl: the same columns' other K parts).
 template <int TN>
 __device__ __forceinline__ int tile_col(int bx, int t, int c, int cwl) {
   return ((bx * TN + t) << cwl) + (c & ((1 << cwl) - 1));
@@ -188,13 +172,7 @@ __device__ __forceinline__ void mma_apply(frag4 (&acc)[TN], const Batch<UM, TN>&
       acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(bt.a[u]), as_frag(bt.b[u][t]), acc[t], 0, 0, 0);
 }
 
-// The wave's k-steps [s0, s1), one batch at a time. Measured slower on
-// MI355X and dropped (profiles/r02/decode/decode_sweep_s6..s8.log): a
-// two-deep batch pipeline (every projection +0.5-1.8 us, LM head +0.5-2.4),
-// 16 waves on the K = 5632 down projection (9.4 -> 10.5 us), and one
-// workgroup per CU forced through padded LDS with 8-column tiles (down
-// unchanged at 9.4 us, QKV 5.9 -> 9.9): the down projection is not bound by
-// per-CU bandwidth or by its serial batches.
+// The wave's k-steps [s0, s1), one batch at a time.
 template <int UM, int TN>
 __device__ __forceinline__ void mma_stream(frag4 (&acc)[TN], __amdgpu_buffer_rsrc_t ra, uint32_t xoff,
                                            __amdgpu_buffer_rsrc_t rw, const uint32_t (&woff)[TN], int s0, int s1) {
@@ -211,22 +189,19 @@ __device__ __forceinline__ void mma_stream(frag4 (&acc)[TN], __amdgpu_buffer_rsr
 // Skinny GEMM + fused epilogue. NW waves split K; TN subtiles of 2^cwl
 // columns per block; UM k-steps per load batch (host: >= each wave's share
 // when possible). Steps of more than 16 rows put each 16-row tile on its own
-// workgroup (blockIdx.y). Sharing each weight fragment across the four tiles
-// of a 64-row step in one workgroup was measured slower (small config, 64
-// rows: 1.19 -> 1.26 ms; 1.1B-shaped checkpoint served at 16 streams 3.0 K ->
-// 2.7 K tok/s, profiles/r02/decode/decode_sweep_s10_rowtiles.log): the extra
-// tiles' weight reads hit the MALL, and a quarter of the workgroups each
-// issuing five times the loads leaves the load path, not HBM, as the limit. ROPE and SILU take weights whose rows are interleaved in
-// pairs (RoPE partners d, d + D/2 of a head; gate_j, up_j), so a pair sits in
-// lanes c, c^1.
+// workgroup (blockIdx.y). ROPE and SILU take weights whose rows are
+// interleaved in pairs (RoPE partners d, d + D/2 of a head; gate_j, up_j), so
+// a pair sits in lanes c, c^1.
 template <int NW, int TN, int EPI, int UM>
 __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
   __shared__ float red[NW][TN][4][kWave];
   __shared__ float red_ss[NW][kWave];
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int m0 = blockIdx.y << 4;    // first row of this workgroup's 16-row tile
-  const int bx = blockIdx.x / a.ks;  // column tile
-  const int kslice = blockIdx.x % a.ks;
+  // The wave index is uniform: held in an SGPR, the k-step bounds and loop
+  // counter derived from it stay out of the VGPR budget.
+  const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int m0 = blockIdx.y << 4;  // first row of this workgroup's 16-row tile
+  const int bx = blockIdx.x;       // column tile
+  const int cwl = tile_cwl(a.kpl);
   const bool norm = a.ss_part != nullptr;
 
   // Row sums of squares for the folded RMSNorm, spread over every wave (lane:
@@ -252,23 +227,22 @@ __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
   const bool a_ok = m0 + m_a < a.M;
   const int kq = (lane >> 4) << 3;
   const int S = Kp >> 5;
-  const int b0 = kslice * S / a.ks, bs = (kslice + 1) * S / a.ks - b0;  // this workgroup's k-steps
-  const int s0 = b0 + wv * bs / NW, s1 = b0 + (wv + 1) * bs / NW;
+  const int s0 = wv * S / NW, s1 = (wv + 1) * S / NW;
   // Byte offsets of this lane's A row and weight rows at k-step 0; rows past
   // M read as zeros (kOob).
   const __amdgpu_buffer_rsrc_t ra = rsrc(a.x, uint32_t(a.M) * uint32_t(a.K) * 2u);
   const __amdgpu_buffer_rsrc_t rw = rsrc(a.w, uint32_t(a.N) * uint32_t(a.K) * 2u);
   const uint32_t xoff = a_ok ? (uint32_t(m0 + m_a) * uint32_t(a.K) + uint32_t(p_a * Kp + kq)) * 2u : kOob;
-  const int p_b = a.kpl ? (lane & 15) >> a.cwl : 0;  // K part of this lane's weight column
+  const int p_b = (lane & 15) >> cwl;  // K part of this lane's weight column
   uint32_t woff[TN];
 #pragma unroll
   for (int t = 0; t < TN; t++)
-    woff[t] = (uint32_t(tile_col<TN>(bx, t, lane & 15, a.cwl)) * uint32_t(a.K) + uint32_t(p_b * Kp + kq)) * 2u;
+    woff[t] = (uint32_t(tile_col<TN>(bx, t, lane & 15, cwl)) * uint32_t(a.K) + uint32_t(p_b * Kp + kq)) * 2u;
 
   // C layout: row m = m0 + 4*(lane>>4) + r, column = tile_col(.., lane & 15).
   const int lrow0 = (lane >> 4) << 2, mrow0 = m0 + lrow0;
   const int c = lane & 15;
-  const bool col_ok = c < (1 << a.cwl);  // lanes past the tile width repeat its columns
+  const bool col_ok = c < (1 << cwl);  // lanes past the tile width carry the other K parts
 
   // RESID: the residual values this lane's epilogue updates, loaded by wave 0
   // ahead of the weight stream (they do not depend on it) instead of after
@@ -281,7 +255,7 @@ __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; r++) {
           const int m = min(mrow0 + r, a.M - 1);
-          rprev[t][r] = bf2f(a.out[size_t(m) * a.N + tile_col<TN>(bx, t, c, a.cwl)]);
+          rprev[t][r] = bf2f(a.out[size_t(m) * a.N + tile_col<TN>(bx, t, c, cwl)]);
         }
     }
   }
@@ -315,27 +289,6 @@ __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
       for (int w = 0; w < NW; w++) sum += red[w][t][r][lane];
       v[t][r] = sum;
     }
-  if (a.ks > 1) {
-    float* slab = a.kpart + size_t(bx) * a.ks * (TN * 4 * kWave);
-#pragma unroll
-    for (int t = 0; t < TN; t++)
-#pragma unroll
-      for (int r = 0; r < 4; r++) st_wt(slab + size_t(kslice) * (TN * 4 * kWave) + (t * 4 + r) * kWave + lane, v[t][r]);
-    drain_stores();
-    unsigned tk = 0;
-    if (lane == 0) tk = arrive(&a.kctr[bx]);
-    tk = __shfl(tk, 0, kWave);
-    if (tk != unsigned(a.ks - 1)) return;
-#pragma unroll
-    for (int t = 0; t < TN; t++)
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        float sum = 0.f;
-        for (int j = 0; j < a.ks; j++) sum += ld_wt(slab + size_t(j) * (TN * 4 * kWave) + (t * 4 + r) * kWave + lane);
-        v[t][r] = sum;
-      }
-    if (lane == 0) st_wt(&a.kctr[bx], 0u);
-  }
 
   if (a.kpl) {
     // Sum the diagonal blocks: output (row m, column c < 2^cwl) is
@@ -352,7 +305,7 @@ __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
       const int row = lrow0 + r;
       float sum = 0.f;
       if (row < (16 >> a.kpl) && col_ok)
-        for (int p = 0; p < kparts; p++) sum += cbuf[(row * kparts + p) * 17 + c + (p << a.cwl)];
+        for (int p = 0; p < kparts; p++) sum += cbuf[(row * kparts + p) * 17 + c + (p << cwl)];
       v[0][r] = sum;
     }
   }
@@ -382,7 +335,7 @@ __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
     }
 #pragma unroll
     for (int t = 0; t < TN; t++) {
-      const int n = tile_col<TN>(bx, t, c, a.cwl);
+      const int n = tile_col<TN>(bx, t, c, cwl);
 #pragma unroll
       for (int r = 0; r < 4; r++) {
         const int m = mrow0 + r;
@@ -406,7 +359,7 @@ __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
     }
   } else if constexpr (EPI == EPI_SILU) {
     // Interleaved rows: even lane = gate_j, odd lane = up_j, j = column / 2.
-    const int n = tile_col<TN>(bx, 0, c, a.cwl);
+    const int n = tile_col<TN>(bx, 0, c, cwl);
 #pragma unroll
     for (int r = 0; r < 4; r++) {
       const float mine = bf_round(v[0][r]);
@@ -417,7 +370,7 @@ __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
   } else if constexpr (EPI == EPI_ROPE) {
     // Interleaved rows within each head: column 2i = dim i, 2i+1 = dim i + D/2.
     const int half = a.D >> 1;
-    const int col = tile_col<TN>(bx, 0, c, a.cwl);
+    const int col = tile_col<TN>(bx, 0, c, cwl);
     const int head = col / a.D, i = (col % a.D) >> 1;
     const bool second = c & 1;
     const float inv_freq = exp2f(-a.log2_theta * (2.f * i) / a.D);
@@ -447,7 +400,7 @@ __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
     float sq[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int t = 0; t < TN; t++) {
-      const int n = tile_col<TN>(bx, t, c, a.cwl);
+      const int n = tile_col<TN>(bx, t, c, cwl);
 #pragma unroll
       for (int r = 0; r < 4; r++) {
         const int m = mrow0 + r;
@@ -537,7 +490,7 @@ __global__ __launch_bounds__(256) void k_embed(const uint16_t* __restrict__ embe
 // workgroups: graph-captured steps launch the same grid whatever the context
 // length, so the grid is sized by the batch (about one round of workgroups on
 // the chip), not by the cache capacity — idle workgroups were a third of the
-// kernel at 1k tokens. Each slot covers a span of >= 256 tokens of row b; its
+// kernel at 1k tokens. Each slot covers a span of >= 64 tokens of row b; its
 // 8 waves walk the span in 32-token pieces with an online softmax.
 // A piece is loaded straight into registers with 16-byte loads whose lanes
 // tile whole K/V rows (D/8 lanes per row: every instruction reads full cache
@@ -553,14 +506,25 @@ __global__ __launch_bounds__(256) void k_embed(const uint16_t* __restrict__ embe
 // to finish merges, its waves taking different heads.
 // Row b reads cache slot slot[b] (rows may share a slot: chunked prefill) and
 // attends to positions 0..pos[b]; the output is bf16 [B][H*D].
-template <int D, int G, int TOK = 32>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(TOK == 16 ? 4 : 1))) void k_attn(const uint16_t* __restrict__ q, const uint16_t* __restrict__ kc,
-                                              const uint16_t* __restrict__ vc, const int* __restrict__ pos,
-                                              const int* __restrict__ slot, int nslots, float* __restrict__ part_o,
-                                              float* __restrict__ part_ml, unsigned* __restrict__ counters,
-                                              uint16_t* __restrict__ out, int H, int Hkv, int Smax, int nsplit,
-                                              float scale, int min_span) {
+constexpr int kAttnSlotCap = 16;  // span slots per (row, KV head) at most
+// Workgroups one launch aims at: one 512-thread, 234-VGPR workgroup per CU.
+// More slots per row are slower: b16 0.522 / 0.567 / 0.597 / 0.645 ms at
+// 256 / 512 / 768 / 1024 (profiles/r03/decode/attn_grid_sweep_head.log).
+constexpr int kAttnTargetWgs = 256;
+// Smallest token span of one workgroup (a multiple of the 32-token wave
+// piece). 64 (two busy waves) puts a short context on 4x the workgroups of
+// 256 (one piece per wave): at batch 1 and 1k tokens the decode step went
+// 396 -> 380 us on MI355X, unchanged at batch 16.
+constexpr int kAttnMinSpan = 64;
+
+template <int D, int G>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1))) void k_attn(
+    const uint16_t* __restrict__ q, const uint16_t* __restrict__ kc, const uint16_t* __restrict__ vc,
+    const int* __restrict__ pos, const int* __restrict__ slot, int nslots, float* __restrict__ part_o,
+    float* __restrict__ part_ml, unsigned* __restrict__ counters, uint16_t* __restrict__ out, int H, int Hkv, int Smax,
+    int nsplit, float scale) {
   constexpr int NWV = 8;
+  constexpr int TOK = 32;  // tokens per wave piece
   constexpr int DPL = D / kWave;  // merges: dims per lane
   constexpr int MAXC = 16;        // partials merged per load batch
   constexpr int LPR = D / 8, RPI = kWave / LPR, NI = TOK / RPI;
@@ -571,7 +535,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(TOK == 16 ?
   const int b = blockIdx.y / Hkv, kvh = blockIdx.y % Hkv;
   const int len = min(max(pos[b], 0), Smax - 1) + 1;
   int span = (len + gridDim.x - 1) / gridDim.x;
-  span = max(min_span, (span + TOK - 1) / TOK * TOK);
+  span = max(kAttnMinSpan, (span + TOK - 1) / TOK * TOK);
   const int nact = (len + span - 1) / span;  // slots with tokens
   const int sl = blockIdx.x;
   if (sl >= nact) return;
@@ -772,42 +736,48 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(TOK == 16 ?
   if (threadIdx.x == 0) st_wt(&counters[blockIdx.y], 0u);
 }
 
-int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return (e && *e) ? atoi(e) : dflt;
-}
-
 // Span slots per (row, KV head): about one round of workgroups on the chip,
 // at most the workspace's partial slots.
 int attn_slots(int B, int Hkv, int nsplit_ws) {
-  static const int cap = env_int("P2PT_ATTN_SLOTS", 16);
-  // Target workgroups of the launch: 256 (one 512-thread, 234-VGPR workgroup
-  // per CU). More slots per row are slower: b16 0.522 / 0.567 / 0.597 /
-  // 0.645 ms at 256 / 512 / 768 / 1024 (profiles/r03/decode/attn_grid_sweep_head.log).
-  static const int wgs = std::max(1, env_int("P2PT_ATTN_WGS", 256));
-  int sl = wgs / std::max(1, B * Hkv);
-  return std::max(1, std::min({sl, cap, nsplit_ws}));
+  const int sl = kAttnTargetWgs / std::max(1, B * Hkv);
+  return std::max(1, std::min({sl, kAttnSlotCap, nsplit_ws}));
 }
 
-// Smallest token span of one attention workgroup (a multiple of its 32-token
-// wave piece). 64 (two busy waves per workgroup) puts a short context on 4x
-// the workgroups of 256 (one piece per wave): at batch 1 and 1k tokens the
-// decode step went 396 -> 380 us on MI355X, unchanged at batch 16
-// (profiles/r02/decode/decode_sweep_s4.log). P2PT_ATTN_MINSPAN overrides.
-// Tokens per wave piece: 32, or 16 (half the K/V registers: 128 instead of
-// 234 VGPRs, so two 8-wave workgroups fit a CU). Occupancy is not what bounds
-// the kernel: 16 measured slower at every batch on MI355X (small, ctx 1024:
-// b1 0.358 -> 0.365 ms, b16 0.522 -> 0.531, b64 1.125 -> 1.134;
-// profiles/r03/decode/attn_tok_ab_head.log). P2PT_ATTN_TOK=16 opts in.
-int attn_tok() {
-  static const int v = env_int("P2PT_ATTN_TOK", 32) == 16 ? 16 : 32;
-  return v;
-}
-
-int attn_min_span() {
-  static const int v = std::max(32, env_int("P2PT_ATTN_MINSPAN", 64) / 32 * 32);
-  return v;
-}
+// Measured on MI355X and rejected; the code is gone, the findings stay. This
+// file reads no environment variables: what ships is the one path below.
+//  - Split-K over workgroups (write-through slabs, arrival ticket, last
+//    arriver combines): the seam costs more than the extra workgroups win at
+//    d_model <= 2048. QKV 8.7 -> 13.5 us, O 7.4 -> 12.0, down 17.3 -> 17.3
+//    (2048-wide config, batch 8).
+//  - Narrow duplicate-column tiles (8 or 4 columns, the other lanes repeating
+//    them): O alone 5.8 -> 5.5 us at batch 1, QKV 6.1 -> 7.8; O and down at
+//    one workgroup per CU 1-4 % slower end to end. 16 everywhere is fastest.
+//  - K parts on QKV and gate/up: batch 1, QKV at 4 columns 0.360 -> 0.373 ms
+//    per step, gate/up 0.368 (8 columns) and 0.391 (4). Their grids already
+//    cover the chip. K parts stay on O and down only (0.372 -> 0.359 ms).
+//  - A 16-token attention piece (128 instead of 234 VGPRs, two workgroups per
+//    CU): small, ctx 1024, b1 0.358 -> 0.365 ms, b16 0.522 -> 0.531, b64
+//    1.125 -> 1.134 (profiles/r03/decode/attn_tok_ab_head.log).
+//  - 8-step load batches: at most 4 k-steps per batch keeps more waves
+//    resident. Batch 1 396 -> 389 us per step, batch 16 unchanged.
+//  - 16-wave workgroups: 8 beats 16 by 20-30 % at K = 5632 (down 9.4 ->
+//    10.5 us); the reduction and barrier cost more than the loads in flight.
+//  - Non-temporal weight loads: 1.75x slower on the 4-layer config, 5 % slower
+//    on the 0.85 GB config (profiles/r02/decode/decode_sweep_s9.log). A decode
+//    step replays the same weights, and the 256 MB MALL keeps them resident.
+//  - One workgroup sharing each weight fragment across the four tiles of a
+//    64-row step: small, 64 rows 1.19 -> 1.26 ms; 16 streams 3.0 K -> 2.7 K
+//    tok/s (profiles/r02/decode/decode_sweep_s10_rowtiles.log). The load
+//    path, not HBM, becomes the limit.
+//  - The argmax merge folded into the LM head's last block: 0.359 -> 0.366 ms
+//    at batch 1, 0.522 -> 0.554 at 16. 1,000 arrivals on one counter cost more
+//    than the launch.
+//  - A persistent O -> gate/up -> down kernel (in-order tile queue,
+//    write-through hand-offs): small b1 0.358 -> 0.61-1.09 ms in every variant
+//    (profiles/r03/decode_block/).
+//  - A two-deep load-batch pipeline (every projection +0.5-1.8 us) and one
+//    workgroup per CU forced through padded LDS (QKV 5.9 -> 9.9 us)
+//    (profiles/r02/decode/decode_sweep_s8.log).
 
 // ------------------------------------------------------------ host side
 struct LlamaDims {
@@ -817,11 +787,6 @@ struct LlamaDims {
 
 constexpr int kChunk = 64;  // tokens per attention workgroup = workspace granularity of its partials
 constexpr int kTnResid = 1, kTnStore = 2;  // LM head: two 16-column subtiles per block
-constexpr int kMaxKs = 8;    // split-K ways over workgroups
-// O / down projections: 16-column tiles too. Narrowing them to one workgroup
-// per CU (256) measured 1-4 % slower end to end once operands went through
-// buffer loads (profiles/r02/decode/decode_sweep_*.log, "min256" vs "cw16").
-constexpr int kResidMinTiles = 0;
 constexpr int kCUs = 256;  // MI355X compute units: K-parts tiling aims at one workgroup per CU
 
 size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
@@ -831,8 +796,6 @@ struct Workspace {
   float *ss, *part_o, *part_ml, *am_val;
   int* am_idx;
   unsigned* counters;  // [kMaxM * H] attention split tickets (self-resetting)
-  float* kpart;        // split-K slabs of the widest split GEMM
-  unsigned* kctr;      // split-K tickets per column tile (self-resetting)
   size_t bytes;
 };
 
@@ -857,126 +820,51 @@ Workspace carve(const LlamaDims& d, uint8_t* base) {
   w.am_val = reinterpret_cast<float*>(take(size_t(am_parts) * kMaxM * 4));
   w.am_idx = reinterpret_cast<int*>(take(size_t(am_parts) * kMaxM * 4));
   w.counters = reinterpret_cast<unsigned*>(take(size_t(kMaxM * d.H) * 4));
-  const int qkv_n = (d.H + 2 * d.Hkv) * d.D;
-  const int max_n = std::max(std::max(qkv_n, d.dim), 2 * d.ffn);
-  w.kpart = reinterpret_cast<float*>(take(size_t(max_n / 16) * kMaxKs * 4 * kWave * 4));
-  w.kctr = reinterpret_cast<unsigned*>(take(size_t(max_n / 16) * 4));
   w.bytes = off;
   return w;
 }
 
 // Waves per workgroup for `steps` 32-wide k-steps per workgroup. Measured on
-// MI355X (scripts/bench_skinny.py, M = 8): 4 and 8 waves tie up to K = 2048,
-// 8 beats 16 by 20-30 % at K = 5632 (a 16-wave block's reduction and barrier
-// cost more than its extra loads in flight win back).
+// MI355X (scripts/bench_skinny.py, M = 8): 4 and 8 waves tie up to K = 2048.
 int pick_nw(int steps) {
   if (steps <= 0) return 0;
   return steps <= 16 ? 4 : 8;
 }
 
-// Split-K ways. Off by default: on MI355X the seam (write-through slabs,
-// drain, arrival ticket, slab reads by the last arriver) costs more latency
-// than the extra workgroups win back at d_model <= 2048 (QKV 8.7 -> 13.5 us,
-// O 7.4 -> 12.0 us, down 17.3 -> 17.3 us on the 2048-wide config, batch 8).
-// P2PT_DECODE_SPLITK=1 enables it (grid grown toward 512 workgroups while
-// every workgroup keeps >= 8 k-steps) for wider models / experiments.
-int pick_ks(int tiles, int K) {
-  static const bool on = [] {
-    const char* e = getenv("P2PT_DECODE_SPLITK");
-    return e && *e == '1';
-  }();
-  if (!on) return 1;
-  const int S = K >> 5;
-  int ks = 1;
-  while (ks < kMaxKs && tiles * ks < 512 && S / (ks * 2) >= 8) ks *= 2;
-  return ks;
-}
-
 template <int NW, int TN, int EPI>
 hipError_t launch_nw(const GemmArgs& a, int grid, hipStream_t s) {
   // Load batch: each wave's share of k-steps, rounded up to a power of two,
-  // capped by the VGPR budget (8, or 4 for 1024-thread two-subtile blocks).
-  // Batches of at most 4 k-steps: fewer registers, more resident waves (batch
-  // 1: 396 -> 389 us per step, batch 16 unchanged; P2PT_DECODE_UMCAP=8 restores
-  // 8-step batches).
-  static const int ucap = env_int("P2PT_DECODE_UMCAP", 4);
-  const int kCap = ((NW >= 16 && TN >= 2) || ucap <= 4) ? 4 : 8;
-  const int per_wave = (((a.K >> a.kpl) >> 5) / a.ks + NW - 1) / NW;
-  const dim3 g(grid * a.ks, (a.M + 15) >> 4), b(NW * 64);
+  // at most 4 (fewer registers, more resident waves).
+  const int per_wave = (((a.K >> a.kpl) >> 5) + NW - 1) / NW;
+  const dim3 g(grid, (a.M + 15) >> 4), b(NW * 64);
   if (per_wave <= 1)
     hipLaunchKernelGGL((k_skinny<NW, TN, EPI, 1>), g, b, 0, s, a);
   else if (per_wave <= 2)
     hipLaunchKernelGGL((k_skinny<NW, TN, EPI, 2>), g, b, 0, s, a);
-  else if (per_wave <= 4 || kCap == 4)
-    hipLaunchKernelGGL((k_skinny<NW, TN, EPI, 4>), g, b, 0, s, a);
   else
-    hipLaunchKernelGGL((k_skinny<NW, TN, EPI, 8>), g, b, 0, s, a);
+    hipLaunchKernelGGL((k_skinny<NW, TN, EPI, 4>), g, b, 0, s, a);
   return hipGetLastError();
 }
 
-// Column-tile width (log2) for an N-column projection with TN subtiles per
-// workgroup: the widest tile (16) that still gives >= min_tiles workgroups,
-// down to 4 columns (P2PT_DECODE_MIN_TILES overrides the threshold; 0: always
-// 16). Measured on MI355X (profiles/r02/decode/): narrower tiles win a
-// little on the O projection alone (5.8 -> 5.5 us at batch 1) and lose on QKV
-// (6.1 -> 7.8 us), where the repeated activation loads cost more than the
-// extra CUs win; 16 everywhere is fastest end to end.
-int pick_cwl(int N, int TN, int dflt_min_tiles) {
-  static const int env = env_int("P2PT_DECODE_MIN_TILES", -1);
-  const int min_tiles = env >= 0 ? env : dflt_min_tiles;
-  int cwl = 4;
-  while (cwl > 2 && (N >> cwl) / TN < min_tiles) cwl--;
-  return cwl;
+// K parts (GemmArgs::kpl) for an N-column, TN = 1 projection of M rows: the
+// widest tile (16, 8 or 4 columns) whose column tiles reach one workgroup per
+// CU, or 4 columns if none does; 0 where 16-column tiles already get there,
+// the spare MFMA rows do not allow it (M * P > 16) or K does not split into P
+// parts of whole k-steps. Used on the d_model-wide O and down projections.
+int pick_kparts(int N, int M, int K) {
+  if ((N >> 4) >= kCUs) return 0;
+  const int kpl = (N >> 3) >= kCUs ? 1 : 2;
+  const int P = 1 << kpl;
+  return (M * P <= 16 && K % (32 * P) == 0) ? kpl : 0;
 }
 
-// K-parts tiling (GemmArgs::kpl) for an N-column, TN = 1 projection of M rows:
-// the tile width 2^cwl whose N >> cwl column tiles first reach `min_tiles`
-// workgroups (one per CU), if the spare MFMA rows allow it (M * P <= 16,
-// P = 16 >> cwl) and K splits into P parts of whole k-steps; false otherwise.
-bool pick_kparts(int N, int M, int K, int min_tiles, int* cwl, int* kpl) {
-  for (int c = 4; c >= 2; c--) {
-    if ((N >> c) < min_tiles && c > 2) continue;
-    const int P = 16 >> c;
-    if (P == 1 || M * P > 16 || K % (P * 32)) return false;
-    *cwl = c;
-    *kpl = 4 - c;
-    return true;
-  }
-  return false;
-}
-
-// K parts for the 2048-wide O and down projections (one workgroup per CU):
-// small config, batch 1, 0.372 -> 0.359 ms per step (profiles/r03/decode/
-// decode_ab_kparts.log). On QKV (3072 columns: 384 workgroups of 8) it cost
-// 3-4 us per step, so that stays opt-in (P2PT_DECODE_QKV_KPARTS=1).
-// P2PT_DECODE_KPARTS=0 turns it off.
-// K parts at a given tile width (2^cwl columns, P = 16 >> cwl parts); false
-// where the rows or K do not allow it.
-bool kparts_at(int M, int K, int cwl, int* out_cwl, int* kpl) {
-  if (cwl < 2 || cwl > 3) return false;
-  const int P = 16 >> cwl;
-  if (M * P > 16 || K % (P * 32)) return false;
-  *out_cwl = cwl;
-  *kpl = 4 - cwl;
-  return true;
-}
-
-bool kparts_on() {
-  static const bool v = env_int("P2PT_DECODE_KPARTS", 1) != 0;
-  return v;
-}
-
-// grid = column tiles of the chosen width; the launch has grid * a.ks workgroups (a.ks == 0: pick).
+// One workgroup per TN subtiles of 16 >> a.kpl columns.
 template <int EPI, int TN>
-hipError_t launch_gemm(GemmArgs a, hipStream_t s, int nw_override = 0) {
-  if (a.cwl <= 0) a.cwl = pick_cwl(a.N, TN, 0);
-  if (a.kpl && (TN != 1 || a.M * (16 >> a.cwl) > 16 || (16 >> a.cwl) != (1 << a.kpl) || a.K % (32 << a.kpl)))
-    return hipErrorInvalidValue;
-  const int grid = a.N / (TN << a.cwl);
-  if (a.ks <= 0) a.ks = (a.kpart && a.kctr && a.cwl == 4) ? pick_ks(grid, a.K) : 1;
-  if (a.M > 16 || a.cwl != 4 || a.kpl) a.ks = 1;  // split-K slabs and tickets: one row tile of 16-column tiles only
-  const int nw = nw_override ? nw_override : pick_nw(((a.K >> a.kpl) >> 5) / a.ks);
-  if (nw == 16) return launch_nw<16, TN, EPI>(a, grid, s);
+hipError_t launch_gemm(const GemmArgs& a, hipStream_t s, int nw_override = 0) {
+  if (a.kpl < 0 || a.kpl > 2) return hipErrorInvalidValue;
+  if (a.kpl && (TN != 1 || (a.M << a.kpl) > 16 || a.K % (32 << a.kpl))) return hipErrorInvalidValue;
+  const int grid = a.N / (TN << tile_cwl(a.kpl));
+  const int nw = nw_override ? nw_override : pick_nw((a.K >> a.kpl) >> 5);
   if (nw == 8) return launch_nw<8, TN, EPI>(a, grid, s);
   if (nw == 4) return launch_nw<4, TN, EPI>(a, grid, s);
   return hipErrorInvalidValue;
@@ -1062,18 +950,6 @@ int p2pt_llama_decode(const LlamaDims* dp, const void* const* w, void* k_cache, 
     a.ss_part = W.ss; a.ss_parts = ss_parts;
     a.pos = pos; a.slot = slots; a.nslots = d.max_batch; a.q_out = W.q; a.kc = kc; a.vc = vc;
     a.H = d.H; a.Hkv = d.Hkv; a.D = d.D; a.Smax = d.max_seq; a.log2_theta = log2_theta;
-    a.kpart = W.kpart; a.kctr = W.kctr;
-    static const bool qkv_kparts = env_int("P2PT_DECODE_QKV_KPARTS", 0) != 0;
-    // Experiments: K parts at a given width. Slower than 16-column tiles on
-    // QKV (batch 1: 4 columns 0.360 -> 0.373 ms per step) and gate/up (8
-    // columns 0.368, 4 columns 0.391 ms): more, smaller workgroups do not
-    // stream faster once the grid already covers the chip
-    // (profiles/r03/decode/decode_ab_cwl.log).
-    static const int qkv_cwl = env_int("P2PT_DECODE_QKV_CWL", 0);
-    if (!(kparts_on() && ((qkv_cwl && kparts_at(B, d.dim, qkv_cwl, &a.cwl, &a.kpl)) ||
-                          (qkv_kparts && pick_kparts(qkv_n, B, d.dim, kCUs, &a.cwl, &a.kpl)))))
-      a.kpl = 0;
-    if (a.kpl == 0) a.cwl = 0;
     if ((e = launch_gemm<EPI_ROPE, 1>(a, s)) != hipSuccess) return int(e);
 
     // attention: (span slot, row, KV head) workgroups of 8 waves
@@ -1082,61 +958,38 @@ int p2pt_llama_decode(const LlamaDims* dp, const void* const* w, void* k_cache, 
       dim3 grid(attn_slots(B, d.Hkv, nsplit_ws), B * d.Hkv);
       const float scale = 1.f / sqrtf(float(d.D));
       const int G = d.H / d.Hkv;
-#define P2PT_ATTN(DD, GG)                                                                                          \
-  do {                                                                                                             \
-    if (attn_tok() == 16)                                                                                          \
-      hipLaunchKernelGGL((k_attn<DD, GG, 16>), grid, dim3(512), 0, s, W.q, kc, vc, pos, slots, d.max_batch,      \
-                         W.part_o, W.part_ml, W.counters, W.attn, d.H, d.Hkv, d.max_seq, nsplit_ws, scale,        \
-                         attn_min_span());                                                                         \
-    else                                                                                                           \
-      hipLaunchKernelGGL((k_attn<DD, GG>), grid, dim3(512), 0, s, W.q, kc, vc, pos, slots, d.max_batch, W.part_o, \
-                         W.part_ml, W.counters, W.attn, d.H, d.Hkv, d.max_seq, nsplit_ws, scale, attn_min_span());\
-  } while (0)
+#define LAUNCH_ATTN(DD, GG)                                                                                       \
+  hipLaunchKernelGGL((k_attn<DD, GG>), grid, dim3(512), 0, s, W.q, kc, vc, pos, slots, d.max_batch, W.part_o,   \
+                     W.part_ml, W.counters, W.attn, d.H, d.Hkv, d.max_seq, nsplit_ws, scale)
       if (d.D == 64) {
-        if (G == 1) P2PT_ATTN(64, 1); else if (G == 2) P2PT_ATTN(64, 2); else if (G == 4) P2PT_ATTN(64, 4); else P2PT_ATTN(64, 8);
+        if (G == 1) LAUNCH_ATTN(64, 1); else if (G == 2) LAUNCH_ATTN(64, 2); else if (G == 4) LAUNCH_ATTN(64, 4); else LAUNCH_ATTN(64, 8);
       } else {
-        if (G == 1) P2PT_ATTN(128, 1); else if (G == 2) P2PT_ATTN(128, 2); else if (G == 4) P2PT_ATTN(128, 4); else P2PT_ATTN(128, 8);
+        if (G == 1) LAUNCH_ATTN(128, 1); else if (G == 2) LAUNCH_ATTN(128, 2); else if (G == 4) LAUNCH_ATTN(128, 4); else LAUNCH_ATTN(128, 8);
       }
-#undef P2PT_ATTN
+#undef LAUNCH_ATTN
       if ((e = hipGetLastError()) != hipSuccess) return int(e);
     }
 
     // O projection + residual
     GemmArgs o{};
     o.M = B; o.x = W.attn; o.w = wo; o.N = d.dim; o.K = d.H * d.D;
-    o.out = W.resid; o.ss_out = W.ss; o.kpart = W.kpart; o.kctr = W.kctr;
-    if (!(kparts_on() && pick_kparts(d.dim, B, d.H * d.D, kCUs, &o.cwl, &o.kpl))) {
-      o.kpl = 0;
-      o.cwl = pick_cwl(d.dim, kTnResid, kResidMinTiles);
-    }
-    // Three launches: a persistent O -> gate/up -> down kernel (one launch, an
-    // in-order tile queue with write-through hand-offs) was built in round 3
-    // and measured slower in every variant (small b1 0.358 -> 0.61-1.09 ms,
-    // profiles/r03/decode_block/), then removed.
+    o.out = W.resid; o.ss_out = W.ss;
+    o.kpl = pick_kparts(d.dim, B, d.H * d.D);
     if ((e = launch_gemm<EPI_RESID, kTnResid>(o, s)) != hipSuccess) return int(e);
-    ss_parts = d.dim / (kTnResid << o.cwl);
+    ss_parts = d.dim >> tile_cwl(o.kpl);
 
     // gate/up + SwiGLU
     GemmArgs g{};
     g.M = B; g.eps = d.eps; g.x = W.resid; g.w = wgu; g.N = 2 * d.ffn; g.K = d.dim;
-    g.ss_part = W.ss; g.ss_parts = ss_parts; g.out = W.h; g.kpart = W.kpart; g.kctr = W.kctr;
-    static const int gu_cwl = env_int("P2PT_DECODE_GU_CWL", 0);  // experiments (see QKV above)
-    if (!(kparts_on() && gu_cwl && kparts_at(B, d.dim, gu_cwl, &g.cwl, &g.kpl))) {
-      g.kpl = 0;
-      g.cwl = 0;
-    }
+    g.ss_part = W.ss; g.ss_parts = ss_parts; g.out = W.h;
     if ((e = launch_gemm<EPI_SILU, 1>(g, s)) != hipSuccess) return int(e);
 
     // down + residual
     GemmArgs dn{};
     dn.M = B; dn.x = W.h; dn.w = wdown; dn.N = d.dim; dn.K = d.ffn; dn.out = W.resid; dn.ss_out = W.ss;
-    dn.kpart = W.kpart; dn.kctr = W.kctr;
-    if (!(kparts_on() && pick_kparts(d.dim, B, d.ffn, kCUs, &dn.cwl, &dn.kpl))) {
-      dn.kpl = 0;
-      dn.cwl = pick_cwl(d.dim, kTnResid, kResidMinTiles);
-    }
+    dn.kpl = pick_kparts(d.dim, B, d.ffn);
     if ((e = launch_gemm<EPI_RESID, kTnResid>(dn, s)) != hipSuccess) return int(e);
-    ss_parts = d.dim / (kTnResid << dn.cwl);
+    ss_parts = d.dim >> tile_cwl(dn.kpl);
   }
 
   // final norm + LM head + argmax
@@ -1145,13 +998,8 @@ int p2pt_llama_decode(const LlamaDims* dp, const void* const* w, void* k_cache, 
   h.ss_part = W.ss; h.ss_parts = ss_parts;
   h.out = static_cast<uint16_t*>(logits);
   h.am_val = W.am_val; h.am_idx = W.am_idx;
-  h.cwl = 4;  // the argmax partials are sized for 16-column tiles
   const int parts = d.vocab / (16 * kTnStore);
   // 4 waves x 2 subtiles: the fastest LM-head shape measured (vocab 32000, K 2048: 22.6 vs 29.6 us).
-  // The merge stays a launch of its own: folded into the LM head's last block
-  // (write-through partials + arrival ticket) the step took 0.359 -> 0.366 ms
-  // at batch 1 and 0.522 -> 0.554 ms at 16, the 1,000 blocks' arrivals on one
-  // counter costing more than the launch (profiles/r03/decode/decode_ab_kparts.log).
   if ((e = launch_gemm<EPI_ARGMAX, kTnStore>(h, s, 4)) != hipSuccess) return int(e);
   hipLaunchKernelGGL(k_argmax_merge, dim3(emit_rows), dim3(256), 0, s, W.am_val, W.am_idx, parts, ids);
   return int(hipGetLastError());
@@ -1164,7 +1012,7 @@ int p2pt_skinny_gemm(const void* x, const void* w, void* out, int M, int N, int 
   a.x = static_cast<const uint16_t*>(x);
   a.w = static_cast<const uint16_t*>(w);
   a.out = static_cast<uint16_t*>(out);
-  a.M = M; a.N = N; a.K = K; a.ks = 1; a.cwl = 4;
+  a.M = M; a.N = N; a.K = K;
   return int(launch_gemm<EPI_STORE, 2>(a, static_cast<hipStream_t>(stream)));
 }
 
@@ -1188,10 +1036,10 @@ int p2pt_attn_bench(const void* q, const void* kc, const void* vc, const int* po
     auto oo = static_cast<uint16_t*>(out);
     if (D == 64)
       hipLaunchKernelGGL((k_attn<64, 4>), grid, dim3(512), 0, st, qq, kk, vv, pos, nullptr, B, part_o, part_ml,
-                         counters, oo, H, Hkv, Smax, nsplit_ws, scale, attn_min_span());
+                         counters, oo, H, Hkv, Smax, nsplit_ws, scale);
     else
       hipLaunchKernelGGL((k_attn<128, 4>), grid, dim3(512), 0, st, qq, kk, vv, pos, nullptr, B, part_o, part_ml,
-                         counters, oo, H, Hkv, Smax, nsplit_ws, scale, attn_min_span());
+                         counters, oo, H, Hkv, Smax, nsplit_ws, scale);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return int(e);
   }
@@ -1199,25 +1047,25 @@ int p2pt_attn_bench(const void* q, const void* kc, const void* vc, const int* po
 }
 
 // Microbenchmark hook (scripts/bench_skinny.py): `reps` back-to-back launches
-// of the skinny GEMM with an explicit waves-per-block / subtile choice.
+// of the skinny GEMM with an explicit waves-per-block (4 or 8) / subtile
+// (1 or 2) choice.
 int p2pt_skinny_bench(const void* x, const void* w, void* out, int M, int N, int K, int nw, int tn, int reps,
                       void* stream) {
+  if ((nw != 4 && nw != 8) || (tn != 1 && tn != 2)) return int(hipErrorInvalidValue);
   if (M <= 0 || M > kMaxM || N % (16 * tn) || K <= 0 || K % 32 || reps <= 0) return int(hipErrorInvalidValue);
   GemmArgs a{};
   a.x = static_cast<const uint16_t*>(x);
   a.w = static_cast<const uint16_t*>(w);
   a.out = static_cast<uint16_t*>(out);
-  a.M = M; a.N = N; a.K = K; a.ks = 1; a.cwl = 4;
+  a.M = M; a.N = N; a.K = K;
   auto st = static_cast<hipStream_t>(stream);
   for (int r = 0; r < reps; r++) {
     hipError_t e;
     const int grid = N / (16 * tn);
     if (tn == 1)
-      e = nw == 4 ? launch_nw<4, 1, EPI_STORE>(a, grid, st) : nw == 8 ? launch_nw<8, 1, EPI_STORE>(a, grid, st)
-                                                          : launch_nw<16, 1, EPI_STORE>(a, grid, st);
+      e = nw == 4 ? launch_nw<4, 1, EPI_STORE>(a, grid, st) : launch_nw<8, 1, EPI_STORE>(a, grid, st);
     else
-      e = nw == 4 ? launch_nw<4, 2, EPI_STORE>(a, grid, st) : nw == 8 ? launch_nw<8, 2, EPI_STORE>(a, grid, st)
-                                                          : launch_nw<16, 2, EPI_STORE>(a, grid, st);
+      e = nw == 4 ? launch_nw<4, 2, EPI_STORE>(a, grid, st) : launch_nw<8, 2, EPI_STORE>(a, grid, st);
     if (e != hipSuccess) return int(e);
   }
   return 0;

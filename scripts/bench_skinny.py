@@ -54,7 +54,7 @@ def main():
         ev1.record()
         torch.cuda.synchronize()
         copy_us = ev0.elapsed_time(ev1) * 1e3 / 20
-        for nw in (4, 8, 16):
+        for nw in (4, 8):
             for tn in (1, 2):
                 if N % (16 * tn):
                     continue

@@ -7,8 +7,13 @@ import os
 import pytest
 import torch
 
+from p2p_llm_tunnel_amd.models.tiny_llm import LlamaConfig
+
 pytestmark = pytest.mark.gpu
 cuda = pytest.mark.skipif(not torch.cuda.is_available(), reason="needs a HIP device")
+
+# One layer, the smallest shape whose O/down projections reach 2 K parts.
+WIDE1 = LlamaConfig(vocab=4096, dim=2048, n_layers=1, n_heads=16, n_kv_heads=4, head_dim=128, ffn=512, max_seq=256)
 
 
 @cuda
@@ -35,7 +40,11 @@ def test_decode_matches_fp32_reference(cfg, fused):
 
 
 @cuda
-@pytest.mark.parametrize("cfg,B", [("micro", 5), ("tiny", 8), ("small", 2)])
+@pytest.mark.parametrize("cfg,B", [("micro", 5), ("tiny", 8), ("small", 2),
+                                   # the last row count whose O/down projections run in 4 K parts
+                                   ("micro", 4),
+                                   # dim 2048: 2 K parts up to 8 rows, none from 9
+                                   pytest.param(WIDE1, 8, id="wide1-8"), pytest.param(WIDE1, 9, id="wide1-9")])
 def test_fused_matches_unfused(cfg, B):
     # Same weights, same token stream: the fused 5-kernels-per-layer step and the
     # unfused kernels + hipBLASLt path agree on logits, caches and greedy ids.
