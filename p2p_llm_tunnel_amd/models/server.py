@@ -47,6 +47,7 @@ from __future__ import annotations
 
 import argparse
 import asyncio
+import functools
 import json
 import os
 import queue
@@ -55,6 +56,7 @@ import sys
 import threading
 import time
 import uuid
+from typing import NamedTuple
 
 import torch
 
@@ -200,15 +202,24 @@ class Request:
         self.state = None  # front-end bookkeeping for batched requests
 
 
+# One token row of a planned step (a decode row's token is read on the device).
+_Row = NamedTuple("_Row", [("slot", int), ("token", int), ("pos", int), ("decode", int), ("emit", bool)])
+
+# Rows of the staging buffer, one column per token row: token (prompt rows),
+# position, cache slot, decode flag, slot to record the sampled id under
+# (scratch for rows that emit nothing), then the sampler's column
+# (temperature bits, top_k, top_p bits, seed, counter; temperature 0 = greedy).
+_TOK, _POS, _SLOT, _DEC, _REC = range(5)
+_SMP = slice(5, 10)
+
+
 class _StepBuf:
     """Host staging of one in-flight step (two alternate: step k+1 is planned
-    and launched while step k runs). Rows: token (prompt rows), position,
-    slot, decode flag, slot to record the sampled id under (scratch for rows
-    that emit nothing), then the sampler's column per row (rows 5-9:
-    temperature bits, top_k, top_p bits, seed, counter; temperature 0 = greedy)."""
+    and launched while step k runs); ``h_in`` has the rows named above."""
 
     def __init__(self, rows: int, cuda: bool):
-        self.h_in = torch.zeros((10, rows), dtype=torch.int64, pin_memory=cuda)
+        self.rows = rows
+        self.h_in = torch.zeros((_SMP.stop, rows), dtype=torch.int64, pin_memory=cuda)
         self.np = self.h_in.numpy()
         self.h_out = torch.zeros(rows, dtype=torch.int64, pin_memory=cuda)
         self.ev = torch.cuda.Event() if cuda else None
@@ -239,7 +250,9 @@ class Engine:
     memory.
 
     ``model`` injects a model object (tests use a CPU stand-in with the same
-    ``decode_step`` / ``cfg`` / ``scratch_slot`` / ``device`` surface).
+    ``decode_step`` / ``cfg`` / ``scratch_slot`` / ``device`` surface). One
+    with ``TinyLlama.step_rows`` on a HIP device runs captured; any other runs
+    the same step eagerly through ``decode_step``, without the sampler.
     """
 
     def __init__(self, device="cuda:0", config="tiny", max_batch=8, seed=0, use_graph=True, rows=64, model=None,
@@ -247,9 +260,9 @@ class Engine:
         if model is None:
             from p2p_llm_tunnel_amd.models.tiny_llm import TinyLlama
             model = TinyLlama(config, device=device, max_batch=max_batch, seed=seed, fused=True)
-        # hipGraphs need the real fused model on a HIP device (a loaded
-        # checkpoint qualifies; CPU stand-ins in tests run eagerly).
-        use_graph = use_graph and model.device.type == "cuda" and hasattr(model, "_decode_impl")
+        # hipGraphs need a model with the capturable step on a HIP device (a
+        # loaded checkpoint qualifies; CPU stand-ins in tests run eagerly).
+        use_graph = use_graph and model.device.type == "cuda" and hasattr(model, "step_rows")
         max_batch = getattr(model, "max_batch", max_batch)
         if not (1 <= max_batch <= rows and 1 <= small_rows <= rows):
             raise ValueError("need 1 <= max_batch <= rows and small_rows <= rows")
@@ -261,28 +274,19 @@ class Engine:
         cuda = self.device.type == "cuda"
         self._k = 0
         self._d_last = torch.zeros(max_batch + 1, dtype=torch.int64, device=self.device)
-        self._graphs = {}
-        if use_graph:
-            # Two row counts: steps of up to 16 rows replay the 16-row graphs,
-            # larger ones (prefill-heavy, or more than 16 generating slots) the
-            # 64-row graphs (4 MFMA row tiles), whose LM head covers only the
-            # leading rows that sample (at most one per slot: max_batch rows).
-            # Each graph holds the whole step: input copy from its pinned
-            # staging buffer, decode-row token gather, the fused step, the
-            # last-token scatter and the copy of the ids back to pinned memory;
-            # one per staging buffer of the pair, so a step is one replay.
-            sizes = [small_rows] + ([rows] if rows > small_rows else [])
-            self._bufs = {R: [_StepBuf(R, cuda), _StepBuf(R, cuda)] for R in sizes}
-            self._d_in = {R: torch.zeros((10, R), dtype=torch.int64, device=self.device) for R in sizes}
-            # Steps where some row samples replay a graph with the sampler
-            # kernel after the fused step; all-greedy steps one without it.
-            for R in sizes:
-                for par in (0, 1):
-                    for smp in (False, True):
-                        self._graphs[(R, par, smp)] = self._capture(self._bufs[R][par], R,
-                                                                    0 if R == small_rows else max_batch, smp)
-        else:
-            self._bufs = {rows: [_StepBuf(rows, cuda), _StepBuf(rows, cuda)]}
+        # Two row counts under graphs: steps of up to 16 rows replay the 16-row
+        # graphs, larger ones (prefill-heavy, or more than 16 generating slots)
+        # the 64-row graphs (4 MFMA row tiles), whose LM head covers only the
+        # leading rows that sample (at most one per slot: max_batch rows).
+        sizes = [small_rows] + ([rows] if rows > small_rows else []) if use_graph else [rows]
+        self._bufs = {R: [_StepBuf(R, cuda), _StepBuf(R, cuda)] for R in sizes}
+        self._d_in = {R: torch.zeros((_SMP.stop, R), dtype=torch.int64, device=self.device) for R in sizes}
+        # Each graph holds the whole step (_step_body), one per staging buffer
+        # of the pair, so a step is one replay. Steps where some row samples
+        # replay a graph with the sampler kernel after the fused step;
+        # all-greedy steps one without it.
+        self._graphs = {(R, par, smp): self._capture(self._bufs[R][par], 0 if R == small_rows else max_batch, smp)
+                        for R in sizes if use_graph for par in (0, 1) for smp in (False, True)}
         self.max_batch = max_batch
         self.pending: queue.Queue = queue.Queue()
         self.slots: list[dict | None] = [None] * max_batch
@@ -321,9 +325,9 @@ class Engine:
                 self.slots[i] = {"req": req, "pos": 0, "ids": ids, "gen": 0}
 
     def _plan(self, batch: list):
-        """Rows of the next step [(slot, token, pos, is_decode, emits)], with the
-        host-side state advanced past them (it does not depend on the tokens)
-        and the emitting rows' (row, req, finished) list."""
+        """Rows of the next step (``_Row``), with the host-side state advanced
+        past them (it does not depend on the tokens) and the emitting rows'
+        (row, req, finished, token index) list."""
         V = self.model.cfg.vocab
         rows, emits = [], []
         for i, s in enumerate(self.slots):  # decode rows first: one token each
@@ -333,30 +337,31 @@ class Engine:
                 self._emit(s["req"], None, batch)
                 self.slots[i] = None
                 continue
-            rows.append((i, 0, s["pos"], 1, True))
+            rows.append(_Row(i, 0, s["pos"], 1, True))
         for i, s in enumerate(self.slots):  # then prompt chunks
             if s is None or s["pos"] >= len(s["ids"]):
                 continue
             take = min(self.rows - len(rows), len(s["ids"]) - s["pos"])
             for p in range(s["pos"], s["pos"] + take):
-                rows.append((i, s["ids"][p] % V, p, 0, p == len(s["ids"]) - 1))
+                rows.append(_Row(i, s["ids"][p] % V, p, 0, p == len(s["ids"]) - 1))
             if len(rows) >= self.rows:
                 break
         # Rows that sample go first: the 64-row graph's LM head covers only the
         # first max_batch rows (each slot samples at most once per step).
-        rows.sort(key=lambda r: not r[4])
+        rows.sort(key=lambda r: not r.emit)
         # Advance every row's slot first: after the sort a slot's sampling row
         # can precede its other prompt rows, so slots are only freed once all
         # rows of the step are accounted for.
         max_seq = self.model.cfg.max_seq
-        for i, _, _, _, emit in rows:
-            self.slots[i]["pos"] += 1
-            if not emit:
+        for row in rows:
+            self.slots[row.slot]["pos"] += 1
+            if not row.emit:
                 self.prefill_tokens += 1
         done = []
-        for r, (i, _, _, _, emit) in enumerate(rows):
-            if not emit:
+        for r, row in enumerate(rows):
+            if not row.emit:
                 continue
+            i = row.slot
             s = self.slots[i]
             s["gen"] += 1
             fin = s["gen"] >= s["req"].max_new or s["pos"] >= max_seq - 1
@@ -367,76 +372,61 @@ class Engine:
             self.slots[i] = None
         return rows, emits
 
-    def _step_body(self, b: _StepBuf, R: int, emit_rows: int, sample: bool = False):
-        """The captured step: staging -> device, token gather, fused step,
-        (the sampler over the emitting rows' logits,) last-token scatter, ids
-        -> pinned staging."""
-        d = self._d_in[R]
-        d.copy_(b.h_in, non_blocking=True)
-        tok = torch.where(d[3] != 0, self._d_last[d[2]], d[0])
-        S = self.model.cfg.max_seq
-        ids, logits = self.model._decode_impl(tok, d[1].to(torch.int32), (0, S - 1), S, d[2].to(torch.int32),
-                                              emit_rows)
-        if sample:
+    def _step_body(self, b: _StepBuf, n: int, run, sample_rows: int = 0):
+        """One step on the first ``n`` rows of ``b``: staging -> device, decode
+        rows' tokens gathered from ``last``, the model through ``run(tokens, pos,
+        slots) -> (ids, logits)``, (the sampler over the leading ``sample_rows``
+        rows' logits,) last-token scatter, ids -> pinned staging."""
+        din = self._d_in[b.rows]
+        din.copy_(b.h_in, non_blocking=True)
+        d = din[:, :n]
+        tok = torch.where(d[_DEC] != 0, self._d_last[d[_SLOT]], d[_TOK])
+        ids, logits = run(tok, d[_POS].to(torch.int32), d[_SLOT].to(torch.int32))
+        if sample_rows:
             from p2p_llm_tunnel_amd import ops
-            n = emit_rows or R
-            ops.sample_(logits[:n], ids[:n], d[5:10])
-        self._d_last.index_copy_(0, d[4], ids)
-        b.h_out.copy_(ids, non_blocking=True)
+            ops.sample_(logits[:sample_rows], ids[:sample_rows], din[_SMP])
+        self._d_last.index_copy_(0, d[_REC], ids)
+        b.h_out[:n].copy_(ids, non_blocking=True)
 
-    def _capture(self, b: _StepBuf, R: int, emit_rows: int, sample: bool = False):
-        scratch = self.model.scratch_slot
+    def _capture(self, b: _StepBuf, emit_rows: int, sample: bool):
+        """The step on all of ``b``'s rows through ``step_rows``, as a hipGraph."""
+        from p2p_llm_tunnel_amd.models.tiny_llm import capture
         b.np[:] = 0
-        b.np[2, :] = scratch  # warm-up and capture touch the scratch slot only
-        b.np[4, :] = scratch
-        side = torch.cuda.Stream(self.device)
-        side.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.no_grad(), torch.cuda.stream(side):
-            for _ in range(2):  # allocator + kernel warm-up outside capture
-                self._step_body(b, R, emit_rows, sample)
-        torch.cuda.current_stream(self.device).wait_stream(side)
-        graph = torch.cuda.CUDAGraph()
-        with torch.no_grad(), torch.cuda.graph(graph):
-            self._step_body(b, R, emit_rows, sample)
+        b.np[_SLOT, :] = b.np[_REC, :] = self.model.scratch_slot  # warm-up and capture touch the scratch slot only
+        run = functools.partial(self.model.step_rows, emit_rows=emit_rows)
+        sample_rows = (emit_rows or b.rows) if sample else 0
+        graph, _ = capture(lambda: self._step_body(b, b.rows, run, sample_rows), self.device)
         torch.cuda.synchronize(self.device)
         return graph
 
     def _launch(self, rows, emits) -> _StepBuf:
         n, scratch = len(rows), self.model.scratch_slot
-        if self.use_graph:
-            R = self.small_rows if n <= self.small_rows else self.rows
-        else:
-            R = self.rows
+        R = self.small_rows if self.use_graph and n <= self.small_rows else self.rows
         par = self._k % 2
         self._k += 1
         b = self._bufs[R][par]
         h = b.np
-        h[0, :n] = [r[1] for r in rows]
-        h[1, :n] = [r[2] for r in rows]
-        h[2, :n] = [r[0] for r in rows]
-        h[3, :n] = [r[3] for r in rows]
-        h[4, :n] = [r[0] if r[4] else scratch for r in rows]
-        h[5:10, :] = 0  # greedy unless an emitting row samples
+        h[_TOK, :n] = [r.token for r in rows]
+        h[_POS, :n] = [r.pos for r in rows]
+        h[_SLOT, :n] = [r.slot for r in rows]
+        h[_DEC, :n] = [r.decode for r in rows]
+        h[_REC, :n] = [r.slot if r.emit else scratch for r in rows]
+        h[_SMP, :] = 0  # greedy unless an emitting row samples
         sample = False
         for r, req, _, ctr in emits:
             if not req.sampling.greedy:
-                h[5:10, r] = req.sampling.column(ctr)
+                h[_SMP, r] = req.sampling.column(ctr)
                 sample = True
         if n < R:  # padding rows: scratch slot, nothing recorded
-            h[0:2, n:R] = 0
-            h[2, n:R] = scratch
-            h[3, n:R] = 0
-            h[4, n:R] = scratch
+            h[_TOK, n:R] = h[_POS, n:R] = h[_DEC, n:R] = 0
+            h[_SLOT, n:R] = h[_REC, n:R] = scratch
         b.n, b.emits = n, emits
         if self.use_graph:
             self._graphs[(R, par, sample)].replay()
-        else:  # injected model (tests): the same step, eagerly, on its n rows
-            d = b.h_in.to(self.device)
-            tok = torch.where(d[3, :n] != 0, self._d_last[d[2, :n]], d[0, :n])
-            lo, hi = min(r[2] for r in rows), max(r[2] for r in rows)
-            ids = self.model.decode_step(tok, d[1, :n].to(torch.int32), (lo, hi), slots=d[2, :n].to(torch.int32))
-            self._d_last.index_copy_(0, d[4, :n], ids.to(torch.int64))
-            b.h_out[:n].copy_(ids)
+        else:  # injected model (tests): the same step, eagerly, on its n rows; no sampler
+            rng = (min(r.pos for r in rows), max(r.pos for r in rows))
+            self._step_body(b, n, lambda tok, pos, slots: (
+                self.model.decode_step(tok, pos, rng, slots=slots).to(torch.int64), None))
         if b.ev is not None:
             b.ev.record()
         self.steps += 1

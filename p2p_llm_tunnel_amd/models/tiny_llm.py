@@ -7,7 +7,7 @@ endpoint's model: random-init weights (no checkpoints offline), bf16.
 Two decode paths over the same weights and caches:
 
 * fused (default, up to 64 token rows per step): ``ops.FusedLlamaDecoder`` — one
-  C++ call launching 5 kernels per layer + 2 (decode_fused.hip: MFMA skinny
+  C++ call launching 5 kernels per layer + 3 (decode_fused.hip: MFMA skinny
   GEMMs with RMSNorm prologues and RoPE/KV-append, SwiGLU, residual and
   argmax epilogues; split-K attention with in-kernel merge);
 * unfused: the standalone kernels of kernels.hip (residual+RMSNorm,
@@ -51,6 +51,22 @@ CONFIGS = {
 }
 
 
+def capture(fn, device, warmup: int = 2):
+    """``fn()`` as a hipGraph (torch.cuda.CUDAGraph): ``warmup`` calls on a side
+    stream keep allocator and GEMM-heuristics warm-up outside the capture.
+    Returns (graph, what ``fn`` returned under capture: the static outputs)."""
+    side = torch.cuda.Stream(device)
+    side.wait_stream(torch.cuda.current_stream(device))
+    with torch.no_grad(), torch.cuda.stream(side):
+        for _ in range(warmup):
+            fn()
+    torch.cuda.current_stream(device).wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.no_grad(), torch.cuda.graph(graph):
+        out = fn()
+    return graph, out
+
+
 class TinyLlama:
     def __init__(self, cfg: LlamaConfig | str = "tiny", device="cuda", max_batch: int = 8, seed: int = 0,
                  fused: bool = True, weights: dict | None = None):
@@ -60,6 +76,7 @@ class TinyLlama:
         self.cfg = CONFIGS[cfg] if isinstance(cfg, str) else cfg
         self.fused = fused
         self._fused = None
+        self._graphs = {}  # rows -> (graph, tokens, pos, slots, ids, logits)
         c = self.cfg
         self.device = torch.device(device)
         self.max_batch = max_batch
@@ -124,7 +141,7 @@ class TinyLlama:
             raise ValueError(f"row->slot mapping needs the fused path and at most {ops.MAX_ROWS} rows")
         if pos_range[0] < 0 or pos_range[1] >= c.max_seq:
             raise ValueError("positions out of [0, max_seq)")
-        ids, logits = self._decode_impl(tokens, pos, pos_range, pos_range[1] + 1, slots, emit_rows)
+        ids, logits = self.step_rows(tokens, pos, slots, emit_rows, pos_range)
         return (ids, logits) if return_logits else ids
 
     def fused_decoder(self) -> ops.FusedLlamaDecoder:
@@ -153,18 +170,22 @@ class TinyLlama:
             self._fused = ops.FusedLlamaDecoder(dims, ws, self.k_cache, self.v_cache)
         return self._fused
 
-    def _decode_impl(self, tokens, pos, pos_range, max_len, slots=None, emit_rows=0):
+    def step_rows(self, tokens, pos, slots=None, emit_rows=0, pos_range=None):
+        """``decode_step`` without host validation (the fused path: without host
+        sync either, so capturable); returns (ids, logits). ``pos_range``: (min,
+        max) of ``pos`` for the unfused kernels' bounds check and attention
+        grid; None means anything in [0, max_seq), the capture case."""
         B = tokens.shape[0]
         if self.fused and B <= ops.MAX_ROWS:
             tokens, pos = tokens.contiguous(), pos.contiguous()
             slots = slots.contiguous() if slots is not None else None
             logits = torch.empty(B, self.cfg.vocab, dtype=torch.bfloat16, device=self.device)
             ids = torch.empty(B, dtype=torch.int64, device=self.device)
-            self.fused_decoder().step(tokens, pos, max_len, logits, ids, slots, emit_rows)
+            self.fused_decoder().step(tokens, pos, logits, ids, slots, emit_rows)
             return ids, logits
-        return self._decode_unfused(tokens, pos, pos_range, max_len)
+        return self._decode_unfused(tokens, pos, pos_range or (0, self.cfg.max_seq - 1))
 
-    def _decode_unfused(self, tokens, pos, pos_range, max_len):
+    def _decode_unfused(self, tokens, pos, pos_range):
         c = self.cfg
         B = tokens.shape[0]
         lens = pos + 1
@@ -176,7 +197,7 @@ class TinyLlama:
             qkv = F.linear(h, L["wqkv"])
             q = ops.rope_qkv_cache(qkv, pos, kc, vc, c.n_heads, c.n_kv_heads, c.head_dim, c.rope_theta,
                                    pos_range=pos_range)
-            a = ops.decode_attention(q, kc, vc, lens, max_len=max_len)
+            a = ops.decode_attention(q, kc, vc, lens, max_len=pos_range[1] + 1)
             o = F.linear(a.view(B, -1), L["wo"])
             h, residual = ops.rmsnorm(o, L["ffn_norm"], c.eps, residual=residual)
             m = F.linear(ops.silu_mul(F.linear(h, L["w_gate_up"])), L["w_down"])
@@ -190,33 +211,22 @@ class TinyLlama:
         """Capture one step of ``rows`` token rows into a hipGraph (torch.cuda.CUDAGraph).
 
         Decode at small batch is bound by kernel count; replaying the captured
-        graph removes the per-kernel launch cost. The attention is captured for
-        the cache capacity (its splits past each row's length exit immediately),
-        so one graph serves every step. Fused path: up to 64 rows with a
-        row->slot map (padding rows point at the scratch slot); unfused: one row
-        per slot. Several row counts may be captured (e.g. 16 for decode-heavy
-        steps, 64 for prefill-heavy ones); ``graph_step`` picks the graph by the
-        number of rows it is given. ``emit_rows``: rows that get ids (0: all).
+        graph removes the per-kernel launch cost. One graph serves every step:
+        the fused kernels' grids depend on the row count alone and read each
+        row's context length from ``pos``; the unfused attention is launched for
+        the cache capacity (splits past a row's length exit immediately). Fused
+        path: up to 64 rows with a row->slot map (padding rows point at the
+        scratch slot); unfused: one row per slot. Several row counts may be
+        captured (e.g. 16 for decode-heavy steps, 64 for prefill-heavy ones);
+        ``graph_step`` picks the graph by the number of rows it is given.
+        ``emit_rows``: rows that get ids (0: all).
         """
-        c = self.cfg
         R = rows or (16 if self.fused else self.max_batch)
-        self.graph_rows = R
         g_tok = torch.zeros(R, dtype=torch.int64, device=self.device)
         g_pos = torch.zeros(R, dtype=torch.int32, device=self.device)
         g_slot = (torch.full((R,), self.scratch_slot, dtype=torch.int32, device=self.device)
                   if self.fused else None)
-        full = (0, c.max_seq - 1)
-        side = torch.cuda.Stream(self.device)
-        side.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.no_grad(), torch.cuda.stream(side):
-            for _ in range(2):  # allocator + GEMM heuristics warm-up outside capture
-                self._decode_impl(g_tok, g_pos, full, c.max_seq, g_slot, emit_rows)
-        torch.cuda.current_stream(self.device).wait_stream(side)
-        graph = torch.cuda.CUDAGraph()
-        with torch.no_grad(), torch.cuda.graph(graph):
-            g_ids, g_logits = self._decode_impl(g_tok, g_pos, full, c.max_seq, g_slot, emit_rows)
-        if not hasattr(self, "_graphs"):
-            self._graphs = {}
+        graph, (g_ids, g_logits) = capture(lambda: self.step_rows(g_tok, g_pos, g_slot, emit_rows), self.device)
         self._graphs[R] = (graph, g_tok, g_pos, g_slot, g_ids, g_logits)
         return self
 
@@ -235,9 +245,6 @@ class TinyLlama:
             g_slot.copy_(slots, non_blocking=True)
         graph.replay()
         return (g_ids, g_logits) if return_logits else g_ids
-
-    def cache_views_contiguous(self) -> bool:
-        return all(self.k_cache[i, : self.max_batch].is_contiguous() for i in range(self.cfg.n_layers))
 
     # ------------------------------------------------------------------ fp32 reference
     @torch.no_grad()

@@ -1,4 +1,4 @@
-"""Python front-end for the gfx950 HIP kernels (``kernels.hip``).
+"""Python front-end for the gfx950 HIP kernels (``kernels.hip``, ``decode_fused.hip``, ``sample.hip``).
 
 The kernels are compiled in-tree into ``_hip_ops.so`` (see ``build.py``) and
 called through ctypes on the current torch stream. Every wrapper validates
@@ -44,19 +44,19 @@ def lib() -> ctypes.CDLL:
         _LIB.p2pt_llama_ws_bytes.argtypes = [ctypes.POINTER(LlamaDims)]
         _LIB.p2pt_llama_ws_bytes.restype = ctypes.c_size_t
         _LIB.p2pt_llama_decode.argtypes = [ctypes.POINTER(LlamaDims), ctypes.POINTER(vp), vp, vp, vp, vp, vp, i, i,
-                                           i, vp, ctypes.c_size_t, vp, vp, vp]
+                                           vp, ctypes.c_size_t, vp, vp, vp]
         for fn in ("p2pt_rmsnorm", "p2pt_silu_mul", "p2pt_rope_qkv_cache", "p2pt_decode_attention", "p2pt_argmax",
                    "p2pt_skinny_gemm", "p2pt_llama_decode", "p2pt_sample"):
             getattr(_LIB, fn).restype = ctypes.c_int
     return _LIB
 
 
-
 MAX_ROWS = 64  # token rows per fused step (decode_fused.hip kMaxM)
 
+
 def loaded_path() -> str:
-    lib()
-    return os.path.join(HERE, "_hip_ops.so")
+    """Path of the library ``lib()`` opened (``P2PT_HIP_OPS_LIB`` honoured)."""
+    return lib()._name
 
 
 def _stream(t: torch.Tensor):
@@ -248,11 +248,11 @@ def skinny_gemm(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
 
 
 class FusedLlamaDecoder:
-    """Host handle for the fused decode step (decode_fused.hip): 5 kernels per layer + 2.
+    """Host handle for the fused decode step (decode_fused.hip): 5 kernels per layer + 3.
 
     Holds the weight pointer table and a zero-initialised workspace; ``step``
     validates the per-call tensors and launches on the current stream (capturable
-    into a hipGraph: no host sync, no allocation).
+    into a hipGraph: no host sync, no allocation, grids sized by the row count).
     """
 
     def __init__(self, dims: LlamaDims, weights: list, k_cache: torch.Tensor, v_cache: torch.Tensor):
@@ -277,8 +277,8 @@ class FusedLlamaDecoder:
         self.k_cache, self.v_cache = k_cache, v_cache
         self.device = dev
 
-    def step(self, tokens: torch.Tensor, pos: torch.Tensor, max_len: int, logits: torch.Tensor,
-             ids: torch.Tensor, slots: torch.Tensor | None = None, emit_rows: int = 0) -> None:
+    def step(self, tokens: torch.Tensor, pos: torch.Tensor, logits: torch.Tensor, ids: torch.Tensor,
+             slots: torch.Tensor | None = None, emit_rows: int = 0) -> None:
         """One step over B <= 64 token rows (16-row MFMA tiles). Row b is token
         ``tokens[b]`` at cache position ``pos[b]`` of cache slot ``slots[b]``
         (default: slot b). Rows of one slot at consecutive positions are a prefill
@@ -301,8 +301,6 @@ class FusedLlamaDecoder:
             raise ValueError(f"rows must be 1..{limit} with matching pos/ids")
         if logits.shape != (B, d.vocab):
             raise ValueError("logits must be [B, vocab]")
-        if not 1 <= max_len <= d.max_seq:
-            raise ValueError("max_len out of range")
         _ok(lib().p2pt_llama_decode(ctypes.byref(d), self._wptr, _p(self.k_cache), _p(self.v_cache), _p(tokens),
-                                    _p(pos), _p(slots), B, emit_rows, max_len, _p(self.ws), self.ws.numel(), _p(logits),
+                                    _p(pos), _p(slots), B, emit_rows, _p(self.ws), self.ws.numel(), _p(logits),
                                     _p(ids), _stream(tokens)), "llama_decode")

@@ -4,7 +4,7 @@
 // 4-layer model; at decode batch sizes every one of them is a few-µs latency
 // chain (dispatch, one HBM round trip, write back) and the step is bound by
 // kernel count, not bytes. This file rebuilds the step as 5 kernels per layer
-// plus 2, each a weight-streaming MFMA GEMM with its neighbours fused in:
+// plus 3, the GEMMs weight-streaming MFMA kernels with their neighbours fused in:
 //
 //   k_embed              token gather -> residual stream, per-row sum of squares
 //   per layer:
@@ -736,11 +736,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1))) void k
   if (threadIdx.x == 0) st_wt(&counters[blockIdx.y], 0u);
 }
 
-// Span slots per (row, KV head): about one round of workgroups on the chip,
-// at most the workspace's partial slots.
-int attn_slots(int B, int Hkv, int nsplit_ws) {
-  const int sl = kAttnTargetWgs / std::max(1, B * Hkv);
-  return std::max(1, std::min({sl, kAttnSlotCap, nsplit_ws}));
+// Partial slots per head in part_o / part_ml (k_attn's nsplit): the most span
+// slots a launch can have. k_attn writes slot sl < nact <= gridDim.x <= stride:
+// span >= ceil(len / gridDim.x), so nact = ceil(len / span) <= gridDim.x, and
+// attn_slots() never exceeds the stride.
+int attn_part_stride(int max_seq) { return std::min(kAttnSlotCap, (max_seq + kAttnMinSpan - 1) / kAttnMinSpan); }
+
+// Span slots per (row, KV head), k_attn's gridDim.x: about one round of
+// workgroups on the chip. Sized by the batch; the context enters through pos.
+int attn_slots(int B, int Hkv, int max_seq) {
+  return std::max(1, std::min(kAttnTargetWgs / std::max(1, B * Hkv), attn_part_stride(max_seq)));
 }
 
 // Measured on MI355X and rejected; the code is gone, the findings stay. This
@@ -785,7 +790,6 @@ struct LlamaDims {
   float eps, theta;
 };
 
-constexpr int kChunk = 64;  // tokens per attention workgroup = workspace granularity of its partials
 constexpr int kTnResid = 1, kTnStore = 2;  // LM head: two 16-column subtiles per block
 constexpr int kCUs = 256;  // MI355X compute units: K-parts tiling aims at one workgroup per CU
 
@@ -807,14 +811,15 @@ Workspace carve(const LlamaDims& d, uint8_t* base) {
     off += align256(n);
     return p;
   };
-  const int nsplit = (d.max_seq + kChunk - 1) / kChunk;
+  const int nsplit = attn_part_stride(d.max_seq);
   const int ss_parts = d.dim / (16 * kTnResid);
   const int am_parts = d.vocab / (16 * kTnStore);
   w.resid = reinterpret_cast<uint16_t*>(take(size_t(kMaxM) * d.dim * 2));
   w.q = reinterpret_cast<uint16_t*>(take(size_t(kMaxM) * d.H * d.D * 2));
   w.attn = reinterpret_cast<uint16_t*>(take(size_t(kMaxM) * d.H * d.D * 2));
   w.h = reinterpret_cast<uint16_t*>(take(size_t(kMaxM) * d.ffn * 2));
-  w.ss = reinterpret_cast<float*>(take(size_t(ss_parts > 1 ? ss_parts : 1) * kMaxM * 4 * 4));  // up to 4-column tiles
+  const int ss_narrow = 16 >> tile_cwl(2);  // K parts narrow the 16-column tiles that ss_parts counts to 4 columns
+  w.ss = reinterpret_cast<float*>(take(size_t(std::max(ss_parts, 1)) * ss_narrow * kMaxM * 4));
   w.part_o = reinterpret_cast<float*>(take(size_t(kMaxM) * d.H * nsplit * d.D * 4));
   w.part_ml = reinterpret_cast<float*>(take(size_t(kMaxM) * d.H * nsplit * 2 * 4));
   w.am_val = reinterpret_cast<float*>(take(size_t(am_parts) * kMaxM * 4));
@@ -898,7 +903,8 @@ size_t p2pt_llama_ws_bytes(const LlamaDims* d) {
   return carve(*d, nullptr).bytes;
 }
 
-// One decode step for B <= 16 sequences (slots 0..B-1 of the caches).
+// One decode step over B <= 64 token rows. The grids depend on B alone (the
+// context enters through pos), so a captured step serves every position.
 //   w: embed, final_norm, lm_head, then per layer
 //      attn_norm, wqkv [(H+2Hkv)*D, dim], wo [dim, H*D], ffn_norm, w_gate_up [2*ffn, dim], w_down [dim, ffn]
 //      where wqkv, w_gate_up and lm_head carry the preceding RMSNorm weight folded
@@ -912,13 +918,11 @@ size_t p2pt_llama_ws_bytes(const LlamaDims* d) {
 //   slots int32 [B] or nullptr: cache slot of each row (< max_batch). Rows of one
 //     slot at consecutive positions form a prefill chunk: every row's K/V is
 //     appended before attention runs, and each row attends up to its own position.
-//   max_len: host bound on max(pos) + 1 (sizes the attention grid; use max_seq under graph capture)
 int p2pt_llama_decode(const LlamaDims* dp, const void* const* w, void* k_cache, void* v_cache, const int64_t* tokens,
-                      const int* pos, const int* slots, int B, int emit_rows, int max_len, void* ws, size_t ws_bytes,
-                      void* logits, int64_t* ids, void* stream) {
+                      const int* pos, const int* slots, int B, int emit_rows, void* ws, size_t ws_bytes, void* logits,
+                      int64_t* ids, void* stream) {
   const LlamaDims d = *dp;
-  if (!dims_ok(d) || B <= 0 || B > kMaxM || (!slots && B > d.max_batch) || max_len <= 0 || max_len > d.max_seq)
-    return int(hipErrorInvalidValue);
+  if (!dims_ok(d) || B <= 0 || B > kMaxM || (!slots && B > d.max_batch)) return int(hipErrorInvalidValue);
   if (emit_rows <= 0 || emit_rows > B) emit_rows = B;
   Workspace W = carve(d, static_cast<uint8_t*>(ws));
   if (ws_bytes < W.bytes) return int(hipErrorInvalidValue);
@@ -926,7 +930,6 @@ int p2pt_llama_decode(const LlamaDims* dp, const void* const* w, void* k_cache, 
   auto bf = [&](int i) { return static_cast<const uint16_t*>(w[i]); };
   const int qkv_n = (d.H + 2 * d.Hkv) * d.D;
   const size_t layer_cache = size_t(d.max_batch) * d.max_seq * d.Hkv * d.D;
-  const int nsplit_ws = (d.max_seq + kChunk - 1) / kChunk;
   const float log2_theta = log2f(d.theta);
 
   hipLaunchKernelGGL(k_embed, dim3(B), dim3(256), 0, s, bf(0), tokens, W.resid, W.ss, d.dim, d.vocab);
@@ -954,13 +957,12 @@ int p2pt_llama_decode(const LlamaDims* dp, const void* const* w, void* k_cache, 
 
     // attention: (span slot, row, KV head) workgroups of 8 waves
     {
-      (void)max_len;  // the grid no longer depends on the context length
-      dim3 grid(attn_slots(B, d.Hkv, nsplit_ws), B * d.Hkv);
+      dim3 grid(attn_slots(B, d.Hkv, d.max_seq), B * d.Hkv);
       const float scale = 1.f / sqrtf(float(d.D));
       const int G = d.H / d.Hkv;
 #define LAUNCH_ATTN(DD, GG)                                                                                       \
   hipLaunchKernelGGL((k_attn<DD, GG>), grid, dim3(512), 0, s, W.q, kc, vc, pos, slots, d.max_batch, W.part_o,   \
-                     W.part_ml, W.counters, W.attn, d.H, d.Hkv, d.max_seq, nsplit_ws, scale)
+                     W.part_ml, W.counters, W.attn, d.H, d.Hkv, d.max_seq, attn_part_stride(d.max_seq), scale)
       if (d.D == 64) {
         if (G == 1) LAUNCH_ATTN(64, 1); else if (G == 2) LAUNCH_ATTN(64, 2); else if (G == 4) LAUNCH_ATTN(64, 4); else LAUNCH_ATTN(64, 8);
       } else {
@@ -1020,26 +1022,25 @@ int p2pt_skinny_gemm(const void* x, const void* w, void* out, int M, int N, int 
 // launches of the decode attention kernel. part_o / part_ml / counters as in
 // the workspace (counters zeroed); q [B][H*D], caches [B][Smax][Hkv][D].
 int p2pt_attn_bench(const void* q, const void* kc, const void* vc, const int* pos, int B, int H, int Hkv, int D,
-                    int Smax, int max_len, float* part_o, float* part_ml, unsigned* counters, void* out, int reps,
-                    void* stream) {
+                    int Smax, float* part_o, float* part_ml, unsigned* counters, void* out, int reps, void* stream) {
   const int G = Hkv > 0 ? H / Hkv : 0;
-  if (B <= 0 || B > kMaxM || (D != 64 && D != 128) || G != 4 || max_len <= 0 || max_len > Smax || reps <= 0)
+  if (B <= 0 || B > kMaxM || (D != 64 && D != 128) || G != 4 || Smax <= 0 || reps <= 0)
     return int(hipErrorInvalidValue);
   auto st = static_cast<hipStream_t>(stream);
-  const int nsplit_ws = (Smax + kChunk - 1) / kChunk;
+  const int nsplit = attn_part_stride(Smax);
   const float scale = 1.f / sqrtf(float(D));
   for (int r = 0; r < reps; r++) {
-    dim3 grid(attn_slots(B, Hkv, nsplit_ws), B * Hkv);
+    dim3 grid(attn_slots(B, Hkv, Smax), B * Hkv);
     auto qq = static_cast<const uint16_t*>(q);
     auto kk = static_cast<const uint16_t*>(kc);
     auto vv = static_cast<const uint16_t*>(vc);
     auto oo = static_cast<uint16_t*>(out);
     if (D == 64)
       hipLaunchKernelGGL((k_attn<64, 4>), grid, dim3(512), 0, st, qq, kk, vv, pos, nullptr, B, part_o, part_ml,
-                         counters, oo, H, Hkv, Smax, nsplit_ws, scale);
+                         counters, oo, H, Hkv, Smax, nsplit, scale);
     else
       hipLaunchKernelGGL((k_attn<128, 4>), grid, dim3(512), 0, st, qq, kk, vv, pos, nullptr, B, part_o, part_ml,
-                         counters, oo, H, Hkv, Smax, nsplit_ws, scale);
+                         counters, oo, H, Hkv, Smax, nsplit, scale);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return int(e);
   }

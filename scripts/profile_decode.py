@@ -21,7 +21,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch  # noqa: E402
 
-from p2p_llm_tunnel_amd.models.tiny_llm import CONFIGS, TinyLlama  # noqa: E402
+from p2p_llm_tunnel_amd.models.tiny_llm import CONFIGS, TinyLlama, capture  # noqa: E402
 
 
 def main():
@@ -86,17 +86,10 @@ def loop(m, a):
     logits = torch.empty(B, c.vocab, dtype=torch.bfloat16, device="cuda")
 
     def body():
-        dec.step(tok, pos, c.max_seq, logits, tok, None, 0)
+        dec.step(tok, pos, logits, tok)
         pos.add_(1)
 
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        body()
-    torch.cuda.current_stream().wait_stream(side)
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        body()
+    g, _ = capture(body, m.device, warmup=1)
     pos.fill_(a.ctx)
     for _ in range(a.warmup):
         g.replay()

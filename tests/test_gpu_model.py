@@ -69,7 +69,7 @@ def test_fused_matches_unfused(cfg, B):
 
 @cuda
 @pytest.mark.parametrize("cfg,positions", [("micro", [0, 63, 64, 300]),
-                                           # head_dim 128: 1024-token workgroup splits, merged across splits
+                                           # head_dim 128: rows of 1, 16, 11 and 16 span slots, merged in-kernel
                                            ("small", [3, 1023, 1024, 2500])])
 def test_fused_ragged_positions(cfg, positions):
     # Slots at different positions in one step (continuous batching).
@@ -95,6 +95,39 @@ def test_fused_ragged_positions(cfg, positions):
     mf.v_cache.copy_(mu.v_cache)
     _, lg = mf.graph_step(toks, pos, return_logits=True)
     assert (lg.float() - lu.float()).abs().max().item() < 0.03 * lu.float().abs().max().item()
+
+
+# One layer whose max_seq exceeds 16 span slots of 64 tokens: the attention
+# partials are strided by the 16 slots a launch can have, not by max_seq / 64.
+LONG1 = LlamaConfig(vocab=4096, dim=256, n_layers=1, n_heads=4, n_kv_heads=2, head_dim=64, ffn=512, max_seq=2048)
+
+
+@cuda
+@pytest.mark.parametrize("positions", [[2047],  # batch 1: all 16 span slots active, 128 tokens each
+                                       # one launch whose rows fill 16, 11, 2 and 1 slots: the rows' arrival
+                                       # counters finish at different counts
+                                       [2047, 1024, 64, 0]], ids=["b1", "ragged"])
+def test_fused_attention_partials_at_slot_cap(positions):
+    from p2p_llm_tunnel_amd.models.tiny_llm import TinyLlama
+    B = len(positions)
+    mf = TinyLlama(LONG1, device="cuda", max_batch=B, seed=6, fused=True)
+    mu = TinyLlama(LONG1, device="cuda", max_batch=B, seed=6, fused=False)
+    torch.manual_seed(2)
+    mf.k_cache.normal_()
+    mf.v_cache.normal_()
+    mu.k_cache.copy_(mf.k_cache)
+    mu.v_cache.copy_(mf.v_cache)
+    toks = torch.randint(0, LONG1.vocab, (B,), device="cuda")
+    pos = torch.tensor(positions, dtype=torch.int32, device="cuda")
+    rng = (min(positions), max(positions))
+    id1, l1 = mf.decode_step(toks, pos, rng, return_logits=True)
+    _, lu = mu.decode_step(toks, pos, rng, return_logits=True)
+    assert (l1.float() - lu.float()).abs().max().item() < 0.03 * lu.float().abs().max().item()
+    # Again: the counters reset themselves, and the step rewrites the K/V it
+    # appended with the same values. Partials merge in slot order whichever
+    # workgroup arrives last, so the result is the same bit for bit.
+    id2, l2 = mf.decode_step(toks, pos, rng, return_logits=True)
+    assert torch.equal(l2, l1) and torch.equal(id2, id1)
 
 
 @cuda
@@ -238,9 +271,9 @@ def test_64_row_prefill_chunk_matches_16_row_chunks():
 @cuda
 @pytest.mark.parametrize("cfg,B", [("micro", 64), ("small", 40)])
 def test_fused_prefill_sized_steps_match_unfused(cfg, B):
-    # Steps of more than 16 rows run every GEMM with four 16-row tiles per
-    # workgroup sharing each weight fragment (decode_fused.hip RT = 4); they
-    # must agree with the unfused kernels + hipBLASLt on the same rows.
+    # Steps of more than 16 rows run every GEMM over up to four 16-row tiles,
+    # one workgroup per tile (decode_fused.hip blockIdx.y); they must agree
+    # with the unfused kernels + hipBLASLt on the same rows.
     from p2p_llm_tunnel_amd.models.tiny_llm import TinyLlama
     mf = TinyLlama(cfg, device="cuda", max_batch=B, seed=9, fused=True)
     mu = TinyLlama(cfg, device="cuda", max_batch=B, seed=9, fused=False)
