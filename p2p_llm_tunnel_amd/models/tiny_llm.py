@@ -144,30 +144,35 @@ class TinyLlama:
         ids, logits = self.step_rows(tokens, pos, slots, emit_rows, pos_range)
         return (ids, logits) if return_logits else ids
 
+    def fused_weights(self) -> list:
+        """The fused step's weight table (device-independent: plain torch)."""
+        c = self.cfg
+        # The fused GEMMs take the RMSNorm weight folded into the following
+        # projection's columns (W[n][k] * g[k]), and QKV / gate-up rows
+        # interleaved in pairs so a 16-column tile holds both members of a
+        # RoPE pair or a SwiGLU pair; see decode_fused.hip.
+        def fold(w, g):
+            return (w.float() * g.float()[None, :]).to(torch.bfloat16)
+
+        def pairs(n):  # [0, n, 1, n + 1, ...]
+            return torch.stack([torch.arange(n), torch.arange(n) + n], 1).flatten().to(self.device)
+
+        heads = c.n_heads + 2 * c.n_kv_heads
+        head_perm = (torch.arange(heads, device=self.device)[:, None] * c.head_dim
+                     + pairs(c.head_dim // 2)[None, :]).flatten()
+        ws = [self.embed, self.final_norm, fold(self.lm_head, self.final_norm)]
+        for L in self.layers:
+            ws += [L["attn_norm"], fold(L["wqkv"], L["attn_norm"])[head_perm].contiguous(), L["wo"],
+                   L["ffn_norm"], fold(L["w_gate_up"], L["ffn_norm"])[pairs(c.ffn)].contiguous(), L["w_down"]]
+        return ws
+
     def fused_decoder(self) -> ops.FusedLlamaDecoder:
         if self._fused is None:
             c = self.cfg
             dims = ops.LlamaDims(vocab=c.vocab, dim=c.dim, n_layers=c.n_layers, H=c.n_heads, Hkv=c.n_kv_heads,
                                  D=c.head_dim, ffn=c.ffn, max_seq=c.max_seq, max_batch=self.max_batch + 1, eps=c.eps,
                                  theta=c.rope_theta)
-            # The fused GEMMs take the RMSNorm weight folded into the following
-            # projection's columns (W[n][k] * g[k]), and QKV / gate-up rows
-            # interleaved in pairs so a 16-column tile holds both members of a
-            # RoPE pair or a SwiGLU pair; see decode_fused.hip.
-            def fold(w, g):
-                return (w.float() * g.float()[None, :]).to(torch.bfloat16)
-
-            def pairs(n):  # [0, n, 1, n + 1, ...]
-                return torch.stack([torch.arange(n), torch.arange(n) + n], 1).flatten().to(self.device)
-
-            heads = c.n_heads + 2 * c.n_kv_heads
-            head_perm = (torch.arange(heads, device=self.device)[:, None] * c.head_dim
-                         + pairs(c.head_dim // 2)[None, :]).flatten()
-            ws = [self.embed, self.final_norm, fold(self.lm_head, self.final_norm)]
-            for L in self.layers:
-                ws += [L["attn_norm"], fold(L["wqkv"], L["attn_norm"])[head_perm].contiguous(), L["wo"],
-                       L["ffn_norm"], fold(L["w_gate_up"], L["ffn_norm"])[pairs(c.ffn)].contiguous(), L["w_down"]]
-            self._fused = ops.FusedLlamaDecoder(dims, ws, self.k_cache, self.v_cache)
+            self._fused = ops.FusedLlamaDecoder(dims, self.fused_weights(), self.k_cache, self.v_cache)
         return self._fused
 
     def step_rows(self, tokens, pos, slots=None, emit_rows=0, pos_range=None):

@@ -43,6 +43,9 @@ def lib() -> ctypes.CDLL:
         _LIB.p2pt_sample.argtypes = [vp, vp, vp, i, i, i, vp]
         _LIB.p2pt_llama_ws_bytes.argtypes = [ctypes.POINTER(LlamaDims)]
         _LIB.p2pt_llama_ws_bytes.restype = ctypes.c_size_t
+        szp = ctypes.POINTER(ctypes.c_size_t)
+        _LIB.p2pt_llama_ws_layout.argtypes = [ctypes.POINTER(LlamaDims), szp, szp, i]
+        _LIB.p2pt_llama_ws_layout.restype = ctypes.c_int
         _LIB.p2pt_llama_decode.argtypes = [ctypes.POINTER(LlamaDims), ctypes.POINTER(vp), vp, vp, vp, vp, vp, i, i,
                                            vp, ctypes.c_size_t, vp, vp, vp]
         for fn in ("p2pt_rmsnorm", "p2pt_silu_mul", "p2pt_rope_qkv_cache", "p2pt_decode_attention", "p2pt_argmax",
@@ -276,6 +279,36 @@ class FusedLlamaDecoder:
         self.ws = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
         self.k_cache, self.v_cache = k_cache, v_cache
         self.device = dev
+
+    # Workspace buffers in the order p2pt_llama_ws_layout reports them.
+    _WS_BUFFERS = (("resid", torch.bfloat16), ("q", torch.bfloat16), ("attn", torch.bfloat16), ("h", torch.bfloat16),
+                   ("ss", torch.float32), ("part_o", torch.float32), ("part_ml", torch.float32),
+                   ("am_val", torch.float32), ("am_idx", torch.int32), ("counters", torch.int32))
+
+    def workspace_views(self) -> dict:
+        """Typed, shaped views into the workspace (no copies; the layout comes from
+        ``p2pt_llama_ws_layout``): what the last ``step`` left in each buffer.
+
+        resid [64, dim], q [64, H, D], attn [64, H*D], h [64, ffn] (bf16);
+        ss [parts, 64], part_o [64, H, nsplit, D], part_ml [64, H, nsplit, 2],
+        am_val [blocks, 64] (fp32); am_idx [blocks, 64], counters [64*H] (int32).
+        Read them after a stream sync; only the first B rows of a step are defined."""
+        d = self.dims
+        n = len(self._WS_BUFFERS)
+        off, cnt = (ctypes.c_size_t * n)(), (ctypes.c_size_t * n)()
+        if lib().p2pt_llama_ws_layout(ctypes.byref(d), off, cnt, n) != n:
+            raise RuntimeError("workspace layout: buffer list out of step with decode_fused.hip")
+        views = {}
+        for (name, dtype), o, c in zip(self._WS_BUFFERS, off, cnt):
+            size = torch.empty(0, dtype=dtype).element_size()
+            if o % size or o + c * size > self.ws.numel():
+                raise RuntimeError(f"workspace layout: {name} lies outside the workspace")
+            views[name] = self.ws[o:o + c * size].view(dtype)
+        M = MAX_ROWS
+        shapes = {"resid": (M, d.dim), "q": (M, d.H, d.D), "attn": (M, d.H * d.D), "h": (M, d.ffn), "ss": (-1, M),
+                  "part_o": (M, d.H, -1, d.D), "part_ml": (M, d.H, -1, 2), "am_val": (-1, M), "am_idx": (-1, M),
+                  "counters": (M * d.H,)}
+        return {name: v.view(*shapes[name]) for name, v in views.items()}
 
     def step(self, tokens: torch.Tensor, pos: torch.Tensor, logits: torch.Tensor, ids: torch.Tensor,
              slots: torch.Tensor | None = None, emit_rows: int = 0) -> None:

@@ -803,29 +803,57 @@ struct Workspace {
   size_t bytes;
 };
 
-Workspace carve(const LlamaDims& d, uint8_t* base) {
-  Workspace w{};
+// The workspace buffers in layout order (p2pt_llama_ws_layout reports them in this order).
+enum WsBuf : int { WS_RESID, WS_Q, WS_ATTN, WS_H, WS_SS, WS_PART_O, WS_PART_ML, WS_AM_VAL, WS_AM_IDX, WS_COUNTERS, WS_NBUF };
+
+struct WsLayout {
+  size_t off[WS_NBUF];    // byte offset from the workspace base (256-byte aligned)
+  size_t count[WS_NBUF];  // elements: bf16 resid/q/attn/h, fp32 ss/part_o/part_ml/am_val, int32 am_idx, uint32 counters
+  size_t bytes;
+};
+
+// The one place that knows the workspace layout.
+WsLayout ws_layout(const LlamaDims& d) {
+  WsLayout l{};
   size_t off = 0;
-  auto take = [&](size_t n) {
-    uint8_t* p = base ? base + off : nullptr;
-    off += align256(n);
-    return p;
+  auto take = [&](WsBuf b, size_t count, size_t elem) {
+    l.off[b] = off;
+    l.count[b] = count;
+    off += align256(count * elem);
   };
   const int nsplit = attn_part_stride(d.max_seq);
   const int ss_parts = d.dim / (16 * kTnResid);
   const int am_parts = d.vocab / (16 * kTnStore);
-  w.resid = reinterpret_cast<uint16_t*>(take(size_t(kMaxM) * d.dim * 2));
-  w.q = reinterpret_cast<uint16_t*>(take(size_t(kMaxM) * d.H * d.D * 2));
-  w.attn = reinterpret_cast<uint16_t*>(take(size_t(kMaxM) * d.H * d.D * 2));
-  w.h = reinterpret_cast<uint16_t*>(take(size_t(kMaxM) * d.ffn * 2));
+  take(WS_RESID, size_t(kMaxM) * d.dim, 2);
+  take(WS_Q, size_t(kMaxM) * d.H * d.D, 2);
+  take(WS_ATTN, size_t(kMaxM) * d.H * d.D, 2);
+  take(WS_H, size_t(kMaxM) * d.ffn, 2);
   const int ss_narrow = 16 >> tile_cwl(2);  // K parts narrow the 16-column tiles that ss_parts counts to 4 columns
-  w.ss = reinterpret_cast<float*>(take(size_t(std::max(ss_parts, 1)) * ss_narrow * kMaxM * 4));
-  w.part_o = reinterpret_cast<float*>(take(size_t(kMaxM) * d.H * nsplit * d.D * 4));
-  w.part_ml = reinterpret_cast<float*>(take(size_t(kMaxM) * d.H * nsplit * 2 * 4));
-  w.am_val = reinterpret_cast<float*>(take(size_t(am_parts) * kMaxM * 4));
-  w.am_idx = reinterpret_cast<int*>(take(size_t(am_parts) * kMaxM * 4));
-  w.counters = reinterpret_cast<unsigned*>(take(size_t(kMaxM * d.H) * 4));
-  w.bytes = off;
+  take(WS_SS, size_t(std::max(ss_parts, 1)) * ss_narrow * kMaxM, 4);
+  take(WS_PART_O, size_t(kMaxM) * d.H * nsplit * d.D, 4);
+  take(WS_PART_ML, size_t(kMaxM) * d.H * nsplit * 2, 4);
+  take(WS_AM_VAL, size_t(am_parts) * kMaxM, 4);
+  take(WS_AM_IDX, size_t(am_parts) * kMaxM, 4);
+  take(WS_COUNTERS, size_t(kMaxM * d.H), 4);
+  l.bytes = off;
+  return l;
+}
+
+Workspace carve(const LlamaDims& d, uint8_t* base) {
+  const WsLayout l = ws_layout(d);
+  Workspace w{};
+  auto at = [&](WsBuf b) { return base ? base + l.off[b] : nullptr; };
+  w.resid = reinterpret_cast<uint16_t*>(at(WS_RESID));
+  w.q = reinterpret_cast<uint16_t*>(at(WS_Q));
+  w.attn = reinterpret_cast<uint16_t*>(at(WS_ATTN));
+  w.h = reinterpret_cast<uint16_t*>(at(WS_H));
+  w.ss = reinterpret_cast<float*>(at(WS_SS));
+  w.part_o = reinterpret_cast<float*>(at(WS_PART_O));
+  w.part_ml = reinterpret_cast<float*>(at(WS_PART_ML));
+  w.am_val = reinterpret_cast<float*>(at(WS_AM_VAL));
+  w.am_idx = reinterpret_cast<int*>(at(WS_AM_IDX));
+  w.counters = reinterpret_cast<unsigned*>(at(WS_COUNTERS));
+  w.bytes = l.bytes;
   return w;
 }
 
@@ -901,6 +929,20 @@ extern "C" {
 size_t p2pt_llama_ws_bytes(const LlamaDims* d) {
   if (!dims_ok(*d)) return 0;
   return carve(*d, nullptr).bytes;
+}
+
+// Where each workspace buffer lies (tests read the step's intermediates through
+// this): byte offsets and element counts of resid, q, attn, h, ss, part_o,
+// part_ml, am_val, am_idx, counters, in that order, into off[n] / count[n].
+// Returns the number of buffers, or 0 for unsupported dims or n too small.
+int p2pt_llama_ws_layout(const LlamaDims* d, size_t* off, size_t* count, int n) {
+  if (!dims_ok(*d) || n < WS_NBUF) return 0;
+  const WsLayout l = ws_layout(*d);
+  for (int b = 0; b < WS_NBUF; b++) {
+    off[b] = l.off[b];
+    count[b] = l.count[b];
+  }
+  return WS_NBUF;
 }
 
 // One decode step over B <= 64 token rows. The grids depend on B alone (the
