@@ -24,6 +24,28 @@ class LlamaDims(ctypes.Structure):
                                            "max_batch")] + [("eps", ctypes.c_float), ("theta", ctypes.c_float)]
 
 
+_INT = ctypes.c_int
+
+
+class GemmPlan(ctypes.Structure):
+    """Mirror of ``GemmPlan`` in decode_fused.hip: ``k_skinny<nw, tn, epi, um>`` with ``1 << kpl`` K parts on a
+    ``grid_x`` x ``grid_y`` grid, reading ``ss_in`` sum-of-squares partials (0: no norm)."""
+    _fields_ = [(n, _INT) for n in ("epi", "nw", "tn", "um", "kpl", "grid_x", "grid_y", "ss_in", "M", "N", "K")]
+
+
+class AttnPlan(ctypes.Structure):
+    """Mirror of ``AttnPlan``: ``k_attn<D, G>`` on ``slots`` x ``grid_y`` workgroups; ``stride`` partial slots per
+    head in part_o / part_ml."""
+    _fields_ = [(n, _INT) for n in ("D", "G", "slots", "stride", "grid_y")]
+
+
+class StepPlan(ctypes.Structure):
+    """Mirror of ``StepPlan``: what one fused step launches (``qkv_first``: layer 0)."""
+    _fields_ = ([("rows", _INT), ("emit_rows", _INT)] +
+                [(n, GemmPlan) for n in ("qkv_first", "qkv", "o", "gate_up", "down", "lm_head")] +
+                [("attn", AttnPlan), ("am_parts", _INT)])
+
+
 def lib() -> ctypes.CDLL:
     global _LIB
     if _LIB is None:
@@ -48,13 +70,36 @@ def lib() -> ctypes.CDLL:
         _LIB.p2pt_llama_ws_layout.restype = ctypes.c_int
         _LIB.p2pt_llama_decode.argtypes = [ctypes.POINTER(LlamaDims), ctypes.POINTER(vp), vp, vp, vp, vp, vp, i, i,
                                            vp, ctypes.c_size_t, vp, vp, vp]
+        _LIB.p2pt_llama_plan.argtypes = [ctypes.POINTER(LlamaDims), i, i, ctypes.POINTER(StepPlan)]
+        _LIB.p2pt_attn_span.argtypes = [i, i]
+        _LIB.p2pt_max_rows.argtypes = []
+        # microbenchmark hooks (scripts/bench_skinny.py)
+        _LIB.p2pt_skinny_bench.argtypes = [vp, vp, vp, i, i, i, i, i, i, vp]
+        _LIB.p2pt_attn_bench.argtypes = [vp, vp, vp, vp, i, i, i, i, i, vp, vp, vp, vp, i, vp]
         for fn in ("p2pt_rmsnorm", "p2pt_silu_mul", "p2pt_rope_qkv_cache", "p2pt_decode_attention", "p2pt_argmax",
-                   "p2pt_skinny_gemm", "p2pt_llama_decode", "p2pt_sample"):
+                   "p2pt_skinny_gemm", "p2pt_llama_decode", "p2pt_sample", "p2pt_llama_plan", "p2pt_attn_span",
+                   "p2pt_max_rows", "p2pt_skinny_bench", "p2pt_attn_bench"):
             getattr(_LIB, fn).restype = ctypes.c_int
+        if _LIB.p2pt_max_rows() != MAX_ROWS:
+            raise RuntimeError(f"MAX_ROWS = {MAX_ROWS}, but {path} was built for {_LIB.p2pt_max_rows()} rows")
     return _LIB
 
 
-MAX_ROWS = 64  # token rows per fused step (decode_fused.hip kMaxM)
+MAX_ROWS = 64  # token rows per fused step; lib() checks it against decode_fused.hip's kMaxM
+
+
+def step_plan(dims: LlamaDims, B: int, emit_rows: int = 0) -> StepPlan:
+    """What ``p2pt_llama_decode`` launches for B rows: the kernel variant, grid and partial counts of every
+    stage, from the library's own planning function (host only: needs the library, not a GPU)."""
+    plan = StepPlan()
+    if lib().p2pt_llama_plan(ctypes.byref(dims), B, emit_rows, ctypes.byref(plan)) != 0:
+        raise ValueError("dims or row count not supported by the fused decode kernels")
+    return plan
+
+
+def attn_span(length: int, slots: int) -> int:
+    """Tokens per span slot of ``k_attn`` for a row of ``length`` tokens on ``slots`` slots (host only)."""
+    return lib().p2pt_attn_span(length, slots)
 
 
 def loaded_path() -> str:

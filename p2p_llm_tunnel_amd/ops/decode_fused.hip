@@ -1,790 +1,11 @@
-// Fused Llama decode step for gfx950 (CDNA4 / MI355X).
-//
-// The unfused step (kernels.hip + hipBLASLt) is ~50 kernels per token for a
-// 4-layer model; at decode batch sizes every one of them is a few-µs latency
-// chain (dispatch, one HBM round trip, write back) and the step is bound by
-// kernel count, not bytes. This file rebuilds the step as 5 kernels per layer
-// plus 3, the GEMMs weight-streaming MFMA kernels with their neighbours fused in:
-//
-//   k_embed              token gather -> residual stream, per-row sum of squares
-//   per layer:
-//     k_skinny<ROPE>     RMSNorm (attn_norm) -> QKV GEMM -> RoPE on q/k,
-//                        q to the attention buffer, k/v appended to the cache
-//     k_attn             GQA flash-decoding split-K; the last split to finish
-//                        for a (sequence, KV head) merges the partials in-kernel
-//     k_skinny<RESID>    O projection -> residual add -> per-row sum-of-squares
-//                        partials for the next norm
-//     k_skinny<SILU>     RMSNorm (ffn_norm) -> gate/up GEMM -> SwiGLU
-//     k_skinny<RESID>    down projection -> residual add -> sum-of-squares
-//   k_skinny<ARGMAX>     RMSNorm (final norm) -> LM head -> logits and
-//                        per-block greedy winners
-//   k_argmax_merge       one block per row merges the winners
-//
-// Skinny GEMM (M <= 64 tokens): Y[M,N] = A[M,K] * W[N,K]^T on
-// v_mfma_f32_16x16x32_bf16. A workgroup owns 16*TN output columns of one
-// 16-row tile (blockIdx.y; prefill-heavy steps carry up to 4) and splits K
-// over its NW waves; each lane streams its weight rows with 16-byte loads
-// straight into MFMA B fragments (no LDS staging: every weight byte is used
-// exactly once, by exactly one lane), the K-split partials are summed through
-// LDS and wave 0 runs the epilogue. RMSNorm is folded away: its weight g is
-// multiplied into the columns of the following projection once at load time
-// (W'[n][k] = W[n][k] g[k]), and the per-row 1/rms factors out of the dot
-// product, so the GEMM streams the raw residual and the epilogue scales the
-// accumulator. 1/rms comes from per-block partial sums of squares written by
-// the residual producer (deterministic: fixed order, no float atomics).
-// The attention splits merge in-kernel through write-through stores and an
-// arrival ticket, never an L2 write-back fence. QKV and gate/up weights have
-// their rows interleaved in pairs (RoPE partners; gate_j/up_j) so that one
-// 16-column tile holds both members of every pair (lanes c, c^1).
-//
-// Numerics: GEMM outputs, the residual and the attention output are rounded
-// to bf16 where the unfused path rounds them; the normed activation is not
-// materialised (rounding differs at the bf16-ulp level); fp32 accumulation.
-#include "bf16_common.h"
-
-#include <algorithm>
+// Host side of the fused Llama decode step for gfx950 (CDNA4 / MI355X): which
+// kernel variant runs on which grid (plan_step, a pure function), the
+// workspace, the launches and the C entry points. The kernels and the design
+// notes are in decode_fused_kernels.h.
+#include "decode_fused_kernels.h"
 
 namespace {
 
-using namespace p2pt_gpu;
-
-constexpr int kMaxM = 64;  // token rows per step: up to 4 MFMA row tiles (blockIdx.y)
-
-typedef short frag8 __attribute__((ext_vector_type(8)));
-typedef float frag4 __attribute__((ext_vector_type(4)));
-
-enum Epi : int { EPI_STORE = 0, EPI_ROPE = 1, EPI_SILU = 2, EPI_RESID = 3, EPI_ARGMAX = 4 };
-
-struct GemmArgs {
-  const uint16_t* x;  // A [M][K]
-  const uint16_t* w;  // W [N][K]; for a normed input, W[n][k] * g[k] folded in
-  int M, N, K;
-  // RMSNorm of A's rows (ss_part == nullptr: A used as is). The norm weight g
-  // is folded into W offline, so only the per-row 1/rms remains, and that
-  // factors out of the dot product: it scales the accumulator in the epilogue.
-  const float* ss_part;  // [ss_parts][16] partial row sums of squares
-  int ss_parts;
-  float eps;
-  // epilogue
-  uint16_t* out;   // STORE/ARGMAX: [M][N] logits; SILU: [M][N/2]; RESID: residual [M][N], in place
-  float* ss_out;   // RESID: [gridDim.x][16]
-  const int* pos;   // ROPE: cache position of each row
-  const int* slot;  // ROPE: cache slot of each row (nullptr: row m -> slot m)
-  int nslots;
-  uint16_t* q_out;
-  uint16_t* kc;
-  uint16_t* vc;
-  int H, Hkv, D, Smax;
-  float log2_theta;
-  float* am_val;  // ARGMAX: [gridDim.x][16]
-  int* am_idx;
-  // K parts (kpl = log2 P, 0: off; TN = 1, M * P <= 16). A subtile then holds
-  // 16 / P output columns instead of 16, so a small-N projection lands on P
-  // times the workgroups and its weight stream spreads over every CU (one CU
-  // streams ~10 B/cycle; a 2048-wide projection in 16-column tiles reaches
-  // only 128 of the 256 CUs). Lanes past the tile width take the other K
-  // parts of the same columns, and MFMA rows m * P + p carry activation row
-  // m's K part p, so every lane streams unique weight bytes. The diagonal
-  // blocks of the 16 x 16 accumulator are summed in the epilogue. It needs
-  // spare MFMA rows: a decode step of <= 16 / P tokens.
-  int kpl;
-};
-
-// log2 of the output columns per 16-lane subtile: 16, 8 or 4 for 1, 2 or 4 K parts.
-__host__ __device__ __forceinline__ int tile_cwl(int kpl) { return 4 - kpl; }
-
-__device__ __forceinline__ frag8 as_frag(const uint4& v) { return __builtin_bit_cast(frag8, v); }
-
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-// v_dot2_f32_bf16: c + a.lo * b.lo + a.hi * b.hi, products and sum in fp32.
-__device__ __forceinline__ float dot2_bf16(uint32_t a, uint32_t b, float c) {
-  return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, a), __builtin_bit_cast(bf16x2_t, b), c, false);
-}
-
-// Cross-workgroup hand-off without L2 write-back/invalidate fences: payload
-// stores are agent-scope relaxed atomics (write-through, `sc1`), drained with
-// s_waitcnt before the arrival ticket; the last arriver reads them back with
-// agent-scope loads that bypass stale cache lines (MI355X_MICROARCH handoff-flag).
-template <typename T>
-__device__ __forceinline__ void st_wt(T* p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-template <typename T>
-__device__ __forceinline__ T ld_wt(const T* p) {
-  return __hip_atomic_load(const_cast<T*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ __forceinline__ void drain_stores() {
-  __atomic_signal_fence(__ATOMIC_SEQ_CST);
-  __builtin_amdgcn_s_waitcnt(0);
-  __atomic_signal_fence(__ATOMIC_SEQ_CST);
-}
-__device__ __forceinline__ unsigned arrive(unsigned* ctr) {
-  return __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// Output column of lane column c (0..15) in subtile t of block bx, for
-// subtiles of 2^cwl columns (lanes past 2^cwl: the same columns' other K parts).
-template <int TN>
-__device__ __forceinline__ int tile_col(int bx, int t, int c, int cwl) {
-  return ((bx * TN + t) << cwl) + (c & ((1 << cwl) - 1));
-}
-
-// Operand loads go through buffer descriptors (wave-uniform base and size
-// from the kernel arguments): a lane whose byte offset lies past the buffer
-// gets zeros from the range check without a memory access. Rows past M and
-// k-steps past a wave's share use that (kOob), so a batch is branch-free and a
-// decode step at batch 1 fetches its one activation row once per k-step
-// instead of for all 16 MFMA rows.
-constexpr uint32_t kOob = 0x80000000u;  // host keeps every operand below 2 GiB
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* p, uint32_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ uint4 buf_ld16(__amdgpu_buffer_rsrc_t r, uint32_t off) {
-  return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
-}
-
-// One batch of up to UM consecutive 32-wide k-steps [s, min(s + UM, s1)):
-// every load of the batch is issued before any of it is used.
-template <int UM, int TN>
-struct Batch {
-  uint4 b[UM][TN];
-  uint4 a[UM];
-};
-
-template <int UM, int TN>
-__device__ __forceinline__ void load_batch(Batch<UM, TN>& bt, __amdgpu_buffer_rsrc_t ra, uint32_t xoff,
-                                           __amdgpu_buffer_rsrc_t rw, const uint32_t (&woff)[TN], int s, int s1) {
-#pragma unroll
-  for (int u = 0; u < UM; u++) {
-    const bool in = s + u < s1;
-    const uint32_t su = uint32_t(s + u) * 64u;  // bytes per 32-wide k-step
-#pragma unroll
-    for (int t = 0; t < TN; t++) bt.b[u][t] = buf_ld16(rw, in ? woff[t] + su : kOob);
-    bt.a[u] = buf_ld16(ra, in ? xoff + su : kOob);
-  }
-}
-
-template <int UM, int TN>
-__device__ __forceinline__ void mma_apply(frag4 (&acc)[TN], const Batch<UM, TN>& bt) {
-#pragma unroll
-  for (int u = 0; u < UM; u++)
-#pragma unroll
-    for (int t = 0; t < TN; t++)
-      acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(bt.a[u]), as_frag(bt.b[u][t]), acc[t], 0, 0, 0);
-}
-
-// The wave's k-steps [s0, s1), one batch at a time.
-template <int UM, int TN>
-__device__ __forceinline__ void mma_stream(frag4 (&acc)[TN], __amdgpu_buffer_rsrc_t ra, uint32_t xoff,
-                                           __amdgpu_buffer_rsrc_t rw, const uint32_t (&woff)[TN], int s0, int s1) {
-  for (int s = s0; s < s1; s += UM) {
-    Batch<UM, TN> p;
-    load_batch<UM, TN>(p, ra, xoff, rw, woff, s, s1);
-    // Keep every load of the batch ahead of the first MFMA: left alone, the
-    // scheduler interleaves them and the batch pays several memory latencies.
-    __builtin_amdgcn_sched_barrier(0);
-    mma_apply<UM, TN>(acc, p);
-  }
-}
-
-// Skinny GEMM + fused epilogue. NW waves split K; TN subtiles of 2^cwl
-// columns per block; UM k-steps per load batch (host: >= each wave's share
-// when possible). Steps of more than 16 rows put each 16-row tile on its own
-// workgroup (blockIdx.y). ROPE and SILU take weights whose rows are
-// interleaved in pairs (RoPE partners d, d + D/2 of a head; gate_j, up_j), so
-// a pair sits in lanes c, c^1.
-template <int NW, int TN, int EPI, int UM>
-__global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
-  __shared__ float red[NW][TN][4][kWave];
-  __shared__ float red_ss[NW][kWave];
-  // The wave index is uniform: held in an SGPR, the k-step bounds and loop
-  // counter derived from it stay out of the VGPR budget.
-  const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int m0 = blockIdx.y << 4;  // first row of this workgroup's 16-row tile
-  const int bx = blockIdx.x;       // column tile
-  const int cwl = tile_cwl(a.kpl);
-  const bool norm = a.ss_part != nullptr;
-
-  // Row sums of squares for the folded RMSNorm, spread over every wave (lane:
-  // row lane & 15, partials (lane >> 4) + 4 * wave + 4 * NW * i): up to 8
-  // loads per lane issued ahead of the weight stream and summed only after
-  // it, so they never stall it; combined through LDS before the epilogue.
-  constexpr int kSsRegs = 8;
-  float ssv[kSsRegs];
-  const int ss_p0 = (lane >> 4) + 4 * wv;
-  if (norm) {
-#pragma unroll
-    for (int i = 0; i < kSsRegs; i++) {
-      const int p = ss_p0 + 4 * NW * i;
-      ssv[i] = p < a.ss_parts ? a.ss_part[p * kMaxM + m0 + (lane & 15)] : 0.f;
-    }
-  }
-
-  // A fragment: row lane & 15, k = 32*s + 8*(lane>>4) + j; B fragment: W row n, same k.
-  // The K steps are split evenly over the NW waves.
-  const int kparts = 1 << a.kpl, Kp = a.K >> a.kpl;  // Kp: K elements per part
-  const int m_a = (lane & 15) >> a.kpl;              // activation row of this lane's MFMA row
-  const int p_a = (lane & 15) & (kparts - 1);        // ... and the K part it carries
-  const bool a_ok = m0 + m_a < a.M;
-  const int kq = (lane >> 4) << 3;
-  const int S = Kp >> 5;
-  const int s0 = wv * S / NW, s1 = (wv + 1) * S / NW;
-  // Byte offsets of this lane's A row and weight rows at k-step 0; rows past
-  // M read as zeros (kOob).
-  const __amdgpu_buffer_rsrc_t ra = rsrc(a.x, uint32_t(a.M) * uint32_t(a.K) * 2u);
-  const __amdgpu_buffer_rsrc_t rw = rsrc(a.w, uint32_t(a.N) * uint32_t(a.K) * 2u);
-  const uint32_t xoff = a_ok ? (uint32_t(m0 + m_a) * uint32_t(a.K) + uint32_t(p_a * Kp + kq)) * 2u : kOob;
-  const int p_b = (lane & 15) >> cwl;  // K part of this lane's weight column
-  uint32_t woff[TN];
-#pragma unroll
-  for (int t = 0; t < TN; t++)
-    woff[t] = (uint32_t(tile_col<TN>(bx, t, lane & 15, cwl)) * uint32_t(a.K) + uint32_t(p_b * Kp + kq)) * 2u;
-
-  // C layout: row m = m0 + 4*(lane>>4) + r, column = tile_col(.., lane & 15).
-  const int lrow0 = (lane >> 4) << 2, mrow0 = m0 + lrow0;
-  const int c = lane & 15;
-  const bool col_ok = c < (1 << cwl);  // lanes past the tile width carry the other K parts
-
-  // RESID: the residual values this lane's epilogue updates, loaded by wave 0
-  // ahead of the weight stream (they do not depend on it) instead of after
-  // the reduction, which would add a dependent memory round trip.
-  float rprev[EPI == EPI_RESID ? TN : 1][4];
-  if constexpr (EPI == EPI_RESID) {
-    if (wv == 0) {
-#pragma unroll
-      for (int t = 0; t < TN; t++)
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-          const int m = min(mrow0 + r, a.M - 1);
-          rprev[t][r] = bf2f(a.out[size_t(m) * a.N + tile_col<TN>(bx, t, c, cwl)]);
-        }
-    }
-  }
-
-  frag4 acc[TN];
-#pragma unroll
-  for (int t = 0; t < TN; t++) acc[t] = frag4{0.f, 0.f, 0.f, 0.f};
-  mma_stream<UM, TN>(acc, ra, xoff, rw, woff, s0, s1);
-
-  if (norm) {
-    float ssum = 0.f;
-#pragma unroll
-    for (int i = 0; i < kSsRegs; i++) ssum += ssv[i];
-    for (int p = ss_p0 + 4 * NW * kSsRegs; p < a.ss_parts; p += 4 * NW) ssum += a.ss_part[p * kMaxM + m0 + (lane & 15)];
-    red_ss[wv][lane] = ssum;
-  }
-  // K-split reduction through LDS (lane-contiguous: conflict-free).
-#pragma unroll
-  for (int t = 0; t < TN; t++)
-#pragma unroll
-    for (int r = 0; r < 4; r++) red[wv][t][r][lane] = acc[t][r];
-  __syncthreads();
-  if (wv != 0) return;
-  float v[TN][4];
-#pragma unroll
-  for (int t = 0; t < TN; t++)
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      float sum = 0.f;
-#pragma unroll
-      for (int w = 0; w < NW; w++) sum += red[w][t][r][lane];
-      v[t][r] = sum;
-    }
-
-  if (a.kpl) {
-    // Sum the diagonal blocks: output (row m, column c < 2^cwl) is
-    // sum_p C[m * P + p][c + p * 2^cwl]. Wave 0 alone from here on: the
-    // reduction buffer (its own reads are done) holds C [16][17].
-    float* cbuf = &red[0][0][0][0];
-#pragma unroll
-    for (int r = 0; r < 4; r++) cbuf[(lrow0 + r) * 17 + c] = v[0][r];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      const int row = lrow0 + r;
-      float sum = 0.f;
-      if (row < (16 >> a.kpl) && col_ok)
-        for (int p = 0; p < kparts; p++) sum += cbuf[(row * kparts + p) * 17 + c + (p << cwl)];
-      v[0][r] = sum;
-    }
-  }
-
-  if (norm) {
-    float ssum = 0.f;
-#pragma unroll
-    for (int w = 0; w < NW; w++) ssum += red_ss[w][lane];
-    ssum = xor32_sum(xor16_sum(ssum));
-    const float rs_row = rsqrtf(ssum * (1.f / float(a.K)) + a.eps);  // for row m0 + (lane & 15)
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      const float rs = __shfl(rs_row, lrow0 + r, kWave);
-#pragma unroll
-      for (int t = 0; t < TN; t++) v[t][r] *= rs;
-    }
-  }
-
-  if constexpr (EPI == EPI_STORE || EPI == EPI_ARGMAX) {
-    // Logits (bf16) and, for ARGMAX, this block's per-row winner (first index on ties).
-    float best[4];
-    int bi[4];
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      best[r] = -INFINITY;
-      bi[r] = 0x7fffffff;
-    }
-#pragma unroll
-    for (int t = 0; t < TN; t++) {
-      const int n = tile_col<TN>(bx, t, c, cwl);
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        const int m = mrow0 + r;
-        const float lv = bf_round(v[t][r]);
-        if (m < a.M && col_ok) a.out[size_t(m) * a.N + n] = uint16_t(f2bf_bits(lv));
-        if (lv > best[r] || (lv == best[r] && n < bi[r])) {
-          best[r] = lv;
-          bi[r] = n;
-        }
-      }
-    }
-    if constexpr (EPI == EPI_ARGMAX) {
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        row16_argmax(best[r], bi[r]);
-        if (c == 0) {
-          a.am_val[bx * kMaxM + mrow0 + r] = best[r];
-          a.am_idx[bx * kMaxM + mrow0 + r] = bi[r];
-        }
-      }
-    }
-  } else if constexpr (EPI == EPI_SILU) {
-    // Interleaved rows: even lane = gate_j, odd lane = up_j, j = column / 2.
-    const int n = tile_col<TN>(bx, 0, c, cwl);
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      const float mine = bf_round(v[0][r]);
-      const float other = dpp<kDppXor1>(mine);
-      if ((c & 1) || !col_ok || mrow0 + r >= a.M) continue;
-      a.out[size_t(mrow0 + r) * (a.N >> 1) + (n >> 1)] = uint16_t(f2bf_bits(mine / (1.f + __expf(-mine)) * other));
-    }
-  } else if constexpr (EPI == EPI_ROPE) {
-    // Interleaved rows within each head: column 2i = dim i, 2i+1 = dim i + D/2.
-    const int half = a.D >> 1;
-    const int col = tile_col<TN>(bx, 0, c, cwl);
-    const int head = col / a.D, i = (col % a.D) >> 1;
-    const bool second = c & 1;
-    const float inv_freq = exp2f(-a.log2_theta * (2.f * i) / a.D);
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      const int m = mrow0 + r;
-      const float mine = bf_round(v[0][r]);
-      const float other = dpp<kDppXor1>(mine);
-      if (m >= a.M || !col_ok) continue;
-      // Host validates; clamped anyway so a bad index can never write outside the cache.
-      const int p = min(max(a.pos[m], 0), a.Smax - 1);
-      const int sl = a.slot ? min(max(a.slot[m], 0), a.nslots - 1) : m;
-      const int d = i + (second ? half : 0);
-      if (head < a.H + a.Hkv) {
-        float sn, cs;
-        sincosf(float(p) * inv_freq, &sn, &cs);
-        const float x1 = second ? other : mine, x2 = second ? mine : other;
-        const float o = second ? x2 * cs + x1 * sn : x1 * cs - x2 * sn;
-        uint16_t* dst = head < a.H ? a.q_out + (size_t(m) * a.H + head) * a.D
-                                   : a.kc + ((size_t(sl) * a.Smax + p) * a.Hkv + (head - a.H)) * a.D;
-        dst[d] = uint16_t(f2bf_bits(o));
-      } else {
-        a.vc[((size_t(sl) * a.Smax + p) * a.Hkv + (head - a.H - a.Hkv)) * a.D + d] = uint16_t(f2bf_bits(mine));
-      }
-    }
-  } else if constexpr (EPI == EPI_RESID) {
-    float sq[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int t = 0; t < TN; t++) {
-      const int n = tile_col<TN>(bx, t, c, cwl);
-#pragma unroll
-      for (int r = 0; r < 4; r++) {
-        const int m = mrow0 + r;
-        if (m >= a.M || !col_ok) continue;
-        const float nv = bf_round(rprev[t][r] + bf_round(v[t][r]));
-        a.out[size_t(m) * a.N + n] = uint16_t(f2bf_bits(nv));
-        sq[r] += nv * nv;
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-      sq[r] = row16_sum(sq[r]);
-      if (c == 0) a.ss_out[bx * kMaxM + mrow0 + r] = sq[r];
-    }
-  }
-}
-
-// Greedy sampling, second stage: one block per row merges the LM-head blocks'
-// winners (first index on ties).
-__global__ __launch_bounds__(256) void k_argmax_merge(const float* __restrict__ am_val, const int* __restrict__ am_idx,
-                                                      int parts, int64_t* __restrict__ ids) {
-  const int m = blockIdx.x;
-  float b = -INFINITY;
-  int i = 0x7fffffff;
-  for (int p0 = threadIdx.x; p0 < parts; p0 += 8 * 256) {
-    float pv[8];
-    int pi[8];
-#pragma unroll
-    for (int j = 0; j < 8; j++) {  // 8 loads in flight per thread
-      const int p = p0 + j * 256;
-      pv[j] = p < parts ? am_val[p * kMaxM + m] : -INFINITY;
-      pi[j] = p < parts ? am_idx[p * kMaxM + m] : 0x7fffffff;
-    }
-#pragma unroll
-    for (int j = 0; j < 8; j++)
-      if (pv[j] > b || (pv[j] == b && pi[j] < i)) {
-        b = pv[j];
-        i = pi[j];
-      }
-  }
-  wave_argmax(b, i);
-  __shared__ float sb[4];
-  __shared__ int si[4];
-  if ((threadIdx.x & 63) == 0) {
-    sb[threadIdx.x >> 6] = b;
-    si[threadIdx.x >> 6] = i;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < 4; w++)
-      if (sb[w] > b || (sb[w] == b && si[w] < i)) {
-        b = sb[w];
-        i = si[w];
-      }
-    ids[m] = i;
-  }
-}
-
-// ------------------------------------------------------------ embedding gather
-// One block per token: residual row = embed[token]; ss_out[0][b] = sum of squares.
-__global__ __launch_bounds__(256) void k_embed(const uint16_t* __restrict__ embed, const int64_t* __restrict__ tok,
-                                               uint16_t* __restrict__ resid, float* __restrict__ ss_out, int dim,
-                                               int vocab) {
-  const int b = blockIdx.x;
-  int64_t t = tok[b];
-  t = t < 0 ? 0 : (t >= vocab ? vocab - 1 : t);
-  const uint4* src = reinterpret_cast<const uint4*>(embed + size_t(t) * dim);
-  uint4* dst = reinterpret_cast<uint4*>(resid + size_t(b) * dim);
-  float ss = 0.f;
-  for (int i = threadIdx.x; i < dim / 8; i += 256) {
-    const uint4 v = src[i];
-    dst[i] = v;
-    float f[8];
-    unpack8(v, f);
-#pragma unroll
-    for (int j = 0; j < 8; j++) ss += f[j] * f[j];
-  }
-  __shared__ float red[4];
-  ss = wave_sum(ss);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
-  __syncthreads();
-  if (threadIdx.x == 0) ss_out[b] = red[0] + red[1] + red[2] + red[3];
-}
-
-// ------------------------------------------------------------ attention
-// GQA flash-decoding with a fixed grid of (span slot, row b, KV head)
-// workgroups: graph-captured steps launch the same grid whatever the context
-// length, so the grid is sized by the batch (about one round of workgroups on
-// the chip), not by the cache capacity — idle workgroups were a third of the
-// kernel at 1k tokens. Each slot covers a span of >= 64 tokens of row b; its
-// 8 waves walk the span in 32-token pieces with an online softmax.
-// A piece is loaded straight into registers with 16-byte loads whose lanes
-// tile whole K/V rows (D/8 lanes per row: every instruction reads full cache
-// lines); nothing is staged through LDS. A lane keeps one 8-dim group of every
-// query head of the KV head (K/V are read once per GQA group), computes its
-// dot products with v_dot2_f32_bf16 and finishes them with in-row DPP sums,
-// and ends up holding the softmax weights of exactly the tokens whose V it
-// loaded: P.V needs no data exchange until the final cross-row sum. Scores and
-// P.V are fp32 VALU: with G <= 8 query rows an MFMA tile would be >= half
-// padding; the kernel is bound by the K/V stream and latency.
-// The 8 waves of a slot merge through LDS; only spans split over several
-// slots publish a partial (write-through + arrival ticket) that the last slot
-// to finish merges, its waves taking different heads.
-// Row b reads cache slot slot[b] (rows may share a slot: chunked prefill) and
-// attends to positions 0..pos[b]; the output is bf16 [B][H*D].
-constexpr int kAttnSlotCap = 16;  // span slots per (row, KV head) at most
-// Workgroups one launch aims at: one 512-thread, 234-VGPR workgroup per CU.
-// More slots per row are slower: b16 0.522 / 0.567 / 0.597 / 0.645 ms at
-// 256 / 512 / 768 / 1024 (profiles/r03/decode/attn_grid_sweep_head.log).
-constexpr int kAttnTargetWgs = 256;
-// Smallest token span of one workgroup (a multiple of the 32-token wave
-// piece). 64 (two busy waves) puts a short context on 4x the workgroups of
-// 256 (one piece per wave): at batch 1 and 1k tokens the decode step went
-// 396 -> 380 us on MI355X, unchanged at batch 16.
-constexpr int kAttnMinSpan = 64;
-
-template <int D, int G>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1))) void k_attn(
-    const uint16_t* __restrict__ q, const uint16_t* __restrict__ kc, const uint16_t* __restrict__ vc,
-    const int* __restrict__ pos, const int* __restrict__ slot, int nslots, float* __restrict__ part_o,
-    float* __restrict__ part_ml, unsigned* __restrict__ counters, uint16_t* __restrict__ out, int H, int Hkv, int Smax,
-    int nsplit, float scale) {
-  constexpr int NWV = 8;
-  constexpr int TOK = 32;  // tokens per wave piece
-  constexpr int DPL = D / kWave;  // merges: dims per lane
-  constexpr int MAXC = 16;        // partials merged per load batch
-  constexpr int LPR = D / 8, RPI = kWave / LPR, NI = TOK / RPI;
-  __shared__ __attribute__((aligned(16))) float pacc[NWV][G][D];
-  __shared__ float pml[NWV][G][2];
-  __shared__ unsigned s_ticket;
-
-  const int b = blockIdx.y / Hkv, kvh = blockIdx.y % Hkv;
-  const int len = min(max(pos[b], 0), Smax - 1) + 1;
-  int span = (len + gridDim.x - 1) / gridDim.x;
-  span = max(kAttnMinSpan, (span + TOK - 1) / TOK * TOK);
-  const int nact = (len + span - 1) / span;  // slots with tokens
-  const int sl = blockIdx.x;
-  if (sl >= nact) return;
-  const int s0 = sl * span, s1 = min(len, s0 + span);
-  const int sb = slot ? min(max(slot[b], 0), nslots - 1) : b;
-  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int dg = lane % LPR, ri = lane / LPR;
-
-  const size_t tok_stride = size_t(Hkv) * D;
-  const uint16_t* kbase = kc + size_t(sb) * Smax * tok_stride + size_t(kvh) * D + 8 * dg;
-  const uint16_t* vbase = vc + size_t(sb) * Smax * tok_stride + size_t(kvh) * D + 8 * dg;
-  // This lane's 8 query dims of every head as bf16 pairs (v_dot2 operands).
-  uint4 qpk[G];
-  {
-    const uint16_t* qp = q + (size_t(b) * H + size_t(kvh) * G) * D + 8 * dg;
-#pragma unroll
-    for (int g = 0; g < G; g++) qpk[g] = *reinterpret_cast<const uint4*>(qp + size_t(g) * D);
-  }
-
-  // Running state over this wave's pieces. m is wave-uniform per head; l and
-  // acc hold this lane's tokens only and are summed across rows at the end.
-  float mg[G], lg[G], acc[G][8];
-#pragma unroll
-  for (int g = 0; g < G; g++) {
-    mg[g] = -INFINITY;
-    lg[g] = 0.f;
-#pragma unroll
-    for (int k = 0; k < 8; k++) acc[g][k] = 0.f;
-  }
-  for (int p0 = s0 + wv * TOK; p0 < s1; p0 += NWV * TOK) {
-    const int ntok = min(TOK, s1 - p0);
-    // Issue the piece (lanes past the end re-read the last valid row).
-    uint4 kr[NI], vr[NI];
-#pragma unroll
-    for (int j = 0; j < NI; j++)
-      kr[j] = *reinterpret_cast<const uint4*>(kbase + size_t(p0 + min(j * RPI + ri, ntok - 1)) * tok_stride);
-#pragma unroll
-    for (int j = 0; j < NI; j++)
-      vr[j] = *reinterpret_cast<const uint4*>(vbase + size_t(p0 + min(j * RPI + ri, ntok - 1)) * tok_stride);
-    // Scores: lane (ri, dg) ends with token j*RPI + ri's score for every head.
-    float sc[G][NI];
-#pragma unroll
-    for (int j = 0; j < NI; j++) {
-#pragma unroll
-      for (int g = 0; g < G; g++) {
-        float d = 0.f;
-        d = dot2_bf16(qpk[g].x, kr[j].x, d);
-        d = dot2_bf16(qpk[g].y, kr[j].y, d);
-        d = dot2_bf16(qpk[g].z, kr[j].z, d);
-        d = dot2_bf16(qpk[g].w, kr[j].w, d);
-        d = (LPR == 16 ? row16_sum(d) : row8_sum(d)) * scale;
-        sc[g][j] = (j * RPI + ri < ntok) ? d : -INFINITY;
-      }
-    }
-#pragma unroll
-    for (int g = 0; g < G; g++) {
-      float pm = -INFINITY;
-#pragma unroll
-      for (int j = 0; j < NI; j++) pm = fmaxf(pm, sc[g][j]);
-      if constexpr (LPR == 8) pm = xor8_max(pm);
-      pm = xor32_max(xor16_max(pm));
-      const float mnew = fmaxf(mg[g], pm);
-      const float corr = __expf(mg[g] - mnew);  // 0 on the first piece (mg = -inf)
-      mg[g] = mnew;
-      float ls = 0.f;
-#pragma unroll
-      for (int j = 0; j < NI; j++) {
-        sc[g][j] = __expf(sc[g][j] - mnew);  // now p (0 for masked tokens)
-        ls += sc[g][j];
-      }
-      lg[g] = lg[g] * corr + ls;
-#pragma unroll
-      for (int k = 0; k < 8; k++) acc[g][k] *= corr;
-    }
-    // P.V: the lane's own tokens times its 8 dims.
-#pragma unroll
-    for (int j = 0; j < NI; j++) {
-      float f[8];
-      unpack8(vr[j], f);
-#pragma unroll
-      for (int g = 0; g < G; g++)
-#pragma unroll
-        for (int k = 0; k < 8; k++) acc[g][k] += sc[g][j] * f[k];
-    }
-  }
-  // Sum across rows (lanes with the same dim group).
-#pragma unroll
-  for (int g = 0; g < G; g++) {
-    float l = lg[g];
-    if constexpr (LPR == 8) l = xor8_sum(l);
-    lg[g] = xor32_sum(xor16_sum(l));
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-      float v = acc[g][k];
-      if constexpr (LPR == 8) v = xor8_sum(v);
-      acc[g][k] = xor32_sum(xor16_sum(v));
-    }
-  }
-  // Publish this wave to the workgroup (waves without pieces: m = -inf, l = 0).
-  if (ri == 0) {
-#pragma unroll
-    for (int g = 0; g < G; g++) {
-      *reinterpret_cast<float4*>(&pacc[wv][g][8 * dg]) = make_float4(acc[g][0], acc[g][1], acc[g][2], acc[g][3]);
-      *reinterpret_cast<float4*>(&pacc[wv][g][8 * dg + 4]) = make_float4(acc[g][4], acc[g][5], acc[g][6], acc[g][7]);
-    }
-  }
-  if (lane == 0) {
-#pragma unroll
-    for (int g = 0; g < G; g++) {
-      pml[wv][g][0] = mg[g];
-      pml[wv][g][1] = lg[g];
-    }
-  }
-  __syncthreads();
-
-  // Slot merge through LDS: wave w takes heads w, w + 8, ...
-  const size_t hb0 = size_t(b) * H + size_t(kvh) * G;
-  for (int g = wv; g < G; g += NWV) {
-    float M = -INFINITY;
-#pragma unroll
-    for (int w = 0; w < NWV; w++) M = fmaxf(M, pml[w][g][0]);
-    float L = 0.f, o[DPL];
-#pragma unroll
-    for (int k = 0; k < DPL; k++) o[k] = 0.f;
-#pragma unroll
-    for (int w = 0; w < NWV; w++) {
-      const float ww = pml[w][g][1] > 0.f ? __expf(pml[w][g][0] - M) : 0.f;
-      L += pml[w][g][1] * ww;
-#pragma unroll
-      for (int k = 0; k < DPL; k++) o[k] += ww * pacc[w][g][lane + k * kWave];
-    }
-    const size_t hb = hb0 + g;
-    if (nact == 1) {
-      const float inv = 1.f / L;
-#pragma unroll
-      for (int k = 0; k < DPL; k++) out[hb * D + lane + k * kWave] = uint16_t(f2bf_bits(o[k] * inv));
-    } else {
-      float* po = part_o + (hb * nsplit + sl) * D;
-#pragma unroll
-      for (int k = 0; k < DPL; k++) st_wt(po + lane + k * kWave, o[k]);
-      if (lane == 0) {
-        st_wt(part_ml + (hb * nsplit + sl) * 2 + 0, M);
-        st_wt(part_ml + (hb * nsplit + sl) * 2 + 1, L);
-      }
-    }
-  }
-  if (nact == 1) return;
-  drain_stores();
-  __syncthreads();
-  if (threadIdx.x == 0) s_ticket = arrive(&counters[blockIdx.y]);
-  __syncthreads();
-  if (s_ticket != unsigned(nact - 1)) return;
-
-  // Last slot: merge the slot partials, heads spread over the waves. Each
-  // batch of up to MAXC partials (maxima, sums and vectors together) is loaded
-  // before any of it is used and folded in with a running maximum, so a merge
-  // of <= MAXC slots is one memory round trip (a separate pass for the global
-  // maximum first cost a second one).
-  for (int g = wv; g < G; g += NWV) {
-    const size_t hb = hb0 + g;
-    const float* ml = part_ml + hb * nsplit * 2;
-    float M = -INFINITY;
-    float L = 0.f, o[DPL];
-#pragma unroll
-    for (int k = 0; k < DPL; k++) o[k] = 0.f;
-    for (int c0 = 0; c0 < nact; c0 += MAXC) {
-      float pv[MAXC][DPL], wl[MAXC], ll[MAXC];
-#pragma unroll
-      for (int j = 0; j < MAXC; j++) {
-        const bool ok = c0 + j < nact;
-        const int c = min(c0 + j, nact - 1);
-        wl[j] = ld_wt(ml + 2 * c);
-        ll[j] = ok ? ld_wt(ml + 2 * c + 1) : 0.f;
-#pragma unroll
-        for (int k = 0; k < DPL; k++) pv[j][k] = ld_wt(part_o + (hb * nsplit + c) * D + lane + k * kWave);
-      }
-      float Mb = M;
-#pragma unroll
-      for (int j = 0; j < MAXC; j++)
-        if (ll[j] > 0.f) Mb = fmaxf(Mb, wl[j]);
-      const float rs = M == -INFINITY ? 0.f : __expf(M - Mb);  // rescale what is folded in so far
-      L *= rs;
-#pragma unroll
-      for (int k = 0; k < DPL; k++) o[k] *= rs;
-      M = Mb;
-#pragma unroll
-      for (int j = 0; j < MAXC; j++) {
-        const float ww = ll[j] > 0.f ? __expf(wl[j] - M) : 0.f;
-        L += ll[j] * ww;
-#pragma unroll
-        for (int k = 0; k < DPL; k++) o[k] += ww * pv[j][k];
-      }
-    }
-    const float inv = 1.f / L;
-#pragma unroll
-    for (int k = 0; k < DPL; k++) out[hb * D + lane + k * kWave] = uint16_t(f2bf_bits(o[k] * inv));
-  }
-  if (threadIdx.x == 0) st_wt(&counters[blockIdx.y], 0u);
-}
-
-// Partial slots per head in part_o / part_ml (k_attn's nsplit): the most span
-// slots a launch can have. k_attn writes slot sl < nact <= gridDim.x <= stride:
-// span >= ceil(len / gridDim.x), so nact = ceil(len / span) <= gridDim.x, and
-// attn_slots() never exceeds the stride.
-int attn_part_stride(int max_seq) { return std::min(kAttnSlotCap, (max_seq + kAttnMinSpan - 1) / kAttnMinSpan); }
-
-// Span slots per (row, KV head), k_attn's gridDim.x: about one round of
-// workgroups on the chip. Sized by the batch; the context enters through pos.
-int attn_slots(int B, int Hkv, int max_seq) {
-  return std::max(1, std::min(kAttnTargetWgs / std::max(1, B * Hkv), attn_part_stride(max_seq)));
-}
-
-// Measured on MI355X and rejected; the code is gone, the findings stay. This
-// file reads no environment variables: what ships is the one path below.
-//  - Split-K over workgroups (write-through slabs, arrival ticket, last
-//    arriver combines): the seam costs more than the extra workgroups win at
-//    d_model <= 2048. QKV 8.7 -> 13.5 us, O 7.4 -> 12.0, down 17.3 -> 17.3
-//    (2048-wide config, batch 8).
-//  - Narrow duplicate-column tiles (8 or 4 columns, the other lanes repeating
-//    them): O alone 5.8 -> 5.5 us at batch 1, QKV 6.1 -> 7.8; O and down at
-//    one workgroup per CU 1-4 % slower end to end. 16 everywhere is fastest.
-//  - K parts on QKV and gate/up: batch 1, QKV at 4 columns 0.360 -> 0.373 ms
-//    per step, gate/up 0.368 (8 columns) and 0.391 (4). Their grids already
-//    cover the chip. K parts stay on O and down only (0.372 -> 0.359 ms).
-//  - A 16-token attention piece (128 instead of 234 VGPRs, two workgroups per
-//    CU): small, ctx 1024, b1 0.358 -> 0.365 ms, b16 0.522 -> 0.531, b64
-//    1.125 -> 1.134 (profiles/r03/decode/attn_tok_ab_head.log).
-//  - 8-step load batches: at most 4 k-steps per batch keeps more waves
-//    resident. Batch 1 396 -> 389 us per step, batch 16 unchanged.
-//  - 16-wave workgroups: 8 beats 16 by 20-30 % at K = 5632 (down 9.4 ->
-//    10.5 us); the reduction and barrier cost more than the loads in flight.
-//  - Non-temporal weight loads: 1.75x slower on the 4-layer config, 5 % slower
-//    on the 0.85 GB config (profiles/r02/decode/decode_sweep_s9.log). A decode
-//    step replays the same weights, and the 256 MB MALL keeps them resident.
-//  - One workgroup sharing each weight fragment across the four tiles of a
-//    64-row step: small, 64 rows 1.19 -> 1.26 ms; 16 streams 3.0 K -> 2.7 K
-//    tok/s (profiles/r02/decode/decode_sweep_s10_rowtiles.log). The load
-//    path, not HBM, becomes the limit.
-//  - The argmax merge folded into the LM head's last block: 0.359 -> 0.366 ms
-//    at batch 1, 0.522 -> 0.554 at 16. 1,000 arrivals on one counter cost more
-//    than the launch.
-//  - A persistent O -> gate/up -> down kernel (in-order tile queue,
-//    write-through hand-offs): small b1 0.358 -> 0.61-1.09 ms in every variant
-//    (profiles/r03/decode_block/).
-//  - A two-deep load-batch pipeline (every projection +0.5-1.8 us) and one
-//    workgroup per CU forced through padded LDS (QKV 5.9 -> 9.9 us)
-//    (profiles/r02/decode/decode_sweep_s8.log).
-
-// ------------------------------------------------------------ host side
 struct LlamaDims {
   int vocab, dim, n_layers, H, Hkv, D, ffn, max_seq, max_batch;
   float eps, theta;
@@ -792,7 +13,87 @@ struct LlamaDims {
 
 constexpr int kTnResid = 1, kTnStore = 2;  // LM head: two 16-column subtiles per block
 constexpr int kCUs = 256;  // MI355X compute units: K-parts tiling aims at one workgroup per CU
+constexpr int kMaxKpl = 2;  // at most 4 K parts: 4-column subtiles
 
+// ------------------------------------------------------------ the plan
+// Everything a launch depends on besides pointers, as plain ints (mirrored with
+// ctypes in ops/__init__.py). A consumer's ss_in is its producer's grid_x.
+struct GemmPlan {
+  int epi, nw, tn, um, kpl;  // k_skinny<nw, tn, epi, um>, 1 << kpl K parts
+  int grid_x, grid_y;
+  int ss_in;  // sum-of-squares partials read (0: no norm)
+  int M, N, K;
+};
+struct AttnPlan {
+  int D, G;    // k_attn<D, G>
+  int slots;   // gridDim.x
+  int stride;  // partial slots per head in part_o / part_ml (k_attn's nsplit)
+  int grid_y;
+};
+struct StepPlan {
+  int rows, emit_rows;
+  GemmPlan qkv_first, qkv, o, gate_up, down, lm_head;  // qkv_first: layer 0 reads k_embed's one partial
+  AttnPlan attn;
+  int am_parts;  // per-row winners k_argmax_merge reads
+};
+
+// One workgroup per tn subtiles of 16 >> kpl columns of one 16-row tile.
+//  - K parts (GemmArgs::kpl), where asked for (the d_model-wide O and down
+//    projections): the widest tile (16, 8 or 4 columns) whose column tiles
+//    reach one workgroup per CU, or 4 columns if none does; none where
+//    16-column tiles already get there, the spare MFMA rows do not allow it
+//    (M * P > 16) or K does not split into P parts of whole k-steps.
+//  - Waves per workgroup, unless fixed: 4 up to 16 k-steps per workgroup, 8
+//    above. Measured on MI355X (scripts/bench_skinny.py, M = 8): 4 and 8 waves
+//    tie up to K = 2048.
+//  - Load batch um: each wave's share of k-steps, rounded up to a power of two,
+//    at most 4 (fewer registers, more resident waves).
+// A K without a whole k-step leaves nw = 0, which launch() refuses.
+GemmPlan plan_gemm(int epi, int tn, int M, int N, int K, bool k_parts = false, int fixed_nw = 0) {
+  GemmPlan p{};
+  p.epi = epi, p.tn = tn, p.M = M, p.N = N, p.K = K;
+  if (k_parts && tn == 1 && (N >> 4) < kCUs) {
+    const int kpl = std::min((N >> 3) >= kCUs ? 1 : 2, kMaxKpl);
+    if ((M << kpl) <= 16 && K % (32 << kpl) == 0) p.kpl = kpl;
+  }
+  const int steps = (K >> p.kpl) >> 5;
+  if (steps <= 0) return p;
+  p.nw = fixed_nw ? fixed_nw : steps <= 16 ? 4 : 8;
+  const int per_wave = (steps + p.nw - 1) / p.nw;
+  p.um = per_wave <= 1 ? 1 : per_wave <= 2 ? 2 : 4;
+  p.grid_x = N / (tn << tile_cwl(p.kpl));
+  p.grid_y = (M + 15) >> 4;
+  return p;
+}
+
+// 4 waves x 2 subtiles: the fastest LM-head shape measured (vocab 32000, K 2048: 22.6 vs 29.6 us).
+GemmPlan plan_lm_head(const LlamaDims& d, int rows) {
+  return plan_gemm(EPI_ARGMAX, kTnStore, rows, d.vocab, d.dim, false, 4);
+}
+
+AttnPlan plan_attn(int B, int H, int Hkv, int D, int max_seq) {
+  return {D, Hkv > 0 ? H / Hkv : 0, attn_slots(B, Hkv, max_seq), attn_part_stride(max_seq), B * Hkv};
+}
+
+StepPlan plan_step(const LlamaDims& d, int B, int emit_rows) {
+  StepPlan p{};
+  p.rows = B;
+  p.emit_rows = emit_rows <= 0 || emit_rows > B ? B : emit_rows;
+  p.qkv = plan_gemm(EPI_ROPE, 1, B, (d.H + 2 * d.Hkv) * d.D, d.dim);
+  p.attn = plan_attn(B, d.H, d.Hkv, d.D, d.max_seq);
+  p.o = plan_gemm(EPI_RESID, kTnResid, B, d.dim, d.H * d.D, true);
+  p.gate_up = plan_gemm(EPI_SILU, 1, B, 2 * d.ffn, d.dim);
+  p.down = plan_gemm(EPI_RESID, kTnResid, B, d.dim, d.ffn, true);
+  p.lm_head = plan_lm_head(d, p.emit_rows);
+  p.qkv_first = p.qkv;
+  p.qkv_first.ss_in = 1;
+  p.gate_up.ss_in = p.o.grid_x;
+  p.qkv.ss_in = p.lm_head.ss_in = p.down.grid_x;
+  p.am_parts = p.lm_head.grid_x;
+  return p;
+}
+
+// ------------------------------------------------------------ workspace
 size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
 struct Workspace {
@@ -812,7 +113,8 @@ struct WsLayout {
   size_t bytes;
 };
 
-// The one place that knows the workspace layout.
+// The one place that knows the workspace layout. The counts that depend on a
+// grid are the plan's own, at their worst case over the row count.
 WsLayout ws_layout(const LlamaDims& d) {
   WsLayout l{};
   size_t off = 0;
@@ -822,14 +124,13 @@ WsLayout ws_layout(const LlamaDims& d) {
     off += align256(count * elem);
   };
   const int nsplit = attn_part_stride(d.max_seq);
-  const int ss_parts = d.dim / (16 * kTnResid);
-  const int am_parts = d.vocab / (16 * kTnStore);
+  const int ss_parts = d.dim / (kTnResid << tile_cwl(kMaxKpl));  // a residual producer's grid_x at the most K parts
+  const int am_parts = plan_lm_head(d, kMaxM).grid_x;
   take(WS_RESID, size_t(kMaxM) * d.dim, 2);
   take(WS_Q, size_t(kMaxM) * d.H * d.D, 2);
   take(WS_ATTN, size_t(kMaxM) * d.H * d.D, 2);
   take(WS_H, size_t(kMaxM) * d.ffn, 2);
-  const int ss_narrow = 16 >> tile_cwl(2);  // K parts narrow the 16-column tiles that ss_parts counts to 4 columns
-  take(WS_SS, size_t(std::max(ss_parts, 1)) * ss_narrow * kMaxM, 4);
+  take(WS_SS, size_t(std::max(ss_parts, 1)) * kMaxM, 4);
   take(WS_PART_O, size_t(kMaxM) * d.H * nsplit * d.D, 4);
   take(WS_PART_ML, size_t(kMaxM) * d.H * nsplit * 2, 4);
   take(WS_AM_VAL, size_t(am_parts) * kMaxM, 4);
@@ -857,49 +158,94 @@ Workspace carve(const LlamaDims& d, uint8_t* base) {
   return w;
 }
 
-// Waves per workgroup for `steps` 32-wide k-steps per workgroup. Measured on
-// MI355X (scripts/bench_skinny.py, M = 8): 4 and 8 waves tie up to K = 2048.
-int pick_nw(int steps) {
-  if (steps <= 0) return 0;
-  return steps <= 16 ? 4 : 8;
+// ------------------------------------------------------------ kernel arguments
+// A stage's GemmArgs is one expression: gemm(x, w) + norm(...) + its
+// epilogue. Each helper takes every field of its group, so none stays zero by
+// omission; launch() checks that a plan with a norm got one.
+template <typename Set>
+GemmArgs operator+(GemmArgs a, Set set) {
+  set(a);
+  return a;
+}
+GemmArgs gemm(const void* x, const void* w) {  // M, N, K and kpl are the plan's: launch() fills them in
+  GemmArgs a{};
+  a.x = static_cast<const uint16_t*>(x), a.w = static_cast<const uint16_t*>(w);
+  return a;
+}
+auto norm(const float* ss, int parts, float eps) {
+  return [=](GemmArgs& a) { a.ss_part = ss, a.ss_parts = parts, a.eps = eps; };
+}
+auto store(void* out) {  // STORE, SILU
+  return [=](GemmArgs& a) { a.out = static_cast<uint16_t*>(out); };
+}
+auto rope(const LlamaDims& d, const int* pos, const int* slot, uint16_t* q, uint16_t* kc, uint16_t* vc) {
+  return [=](GemmArgs& a) {
+    a.pos = pos, a.slot = slot, a.nslots = d.max_batch, a.q_out = q, a.kc = kc, a.vc = vc;
+    a.H = d.H, a.Hkv = d.Hkv, a.D = d.D, a.Smax = d.max_seq, a.log2_theta = log2f(d.theta);
+  };
+}
+auto resid(uint16_t* r, float* ss_out) {
+  return [=](GemmArgs& a) { a.out = r, a.ss_out = ss_out; };
+}
+auto argmax(void* logits, float* am_val, int* am_idx) {
+  return [=](GemmArgs& a) { a.out = static_cast<uint16_t*>(logits), a.am_val = am_val, a.am_idx = am_idx; };
 }
 
-template <int NW, int TN, int EPI>
-hipError_t launch_nw(const GemmArgs& a, int grid, hipStream_t s) {
-  // Load batch: each wave's share of k-steps, rounded up to a power of two,
-  // at most 4 (fewer registers, more resident waves).
-  const int per_wave = (((a.K >> a.kpl) >> 5) + NW - 1) / NW;
-  const dim3 g(grid, (a.M + 15) >> 4), b(NW * 64);
-  if (per_wave <= 1)
-    hipLaunchKernelGGL((k_skinny<NW, TN, EPI, 1>), g, b, 0, s, a);
-  else if (per_wave <= 2)
-    hipLaunchKernelGGL((k_skinny<NW, TN, EPI, 2>), g, b, 0, s, a);
-  else
-    hipLaunchKernelGGL((k_skinny<NW, TN, EPI, 4>), g, b, 0, s, a);
+// ------------------------------------------------------------ launches
+template <int TN, int EPI>
+hipError_t launch_as(const GemmPlan& p, GemmArgs a, hipStream_t s) {
+  a.M = p.M, a.N = p.N, a.K = p.K, a.kpl = p.kpl;
+  const dim3 g(p.grid_x, p.grid_y), b(p.nw * 64);
+  switch (p.nw * 8 + p.um) {
+    case 8 * 8 + 1: hipLaunchKernelGGL((k_skinny<8, TN, EPI, 1>), g, b, 0, s, a); break;
+    case 8 * 8 + 2: hipLaunchKernelGGL((k_skinny<8, TN, EPI, 2>), g, b, 0, s, a); break;
+    case 8 * 8 + 4: hipLaunchKernelGGL((k_skinny<8, TN, EPI, 4>), g, b, 0, s, a); break;
+    case 4 * 8 + 1: hipLaunchKernelGGL((k_skinny<4, TN, EPI, 1>), g, b, 0, s, a); break;
+    case 4 * 8 + 2: hipLaunchKernelGGL((k_skinny<4, TN, EPI, 2>), g, b, 0, s, a); break;
+    case 4 * 8 + 4: hipLaunchKernelGGL((k_skinny<4, TN, EPI, 4>), g, b, 0, s, a); break;
+    default: return hipErrorInvalidValue;
+  }
   return hipGetLastError();
 }
 
-// K parts (GemmArgs::kpl) for an N-column, TN = 1 projection of M rows: the
-// widest tile (16, 8 or 4 columns) whose column tiles reach one workgroup per
-// CU, or 4 columns if none does; 0 where 16-column tiles already get there,
-// the spare MFMA rows do not allow it (M * P > 16) or K does not split into P
-// parts of whole k-steps. Used on the d_model-wide O and down projections.
-int pick_kparts(int N, int M, int K) {
-  if ((N >> 4) >= kCUs) return 0;
-  const int kpl = (N >> 3) >= kCUs ? 1 : 2;
-  const int P = 1 << kpl;
-  return (M * P <= 16 && K % (32 * P) == 0) ? kpl : 0;
+// The one (nw, tn, epi, um) dispatch: the 36 k_skinny instantiations.
+hipError_t launch(const GemmPlan& p, const GemmArgs& a, hipStream_t s) {
+  if (p.kpl < 0 || p.kpl > kMaxKpl || (p.ss_in > 0) != (a.ss_part != nullptr)) return hipErrorInvalidValue;
+  if (p.kpl && (p.tn != 1 || (p.M << p.kpl) > 16 || p.K % (32 << p.kpl))) return hipErrorInvalidValue;
+  switch (p.epi * 4 + p.tn) {
+    case EPI_ROPE * 4 + 1: return launch_as<1, EPI_ROPE>(p, a, s);
+    case EPI_RESID * 4 + 1: return launch_as<1, EPI_RESID>(p, a, s);
+    case EPI_SILU * 4 + 1: return launch_as<1, EPI_SILU>(p, a, s);
+    case EPI_ARGMAX * 4 + 2: return launch_as<2, EPI_ARGMAX>(p, a, s);
+    case EPI_STORE * 4 + 1: return launch_as<1, EPI_STORE>(p, a, s);
+    case EPI_STORE * 4 + 2: return launch_as<2, EPI_STORE>(p, a, s);
+  }
+  return hipErrorInvalidValue;
 }
 
-// One workgroup per TN subtiles of 16 >> a.kpl columns.
-template <int EPI, int TN>
-hipError_t launch_gemm(const GemmArgs& a, hipStream_t s, int nw_override = 0) {
-  if (a.kpl < 0 || a.kpl > 2) return hipErrorInvalidValue;
-  if (a.kpl && (TN != 1 || (a.M << a.kpl) > 16 || a.K % (32 << a.kpl))) return hipErrorInvalidValue;
-  const int grid = a.N / (TN << tile_cwl(a.kpl));
-  const int nw = nw_override ? nw_override : pick_nw((a.K >> a.kpl) >> 5);
-  if (nw == 8) return launch_nw<8, TN, EPI>(a, grid, s);
-  if (nw == 4) return launch_nw<4, TN, EPI>(a, grid, s);
+// (span slot, row, KV head) workgroups of 8 waves. Row b reads cache slot
+// slot[b] (nullptr: slot b) of nslots.
+hipError_t launch_attn(const AttnPlan& p, const void* q, const void* kc, const void* vc, const int* pos,
+                       const int* slot, int nslots, float* part_o, float* part_ml, unsigned* counters, void* out,
+                       int H, int Hkv, int Smax, hipStream_t s) {
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(p.slots, p.grid_y), dim3(512), 0, s, static_cast<const uint16_t*>(q),
+                       static_cast<const uint16_t*>(kc), static_cast<const uint16_t*>(vc), pos, slot, nslots, part_o,
+                       part_ml, counters, static_cast<uint16_t*>(out), H, Hkv, Smax, p.stride,
+                       1.f / sqrtf(float(p.D)));
+    return hipGetLastError();
+  };
+  if (p.G < 1 || p.G > 8) return hipErrorInvalidValue;
+  switch (p.D * 16 + p.G) {
+    case 64 * 16 + 1: return go(k_attn<64, 1>);
+    case 64 * 16 + 2: return go(k_attn<64, 2>);
+    case 64 * 16 + 4: return go(k_attn<64, 4>);
+    case 64 * 16 + 8: return go(k_attn<64, 8>);
+    case 128 * 16 + 1: return go(k_attn<128, 1>);
+    case 128 * 16 + 2: return go(k_attn<128, 2>);
+    case 128 * 16 + 4: return go(k_attn<128, 4>);
+    case 128 * 16 + 8: return go(k_attn<128, 8>);
+  }
   return hipErrorInvalidValue;
 }
 
@@ -919,6 +265,8 @@ bool dims_ok(const LlamaDims& d) {
   if (d.max_batch <= 0 || d.max_seq <= 0 || d.n_layers <= 0) return false;
   return true;
 }
+
+bool rows_ok(int B) { return B > 0 && B <= kMaxM; }
 
 }  // namespace
 
@@ -945,6 +293,19 @@ int p2pt_llama_ws_layout(const LlamaDims* d, size_t* off, size_t* count, int n) 
   return WS_NBUF;
 }
 
+// What p2pt_llama_decode launches for B rows (host only: no device is touched).
+// Refuses the dims and row counts that the step refuses.
+int p2pt_llama_plan(const LlamaDims* d, int B, int emit_rows, StepPlan* out) {
+  if (!dims_ok(*d) || !rows_ok(B)) return int(hipErrorInvalidValue);
+  *out = plan_step(*d, B, emit_rows);
+  return 0;
+}
+
+// k_attn's span rule: tokens per span slot for a row of `len` tokens.
+int p2pt_attn_span(int len, int slots) { return len > 0 && slots > 0 ? attn_span(len, unsigned(slots)) : 0; }
+
+int p2pt_max_rows() { return kMaxM; }
+
 // One decode step over B <= 64 token rows. The grids depend on B alone (the
 // context enters through pos), so a captured step serves every position.
 //   w: embed, final_norm, lm_head, then per layer
@@ -964,100 +325,47 @@ int p2pt_llama_decode(const LlamaDims* dp, const void* const* w, void* k_cache, 
                       const int* pos, const int* slots, int B, int emit_rows, void* ws, size_t ws_bytes, void* logits,
                       int64_t* ids, void* stream) {
   const LlamaDims d = *dp;
-  if (!dims_ok(d) || B <= 0 || B > kMaxM || (!slots && B > d.max_batch)) return int(hipErrorInvalidValue);
-  if (emit_rows <= 0 || emit_rows > B) emit_rows = B;
-  Workspace W = carve(d, static_cast<uint8_t*>(ws));
+  if (!dims_ok(d) || !rows_ok(B) || (!slots && B > d.max_batch)) return int(hipErrorInvalidValue);
+  const Workspace W = carve(d, static_cast<uint8_t*>(ws));
   if (ws_bytes < W.bytes) return int(hipErrorInvalidValue);
+  const StepPlan P = plan_step(d, B, emit_rows);
   auto s = static_cast<hipStream_t>(stream);
-  auto bf = [&](int i) { return static_cast<const uint16_t*>(w[i]); };
-  const int qkv_n = (d.H + 2 * d.Hkv) * d.D;
   const size_t layer_cache = size_t(d.max_batch) * d.max_seq * d.Hkv * d.D;
-  const float log2_theta = log2f(d.theta);
+  hipError_t e;
+  auto failed = [&](hipError_t r) { return (e = r) != hipSuccess; };
 
-  hipLaunchKernelGGL(k_embed, dim3(B), dim3(256), 0, s, bf(0), tokens, W.resid, W.ss, d.dim, d.vocab);
-  int ss_parts = 1;
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return int(e);
-
+  hipLaunchKernelGGL(k_embed, dim3(B), dim3(256), 0, s, static_cast<const uint16_t*>(w[0]), tokens, W.resid, W.ss,
+                     d.dim, d.vocab);
+  if (failed(hipGetLastError())) return int(e);
   for (int L = 0; L < d.n_layers; L++) {
-    const uint16_t* wqkv = bf(4 + 6 * L);
-    const uint16_t* wo = bf(5 + 6 * L);
-    const uint16_t* wgu = bf(7 + 6 * L);
-    const uint16_t* wdown = bf(8 + 6 * L);
+    const void* const* wl = w + 3 + 6 * L;  // attn_norm, wqkv, wo, ffn_norm, w_gate_up, w_down
     uint16_t* kc = static_cast<uint16_t*>(k_cache) + L * layer_cache;
     uint16_t* vc = static_cast<uint16_t*>(v_cache) + L * layer_cache;
-
-    GemmArgs a{};
-    a.M = B;
-    a.eps = d.eps;
-    // QKV + RoPE + cache append
-    a.x = W.resid; a.w = wqkv; a.N = qkv_n; a.K = d.dim;
-    a.ss_part = W.ss; a.ss_parts = ss_parts;
-    a.pos = pos; a.slot = slots; a.nslots = d.max_batch; a.q_out = W.q; a.kc = kc; a.vc = vc;
-    a.H = d.H; a.Hkv = d.Hkv; a.D = d.D; a.Smax = d.max_seq; a.log2_theta = log2_theta;
-    if ((e = launch_gemm<EPI_ROPE, 1>(a, s)) != hipSuccess) return int(e);
-
-    // attention: (span slot, row, KV head) workgroups of 8 waves
-    {
-      dim3 grid(attn_slots(B, d.Hkv, d.max_seq), B * d.Hkv);
-      const float scale = 1.f / sqrtf(float(d.D));
-      const int G = d.H / d.Hkv;
-#define LAUNCH_ATTN(DD, GG)                                                                                       \
-  hipLaunchKernelGGL((k_attn<DD, GG>), grid, dim3(512), 0, s, W.q, kc, vc, pos, slots, d.max_batch, W.part_o,   \
-                     W.part_ml, W.counters, W.attn, d.H, d.Hkv, d.max_seq, attn_part_stride(d.max_seq), scale)
-      if (d.D == 64) {
-        if (G == 1) LAUNCH_ATTN(64, 1); else if (G == 2) LAUNCH_ATTN(64, 2); else if (G == 4) LAUNCH_ATTN(64, 4); else LAUNCH_ATTN(64, 8);
-      } else {
-        if (G == 1) LAUNCH_ATTN(128, 1); else if (G == 2) LAUNCH_ATTN(128, 2); else if (G == 4) LAUNCH_ATTN(128, 4); else LAUNCH_ATTN(128, 8);
-      }
-#undef LAUNCH_ATTN
-      if ((e = hipGetLastError()) != hipSuccess) return int(e);
-    }
-
-    // O projection + residual
-    GemmArgs o{};
-    o.M = B; o.x = W.attn; o.w = wo; o.N = d.dim; o.K = d.H * d.D;
-    o.out = W.resid; o.ss_out = W.ss;
-    o.kpl = pick_kparts(d.dim, B, d.H * d.D);
-    if ((e = launch_gemm<EPI_RESID, kTnResid>(o, s)) != hipSuccess) return int(e);
-    ss_parts = d.dim >> tile_cwl(o.kpl);
-
-    // gate/up + SwiGLU
-    GemmArgs g{};
-    g.M = B; g.eps = d.eps; g.x = W.resid; g.w = wgu; g.N = 2 * d.ffn; g.K = d.dim;
-    g.ss_part = W.ss; g.ss_parts = ss_parts; g.out = W.h;
-    if ((e = launch_gemm<EPI_SILU, 1>(g, s)) != hipSuccess) return int(e);
-
-    // down + residual
-    GemmArgs dn{};
-    dn.M = B; dn.x = W.h; dn.w = wdown; dn.N = d.dim; dn.K = d.ffn; dn.out = W.resid; dn.ss_out = W.ss;
-    dn.kpl = pick_kparts(d.dim, B, d.ffn);
-    if ((e = launch_gemm<EPI_RESID, kTnResid>(dn, s)) != hipSuccess) return int(e);
-    ss_parts = d.dim >> tile_cwl(dn.kpl);
+    const GemmPlan& qkv = L ? P.qkv : P.qkv_first;
+    const GemmArgs to_qkv = gemm(W.resid, wl[1]) + norm(W.ss, qkv.ss_in, d.eps) + rope(d, pos, slots, W.q, kc, vc);
+    const GemmArgs to_o = gemm(W.attn, wl[2]) + resid(W.resid, W.ss);
+    const GemmArgs to_gate_up = gemm(W.resid, wl[4]) + norm(W.ss, P.gate_up.ss_in, d.eps) + store(W.h);
+    const GemmArgs to_down = gemm(W.h, wl[5]) + resid(W.resid, W.ss);
+    if (failed(launch(qkv, to_qkv, s))) return int(e);
+    if (failed(launch_attn(P.attn, W.q, kc, vc, pos, slots, d.max_batch, W.part_o, W.part_ml, W.counters, W.attn, d.H,
+                           d.Hkv, d.max_seq, s)))
+      return int(e);
+    if (failed(launch(P.o, to_o, s))) return int(e);
+    if (failed(launch(P.gate_up, to_gate_up, s))) return int(e);
+    if (failed(launch(P.down, to_down, s))) return int(e);
   }
-
-  // final norm + LM head + argmax
-  GemmArgs h{};
-  h.M = emit_rows; h.eps = d.eps; h.x = W.resid; h.w = bf(2); h.N = d.vocab; h.K = d.dim;
-  h.ss_part = W.ss; h.ss_parts = ss_parts;
-  h.out = static_cast<uint16_t*>(logits);
-  h.am_val = W.am_val; h.am_idx = W.am_idx;
-  const int parts = d.vocab / (16 * kTnStore);
-  // 4 waves x 2 subtiles: the fastest LM-head shape measured (vocab 32000, K 2048: 22.6 vs 29.6 us).
-  if ((e = launch_gemm<EPI_ARGMAX, kTnStore>(h, s, 4)) != hipSuccess) return int(e);
-  hipLaunchKernelGGL(k_argmax_merge, dim3(emit_rows), dim3(256), 0, s, W.am_val, W.am_idx, parts, ids);
+  const GemmArgs to_logits =
+      gemm(W.resid, w[2]) + norm(W.ss, P.lm_head.ss_in, d.eps) + argmax(logits, W.am_val, W.am_idx);
+  if (failed(launch(P.lm_head, to_logits, s))) return int(e);
+  hipLaunchKernelGGL(k_argmax_merge, dim3(P.emit_rows), dim3(256), 0, s, W.am_val, W.am_idx, P.am_parts, ids);
   return int(hipGetLastError());
 }
 
 // Standalone skinny GEMM (tests/benchmarks): out[M][N] = bf16(x[M][K] @ w[N][K]^T), M <= 64.
 int p2pt_skinny_gemm(const void* x, const void* w, void* out, int M, int N, int K, void* stream) {
-  if (M <= 0 || M > kMaxM || N % 32 || K <= 0 || K % 32) return int(hipErrorInvalidValue);
-  GemmArgs a{};
-  a.x = static_cast<const uint16_t*>(x);
-  a.w = static_cast<const uint16_t*>(w);
-  a.out = static_cast<uint16_t*>(out);
-  a.M = M; a.N = N; a.K = K;
-  return int(launch_gemm<EPI_STORE, 2>(a, static_cast<hipStream_t>(stream)));
+  if (!rows_ok(M) || N % 32 || K <= 0 || K % 32) return int(hipErrorInvalidValue);
+  const GemmPlan p = plan_gemm(EPI_STORE, 2, M, N, K);
+  return int(launch(p, gemm(x, w) + store(out), static_cast<hipStream_t>(stream)));
 }
 
 // Microbenchmark hook (scripts/bench_skinny.py --attn): `reps` back-to-back
@@ -1065,25 +373,11 @@ int p2pt_skinny_gemm(const void* x, const void* w, void* out, int M, int N, int 
 // the workspace (counters zeroed); q [B][H*D], caches [B][Smax][Hkv][D].
 int p2pt_attn_bench(const void* q, const void* kc, const void* vc, const int* pos, int B, int H, int Hkv, int D,
                     int Smax, float* part_o, float* part_ml, unsigned* counters, void* out, int reps, void* stream) {
-  const int G = Hkv > 0 ? H / Hkv : 0;
-  if (B <= 0 || B > kMaxM || (D != 64 && D != 128) || G != 4 || Smax <= 0 || reps <= 0)
-    return int(hipErrorInvalidValue);
-  auto st = static_cast<hipStream_t>(stream);
-  const int nsplit = attn_part_stride(Smax);
-  const float scale = 1.f / sqrtf(float(D));
+  if (!rows_ok(B) || Hkv <= 0 || H % Hkv || Smax <= 0 || reps <= 0) return int(hipErrorInvalidValue);
+  const AttnPlan p = plan_attn(B, H, Hkv, D, Smax);
   for (int r = 0; r < reps; r++) {
-    dim3 grid(attn_slots(B, Hkv, Smax), B * Hkv);
-    auto qq = static_cast<const uint16_t*>(q);
-    auto kk = static_cast<const uint16_t*>(kc);
-    auto vv = static_cast<const uint16_t*>(vc);
-    auto oo = static_cast<uint16_t*>(out);
-    if (D == 64)
-      hipLaunchKernelGGL((k_attn<64, 4>), grid, dim3(512), 0, st, qq, kk, vv, pos, nullptr, B, part_o, part_ml,
-                         counters, oo, H, Hkv, Smax, nsplit, scale);
-    else
-      hipLaunchKernelGGL((k_attn<128, 4>), grid, dim3(512), 0, st, qq, kk, vv, pos, nullptr, B, part_o, part_ml,
-                         counters, oo, H, Hkv, Smax, nsplit, scale);
-    hipError_t e = hipGetLastError();
+    hipError_t e = launch_attn(p, q, kc, vc, pos, nullptr, B, part_o, part_ml, counters, out, H, Hkv, Smax,
+                               static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return int(e);
   }
   return 0;
@@ -1095,20 +389,11 @@ int p2pt_attn_bench(const void* q, const void* kc, const void* vc, const int* po
 int p2pt_skinny_bench(const void* x, const void* w, void* out, int M, int N, int K, int nw, int tn, int reps,
                       void* stream) {
   if ((nw != 4 && nw != 8) || (tn != 1 && tn != 2)) return int(hipErrorInvalidValue);
-  if (M <= 0 || M > kMaxM || N % (16 * tn) || K <= 0 || K % 32 || reps <= 0) return int(hipErrorInvalidValue);
-  GemmArgs a{};
-  a.x = static_cast<const uint16_t*>(x);
-  a.w = static_cast<const uint16_t*>(w);
-  a.out = static_cast<uint16_t*>(out);
-  a.M = M; a.N = N; a.K = K;
-  auto st = static_cast<hipStream_t>(stream);
+  if (!rows_ok(M) || N % (16 * tn) || K <= 0 || K % 32 || reps <= 0) return int(hipErrorInvalidValue);
+  const GemmPlan p = plan_gemm(EPI_STORE, tn, M, N, K, false, nw);
+  const GemmArgs a = gemm(x, w) + store(out);
   for (int r = 0; r < reps; r++) {
-    hipError_t e;
-    const int grid = N / (16 * tn);
-    if (tn == 1)
-      e = nw == 4 ? launch_nw<4, 1, EPI_STORE>(a, grid, st) : launch_nw<8, 1, EPI_STORE>(a, grid, st);
-    else
-      e = nw == 4 ? launch_nw<4, 2, EPI_STORE>(a, grid, st) : launch_nw<8, 2, EPI_STORE>(a, grid, st);
+    hipError_t e = launch(p, a, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return int(e);
   }
   return 0;

@@ -1,0 +1,798 @@
+// Fused Llama decode step for gfx950 (CDNA4 / MI355X).
+//
+// The unfused step (kernels.hip + hipBLASLt) is ~50 kernels per token for a
+// 4-layer model; at decode batch sizes every one of them is a few-µs latency
+// chain (dispatch, one HBM round trip, write back) and the step is bound by
+// kernel count, not bytes. This file rebuilds the step as 5 kernels per layer
+// plus 3, the GEMMs weight-streaming MFMA kernels with their neighbours fused in:
+//
+//   k_embed              token gather -> residual stream, per-row sum of squares
+//   per layer:
+//     k_skinny<ROPE>     RMSNorm (attn_norm) -> QKV GEMM -> RoPE on q/k,
+//                        q to the attention buffer, k/v appended to the cache
+//     k_attn             GQA flash-decoding split-K; the last split to finish
+//                        for a (sequence, KV head) merges the partials in-kernel
+//     k_skinny<RESID>    O projection -> residual add -> per-row sum-of-squares
+//                        partials for the next norm
+//     k_skinny<SILU>     RMSNorm (ffn_norm) -> gate/up GEMM -> SwiGLU
+//     k_skinny<RESID>    down projection -> residual add -> sum-of-squares
+//   k_skinny<ARGMAX>     RMSNorm (final norm) -> LM head -> logits and
+//                        per-block greedy winners
+//   k_argmax_merge       one block per row merges the winners
+//
+// Skinny GEMM (M <= 64 tokens): Y[M,N] = A[M,K] * W[N,K]^T on
+// v_mfma_f32_16x16x32_bf16. A workgroup owns 16*TN output columns of one
+// 16-row tile (blockIdx.y; prefill-heavy steps carry up to 4) and splits K
+// over its NW waves; each lane streams its weight rows with 16-byte loads
+// straight into MFMA B fragments (no LDS staging: every weight byte is used
+// exactly once, by exactly one lane), the K-split partials are summed through
+// LDS and wave 0 runs the epilogue. RMSNorm is folded away: its weight g is
+// multiplied into the columns of the following projection once at load time
+// (W'[n][k] = W[n][k] g[k]), and the per-row 1/rms factors out of the dot
+// product, so the GEMM streams the raw residual and the epilogue scales the
+// accumulator. 1/rms comes from per-block partial sums of squares written by
+// the residual producer (deterministic: fixed order, no float atomics).
+// The attention splits merge in-kernel through write-through stores and an
+// arrival ticket, never an L2 write-back fence. QKV and gate/up weights have
+// their rows interleaved in pairs (RoPE partners; gate_j/up_j) so that one
+// 16-column tile holds both members of every pair (lanes c, c^1).
+//
+// Numerics: GEMM outputs, the residual and the attention output are rounded
+// to bf16 where the unfused path rounds them; the normed activation is not
+// materialised (rounding differs at the bf16-ulp level); fp32 accumulation.
+//
+// This header is the device side: kernel arguments, the kernels, the attention
+// grid rules and the record of what was measured and rejected. decode_fused.hip
+// includes it and holds the host side (planning, workspace, launches).
+#pragma once
+#include "bf16_common.h"
+
+#include <algorithm>
+
+namespace {
+
+using namespace p2pt_gpu;
+
+constexpr int kMaxM = 64;  // token rows per step: up to 4 MFMA row tiles (blockIdx.y)
+
+typedef short frag8 __attribute__((ext_vector_type(8)));
+typedef float frag4 __attribute__((ext_vector_type(4)));
+
+enum Epi : int { EPI_STORE = 0, EPI_ROPE = 1, EPI_SILU = 2, EPI_RESID = 3, EPI_ARGMAX = 4 };
+
+struct GemmArgs {
+  const uint16_t* x;  // A [M][K]
+  const uint16_t* w;  // W [N][K]; for a normed input, W[n][k] * g[k] folded in
+  int M, N, K;
+  // RMSNorm of A's rows (ss_part == nullptr: A used as is). The norm weight g
+  // is folded into W offline, so only the per-row 1/rms remains, and that
+  // factors out of the dot product: it scales the accumulator in the epilogue.
+  const float* ss_part;  // [ss_parts][16] partial row sums of squares
+  int ss_parts;
+  float eps;
+  // epilogue
+  uint16_t* out;   // STORE/ARGMAX: [M][N] logits; SILU: [M][N/2]; RESID: residual [M][N], in place
+  float* ss_out;   // RESID: [gridDim.x][16]
+  const int* pos;   // ROPE: cache position of each row
+  const int* slot;  // ROPE: cache slot of each row (nullptr: row m -> slot m)
+  int nslots;
+  uint16_t* q_out;
+  uint16_t* kc;
+  uint16_t* vc;
+  int H, Hkv, D, Smax;
+  float log2_theta;
+  float* am_val;  // ARGMAX: [gridDim.x][16]
+  int* am_idx;
+  // K parts (kpl = log2 P, 0: off; TN = 1, M * P <= 16). A subtile then holds
+  // 16 / P output columns instead of 16, so a small-N projection lands on P
+  // times the workgroups and its weight stream spreads over every CU (one CU
+  // streams ~10 B/cycle; a 2048-wide projection in 16-column tiles reaches
+  // only 128 of the 256 CUs). Lanes past the tile width take the other K
+  // parts of the same columns, and MFMA rows m * P + p carry activation row
+  // m's K part p, so every lane streams unique weight bytes. The diagonal
+  // blocks of the 16 x 16 accumulator are summed in the epilogue. It needs
+  // spare MFMA rows: a decode step of <= 16 / P tokens.
+  int kpl;
+};
+
+// log2 of the output columns per 16-lane subtile: 16, 8 or 4 for 1, 2 or 4 K parts.
+__host__ __device__ __forceinline__ int tile_cwl(int kpl) { return 4 - kpl; }
+
+__device__ __forceinline__ frag8 as_frag(const uint4& v) { return __builtin_bit_cast(frag8, v); }
+
+typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+// v_dot2_f32_bf16: c + a.lo * b.lo + a.hi * b.hi, products and sum in fp32.
+__device__ __forceinline__ float dot2_bf16(uint32_t a, uint32_t b, float c) {
+  return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, a), __builtin_bit_cast(bf16x2_t, b), c, false);
+}
+
+// Cross-workgroup hand-off without L2 write-back/invalidate fences: payload
+// stores are agent-scope relaxed atomics (write-through, `sc1`), drained with
+// s_waitcnt before the arrival ticket; the last arriver reads them back with
+// agent-scope loads that bypass stale cache lines (MI355X_MICROARCH handoff-flag).
+template <typename T>
+__device__ __forceinline__ void st_wt(T* p, T v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+template <typename T>
+__device__ __forceinline__ T ld_wt(const T* p) {
+  return __hip_atomic_load(const_cast<T*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ __forceinline__ void drain_stores() {
+  __atomic_signal_fence(__ATOMIC_SEQ_CST);
+  __builtin_amdgcn_s_waitcnt(0);
+  __atomic_signal_fence(__ATOMIC_SEQ_CST);
+}
+__device__ __forceinline__ unsigned arrive(unsigned* ctr) {
+  return __hip_atomic_fetch_add(ctr, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Output column of lane column c (0..15) in subtile t of block bx, for
+// subtiles of 2^cwl columns (lanes past 2^cwl: the same columns' other K parts).
+template <int TN>
+__device__ __forceinline__ int tile_col(int bx, int t, int c, int cwl) {
+  return ((bx * TN + t) << cwl) + (c & ((1 << cwl) - 1));
+}
+
+// Operand loads go through buffer descriptors (wave-uniform base and size
+// from the kernel arguments): a lane whose byte offset lies past the buffer
+// gets zeros from the range check without a memory access. Rows past M and
+// k-steps past a wave's share use that (kOob), so a batch is branch-free and a
+// decode step at batch 1 fetches its one activation row once per k-step
+// instead of for all 16 MFMA rows.
+constexpr uint32_t kOob = 0x80000000u;  // host keeps every operand below 2 GiB
+
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* p, uint32_t bytes) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), (short)0, (int)bytes, 0x00020000);
+}
+__device__ __forceinline__ uint4 buf_ld16(__amdgpu_buffer_rsrc_t r, uint32_t off) {
+  return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
+}
+
+// One batch of up to UM consecutive 32-wide k-steps [s, min(s + UM, s1)):
+// every load of the batch is issued before any of it is used.
+template <int UM, int TN>
+struct Batch {
+  uint4 b[UM][TN];
+  uint4 a[UM];
+};
+
+template <int UM, int TN>
+__device__ __forceinline__ void load_batch(Batch<UM, TN>& bt, __amdgpu_buffer_rsrc_t ra, uint32_t xoff,
+                                           __amdgpu_buffer_rsrc_t rw, const uint32_t (&woff)[TN], int s, int s1) {
+#pragma unroll
+  for (int u = 0; u < UM; u++) {
+    const bool in = s + u < s1;
+    const uint32_t su = uint32_t(s + u) * 64u;  // bytes per 32-wide k-step
+#pragma unroll
+    for (int t = 0; t < TN; t++) bt.b[u][t] = buf_ld16(rw, in ? woff[t] + su : kOob);
+    bt.a[u] = buf_ld16(ra, in ? xoff + su : kOob);
+  }
+}
+
+template <int UM, int TN>
+__device__ __forceinline__ void mma_apply(frag4 (&acc)[TN], const Batch<UM, TN>& bt) {
+#pragma unroll
+  for (int u = 0; u < UM; u++)
+#pragma unroll
+    for (int t = 0; t < TN; t++)
+      acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(bt.a[u]), as_frag(bt.b[u][t]), acc[t], 0, 0, 0);
+}
+
+// The wave's k-steps [s0, s1), one batch at a time.
+template <int UM, int TN>
+__device__ __forceinline__ void mma_stream(frag4 (&acc)[TN], __amdgpu_buffer_rsrc_t ra, uint32_t xoff,
+                                           __amdgpu_buffer_rsrc_t rw, const uint32_t (&woff)[TN], int s0, int s1) {
+  for (int s = s0; s < s1; s += UM) {
+    Batch<UM, TN> p;
+    load_batch<UM, TN>(p, ra, xoff, rw, woff, s, s1);
+    // Keep every load of the batch ahead of the first MFMA: left alone, the
+    // scheduler interleaves them and the batch pays several memory latencies.
+    __builtin_amdgcn_sched_barrier(0);
+    mma_apply<UM, TN>(acc, p);
+  }
+}
+
+// Skinny GEMM + fused epilogue. NW waves split K; TN subtiles of 2^cwl
+// columns per block; UM k-steps per load batch (host: >= each wave's share
+// when possible). Steps of more than 16 rows put each 16-row tile on its own
+// workgroup (blockIdx.y). ROPE and SILU take weights whose rows are
+// interleaved in pairs (RoPE partners d, d + D/2 of a head; gate_j, up_j), so
+// a pair sits in lanes c, c^1.
+template <int NW, int TN, int EPI, int UM>
+__global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
+  __shared__ float red[NW][TN][4][kWave];
+  __shared__ float red_ss[NW][kWave];
+  // The wave index is uniform: held in an SGPR, the k-step bounds and loop
+  // counter derived from it stay out of the VGPR budget.
+  const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int m0 = blockIdx.y << 4;  // first row of this workgroup's 16-row tile
+  const int bx = blockIdx.x;       // column tile
+  const int cwl = tile_cwl(a.kpl);
+  const bool norm = a.ss_part != nullptr;
+
+  // Row sums of squares for the folded RMSNorm, spread over every wave (lane:
+  // row lane & 15, partials (lane >> 4) + 4 * wave + 4 * NW * i): up to 8
+  // loads per lane issued ahead of the weight stream and summed only after
+  // it, so they never stall it; combined through LDS before the epilogue.
+  constexpr int kSsRegs = 8;
+  float ssv[kSsRegs];
+  const int ss_p0 = (lane >> 4) + 4 * wv;
+  if (norm) {
+#pragma unroll
+    for (int i = 0; i < kSsRegs; i++) {
+      const int p = ss_p0 + 4 * NW * i;
+      ssv[i] = p < a.ss_parts ? a.ss_part[p * kMaxM + m0 + (lane & 15)] : 0.f;
+    }
+  }
+
+  // A fragment: row lane & 15, k = 32*s + 8*(lane>>4) + j; B fragment: W row n, same k.
+  // The K steps are split evenly over the NW waves.
+  const int kparts = 1 << a.kpl, Kp = a.K >> a.kpl;  // Kp: K elements per part
+  const int m_a = (lane & 15) >> a.kpl;              // activation row of this lane's MFMA row
+  const int p_a = (lane & 15) & (kparts - 1);        // ... and the K part it carries
+  const bool a_ok = m0 + m_a < a.M;
+  const int kq = (lane >> 4) << 3;
+  const int S = Kp >> 5;
+  const int s0 = wv * S / NW, s1 = (wv + 1) * S / NW;
+  // Byte offsets of this lane's A row and weight rows at k-step 0; rows past
+  // M read as zeros (kOob).
+  const __amdgpu_buffer_rsrc_t ra = rsrc(a.x, uint32_t(a.M) * uint32_t(a.K) * 2u);
+  const __amdgpu_buffer_rsrc_t rw = rsrc(a.w, uint32_t(a.N) * uint32_t(a.K) * 2u);
+  const uint32_t xoff = a_ok ? (uint32_t(m0 + m_a) * uint32_t(a.K) + uint32_t(p_a * Kp + kq)) * 2u : kOob;
+  const int p_b = (lane & 15) >> cwl;  // K part of this lane's weight column
+  uint32_t woff[TN];
+#pragma unroll
+  for (int t = 0; t < TN; t++)
+    woff[t] = (uint32_t(tile_col<TN>(bx, t, lane & 15, cwl)) * uint32_t(a.K) + uint32_t(p_b * Kp + kq)) * 2u;
+
+  // C layout: row m = m0 + 4*(lane>>4) + r, column = tile_col(.., lane & 15).
+  const int lrow0 = (lane >> 4) << 2, mrow0 = m0 + lrow0;
+  const int c = lane & 15;
+  const bool col_ok = c < (1 << cwl);  // lanes past the tile width carry the other K parts
+
+  // RESID: the residual values this lane's epilogue updates, loaded by wave 0
+  // ahead of the weight stream (they do not depend on it) instead of after
+  // the reduction, which would add a dependent memory round trip.
+  float rprev[EPI == EPI_RESID ? TN : 1][4];
+  if constexpr (EPI == EPI_RESID) {
+    if (wv == 0) {
+#pragma unroll
+      for (int t = 0; t < TN; t++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+          const int m = min(mrow0 + r, a.M - 1);
+          rprev[t][r] = bf2f(a.out[size_t(m) * a.N + tile_col<TN>(bx, t, c, cwl)]);
+        }
+    }
+  }
+
+  frag4 acc[TN];
+#pragma unroll
+  for (int t = 0; t < TN; t++) acc[t] = frag4{0.f, 0.f, 0.f, 0.f};
+  mma_stream<UM, TN>(acc, ra, xoff, rw, woff, s0, s1);
+
+  if (norm) {
+    float ssum = 0.f;
+#pragma unroll
+    for (int i = 0; i < kSsRegs; i++) ssum += ssv[i];
+    for (int p = ss_p0 + 4 * NW * kSsRegs; p < a.ss_parts; p += 4 * NW) ssum += a.ss_part[p * kMaxM + m0 + (lane & 15)];
+    red_ss[wv][lane] = ssum;
+  }
+  // K-split reduction through LDS (lane-contiguous: conflict-free).
+#pragma unroll
+  for (int t = 0; t < TN; t++)
+#pragma unroll
+    for (int r = 0; r < 4; r++) red[wv][t][r][lane] = acc[t][r];
+  __syncthreads();
+  if (wv != 0) return;
+  float v[TN][4];
+#pragma unroll
+  for (int t = 0; t < TN; t++)
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      float sum = 0.f;
+#pragma unroll
+      for (int w = 0; w < NW; w++) sum += red[w][t][r][lane];
+      v[t][r] = sum;
+    }
+
+  if (a.kpl) {
+    // Sum the diagonal blocks: output (row m, column c < 2^cwl) is
+    // sum_p C[m * P + p][c + p * 2^cwl]. Wave 0 alone from here on: the
+    // reduction buffer (its own reads are done) holds C [16][17].
+    float* cbuf = &red[0][0][0][0];
+#pragma unroll
+    for (int r = 0; r < 4; r++) cbuf[(lrow0 + r) * 17 + c] = v[0][r];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const int row = lrow0 + r;
+      float sum = 0.f;
+      if (row < (16 >> a.kpl) && col_ok)
+        for (int p = 0; p < kparts; p++) sum += cbuf[(row * kparts + p) * 17 + c + (p << cwl)];
+      v[0][r] = sum;
+    }
+  }
+
+  if (norm) {
+    float ssum = 0.f;
+#pragma unroll
+    for (int w = 0; w < NW; w++) ssum += red_ss[w][lane];
+    ssum = xor32_sum(xor16_sum(ssum));
+    const float rs_row = rsqrtf(ssum * (1.f / float(a.K)) + a.eps);  // for row m0 + (lane & 15)
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const float rs = __shfl(rs_row, lrow0 + r, kWave);
+#pragma unroll
+      for (int t = 0; t < TN; t++) v[t][r] *= rs;
+    }
+  }
+
+  if constexpr (EPI == EPI_STORE || EPI == EPI_ARGMAX) {
+    // Logits (bf16) and, for ARGMAX, this block's per-row winner (first index on ties).
+    float best[4];
+    int bi[4];
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      best[r] = -INFINITY;
+      bi[r] = 0x7fffffff;
+    }
+#pragma unroll
+    for (int t = 0; t < TN; t++) {
+      const int n = tile_col<TN>(bx, t, c, cwl);
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const int m = mrow0 + r;
+        const float lv = bf_round(v[t][r]);
+        if (m < a.M && col_ok) a.out[size_t(m) * a.N + n] = uint16_t(f2bf_bits(lv));
+        if (lv > best[r] || (lv == best[r] && n < bi[r])) {
+          best[r] = lv;
+          bi[r] = n;
+        }
+      }
+    }
+    if constexpr (EPI == EPI_ARGMAX) {
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        row16_argmax(best[r], bi[r]);
+        if (c == 0) {
+          a.am_val[bx * kMaxM + mrow0 + r] = best[r];
+          a.am_idx[bx * kMaxM + mrow0 + r] = bi[r];
+        }
+      }
+    }
+  } else if constexpr (EPI == EPI_SILU) {
+    // Interleaved rows: even lane = gate_j, odd lane = up_j, j = column / 2.
+    const int n = tile_col<TN>(bx, 0, c, cwl);
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const float mine = bf_round(v[0][r]);
+      const float other = dpp<kDppXor1>(mine);
+      if ((c & 1) || !col_ok || mrow0 + r >= a.M) continue;
+      a.out[size_t(mrow0 + r) * (a.N >> 1) + (n >> 1)] = uint16_t(f2bf_bits(mine / (1.f + __expf(-mine)) * other));
+    }
+  } else if constexpr (EPI == EPI_ROPE) {
+    // Interleaved rows within each head: column 2i = dim i, 2i+1 = dim i + D/2.
+    const int half = a.D >> 1;
+    const int col = tile_col<TN>(bx, 0, c, cwl);
+    const int head = col / a.D, i = (col % a.D) >> 1;
+    const bool second = c & 1;
+    const float inv_freq = exp2f(-a.log2_theta * (2.f * i) / a.D);
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      const int m = mrow0 + r;
+      const float mine = bf_round(v[0][r]);
+      const float other = dpp<kDppXor1>(mine);
+      if (m >= a.M || !col_ok) continue;
+      // Host validates; clamped anyway so a bad index can never write outside the cache.
+      const int p = min(max(a.pos[m], 0), a.Smax - 1);
+      const int sl = a.slot ? min(max(a.slot[m], 0), a.nslots - 1) : m;
+      const int d = i + (second ? half : 0);
+      if (head < a.H + a.Hkv) {
+        float sn, cs;
+        sincosf(float(p) * inv_freq, &sn, &cs);
+        const float x1 = second ? other : mine, x2 = second ? mine : other;
+        const float o = second ? x2 * cs + x1 * sn : x1 * cs - x2 * sn;
+        uint16_t* dst = head < a.H ? a.q_out + (size_t(m) * a.H + head) * a.D
+                                   : a.kc + ((size_t(sl) * a.Smax + p) * a.Hkv + (head - a.H)) * a.D;
+        dst[d] = uint16_t(f2bf_bits(o));
+      } else {
+        a.vc[((size_t(sl) * a.Smax + p) * a.Hkv + (head - a.H - a.Hkv)) * a.D + d] = uint16_t(f2bf_bits(mine));
+      }
+    }
+  } else if constexpr (EPI == EPI_RESID) {
+    float sq[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int t = 0; t < TN; t++) {
+      const int n = tile_col<TN>(bx, t, c, cwl);
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const int m = mrow0 + r;
+        if (m >= a.M || !col_ok) continue;
+        const float nv = bf_round(rprev[t][r] + bf_round(v[t][r]));
+        a.out[size_t(m) * a.N + n] = uint16_t(f2bf_bits(nv));
+        sq[r] += nv * nv;
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      sq[r] = row16_sum(sq[r]);
+      if (c == 0) a.ss_out[bx * kMaxM + mrow0 + r] = sq[r];
+    }
+  }
+}
+
+// Greedy sampling, second stage: one block per row merges the LM-head blocks'
+// winners (first index on ties).
+__global__ __launch_bounds__(256) void k_argmax_merge(const float* __restrict__ am_val, const int* __restrict__ am_idx,
+                                                      int parts, int64_t* __restrict__ ids) {
+  const int m = blockIdx.x;
+  float b = -INFINITY;
+  int i = 0x7fffffff;
+  for (int p0 = threadIdx.x; p0 < parts; p0 += 8 * 256) {
+    float pv[8];
+    int pi[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) {  // 8 loads in flight per thread
+      const int p = p0 + j * 256;
+      pv[j] = p < parts ? am_val[p * kMaxM + m] : -INFINITY;
+      pi[j] = p < parts ? am_idx[p * kMaxM + m] : 0x7fffffff;
+    }
+#pragma unroll
+    for (int j = 0; j < 8; j++)
+      if (pv[j] > b || (pv[j] == b && pi[j] < i)) {
+        b = pv[j];
+        i = pi[j];
+      }
+  }
+  wave_argmax(b, i);
+  __shared__ float sb[4];
+  __shared__ int si[4];
+  if ((threadIdx.x & 63) == 0) {
+    sb[threadIdx.x >> 6] = b;
+    si[threadIdx.x >> 6] = i;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 4; w++)
+      if (sb[w] > b || (sb[w] == b && si[w] < i)) {
+        b = sb[w];
+        i = si[w];
+      }
+    ids[m] = i;
+  }
+}
+
+// ------------------------------------------------------------ embedding gather
+// One block per token: residual row = embed[token]; ss_out[0][b] = sum of squares.
+__global__ __launch_bounds__(256) void k_embed(const uint16_t* __restrict__ embed, const int64_t* __restrict__ tok,
+                                               uint16_t* __restrict__ resid, float* __restrict__ ss_out, int dim,
+                                               int vocab) {
+  const int b = blockIdx.x;
+  int64_t t = tok[b];
+  t = t < 0 ? 0 : (t >= vocab ? vocab - 1 : t);
+  const uint4* src = reinterpret_cast<const uint4*>(embed + size_t(t) * dim);
+  uint4* dst = reinterpret_cast<uint4*>(resid + size_t(b) * dim);
+  float ss = 0.f;
+  for (int i = threadIdx.x; i < dim / 8; i += 256) {
+    const uint4 v = src[i];
+    dst[i] = v;
+    float f[8];
+    unpack8(v, f);
+#pragma unroll
+    for (int j = 0; j < 8; j++) ss += f[j] * f[j];
+  }
+  __shared__ float red[4];
+  ss = wave_sum(ss);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
+  __syncthreads();
+  if (threadIdx.x == 0) ss_out[b] = red[0] + red[1] + red[2] + red[3];
+}
+
+// ------------------------------------------------------------ attention
+// GQA flash-decoding with a fixed grid of (span slot, row b, KV head)
+// workgroups: graph-captured steps launch the same grid whatever the context
+// length, so the grid is sized by the batch (about one round of workgroups on
+// the chip), not by the cache capacity — idle workgroups were a third of the
+// kernel at 1k tokens. Each slot covers a span of >= 64 tokens of row b; its
+// 8 waves walk the span in 32-token pieces with an online softmax.
+// A piece is loaded straight into registers with 16-byte loads whose lanes
+// tile whole K/V rows (D/8 lanes per row: every instruction reads full cache
+// lines); nothing is staged through LDS. A lane keeps one 8-dim group of every
+// query head of the KV head (K/V are read once per GQA group), computes its
+// dot products with v_dot2_f32_bf16 and finishes them with in-row DPP sums,
+// and ends up holding the softmax weights of exactly the tokens whose V it
+// loaded: P.V needs no data exchange until the final cross-row sum. Scores and
+// P.V are fp32 VALU: with G <= 8 query rows an MFMA tile would be >= half
+// padding; the kernel is bound by the K/V stream and latency.
+// The 8 waves of a slot merge through LDS; only spans split over several
+// slots publish a partial (write-through + arrival ticket) that the last slot
+// to finish merges, its waves taking different heads.
+// Row b reads cache slot slot[b] (rows may share a slot: chunked prefill) and
+// attends to positions 0..pos[b]; the output is bf16 [B][H*D].
+constexpr int kAttnSlotCap = 16;  // span slots per (row, KV head) at most
+// Workgroups one launch aims at: one 512-thread, 234-VGPR workgroup per CU.
+// More slots per row are slower: b16 0.522 / 0.567 / 0.597 / 0.645 ms at
+// 256 / 512 / 768 / 1024 (profiles/r03/decode/attn_grid_sweep_head.log).
+constexpr int kAttnTargetWgs = 256;
+// Smallest token span of one workgroup (a multiple of the 32-token wave
+// piece). 64 (two busy waves) puts a short context on 4x the workgroups of
+// 256 (one piece per wave): at batch 1 and 1k tokens the decode step went
+// 396 -> 380 us on MI355X, unchanged at batch 16.
+constexpr int kAttnMinSpan = 64;
+constexpr int kAttnPiece = 32;  // tokens per wave piece
+
+// Tokens per span slot for a row of `len` tokens on `slots` slots (gridDim.x):
+// an even share in whole wave pieces, at least kAttnMinSpan.
+__host__ __device__ __forceinline__ int attn_span(int len, unsigned slots) {
+  const int span = (len + slots - 1) / slots;
+  return std::max(kAttnMinSpan, (span + kAttnPiece - 1) / kAttnPiece * kAttnPiece);
+}
+
+template <int D, int G>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1))) void k_attn(
+    const uint16_t* __restrict__ q, const uint16_t* __restrict__ kc, const uint16_t* __restrict__ vc,
+    const int* __restrict__ pos, const int* __restrict__ slot, int nslots, float* __restrict__ part_o,
+    float* __restrict__ part_ml, unsigned* __restrict__ counters, uint16_t* __restrict__ out, int H, int Hkv, int Smax,
+    int nsplit, float scale) {
+  constexpr int NWV = 8;
+  constexpr int TOK = kAttnPiece;
+  constexpr int DPL = D / kWave;  // merges: dims per lane
+  constexpr int MAXC = 16;        // partials merged per load batch
+  constexpr int LPR = D / 8, RPI = kWave / LPR, NI = TOK / RPI;
+  __shared__ __attribute__((aligned(16))) float pacc[NWV][G][D];
+  __shared__ float pml[NWV][G][2];
+  __shared__ unsigned s_ticket;
+
+  const int b = blockIdx.y / Hkv, kvh = blockIdx.y % Hkv;
+  const int len = min(max(pos[b], 0), Smax - 1) + 1;
+  const int span = attn_span(len, gridDim.x);
+  const int nact = (len + span - 1) / span;  // slots with tokens
+  const int sl = blockIdx.x;
+  if (sl >= nact) return;
+  const int s0 = sl * span, s1 = min(len, s0 + span);
+  const int sb = slot ? min(max(slot[b], 0), nslots - 1) : b;
+  const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int dg = lane % LPR, ri = lane / LPR;
+
+  const size_t tok_stride = size_t(Hkv) * D;
+  const uint16_t* kbase = kc + size_t(sb) * Smax * tok_stride + size_t(kvh) * D + 8 * dg;
+  const uint16_t* vbase = vc + size_t(sb) * Smax * tok_stride + size_t(kvh) * D + 8 * dg;
+  // This lane's 8 query dims of every head as bf16 pairs (v_dot2 operands).
+  uint4 qpk[G];
+  {
+    const uint16_t* qp = q + (size_t(b) * H + size_t(kvh) * G) * D + 8 * dg;
+#pragma unroll
+    for (int g = 0; g < G; g++) qpk[g] = *reinterpret_cast<const uint4*>(qp + size_t(g) * D);
+  }
+
+  // Running state over this wave's pieces. m is wave-uniform per head; l and
+  // acc hold this lane's tokens only and are summed across rows at the end.
+  float mg[G], lg[G], acc[G][8];
+#pragma unroll
+  for (int g = 0; g < G; g++) {
+    mg[g] = -INFINITY;
+    lg[g] = 0.f;
+#pragma unroll
+    for (int k = 0; k < 8; k++) acc[g][k] = 0.f;
+  }
+  for (int p0 = s0 + wv * TOK; p0 < s1; p0 += NWV * TOK) {
+    const int ntok = min(TOK, s1 - p0);
+    // Issue the piece (lanes past the end re-read the last valid row).
+    uint4 kr[NI], vr[NI];
+#pragma unroll
+    for (int j = 0; j < NI; j++)
+      kr[j] = *reinterpret_cast<const uint4*>(kbase + size_t(p0 + min(j * RPI + ri, ntok - 1)) * tok_stride);
+#pragma unroll
+    for (int j = 0; j < NI; j++)
+      vr[j] = *reinterpret_cast<const uint4*>(vbase + size_t(p0 + min(j * RPI + ri, ntok - 1)) * tok_stride);
+    // Scores: lane (ri, dg) ends with token j*RPI + ri's score for every head.
+    float sc[G][NI];
+#pragma unroll
+    for (int j = 0; j < NI; j++) {
+#pragma unroll
+      for (int g = 0; g < G; g++) {
+        float d = 0.f;
+        d = dot2_bf16(qpk[g].x, kr[j].x, d);
+        d = dot2_bf16(qpk[g].y, kr[j].y, d);
+        d = dot2_bf16(qpk[g].z, kr[j].z, d);
+        d = dot2_bf16(qpk[g].w, kr[j].w, d);
+        d = (LPR == 16 ? row16_sum(d) : row8_sum(d)) * scale;
+        sc[g][j] = (j * RPI + ri < ntok) ? d : -INFINITY;
+      }
+    }
+#pragma unroll
+    for (int g = 0; g < G; g++) {
+      float pm = -INFINITY;
+#pragma unroll
+      for (int j = 0; j < NI; j++) pm = fmaxf(pm, sc[g][j]);
+      if constexpr (LPR == 8) pm = xor8_max(pm);
+      pm = xor32_max(xor16_max(pm));
+      const float mnew = fmaxf(mg[g], pm);
+      const float corr = __expf(mg[g] - mnew);  // 0 on the first piece (mg = -inf)
+      mg[g] = mnew;
+      float ls = 0.f;
+#pragma unroll
+      for (int j = 0; j < NI; j++) {
+        sc[g][j] = __expf(sc[g][j] - mnew);  // now p (0 for masked tokens)
+        ls += sc[g][j];
+      }
+      lg[g] = lg[g] * corr + ls;
+#pragma unroll
+      for (int k = 0; k < 8; k++) acc[g][k] *= corr;
+    }
+    // P.V: the lane's own tokens times its 8 dims.
+#pragma unroll
+    for (int j = 0; j < NI; j++) {
+      float f[8];
+      unpack8(vr[j], f);
+#pragma unroll
+      for (int g = 0; g < G; g++)
+#pragma unroll
+        for (int k = 0; k < 8; k++) acc[g][k] += sc[g][j] * f[k];
+    }
+  }
+  // Sum across rows (lanes with the same dim group).
+#pragma unroll
+  for (int g = 0; g < G; g++) {
+    float l = lg[g];
+    if constexpr (LPR == 8) l = xor8_sum(l);
+    lg[g] = xor32_sum(xor16_sum(l));
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+      float v = acc[g][k];
+      if constexpr (LPR == 8) v = xor8_sum(v);
+      acc[g][k] = xor32_sum(xor16_sum(v));
+    }
+  }
+  // Publish this wave to the workgroup (waves without pieces: m = -inf, l = 0).
+  if (ri == 0) {
+#pragma unroll
+    for (int g = 0; g < G; g++) {
+      *reinterpret_cast<float4*>(&pacc[wv][g][8 * dg]) = make_float4(acc[g][0], acc[g][1], acc[g][2], acc[g][3]);
+      *reinterpret_cast<float4*>(&pacc[wv][g][8 * dg + 4]) = make_float4(acc[g][4], acc[g][5], acc[g][6], acc[g][7]);
+    }
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int g = 0; g < G; g++) {
+      pml[wv][g][0] = mg[g];
+      pml[wv][g][1] = lg[g];
+    }
+  }
+  __syncthreads();
+
+  // Slot merge through LDS: wave w takes heads w, w + 8, ...
+  const size_t hb0 = size_t(b) * H + size_t(kvh) * G;
+  for (int g = wv; g < G; g += NWV) {
+    float M = -INFINITY;
+#pragma unroll
+    for (int w = 0; w < NWV; w++) M = fmaxf(M, pml[w][g][0]);
+    float L = 0.f, o[DPL];
+#pragma unroll
+    for (int k = 0; k < DPL; k++) o[k] = 0.f;
+#pragma unroll
+    for (int w = 0; w < NWV; w++) {
+      const float ww = pml[w][g][1] > 0.f ? __expf(pml[w][g][0] - M) : 0.f;
+      L += pml[w][g][1] * ww;
+#pragma unroll
+      for (int k = 0; k < DPL; k++) o[k] += ww * pacc[w][g][lane + k * kWave];
+    }
+    const size_t hb = hb0 + g;
+    if (nact == 1) {
+      const float inv = 1.f / L;
+#pragma unroll
+      for (int k = 0; k < DPL; k++) out[hb * D + lane + k * kWave] = uint16_t(f2bf_bits(o[k] * inv));
+    } else {
+      float* po = part_o + (hb * nsplit + sl) * D;
+#pragma unroll
+      for (int k = 0; k < DPL; k++) st_wt(po + lane + k * kWave, o[k]);
+      if (lane == 0) {
+        st_wt(part_ml + (hb * nsplit + sl) * 2 + 0, M);
+        st_wt(part_ml + (hb * nsplit + sl) * 2 + 1, L);
+      }
+    }
+  }
+  if (nact == 1) return;
+  drain_stores();
+  __syncthreads();
+  if (threadIdx.x == 0) s_ticket = arrive(&counters[blockIdx.y]);
+  __syncthreads();
+  if (s_ticket != unsigned(nact - 1)) return;
+
+  // Last slot: merge the slot partials, heads spread over the waves. Each
+  // batch of up to MAXC partials (maxima, sums and vectors together) is loaded
+  // before any of it is used and folded in with a running maximum, so a merge
+  // of <= MAXC slots is one memory round trip (a separate pass for the global
+  // maximum first cost a second one).
+  for (int g = wv; g < G; g += NWV) {
+    const size_t hb = hb0 + g;
+    const float* ml = part_ml + hb * nsplit * 2;
+    float M = -INFINITY;
+    float L = 0.f, o[DPL];
+#pragma unroll
+    for (int k = 0; k < DPL; k++) o[k] = 0.f;
+    for (int c0 = 0; c0 < nact; c0 += MAXC) {
+      float pv[MAXC][DPL], wl[MAXC], ll[MAXC];
+#pragma unroll
+      for (int j = 0; j < MAXC; j++) {
+        const bool ok = c0 + j < nact;
+        const int c = min(c0 + j, nact - 1);
+        wl[j] = ld_wt(ml + 2 * c);
+        ll[j] = ok ? ld_wt(ml + 2 * c + 1) : 0.f;
+#pragma unroll
+        for (int k = 0; k < DPL; k++) pv[j][k] = ld_wt(part_o + (hb * nsplit + c) * D + lane + k * kWave);
+      }
+      float Mb = M;
+#pragma unroll
+      for (int j = 0; j < MAXC; j++)
+        if (ll[j] > 0.f) Mb = fmaxf(Mb, wl[j]);
+      const float rs = M == -INFINITY ? 0.f : __expf(M - Mb);  // rescale what is folded in so far
+      L *= rs;
+#pragma unroll
+      for (int k = 0; k < DPL; k++) o[k] *= rs;
+      M = Mb;
+#pragma unroll
+      for (int j = 0; j < MAXC; j++) {
+        const float ww = ll[j] > 0.f ? __expf(wl[j] - M) : 0.f;
+        L += ll[j] * ww;
+#pragma unroll
+        for (int k = 0; k < DPL; k++) o[k] += ww * pv[j][k];
+      }
+    }
+    const float inv = 1.f / L;
+#pragma unroll
+    for (int k = 0; k < DPL; k++) out[hb * D + lane + k * kWave] = uint16_t(f2bf_bits(o[k] * inv));
+  }
+  if (threadIdx.x == 0) st_wt(&counters[blockIdx.y], 0u);
+}
+
+// Partial slots per head in part_o / part_ml (k_attn's nsplit): the most span
+// slots a launch can have. k_attn writes slot sl < nact <= gridDim.x <= stride:
+// span >= ceil(len / gridDim.x), so nact = ceil(len / span) <= gridDim.x, and
+// attn_slots() never exceeds the stride.
+int attn_part_stride(int max_seq) { return std::min(kAttnSlotCap, (max_seq + kAttnMinSpan - 1) / kAttnMinSpan); }
+
+// Span slots per (row, KV head), k_attn's gridDim.x: about one round of
+// workgroups on the chip. Sized by the batch; the context enters through pos.
+int attn_slots(int B, int Hkv, int max_seq) {
+  return std::max(1, std::min(kAttnTargetWgs / std::max(1, B * Hkv), attn_part_stride(max_seq)));
+}
+
+// Measured on MI355X and rejected; the code is gone, the findings stay. This
+// file reads no environment variables: what ships is the one path below.
+//  - Split-K over workgroups (write-through slabs, arrival ticket, last
+//    arriver combines): the seam costs more than the extra workgroups win at
+//    d_model <= 2048. QKV 8.7 -> 13.5 us, O 7.4 -> 12.0, down 17.3 -> 17.3
+//    (2048-wide config, batch 8).
+//  - Narrow duplicate-column tiles (8 or 4 columns, the other lanes repeating
+//    them): O alone 5.8 -> 5.5 us at batch 1, QKV 6.1 -> 7.8; O and down at
+//    one workgroup per CU 1-4 % slower end to end. 16 everywhere is fastest.
+//  - K parts on QKV and gate/up: batch 1, QKV at 4 columns 0.360 -> 0.373 ms
+//    per step, gate/up 0.368 (8 columns) and 0.391 (4). Their grids already
+//    cover the chip. K parts stay on O and down only (0.372 -> 0.359 ms).
+//  - A 16-token attention piece (128 instead of 234 VGPRs, two workgroups per
+//    CU): small, ctx 1024, b1 0.358 -> 0.365 ms, b16 0.522 -> 0.531, b64
+//    1.125 -> 1.134 (profiles/r03/decode/attn_tok_ab_head.log).
+//  - 8-step load batches: at most 4 k-steps per batch keeps more waves
+//    resident. Batch 1 396 -> 389 us per step, batch 16 unchanged.
+//  - 16-wave workgroups: 8 beats 16 by 20-30 % at K = 5632 (down 9.4 ->
+//    10.5 us); the reduction and barrier cost more than the loads in flight.
+//  - Non-temporal weight loads: 1.75x slower on the 4-layer config, 5 % slower
+//    on the 0.85 GB config (profiles/r02/decode/decode_sweep_s9.log). A decode
+//    step replays the same weights, and the 256 MB MALL keeps them resident.
+//  - One workgroup sharing each weight fragment across the four tiles of a
+//    64-row step: small, 64 rows 1.19 -> 1.26 ms; 16 streams 3.0 K -> 2.7 K
+//    tok/s (profiles/r02/decode/decode_sweep_s10_rowtiles.log). The load
+//    path, not HBM, becomes the limit.
+//  - The argmax merge folded into the LM head's last block: 0.359 -> 0.366 ms
+//    at batch 1, 0.522 -> 0.554 at 16. 1,000 arrivals on one counter cost more
+//    than the launch.
+//  - A persistent O -> gate/up -> down kernel (in-order tile queue,
+//    write-through hand-offs): small b1 0.358 -> 0.61-1.09 ms in every variant
+//    (profiles/r03/decode_block/).
+//  - A two-deep load-batch pipeline (every projection +0.5-1.8 us) and one
+//    workgroup per CU forced through padded LDS (QKV 5.9 -> 9.9 us)
+//    (profiles/r02/decode/decode_sweep_s8.log).
+}  // namespace

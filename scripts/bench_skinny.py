@@ -12,7 +12,6 @@ copy of the same weight tensor (read + write) for the achievable HBM rate.
 from __future__ import annotations
 
 import argparse
-import ctypes
 import json
 import os
 import sys
@@ -33,9 +32,6 @@ def main():
     if a.attn:
         return attn(a)
     lib = ops.lib()
-    vp, i = ctypes.c_void_p, ctypes.c_int
-    lib.p2pt_skinny_bench.argtypes = [vp, vp, vp, i, i, i, i, i, i, vp]
-    lib.p2pt_skinny_bench.restype = ctypes.c_int
     shapes = {"qkv_small": (3072, 2048), "o_small": (2048, 2048), "gate_up_small": (11264, 2048),
               "down_small": (2048, 5632), "lm_head": (32000, 2048), "o_tiny": (1024, 1024)}
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -79,9 +75,6 @@ def main():
 def attn(a):
     """Decode attention alone: K/V bytes per launch vs time, over batch and context."""
     lib = ops.lib()
-    vp, i = ctypes.c_void_p, ctypes.c_int
-    lib.p2pt_attn_bench.argtypes = [vp, vp, vp, vp, i, i, i, i, i, vp, vp, vp, vp, i, vp]
-    lib.p2pt_attn_bench.restype = ctypes.c_int
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     H, Hkv, Smax = 16, 4, 4096
     for D in (128, 64):
@@ -90,7 +83,9 @@ def attn(a):
             vc = torch.randn_like(kc)
             q = torch.randn(B, H * D, device="cuda", dtype=torch.bfloat16)
             out = torch.empty_like(q)
-            nsplit = min(16, -(-Smax // 64))  # decode_fused.hip attn_part_stride: partial slots per row and head
+            dims = ops.LlamaDims(vocab=32, dim=H * D, n_layers=1, H=H, Hkv=Hkv, D=D, ffn=32, max_seq=Smax,
+                                 max_batch=B, eps=1e-5, theta=1e4)
+            nsplit = ops.step_plan(dims, B).attn.stride  # partial slots per row and head
             part_o = torch.empty(B * H * nsplit * D, device="cuda", dtype=torch.float32)
             part_ml = torch.empty(B * H * nsplit * 2, device="cuda", dtype=torch.float32)
             ctr = torch.zeros(B * H, device="cuda", dtype=torch.int32)

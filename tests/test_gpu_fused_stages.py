@@ -36,6 +36,7 @@ emulation with the same rounding points stays inside every bound, and the same
 emulation with one arithmetic slip (a dropped k-step, a RoPE sign, a token too
 few, a wrong split maximum, a swapped gate/up pair) violates it.
 """
+import ctypes
 import functools
 import math
 from dataclasses import dataclass, replace
@@ -43,6 +44,7 @@ from dataclasses import dataclass, replace
 import pytest
 import torch
 
+from p2p_llm_tunnel_amd import ops
 from p2p_llm_tunnel_amd.models.tiny_llm import LlamaConfig, TinyLlama
 
 cuda = pytest.mark.skipif(not torch.cuda.is_available(), reason="needs a HIP device")
@@ -138,40 +140,28 @@ CASES = _cases()
 CASE_IDS = [c.name for c in CASES]
 
 
-def attn_slots(B, Hkv, max_seq):
-    """k_attn's gridDim.x (decode_fused.hip attn_slots / attn_part_stride)."""
-    return max(1, min(256 // max(1, B * Hkv), min(16, (max_seq + 63) // 64)))
+EPI_NAMES = ("STORE", "ROPE", "SILU", "RESID", "ARGMAX")  # decode_fused_kernels.h enum Epi
+STAGES = ("qkv", "attn", "o", "gate_up", "down", "lm_head")
 
 
-def attn_span(length, nslots):
-    span = -(-length // nslots)
-    return max(64, -(-span // 32) * 32)
+@functools.lru_cache(maxsize=None)
+def step_plan(case):
+    """What the library launches for a case: its own plan (host only), never a copy of its rules."""
+    c = case.cfg
+    dims = ops.LlamaDims(vocab=c.vocab, dim=c.dim, n_layers=c.n_layers, H=c.n_heads, Hkv=c.n_kv_heads, D=c.head_dim,
+                         ffn=c.ffn, max_seq=c.max_seq, max_batch=case.max_batch + 1, eps=c.eps, theta=c.rope_theta)
+    return ops.step_plan(dims, case.rows, case.emit_rows)
 
 
-def plan(case):
-    """The instantiations a case launches, read off pick_nw, pick_kparts, launch_nw and attn_slots."""
-    c, M = case.cfg, case.rows
+def fmt(p):
+    """A GemmPlan as ``<nw,tn,EPI,um> kpP``, an AttnPlan as ``k_attn<D,G> N slots``."""
+    if isinstance(p, ops.AttnPlan):
+        return f"k_attn<{p.D},{p.G}> {p.slots} slots"
+    return f"<{p.nw},{p.tn},{EPI_NAMES[p.epi]},{p.um}>" + (f" kp{1 << p.kpl}" if p.kpl else "")
 
-    def kparts(N, K):
-        if N // 16 >= 256:
-            return 0
-        kpl = 1 if N // 8 >= 256 else 2
-        return kpl if (M << kpl) <= 16 and K % (32 << kpl) == 0 else 0
 
-    def skinny(epi, K, kpl=0, tn=1, nw=0):
-        steps = (K >> kpl) // 32
-        nw = nw or (4 if steps <= 16 else 8)
-        per = -(-steps // nw)
-        return f"<{nw},{tn},{epi},{1 if per <= 1 else 2 if per <= 2 else 4}>" + (f" kp{1 << kpl}" if kpl else "")
-
-    hd = c.n_heads * c.head_dim
-    lens = [p + 1 for p in case.pos]
-    ns = attn_slots(M, c.n_kv_heads, c.max_seq)
-    pieces = max(-(-min(attn_span(n, ns), n) // 32) for n in lens)
-    return {"qkv": skinny("ROPE", c.dim), "attn": f"k_attn<{c.head_dim},{c.n_heads // c.n_kv_heads}> "
-            f"{ns} slots, <= {-(-pieces // 8)} pieces/wave",
-            "o": skinny("RESID", hd, kparts(c.dim, hd)), "gate_up": skinny("SILU", c.dim),
-            "down": skinny("RESID", c.ffn, kparts(c.dim, c.ffn)), "lm_head": skinny("ARGMAX", c.dim, tn=2, nw=4)}
+def plan_strings(plan):
+    return tuple(fmt(getattr(plan, s)) for s in STAGES)
 
 
 @dataclass
@@ -462,7 +452,7 @@ def emulate(case, mut=None):
     kc, vc = inp.kc0.clone(), inp.vc0.clone()
     kc[sl, pos], vc[sl, pos] = qk[:, H:], v
 
-    ns = attn_slots(B, Hkv, c.max_seq)
+    ns = step_plan(case).attn.slots
     scale = torch.tensor(1.0 / math.sqrt(D), dtype=torch.float32)
     attn = torch.empty(B, H * D, dtype=BF)
     for b in range(B):
@@ -471,7 +461,7 @@ def emulate(case, mut=None):
             n = max(1, n - 1)
         K, V = kc[sl[b], :n].float(), vc[sl[b], :n].float()
         s = torch.einsum("hgd,lhd->hgl", q[b].float().view(Hkv, G, D), K) * scale
-        span = attn_span(n, ns)
+        span = ops.attn_span(n, ns)
         ms, ls, os_ = [], [], []
         for s0 in range(0, n, span):  # one span slot: its own maximum, sum and weighted V
             seg = s[..., s0:s0 + span]
@@ -513,7 +503,7 @@ MUT_CASES = [c for c in CASES if c.name in ("gemm-d256-f352-r3", "attn-ragged-D6
 
 # A launch with one span slot has no split partials to weight wrongly.
 MUT_PARAMS = [pytest.param(c, m, id=f"{c.name}-{m}") for c in MUT_CASES for m in MUTATIONS
-              if not (m == "wrong_split_max" and attn_slots(c.rows, c.cfg.n_kv_heads, c.cfg.max_seq) == 1)]
+              if not (m == "wrong_split_max" and step_plan(c).attn.slots == 1)]
 
 
 @pytest.mark.parametrize("case,mut", MUT_PARAMS)
@@ -525,6 +515,155 @@ def test_perturbed_emulation_violates_the_bounds(case, mut):
     # ... and no stage downstream of it: each is judged from its own observed inputs.
     clean = {s: r for s, r in ratios.items() if s not in hit and s != "ids"}
     assert max(clean.values()) <= 1.0, ratios
+
+
+# ---------------------------------------------------------------- the plan (CPU: the library, no device)
+# What each case launches (qkv, attn, o, gate_up, down, lm_head), from the Python copy of the host rules that this
+# module held before the library exported its plan (cross-checked against the list in the commit that added the
+# cases). A literal: a change to a heuristic that moves a case off its instantiation fails here.
+_G = ("<4,1,ROPE,2>", "<4,1,SILU,2>", "<4,2,ARGMAX,2>")
+_W = ("<8,1,ROPE,4>", "<8,1,SILU,4>", "<4,2,ARGMAX,4>")
+
+
+def _row(attn, o, down, three=_G):
+    return (three[0], attn, o, three[1], down, three[2])
+
+
+EXPECTED_PLAN = {
+    **{f"gemm-d256-f512-r{r}": _row("k_attn<64,2> 1 slots", "<4,1,RESID,1> kp4", "<4,1,RESID,1> kp4") for r in (1, 4)},
+    **{f"gemm-d256-f512-r{r}": _row("k_attn<64,2> 1 slots", "<4,1,RESID,2>", "<4,1,RESID,4>") for r in (5, 16, 17, 64)},
+    "gemm-d256-f352-r3": _row("k_attn<64,2> 1 slots", "<4,1,RESID,1> kp4", "<4,1,RESID,4>"),
+    "gemm-d256-f2816-r5": _row("k_attn<64,2> 1 slots", "<4,1,RESID,2>", "<8,1,RESID,4>"),
+    "gemm-d1536-f1152-r2": _row("k_attn<64,2> 1 slots", "<4,1,RESID,1> kp4", "<4,1,RESID,4> kp4", _W),
+    "gemm-d2048-r8": _row("k_attn<128,4> 1 slots", "<8,1,RESID,4> kp2", "<4,1,RESID,2> kp2", _W),
+    "gemm-d2048-r9": _row("k_attn<128,4> 1 slots", "<8,1,RESID,4>", "<4,1,RESID,4>", _W),
+    "ids-dup-head": _row("k_attn<64,2> 1 slots", "<4,1,RESID,2>", "<4,1,RESID,4>"),
+    "ids-emit3of5": _row("k_attn<64,2> 1 slots", "<4,1,RESID,2>", "<4,1,RESID,4>"),
+    # ragged: O has K = 2 G D, so its load batch grows with G and D
+    **{f"attn-ragged-D{D}-G{G}": _row(f"k_attn<{D},{G}> 16 slots", f"<4,1,RESID,{um}> kp4", "<4,1,RESID,1> kp4")
+       for D, G, um in ((64, 1, 1), (64, 2, 1), (64, 4, 1), (64, 8, 2), (128, 1, 1), (128, 2, 1), (128, 4, 2),
+                        (128, 8, 4))},
+    **{f"attn-{k}-D{D}-G{G}": _row(f"k_attn<{D},{G}> {n} slots", "<8,1,RESID,4>", "<4,1,RESID,2>")
+       for k, n in (("A", 1), ("B", 2), ("C", 1)) for D in (64, 128) for G in (4, 8)},
+}
+
+# The instantiations the cases launch between them, K parts told apart: 14 k_skinny variants and all 8 k_attn.
+EXPECTED_COVERAGE = {
+    "<4,1,ROPE,2>", "<8,1,ROPE,4>", "<4,1,SILU,2>", "<8,1,SILU,4>", "<4,2,ARGMAX,2>", "<4,2,ARGMAX,4>",
+    "<4,1,RESID,1> kp4", "<4,1,RESID,2>", "<4,1,RESID,2> kp2", "<4,1,RESID,2> kp4", "<4,1,RESID,4>",
+    "<4,1,RESID,4> kp4", "<8,1,RESID,4>", "<8,1,RESID,4> kp2",
+    *(f"k_attn<{D},{G}>" for D in (64, 128) for G in (1, 2, 4, 8)),
+}
+
+
+def _dims(dim, ffn, H, Hkv, D, max_seq, vocab=VOCAB, max_batch=64):
+    return ops.LlamaDims(vocab=vocab, dim=dim, n_layers=2, H=H, Hkv=Hkv, D=D, ffn=ffn, max_seq=max_seq,
+                         max_batch=max_batch, eps=1e-5, theta=1e4)
+
+
+def _shape(p):
+    return (p.nw, p.tn, p.um, 1 << p.kpl, p.grid_x, p.grid_y)
+
+
+def test_plan_of_every_case_is_the_recorded_one():
+    assert set(EXPECTED_PLAN) == set(CASE_IDS)
+    for case in CASES:
+        assert plan_strings(step_plan(case)) == EXPECTED_PLAN[case.name], case.name
+
+
+def test_plan_of_the_small_config():
+    # dim 2048, 16 heads of 128 over 4 KV heads, ffn 5632, vocab 32000: by hand from the rules. 64 k-steps (K 2048)
+    # or 176 (K 5632) are above 16, so 8 waves with load batches of 4; the 2048-wide O and down have 128 16-column
+    # tiles, below the 256 CUs, and 256 8-column ones: 2 K parts while rows * 2 <= 16.
+    small = _dims(2048, 5632, 16, 4, 128, 4096, vocab=32000, max_batch=17)
+    p = ops.step_plan(small, 1)
+    assert _shape(p.qkv) == _shape(p.qkv_first) == (8, 1, 4, 1, 192, 1)
+    assert _shape(p.o) == (8, 1, 4, 2, 256, 1)
+    assert _shape(p.gate_up) == (8, 1, 4, 1, 704, 1)
+    assert _shape(p.down) == (8, 1, 4, 2, 256, 1)
+    assert _shape(p.lm_head) == (4, 2, 4, 1, 1000, 1)
+    assert (p.gate_up.ss_in, p.lm_head.ss_in, p.qkv.ss_in, p.qkv_first.ss_in) == (256, 256, 256, 1)
+    assert (p.o.ss_in, p.down.ss_in, p.am_parts) == (0, 0, 1000)
+    assert (p.attn.D, p.attn.G, p.attn.slots, p.attn.stride, p.attn.grid_y) == (128, 4, 16, 16, 4)
+    p = ops.step_plan(small, 9)
+    assert _shape(p.o) == _shape(p.down) == (8, 1, 4, 1, 128, 1)
+    assert ops.step_plan(small, 16).attn.slots == 4
+    assert ops.lib().p2pt_llama_ws_bytes(small) == 10_674_176
+
+
+def test_cases_cover_the_instantiations_they_claim():
+    got = set()
+    for case in CASES:
+        p = step_plan(case)
+        got |= {fmt(getattr(p, s)) for s in STAGES if s != "attn"} | {fmt(p.attn).split(" ")[0]}
+    assert got == EXPECTED_COVERAGE
+
+
+def _ws_counts(dims):
+    n = len(ops.FusedLlamaDecoder._WS_BUFFERS)
+    off, cnt = (ctypes.c_size_t * n)(), (ctypes.c_size_t * n)()
+    assert ops.lib().p2pt_llama_ws_layout(dims, off, cnt, n) == n
+    return {name: c for (name, _), c in zip(ops.FusedLlamaDecoder._WS_BUFFERS, cnt)}
+
+
+def test_plan_invariants_over_a_sweep():
+    # Every 3rd of the 640 combinations (3 shares no factor with 5, 4, 2, 4, 4, so each value of each axis and
+    # every pair occurs) times 64 row counts times 3 emit_rows: 41,088 plans.
+    grid = [(dim, ffn, D, G, S) for dim in (256, 1024, 1536, 2048, 4096) for ffn in (352, 512, 2816, 5632)
+            for D in (64, 128) for G in (1, 2, 4, 8) for S in (64, 512, 2048, 4096)][::3]
+    M = ops.MAX_ROWS
+    for dim, ffn, D, G, S in grid:
+        dims = _dims(dim, ffn, 2 * G, 2, D, S)
+        count = _ws_counts(dims)
+        for B in range(1, M + 1):
+            for emit in (0, 1, B):
+                p = ops.step_plan(dims, B, emit)
+                assert (p.rows, p.emit_rows) == (B, emit or B)
+                gemms = {s: getattr(p, s) for s in ("qkv_first", "qkv", "o", "gate_up", "down", "lm_head")}
+                for name, g in gemms.items():
+                    rows = p.emit_rows if name == "lm_head" else B
+                    assert g.M == rows and g.nw in (4, 8) and g.um in (1, 2, 4), (name, B)
+                    assert g.grid_x * g.tn * (16 >> g.kpl) == g.N and g.grid_y == -(-g.M // 16), (name, B)
+                    if g.kpl:
+                        assert g.tn == 1 and (g.M << g.kpl) <= 16 and g.K % (32 << g.kpl) == 0, (name, B)
+                    assert g.ss_in * M <= count["ss"]
+                assert p.qkv.kpl == p.gate_up.kpl == p.lm_head.kpl == 0  # K parts on O and down only
+                # a consumer reads exactly the partials its producer wrote
+                assert (p.qkv_first.ss_in, p.o.ss_in, p.down.ss_in) == (1, 0, 0)
+                assert p.gate_up.ss_in == p.o.grid_x
+                assert p.qkv.ss_in == p.lm_head.ss_in == p.down.grid_x
+                assert p.am_parts == p.lm_head.grid_x
+                # ... and everything fits its workspace buffer
+                assert max(p.o.grid_x, p.down.grid_x) * M <= count["ss"]
+                assert p.am_parts * M <= count["am_val"] == count["am_idx"]
+                a = p.attn
+                assert (a.D, a.G, a.grid_y) == (D, G, B * 2) and 1 <= a.slots <= a.stride
+                assert M * dims.H * a.stride * D <= count["part_o"]
+
+
+def test_plan_refuses_what_the_step_refuses():
+    ok = _dims(256, 512, 4, 2, 64, 64)
+    bad = [_dims(256, 512, 4, 2, 96, 64), _dims(256, 512, 6, 2, 64, 64), _dims(48, 512, 4, 2, 64, 64),
+           _dims(256, 520, 4, 2, 64, 64), _dims(256, 512, 4, 2, 64, 64, vocab=500), _dims(256, 512, 4, 2, 64, 0),
+           _dims(256, 512, 4, 2, 64, 64, max_batch=0), _dims(256, 512, 4, 2, 64, 64, vocab=1 << 23)]
+    out = ops.StepPlan()
+    for dims in [ok] + bad:
+        supported = ops.lib().p2pt_llama_ws_bytes(dims) != 0
+        assert supported == (dims is ok)
+        for B in (-1, 0, 1, 16, ops.MAX_ROWS, ops.MAX_ROWS + 1):
+            rc = ops.lib().p2pt_llama_plan(dims, B, 0, out)
+            assert (rc == 0) == (supported and 1 <= B <= ops.MAX_ROWS), (B, rc)
+            if rc:
+                with pytest.raises(ValueError):
+                    ops.step_plan(dims, B)
+
+
+def test_attn_span_rule():
+    for slots in range(1, 17):
+        for n in range(1, 4097):
+            span = ops.attn_span(n, slots)
+            assert span == max(64, -(-(-(-n // slots)) // 32) * 32), (n, slots)
+            assert -(-n // span) <= slots, (n, slots)  # the slots with tokens never exceed the grid
 
 
 # ---------------------------------------------------------------- the kernels (GPU)
@@ -574,7 +713,7 @@ def test_fused_stages_match_fp64(case):
     for a, b in zip(W, inp.weights):  # the decoder's own table is what the references use
         assert torch.equal(a, b)
     ratios = stage_ratios(case, W, obs)
-    print("RATIO", case.name, {k: round(v, 3) for k, v in ratios.items()}, "PLAN", plan(case))
+    print("RATIO", case.name, {k: round(v, 3) for k, v in ratios.items()}, "PLAN", plan_strings(step_plan(case)))
     assert max(ratios.values()) <= 1.0, ratios
     if case.dup_head:  # every maximum ties 64 times over: the first of them is one of the 8 distinct rows
         assert int(obs["ids"].max()) < 8, obs["ids"]
