@@ -30,8 +30,22 @@ to 4; Ollama "options.stop") end a completion at the first match in the
 detokenised text, which is left out (finish_reason "stop"); a streamed
 response holds back only a tail that could still begin one. Parameters that
 would change the output and are not implemented (n > 1, penalties,
-logit_bias, logprobs, Ollama's repeat_penalty, mirostat, ...) are answered
+logit_bias, Ollama's repeat_penalty, mirostat, ...) are answered
 with 400, as is sampling on an engine without the captured HIP step.
+
+Log-probabilities: /v1/chat/completions takes "logprobs": true with
+"top_logprobs" 0..20, /v1/completions the legacy "logprobs" 1..5. They are
+computed on device inside the captured step (ops.logprobs_, logprobs.hip: a
+log-sum-exp and a deterministic top-N selection per requesting row) and come
+back with the sampled ids through pinned memory. The distribution is the
+model's own softmax(logits): it does not depend on temperature, top_k or top_p
+(vLLM's default too). Every delivered token has an entry, the tokens of a
+matched stop sequence included (their text is cut, their entries are not); the
+EOS token has none. A streamed chat response with logprobs sends exactly one
+chunk per token (its "content" is "" when the detokeniser or the stop matcher
+holds the text back). Non-finite values are sent as -9999.0. The eager engine
+has no logits and answers such a request with 400; /api/generate has no
+logprobs.
 
 Two model sources:
 
@@ -111,7 +125,11 @@ _MAX_STOPS = 4  # the OpenAI API's limit
 def sampling_params(body: dict, ollama: bool, default_temperature: float = 0.0) -> Sampling:
     """Sampling of an OpenAI request (top-level temperature / top_p / seed, and
     the common top_k extension) or an Ollama one ("options"). Raises
-    SamplingError for values out of range or parameters not implemented."""
+    SamplingError for values out of range or parameters not implemented.
+
+    "logprobs" and "top_logprobs" are not sampling: this function refuses any
+    non-neutral value of either. The OpenAI endpoints parse them first with
+    ``logprob_params`` and pass this function the body without the two keys."""
     src = body.get("options", {}) if ollama else body
     if src is None:
         src = {}
@@ -126,6 +144,84 @@ def sampling_params(body: dict, ollama: bool, default_temperature: float = 0.0) 
     top_k = _number(src, "top_k", 0, 1 << 30, 0, integer=True)
     seed = _number(src, "seed", -(1 << 63), (1 << 64) - 1, None, integer=True)
     return Sampling(t, top_k, top_p, seed)
+
+
+_LEGACY_MAX_LOGPROBS = 5  # /v1/completions: the OpenAI API's limit for the legacy integer form
+_LOGPROB_KEYS = ("logprobs", "top_logprobs")
+
+
+def logprob_params(body: dict, kind: str) -> int | None:
+    """How many top log-probabilities a request wants beside each chosen
+    token's own: None = no logprobs at all, N in 0..20 = the chosen token's plus
+    the top N. ``kind`` is the endpoint: "chat" takes "logprobs": true with
+    "top_logprobs" in 0..20 (default 0; a non-zero "top_logprobs" without
+    "logprobs": true is refused), "text" the legacy integer "logprobs" in 1..5
+    (null, false and 0 are off), "ollama" has none. Raises SamplingError
+    (answered with 400) naming the offending field."""
+    if kind == "ollama":
+        return None
+    lp = body.get("logprobs")
+    if kind == "chat":
+        if lp is not None and not isinstance(lp, bool) and not (type(lp) is int and lp == 0):  # 0: off, as before
+            raise SamplingError(f"logprobs must be a boolean, got {lp!r}")
+        from p2p_llm_tunnel_amd.ops import MAX_TOP_LOGPROBS
+        top = _number(body, "top_logprobs", 0, MAX_TOP_LOGPROBS, None, integer=True)
+        if not lp:
+            if top:
+                raise SamplingError(f"top_logprobs={top!r} needs logprobs: true")
+            return None
+        return top or 0
+    top = body.get("top_logprobs")
+    if top is not None and not (top == 0 and type(top) is int):
+        raise SamplingError(f"top_logprobs={top!r} belongs to /v1/chat/completions; /v1/completions takes "
+                            f"logprobs: 1..{_LEGACY_MAX_LOGPROBS}")
+    if lp is None or lp is False:
+        return None
+    n = _number(body, "logprobs", 0, _LEGACY_MAX_LOGPROBS, None, integer=True)
+    return n or None
+
+
+def _finite(x: float) -> float:
+    """JSON has no -inf: a non-finite logprob is sent as -9999.0, as the OpenAI API does."""
+    return x if -float("inf") < x < float("inf") else -9999.0
+
+
+def chat_logprob_entry(token: int, record, text_of) -> dict:
+    """One element of a chat response's ``logprobs.content``: ``record`` is
+    ``(chosen_logprob, [(id, logprob), ...])`` as the engine appends it to
+    ``Request.lp``, ``text_of(id)`` the token's text."""
+    def one(tid, lp):
+        text = text_of(tid)
+        return {"token": text, "logprob": _finite(lp), "bytes": list(text.encode("utf-8"))}
+    chosen, top = record
+    entry = one(token, chosen)
+    entry["top_logprobs"] = [one(tid, lp) for tid, lp in top]
+    return entry
+
+
+def chat_logprobs(tokens: list[int], records: list, text_of) -> dict:
+    """``choices[0].logprobs`` of a chat completion."""
+    return {"content": [chat_logprob_entry(t, r, text_of) for t, r in zip(tokens, records)]}
+
+
+def completion_logprobs(tokens: list[int], records: list, text_of, offset: int = 0) -> dict:
+    """``choices[0].logprobs`` of a legacy completion: four lists of one length.
+    ``text_offset`` counts characters of the tokens' own texts from the start
+    of the completion (``offset``: where the first of ``tokens`` starts, for a
+    streamed chunk); ``top_logprobs`` maps token text to logprob (of two ids
+    with the same text the more probable one stays)."""
+    out = {"tokens": [], "token_logprobs": [], "top_logprobs": [], "text_offset": []}
+    for t, (chosen, top) in zip(tokens, records):
+        text = text_of(t)
+        out["tokens"].append(text)
+        out["token_logprobs"].append(_finite(chosen))
+        tops = {}
+        for tid, lp in top:
+            tops.setdefault(text_of(tid), _finite(lp))
+        out["top_logprobs"].append(tops)
+        out["text_offset"].append(offset)
+        offset += len(text)
+    return out
 
 
 def stop_sequences(body: dict, ollama: bool) -> list[str]:
@@ -189,9 +285,19 @@ class StopMatcher:
 class Request:
     """A generation request. Tokens go to ``out`` (a queue ending with None)
     unless ``batched`` is set: then the engine's ``deliver`` hook receives them
-    together with every other batched request's tokens of the same step."""
+    together with every other batched request's tokens of the same step.
+    ``logprobs``: None is off; N in 0..20 asks for each token's log-probability
+    and the top N: the engine appends ``(chosen_logprob, [(id, logprob), ...])``
+    to ``lp`` before it hands the token over."""
 
-    def __init__(self, prompt_ids: list[int], max_new: int, batched: bool = False, sampling: Sampling | None = None):
+    def __init__(self, prompt_ids: list[int], max_new: int, batched: bool = False, sampling: Sampling | None = None,
+                 logprobs: int | None = None):
+        if logprobs is not None:
+            from p2p_llm_tunnel_amd.ops import MAX_TOP_LOGPROBS
+            if isinstance(logprobs, bool) or not isinstance(logprobs, int) or not 0 <= logprobs <= MAX_TOP_LOGPROBS:
+                raise ValueError(f"logprobs must be None or an integer in 0..{MAX_TOP_LOGPROBS}, got {logprobs!r}")
+        self.logprobs = logprobs
+        self.lp: list = []
         self.prompt = prompt_ids
         self.max_new = max_new
         self.out: queue.Queue = queue.Queue()
@@ -208,20 +314,34 @@ _Row = NamedTuple("_Row", [("slot", int), ("token", int), ("pos", int), ("decode
 # Rows of the staging buffer, one column per token row: token (prompt rows),
 # position, cache slot, decode flag, slot to record the sampled id under
 # (scratch for rows that emit nothing), then the sampler's column
-# (temperature bits, top_k, top_p bits, seed, counter; temperature 0 = greedy).
+# (temperature bits, top_k, top_p bits, seed, counter; temperature 0 = greedy),
+# then what the row wants of ops.logprobs_ (0 = nothing, 1 + N = the chosen
+# token's logprob and the top N).
 _TOK, _POS, _SLOT, _DEC, _REC = range(5)
 _SMP = slice(5, 10)
+_LP = 10
+_IN_ROWS = _LP + 1
 
 
 class _StepBuf:
     """Host staging of one in-flight step (two alternate: step k+1 is planned
-    and launched while step k runs); ``h_in`` has the rows named above."""
+    and launched while step k runs); ``h_in`` has the rows named above.
+    ``h_lp`` / ``h_lp_ids`` receive ops.logprobs_'s outputs of the rows that
+    asked (steps that replay a graph with the logprobs kernel)."""
 
-    def __init__(self, rows: int, cuda: bool):
+    def __init__(self, rows: int, cuda: bool, device=None):
+        from p2p_llm_tunnel_amd.ops import MAX_TOP_LOGPROBS
         self.rows = rows
-        self.h_in = torch.zeros((_SMP.stop, rows), dtype=torch.int64, pin_memory=cuda)
+        self.h_in = torch.zeros((_IN_ROWS, rows), dtype=torch.int64, pin_memory=cuda)
         self.np = self.h_in.numpy()
         self.h_out = torch.zeros(rows, dtype=torch.int64, pin_memory=cuda)
+        self.h_lp = torch.zeros((rows, MAX_TOP_LOGPROBS + 1), dtype=torch.float32, pin_memory=cuda)
+        self.h_lp_ids = torch.zeros((rows, MAX_TOP_LOGPROBS), dtype=torch.int32, pin_memory=cuda)
+        # Device twins (captured engines only: the eager step has no logits).
+        self.d_lp = self.d_lp_ids = None
+        if device is not None:
+            self.d_lp = torch.zeros(self.h_lp.shape, dtype=torch.float32, device=device)
+            self.d_lp_ids = torch.zeros(self.h_lp_ids.shape, dtype=torch.int32, device=device)
         self.ev = torch.cuda.Event() if cuda else None
         self.n = 0
         self.emits = []  # (row, req, finished, token index)
@@ -246,8 +366,8 @@ class Engine:
     buffer and an event per step. The host waits on step k (GIL released, so
     the HTTP thread writes meanwhile) only after step k+1 is queued behind it.
     Each step is one hipGraph replay: input copy from pinned staging, decode
-    token gather, the fused step, last-token scatter, ids back to pinned
-    memory.
+    token gather, the fused step, (the sampler, the logprobs kernel,)
+    last-token scatter, ids (and logprobs) back to pinned memory.
 
     ``model`` injects a model object (tests use a CPU stand-in with the same
     ``decode_step`` / ``cfg`` / ``scratch_slot`` / ``device`` surface). One
@@ -279,14 +399,16 @@ class Engine:
         # the 64-row graphs (4 MFMA row tiles), whose LM head covers only the
         # leading rows that sample (at most one per slot: max_batch rows).
         sizes = [small_rows] + ([rows] if rows > small_rows else []) if use_graph else [rows]
-        self._bufs = {R: [_StepBuf(R, cuda), _StepBuf(R, cuda)] for R in sizes}
-        self._d_in = {R: torch.zeros((_SMP.stop, R), dtype=torch.int64, device=self.device) for R in sizes}
+        lp_dev = self.device if use_graph else None
+        self._bufs = {R: [_StepBuf(R, cuda, lp_dev), _StepBuf(R, cuda, lp_dev)] for R in sizes}
+        self._d_in = {R: torch.zeros((_IN_ROWS, R), dtype=torch.int64, device=self.device) for R in sizes}
         # Each graph holds the whole step (_step_body), one per staging buffer
-        # of the pair, so a step is one replay. Steps where some row samples
-        # replay a graph with the sampler kernel after the fused step;
-        # all-greedy steps one without it.
-        self._graphs = {(R, par, smp): self._capture(self._bufs[R][par], 0 if R == small_rows else max_batch, smp)
-                        for R in sizes if use_graph for par in (0, 1) for smp in (False, True)}
+        # of the pair, so a step is one replay. What follows the fused step is
+        # the graph's ``post``: 0 nothing (all-greedy steps), 1 the sampler
+        # (some row samples), 2 the sampler, then the logprobs kernel and its
+        # two copies back (some emitting row's request has logprobs set).
+        self._graphs = {(R, par, post): self._capture(self._bufs[R][par], 0 if R == small_rows else max_batch, post)
+                        for R in sizes if use_graph for par in (0, 1) for post in (0, 1, 2)}
         self.max_batch = max_batch
         self.pending: queue.Queue = queue.Queue()
         self.slots: list[dict | None] = [None] * max_batch
@@ -300,6 +422,8 @@ class Engine:
         self.thread.start()
 
     def submit(self, req: Request) -> Request:
+        if req.logprobs is not None and not self.use_graph:
+            raise ValueError("logprobs need the graph-captured HIP step; this engine runs eagerly")
         self.pending.put(req)
         self._wake.set()
         return req
@@ -372,11 +496,13 @@ class Engine:
             self.slots[i] = None
         return rows, emits
 
-    def _step_body(self, b: _StepBuf, n: int, run, sample_rows: int = 0):
+    def _step_body(self, b: _StepBuf, n: int, run, sample_rows: int = 0, logprobs: bool = False):
         """One step on the first ``n`` rows of ``b``: staging -> device, decode
         rows' tokens gathered from ``last``, the model through ``run(tokens, pos,
         slots) -> (ids, logits)``, (the sampler over the leading ``sample_rows``
-        rows' logits,) last-token scatter, ids -> pinned staging."""
+        rows' logits; with ``logprobs``, the logprobs kernel over the same rows
+        and the sampled ids, and its outputs -> pinned staging,) last-token
+        scatter, ids -> pinned staging."""
         din = self._d_in[b.rows]
         din.copy_(b.h_in, non_blocking=True)
         d = din[:, :n]
@@ -385,17 +511,23 @@ class Engine:
         if sample_rows:
             from p2p_llm_tunnel_amd import ops
             ops.sample_(logits[:sample_rows], ids[:sample_rows], din[_SMP])
+            if logprobs:
+                ops.logprobs_(logits[:sample_rows], ids[:sample_rows], din[_LP], b.d_lp[:sample_rows],
+                              b.d_lp_ids[:sample_rows])
+                b.h_lp.copy_(b.d_lp, non_blocking=True)
+                b.h_lp_ids.copy_(b.d_lp_ids, non_blocking=True)
         self._d_last.index_copy_(0, d[_REC], ids)
         b.h_out[:n].copy_(ids, non_blocking=True)
 
-    def _capture(self, b: _StepBuf, emit_rows: int, sample: bool):
-        """The step on all of ``b``'s rows through ``step_rows``, as a hipGraph."""
+    def _capture(self, b: _StepBuf, emit_rows: int, post: int):
+        """The step on all of ``b``'s rows through ``step_rows``, as a hipGraph;
+        ``post``: what follows the fused step (see ``_graphs``)."""
         from p2p_llm_tunnel_amd.models.tiny_llm import capture
         b.np[:] = 0
         b.np[_SLOT, :] = b.np[_REC, :] = self.model.scratch_slot  # warm-up and capture touch the scratch slot only
         run = functools.partial(self.model.step_rows, emit_rows=emit_rows)
-        sample_rows = (emit_rows or b.rows) if sample else 0
-        graph, _ = capture(lambda: self._step_body(b, b.rows, run, sample_rows), self.device)
+        sample_rows = (emit_rows or b.rows) if post else 0
+        graph, _ = capture(lambda: self._step_body(b, b.rows, run, sample_rows, post == 2), self.device)
         torch.cuda.synchronize(self.device)
         return graph
 
@@ -412,17 +544,21 @@ class Engine:
         h[_DEC, :n] = [r.decode for r in rows]
         h[_REC, :n] = [r.slot if r.emit else scratch for r in rows]
         h[_SMP, :] = 0  # greedy unless an emitting row samples
-        sample = False
+        h[_LP, :] = 0  # no logprobs unless an emitting row's request asks
+        post = 0
         for r, req, _, ctr in emits:
             if not req.sampling.greedy:
                 h[_SMP, r] = req.sampling.column(ctr)
-                sample = True
+                post = max(post, 1)
+            if req.logprobs is not None:
+                h[_LP, r] = 1 + req.logprobs
+                post = 2
         if n < R:  # padding rows: scratch slot, nothing recorded
             h[_TOK, n:R] = h[_POS, n:R] = h[_DEC, n:R] = 0
             h[_SLOT, n:R] = h[_REC, n:R] = scratch
         b.n, b.emits = n, emits
         if self.use_graph:
-            self._graphs[(R, par, sample)].replay()
+            self._graphs[(R, par, post)].replay()
         else:  # injected model (tests): the same step, eagerly, on its n rows; no sampler
             rng = (min(r.pos for r in rows), max(r.pos for r in rows))
             self._step_body(b, n, lambda tok, pos, slots: (
@@ -439,6 +575,9 @@ class Engine:
         for r, req, fin, _ in b.emits:
             if req.cancelled:
                 continue
+            if req.logprobs is not None:  # the record first: the token's consumer finds it there
+                lps = b.h_lp[r, :1 + req.logprobs].tolist()
+                req.lp.append((lps[0], list(zip(b.h_lp_ids[r, :req.logprobs].tolist(), lps[1:]))))
             self._emit(req, out[r], batch)
             req.generated += 1
             self.tokens_out += 1
@@ -507,9 +646,11 @@ class _Stream:
     template around each token piece (token ids render as " t<id>": no JSON
     escaping needed)."""
     __slots__ = ("writer", "stream", "kind", "rid", "pre", "post", "toks", "done", "detok", "reason", "stop",
-                 "stop_hit")
+                 "stop_hit", "lp_toks", "lp_off")
 
-    def __init__(self, writer, stream, kind, rid, model, detok=None, stop=None):
+    def __init__(self, writer, stream, kind, rid, model, detok=None, stop=None, logprobs=False):
+        self.lp_toks = [] if logprobs else None  # with logprobs: the delivered ids; Request.lp[k] belongs to the k-th
+        self.lp_off = 0  # legacy completions, streamed: text_offset of the next token
         self.writer = writer
         self.stream = stream
         self.kind = kind  # "chat" | "text" | "ollama"
@@ -603,6 +744,9 @@ class FrontEnd:
                 st.reason = "stop"
                 self._finish(req, st)
                 continue
+            if st.lp_toks is not None:
+                self._on_token_logprobs(req, st, tok)
+                continue
             if st.stop is not None:
                 piece = st.detok.push(tok) if st.detok is not None else " t%d" % tok
                 text, stopped = st.stop.push(piece)
@@ -622,6 +766,40 @@ class FrontEnd:
             else:
                 body = b" t%d" % tok
             self._emit_piece(st, body)
+
+    def _token_text(self, tid: int) -> str:
+        return self.tok.decode([tid]) if self.tok is not None else " t%d" % tid
+
+    def _on_token_logprobs(self, req, st, tok):
+        """A token of a request with logprobs: its entry goes out with it. A
+        streamed response gets exactly one chunk per token, rendered here
+        (``content`` is "" while the detokeniser or the stop matcher holds the
+        text back); the tokens of a matched stop sequence keep their entries."""
+        record = req.lp[len(st.lp_toks)]  # appended by the engine before it delivered the token
+        st.lp_toks.append(tok)
+        piece = st.detok.push(tok) if st.detok is not None else " t%d" % tok
+        stopped = False
+        if st.stop is not None:
+            piece, stopped = st.stop.push(piece)
+        if st.stream:
+            if st.kind == "chat":
+                choice = {"index": 0, "delta": {"content": piece},
+                          "logprobs": {"content": [chat_logprob_entry(tok, record, self._token_text)]},
+                          "finish_reason": None}
+                obj = {"id": st.rid, "object": "chat.completion.chunk", "model": self.model_name, "choices": [choice]}
+            else:
+                lp = completion_logprobs([tok], [record], self._token_text, st.lp_off)
+                st.lp_off += len(lp["tokens"][0])
+                obj = {"id": st.rid, "object": "text_completion", "model": self.model_name,
+                       "choices": [{"index": 0, "text": piece, "logprobs": lp, "finish_reason": None}]}
+            st.writer.write(_chunk(f"data: {json.dumps(obj, ensure_ascii=False)}\n\n".encode()))
+        elif piece:
+            st.toks.append(_piece(piece))
+        if stopped:  # the engine frees the slot on its next step
+            req.cancelled = True
+            st.reason = "stop"
+            st.stop_hit = True
+            self._finish(req, st)
 
     @staticmethod
     def _emit_piece(st, body: bytes):
@@ -662,6 +840,9 @@ class FrontEnd:
             else:
                 obj = {"id": st.rid, "object": "text_completion", "model": self.model_name,
                        "choices": [{"index": 0, "text": text, "finish_reason": st.reason}]}
+            if st.lp_toks is not None:  # (never an Ollama request)
+                render = chat_logprobs if st.kind == "chat" else completion_logprobs
+                obj["choices"][0]["logprobs"] = render(st.lp_toks, req.lp[:len(st.lp_toks)], self._token_text)
             w.write(self._json_response(obj))
         st.done.set_result(True)
 
@@ -768,7 +949,13 @@ class FrontEnd:
         ollama = path == "/api/generate"
         kind = "ollama" if ollama else ("chat" if "chat" in path else "text")
         try:
-            sampling = sampling_params(req_body, ollama, self.default_temperature)
+            # Logprobs first; sampling_params refuses both keys, so the OpenAI
+            # endpoints hand it the body without them.
+            logprobs = logprob_params(req_body, kind)
+            if logprobs is not None and not self.engine.use_graph:
+                raise SamplingError("logprobs need the graph-captured HIP step; this engine runs eagerly")
+            rest = req_body if ollama else {k: v for k, v in req_body.items() if k not in _LOGPROB_KEYS}
+            sampling = sampling_params(rest, ollama, self.default_temperature)
             stops = stop_sequences(req_body, ollama)
             if not sampling.greedy and not self.engine.use_graph:
                 # The eager step (CPU stand-ins, injected models) has no sampler:
@@ -781,9 +968,9 @@ class FrontEnd:
         stream = bool(req_body.get("stream", ollama))
         rid = ("chatcmpl-" if kind == "chat" else "cmpl-") + uuid.uuid4().hex[:12]
         prompt = _prompt_ids(req_body, self.tok)
-        req = Request(prompt, max(1, min(max_new, 1024)), batched=True, sampling=sampling)
+        req = Request(prompt, max(1, min(max_new, 1024)), batched=True, sampling=sampling, logprobs=logprobs)
         st = _Stream(writer, stream, kind, rid, name, self.tok.detokenizer(prompt) if self.tok is not None else None,
-                     StopMatcher(stops) if stops else None)
+                     StopMatcher(stops) if stops else None, logprobs is not None)
         req.state = st
         if stream:
             writer.write(b"HTTP/1.1 200 OK\r\nContent-Type: %s\r\nCache-Control: no-cache\r\n"

@@ -1,4 +1,5 @@
-"""Python front-end for the gfx950 HIP kernels (``kernels.hip``, ``decode_fused.hip``, ``sample.hip``).
+"""Python front-end for the gfx950 HIP kernels (``kernels.hip``, ``decode_fused.hip``, ``sample.hip``,
+``logprobs.hip``).
 
 The kernels are compiled in-tree into ``_hip_ops.so`` (see ``build.py``) and
 called through ctypes on the current torch stream. Every wrapper validates
@@ -63,6 +64,7 @@ def lib() -> ctypes.CDLL:
         _LIB.p2pt_argmax.argtypes = [vp, vp, i, i, vp]
         _LIB.p2pt_skinny_gemm.argtypes = [vp, vp, vp, i, i, i, vp]
         _LIB.p2pt_sample.argtypes = [vp, vp, vp, i, i, i, vp]
+        _LIB.p2pt_logprobs.argtypes = [vp, vp, vp, vp, vp, i, i, vp]
         _LIB.p2pt_llama_ws_bytes.argtypes = [ctypes.POINTER(LlamaDims)]
         _LIB.p2pt_llama_ws_bytes.restype = ctypes.c_size_t
         szp = ctypes.POINTER(ctypes.c_size_t)
@@ -77,7 +79,7 @@ def lib() -> ctypes.CDLL:
         _LIB.p2pt_skinny_bench.argtypes = [vp, vp, vp, i, i, i, i, i, i, vp]
         _LIB.p2pt_attn_bench.argtypes = [vp, vp, vp, vp, i, i, i, i, i, vp, vp, vp, vp, i, vp]
         for fn in ("p2pt_rmsnorm", "p2pt_silu_mul", "p2pt_rope_qkv_cache", "p2pt_decode_attention", "p2pt_argmax",
-                   "p2pt_skinny_gemm", "p2pt_llama_decode", "p2pt_sample", "p2pt_llama_plan", "p2pt_attn_span",
+                   "p2pt_skinny_gemm", "p2pt_llama_decode", "p2pt_sample", "p2pt_logprobs", "p2pt_llama_plan", "p2pt_attn_span",
                    "p2pt_max_rows", "p2pt_skinny_bench", "p2pt_attn_bench"):
             getattr(_LIB, fn).restype = ctypes.c_int
         if _LIB.p2pt_max_rows() != MAX_ROWS:
@@ -86,6 +88,7 @@ def lib() -> ctypes.CDLL:
 
 
 MAX_ROWS = 64  # token rows per fused step; lib() checks it against decode_fused.hip's kMaxM
+MAX_TOP_LOGPROBS = 20  # top (id, logprob) pairs per row of logprobs_ (logprobs.hip's kMaxTop; the OpenAI API's limit)
 
 
 def step_plan(dims: LlamaDims, B: int, emit_rows: int = 0) -> StepPlan:
@@ -266,6 +269,35 @@ def sample_(logits: torch.Tensor, ids: torch.Tensor, params: torch.Tensor) -> to
         raise ValueError("params need a column per row")
     _ok(lib().p2pt_sample(_p(logits), _p(ids), _p(params), B, params.shape[1], V, _stream(logits)), "sample")
     return ids
+
+
+def logprobs_(logits: torch.Tensor, ids: torch.Tensor, want: torch.Tensor, out_lp: torch.Tensor,
+              out_ids: torch.Tensor) -> None:
+    """Log-probabilities under softmax(logits) (logprobs.hip), for the rows of
+    bf16 ``logits`` [B, V >= 32] that ask: ``want`` (int64 [>= B]) is 0 for a row
+    that is off — its outputs are left as they were — and 1 + N for the chosen
+    token plus the top N (N in 0..MAX_TOP_LOGPROBS; larger values count as the
+    maximum, so callers clamp). ``out_lp`` (float32 [B, 21]): column 0 the
+    logprob of ``ids[b]`` (int64 [B], the id chosen after the sampler, wherever
+    it ranks), columns 1..N the top N, descending. ``out_ids`` (int32 [B, 20]):
+    their ids, ordered by (bf16 value descending, id ascending). The
+    distribution is the model's own: temperature, top-k and top-p play no part."""
+    _check(logits, torch.bfloat16, "logits")
+    _check(ids, torch.int64, "ids", logits.device)
+    _check(want, torch.int64, "want", logits.device)
+    _check(out_lp, torch.float32, "out_lp", logits.device)
+    _check(out_ids, torch.int32, "out_ids", logits.device)
+    if logits.dim() != 2 or ids.shape != (logits.shape[0],) or want.dim() != 1:
+        raise ValueError("need logits [B, V], ids [B], want [>= B]")
+    B, V = logits.shape
+    if B < 1 or V < 32:
+        raise ValueError("need B >= 1 and V >= 32")
+    if want.shape[0] < B:
+        raise ValueError("want needs an entry per row")
+    if out_lp.shape != (B, MAX_TOP_LOGPROBS + 1) or out_ids.shape != (B, MAX_TOP_LOGPROBS):
+        raise ValueError(f"need out_lp [B, {MAX_TOP_LOGPROBS + 1}] and out_ids [B, {MAX_TOP_LOGPROBS}]")
+    _ok(lib().p2pt_logprobs(_p(logits), _p(ids), _p(want), _p(out_lp), _p(out_ids), B, V, _stream(logits)),
+        "logprobs")
 
 
 def f32_bits(x: float) -> int:
