@@ -92,6 +92,13 @@ __device__ __forceinline__ void find_bucket(const T* hist, T need, int* digit_ou
   const T excl = incl - s;
   const bool hit = excl < need && incl >= need;
   const uint64_t b = __ballot(hit);
+  // No hit: the integer select always has one (need <= k < V = the level's total). The float select can miss
+  // when the totals, re-accumulated at this level by unordered atomics, fall short of the `need` carried down,
+  // i.e. when p * Z lies within rounding of the enclosing bucket's end. Lane 63 then takes digit 0 (q == 3
+  // below) with everything else above it, and so on down: the cut ends at the bottom of the enclosing bucket's
+  // key range. No key lies between that and the bucket's lowest token, so the kept set is the bucket and all
+  // above it, whose mass is `need` to within those roundings: the cut an exact sum could have chosen. At the
+  // first level the same reasoning keeps everything (p * Z within rounding of Z).
   const int first = b ? __ffsll((unsigned long long)b) - 1 : 63;
   if (lane == first) {
     T run = excl;

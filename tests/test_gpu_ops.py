@@ -224,8 +224,9 @@ def test_sample_matches_reference_distribution(ops, V, scale, T, k, p):
     """12,800 draws from one logits row vs the fp32 reference distribution:
     a chi-square test (bins of expected count >= 5, the rest pooled) at the
     0.01 % level, and no draw outside the kept set. (Over 20 seeds per case
-    the p-values are uniform — mean 0.43-0.49 — and a host replay of the hash
-    reproduces every draw: profiles/r03/sample_diag.json.)"""
+    the p-values are uniform — mean 0.43-0.49: profiles/r03/sample_diag.json.
+    The host replay of the hash that reproduces every draw is
+    tests/test_gpu_sample.py, which compares ids, not histograms.)"""
     from scipy.stats import chi2
     torch.manual_seed(11)
     row = bf(torch.randn(V, device="cuda") * scale)
