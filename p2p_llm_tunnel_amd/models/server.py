@@ -47,6 +47,13 @@ holds the text back). Non-finite values are sent as -9999.0. The eager engine
 has no logits and answers such a request with 400; /api/generate has no
 logprobs.
 
+Prefix cache (--prefix-cache, off by default): a request whose prompt begins
+like the K/V rows a cache slot already holds — the next turn of a chat, a
+second stream with the same system prompt — takes those rows instead of
+prefilling them again: in place when that slot is free, copied slot to slot on
+the device (ops.kv_copy_, kv_copy.hip) when it is busy; see ``Engine``.
+Non-streamed chat responses then report usage.prompt_tokens_details.cached_tokens.
+
 Two model sources:
 
 * random-init (``--config tiny|small|micro``, the benchmark default): byte-level
@@ -306,6 +313,21 @@ class Request:
         self.batched = batched
         self.sampling = sampling or Sampling()
         self.state = None  # front-end bookkeeping for batched requests
+        self.cached_tokens = 0  # prompt rows taken from the prefix cache (set at admission)
+        self.kv = None  # the engine's slot state of this request (prefix cache: drained ids are recorded there)
+
+
+_MAX_COPY_JOBS = 8  # jobs per ``model.kv_copy`` call (ops.MAX_KV_COPY_JOBS)
+
+
+def _common_prefix(a: list, b: list) -> int:
+    """Length of the longest common prefix of two lists (slices compare at C speed)."""
+    n, i = min(len(a), len(b)), 0
+    while i < n and a[i:min(i + 64, n)] == b[i:min(i + 64, n)]:
+        i = min(i + 64, n)
+    while i < n and a[i] == b[i]:
+        i += 1
+    return i
 
 
 # One token row of a planned step (a decode row's token is read on the device).
@@ -373,13 +395,37 @@ class Engine:
     ``decode_step`` / ``cfg`` / ``scratch_slot`` / ``device`` surface). One
     with ``TinyLlama.step_rows`` on a HIP device runs captured; any other runs
     the same step eagerly through ``decode_step``, without the sampler.
+
+    ``prefix_cache`` (off by default: admission, planning and the slot order
+    are then exactly as described above) reuses K/V rows across requests. Per
+    slot the engine keeps the token ids whose rows at positions 0..n-1 are valid
+    once the work already queued on the stream has run (``_resident``): a row
+    counts from the moment its step is launched, a token once it is a prompt id
+    or a drained output, and the last generated token is never fed back, so it
+    is never resident. A slot keeps its residency after its request finishes,
+    is cancelled or stops, until a new request takes the slot. A new request
+    is matched against every slot's residency (longest common prefix, capped at
+    its length - 1 since the last prompt token must still run to sample, and
+    ignored below ``prefix_min``); the longest match wins, ties go to a free
+    slot. If that slot is free the request is admitted into it at position m
+    (in place, nothing moves); if it is busy the request goes to the
+    least-recently-freed free slot (never-used slots first) and the rows are
+    copied there on the device (``model.kv_copy``: kv_copy.hip, one launch per
+    up to 8 jobs, on the engine's stream between two graph replays, never
+    captured). A request takes what is resident at that moment; it never waits
+    for another request's prefill. The scratch slot never takes part.
+    ``Request.cached_tokens``, ``prefix_hits``, ``cached_tokens`` and
+    ``kv_copies`` (jobs) count the reuse; ``prefill_tokens`` still counts only
+    rows that ran.
     """
 
     def __init__(self, device="cuda:0", config="tiny", max_batch=8, seed=0, use_graph=True, rows=64, model=None,
-                 small_rows=16):
+                 small_rows=16, prefix_cache=False, prefix_min=16):
         if model is None:
             from p2p_llm_tunnel_amd.models.tiny_llm import TinyLlama
             model = TinyLlama(config, device=device, max_batch=max_batch, seed=seed, fused=True)
+        if prefix_cache and not callable(getattr(model, "kv_copy", None)):
+            raise ValueError("prefix_cache needs a model with kv_copy(jobs) (slot-to-slot K/V row copy)")
         # hipGraphs need a model with the capturable step on a HIP device (a
         # loaded checkpoint qualifies; CPU stand-ins in tests run eagerly).
         use_graph = use_graph and model.device.type == "cuda" and hasattr(model, "step_rows")
@@ -418,6 +464,19 @@ class Engine:
         self.steps = 0
         self.tokens_out = 0
         self.prefill_tokens = 0
+        self.prefix_cache = bool(prefix_cache)
+        self.prefix_min = max(1, int(prefix_min))
+        self.prefix_hits = 0  # requests admitted with cached rows
+        self.cached_tokens = 0  # prompt rows not run, over all requests
+        self.kv_copies = 0  # slot-to-slot copy jobs issued
+        # Prefix cache: per slot the state of the request that last took it (its
+        # residency; kept after the slot is freed), whether the slot was busy at
+        # the last admission pass, and the pass-ordered tick at which it was
+        # seen free (least recently freed = smallest).
+        self._kv: list[dict | None] = [None] * max_batch
+        self._was_busy = [False] * max_batch
+        self._freed = [0] * max_batch
+        self._tick = 0
         self.thread = threading.Thread(target=self._loop, daemon=True, name="engine")
         self.thread.start()
 
@@ -433,7 +492,67 @@ class Engine:
         self._wake.set()
         self.thread.join(timeout=10)
 
+    @staticmethod
+    def _resident(s: dict) -> list:
+        """Token ids of the rows of ``s``'s slot that are valid once the queued
+        work has run: the known ids (prompt, then drained outputs) as far as rows
+        were launched."""
+        return s["known"][:min(s["pos"], len(s["known"]))]
+
+    def _admit_prefix(self):
+        """``_admit`` with the prefix cache on (see the class docstring)."""
+        for i, s in enumerate(self.slots):
+            if s is None and self._was_busy[i]:
+                self._was_busy[i] = False
+                self._tick += 1
+                self._freed[i] = self._tick
+        free = [i for i, s in enumerate(self.slots) if s is None]
+        jobs = []
+        max_seq, V = self.model.cfg.max_seq, self.model.cfg.vocab
+        while free:
+            try:
+                req = self.pending.get_nowait()
+            except queue.Empty:
+                break
+            req.max_new = max(1, min(req.max_new, max_seq - 2))  # as in _admit
+            ids = [t % V for t in req.prompt[-(max_seq - req.max_new - 1):]] or [0]
+            m, src = 0, None
+            for i, s in enumerate(self._kv):
+                if s is None:
+                    continue
+                n = min(_common_prefix(ids, self._resident(s)), len(ids) - 1)
+                if n >= self.prefix_min and (n > m or (n == m and self.slots[i] is None and self.slots[src] is not None)):
+                    m, src = n, i
+            if src is not None and self.slots[src] is None:
+                slot = src  # in place
+            else:
+                slot = min(free, key=lambda i: (self._kv[i] is not None, self._freed[i]))
+                if src is not None:
+                    jobs.append((src, slot, m))
+            free.remove(slot)
+            s = {"req": req, "pos": m, "ids": ids, "gen": 0, "known": list(ids)}
+            self.slots[slot] = self._kv[slot] = req.kv = s
+            self._was_busy[slot] = True
+            req.cached_tokens = m
+            if m:
+                self.prefix_hits += 1
+                self.cached_tokens += m
+        # One launch per up to MAX_KV_COPY_JOBS jobs, in admission order; a job
+        # that reads a slot an earlier job of the launch writes (or the reverse)
+        # starts the next launch, so within one no slot is source and destination.
+        launch: list = []
+        for job in jobs + [None]:
+            if launch and (job is None or len(launch) >= _MAX_COPY_JOBS or
+                           any(job[0] == d or job[1] in (a, d) for a, d, _ in launch)):
+                self.model.kv_copy(launch)
+                self.kv_copies += len(launch)
+                launch = []
+            if job is not None:
+                launch.append(job)
+
     def _admit(self):
+        if self.prefix_cache:
+            return self._admit_prefix()
         for i in range(self.max_batch):
             if self.slots[i] is None:
                 try:
@@ -573,6 +692,8 @@ class Engine:
             b.ev.synchronize()  # GIL released: the HTTP thread writes meanwhile
         out = b.h_out[: b.n].tolist() if b.emits else []
         for r, req, fin, _ in b.emits:
+            if self.prefix_cache:  # drained: the id is known (a cancelled request's too: its row may have been fed)
+                req.kv["known"].append(out[r])
             if req.cancelled:
                 continue
             if req.logprobs is not None:  # the record first: the token's consumer finds it there
@@ -837,6 +958,8 @@ class FrontEnd:
                                     "finish_reason": st.reason}],
                        "usage": {"prompt_tokens": len(req.prompt), "completion_tokens": req.generated,
                                  "total_tokens": len(req.prompt) + req.generated}}
+                if self.engine.prefix_cache:  # the OpenAI field; absent with the cache off
+                    obj["usage"]["prompt_tokens_details"] = {"cached_tokens": req.cached_tokens}
             else:
                 obj = {"id": st.rid, "object": "text_completion", "model": self.model_name,
                        "choices": [{"index": 0, "text": text, "finish_reason": st.reason}]}
@@ -982,12 +1105,16 @@ class FrontEnd:
 
 def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_batch=8, model_name=None,
                  engine: Engine | None = None, checkpoint: str | None = None, max_seq: int | None = None,
-                 tokenizer=None, default_temperature: float = 0.0):
+                 tokenizer=None, default_temperature: float = 0.0, prefix_cache: bool = False, prefix_min: int = 16):
     """Engine + HTTP front-end; returns (server, port, engine). ``server.shutdown()``
     stops the HTTP side, ``engine.stop()`` the GPU side. ``checkpoint``: serve a
     Hugging Face Llama checkpoint directory (weights + tokenizer) instead of
     the random-init ``config``. ``tokenizer`` (a ``checkpoint.Tokenizer``)
-    overrides the checkpoint's own or gives an injected engine a text side."""
+    overrides the checkpoint's own or gives an injected engine a text side.
+    ``prefix_cache`` / ``prefix_min``: the engine's prefix cache (``Engine``);
+    an injected ``engine`` brings its own setting, which must not contradict."""
+    if engine is not None and prefix_cache and not engine.prefix_cache:
+        raise ValueError("prefix_cache=True, but the injected engine was built without it")
     sys.setswitchinterval(0.0005)  # two busy threads: bound a GIL wait at 0.5 ms, not 5
     tok = tokenizer
     if checkpoint and engine is None:
@@ -995,9 +1122,11 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
         from p2p_llm_tunnel_amd.models.checkpoint import Tokenizer, load_llama
         model = load_llama(checkpoint, device=device, max_batch=max_batch, max_seq=max_seq)
         tok = tok or Tokenizer.for_checkpoint(checkpoint)
-        engine = Engine(device=device, max_batch=max_batch, model=model)
+        engine = Engine(device=device, max_batch=max_batch, model=model, prefix_cache=prefix_cache,
+                        prefix_min=prefix_min)
         model_name = model_name or os.path.basename(os.path.normpath(checkpoint))
-    engine = engine or Engine(device=device, config=config, max_batch=max_batch)
+    engine = engine or Engine(device=device, config=config, max_batch=max_batch, prefix_cache=prefix_cache,
+                              prefix_min=prefix_min)
     srv = FrontEnd(engine, host, port, model_name or f"p2pt-{config}", tokenizer=tok,
                    default_temperature=default_temperature)
     return srv, srv.server_address[1], engine
@@ -1019,6 +1148,8 @@ def _replicas(a) -> int:
         if a.checkpoint:
             cmd += ["--checkpoint", a.checkpoint] + (["--max-seq", str(a.max_seq)] if a.max_seq else [])
         cmd += ["--default-temperature", str(a.default_temperature)]
+        if a.prefix_cache:
+            cmd += ["--prefix-cache", "--prefix-min", str(a.prefix_min)]
         procs.append(subprocess.Popen(cmd))
     ups = ",".join(f"http://{a.host}:{base + i}" for i in range(a.gpus))
     print(f"{a.gpus} inference endpoints; use: tunnel serve --upstream {ups}", flush=True)
@@ -1054,11 +1185,17 @@ def main(argv=None):
     ap.add_argument("--default-temperature", type=float, default=0.0,
                     help="temperature of requests that set none (0: greedy; requests may set temperature, top_p, "
                          "top_k, seed)")
+    ap.add_argument("--prefix-cache", action="store_true",
+                    help="reuse the K/V rows of a prompt prefix a cache slot already holds (multi-turn chats, "
+                         "shared system prompts) instead of prefilling them again")
+    ap.add_argument("--prefix-min", type=int, default=16, metavar="N",
+                    help="shortest common prefix, in tokens, worth reusing (with --prefix-cache)")
     a = ap.parse_args(argv)
     if a.gpus > 0:
         raise SystemExit(_replicas(a))
     srv, port, engine = start_server(a.host, a.port, a.device, a.config, a.max_batch, checkpoint=a.checkpoint,
-                                     max_seq=a.max_seq, default_temperature=a.default_temperature)
+                                     max_seq=a.max_seq, default_temperature=a.default_temperature,
+                                     prefix_cache=a.prefix_cache, prefix_min=a.prefix_min)
     print(f"inference endpoint on http://{a.host}:{port} ({a.checkpoint or a.config}, {a.device})", flush=True)
     try:
         threading.Event().wait()

@@ -121,6 +121,12 @@ class TinyLlama:
         self.k_cache = torch.zeros(cache_shape, dtype=torch.bfloat16, device=self.device)
         self.v_cache = torch.zeros(cache_shape, dtype=torch.bfloat16, device=self.device)
 
+    def kv_copy(self, jobs) -> None:
+        """Copy K/V rows between cache slots on the current stream: ``jobs`` is a
+        list of ``(src, dst, n)``, rows [0, n) of slot src -> slot dst in every
+        layer (``ops.kv_copy_``, at most ``ops.MAX_KV_COPY_JOBS`` per call)."""
+        ops.kv_copy_(self.k_cache, self.v_cache, jobs)
+
     # ------------------------------------------------------------------ HIP path
     @torch.no_grad()
     def decode_step(self, tokens: torch.Tensor, pos: torch.Tensor, pos_range: tuple[int, int],

@@ -1,5 +1,5 @@
 """Python front-end for the gfx950 HIP kernels (``kernels.hip``, ``decode_fused.hip``, ``sample.hip``,
-``logprobs.hip``).
+``logprobs.hip``, ``kv_copy.hip``).
 
 The kernels are compiled in-tree into ``_hip_ops.so`` (see ``build.py``) and
 called through ctypes on the current torch stream. Every wrapper validates
@@ -65,6 +65,8 @@ def lib() -> ctypes.CDLL:
         _LIB.p2pt_skinny_gemm.argtypes = [vp, vp, vp, i, i, i, vp]
         _LIB.p2pt_sample.argtypes = [vp, vp, vp, i, i, i, vp]
         _LIB.p2pt_logprobs.argtypes = [vp, vp, vp, vp, vp, i, i, vp]
+        _LIB.p2pt_kv_copy.argtypes = [vp, vp, i, i, i, i, i, ctypes.POINTER(ctypes.c_int), vp]
+        _LIB.p2pt_max_kv_copy_jobs.argtypes = []
         _LIB.p2pt_llama_ws_bytes.argtypes = [ctypes.POINTER(LlamaDims)]
         _LIB.p2pt_llama_ws_bytes.restype = ctypes.c_size_t
         szp = ctypes.POINTER(ctypes.c_size_t)
@@ -80,14 +82,18 @@ def lib() -> ctypes.CDLL:
         _LIB.p2pt_attn_bench.argtypes = [vp, vp, vp, vp, i, i, i, i, i, vp, vp, vp, vp, i, vp]
         for fn in ("p2pt_rmsnorm", "p2pt_silu_mul", "p2pt_rope_qkv_cache", "p2pt_decode_attention", "p2pt_argmax",
                    "p2pt_skinny_gemm", "p2pt_llama_decode", "p2pt_sample", "p2pt_logprobs", "p2pt_llama_plan", "p2pt_attn_span",
-                   "p2pt_max_rows", "p2pt_skinny_bench", "p2pt_attn_bench"):
+                   "p2pt_max_rows", "p2pt_skinny_bench", "p2pt_attn_bench", "p2pt_kv_copy", "p2pt_max_kv_copy_jobs"):
             getattr(_LIB, fn).restype = ctypes.c_int
         if _LIB.p2pt_max_rows() != MAX_ROWS:
             raise RuntimeError(f"MAX_ROWS = {MAX_ROWS}, but {path} was built for {_LIB.p2pt_max_rows()} rows")
+        if _LIB.p2pt_max_kv_copy_jobs() != MAX_KV_COPY_JOBS:
+            raise RuntimeError(f"MAX_KV_COPY_JOBS = {MAX_KV_COPY_JOBS}, but {path} was built for "
+                               f"{_LIB.p2pt_max_kv_copy_jobs()} jobs")
     return _LIB
 
 
 MAX_ROWS = 64  # token rows per fused step; lib() checks it against decode_fused.hip's kMaxM
+MAX_KV_COPY_JOBS = 8  # jobs per launch of kv_copy_ (kv_copy.hip's kMaxJobs: they travel in the kernel arguments)
 MAX_TOP_LOGPROBS = 20  # top (id, logprob) pairs per row of logprobs_ (logprobs.hip's kMaxTop; the OpenAI API's limit)
 
 
@@ -298,6 +304,50 @@ def logprobs_(logits: torch.Tensor, ids: torch.Tensor, want: torch.Tensor, out_l
         raise ValueError(f"need out_lp [B, {MAX_TOP_LOGPROBS + 1}] and out_ids [B, {MAX_TOP_LOGPROBS}]")
     _ok(lib().p2pt_logprobs(_p(logits), _p(ids), _p(want), _p(out_lp), _p(out_ids), B, V, _stream(logits)),
         "logprobs")
+
+
+def kv_copy_(k_cache: torch.Tensor, v_cache: torch.Tensor, jobs) -> None:
+    """In-place slot-to-slot copy of K/V rows (kv_copy.hip). The caches are
+    bf16 [n_layers, n_slots, max_seq, Hkv, D]; ``jobs`` is a list of 1..8
+    ``(src, dst, n)``: rows [0, n) of slot ``src`` go to slot ``dst`` in every
+    layer, for K and V, in ONE launch on the current stream (the triples travel
+    in the kernel arguments: no device table, no copy, no sync). Within a call
+    no slot may be both a source and a destination and no destination may
+    repeat, so the result does not depend on the order of the jobs; n == 0
+    moves nothing. Nothing outside the destination rows is written."""
+    _check(k_cache, torch.bfloat16, "k_cache")
+    _check(v_cache, torch.bfloat16, "v_cache", k_cache.device)
+    if k_cache.dim() != 5 or v_cache.dim() != 5:
+        raise ValueError("caches must be [n_layers, n_slots, max_seq, Hkv, D]")
+    if k_cache.shape != v_cache.shape:
+        raise ValueError(f"cache shapes differ: {tuple(k_cache.shape)} and {tuple(v_cache.shape)}")
+    L, n_slots, max_seq, Hkv, D = k_cache.shape
+    if (Hkv * D * 2) % 16 or Hkv * D == 0 or L == 0 or max_seq == 0:
+        raise ValueError("a cache row (Hkv * D bf16) must be a non-empty multiple of 16 bytes")
+    jobs = list(jobs)
+    if not 1 <= len(jobs) <= MAX_KV_COPY_JOBS:
+        raise ValueError(f"need 1..{MAX_KV_COPY_JOBS} jobs, got {len(jobs)}")
+    flat, srcs, dsts = [], set(), set()
+    for job in jobs:
+        if len(job) != 3 or not all(isinstance(x, int) and not isinstance(x, bool) for x in job):
+            raise TypeError(f"a job is (src, dst, n) of ints, got {job!r}")
+        src, dst, n = job
+        if not (0 <= src < n_slots and 0 <= dst < n_slots):
+            raise ValueError(f"job {job!r}: slots must be in [0, {n_slots})")
+        if not 0 <= n <= max_seq:
+            raise ValueError(f"job {job!r}: rows must be in [0, {max_seq}]")
+        if src == dst:
+            raise ValueError(f"job {job!r}: source and destination are the same slot")
+        if dst in dsts:
+            raise ValueError(f"slot {dst} is a destination twice")
+        srcs.add(src)
+        dsts.add(dst)
+        flat += [src, dst, n]
+    if srcs & dsts:
+        raise ValueError(f"slots {sorted(srcs & dsts)} are both a source and a destination in one call")
+    arr = (ctypes.c_int * len(flat))(*flat)
+    _ok(lib().p2pt_kv_copy(_p(k_cache), _p(v_cache), L, n_slots, max_seq, Hkv * D, len(jobs), arr,
+                           _stream(k_cache)), "kv_copy")
 
 
 def f32_bits(x: float) -> int:
