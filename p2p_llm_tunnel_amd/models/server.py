@@ -20,6 +20,7 @@ profiles/bench_gpu_upstream_r01.json.)
   POST /v1/chat/completions  (SSE when "stream": true; JSON otherwise)
   POST /v1/completions       (same, "prompt" instead of "messages")
   POST /api/generate         (Ollama NDJSON stream)
+  POST /v1/embeddings, /api/embed, /api/embeddings  (see "Embeddings" below)
 
 Sampling: temperature / top_p / seed (and the common top_k extension) from an
 OpenAI request, or "options" of an Ollama one, drawn on device after the LM
@@ -53,6 +54,19 @@ second stream with the same system prompt — takes those rows instead of
 prefilling them again: in place when that slot is free, copied slot to slot on
 the device (ops.kv_copy_, kv_copy.hip) when it is busy; see ``Engine``.
 Non-streamed chat responses then report usage.prompt_tokens_details.cached_tokens.
+
+Embeddings: /v1/embeddings (OpenAI: "input" a string, a list of strings, a
+list of token ids or a list of such lists, 1..256 items; "encoding_format"
+"float" or "base64" = little-endian float32 bytes; "dimensions" must equal the
+model's), /api/embed (Ollama: "input" a string or a list of strings;
+"truncate", default true, keeps the first max_seq - 1 tokens) and the legacy
+/api/embeddings ("prompt"). The text is tokenised without a chat template;
+every item is one engine request that prefills and never samples, and its
+final hidden state (after the final norm) is pooled on the device
+(ops.embed_pool_, embed_pool.hip: the mean over all positions, or with
+--embed-pooling last the last position's; L2-normalised). An empty item, or
+one longer than max_seq - 1 tokens where nothing truncates, is answered with
+400 naming the item.
 
 Two model sources:
 
@@ -295,10 +309,19 @@ class Request:
     together with every other batched request's tokens of the same step.
     ``logprobs``: None is off; N in 0..20 asks for each token's log-probability
     and the top N: the engine appends ``(chosen_logprob, [(id, logprob), ...])``
-    to ``lp`` before it hands the token over."""
+    to ``lp`` before it hands the token over.
+    ``embed``: None generates; "mean" or "last" makes it an embedding request,
+    which prefills the prompt's first ``max_seq - 1`` tokens and samples
+    nothing: no token is delivered, and when the terminating None arrives
+    ``embedding`` holds the pooled, L2-normalised final hidden state (float32,
+    ``dim`` values; the mean over all positions, or the last position's)."""
 
     def __init__(self, prompt_ids: list[int], max_new: int, batched: bool = False, sampling: Sampling | None = None,
-                 logprobs: int | None = None):
+                 logprobs: int | None = None, embed: str | None = None):
+        if embed not in (None, "mean", "last"):
+            raise ValueError(f'embed must be None, "mean" or "last", got {embed!r}')
+        self.embed = embed
+        self.embedding = None
         if logprobs is not None:
             from p2p_llm_tunnel_amd.ops import MAX_TOP_LOGPROBS
             if isinstance(logprobs, bool) or not isinstance(logprobs, int) or not 0 <= logprobs <= MAX_TOP_LOGPROBS:
@@ -318,6 +341,7 @@ class Request:
 
 
 _MAX_COPY_JOBS = 8  # jobs per ``model.kv_copy`` call (ops.MAX_KV_COPY_JOBS)
+_MAX_EMBED_JOBS = 16  # jobs per ``model.embed_pool`` call (ops.MAX_EMBED_JOBS)
 
 
 def _common_prefix(a: list, b: list) -> int:
@@ -367,6 +391,10 @@ class _StepBuf:
         self.ev = torch.cuda.Event() if cuda else None
         self.n = 0
         self.emits = []  # (row, req, finished, token index)
+        # Embedding requests that finish in this step: (req, row of h_emb). The
+        # buffers ([max_batch, dim] fp32, device and pinned) come with the first such step.
+        self.embeds = []
+        self.d_emb = self.h_emb = None
 
 
 class Engine:
@@ -417,6 +445,23 @@ class Engine:
     ``Request.cached_tokens``, ``prefix_hits``, ``cached_tokens`` and
     ``kv_copies`` (jobs) count the reuse; ``prefill_tokens`` still counts only
     rows that ran.
+
+    Embedding requests (``Request(embed="mean" | "last")``) prefill and never
+    sample: their rows emit nothing, take no LM-head rows and never touch
+    ``last``, and the slot is freed in the step that runs the last prompt row.
+    After every fused step the decoder's ``resid`` buffer holds the final
+    residual of all rows of the step, so right after the replay of a step with
+    embed rows, before anything else is queued on the stream, the engine
+    launches ``model.embed_pool`` (embed_pool.hip; never captured, one launch
+    per up to 16 jobs, one job per slot: a slot's rows are contiguous and in
+    position order, since non-emitting rows keep their order in the sort). A
+    sequence that spans several steps carries its fp32 sum in the model's
+    ``acc`` row of its slot; the sequences that finish are normalised into the
+    step buffer's ``d_emb`` and come back through one copy into its pinned
+    ``h_emb``, which ``_drain`` hands over after the step's event. With the
+    prefix cache on, an embed request takes no cached prefix (mean pooling needs
+    every row); its own rows become resident like any other request's. Steps
+    without embed rows launch exactly what they launched before.
     """
 
     def __init__(self, device="cuda:0", config="tiny", max_batch=8, seed=0, use_graph=True, rows=64, model=None,
@@ -469,6 +514,9 @@ class Engine:
         self.prefix_hits = 0  # requests admitted with cached rows
         self.cached_tokens = 0  # prompt rows not run, over all requests
         self.kv_copies = 0  # slot-to-slot copy jobs issued
+        self.can_embed = callable(getattr(model, "embed_pool", None))
+        self.embeddings = 0  # embedding requests finished
+        self._pools = []  # _plan -> _launch: the step's (slot, first row, rows, first piece, req when it finishes)
         # Prefix cache: per slot the state of the request that last took it (its
         # residency; kept after the slot is freed), whether the slot was busy at
         # the last admission pass, and the pass-ordered tick at which it was
@@ -483,6 +531,8 @@ class Engine:
     def submit(self, req: Request) -> Request:
         if req.logprobs is not None and not self.use_graph:
             raise ValueError("logprobs need the graph-captured HIP step; this engine runs eagerly")
+        if req.embed is not None and not self.can_embed:
+            raise ValueError("embeddings need a model with embed_pool(jobs, out) (pooling of the final hidden state)")
         self.pending.put(req)
         self._wake.set()
         return req
@@ -515,10 +565,13 @@ class Engine:
             except queue.Empty:
                 break
             req.max_new = max(1, min(req.max_new, max_seq - 2))  # as in _admit
-            ids = [t % V for t in req.prompt[-(max_seq - req.max_new - 1):]] or [0]
+            if req.embed is not None:  # the prompt's head, as in _admit
+                ids = [t % V for t in req.prompt[:max_seq - 1]] or [0]
+            else:
+                ids = [t % V for t in req.prompt[-(max_seq - req.max_new - 1):]] or [0]
             m, src = 0, None
             for i, s in enumerate(self._kv):
-                if s is None:
+                if s is None or req.embed is not None:  # an embed request pools every row: it takes no prefix
                     continue
                 n = min(_common_prefix(ids, self._resident(s)), len(ids) - 1)
                 if n >= self.prefix_min and (n > m or (n == m and self.slots[i] is None and self.slots[src] is not None)):
@@ -530,7 +583,7 @@ class Engine:
                 if src is not None:
                     jobs.append((src, slot, m))
             free.remove(slot)
-            s = {"req": req, "pos": m, "ids": ids, "gen": 0, "known": list(ids)}
+            s = {"req": req, "pos": m, "ids": ids, "gen": 0, "known": list(ids), "embed": req.embed}
             self.slots[slot] = self._kv[slot] = req.kv = s
             self._was_busy[slot] = True
             req.cached_tokens = m
@@ -565,7 +618,9 @@ class Engine:
                 max_seq = self.model.cfg.max_seq
                 req.max_new = max(1, min(req.max_new, max_seq - 2))
                 ids = req.prompt[-(max_seq - req.max_new - 1):] or [0]
-                self.slots[i] = {"req": req, "pos": 0, "ids": ids, "gen": 0}
+                if req.embed is not None:  # nothing is generated: the prompt's head, up to the cache's rows
+                    ids = req.prompt[:max_seq - 1] or [0]
+                self.slots[i] = {"req": req, "pos": 0, "ids": ids, "gen": 0, "embed": req.embed}
 
     def _plan(self, batch: list):
         """Rows of the next step (``_Row``), with the host-side state advanced
@@ -584,14 +639,28 @@ class Engine:
         for i, s in enumerate(self.slots):  # then prompt chunks
             if s is None or s["pos"] >= len(s["ids"]):
                 continue
+            if s["embed"] and s["req"].cancelled:  # it never reaches a decode row: dropped here
+                self._emit(s["req"], None, batch)
+                self.slots[i] = None
+                continue
             take = min(self.rows - len(rows), len(s["ids"]) - s["pos"])
             for p in range(s["pos"], s["pos"] + take):
-                rows.append(_Row(i, s["ids"][p] % V, p, 0, p == len(s["ids"]) - 1))
+                rows.append(_Row(i, s["ids"][p] % V, p, 0, p == len(s["ids"]) - 1 and not s["embed"]))
             if len(rows) >= self.rows:
                 break
         # Rows that sample go first: the 64-row graph's LM head covers only the
         # first max_batch rows (each slot samples at most once per step).
         rows.sort(key=lambda r: not r.emit)
+        # Embed slots: all their rows are non-emitting, so after the (stable)
+        # sort they are still contiguous and in position order.
+        self._pools = pools = []
+        for r, row in enumerate(rows):
+            s = self.slots[row.slot]
+            if s["embed"]:
+                if pools and pools[-1][0] == row.slot:
+                    pools[-1][2] += 1
+                else:
+                    pools.append([row.slot, r, 1, row.pos == 0, None])
         # Advance every row's slot first: after the sort a slot's sampling row
         # can precede its other prompt rows, so slots are only freed once all
         # rows of the step are accounted for.
@@ -611,6 +680,11 @@ class Engine:
             emits.append((r, s["req"], fin, s["gen"] - 1))  # the token's index: the sampler's counter
             if fin:
                 done.append(i)
+        for pool in pools:  # an embed request is done with its last prompt row
+            s = self.slots[pool[0]]
+            if s["pos"] >= len(s["ids"]):
+                pool[4] = s["req"]
+                done.append(pool[0])
         for i in done:
             self.slots[i] = None
         return rows, emits
@@ -682,10 +756,35 @@ class Engine:
             rng = (min(r.pos for r in rows), max(r.pos for r in rows))
             self._step_body(b, n, lambda tok, pos, slots: (
                 self.model.decode_step(tok, pos, rng, slots=slots).to(torch.int64), None))
+        b.embeds = []
+        if self._pools:
+            self._pool(b, self._pools)
         if b.ev is not None:
             b.ev.record()
         self.steps += 1
         return b
+
+    def _pool(self, b: _StepBuf, pools):
+        """Pool the embed rows of the step just queued (see the class docstring)."""
+        if b.h_emb is None:
+            shape = (self.max_batch, self.model.cfg.dim)
+            b.h_emb = torch.zeros(shape, dtype=torch.float32, pin_memory=self.device.type == "cuda")
+            b.d_emb = torch.zeros(shape, dtype=torch.float32, device=self.device)
+        jobs = []
+        for slot, row0, n, first, req in pools:
+            if req is None:  # more rows to come: "mean" carries its sum in acc[slot], "last" waits for the last row
+                if self.slots[slot]["embed"] == "mean":
+                    jobs.append((slot, row0, n, 1 if first else 0, -1))
+                continue
+            if req.embed == "last":
+                row0, n, first = row0 + n - 1, 1, True
+            jobs.append((slot, row0, n, (1 if first else 0) | 2, len(b.embeds)))
+            b.embeds.append((req, len(b.embeds)))
+        for k in range(0, len(jobs), _MAX_EMBED_JOBS):
+            self.model.embed_pool([(row0, n, slot, flags, out_row)
+                                   for slot, row0, n, flags, out_row in jobs[k:k + _MAX_EMBED_JOBS]], b.d_emb)
+        if b.embeds:
+            b.h_emb[:len(b.embeds)].copy_(b.d_emb[:len(b.embeds)], non_blocking=True)
 
     def _drain(self, b: _StepBuf, batch: list):
         if b.ev is not None:
@@ -704,6 +803,10 @@ class Engine:
             self.tokens_out += 1
             if fin:
                 self._emit(req, None, batch)
+        for req, row in b.embeds:
+            req.embedding = b.h_emb[row].numpy().copy()
+            self.embeddings += 1
+            self._emit(req, None, batch)
 
     def _loop(self):
         if self.device.type == "cuda":
@@ -796,11 +899,37 @@ class _Stream:
             self.post = b'", "done": false}\n'
 
 
+class _EmbedBatch:
+    """The items of one embeddings HTTP request on the I/O thread: one engine
+    request each; ``done`` resolves when the last has arrived (True) or the
+    client has gone (False)."""
+    __slots__ = ("writer", "reader", "reqs", "left", "done")
+
+    def __init__(self, writer, reader, reqs):
+        self.writer = writer
+        self.reader = reader
+        self.reqs = reqs
+        self.left = len(reqs)
+        self.done = asyncio.get_running_loop().create_future()
+
+    def gone(self) -> bool:
+        """The client closed the connection. Nothing is written before the last
+        item has arrived, so its end of stream is the only sign there is."""
+        return self.writer.transport.is_closing() or (self.reader is not None and self.reader.at_eof())
+
+
+_MAX_EMBED_INPUTS = 256  # items per embeddings request
+_EMBED_PATHS = ("/v1/embeddings", "/embeddings", "/api/embed", "/api/embeddings")
+
+
 class FrontEnd:
     """HTTP/1.1 server on one asyncio thread (see the module docstring)."""
 
     def __init__(self, engine: Engine, host: str, port: int, model_name: str, tokenizer=None,
-                 default_temperature: float = 0.0):
+                 default_temperature: float = 0.0, embed_pooling: str = "mean"):
+        if embed_pooling not in ("mean", "last"):
+            raise ValueError(f'embed_pooling must be "mean" or "last", got {embed_pooling!r}')
+        self.embed_pooling = embed_pooling
         self.engine = engine
         self.model_name = model_name
         # Temperature of requests that give none. 0 (greedy) by default — the
@@ -852,6 +981,16 @@ class FrontEnd:
         for req, tok in batch:
             st = req.state
             if st is None or st.done.done():
+                continue
+            if req.embed is not None:  # st is the _EmbedBatch of its HTTP request; tok is the terminating None
+                if st.gone():  # client went away: drop the items still queued or running
+                    for r in st.reqs:
+                        r.cancelled = True
+                    st.done.set_result(False)
+                    continue
+                st.left -= 1
+                if st.left == 0:
+                    st.done.set_result(True)
                 continue
             if st.writer.transport.is_closing():  # client went away: free the slot
                 req.cancelled = True
@@ -1013,7 +1152,7 @@ class FrontEnd:
                     break
                 conn = hdrs.get("connection", "").lower()
                 keep = (version == "HTTP/1.1" and conn != "close") or (version == "HTTP/1.0" and conn == "keep-alive")
-                ok = await self._dispatch(method, target.split("?")[0], body, writer)
+                ok = await self._dispatch(method, target.split("?")[0], body, writer, reader)
                 if not ok or not keep:
                     break
                 await writer.drain()
@@ -1037,7 +1176,99 @@ class FrontEnd:
             out += await reader.readexactly(size)
             await reader.readexactly(2)
 
-    async def _dispatch(self, method, path, body, writer) -> bool:
+    def _embed_inputs(self, path: str, body: dict) -> tuple[list[list[int]], str]:
+        """Token ids of every item of an embeddings request and the response's
+        encoding ("float" | "base64"); raises SamplingError (answered with 400)
+        naming the offending field or item."""
+        openai = path in ("/v1/embeddings", "/embeddings")
+        cfg = self.engine.model.cfg
+        limit = cfg.max_seq - 1
+        fmt = "float"
+        if openai:
+            fmt = body.get("encoding_format") or "float"
+            if fmt not in ("float", "base64"):
+                raise SamplingError(f'encoding_format must be "float" or "base64", got {fmt!r}')
+            dims = body.get("dimensions")
+            if dims is not None and (isinstance(dims, bool) or dims != cfg.dim):
+                raise SamplingError(f"dimensions={dims!r} is not supported: this model's embeddings have {cfg.dim}")
+        key = "prompt" if path == "/api/embeddings" else "input"
+        raw = body.get(key)
+        is_ids = lambda v: isinstance(v, list) and bool(v) and all(type(t) is int for t in v)
+        single = isinstance(raw, str) or (openai and is_ids(raw)) or path == "/api/embeddings"
+        if single:
+            raw = [raw]
+        if not isinstance(raw, list) or not 1 <= len(raw) <= _MAX_EMBED_INPUTS:
+            raise SamplingError(f"{key} must be a string or a list of 1..{_MAX_EMBED_INPUTS} items")
+        truncate = True if openai else body.get("truncate", True)
+        if not isinstance(truncate, bool):
+            raise SamplingError(f"truncate must be a boolean, got {truncate!r}")
+        items = []
+        for n, item in enumerate(raw):
+            name = key if single else f"{key}[{n}]"
+            if isinstance(item, str):
+                ids = self.tok.encode(item) if self.tok is not None else list(item.encode("utf-8"))
+            elif openai and isinstance(item, list) and all(type(t) is int for t in item):
+                if not all(0 <= t < cfg.vocab for t in item):
+                    raise SamplingError(f"{name}: token ids must be in [0, {cfg.vocab})")
+                ids = list(item)
+            else:
+                raise SamplingError(f"{name} must be a string" + (" or a list of token ids" if openai else ""))
+            if not ids:
+                raise SamplingError(f"{name} is empty")
+            if len(ids) > limit:
+                if openai or not truncate:
+                    raise SamplingError(f"{name} has {len(ids)} tokens; this model takes at most {limit}")
+                ids = ids[:limit]
+            items.append(ids)
+        return items, fmt
+
+    async def _embeddings(self, path, body, writer, reader=None) -> bool:
+        """POST /v1/embeddings (+ /embeddings), /api/embed and /api/embeddings:
+        every item is one engine request (``Request(embed=)``), and the response
+        is written when all have arrived."""
+        t0 = time.perf_counter_ns()
+
+        def refuse(msg):
+            writer.write(self._json_response({"error": {"message": msg, "type": "invalid_request_error"}}, 400))
+            return True
+        try:
+            req_body = json.loads(body or b"{}")
+        except ValueError:
+            return refuse("the request body is not JSON")
+        if not isinstance(req_body, dict):
+            return refuse("the request body must be a JSON object")
+        if not self.engine.can_embed:
+            return refuse("embeddings need a model with embed_pool (pooling of the final hidden state)")
+        try:
+            items, fmt = self._embed_inputs(path, req_body)
+        except SamplingError as e:
+            return refuse(str(e))
+        reqs = [Request(ids, 1, batched=True, embed=self.embed_pooling) for ids in items]
+        group = _EmbedBatch(writer, reader, reqs)
+        for r in reqs:
+            r.state = group
+            self.engine.submit(r)
+        if not await group.done:
+            return False
+        n_tok = sum(len(ids) for ids in items)
+        if fmt == "base64":
+            import base64
+            vecs = [base64.b64encode(r.embedding.astype("<f4").tobytes()).decode() for r in reqs]
+        else:
+            vecs = [r.embedding.tolist() for r in reqs]
+        if path == "/api/embed":
+            obj = {"model": self.model_name, "embeddings": vecs, "prompt_eval_count": n_tok,
+                   "total_duration": time.perf_counter_ns() - t0}
+        elif path == "/api/embeddings":
+            obj = {"embedding": vecs[0]}
+        else:
+            obj = {"object": "list", "data": [{"object": "embedding", "index": i, "embedding": v}
+                                               for i, v in enumerate(vecs)],
+                   "model": self.model_name, "usage": {"prompt_tokens": n_tok, "total_tokens": n_tok}}
+        writer.write(self._json_response(obj))
+        return True
+
+    async def _dispatch(self, method, path, body, writer, reader=None) -> bool:
         name = self.model_name
         if method in ("GET", "HEAD"):
             if path in ("/v1/models", "/models"):
@@ -1053,6 +1284,8 @@ class FrontEnd:
                 resp = resp[: resp.index(b"\r\n\r\n") + 4]
             writer.write(resp)
             return True
+        if method == "POST" and path in _EMBED_PATHS:
+            return await self._embeddings(path, body, writer, reader)
         if method != "POST" or path not in ("/v1/chat/completions", "/chat/completions", "/v1/completions",
                                             "/api/generate"):
             writer.write(self._json_response({"error": "not found"}, 404))
@@ -1105,14 +1338,17 @@ class FrontEnd:
 
 def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_batch=8, model_name=None,
                  engine: Engine | None = None, checkpoint: str | None = None, max_seq: int | None = None,
-                 tokenizer=None, default_temperature: float = 0.0, prefix_cache: bool = False, prefix_min: int = 16):
+                 tokenizer=None, default_temperature: float = 0.0, prefix_cache: bool = False, prefix_min: int = 16,
+                 embed_pooling: str = "mean"):
     """Engine + HTTP front-end; returns (server, port, engine). ``server.shutdown()``
     stops the HTTP side, ``engine.stop()`` the GPU side. ``checkpoint``: serve a
     Hugging Face Llama checkpoint directory (weights + tokenizer) instead of
     the random-init ``config``. ``tokenizer`` (a ``checkpoint.Tokenizer``)
     overrides the checkpoint's own or gives an injected engine a text side.
     ``prefix_cache`` / ``prefix_min``: the engine's prefix cache (``Engine``);
-    an injected ``engine`` brings its own setting, which must not contradict."""
+    an injected ``engine`` brings its own setting, which must not contradict.
+    ``embed_pooling``: how the embedding routes pool the final hidden state
+    ("mean" over all positions, or the "last" position's)."""
     if engine is not None and prefix_cache and not engine.prefix_cache:
         raise ValueError("prefix_cache=True, but the injected engine was built without it")
     sys.setswitchinterval(0.0005)  # two busy threads: bound a GIL wait at 0.5 ms, not 5
@@ -1128,7 +1364,7 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
     engine = engine or Engine(device=device, config=config, max_batch=max_batch, prefix_cache=prefix_cache,
                               prefix_min=prefix_min)
     srv = FrontEnd(engine, host, port, model_name or f"p2pt-{config}", tokenizer=tok,
-                   default_temperature=default_temperature)
+                   default_temperature=default_temperature, embed_pooling=embed_pooling)
     return srv, srv.server_address[1], engine
 
 
@@ -1150,6 +1386,8 @@ def _replicas(a) -> int:
         cmd += ["--default-temperature", str(a.default_temperature)]
         if a.prefix_cache:
             cmd += ["--prefix-cache", "--prefix-min", str(a.prefix_min)]
+        if getattr(a, "embed_pooling", "mean") != "mean":
+            cmd += ["--embed-pooling", a.embed_pooling]
         procs.append(subprocess.Popen(cmd))
     ups = ",".join(f"http://{a.host}:{base + i}" for i in range(a.gpus))
     print(f"{a.gpus} inference endpoints; use: tunnel serve --upstream {ups}", flush=True)
@@ -1190,12 +1428,16 @@ def main(argv=None):
                          "shared system prompts) instead of prefilling them again")
     ap.add_argument("--prefix-min", type=int, default=16, metavar="N",
                     help="shortest common prefix, in tokens, worth reusing (with --prefix-cache)")
+    ap.add_argument("--embed-pooling", choices=("mean", "last"), default="mean",
+                    help="how /v1/embeddings, /api/embed and /api/embeddings pool the final hidden state: the mean "
+                         "over all positions, or the last position's (both L2-normalised)")
     a = ap.parse_args(argv)
     if a.gpus > 0:
         raise SystemExit(_replicas(a))
     srv, port, engine = start_server(a.host, a.port, a.device, a.config, a.max_batch, checkpoint=a.checkpoint,
                                      max_seq=a.max_seq, default_temperature=a.default_temperature,
-                                     prefix_cache=a.prefix_cache, prefix_min=a.prefix_min)
+                                     prefix_cache=a.prefix_cache, prefix_min=a.prefix_min,
+                                     embed_pooling=a.embed_pooling)
     print(f"inference endpoint on http://{a.host}:{port} ({a.checkpoint or a.config}, {a.device})", flush=True)
     try:
         threading.Event().wait()

@@ -77,6 +77,7 @@ class TinyLlama:
         self.fused = fused
         self._fused = None
         self._graphs = {}  # rows -> (graph, tokens, pos, slots, ids, logits)
+        self._embed_acc = None  # embed_pool's running sums, allocated on first use
         c = self.cfg
         self.device = torch.device(device)
         self.max_batch = max_batch
@@ -126,6 +127,18 @@ class TinyLlama:
         list of ``(src, dst, n)``, rows [0, n) of slot src -> slot dst in every
         layer (``ops.kv_copy_``, at most ``ops.MAX_KV_COPY_JOBS`` per call)."""
         ops.kv_copy_(self.k_cache, self.v_cache, jobs)
+
+    def embed_pool(self, jobs, out: torch.Tensor) -> None:
+        """Pool rows of the last fused step's final hidden state into embeddings
+        on the current stream: ``jobs`` is a list of ``(row0, n, acc, flags,
+        out_row)`` (``ops.embed_pool_``, at most ``ops.MAX_EMBED_JOBS`` per call);
+        ``acc`` indexes this model's own running sums (fp32 [max_batch + 1, dim],
+        one per cache slot), ``out`` is fp32 [n, dim] on the model's device."""
+        if not self.fused:
+            raise ValueError("embed_pool needs the fused path (it reads the fused step's workspace)")
+        if self._embed_acc is None:
+            self._embed_acc = torch.zeros(self.max_batch + 1, self.cfg.dim, dtype=torch.float32, device=self.device)
+        self.fused_decoder().embed_pool(self._embed_acc, out, jobs)
 
     # ------------------------------------------------------------------ HIP path
     @torch.no_grad()
@@ -261,6 +274,12 @@ class TinyLlama:
     @torch.no_grad()
     def reference_logits(self, seqs: torch.Tensor) -> torch.Tensor:
         """fp32 forward of full sequences [B, T]; returns logits of the last position [B, V]."""
+        return self.reference_hidden(seqs)[:, -1] @ self.lm_head.float().T
+
+    @torch.no_grad()
+    def reference_hidden(self, seqs: torch.Tensor) -> torch.Tensor:
+        """fp32 forward of full sequences [B, T]; returns the final normed hidden
+        state of every position [B, T, dim] (what the LM head multiplies)."""
         c = self.cfg
         B, T = seqs.shape
         f32 = lambda t: t.float()
@@ -308,7 +327,7 @@ class TinyLlama:
             residual = bf(residual + m)
             nxt = self.layers[i + 1]["attn_norm"] if i + 1 < len(self.layers) else self.final_norm
             h = bf(rms(residual, nxt))
-        return (h[:, -1] @ f32(self.lm_head).T)
+        return h
 
     @torch.no_grad()
     def generate(self, prompt: list[int], max_new: int) -> list[int]:

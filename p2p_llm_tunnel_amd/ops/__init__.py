@@ -1,5 +1,5 @@
 """Python front-end for the gfx950 HIP kernels (``kernels.hip``, ``decode_fused.hip``, ``sample.hip``,
-``logprobs.hip``, ``kv_copy.hip``).
+``logprobs.hip``, ``kv_copy.hip``, ``embed_pool.hip``).
 
 The kernels are compiled in-tree into ``_hip_ops.so`` (see ``build.py``) and
 called through ctypes on the current torch stream. Every wrapper validates
@@ -67,6 +67,8 @@ def lib() -> ctypes.CDLL:
         _LIB.p2pt_logprobs.argtypes = [vp, vp, vp, vp, vp, i, i, vp]
         _LIB.p2pt_kv_copy.argtypes = [vp, vp, i, i, i, i, i, ctypes.POINTER(ctypes.c_int), vp]
         _LIB.p2pt_max_kv_copy_jobs.argtypes = []
+        _LIB.p2pt_embed_pool.argtypes = [vp, i, i, vp, vp, i, vp, i, f, i, ctypes.POINTER(ctypes.c_int), vp]
+        _LIB.p2pt_max_embed_jobs.argtypes = []
         _LIB.p2pt_llama_ws_bytes.argtypes = [ctypes.POINTER(LlamaDims)]
         _LIB.p2pt_llama_ws_bytes.restype = ctypes.c_size_t
         szp = ctypes.POINTER(ctypes.c_size_t)
@@ -82,18 +84,23 @@ def lib() -> ctypes.CDLL:
         _LIB.p2pt_attn_bench.argtypes = [vp, vp, vp, vp, i, i, i, i, i, vp, vp, vp, vp, i, vp]
         for fn in ("p2pt_rmsnorm", "p2pt_silu_mul", "p2pt_rope_qkv_cache", "p2pt_decode_attention", "p2pt_argmax",
                    "p2pt_skinny_gemm", "p2pt_llama_decode", "p2pt_sample", "p2pt_logprobs", "p2pt_llama_plan", "p2pt_attn_span",
-                   "p2pt_max_rows", "p2pt_skinny_bench", "p2pt_attn_bench", "p2pt_kv_copy", "p2pt_max_kv_copy_jobs"):
+                   "p2pt_max_rows", "p2pt_skinny_bench", "p2pt_attn_bench", "p2pt_kv_copy", "p2pt_max_kv_copy_jobs",
+                   "p2pt_embed_pool", "p2pt_max_embed_jobs"):
             getattr(_LIB, fn).restype = ctypes.c_int
         if _LIB.p2pt_max_rows() != MAX_ROWS:
             raise RuntimeError(f"MAX_ROWS = {MAX_ROWS}, but {path} was built for {_LIB.p2pt_max_rows()} rows")
         if _LIB.p2pt_max_kv_copy_jobs() != MAX_KV_COPY_JOBS:
             raise RuntimeError(f"MAX_KV_COPY_JOBS = {MAX_KV_COPY_JOBS}, but {path} was built for "
                                f"{_LIB.p2pt_max_kv_copy_jobs()} jobs")
+        if _LIB.p2pt_max_embed_jobs() != MAX_EMBED_JOBS:
+            raise RuntimeError(f"MAX_EMBED_JOBS = {MAX_EMBED_JOBS}, but {path} was built for "
+                               f"{_LIB.p2pt_max_embed_jobs()} jobs")
     return _LIB
 
 
 MAX_ROWS = 64  # token rows per fused step; lib() checks it against decode_fused.hip's kMaxM
 MAX_KV_COPY_JOBS = 8  # jobs per launch of kv_copy_ (kv_copy.hip's kMaxJobs: they travel in the kernel arguments)
+MAX_EMBED_JOBS = 16  # jobs per launch of embed_pool_ (embed_pool.hip's kMaxJobs: in the kernel arguments too)
 MAX_TOP_LOGPROBS = 20  # top (id, logprob) pairs per row of logprobs_ (logprobs.hip's kMaxTop; the OpenAI API's limit)
 
 
@@ -350,6 +357,75 @@ def kv_copy_(k_cache: torch.Tensor, v_cache: torch.Tensor, jobs) -> None:
                            _stream(k_cache)), "kv_copy")
 
 
+EMBED_FIRST, EMBED_LAST = 1, 2  # a job's flags: first / last piece of its sequence
+
+
+def embed_pool_(resid: torch.Tensor, norm_weight: torch.Tensor, acc: torch.Tensor, out: torch.Tensor, jobs,
+                eps: float) -> None:
+    """Pool rows of the fused step's final residual into embeddings
+    (embed_pool.hip). ``resid`` is bf16 [rows <= 64, dim], ``norm_weight`` bf16
+    (dim,), ``acc`` fp32 [n_acc, dim] (running sums of sequences that span
+    several steps), ``out`` fp32 [n_out, dim]; ``jobs`` is a list of 1..16
+    ``(row0, n, acc, flags, out_row)`` of plain ints, all in ONE launch on the
+    current stream (the jobs travel in the kernel arguments: no device table,
+    no copy, no sync). A job adds rmsnorm(resid[r]) * norm_weight for r in
+    [row0, row0 + n), in fp32 and in row order, to a sum that starts at zero
+    (``flags & EMBED_FIRST``) or at ``acc[acc]``; with ``flags & EMBED_LAST``
+    the sum, L2-normalised (zeros when its norm is 0 or not finite), goes to
+    ``out[out_row]`` and ``acc`` is not written, otherwise the sum goes back to
+    ``acc[acc]`` and ``out_row`` must be -1. No ``acc`` index and no
+    ``out_row`` may appear twice in a call. Nothing else is written."""
+    _check(resid, torch.bfloat16, "resid")
+    dev = resid.device
+    _check(norm_weight, torch.bfloat16, "norm_weight", dev)
+    _check(acc, torch.float32, "acc", dev)
+    _check(out, torch.float32, "out", dev)
+    if resid.dim() != 2 or not 1 <= resid.shape[0] <= MAX_ROWS:
+        raise ValueError(f"resid must be [rows <= {MAX_ROWS}, dim], got {tuple(resid.shape)}")
+    rows, dim = resid.shape
+    if dim < 8 or dim % 8 or dim > 16384:
+        raise ValueError("dim must be a multiple of 8 and <= 16384")
+    if norm_weight.shape != (dim,):
+        raise ValueError(f"norm_weight shape {tuple(norm_weight.shape)} != ({dim},)")
+    if acc.dim() != 2 or acc.shape[1] != dim or acc.shape[0] < 1 or out.dim() != 2 or out.shape[1] != dim or \
+            out.shape[0] < 1:
+        raise ValueError(f"acc and out must be [n >= 1, {dim}], got {tuple(acc.shape)} and {tuple(out.shape)}")
+    if any(t.data_ptr() % 16 for t in (resid, norm_weight, acc, out)):
+        raise ValueError("resid, norm_weight, acc and out must be 16-byte aligned")
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 0.0 <= eps < float("inf"):
+        raise ValueError(f"eps must be a finite number >= 0, got {eps!r}")
+    jobs = list(jobs)
+    if not 1 <= len(jobs) <= MAX_EMBED_JOBS:
+        raise ValueError(f"need 1..{MAX_EMBED_JOBS} jobs, got {len(jobs)}")
+    flat, accs, outs = [], set(), set()
+    for job in jobs:
+        if not isinstance(job, (tuple, list)) or len(job) != 5 or \
+                not all(isinstance(x, int) and not isinstance(x, bool) for x in job):
+            raise TypeError(f"a job is (row0, n, acc, flags, out_row) of ints, got {job!r}")
+        row0, n, a, flags, out_row = job
+        if n < 1 or row0 < 0 or row0 + n > rows:
+            raise ValueError(f"job {job!r}: rows [row0, row0 + n) must be non-empty and inside [0, {rows})")
+        if not 0 <= a < acc.shape[0]:
+            raise ValueError(f"job {job!r}: acc must be in [0, {acc.shape[0]})")
+        if not 0 <= flags <= (EMBED_FIRST | EMBED_LAST):
+            raise ValueError(f"job {job!r}: flags must be a combination of EMBED_FIRST and EMBED_LAST")
+        if flags & EMBED_LAST:
+            if not 0 <= out_row < out.shape[0]:
+                raise ValueError(f"job {job!r}: out_row must be in [0, {out.shape[0]})")
+            if out_row in outs:
+                raise ValueError(f"out row {out_row} appears twice")
+            outs.add(out_row)
+        elif out_row != -1:
+            raise ValueError(f"job {job!r}: a job without EMBED_LAST writes no out row (out_row must be -1)")
+        if a in accs:
+            raise ValueError(f"acc row {a} appears twice")
+        accs.add(a)
+        flat += [row0, n, a, flags, out_row]
+    arr = (ctypes.c_int * len(flat))(*flat)
+    _ok(lib().p2pt_embed_pool(_p(resid), rows, dim, _p(norm_weight), _p(acc), acc.shape[0], _p(out), out.shape[0],
+                              float(eps), len(jobs), arr, _stream(resid)), "embed_pool")
+
+
 def f32_bits(x: float) -> int:
     """The float32 bit pattern of x as a non-negative int (the sampler's params encoding)."""
     import struct
@@ -406,6 +482,7 @@ class FusedLlamaDecoder:
         self.ws = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
         self.k_cache, self.v_cache = k_cache, v_cache
         self.device = dev
+        self._resid = None  # embed_pool's view of the workspace's resid buffer
 
     # Workspace buffers in the order p2pt_llama_ws_layout reports them.
     _WS_BUFFERS = (("resid", torch.bfloat16), ("q", torch.bfloat16), ("attn", torch.bfloat16), ("h", torch.bfloat16),
@@ -436,6 +513,14 @@ class FusedLlamaDecoder:
                   "part_o": (M, d.H, -1, d.D), "part_ml": (M, d.H, -1, 2), "am_val": (-1, M), "am_idx": (-1, M),
                   "counters": (M * d.H,)}
         return {name: v.view(*shapes[name]) for name, v in views.items()}
+
+    def embed_pool(self, acc: torch.Tensor, out: torch.Tensor, jobs) -> None:
+        """``embed_pool_`` over the rows the last ``step`` left in ``resid`` (the
+        final residual of every row, prefill rows included), with the final-norm
+        weight and this model's eps."""
+        if self._resid is None:
+            self._resid = self.workspace_views()["resid"]
+        embed_pool_(self._resid, self.weights[1], acc, out, jobs, self.dims.eps)
 
     def step(self, tokens: torch.Tensor, pos: torch.Tensor, logits: torch.Tensor, ids: torch.Tensor,
              slots: torch.Tensor | None = None, emit_rows: int = 0) -> None:
