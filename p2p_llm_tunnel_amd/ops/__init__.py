@@ -239,6 +239,8 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
         raise ValueError("n_heads / n_kv_heads must be an integer <= 8")
     if lens.shape != (B,):
         raise ValueError("lens must be [B]")
+    if isinstance(chunk, bool) or not isinstance(chunk, int) or chunk <= 0:
+        raise ValueError(f"chunk must be a positive int, got {chunk!r}")
     if max_len is None:
         max_len = int(lens.max().item())
         if int(lens.min().item()) < 1:
@@ -255,7 +257,11 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
 
 
 def argmax(logits: torch.Tensor) -> torch.Tensor:
-    """Row-wise argmax (first index on ties) of bf16 logits [B, V] -> int64 [B]."""
+    """Row-wise argmax (first index on ties) of bf16 logits [B, V] -> int64 [B].
+
+    Every id is in [0, V). NaN never wins: the winner is the first index of the
+    largest non-NaN entry (-0.0 and +0.0 compare equal). A row with no winner
+    (nothing above -inf: all -inf, all NaN or a mix of the two) returns 0."""
     _check(logits, torch.bfloat16, "logits")
     if logits.dim() != 2:
         raise ValueError("logits must be [B, V]")

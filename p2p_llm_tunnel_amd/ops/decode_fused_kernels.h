@@ -460,7 +460,7 @@ __global__ __launch_bounds__(256) void k_argmax_merge(const float* __restrict__ 
         b = sb[w];
         i = si[w];
       }
-    ids[m] = i;
+    ids[m] = i == 0x7fffffff ? 0 : i;  // a row of NaN logits has no winner: id 0, never out of range
   }
 }
 

@@ -284,7 +284,9 @@ __global__ __launch_bounds__(256) void k_argmax(const uint16_t* __restrict__ log
   }
   for (int i = vv * 8 + threadIdx.x; i < V; i += 256) {
     float f = bf2f(x[i]);
-    if (f > best || (f == best && i < bi)) {
+    // Strict here too: a thread's tail indices ascend and lie past its vector ones, and an
+    // equality clause would let a -inf entry "win" against the initial -inf.
+    if (f > best) {
       best = f;
       bi = i;
     }
@@ -303,7 +305,7 @@ __global__ __launch_bounds__(256) void k_argmax(const uint16_t* __restrict__ log
         best = sb[w];
         bi = si[w];
       }
-    out[row] = bi;
+    out[row] = bi == 0x7fffffff ? 0 : bi;  // no entry above -inf (all -inf and/or NaN): id 0, never out of range
   }
 }
 
