@@ -20,7 +20,15 @@ Name mapping (HF ``LlamaForCausalLM`` → ours, see ``tiny_llm.py``):
 ``...mlp.down_proj.weight``                              ``layers[i]["w_down"]``
 ``model.norm.weight``                                    ``final_norm``
 ``lm_head.weight`` (or the embedding when tied)          ``lm_head``
+``...self_attn.q_norm.weight`` (Qwen3 only)              ``layers[i]["q_norm"]``
+``...self_attn.k_norm.weight`` (Qwen3 only)              ``layers[i]["k_norm"]``
 =====================================================  ===========================
+
+``Qwen3ForCausalLM`` (dense) is the Llama layout plus a per-head RMSNorm over
+``head_dim`` on q and k before RoPE (``LlamaConfig.qk_norm``); its ``head_dim``
+comes from the config and need not be ``hidden_size / num_attention_heads``.
+A Llama or Mistral checkpoint that carries these tensors is refused: loading
+it without the norm would compute a different model.
 
 HF Llama q/k projections are already laid out for the rotate-half RoPE
 convention our kernels use (``reference_logits``), so no head permutation is
@@ -35,7 +43,8 @@ import torch
 
 from p2p_llm_tunnel_amd.models.tiny_llm import LlamaConfig, TinyLlama
 
-_SUPPORTED = {"LlamaForCausalLM", "MistralForCausalLM"}
+_SUPPORTED = {"LlamaForCausalLM", "MistralForCausalLM", "Qwen3ForCausalLM"}
+_QK_NORM = {"Qwen3ForCausalLM"}  # per-head RMSNorm on q and k before RoPE
 
 
 def read_config(path: str, max_seq: int | None = None) -> tuple[LlamaConfig, dict]:
@@ -45,6 +54,9 @@ def read_config(path: str, max_seq: int | None = None) -> tuple[LlamaConfig, dic
     with open(f) as fh:
         raw = json.load(fh)
     arch = (raw.get("architectures") or ["LlamaForCausalLM"])[0]
+    if arch == "Qwen3MoeForCausalLM":
+        raise ValueError("unsupported architecture 'Qwen3MoeForCausalLM': mixture-of-experts layers are not "
+                         "supported by the decode kernels (dense Qwen3 only)")
     if arch not in _SUPPORTED:
         raise ValueError(f"unsupported architecture {arch!r} (Llama-style decoders only: {sorted(_SUPPORTED)})")
     # transformers >= 5 writes rope_parameters {rope_theta, rope_type}; older
@@ -57,6 +69,9 @@ def read_config(path: str, max_seq: int | None = None) -> tuple[LlamaConfig, dic
         raise ValueError(f"hidden_act {raw['hidden_act']!r}: only SwiGLU (silu) decoders are supported")
     if raw.get("attention_bias") or raw.get("mlp_bias"):
         raise ValueError("projection biases are not supported by the decode kernels")
+    other = sorted({str(t) for t in raw.get("layer_types") or []} - {"full_attention"})
+    if other:
+        raise ValueError(f"layer_types {other}: only full_attention layers are supported by the decode kernels")
     sw = raw.get("sliding_window")
     if sw and raw.get("use_sliding_window", True):  # full attention == sliding attention up to the window
         max_seq = min(int(max_seq or sw), int(sw))
@@ -67,7 +82,7 @@ def read_config(path: str, max_seq: int | None = None) -> tuple[LlamaConfig, dic
         n_kv_heads=int(raw.get("num_key_value_heads", heads)), head_dim=int(raw.get("head_dim") or dim // heads),
         ffn=int(raw["intermediate_size"]),
         max_seq=int(max_seq or min(int(raw.get("max_position_embeddings", 2048)), 8192)),
-        eps=float(raw.get("rms_norm_eps", 1e-5)), rope_theta=float(theta))
+        eps=float(raw.get("rms_norm_eps", 1e-5)), rope_theta=float(theta), qk_norm=arch in _QK_NORM)
     return cfg, raw
 
 
@@ -161,6 +176,13 @@ def load_llama(path: str, device="cuda", max_batch: int = 8, max_seq: int | None
                 "w_gate_up": torch.cat([gate, up], 0).contiguous(),
                 "w_down": t(p + "mlp.down_proj.weight", (c.dim, c.ffn)),
             })
+            if c.qk_norm:
+                w["layers"][-1]["q_norm"] = t(p + "self_attn.q_norm.weight", (c.head_dim,))
+                w["layers"][-1]["k_norm"] = t(p + "self_attn.k_norm.weight", (c.head_dim,))
+            elif rd.has(p + "self_attn.q_norm.weight") or rd.has(p + "self_attn.k_norm.weight"):
+                raise ValueError(f"{p}self_attn has q_norm / k_norm weights, but the architecture "
+                                 f"{(raw.get('architectures') or ['LlamaForCausalLM'])[0]!r} applies no QK-norm: refusing "
+                                 "to load it without them")
             del q, k, v, gate, up
     finally:
         rd.close()
@@ -242,6 +264,17 @@ class Tokenizer:
             eos = e if isinstance(e, list) else ([e] if e is not None else [])
         except (OSError, ValueError, KeyError):
             pass
+        # generation_config.json may list more (Qwen3: <|im_end|> and <|endoftext|>)
+        gc = os.path.join(path, "generation_config.json")
+        if os.path.exists(gc):
+            try:
+                with open(gc) as fh:
+                    e = json.load(fh).get("eos_token_id")
+                more = e if isinstance(e, list) else ([e] if e is not None else [])
+                eos = list(eos) + [int(x) for x in more if isinstance(x, int) and not isinstance(x, bool)
+                                   and x not in eos]
+            except (OSError, ValueError, AttributeError):
+                pass
         return cls(path, eos)
 
     def encode(self, text: str, special: bool = True) -> list[int]:
@@ -250,13 +283,15 @@ class Tokenizer:
     def decode(self, ids: list[int]) -> str:
         return self.tok.decode(ids, skip_special_tokens=True)
 
-    def chat(self, messages: list[dict]) -> list[int]:
+    def chat(self, messages: list[dict], template_kwargs: dict | None = None) -> list[int]:
         """Prompt ids for a chat: the checkpoint's template with the generation
-        prompt appended, or plain ``role: content`` lines without one."""
+        prompt appended, or plain ``role: content`` lines without one.
+        ``template_kwargs``: extra scalar variables for the template (e.g.
+        ``enable_thinking`` for Qwen3's); they never override the ones set here."""
         msgs = [{"role": str(m.get("role", "user")), "content": str(m.get("content", ""))} for m in messages]
         if self.template is not None:
-            text = self.template.render(messages=msgs, add_generation_prompt=True, bos_token=self.bos,
-                                        eos_token=self.eos)
+            text = self.template.render(**{**(template_kwargs or {}), "messages": msgs, "add_generation_prompt": True,
+                                           "bos_token": self.bos, "eos_token": self.eos})
             return self.encode(text, special=False)
         return self.encode("".join(f"{m['role']}: {m['content']}\n" for m in msgs) + "assistant:")
 

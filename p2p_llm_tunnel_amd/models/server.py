@@ -34,6 +34,10 @@ would change the output and are not implemented (n > 1, penalties,
 logit_bias, Ollama's repeat_penalty, mirostat, ...) are answered
 with 400, as is sampling on an engine without the captured HIP step.
 
+Chat template variables: a chat request's optional "chat_template_kwargs", a
+JSON object of scalars, is handed to the checkpoint's chat template
+({"enable_thinking": false} for Qwen3's); anything else is answered with 400.
+
 Log-probabilities: /v1/chat/completions takes "logprobs": true with
 "top_logprobs" 0..20, /v1/completions the legacy "logprobs" 1..5. They are
 computed on device inside the captured step (ops.logprobs_, logprobs.hip: a
@@ -843,11 +847,30 @@ class Engine:
             self.deliver(batch)
 
 
-def _prompt_ids(body: dict, tok=None) -> list[int]:
+def chat_template_kwargs(body: dict) -> dict | None:
+    """The request's optional ``chat_template_kwargs``: a JSON object of scalars
+    handed to the chat-template render (``{"enable_thinking": false}`` for
+    Qwen3's template). Anything else raises SamplingError (answered with 400)
+    naming the field."""
+    kw = body.get("chat_template_kwargs")
+    if kw is None:
+        return None
+    if not isinstance(kw, dict):
+        raise SamplingError(f"chat_template_kwargs must be a JSON object, got {kw!r}")
+    for k, v in kw.items():
+        if v is not None and not isinstance(v, (bool, int, float, str)):
+            raise SamplingError(f"chat_template_kwargs[{k!r}] must be a scalar (string, number, boolean or null), "
+                                f"got {v!r}")
+    return kw
+
+
+def _prompt_ids(body: dict, tok=None, template_kwargs: dict | None = None) -> list[int]:
     msgs = body.get("messages")
     if tok is not None:
         if isinstance(msgs, list):
-            return tok.chat([m for m in msgs if isinstance(m, dict)]) or [0]
+            msgs = [m for m in msgs if isinstance(m, dict)]
+            # the keyword only when the request carries the field: any tokenizer with chat(messages) still serves
+            return (tok.chat(msgs, template_kwargs=template_kwargs) if template_kwargs else tok.chat(msgs)) or [0]
         return tok.encode(str(body.get("prompt", ""))) or [0]
     if "messages" in body:
         text = "\n".join(str(m.get("content", "")) for m in body.get("messages", []) if isinstance(m, dict))
@@ -1313,6 +1336,7 @@ class FrontEnd:
             rest = req_body if ollama else {k: v for k, v in req_body.items() if k not in _LOGPROB_KEYS}
             sampling = sampling_params(rest, ollama, self.default_temperature)
             stops = stop_sequences(req_body, ollama)
+            template_kwargs = chat_template_kwargs(req_body)
             if not sampling.greedy and not self.engine.use_graph:
                 # The eager step (CPU stand-ins, injected models) has no sampler:
                 # refuse rather than answer a sampled request greedily.
@@ -1323,7 +1347,7 @@ class FrontEnd:
             return True
         stream = bool(req_body.get("stream", ollama))
         rid = ("chatcmpl-" if kind == "chat" else "cmpl-") + uuid.uuid4().hex[:12]
-        prompt = _prompt_ids(req_body, self.tok)
+        prompt = _prompt_ids(req_body, self.tok, template_kwargs)
         req = Request(prompt, max(1, min(max_new, 1024)), batched=True, sampling=sampling, logprobs=logprobs)
         st = _Stream(writer, stream, kind, rid, name, self.tok.detokenizer(prompt) if self.tok is not None else None,
                      StopMatcher(stops) if stops else None, logprobs is not None)

@@ -41,6 +41,7 @@ class LlamaConfig:
     max_seq: int = 2048
     eps: float = 1e-5
     rope_theta: float = 10000.0
+    qk_norm: bool = False  # per-head RMSNorm on q and k before RoPE (Qwen3): layers carry q_norm, k_norm [head_dim]
 
 
 CONFIGS = {
@@ -71,8 +72,9 @@ class TinyLlama:
     def __init__(self, cfg: LlamaConfig | str = "tiny", device="cuda", max_batch: int = 8, seed: int = 0,
                  fused: bool = True, weights: dict | None = None):
         """Random-init weights from ``seed``, or ``weights`` (embed, final_norm,
-        lm_head, layers[{attn_norm, wqkv, wo, ffn_norm, w_gate_up, w_down}],
-        bf16 on ``device``) — see ``checkpoint.load_llama``."""
+        lm_head, layers[{attn_norm, wqkv, wo, ffn_norm, w_gate_up, w_down}, plus
+        q_norm, k_norm when ``cfg.qk_norm``], bf16 on ``device``) — see
+        ``checkpoint.load_llama``."""
         self.cfg = CONFIGS[cfg] if isinstance(cfg, str) else cfg
         self.fused = fused
         self._fused = None
@@ -84,6 +86,11 @@ class TinyLlama:
         if weights is not None:
             self.embed, self.final_norm, self.lm_head = weights["embed"], weights["final_norm"], weights["lm_head"]
             self.layers = weights["layers"]
+            if c.qk_norm:
+                for i, L in enumerate(self.layers):
+                    for n in ("q_norm", "k_norm"):
+                        if n not in L or tuple(L[n].shape) != (c.head_dim,):
+                            raise ValueError(f"layer {i}: a QK-norm model needs {n} of shape ({c.head_dim},)")
             self._alloc_caches()
             return
         g = torch.Generator(device="cpu").manual_seed(seed)
@@ -106,6 +113,9 @@ class TinyLlama:
                 "w_gate_up": w(2 * c.ffn, c.dim, scale=1 / math.sqrt(c.dim)),
                 "w_down": w(c.dim, c.ffn, scale=1 / math.sqrt(c.ffn)),
             })
+            if c.qk_norm:  # drawn well away from 1 and from each other: a missing or swapped weight shows
+                for n in ("q_norm", "k_norm"):
+                    self.layers[-1][n] = (0.5 + torch.rand(c.head_dim, generator=g)).to(torch.bfloat16).to(self.device)
         self.final_norm = norm_w(c.dim)
         self.lm_head = w(c.vocab, c.dim, scale=1 / math.sqrt(c.dim))
         self._alloc_caches()
@@ -169,7 +179,9 @@ class TinyLlama:
         # The fused GEMMs take the RMSNorm weight folded into the following
         # projection's columns (W[n][k] * g[k]), and QKV / gate-up rows
         # interleaved in pairs so a 16-column tile holds both members of a
-        # RoPE pair or a SwiGLU pair; see decode_fused.hip.
+        # RoPE pair or a SwiGLU pair; see decode_fused.hip. A QK-norm model keeps
+        # wqkv's rows in plain order (its RoPE runs in k_qknorm_rope, which pairs
+        # the partners itself) and appends q_norm, k_norm to each layer's six.
         def fold(w, g):
             return (w.float() * g.float()[None, :]).to(torch.bfloat16)
 
@@ -181,8 +193,11 @@ class TinyLlama:
                      + pairs(c.head_dim // 2)[None, :]).flatten()
         ws = [self.embed, self.final_norm, fold(self.lm_head, self.final_norm)]
         for L in self.layers:
-            ws += [L["attn_norm"], fold(L["wqkv"], L["attn_norm"])[head_perm].contiguous(), L["wo"],
+            wqkv = fold(L["wqkv"], L["attn_norm"])
+            ws += [L["attn_norm"], wqkv.contiguous() if c.qk_norm else wqkv[head_perm].contiguous(), L["wo"],
                    L["ffn_norm"], fold(L["w_gate_up"], L["ffn_norm"])[pairs(c.ffn)].contiguous(), L["w_down"]]
+            if c.qk_norm:
+                ws += [L["q_norm"].contiguous(), L["k_norm"].contiguous()]
         return ws
 
     def fused_decoder(self) -> ops.FusedLlamaDecoder:
@@ -190,7 +205,7 @@ class TinyLlama:
             c = self.cfg
             dims = ops.LlamaDims(vocab=c.vocab, dim=c.dim, n_layers=c.n_layers, H=c.n_heads, Hkv=c.n_kv_heads,
                                  D=c.head_dim, ffn=c.ffn, max_seq=c.max_seq, max_batch=self.max_batch + 1, eps=c.eps,
-                                 theta=c.rope_theta)
+                                 theta=c.rope_theta, qk_norm=int(c.qk_norm))
             self._fused = ops.FusedLlamaDecoder(dims, self.fused_weights(), self.k_cache, self.v_cache)
         return self._fused
 
@@ -219,6 +234,11 @@ class TinyLlama:
         for i, L in enumerate(self.layers):
             kc, vc = self.k_cache[i, :B], self.v_cache[i, :B]
             qkv = F.linear(h, L["wqkv"])
+            if c.qk_norm:  # per-head norm with the standalone rmsnorm kernel on [B * heads, D] views
+                nq, nk = c.n_heads * c.head_dim, c.n_kv_heads * c.head_dim
+                qn = ops.rmsnorm(qkv[:, :nq].reshape(-1, c.head_dim), L["q_norm"], c.eps).view(B, nq)
+                kn = ops.rmsnorm(qkv[:, nq:nq + nk].reshape(-1, c.head_dim), L["k_norm"], c.eps).view(B, nk)
+                qkv = torch.cat([qn, kn, qkv[:, nq + nk:]], 1)
             q = ops.rope_qkv_cache(qkv, pos, kc, vc, c.n_heads, c.n_kv_heads, c.head_dim, c.rope_theta,
                                    pos_range=pos_range)
             a = ops.decode_attention(q, kc, vc, lens, max_len=pos_range[1] + 1)
@@ -313,6 +333,8 @@ class TinyLlama:
             k = qkv[..., c.n_heads * c.head_dim: (c.n_heads + c.n_kv_heads) * c.head_dim].view(
                 B, T, c.n_kv_heads, c.head_dim)
             v = qkv[..., (c.n_heads + c.n_kv_heads) * c.head_dim:].view(B, T, c.n_kv_heads, c.head_dim)
+            if c.qk_norm:
+                q, k = rms(q, L["q_norm"]), rms(k, L["k_norm"])
             q, k = bf(rope(q)), bf(rope(k))
             k = k.repeat_interleave(G, dim=2)
             v = v.repeat_interleave(G, dim=2)

@@ -22,7 +22,8 @@ _LIB = None
 class LlamaDims(ctypes.Structure):
     """Mirror of ``LlamaDims`` in decode_fused.hip."""
     _fields_ = [(n, ctypes.c_int) for n in ("vocab", "dim", "n_layers", "H", "Hkv", "D", "ffn", "max_seq",
-                                           "max_batch")] + [("eps", ctypes.c_float), ("theta", ctypes.c_float)]
+                                           "max_batch")] + [("eps", ctypes.c_float), ("theta", ctypes.c_float),
+                                                            ("qk_norm", ctypes.c_int)]
 
 
 _INT = ctypes.c_int
@@ -41,10 +42,11 @@ class AttnPlan(ctypes.Structure):
 
 
 class StepPlan(ctypes.Structure):
-    """Mirror of ``StepPlan``: what one fused step launches (``qkv_first``: layer 0)."""
+    """Mirror of ``StepPlan``: what one fused step launches (``qkv_first``: layer 0; ``qk_norm_grid``:
+    ``k_qknorm_rope``'s gridDim.x, 0 when the model has no QK-norm and the kernel is not launched)."""
     _fields_ = ([("rows", _INT), ("emit_rows", _INT)] +
                 [(n, GemmPlan) for n in ("qkv_first", "qkv", "o", "gate_up", "down", "lm_head")] +
-                [("attn", AttnPlan), ("am_parts", _INT)])
+                [("attn", AttnPlan), ("am_parts", _INT), ("qk_norm_grid", _INT)])
 
 
 def lib() -> ctypes.CDLL:
@@ -60,6 +62,7 @@ def lib() -> ctypes.CDLL:
         _LIB.p2pt_rmsnorm.argtypes = [vp, vp, vp, vp, vp, i, i, f, vp]
         _LIB.p2pt_silu_mul.argtypes = [vp, vp, i, i, vp]
         _LIB.p2pt_rope_qkv_cache.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, f, vp]
+        _LIB.p2pt_qk_norm_rope_cache.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, f, f, vp]
         _LIB.p2pt_decode_attention.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, f, vp]
         _LIB.p2pt_argmax.argtypes = [vp, vp, i, i, vp]
         _LIB.p2pt_skinny_gemm.argtypes = [vp, vp, vp, i, i, i, vp]
@@ -85,7 +88,7 @@ def lib() -> ctypes.CDLL:
         for fn in ("p2pt_rmsnorm", "p2pt_silu_mul", "p2pt_rope_qkv_cache", "p2pt_decode_attention", "p2pt_argmax",
                    "p2pt_skinny_gemm", "p2pt_llama_decode", "p2pt_sample", "p2pt_logprobs", "p2pt_llama_plan", "p2pt_attn_span",
                    "p2pt_max_rows", "p2pt_skinny_bench", "p2pt_attn_bench", "p2pt_kv_copy", "p2pt_max_kv_copy_jobs",
-                   "p2pt_embed_pool", "p2pt_max_embed_jobs"):
+                   "p2pt_embed_pool", "p2pt_max_embed_jobs", "p2pt_qk_norm_rope_cache"):
             getattr(_LIB, fn).restype = ctypes.c_int
         if _LIB.p2pt_max_rows() != MAX_ROWS:
             raise RuntimeError(f"MAX_ROWS = {MAX_ROWS}, but {path} was built for {_LIB.p2pt_max_rows()} rows")
@@ -213,6 +216,69 @@ def rope_qkv_cache(qkv: torch.Tensor, pos: torch.Tensor, k_cache: torch.Tensor, 
     q = torch.empty(B, n_heads, head_dim, dtype=qkv.dtype, device=qkv.device)
     _ok(lib().p2pt_rope_qkv_cache(_p(qkv), _p(pos), _p(q), _p(k_cache), _p(v_cache), B, n_heads, n_kv_heads,
                                   head_dim, Smax, theta, _stream(qkv)), "rope_qkv_cache")
+    return q
+
+
+def qk_norm_rope_cache(qkv: torch.Tensor, pos: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                       q_weight: torch.Tensor, k_weight: torch.Tensor, n_heads: int, n_kv_heads: int, head_dim: int,
+                       eps: float, theta: float, slots: torch.Tensor | None = None,
+                       pos_range: tuple[int, int] | None = None) -> torch.Tensor:
+    """Per-head RMSNorm of q and k (QK-norm models: Qwen3), then RoPE and the cache append: the kernel the
+    fused step of such a model launches after its QKV GEMM (``k_qknorm_rope``), on caller tensors.
+
+    qkv: [B <= 64, (H + 2*Hkv) * D] in plain head order; pos: int32 [B]; caches: [n_slots, Smax, Hkv, D];
+    q_weight, k_weight: (D,), D in {64, 128}. Every q and k head becomes x * rsqrt(mean(x^2) + eps) * weight in
+    fp32, is rotated (rotate-half) at ``pos[b]`` and rounded to bf16 once; v is copied bit for bit. Row b goes
+    to cache slot ``slots[b]`` (int32 [B]; default: slot b, so B <= n_slots). Returns q [B, H, D]. ``pos_range``
+    = host-known (min, max) of ``pos``; without it the bounds are read back from the device (a sync) before
+    launch, as those of ``slots`` always are."""
+    _check(qkv, torch.bfloat16, "qkv")
+    dev = qkv.device
+    _check(pos, torch.int32, "pos", dev)
+    _check(k_cache, torch.bfloat16, "k_cache", dev)
+    _check(v_cache, torch.bfloat16, "v_cache", dev)
+    _check(q_weight, torch.bfloat16, "q_weight", dev)
+    _check(k_weight, torch.bfloat16, "k_weight", dev)
+    for name, v in (("n_heads", n_heads), ("n_kv_heads", n_kv_heads), ("head_dim", head_dim)):
+        if isinstance(v, bool) or not isinstance(v, int) or v <= 0:
+            raise ValueError(f"{name} must be a positive int, got {v!r}")
+    if head_dim not in (64, 128):
+        raise ValueError("head_dim must be 64 or 128")
+    if n_heads % n_kv_heads:
+        raise ValueError("n_heads must be a multiple of n_kv_heads")
+    if qkv.dim() != 2 or qkv.shape[1] != (n_heads + 2 * n_kv_heads) * head_dim:
+        raise ValueError(f"qkv shape {tuple(qkv.shape)} inconsistent with heads")
+    B = qkv.shape[0]
+    if not 1 <= B <= MAX_ROWS:
+        raise ValueError(f"rows must be 1..{MAX_ROWS}")
+    if pos.shape != (B,):
+        raise ValueError("pos must be [B]")
+    if k_cache.dim() != 4 or k_cache.shape[2:] != (n_kv_heads, head_dim) or v_cache.shape != k_cache.shape or \
+            k_cache.shape[0] < 1 or k_cache.shape[1] < 1:
+        raise ValueError(f"cache shape {tuple(k_cache.shape)} != (n_slots, Smax, {n_kv_heads}, {head_dim})")
+    n_slots, Smax = k_cache.shape[0], k_cache.shape[1]
+    for name, wgt in (("q_weight", q_weight), ("k_weight", k_weight)):
+        if wgt.shape != (head_dim,):
+            raise ValueError(f"{name} shape {tuple(wgt.shape)} != ({head_dim},)")
+    if any(t.data_ptr() % 4 for t in (qkv, k_cache, v_cache, q_weight, k_weight)):
+        raise ValueError("qkv, the caches and the weights must be 4-byte aligned")
+    if not (math.isfinite(eps) and eps >= 0.0) or not (math.isfinite(theta) and theta > 0.0):
+        raise ValueError("eps must be finite and >= 0, theta finite and > 0")
+    if slots is not None:
+        _check(slots, torch.int32, "slots", dev)
+        if slots.shape != (B,):
+            raise ValueError("slots must be [B]")
+        if int(slots.min().item()) < 0 or int(slots.max().item()) >= n_slots:
+            raise ValueError(f"slots out of range [0, {n_slots})")
+    elif B > n_slots:
+        raise ValueError(f"{B} rows but {n_slots} cache slots: pass slots")
+    pmin, pmax = pos_range if pos_range is not None else (int(pos.min().item()), int(pos.max().item()))
+    if pmin < 0 or pmax >= Smax:
+        raise ValueError(f"positions out of cache range [0, {Smax})")
+    q = torch.empty(B, n_heads, head_dim, dtype=qkv.dtype, device=dev)
+    _ok(lib().p2pt_qk_norm_rope_cache(_p(qkv), _p(pos), _p(slots), _p(q_weight), _p(k_weight), _p(q), _p(k_cache),
+                                      _p(v_cache), B, n_heads, n_kv_heads, head_dim, Smax, n_slots, float(eps),
+                                      float(theta), _stream(qkv)), "qk_norm_rope_cache")
     return q
 
 
@@ -460,7 +526,8 @@ def skinny_gemm(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
 
 
 class FusedLlamaDecoder:
-    """Host handle for the fused decode step (decode_fused.hip): 5 kernels per layer + 3.
+    """Host handle for the fused decode step (decode_fused.hip): 5 kernels per layer + 3
+    (6 per layer with ``dims.qk_norm``: the per-head q/k RMSNorm of Qwen3 runs in a kernel of its own).
 
     Holds the weight pointer table and a zero-initialised workspace; ``step``
     validates the per-call tensors and launches on the current stream (capturable
@@ -477,9 +544,16 @@ class FusedLlamaDecoder:
             raise ValueError("cache shape does not match dims")
         _check(k_cache, torch.bfloat16, "k_cache", dev)
         _check(v_cache, torch.bfloat16, "v_cache", dev)
-        if len(weights) != 3 + 6 * dims.n_layers:
-            raise ValueError("weight table: embed, final_norm, lm_head, then 6 per layer "
-                             "(wqkv, w_gate_up and lm_head with the preceding norm weight folded in)")
+        per_layer = 8 if dims.qk_norm else 6
+        if len(weights) != 3 + per_layer * dims.n_layers:
+            raise ValueError(f"weight table: embed, final_norm, lm_head, then {per_layer} per layer "
+                             "(wqkv, w_gate_up and lm_head with the preceding norm weight folded in"
+                             + ("; q_norm and k_norm last)" if dims.qk_norm else ")"))
+        if dims.qk_norm:
+            for L in range(dims.n_layers):
+                for j in (6, 7):
+                    if weights[3 + 8 * L + j].shape != (dims.D,):
+                        raise ValueError(f"layer {L}: q_norm and k_norm must be ({dims.D},)")
         nbytes = lib().p2pt_llama_ws_bytes(ctypes.byref(dims))
         if nbytes == 0:
             raise ValueError("model dims not supported by the fused decode kernels")
@@ -493,7 +567,8 @@ class FusedLlamaDecoder:
     # Workspace buffers in the order p2pt_llama_ws_layout reports them.
     _WS_BUFFERS = (("resid", torch.bfloat16), ("q", torch.bfloat16), ("attn", torch.bfloat16), ("h", torch.bfloat16),
                    ("ss", torch.float32), ("part_o", torch.float32), ("part_ml", torch.float32),
-                   ("am_val", torch.float32), ("am_idx", torch.int32), ("counters", torch.int32))
+                   ("am_val", torch.float32), ("am_idx", torch.int32), ("counters", torch.int32),
+                   ("qkv", torch.bfloat16))
 
     def workspace_views(self) -> dict:
         """Typed, shaped views into the workspace (no copies; the layout comes from
@@ -501,7 +576,9 @@ class FusedLlamaDecoder:
 
         resid [64, dim], q [64, H, D], attn [64, H*D], h [64, ffn] (bf16);
         ss [parts, 64], part_o [64, H, nsplit, D], part_ml [64, H, nsplit, 2],
-        am_val [blocks, 64] (fp32); am_idx [blocks, 64], counters [64*H] (int32).
+        am_val [blocks, 64] (fp32); am_idx [blocks, 64], counters [64*H] (int32);
+        qkv [64, (H+2*Hkv)*D] (bf16): the raw QKV projection of a QK-norm model's
+        last layer, as ``k_qknorm_rope`` read it ([0, ...] for other models).
         Read them after a stream sync; only the first B rows of a step are defined."""
         d = self.dims
         n = len(self._WS_BUFFERS)
@@ -517,7 +594,7 @@ class FusedLlamaDecoder:
         M = MAX_ROWS
         shapes = {"resid": (M, d.dim), "q": (M, d.H, d.D), "attn": (M, d.H * d.D), "h": (M, d.ffn), "ss": (-1, M),
                   "part_o": (M, d.H, -1, d.D), "part_ml": (M, d.H, -1, 2), "am_val": (-1, M), "am_idx": (-1, M),
-                  "counters": (M * d.H,)}
+                  "counters": (M * d.H,), "qkv": (M if d.qk_norm else 0, (d.H + 2 * d.Hkv) * d.D)}
         return {name: v.view(*shapes[name]) for name, v in views.items()}
 
     def embed_pool(self, acc: torch.Tensor, out: torch.Tensor, jobs) -> None:

@@ -9,6 +9,7 @@ namespace {
 struct LlamaDims {
   int vocab, dim, n_layers, H, Hkv, D, ffn, max_seq, max_batch;
   float eps, theta;
+  int qk_norm;  // per-head RMSNorm on q and k before RoPE (Qwen3): a sixth kernel per layer
 };
 
 constexpr int kTnResid = 1, kTnStore = 2;  // LM head: two 16-column subtiles per block
@@ -35,6 +36,7 @@ struct StepPlan {
   GemmPlan qkv_first, qkv, o, gate_up, down, lm_head;  // qkv_first: layer 0 reads k_embed's one partial
   AttnPlan attn;
   int am_parts;  // per-row winners k_argmax_merge reads
+  int qk_norm_grid;  // k_qknorm_rope's gridDim.x (gridDim.y: rows); 0: not launched
 };
 
 // One workgroup per tn subtiles of 16 >> kpl columns of one 16-row tile.
@@ -79,7 +81,12 @@ StepPlan plan_step(const LlamaDims& d, int B, int emit_rows) {
   StepPlan p{};
   p.rows = B;
   p.emit_rows = emit_rows <= 0 || emit_rows > B ? B : emit_rows;
-  p.qkv = plan_gemm(EPI_ROPE, 1, B, (d.H + 2 * d.Hkv) * d.D, d.dim);
+  // QK-norm models: the GEMM stores the raw projection and k_qknorm_rope finishes it.
+  p.qkv = plan_gemm(d.qk_norm ? EPI_STORE : EPI_ROPE, 1, B, (d.H + 2 * d.Hkv) * d.D, d.dim);
+  if (d.qk_norm) {
+    const int per_wg = qknorm_heads_per_wg(d.D);
+    p.qk_norm_grid = (d.H + 2 * d.Hkv + per_wg - 1) / per_wg;
+  }
   p.attn = plan_attn(B, d.H, d.Hkv, d.D, d.max_seq);
   p.o = plan_gemm(EPI_RESID, kTnResid, B, d.dim, d.H * d.D, true);
   p.gate_up = plan_gemm(EPI_SILU, 1, B, 2 * d.ffn, d.dim);
@@ -97,7 +104,7 @@ StepPlan plan_step(const LlamaDims& d, int B, int emit_rows) {
 size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
 struct Workspace {
-  uint16_t *resid, *q, *attn, *h;
+  uint16_t *resid, *q, *attn, *h, *qkv;
   float *ss, *part_o, *part_ml, *am_val;
   int* am_idx;
   unsigned* counters;  // [kMaxM * H] attention split tickets (self-resetting)
@@ -105,11 +112,11 @@ struct Workspace {
 };
 
 // The workspace buffers in layout order (p2pt_llama_ws_layout reports them in this order).
-enum WsBuf : int { WS_RESID, WS_Q, WS_ATTN, WS_H, WS_SS, WS_PART_O, WS_PART_ML, WS_AM_VAL, WS_AM_IDX, WS_COUNTERS, WS_NBUF };
+enum WsBuf : int { WS_RESID, WS_Q, WS_ATTN, WS_H, WS_SS, WS_PART_O, WS_PART_ML, WS_AM_VAL, WS_AM_IDX, WS_COUNTERS, WS_QKV, WS_NBUF };
 
 struct WsLayout {
   size_t off[WS_NBUF];    // byte offset from the workspace base (256-byte aligned)
-  size_t count[WS_NBUF];  // elements: bf16 resid/q/attn/h, fp32 ss/part_o/part_ml/am_val, int32 am_idx, uint32 counters
+  size_t count[WS_NBUF];  // elements: bf16 resid/q/attn/h/qkv, fp32 ss/part_o/part_ml/am_val, int32 am_idx, uint32 counters
   size_t bytes;
 };
 
@@ -136,6 +143,8 @@ WsLayout ws_layout(const LlamaDims& d) {
   take(WS_AM_VAL, size_t(am_parts) * kMaxM, 4);
   take(WS_AM_IDX, size_t(am_parts) * kMaxM, 4);
   take(WS_COUNTERS, size_t(kMaxM * d.H), 4);
+  // The raw QKV projection of a QK-norm model; empty otherwise (the layout of other models is unchanged).
+  take(WS_QKV, d.qk_norm ? size_t(kMaxM) * (d.H + 2 * d.Hkv) * d.D : 0, 2);
   l.bytes = off;
   return l;
 }
@@ -154,6 +163,7 @@ Workspace carve(const LlamaDims& d, uint8_t* base) {
   w.am_val = reinterpret_cast<float*>(at(WS_AM_VAL));
   w.am_idx = reinterpret_cast<int*>(at(WS_AM_IDX));
   w.counters = reinterpret_cast<unsigned*>(at(WS_COUNTERS));
+  w.qkv = reinterpret_cast<uint16_t*>(at(WS_QKV));
   w.bytes = l.bytes;
   return w;
 }
@@ -249,8 +259,21 @@ hipError_t launch_attn(const AttnPlan& p, const void* q, const void* kc, const v
   return hipErrorInvalidValue;
 }
 
+// (row, head group) workgroups of k_qknorm_rope: grid_x groups of qknorm_heads_per_wg(D) heads.
+hipError_t launch_qknorm(int grid_x, int rows, int D, const QkNormArgs& a, hipStream_t s) {
+  if (grid_x <= 0 || rows <= 0 || grid_x * qknorm_heads_per_wg(D) < a.H + 2 * a.Hkv) return hipErrorInvalidValue;
+  const dim3 g(grid_x, rows), b(kQkNormWaves * 64);
+  switch (D) {
+    case 64: hipLaunchKernelGGL(k_qknorm_rope<64>, g, b, 0, s, a); break;
+    case 128: hipLaunchKernelGGL(k_qknorm_rope<128>, g, b, 0, s, a); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
 bool dims_ok(const LlamaDims& d) {
   if (d.D != 64 && d.D != 128) return false;
+  if (d.qk_norm != 0 && d.qk_norm != 1) return false;
   // GEMM operands are addressed with 32-bit byte offsets below kOob (2 GiB):
   // each weight's own N x K bf16 extent (LM head vocab x dim, QKV, gate/up,
   // O, down), not the widest N times the largest K of different GEMMs.
@@ -281,7 +304,7 @@ size_t p2pt_llama_ws_bytes(const LlamaDims* d) {
 
 // Where each workspace buffer lies (tests read the step's intermediates through
 // this): byte offsets and element counts of resid, q, attn, h, ss, part_o,
-// part_ml, am_val, am_idx, counters, in that order, into off[n] / count[n].
+// part_ml, am_val, am_idx, counters, qkv (empty unless qk_norm), in that order, into off[n] / count[n].
 // Returns the number of buffers, or 0 for unsupported dims or n too small.
 int p2pt_llama_ws_layout(const LlamaDims* d, size_t* off, size_t* count, int n) {
   if (!dims_ok(*d) || n < WS_NBUF) return 0;
@@ -314,6 +337,8 @@ int p2pt_max_rows() { return kMaxM; }
 //      into their columns (W[n][k] * g[k]); the norm-weight slots are not read.
 //      wqkv rows are interleaved per head (dim i, dim i + D/2, ...) and w_gate_up
 //      rows per pair (gate_j, up_j, ...).
+//      With dims.qk_norm each layer has 8 entries, q_norm [D] and k_norm [D] appended, and
+//      wqkv rows stay in plain order (k_qknorm_rope pairs the RoPE partners itself).
 //   k_cache/v_cache: [n_layers][max_batch][max_seq][Hkv][D]
 //   tokens int64 [B <= 64], pos int32 [B] (< max_seq), logits bf16 [B][vocab], ids int64 [B]
 //   emit_rows: only rows [0, emit_rows) get logits and ids (the LM head runs on
@@ -338,15 +363,23 @@ int p2pt_llama_decode(const LlamaDims* dp, const void* const* w, void* k_cache, 
                      d.dim, d.vocab);
   if (failed(hipGetLastError())) return int(e);
   for (int L = 0; L < d.n_layers; L++) {
-    const void* const* wl = w + 3 + 6 * L;  // attn_norm, wqkv, wo, ffn_norm, w_gate_up, w_down
+    // attn_norm, wqkv, wo, ffn_norm, w_gate_up, w_down (+ q_norm, k_norm)
+    const void* const* wl = w + 3 + (d.qk_norm ? 8 : 6) * L;
     uint16_t* kc = static_cast<uint16_t*>(k_cache) + L * layer_cache;
     uint16_t* vc = static_cast<uint16_t*>(v_cache) + L * layer_cache;
     const GemmPlan& qkv = L ? P.qkv : P.qkv_first;
-    const GemmArgs to_qkv = gemm(W.resid, wl[1]) + norm(W.ss, qkv.ss_in, d.eps) + rope(d, pos, slots, W.q, kc, vc);
+    const GemmArgs to_qkv = d.qk_norm
+                                ? gemm(W.resid, wl[1]) + norm(W.ss, qkv.ss_in, d.eps) + store(W.qkv)
+                                : gemm(W.resid, wl[1]) + norm(W.ss, qkv.ss_in, d.eps) + rope(d, pos, slots, W.q, kc, vc);
     const GemmArgs to_o = gemm(W.attn, wl[2]) + resid(W.resid, W.ss);
     const GemmArgs to_gate_up = gemm(W.resid, wl[4]) + norm(W.ss, P.gate_up.ss_in, d.eps) + store(W.h);
     const GemmArgs to_down = gemm(W.h, wl[5]) + resid(W.resid, W.ss);
     if (failed(launch(qkv, to_qkv, s))) return int(e);
+    if (P.qk_norm_grid) {
+      const QkNormArgs qn{W.qkv, static_cast<const uint16_t*>(wl[6]), static_cast<const uint16_t*>(wl[7]), pos, slots,
+                          d.max_batch, W.q, kc, vc, d.H, d.Hkv, d.max_seq, d.eps, log2f(d.theta)};
+      if (failed(launch_qknorm(P.qk_norm_grid, B, d.D, qn, s))) return int(e);
+    }
     if (failed(launch_attn(P.attn, W.q, kc, vc, pos, slots, d.max_batch, W.part_o, W.part_ml, W.counters, W.attn, d.H,
                            d.Hkv, d.max_seq, s)))
       return int(e);
@@ -366,6 +399,22 @@ int p2pt_skinny_gemm(const void* x, const void* w, void* out, int M, int N, int 
   if (!rows_ok(M) || N % 32 || K <= 0 || K % 32) return int(hipErrorInvalidValue);
   const GemmPlan p = plan_gemm(EPI_STORE, 2, M, N, K);
   return int(launch(p, gemm(x, w) + store(out), static_cast<hipStream_t>(stream)));
+}
+
+// Standalone per-head RMSNorm + RoPE + cache append (tests): the kernel the fused step of a QK-norm model
+// runs, on caller tensors. qkv [B <= 64][(H + 2 Hkv) * D], q_weight / k_weight [D], q [B][H][D], caches
+// [nslots][Smax][Hkv][D]; row b goes to slot slots[b] (nullptr: slot b, B <= nslots) at pos[b].
+int p2pt_qk_norm_rope_cache(const void* qkv, const int* pos, const int* slots, const void* q_weight,
+                            const void* k_weight, void* q, void* k_cache, void* v_cache, int B, int H, int Hkv, int D,
+                            int Smax, int nslots, float eps, float theta, void* stream) {
+  if (!rows_ok(B) || (D != 64 && D != 128) || H <= 0 || Hkv <= 0 || Smax <= 0 || nslots <= 0)
+    return int(hipErrorInvalidValue);
+  if ((!slots && B > nslots) || !(theta > 0.f)) return int(hipErrorInvalidValue);
+  const QkNormArgs a{static_cast<const uint16_t*>(qkv), static_cast<const uint16_t*>(q_weight),
+                     static_cast<const uint16_t*>(k_weight), pos, slots, nslots, static_cast<uint16_t*>(q),
+                     static_cast<uint16_t*>(k_cache), static_cast<uint16_t*>(v_cache), H, Hkv, Smax, eps, log2f(theta)};
+  const int per_wg = qknorm_heads_per_wg(D);
+  return int(launch_qknorm((H + 2 * Hkv + per_wg - 1) / per_wg, B, D, a, static_cast<hipStream_t>(stream)));
 }
 
 // Microbenchmark hook (scripts/bench_skinny.py --attn): `reps` back-to-back

@@ -10,7 +10,9 @@
 //   per layer:
 //     k_skinny<ROPE>     RMSNorm (attn_norm) -> QKV GEMM -> RoPE on q/k,
 //                        q to the attention buffer, k/v appended to the cache
-//     k_attn             GQA flash-decoding split-K; the last split to finish
+//     (QK-norm models:   k_skinny<STORE> writes the raw projection instead, and
+//      k_qknorm_rope     norms every q and k head, rotates and appends: a sixth kernel)
+//     k_attn            GQA flash-decoding split-K; the last split to finish
 //                        for a (sequence, KV head) merges the partials in-kernel
 //     k_skinny<RESID>    O projection -> residual add -> per-row sum-of-squares
 //                        partials for the next norm
@@ -488,6 +490,90 @@ __global__ __launch_bounds__(256) void k_embed(const uint16_t* __restrict__ embe
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
   __syncthreads();
   if (threadIdx.x == 0) ss_out[b] = red[0] + red[1] + red[2] + red[3];
+}
+
+// ------------------------------------------------------------ per-head QK RMSNorm + RoPE + cache append
+// QK-norm models (Qwen3): an RMSNorm over head_dim with a learned [D] weight on
+// every q and k head, after the projection and before RoPE. A head is spread
+// over 4 or 8 workgroups of the QKV GEMM, so the norm cannot sit in its
+// epilogue; the GEMM stores the raw projection (EPI_STORE, plain row order) and
+// this kernel finishes it: norm, rotate-half RoPE, q to the attention buffer,
+// k appended to the cache, v copied bit for bit. D / 4 lanes per head (2 or 4
+// heads per wave): lane j holds dims 2j, 2j + 1 and their RoPE partners
+// 2j + D/2, 2j + 1 + D/2 as two 4-byte loads, so the rotation needs no lane
+// exchange and the sum of squares is one DPP row sum (plus one half-swap at
+// D = 128). fp32 throughout, rounded to bf16 once. No LDS, no barrier.
+struct QkNormArgs {
+  const uint16_t* qkv;  // [M][(H + 2 Hkv) * D], plain head order
+  const uint16_t* gq;   // [D] q_norm weight
+  const uint16_t* gk;   // [D] k_norm weight
+  const int* pos;
+  const int* slot;  // nullptr: row m -> slot m
+  int nslots;
+  uint16_t* q_out;  // [M][H][D]
+  uint16_t* kc;     // [nslots][Smax][Hkv][D]
+  uint16_t* vc;
+  int H, Hkv, Smax;
+  float eps, log2_theta;
+};
+
+constexpr int kQkNormWaves = 4;  // waves per workgroup of k_qknorm_rope
+
+// Heads one workgroup of k_qknorm_rope covers.
+__host__ __device__ __forceinline__ int qknorm_heads_per_wg(int D) { return kQkNormWaves * kWave / (D / 4); }
+
+template <int D>
+__global__ __launch_bounds__(kQkNormWaves * 64) void k_qknorm_rope(QkNormArgs a) {
+  constexpr int LPH = D / 4, half = D / 2;  // lanes per head
+  const int lane = threadIdx.x & 63;
+  const int m = blockIdx.y;
+  const int heads = a.H + 2 * a.Hkv;
+  const int head = (blockIdx.x * kQkNormWaves * 64 + threadIdx.x) / LPH;
+  // Lane groups past the last head follow it (every lane stays in the
+  // cross-lane sums) and store nothing.
+  const int hc = min(head, heads - 1);
+  const int j = lane % LPH;
+  const uint16_t* src = a.qkv + (size_t(m) * heads + hc) * D + 2 * j;
+  const uint32_t lo = *reinterpret_cast<const uint32_t*>(src);
+  const uint32_t hi = *reinterpret_cast<const uint32_t*>(src + half);
+  const bool is_q = hc < a.H, is_v = hc >= a.H + a.Hkv;
+  const uint16_t* g = (is_q ? a.gq : a.gk) + 2 * j;
+  const uint32_t glo = *reinterpret_cast<const uint32_t*>(g);
+  const uint32_t ghi = *reinterpret_cast<const uint32_t*>(g + half);
+  // Host validates; clamped anyway so a bad index can never write outside the cache.
+  const int p = min(max(a.pos[m], 0), a.Smax - 1);
+  const int sl = a.slot ? min(max(a.slot[m], 0), a.nslots - 1) : m;
+
+  const float x1[2] = {bf_lo(lo), bf_hi(lo)}, x2[2] = {bf_lo(hi), bf_hi(hi)};
+  float ss = x1[0] * x1[0] + x1[1] * x1[1] + x2[0] * x2[0] + x2[1] * x2[1];
+  ss = row16_sum(ss);
+  if constexpr (LPH == 32) ss = xor16_sum(ss);
+  const float rs = rsqrtf(ss * (1.f / float(D)) + a.eps);
+  if (head >= heads) return;
+
+  uint32_t olo = lo, ohi = hi;  // v: copied as is
+  if (!is_v) {
+    const float g1[2] = {bf_lo(glo), bf_hi(glo)}, g2[2] = {bf_lo(ghi), bf_hi(ghi)};
+    float o1[2], o2[2];
+#pragma unroll
+    for (int e = 0; e < 2; e++) {
+      const int i = 2 * j + e;
+      const float inv_freq = exp2f(-a.log2_theta * (2.f * i) / D);
+      float sn, cs;
+      sincosf(float(p) * inv_freq, &sn, &cs);
+      const float n1 = x1[e] * rs * g1[e], n2 = x2[e] * rs * g2[e];
+      o1[e] = n1 * cs - n2 * sn;
+      o2[e] = n2 * cs + n1 * sn;
+    }
+    olo = pack2(o1[0], o1[1]);
+    ohi = pack2(o2[0], o2[1]);
+  }
+  const size_t row = (size_t(sl) * a.Smax + p) * a.Hkv;
+  uint16_t* dst = is_q   ? a.q_out + (size_t(m) * a.H + hc) * D
+                  : is_v ? a.vc + (row + (hc - a.H - a.Hkv)) * D
+                         : a.kc + (row + (hc - a.H)) * D;
+  *reinterpret_cast<uint32_t*>(dst + 2 * j) = olo;
+  *reinterpret_cast<uint32_t*>(dst + 2 * j + half) = ohi;
 }
 
 // ------------------------------------------------------------ attention

@@ -21,7 +21,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch  # noqa: E402
 
-from p2p_llm_tunnel_amd.models.tiny_llm import CONFIGS, TinyLlama, capture  # noqa: E402
+from p2p_llm_tunnel_amd.models.tiny_llm import CONFIGS, LlamaConfig, TinyLlama, capture  # noqa: E402
 
 
 def main():
@@ -35,6 +35,12 @@ def main():
     ap.add_argument("--unfused", action="store_true", help="kernels.hip + hipBLASLt path instead of decode_fused.hip")
     ap.add_argument("--set", action="append", default=[], metavar="FIELD=INT",
                     help="override a field of --config (e.g. --set n_layers=2 --set vocab=8000)")
+    ap.add_argument("--cfg", default=None, metavar="JSON",
+                    help="an explicit LlamaConfig as a JSON object of its fields, instead of --config, e.g. a "
+                         "Qwen3-0.6B-shaped model: '{\"vocab\": 151936, \"dim\": 1024, \"n_layers\": 28, "
+                         "\"n_heads\": 16, \"n_kv_heads\": 8, \"head_dim\": 128, \"ffn\": 3072, \"max_seq\": 2048, "
+                         "\"eps\": 1e-6, \"rope_theta\": 1e6, \"qk_norm\": true}'")
+    ap.add_argument("--name", default=None, help="label of a --cfg model in the result line")
     ap.add_argument("--checkpoint", default=None, help="load this HF Llama checkpoint instead of a random --config")
     ap.add_argument("--loop", action="store_true",
                     help="device-side autoregression: one graph = the fused step (ids feed the next step's "
@@ -45,7 +51,11 @@ def main():
         m = load_llama(a.checkpoint, device="cuda", max_batch=a.batch, fused=not a.unfused)
         a.config = os.path.basename(os.path.normpath(a.checkpoint))
     else:
-        cfg = CONFIGS[a.config]
+        if a.cfg:
+            cfg = LlamaConfig(**json.loads(a.cfg))
+            a.config = a.name or "custom"
+        else:
+            cfg = CONFIGS[a.config]
         if a.set:
             cfg = dataclasses.replace(cfg, **{k: int(v) for k, v in (x.split("=", 1) for x in a.set)})
             a.config += "[" + ",".join(a.set) + "]"
