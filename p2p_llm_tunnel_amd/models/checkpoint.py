@@ -22,6 +22,7 @@ Name mapping (HF ``LlamaForCausalLM`` → ours, see ``tiny_llm.py``):
 ``lm_head.weight`` (or the embedding when tied)          ``lm_head``
 ``...self_attn.q_norm.weight`` (Qwen3 only)              ``layers[i]["q_norm"]``
 ``...self_attn.k_norm.weight`` (Qwen3 only)              ``layers[i]["k_norm"]``
+``...self_attn.{q,k,v}_proj.bias`` (Qwen2, concatenated)  ``layers[i]["bqkv"]``
 =====================================================  ===========================
 
 ``Qwen3ForCausalLM`` (dense) is the Llama layout plus a per-head RMSNorm over
@@ -29,6 +30,12 @@ Name mapping (HF ``LlamaForCausalLM`` → ours, see ``tiny_llm.py``):
 comes from the config and need not be ``hidden_size / num_attention_heads``.
 A Llama or Mistral checkpoint that carries these tensors is refused: loading
 it without the norm would compute a different model.
+
+``Qwen2ForCausalLM`` (Qwen2, Qwen2.5 and their Coder, Math and R1-Distill
+variants) is the Llama layout plus a bias on the q, k and v projections
+(``LlamaConfig.qkv_bias``), and none on ``o_proj`` or the MLP. A checkpoint of
+another architecture that carries ``q_proj.bias`` is refused, as is any
+checkpoint with an ``o_proj`` or MLP bias.
 
 HF Llama q/k projections are already laid out for the rotate-half RoPE
 convention our kernels use (``reference_logits``), so no head permutation is
@@ -43,8 +50,10 @@ import torch
 
 from p2p_llm_tunnel_amd.models.tiny_llm import LlamaConfig, TinyLlama
 
-_SUPPORTED = {"LlamaForCausalLM", "MistralForCausalLM", "Qwen3ForCausalLM"}
+_SUPPORTED = {"LlamaForCausalLM", "MistralForCausalLM", "Qwen2ForCausalLM", "Qwen3ForCausalLM"}
 _QK_NORM = {"Qwen3ForCausalLM"}  # per-head RMSNorm on q and k before RoPE
+_QKV_BIAS = {"Qwen2ForCausalLM"}  # bias on q_proj, k_proj and v_proj, always (the config has no flag for it)
+_GQA_RATIOS = (1, 2, 4, 5, 6, 7, 8)  # the fused step's attention instantiations (decode_fused.hip: dims_ok)
 
 
 def read_config(path: str, max_seq: int | None = None) -> tuple[LlamaConfig, dict]:
@@ -57,6 +66,9 @@ def read_config(path: str, max_seq: int | None = None) -> tuple[LlamaConfig, dic
     if arch == "Qwen3MoeForCausalLM":
         raise ValueError("unsupported architecture 'Qwen3MoeForCausalLM': mixture-of-experts layers are not "
                          "supported by the decode kernels (dense Qwen3 only)")
+    if arch == "Qwen2MoeForCausalLM":
+        raise ValueError("unsupported architecture 'Qwen2MoeForCausalLM': mixture-of-experts layers are not "
+                         "supported by the decode kernels (dense Qwen2 only)")
     if arch not in _SUPPORTED:
         raise ValueError(f"unsupported architecture {arch!r} (Llama-style decoders only: {sorted(_SUPPORTED)})")
     # transformers >= 5 writes rope_parameters {rope_theta, rope_type}; older
@@ -68,7 +80,8 @@ def read_config(path: str, max_seq: int | None = None) -> tuple[LlamaConfig, dic
     if raw.get("hidden_act", "silu") != "silu":
         raise ValueError(f"hidden_act {raw['hidden_act']!r}: only SwiGLU (silu) decoders are supported")
     if raw.get("attention_bias") or raw.get("mlp_bias"):
-        raise ValueError("projection biases are not supported by the decode kernels")
+        raise ValueError("projection biases are not supported by the decode kernels"
+                         + (" (Qwen2: on q, k and v only, without a config flag)" if arch in _QKV_BIAS else ""))
     other = sorted({str(t) for t in raw.get("layer_types") or []} - {"full_attention"})
     if other:
         raise ValueError(f"layer_types {other}: only full_attention layers are supported by the decode kernels")
@@ -77,12 +90,19 @@ def read_config(path: str, max_seq: int | None = None) -> tuple[LlamaConfig, dic
         max_seq = min(int(max_seq or sw), int(sw))
     heads = int(raw["num_attention_heads"])
     dim = int(raw["hidden_size"])
+    kv_heads = int(raw.get("num_key_value_heads", heads))
+    if kv_heads <= 0 or heads % kv_heads or heads // kv_heads not in _GQA_RATIOS:
+        raise ValueError(f"GQA ratio {heads}/{kv_heads}"
+                         + (f" = {heads // kv_heads}" if kv_heads > 0 and heads % kv_heads == 0 else "")
+                         + f" is not supported by the decode kernels (num_attention_heads / num_key_value_heads "
+                           f"must be one of {list(_GQA_RATIOS)})")
     cfg = LlamaConfig(
         vocab=int(raw["vocab_size"]), dim=dim, n_layers=int(raw["num_hidden_layers"]), n_heads=heads,
-        n_kv_heads=int(raw.get("num_key_value_heads", heads)), head_dim=int(raw.get("head_dim") or dim // heads),
+        n_kv_heads=kv_heads, head_dim=int(raw.get("head_dim") or dim // heads),
         ffn=int(raw["intermediate_size"]),
         max_seq=int(max_seq or min(int(raw.get("max_position_embeddings", 2048)), 8192)),
-        eps=float(raw.get("rms_norm_eps", 1e-5)), rope_theta=float(theta), qk_norm=arch in _QK_NORM)
+        eps=float(raw.get("rms_norm_eps", 1e-5)), rope_theta=float(theta), qk_norm=arch in _QK_NORM,
+        qkv_bias=arch in _QKV_BIAS)
     return cfg, raw
 
 
@@ -164,8 +184,18 @@ def load_llama(path: str, device="cuda", max_batch: int = 8, max_seq: int | None
             q = t(p + "self_attn.q_proj.weight", (q_out, c.dim))
             k = t(p + "self_attn.k_proj.weight", (kv_out, c.dim))
             v = t(p + "self_attn.v_proj.weight", (kv_out, c.dim))
-            if rd.has(p + "self_attn.q_proj.bias"):
-                raise ValueError("attention projection biases are not supported by the decode kernels")
+            for n in ("self_attn.o_proj", "mlp.gate_proj", "mlp.up_proj", "mlp.down_proj"):
+                if rd.has(p + n + ".bias"):
+                    raise ValueError(f"{p}{n}.bias: only q, k and v projection biases are supported by the decode "
+                                     "kernels")
+            bqkv = None
+            if c.qkv_bias:
+                bqkv = torch.cat([t(p + "self_attn.q_proj.bias", (q_out,)), t(p + "self_attn.k_proj.bias", (kv_out,)),
+                                  t(p + "self_attn.v_proj.bias", (kv_out,))], 0).contiguous()
+            elif any(rd.has(f"{p}self_attn.{n}_proj.bias") for n in "qkv"):
+                raise ValueError(f"{p}self_attn has q/k/v projection biases, but the architecture "
+                                 f"{(raw.get('architectures') or ['LlamaForCausalLM'])[0]!r} applies none: attention "
+                                 "projection biases are not supported for it, refusing to load it without them")
             gate = t(p + "mlp.gate_proj.weight", (c.ffn, c.dim))
             up = t(p + "mlp.up_proj.weight", (c.ffn, c.dim))
             w["layers"].append({
@@ -176,6 +206,8 @@ def load_llama(path: str, device="cuda", max_batch: int = 8, max_seq: int | None
                 "w_gate_up": torch.cat([gate, up], 0).contiguous(),
                 "w_down": t(p + "mlp.down_proj.weight", (c.dim, c.ffn)),
             })
+            if bqkv is not None:
+                w["layers"][-1]["bqkv"] = bqkv
             if c.qk_norm:
                 w["layers"][-1]["q_norm"] = t(p + "self_attn.q_norm.weight", (c.head_dim,))
                 w["layers"][-1]["k_norm"] = t(p + "self_attn.k_norm.weight", (c.head_dim,))

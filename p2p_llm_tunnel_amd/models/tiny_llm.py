@@ -42,6 +42,7 @@ class LlamaConfig:
     eps: float = 1e-5
     rope_theta: float = 10000.0
     qk_norm: bool = False  # per-head RMSNorm on q and k before RoPE (Qwen3): layers carry q_norm, k_norm [head_dim]
+    qkv_bias: bool = False  # bias on the q, k and v projections (Qwen2): layers carry bqkv [(H + 2 Hkv) * head_dim]
 
 
 CONFIGS = {
@@ -73,9 +74,11 @@ class TinyLlama:
                  fused: bool = True, weights: dict | None = None):
         """Random-init weights from ``seed``, or ``weights`` (embed, final_norm,
         lm_head, layers[{attn_norm, wqkv, wo, ffn_norm, w_gate_up, w_down}, plus
-        q_norm, k_norm when ``cfg.qk_norm``], bf16 on ``device``) — see
-        ``checkpoint.load_llama``."""
+        q_norm, k_norm when ``cfg.qk_norm``, or bqkv in plain q | k | v order when
+        ``cfg.qkv_bias``], bf16 on ``device``) — see ``checkpoint.load_llama``."""
         self.cfg = CONFIGS[cfg] if isinstance(cfg, str) else cfg
+        if self.cfg.qkv_bias and self.cfg.qk_norm:
+            raise ValueError("qkv_bias with qk_norm: no supported family has both, and the fused step refuses it")
         self.fused = fused
         self._fused = None
         self._graphs = {}  # rows -> (graph, tokens, pos, slots, ids, logits)
@@ -91,6 +94,11 @@ class TinyLlama:
                     for n in ("q_norm", "k_norm"):
                         if n not in L or tuple(L[n].shape) != (c.head_dim,):
                             raise ValueError(f"layer {i}: a QK-norm model needs {n} of shape ({c.head_dim},)")
+            if c.qkv_bias:
+                n_qkv = (c.n_heads + 2 * c.n_kv_heads) * c.head_dim
+                for i, L in enumerate(self.layers):
+                    if "bqkv" not in L or tuple(L["bqkv"].shape) != (n_qkv,):
+                        raise ValueError(f"layer {i}: a QKV-bias model needs bqkv of shape ({n_qkv},)")
             self._alloc_caches()
             return
         g = torch.Generator(device="cpu").manual_seed(seed)
@@ -116,6 +124,8 @@ class TinyLlama:
             if c.qk_norm:  # drawn well away from 1 and from each other: a missing or swapped weight shows
                 for n in ("q_norm", "k_norm"):
                     self.layers[-1][n] = (0.5 + torch.rand(c.head_dim, generator=g)).to(torch.bfloat16).to(self.device)
+            if c.qkv_bias:  # up to a few units, as real k-biases are: one that is dropped or scaled by 1/rms shows
+                self.layers[-1]["bqkv"] = w(qkv_out, scale=1.0)
         self.final_norm = norm_w(c.dim)
         self.lm_head = w(c.vocab, c.dim, scale=1 / math.sqrt(c.dim))
         self._alloc_caches()
@@ -181,7 +191,9 @@ class TinyLlama:
         # interleaved in pairs so a 16-column tile holds both members of a
         # RoPE pair or a SwiGLU pair; see decode_fused.hip. A QK-norm model keeps
         # wqkv's rows in plain order (its RoPE runs in k_qknorm_rope, which pairs
-        # the partners itself) and appends q_norm, k_norm to each layer's six.
+        # the partners itself) and appends q_norm, k_norm to each layer's six. A
+        # QKV-bias model appends bqkv, interleaved like wqkv's rows (the fold
+        # touches only wqkv).
         def fold(w, g):
             return (w.float() * g.float()[None, :]).to(torch.bfloat16)
 
@@ -198,6 +210,8 @@ class TinyLlama:
                    L["ffn_norm"], fold(L["w_gate_up"], L["ffn_norm"])[pairs(c.ffn)].contiguous(), L["w_down"]]
             if c.qk_norm:
                 ws += [L["q_norm"].contiguous(), L["k_norm"].contiguous()]
+            if c.qkv_bias:
+                ws += [L["bqkv"][head_perm].contiguous()]
         return ws
 
     def fused_decoder(self) -> ops.FusedLlamaDecoder:
@@ -205,7 +219,7 @@ class TinyLlama:
             c = self.cfg
             dims = ops.LlamaDims(vocab=c.vocab, dim=c.dim, n_layers=c.n_layers, H=c.n_heads, Hkv=c.n_kv_heads,
                                  D=c.head_dim, ffn=c.ffn, max_seq=c.max_seq, max_batch=self.max_batch + 1, eps=c.eps,
-                                 theta=c.rope_theta, qk_norm=int(c.qk_norm))
+                                 theta=c.rope_theta, qk_norm=int(c.qk_norm), qkv_bias=int(c.qkv_bias))
             self._fused = ops.FusedLlamaDecoder(dims, self.fused_weights(), self.k_cache, self.v_cache)
         return self._fused
 
@@ -233,7 +247,7 @@ class TinyLlama:
         residual = x
         for i, L in enumerate(self.layers):
             kc, vc = self.k_cache[i, :B], self.v_cache[i, :B]
-            qkv = F.linear(h, L["wqkv"])
+            qkv = F.linear(h, L["wqkv"], L["bqkv"] if c.qkv_bias else None)
             if c.qk_norm:  # per-head norm with the standalone rmsnorm kernel on [B * heads, D] views
                 nq, nk = c.n_heads * c.head_dim, c.n_kv_heads * c.head_dim
                 qn = ops.rmsnorm(qkv[:, :nq].reshape(-1, c.head_dim), L["q_norm"], c.eps).view(B, nq)
@@ -328,7 +342,8 @@ class TinyLlama:
         G = c.n_heads // c.n_kv_heads
         mask = torch.full((T, T), float("-inf"), device=seqs.device).triu(1)
         for i, L in enumerate(self.layers):
-            qkv = bf(h @ f32(L["wqkv"]).T)
+            qkv = h @ f32(L["wqkv"]).T
+            qkv = bf(qkv + f32(L["bqkv"]) if c.qkv_bias else qkv)
             q = qkv[..., : c.n_heads * c.head_dim].view(B, T, c.n_heads, c.head_dim)
             k = qkv[..., c.n_heads * c.head_dim: (c.n_heads + c.n_kv_heads) * c.head_dim].view(
                 B, T, c.n_kv_heads, c.head_dim)

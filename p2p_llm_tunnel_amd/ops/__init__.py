@@ -23,7 +23,7 @@ class LlamaDims(ctypes.Structure):
     """Mirror of ``LlamaDims`` in decode_fused.hip."""
     _fields_ = [(n, ctypes.c_int) for n in ("vocab", "dim", "n_layers", "H", "Hkv", "D", "ffn", "max_seq",
                                            "max_batch")] + [("eps", ctypes.c_float), ("theta", ctypes.c_float),
-                                                            ("qk_norm", ctypes.c_int)]
+                                                            ("qk_norm", ctypes.c_int), ("qkv_bias", ctypes.c_int)]
 
 
 _INT = ctypes.c_int
@@ -527,7 +527,8 @@ def skinny_gemm(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
 
 class FusedLlamaDecoder:
     """Host handle for the fused decode step (decode_fused.hip): 5 kernels per layer + 3
-    (6 per layer with ``dims.qk_norm``: the per-head q/k RMSNorm of Qwen3 runs in a kernel of its own).
+    (6 per layer with ``dims.qk_norm``: the per-head q/k RMSNorm of Qwen3 runs in a kernel of its own;
+    with ``dims.qkv_bias`` the q/k/v bias of Qwen2 is added in the QKV GEMM's epilogue, still 5).
 
     Holds the weight pointer table and a zero-initialised workspace; ``step``
     validates the per-call tensors and launches on the current stream (capturable
@@ -544,16 +545,22 @@ class FusedLlamaDecoder:
             raise ValueError("cache shape does not match dims")
         _check(k_cache, torch.bfloat16, "k_cache", dev)
         _check(v_cache, torch.bfloat16, "v_cache", dev)
-        per_layer = 8 if dims.qk_norm else 6
+        per_layer = 8 if dims.qk_norm else 7 if dims.qkv_bias else 6
         if len(weights) != 3 + per_layer * dims.n_layers:
             raise ValueError(f"weight table: embed, final_norm, lm_head, then {per_layer} per layer "
                              "(wqkv, w_gate_up and lm_head with the preceding norm weight folded in"
-                             + ("; q_norm and k_norm last)" if dims.qk_norm else ")"))
+                             + ("; q_norm and k_norm last)" if dims.qk_norm else
+                                "; bqkv last)" if dims.qkv_bias else ")"))
         if dims.qk_norm:
             for L in range(dims.n_layers):
                 for j in (6, 7):
                     if weights[3 + 8 * L + j].shape != (dims.D,):
                         raise ValueError(f"layer {L}: q_norm and k_norm must be ({dims.D},)")
+        elif dims.qkv_bias:
+            n_qkv = (dims.H + 2 * dims.Hkv) * dims.D
+            for L in range(dims.n_layers):
+                if weights[3 + 7 * L + 6].shape != (n_qkv,):
+                    raise ValueError(f"layer {L}: bqkv must be ({n_qkv},)")
         nbytes = lib().p2pt_llama_ws_bytes(ctypes.byref(dims))
         if nbytes == 0:
             raise ValueError("model dims not supported by the fused decode kernels")

@@ -10,6 +10,7 @@ struct LlamaDims {
   int vocab, dim, n_layers, H, Hkv, D, ffn, max_seq, max_batch;
   float eps, theta;
   int qk_norm;  // per-head RMSNorm on q and k before RoPE (Qwen3): a sixth kernel per layer
+  int qkv_bias;  // a bias on the q, k and v projections (Qwen2): added in the QKV GEMM's epilogue
 };
 
 constexpr int kTnResid = 1, kTnStore = 2;  // LM head: two 16-column subtiles per block
@@ -82,7 +83,9 @@ StepPlan plan_step(const LlamaDims& d, int B, int emit_rows) {
   p.rows = B;
   p.emit_rows = emit_rows <= 0 || emit_rows > B ? B : emit_rows;
   // QK-norm models: the GEMM stores the raw projection and k_qknorm_rope finishes it.
-  p.qkv = plan_gemm(d.qk_norm ? EPI_STORE : EPI_ROPE, 1, B, (d.H + 2 * d.Hkv) * d.D, d.dim);
+  // QKV-bias models: the RoPE epilogue with the bias add. No K parts on QKV (launch() refuses them with a bias).
+  p.qkv = plan_gemm(d.qk_norm ? EPI_STORE : d.qkv_bias ? EPI_ROPE_BIAS : EPI_ROPE, 1, B, (d.H + 2 * d.Hkv) * d.D,
+                    d.dim);
   if (d.qk_norm) {
     const int per_wg = qknorm_heads_per_wg(d.D);
     p.qk_norm_grid = (d.H + 2 * d.Hkv + per_wg - 1) / per_wg;
@@ -194,6 +197,13 @@ auto rope(const LlamaDims& d, const int* pos, const int* slot, uint16_t* q, uint
     a.H = d.H, a.Hkv = d.Hkv, a.D = d.D, a.Smax = d.max_seq, a.log2_theta = log2f(d.theta);
   };
 }
+auto rope_bias(const LlamaDims& d, const int* pos, const int* slot, uint16_t* q, uint16_t* kc, uint16_t* vc,
+               const void* bias) {  // ROPE_BIAS
+  return [=](GemmArgs& a) {
+    rope(d, pos, slot, q, kc, vc)(a);
+    a.bias = static_cast<const uint16_t*>(bias);
+  };
+}
 auto resid(uint16_t* r, float* ss_out) {
   return [=](GemmArgs& a) { a.out = r, a.ss_out = ss_out; };
 }
@@ -218,12 +228,15 @@ hipError_t launch_as(const GemmPlan& p, GemmArgs a, hipStream_t s) {
   return hipGetLastError();
 }
 
-// The one (nw, tn, epi, um) dispatch: the 36 k_skinny instantiations.
+// The one (nw, tn, epi, um) dispatch: the 42 k_skinny instantiations.
 hipError_t launch(const GemmPlan& p, const GemmArgs& a, hipStream_t s) {
   if (p.kpl < 0 || p.kpl > kMaxKpl || (p.ss_in > 0) != (a.ss_part != nullptr)) return hipErrorInvalidValue;
   if (p.kpl && (p.tn != 1 || (p.M << p.kpl) > 16 || p.K % (32 << p.kpl))) return hipErrorInvalidValue;
+  // The bias is added once, after the K-split reduction: never with K parts, never without a bias.
+  if (p.epi == EPI_ROPE_BIAS && (p.kpl != 0 || a.bias == nullptr)) return hipErrorInvalidValue;
   switch (p.epi * 4 + p.tn) {
     case EPI_ROPE * 4 + 1: return launch_as<1, EPI_ROPE>(p, a, s);
+    case EPI_ROPE_BIAS * 4 + 1: return launch_as<1, EPI_ROPE_BIAS>(p, a, s);
     case EPI_RESID * 4 + 1: return launch_as<1, EPI_RESID>(p, a, s);
     case EPI_SILU * 4 + 1: return launch_as<1, EPI_SILU>(p, a, s);
     case EPI_ARGMAX * 4 + 2: return launch_as<2, EPI_ARGMAX>(p, a, s);
@@ -250,10 +263,16 @@ hipError_t launch_attn(const AttnPlan& p, const void* q, const void* kc, const v
     case 64 * 16 + 1: return go(k_attn<64, 1>);
     case 64 * 16 + 2: return go(k_attn<64, 2>);
     case 64 * 16 + 4: return go(k_attn<64, 4>);
+    case 64 * 16 + 5: return go(k_attn<64, 5>);
+    case 64 * 16 + 6: return go(k_attn<64, 6>);
+    case 64 * 16 + 7: return go(k_attn<64, 7>);
     case 64 * 16 + 8: return go(k_attn<64, 8>);
     case 128 * 16 + 1: return go(k_attn<128, 1>);
     case 128 * 16 + 2: return go(k_attn<128, 2>);
     case 128 * 16 + 4: return go(k_attn<128, 4>);
+    case 128 * 16 + 5: return go(k_attn<128, 5>);
+    case 128 * 16 + 6: return go(k_attn<128, 6>);
+    case 128 * 16 + 7: return go(k_attn<128, 7>);
     case 128 * 16 + 8: return go(k_attn<128, 8>);
   }
   return hipErrorInvalidValue;
@@ -274,6 +293,9 @@ hipError_t launch_qknorm(int grid_x, int rows, int D, const QkNormArgs& a, hipSt
 bool dims_ok(const LlamaDims& d) {
   if (d.D != 64 && d.D != 128) return false;
   if (d.qk_norm != 0 && d.qk_norm != 1) return false;
+  if (d.qkv_bias != 0 && d.qkv_bias != 1) return false;
+  // No family has both, and the EPI_STORE + k_qknorm_rope route would need the bias elsewhere.
+  if (d.qkv_bias && d.qk_norm) return false;
   // GEMM operands are addressed with 32-bit byte offsets below kOob (2 GiB):
   // each weight's own N x K bf16 extent (LM head vocab x dim, QKV, gate/up,
   // O, down), not the widest N times the largest K of different GEMMs.
@@ -282,7 +304,11 @@ bool dims_ok(const LlamaDims& d) {
                                2 * ffn * dim * 2, dim * hd * 2, dim * ffn * 2};
   for (size_t b : gemm_bytes)
     if (b >= kOob) return false;
-  if (d.H % d.Hkv || (d.H / d.Hkv != 1 && d.H / d.Hkv != 2 && d.H / d.Hkv != 4 && d.H / d.Hkv != 8)) return false;
+  // GQA ratios 1, 2, 4 to 8: the k_attn<D, G> instantiations of launch_attn. 5, 6 and 7 are the Qwen2 /
+  // Qwen2.5 family's (40/8, 12/2, 14/2 and 28/4). 3 stays refused: no checkpoint the loader accepts uses it.
+  if (d.Hkv <= 0 || d.H % d.Hkv) return false;
+  const int gqa = d.H / d.Hkv;
+  if (gqa != 1 && gqa != 2 && (gqa < 4 || gqa > 8)) return false;
   if (d.dim % 32 || (d.H * d.D) % 32 || d.ffn % 32) return false;
   if (d.dim % (16 * kTnResid) || d.vocab % (16 * kTnStore) || d.ffn % 16) return false;
   if (d.max_batch <= 0 || d.max_seq <= 0 || d.n_layers <= 0) return false;
@@ -339,6 +365,7 @@ int p2pt_max_rows() { return kMaxM; }
 //      rows per pair (gate_j, up_j, ...).
 //      With dims.qk_norm each layer has 8 entries, q_norm [D] and k_norm [D] appended, and
 //      wqkv rows stay in plain order (k_qknorm_rope pairs the RoPE partners itself).
+//      With dims.qkv_bias each layer has 7 entries: the six, then bqkv [(H+2Hkv)*D], interleaved like wqkv's rows.
 //   k_cache/v_cache: [n_layers][max_batch][max_seq][Hkv][D]
 //   tokens int64 [B <= 64], pos int32 [B] (< max_seq), logits bf16 [B][vocab], ids int64 [B]
 //   emit_rows: only rows [0, emit_rows) get logits and ids (the LM head runs on
@@ -363,13 +390,16 @@ int p2pt_llama_decode(const LlamaDims* dp, const void* const* w, void* k_cache, 
                      d.dim, d.vocab);
   if (failed(hipGetLastError())) return int(e);
   for (int L = 0; L < d.n_layers; L++) {
-    // attn_norm, wqkv, wo, ffn_norm, w_gate_up, w_down (+ q_norm, k_norm)
-    const void* const* wl = w + 3 + (d.qk_norm ? 8 : 6) * L;
+    // attn_norm, wqkv, wo, ffn_norm, w_gate_up, w_down (+ q_norm, k_norm, or + bqkv)
+    const void* const* wl = w + 3 + (d.qk_norm ? 8 : d.qkv_bias ? 7 : 6) * L;
     uint16_t* kc = static_cast<uint16_t*>(k_cache) + L * layer_cache;
     uint16_t* vc = static_cast<uint16_t*>(v_cache) + L * layer_cache;
     const GemmPlan& qkv = L ? P.qkv : P.qkv_first;
     const GemmArgs to_qkv = d.qk_norm
                                 ? gemm(W.resid, wl[1]) + norm(W.ss, qkv.ss_in, d.eps) + store(W.qkv)
+                            : d.qkv_bias
+                                ? gemm(W.resid, wl[1]) + norm(W.ss, qkv.ss_in, d.eps) +
+                                      rope_bias(d, pos, slots, W.q, kc, vc, wl[6])
                                 : gemm(W.resid, wl[1]) + norm(W.ss, qkv.ss_in, d.eps) + rope(d, pos, slots, W.q, kc, vc);
     const GemmArgs to_o = gemm(W.attn, wl[2]) + resid(W.resid, W.ss);
     const GemmArgs to_gate_up = gemm(W.resid, wl[4]) + norm(W.ss, P.gate_up.ss_in, d.eps) + store(W.h);

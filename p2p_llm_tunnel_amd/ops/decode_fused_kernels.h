@@ -10,6 +10,7 @@
 //   per layer:
 //     k_skinny<ROPE>     RMSNorm (attn_norm) -> QKV GEMM -> RoPE on q/k,
 //                        q to the attention buffer, k/v appended to the cache
+//     (QKV-bias models:  k_skinny<ROPE_BIAS>, the same with a bias on q, k and v)
 //     (QK-norm models:   k_skinny<STORE> writes the raw projection instead, and
 //      k_qknorm_rope     norms every q and k head, rotates and appends: a sixth kernel)
 //     k_attn            GQA flash-decoding split-K; the last split to finish
@@ -60,7 +61,9 @@ constexpr int kMaxM = 64;  // token rows per step: up to 4 MFMA row tiles (block
 typedef short frag8 __attribute__((ext_vector_type(8)));
 typedef float frag4 __attribute__((ext_vector_type(4)));
 
-enum Epi : int { EPI_STORE = 0, EPI_ROPE = 1, EPI_SILU = 2, EPI_RESID = 3, EPI_ARGMAX = 4 };
+// EPI_ROPE_BIAS: EPI_ROPE with a per-column bias on q, k and v (Qwen2). A variant of its own, so that
+// models without a bias keep the EPI_ROPE kernels as they are, with no run-time test of a pointer.
+enum Epi : int { EPI_STORE = 0, EPI_ROPE = 1, EPI_SILU = 2, EPI_RESID = 3, EPI_ARGMAX = 4, EPI_ROPE_BIAS = 5 };
 
 struct GemmArgs {
   const uint16_t* x;  // A [M][K]
@@ -81,6 +84,7 @@ struct GemmArgs {
   uint16_t* q_out;
   uint16_t* kc;
   uint16_t* vc;
+  const uint16_t* bias;  // ROPE_BIAS: [N], in the row order of W (interleaved like its rows)
   int H, Hkv, D, Smax;
   float log2_theta;
   float* am_val;  // ARGMAX: [gridDim.x][16]
@@ -267,6 +271,13 @@ __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
     }
   }
 
+  // ROPE_BIAS: this lane's column bias, loaded by wave 0 ahead of the weight
+  // stream like rprev. The host keeps kpl == 0 here, so the column is < N.
+  float bias = 0.f;
+  if constexpr (EPI == EPI_ROPE_BIAS) {
+    if (wv == 0) bias = bf2f(a.bias[tile_col<TN>(bx, 0, c, cwl)]);
+  }
+
   frag4 acc[TN];
 #pragma unroll
   for (int t = 0; t < TN; t++) acc[t] = frag4{0.f, 0.f, 0.f, 0.f};
@@ -374,8 +385,10 @@ __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
       if ((c & 1) || !col_ok || mrow0 + r >= a.M) continue;
       a.out[size_t(mrow0 + r) * (a.N >> 1) + (n >> 1)] = uint16_t(f2bf_bits(mine / (1.f + __expf(-mine)) * other));
     }
-  } else if constexpr (EPI == EPI_ROPE) {
+  } else if constexpr (EPI == EPI_ROPE || EPI == EPI_ROPE_BIAS) {
     // Interleaved rows within each head: column 2i = dim i, 2i+1 = dim i + D/2.
+    // ROPE_BIAS adds the column's bias in fp32 after the 1/rms scale and before
+    // the one rounding ahead of the rotation: q, k and v alike.
     const int half = a.D >> 1;
     const int col = tile_col<TN>(bx, 0, c, cwl);
     const int head = col / a.D, i = (col % a.D) >> 1;
@@ -384,7 +397,7 @@ __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
 #pragma unroll
     for (int r = 0; r < 4; r++) {
       const int m = mrow0 + r;
-      const float mine = bf_round(v[0][r]);
+      const float mine = bf_round(EPI == EPI_ROPE_BIAS ? v[0][r] + bias : v[0][r]);
       const float other = dpp<kDppXor1>(mine);
       if (m >= a.M || !col_ok) continue;
       // Host validates; clamped anyway so a bad index can never write outside the cache.
@@ -590,7 +603,7 @@ __global__ __launch_bounds__(kQkNormWaves * 64) void k_qknorm_rope(QkNormArgs a)
 // dot products with v_dot2_f32_bf16 and finishes them with in-row DPP sums,
 // and ends up holding the softmax weights of exactly the tokens whose V it
 // loaded: P.V needs no data exchange until the final cross-row sum. Scores and
-// P.V are fp32 VALU: with G <= 8 query rows an MFMA tile would be >= half
+// P.V are fp32 VALU (G is only a compile-time loop bound): with G <= 8 query rows an MFMA tile would be >= half
 // padding; the kernel is bound by the K/V stream and latency.
 // The 8 waves of a slot merge through LDS; only spans split over several
 // slots publish a partial (write-through + arrival ticket) that the last slot
