@@ -35,6 +35,10 @@ Two CPU tests keep the bounds honest without the kernel: a plain fp32 torch
 emulation with the same rounding points stays inside every bound, and the same
 emulation with one arithmetic slip (a dropped k-step, a RoPE sign, a token too
 few, a wrong split maximum, a swapped gate/up pair) violates it.
+
+The stage helpers, ``stage_ratios`` and ``emulate`` take any layer of a deeper model (``layer``, default 0, and a
+weight table of 6, 7 or 8 entries per layer); tests/test_gpu_fused_layers.py judges layer 1 of two-layer models
+with them.
 """
 import ctypes
 import functools
@@ -140,7 +144,7 @@ CASES = _cases()
 CASE_IDS = [c.name for c in CASES]
 
 
-EPI_NAMES = ("STORE", "ROPE", "SILU", "RESID", "ARGMAX")  # decode_fused_kernels.h enum Epi
+EPI_NAMES = ("STORE", "ROPE", "SILU", "RESID", "ARGMAX", "ROPE_BIAS")  # decode_fused_kernels.h enum Epi
 STAGES = ("qkv", "attn", "o", "gate_up", "down", "lm_head")
 
 
@@ -149,7 +153,8 @@ def step_plan(case):
     """What the library launches for a case: its own plan (host only), never a copy of its rules."""
     c = case.cfg
     dims = ops.LlamaDims(vocab=c.vocab, dim=c.dim, n_layers=c.n_layers, H=c.n_heads, Hkv=c.n_kv_heads, D=c.head_dim,
-                         ffn=c.ffn, max_seq=c.max_seq, max_batch=case.max_batch + 1, eps=c.eps, theta=c.rope_theta)
+                         ffn=c.ffn, max_seq=c.max_seq, max_batch=case.max_batch + 1, eps=c.eps, theta=c.rope_theta,
+                         qk_norm=int(c.qk_norm), qkv_bias=int(c.qkv_bias))
     return ops.step_plan(dims, case.rows, case.emit_rows)
 
 
@@ -263,8 +268,19 @@ def rope_tables(cfg, pos):
     return torch.cos(ang), torch.sin(ang), dsc
 
 
-def stage_qkv(case, W, x0, pos):
-    """QKV GEMM + RoPE + cache append from embed[token]: (q, k, v) references and bounds, [M, heads, D].
+def table_stride(cfg):
+    """Entries per layer of the fused weight table: the six, + bqkv (Qwen2), or + q_norm, k_norm (Qwen3)."""
+    return 8 if cfg.qk_norm else 7 if cfg.qkv_bias else 6
+
+
+def layer_w(cfg, W, layer, k):
+    """Entry k of ``layer`` in the table W: attn_norm, wqkv, wo, ffn_norm, w_gate_up, w_down (, bqkv | q_norm, k_norm)."""
+    return W[3 + table_stride(cfg) * layer + k]
+
+
+def stage_qkv(case, W, x0, pos, layer=0):
+    """QKV GEMM + RoPE + cache append from the layer's input rows x0 (embed[token] for layer 0): (q, k, v)
+    references and bounds, [M, heads, D].
 
     v = bf(y): bound E + ulp/2 (gemm_ref's E). q and k: the kernel rounds both members of a pair to bf16
     (x1, x2), rotates in fp32 and rounds once more; the reference does the same in fp64. Error before the last
@@ -273,7 +289,7 @@ def stage_qkv(case, W, x0, pos):
     """
     c = case.cfg
     H, Hkv, D, half = c.n_heads, c.n_kv_heads, c.head_dim, c.head_dim // 2
-    y, E = gemm_ref(x0, W[4], c.eps)
+    y, E = gemm_ref(x0, layer_w(c, W, layer, 1), c.eps)
     M = y.shape[0]
     y, E = y.view(M, H + 2 * Hkv, half, 2), E.view(M, H + 2 * Hkv, half, 2)  # pairs (dim i, dim i + D/2)
     vy, vE = y[:, H + Hkv:], E[:, H + Hkv:]
@@ -346,7 +362,7 @@ def silu(z):
     return z / (1 + torch.exp(-z))
 
 
-def stage_swiglu(case, W, r1):
+def stage_swiglu(case, W, r1, layer=0):
     """RMSNorm + gate/up GEMM + SwiGLU, h = bf(silu(bf(g)) * bf(u)): reference and bound [M, ffn].
 
     The inner roundings of g and u can flip within gemm_ref's E: the change of silu over that step of g
@@ -354,7 +370,7 @@ def stage_swiglu(case, W, r1):
     fp32: __expf(-g) is off by (2 |g| + 2) U relatively, which 1 / (1 + e) damps to at most as much; the add,
     the divide (correctly rounded: no fast-math flag) and the multiply add 3 U.
     """
-    y, E = gemm_ref(r1, W[7], case.cfg.eps)
+    y, E = gemm_ref(r1, layer_w(case.cfg, W, layer, 4), case.cfg.eps)
     M = y.shape[0]
     y, E = y.view(M, -1, 2), E.view(M, -1, 2)  # pairs (gate_j, up_j)
     g, u = bf64(y[..., 0]), bf64(y[..., 1])
@@ -379,30 +395,37 @@ def first_argmax(logits):
     return torch.where(l == l.amax(1, keepdim=True), idx, l.shape[1]).amin(1)
 
 
-def stage_ratios(case, W, obs):
-    """Largest |observed - reference| / bound of every stage, each reference computed from the observed
-    inputs of that stage alone."""
+def worst(got, ref_bound):
+    """Largest |got - ref| / bound over the elements: 0 where they agree exactly (a bound of 0 asks for that),
+    inf where the comparison does not hold, a NaN on either side included."""
+    ref, bound = ref_bound
+    err = (got.to(F64).reshape(ref.shape) - ref).abs()
+    r = torch.where(err == 0, torch.zeros_like(err), err / bound)
+    return torch.where(torch.isnan(r), torch.full_like(r, float("inf")), r).max().item()
+
+
+def stage_ratios(case, W, obs, layer=0, qkv_stage=stage_qkv):
+    """Largest |observed - reference| / bound of every stage of ``layer``, each reference computed from the
+    observed inputs of that stage alone. Layer 0 starts from embed[token]; a later layer from its observed input
+    rows ``obs["x0"]``, and ``obs`` then holds that layer's q, attn, r1, h, r2 and its own cache as kc, vc.
+    ``qkv_stage(case, W, x0, pos, layer)`` gives the (q, k, v) references of the model's family."""
     inp = inputs(case)
     c, B = case.cfg, case.rows
     emit = case.emit_rows or B
     rows = torch.arange(B)
     sl = inp.slots.long() if inp.slots is not None else rows
-    x0 = W[0][inp.tokens]
-
-    def ratio(got, ref_bound):
-        ref, bound = ref_bound
-        return ((got.to(F64).reshape(ref.shape) - ref).abs() / bound).max().item()
+    x0 = W[0][inp.tokens] if layer == 0 else obs["x0"]
 
     out = {}
-    qr, kr, vr = stage_qkv(case, W, x0, inp.pos)
-    out["q"] = ratio(obs["q"], qr)
-    out["k"] = ratio(obs["kc"][sl, inp.pos.long()], kr)
-    out["v"] = ratio(obs["vc"][sl, inp.pos.long()], vr)
-    out["attn"] = ratio(obs["attn"], stage_attn(case, obs["q"], obs["kc"], obs["vc"], inp.pos, inp.slots))
-    out["o"] = ratio(obs["r1"], stage_resid(obs["attn"], W[5], x0))
-    out["h"] = ratio(obs["h"], stage_swiglu(case, W, obs["r1"]))
-    out["down"] = ratio(obs["r2"], stage_resid(obs["h"], W[8], obs["r1"]))
-    out["logits"] = ratio(obs["logits"][:emit], stage_lm_head(case, W, obs["r2"][:emit]))
+    qr, kr, vr = qkv_stage(case, W, x0, inp.pos, layer)
+    out["q"] = worst(obs["q"], qr)
+    out["k"] = worst(obs["kc"][sl, inp.pos.long()], kr)
+    out["v"] = worst(obs["vc"][sl, inp.pos.long()], vr)
+    out["attn"] = worst(obs["attn"], stage_attn(case, obs["q"], obs["kc"], obs["vc"], inp.pos, inp.slots))
+    out["o"] = worst(obs["r1"], stage_resid(obs["attn"], layer_w(c, W, layer, 2), x0))
+    out["h"] = worst(obs["h"], stage_swiglu(case, W, obs["r1"], layer))
+    out["down"] = worst(obs["r2"], stage_resid(obs["h"], layer_w(c, W, layer, 5), obs["r1"]))
+    out["logits"] = worst(obs["logits"][:emit], stage_lm_head(case, W, obs["r2"][:emit]))
     want = first_argmax(obs["logits"][:emit])
     out["ids"] = 0.0 if torch.equal(obs["ids"][:emit], want) else float("inf")
     return out
@@ -420,9 +443,27 @@ MUTATIONS = {  # mutation -> the stage outputs of which at least one must leave 
 }
 
 
-def emulate(case, mut=None):
-    """The step in plain fp32 torch with the kernels' bf16 rounding points; ``mut`` names one arithmetic slip.
-    Returns what ``observe_gpu`` returns, so the same ``stage_ratios`` judges it."""
+# Slips of a layer past the first (``emulate``'s ``slip``): what only a layer L >= 1 can get wrong.
+LAYER_SLIPS = (
+    "late_loop",  # the QKV GEMM sums only the 32 * nw sum-of-squares partials that fit its registers
+    "stale_ss",  # ... or takes 1/rms from the partials the previous layer's O projection left
+    "table:wqkv", "table:bias", "table:qk_norm",  # the previous layer's weight-table entry
+    "attend_layer0",  # attention over layer 0's cache
+    "kv_into_layer0",  # the K and V rows appended to layer 0's cache
+    "drop_ss_partial",  # down's epilogue leaves one of its sum-of-squares partials out (every layer)
+)
+
+
+def emulate(case, mut=None, slip=None):
+    """The step in plain fp32 torch with the kernels' bf16 rounding points, layer after layer, each layer on a
+    cache of its own that starts from the case's kc0 / vc0; ``mut`` names one arithmetic slip (in every layer),
+    ``slip`` one of LAYER_SLIPS (in the layers past the first).
+
+    Returns what ``observe_gpu`` returns, for the last layer (kc, vc: its cache), so the same ``stage_ratios``
+    judges it, and with it: x0, the last layer's input rows; caches, every layer's (kc, vc); ss2 and ss3 [parts,
+    B], the sum-of-squares partials the last layer's down projection writes over the residual before it (r1, as
+    when w_down is zero) and after it (r2), one per down.grid_x column tile; qkv, the raw projection of a QK-norm
+    model's last layer."""
     inp = inputs(case)
     c, B, W = case.cfg, case.rows, inp.weights
     H, Hkv, D, half = c.n_heads, c.n_kv_heads, c.head_dim, c.head_dim // 2
@@ -430,28 +471,87 @@ def emulate(case, mut=None):
     emit = case.emit_rows or B
     sl = inp.slots.long() if inp.slots is not None else torch.arange(B)
     pos = inp.pos.long()
+    plan = step_plan(case)
 
-    def gemm(stage, x, w, norm):
+    def sumsq(x):
+        return x.float().pow(2).sum(1)
+
+    def partials(x):  # [B, parts]: down's RESID epilogue sums the squares of its own columns
+        p = x.float().pow(2).view(B, plan.down.grid_x, -1).sum(-1)
+        if slip == "drop_ss_partial":
+            p[:, plan.down.grid_x // 2] = 0
+        return p
+
+    def gemm(stage, x, w, ss=None):  # ss: the row sums of squares of the folded norm (None: no norm)
         x = x.float()
-        rs = torch.rsqrt(x.pow(2).sum(1, keepdim=True) / x.shape[1] + c.eps) if norm else 1.0
+        rs = torch.rsqrt(ss[:, None] / x.shape[1] + c.eps) if ss is not None else 1.0
         if mut == f"drop_kstep:{stage}":
             x = x.clone()
             x[:, 32:64] = 0
         return (x @ w.float().T) * rs
 
-    x0 = W[0][inp.tokens]
-    y = bf32(gemm("qkv", x0, W[4], True)).view(B, H + 2 * Hkv, half, 2)
     inv = torch.exp2(-math.log2(c.rope_theta) * 2 * torch.arange(half, dtype=torch.float32) / D)
     ang = pos.float()[:, None, None] * inv[None, None, :]
     cs, sn = torch.cos(ang), torch.sin(ang)
-    x1, x2 = y[:, :H + Hkv, :, 0], y[:, :H + Hkv, :, 1]
     sn2 = -sn if mut == "rope_sign" else sn
-    qk = torch.cat([x1 * cs - x2 * sn, x2 * cs + x1 * sn2], -1).to(BF)
-    v = torch.cat([y[:, H + Hkv:, :, 0], y[:, H + Hkv:, :, 1]], -1).to(BF)
-    q = qk[:, :H].contiguous()
-    kc, vc = inp.kc0.clone(), inp.vc0.clone()
-    kc[sl, pos], vc[sl, pos] = qk[:, H:], v
+    caches = [(inp.kc0.clone(), inp.vc0.clone()) for _ in range(c.n_layers)]
+    ss_down = ss_o = raw = None
+    r2 = W[0][inp.tokens]
+    for L in range(c.n_layers):
+        late = L > 0
 
+        def entry(k, slipped):  # this layer's table entry k, or layer 0's under the slip that names it
+            return layer_w(c, W, 0 if late and slip == slipped else L, k)
+
+        x0 = r2
+        ss = sumsq(x0)  # layer 0: k_embed's one partial
+        if late:  # the previous down projection's partials
+            ss = (ss_down[:, :32 * plan.qkv.nw] if slip == "late_loop" else ss_down).sum(1)
+            if slip == "stale_ss":
+                ss = ss_o
+        y = gemm("qkv", x0, entry(1, "table:wqkv"), ss)
+        if c.qkv_bias:
+            y = y + entry(6, "table:bias").float()[None, :]
+        if c.qk_norm:  # STORE, then k_qknorm_rope: plain row order, RoPE partners d and d + D/2
+            raw = y.to(BF)
+            xh = raw.float().view(B, H + 2 * Hkv, D)
+            g = torch.cat([entry(6, "table:qk_norm").float().expand(H, D), entry(7, "table:qk_norm").float().expand(Hkv, D)])
+            n = xh[:, :H + Hkv] * torch.rsqrt(xh[:, :H + Hkv].pow(2).sum(-1, keepdim=True) / D + c.eps) * g[None]
+            x1, x2 = n[..., :half], n[..., half:]
+            v = xh[:, H + Hkv:].to(BF)
+        else:
+            y = bf32(y).view(B, H + 2 * Hkv, half, 2)
+            x1, x2 = y[:, :H + Hkv, :, 0], y[:, :H + Hkv, :, 1]
+            v = torch.cat([y[:, H + Hkv:, :, 0], y[:, H + Hkv:, :, 1]], -1).to(BF)
+        qk = torch.cat([x1 * cs - x2 * sn, x2 * cs + x1 * sn2], -1).to(BF)
+        q = qk[:, :H].contiguous()
+        kc, vc = caches[0 if late and slip == "kv_into_layer0" else L]
+        kc[sl, pos], vc[sl, pos] = qk[:, H:], v
+        kc, vc = caches[0 if late and slip == "attend_layer0" else L]
+        attn = _emulate_attn(case, q, kc, vc, mut)
+
+        r1 = bf32(x0.float() + bf32(gemm("o", attn, layer_w(c, W, L, 2)))).to(BF)
+        ss_o = sumsq(r1)
+        gu = bf32(gemm("gate_up", r1, layer_w(c, W, L, 4), ss_o)).view(B, c.ffn, 2)
+        g_, u_ = (gu[..., 1], gu[..., 0]) if mut == "swap_gate_up" else (gu[..., 0], gu[..., 1])
+        h = (g_ / (1 + torch.exp(-g_)) * u_).to(BF)
+        r2 = bf32(r1.float() + bf32(gemm("down", h, layer_w(c, W, L, 5)))).to(BF)
+        ss_down = partials(r2)
+    logits = gemm("lm_head", r2[:emit], W[2], sumsq(r2[:emit])).to(BF)
+    kc, vc = caches[-1]
+    return {"q": q, "kc": kc, "vc": vc, "attn": attn, "r1": r1, "h": h, "r2": r2, "logits": logits,
+            "ids": first_argmax(logits), "x0": x0, "caches": caches, "ss2": partials(r1).T, "ss3": ss_down.T,
+            "qkv": raw}
+
+
+def _emulate_attn(case, q, kc, vc, mut):
+    """``emulate``'s attention: every row over positions 0..pos[row] of its slot, one span slot at a time."""
+    inp = inputs(case)
+    c, B = case.cfg, case.rows
+    H, Hkv, D = c.n_heads, c.n_kv_heads, c.head_dim
+    G = H // Hkv
+    sl = inp.slots.long() if inp.slots is not None else torch.arange(B)
+    pos = inp.pos.long()
     ns = step_plan(case).attn.slots
     scale = torch.tensor(1.0 / math.sqrt(D), dtype=torch.float32)
     attn = torch.empty(B, H * D, dtype=BF)
@@ -477,15 +577,7 @@ def emulate(case, mut=None):
         L = sum(w_ * l for w_, l in zip(ww, ls))
         o = sum(w_ * o_ for w_, o_ in zip(ww, os_))
         attn[b] = (o / L).reshape(H * D).to(BF)
-
-    r1 = bf32(x0.float() + bf32(gemm("o", attn, W[5], False))).to(BF)
-    gu = bf32(gemm("gate_up", r1, W[7], True)).view(B, c.ffn, 2)
-    g_, u_ = (gu[..., 1], gu[..., 0]) if mut == "swap_gate_up" else (gu[..., 0], gu[..., 1])
-    h = (g_ / (1 + torch.exp(-g_)) * u_).to(BF)
-    r2 = bf32(r1.float() + bf32(gemm("down", h, W[8], False))).to(BF)
-    logits = gemm("lm_head", r2[:emit], W[2], True).to(BF)
-    return {"q": q, "kc": kc, "vc": vc, "attn": attn, "r1": r1, "h": h, "r2": r2, "logits": logits,
-            "ids": first_argmax(logits)}
+    return attn
 
 
 @pytest.mark.parametrize("case", CASES, ids=CASE_IDS)
