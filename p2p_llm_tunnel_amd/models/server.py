@@ -34,6 +34,22 @@ would change the output and are not implemented (n > 1, penalties,
 logit_bias, Ollama's repeat_penalty, mirostat, ...) are answered
 with 400, as is sampling on an engine without the captured HIP step.
 
+Penalties (--penalties, off by default: the 400s above stand): OpenAI
+"presence_penalty" and "frequency_penalty" in [-2, 2], the vLLM extension
+"repetition_penalty" in (0, 10] and "logit_bias" (an object of up to 300
+decimal token ids in [0, vocab) -> a bias in [-100, 100]); Ollama
+"options.repeat_penalty" in (0, 10], "presence_penalty" and
+"frequency_penalty". They run on device inside the captured step, ahead of
+the sampler (ops.penalize_, penalty.hip): a per-slot table counts every
+generated id and marks the prompt's, the repetition penalty divides or
+multiplies the logit of every id seen in the prompt or generated (HF / vLLM
+semantics — NOT Ollama's window of the last 64 tokens: "repeat_last_n" is
+accepted only as -1, or 0 = repeat penalty off; anything else is a 400 that
+says so), frequency and presence subtract by the generated count, the bias
+is added last, and greedy requests take the argmax of the result. n > 1,
+best_of, mirostat, tfs_z, typical_p and min_p stay refused. See
+docs/PENALTIES.md.
+
 Chat template variables: a chat request's optional "chat_template_kwargs", a
 JSON object of scalars, is handed to the checkpoint's chat template
 ({"enable_thinking": false} for Qwen3's); anything else is answered with 400.
@@ -44,7 +60,8 @@ computed on device inside the captured step (ops.logprobs_, logprobs.hip: a
 log-sum-exp and a deterministic top-N selection per requesting row) and come
 back with the sampled ids through pinned memory. The distribution is the
 model's own softmax(logits): it does not depend on temperature, top_k or top_p
-(vLLM's default too). Every delivered token has an entry, the tokens of a
+(vLLM's default too), nor on penalties or logit_bias: the logprobs kernel
+reads the raw logits, so a banned token still reports the model's probability. Every delivered token has an entry, the tokens of a
 matched stop sequence included (their text is cut, their entries are not); the
 EOS token has none. A streamed chat response with logprobs sends exactly one
 chunk per token (its "content" is "" when the detokeniser or the stop matcher
@@ -122,6 +139,44 @@ class Sampling:
         return pack_sampling(0.0 if self.greedy else self.temperature, self.top_k, self.top_p, self.seed, counter)
 
 
+class Penalties:
+    """What a request does to its logits ahead of the sampler, on device
+    (``ops.penalize_``, penalty.hip; an engine built with ``penalties=True``):
+    ``repetition`` (HF / vLLM: a seen id's logit x becomes x / r when x > 0,
+    else x * r; seen = anywhere in the prompt or generated; 1 = off), then
+    ``frequency`` and ``presence`` (OpenAI: x -= f * count and x -= p *
+    (count > 0), counts over generated tokens; 0 = off), then ``logit_bias``
+    ({id: value in [-100, 100]}, at most 300 ids, added last)."""
+    __slots__ = ("repetition", "frequency", "presence", "logit_bias")
+
+    def __init__(self, repetition: float = 1.0, frequency: float = 0.0, presence: float = 0.0, logit_bias=None):
+        from p2p_llm_tunnel_amd.ops import MAX_LOGIT_BIAS
+        for name, v, ok in (("repetition", repetition, lambda x: 0.0 < x <= 10.0),
+                            ("frequency", frequency, lambda x: -2.0 <= x <= 2.0),
+                            ("presence", presence, lambda x: -2.0 <= x <= 2.0)):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not ok(v):
+                raise ValueError(f"{name}={v!r} is out of range (repetition in (0, 10], frequency and presence "
+                                 "in [-2, 2])")
+        self.repetition, self.frequency, self.presence = float(repetition), float(frequency), float(presence)
+        bias = dict(logit_bias or {})
+        if len(bias) > MAX_LOGIT_BIAS:
+            raise ValueError(f"logit_bias takes at most {MAX_LOGIT_BIAS} entries, got {len(bias)}")
+        for k, v in bias.items():
+            if type(k) is not int or k < 0 or isinstance(v, bool) or not isinstance(v, (int, float)) or \
+                    not -100.0 <= v <= 100.0:
+                raise ValueError(f"logit_bias maps token ids (ints >= 0) to values in [-100, 100], got {k!r}: {v!r}")
+        self.logit_bias = {k: float(v) for k, v in bias.items()}  # a dict: no id twice
+
+    @property
+    def neutral(self) -> bool:
+        return self.repetition == 1.0 and self.frequency == 0.0 and self.presence == 0.0 and \
+            not any(self.logit_bias.values())
+
+    def column(self) -> list[int]:
+        from p2p_llm_tunnel_amd.ops import pack_penalties
+        return pack_penalties(self.repetition, self.frequency, self.presence)
+
+
 class SamplingError(ValueError):
     """A request asks for sampling this server does not implement (answered with 400)."""
 
@@ -147,23 +202,93 @@ _OLLAMA_NEUTRAL = {"repeat_penalty": (1, 1.0), "presence_penalty": (0, 0.0), "fr
 _MAX_STOPS = 4  # the OpenAI API's limit
 
 
-def sampling_params(body: dict, ollama: bool, default_temperature: float = 0.0) -> Sampling:
+# What --penalties takes out of the two tables above (ops.penalize_ implements them).
+_OPENAI_PENALTY_KEYS = ("presence_penalty", "frequency_penalty", "logit_bias")
+_OLLAMA_PENALTY_KEYS = ("repeat_penalty", "presence_penalty", "frequency_penalty")
+
+
+def penalty_params(body: dict, ollama: bool, vocab: int | None = None) -> Penalties | None:
+    """Penalties of a request on a server started with --penalties; None when
+    every one is absent or neutral. OpenAI: "presence_penalty" and
+    "frequency_penalty" in [-2, 2], the vLLM extension "repetition_penalty" in
+    (0, 10], "logit_bias": an object of at most 300 entries whose keys are
+    decimal token ids in [0, vocab) — two keys that name one id are refused —
+    and whose values are numbers in [-100, 100]. Ollama ("options"):
+    "repeat_penalty" in (0, 10], "presence_penalty", "frequency_penalty" in
+    [-2, 2]. The repeat penalty covers the whole prompt and everything generated
+    (HF / vLLM), not Ollama's window of the last 64 tokens, so "repeat_last_n" is
+    accepted only as -1 (everything) or 0 (which switches the repeat penalty
+    off). Raises SamplingError (answered with 400) naming the parameter."""
+    src = body.get("options", {}) if ollama else body
+    if src is None:
+        src = {}
+    if not isinstance(src, dict):
+        raise SamplingError("options must be an object")
+    presence = _number(src, "presence_penalty", -2.0, 2.0, 0.0)
+    frequency = _number(src, "frequency_penalty", -2.0, 2.0, 0.0)
+    bias = {}
+    if ollama:
+        rep = _number(src, "repeat_penalty", 0.0, 10.0, 1.0, lo_open=True)
+        last_n = src.get("repeat_last_n")
+        if last_n is not None:
+            if type(last_n) is not int or last_n not in (-1, 0):
+                raise SamplingError(f"repeat_last_n={last_n!r} is not supported: the repeat penalty covers the whole "
+                                    "prompt and everything generated; only -1 (everything) and 0 (repeat penalty "
+                                    "off) are accepted")
+            if last_n == 0:
+                rep = 1.0
+    else:
+        rep = _number(src, "repetition_penalty", 0.0, 10.0, 1.0, lo_open=True)
+        raw = src.get("logit_bias")
+        if raw is not None:
+            from p2p_llm_tunnel_amd.ops import MAX_LOGIT_BIAS
+            if not isinstance(raw, dict):
+                raise SamplingError(f"logit_bias must be an object of token id: bias, got {raw!r}")
+            if len(raw) > MAX_LOGIT_BIAS:
+                raise SamplingError(f"logit_bias takes at most {MAX_LOGIT_BIAS} entries, got {len(raw)}")
+            for k, v in raw.items():
+                if not (isinstance(k, str) and k.isascii() and k.isdigit()):
+                    raise SamplingError(f"logit_bias key {k!r} is not a decimal token id")
+                tid = int(k)
+                if vocab is not None and tid >= vocab:
+                    raise SamplingError(f"logit_bias key {k!r} is outside the vocabulary [0, {vocab})")
+                if tid in bias:
+                    raise SamplingError(f"logit_bias names token id {tid} twice")
+                if isinstance(v, bool) or not isinstance(v, (int, float)) or not -100.0 <= v <= 100.0:
+                    raise SamplingError(f"logit_bias[{k!r}] must be a number in [-100, 100], got {v!r}")
+                bias[tid] = float(v)
+    pen = Penalties(rep, frequency, presence, bias)
+    return None if pen.neutral else pen
+
+
+def sampling_params(body: dict, ollama: bool, default_temperature: float = 0.0, penalties: bool = False,
+                    vocab: int | None = None) -> Sampling:
     """Sampling of an OpenAI request (top-level temperature / top_p / seed, and
     the common top_k extension) or an Ollama one ("options"). Raises
     SamplingError for values out of range or parameters not implemented.
 
     "logprobs" and "top_logprobs" are not sampling: this function refuses any
     non-neutral value of either. The OpenAI endpoints parse them first with
-    ``logprob_params`` and pass this function the body without the two keys."""
+    ``logprob_params`` and pass this function the body without the two keys.
+
+    ``penalties`` (a server started with --penalties; ``vocab``: the model's):
+    the penalty parameters and logit_bias are then checked by
+    ``penalty_params`` — whose result the caller takes from there — instead of
+    being refused unless neutral; everything else is as without the switch."""
     src = body.get("options", {}) if ollama else body
     if src is None:
         src = {}
     if not isinstance(src, dict):
         raise SamplingError("options must be an object")
+    taken = () if not penalties else _OLLAMA_PENALTY_KEYS if ollama else _OPENAI_PENALTY_KEYS
     for key, neutral in (_OLLAMA_NEUTRAL if ollama else _OPENAI_NEUTRAL).items():
+        if key in taken:
+            continue
         if key in src and src[key] is not None and not any(src[key] == x and type(src[key]) is type(x)
                                                             for x in neutral):
             raise SamplingError(f"{key}={src[key]!r} is not supported by this server")
+    if penalties:
+        penalty_params(body, ollama, vocab)
     t = _number(src, "temperature", 0.0, 100.0, default_temperature)
     top_p = _number(src, "top_p", 0.0, 1.0, 1.0, lo_open=True)
     top_k = _number(src, "top_k", 0, 1 << 30, 0, integer=True)
@@ -318,12 +443,21 @@ class Request:
     which prefills the prompt's first ``max_seq - 1`` tokens and samples
     nothing: no token is delivered, and when the terminating None arrives
     ``embedding`` holds the pooled, L2-normalised final hidden state (float32,
-    ``dim`` values; the mean over all positions, or the last position's)."""
+    ``dim`` values; the mean over all positions, or the last position's).
+    ``penalties``: a ``Penalties`` (None, or a neutral one, is off); needs an
+    engine built with ``penalties=True``, and an embedding request takes none."""
 
     def __init__(self, prompt_ids: list[int], max_new: int, batched: bool = False, sampling: Sampling | None = None,
-                 logprobs: int | None = None, embed: str | None = None):
+                 logprobs: int | None = None, embed: str | None = None, penalties: Penalties | None = None):
         if embed not in (None, "mean", "last"):
             raise ValueError(f'embed must be None, "mean" or "last", got {embed!r}')
+        if penalties is not None and not isinstance(penalties, Penalties):
+            raise TypeError(f"penalties must be a Penalties, got {penalties!r}")
+        if penalties is not None and penalties.neutral:
+            penalties = None
+        if penalties is not None and embed is not None:
+            raise ValueError("an embedding request samples nothing and takes no penalties")
+        self.penalties = penalties
         self.embed = embed
         self.embedding = None
         if logprobs is not None:
@@ -371,6 +505,9 @@ _TOK, _POS, _SLOT, _DEC, _REC = range(5)
 _SMP = slice(5, 10)
 _LP = 10
 _IN_ROWS = _LP + 1
+# An engine built with penalties=True stages four more rows, ops.penalize_'s
+# column: repetition, frequency and presence bits, flags (0 = the row is off).
+_PEN = slice(_IN_ROWS, _IN_ROWS + 4)
 
 
 class _StepBuf:
@@ -379,10 +516,10 @@ class _StepBuf:
     ``h_lp`` / ``h_lp_ids`` receive ops.logprobs_'s outputs of the rows that
     asked (steps that replay a graph with the logprobs kernel)."""
 
-    def __init__(self, rows: int, cuda: bool, device=None):
+    def __init__(self, rows: int, cuda: bool, device=None, in_rows: int = _IN_ROWS):
         from p2p_llm_tunnel_amd.ops import MAX_TOP_LOGPROBS
         self.rows = rows
-        self.h_in = torch.zeros((_IN_ROWS, rows), dtype=torch.int64, pin_memory=cuda)
+        self.h_in = torch.zeros((in_rows, rows), dtype=torch.int64, pin_memory=cuda)
         self.np = self.h_in.numpy()
         self.h_out = torch.zeros(rows, dtype=torch.int64, pin_memory=cuda)
         self.h_lp = torch.zeros((rows, MAX_TOP_LOGPROBS + 1), dtype=torch.float32, pin_memory=cuda)
@@ -466,10 +603,29 @@ class Engine:
     prefix cache on, an embed request takes no cached prefix (mean pooling needs
     every row); its own rows become resident like any other request's. Steps
     without embed rows launch exactly what they launched before.
+
+    ``penalties`` (off by default: the engine then allocates, captures, stages
+    and replays exactly what is described above) serves ``Request(penalties=)``.
+    The engine keeps, per cache slot and vocabulary id, how often the id was
+    generated and whether it occurs in the prompt (``_pen_state``, int32
+    [max_batch + 1, V]; the scratch slot's row serves capture and padding) and
+    the slot's logit_bias list, and captures a fourth ``post`` per (R, par): 3
+    runs ``ops.penalize_`` (penalty.hip) from the raw logits into a ``work``
+    buffer and replaces the greedy ids by the argmax of that buffer, then the
+    sampler on ``work``, then the logprobs kernel on the RAW logits (so
+    log-probabilities stay the model's own). A step replays post 3 when an
+    emitting row's request has penalties, otherwise the graph it replayed
+    before; rows of other requests in a post-3 step are off (``work`` is a copy
+    of their logits, their ids stand). The count of the token a step samples
+    exists only on the device when the next step is queued, so the kernel
+    counts a decode row's input token itself, one step late and in time.
+    Admission of such a request queues ``ops.penalty_reset_`` for its slot
+    ahead of its first step (``_pen_reset``), whether its prompt's head runs,
+    is reused in place or is copied: the prompt bits come from the prompt ids.
     """
 
     def __init__(self, device="cuda:0", config="tiny", max_batch=8, seed=0, use_graph=True, rows=64, model=None,
-                 small_rows=16, prefix_cache=False, prefix_min=16):
+                 small_rows=16, prefix_cache=False, prefix_min=16, penalties=False):
         if model is None:
             from p2p_llm_tunnel_amd.models.tiny_llm import TinyLlama
             model = TinyLlama(config, device=device, max_batch=max_batch, seed=seed, fused=True)
@@ -495,15 +651,23 @@ class Engine:
         # leading rows that sample (at most one per slot: max_batch rows).
         sizes = [small_rows] + ([rows] if rows > small_rows else []) if use_graph else [rows]
         lp_dev = self.device if use_graph else None
-        self._bufs = {R: [_StepBuf(R, cuda, lp_dev), _StepBuf(R, cuda, lp_dev)] for R in sizes}
-        self._d_in = {R: torch.zeros((_IN_ROWS, R), dtype=torch.int64, device=self.device) for R in sizes}
+        if penalties and not use_graph:
+            raise ValueError("penalties need the graph-captured HIP step; this engine runs eagerly")
+        self.penalties = bool(penalties)
+        in_rows = _PEN.stop if self.penalties else _IN_ROWS
+        self._bufs = {R: [_StepBuf(R, cuda, lp_dev, in_rows), _StepBuf(R, cuda, lp_dev, in_rows)] for R in sizes}
+        self._d_in = {R: torch.zeros((in_rows, R), dtype=torch.int64, device=self.device) for R in sizes}
+        if self.penalties:
+            self._pen_alloc(max_batch, {R: (R if R == small_rows else max_batch) for R in sizes})
         # Each graph holds the whole step (_step_body), one per staging buffer
         # of the pair, so a step is one replay. What follows the fused step is
         # the graph's ``post``: 0 nothing (all-greedy steps), 1 the sampler
         # (some row samples), 2 the sampler, then the logprobs kernel and its
-        # two copies back (some emitting row's request has logprobs set).
+        # two copies back (some emitting row's request has logprobs set); with
+        # ``penalties`` also 3: penalize_, the sampler on its output, logprobs_.
         self._graphs = {(R, par, post): self._capture(self._bufs[R][par], 0 if R == small_rows else max_batch, post)
-                        for R in sizes if use_graph for par in (0, 1) for post in (0, 1, 2)}
+                        for R in sizes if use_graph for par in (0, 1)
+                        for post in ((0, 1, 2, 3) if self.penalties else (0, 1, 2))}
         self.max_batch = max_batch
         self.pending: queue.Queue = queue.Queue()
         self.slots: list[dict | None] = [None] * max_batch
@@ -537,6 +701,11 @@ class Engine:
             raise ValueError("logprobs need the graph-captured HIP step; this engine runs eagerly")
         if req.embed is not None and not self.can_embed:
             raise ValueError("embeddings need a model with embed_pool(jobs, out) (pooling of the final hidden state)")
+        if req.penalties is not None and not self.penalties:
+            raise ValueError("penalties and logit_bias need an engine built with penalties=True (--penalties) on the "
+                             "graph-captured HIP step")
+        if req.penalties is not None and any(t >= self.model.cfg.vocab for t in req.penalties.logit_bias):
+            raise ValueError(f"logit_bias ids must be in [0, {self.model.cfg.vocab})")
         self.pending.put(req)
         self._wake.set()
         return req
@@ -545,6 +714,58 @@ class Engine:
         self._stop.set()
         self._wake.set()
         self.thread.join(timeout=10)
+
+    def _pen_alloc(self, max_batch: int, sample_rows: dict):
+        """Device state of ``penalties`` and the stagings of ``_pen_reset``."""
+        from p2p_llm_tunnel_amd.ops import MAX_LOGIT_BIAS
+        cfg, dev = self.model.cfg, self.device
+        self._pen_state = torch.zeros((max_batch + 1, cfg.vocab), dtype=torch.int32, device=dev)
+        self._pen_bias_n = torch.zeros(max_batch + 1, dtype=torch.int32, device=dev)
+        self._pen_bias_ids = torch.zeros((max_batch + 1, MAX_LOGIT_BIAS), dtype=torch.int32, device=dev)
+        self._pen_bias_val = torch.zeros((max_batch + 1, MAX_LOGIT_BIAS), dtype=torch.float32, device=dev)
+        self._work = {R: torch.zeros((n, cfg.vocab), dtype=torch.bfloat16, device=dev) for R, n in sample_rows.items()}
+        # A reset's input: the prompt ids, then [2, k] bias ids and value bits,
+        # written into pinned memory and copied to ONE device twin (the copy and
+        # the kernel that reads the twin are ordered on the stream, so one is
+        # enough). The pinned side must not be rewritten while a queued copy may
+        # still read it, and a slot can be taken again before its previous
+        # request's only step has drained (one-chunk prompt, max_new = 1: freed
+        # at plan time). Two alternating stagings per slot, no event: a slot is
+        # freed only by a pass of ``_plan`` that ran rows of it or that follows
+        # such a pass, so between two admissions into one slot a step is launched
+        # behind the first one's copy, and ``_loop`` has drained every step
+        # launched two passes back (the step's event covers the copy queued ahead
+        # of it). The third admission is at least two passes after the first:
+        # the staging it rewrites is no longer read.
+        n = cfg.max_seq + 2 * MAX_LOGIT_BIAS
+        self._pen_stage = [[torch.zeros(n, dtype=torch.int32, pin_memory=True) for _ in (0, 1)]
+                           for _ in range(max_batch)]
+        self._pen_turn = [0] * max_batch
+        self._pen_dev = torch.zeros(n, dtype=torch.int32, device=dev)
+
+    def _pen_reset(self, slot: int, req: Request, ids: list):
+        """Queue ``ops.penalty_reset_`` for a request with penalties admitted
+        into ``slot``: ``ids`` is its whole prompt as admitted, cached rows
+        included."""
+        if req.penalties is None:
+            return
+        import numpy as np
+        from p2p_llm_tunnel_amd import ops
+        V = self.model.cfg.vocab
+        h = self._pen_stage[slot][self._pen_turn[slot]]
+        self._pen_turn[slot] ^= 1
+        hn = h.numpy()
+        n = len(ids)
+        hn[:n] = np.asarray(ids, dtype=np.int64) % V
+        bias = [(t, v) for t, v in req.penalties.logit_bias.items() if v != 0.0]  # submit checked the ids
+        k = len(bias)
+        if k:
+            hn[n:n + k] = [t for t, _ in bias]
+            hn[n + k:n + 2 * k] = np.asarray([v for _, v in bias], dtype=np.float32).view(np.int32)
+        d = self._pen_dev[:n + 2 * k]
+        d.copy_(h[:n + 2 * k], non_blocking=True)
+        ops.penalty_reset_(self._pen_state, slot, d[:n], self._pen_bias_n, self._pen_bias_ids, self._pen_bias_val,
+                           d[n:].view(2, k) if k else None)
 
     @staticmethod
     def _resident(s: dict) -> list:
@@ -591,6 +812,8 @@ class Engine:
             self.slots[slot] = self._kv[slot] = req.kv = s
             self._was_busy[slot] = True
             req.cached_tokens = m
+            if self.penalties:
+                self._pen_reset(slot, req, ids)
             if m:
                 self.prefix_hits += 1
                 self.cached_tokens += m
@@ -625,6 +848,8 @@ class Engine:
                 if req.embed is not None:  # nothing is generated: the prompt's head, up to the cache's rows
                     ids = req.prompt[:max_seq - 1] or [0]
                 self.slots[i] = {"req": req, "pos": 0, "ids": ids, "gen": 0, "embed": req.embed}
+                if self.penalties:
+                    self._pen_reset(i, req, ids)
 
     def _plan(self, batch: list):
         """Rows of the next step (``_Row``), with the host-side state advanced
@@ -693,13 +918,16 @@ class Engine:
             self.slots[i] = None
         return rows, emits
 
-    def _step_body(self, b: _StepBuf, n: int, run, sample_rows: int = 0, logprobs: bool = False):
+    def _step_body(self, b: _StepBuf, n: int, run, sample_rows: int = 0, logprobs: bool = False,
+                   penalize: bool = False):
         """One step on the first ``n`` rows of ``b``: staging -> device, decode
         rows' tokens gathered from ``last``, the model through ``run(tokens, pos,
         slots) -> (ids, logits)``, (the sampler over the leading ``sample_rows``
         rows' logits; with ``logprobs``, the logprobs kernel over the same rows
         and the sampled ids, and its outputs -> pinned staging,) last-token
-        scatter, ids -> pinned staging."""
+        scatter, ids -> pinned staging. With ``penalize`` the sampler reads what
+        ``ops.penalize_`` made of those rows' logits; the logprobs kernel still
+        reads the raw ones."""
         din = self._d_in[b.rows]
         din.copy_(b.h_in, non_blocking=True)
         d = din[:, :n]
@@ -707,7 +935,12 @@ class Engine:
         ids, logits = run(tok, d[_POS].to(torch.int32), d[_SLOT].to(torch.int32))
         if sample_rows:
             from p2p_llm_tunnel_amd import ops
-            ops.sample_(logits[:sample_rows], ids[:sample_rows], din[_SMP])
+            drawn = logits[:sample_rows]
+            if penalize:
+                drawn = ops.penalize_(drawn, self._work[b.rows], ids[:sample_rows], tok[:sample_rows], din[_DEC],
+                                      din[_SLOT], din[_PEN], self._pen_state, self._pen_bias_n, self._pen_bias_ids,
+                                      self._pen_bias_val)
+            ops.sample_(drawn, ids[:sample_rows], din[_SMP])
             if logprobs:
                 ops.logprobs_(logits[:sample_rows], ids[:sample_rows], din[_LP], b.d_lp[:sample_rows],
                               b.d_lp_ids[:sample_rows])
@@ -724,7 +957,7 @@ class Engine:
         b.np[_SLOT, :] = b.np[_REC, :] = self.model.scratch_slot  # warm-up and capture touch the scratch slot only
         run = functools.partial(self.model.step_rows, emit_rows=emit_rows)
         sample_rows = (emit_rows or b.rows) if post else 0
-        graph, _ = capture(lambda: self._step_body(b, b.rows, run, sample_rows, post == 2), self.device)
+        graph, _ = capture(lambda: self._step_body(b, b.rows, run, sample_rows, post >= 2, post == 3), self.device)
         torch.cuda.synchronize(self.device)
         return graph
 
@@ -750,6 +983,12 @@ class Engine:
             if req.logprobs is not None:
                 h[_LP, r] = 1 + req.logprobs
                 post = 2
+        if self.penalties:
+            h[_PEN, :] = 0  # every row off unless its request has penalties
+            for r, req, _, _ in emits:
+                if req.penalties is not None:
+                    h[_PEN, r] = req.penalties.column()
+                    post = 3
         if n < R:  # padding rows: scratch slot, nothing recorded
             h[_TOK, n:R] = h[_POS, n:R] = h[_DEC, n:R] = 0
             h[_SLOT, n:R] = h[_REC, n:R] = scratch
@@ -1334,7 +1573,10 @@ class FrontEnd:
             if logprobs is not None and not self.engine.use_graph:
                 raise SamplingError("logprobs need the graph-captured HIP step; this engine runs eagerly")
             rest = req_body if ollama else {k: v for k, v in req_body.items() if k not in _LOGPROB_KEYS}
-            sampling = sampling_params(rest, ollama, self.default_temperature)
+            pen_on = getattr(self.engine, "penalties", False)
+            sampling = sampling_params(rest, ollama, self.default_temperature, penalties=pen_on,
+                                       vocab=self.engine.model.cfg.vocab)
+            penalties = penalty_params(rest, ollama, self.engine.model.cfg.vocab) if pen_on else None
             stops = stop_sequences(req_body, ollama)
             template_kwargs = chat_template_kwargs(req_body)
             if not sampling.greedy and not self.engine.use_graph:
@@ -1348,7 +1590,8 @@ class FrontEnd:
         stream = bool(req_body.get("stream", ollama))
         rid = ("chatcmpl-" if kind == "chat" else "cmpl-") + uuid.uuid4().hex[:12]
         prompt = _prompt_ids(req_body, self.tok, template_kwargs)
-        req = Request(prompt, max(1, min(max_new, 1024)), batched=True, sampling=sampling, logprobs=logprobs)
+        req = Request(prompt, max(1, min(max_new, 1024)), batched=True, sampling=sampling, logprobs=logprobs,
+                      penalties=penalties)
         st = _Stream(writer, stream, kind, rid, name, self.tok.detokenizer(prompt) if self.tok is not None else None,
                      StopMatcher(stops) if stops else None, logprobs is not None)
         req.state = st
@@ -1363,7 +1606,7 @@ class FrontEnd:
 def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_batch=8, model_name=None,
                  engine: Engine | None = None, checkpoint: str | None = None, max_seq: int | None = None,
                  tokenizer=None, default_temperature: float = 0.0, prefix_cache: bool = False, prefix_min: int = 16,
-                 embed_pooling: str = "mean"):
+                 embed_pooling: str = "mean", penalties: bool = False):
     """Engine + HTTP front-end; returns (server, port, engine). ``server.shutdown()``
     stops the HTTP side, ``engine.stop()`` the GPU side. ``checkpoint``: serve a
     Hugging Face Llama checkpoint directory (weights + tokenizer) instead of
@@ -1372,9 +1615,14 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
     ``prefix_cache`` / ``prefix_min``: the engine's prefix cache (``Engine``);
     an injected ``engine`` brings its own setting, which must not contradict.
     ``embed_pooling``: how the embedding routes pool the final hidden state
-    ("mean" over all positions, or the "last" position's)."""
+    ("mean" over all positions, or the "last" position's). ``penalties``: the
+    engine's on-device penalties and logit_bias (``Engine``); the endpoint then
+    takes the parameters ``penalty_params`` describes instead of answering 400,
+    and an injected ``engine`` must have been built with them too."""
     if engine is not None and prefix_cache and not engine.prefix_cache:
         raise ValueError("prefix_cache=True, but the injected engine was built without it")
+    if engine is not None and penalties and not getattr(engine, "penalties", False):
+        raise ValueError("penalties=True, but the injected engine was built without them")
     sys.setswitchinterval(0.0005)  # two busy threads: bound a GIL wait at 0.5 ms, not 5
     tok = tokenizer
     if checkpoint and engine is None:
@@ -1383,10 +1631,10 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
         model = load_llama(checkpoint, device=device, max_batch=max_batch, max_seq=max_seq)
         tok = tok or Tokenizer.for_checkpoint(checkpoint)
         engine = Engine(device=device, max_batch=max_batch, model=model, prefix_cache=prefix_cache,
-                        prefix_min=prefix_min)
+                        prefix_min=prefix_min, penalties=penalties)
         model_name = model_name or os.path.basename(os.path.normpath(checkpoint))
     engine = engine or Engine(device=device, config=config, max_batch=max_batch, prefix_cache=prefix_cache,
-                              prefix_min=prefix_min)
+                              prefix_min=prefix_min, penalties=penalties)
     srv = FrontEnd(engine, host, port, model_name or f"p2pt-{config}", tokenizer=tok,
                    default_temperature=default_temperature, embed_pooling=embed_pooling)
     return srv, srv.server_address[1], engine
@@ -1412,6 +1660,8 @@ def _replicas(a) -> int:
             cmd += ["--prefix-cache", "--prefix-min", str(a.prefix_min)]
         if getattr(a, "embed_pooling", "mean") != "mean":
             cmd += ["--embed-pooling", a.embed_pooling]
+        if getattr(a, "penalties", False):
+            cmd += ["--penalties"]
         procs.append(subprocess.Popen(cmd))
     ups = ",".join(f"http://{a.host}:{base + i}" for i in range(a.gpus))
     print(f"{a.gpus} inference endpoints; use: tunnel serve --upstream {ups}", flush=True)
@@ -1455,13 +1705,19 @@ def main(argv=None):
     ap.add_argument("--embed-pooling", choices=("mean", "last"), default="mean",
                     help="how /v1/embeddings, /api/embed and /api/embeddings pool the final hidden state: the mean "
                          "over all positions, or the last position's (both L2-normalised)")
+    ap.add_argument("--penalties", action="store_true",
+                    help="apply presence_penalty, frequency_penalty, repetition_penalty and logit_bias (OpenAI) and "
+                         "repeat_penalty, presence_penalty, frequency_penalty (Ollama options) on the device ahead "
+                         "of the sampler instead of answering 400; the repeat penalty covers the whole prompt and "
+                         "everything generated (repeat_last_n: only -1, or 0 = off). Costs a [max_batch + 1, vocab] "
+                         "int32 count table and four more captured graphs")
     a = ap.parse_args(argv)
     if a.gpus > 0:
         raise SystemExit(_replicas(a))
     srv, port, engine = start_server(a.host, a.port, a.device, a.config, a.max_batch, checkpoint=a.checkpoint,
                                      max_seq=a.max_seq, default_temperature=a.default_temperature,
                                      prefix_cache=a.prefix_cache, prefix_min=a.prefix_min,
-                                     embed_pooling=a.embed_pooling)
+                                     embed_pooling=a.embed_pooling, penalties=a.penalties)
     print(f"inference endpoint on http://{a.host}:{port} ({a.checkpoint or a.config}, {a.device})", flush=True)
     try:
         threading.Event().wait()

@@ -1,5 +1,5 @@
 """Python front-end for the gfx950 HIP kernels (``kernels.hip``, ``decode_fused.hip``, ``sample.hip``,
-``logprobs.hip``, ``kv_copy.hip``, ``embed_pool.hip``).
+``logprobs.hip``, ``kv_copy.hip``, ``embed_pool.hip``, ``penalty.hip``).
 
 The kernels are compiled in-tree into ``_hip_ops.so`` (see ``build.py``) and
 called through ctypes on the current torch stream. Every wrapper validates
@@ -72,6 +72,9 @@ def lib() -> ctypes.CDLL:
         _LIB.p2pt_max_kv_copy_jobs.argtypes = []
         _LIB.p2pt_embed_pool.argtypes = [vp, i, i, vp, vp, i, vp, i, f, i, ctypes.POINTER(ctypes.c_int), vp]
         _LIB.p2pt_max_embed_jobs.argtypes = []
+        _LIB.p2pt_penalize.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, vp, i, vp, vp, vp, i, i, vp]
+        _LIB.p2pt_penalty_reset.argtypes = [vp, i, i, i, vp, i, vp, vp, vp, vp, i, vp]
+        _LIB.p2pt_max_logit_bias.argtypes = []
         _LIB.p2pt_llama_ws_bytes.argtypes = [ctypes.POINTER(LlamaDims)]
         _LIB.p2pt_llama_ws_bytes.restype = ctypes.c_size_t
         szp = ctypes.POINTER(ctypes.c_size_t)
@@ -88,7 +91,8 @@ def lib() -> ctypes.CDLL:
         for fn in ("p2pt_rmsnorm", "p2pt_silu_mul", "p2pt_rope_qkv_cache", "p2pt_decode_attention", "p2pt_argmax",
                    "p2pt_skinny_gemm", "p2pt_llama_decode", "p2pt_sample", "p2pt_logprobs", "p2pt_llama_plan", "p2pt_attn_span",
                    "p2pt_max_rows", "p2pt_skinny_bench", "p2pt_attn_bench", "p2pt_kv_copy", "p2pt_max_kv_copy_jobs",
-                   "p2pt_embed_pool", "p2pt_max_embed_jobs", "p2pt_qk_norm_rope_cache"):
+                   "p2pt_embed_pool", "p2pt_max_embed_jobs", "p2pt_qk_norm_rope_cache", "p2pt_penalize",
+                   "p2pt_penalty_reset", "p2pt_max_logit_bias"):
             getattr(_LIB, fn).restype = ctypes.c_int
         if _LIB.p2pt_max_rows() != MAX_ROWS:
             raise RuntimeError(f"MAX_ROWS = {MAX_ROWS}, but {path} was built for {_LIB.p2pt_max_rows()} rows")
@@ -98,12 +102,16 @@ def lib() -> ctypes.CDLL:
         if _LIB.p2pt_max_embed_jobs() != MAX_EMBED_JOBS:
             raise RuntimeError(f"MAX_EMBED_JOBS = {MAX_EMBED_JOBS}, but {path} was built for "
                                f"{_LIB.p2pt_max_embed_jobs()} jobs")
+        if _LIB.p2pt_max_logit_bias() != MAX_LOGIT_BIAS:
+            raise RuntimeError(f"MAX_LOGIT_BIAS = {MAX_LOGIT_BIAS}, but {path} was built for "
+                               f"{_LIB.p2pt_max_logit_bias()} entries")
     return _LIB
 
 
 MAX_ROWS = 64  # token rows per fused step; lib() checks it against decode_fused.hip's kMaxM
 MAX_KV_COPY_JOBS = 8  # jobs per launch of kv_copy_ (kv_copy.hip's kMaxJobs: they travel in the kernel arguments)
 MAX_EMBED_JOBS = 16  # jobs per launch of embed_pool_ (embed_pool.hip's kMaxJobs: in the kernel arguments too)
+MAX_LOGIT_BIAS = 300  # entries of a slot's logit_bias list (penalty.hip's kMaxBias; the OpenAI API's limit)
 MAX_TOP_LOGPROBS = 20  # top (id, logprob) pairs per row of logprobs_ (logprobs.hip's kMaxTop; the OpenAI API's limit)
 
 
@@ -383,6 +391,110 @@ def logprobs_(logits: torch.Tensor, ids: torch.Tensor, want: torch.Tensor, out_l
         raise ValueError(f"need out_lp [B, {MAX_TOP_LOGPROBS + 1}] and out_ids [B, {MAX_TOP_LOGPROBS}]")
     _ok(lib().p2pt_logprobs(_p(logits), _p(ids), _p(want), _p(out_lp), _p(out_ids), B, V, _stream(logits)),
         "logprobs")
+
+
+def _penalty_tables(state, bias_n, bias_ids, bias_val):
+    """Shape, dtype and device checks of the penalty state shared by ``penalize_`` and ``penalty_reset_``."""
+    _check(state, torch.int32, "state")
+    dev = state.device
+    _check(bias_n, torch.int32, "bias_n", dev)
+    _check(bias_ids, torch.int32, "bias_ids", dev)
+    _check(bias_val, torch.float32, "bias_val", dev)
+    if state.dim() != 2 or state.shape[0] < 1 or state.shape[1] < 32:
+        raise ValueError(f"state must be [n_slots >= 1, V >= 32], got {tuple(state.shape)}")
+    n_slots, V = state.shape
+    if bias_n.shape != (n_slots,) or bias_ids.shape != (n_slots, MAX_LOGIT_BIAS) or bias_val.shape != bias_ids.shape:
+        raise ValueError(f"need bias_n [{n_slots}], bias_ids and bias_val [{n_slots}, {MAX_LOGIT_BIAS}]")
+    if V % 8 == 0 and state.data_ptr() % 16:
+        raise ValueError("state must be 16-byte aligned")
+    return n_slots, V
+
+
+PENALTY_ON = 1  # flags word of a ``penalize_`` params column: bit 0 = the row is on
+
+
+def pack_penalties(repetition: float, frequency: float, presence: float, on: bool = True) -> list[int]:
+    """One params column for ``penalize_``."""
+    return [f32_bits(repetition), f32_bits(frequency), f32_bits(presence), PENALTY_ON if on else 0]
+
+
+def penalize_(logits: torch.Tensor, work: torch.Tensor, ids: torch.Tensor, tok: torch.Tensor, dec: torch.Tensor,
+              slot: torch.Tensor, params: torch.Tensor, state: torch.Tensor, bias_n: torch.Tensor,
+              bias_ids: torch.Tensor, bias_val: torch.Tensor) -> torch.Tensor:
+    """Repetition / frequency / presence penalties and logit_bias ahead of the
+    sampler (penalty.hip), one workgroup per row of bf16 ``logits`` [B, V >= 32],
+    which is never written. ``params``: int64 [4, >= B] (column b for row b; see
+    ``pack_penalties``): float32 bits of repetition (1 off), frequency (0 off)
+    and presence (0 off), then a flags word, 0 = the row is off. An off row
+    gets ``work[b]`` (bf16 [B, V], another buffer than ``logits``) as a
+    bit-for-bit copy and nothing else. A row that is on reads the counts of its
+    slot ``slot[b]`` (int64 [>= B]; a slot outside ``state`` turns the row off)
+    from ``state`` (int32 [n_slots, V]: bits 0..29 times generated, bit 30 "in
+    the prompt"); if ``dec[b]`` (int64 [>= B]) is non-zero its input token
+    ``tok[b]`` (int64 [B]) counts once more and the incremented word is written
+    back. Seen ids (count > 0 or prompt bit) get x > 0 ? x / rep : x * rep, then
+    every id x -= freq * count and x -= pres * (count > 0), in fp32, rounded
+    to bf16 into ``work``; then the slot's ``bias_n[s]`` (int32 [n_slots])
+    entries of ``bias_ids`` / ``bias_val`` (int32 / float32 [n_slots, 300]) are
+    added to the stored values; then ``ids[b]`` (int64 [B], in place) becomes the
+    argmax of the stored row (lowest id on ties, NaN never wins, 0 without a
+    winner). Returns ``work``."""
+    _check(logits, torch.bfloat16, "logits")
+    dev = logits.device
+    _check(work, torch.bfloat16, "work", dev)
+    for name, t in (("ids", ids), ("tok", tok), ("dec", dec), ("slot", slot), ("params", params)):
+        _check(t, torch.int64, name, dev)
+    n_slots, V = _penalty_tables(state, bias_n, bias_ids, bias_val)
+    if state.device != dev:
+        raise ValueError(f"state on {state.device}, expected {dev}")
+    if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] != V:
+        raise ValueError(f"logits must be [B >= 1, {V}] (state's vocabulary), got {tuple(logits.shape)}")
+    B = logits.shape[0]
+    if work.shape != logits.shape:
+        raise ValueError(f"work must be {tuple(logits.shape)}, got {tuple(work.shape)}")
+    lo, hi = logits.data_ptr(), logits.data_ptr() + logits.numel() * 2
+    if work.data_ptr() < hi and lo < work.data_ptr() + work.numel() * 2:
+        raise ValueError("work must not overlap logits (the raw logits are never written)")
+    if ids.shape != (B,) or tok.shape != (B,):
+        raise ValueError("ids and tok must be [B]")
+    if dec.dim() != 1 or slot.dim() != 1 or dec.shape[0] < B or slot.shape[0] < B:
+        raise ValueError("dec and slot need an entry per row")
+    if params.dim() != 2 or params.shape[0] != 4 or params.shape[1] < B:
+        raise ValueError("params must be [4, >= B]")
+    if V % 8 == 0 and (logits.data_ptr() % 16 or work.data_ptr() % 16):
+        raise ValueError("logits and work must be 16-byte aligned")
+    _ok(lib().p2pt_penalize(_p(logits), _p(work), _p(ids), _p(tok), _p(dec), _p(slot), _p(params), params.shape[1],
+                            _p(state), n_slots, _p(bias_n), _p(bias_ids), _p(bias_val), B, V, _stream(logits)),
+        "penalize")
+    return work
+
+
+def penalty_reset_(state: torch.Tensor, slot: int, prompt_ids: torch.Tensor, bias_n: torch.Tensor,
+                   bias_ids: torch.Tensor, bias_val: torch.Tensor, bias: torch.Tensor | None = None) -> None:
+    """Admission of a request into ``slot`` of the penalty state (penalty.hip;
+    see ``penalize_`` for the tables): the slot's ``state`` row is zeroed, bit 30
+    is set for every id of ``prompt_ids`` (int32 [n >= 1] on the device; ids
+    outside [0, V) are ignored) and the slot's bias list becomes ``bias``: None
+    for an empty one, or int32 [2, k <= 300] on the device, ids in row 0 and the
+    float32 bits of their values in row 1 (the caller keeps the ids distinct).
+    A clear and one launch on the current stream: no sync, no allocation, other
+    slots untouched. Never captured."""
+    n_slots, V = _penalty_tables(state, bias_n, bias_ids, bias_val)
+    dev = state.device
+    if isinstance(slot, bool) or not isinstance(slot, int) or not 0 <= slot < n_slots:
+        raise ValueError(f"slot must be an int in [0, {n_slots}), got {slot!r}")
+    _check(prompt_ids, torch.int32, "prompt_ids", dev)
+    if prompt_ids.dim() != 1 or prompt_ids.shape[0] < 1:
+        raise ValueError("prompt_ids must be [n >= 1]")
+    k = 0
+    if bias is not None:
+        _check(bias, torch.int32, "bias", dev)
+        if bias.dim() != 2 or bias.shape[0] != 2 or not 1 <= bias.shape[1] <= MAX_LOGIT_BIAS:
+            raise ValueError(f"bias must be int32 [2, 1..{MAX_LOGIT_BIAS}] (ids; float32 bits), got {tuple(bias.shape)}")
+        k = bias.shape[1]
+    _ok(lib().p2pt_penalty_reset(_p(state), n_slots, V, slot, _p(prompt_ids), prompt_ids.shape[0],
+                                 _p(bias_n), _p(bias_ids), _p(bias_val), _p(bias), k, _stream(state)),
+        "penalty_reset")
 
 
 def kv_copy_(k_cache: torch.Tensor, v_cache: torch.Tensor, jobs) -> None:
