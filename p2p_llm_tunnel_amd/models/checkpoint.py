@@ -37,6 +37,12 @@ variants) is the Llama layout plus a bias on the q, k and v projections
 another architecture that carries ``q_proj.bias`` is refused, as is any
 checkpoint with an ``o_proj`` or MLP bias.
 
+Llama 3.1 / 3.2 / 3.3 checkpoints (and their distillations) scale the RoPE
+frequencies: ``rope_scaling`` of type ``llama3``, or ``linear`` in older
+long-context fine-tunes (``LlamaConfig.rope_scaling``, ``models/rope.py``).
+Every key the type needs must be in the config; ``yarn``, ``dynamic``,
+``longrope`` and any other type are refused.
+
 HF Llama q/k projections are already laid out for the rotate-half RoPE
 convention our kernels use (``reference_logits``), so no head permutation is
 needed here; the fused decoder applies its own interleaving at setup.
@@ -48,6 +54,7 @@ import os
 
 import torch
 
+from p2p_llm_tunnel_amd.models import rope as rope_mod
 from p2p_llm_tunnel_amd.models.tiny_llm import LlamaConfig, TinyLlama
 
 _SUPPORTED = {"LlamaForCausalLM", "MistralForCausalLM", "Qwen2ForCausalLM", "Qwen3ForCausalLM"}
@@ -74,8 +81,7 @@ def read_config(path: str, max_seq: int | None = None) -> tuple[LlamaConfig, dic
     # transformers >= 5 writes rope_parameters {rope_theta, rope_type}; older
     # files carry rope_theta (+ rope_scaling) at the top level.
     rope = raw.get("rope_parameters") or raw.get("rope_scaling") or {}
-    if rope.get("rope_type", rope.get("type", "default")) != "default":
-        raise ValueError(f"rope type {rope.get('rope_type', rope.get('type'))!r} is not supported by the decode kernels")
+    scaling = rope_mod.from_hf(rope)  # None: default RoPE; llama3 or linear; anything else is refused
     theta = rope.get("rope_theta", raw.get("rope_theta", 10000.0))
     if raw.get("hidden_act", "silu") != "silu":
         raise ValueError(f"hidden_act {raw['hidden_act']!r}: only SwiGLU (silu) decoders are supported")
@@ -102,7 +108,7 @@ def read_config(path: str, max_seq: int | None = None) -> tuple[LlamaConfig, dic
         ffn=int(raw["intermediate_size"]),
         max_seq=int(max_seq or min(int(raw.get("max_position_embeddings", 2048)), 8192)),
         eps=float(raw.get("rms_norm_eps", 1e-5)), rope_theta=float(theta), qk_norm=arch in _QK_NORM,
-        qkv_bias=arch in _QKV_BIAS)
+        qkv_bias=arch in _QKV_BIAS, rope_scaling=scaling)
     return cfg, raw
 
 

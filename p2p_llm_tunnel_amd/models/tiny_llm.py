@@ -27,6 +27,8 @@ import torch
 import torch.nn.functional as F
 
 from p2p_llm_tunnel_amd import ops
+from p2p_llm_tunnel_amd.models import rope as rope_mod
+from p2p_llm_tunnel_amd.models.rope import RopeScaling
 
 
 @dataclass(frozen=True)
@@ -43,6 +45,8 @@ class LlamaConfig:
     rope_theta: float = 10000.0
     qk_norm: bool = False  # per-head RMSNorm on q and k before RoPE (Qwen3): layers carry q_norm, k_norm [head_dim]
     qkv_bias: bool = False  # bias on the q, k and v projections (Qwen2): layers carry bqkv [(H + 2 Hkv) * head_dim]
+    # llama3 / linear RoPE scaling (Llama 3.1+): the kernels read inv_freq from a table instead of computing it
+    rope_scaling: RopeScaling | None = None
 
 
 CONFIGS = {
@@ -83,6 +87,7 @@ class TinyLlama:
         self._fused = None
         self._graphs = {}  # rows -> (graph, tokens, pos, slots, ids, logits)
         self._embed_acc = None  # embed_pool's running sums, allocated on first use
+        self._inv_freq = None  # the scaled model's RoPE frequency table on the device, made on first use
         c = self.cfg
         self.device = torch.device(device)
         self.max_batch = max_batch
@@ -183,6 +188,17 @@ class TinyLlama:
         ids, logits = self.step_rows(tokens, pos, slots, emit_rows, pos_range)
         return (ids, logits) if return_logits else ids
 
+    def rope_inv_freq(self) -> torch.Tensor | None:
+        """fp32 [head_dim / 2] RoPE frequencies of a model with ``cfg.rope_scaling`` (``rope.inv_freq``), on the
+        model's device; None for default RoPE, whose kernels compute theirs inline. Made once, and its entries
+        checked then (``rope.inv_freq``): the unfused step passes it on with ``inv_freq_checked``."""
+        c = self.cfg
+        if c.rope_scaling is None:
+            return None
+        if self._inv_freq is None:
+            self._inv_freq = rope_mod.inv_freq(c.rope_theta, c.head_dim, c.rope_scaling, self.device)
+        return self._inv_freq
+
     def fused_weights(self) -> list:
         """The fused step's weight table (device-independent: plain torch)."""
         c = self.cfg
@@ -193,7 +209,8 @@ class TinyLlama:
         # wqkv's rows in plain order (its RoPE runs in k_qknorm_rope, which pairs
         # the partners itself) and appends q_norm, k_norm to each layer's six. A
         # QKV-bias model appends bqkv, interleaved like wqkv's rows (the fold
-        # touches only wqkv).
+        # touches only wqkv). A model with scaled RoPE carries its frequency table (fp32)
+        # as a fourth global entry, between lm_head and the layers.
         def fold(w, g):
             return (w.float() * g.float()[None, :]).to(torch.bfloat16)
 
@@ -204,6 +221,8 @@ class TinyLlama:
         head_perm = (torch.arange(heads, device=self.device)[:, None] * c.head_dim
                      + pairs(c.head_dim // 2)[None, :]).flatten()
         ws = [self.embed, self.final_norm, fold(self.lm_head, self.final_norm)]
+        if c.rope_scaling is not None:
+            ws.append(self.rope_inv_freq())
         for L in self.layers:
             wqkv = fold(L["wqkv"], L["attn_norm"])
             ws += [L["attn_norm"], wqkv.contiguous() if c.qk_norm else wqkv[head_perm].contiguous(), L["wo"],
@@ -219,7 +238,8 @@ class TinyLlama:
             c = self.cfg
             dims = ops.LlamaDims(vocab=c.vocab, dim=c.dim, n_layers=c.n_layers, H=c.n_heads, Hkv=c.n_kv_heads,
                                  D=c.head_dim, ffn=c.ffn, max_seq=c.max_seq, max_batch=self.max_batch + 1, eps=c.eps,
-                                 theta=c.rope_theta, qk_norm=int(c.qk_norm), qkv_bias=int(c.qkv_bias))
+                                 theta=c.rope_theta, qk_norm=int(c.qk_norm), qkv_bias=int(c.qkv_bias),
+                                 rope_table=int(c.rope_scaling is not None))
             self._fused = ops.FusedLlamaDecoder(dims, self.fused_weights(), self.k_cache, self.v_cache)
         return self._fused
 
@@ -254,7 +274,7 @@ class TinyLlama:
                 kn = ops.rmsnorm(qkv[:, nq:nq + nk].reshape(-1, c.head_dim), L["k_norm"], c.eps).view(B, nk)
                 qkv = torch.cat([qn, kn, qkv[:, nq + nk:]], 1)
             q = ops.rope_qkv_cache(qkv, pos, kc, vc, c.n_heads, c.n_kv_heads, c.head_dim, c.rope_theta,
-                                   pos_range=pos_range)
+                                   pos_range=pos_range, inv_freq=self.rope_inv_freq(), inv_freq_checked=True)
             a = ops.decode_attention(q, kc, vc, lens, max_len=pos_range[1] + 1)
             o = F.linear(a.view(B, -1), L["wo"])
             h, residual = ops.rmsnorm(o, L["ffn_norm"], c.eps, residual=residual)
@@ -326,8 +346,11 @@ class TinyLlama:
             return v.to(torch.bfloat16).float()
 
         pos = torch.arange(T, device=seqs.device, dtype=torch.float32)
-        inv_freq = torch.exp2(-math.log2(c.rope_theta) * torch.arange(0, c.head_dim // 2, device=seqs.device,
-                                                                      dtype=torch.float32) * 2 / c.head_dim)
+        if c.rope_scaling is not None:  # the table the kernels read
+            inv_freq = rope_mod.inv_freq(c.rope_theta, c.head_dim, c.rope_scaling, seqs.device)
+        else:
+            inv_freq = torch.exp2(-math.log2(c.rope_theta) * torch.arange(0, c.head_dim // 2, device=seqs.device,
+                                                                          dtype=torch.float32) * 2 / c.head_dim)
         ang = pos[:, None] * inv_freq[None, :]
         cos, sin = torch.cos(ang), torch.sin(ang)
 

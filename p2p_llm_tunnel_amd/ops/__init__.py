@@ -23,6 +23,7 @@ class LlamaDims(ctypes.Structure):
     """Mirror of ``LlamaDims`` in decode_fused.hip."""
     _fields_ = [(n, ctypes.c_int) for n in ("vocab", "dim", "n_layers", "H", "Hkv", "D", "ffn", "max_seq",
                                            "max_batch")] + [("eps", ctypes.c_float), ("theta", ctypes.c_float),
+                                                            ("rope_table", ctypes.c_int),
                                                             ("qk_norm", ctypes.c_int), ("qkv_bias", ctypes.c_int)]
 
 
@@ -43,10 +44,11 @@ class AttnPlan(ctypes.Structure):
 
 class StepPlan(ctypes.Structure):
     """Mirror of ``StepPlan``: what one fused step launches (``qkv_first``: layer 0; ``qk_norm_grid``:
-    ``k_qknorm_rope``'s gridDim.x, 0 when the model has no QK-norm and the kernel is not launched)."""
+    ``k_qknorm_rope``'s gridDim.x, 0 when the model has no QK-norm and the kernel is not launched;
+    ``qk_norm_table``: 1 when that kernel is the variant that reads the RoPE frequencies from a table)."""
     _fields_ = ([("rows", _INT), ("emit_rows", _INT)] +
                 [(n, GemmPlan) for n in ("qkv_first", "qkv", "o", "gate_up", "down", "lm_head")] +
-                [("attn", AttnPlan), ("am_parts", _INT), ("qk_norm_grid", _INT)])
+                [("attn", AttnPlan), ("am_parts", _INT), ("qk_norm_grid", _INT), ("qk_norm_table", _INT)])
 
 
 def lib() -> ctypes.CDLL:
@@ -61,8 +63,8 @@ def lib() -> ctypes.CDLL:
         vp, i, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
         _LIB.p2pt_rmsnorm.argtypes = [vp, vp, vp, vp, vp, i, i, f, vp]
         _LIB.p2pt_silu_mul.argtypes = [vp, vp, i, i, vp]
-        _LIB.p2pt_rope_qkv_cache.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, f, vp]
-        _LIB.p2pt_qk_norm_rope_cache.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, f, f, vp]
+        _LIB.p2pt_rope_qkv_cache.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, f, vp, vp]
+        _LIB.p2pt_qk_norm_rope_cache.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, f, f, vp, vp]
         _LIB.p2pt_decode_attention.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, f, vp]
         _LIB.p2pt_argmax.argtypes = [vp, vp, i, i, vp]
         _LIB.p2pt_skinny_gemm.argtypes = [vp, vp, vp, i, i, i, vp]
@@ -195,14 +197,32 @@ def silu_mul(gate_up: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _check_inv_freq(inv_freq: torch.Tensor, head_dim: int, device, values: bool = True) -> None:
+    """A RoPE frequency table for the kernels that take one: fp32, contiguous, (head_dim / 2,), on ``device``,
+    8-byte aligned (``k_qknorm_rope`` reads it in pairs), every entry finite and > 0. ``values``: read the table
+    back (a sync) for the last of these; a per-step caller that made and checked its table once passes False and
+    keeps the host-side checks alone."""
+    _check(inv_freq, torch.float32, "inv_freq", device)
+    if inv_freq.shape != (head_dim // 2,):
+        raise ValueError(f"inv_freq shape {tuple(inv_freq.shape)} != ({head_dim // 2},)")
+    if inv_freq.data_ptr() % 8:
+        raise ValueError("inv_freq must be 8-byte aligned")
+    if values and not bool((torch.isfinite(inv_freq) & (inv_freq > 0)).all().item()):
+        raise ValueError("inv_freq entries must be finite and > 0")
+
+
 def rope_qkv_cache(qkv: torch.Tensor, pos: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
                    n_heads: int, n_kv_heads: int, head_dim: int, theta: float = 10000.0,
-                   pos_range: tuple[int, int] | None = None) -> torch.Tensor:
+                   pos_range: tuple[int, int] | None = None, inv_freq: torch.Tensor | None = None,
+                   inv_freq_checked: bool = False) -> torch.Tensor:
     """Apply RoPE to q and k of one new token per sequence and append k, v to the caches.
 
     qkv: [B, (H + 2*Hkv) * D]; pos: int32 [B]; caches: [B, Smax, Hkv, D]. Returns q [B, H, D].
     ``pos_range`` = host-known (min, max) of ``pos``; without it the bounds are
-    read back from the device (a sync) before launch.
+    read back from the device (a sync) before launch. ``inv_freq``: fp32 (head_dim / 2,) RoPE frequencies
+    (scaled RoPE: ``models.rope.inv_freq``), used instead of theta's own. Its entries are read back (a sync) and
+    checked unless ``inv_freq_checked`` says the caller has done so (``models.rope.inv_freq`` does, on the host):
+    with it and ``pos_range`` the call syncs nothing and can be captured into a hipGraph.
     """
     _check(qkv, torch.bfloat16, "qkv")
     _check(pos, torch.int32, "pos", qkv.device)
@@ -221,16 +241,19 @@ def rope_qkv_cache(qkv: torch.Tensor, pos: torch.Tensor, k_cache: torch.Tensor, 
     pmin, pmax = pos_range if pos_range is not None else (int(pos.min().item()), int(pos.max().item()))
     if pmin < 0 or pmax >= Smax:
         raise ValueError(f"positions out of cache range [0, {Smax})")
+    if inv_freq is not None:
+        _check_inv_freq(inv_freq, head_dim, qkv.device, values=not inv_freq_checked)
     q = torch.empty(B, n_heads, head_dim, dtype=qkv.dtype, device=qkv.device)
     _ok(lib().p2pt_rope_qkv_cache(_p(qkv), _p(pos), _p(q), _p(k_cache), _p(v_cache), B, n_heads, n_kv_heads,
-                                  head_dim, Smax, theta, _stream(qkv)), "rope_qkv_cache")
+                                  head_dim, Smax, theta, _p(inv_freq), _stream(qkv)), "rope_qkv_cache")
     return q
 
 
 def qk_norm_rope_cache(qkv: torch.Tensor, pos: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
                        q_weight: torch.Tensor, k_weight: torch.Tensor, n_heads: int, n_kv_heads: int, head_dim: int,
                        eps: float, theta: float, slots: torch.Tensor | None = None,
-                       pos_range: tuple[int, int] | None = None) -> torch.Tensor:
+                       pos_range: tuple[int, int] | None = None, inv_freq: torch.Tensor | None = None,
+                       inv_freq_checked: bool = False) -> torch.Tensor:
     """Per-head RMSNorm of q and k (QK-norm models: Qwen3), then RoPE and the cache append: the kernel the
     fused step of such a model launches after its QKV GEMM (``k_qknorm_rope``), on caller tensors.
 
@@ -239,7 +262,9 @@ def qk_norm_rope_cache(qkv: torch.Tensor, pos: torch.Tensor, k_cache: torch.Tens
     fp32, is rotated (rotate-half) at ``pos[b]`` and rounded to bf16 once; v is copied bit for bit. Row b goes
     to cache slot ``slots[b]`` (int32 [B]; default: slot b, so B <= n_slots). Returns q [B, H, D]. ``pos_range``
     = host-known (min, max) of ``pos``; without it the bounds are read back from the device (a sync) before
-    launch, as those of ``slots`` always are."""
+    launch, as those of ``slots`` always are. ``inv_freq``: fp32 (D / 2,) RoPE frequencies (scaled RoPE), used
+    instead of theta's own: the ``k_qknorm_rope<D, true>`` variant; ``inv_freq_checked`` skips the readback of its
+    entries, as in ``rope_qkv_cache``."""
     _check(qkv, torch.bfloat16, "qkv")
     dev = qkv.device
     _check(pos, torch.int32, "pos", dev)
@@ -283,10 +308,12 @@ def qk_norm_rope_cache(qkv: torch.Tensor, pos: torch.Tensor, k_cache: torch.Tens
     pmin, pmax = pos_range if pos_range is not None else (int(pos.min().item()), int(pos.max().item()))
     if pmin < 0 or pmax >= Smax:
         raise ValueError(f"positions out of cache range [0, {Smax})")
+    if inv_freq is not None:
+        _check_inv_freq(inv_freq, head_dim, dev, values=not inv_freq_checked)
     q = torch.empty(B, n_heads, head_dim, dtype=qkv.dtype, device=dev)
     _ok(lib().p2pt_qk_norm_rope_cache(_p(qkv), _p(pos), _p(slots), _p(q_weight), _p(k_weight), _p(q), _p(k_cache),
                                       _p(v_cache), B, n_heads, n_kv_heads, head_dim, Smax, n_slots, float(eps),
-                                      float(theta), _stream(qkv)), "qk_norm_rope_cache")
+                                      float(theta), _p(inv_freq), _stream(qkv)), "qk_norm_rope_cache")
     return q
 
 
@@ -640,7 +667,9 @@ def skinny_gemm(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
 class FusedLlamaDecoder:
     """Host handle for the fused decode step (decode_fused.hip): 5 kernels per layer + 3
     (6 per layer with ``dims.qk_norm``: the per-head q/k RMSNorm of Qwen3 runs in a kernel of its own;
-    with ``dims.qkv_bias`` the q/k/v bias of Qwen2 is added in the QKV GEMM's epilogue, still 5).
+    with ``dims.qkv_bias`` the q/k/v bias of Qwen2 is added in the QKV GEMM's epilogue, still 5; with
+    ``dims.rope_table`` the kernel that rotates reads its frequencies from ``weights[3]``, an fp32 (D / 2,)
+    table that sits between lm_head and the layers, and the kernel count does not change).
 
     Holds the weight pointer table and a zero-initialised workspace; ``step``
     validates the per-call tensors and launches on the current stream (capturable
@@ -650,28 +679,35 @@ class FusedLlamaDecoder:
     def __init__(self, dims: LlamaDims, weights: list, k_cache: torch.Tensor, v_cache: torch.Tensor):
         self.dims = dims
         dev = k_cache.device
+        if dims.rope_table not in (0, 1):
+            raise ValueError("dims.rope_table must be 0 or 1")
+        g0 = 3 + dims.rope_table  # global entries ahead of the layers
         for i, t in enumerate(weights):
-            _check(t, torch.bfloat16, f"weight[{i}]", dev)
+            if dims.rope_table and i == 3:
+                _check_inv_freq(t, dims.D, dev)
+            else:
+                _check(t, torch.bfloat16, f"weight[{i}]", dev)
         L, Bmax, S, Hkv, D = k_cache.shape
         if (L, Bmax, S, Hkv, D) != (dims.n_layers, dims.max_batch, dims.max_seq, dims.Hkv, dims.D):
             raise ValueError("cache shape does not match dims")
         _check(k_cache, torch.bfloat16, "k_cache", dev)
         _check(v_cache, torch.bfloat16, "v_cache", dev)
         per_layer = 8 if dims.qk_norm else 7 if dims.qkv_bias else 6
-        if len(weights) != 3 + per_layer * dims.n_layers:
-            raise ValueError(f"weight table: embed, final_norm, lm_head, then {per_layer} per layer "
+        if len(weights) != g0 + per_layer * dims.n_layers:
+            raise ValueError(f"weight table: embed, final_norm, lm_head, "
+                             + ("inv_freq, " if dims.rope_table else "") + f"then {per_layer} per layer "
                              "(wqkv, w_gate_up and lm_head with the preceding norm weight folded in"
                              + ("; q_norm and k_norm last)" if dims.qk_norm else
                                 "; bqkv last)" if dims.qkv_bias else ")"))
         if dims.qk_norm:
             for L in range(dims.n_layers):
                 for j in (6, 7):
-                    if weights[3 + 8 * L + j].shape != (dims.D,):
+                    if weights[g0 + 8 * L + j].shape != (dims.D,):
                         raise ValueError(f"layer {L}: q_norm and k_norm must be ({dims.D},)")
         elif dims.qkv_bias:
             n_qkv = (dims.H + 2 * dims.Hkv) * dims.D
             for L in range(dims.n_layers):
-                if weights[3 + 7 * L + 6].shape != (n_qkv,):
+                if weights[g0 + 7 * L + 6].shape != (n_qkv,):
                     raise ValueError(f"layer {L}: bqkv must be ({n_qkv},)")
         nbytes = lib().p2pt_llama_ws_bytes(ctypes.byref(dims))
         if nbytes == 0:

@@ -9,6 +9,7 @@ namespace {
 struct LlamaDims {
   int vocab, dim, n_layers, H, Hkv, D, ffn, max_seq, max_batch;
   float eps, theta;
+  int rope_table;  // RoPE frequencies from an fp32 table [D/2] (llama3 / linear scaling): w[3] points at it
   int qk_norm;  // per-head RMSNorm on q and k before RoPE (Qwen3): a sixth kernel per layer
   int qkv_bias;  // a bias on the q, k and v projections (Qwen2): added in the QKV GEMM's epilogue
 };
@@ -38,6 +39,7 @@ struct StepPlan {
   AttnPlan attn;
   int am_parts;  // per-row winners k_argmax_merge reads
   int qk_norm_grid;  // k_qknorm_rope's gridDim.x (gridDim.y: rows); 0: not launched
+  int qk_norm_table;  // k_qknorm_rope<D, true>: frequencies from the table (a QK-norm model with scaled RoPE)
 };
 
 // One workgroup per tn subtiles of 16 >> kpl columns of one 16-row tile.
@@ -84,11 +86,14 @@ StepPlan plan_step(const LlamaDims& d, int B, int emit_rows) {
   p.emit_rows = emit_rows <= 0 || emit_rows > B ? B : emit_rows;
   // QK-norm models: the GEMM stores the raw projection and k_qknorm_rope finishes it.
   // QKV-bias models: the RoPE epilogue with the bias add. No K parts on QKV (launch() refuses them with a bias).
-  p.qkv = plan_gemm(d.qk_norm ? EPI_STORE : d.qkv_bias ? EPI_ROPE_BIAS : EPI_ROPE, 1, B, (d.H + 2 * d.Hkv) * d.D,
-                    d.dim);
+  // Scaled RoPE (rope_table): the table counterpart of whichever kernel rotates; nothing else moves.
+  const int rope_epi = d.rope_table ? (d.qkv_bias ? EPI_ROPE_BIAS_TAB : EPI_ROPE_TAB)
+                                    : (d.qkv_bias ? EPI_ROPE_BIAS : EPI_ROPE);
+  p.qkv = plan_gemm(d.qk_norm ? EPI_STORE : rope_epi, 1, B, (d.H + 2 * d.Hkv) * d.D, d.dim);
   if (d.qk_norm) {
     const int per_wg = qknorm_heads_per_wg(d.D);
     p.qk_norm_grid = (d.H + 2 * d.Hkv + per_wg - 1) / per_wg;
+    p.qk_norm_table = d.rope_table;
   }
   p.attn = plan_attn(B, d.H, d.Hkv, d.D, d.max_seq);
   p.o = plan_gemm(EPI_RESID, kTnResid, B, d.dim, d.H * d.D, true);
@@ -204,6 +209,13 @@ auto rope_bias(const LlamaDims& d, const int* pos, const int* slot, uint16_t* q,
     a.bias = static_cast<const uint16_t*>(bias);
   };
 }
+template <typename Rope>
+auto with_table(Rope r, const void* inv_freq) {  // ROPE_TAB, ROPE_BIAS_TAB: rope(...) or rope_bias(...) + the table
+  return [=](GemmArgs& a) {
+    r(a);
+    a.inv_freq = static_cast<const float*>(inv_freq);
+  };
+}
 auto resid(uint16_t* r, float* ss_out) {
   return [=](GemmArgs& a) { a.out = r, a.ss_out = ss_out; };
 }
@@ -228,13 +240,34 @@ hipError_t launch_as(const GemmPlan& p, GemmArgs a, hipStream_t s) {
   return hipGetLastError();
 }
 
-// The one (nw, tn, epi, um) dispatch: the 42 k_skinny instantiations.
+// The table epilogues run QKV projections only, so they carry just the (nw, um) pairs plan_gemm can give one
+// (fixed_nw == 0): 4 waves up to 16 k-steps with um 1, 2 or 4, and 8 waves from 17 on, where a wave's share is
+// at least 3 k-steps and um is 4.
+template <int EPI>
+hipError_t launch_qkv_table(const GemmPlan& p, GemmArgs a, hipStream_t s) {
+  a.M = p.M, a.N = p.N, a.K = p.K, a.kpl = p.kpl;
+  const dim3 g(p.grid_x, p.grid_y), b(p.nw * 64);
+  switch (p.nw * 8 + p.um) {
+    case 8 * 8 + 4: hipLaunchKernelGGL((k_skinny<8, 1, EPI, 4>), g, b, 0, s, a); break;
+    case 4 * 8 + 1: hipLaunchKernelGGL((k_skinny<4, 1, EPI, 1>), g, b, 0, s, a); break;
+    case 4 * 8 + 2: hipLaunchKernelGGL((k_skinny<4, 1, EPI, 2>), g, b, 0, s, a); break;
+    case 4 * 8 + 4: hipLaunchKernelGGL((k_skinny<4, 1, EPI, 4>), g, b, 0, s, a); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+// The one (nw, tn, epi, um) dispatch: the 50 k_skinny instantiations (42, and 4 for each table epilogue).
 hipError_t launch(const GemmPlan& p, const GemmArgs& a, hipStream_t s) {
   if (p.kpl < 0 || p.kpl > kMaxKpl || (p.ss_in > 0) != (a.ss_part != nullptr)) return hipErrorInvalidValue;
   if (p.kpl && (p.tn != 1 || (p.M << p.kpl) > 16 || p.K % (32 << p.kpl))) return hipErrorInvalidValue;
   // The bias is added once, after the K-split reduction: never with K parts, never without a bias.
-  if (p.epi == EPI_ROPE_BIAS && (p.kpl != 0 || a.bias == nullptr)) return hipErrorInvalidValue;
+  if (epi_has_bias(p.epi) && (p.kpl != 0 || a.bias == nullptr)) return hipErrorInvalidValue;
+  // A table epilogue reads its table unconditionally: never without one.
+  if (epi_has_table(p.epi) && a.inv_freq == nullptr) return hipErrorInvalidValue;
   switch (p.epi * 4 + p.tn) {
+    case EPI_ROPE_TAB * 4 + 1: return launch_qkv_table<EPI_ROPE_TAB>(p, a, s);
+    case EPI_ROPE_BIAS_TAB * 4 + 1: return launch_qkv_table<EPI_ROPE_BIAS_TAB>(p, a, s);
     case EPI_ROPE * 4 + 1: return launch_as<1, EPI_ROPE>(p, a, s);
     case EPI_ROPE_BIAS * 4 + 1: return launch_as<1, EPI_ROPE_BIAS>(p, a, s);
     case EPI_RESID * 4 + 1: return launch_as<1, EPI_RESID>(p, a, s);
@@ -279,12 +312,16 @@ hipError_t launch_attn(const AttnPlan& p, const void* q, const void* kc, const v
 }
 
 // (row, head group) workgroups of k_qknorm_rope: grid_x groups of qknorm_heads_per_wg(D) heads.
-hipError_t launch_qknorm(int grid_x, int rows, int D, const QkNormArgs& a, hipStream_t s) {
+// table: the k_qknorm_rope<D, true> variant, which reads a.inv_freq (8-byte loads) and is refused without it.
+hipError_t launch_qknorm(int grid_x, int rows, int D, bool table, const QkNormArgs& a, hipStream_t s) {
   if (grid_x <= 0 || rows <= 0 || grid_x * qknorm_heads_per_wg(D) < a.H + 2 * a.Hkv) return hipErrorInvalidValue;
+  if (table && (a.inv_freq == nullptr || reinterpret_cast<uintptr_t>(a.inv_freq) % 8)) return hipErrorInvalidValue;
   const dim3 g(grid_x, rows), b(kQkNormWaves * 64);
-  switch (D) {
-    case 64: hipLaunchKernelGGL(k_qknorm_rope<64>, g, b, 0, s, a); break;
-    case 128: hipLaunchKernelGGL(k_qknorm_rope<128>, g, b, 0, s, a); break;
+  switch (D * 2 + int(table)) {
+    case 64 * 2: hipLaunchKernelGGL((k_qknorm_rope<64, false>), g, b, 0, s, a); break;
+    case 128 * 2: hipLaunchKernelGGL((k_qknorm_rope<128, false>), g, b, 0, s, a); break;
+    case 64 * 2 + 1: hipLaunchKernelGGL((k_qknorm_rope<64, true>), g, b, 0, s, a); break;
+    case 128 * 2 + 1: hipLaunchKernelGGL((k_qknorm_rope<128, true>), g, b, 0, s, a); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
@@ -294,6 +331,7 @@ bool dims_ok(const LlamaDims& d) {
   if (d.D != 64 && d.D != 128) return false;
   if (d.qk_norm != 0 && d.qk_norm != 1) return false;
   if (d.qkv_bias != 0 && d.qkv_bias != 1) return false;
+  if (d.rope_table != 0 && d.rope_table != 1) return false;
   // No family has both, and the EPI_STORE + k_qknorm_rope route would need the bias elsewhere.
   if (d.qkv_bias && d.qk_norm) return false;
   // GEMM operands are addressed with 32-bit byte offsets below kOob (2 GiB):
@@ -366,6 +404,8 @@ int p2pt_max_rows() { return kMaxM; }
 //      With dims.qk_norm each layer has 8 entries, q_norm [D] and k_norm [D] appended, and
 //      wqkv rows stay in plain order (k_qknorm_rope pairs the RoPE partners itself).
 //      With dims.qkv_bias each layer has 7 entries: the six, then bqkv [(H+2Hkv)*D], interleaved like wqkv's rows.
+//      With dims.rope_table a fourth global entry follows lm_head, ahead of the layers: inv_freq, fp32 [D/2],
+//      8-byte aligned, the RoPE frequencies every layer rotates with (theta is then not read).
 //   k_cache/v_cache: [n_layers][max_batch][max_seq][Hkv][D]
 //   tokens int64 [B <= 64], pos int32 [B] (< max_seq), logits bf16 [B][vocab], ids int64 [B]
 //   emit_rows: only rows [0, emit_rows) get logits and ids (the LM head runs on
@@ -386,29 +426,33 @@ int p2pt_llama_decode(const LlamaDims* dp, const void* const* w, void* k_cache, 
   hipError_t e;
   auto failed = [&](hipError_t r) { return (e = r) != hipSuccess; };
 
+  const void* inv_freq = d.rope_table ? w[3] : nullptr;
   hipLaunchKernelGGL(k_embed, dim3(B), dim3(256), 0, s, static_cast<const uint16_t*>(w[0]), tokens, W.resid, W.ss,
                      d.dim, d.vocab);
   if (failed(hipGetLastError())) return int(e);
   for (int L = 0; L < d.n_layers; L++) {
     // attn_norm, wqkv, wo, ffn_norm, w_gate_up, w_down (+ q_norm, k_norm, or + bqkv)
-    const void* const* wl = w + 3 + (d.qk_norm ? 8 : d.qkv_bias ? 7 : 6) * L;
+    const void* const* wl = w + 3 + d.rope_table + (d.qk_norm ? 8 : d.qkv_bias ? 7 : 6) * L;
     uint16_t* kc = static_cast<uint16_t*>(k_cache) + L * layer_cache;
     uint16_t* vc = static_cast<uint16_t*>(v_cache) + L * layer_cache;
     const GemmPlan& qkv = L ? P.qkv : P.qkv_first;
-    const GemmArgs to_qkv = d.qk_norm
-                                ? gemm(W.resid, wl[1]) + norm(W.ss, qkv.ss_in, d.eps) + store(W.qkv)
-                            : d.qkv_bias
-                                ? gemm(W.resid, wl[1]) + norm(W.ss, qkv.ss_in, d.eps) +
-                                      rope_bias(d, pos, slots, W.q, kc, vc, wl[6])
-                                : gemm(W.resid, wl[1]) + norm(W.ss, qkv.ss_in, d.eps) + rope(d, pos, slots, W.q, kc, vc);
+    const GemmArgs qkv_in = gemm(W.resid, wl[1]) + norm(W.ss, qkv.ss_in, d.eps);
+    const GemmArgs to_qkv =
+        d.qk_norm ? qkv_in + store(W.qkv)
+        : d.qkv_bias
+            ? (d.rope_table ? qkv_in + with_table(rope_bias(d, pos, slots, W.q, kc, vc, wl[6]), inv_freq)
+                            : qkv_in + rope_bias(d, pos, slots, W.q, kc, vc, wl[6]))
+            : (d.rope_table ? qkv_in + with_table(rope(d, pos, slots, W.q, kc, vc), inv_freq)
+                            : qkv_in + rope(d, pos, slots, W.q, kc, vc));
     const GemmArgs to_o = gemm(W.attn, wl[2]) + resid(W.resid, W.ss);
     const GemmArgs to_gate_up = gemm(W.resid, wl[4]) + norm(W.ss, P.gate_up.ss_in, d.eps) + store(W.h);
     const GemmArgs to_down = gemm(W.h, wl[5]) + resid(W.resid, W.ss);
     if (failed(launch(qkv, to_qkv, s))) return int(e);
     if (P.qk_norm_grid) {
       const QkNormArgs qn{W.qkv, static_cast<const uint16_t*>(wl[6]), static_cast<const uint16_t*>(wl[7]), pos, slots,
-                          d.max_batch, W.q, kc, vc, d.H, d.Hkv, d.max_seq, d.eps, log2f(d.theta)};
-      if (failed(launch_qknorm(P.qk_norm_grid, B, d.D, qn, s))) return int(e);
+                          d.max_batch, W.q, kc, vc, d.H, d.Hkv, d.max_seq, d.eps, log2f(d.theta),
+                          static_cast<const float*>(inv_freq)};
+      if (failed(launch_qknorm(P.qk_norm_grid, B, d.D, P.qk_norm_table != 0, qn, s))) return int(e);
     }
     if (failed(launch_attn(P.attn, W.q, kc, vc, pos, slots, d.max_batch, W.part_o, W.part_ml, W.counters, W.attn, d.H,
                            d.Hkv, d.max_seq, s)))
@@ -433,18 +477,21 @@ int p2pt_skinny_gemm(const void* x, const void* w, void* out, int M, int N, int 
 
 // Standalone per-head RMSNorm + RoPE + cache append (tests): the kernel the fused step of a QK-norm model
 // runs, on caller tensors. qkv [B <= 64][(H + 2 Hkv) * D], q_weight / k_weight [D], q [B][H][D], caches
-// [nslots][Smax][Hkv][D]; row b goes to slot slots[b] (nullptr: slot b, B <= nslots) at pos[b].
+// [nslots][Smax][Hkv][D]; row b goes to slot slots[b] (nullptr: slot b, B <= nslots) at pos[b]. inv_freq: fp32
+// [D / 2], 8-byte aligned, for the table variant (theta is then not read), or nullptr for theta's own frequencies.
 int p2pt_qk_norm_rope_cache(const void* qkv, const int* pos, const int* slots, const void* q_weight,
                             const void* k_weight, void* q, void* k_cache, void* v_cache, int B, int H, int Hkv, int D,
-                            int Smax, int nslots, float eps, float theta, void* stream) {
+                            int Smax, int nslots, float eps, float theta, const float* inv_freq, void* stream) {
   if (!rows_ok(B) || (D != 64 && D != 128) || H <= 0 || Hkv <= 0 || Smax <= 0 || nslots <= 0)
     return int(hipErrorInvalidValue);
   if ((!slots && B > nslots) || !(theta > 0.f)) return int(hipErrorInvalidValue);
   const QkNormArgs a{static_cast<const uint16_t*>(qkv), static_cast<const uint16_t*>(q_weight),
                      static_cast<const uint16_t*>(k_weight), pos, slots, nslots, static_cast<uint16_t*>(q),
-                     static_cast<uint16_t*>(k_cache), static_cast<uint16_t*>(v_cache), H, Hkv, Smax, eps, log2f(theta)};
+                     static_cast<uint16_t*>(k_cache), static_cast<uint16_t*>(v_cache), H, Hkv, Smax, eps, log2f(theta),
+                     inv_freq};
   const int per_wg = qknorm_heads_per_wg(D);
-  return int(launch_qknorm((H + 2 * Hkv + per_wg - 1) / per_wg, B, D, a, static_cast<hipStream_t>(stream)));
+  return int(launch_qknorm((H + 2 * Hkv + per_wg - 1) / per_wg, B, D, inv_freq != nullptr, a,
+                           static_cast<hipStream_t>(stream)));
 }
 
 // Microbenchmark hook (scripts/bench_skinny.py --attn): `reps` back-to-back

@@ -11,6 +11,8 @@
 //     k_skinny<ROPE>     RMSNorm (attn_norm) -> QKV GEMM -> RoPE on q/k,
 //                        q to the attention buffer, k/v appended to the cache
 //     (QKV-bias models:  k_skinny<ROPE_BIAS>, the same with a bias on q, k and v)
+//     (scaled RoPE:      k_skinny<ROPE_TAB> / <ROPE_BIAS_TAB>, the same with the frequencies
+//                        read from an fp32 table [D/2] instead of computed inline)
 //     (QK-norm models:   k_skinny<STORE> writes the raw projection instead, and
 //      k_qknorm_rope     norms every q and k head, rotates and appends: a sixth kernel)
 //     k_attn            GQA flash-decoding split-K; the last split to finish
@@ -63,7 +65,18 @@ typedef float frag4 __attribute__((ext_vector_type(4)));
 
 // EPI_ROPE_BIAS: EPI_ROPE with a per-column bias on q, k and v (Qwen2). A variant of its own, so that
 // models without a bias keep the EPI_ROPE kernels as they are, with no run-time test of a pointer.
-enum Epi : int { EPI_STORE = 0, EPI_ROPE = 1, EPI_SILU = 2, EPI_RESID = 3, EPI_ARGMAX = 4, EPI_ROPE_BIAS = 5 };
+// EPI_ROPE_TAB, EPI_ROPE_BIAS_TAB: EPI_ROPE and EPI_ROPE_BIAS with inv_freq[i] read from a table in device
+// memory (llama3 / linear RoPE scaling: the host computes the table once per model). Variants of their own for
+// the same reason: models with default RoPE keep the inline exp2f and launch exactly what they did.
+enum Epi : int {
+  EPI_STORE = 0, EPI_ROPE = 1, EPI_SILU = 2, EPI_RESID = 3, EPI_ARGMAX = 4, EPI_ROPE_BIAS = 5, EPI_ROPE_TAB = 6,
+  EPI_ROPE_BIAS_TAB = 7
+};
+constexpr bool epi_is_rope(int epi) {
+  return epi == EPI_ROPE || epi == EPI_ROPE_BIAS || epi == EPI_ROPE_TAB || epi == EPI_ROPE_BIAS_TAB;
+}
+constexpr bool epi_has_bias(int epi) { return epi == EPI_ROPE_BIAS || epi == EPI_ROPE_BIAS_TAB; }
+constexpr bool epi_has_table(int epi) { return epi == EPI_ROPE_TAB || epi == EPI_ROPE_BIAS_TAB; }
 
 struct GemmArgs {
   const uint16_t* x;  // A [M][K]
@@ -84,7 +97,8 @@ struct GemmArgs {
   uint16_t* q_out;
   uint16_t* kc;
   uint16_t* vc;
-  const uint16_t* bias;  // ROPE_BIAS: [N], in the row order of W (interleaved like its rows)
+  const uint16_t* bias;  // ROPE_BIAS(_TAB): [N], in the row order of W (interleaved like its rows)
+  const float* inv_freq;  // ROPE_TAB, ROPE_BIAS_TAB: [D / 2] RoPE frequencies (the others compute them from log2_theta)
   int H, Hkv, D, Smax;
   float log2_theta;
   float* am_val;  // ARGMAX: [gridDim.x][16]
@@ -274,8 +288,20 @@ __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
   // ROPE_BIAS: this lane's column bias, loaded by wave 0 ahead of the weight
   // stream like rprev. The host keeps kpl == 0 here, so the column is < N.
   float bias = 0.f;
-  if constexpr (EPI == EPI_ROPE_BIAS) {
+  if constexpr (epi_has_bias(EPI)) {
     if (wv == 0) bias = bf2f(a.bias[tile_col<TN>(bx, 0, c, cwl)]);
+  }
+
+  // ROPE_TAB: this lane's RoPE frequency, inv_freq[i] of its column's pair i = (col % D) / 2, loaded ahead of
+  // the weight stream for the same reason: after it, a 4-byte load, cache hit or not, would sit between the
+  // last MFMA and the sincosf. The index is < D / 2, the table's length, for any column whatever. plan_step
+  // gives QKV no K parts (k_parts = false), so these epilogues are planned and tested at kpl == 0 only.
+  // Measured on MI355X and rejected: col & (D - 1) for col % D (D is 64 or 128). Without the integer division
+  // the QKV kernel was slower, not faster: 6.32 us per launch against 6.22 with the division and 6.10 for
+  // EPI_ROPE (Llama-3.2-1B's shape, batch 1, kernel trace); the step +4.1 us against +1.4 us.
+  float tab_freq = 0.f;
+  if constexpr (epi_has_table(EPI)) {
+    if (wv == 0) tab_freq = a.inv_freq[(tile_col<TN>(bx, 0, c, cwl) % a.D) >> 1];
   }
 
   frag4 acc[TN];
@@ -385,19 +411,22 @@ __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
       if ((c & 1) || !col_ok || mrow0 + r >= a.M) continue;
       a.out[size_t(mrow0 + r) * (a.N >> 1) + (n >> 1)] = uint16_t(f2bf_bits(mine / (1.f + __expf(-mine)) * other));
     }
-  } else if constexpr (EPI == EPI_ROPE || EPI == EPI_ROPE_BIAS) {
+  } else if constexpr (epi_is_rope(EPI)) {
     // Interleaved rows within each head: column 2i = dim i, 2i+1 = dim i + D/2.
     // ROPE_BIAS adds the column's bias in fp32 after the 1/rms scale and before
-    // the one rounding ahead of the rotation: q, k and v alike.
+    // the one rounding ahead of the rotation: q, k and v alike. The _TAB variants take the frequency from the
+    // table (loaded above) and are otherwise this code.
     const int half = a.D >> 1;
     const int col = tile_col<TN>(bx, 0, c, cwl);
     const int head = col / a.D, i = (col % a.D) >> 1;
     const bool second = c & 1;
-    const float inv_freq = exp2f(-a.log2_theta * (2.f * i) / a.D);
+    float inv_freq;
+    if constexpr (epi_has_table(EPI)) inv_freq = tab_freq;
+    else inv_freq = exp2f(-a.log2_theta * (2.f * i) / a.D);
 #pragma unroll
     for (int r = 0; r < 4; r++) {
       const int m = mrow0 + r;
-      const float mine = bf_round(EPI == EPI_ROPE_BIAS ? v[0][r] + bias : v[0][r]);
+      const float mine = bf_round(epi_has_bias(EPI) ? v[0][r] + bias : v[0][r]);
       const float other = dpp<kDppXor1>(mine);
       if (m >= a.M || !col_ok) continue;
       // Host validates; clamped anyway so a bad index can never write outside the cache.
@@ -528,6 +557,7 @@ struct QkNormArgs {
   uint16_t* vc;
   int H, Hkv, Smax;
   float eps, log2_theta;
+  const float* inv_freq;  // k_qknorm_rope<D, true>: [D / 2] RoPE frequencies, 8-byte aligned
 };
 
 constexpr int kQkNormWaves = 4;  // waves per workgroup of k_qknorm_rope
@@ -535,7 +565,9 @@ constexpr int kQkNormWaves = 4;  // waves per workgroup of k_qknorm_rope
 // Heads one workgroup of k_qknorm_rope covers.
 __host__ __device__ __forceinline__ int qknorm_heads_per_wg(int D) { return kQkNormWaves * kWave / (D / 4); }
 
-template <int D>
+// TAB: the frequencies of dims 2j and 2j + 1 come from a.inv_freq as one 8-byte load (scaled RoPE) instead
+// of exp2f; 2j + 1 < D / 2 for every lane.
+template <int D, bool TAB = false>
 __global__ __launch_bounds__(kQkNormWaves * 64) void k_qknorm_rope(QkNormArgs a) {
   constexpr int LPH = D / 4, half = D / 2;  // lanes per head
   const int lane = threadIdx.x & 63;
@@ -553,6 +585,8 @@ __global__ __launch_bounds__(kQkNormWaves * 64) void k_qknorm_rope(QkNormArgs a)
   const uint16_t* g = (is_q ? a.gq : a.gk) + 2 * j;
   const uint32_t glo = *reinterpret_cast<const uint32_t*>(g);
   const uint32_t ghi = *reinterpret_cast<const uint32_t*>(g + half);
+  float2 tab_freq = make_float2(0.f, 0.f);
+  if constexpr (TAB) tab_freq = *reinterpret_cast<const float2*>(a.inv_freq + 2 * j);
   // Host validates; clamped anyway so a bad index can never write outside the cache.
   const int p = min(max(a.pos[m], 0), a.Smax - 1);
   const int sl = a.slot ? min(max(a.slot[m], 0), a.nslots - 1) : m;
@@ -571,7 +605,9 @@ __global__ __launch_bounds__(kQkNormWaves * 64) void k_qknorm_rope(QkNormArgs a)
 #pragma unroll
     for (int e = 0; e < 2; e++) {
       const int i = 2 * j + e;
-      const float inv_freq = exp2f(-a.log2_theta * (2.f * i) / D);
+      float inv_freq;
+      if constexpr (TAB) inv_freq = e ? tab_freq.y : tab_freq.x;
+      else inv_freq = exp2f(-a.log2_theta * (2.f * i) / D);
       float sn, cs;
       sincosf(float(p) * inv_freq, &sn, &cs);
       const float n1 = x1[e] * rs * g1[e], n2 = x2[e] * rs * g2[e];

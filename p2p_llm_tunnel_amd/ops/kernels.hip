@@ -87,11 +87,13 @@ __global__ __launch_bounds__(256) void k_silu_mul(const uint4* __restrict__ in, 
 
 // ------------------------------------------------------------ RoPE + KV append
 // qkv: [B, (H + 2*Hkv) * D]; q_out: [B, H, D]; caches: [B, Smax, Hkv, D].
-// NeoX rotate-half convention, inv_freq_i = theta^(-2i/D).
+// NeoX rotate-half convention, inv_freq_i = theta^(-2i/D), or (TAB) inv_freq[i] from an fp32 table [D/2]
+// in device memory: scaled RoPE (llama3, linear), whose frequencies the host computes once per model.
+template <bool TAB>
 __global__ __launch_bounds__(256) void k_rope_qkv_cache(const uint16_t* __restrict__ qkv, const int* __restrict__ pos,
                                                         uint16_t* __restrict__ q_out, uint16_t* __restrict__ kc,
                                                         uint16_t* __restrict__ vc, int H, int Hkv, int D, int Smax,
-                                                        float log2_theta) {
+                                                        float log2_theta, const float* __restrict__ inv_freq_tab) {
   const int b = blockIdx.x;
   const int p = pos[b];
   const int half = D / 2;
@@ -100,7 +102,9 @@ __global__ __launch_bounds__(256) void k_rope_qkv_cache(const uint16_t* __restri
   const int pairs = (H + Hkv) * half;
   for (int j = threadIdx.x; j < pairs; j += blockDim.x) {
     int head = j / half, i = j % half;
-    float inv_freq = exp2f(-log2_theta * (2.f * i) / D);
+    float inv_freq;
+    if constexpr (TAB) inv_freq = inv_freq_tab[i];  // i < D / 2, the table's length
+    else inv_freq = exp2f(-log2_theta * (2.f * i) / D);
     float s, c;
     sincosf(float(p) * inv_freq, &s, &c);
     const uint16_t* x = src + head * D;
@@ -345,12 +349,16 @@ int p2pt_silu_mul(const void* in, void* out, int rows, int F, void* stream) {
 }
 
 int p2pt_rope_qkv_cache(const void* qkv, const int* pos, void* q_out, void* kc, void* vc, int B, int H, int Hkv, int D,
-                        int Smax, float theta, void* stream) {
+                        int Smax, float theta, const float* inv_freq, void* stream) {
   if (D % 2 || B <= 0 || H % Hkv) return int(hipErrorInvalidValue);
-  hipLaunchKernelGGL(k_rope_qkv_cache, dim3(B), dim3(256), 0, static_cast<hipStream_t>(stream),
-                     static_cast<const uint16_t*>(qkv), pos, static_cast<uint16_t*>(q_out), static_cast<uint16_t*>(kc),
-                     static_cast<uint16_t*>(vc), H, Hkv, D, Smax, log2f(theta));
-  return int(hipGetLastError());
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(B), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const uint16_t*>(qkv), pos, static_cast<uint16_t*>(q_out),
+                       static_cast<uint16_t*>(kc), static_cast<uint16_t*>(vc), H, Hkv, D, Smax, log2f(theta), inv_freq);
+    return int(hipGetLastError());
+  };
+  // inv_freq: fp32 [D / 2] for the table variant (theta is then not read), or nullptr.
+  return inv_freq ? go(k_rope_qkv_cache<true>) : go(k_rope_qkv_cache<false>);
 }
 
 // Workspace: part_o [B*H*nsplit*D] f32 followed by part_ml [B*H*nsplit*2] f32.

@@ -4,6 +4,10 @@
 tests at full size without downloading anything.
 
     python scripts/make_synthetic_checkpoint.py --shape tinyllama-1.1b --out /tmp/tl11 [--shards 2]
+    python scripts/make_synthetic_checkpoint.py --shape llama-1b --llama3-rope 32 --out /tmp/l32
+
+--llama3-rope FACTOR writes the ``rope_scaling`` block of Llama 3.1 / 3.2 (type llama3, low_freq_factor 1,
+high_freq_factor 4, original_max_position_embeddings 8192; 3.1 uses factor 8, 3.2 factor 32).
 
 Weights are N(0, 0.02) bf16 (norms ~1), named and shaped as transformers'
 LlamaForCausalLM saves them; there is no tokenizer (the endpoint then falls
@@ -65,9 +69,16 @@ def main():
     ap.add_argument("--out", required=True)
     ap.add_argument("--shards", type=int, default=2)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--llama3-rope", type=float, default=None, metavar="FACTOR",
+                    help="write a llama3 rope_scaling block with this factor (Llama 3.1: 8, Llama 3.2: 32)")
+    ap.add_argument("--original-max-seq", type=int, default=8192,
+                    help="original_max_position_embeddings of the --llama3-rope block")
     a = ap.parse_args()
     cfg = dict(SHAPES[a.shape], architectures=["LlamaForCausalLM"], model_type="llama", hidden_act="silu",
                torch_dtype="bfloat16", bos_token_id=1, eos_token_id=2)
+    if a.llama3_rope is not None:
+        cfg["rope_scaling"] = {"rope_type": "llama3", "factor": a.llama3_rope, "low_freq_factor": 1.0,
+                               "high_freq_factor": 4.0, "original_max_position_embeddings": a.original_max_seq}
     os.makedirs(a.out, exist_ok=True)
     with open(os.path.join(a.out, "config.json"), "w") as fh:
         json.dump(cfg, fh, indent=1)

@@ -21,6 +21,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch  # noqa: E402
 
+from p2p_llm_tunnel_amd.models.rope import RopeScaling  # noqa: E402
 from p2p_llm_tunnel_amd.models.tiny_llm import CONFIGS, LlamaConfig, TinyLlama, capture  # noqa: E402
 
 
@@ -39,7 +40,9 @@ def main():
                     help="an explicit LlamaConfig as a JSON object of its fields, instead of --config, e.g. a "
                          "Qwen3-0.6B-shaped model: '{\"vocab\": 151936, \"dim\": 1024, \"n_layers\": 28, "
                          "\"n_heads\": 16, \"n_kv_heads\": 8, \"head_dim\": 128, \"ffn\": 3072, \"max_seq\": 2048, "
-                         "\"eps\": 1e-6, \"rope_theta\": 1e6, \"qk_norm\": true}'")
+                         "\"eps\": 1e-6, \"rope_theta\": 1e6, \"qk_norm\": true}'. \"rope_scaling\" takes an "
+                         "object of RopeScaling's fields, e.g. {\"kind\": \"llama3\", \"factor\": 32, "
+                         "\"low_freq_factor\": 1, \"high_freq_factor\": 4, \"original_max_seq\": 8192}")
     ap.add_argument("--name", default=None, help="label of a --cfg model in the result line")
     ap.add_argument("--checkpoint", default=None, help="load this HF Llama checkpoint instead of a random --config")
     ap.add_argument("--loop", action="store_true",
@@ -52,7 +55,10 @@ def main():
         a.config = os.path.basename(os.path.normpath(a.checkpoint))
     else:
         if a.cfg:
-            cfg = LlamaConfig(**json.loads(a.cfg))
+            fields = json.loads(a.cfg)
+            if fields.get("rope_scaling") is not None:
+                fields["rope_scaling"] = RopeScaling(**fields["rope_scaling"])
+            cfg = LlamaConfig(**fields)
             a.config = a.name or "custom"
         else:
             cfg = CONFIGS[a.config]
