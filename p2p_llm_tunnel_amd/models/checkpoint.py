@@ -162,8 +162,10 @@ class _Reader:
 
 
 def load_llama(path: str, device="cuda", max_batch: int = 8, max_seq: int | None = None,
-               fused: bool = True, prefix: str = "model.") -> TinyLlama:
-    """A TinyLlama with the checkpoint's weights (bf16 on ``device``)."""
+               fused: bool = True, prefix: str = "model.", kv_dtype: str = "bf16") -> TinyLlama:
+    """A TinyLlama with the checkpoint's weights (bf16 on ``device``). ``kv_dtype``: "bf16" or "fp8", the KV
+    cache's format (``TinyLlama``), for every family alike; ``k_scale`` / ``v_scale`` tensors a checkpoint may
+    carry are not read (the FP8 cache's scale is 1)."""
     cfg, raw = read_config(path, max_seq)
     c = cfg
     rd = _Reader(path)
@@ -224,7 +226,7 @@ def load_llama(path: str, device="cuda", max_batch: int = 8, max_seq: int | None
             del q, k, v, gate, up
     finally:
         rd.close()
-    return TinyLlama.from_weights(cfg, w, device=dev, max_batch=max_batch, fused=fused)
+    return TinyLlama.from_weights(cfg, w, device=dev, max_batch=max_batch, fused=fused, kv_dtype=kv_dtype)
 
 
 class Detokenizer:

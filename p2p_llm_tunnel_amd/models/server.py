@@ -625,10 +625,13 @@ class Engine:
     """
 
     def __init__(self, device="cuda:0", config="tiny", max_batch=8, seed=0, use_graph=True, rows=64, model=None,
-                 small_rows=16, prefix_cache=False, prefix_min=16, penalties=False):
+                 small_rows=16, prefix_cache=False, prefix_min=16, penalties=False, kv_dtype="bf16"):
         if model is None:
             from p2p_llm_tunnel_amd.models.tiny_llm import TinyLlama
-            model = TinyLlama(config, device=device, max_batch=max_batch, seed=seed, fused=True)
+            model = TinyLlama(config, device=device, max_batch=max_batch, seed=seed, fused=True, kv_dtype=kv_dtype)
+        elif kv_dtype != "bf16" and getattr(model, "kv_dtype", "bf16") != kv_dtype:
+            raise ValueError(f"kv_dtype={kv_dtype!r}, but the injected model was built with "
+                             f"{getattr(model, 'kv_dtype', 'bf16')!r} caches")
         if prefix_cache and not callable(getattr(model, "kv_copy", None)):
             raise ValueError("prefix_cache needs a model with kv_copy(jobs) (slot-to-slot K/V row copy)")
         # hipGraphs need a model with the capturable step on a HIP device (a
@@ -653,6 +656,9 @@ class Engine:
         lp_dev = self.device if use_graph else None
         if penalties and not use_graph:
             raise ValueError("penalties need the graph-captured HIP step; this engine runs eagerly")
+        # An FP8 cache is read and written by the fused HIP step alone: refused on the eager engine, like sampling.
+        if getattr(model, "kv_dtype", "bf16") != "bf16" and not use_graph:
+            raise ValueError("an fp8 KV cache needs the graph-captured HIP step; this engine runs eagerly")
         self.penalties = bool(penalties)
         in_rows = _PEN.stop if self.penalties else _IN_ROWS
         self._bufs = {R: [_StepBuf(R, cuda, lp_dev, in_rows), _StepBuf(R, cuda, lp_dev, in_rows)] for R in sizes}
@@ -1606,7 +1612,7 @@ class FrontEnd:
 def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_batch=8, model_name=None,
                  engine: Engine | None = None, checkpoint: str | None = None, max_seq: int | None = None,
                  tokenizer=None, default_temperature: float = 0.0, prefix_cache: bool = False, prefix_min: int = 16,
-                 embed_pooling: str = "mean", penalties: bool = False):
+                 embed_pooling: str = "mean", penalties: bool = False, kv_dtype: str = "bf16"):
     """Engine + HTTP front-end; returns (server, port, engine). ``server.shutdown()``
     stops the HTTP side, ``engine.stop()`` the GPU side. ``checkpoint``: serve a
     Hugging Face Llama checkpoint directory (weights + tokenizer) instead of
@@ -1618,7 +1624,14 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
     ("mean" over all positions, or the "last" position's). ``penalties``: the
     engine's on-device penalties and logit_bias (``Engine``); the endpoint then
     takes the parameters ``penalty_params`` describes instead of answering 400,
-    and an injected ``engine`` must have been built with them too."""
+    and an injected ``engine`` must have been built with them too. ``kv_dtype``:
+    "bf16" or "fp8", the KV cache's format (``TinyLlama``; docs/KV_FP8.md): fp8 halves
+    its bytes, needs the graph-captured HIP step (refused on an eager engine) and must
+    not contradict an injected ``engine``'s model."""
+    kv_dtype = parse_kv_dtype(kv_dtype)
+    if engine is not None and getattr(engine.model, "kv_dtype", "bf16") != kv_dtype:
+        raise ValueError(f"kv_dtype={kv_dtype!r}, but the injected engine's model has "
+                         f"{getattr(engine.model, 'kv_dtype', 'bf16')!r} caches")
     if engine is not None and prefix_cache and not engine.prefix_cache:
         raise ValueError("prefix_cache=True, but the injected engine was built without it")
     if engine is not None and penalties and not getattr(engine, "penalties", False):
@@ -1628,16 +1641,53 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
     if checkpoint and engine is None:
         import os
         from p2p_llm_tunnel_amd.models.checkpoint import Tokenizer, load_llama
-        model = load_llama(checkpoint, device=device, max_batch=max_batch, max_seq=max_seq)
+        model = load_llama(checkpoint, device=device, max_batch=max_batch, max_seq=max_seq, kv_dtype=kv_dtype)
         tok = tok or Tokenizer.for_checkpoint(checkpoint)
         engine = Engine(device=device, max_batch=max_batch, model=model, prefix_cache=prefix_cache,
                         prefix_min=prefix_min, penalties=penalties)
         model_name = model_name or os.path.basename(os.path.normpath(checkpoint))
     engine = engine or Engine(device=device, config=config, max_batch=max_batch, prefix_cache=prefix_cache,
-                              prefix_min=prefix_min, penalties=penalties)
+                              prefix_min=prefix_min, penalties=penalties, kv_dtype=kv_dtype)
     srv = FrontEnd(engine, host, port, model_name or f"p2pt-{config}", tokenizer=tok,
                    default_temperature=default_temperature, embed_pooling=embed_pooling)
     return srv, srv.server_address[1], engine
+
+
+KV_DTYPE_CHOICES = ("bf16", "fp8")
+
+
+def parse_kv_dtype(v) -> str:
+    """--kv-dtype / ``start_server(kv_dtype=)``: "bf16" (the default) or "fp8"; anything else is refused."""
+    if v not in KV_DTYPE_CHOICES:
+        raise ValueError(f"kv_dtype must be one of {list(KV_DTYPE_CHOICES)}, got {v!r}")
+    return v
+
+
+def kv_cache_line(model, kv_dtype: str) -> str:
+    """The start-up log line with the KV cache's size."""
+    k, v = getattr(model, "k_cache", None), getattr(model, "v_cache", None)
+    nbytes = sum(t.numel() * t.element_size() for t in (k, v) if t is not None)
+    shape = "x".join(str(n) for n in k.shape) if k is not None else "?"
+    return f"kv cache: {nbytes} bytes ({kv_dtype}, K and V of {shape})"
+
+
+def replica_cmd(a, i: int) -> list[str]:
+    """The command line of replica ``i`` of ``--gpus``: this process's own switches, on device ``cuda:i`` and port
+    ``a.port + i``."""
+    cmd = [sys.executable, "-m", "p2p_llm_tunnel_amd.models.server", "--host", a.host, "--port", str(a.port + i),
+           "--device", f"cuda:{i}", "--config", a.config, "--max-batch", str(a.max_batch)]
+    if a.checkpoint:
+        cmd += ["--checkpoint", a.checkpoint] + (["--max-seq", str(a.max_seq)] if a.max_seq else [])
+    cmd += ["--default-temperature", str(a.default_temperature)]
+    if a.prefix_cache:
+        cmd += ["--prefix-cache", "--prefix-min", str(a.prefix_min)]
+    if getattr(a, "embed_pooling", "mean") != "mean":
+        cmd += ["--embed-pooling", a.embed_pooling]
+    if getattr(a, "penalties", False):
+        cmd += ["--penalties"]
+    if getattr(a, "kv_dtype", "bf16") != "bf16":
+        cmd += ["--kv-dtype", a.kv_dtype]
+    return cmd
 
 
 def _replicas(a) -> int:
@@ -1651,18 +1701,7 @@ def _replicas(a) -> int:
     base = a.port
     procs = []
     for i in range(a.gpus):
-        cmd = [sys.executable, "-m", "p2p_llm_tunnel_amd.models.server", "--host", a.host, "--port", str(base + i),
-               "--device", f"cuda:{i}", "--config", a.config, "--max-batch", str(a.max_batch)]
-        if a.checkpoint:
-            cmd += ["--checkpoint", a.checkpoint] + (["--max-seq", str(a.max_seq)] if a.max_seq else [])
-        cmd += ["--default-temperature", str(a.default_temperature)]
-        if a.prefix_cache:
-            cmd += ["--prefix-cache", "--prefix-min", str(a.prefix_min)]
-        if getattr(a, "embed_pooling", "mean") != "mean":
-            cmd += ["--embed-pooling", a.embed_pooling]
-        if getattr(a, "penalties", False):
-            cmd += ["--penalties"]
-        procs.append(subprocess.Popen(cmd))
+        procs.append(subprocess.Popen(replica_cmd(a, i)))
     ups = ",".join(f"http://{a.host}:{base + i}" for i in range(a.gpus))
     print(f"{a.gpus} inference endpoints; use: tunnel serve --upstream {ups}", flush=True)
     try:
@@ -1681,7 +1720,7 @@ def _replicas(a) -> int:
         return 0
 
 
-def main(argv=None):
+def arg_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="GPU-backed OpenAI/Ollama-compatible endpoint")
     ap.add_argument("--host", default="127.0.0.1")
     ap.add_argument("--port", type=int, default=11434)
@@ -1711,13 +1750,22 @@ def main(argv=None):
                          "of the sampler instead of answering 400; the repeat penalty covers the whole prompt and "
                          "everything generated (repeat_last_n: only -1, or 0 = off). Costs a [max_batch + 1, vocab] "
                          "int32 count table and four more captured graphs")
-    a = ap.parse_args(argv)
+    ap.add_argument("--kv-dtype", choices=KV_DTYPE_CHOICES, default="bf16",
+                    help="format of the KV cache: bf16, or fp8 (OCP e4m3, scale 1, no calibration): half the bytes "
+                         "per cached token, so the same memory holds twice the context or slots; values beyond "
+                         "+-448 saturate (docs/KV_FP8.md)")
+    return ap
+
+
+def main(argv=None):
+    a = arg_parser().parse_args(argv)
     if a.gpus > 0:
         raise SystemExit(_replicas(a))
     srv, port, engine = start_server(a.host, a.port, a.device, a.config, a.max_batch, checkpoint=a.checkpoint,
                                      max_seq=a.max_seq, default_temperature=a.default_temperature,
                                      prefix_cache=a.prefix_cache, prefix_min=a.prefix_min,
-                                     embed_pooling=a.embed_pooling, penalties=a.penalties)
+                                     embed_pooling=a.embed_pooling, penalties=a.penalties, kv_dtype=a.kv_dtype)
+    print(kv_cache_line(engine.model, a.kv_dtype), flush=True)
     print(f"inference endpoint on http://{a.host}:{port} ({a.checkpoint or a.config}, {a.device})", flush=True)
     try:
         threading.Event().wait()

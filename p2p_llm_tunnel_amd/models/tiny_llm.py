@@ -57,6 +57,16 @@ CONFIGS = {
 }
 
 
+KV_DTYPES = {"bf16": torch.bfloat16, "fp8": torch.float8_e4m3fn}  # TinyLlama(kv_dtype=): the caches' dtype
+
+
+def e4m3_round(x: torch.Tensor) -> torch.Tensor:
+    """x (fp32) as the FP8 KV cache holds it (OCP e4m3fn, scale 1), back in fp32: finite values clamped to +-448,
+    then one rounding to nearest-even (torch's own cast, which does that for |x| <= 448 and would give NaN above
+    464: hence the clamp first). NaN stays NaN. ``utils/kv_fp8_ref.py`` is the same rule in NumPy integers."""
+    return x.float().clamp(-448.0, 448.0).to(torch.float8_e4m3fn).float()
+
+
 def capture(fn, device, warmup: int = 2):
     """``fn()`` as a hipGraph (torch.cuda.CUDAGraph): ``warmup`` calls on a side
     stream keep allocator and GEMM-heuristics warm-up outside the capture.
@@ -75,14 +85,20 @@ def capture(fn, device, warmup: int = 2):
 
 class TinyLlama:
     def __init__(self, cfg: LlamaConfig | str = "tiny", device="cuda", max_batch: int = 8, seed: int = 0,
-                 fused: bool = True, weights: dict | None = None):
-        """Random-init weights from ``seed``, or ``weights`` (embed, final_norm,
+                 fused: bool = True, weights: dict | None = None, kv_dtype: str = "bf16"):
+        """``kv_dtype``: "bf16" (default) or "fp8": the K/V caches as ``torch.float8_e4m3fn`` (OCP e4m3, scale 1,
+        half the bytes; docs/KV_FP8.md), which only the fused step reads and writes.
+
+        Random-init weights from ``seed``, or ``weights`` (embed, final_norm,
         lm_head, layers[{attn_norm, wqkv, wo, ffn_norm, w_gate_up, w_down}, plus
         q_norm, k_norm when ``cfg.qk_norm``, or bqkv in plain q | k | v order when
         ``cfg.qkv_bias``], bf16 on ``device``) — see ``checkpoint.load_llama``."""
         self.cfg = CONFIGS[cfg] if isinstance(cfg, str) else cfg
         if self.cfg.qkv_bias and self.cfg.qk_norm:
             raise ValueError("qkv_bias with qk_norm: no supported family has both, and the fused step refuses it")
+        if kv_dtype not in KV_DTYPES:
+            raise ValueError(f"kv_dtype must be one of {sorted(KV_DTYPES)}, got {kv_dtype!r}")
+        self.kv_dtype = kv_dtype
         self.fused = fused
         self._fused = None
         self._graphs = {}  # rows -> (graph, tokens, pos, slots, ids, logits)
@@ -136,21 +152,32 @@ class TinyLlama:
         self._alloc_caches()
 
     @classmethod
-    def from_weights(cls, cfg: LlamaConfig, weights: dict, device="cuda", max_batch: int = 8, fused: bool = True):
-        return cls(cfg, device=device, max_batch=max_batch, fused=fused, weights=weights)
+    def from_weights(cls, cfg: LlamaConfig, weights: dict, device="cuda", max_batch: int = 8, fused: bool = True,
+                     kv_dtype: str = "bf16"):
+        return cls(cfg, device=device, max_batch=max_batch, fused=fused, weights=weights, kv_dtype=kv_dtype)
 
     def _alloc_caches(self):
         c = self.cfg
         # One spare slot (index max_batch) absorbs the K/V writes of padding rows.
         self.scratch_slot = self.max_batch
         cache_shape = (c.n_layers, self.max_batch + 1, c.max_seq, c.n_kv_heads, c.head_dim)
-        self.k_cache = torch.zeros(cache_shape, dtype=torch.bfloat16, device=self.device)
-        self.v_cache = torch.zeros(cache_shape, dtype=torch.bfloat16, device=self.device)
+        self.k_cache = torch.zeros(cache_shape, dtype=KV_DTYPES[self.kv_dtype], device=self.device)
+        self.v_cache = torch.zeros(cache_shape, dtype=KV_DTYPES[self.kv_dtype], device=self.device)
+
+    def kv_cache_bytes(self) -> int:
+        """Bytes of the K and V caches together."""
+        return self.k_cache.nbytes + self.v_cache.nbytes
 
     def kv_copy(self, jobs) -> None:
         """Copy K/V rows between cache slots on the current stream: ``jobs`` is a
         list of ``(src, dst, n)``, rows [0, n) of slot src -> slot dst in every
-        layer (``ops.kv_copy_``, at most ``ops.MAX_KV_COPY_JOBS`` per call)."""
+        layer (``ops.kv_copy_``, at most ``ops.MAX_KV_COPY_JOBS`` per call). An FP8 cache goes through the same
+        kernel as bf16 [L, slots, S, Hkv, D / 2]: the rows are moved bit for bit, two e4m3 bytes per element."""
+        if self.kv_dtype == "fp8":
+            shape = tuple(self.k_cache.shape[:-1]) + (self.cfg.head_dim // 2,)
+            ops.kv_copy_(self.k_cache.view(torch.bfloat16).view(shape), self.v_cache.view(torch.bfloat16).view(shape),
+                         jobs)
+            return
         ops.kv_copy_(self.k_cache, self.v_cache, jobs)
 
     def embed_pool(self, jobs, out: torch.Tensor) -> None:
@@ -239,7 +266,7 @@ class TinyLlama:
             dims = ops.LlamaDims(vocab=c.vocab, dim=c.dim, n_layers=c.n_layers, H=c.n_heads, Hkv=c.n_kv_heads,
                                  D=c.head_dim, ffn=c.ffn, max_seq=c.max_seq, max_batch=self.max_batch + 1, eps=c.eps,
                                  theta=c.rope_theta, qk_norm=int(c.qk_norm), qkv_bias=int(c.qkv_bias),
-                                 rope_table=int(c.rope_scaling is not None))
+                                 rope_table=int(c.rope_scaling is not None), kv_fp8=int(self.kv_dtype == "fp8"))
             self._fused = ops.FusedLlamaDecoder(dims, self.fused_weights(), self.k_cache, self.v_cache)
         return self._fused
 
@@ -256,6 +283,9 @@ class TinyLlama:
             ids = torch.empty(B, dtype=torch.int64, device=self.device)
             self.fused_decoder().step(tokens, pos, logits, ids, slots, emit_rows)
             return ids, logits
+        if self.kv_dtype != "bf16":
+            raise ValueError(f"an {self.kv_dtype} KV cache runs the fused step only (at most {ops.MAX_ROWS} rows, "
+                             "fused=True): the unfused kernels read and write bf16 caches")
         return self._decode_unfused(tokens, pos, pos_range or (0, self.cfg.max_seq - 1))
 
     def _decode_unfused(self, tokens, pos, pos_range):
@@ -326,14 +356,19 @@ class TinyLlama:
 
     # ------------------------------------------------------------------ fp32 reference
     @torch.no_grad()
-    def reference_logits(self, seqs: torch.Tensor) -> torch.Tensor:
-        """fp32 forward of full sequences [B, T]; returns logits of the last position [B, V]."""
-        return self.reference_hidden(seqs)[:, -1] @ self.lm_head.float().T
+    def reference_logits(self, seqs: torch.Tensor, kv_round=None) -> torch.Tensor:
+        """fp32 forward of full sequences [B, T]; returns logits of the last position [B, V]. ``kv_round``: see
+        ``reference_hidden``."""
+        return self.reference_hidden(seqs, kv_round)[:, -1] @ self.lm_head.float().T
 
     @torch.no_grad()
-    def reference_hidden(self, seqs: torch.Tensor) -> torch.Tensor:
+    def reference_hidden(self, seqs: torch.Tensor, kv_round=None) -> torch.Tensor:
         """fp32 forward of full sequences [B, T]; returns the final normed hidden
-        state of every position [B, T, dim] (what the LM head multiplies)."""
+        state of every position [B, T, dim] (what the LM head multiplies).
+        ``kv_round``: how K and V rows are stored, a function of the fp32 rows. None: the model's own cache
+        format, bf16 rounding or ``e4m3_round`` (one rounding from fp32, not through bf16)."""
+        if kv_round is None:
+            kv_round = e4m3_round if self.kv_dtype == "fp8" else (lambda t: t.to(torch.bfloat16).float())
         c = self.cfg
         B, T = seqs.shape
         f32 = lambda t: t.float()
@@ -365,15 +400,19 @@ class TinyLlama:
         G = c.n_heads // c.n_kv_heads
         mask = torch.full((T, T), float("-inf"), device=seqs.device).triu(1)
         for i, L in enumerate(self.layers):
-            qkv = h @ f32(L["wqkv"]).T
-            qkv = bf(qkv + f32(L["bqkv"]) if c.qkv_bias else qkv)
+            raw = h @ f32(L["wqkv"]).T
+            raw = raw + f32(L["bqkv"]) if c.qkv_bias else raw
+            qkv = bf(raw)
             q = qkv[..., : c.n_heads * c.head_dim].view(B, T, c.n_heads, c.head_dim)
             k = qkv[..., c.n_heads * c.head_dim: (c.n_heads + c.n_kv_heads) * c.head_dim].view(
                 B, T, c.n_kv_heads, c.head_dim)
-            v = qkv[..., (c.n_heads + c.n_kv_heads) * c.head_dim:].view(B, T, c.n_kv_heads, c.head_dim)
+            # V is stored from the fp32 projection (the bf16 rounding of it is the bf16 store itself; the FP8 store
+            # rounds the fp32 value once). A QK-norm model's V passes through the bf16 projection buffer first.
+            v = kv_round((qkv if c.qk_norm else raw)[..., (c.n_heads + c.n_kv_heads) * c.head_dim:]).view(
+                B, T, c.n_kv_heads, c.head_dim)
             if c.qk_norm:
                 q, k = rms(q, L["q_norm"]), rms(k, L["k_norm"])
-            q, k = bf(rope(q)), bf(rope(k))
+            q, k = bf(rope(q)), kv_round(rope(k))
             k = k.repeat_interleave(G, dim=2)
             v = v.repeat_interleave(G, dim=2)
             s = torch.einsum("bqhd,bkhd->bhqk", q, k) / math.sqrt(c.head_dim) + mask

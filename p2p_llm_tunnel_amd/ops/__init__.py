@@ -23,7 +23,7 @@ class LlamaDims(ctypes.Structure):
     """Mirror of ``LlamaDims`` in decode_fused.hip."""
     _fields_ = [(n, ctypes.c_int) for n in ("vocab", "dim", "n_layers", "H", "Hkv", "D", "ffn", "max_seq",
                                            "max_batch")] + [("eps", ctypes.c_float), ("theta", ctypes.c_float),
-                                                            ("rope_table", ctypes.c_int),
+                                                            ("kv_fp8", ctypes.c_int), ("rope_table", ctypes.c_int),
                                                             ("qk_norm", ctypes.c_int), ("qkv_bias", ctypes.c_int)]
 
 
@@ -49,6 +49,13 @@ class StepPlan(ctypes.Structure):
     _fields_ = ([("rows", _INT), ("emit_rows", _INT)] +
                 [(n, GemmPlan) for n in ("qkv_first", "qkv", "o", "gate_up", "down", "lm_head")] +
                 [("attn", AttnPlan), ("am_parts", _INT), ("qk_norm_grid", _INT), ("qk_norm_table", _INT)])
+
+
+class KvPlan(ctypes.Structure):
+    """Mirror of ``KvPlan``: the FP8-cache variants a step launches beside its ``StepPlan`` (``dims.kv_fp8``):
+    ``attn_kv8``: 1 for ``k_attn<D, G, true>``, which reads an e4m3 cache; ``qk_norm_kv8``: 1 when
+    ``k_qknorm_rope`` is the variant that appends k and v as e4m3. The _KV8 epilogue shows in ``StepPlan.qkv.epi``."""
+    _fields_ = [("attn_kv8", _INT), ("qk_norm_kv8", _INT)]
 
 
 def lib() -> ctypes.CDLL:
@@ -85,6 +92,7 @@ def lib() -> ctypes.CDLL:
         _LIB.p2pt_llama_decode.argtypes = [ctypes.POINTER(LlamaDims), ctypes.POINTER(vp), vp, vp, vp, vp, vp, i, i,
                                            vp, ctypes.c_size_t, vp, vp, vp]
         _LIB.p2pt_llama_plan.argtypes = [ctypes.POINTER(LlamaDims), i, i, ctypes.POINTER(StepPlan)]
+        _LIB.p2pt_llama_kv_plan.argtypes = [ctypes.POINTER(LlamaDims), ctypes.POINTER(KvPlan)]
         _LIB.p2pt_attn_span.argtypes = [i, i]
         _LIB.p2pt_max_rows.argtypes = []
         # microbenchmark hooks (scripts/bench_skinny.py)
@@ -92,6 +100,7 @@ def lib() -> ctypes.CDLL:
         _LIB.p2pt_attn_bench.argtypes = [vp, vp, vp, vp, i, i, i, i, i, vp, vp, vp, vp, i, vp]
         for fn in ("p2pt_rmsnorm", "p2pt_silu_mul", "p2pt_rope_qkv_cache", "p2pt_decode_attention", "p2pt_argmax",
                    "p2pt_skinny_gemm", "p2pt_llama_decode", "p2pt_sample", "p2pt_logprobs", "p2pt_llama_plan", "p2pt_attn_span",
+                   "p2pt_llama_kv_plan",
                    "p2pt_max_rows", "p2pt_skinny_bench", "p2pt_attn_bench", "p2pt_kv_copy", "p2pt_max_kv_copy_jobs",
                    "p2pt_embed_pool", "p2pt_max_embed_jobs", "p2pt_qk_norm_rope_cache", "p2pt_penalize",
                    "p2pt_penalty_reset", "p2pt_max_logit_bias"):
@@ -114,6 +123,7 @@ MAX_ROWS = 64  # token rows per fused step; lib() checks it against decode_fused
 MAX_KV_COPY_JOBS = 8  # jobs per launch of kv_copy_ (kv_copy.hip's kMaxJobs: they travel in the kernel arguments)
 MAX_EMBED_JOBS = 16  # jobs per launch of embed_pool_ (embed_pool.hip's kMaxJobs: in the kernel arguments too)
 MAX_LOGIT_BIAS = 300  # entries of a slot's logit_bias list (penalty.hip's kMaxBias; the OpenAI API's limit)
+KV_FP8_DTYPES = (torch.float8_e4m3fn, torch.uint8)  # cache dtypes of a decoder with dims.kv_fp8 (the same bytes)
 MAX_TOP_LOGPROBS = 20  # top (id, logprob) pairs per row of logprobs_ (logprobs.hip's kMaxTop; the OpenAI API's limit)
 
 
@@ -123,6 +133,14 @@ def step_plan(dims: LlamaDims, B: int, emit_rows: int = 0) -> StepPlan:
     plan = StepPlan()
     if lib().p2pt_llama_plan(ctypes.byref(dims), B, emit_rows, ctypes.byref(plan)) != 0:
         raise ValueError("dims or row count not supported by the fused decode kernels")
+    return plan
+
+
+def kv_plan(dims: LlamaDims) -> KvPlan:
+    """The FP8-cache variants ``p2pt_llama_decode`` launches for ``dims`` (host only); both 0 without ``kv_fp8``."""
+    plan = KvPlan()
+    if lib().p2pt_llama_kv_plan(ctypes.byref(dims), ctypes.byref(plan)) != 0:
+        raise ValueError("dims not supported by the fused decode kernels")
     return plan
 
 
@@ -669,7 +687,10 @@ class FusedLlamaDecoder:
     (6 per layer with ``dims.qk_norm``: the per-head q/k RMSNorm of Qwen3 runs in a kernel of its own;
     with ``dims.qkv_bias`` the q/k/v bias of Qwen2 is added in the QKV GEMM's epilogue, still 5; with
     ``dims.rope_table`` the kernel that rotates reads its frequencies from ``weights[3]``, an fp32 (D / 2,)
-    table that sits between lm_head and the layers, and the kernel count does not change).
+    table that sits between lm_head and the layers, and the kernel count does not change; with
+    ``dims.kv_fp8`` the caches are ``torch.float8_e4m3fn`` (or uint8), one OCP e4m3 byte per element at scale 1,
+    written by the _KV8 epilogues / ``k_qknorm_rope`` variant and read by ``k_attn<D, G, true>``: the same
+    kernel count again).
 
     Holds the weight pointer table and a zero-initialised workspace; ``step``
     validates the per-call tensors and launches on the current stream (capturable
@@ -679,6 +700,16 @@ class FusedLlamaDecoder:
     def __init__(self, dims: LlamaDims, weights: list, k_cache: torch.Tensor, v_cache: torch.Tensor):
         self.dims = dims
         dev = k_cache.device
+        # The cache dtype against dims.kv_fp8 first (a host-only check): a mismatch would have every kernel read
+        # and write rows of the wrong width.
+        if dims.kv_fp8 not in (0, 1):
+            raise ValueError("dims.kv_fp8 must be 0 or 1")
+        for name, c in (("k_cache", k_cache), ("v_cache", v_cache)):
+            if dims.kv_fp8 and c.dtype not in KV_FP8_DTYPES:
+                raise TypeError(f"{name}: dims.kv_fp8 is set, so the cache must be torch.float8_e4m3fn (or uint8), "
+                                f"got {c.dtype}")
+            if not dims.kv_fp8 and c.dtype in KV_FP8_DTYPES:
+                raise TypeError(f"{name}: a {c.dtype} cache needs dims.kv_fp8 = 1")
         if dims.rope_table not in (0, 1):
             raise ValueError("dims.rope_table must be 0 or 1")
         g0 = 3 + dims.rope_table  # global entries ahead of the layers
@@ -690,8 +721,10 @@ class FusedLlamaDecoder:
         L, Bmax, S, Hkv, D = k_cache.shape
         if (L, Bmax, S, Hkv, D) != (dims.n_layers, dims.max_batch, dims.max_seq, dims.Hkv, dims.D):
             raise ValueError("cache shape does not match dims")
-        _check(k_cache, torch.bfloat16, "k_cache", dev)
-        _check(v_cache, torch.bfloat16, "v_cache", dev)
+        for name, c in (("k_cache", k_cache), ("v_cache", v_cache)):
+            _check(c, c.dtype if dims.kv_fp8 else torch.bfloat16, name, dev)
+        if v_cache.shape != k_cache.shape or v_cache.dtype != k_cache.dtype:
+            raise ValueError("k_cache and v_cache must have the same shape and dtype")
         per_layer = 8 if dims.qk_norm else 7 if dims.qkv_bias else 6
         if len(weights) != g0 + per_layer * dims.n_layers:
             raise ValueError(f"weight table: embed, final_norm, lm_head, "

@@ -9,6 +9,9 @@ namespace {
 struct LlamaDims {
   int vocab, dim, n_layers, H, Hkv, D, ffn, max_seq, max_batch;
   float eps, theta;
+  // The KV cache holds OCP e4m3fn bytes (scale 1) instead of bf16: the _KV8 epilogues and k_attn<D, G, true>. It sits
+  // ahead of the three family flags, whose order (qkv_bias last) the plan tests of those families pin.
+  int kv_fp8;
   int rope_table;  // RoPE frequencies from an fp32 table [D/2] (llama3 / linear scaling): w[3] points at it
   int qk_norm;  // per-head RMSNorm on q and k before RoPE (Qwen3): a sixth kernel per layer
   int qkv_bias;  // a bias on the q, k and v projections (Qwen2): added in the QKV GEMM's epilogue
@@ -41,6 +44,13 @@ struct StepPlan {
   int qk_norm_grid;  // k_qknorm_rope's gridDim.x (gridDim.y: rows); 0: not launched
   int qk_norm_table;  // k_qknorm_rope<D, true>: frequencies from the table (a QK-norm model with scaled RoPE)
 };
+// The FP8-cache choices of a step, beside StepPlan (whose layout the plan tests of earlier families pin int for
+// int): which k_attn and which k_qknorm_rope variant run. The _KV8 epilogue is StepPlan's own qkv.epi.
+struct KvPlan {
+  int attn_kv8;     // k_attn<D, G, true>: the cache is e4m3
+  int qk_norm_kv8;  // k_qknorm_rope<D, TAB, true>: k and v appended as e4m3 (a QK-norm model with an FP8 cache)
+};
+KvPlan plan_kv(const LlamaDims& d) { return {d.kv_fp8, d.qk_norm ? d.kv_fp8 : 0}; }
 
 // One workgroup per tn subtiles of 16 >> kpl columns of one 16-row tile.
 //  - K parts (GemmArgs::kpl), where asked for (the d_model-wide O and down
@@ -87,8 +97,9 @@ StepPlan plan_step(const LlamaDims& d, int B, int emit_rows) {
   // QK-norm models: the GEMM stores the raw projection and k_qknorm_rope finishes it.
   // QKV-bias models: the RoPE epilogue with the bias add. No K parts on QKV (launch() refuses them with a bias).
   // Scaled RoPE (rope_table): the table counterpart of whichever kernel rotates; nothing else moves.
-  const int rope_epi = d.rope_table ? (d.qkv_bias ? EPI_ROPE_BIAS_TAB : EPI_ROPE_TAB)
-                                    : (d.qkv_bias ? EPI_ROPE_BIAS : EPI_ROPE);
+  // FP8 cache (kv_fp8): the _KV8 counterpart of whichever kernel appends, and of k_attn; nothing else moves.
+  const int rope_epi = (d.rope_table ? (d.qkv_bias ? EPI_ROPE_BIAS_TAB : EPI_ROPE_TAB)
+                                     : (d.qkv_bias ? EPI_ROPE_BIAS : EPI_ROPE)) + (d.kv_fp8 ? kEpiKv8 : 0);
   p.qkv = plan_gemm(d.qk_norm ? EPI_STORE : rope_epi, 1, B, (d.H + 2 * d.Hkv) * d.D, d.dim);
   if (d.qk_norm) {
     const int per_wg = qknorm_heads_per_wg(d.D);
@@ -240,7 +251,7 @@ hipError_t launch_as(const GemmPlan& p, GemmArgs a, hipStream_t s) {
   return hipGetLastError();
 }
 
-// The table epilogues run QKV projections only, so they carry just the (nw, um) pairs plan_gemm can give one
+// The table and FP8-cache epilogues run QKV projections only, so they carry just the (nw, um) pairs plan_gemm can give one
 // (fixed_nw == 0): 4 waves up to 16 k-steps with um 1, 2 or 4, and 8 waves from 17 on, where a wave's share is
 // at least 3 k-steps and um is 4.
 template <int EPI>
@@ -257,7 +268,7 @@ hipError_t launch_qkv_table(const GemmPlan& p, GemmArgs a, hipStream_t s) {
   return hipGetLastError();
 }
 
-// The one (nw, tn, epi, um) dispatch: the 50 k_skinny instantiations (42, and 4 for each table epilogue).
+// The one (nw, tn, epi, um) dispatch: the 66 k_skinny instantiations (42, and 4 for each table or FP8-cache epilogue).
 hipError_t launch(const GemmPlan& p, const GemmArgs& a, hipStream_t s) {
   if (p.kpl < 0 || p.kpl > kMaxKpl || (p.ss_in > 0) != (a.ss_part != nullptr)) return hipErrorInvalidValue;
   if (p.kpl && (p.tn != 1 || (p.M << p.kpl) > 16 || p.K % (32 << p.kpl))) return hipErrorInvalidValue;
@@ -268,6 +279,10 @@ hipError_t launch(const GemmPlan& p, const GemmArgs& a, hipStream_t s) {
   switch (p.epi * 4 + p.tn) {
     case EPI_ROPE_TAB * 4 + 1: return launch_qkv_table<EPI_ROPE_TAB>(p, a, s);
     case EPI_ROPE_BIAS_TAB * 4 + 1: return launch_qkv_table<EPI_ROPE_BIAS_TAB>(p, a, s);
+    case EPI_ROPE_KV8 * 4 + 1: return launch_qkv_table<EPI_ROPE_KV8>(p, a, s);
+    case EPI_ROPE_BIAS_KV8 * 4 + 1: return launch_qkv_table<EPI_ROPE_BIAS_KV8>(p, a, s);
+    case EPI_ROPE_TAB_KV8 * 4 + 1: return launch_qkv_table<EPI_ROPE_TAB_KV8>(p, a, s);
+    case EPI_ROPE_BIAS_TAB_KV8 * 4 + 1: return launch_qkv_table<EPI_ROPE_BIAS_TAB_KV8>(p, a, s);
     case EPI_ROPE * 4 + 1: return launch_as<1, EPI_ROPE>(p, a, s);
     case EPI_ROPE_BIAS * 4 + 1: return launch_as<1, EPI_ROPE_BIAS>(p, a, s);
     case EPI_RESID * 4 + 1: return launch_as<1, EPI_RESID>(p, a, s);
@@ -280,8 +295,8 @@ hipError_t launch(const GemmPlan& p, const GemmArgs& a, hipStream_t s) {
 }
 
 // (span slot, row, KV head) workgroups of 8 waves. Row b reads cache slot
-// slot[b] (nullptr: slot b) of nslots.
-hipError_t launch_attn(const AttnPlan& p, const void* q, const void* kc, const void* vc, const int* pos,
+// slot[b] (nullptr: slot b) of nslots. kv8: the caches hold e4m3 bytes (KvPlan::attn_kv8).
+hipError_t launch_attn(const AttnPlan& p, int kv8, const void* q, const void* kc, const void* vc, const int* pos,
                        const int* slot, int nslots, float* part_o, float* part_ml, unsigned* counters, void* out,
                        int H, int Hkv, int Smax, hipStream_t s) {
   auto go = [&](auto kern) {
@@ -291,37 +306,57 @@ hipError_t launch_attn(const AttnPlan& p, const void* q, const void* kc, const v
                        1.f / sqrtf(float(p.D)));
     return hipGetLastError();
   };
-  if (p.G < 1 || p.G > 8) return hipErrorInvalidValue;
-  switch (p.D * 16 + p.G) {
-    case 64 * 16 + 1: return go(k_attn<64, 1>);
-    case 64 * 16 + 2: return go(k_attn<64, 2>);
-    case 64 * 16 + 4: return go(k_attn<64, 4>);
-    case 64 * 16 + 5: return go(k_attn<64, 5>);
-    case 64 * 16 + 6: return go(k_attn<64, 6>);
-    case 64 * 16 + 7: return go(k_attn<64, 7>);
-    case 64 * 16 + 8: return go(k_attn<64, 8>);
-    case 128 * 16 + 1: return go(k_attn<128, 1>);
-    case 128 * 16 + 2: return go(k_attn<128, 2>);
-    case 128 * 16 + 4: return go(k_attn<128, 4>);
-    case 128 * 16 + 5: return go(k_attn<128, 5>);
-    case 128 * 16 + 6: return go(k_attn<128, 6>);
-    case 128 * 16 + 7: return go(k_attn<128, 7>);
-    case 128 * 16 + 8: return go(k_attn<128, 8>);
+  if (p.G < 1 || p.G > 8 || (kv8 != 0 && kv8 != 1)) return hipErrorInvalidValue;
+  switch ((p.D * 16 + p.G) * 2 + kv8) {
+    case (64 * 16 + 1) * 2: return go(k_attn<64, 1>);
+    case (64 * 16 + 2) * 2: return go(k_attn<64, 2>);
+    case (64 * 16 + 4) * 2: return go(k_attn<64, 4>);
+    case (64 * 16 + 5) * 2: return go(k_attn<64, 5>);
+    case (64 * 16 + 6) * 2: return go(k_attn<64, 6>);
+    case (64 * 16 + 7) * 2: return go(k_attn<64, 7>);
+    case (64 * 16 + 8) * 2: return go(k_attn<64, 8>);
+    case (128 * 16 + 1) * 2: return go(k_attn<128, 1>);
+    case (128 * 16 + 2) * 2: return go(k_attn<128, 2>);
+    case (128 * 16 + 4) * 2: return go(k_attn<128, 4>);
+    case (128 * 16 + 5) * 2: return go(k_attn<128, 5>);
+    case (128 * 16 + 6) * 2: return go(k_attn<128, 6>);
+    case (128 * 16 + 7) * 2: return go(k_attn<128, 7>);
+    case (128 * 16 + 8) * 2: return go(k_attn<128, 8>);
+    // an e4m3 cache: the same (D, G) set
+    case (64 * 16 + 1) * 2 + 1: return go(k_attn<64, 1, true>);
+    case (64 * 16 + 2) * 2 + 1: return go(k_attn<64, 2, true>);
+    case (64 * 16 + 4) * 2 + 1: return go(k_attn<64, 4, true>);
+    case (64 * 16 + 5) * 2 + 1: return go(k_attn<64, 5, true>);
+    case (64 * 16 + 6) * 2 + 1: return go(k_attn<64, 6, true>);
+    case (64 * 16 + 7) * 2 + 1: return go(k_attn<64, 7, true>);
+    case (64 * 16 + 8) * 2 + 1: return go(k_attn<64, 8, true>);
+    case (128 * 16 + 1) * 2 + 1: return go(k_attn<128, 1, true>);
+    case (128 * 16 + 2) * 2 + 1: return go(k_attn<128, 2, true>);
+    case (128 * 16 + 4) * 2 + 1: return go(k_attn<128, 4, true>);
+    case (128 * 16 + 5) * 2 + 1: return go(k_attn<128, 5, true>);
+    case (128 * 16 + 6) * 2 + 1: return go(k_attn<128, 6, true>);
+    case (128 * 16 + 7) * 2 + 1: return go(k_attn<128, 7, true>);
+    case (128 * 16 + 8) * 2 + 1: return go(k_attn<128, 8, true>);
   }
   return hipErrorInvalidValue;
 }
 
 // (row, head group) workgroups of k_qknorm_rope: grid_x groups of qknorm_heads_per_wg(D) heads.
 // table: the k_qknorm_rope<D, true> variant, which reads a.inv_freq (8-byte loads) and is refused without it.
-hipError_t launch_qknorm(int grid_x, int rows, int D, bool table, const QkNormArgs& a, hipStream_t s) {
+// kv8: the variants that append k and v to an e4m3 cache.
+hipError_t launch_qknorm(int grid_x, int rows, int D, bool table, bool kv8, const QkNormArgs& a, hipStream_t s) {
   if (grid_x <= 0 || rows <= 0 || grid_x * qknorm_heads_per_wg(D) < a.H + 2 * a.Hkv) return hipErrorInvalidValue;
   if (table && (a.inv_freq == nullptr || reinterpret_cast<uintptr_t>(a.inv_freq) % 8)) return hipErrorInvalidValue;
   const dim3 g(grid_x, rows), b(kQkNormWaves * 64);
-  switch (D * 2 + int(table)) {
-    case 64 * 2: hipLaunchKernelGGL((k_qknorm_rope<64, false>), g, b, 0, s, a); break;
-    case 128 * 2: hipLaunchKernelGGL((k_qknorm_rope<128, false>), g, b, 0, s, a); break;
-    case 64 * 2 + 1: hipLaunchKernelGGL((k_qknorm_rope<64, true>), g, b, 0, s, a); break;
-    case 128 * 2 + 1: hipLaunchKernelGGL((k_qknorm_rope<128, true>), g, b, 0, s, a); break;
+  switch (D * 4 + int(kv8) * 2 + int(table)) {
+    case 64 * 4: hipLaunchKernelGGL((k_qknorm_rope<64, false>), g, b, 0, s, a); break;
+    case 128 * 4: hipLaunchKernelGGL((k_qknorm_rope<128, false>), g, b, 0, s, a); break;
+    case 64 * 4 + 1: hipLaunchKernelGGL((k_qknorm_rope<64, true>), g, b, 0, s, a); break;
+    case 128 * 4 + 1: hipLaunchKernelGGL((k_qknorm_rope<128, true>), g, b, 0, s, a); break;
+    case 64 * 4 + 2: hipLaunchKernelGGL((k_qknorm_rope<64, false, true>), g, b, 0, s, a); break;
+    case 128 * 4 + 2: hipLaunchKernelGGL((k_qknorm_rope<128, false, true>), g, b, 0, s, a); break;
+    case 64 * 4 + 3: hipLaunchKernelGGL((k_qknorm_rope<64, true, true>), g, b, 0, s, a); break;
+    case 128 * 4 + 3: hipLaunchKernelGGL((k_qknorm_rope<128, true, true>), g, b, 0, s, a); break;
     default: return hipErrorInvalidValue;
   }
   return hipGetLastError();
@@ -332,6 +367,8 @@ bool dims_ok(const LlamaDims& d) {
   if (d.qk_norm != 0 && d.qk_norm != 1) return false;
   if (d.qkv_bias != 0 && d.qkv_bias != 1) return false;
   if (d.rope_table != 0 && d.rope_table != 1) return false;
+  // An e4m3 row of D in {64, 128} bytes stays a multiple of 16 bytes (k_attn's 8-byte loads, kv_copy's 16-byte ones).
+  if (d.kv_fp8 != 0 && d.kv_fp8 != 1) return false;
   // No family has both, and the EPI_STORE + k_qknorm_rope route would need the bias elsewhere.
   if (d.qkv_bias && d.qk_norm) return false;
   // GEMM operands are addressed with 32-bit byte offsets below kOob (2 GiB):
@@ -388,6 +425,13 @@ int p2pt_llama_plan(const LlamaDims* d, int B, int emit_rows, StepPlan* out) {
   return 0;
 }
 
+// The FP8-cache variants p2pt_llama_decode launches beside the plan above (host only); both 0 for a bf16 cache.
+int p2pt_llama_kv_plan(const LlamaDims* d, KvPlan* out) {
+  if (!dims_ok(*d)) return int(hipErrorInvalidValue);
+  *out = plan_kv(*d);
+  return 0;
+}
+
 // k_attn's span rule: tokens per span slot for a row of `len` tokens.
 int p2pt_attn_span(int len, int slots) { return len > 0 && slots > 0 ? attn_span(len, unsigned(slots)) : 0; }
 
@@ -406,7 +450,7 @@ int p2pt_max_rows() { return kMaxM; }
 //      With dims.qkv_bias each layer has 7 entries: the six, then bqkv [(H+2Hkv)*D], interleaved like wqkv's rows.
 //      With dims.rope_table a fourth global entry follows lm_head, ahead of the layers: inv_freq, fp32 [D/2],
 //      8-byte aligned, the RoPE frequencies every layer rotates with (theta is then not read).
-//   k_cache/v_cache: [n_layers][max_batch][max_seq][Hkv][D]
+//   k_cache/v_cache: [n_layers][max_batch][max_seq][Hkv][D], bf16, or with dims.kv_fp8 one e4m3 byte per element
 //   tokens int64 [B <= 64], pos int32 [B] (< max_seq), logits bf16 [B][vocab], ids int64 [B]
 //   emit_rows: only rows [0, emit_rows) get logits and ids (the LM head runs on
 //     them alone: prefill rows that sample nothing go last); <= 0 means B
@@ -421,8 +465,9 @@ int p2pt_llama_decode(const LlamaDims* dp, const void* const* w, void* k_cache, 
   const Workspace W = carve(d, static_cast<uint8_t*>(ws));
   if (ws_bytes < W.bytes) return int(hipErrorInvalidValue);
   const StepPlan P = plan_step(d, B, emit_rows);
+  const KvPlan KV = plan_kv(d);
   auto s = static_cast<hipStream_t>(stream);
-  const size_t layer_cache = size_t(d.max_batch) * d.max_seq * d.Hkv * d.D;
+  const size_t layer_cache = size_t(d.max_batch) * d.max_seq * d.Hkv * d.D * (d.kv_fp8 ? 1 : 2);  // bytes
   hipError_t e;
   auto failed = [&](hipError_t r) { return (e = r) != hipSuccess; };
 
@@ -433,8 +478,8 @@ int p2pt_llama_decode(const LlamaDims* dp, const void* const* w, void* k_cache, 
   for (int L = 0; L < d.n_layers; L++) {
     // attn_norm, wqkv, wo, ffn_norm, w_gate_up, w_down (+ q_norm, k_norm, or + bqkv)
     const void* const* wl = w + 3 + d.rope_table + (d.qk_norm ? 8 : d.qkv_bias ? 7 : 6) * L;
-    uint16_t* kc = static_cast<uint16_t*>(k_cache) + L * layer_cache;
-    uint16_t* vc = static_cast<uint16_t*>(v_cache) + L * layer_cache;
+    uint16_t* kc = reinterpret_cast<uint16_t*>(static_cast<uint8_t*>(k_cache) + L * layer_cache);
+    uint16_t* vc = reinterpret_cast<uint16_t*>(static_cast<uint8_t*>(v_cache) + L * layer_cache);
     const GemmPlan& qkv = L ? P.qkv : P.qkv_first;
     const GemmArgs qkv_in = gemm(W.resid, wl[1]) + norm(W.ss, qkv.ss_in, d.eps);
     const GemmArgs to_qkv =
@@ -452,9 +497,10 @@ int p2pt_llama_decode(const LlamaDims* dp, const void* const* w, void* k_cache, 
       const QkNormArgs qn{W.qkv, static_cast<const uint16_t*>(wl[6]), static_cast<const uint16_t*>(wl[7]), pos, slots,
                           d.max_batch, W.q, kc, vc, d.H, d.Hkv, d.max_seq, d.eps, log2f(d.theta),
                           static_cast<const float*>(inv_freq)};
-      if (failed(launch_qknorm(P.qk_norm_grid, B, d.D, P.qk_norm_table != 0, qn, s))) return int(e);
+      if (failed(launch_qknorm(P.qk_norm_grid, B, d.D, P.qk_norm_table != 0, KV.qk_norm_kv8 != 0, qn, s)))
+        return int(e);
     }
-    if (failed(launch_attn(P.attn, W.q, kc, vc, pos, slots, d.max_batch, W.part_o, W.part_ml, W.counters, W.attn, d.H,
+    if (failed(launch_attn(P.attn, KV.attn_kv8, W.q, kc, vc, pos, slots, d.max_batch, W.part_o, W.part_ml, W.counters, W.attn, d.H,
                            d.Hkv, d.max_seq, s)))
       return int(e);
     if (failed(launch(P.o, to_o, s))) return int(e);
@@ -490,7 +536,7 @@ int p2pt_qk_norm_rope_cache(const void* qkv, const int* pos, const int* slots, c
                      static_cast<uint16_t*>(k_cache), static_cast<uint16_t*>(v_cache), H, Hkv, Smax, eps, log2f(theta),
                      inv_freq};
   const int per_wg = qknorm_heads_per_wg(D);
-  return int(launch_qknorm((H + 2 * Hkv + per_wg - 1) / per_wg, B, D, inv_freq != nullptr, a,
+  return int(launch_qknorm((H + 2 * Hkv + per_wg - 1) / per_wg, B, D, inv_freq != nullptr, false, a,
                            static_cast<hipStream_t>(stream)));
 }
 
@@ -502,7 +548,7 @@ int p2pt_attn_bench(const void* q, const void* kc, const void* vc, const int* po
   if (!rows_ok(B) || Hkv <= 0 || H % Hkv || Smax <= 0 || reps <= 0) return int(hipErrorInvalidValue);
   const AttnPlan p = plan_attn(B, H, Hkv, D, Smax);
   for (int r = 0; r < reps; r++) {
-    hipError_t e = launch_attn(p, q, kc, vc, pos, nullptr, B, part_o, part_ml, counters, out, H, Hkv, Smax,
+    hipError_t e = launch_attn(p, 0, q, kc, vc, pos, nullptr, B, part_o, part_ml, counters, out, H, Hkv, Smax,
                                static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return int(e);
   }

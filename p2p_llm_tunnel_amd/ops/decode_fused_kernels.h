@@ -15,6 +15,8 @@
 //                        read from an fp32 table [D/2] instead of computed inline)
 //     (QK-norm models:   k_skinny<STORE> writes the raw projection instead, and
 //      k_qknorm_rope     norms every q and k head, rotates and appends: a sixth kernel)
+//     (FP8 KV cache:     the _KV8 counterpart of whichever kernel appends writes e4m3 bytes,
+//                        and k_attn<D, G, true> reads them: the same kernel count)
 //     k_attn            GQA flash-decoding split-K; the last split to finish
 //                        for a (sequence, KV head) merges the partials in-kernel
 //     k_skinny<RESID>    O projection -> residual add -> per-row sum-of-squares
@@ -68,15 +70,27 @@ typedef float frag4 __attribute__((ext_vector_type(4)));
 // EPI_ROPE_TAB, EPI_ROPE_BIAS_TAB: EPI_ROPE and EPI_ROPE_BIAS with inv_freq[i] read from a table in device
 // memory (llama3 / linear RoPE scaling: the host computes the table once per model). Variants of their own for
 // the same reason: models with default RoPE keep the inline exp2f and launch exactly what they did.
+// EPI_ROPE_KV8, EPI_ROPE_BIAS_KV8, EPI_ROPE_TAB_KV8, EPI_ROPE_BIAS_TAB_KV8: the four RoPE epilogues for an FP8
+// (OCP e4m3fn, scale 1) KV cache: q is written as before, the K and V rows as one byte per element, rounded once
+// from the epilogue's fp32 value (f32_to_e4m3x2). Variants of their own, kEpiKv8 above their bf16 counterparts, so
+// that a bf16 cache launches exactly the kernels it did.
+constexpr int kEpiKv8 = 8;
 enum Epi : int {
   EPI_STORE = 0, EPI_ROPE = 1, EPI_SILU = 2, EPI_RESID = 3, EPI_ARGMAX = 4, EPI_ROPE_BIAS = 5, EPI_ROPE_TAB = 6,
-  EPI_ROPE_BIAS_TAB = 7
+  EPI_ROPE_BIAS_TAB = 7,
+  EPI_ROPE_KV8 = kEpiKv8 + EPI_ROPE, EPI_ROPE_BIAS_KV8 = kEpiKv8 + EPI_ROPE_BIAS,
+  EPI_ROPE_TAB_KV8 = kEpiKv8 + EPI_ROPE_TAB, EPI_ROPE_BIAS_TAB_KV8 = kEpiKv8 + EPI_ROPE_BIAS_TAB
 };
-constexpr bool epi_is_rope(int epi) {
-  return epi == EPI_ROPE || epi == EPI_ROPE_BIAS || epi == EPI_ROPE_TAB || epi == EPI_ROPE_BIAS_TAB;
+constexpr bool epi_kv8(int epi) {
+  return epi == EPI_ROPE_KV8 || epi == EPI_ROPE_BIAS_KV8 || epi == EPI_ROPE_TAB_KV8 || epi == EPI_ROPE_BIAS_TAB_KV8;
 }
-constexpr bool epi_has_bias(int epi) { return epi == EPI_ROPE_BIAS || epi == EPI_ROPE_BIAS_TAB; }
-constexpr bool epi_has_table(int epi) { return epi == EPI_ROPE_TAB || epi == EPI_ROPE_BIAS_TAB; }
+constexpr int epi_base(int epi) { return epi_kv8(epi) ? epi - kEpiKv8 : epi; }  // the bf16-cache counterpart
+constexpr bool epi_is_rope(int epi) {
+  return epi_base(epi) == EPI_ROPE || epi_base(epi) == EPI_ROPE_BIAS || epi_base(epi) == EPI_ROPE_TAB ||
+         epi_base(epi) == EPI_ROPE_BIAS_TAB;
+}
+constexpr bool epi_has_bias(int epi) { return epi_base(epi) == EPI_ROPE_BIAS || epi_base(epi) == EPI_ROPE_BIAS_TAB; }
+constexpr bool epi_has_table(int epi) { return epi_base(epi) == EPI_ROPE_TAB || epi_base(epi) == EPI_ROPE_BIAS_TAB; }
 
 struct GemmArgs {
   const uint16_t* x;  // A [M][K]
@@ -95,7 +109,7 @@ struct GemmArgs {
   const int* slot;  // ROPE: cache slot of each row (nullptr: row m -> slot m)
   int nslots;
   uint16_t* q_out;
-  uint16_t* kc;
+  uint16_t* kc;  // the _KV8 epilogues: e4m3 bytes, the same [slot][pos][Hkv][D] order
   uint16_t* vc;
   const uint16_t* bias;  // ROPE_BIAS(_TAB): [N], in the row order of W (interleaved like its rows)
   const float* inv_freq;  // ROPE_TAB, ROPE_BIAS_TAB: [D / 2] RoPE frequencies (the others compute them from log2_theta)
@@ -124,6 +138,34 @@ typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 // v_dot2_f32_bf16: c + a.lo * b.lo + a.hi * b.hi, products and sum in fp32.
 __device__ __forceinline__ float dot2_bf16(uint32_t a, uint32_t b, float c) {
   return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, a), __builtin_bit_cast(bf16x2_t, b), c, false);
+}
+
+// FP8 KV cache: OCP e4m3fn (4 exponent bits, bias 7, 3 mantissa bits, no infinities, 0x7f / 0xff NaN, largest
+// finite value 448), scale 1. Two fp32 values to two bytes (a in bits 0..7, b in 8..15), each rounded once to
+// nearest-even by v_cvt_pk_fp8_f32, subnormals (multiples of 2^-9) included. Finite values are clamped to +-448
+// first (v_med3_f32): what the conversion alone does above 448 (saturate, or NaN) depends on the wave's FP16_OVFL
+// mode bit, and the stored byte must not. NaN stays NaN: v_med3 would turn it into a bound, so it is passed by.
+__device__ __forceinline__ float e4m3_clamp(float x) {
+  const float c = __builtin_amdgcn_fmed3f(x, -448.f, 448.f);
+  return x != x ? x : c;
+}
+__device__ __forceinline__ uint16_t f32_to_e4m3x2(float a, float b) {
+  return uint16_t(__builtin_amdgcn_cvt_pk_fp8_f32(e4m3_clamp(a), e4m3_clamp(b), 0, false));
+}
+typedef float float2v __attribute__((ext_vector_type(2)));
+// Eight e4m3 bytes to fp32 (v_cvt_pk_f32_fp8: exact, every e4m3 value is an fp32 value).
+__device__ __forceinline__ void unpack8_e4m3(const uint2& v, float* f) {
+  const float2v a = __builtin_amdgcn_cvt_pk_f32_fp8(int(v.x), false), b = __builtin_amdgcn_cvt_pk_f32_fp8(int(v.x), true);
+  const float2v c = __builtin_amdgcn_cvt_pk_f32_fp8(int(v.y), false), d = __builtin_amdgcn_cvt_pk_f32_fp8(int(v.y), true);
+  f[0] = a[0]; f[1] = a[1]; f[2] = b[0]; f[3] = b[1];
+  f[4] = c[0]; f[5] = c[1]; f[6] = d[0]; f[7] = d[1];
+}
+// Eight e4m3 bytes as eight bf16 (exact: the low 16 bits of every decoded fp32 are zero).
+__device__ __forceinline__ uint4 e4m3x8_to_bf16x8(const uint2& v) {
+  float f[8];
+  unpack8_e4m3(v, f);
+  auto pk = [](float lo, float hi) { return (__float_as_uint(hi) & 0xffff0000u) | (__float_as_uint(lo) >> 16); };
+  return make_uint4(pk(f[0], f[1]), pk(f[2], f[3]), pk(f[4], f[5]), pk(f[6], f[7]));
 }
 
 // Cross-workgroup hand-off without L2 write-back/invalidate fences: payload
@@ -433,7 +475,28 @@ __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
       const int p = min(max(a.pos[m], 0), a.Smax - 1);
       const int sl = a.slot ? min(max(a.slot[m], 0), a.nslots - 1) : m;
       const int d = i + (second ? half : 0);
-      if (head < a.H + a.Hkv) {
+      if constexpr (epi_kv8(EPI)) {
+        // The head is the same for the whole workgroup (16 columns of one head) and m for the 16 lanes of a row,
+        // so the four lanes of a quad are always here together: lane c + 2 holds dim d + 1, and lanes with
+        // (c & 2) == 0 store dims d, d + 1 as one 2-byte word (d is even there). K: the rotated fp32 value; V: the
+        // fp32 projection (+ bias) itself, not its bf16 rounding.
+        float val = epi_has_bias(EPI) ? v[0][r] + bias : v[0][r];
+        if (head < a.H + a.Hkv) {
+          float sn, cs;
+          sincosf(float(p) * inv_freq, &sn, &cs);
+          const float x1 = second ? other : mine, x2 = second ? mine : other;
+          val = second ? x2 * cs + x1 * sn : x1 * cs - x2 * sn;
+        }
+        const float next = dpp<kDppXor2>(val);
+        if (head < a.H) {
+          a.q_out[(size_t(m) * a.H + head) * a.D + d] = uint16_t(f2bf_bits(val));
+        } else if (!(c & 2)) {
+          const bool is_k = head < a.H + a.Hkv;
+          uint8_t* row = reinterpret_cast<uint8_t*>(is_k ? a.kc : a.vc) +
+                         ((size_t(sl) * a.Smax + p) * a.Hkv + (head - a.H - (is_k ? 0 : a.Hkv))) * a.D;
+          *reinterpret_cast<uint16_t*>(row + d) = f32_to_e4m3x2(val, next);
+        }
+      } else if (head < a.H + a.Hkv) {
         float sn, cs;
         sincosf(float(p) * inv_freq, &sn, &cs);
         const float x1 = second ? other : mine, x2 = second ? mine : other;
@@ -553,7 +616,7 @@ struct QkNormArgs {
   const int* slot;  // nullptr: row m -> slot m
   int nslots;
   uint16_t* q_out;  // [M][H][D]
-  uint16_t* kc;     // [nslots][Smax][Hkv][D]
+  uint16_t* kc;     // [nslots][Smax][Hkv][D]; k_qknorm_rope<D, TAB, true>: e4m3 bytes
   uint16_t* vc;
   int H, Hkv, Smax;
   float eps, log2_theta;
@@ -567,7 +630,10 @@ __host__ __device__ __forceinline__ int qknorm_heads_per_wg(int D) { return kQkN
 
 // TAB: the frequencies of dims 2j and 2j + 1 come from a.inv_freq as one 8-byte load (scaled RoPE) instead
 // of exp2f; 2j + 1 < D / 2 for every lane.
-template <int D, bool TAB = false>
+// KV8: an FP8 (e4m3) cache. q is written as bf16 as before; k goes from the rotated fp32 value to e4m3 in one
+// rounding, v from the bf16 value read (exactly an fp32 value) likewise: two 2-byte stores per lane instead of two
+// 4-byte ones.
+template <int D, bool TAB = false, bool KV8 = false>
 __global__ __launch_bounds__(kQkNormWaves * 64) void k_qknorm_rope(QkNormArgs a) {
   constexpr int LPH = D / 4, half = D / 2;  // lanes per head
   const int lane = threadIdx.x & 63;
@@ -599,9 +665,9 @@ __global__ __launch_bounds__(kQkNormWaves * 64) void k_qknorm_rope(QkNormArgs a)
   if (head >= heads) return;
 
   uint32_t olo = lo, ohi = hi;  // v: copied as is
+  float o1[2] = {x1[0], x1[1]}, o2[2] = {x2[0], x2[1]};
   if (!is_v) {
     const float g1[2] = {bf_lo(glo), bf_hi(glo)}, g2[2] = {bf_lo(ghi), bf_hi(ghi)};
-    float o1[2], o2[2];
 #pragma unroll
     for (int e = 0; e < 2; e++) {
       const int i = 2 * j + e;
@@ -618,6 +684,14 @@ __global__ __launch_bounds__(kQkNormWaves * 64) void k_qknorm_rope(QkNormArgs a)
     ohi = pack2(o2[0], o2[1]);
   }
   const size_t row = (size_t(sl) * a.Smax + p) * a.Hkv;
+  if constexpr (KV8) {
+    if (!is_q) {
+      uint8_t* dst8 = reinterpret_cast<uint8_t*>(is_v ? a.vc : a.kc) + (row + (hc - a.H - (is_v ? a.Hkv : 0))) * D;
+      *reinterpret_cast<uint16_t*>(dst8 + 2 * j) = f32_to_e4m3x2(o1[0], o1[1]);
+      *reinterpret_cast<uint16_t*>(dst8 + 2 * j + half) = f32_to_e4m3x2(o2[0], o2[1]);
+      return;
+    }
+  }
   uint16_t* dst = is_q   ? a.q_out + (size_t(m) * a.H + hc) * D
                   : is_v ? a.vc + (row + (hc - a.H - a.Hkv)) * D
                          : a.kc + (row + (hc - a.H)) * D;
@@ -665,7 +739,12 @@ __host__ __device__ __forceinline__ int attn_span(int len, unsigned slots) {
   return std::max(kAttnMinSpan, (span + kAttnPiece - 1) / kAttnPiece * kAttnPiece);
 }
 
-template <int D, int G>
+// KV8: an FP8 (e4m3, scale 1) cache. The same lane -> (token, 8-dim group) map and the same reductions; a lane
+// loads its 8 dims as 8 bytes instead of 16 and decodes them with v_cvt_pk_f32_fp8 (exact). For the scores the
+// decoded K is packed to bf16 pairs (exact too: 3 mantissa bits, and e4m3's exponents lie inside bf16's), so the
+// dot products are the bf16 kernel's v_dot2_f32_bf16 chain against the packed q, product and sum in fp32; P.V
+// takes the decoded V in fp32. The softmax and everything after the span loop are the bf16 kernel's code.
+template <int D, int G, bool KV8 = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1))) void k_attn(
     const uint16_t* __restrict__ q, const uint16_t* __restrict__ kc, const uint16_t* __restrict__ vc,
     const int* __restrict__ pos, const int* __restrict__ slot, int nslots, float* __restrict__ part_o,
@@ -694,6 +773,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1))) void k
   const size_t tok_stride = size_t(Hkv) * D;
   const uint16_t* kbase = kc + size_t(sb) * Smax * tok_stride + size_t(kvh) * D + 8 * dg;
   const uint16_t* vbase = vc + size_t(sb) * Smax * tok_stride + size_t(kvh) * D + 8 * dg;
+  // KV8: the same element offsets, one byte per element.
+  const uint8_t* kbase8 = reinterpret_cast<const uint8_t*>(kc) + size_t(sb) * Smax * tok_stride + size_t(kvh) * D + 8 * dg;
+  const uint8_t* vbase8 = reinterpret_cast<const uint8_t*>(vc) + size_t(sb) * Smax * tok_stride + size_t(kvh) * D + 8 * dg;
   // This lane's 8 query dims of every head as bf16 pairs (v_dot2 operands).
   uint4 qpk[G];
   {
@@ -715,24 +797,34 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1))) void k
   for (int p0 = s0 + wv * TOK; p0 < s1; p0 += NWV * TOK) {
     const int ntok = min(TOK, s1 - p0);
     // Issue the piece (lanes past the end re-read the last valid row).
-    uint4 kr[NI], vr[NI];
+    uint4 kr[KV8 ? 1 : NI], vr[KV8 ? 1 : NI];
+    uint2 kr8[KV8 ? NI : 1], vr8[KV8 ? NI : 1];
 #pragma unroll
-    for (int j = 0; j < NI; j++)
-      kr[j] = *reinterpret_cast<const uint4*>(kbase + size_t(p0 + min(j * RPI + ri, ntok - 1)) * tok_stride);
+    for (int j = 0; j < NI; j++) {
+      const size_t t = size_t(p0 + min(j * RPI + ri, ntok - 1)) * tok_stride;
+      if constexpr (KV8) kr8[j] = *reinterpret_cast<const uint2*>(kbase8 + t);
+      else kr[j] = *reinterpret_cast<const uint4*>(kbase + t);
+    }
 #pragma unroll
-    for (int j = 0; j < NI; j++)
-      vr[j] = *reinterpret_cast<const uint4*>(vbase + size_t(p0 + min(j * RPI + ri, ntok - 1)) * tok_stride);
+    for (int j = 0; j < NI; j++) {
+      const size_t t = size_t(p0 + min(j * RPI + ri, ntok - 1)) * tok_stride;
+      if constexpr (KV8) vr8[j] = *reinterpret_cast<const uint2*>(vbase8 + t);
+      else vr[j] = *reinterpret_cast<const uint4*>(vbase + t);
+    }
     // Scores: lane (ri, dg) ends with token j*RPI + ri's score for every head.
     float sc[G][NI];
 #pragma unroll
     for (int j = 0; j < NI; j++) {
+      uint4 kj;
+      if constexpr (KV8) kj = e4m3x8_to_bf16x8(kr8[j]);
+      else kj = kr[j];
 #pragma unroll
       for (int g = 0; g < G; g++) {
         float d = 0.f;
-        d = dot2_bf16(qpk[g].x, kr[j].x, d);
-        d = dot2_bf16(qpk[g].y, kr[j].y, d);
-        d = dot2_bf16(qpk[g].z, kr[j].z, d);
-        d = dot2_bf16(qpk[g].w, kr[j].w, d);
+        d = dot2_bf16(qpk[g].x, kj.x, d);
+        d = dot2_bf16(qpk[g].y, kj.y, d);
+        d = dot2_bf16(qpk[g].z, kj.z, d);
+        d = dot2_bf16(qpk[g].w, kj.w, d);
         d = (LPR == 16 ? row16_sum(d) : row8_sum(d)) * scale;
         sc[g][j] = (j * RPI + ri < ntok) ? d : -INFINITY;
       }
@@ -761,7 +853,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1))) void k
 #pragma unroll
     for (int j = 0; j < NI; j++) {
       float f[8];
-      unpack8(vr[j], f);
+      if constexpr (KV8) unpack8_e4m3(vr8[j], f);
+      else unpack8(vr[j], f);
 #pragma unroll
       for (int g = 0; g < G; g++)
 #pragma unroll
@@ -927,6 +1020,11 @@ int attn_slots(int B, int Hkv, int max_seq) {
 //  - A persistent O -> gate/up -> down kernel (in-order tile queue,
 //    write-through hand-offs): small b1 0.358 -> 0.61-1.09 ms in every variant
 //    (profiles/r03/decode_block/).
+//  - FP8 KV cache, k_attn<D, G, true>: fp32 FMAs against q unpacked to fp32 (8 G more registers, <128,8> spilled
+//    232 bytes per lane) gave way before any run to packing the decoded K to bf16 for the v_dot2 chain
+//    (<128,4> 184 VGPRs, <128,8> 72 bytes). A layout with 16-byte loads (D / 16 lanes per row) was not tried.
+//    What ships, against bf16 (profiles/kv_fp8.json): batch 16 at 32k tokens 1.987 -> 1.479 ms (small) and
+//    4.298 -> 3.701 (Llama-3.2-1B's shape); batch 1 0.2-0.6 % slower at every context.
 //  - A two-deep load-batch pipeline (every projection +0.5-1.8 us) and one
 //    workgroup per CU forced through padded LDS (QKV 5.9 -> 9.9 us)
 //    (profiles/r02/decode/decode_sweep_s8.log).

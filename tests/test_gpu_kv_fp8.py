@@ -1,0 +1,475 @@
+"""FP8 (OCP e4m3fn, scale 1) KV cache in the fused decode step, on the GPU: the bytes the _KV8 epilogues and the
+``k_qknorm_rope`` variant append, ``k_attn<D, G, true>`` over them, then graph replay, the model against its fp32
+reference, the engine and a served checkpoint. One-layer models and one step, as in test_gpu_fused_stages.py, whose
+references and bounds this module reuses; ``judge`` is tests/test_kv_fp8.py's.
+
+Appended rows. Every stored byte is compared with the fp64 value x computed from the exact inputs its kernel read,
+and e_pre bounds how far the kernel's fp32 value can be from x before the one rounding:
+
+* V of a RoPE epilogue: x = proj / rms (+ bias); e_pre = gemm_ref's E (accumulation and 1/rms), plus U |x| for the
+  bias add: ``stage_qkv``'s vE. The kernel converts this fp32 value, not its bf16 rounding.
+* K of a RoPE epilogue: both members of a pair are rounded to bf16 (x1, x2: the rounding q shares), rotated in fp32
+  and converted; x = the rotation of bf(x1), bf(x2) in fp64, and e_pre is ``stage_qkv``'s error before the last
+  rounding: the inner flips flip(x1)|cos| + flip(x2)|sin|, the cos / sin error times |x1| + |x2| (inline exp2f:
+  ``rope_tables``; a table: ``table_angles``) and 3 U (|x1 cos| + |x2 sin|) for two products and an add.
+* ``k_qknorm_rope``: V is the bf16 value of the raw projection the kernel read, so e_pre = 0 and every byte is
+  decided; K: e_pre = (RN + 3 U)(|n1 cos| + |n2 sin|) + (|n1| + |n2|) dsc, test_gpu_qk_norm.py's E.
+
+Then |decode(byte) - clamp(x)| <= hu + e_pre, and the byte equals RNE(clamp(x)) wherever x lies farther than e_pre
+from a rounding boundary; at most 1 % of a case's elements may be undecided (e_pre is ~1e-6 |x| against a spacing of
+2^-3 |x|, so in practice none are). Nothing is scaled by a maximum.
+
+Attention. The reference is test_gpu_fused_stages.stage_attn in fp64 from the decoded cache bytes and the bf16 q
+the kernel read. Its bound carries over term by term: the kernel packs the decoded K to bf16 (exact: an e4m3 value
+has 3 mantissa bits and an exponent inside bf16's range) and runs the bf16 kernel's v_dot2_f32_bf16 chain, so a
+score is again D exact products summed in fp32, (D + 8) U scale sum|q||k|; the decoded V enters P.V as exact fp32
+values like an unpacked bf16 V; softmax, merges and the output rounding are the same code.
+
+Planted values. Models with a bias take exact ones: the weight rows of a few K and V columns are zeroed and the
+bias set to values in (448, 464), beyond 464, subnormals, values that round to +-0, and NaN (K rows at position 0
+keep them: cos = 1, sin = 0). The other families get the same classes by scaling weight rows (or the k_norm
+weight) by 2^8 and 2^-9 and by NaN weights. Planted cases judge the appended rows only: a NaN K or V row makes the
+attention output NaN by definition.
+
+Seen on an MI355X (printed by each case as a RATIO line; recorded, not asserted): over the 20 cases no decided byte
+differed, K and V ratios 0.987 .. 1.000 (an element next to a tie sits just under 1), q 0.993 .. 1.000, attention
+0.731 .. 0.938, undecided shares 0 .. 0.9 % of a case.
+"""
+import functools
+import http.client
+import json
+import math
+import random
+from dataclasses import dataclass, replace
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+import torch
+
+from p2p_llm_tunnel_amd import ops
+from p2p_llm_tunnel_amd.models import rope
+from p2p_llm_tunnel_amd.models.rope import RopeScaling
+from p2p_llm_tunnel_amd.models.tiny_llm import CONFIGS, LlamaConfig, TinyLlama
+from test_gpu_fused_stages import BF, F64, U, bf64, flip, gemm_ref, rope_tables, rounded, stage_attn, worst
+from test_gpu_qk_norm import RN
+from test_kv_fp8 import judge
+
+cuda = pytest.mark.skipif(not torch.cuda.is_available(), reason="needs a HIP device")
+gpu = pytest.mark.gpu
+
+F8 = torch.float8_e4m3fn
+NAN_BYTE = 0x7F
+EPS = 1e-5
+SCALING = RopeScaling("llama3", 8.0, 1.0, 4.0, 64)
+EPI = {"plain": 1 + 8, "bias": 5 + 8, "table": 6 + 8, "bias_table": 7 + 8, "qk_norm": 0, "qk_norm_table": 0}
+
+
+@dataclass(frozen=True)
+class Case:
+    kind: str
+    D: int
+    G: int
+    Hkv: int
+    rows: int
+    smax: int
+    plant: bool = False
+    seed: int = 0
+    dim: int = 64
+
+    @property
+    def name(self):
+        return (f"{self.kind}-D{self.D}-G{self.G}x{self.Hkv}-r{self.rows}-s{self.smax}"
+                + (f"-dim{self.dim}" if self.dim != 64 else "") + ("-planted" if self.plant else ""))
+
+    @property
+    def cfg(self):
+        return LlamaConfig(vocab=512, dim=self.dim, n_layers=1, n_heads=self.G * self.Hkv, n_kv_heads=self.Hkv,
+                           head_dim=self.D, ffn=64, max_seq=self.smax, eps=EPS, rope_theta=1e4,
+                           rope_scaling=SCALING if "table" in self.kind else None, qkv_bias="bias" in self.kind,
+                           qk_norm="qk_norm" in self.kind)
+
+
+# Every k_attn<D, G, true> once, on 1, 2, 3, 15 and 16 span slots (slots = min(256 / (rows Hkv), ceil(smax / 64),
+# 16)), rows 1, 16, 17 and 40 (one row tile, a full one, a second one, three), every epilogue and both
+# k_qknorm_rope variants at both head sizes.
+_C = [("plain", 64, 1, 2, 1, 64), ("plain", 128, 8, 1, 16, 1024), ("bias", 64, 7, 2, 17, 128),
+      ("bias", 128, 6, 1, 40, 96), ("table", 64, 4, 2, 40, 1024), ("table", 128, 4, 1, 17, 64),
+      ("bias_table", 64, 2, 2, 16, 128), ("bias_table", 128, 5, 1, 1, 1024), ("qk_norm", 64, 8, 1, 17, 1024),
+      ("qk_norm", 128, 2, 2, 40, 64), ("qk_norm_table", 64, 5, 2, 16, 128), ("qk_norm_table", 128, 1, 2, 1, 64),
+      ("plain", 64, 6, 1, 8, 1024), ("plain", 128, 7, 1, 4, 128)]
+CASES = [Case(*c, seed=i + 1) for i, c in enumerate(_C)]
+CASES += [Case(kind, (64, 128)[i % 2], 2, 2, 5, 64, plant=True, seed=40 + i) for i, kind in enumerate(EPI)]
+# The hidden size is 64 (two k-steps: k_skinny<4, 1, EPI, 1>): gemm_ref's E grows with K, and at 256 and above
+# the inner bf16 flips alone leave more than 1 % of a case undecided (2.6 % at 256, 15 % at 1024 on the CPU
+# emulation). The wider instantiations <4,1,.,2>, <4,1,.,4> and <8,1,.,4> differ from this one in the K loop, not
+# in the epilogue; <4,1,ROPE_KV8,2> runs in the model tests below (micro: dim 256).
+# Two seeds moved after the CPU emulation left 1.6 % and 1.2 % of their elements undecided (a one-row case has 256).
+CASES = [replace(c, seed={"bias_table-D128-G5x1-r1-s1024": 100, "bias-D128-G2x2-r5-s64-planted": 101}.get(c.name, c.seed))
+         for c in CASES]
+CASE_IDS = [c.name for c in CASES]
+SLOTS = {c.name: s for c, s in zip(CASES, (1, 16, 2, 2, 3, 1, 2, 16, 15, 1, 2, 1, 16, 2) + (1,) * 6)}
+
+
+def layout(case):
+    """(pos, slots): decode rows whose lengths are the cache's capacity, 31, 32, 33, a span's last token and the
+    first of the next span (64, 65) and 1, each on a slot of its own in descending slot order; then a prefill chunk
+    of up to 8 consecutive positions and a second chunk with the rest, on two more slots. One row alone has length
+    34; a planted case puts the first of its five rows at position 0."""
+    rows, smax = case.rows, case.smax
+    if case.plant:
+        return (0, 5, 9, 7, smax - 1), (4, 2, 0, 1, 3)
+    if rows == 1:
+        return (33,), (1,)
+    single = [p for p in (smax - 1, 30, 31, 32, 63, 64, 0) if p < smax][:min(rows, 7)]
+    n = len(single)
+    pos, slots = list(single), list(range(n - 1, -1, -1))
+    a = min(8, rows - n)
+    pos += list(range(20, 20 + a))
+    slots += [n + 1] * a
+    b = rows - len(pos)
+    pos += list(range(3, 3 + b))
+    slots += [n] * b
+    assert len(set(zip(slots, pos))) == rows and max(pos) < smax
+    return tuple(pos), tuple(slots)
+
+
+N_SLOTS = 9
+
+# (column within the head, value): exact plants of the bias families, pair-aligned (d and d + D/2 alike)
+PLANTS = (456.0, -460.0, 480.0, -3.0e4, 2.0 ** -8, -3 * 2.0 ** -11, 2.0 ** -12, -2.0 ** -12, float("nan"))
+
+
+def plant(m, case):
+    """Plants the value classes of the module docstring in K head 0 and V head 0 of the CPU model ``m``."""
+    c, L = case.cfg, m.layers[0]
+    H, D, half = c.n_heads, c.head_dim, c.head_dim // 2
+    k0, v0 = H * D, (H + c.n_kv_heads) * D
+    if c.qkv_bias:  # exact: W rows zero, the bias is the value
+        for j, val in enumerate(PLANTS):
+            for base in (k0, v0):
+                for d in (j, j + half):
+                    L["wqkv"][base + d] = 0
+                    L["bqkv"][base + d] = val
+        return
+    big, small, nan = range(0, 4), range(4, 8), (8,)
+    for base in ((v0,) if c.qk_norm else (k0, v0)):
+        for d in [*big, *small, *nan]:
+            for dd in (d, d + half):
+                f = 256.0 if d in big else 2.0 ** -9 if d in small else float("nan")
+                L["wqkv"][base + dd] = (L["wqkv"][base + dd].float() * f).to(BF)
+    if c.qk_norm:
+        for d in [*big, *small, *nan]:
+            for dd in (d, d + half):
+                L["k_norm"][dd] = 512.0 if d in big else 2.0 ** -9 if d in small else float("nan")
+
+
+@dataclass
+class Inputs:
+    model: TinyLlama  # on the CPU
+    weights: list
+    tokens: torch.Tensor
+    pos: torch.Tensor
+    slots: torch.Tensor
+    kc0: torch.Tensor  # uint8 [N_SLOTS + 1, smax, Hkv, D]: the cache before the step
+    vc0: torch.Tensor
+
+
+@functools.lru_cache(maxsize=None)
+def inputs(case) -> Inputs:
+    """Seeded inputs of a case, made once and shared (never modified). The caches hold e4m3 bytes of N(0, 2.5) K
+    and N(0, 1) V values up to each slot's length and NaN bytes (0x7f) beyond it and in unused slots."""
+    m = TinyLlama(case.cfg, device="cpu", max_batch=N_SLOTS, seed=case.seed, kv_dtype="fp8")
+    if case.plant:
+        plant(m, case)
+    g = torch.Generator().manual_seed(1000 + case.seed)
+    shape = tuple(m.k_cache.shape[1:])
+    kc0 = (torch.randn(shape, generator=g) * 2.5).to(F8).view(torch.uint8)
+    vc0 = torch.randn(shape, generator=g).to(F8).view(torch.uint8)
+    pos, slots = layout(case)
+    length = [0] * shape[0]
+    for p, s in zip(pos, slots):
+        length[s] = max(length[s], p + 1)
+    for s, n in enumerate(length):
+        kc0[s, n:] = NAN_BYTE
+        vc0[s, n:] = NAN_BYTE
+    tokens = torch.randint(0, case.cfg.vocab, (case.rows,), generator=g)
+    return Inputs(m, m.fused_weights(), tokens, torch.tensor(pos, dtype=torch.int32),
+                  torch.tensor(slots, dtype=torch.int32), kc0, vc0)
+
+
+# ---------------------------------------------------------------- fp64 references of the appended rows
+def angles(cfg, pos, table):
+    if table is None:
+        return rope_tables(cfg, pos)
+    from test_llama3_rope import table_angles
+    return table_angles(pos, table)
+
+
+def rotate(x1, x2, f1, f2, e_rel, cs, sn, dsc):
+    """The rotated pair (o1 | o2) in fp64 and the error bound before the last rounding."""
+    o1, o2 = x1 * cs - x2 * sn, x2 * cs + x1 * sn
+    common = (x1.abs() + x2.abs()) * dsc
+    E1 = f1 * cs.abs() + f2 * sn.abs() + common + e_rel * ((x1 * cs).abs() + (x2 * sn).abs())
+    E2 = f2 * cs.abs() + f1 * sn.abs() + common + e_rel * ((x2 * cs).abs() + (x1 * sn).abs())
+    return torch.cat([o1, o2], -1), torch.cat([E1, E2], -1)
+
+
+def appended_reference(case, W, x0, pos, raw):
+    """(q, bound) and (x, e_pre) of the appended K and V rows [M, heads, D], per the module docstring. ``raw``: the
+    observed bf16 projection of a QK-norm model."""
+    c = case.cfg
+    H, Hkv, D, half = c.n_heads, c.n_kv_heads, c.head_dim, c.head_dim // 2
+    g0 = 3 + int(c.rope_scaling is not None)
+    table = W[3] if c.rope_scaling is not None else None
+    cs, sn, dsc = angles(c, pos, table)
+    if c.qk_norm:
+        x = raw.view(-1, H + 2 * Hkv, D)
+        xd = x[:, :H + Hkv].to(F64)
+        g = torch.cat([W[g0 + 6].to(F64).expand(H, D), W[g0 + 7].to(F64).expand(Hkv, D)])[None]
+        n = xd * torch.rsqrt(xd.pow(2).mean(-1, keepdim=True) + c.eps) * g
+        zero = torch.zeros_like(n[..., :half])
+        o, E = rotate(n[..., :half], n[..., half:], zero, zero, RN + 3 * U, cs, sn, dsc)
+        v = x[:, H + Hkv:].to(F64)
+        return (o[:, :H], rounded(o, E)[:, :H]), (o[:, H:], E[:, H:]), (v, torch.zeros_like(v))
+    y, E = gemm_ref(x0, W[g0 + 1], c.eps)
+    if c.qkv_bias:
+        y = y + W[g0 + 6].to(F64)[None, :]
+        E = E + U * y.abs()
+    M = y.shape[0]
+    y, E = y.view(M, H + 2 * Hkv, half, 2), E.view(M, H + 2 * Hkv, half, 2)  # pairs (dim i, dim i + D/2)
+    v = torch.cat([y[:, H + Hkv:, :, 0], y[:, H + Hkv:, :, 1]], -1)
+    vE = torch.cat([E[:, H + Hkv:, :, 0], E[:, H + Hkv:, :, 1]], -1)
+    ry, rE = y[:, :H + Hkv], E[:, :H + Hkv]
+    o, Eo = rotate(bf64(ry[..., 0]), bf64(ry[..., 1]), flip(ry[..., 0], rE[..., 0]), flip(ry[..., 1], rE[..., 1]),
+                   3 * U, cs, sn, dsc)
+    return (o[:, :H], rounded(o, Eo)[:, :H]), (o[:, H:], Eo[:, H:]), (v, vE)
+
+
+def judge_rows(ref_e, got):
+    x, e = ref_e
+    e = torch.where(torch.isnan(x) | torch.isnan(e), torch.zeros_like(e), e)
+    return judge(x.numpy(), e.numpy(), got.numpy().reshape(x.shape))
+
+
+def decoded(b):
+    return b.view(F8).float()
+
+
+@cuda
+@gpu
+@pytest.mark.parametrize("case", CASES, ids=CASE_IDS)
+def test_appended_rows_and_attention_match_fp64(case):
+    inp = inputs(case)
+    c, B = case.cfg, case.rows
+    src = inp.model
+    w = dict(embed=src.embed.cuda(), final_norm=src.final_norm.cuda(), lm_head=src.lm_head.cuda(),
+             layers=[{k: v.cuda() for k, v in L.items()} for L in src.layers])
+    m = TinyLlama.from_weights(c, w, device="cuda", max_batch=N_SLOTS, kv_dtype="fp8")
+    assert m.k_cache.dtype == F8 and m.k_cache.element_size() == 1
+    dec = m.fused_decoder()
+    for a, b in zip(dec.weights, inp.weights):  # the decoder's own table is what the references use
+        # (a planted NaN weight may carry another payload after the device's fold: NaN against NaN is a match)
+        assert torch.equal(a.cpu().float().nan_to_num(nan=4096.0), b.float().nan_to_num(nan=4096.0))
+    plan = ops.step_plan(dec.dims, B)
+    kv = ops.kv_plan(dec.dims)
+    assert plan.qkv.epi == plan.qkv_first.epi == EPI[case.kind] and kv.qk_norm_kv8 == int(c.qk_norm)
+    assert (kv.attn_kv8, plan.attn.D, plan.attn.G, plan.attn.slots) == (1, case.D, case.G, SLOTS[case.name])
+    assert plan.qk_norm_table == int(case.kind == "qk_norm_table")
+    m.k_cache[0].view(torch.uint8).copy_(inp.kc0)
+    m.v_cache[0].view(torch.uint8).copy_(inp.vc0)
+    pos = inp.pos.tolist()
+    m.decode_step(inp.tokens.cuda(), inp.pos.cuda(), (min(pos), max(pos)), slots=inp.slots.cuda())
+    torch.cuda.synchronize()
+    views = dec.workspace_views()
+    q, attn, raw = views["q"][:B].cpu(), views["attn"][:B].cpu(), views["qkv"][:B].cpu()
+    kc, vc = m.k_cache[0].view(torch.uint8).cpu(), m.v_cache[0].view(torch.uint8).cpu()
+
+    sl, ps = inp.slots.long(), inp.pos.long()
+    qr, kr, vr = appended_reference(case, inp.weights, inp.weights[0][inp.tokens], inp.pos, raw)
+    out = {"q": worst(q, qr)}
+    open_share = 0.0
+    for name, r, got in (("k", kr, kc[sl, ps]), ("v", vr, vc[sl, ps])):
+        ratio, wrong, undecided = judge_rows(r, got)
+        out[name] = (round(ratio, 3), wrong, round(undecided, 5))
+        open_share += undecided / 2  # K and V have the same number of elements
+        assert ratio <= 1.0 and wrong == 0, (name, out)
+    assert open_share <= 0.01, out  # at most 1 % of the case's appended elements undecided
+    # Both caches whole: nothing outside the appended rows changed (NaN bytes beyond every length included).
+    for got, before in ((kc, inp.kc0), (vc, inp.vc0)):
+        same = got == before
+        same[sl, ps] = True
+        assert bool(same.all())
+    if case.plant:
+        x = torch.cat([kr[0][:1].flatten(), vr[0].flatten()])  # the K row at position 0, every V row
+        a = x.abs()
+        assert bool(x.isnan().any()) and bool((a > 464).any()) and bool(((a > 0) & (a < 2.0 ** -6)).any())
+        assert bool(((a > 0) & (a < 2.0 ** -10)).any())  # rounds to a zero that keeps its sign
+        if c.qkv_bias:
+            assert bool(((a > 448) & (a < 464)).any())
+    else:
+        ar = stage_attn(SimpleNamespace(cfg=c), q, decoded(kc), decoded(vc), inp.pos, inp.slots)
+        out["attn"] = worst(attn, ar)
+        assert out["attn"] <= 1.0, out
+    print("RATIO kv8", case.name, out)
+    assert out["q"] <= 1.0, out
+
+
+# ---------------------------------------------------------------- graph replay, the model, the engine
+MICRO = CONFIGS["micro"]
+N_NEW = 6
+# The fused step's logits stay within 5 % of the largest logit of the fp32 reference for every family
+# (test_gpu_qk_norm.py, test_gpu_qwen2.py); with an FP8 cache the reference rounds K and V the same way, and what
+# remains on top is single K / V elements that land on the other e4m3 neighbour (2^-3 relative, one element of
+# D n), far inside that. A token is decided when the reference's top-2 gap exceeds the bound.
+LOGIT_BOUND = 0.05
+
+
+def _ids(seed, n, vocab=4096):
+    rng = random.Random(seed)
+    return [rng.randrange(vocab) for _ in range(n)]
+
+
+def reference_generation(m, prompt, n):
+    """Greedy continuation under the CPU fp32 reference of ``m`` (its own cache format) and the smallest top-2 gap /
+    max|logit| over the generated tokens."""
+    seq, margin = list(prompt), math.inf
+    for _ in range(n):
+        lg = m.reference_logits(torch.tensor([seq]))[0]
+        top = lg.topk(2).values
+        margin = min(margin, float(top[0] - top[1]) / float(lg.abs().max()))
+        seq.append(int(lg.argmax()))
+    return seq[len(prompt):], margin
+
+
+# Prompts searched on the CPU for a margin above LOGIT_BOUND at every generated token under the FP8 reference of
+# micro, seed 0: 37 tokens, one token, 71 tokens (more than one 64-row step). ``reference_generation`` re-checks.
+PROMPT_SEEDS = ((257, 37), (466, 1), (267, 71))  # margins 0.076, 0.072, 0.101
+
+
+@functools.lru_cache(maxsize=None)
+def confident_prompts():
+    ref = TinyLlama(MICRO, device="cpu", max_batch=1, seed=0, kv_dtype="fp8")
+    out = []
+    for seed, n in PROMPT_SEEDS:
+        prompt = _ids(seed, n)
+        want, margin = reference_generation(ref, prompt, N_NEW)
+        assert margin > LOGIT_BOUND, (seed, margin)  # every compared token is decided; none is skipped
+        out.append((prompt, want))
+    return out
+
+
+@cuda
+@gpu
+def test_fp8_model_generates_the_reference_tokens():
+    m = TinyLlama(MICRO, device="cuda", max_batch=1, seed=0, kv_dtype="fp8")
+    half = TinyLlama(MICRO, device="cuda", max_batch=1, seed=0)
+    assert m.k_cache.element_size() == 1 and 2 * m.k_cache.nbytes == half.k_cache.nbytes
+    for prompt, want in confident_prompts():
+        assert m.generate(list(prompt), N_NEW) == want, len(prompt)
+    with pytest.raises(ValueError, match="fused step only"):
+        TinyLlama(MICRO, device="cuda", max_batch=1, kv_dtype="fp8", fused=False).decode_step(
+            torch.tensor([1], device="cuda"), torch.tensor([0], dtype=torch.int32, device="cuda"), (0, 0))
+
+
+@cuda
+@gpu
+def test_fp8_graph_replay_equals_eager_bit_for_bit():
+    torch.manual_seed(3)
+    m = TinyLlama(MICRO, device="cuda", max_batch=4, seed=2, kv_dtype="fp8")
+    for c in (m.k_cache, m.v_cache):
+        c.copy_(torch.randn(c.shape, device="cuda").to(F8))
+    m.capture_graph(rows=4)
+    toks = torch.randint(0, MICRO.vocab, (4,), device="cuda")
+    pos = torch.tensor([5, 130, 0, 300], dtype=torch.int32, device="cuda")
+    kc, vc = m.k_cache.clone(), m.v_cache.clone()
+    ids_g, logits_g = m.graph_step(toks, pos, return_logits=True)
+    ids_g, logits_g, kg, vg = ids_g.clone(), logits_g.clone(), m.k_cache.clone(), m.v_cache.clone()
+    m.k_cache.copy_(kc)
+    m.v_cache.copy_(vc)
+    ids_e, logits_e = m.decode_step(toks, pos, (0, 300), return_logits=True)
+    assert torch.equal(ids_g, ids_e) and torch.equal(logits_g.view(torch.int16), logits_e.view(torch.int16))
+    assert torch.equal(kg.view(torch.uint8), m.k_cache.view(torch.uint8))
+    assert torch.equal(vg.view(torch.uint8), m.v_cache.view(torch.uint8))
+    assert not torch.equal(kg.view(torch.uint8), kc.view(torch.uint8))  # the step appended
+
+
+def collect(req):
+    out = []
+    while (t := req.out.get(timeout=60)) is not None:
+        out.append(t)
+    return out
+
+
+@cuda
+@gpu
+def test_engine_serves_an_fp8_model():
+    from p2p_llm_tunnel_amd.models.server import Engine, Request, Sampling
+    eng = Engine(device="cuda:0", config="micro", max_batch=4, seed=0, prefix_cache=True, kv_dtype="fp8")
+    try:
+        m = eng.model
+        assert len(eng._graphs) == 12 and m.kv_dtype == "fp8" and m.k_cache.dtype == F8
+        prompts = confident_prompts()
+        # one by one (the prefix cache reuses a slot in place where prompts share a start), then all at once
+        for prompt, want in prompts:
+            assert collect(eng.submit(Request(list(prompt), N_NEW))) == want
+        reqs = [eng.submit(Request(list(prompt), N_NEW)) for prompt, want in prompts]
+        assert [collect(r) for r in reqs] == [want for _, want in prompts]
+        # a shared prefix copied from a slot that is still generating: the copied rows are the source's, bit for bit
+        long, want = prompts[2]
+        copies = eng.kv_copies
+        bg = eng.submit(Request(list(long) + [5, 6, 7], 200))
+        bg.out.get(timeout=60)
+        r = eng.submit(Request(list(long), N_NEW))
+        assert collect(r) == want and r.cached_tokens >= 64 and eng.kv_copies == copies + 1
+        torch.cuda.synchronize()
+        src = next(i for i, s in enumerate(eng._kv) if s is bg.kv)
+        dst = next(i for i, s in enumerate(eng._kv) if s is r.kv)
+        n = r.cached_tokens
+        assert src != dst
+        assert torch.equal(m.k_cache[:, dst, :n].view(torch.uint8), m.k_cache[:, src, :n].view(torch.uint8))
+        assert torch.equal(m.v_cache[:, dst, :n].view(torch.uint8), m.v_cache[:, src, :n].view(torch.uint8))
+        bg.cancelled = True
+        # a sampled request with logprobs: the sampler and the logprobs kernel follow the FP8 step in its graph
+        s = eng.submit(Request(list(prompts[0][0]), N_NEW, sampling=Sampling(temperature=0.8, top_p=0.9, seed=7),
+                               logprobs=3))
+        toks = collect(s)
+        assert len(toks) == N_NEW and all(0 <= t < MICRO.vocab for t in toks)
+        assert len(s.lp) == N_NEW and all(math.isfinite(lp[0]) and lp[0] <= 0.0 and len(lp[1]) == 3 for lp in s.lp)
+    finally:
+        eng.stop()
+
+
+@cuda
+@gpu
+def test_endpoint_serves_a_checkpoint_with_an_fp8_cache(tmp_path):
+    from test_checkpoint import _tokenizer_dir
+    from test_gpu_qwen2 import SERVED_MESSAGES, SERVED_NEW, SERVED_SEED
+    from test_qwen2_checkpoint import qwen2_checkpoint
+    from p2p_llm_tunnel_amd.models.checkpoint import Tokenizer, load_llama
+    from p2p_llm_tunnel_amd.models.server import start_server
+    qwen2_checkpoint(str(tmp_path), tie=True, seed=SERVED_SEED)
+    _tokenizer_dir(str(tmp_path))
+    tok = Tokenizer(str(tmp_path))
+    ref = load_llama(str(tmp_path), device="cpu", max_batch=1, max_seq=256, kv_dtype="fp8")
+    prompt = tok.chat(SERVED_MESSAGES)
+    new, margin = reference_generation(ref, prompt, SERVED_NEW)
+    assert margin > LOGIT_BOUND and not set(new) & tok.eos_ids, (new, margin)
+    srv, port, eng = start_server(port=0, device="cuda:0", max_batch=2, checkpoint=str(tmp_path), max_seq=256,
+                                  kv_dtype="fp8")
+    bf = load_llama(str(tmp_path), device="cpu", max_batch=2, max_seq=256)
+    try:
+        assert eng.use_graph and len(eng._graphs) == 12 and eng.model.cfg.qkv_bias
+        assert eng.model.k_cache.element_size() == 1 and 2 * eng.model.kv_cache_bytes() == bf.kv_cache_bytes()
+        c = http.client.HTTPConnection("127.0.0.1", port, timeout=60)
+        c.request("POST", "/v1/chat/completions", body=json.dumps(
+            {"stream": True, "max_tokens": SERVED_NEW, "messages": SERVED_MESSAGES}))
+        r = c.getresponse()
+        data = r.read()
+        assert r.status == 200 and data.rstrip().endswith(b"data: [DONE]")
+        objs = [json.loads(l[6:]) for l in data.split(b"\n") if l.startswith(b"data: {")]
+        text = "".join(o["choices"][0]["delta"].get("content", "") for o in objs)
+        assert text == tok.decode(new).rstrip("�"), (text, new)
+    finally:
+        srv.shutdown()
+        eng.stop()
