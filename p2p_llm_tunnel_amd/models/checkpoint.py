@@ -337,3 +337,61 @@ class Tokenizer:
 
     def detokenizer(self, prompt_ids: list[int]) -> Detokenizer:
         return Detokenizer(self.tok, prompt_ids)
+
+    def token_bytes(self) -> list[bytes]:
+        """The bytes every id adds to the text, by id (guided decoding walks
+        them through its automaton; ``models/guided.py``). Special (control)
+        tokens and ids the vocabulary leaves unused give b"": they never take
+        part in a guided completion. Two kinds of vocabulary are understood:
+        ByteLevel BPE (Llama 3, Qwen: every character of a token stands for one
+        byte, by the GPT-2 byte table, inverted here) and Metaspace /
+        byte-fallback vocabularies (Llama 2, Mistral: U+2581 stands for a space,
+        ``<0xNN>`` for the byte NN). Any other kind raises ValueError. Computed
+        once."""
+        got = getattr(self, "_token_bytes", None)
+        if got is not None:
+            return got
+        spec = json.loads(self.tok.to_str())
+        model = spec.get("model") or {}
+
+        def kinds(node):
+            if not isinstance(node, dict):
+                return set()
+            out = {node.get("type")}
+            for sub in node.get("decoders") or node.get("pretokenizers") or []:
+                out |= kinds(sub)
+            return out
+        used = kinds(spec.get("decoder")) | kinds(spec.get("pre_tokenizer"))
+        if model.get("type") == "BPE" and "ByteLevel" in used:
+            # The GPT-2 table: printable bytes stand for themselves, the rest are numbered from U+0100 up.
+            keep = list(range(33, 127)) + list(range(161, 173)) + list(range(174, 256))
+            table, n = {chr(b): b for b in keep}, 0
+            for b in range(256):
+                if b not in keep:
+                    table[chr(256 + n)] = b
+                    n += 1
+
+            def to_bytes(text):
+                return bytes(table[c] for c in text) if all(c in table for c in text) else None
+        elif model.get("type") in ("BPE", "Unigram") and ("Metaspace" in used or model.get("byte_fallback")):
+            def to_bytes(text):
+                if len(text) == 6 and text.startswith("<0x") and text.endswith(">"):
+                    try:
+                        return bytes([int(text[3:5], 16)])
+                    except ValueError:
+                        pass
+                return text.replace("▁", " ").encode("utf-8")
+        else:
+            raise ValueError(f"guided decoding understands ByteLevel BPE and Metaspace / byte-fallback tokenizers; "
+                             f"this one is a {model.get('type')!r} model with {sorted(k for k in used if k)}")
+        added = {a["id"]: a for a in spec.get("added_tokens") or []}
+        vocab = self.tok.get_vocab(with_added_tokens=True)
+        out = [b""] * (max(vocab.values()) + 1 if vocab else 0)
+        for text, tid in vocab.items():
+            a = added.get(tid)
+            if a is not None:  # an added token is literal text; a special one is control
+                out[tid] = b"" if a.get("special") else a.get("content", "").encode("utf-8")
+            else:
+                out[tid] = to_bytes(text) or b""
+        self._token_bytes = out
+        return out

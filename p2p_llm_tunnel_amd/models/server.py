@@ -50,6 +50,23 @@ is added last, and greedy requests take the argmax of the result. n > 1,
 best_of, mirostat, tfs_z, typical_p and min_p stay refused. See
 docs/PENALTIES.md.
 
+Guided decoding (--guided, off by default: the keys below are then not acted
+on): /v1/chat/completions and /v1/completions take "guided_regex" (a string:
+the whole completion matches it), "guided_choice" (a non-empty list of
+non-empty strings: the completion is one of them) or the newer
+"structured_outputs": {"regex": ...} / {"choice": [...]}; more than one of
+them, a wrong type, a pattern outside the supported subset, a server without a
+tokenizer or with one whose tokens' bytes are not known are answered with 400
+and the reason. The pattern is compiled off the I/O thread (an executor; a small
+LRU of compiled guides) into a token-level automaton (models/guided.py) whose
+table the engine keeps in a device arena; ops.guide_ (guide.hip) walks it
+inside the captured step, after the penalties and ahead of the sampler, and
+masks every token the automaton's state does not allow. A completion that
+reaches a full match with nothing left to add ends through EOS (finish_reason
+"stop"); one cut by max_tokens ends with "length" and may be an incomplete
+match. "response_format", JSON schemas, Ollama's "format" and grammars that
+need a stack are out of scope. See docs/GUIDED.md.
+
 Chat template variables: a chat request's optional "chat_template_kwargs", a
 JSON object of scalars, is handed to the checkpoint's chat template
 ({"enable_thinking": false} for Qwen3's); anything else is answered with 400.
@@ -296,6 +313,49 @@ def sampling_params(body: dict, ollama: bool, default_temperature: float = 0.0, 
     return Sampling(t, top_k, top_p, seed)
 
 
+_GUIDE_KEYS = ("guided_regex", "guided_choice", "structured_outputs")
+
+
+def guided_params(body: dict):
+    """What a request on a server started with --guided asks its completion to
+    match: None, or ``(kind, pattern)`` for ``guided.compile_guide``: ("regex",
+    a string) from "guided_regex" or "structured_outputs": {"regex": ...},
+    ("choice", a tuple of non-empty strings) from "guided_choice" or
+    "structured_outputs": {"choice": [...]}. A null value counts as absent.
+    More than one of them, or a wrong type, raises SamplingError (answered with
+    400) naming the key. The pattern itself is checked by the compiler."""
+    found = []
+    v = body.get("guided_regex")
+    if v is not None:
+        found.append(("guided_regex", "regex", v))
+    v = body.get("guided_choice")
+    if v is not None:
+        found.append(("guided_choice", "choice", v))
+    so = body.get("structured_outputs")
+    if so is not None:
+        if not isinstance(so, dict):
+            raise SamplingError(f"structured_outputs must be an object, got {so!r}")
+        other = sorted(k for k, x in so.items() if k not in ("regex", "choice") and x is not None)
+        if other:
+            raise SamplingError(f"structured_outputs.{other[0]} is not supported by this server: it takes "
+                                '"regex" and "choice"')
+        for k in ("regex", "choice"):
+            if so.get(k) is not None:
+                found.append((f"structured_outputs.{k}", k, so[k]))
+    if not found:
+        return None
+    if len(found) > 1:
+        raise SamplingError(f"{found[0][0]} and {found[1][0]} cannot be combined: a request takes one guide")
+    name, kind, v = found[0]
+    if kind == "regex":
+        if not isinstance(v, str):
+            raise SamplingError(f"{name} must be a string, got {v!r}")
+        return kind, v
+    if not isinstance(v, list) or not v or not all(isinstance(c, str) and c for c in v):
+        raise SamplingError(f"{name} must be a non-empty list of non-empty strings, got {v!r}")
+    return kind, tuple(v)
+
+
 _LEGACY_MAX_LOGPROBS = 5  # /v1/completions: the OpenAI API's limit for the legacy integer form
 _LOGPROB_KEYS = ("logprobs", "top_logprobs")
 
@@ -445,12 +505,23 @@ class Request:
     ``embedding`` holds the pooled, L2-normalised final hidden state (float32,
     ``dim`` values; the mean over all positions, or the last position's).
     ``penalties``: a ``Penalties`` (None, or a neutral one, is off); needs an
-    engine built with ``penalties=True``, and an embedding request takes none."""
+    engine built with ``penalties=True``, and an embedding request takes none.
+    ``guide``: a ``guided.Guide`` compiled for the model's vocabulary (None is
+    off): every token is then one the guide's automaton allows; needs an engine
+    built with ``guided=True``, and an embedding request takes none."""
 
     def __init__(self, prompt_ids: list[int], max_new: int, batched: bool = False, sampling: Sampling | None = None,
-                 logprobs: int | None = None, embed: str | None = None, penalties: Penalties | None = None):
+                 logprobs: int | None = None, embed: str | None = None, penalties: Penalties | None = None,
+                 guide=None):
         if embed not in (None, "mean", "last"):
             raise ValueError(f'embed must be None, "mean" or "last", got {embed!r}')
+        if guide is not None:
+            from p2p_llm_tunnel_amd.models.guided import Guide
+            if not isinstance(guide, Guide):
+                raise TypeError(f"guide must be a guided.Guide, got {guide!r}")
+            if embed is not None:
+                raise ValueError("an embedding request samples nothing and takes no guide")
+        self.guide = guide
         if penalties is not None and not isinstance(penalties, Penalties):
             raise TypeError(f"penalties must be a Penalties, got {penalties!r}")
         if penalties is not None and penalties.neutral:
@@ -622,10 +693,30 @@ class Engine:
     Admission of such a request queues ``ops.penalty_reset_`` for its slot
     ahead of its first step (``_pen_reset``), whether its prompt's head runs,
     is reused in place or is copied: the prompt bits come from the prompt ids.
+
+    ``guided`` (off by default, like ``penalties``) serves ``Request(guide=)``:
+    guided decoding, see docs/GUIDED.md. The engine keeps one device arena of
+    ``guided_states`` token-table rows (int16 [guided_states, V]), per cache
+    slot the arena row its request's table starts at (``_gd_base``, -1 = not
+    guided) and the automaton's state (``_gd_cur``), and captures one more
+    ``post`` per (R, par): 4 runs ``ops.penalize_`` (an engine with penalties),
+    then ``ops.guide_`` (guide.hip), which advances the slot's state by the
+    row's input token, masks what the state does not allow to -inf in ``work``
+    and replaces the greedy id by the argmax of the masked row, then the sampler
+    on ``work`` and the logprobs kernel on the RAW logits. A step replays post 4
+    when an emitting row's request is guided; rows of other requests are off
+    there. Tables are shared between requests with the same pattern, stay
+    resident after their last request and are evicted least recently used when
+    room is needed; a request whose table does not fit while others are in use
+    waits at the head of the admission queue. Admission queues
+    ``ops.guide_reset_`` for the slot ahead of the request's first step
+    (``_gd_bind``), and also when a request without a guide takes a slot whose
+    last request had one.
     """
 
     def __init__(self, device="cuda:0", config="tiny", max_batch=8, seed=0, use_graph=True, rows=64, model=None,
-                 small_rows=16, prefix_cache=False, prefix_min=16, penalties=False, kv_dtype="bf16"):
+                 small_rows=16, prefix_cache=False, prefix_min=16, penalties=False, kv_dtype="bf16",
+                 guided=False, guided_states=1024):
         if model is None:
             from p2p_llm_tunnel_amd.models.tiny_llm import TinyLlama
             model = TinyLlama(config, device=device, max_batch=max_batch, seed=seed, fused=True, kv_dtype=kv_dtype)
@@ -659,21 +750,29 @@ class Engine:
         # An FP8 cache is read and written by the fused HIP step alone: refused on the eager engine, like sampling.
         if getattr(model, "kv_dtype", "bf16") != "bf16" and not use_graph:
             raise ValueError("an fp8 KV cache needs the graph-captured HIP step; this engine runs eagerly")
+        if guided and not use_graph:
+            raise ValueError("guided decoding needs the graph-captured HIP step; this engine runs eagerly")
         self.penalties = bool(penalties)
+        self.guided = bool(guided)
+        self._held = None  # a guided request that waits for room in the arena (the head of the admission queue)
         in_rows = _PEN.stop if self.penalties else _IN_ROWS
         self._bufs = {R: [_StepBuf(R, cuda, lp_dev, in_rows), _StepBuf(R, cuda, lp_dev, in_rows)] for R in sizes}
         self._d_in = {R: torch.zeros((in_rows, R), dtype=torch.int64, device=self.device) for R in sizes}
         if self.penalties:
             self._pen_alloc(max_batch, {R: (R if R == small_rows else max_batch) for R in sizes})
+        if self.guided:
+            self._gd_alloc(max_batch, {R: (R if R == small_rows else max_batch) for R in sizes}, guided_states)
         # Each graph holds the whole step (_step_body), one per staging buffer
         # of the pair, so a step is one replay. What follows the fused step is
         # the graph's ``post``: 0 nothing (all-greedy steps), 1 the sampler
         # (some row samples), 2 the sampler, then the logprobs kernel and its
         # two copies back (some emitting row's request has logprobs set); with
-        # ``penalties`` also 3: penalize_, the sampler on its output, logprobs_.
+        # ``penalties`` also 3: penalize_, the sampler on its output, logprobs_;
+        # with ``guided`` also 4: (penalize_,) guide_, the sampler on its
+        # output, logprobs_.
         self._graphs = {(R, par, post): self._capture(self._bufs[R][par], 0 if R == small_rows else max_batch, post)
                         for R in sizes if use_graph for par in (0, 1)
-                        for post in ((0, 1, 2, 3) if self.penalties else (0, 1, 2))}
+                        for post in (0, 1, 2) + ((3,) if self.penalties else ()) + ((4,) if self.guided else ())}
         self.max_batch = max_batch
         self.pending: queue.Queue = queue.Queue()
         self.slots: list[dict | None] = [None] * max_batch
@@ -712,6 +811,16 @@ class Engine:
                              "graph-captured HIP step")
         if req.penalties is not None and any(t >= self.model.cfg.vocab for t in req.penalties.logit_bias):
             raise ValueError(f"logit_bias ids must be in [0, {self.model.cfg.vocab})")
+        if req.guide is not None:
+            if not self.guided:
+                raise ValueError("a guide needs an engine built with guided=True (--guided) on the graph-captured "
+                                 "HIP step")
+            if req.guide.vocab != self.model.cfg.vocab:
+                raise ValueError(f"the guide was compiled for a vocabulary of {req.guide.vocab}, the model has "
+                                 f"{self.model.cfg.vocab}")
+            if req.guide.n_states > self._gd_arena.shape[0]:
+                raise ValueError(f"the guide has {req.guide.n_states} states, the arena holds "
+                                 f"{self._gd_arena.shape[0]} (--guided-states)")
         self.pending.put(req)
         self._wake.set()
         return req
@@ -773,6 +882,125 @@ class Engine:
         ops.penalty_reset_(self._pen_state, slot, d[:n], self._pen_bias_n, self._pen_bias_ids, self._pen_bias_val,
                            d[n:].view(2, k) if k else None)
 
+    _GD_STAGE_BYTES = 4 << 20  # pinned staging of a table upload, two of them
+
+    def _gd_alloc(self, max_batch: int, sample_rows: dict, states: int):
+        """Device state of ``guided`` and the staging of table uploads."""
+        from p2p_llm_tunnel_amd.models.guided import MAX_STATES
+        cfg, dev = self.model.cfg, self.device
+        if isinstance(states, bool) or not isinstance(states, int) or not 1 <= states <= MAX_STATES:
+            raise ValueError(f"guided_states must be an integer in 1..{MAX_STATES}, got {states!r}")
+        self._gd_arena = torch.full((states, cfg.vocab), -1, dtype=torch.int16, device=dev)
+        self._gd_base = torch.full((max_batch + 1,), -1, dtype=torch.int32, device=dev)
+        self._gd_cur = torch.zeros(max_batch + 1, dtype=torch.int32, device=dev)
+        if not hasattr(self, "_work"):  # an engine with penalties masks their output in place
+            self._work = {R: torch.zeros((n, cfg.vocab), dtype=torch.bfloat16, device=dev)
+                          for R, n in sample_rows.items()}
+        # Uploads go through pinned memory in pieces of whole table rows. The
+        # pinned side must not be rewritten while a queued copy may still read
+        # it. Unlike a penalty reset, an upload is rare (only a pattern that is
+        # not resident) and large, so nothing is derived from the order of the
+        # loop's passes here: each of the two stagings has an event, recorded
+        # behind the copy that reads it, and the engine waits for it before it
+        # writes that staging again. The wait is for copies queued behind at
+        # most the two steps in flight.
+        per = max(1, self._GD_STAGE_BYTES // (2 * cfg.vocab))
+        self._gd_stage = [torch.zeros((per, cfg.vocab), dtype=torch.int16, pin_memory=True) for _ in (0, 1)]
+        self._gd_stage_ev = [None, None]
+        self._gd_turn = 0
+        self._gd_tables: dict = {}  # key -> [first arena row, rows, requests holding it, tick of last use]
+        self._gd_slot: list = [None] * max_batch  # (key, req) of the guided request a slot holds
+        self._gd_on = [False] * max_batch  # the device's base[slot] is >= 0
+        self._gd_tick = 0
+        self.guide_uploads = 0  # tables copied into the arena
+        self.guide_shared = 0  # guided requests that found their table resident
+
+    def _gd_release(self):
+        """Give back the tables of slots whose guided request has left."""
+        for i, held in enumerate(self._gd_slot):
+            if held is not None and (self.slots[i] is None or self.slots[i]["req"] is not held[1]):
+                self._gd_tables[held[0]][2] -= 1
+                self._gd_slot[i] = None
+
+    def _gd_room(self, n: int, held_only: bool = False):
+        """First arena row of a gap of ``n`` rows between the resident tables
+        (``held_only``: between those a request holds, as if every idle one
+        were gone), or None."""
+        at = 0
+        for first, rows, held, _ in sorted(self._gd_tables.values()):
+            if held_only and not held:
+                continue
+            if first - at >= n:
+                return at
+            at = first + rows
+        return at if self._gd_arena.shape[0] - at >= n else None
+
+    def _gd_reserve(self, req: Request) -> bool:
+        """Make ``req``'s table resident and count the request as holding it;
+        False when it does not fit beside the tables that requests hold now.
+        Tables nobody holds are evicted least recently used first, and only
+        when evicting them can make the room. What a new
+        table overwrites was last read by steps queued ahead of the upload."""
+        g = req.guide
+        self._gd_tick += 1
+        t = self._gd_tables.get(g.key)
+        if t is not None:
+            t[2] += 1
+            t[3] = self._gd_tick
+            self.guide_shared += 1
+            return True
+        at = self._gd_room(g.n_states)
+        if at is None and self._gd_room(g.n_states, held_only=True) is None:
+            return False  # not even without the idle tables: they stay resident for the requests that come back
+        while at is None:
+            idle = [k for k, v in self._gd_tables.items() if v[2] == 0]
+            del self._gd_tables[min(idle, key=lambda k: self._gd_tables[k][3])]
+            at = self._gd_room(g.n_states)
+        per = self._gd_stage[0].shape[0]
+        for r0 in range(0, g.n_states, per):
+            n = min(per, g.n_states - r0)
+            turn = self._gd_turn
+            self._gd_turn ^= 1
+            if self._gd_stage_ev[turn] is not None:
+                self._gd_stage_ev[turn].synchronize()
+            h = self._gd_stage[turn]
+            h.numpy()[:n] = g.next[r0:r0 + n]
+            self._gd_arena[at + r0:at + r0 + n].copy_(h[:n], non_blocking=True)
+            ev = self._gd_stage_ev[turn] = self._gd_stage_ev[turn] or torch.cuda.Event()
+            ev.record()
+        self._gd_tables[g.key] = [at, g.n_states, 1, self._gd_tick]
+        self.guide_uploads += 1
+        return True
+
+    def _gd_bind(self, slot: int, req: Request):
+        """Queue ``ops.guide_reset_`` for a request admitted into ``slot``:
+        its table's first row and state 0, or -1 when the request has no guide
+        and the slot's last one had."""
+        from p2p_llm_tunnel_amd import ops
+        if req.guide is None:
+            if self._gd_on[slot]:
+                ops.guide_reset_(self._gd_base, self._gd_cur, self._gd_arena, slot, -1)
+                self._gd_on[slot] = False
+            return
+        self._gd_slot[slot] = (req.guide.key, req)
+        ops.guide_reset_(self._gd_base, self._gd_cur, self._gd_arena, slot, self._gd_tables[req.guide.key][0])
+        self._gd_on[slot] = True
+
+    def _take(self):
+        """The next request to admit, or None: the queue is empty, or its head
+        is a guided request whose table has no room yet (it stays the head)."""
+        if self._held is not None:
+            req, self._held = self._held, None
+        else:
+            try:
+                req = self.pending.get_nowait()
+            except queue.Empty:
+                return None
+        if req.guide is not None and not self._gd_reserve(req):
+            self._held = req
+            return None
+        return req
+
     @staticmethod
     def _resident(s: dict) -> list:
         """Token ids of the rows of ``s``'s slot that are valid once the queued
@@ -790,10 +1018,11 @@ class Engine:
         free = [i for i, s in enumerate(self.slots) if s is None]
         jobs = []
         max_seq, V = self.model.cfg.max_seq, self.model.cfg.vocab
+        if self.guided:
+            self._gd_release()
         while free:
-            try:
-                req = self.pending.get_nowait()
-            except queue.Empty:
+            req = self._take()
+            if req is None:
                 break
             req.max_new = max(1, min(req.max_new, max_seq - 2))  # as in _admit
             if req.embed is not None:  # the prompt's head, as in _admit
@@ -820,6 +1049,8 @@ class Engine:
             req.cached_tokens = m
             if self.penalties:
                 self._pen_reset(slot, req, ids)
+            if self.guided:
+                self._gd_bind(slot, req)
             if m:
                 self.prefix_hits += 1
                 self.cached_tokens += m
@@ -839,11 +1070,12 @@ class Engine:
     def _admit(self):
         if self.prefix_cache:
             return self._admit_prefix()
+        if self.guided:
+            self._gd_release()
         for i in range(self.max_batch):
             if self.slots[i] is None:
-                try:
-                    req = self.pending.get_nowait()
-                except queue.Empty:
+                req = self._take()
+                if req is None:
                     return
                 # max_new is clamped so prompt + generated rows fit max_seq; a
                 # prompt too long for the rest keeps its end (for a chat, the
@@ -856,6 +1088,8 @@ class Engine:
                 self.slots[i] = {"req": req, "pos": 0, "ids": ids, "gen": 0, "embed": req.embed}
                 if self.penalties:
                     self._pen_reset(i, req, ids)
+                if self.guided:
+                    self._gd_bind(i, req)
 
     def _plan(self, batch: list):
         """Rows of the next step (``_Row``), with the host-side state advanced
@@ -925,7 +1159,7 @@ class Engine:
         return rows, emits
 
     def _step_body(self, b: _StepBuf, n: int, run, sample_rows: int = 0, logprobs: bool = False,
-                   penalize: bool = False):
+                   penalize: bool = False, guide: bool = False):
         """One step on the first ``n`` rows of ``b``: staging -> device, decode
         rows' tokens gathered from ``last``, the model through ``run(tokens, pos,
         slots) -> (ids, logits)``, (the sampler over the leading ``sample_rows``
@@ -933,7 +1167,8 @@ class Engine:
         and the sampled ids, and its outputs -> pinned staging,) last-token
         scatter, ids -> pinned staging. With ``penalize`` the sampler reads what
         ``ops.penalize_`` made of those rows' logits; the logprobs kernel still
-        reads the raw ones."""
+        reads the raw ones. With ``guide`` ``ops.guide_`` masks those rows (the
+        penalised ones in place) ahead of the sampler."""
         din = self._d_in[b.rows]
         din.copy_(b.h_in, non_blocking=True)
         d = din[:, :n]
@@ -946,6 +1181,9 @@ class Engine:
                 drawn = ops.penalize_(drawn, self._work[b.rows], ids[:sample_rows], tok[:sample_rows], din[_DEC],
                                       din[_SLOT], din[_PEN], self._pen_state, self._pen_bias_n, self._pen_bias_ids,
                                       self._pen_bias_val)
+            if guide:
+                drawn = ops.guide_(drawn, self._work[b.rows], ids[:sample_rows], tok[:sample_rows], din[_DEC],
+                                   din[_SLOT], self._gd_base, self._gd_cur, self._gd_arena)
             ops.sample_(drawn, ids[:sample_rows], din[_SMP])
             if logprobs:
                 ops.logprobs_(logits[:sample_rows], ids[:sample_rows], din[_LP], b.d_lp[:sample_rows],
@@ -963,7 +1201,9 @@ class Engine:
         b.np[_SLOT, :] = b.np[_REC, :] = self.model.scratch_slot  # warm-up and capture touch the scratch slot only
         run = functools.partial(self.model.step_rows, emit_rows=emit_rows)
         sample_rows = (emit_rows or b.rows) if post else 0
-        graph, _ = capture(lambda: self._step_body(b, b.rows, run, sample_rows, post >= 2, post == 3), self.device)
+        graph, _ = capture(lambda: self._step_body(b, b.rows, run, sample_rows, post >= 2,
+                                                   post == 3 or (post == 4 and self.penalties), post == 4),
+                           self.device)
         torch.cuda.synchronize(self.device)
         return graph
 
@@ -995,6 +1235,8 @@ class Engine:
                 if req.penalties is not None:
                     h[_PEN, r] = req.penalties.column()
                     post = 3
+        if self.guided and any(req.guide is not None for _, req, _, _ in emits):
+            post = 4
         if n < R:  # padding rows: scratch slot, nothing recorded
             h[_TOK, n:R] = h[_POS, n:R] = h[_DEC, n:R] = 0
             h[_SLOT, n:R] = h[_REC, n:R] = scratch
@@ -1206,6 +1448,10 @@ class FrontEnd:
         self.default_temperature = default_temperature
         self.tok = tokenizer
         self.eos = tokenizer.eos_ids if tokenizer is not None else frozenset()
+        # Compiled guides, most recently used last (--guided): compilation runs in an executor, off the I/O thread.
+        self._guides: dict = {}
+        self._guides_lock = threading.Lock()
+        self._guide_pool = None  # one worker: compilations run one at a time (they hold the GIL the engine needs)
         self.loop = asyncio.new_event_loop()
         self._ready = threading.Event()
         self._err = None
@@ -1243,6 +1489,8 @@ class FrontEnd:
             self.loop.stop()
         self.loop.call_soon_threadsafe(stop)
         self.thread.join(timeout=10)
+        if self._guide_pool is not None:
+            self._guide_pool.shutdown(wait=False, cancel_futures=True)
 
     # ---------------------------------------------------------------- tokens
     def _on_batch(self, batch):
@@ -1536,6 +1784,37 @@ class FrontEnd:
         writer.write(self._json_response(obj))
         return True
 
+    _GUIDE_CACHE = 32  # compiled guides kept by the front end
+
+    def _guide(self, kind: str, pattern):
+        """The compiled ``Guide`` of a request's pattern (runs in an executor
+        thread); raises SamplingError (answered with 400) with the reason."""
+        from p2p_llm_tunnel_amd.models.guided import compile_guide
+        with self._guides_lock:
+            g = self._guides.pop((kind, pattern), None)
+            if g is not None:
+                self._guides[(kind, pattern)] = g
+                return g
+        if self.tok is None:
+            raise SamplingError("guided decoding needs a tokenizer: this server has none (it serves a random-init "
+                                "model whose ids have no text)")
+        V = self.engine.model.cfg.vocab
+        try:
+            tb = self.tok.token_bytes()
+        except (ValueError, AttributeError) as e:
+            raise SamplingError(f"guided decoding is not available with this tokenizer: {e}") from None
+        if len(tb) > V:
+            raise SamplingError(f"the tokenizer has {len(tb)} ids, the model's vocabulary {V}")
+        tb = list(tb) + [b""] * (V - len(tb))
+        states = self.engine._gd_arena.shape[0]
+        g = compile_guide(kind, list(pattern) if kind == "choice" else pattern, tb,
+                          [e for e in self.eos if 0 <= e < V], states)
+        with self._guides_lock:
+            self._guides[(kind, pattern)] = g
+            while len(self._guides) > self._GUIDE_CACHE:
+                self._guides.pop(next(iter(self._guides)))
+        return g
+
     async def _dispatch(self, method, path, body, writer, reader=None) -> bool:
         name = self.model_name
         if method in ("GET", "HEAD"):
@@ -1585,6 +1864,14 @@ class FrontEnd:
             penalties = penalty_params(rest, ollama, self.engine.model.cfg.vocab) if pen_on else None
             stops = stop_sequences(req_body, ollama)
             template_kwargs = chat_template_kwargs(req_body)
+            guide = None
+            if getattr(self.engine, "guided", False) and not ollama:
+                want = guided_params(req_body)
+                if want is not None:
+                    if self._guide_pool is None:
+                        from concurrent.futures import ThreadPoolExecutor
+                        self._guide_pool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="guide")
+                    guide = await asyncio.get_running_loop().run_in_executor(self._guide_pool, self._guide, *want)
             if not sampling.greedy and not self.engine.use_graph:
                 # The eager step (CPU stand-ins, injected models) has no sampler:
                 # refuse rather than answer a sampled request greedily.
@@ -1597,7 +1884,7 @@ class FrontEnd:
         rid = ("chatcmpl-" if kind == "chat" else "cmpl-") + uuid.uuid4().hex[:12]
         prompt = _prompt_ids(req_body, self.tok, template_kwargs)
         req = Request(prompt, max(1, min(max_new, 1024)), batched=True, sampling=sampling, logprobs=logprobs,
-                      penalties=penalties)
+                      penalties=penalties, guide=guide)
         st = _Stream(writer, stream, kind, rid, name, self.tok.detokenizer(prompt) if self.tok is not None else None,
                      StopMatcher(stops) if stops else None, logprobs is not None)
         req.state = st
@@ -1612,7 +1899,8 @@ class FrontEnd:
 def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_batch=8, model_name=None,
                  engine: Engine | None = None, checkpoint: str | None = None, max_seq: int | None = None,
                  tokenizer=None, default_temperature: float = 0.0, prefix_cache: bool = False, prefix_min: int = 16,
-                 embed_pooling: str = "mean", penalties: bool = False, kv_dtype: str = "bf16"):
+                 embed_pooling: str = "mean", penalties: bool = False, kv_dtype: str = "bf16",
+                 guided: bool = False, guided_states: int = 1024):
     """Engine + HTTP front-end; returns (server, port, engine). ``server.shutdown()``
     stops the HTTP side, ``engine.stop()`` the GPU side. ``checkpoint``: serve a
     Hugging Face Llama checkpoint directory (weights + tokenizer) instead of
@@ -1627,8 +1915,14 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
     and an injected ``engine`` must have been built with them too. ``kv_dtype``:
     "bf16" or "fp8", the KV cache's format (``TinyLlama``; docs/KV_FP8.md): fp8 halves
     its bytes, needs the graph-captured HIP step (refused on an eager engine) and must
-    not contradict an injected ``engine``'s model."""
+    not contradict an injected ``engine``'s model. ``guided`` / ``guided_states``: the
+    engine's guided decoding and the rows of its table arena (``Engine``; docs/GUIDED.md);
+    /v1/chat/completions and /v1/completions then act on "guided_regex", "guided_choice" and
+    "structured_outputs" (``guided_params``), which are ignored without the switch, and an
+    injected ``engine`` must have been built with it too."""
     kv_dtype = parse_kv_dtype(kv_dtype)
+    if engine is not None and guided and not getattr(engine, "guided", False):
+        raise ValueError("guided=True, but the injected engine was built without it")
     if engine is not None and getattr(engine.model, "kv_dtype", "bf16") != kv_dtype:
         raise ValueError(f"kv_dtype={kv_dtype!r}, but the injected engine's model has "
                          f"{getattr(engine.model, 'kv_dtype', 'bf16')!r} caches")
@@ -1644,10 +1938,11 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
         model = load_llama(checkpoint, device=device, max_batch=max_batch, max_seq=max_seq, kv_dtype=kv_dtype)
         tok = tok or Tokenizer.for_checkpoint(checkpoint)
         engine = Engine(device=device, max_batch=max_batch, model=model, prefix_cache=prefix_cache,
-                        prefix_min=prefix_min, penalties=penalties)
+                        prefix_min=prefix_min, penalties=penalties, guided=guided, guided_states=guided_states)
         model_name = model_name or os.path.basename(os.path.normpath(checkpoint))
     engine = engine or Engine(device=device, config=config, max_batch=max_batch, prefix_cache=prefix_cache,
-                              prefix_min=prefix_min, penalties=penalties, kv_dtype=kv_dtype)
+                              prefix_min=prefix_min, penalties=penalties, kv_dtype=kv_dtype, guided=guided,
+                              guided_states=guided_states)
     srv = FrontEnd(engine, host, port, model_name or f"p2pt-{config}", tokenizer=tok,
                    default_temperature=default_temperature, embed_pooling=embed_pooling)
     return srv, srv.server_address[1], engine
@@ -1687,6 +1982,8 @@ def replica_cmd(a, i: int) -> list[str]:
         cmd += ["--penalties"]
     if getattr(a, "kv_dtype", "bf16") != "bf16":
         cmd += ["--kv-dtype", a.kv_dtype]
+    if getattr(a, "guided", False):
+        cmd += ["--guided", "--guided-states", str(a.guided_states)]
     return cmd
 
 
@@ -1754,6 +2051,14 @@ def arg_parser() -> argparse.ArgumentParser:
                     help="format of the KV cache: bf16, or fp8 (OCP e4m3, scale 1, no calibration): half the bytes "
                          "per cached token, so the same memory holds twice the context or slots; values beyond "
                          "+-448 saturate (docs/KV_FP8.md)")
+    ap.add_argument("--guided", action="store_true",
+                    help="guided decoding on the device: /v1/chat/completions and /v1/completions act on "
+                         "guided_regex, guided_choice and structured_outputs {regex | choice} (a checkpoint with a "
+                         "ByteLevel or Metaspace tokenizer). Costs the table arena and four more captured graphs "
+                         "(docs/GUIDED.md)")
+    ap.add_argument("--guided-states", type=int, default=1024, metavar="N",
+                    help="rows of the guided-decoding arena, 2 x vocab bytes each: the token-level states of all "
+                         "resident patterns together (with --guided)")
     return ap
 
 
@@ -1764,7 +2069,8 @@ def main(argv=None):
     srv, port, engine = start_server(a.host, a.port, a.device, a.config, a.max_batch, checkpoint=a.checkpoint,
                                      max_seq=a.max_seq, default_temperature=a.default_temperature,
                                      prefix_cache=a.prefix_cache, prefix_min=a.prefix_min,
-                                     embed_pooling=a.embed_pooling, penalties=a.penalties, kv_dtype=a.kv_dtype)
+                                     embed_pooling=a.embed_pooling, penalties=a.penalties, kv_dtype=a.kv_dtype,
+                                     guided=a.guided, guided_states=a.guided_states)
     print(kv_cache_line(engine.model, a.kv_dtype), flush=True)
     print(f"inference endpoint on http://{a.host}:{port} ({a.checkpoint or a.config}, {a.device})", flush=True)
     try:

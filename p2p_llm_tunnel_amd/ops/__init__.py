@@ -1,5 +1,5 @@
 """Python front-end for the gfx950 HIP kernels (``kernels.hip``, ``decode_fused.hip``, ``sample.hip``,
-``logprobs.hip``, ``kv_copy.hip``, ``embed_pool.hip``, ``penalty.hip``).
+``logprobs.hip``, ``kv_copy.hip``, ``embed_pool.hip``, ``penalty.hip``, ``guide.hip``).
 
 The kernels are compiled in-tree into ``_hip_ops.so`` (see ``build.py``) and
 called through ctypes on the current torch stream. Every wrapper validates
@@ -84,6 +84,8 @@ def lib() -> ctypes.CDLL:
         _LIB.p2pt_penalize.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, vp, i, vp, vp, vp, i, i, vp]
         _LIB.p2pt_penalty_reset.argtypes = [vp, i, i, i, vp, i, vp, vp, vp, vp, i, vp]
         _LIB.p2pt_max_logit_bias.argtypes = []
+        _LIB.p2pt_guide.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, vp, i, i, i, vp]
+        _LIB.p2pt_guide_reset.argtypes = [vp, vp, i, i, i, i, vp]
         _LIB.p2pt_llama_ws_bytes.argtypes = [ctypes.POINTER(LlamaDims)]
         _LIB.p2pt_llama_ws_bytes.restype = ctypes.c_size_t
         szp = ctypes.POINTER(ctypes.c_size_t)
@@ -103,7 +105,7 @@ def lib() -> ctypes.CDLL:
                    "p2pt_llama_kv_plan",
                    "p2pt_max_rows", "p2pt_skinny_bench", "p2pt_attn_bench", "p2pt_kv_copy", "p2pt_max_kv_copy_jobs",
                    "p2pt_embed_pool", "p2pt_max_embed_jobs", "p2pt_qk_norm_rope_cache", "p2pt_penalize",
-                   "p2pt_penalty_reset", "p2pt_max_logit_bias"):
+                   "p2pt_penalty_reset", "p2pt_max_logit_bias", "p2pt_guide", "p2pt_guide_reset"):
             getattr(_LIB, fn).restype = ctypes.c_int
         if _LIB.p2pt_max_rows() != MAX_ROWS:
             raise RuntimeError(f"MAX_ROWS = {MAX_ROWS}, but {path} was built for {_LIB.p2pt_max_rows()} rows")
@@ -540,6 +542,81 @@ def penalty_reset_(state: torch.Tensor, slot: int, prompt_ids: torch.Tensor, bia
     _ok(lib().p2pt_penalty_reset(_p(state), n_slots, V, slot, _p(prompt_ids), prompt_ids.shape[0],
                                  _p(bias_n), _p(bias_ids), _p(bias_val), _p(bias), k, _stream(state)),
         "penalty_reset")
+
+
+def _guide_tables(base, cur, arena):
+    """Shape, dtype and device checks of the guide state shared by ``guide_`` and ``guide_reset_``."""
+    _check(arena, torch.int16, "arena")
+    dev = arena.device
+    _check(base, torch.int32, "base", dev)
+    _check(cur, torch.int32, "cur", dev)
+    if arena.dim() != 2 or arena.shape[0] < 1 or arena.shape[1] < 32:
+        raise ValueError(f"arena must be [arena_states >= 1, V >= 32], got {tuple(arena.shape)}")
+    if arena.shape[0] > 32767:
+        raise ValueError(f"arena holds at most 32767 states (its entries are int16), got {arena.shape[0]}")
+    if base.dim() != 1 or base.shape[0] < 1 or cur.shape != base.shape:
+        raise ValueError(f"base and cur must be [n_slots >= 1], got {tuple(base.shape)} and {tuple(cur.shape)}")
+    if arena.shape[1] % 8 == 0 and arena.data_ptr() % 16:
+        raise ValueError("arena must be 16-byte aligned")
+    return base.shape[0], arena.shape[0], arena.shape[1]
+
+
+def guide_(x: torch.Tensor, work: torch.Tensor, ids: torch.Tensor, tok: torch.Tensor, dec: torch.Tensor,
+           slot: torch.Tensor, base: torch.Tensor, cur: torch.Tensor, arena: torch.Tensor) -> torch.Tensor:
+    """Guided decoding ahead of the sampler (guide.hip), one workgroup per row
+    of bf16 ``x`` [B, V >= 32]. ``arena`` (int16 [arena_states, V]) holds token
+    automata one after the other: ``arena[base + c][t]`` is the state after
+    token t in state c of the table that starts at arena row ``base``, -1 when t
+    is not allowed. Row b belongs to slot ``slot[b]`` (int64 [>= B]); the
+    slot's table starts at ``base[s]`` (int32 [n_slots]; negative, like a slot
+    outside ``base`` or a state outside the arena, turns the row off) and its
+    state is ``cur[s]`` (int32 [n_slots]). An off row gets ``work[b]`` (bf16
+    [B, V]: ``x`` itself, or a buffer that does not overlap it) as a bit-for-bit
+    copy and nothing else. A row that is on first advances: if ``dec[b]``
+    (int64 [>= B]) is non-zero, ``t = arena[base + cur][tok[b]]`` (``tok``:
+    int64 [B]) and ``cur[s] = t`` when t >= 0; then ``work[b][v]`` is
+    ``x[b][v]`` where ``arena[base + cur][v] >= 0`` and -inf elsewhere; then
+    ``ids[b]`` (int64 [B], in place) becomes the argmax of the stored row (lowest
+    id on ties, NaN never wins, 0 without a winner). Rows that are on must
+    belong to different slots. Returns ``work``."""
+    _check(x, torch.bfloat16, "x")
+    dev = x.device
+    _check(work, torch.bfloat16, "work", dev)
+    for name, t in (("ids", ids), ("tok", tok), ("dec", dec), ("slot", slot)):
+        _check(t, torch.int64, name, dev)
+    n_slots, n_states, V = _guide_tables(base, cur, arena)
+    if arena.device != dev:
+        raise ValueError(f"arena on {arena.device}, expected {dev}")
+    if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] != V:
+        raise ValueError(f"x must be [B >= 1, {V}] (the arena's vocabulary), got {tuple(x.shape)}")
+    B = x.shape[0]
+    if work.shape != x.shape:
+        raise ValueError(f"work must be {tuple(x.shape)}, got {tuple(work.shape)}")
+    lo, hi = x.data_ptr(), x.data_ptr() + x.numel() * 2
+    if work.data_ptr() != lo and work.data_ptr() < hi and lo < work.data_ptr() + work.numel() * 2:
+        raise ValueError("work must be x itself or must not overlap it")
+    if ids.shape != (B,) or tok.shape != (B,):
+        raise ValueError("ids and tok must be [B]")
+    if dec.dim() != 1 or slot.dim() != 1 or dec.shape[0] < B or slot.shape[0] < B:
+        raise ValueError("dec and slot need an entry per row")
+    if V % 8 == 0 and (x.data_ptr() % 16 or work.data_ptr() % 16):
+        raise ValueError("x and work must be 16-byte aligned")
+    _ok(lib().p2pt_guide(_p(x), _p(work), _p(ids), _p(tok), _p(dec), _p(slot), _p(base), _p(cur), n_slots, _p(arena),
+                         n_states, B, V, _stream(x)), "guide")
+    return work
+
+
+def guide_reset_(base: torch.Tensor, cur: torch.Tensor, arena: torch.Tensor, slot: int, first: int) -> None:
+    """Admission of a request into ``slot`` of the guide state (guide.hip; see
+    ``guide_`` for the tables): ``base[slot] = first``, the arena row its table
+    starts at (-1: the slot is not guided), and ``cur[slot] = 0``. One launch on
+    the current stream: no sync, no allocation, other slots untouched. Never
+    captured."""
+    n_slots, n_states, _ = _guide_tables(base, cur, arena)
+    for name, v, lo, hi in (("slot", slot, 0, n_slots), ("first", first, -1, n_states)):
+        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v < hi:
+            raise ValueError(f"{name} must be an int in [{lo}, {hi}), got {v!r}")
+    _ok(lib().p2pt_guide_reset(_p(base), _p(cur), n_slots, slot, first, n_states, _stream(base)), "guide_reset")
 
 
 def kv_copy_(k_cache: torch.Tensor, v_cache: torch.Tensor, jobs) -> None:

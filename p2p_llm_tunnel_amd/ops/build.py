@@ -1,7 +1,7 @@
 """Compile the HIP kernels in-tree for gfx950 (CDNA4 / MI355X).
 
     hipcc -O3 --offload-arch=gfx950 -shared -fPIC kernels.hip decode_fused.hip sample.hip \
-          logprobs.hip kv_copy.hip embed_pool.hip penalty.hip -o _hip_ops.so
+          logprobs.hip kv_copy.hip embed_pool.hip penalty.hip guide.hip -o _hip_ops.so
 
 Cross-compiles on a CPU-only host; the .so travels with the repo snapshot to
 the GPU box.
@@ -14,7 +14,7 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRCS = [os.path.join(HERE, f) for f in ("kernels.hip", "decode_fused.hip", "sample.hip", "logprobs.hip",
-                                          "kv_copy.hip", "embed_pool.hip", "penalty.hip")]
+                                          "kv_copy.hip", "embed_pool.hip", "penalty.hip", "guide.hip")]
 DEPS = SRCS + [os.path.join(HERE, h) for h in ("bf16_common.h", "decode_fused_kernels.h")]
 OUT = os.path.join(HERE, "_hip_ops.so")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950").split(";")[0]
