@@ -60,7 +60,7 @@ from p2p_llm_tunnel_amd.models.tiny_llm import LlamaConfig, TinyLlama
 _SUPPORTED = {"LlamaForCausalLM", "MistralForCausalLM", "Qwen2ForCausalLM", "Qwen3ForCausalLM"}
 _QK_NORM = {"Qwen3ForCausalLM"}  # per-head RMSNorm on q and k before RoPE
 _QKV_BIAS = {"Qwen2ForCausalLM"}  # bias on q_proj, k_proj and v_proj, always (the config has no flag for it)
-_GQA_RATIOS = (1, 2, 4, 5, 6, 7, 8)  # the fused step's attention instantiations (decode_fused.hip: dims_ok)
+_GQA_RATIOS = (1, 2, 4, 5, 6, 7, 8)  # the fused step's attention instantiations (decode_fused.hip: GqaRatios)
 
 
 def read_config(path: str, max_seq: int | None = None) -> tuple[LlamaConfig, dict]:

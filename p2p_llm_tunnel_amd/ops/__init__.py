@@ -95,6 +95,7 @@ def lib() -> ctypes.CDLL:
                                            vp, ctypes.c_size_t, vp, vp, vp]
         _LIB.p2pt_llama_plan.argtypes = [ctypes.POINTER(LlamaDims), i, i, ctypes.POINTER(StepPlan)]
         _LIB.p2pt_llama_kv_plan.argtypes = [ctypes.POINTER(LlamaDims), ctypes.POINTER(KvPlan)]
+        _LIB.p2pt_llama_plan_kernels.argtypes = [ctypes.POINTER(LlamaDims), i, i]
         _LIB.p2pt_attn_span.argtypes = [i, i]
         _LIB.p2pt_max_rows.argtypes = []
         # microbenchmark hooks (scripts/bench_skinny.py)
@@ -102,7 +103,7 @@ def lib() -> ctypes.CDLL:
         _LIB.p2pt_attn_bench.argtypes = [vp, vp, vp, vp, i, i, i, i, i, vp, vp, vp, vp, i, vp]
         for fn in ("p2pt_rmsnorm", "p2pt_silu_mul", "p2pt_rope_qkv_cache", "p2pt_decode_attention", "p2pt_argmax",
                    "p2pt_skinny_gemm", "p2pt_llama_decode", "p2pt_sample", "p2pt_logprobs", "p2pt_llama_plan", "p2pt_attn_span",
-                   "p2pt_llama_kv_plan",
+                   "p2pt_llama_kv_plan", "p2pt_llama_plan_kernels",
                    "p2pt_max_rows", "p2pt_skinny_bench", "p2pt_attn_bench", "p2pt_kv_copy", "p2pt_max_kv_copy_jobs",
                    "p2pt_embed_pool", "p2pt_max_embed_jobs", "p2pt_qk_norm_rope_cache", "p2pt_penalize",
                    "p2pt_penalty_reset", "p2pt_max_logit_bias", "p2pt_guide", "p2pt_guide_reset"):
@@ -144,6 +145,15 @@ def kv_plan(dims: LlamaDims) -> KvPlan:
     if lib().p2pt_llama_kv_plan(ctypes.byref(dims), ctypes.byref(plan)) != 0:
         raise ValueError("dims not supported by the fused decode kernels")
     return plan
+
+
+def plan_kernels_ok(dims: LlamaDims, B: int, emit_rows: int = 0) -> bool:
+    """Whether every stage of ``step_plan(dims, B, emit_rows)`` and ``kv_plan(dims)`` names a kernel the library
+    instantiates, by the lookups its launchers use (host only)."""
+    rc = lib().p2pt_llama_plan_kernels(ctypes.byref(dims), B, emit_rows)
+    if rc < 0:
+        raise ValueError("dims or row count not supported by the fused decode kernels")
+    return rc == 0
 
 
 def attn_span(length: int, slots: int) -> int:

@@ -1,8 +1,12 @@
 // Host side of the fused Llama decode step for gfx950 (CDNA4 / MI355X): which
 // kernel variant runs on which grid (plan_step, a pure function), the
-// workspace, the launches and the C entry points. The kernels and the design
-// notes are in decode_fused_kernels.h.
+// workspace, the set of kernel instantiations (lists and one predicate), the
+// lookups and launches that follow a plan into that set, and the C entry
+// points. The kernels and the design notes are in decode_fused_kernels.h.
 #include "decode_fused_kernels.h"
+
+#include <type_traits>
+#include <utility>
 
 namespace {
 
@@ -98,9 +102,8 @@ StepPlan plan_step(const LlamaDims& d, int B, int emit_rows) {
   // QKV-bias models: the RoPE epilogue with the bias add. No K parts on QKV (launch() refuses them with a bias).
   // Scaled RoPE (rope_table): the table counterpart of whichever kernel rotates; nothing else moves.
   // FP8 cache (kv_fp8): the _KV8 counterpart of whichever kernel appends, and of k_attn; nothing else moves.
-  const int rope_epi = (d.rope_table ? (d.qkv_bias ? EPI_ROPE_BIAS_TAB : EPI_ROPE_TAB)
-                                     : (d.qkv_bias ? EPI_ROPE_BIAS : EPI_ROPE)) + (d.kv_fp8 ? kEpiKv8 : 0);
-  p.qkv = plan_gemm(d.qk_norm ? EPI_STORE : rope_epi, 1, B, (d.H + 2 * d.Hkv) * d.D, d.dim);
+  const int qkv_epi = d.qk_norm ? EPI_STORE : rope_epi(d.qkv_bias, d.rope_table, d.kv_fp8);
+  p.qkv = plan_gemm(qkv_epi, 1, B, (d.H + 2 * d.Hkv) * d.D, d.dim);
   if (d.qk_norm) {
     const int per_wg = qknorm_heads_per_wg(d.D);
     p.qk_norm_grid = (d.H + 2 * d.Hkv + per_wg - 1) / per_wg;
@@ -207,24 +210,14 @@ auto norm(const float* ss, int parts, float eps) {
 auto store(void* out) {  // STORE, SILU
   return [=](GemmArgs& a) { a.out = static_cast<uint16_t*>(out); };
 }
-auto rope(const LlamaDims& d, const int* pos, const int* slot, uint16_t* q, uint16_t* kc, uint16_t* vc) {
+// Every RoPE epilogue. bias and inv_freq: nullptr where the epilogue reads none (launch() refuses a bias or
+// table epilogue without its pointer).
+auto rope(const LlamaDims& d, const int* pos, const int* slot, uint16_t* q, uint16_t* kc, uint16_t* vc,
+          const void* bias, const void* inv_freq) {
   return [=](GemmArgs& a) {
     a.pos = pos, a.slot = slot, a.nslots = d.max_batch, a.q_out = q, a.kc = kc, a.vc = vc;
+    a.bias = static_cast<const uint16_t*>(bias), a.inv_freq = static_cast<const float*>(inv_freq);
     a.H = d.H, a.Hkv = d.Hkv, a.D = d.D, a.Smax = d.max_seq, a.log2_theta = log2f(d.theta);
-  };
-}
-auto rope_bias(const LlamaDims& d, const int* pos, const int* slot, uint16_t* q, uint16_t* kc, uint16_t* vc,
-               const void* bias) {  // ROPE_BIAS
-  return [=](GemmArgs& a) {
-    rope(d, pos, slot, q, kc, vc)(a);
-    a.bias = static_cast<const uint16_t*>(bias);
-  };
-}
-template <typename Rope>
-auto with_table(Rope r, const void* inv_freq) {  // ROPE_TAB, ROPE_BIAS_TAB: rope(...) or rope_bias(...) + the table
-  return [=](GemmArgs& a) {
-    r(a);
-    a.inv_freq = static_cast<const float*>(inv_freq);
   };
 }
 auto resid(uint16_t* r, float* ss_out) {
@@ -234,64 +227,84 @@ auto argmax(void* logits, float* am_val, int* am_idx) {
   return [=](GemmArgs& a) { a.out = static_cast<uint16_t*>(logits), a.am_val = am_val, a.am_idx = am_idx; };
 }
 
+// ------------------------------------------------------------ the kernels that exist
+// Stated once: a list of values per template parameter and, for k_skinny, one predicate over their product. The
+// three *_kernel() lookups instantiate exactly this set; the launchers, p2pt_llama_plan_kernels and dims_ok read
+// nothing else.
+template <int... V>
+using Ints = std::integer_sequence<int, V...>;
+using HeadDims = Ints<64, 128>;  // D of k_attn and k_qknorm_rope
+// G of k_attn, the GQA ratio H / Hkv (models/checkpoint.py mirrors it as _GQA_RATIOS). 5, 6 and 7 are the Qwen2 /
+// Qwen2.5 family's (40/8, 12/2, 14/2 and 28/4). 3 is absent: no checkpoint the loader accepts uses it.
+using GqaRatios = Ints<1, 2, 4, 5, 6, 7, 8>;
+using Flags = Ints<0, 1>;  // KV8 of k_attn; TAB and KV8 of k_qknorm_rope
+using SkinnyWaves = Ints<4, 8>;
+using SkinnyTiles = Ints<1, 2>;
+using SkinnyBatches = Ints<1, 2, 4>;
+using SkinnyEpis = Ints<EPI_STORE, EPI_ROPE, EPI_SILU, EPI_RESID, EPI_ARGMAX, EPI_ROPE_BIAS, EPI_ROPE_TAB,
+                        EPI_ROPE_BIAS_TAB, EPI_ROPE_KV8, EPI_ROPE_BIAS_KV8, EPI_ROPE_TAB_KV8, EPI_ROPE_BIAS_TAB_KV8>;
+constexpr bool skinny_exists(int nw, int tn, int epi, int um) {
+  // Two subtiles for the LM head and the standalone GEMM (plain STORE has both), one for every other epilogue.
+  if (tn != (epi == EPI_ARGMAX ? 2 : 1) && !(epi == EPI_STORE && tn == 2)) return false;
+  // The table and FP8-cache epilogues run QKV projections only, so they carry just the (nw, um) pairs plan_gemm
+  // can give one (fixed_nw == 0): 4 waves up to 16 k-steps with um 1, 2 or 4, and 8 waves from 17 on, where a
+  // wave's share is at least 3 k-steps and um is 4.
+  if (epi_has_table(epi) || epi_kv8(epi)) return nw == 4 || um == 4;
+  return true;
+}
+template <int... V>
+constexpr bool contains(Ints<V...>, int v) {
+  return ((v == V) || ...);
+}
+
+// pick(f, v0, Ints<...>{}, v1, Ints<...>{}, ...) calls f(c0, c1, ...), each c a std::integral_constant equal to
+// its run-time v, and calls nothing when some v is in no list.
+template <typename F>
+void pick(F&& f) {
+  f();
+}
+template <typename F, int... V, typename... Rest>
+void pick(F&& f, int v, Ints<V...>, Rest... rest) {
+  ((v == V ? pick([&](auto... c) { f(std::integral_constant<int, V>{}, c...); }, rest...) : void()), ...);
+}
+
+// The kernel a plan names, or nullptr where it is not instantiated.
+using SkinnyKernel = void (*)(GemmArgs);
+SkinnyKernel skinny_kernel(const GemmPlan& p) {
+  SkinnyKernel k = nullptr;
+  pick([&](auto nw, auto tn, auto epi, auto um) {
+    if constexpr (skinny_exists(nw, tn, epi, um)) k = k_skinny<nw, tn, epi, um>;
+  }, p.nw, SkinnyWaves{}, p.tn, SkinnyTiles{}, p.epi, SkinnyEpis{}, p.um, SkinnyBatches{});
+  return k;
+}
+using AttnKernel = decltype(&k_attn<64, 1, false>);
+AttnKernel attn_kernel(int D, int G, int kv8) {
+  AttnKernel k = nullptr;
+  pick([&](auto d, auto g, auto f8) { k = k_attn<d, g, f8 != 0>; }, D, HeadDims{}, G, GqaRatios{}, kv8, Flags{});
+  return k;
+}
+using QkNormKernel = void (*)(QkNormArgs);
+QkNormKernel qknorm_kernel(int D, int table, int kv8) {
+  QkNormKernel k = nullptr;
+  pick([&](auto d, auto tab, auto f8) { k = k_qknorm_rope<d, tab != 0, f8 != 0>; }, D, HeadDims{}, table, Flags{},
+       kv8, Flags{});
+  return k;
+}
+
 // ------------------------------------------------------------ launches
-template <int TN, int EPI>
-hipError_t launch_as(const GemmPlan& p, GemmArgs a, hipStream_t s) {
-  a.M = p.M, a.N = p.N, a.K = p.K, a.kpl = p.kpl;
-  const dim3 g(p.grid_x, p.grid_y), b(p.nw * 64);
-  switch (p.nw * 8 + p.um) {
-    case 8 * 8 + 1: hipLaunchKernelGGL((k_skinny<8, TN, EPI, 1>), g, b, 0, s, a); break;
-    case 8 * 8 + 2: hipLaunchKernelGGL((k_skinny<8, TN, EPI, 2>), g, b, 0, s, a); break;
-    case 8 * 8 + 4: hipLaunchKernelGGL((k_skinny<8, TN, EPI, 4>), g, b, 0, s, a); break;
-    case 4 * 8 + 1: hipLaunchKernelGGL((k_skinny<4, TN, EPI, 1>), g, b, 0, s, a); break;
-    case 4 * 8 + 2: hipLaunchKernelGGL((k_skinny<4, TN, EPI, 2>), g, b, 0, s, a); break;
-    case 4 * 8 + 4: hipLaunchKernelGGL((k_skinny<4, TN, EPI, 4>), g, b, 0, s, a); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-
-// The table and FP8-cache epilogues run QKV projections only, so they carry just the (nw, um) pairs plan_gemm can give one
-// (fixed_nw == 0): 4 waves up to 16 k-steps with um 1, 2 or 4, and 8 waves from 17 on, where a wave's share is
-// at least 3 k-steps and um is 4.
-template <int EPI>
-hipError_t launch_qkv_table(const GemmPlan& p, GemmArgs a, hipStream_t s) {
-  a.M = p.M, a.N = p.N, a.K = p.K, a.kpl = p.kpl;
-  const dim3 g(p.grid_x, p.grid_y), b(p.nw * 64);
-  switch (p.nw * 8 + p.um) {
-    case 8 * 8 + 4: hipLaunchKernelGGL((k_skinny<8, 1, EPI, 4>), g, b, 0, s, a); break;
-    case 4 * 8 + 1: hipLaunchKernelGGL((k_skinny<4, 1, EPI, 1>), g, b, 0, s, a); break;
-    case 4 * 8 + 2: hipLaunchKernelGGL((k_skinny<4, 1, EPI, 2>), g, b, 0, s, a); break;
-    case 4 * 8 + 4: hipLaunchKernelGGL((k_skinny<4, 1, EPI, 4>), g, b, 0, s, a); break;
-    default: return hipErrorInvalidValue;
-  }
-  return hipGetLastError();
-}
-
-// The one (nw, tn, epi, um) dispatch: the 66 k_skinny instantiations (42, and 4 for each table or FP8-cache epilogue).
-hipError_t launch(const GemmPlan& p, const GemmArgs& a, hipStream_t s) {
+// Each checks its arguments, looks its kernel up and launches it; a plan that names no kernel is hipErrorInvalidValue.
+hipError_t launch(const GemmPlan& p, GemmArgs a, hipStream_t s) {
   if (p.kpl < 0 || p.kpl > kMaxKpl || (p.ss_in > 0) != (a.ss_part != nullptr)) return hipErrorInvalidValue;
   if (p.kpl && (p.tn != 1 || (p.M << p.kpl) > 16 || p.K % (32 << p.kpl))) return hipErrorInvalidValue;
   // The bias is added once, after the K-split reduction: never with K parts, never without a bias.
   if (epi_has_bias(p.epi) && (p.kpl != 0 || a.bias == nullptr)) return hipErrorInvalidValue;
   // A table epilogue reads its table unconditionally: never without one.
   if (epi_has_table(p.epi) && a.inv_freq == nullptr) return hipErrorInvalidValue;
-  switch (p.epi * 4 + p.tn) {
-    case EPI_ROPE_TAB * 4 + 1: return launch_qkv_table<EPI_ROPE_TAB>(p, a, s);
-    case EPI_ROPE_BIAS_TAB * 4 + 1: return launch_qkv_table<EPI_ROPE_BIAS_TAB>(p, a, s);
-    case EPI_ROPE_KV8 * 4 + 1: return launch_qkv_table<EPI_ROPE_KV8>(p, a, s);
-    case EPI_ROPE_BIAS_KV8 * 4 + 1: return launch_qkv_table<EPI_ROPE_BIAS_KV8>(p, a, s);
-    case EPI_ROPE_TAB_KV8 * 4 + 1: return launch_qkv_table<EPI_ROPE_TAB_KV8>(p, a, s);
-    case EPI_ROPE_BIAS_TAB_KV8 * 4 + 1: return launch_qkv_table<EPI_ROPE_BIAS_TAB_KV8>(p, a, s);
-    case EPI_ROPE * 4 + 1: return launch_as<1, EPI_ROPE>(p, a, s);
-    case EPI_ROPE_BIAS * 4 + 1: return launch_as<1, EPI_ROPE_BIAS>(p, a, s);
-    case EPI_RESID * 4 + 1: return launch_as<1, EPI_RESID>(p, a, s);
-    case EPI_SILU * 4 + 1: return launch_as<1, EPI_SILU>(p, a, s);
-    case EPI_ARGMAX * 4 + 2: return launch_as<2, EPI_ARGMAX>(p, a, s);
-    case EPI_STORE * 4 + 1: return launch_as<1, EPI_STORE>(p, a, s);
-    case EPI_STORE * 4 + 2: return launch_as<2, EPI_STORE>(p, a, s);
-  }
-  return hipErrorInvalidValue;
+  const SkinnyKernel k = skinny_kernel(p);
+  if (!k) return hipErrorInvalidValue;
+  a.M = p.M, a.N = p.N, a.K = p.K, a.kpl = p.kpl;
+  hipLaunchKernelGGL(k, dim3(p.grid_x, p.grid_y), dim3(p.nw * 64), 0, s, a);
+  return hipGetLastError();
 }
 
 // (span slot, row, KV head) workgroups of 8 waves. Row b reads cache slot
@@ -299,71 +312,28 @@ hipError_t launch(const GemmPlan& p, const GemmArgs& a, hipStream_t s) {
 hipError_t launch_attn(const AttnPlan& p, int kv8, const void* q, const void* kc, const void* vc, const int* pos,
                        const int* slot, int nslots, float* part_o, float* part_ml, unsigned* counters, void* out,
                        int H, int Hkv, int Smax, hipStream_t s) {
-  auto go = [&](auto kern) {
-    hipLaunchKernelGGL(kern, dim3(p.slots, p.grid_y), dim3(512), 0, s, static_cast<const uint16_t*>(q),
-                       static_cast<const uint16_t*>(kc), static_cast<const uint16_t*>(vc), pos, slot, nslots, part_o,
-                       part_ml, counters, static_cast<uint16_t*>(out), H, Hkv, Smax, p.stride,
-                       1.f / sqrtf(float(p.D)));
-    return hipGetLastError();
-  };
-  if (p.G < 1 || p.G > 8 || (kv8 != 0 && kv8 != 1)) return hipErrorInvalidValue;
-  switch ((p.D * 16 + p.G) * 2 + kv8) {
-    case (64 * 16 + 1) * 2: return go(k_attn<64, 1>);
-    case (64 * 16 + 2) * 2: return go(k_attn<64, 2>);
-    case (64 * 16 + 4) * 2: return go(k_attn<64, 4>);
-    case (64 * 16 + 5) * 2: return go(k_attn<64, 5>);
-    case (64 * 16 + 6) * 2: return go(k_attn<64, 6>);
-    case (64 * 16 + 7) * 2: return go(k_attn<64, 7>);
-    case (64 * 16 + 8) * 2: return go(k_attn<64, 8>);
-    case (128 * 16 + 1) * 2: return go(k_attn<128, 1>);
-    case (128 * 16 + 2) * 2: return go(k_attn<128, 2>);
-    case (128 * 16 + 4) * 2: return go(k_attn<128, 4>);
-    case (128 * 16 + 5) * 2: return go(k_attn<128, 5>);
-    case (128 * 16 + 6) * 2: return go(k_attn<128, 6>);
-    case (128 * 16 + 7) * 2: return go(k_attn<128, 7>);
-    case (128 * 16 + 8) * 2: return go(k_attn<128, 8>);
-    // an e4m3 cache: the same (D, G) set
-    case (64 * 16 + 1) * 2 + 1: return go(k_attn<64, 1, true>);
-    case (64 * 16 + 2) * 2 + 1: return go(k_attn<64, 2, true>);
-    case (64 * 16 + 4) * 2 + 1: return go(k_attn<64, 4, true>);
-    case (64 * 16 + 5) * 2 + 1: return go(k_attn<64, 5, true>);
-    case (64 * 16 + 6) * 2 + 1: return go(k_attn<64, 6, true>);
-    case (64 * 16 + 7) * 2 + 1: return go(k_attn<64, 7, true>);
-    case (64 * 16 + 8) * 2 + 1: return go(k_attn<64, 8, true>);
-    case (128 * 16 + 1) * 2 + 1: return go(k_attn<128, 1, true>);
-    case (128 * 16 + 2) * 2 + 1: return go(k_attn<128, 2, true>);
-    case (128 * 16 + 4) * 2 + 1: return go(k_attn<128, 4, true>);
-    case (128 * 16 + 5) * 2 + 1: return go(k_attn<128, 5, true>);
-    case (128 * 16 + 6) * 2 + 1: return go(k_attn<128, 6, true>);
-    case (128 * 16 + 7) * 2 + 1: return go(k_attn<128, 7, true>);
-    case (128 * 16 + 8) * 2 + 1: return go(k_attn<128, 8, true>);
-  }
-  return hipErrorInvalidValue;
+  const AttnKernel k = attn_kernel(p.D, p.G, kv8);
+  if (!k) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k, dim3(p.slots, p.grid_y), dim3(512), 0, s, static_cast<const uint16_t*>(q),
+                     static_cast<const uint16_t*>(kc), static_cast<const uint16_t*>(vc), pos, slot, nslots, part_o,
+                     part_ml, counters, static_cast<uint16_t*>(out), H, Hkv, Smax, p.stride, 1.f / sqrtf(float(p.D)));
+  return hipGetLastError();
 }
 
 // (row, head group) workgroups of k_qknorm_rope: grid_x groups of qknorm_heads_per_wg(D) heads.
 // table: the k_qknorm_rope<D, true> variant, which reads a.inv_freq (8-byte loads) and is refused without it.
 // kv8: the variants that append k and v to an e4m3 cache.
 hipError_t launch_qknorm(int grid_x, int rows, int D, bool table, bool kv8, const QkNormArgs& a, hipStream_t s) {
+  const QkNormKernel k = qknorm_kernel(D, table, kv8);
+  if (!k) return hipErrorInvalidValue;
   if (grid_x <= 0 || rows <= 0 || grid_x * qknorm_heads_per_wg(D) < a.H + 2 * a.Hkv) return hipErrorInvalidValue;
   if (table && (a.inv_freq == nullptr || reinterpret_cast<uintptr_t>(a.inv_freq) % 8)) return hipErrorInvalidValue;
-  const dim3 g(grid_x, rows), b(kQkNormWaves * 64);
-  switch (D * 4 + int(kv8) * 2 + int(table)) {
-    case 64 * 4: hipLaunchKernelGGL((k_qknorm_rope<64, false>), g, b, 0, s, a); break;
-    case 128 * 4: hipLaunchKernelGGL((k_qknorm_rope<128, false>), g, b, 0, s, a); break;
-    case 64 * 4 + 1: hipLaunchKernelGGL((k_qknorm_rope<64, true>), g, b, 0, s, a); break;
-    case 128 * 4 + 1: hipLaunchKernelGGL((k_qknorm_rope<128, true>), g, b, 0, s, a); break;
-    case 64 * 4 + 2: hipLaunchKernelGGL((k_qknorm_rope<64, false, true>), g, b, 0, s, a); break;
-    case 128 * 4 + 2: hipLaunchKernelGGL((k_qknorm_rope<128, false, true>), g, b, 0, s, a); break;
-    case 64 * 4 + 3: hipLaunchKernelGGL((k_qknorm_rope<64, true, true>), g, b, 0, s, a); break;
-    case 128 * 4 + 3: hipLaunchKernelGGL((k_qknorm_rope<128, true, true>), g, b, 0, s, a); break;
-    default: return hipErrorInvalidValue;
-  }
+  hipLaunchKernelGGL(k, dim3(grid_x, rows), dim3(kQkNormWaves * 64), 0, s, a);
   return hipGetLastError();
 }
 
 bool dims_ok(const LlamaDims& d) {
-  if (d.D != 64 && d.D != 128) return false;
+  if (!contains(HeadDims{}, d.D)) return false;
   if (d.qk_norm != 0 && d.qk_norm != 1) return false;
   if (d.qkv_bias != 0 && d.qkv_bias != 1) return false;
   if (d.rope_table != 0 && d.rope_table != 1) return false;
@@ -379,11 +349,7 @@ bool dims_ok(const LlamaDims& d) {
                                2 * ffn * dim * 2, dim * hd * 2, dim * ffn * 2};
   for (size_t b : gemm_bytes)
     if (b >= kOob) return false;
-  // GQA ratios 1, 2, 4 to 8: the k_attn<D, G> instantiations of launch_attn. 5, 6 and 7 are the Qwen2 /
-  // Qwen2.5 family's (40/8, 12/2, 14/2 and 28/4). 3 stays refused: no checkpoint the loader accepts uses it.
-  if (d.Hkv <= 0 || d.H % d.Hkv) return false;
-  const int gqa = d.H / d.Hkv;
-  if (gqa != 1 && gqa != 2 && (gqa < 4 || gqa > 8)) return false;
+  if (d.Hkv <= 0 || d.H % d.Hkv || !contains(GqaRatios{}, d.H / d.Hkv)) return false;
   if (d.dim % 32 || (d.H * d.D) % 32 || d.ffn % 32) return false;
   if (d.dim % (16 * kTnResid) || d.vocab % (16 * kTnStore) || d.ffn % 16) return false;
   if (d.max_batch <= 0 || d.max_seq <= 0 || d.n_layers <= 0) return false;
@@ -429,6 +395,26 @@ int p2pt_llama_plan(const LlamaDims* d, int B, int emit_rows, StepPlan* out) {
 int p2pt_llama_kv_plan(const LlamaDims* d, KvPlan* out) {
   if (!dims_ok(*d)) return int(hipErrorInvalidValue);
   *out = plan_kv(*d);
+  return 0;
+}
+
+// Whether every stage of the plans above names a kernel that exists, by the launchers' own lookups (host only).
+// 0: all do; 1 + n: stage n, counting qkv_first, qkv, qk_norm, attn, o, gate_up, down, lm_head, is the first that
+// does not; -1: dims or row count refused.
+int p2pt_llama_plan_kernels(const LlamaDims* d, int B, int emit_rows) {
+  if (!dims_ok(*d) || !rows_ok(B)) return -1;
+  const StepPlan P = plan_step(*d, B, emit_rows);
+  const KvPlan KV = plan_kv(*d);
+  const bool found[] = {skinny_kernel(P.qkv_first) != nullptr,
+                        skinny_kernel(P.qkv) != nullptr,
+                        !P.qk_norm_grid || qknorm_kernel(d->D, P.qk_norm_table, KV.qk_norm_kv8) != nullptr,
+                        attn_kernel(P.attn.D, P.attn.G, KV.attn_kv8) != nullptr,
+                        skinny_kernel(P.o) != nullptr,
+                        skinny_kernel(P.gate_up) != nullptr,
+                        skinny_kernel(P.down) != nullptr,
+                        skinny_kernel(P.lm_head) != nullptr};
+  for (int n = 0; n < 8; n++)
+    if (!found[n]) return 1 + n;
   return 0;
 }
 
@@ -484,11 +470,7 @@ int p2pt_llama_decode(const LlamaDims* dp, const void* const* w, void* k_cache, 
     const GemmArgs qkv_in = gemm(W.resid, wl[1]) + norm(W.ss, qkv.ss_in, d.eps);
     const GemmArgs to_qkv =
         d.qk_norm ? qkv_in + store(W.qkv)
-        : d.qkv_bias
-            ? (d.rope_table ? qkv_in + with_table(rope_bias(d, pos, slots, W.q, kc, vc, wl[6]), inv_freq)
-                            : qkv_in + rope_bias(d, pos, slots, W.q, kc, vc, wl[6]))
-            : (d.rope_table ? qkv_in + with_table(rope(d, pos, slots, W.q, kc, vc), inv_freq)
-                            : qkv_in + rope(d, pos, slots, W.q, kc, vc));
+                  : qkv_in + rope(d, pos, slots, W.q, kc, vc, d.qkv_bias ? wl[6] : nullptr, inv_freq);
     const GemmArgs to_o = gemm(W.attn, wl[2]) + resid(W.resid, W.ss);
     const GemmArgs to_gate_up = gemm(W.resid, wl[4]) + norm(W.ss, P.gate_up.ss_in, d.eps) + store(W.h);
     const GemmArgs to_down = gemm(W.h, wl[5]) + resid(W.resid, W.ss);
@@ -528,7 +510,7 @@ int p2pt_skinny_gemm(const void* x, const void* w, void* out, int M, int N, int 
 int p2pt_qk_norm_rope_cache(const void* qkv, const int* pos, const int* slots, const void* q_weight,
                             const void* k_weight, void* q, void* k_cache, void* v_cache, int B, int H, int Hkv, int D,
                             int Smax, int nslots, float eps, float theta, const float* inv_freq, void* stream) {
-  if (!rows_ok(B) || (D != 64 && D != 128) || H <= 0 || Hkv <= 0 || Smax <= 0 || nslots <= 0)
+  if (!rows_ok(B) || !contains(HeadDims{}, D) || H <= 0 || Hkv <= 0 || Smax <= 0 || nslots <= 0)
     return int(hipErrorInvalidValue);
   if ((!slots && B > nslots) || !(theta > 0.f)) return int(hipErrorInvalidValue);
   const QkNormArgs a{static_cast<const uint16_t*>(qkv), static_cast<const uint16_t*>(q_weight),

@@ -27,6 +27,10 @@
 //                        per-block greedy winners
 //   k_argmax_merge       one block per row merges the winners
 //
+// k_skinny<NW, TN, EPI, UM>, k_attn<D, G, KV8> and k_qknorm_rope<D, TAB, KV8> are templates; which instantiations
+// exist is stated once, as lists of parameter values and one predicate, in decode_fused.hip, and a plan that names
+// any other is refused there. The RoPE epilogue of a model is rope_epi(bias, table, kv8) below.
+//
 // Skinny GEMM (M <= 64 tokens): Y[M,N] = A[M,K] * W[N,K]^T on
 // v_mfma_f32_16x16x32_bf16. A workgroup owns 16*TN output columns of one
 // 16-row tile (blockIdx.y; prefill-heavy steps carry up to 4) and splits K
@@ -50,7 +54,7 @@
 //
 // This header is the device side: kernel arguments, the kernels, the attention
 // grid rules and the record of what was measured and rejected. decode_fused.hip
-// includes it and holds the host side (planning, workspace, launches).
+// includes it and holds the host side (planning, workspace, the instantiation set, launches).
 #pragma once
 #include "bf16_common.h"
 
@@ -91,6 +95,17 @@ constexpr bool epi_is_rope(int epi) {
 }
 constexpr bool epi_has_bias(int epi) { return epi_base(epi) == EPI_ROPE_BIAS || epi_base(epi) == EPI_ROPE_BIAS_TAB; }
 constexpr bool epi_has_table(int epi) { return epi_base(epi) == EPI_ROPE_TAB || epi_base(epi) == EPI_ROPE_BIAS_TAB; }
+// The RoPE epilogue with these traits (host: plan_step), and the proof that the traits above are its inverse.
+constexpr int rope_epi(bool bias, bool table, bool kv8) {
+  return (table ? (bias ? EPI_ROPE_BIAS_TAB : EPI_ROPE_TAB) : (bias ? EPI_ROPE_BIAS : EPI_ROPE)) + (kv8 ? kEpiKv8 : 0);
+}
+constexpr bool rope_epi_inverts(bool bias, bool table, bool kv8) {
+  const int e = rope_epi(bias, table, kv8);
+  return epi_is_rope(e) && epi_has_bias(e) == bias && epi_has_table(e) == table && epi_kv8(e) == kv8;
+}
+static_assert(rope_epi_inverts(0, 0, 0) && rope_epi_inverts(1, 0, 0) && rope_epi_inverts(0, 1, 0) &&
+              rope_epi_inverts(1, 1, 0) && rope_epi_inverts(0, 0, 1) && rope_epi_inverts(1, 0, 1) &&
+              rope_epi_inverts(0, 1, 1) && rope_epi_inverts(1, 1, 1));
 
 struct GemmArgs {
   const uint16_t* x;  // A [M][K]

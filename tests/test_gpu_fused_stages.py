@@ -42,6 +42,7 @@ with them.
 """
 import ctypes
 import functools
+import itertools
 import math
 from dataclasses import dataclass, replace
 
@@ -731,6 +732,68 @@ def test_plan_invariants_over_a_sweep():
                 a = p.attn
                 assert (a.D, a.G, a.grid_y) == (D, G, B * 2) and 1 <= a.slots <= a.stride
                 assert M * dims.H * a.stride * D <= count["part_o"]
+
+
+# The six model families by their LlamaDims flags (qkv_bias + qk_norm is refused: no family has both).
+FAMILIES = {
+    "plain": {}, "bias": {"qkv_bias": 1}, "table": {"rope_table": 1}, "bias+table": {"qkv_bias": 1, "rope_table": 1},
+    "qk_norm": {"qk_norm": 1}, "qk_norm+table": {"qk_norm": 1, "rope_table": 1},
+}
+RESTRICTED_PAIRS = {(4, 1), (4, 2), (4, 4), (8, 4)}  # (nw, um) of a table or FP8-cache RoPE epilogue's k_skinny
+
+
+def _gqa_dims(G, D=64, dim=256, **flags):
+    dims = _dims(dim, 512, 2 * G, 2, D, 512)
+    for name, value in flags.items():
+        setattr(dims, name, value)
+    return dims
+
+
+def test_every_plan_names_an_instantiated_kernel():
+    # dim 32 to 8192 is 1 to 256 k-steps on QKV and gate/up, so every (nw, um) branch of plan_gemm: (4, 1) at 1 and
+    # 2 k-steps, (4, 2) at 8, (4, 4) at 16, (8, 4) from 17 (dim 544) on. (8, 1) and (8, 2) need 8 waves with at
+    # most 2 k-steps each, which the 17-step threshold rules out; the table and FP8-cache epilogues have neither.
+    from p2p_llm_tunnel_amd.models.checkpoint import _GQA_RATIOS
+    met = set()
+    accepted = 0
+    for (family, flags), kv_fp8 in itertools.product(FAMILIES.items(), (0, 1)):
+        for D, G, dim in itertools.product((64, 128), _GQA_RATIOS, (32, 64, 256, 512, 544, 1024, 2048, 4096, 8192)):
+            dims = _gqa_dims(G, D, dim, kv_fp8=kv_fp8, **flags)
+            for B in (1, 2, 4, 5, 16, 17, 64):
+                for emit in sorted({0, 1, B}):
+                    try:
+                        p = ops.step_plan(dims, B, emit)
+                    except ValueError:
+                        continue
+                    accepted += 1
+                    assert ops.plan_kernels_ok(dims, B, emit), (family, kv_fp8, D, G, dim, B, emit)
+                    if "qk_norm" not in flags and (kv_fp8 or "rope_table" in flags):
+                        assert p.qkv.epi >= 6, (family, kv_fp8)  # a table or _KV8 RoPE epilogue
+                        met |= {(p.qkv.nw, p.qkv.um), (p.qkv_first.nw, p.qkv_first.um)}
+    assert accepted == 12 * 2 * len(_GQA_RATIOS) * 9 * (2 + 6 * 3)  # step_plan refused none of them
+    assert met == RESTRICTED_PAIRS
+
+
+def test_gqa_ratios_outside_the_set_are_refused():
+    for D in (64, 128):
+        for G in (3, *range(9, 17)):
+            with pytest.raises(ValueError):
+                ops.step_plan(_gqa_dims(G, D), 1)
+            with pytest.raises(ValueError):
+                ops.plan_kernels_ok(_gqa_dims(G, D), 1)
+
+
+def test_the_loader_and_the_plan_accept_the_same_gqa_ratios():
+    from p2p_llm_tunnel_amd.models.checkpoint import _GQA_RATIOS
+
+    def accepts(G):
+        try:
+            ops.step_plan(_gqa_dims(G), 1)
+        except ValueError:
+            return False
+        return True
+
+    assert {G for G in range(1, 17) if accepts(G)} == set(_GQA_RATIOS)
 
 
 def test_plan_refuses_what_the_step_refuses():
