@@ -30,6 +30,8 @@ import hashlib
 
 import numpy as np
 
+from p2p_llm_tunnel_amd.models.params import SamplingError
+
 MAX_PATTERN = 2048  # characters of a guided_regex
 MAX_CHOICES = 256  # strings of a guided_choice
 MAX_CHOICE_BYTES = 16384  # UTF-8 bytes of all the strings of a guided_choice together
@@ -39,11 +41,6 @@ MAX_NFA_STATES = 4096  # Thompson states of a regex, counted before any is built
 MAX_DFA_STATES = 16384  # byte-DFA states during the subset construction, whatever max_states is
 DFA_PER_STATE = 4  # ... and at most DFA_PER_STATE * max_states + 256 of them (see ``dfa_limit``)
 MAX_STATES = 32767  # states of a token table (its entries are int16)
-
-
-def _error(msg: str):
-    from p2p_llm_tunnel_amd.models.server import SamplingError
-    return SamplingError(msg)
 
 
 # ---------------------------------------------------------------- parser
@@ -79,7 +76,7 @@ class _Parser:
         self.depth = 0
 
     def fail(self, what: str):
-        return _error(f"guided_regex: {what} (at offset {self.i} of {self.p!r})")
+        return SamplingError(f"guided_regex: {what} (at offset {self.i} of {self.p!r})")
 
     def peek(self) -> str:
         return self.p[self.i] if self.i < len(self.p) else ""
@@ -412,8 +409,8 @@ def _determinize(nfa: _Nfa, start: int, final: int, limit: int = MAX_DFA_STATES)
                 k = index.get(to)
                 if k is None:
                     if len(order) >= limit:
-                        raise _error(f"the pattern needs more than {limit} byte-level states (at most "
-                                     f"{DFA_PER_STATE} x max_states + 256, and {MAX_DFA_STATES})")
+                        raise SamplingError(f"the pattern needs more than {limit} byte-level states (at most "
+                                            f"{DFA_PER_STATE} x max_states + 256, and {MAX_DFA_STATES})")
                     k = index[to] = len(order)
                     order.append(to)
                 row[inv == j] = k
@@ -508,31 +505,32 @@ def compile_dfa(kind: str, pattern, limit: int = MAX_DFA_STATES):
     construction may make before the pattern is refused."""
     if kind == "regex":
         if not isinstance(pattern, str):
-            raise _error(f"guided_regex must be a string, got {pattern!r}")
+            raise SamplingError(f"guided_regex must be a string, got {pattern!r}")
         if len(pattern) > MAX_PATTERN:
-            raise _error(f"guided_regex takes at most {MAX_PATTERN} characters, got {len(pattern)}")
+            raise SamplingError(f"guided_regex takes at most {MAX_PATTERN} characters, got {len(pattern)}")
         ast = _Parser(pattern).parse()
         size = nfa_size(ast)
         if size > MAX_NFA_STATES:
-            raise _error(f"guided_regex: the pattern is too large: its counted repeats and groups expand to {size} "
-                         f"automaton states, at most {MAX_NFA_STATES} are accepted (nested counts multiply)")
+            raise SamplingError(f"guided_regex: the pattern is too large: its counted repeats and groups expand to "
+                                f"{size} automaton states, at most {MAX_NFA_STATES} are accepted (nested counts "
+                                "multiply)")
     elif kind == "choice":
         if not isinstance(pattern, (list, tuple)) or not pattern or \
                 not all(isinstance(c, str) and c for c in pattern):
-            raise _error(f"guided_choice must be a non-empty list of non-empty strings, got {pattern!r}")
+            raise SamplingError(f"guided_choice must be a non-empty list of non-empty strings, got {pattern!r}")
         if len(pattern) > MAX_CHOICES:
-            raise _error(f"guided_choice takes at most {MAX_CHOICES} strings, got {len(pattern)}")
+            raise SamplingError(f"guided_choice takes at most {MAX_CHOICES} strings, got {len(pattern)}")
         if sum(len(c.encode("utf-8")) for c in pattern) > MAX_CHOICE_BYTES:
-            raise _error(f"guided_choice takes at most {MAX_CHOICE_BYTES} bytes of text in all")
+            raise SamplingError(f"guided_choice takes at most {MAX_CHOICE_BYTES} bytes of text in all")
         ast = ("alt", [("cat", [("set", _mask([b]), False) for b in c.encode("utf-8")]) for c in dict.fromkeys(pattern)])
     else:
-        raise _error(f'a guide is a "regex" or a "choice", got {kind!r}')
+        raise SamplingError(f'a guide is a "regex" or a "choice", got {kind!r}')
     nfa = _Nfa()
     start, final = nfa.build(ast)
     trans, accept = _determinize(nfa, start, final, limit)
     trans, live = _prune_dead(trans, accept)
     if not live[0]:
-        raise _error("the pattern matches nothing")
+        raise SamplingError("the pattern matches nothing")
     return _minimize(trans, accept)
 
 
@@ -588,9 +586,9 @@ def token_table(trans: np.ndarray, accept: np.ndarray, token_bytes, eos_ids, max
     V = len(token_bytes)
     eos = sorted({int(e) for e in eos_ids})
     if not eos:
-        raise _error("guided decoding needs at least one EOS token id: a completion ends by sampling one")
+        raise SamplingError("guided decoding needs at least one EOS token id: a completion ends by sampling one")
     if any(not 0 <= e < V for e in eos):
-        raise _error(f"EOS ids {eos} are not all inside the vocabulary [0, {V})")
+        raise SamplingError(f"EOS ids {eos} are not all inside the vocabulary [0, {V})")
     max_states = min(int(max_states), MAX_STATES)
     lens = np.fromiter((len(b) for b in token_bytes), dtype=np.int64, count=V)
     lens[eos] = 0  # an EOS id never walks: it is allowed exactly in accepting states
@@ -623,7 +621,7 @@ def token_table(trans: np.ndarray, accept: np.ndarray, token_bytes, eos_ids, max
                     index[int(t)] = len(order)
                     order.append(int(t))
                     if len(order) > max_states:
-                        raise _error(f"the pattern needs more than max_states = {max_states} token-level states")
+                        raise SamplingError(f"the pattern needs more than max_states = {max_states} token-level states")
             rows.append(row)
         done += len(block)
     remap = np.full(sink + 1, -1, dtype=np.int64)
@@ -634,8 +632,8 @@ def token_table(trans: np.ndarray, accept: np.ndarray, token_bytes, eos_ids, max
         if accepting[s]:
             table[s, eos] = s
         elif not (table[s] >= 0).any():
-            raise _error(f"the pattern cannot be completed with this vocabulary: after some allowed text (token "
-                         f"state {s}) no token continues it and it is not a full match")
+            raise SamplingError(f"the pattern cannot be completed with this vocabulary: after some allowed text "
+                                f"(token state {s}) no token continues it and it is not a full match")
     return table, accepting, np.asarray(order, dtype=np.int32)
 
 

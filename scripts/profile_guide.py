@@ -96,15 +96,15 @@ def _engine(config, guided):
 def step(config):
     """post = 4 against post = 2 on one engine: 16 rows, one per slot, every row on."""
     import torch
-    from p2p_llm_tunnel_amd.models import server as S
+    from p2p_llm_tunnel_amd.models import engine as S
     eng, _ = _engine(config, True)
     try:
         V = eng.model.cfg.vocab
         g = torch.Generator().manual_seed(1)
         table = torch.randint(0, 8, (8, V), generator=g, dtype=torch.int16)
         table[torch.rand(8, V, generator=g) < 0.5] = -1
-        eng._gd_arena[:8].copy_(table)
-        eng._gd_base[:16] = 0
+        eng._gd.arena[:8].copy_(table)
+        eng._gd.base[:16] = 0
         b = eng._bufs[16][0]
         b.np[:] = 0
         b.np[S._SLOT, :] = b.np[S._REC, :] = range(16)

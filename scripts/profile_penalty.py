@@ -80,7 +80,7 @@ def _engine(config, penalties):
 
 def step(config):
     """post = 3 against post = 2 on one engine: 16 rows, one per slot, every row on."""
-    from p2p_llm_tunnel_amd.models import server as S
+    from p2p_llm_tunnel_amd.models import engine as S
     eng, _ = _engine(config, True)
     try:
         b = eng._bufs[16][0]

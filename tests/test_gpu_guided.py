@@ -14,6 +14,7 @@ at every generated index; ``test_fixed_inputs_are_confident`` (CPU) re-checks
 that from the seeds, and the GPU tests then demand equality at every index."""
 import http.client
 import json
+import queue
 import random
 import re
 
@@ -222,7 +223,7 @@ def test_engine_on_tiny_keeps_every_completion_inside_its_pattern():
     on = Engine(device="cuda:0", config="tiny", max_batch=4, seed=0, guided=True, guided_states=64)
     off = Engine(device="cuda:0", config="tiny", max_batch=4, seed=0)
     try:
-        assert len(on._graphs) == 16 and len(off._graphs) == 12 and not hasattr(off, "_gd_arena")
+        assert len(on._graphs) == 16 and len(off._graphs) == 12 and off._gd is None
         assert on._bufs[16][0].h_in.shape[0] == off._bufs[16][0].h_in.shape[0] == 11
         plain_prompt = ids_of(99, 100, 32000)
         want_plain = collect(off.submit(Request(list(plain_prompt), 10)))
@@ -298,6 +299,55 @@ def test_engine_with_penalties_and_the_prefix_cache(micro_engine, micro_guides):
     # ... and an unguided request into a slot a guided one has left is not masked.
     plain = collect(eng.submit(Request(list(prompt), N_NEW)))
     assert plain != want and not g.viable(completion(plain, tb, eos)[0])
+
+
+class _LoggedQueue(queue.Queue):
+    """A request's output queue that also notes every put in a list shared by
+    several requests: the engine thread makes all of them, so the list is the
+    order in which their tokens arrived."""
+
+    def __init__(self, log, name):
+        super().__init__()
+        self.log, self.name = log, name
+
+    def put(self, item, *a, **kw):
+        self.log.append((self.name, item))
+        super().put(item, *a, **kw)
+
+
+@gpu
+@cuda
+def test_a_guided_request_without_room_waits_at_the_head_of_the_queue():
+    """The arena holds either table, not both: B waits for A's table to be given
+    back, and C, unguided and queued behind B, does not overtake it although
+    slots are free all the time."""
+    tb, eos = synthetic_vocab(MICRO_V)
+    ga, gb = compile_guide("regex", "[a-c]{20}", tb, eos, 64), compile_guide("regex", PATTERNS[1], tb, eos, 64)
+    S = max(ga.n_states, gb.n_states)
+    assert S < ga.n_states + gb.n_states
+    eng = Engine(device="cuda:0", config="micro", max_batch=4, seed=0, guided=True, guided_states=S)
+    try:
+        log = []
+        reqs = {"A": Request(ids_of(1, 20), 30, guide=ga), "B": Request(ids_of(2, 20), 12, guide=gb),
+                "C": Request(ids_of(3, 20), 4)}
+        for name, r in reqs.items():
+            r.out = _LoggedQueue(log, name)
+        for r in reqs.values():  # in this order
+            eng.submit(r)
+        outs = {name: collect(r) for name, r in reqs.items()}
+        assert [len(outs[k]) for k in "ABC"] == [30, 12, 4]
+        for g, out in ((ga, outs["A"]), (gb, outs["B"])):
+            text, ended = completion(out, tb, eos)
+            assert g.matches(text) if ended else g.viable(text), text
+        assert eng.guide_uploads == 2 and eng.guide_shared == 0
+        first = {k: next(i for i, (name, t) in enumerate(log) if name == k and t is not None) for k in "ABC"}
+        last_a = max(i for i, (name, t) in enumerate(log) if name == "A" and t is not None)
+        assert first["B"] > last_a  # B was admitted only once A had left
+        # C came after B: its prompt is as long as B's and it sits in a higher slot, so its first token
+        # follows B's in the step that runs both; admitted ahead of B it would have come during A.
+        assert first["C"] > first["B"]
+    finally:
+        eng.stop()
 
 
 def _post(port, path, body):

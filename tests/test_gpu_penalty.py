@@ -324,7 +324,7 @@ def _cases():
 
 def _slot_state(eng, slot):
     torch.cuda.synchronize()
-    st = eng._pen_state[slot].cpu().numpy()
+    st = eng._pen.state[slot].cpu().numpy()
     return ({int(t) for t in np.nonzero(st & ref.PROMPT_BIT)[0]},
             {int(t): int(st[t] & ref.COUNT_MASK) for t in np.nonzero(st & ref.COUNT_MASK)[0]})
 
@@ -335,7 +335,7 @@ def test_engine_graphs_and_unpenalised_requests(engines):
     on, off = engines
     assert len(on._graphs) == 16 and len(off._graphs) == 12
     assert on._bufs[16][0].h_in.shape[0] == 15 and off._bufs[16][0].h_in.shape[0] == 11
-    assert not hasattr(off, "_pen_state")
+    assert off._pen is None
     for prompt, _, _, plain in _cases():
         got = [collect(e.submit(Request(list(prompt), N_NEW))) for e in (on, off)]
         assert got[0] == got[1]
@@ -357,7 +357,7 @@ def test_engine_one_by_one_matches_the_reference_and_resets_the_slot(engines):
         assert out == want
         bits, counts = _slot_state(on, 0)
         assert bits == set(prompt) and counts == dict(Counter(want[:-1]))  # the last token is never fed back
-        assert on._pen_bias_n[0].item() == len(pen.get("logit_bias", {}))
+        assert on._pen.bias_n[0].item() == len(pen.get("logit_bias", {}))
 
 
 @gpu
