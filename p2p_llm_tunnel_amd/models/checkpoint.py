@@ -162,10 +162,17 @@ class _Reader:
 
 
 def load_llama(path: str, device="cuda", max_batch: int = 8, max_seq: int | None = None,
-               fused: bool = True, prefix: str = "model.", kv_dtype: str = "bf16") -> TinyLlama:
+               fused: bool = True, prefix: str = "model.", kv_dtype: str = "bf16",
+               weight_dtype: str = "bf16") -> TinyLlama:
     """A TinyLlama with the checkpoint's weights (bf16 on ``device``). ``kv_dtype``: "bf16" or "fp8", the KV
     cache's format (``TinyLlama``), for every family alike; ``k_scale`` / ``v_scale`` tensors a checkpoint may
-    carry are not read (the FP8 cache's scale is 1)."""
+    carry are not read (the FP8 cache's scale is 1). ``weight_dtype``: "bf16" or "fp8" (docs/WEIGHT_FP8.md): each
+    layer's GEMM weights are quantised on ``device`` as soon as the layer is read and its bf16 tensors dropped, so
+    the device never holds the bf16 and the FP8 copies of all layers together. The checkpoint itself is bf16 / fp16
+    / fp32 either way: one that is already quantised on disk is treated as before."""
+    from p2p_llm_tunnel_amd.models.tiny_llm import WEIGHT_DTYPES, quantize_layer_
+    if weight_dtype not in WEIGHT_DTYPES:
+        raise ValueError(f"weight_dtype must be one of {list(WEIGHT_DTYPES)}, got {weight_dtype!r}")
     cfg, raw = read_config(path, max_seq)
     c = cfg
     rd = _Reader(path)
@@ -224,9 +231,12 @@ def load_llama(path: str, device="cuda", max_batch: int = 8, max_seq: int | None
                                  f"{(raw.get('architectures') or ['LlamaForCausalLM'])[0]!r} applies no QK-norm: refusing "
                                  "to load it without them")
             del q, k, v, gate, up
+            if weight_dtype == "fp8":  # this layer's bf16 GEMM weights give way to e4m3 + scales before the next is read
+                quantize_layer_(c, w["layers"][-1])
     finally:
         rd.close()
-    return TinyLlama.from_weights(cfg, w, device=dev, max_batch=max_batch, fused=fused, kv_dtype=kv_dtype)
+    return TinyLlama.from_weights(cfg, w, device=dev, max_batch=max_batch, fused=fused, kv_dtype=kv_dtype,
+                                  weight_dtype=weight_dtype)
 
 
 class Detokenizer:

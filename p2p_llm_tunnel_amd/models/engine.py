@@ -415,13 +415,17 @@ class Engine:
 
     def __init__(self, device="cuda:0", config="tiny", max_batch=8, seed=0, use_graph=True, rows=64, model=None,
                  small_rows=16, prefix_cache=False, prefix_min=16, penalties=False, kv_dtype="bf16",
-                 guided=False, guided_states=1024):
+                 guided=False, guided_states=1024, weight_dtype="bf16"):
         if model is None:
             from p2p_llm_tunnel_amd.models.tiny_llm import TinyLlama
-            model = TinyLlama(config, device=device, max_batch=max_batch, seed=seed, fused=True, kv_dtype=kv_dtype)
+            model = TinyLlama(config, device=device, max_batch=max_batch, seed=seed, fused=True, kv_dtype=kv_dtype,
+                              weight_dtype=weight_dtype)
         elif kv_dtype != "bf16" and getattr(model, "kv_dtype", "bf16") != kv_dtype:
             raise ValueError(f"kv_dtype={kv_dtype!r}, but the injected model was built with "
                              f"{getattr(model, 'kv_dtype', 'bf16')!r} caches")
+        elif weight_dtype != "bf16" and getattr(model, "weight_dtype", "bf16") != weight_dtype:
+            raise ValueError(f"weight_dtype={weight_dtype!r}, but the injected model was built with "
+                             f"{getattr(model, 'weight_dtype', 'bf16')!r} weights")
         if prefix_cache and not callable(getattr(model, "kv_copy", None)):
             raise ValueError("prefix_cache needs a model with kv_copy(jobs) (slot-to-slot K/V row copy)")
         # hipGraphs need a model with the capturable step on a HIP device (a
@@ -443,7 +447,8 @@ class Engine:
         sizes = [small_rows] + ([rows] if rows > small_rows else []) if use_graph else [rows]
         lp_dev = self.device if use_graph else None
         fp8 = getattr(model, "kv_dtype", "bf16") != "bf16"  # read and written by the fused HIP step alone
-        for on, what in ((penalties, "penalties need"), (fp8, "an fp8 KV cache needs"),
+        w8 = getattr(model, "weight_dtype", "bf16") != "bf16"  # multiplied by the fused HIP step alone
+        for on, what in ((penalties, "penalties need"), (fp8, "an fp8 KV cache needs"), (w8, "fp8 weights need"),
                          (guided, "guided decoding needs")):
             if on and not use_graph:
                 raise ValueError(f"{what} the graph-captured HIP step; this engine runs eagerly")

@@ -693,7 +693,7 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
                  engine: Engine | None = None, checkpoint: str | None = None, max_seq: int | None = None,
                  tokenizer=None, default_temperature: float = 0.0, prefix_cache: bool = False, prefix_min: int = 16,
                  embed_pooling: str = "mean", penalties: bool = False, kv_dtype: str = "bf16",
-                 guided: bool = False, guided_states: int = 1024):
+                 guided: bool = False, guided_states: int = 1024, weight_dtype: str = "bf16"):
     """Engine + HTTP front-end; returns (server, port, engine). ``server.shutdown()``
     stops the HTTP side, ``engine.stop()`` the GPU side. ``checkpoint``: serve a
     Hugging Face Llama checkpoint directory (weights + tokenizer) instead of
@@ -707,8 +707,13 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
     With ``penalties`` the endpoint takes the parameters ``penalty_params``
     describes instead of answering 400; with ``guided`` /v1/chat/completions and
     /v1/completions act on what ``guided_params`` describes, which is ignored
-    without the switch."""
+    without the switch. ``weight_dtype`` ("bf16" or "fp8", the format of the GEMM weights:
+    docs/WEIGHT_FP8.md) is ``Engine``'s and ``load_llama``'s, and an injected engine's model must have it."""
     kv_dtype = parse_kv_dtype(kv_dtype)
+    weight_dtype = parse_weight_dtype(weight_dtype)
+    if engine is not None and getattr(engine.model, "weight_dtype", "bf16") != weight_dtype:
+        raise ValueError(f"weight_dtype={weight_dtype!r}, but the injected engine's model has "
+                         f"{getattr(engine.model, 'weight_dtype', 'bf16')!r} weights")
     if engine is not None and guided and not getattr(engine, "guided", False):
         raise ValueError("guided=True, but the injected engine was built without it")
     if engine is not None and getattr(engine.model, "kv_dtype", "bf16") != kv_dtype:
@@ -723,14 +728,15 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
     if checkpoint and engine is None:
         import os
         from p2p_llm_tunnel_amd.models.checkpoint import Tokenizer, load_llama
-        model = load_llama(checkpoint, device=device, max_batch=max_batch, max_seq=max_seq, kv_dtype=kv_dtype)
+        model = load_llama(checkpoint, device=device, max_batch=max_batch, max_seq=max_seq, kv_dtype=kv_dtype,
+                           weight_dtype=weight_dtype)
         tok = tok or Tokenizer.for_checkpoint(checkpoint)
         engine = Engine(device=device, max_batch=max_batch, model=model, prefix_cache=prefix_cache,
                         prefix_min=prefix_min, penalties=penalties, guided=guided, guided_states=guided_states)
         model_name = model_name or os.path.basename(os.path.normpath(checkpoint))
     engine = engine or Engine(device=device, config=config, max_batch=max_batch, prefix_cache=prefix_cache,
                               prefix_min=prefix_min, penalties=penalties, kv_dtype=kv_dtype, guided=guided,
-                              guided_states=guided_states)
+                              guided_states=guided_states, weight_dtype=weight_dtype)
     srv = FrontEnd(engine, host, port, model_name or f"p2pt-{config}", tokenizer=tok,
                    default_temperature=default_temperature, embed_pooling=embed_pooling)
     return srv, srv.server_address[1], engine
@@ -744,6 +750,25 @@ def parse_kv_dtype(v) -> str:
     if v not in KV_DTYPE_CHOICES:
         raise ValueError(f"kv_dtype must be one of {list(KV_DTYPE_CHOICES)}, got {v!r}")
     return v
+
+
+WEIGHT_DTYPE_CHOICES = ("bf16", "fp8")
+
+
+def parse_weight_dtype(v) -> str:
+    """--weight-dtype / ``start_server(weight_dtype=)``: "bf16" (the default) or "fp8"; anything else is refused."""
+    if v not in WEIGHT_DTYPE_CHOICES:
+        raise ValueError(f"weight_dtype must be one of {list(WEIGHT_DTYPE_CHOICES)}, got {v!r}")
+    return v
+
+
+def weights_line(model, weight_dtype: str) -> str:
+    """The start-up log line with the weights' size."""
+    sizes = getattr(model, "weight_bytes", None)
+    if not callable(sizes):
+        return f"weights: ? bytes ({weight_dtype})"
+    b = sizes()
+    return (f"weights: {b['total']} bytes ({weight_dtype} GEMM weights {b['gemm']}, bf16 embedding {b['embed']})")
 
 
 def kv_cache_line(model, kv_dtype: str) -> str:
@@ -772,6 +797,8 @@ def replica_cmd(a, i: int) -> list[str]:
         cmd += ["--kv-dtype", a.kv_dtype]
     if getattr(a, "guided", False):
         cmd += ["--guided", "--guided-states", str(a.guided_states)]
+    if getattr(a, "weight_dtype", "bf16") != "bf16":
+        cmd += ["--weight-dtype", a.weight_dtype]
     return cmd
 
 
@@ -839,6 +866,11 @@ def arg_parser() -> argparse.ArgumentParser:
                     help="format of the KV cache: bf16, or fp8 (OCP e4m3, scale 1, no calibration): half the bytes "
                          "per cached token, so the same memory holds twice the context or slots; values beyond "
                          "+-448 saturate (docs/KV_FP8.md)")
+    ap.add_argument("--weight-dtype", choices=WEIGHT_DTYPE_CHOICES, default="bf16",
+                    help="format of the GEMM weights (QKV, O, gate/up, down and the LM head): bf16, or fp8 (OCP e4m3 "
+                         "with one fp32 scale per output row, per-row absmax, no calibration; the activations stay "
+                         "bf16): half the weight bytes per decode step; the embedding table stays bf16 "
+                         "(docs/WEIGHT_FP8.md)")
     ap.add_argument("--guided", action="store_true",
                     help="guided decoding on the device: /v1/chat/completions and /v1/completions act on "
                          "guided_regex, guided_choice and structured_outputs {regex | choice} (a checkpoint with a "
@@ -858,7 +890,8 @@ def main(argv=None):
                                      max_seq=a.max_seq, default_temperature=a.default_temperature,
                                      prefix_cache=a.prefix_cache, prefix_min=a.prefix_min,
                                      embed_pooling=a.embed_pooling, penalties=a.penalties, kv_dtype=a.kv_dtype,
-                                     guided=a.guided, guided_states=a.guided_states)
+                                     guided=a.guided, guided_states=a.guided_states, weight_dtype=a.weight_dtype)
+    print(weights_line(engine.model, a.weight_dtype), flush=True)
     print(kv_cache_line(engine.model, a.kv_dtype), flush=True)
     print(f"inference endpoint on http://{a.host}:{port} ({a.checkpoint or a.config}, {a.device})", flush=True)
     try:

@@ -58,6 +58,49 @@ CONFIGS = {
 
 
 KV_DTYPES = {"bf16": torch.bfloat16, "fp8": torch.float8_e4m3fn}  # TinyLlama(kv_dtype=): the caches' dtype
+WEIGHT_DTYPES = ("bf16", "fp8")  # TinyLlama(weight_dtype=): the format of the five GEMM weights
+GEMM_WEIGHTS = ("wqkv", "wo", "w_gate_up", "w_down")  # a layer's GEMM weights, in the order of their scales
+
+
+def _pairs(n, device):  # [0, n, 1, n + 1, ...]
+    return torch.stack([torch.arange(n), torch.arange(n) + n], 1).flatten().to(device)
+
+
+def fused_row_perm(cfg: "LlamaConfig", name: str, device) -> torch.Tensor | None:
+    """The row order of GEMM weight ``name`` in the fused table: row i of the table is row perm[i] of the plain
+    weight (RoPE partners of a head, gate_j / up_j, in pairs); None where the table keeps the plain order."""
+    if name == "wqkv" and not cfg.qk_norm:
+        heads = cfg.n_heads + 2 * cfg.n_kv_heads
+        return (torch.arange(heads, device=device)[:, None] * cfg.head_dim
+                + _pairs(cfg.head_dim // 2, device)[None, :]).flatten()
+    if name == "w_gate_up":
+        return _pairs(cfg.ffn, device)
+    return None
+
+
+def quantize_gemm_weight(w: torch.Tensor, g: torch.Tensor | None, perm: torch.Tensor | None):
+    """A GEMM weight as the fused table holds it, W'[n][k] = w[perm[n]][k] * g[k] with the fold in fp32, quantised
+    from that fp32 value (``ops.quantize_weight_fp8``), not through bf16: ``(q, scale)`` in the table's row order."""
+    wf = w.float()
+    if g is not None:
+        wf = wf * g.float()[None, :]
+    if perm is not None:
+        wf = wf[perm]
+    return ops.quantize_weight_fp8(wf.contiguous())
+
+
+def quantize_layer_(cfg: "LlamaConfig", L: dict) -> dict:
+    """One layer's four GEMM weights to FP8 in place: ``L[name]`` (bf16) gives way to ``L[name + "_q"]`` (e4m3,
+    folded and interleaved as the fused table wants it) and ``L[name + "_s"]`` (fp32 row scales). The loader calls
+    it layer by layer, so the bf16 and FP8 copies of all layers are never resident together."""
+    for name, norm in zip(GEMM_WEIGHTS, ("attn_norm", None, "ffn_norm", None)):
+        if name + "_q" in L:
+            continue
+        w = L.pop(name)
+        L[name + "_q"], L[name + "_s"] = quantize_gemm_weight(w, L[norm] if norm else None,
+                                                              fused_row_perm(cfg, name, w.device))
+        del w
+    return L
 
 
 def e4m3_round(x: torch.Tensor) -> torch.Tensor:
@@ -85,9 +128,15 @@ def capture(fn, device, warmup: int = 2):
 
 class TinyLlama:
     def __init__(self, cfg: LlamaConfig | str = "tiny", device="cuda", max_batch: int = 8, seed: int = 0,
-                 fused: bool = True, weights: dict | None = None, kv_dtype: str = "bf16"):
+                 fused: bool = True, weights: dict | None = None, kv_dtype: str = "bf16",
+                 weight_dtype: str = "bf16"):
         """``kv_dtype``: "bf16" (default) or "fp8": the K/V caches as ``torch.float8_e4m3fn`` (OCP e4m3, scale 1,
         half the bytes; docs/KV_FP8.md), which only the fused step reads and writes.
+
+        ``weight_dtype``: "bf16" (default) or "fp8": wqkv, wo, w_gate_up, w_down and lm_head as e4m3 bytes with
+        one fp32 scale per output row (docs/WEIGHT_FP8.md), quantised here layer by layer (the bf16 tensor of each
+        is dropped as it goes; ``weights`` may bring layers ``quantize_layer_`` has already seen). Only the fused
+        step reads them. The embedding stays bf16, so a tied model keeps it and gets an FP8 copy for the LM head.
 
         Random-init weights from ``seed``, or ``weights`` (embed, final_norm,
         lm_head, layers[{attn_norm, wqkv, wo, ffn_norm, w_gate_up, w_down}, plus
@@ -98,7 +147,11 @@ class TinyLlama:
             raise ValueError("qkv_bias with qk_norm: no supported family has both, and the fused step refuses it")
         if kv_dtype not in KV_DTYPES:
             raise ValueError(f"kv_dtype must be one of {sorted(KV_DTYPES)}, got {kv_dtype!r}")
+        if weight_dtype not in WEIGHT_DTYPES:
+            raise ValueError(f"weight_dtype must be one of {list(WEIGHT_DTYPES)}, got {weight_dtype!r}")
         self.kv_dtype = kv_dtype
+        self.weight_dtype = weight_dtype
+        self.lm_head_q = self.lm_head_s = None  # weight_dtype "fp8": the LM head's bytes and row scales
         self.fused = fused
         self._fused = None
         self._graphs = {}  # rows -> (graph, tokens, pos, slots, ids, logits)
@@ -120,6 +173,7 @@ class TinyLlama:
                 for i, L in enumerate(self.layers):
                     if "bqkv" not in L or tuple(L["bqkv"].shape) != (n_qkv,):
                         raise ValueError(f"layer {i}: a QKV-bias model needs bqkv of shape ({n_qkv},)")
+            self._quantize_weights()
             self._alloc_caches()
             return
         g = torch.Generator(device="cpu").manual_seed(seed)
@@ -149,12 +203,44 @@ class TinyLlama:
                 self.layers[-1]["bqkv"] = w(qkv_out, scale=1.0)
         self.final_norm = norm_w(c.dim)
         self.lm_head = w(c.vocab, c.dim, scale=1 / math.sqrt(c.dim))
+        self._quantize_weights()
         self._alloc_caches()
 
     @classmethod
     def from_weights(cls, cfg: LlamaConfig, weights: dict, device="cuda", max_batch: int = 8, fused: bool = True,
-                     kv_dtype: str = "bf16"):
-        return cls(cfg, device=device, max_batch=max_batch, fused=fused, weights=weights, kv_dtype=kv_dtype)
+                     kv_dtype: str = "bf16", weight_dtype: str = "bf16"):
+        return cls(cfg, device=device, max_batch=max_batch, fused=fused, weights=weights, kv_dtype=kv_dtype,
+                   weight_dtype=weight_dtype)
+
+    def _quantize_weights(self):
+        """``weight_dtype`` "fp8": every layer's GEMM weights and the LM head to e4m3 + row scales, one tensor at
+        a time. The bf16 LM head is dropped unless it is the embedding itself (a tied model)."""
+        if self.weight_dtype != "fp8":
+            if any(n + "_q" in L for L in self.layers for n in GEMM_WEIGHTS):
+                raise ValueError("the weights hold FP8 layers: pass weight_dtype='fp8'")
+            return
+        self.layers = [quantize_layer_(self.cfg, dict(L)) for L in self.layers]
+        self.lm_head_q, self.lm_head_s = quantize_gemm_weight(self.lm_head, self.final_norm, None)
+        self.lm_head = None
+
+    def weight_bytes(self) -> dict:
+        """Bytes of the weights on the device: ``gemm`` (the five GEMM weights, with their scales when FP8),
+        ``embed`` (the bf16 embedding table, which FP8 weights leave alone) and ``total`` (those and the norms,
+        biases and QK-norm weights). A tied bf16 model counts its one shared table under ``embed`` only."""
+        nb = lambda t: t.numel() * t.element_size()
+        gemm = other = 0
+        for L in self.layers:
+            for k, t in L.items():
+                if k in GEMM_WEIGHTS or k[:-2] in GEMM_WEIGHTS:  # name, name_q, name_s
+                    gemm += nb(t)
+                else:
+                    other += nb(t)
+        if self.weight_dtype == "fp8":
+            gemm += nb(self.lm_head_q) + nb(self.lm_head_s)
+        elif self.lm_head is not self.embed and self.lm_head.data_ptr() != self.embed.data_ptr():
+            gemm += nb(self.lm_head)
+        embed = nb(self.embed)
+        return {"gemm": gemm, "embed": embed, "total": gemm + embed + other + nb(self.final_norm)}
 
     def _alloc_caches(self):
         c = self.cfg
@@ -242,11 +328,26 @@ class TinyLlama:
             return (w.float() * g.float()[None, :]).to(torch.bfloat16)
 
         def pairs(n):  # [0, n, 1, n + 1, ...]
-            return torch.stack([torch.arange(n), torch.arange(n) + n], 1).flatten().to(self.device)
+            return _pairs(n, self.device)
 
         heads = c.n_heads + 2 * c.n_kv_heads
         head_perm = (torch.arange(heads, device=self.device)[:, None] * c.head_dim
                      + pairs(c.head_dim // 2)[None, :]).flatten()
+        if self.weight_dtype == "fp8":
+            # The same layout with the five GEMM weights as e4m3 bytes (quantised after the fold and the
+            # interleave: _quantize_weights), followed by their row scales: lm_head's, then four per layer.
+            ws = [self.embed, self.final_norm, self.lm_head_q]
+            if c.rope_scaling is not None:
+                ws.append(self.rope_inv_freq())
+            scales = [self.lm_head_s]
+            for L in self.layers:
+                ws += [L["attn_norm"], L["wqkv_q"], L["wo_q"], L["ffn_norm"], L["w_gate_up_q"], L["w_down_q"]]
+                if c.qk_norm:
+                    ws += [L["q_norm"].contiguous(), L["k_norm"].contiguous()]
+                if c.qkv_bias:
+                    ws += [L["bqkv"][head_perm].contiguous()]
+                scales += [L[n + "_s"] for n in GEMM_WEIGHTS]
+            return ws + scales
         ws = [self.embed, self.final_norm, fold(self.lm_head, self.final_norm)]
         if c.rope_scaling is not None:
             ws.append(self.rope_inv_freq())
@@ -267,7 +368,8 @@ class TinyLlama:
                                  D=c.head_dim, ffn=c.ffn, max_seq=c.max_seq, max_batch=self.max_batch + 1, eps=c.eps,
                                  theta=c.rope_theta, qk_norm=int(c.qk_norm), qkv_bias=int(c.qkv_bias),
                                  rope_table=int(c.rope_scaling is not None), kv_fp8=int(self.kv_dtype == "fp8"))
-            self._fused = ops.FusedLlamaDecoder(dims, self.fused_weights(), self.k_cache, self.v_cache)
+            self._fused = ops.FusedLlamaDecoder(dims, self.fused_weights(), self.k_cache, self.v_cache,
+                                                weight_fp8=self.weight_dtype == "fp8")
         return self._fused
 
     def step_rows(self, tokens, pos, slots=None, emit_rows=0, pos_range=None):
@@ -286,6 +388,9 @@ class TinyLlama:
         if self.kv_dtype != "bf16":
             raise ValueError(f"an {self.kv_dtype} KV cache runs the fused step only (at most {ops.MAX_ROWS} rows, "
                              "fused=True): the unfused kernels read and write bf16 caches")
+        if self.weight_dtype != "bf16":
+            raise ValueError(f"{self.weight_dtype} weights run the fused step only (at most {ops.MAX_ROWS} rows, "
+                             "fused=True): the unfused path multiplies bf16 weights")
         return self._decode_unfused(tokens, pos, pos_range or (0, self.cfg.max_seq - 1))
 
     def _decode_unfused(self, tokens, pos, pos_range):
@@ -359,7 +464,27 @@ class TinyLlama:
     def reference_logits(self, seqs: torch.Tensor, kv_round=None) -> torch.Tensor:
         """fp32 forward of full sequences [B, T]; returns logits of the last position [B, V]. ``kv_round``: see
         ``reference_hidden``."""
-        return self.reference_hidden(seqs, kv_round)[:, -1] @ self.lm_head.float().T
+        return self.reference_hidden(seqs, kv_round)[:, -1] @ self.reference_weight("lm_head").T
+
+    def reference_weight(self, name: str, layer: int | None = None) -> torch.Tensor:
+        """GEMM weight ``name`` ("lm_head", or one of a layer's four) in fp32 and plain row order, as the reference
+        multiplies it. bf16 weights: the tensor itself. FP8 weights: the dequantised ``q * s`` (the function the
+        kernels compute; the quantisation error against the original is a separate quantity), which carries the
+        preceding norm's weight folded in, so the reference then norms with a weight of one (``_ref_norm``)."""
+        if self.weight_dtype != "fp8":
+            return (self.lm_head if layer is None else self.layers[layer][name]).float()
+        if layer is None:
+            return ops.dequantize_weight_fp8(self.lm_head_q, self.lm_head_s)
+        L = self.layers[layer]
+        w = ops.dequantize_weight_fp8(L[name + "_q"], L[name + "_s"])
+        perm = fused_row_perm(self.cfg, name, w.device)
+        if perm is not None:
+            w = w[torch.argsort(perm)]
+        return w
+
+    def _ref_norm(self, g: torch.Tensor) -> torch.Tensor:
+        """The weight the reference's RMSNorm ahead of a folded GEMM applies: g, or one where g is in the weight."""
+        return torch.ones_like(g) if self.weight_dtype == "fp8" else g
 
     @torch.no_grad()
     def reference_hidden(self, seqs: torch.Tensor, kv_round=None) -> torch.Tensor:
@@ -396,11 +521,11 @@ class TinyLlama:
             return torch.cat([t1 * cc - t2 * ss, t2 * cc + t1 * ss], -1)
 
         residual = x
-        h = bf(rms(x, self.layers[0]["attn_norm"]))
+        h = bf(rms(x, self._ref_norm(self.layers[0]["attn_norm"])))
         G = c.n_heads // c.n_kv_heads
         mask = torch.full((T, T), float("-inf"), device=seqs.device).triu(1)
         for i, L in enumerate(self.layers):
-            raw = h @ f32(L["wqkv"]).T
+            raw = h @ self.reference_weight("wqkv", i).T
             raw = raw + f32(L["bqkv"]) if c.qkv_bias else raw
             qkv = bf(raw)
             q = qkv[..., : c.n_heads * c.head_dim].view(B, T, c.n_heads, c.head_dim)
@@ -417,15 +542,15 @@ class TinyLlama:
             v = v.repeat_interleave(G, dim=2)
             s = torch.einsum("bqhd,bkhd->bhqk", q, k) / math.sqrt(c.head_dim) + mask
             a = bf(torch.einsum("bhqk,bkhd->bqhd", s.softmax(-1), v).reshape(B, T, -1))
-            o = bf(a @ f32(L["wo"]).T)
+            o = bf(a @ self.reference_weight("wo", i).T)
             residual = bf(residual + o)
-            h = bf(rms(residual, L["ffn_norm"]))
-            gu = bf(h @ f32(L["w_gate_up"]).T)
+            h = bf(rms(residual, self._ref_norm(L["ffn_norm"])))
+            gu = bf(h @ self.reference_weight("w_gate_up", i).T)
             g_, u_ = gu[..., : c.ffn], gu[..., c.ffn:]
-            m = bf(bf(F.silu(g_) * u_) @ f32(L["w_down"]).T)
+            m = bf(bf(F.silu(g_) * u_) @ self.reference_weight("w_down", i).T)
             residual = bf(residual + m)
             nxt = self.layers[i + 1]["attn_norm"] if i + 1 < len(self.layers) else self.final_norm
-            h = bf(rms(residual, nxt))
+            h = bf(rms(residual, self._ref_norm(nxt)))
         return h
 
     @torch.no_grad()

@@ -58,6 +58,13 @@ class KvPlan(ctypes.Structure):
     _fields_ = [("attn_kv8", _INT), ("qk_norm_kv8", _INT)]
 
 
+class WeightPlan(ctypes.Structure):
+    """Mirror of ``WeightPlan``: the weight format of a step, beside its ``StepPlan`` as ``KvPlan`` is. ``w8``: 1
+    when the five GEMM weights (wqkv, wo, w_gate_up, w_down, lm_head) are e4m3 bytes with one fp32 scale per
+    output row and every ``k_skinny`` is its FP8-weight instantiation (docs/WEIGHT_FP8.md); 0: bf16."""
+    _fields_ = [("w8", _INT)]
+
+
 def lib() -> ctypes.CDLL:
     global _LIB
     if _LIB is None:
@@ -96,6 +103,10 @@ def lib() -> ctypes.CDLL:
         _LIB.p2pt_llama_plan.argtypes = [ctypes.POINTER(LlamaDims), i, i, ctypes.POINTER(StepPlan)]
         _LIB.p2pt_llama_kv_plan.argtypes = [ctypes.POINTER(LlamaDims), ctypes.POINTER(KvPlan)]
         _LIB.p2pt_llama_plan_kernels.argtypes = [ctypes.POINTER(LlamaDims), i, i]
+        _LIB.p2pt_llama_weight_plan.argtypes = [ctypes.POINTER(LlamaDims), i, ctypes.POINTER(WeightPlan)]
+        _LIB.p2pt_llama_plan_kernels_w.argtypes = [ctypes.POINTER(LlamaDims), i, i, ctypes.POINTER(WeightPlan)]
+        _LIB.p2pt_llama_decode_w.argtypes = [ctypes.POINTER(LlamaDims), ctypes.POINTER(WeightPlan), ctypes.POINTER(vp),
+                                             vp, vp, vp, vp, vp, i, i, vp, ctypes.c_size_t, vp, vp, vp]
         _LIB.p2pt_attn_span.argtypes = [i, i]
         _LIB.p2pt_max_rows.argtypes = []
         # microbenchmark hooks (scripts/bench_skinny.py)
@@ -103,7 +114,8 @@ def lib() -> ctypes.CDLL:
         _LIB.p2pt_attn_bench.argtypes = [vp, vp, vp, vp, i, i, i, i, i, vp, vp, vp, vp, i, vp]
         for fn in ("p2pt_rmsnorm", "p2pt_silu_mul", "p2pt_rope_qkv_cache", "p2pt_decode_attention", "p2pt_argmax",
                    "p2pt_skinny_gemm", "p2pt_llama_decode", "p2pt_sample", "p2pt_logprobs", "p2pt_llama_plan", "p2pt_attn_span",
-                   "p2pt_llama_kv_plan", "p2pt_llama_plan_kernels",
+                   "p2pt_llama_kv_plan", "p2pt_llama_plan_kernels", "p2pt_llama_weight_plan",
+                   "p2pt_llama_plan_kernels_w", "p2pt_llama_decode_w",
                    "p2pt_max_rows", "p2pt_skinny_bench", "p2pt_attn_bench", "p2pt_kv_copy", "p2pt_max_kv_copy_jobs",
                    "p2pt_embed_pool", "p2pt_max_embed_jobs", "p2pt_qk_norm_rope_cache", "p2pt_penalize",
                    "p2pt_penalty_reset", "p2pt_max_logit_bias", "p2pt_guide", "p2pt_guide_reset"):
@@ -127,6 +139,8 @@ MAX_KV_COPY_JOBS = 8  # jobs per launch of kv_copy_ (kv_copy.hip's kMaxJobs: the
 MAX_EMBED_JOBS = 16  # jobs per launch of embed_pool_ (embed_pool.hip's kMaxJobs: in the kernel arguments too)
 MAX_LOGIT_BIAS = 300  # entries of a slot's logit_bias list (penalty.hip's kMaxBias; the OpenAI API's limit)
 KV_FP8_DTYPES = (torch.float8_e4m3fn, torch.uint8)  # cache dtypes of a decoder with dims.kv_fp8 (the same bytes)
+WEIGHT_FP8_DTYPES = KV_FP8_DTYPES  # GEMM-weight dtypes of a decoder with weight_fp8 (the same bytes)
+E4M3_MAX = 448.0  # the largest finite e4m3fn value: a row's largest magnitude quantises to it
 MAX_TOP_LOGPROBS = 20  # top (id, logprob) pairs per row of logprobs_ (logprobs.hip's kMaxTop; the OpenAI API's limit)
 
 
@@ -147,10 +161,24 @@ def kv_plan(dims: LlamaDims) -> KvPlan:
     return plan
 
 
-def plan_kernels_ok(dims: LlamaDims, B: int, emit_rows: int = 0) -> bool:
-    """Whether every stage of ``step_plan(dims, B, emit_rows)`` and ``kv_plan(dims)`` names a kernel the library
-    instantiates, by the lookups its launchers use (host only)."""
-    rc = lib().p2pt_llama_plan_kernels(ctypes.byref(dims), B, emit_rows)
+def weight_plan(dims: LlamaDims, weight_fp8: bool = False) -> WeightPlan:
+    """The weight format ``p2pt_llama_decode_w`` launches for (host only): ``w8`` 1 with FP8 weights, 0 without.
+    ``step_plan(dims, B)`` is the same either way: the format changes no grid, wave count or load batch."""
+    plan = WeightPlan()
+    if lib().p2pt_llama_weight_plan(ctypes.byref(dims), int(bool(weight_fp8)), ctypes.byref(plan)) != 0:
+        raise ValueError("dims not supported by the fused decode kernels")
+    return plan
+
+
+def plan_kernels_ok(dims: LlamaDims, B: int, emit_rows: int = 0, weight_fp8: bool = False) -> bool:
+    """Whether every stage of ``step_plan(dims, B, emit_rows)``, ``kv_plan(dims)`` and
+    ``weight_plan(dims, weight_fp8)`` names a kernel the library instantiates, by the lookups its launchers use
+    (host only)."""
+    if weight_fp8:
+        wp = WeightPlan(w8=1)
+        rc = lib().p2pt_llama_plan_kernels_w(ctypes.byref(dims), B, emit_rows, ctypes.byref(wp))
+    else:
+        rc = lib().p2pt_llama_plan_kernels(ctypes.byref(dims), B, emit_rows)
     if rc < 0:
         raise ValueError("dims or row count not supported by the fused decode kernels")
     return rc == 0
@@ -769,6 +797,32 @@ def skinny_gemm(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def quantize_weight_fp8(w: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """One GEMM weight ``w`` (fp32 [N, K], as it sits in the fused table: folded and interleaved) to the FP8 weight
+    format (docs/WEIGHT_FP8.md): ``(q, scale)`` with ``scale[n] = max_k |w[n][k]| / 448`` (fp32; 1.0 for a row
+    whose maximum is zero or so small that the division underflows to zero) and ``q[n][k]`` the OCP e4m3fn byte,
+    round to nearest even, of ``w[n][k] / scale[n]`` (the division in fp32), as ``torch.float8_e4m3fn``. A row's
+    largest magnitude lands on +-448, so nothing saturates and no NaN byte is written. Non-finite weights are
+    refused. Plain torch on ``w``'s device: runs without a GPU."""
+    if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or w.dim() != 2:
+        raise TypeError("quantize_weight_fp8 takes an fp32 [N, K] tensor (fold and quantise in fp32, not through bf16)")
+    if not bool(torch.isfinite(w).all()):
+        raise ValueError("non-finite weight (NaN or inf): refusing to quantise it to FP8")
+    scale = w.abs().amax(1) / E4M3_MAX
+    scale = torch.where(scale > 0, scale, torch.ones_like(scale))
+    # |w / scale| <= 448 (1 + 2^-23): below 464, where the cast's rounding to nearest even still gives 448.
+    q = (w / scale[:, None]).to(torch.float8_e4m3fn)
+    return q.contiguous(), scale.contiguous()
+
+
+def dequantize_weight_fp8(q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """``q * scale`` per row in fp32: the weight the FP8 kernels compute with (one fp32 rounding per element, none
+    when the scales are powers of two)."""
+    if q.dtype == torch.uint8:
+        q = q.view(torch.float8_e4m3fn)
+    return q.float() * scale.float()[:, None]
+
+
 class FusedLlamaDecoder:
     """Host handle for the fused decode step (decode_fused.hip): 5 kernels per layer + 3
     (6 per layer with ``dims.qk_norm``: the per-head q/k RMSNorm of Qwen3 runs in a kernel of its own;
@@ -779,13 +833,24 @@ class FusedLlamaDecoder:
     written by the _KV8 epilogues / ``k_qknorm_rope`` variant and read by ``k_attn<D, G, true>``: the same
     kernel count again).
 
+    ``weight_fp8``: the five GEMM weights as OCP e4m3 bytes with one fp32 scale per output row
+    (docs/WEIGHT_FP8.md, ``quantize_weight_fp8``). The table keeps the layout above, 6, 7 or 8 entries per layer
+    behind the 3 or 4 global ones, with lm_head, wqkv, wo, w_gate_up and w_down as ``torch.float8_e4m3fn`` (or
+    uint8) [N, K] instead of bf16, and is followed by the scales: lm_head's (vocab,), then per layer wqkv's, wo's,
+    w_gate_up's and w_down's, each fp32 (N,) in the row order of its weight: 1 + 4 * n_layers more entries. Every
+    ``k_skinny`` is then its FP8-weight instantiation; the kernel count, ``step_plan`` and the workspace are the
+    same. The bf16 table is unchanged.
+
     Holds the weight pointer table and a zero-initialised workspace; ``step``
     validates the per-call tensors and launches on the current stream (capturable
     into a hipGraph: no host sync, no allocation, grids sized by the row count).
     """
 
-    def __init__(self, dims: LlamaDims, weights: list, k_cache: torch.Tensor, v_cache: torch.Tensor):
+    def __init__(self, dims: LlamaDims, weights: list, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                 weight_fp8: bool = False):
         self.dims = dims
+        self.weight_fp8 = bool(weight_fp8)
+        self._wplan = WeightPlan(w8=int(self.weight_fp8))
         dev = k_cache.device
         # The cache dtype against dims.kv_fp8 first (a host-only check): a mismatch would have every kernel read
         # and write rows of the wrong width.
@@ -800,9 +865,16 @@ class FusedLlamaDecoder:
         if dims.rope_table not in (0, 1):
             raise ValueError("dims.rope_table must be 0 or 1")
         g0 = 3 + dims.rope_table  # global entries ahead of the layers
+        per_layer = 8 if dims.qk_norm else 7 if dims.qkv_bias else 6
+        n_table = g0 + per_layer * dims.n_layers  # entries of the bf16 layout; the FP8 scales follow them
+        gemm_at = self._gemm_entries(dims, g0, per_layer) if self.weight_fp8 else {}
         for i, t in enumerate(weights):
             if dims.rope_table and i == 3:
                 _check_inv_freq(t, dims.D, dev)
+            elif i in gemm_at or (self.weight_fp8 and i >= n_table):
+                continue  # checked below, once the table's length is known to be the FP8 layout's
+            elif isinstance(t, torch.Tensor) and t.dtype in WEIGHT_FP8_DTYPES and t.dtype != torch.uint8:
+                raise TypeError(f"weight[{i}] is {t.dtype}: an FP8 weight table needs weight_fp8=True")
             else:
                 _check(t, torch.bfloat16, f"weight[{i}]", dev)
         L, Bmax, S, Hkv, D = k_cache.shape
@@ -812,13 +884,16 @@ class FusedLlamaDecoder:
             _check(c, c.dtype if dims.kv_fp8 else torch.bfloat16, name, dev)
         if v_cache.shape != k_cache.shape or v_cache.dtype != k_cache.dtype:
             raise ValueError("k_cache and v_cache must have the same shape and dtype")
-        per_layer = 8 if dims.qk_norm else 7 if dims.qkv_bias else 6
-        if len(weights) != g0 + per_layer * dims.n_layers:
+        if len(weights) != n_table + (1 + 4 * dims.n_layers if self.weight_fp8 else 0):
             raise ValueError(f"weight table: embed, final_norm, lm_head, "
                              + ("inv_freq, " if dims.rope_table else "") + f"then {per_layer} per layer "
                              "(wqkv, w_gate_up and lm_head with the preceding norm weight folded in"
                              + ("; q_norm and k_norm last)" if dims.qk_norm else
-                                "; bqkv last)" if dims.qkv_bias else ")"))
+                                "; bqkv last)" if dims.qkv_bias else ")")
+                             + ("; weight_fp8: then the fp32 row scales, lm_head's and four per layer"
+                                if self.weight_fp8 else ""))
+        if self.weight_fp8:
+            self._check_fp8_table(weights, gemm_at, n_table, dev)
         if dims.qk_norm:
             for L in range(dims.n_layers):
                 for j in (6, 7):
@@ -838,6 +913,37 @@ class FusedLlamaDecoder:
         self.k_cache, self.v_cache = k_cache, v_cache
         self.device = dev
         self._resid = None  # embed_pool's view of the workspace's resid buffer
+
+    @staticmethod
+    def _gemm_entries(dims, g0, per_layer) -> dict:
+        """Index in the weight table -> (name, N, K, index of its scale behind the table) of the five GEMMs."""
+        n_table = g0 + per_layer * dims.n_layers
+        at = {2: ("lm_head", dims.vocab, dims.dim, n_table)}
+        shapes = (("wqkv", 1, (dims.H + 2 * dims.Hkv) * dims.D, dims.dim), ("wo", 2, dims.dim, dims.H * dims.D),
+                  ("w_gate_up", 4, 2 * dims.ffn, dims.dim), ("w_down", 5, dims.dim, dims.ffn))
+        for L in range(dims.n_layers):
+            for j, (name, k, N, K) in enumerate(shapes):
+                at[g0 + per_layer * L + k] = (f"layer {L} {name}", N, K, n_table + 1 + 4 * L + j)
+        return at
+
+    @staticmethod
+    def _check_fp8_table(weights, gemm_at, n_table, dev) -> None:
+        """The FP8 entries of a weight table, on the host before any launch: every GEMM weight e4m3 (or uint8)
+        [N, K], contiguous, on the device and 8-byte aligned (a lane loads 8 bytes at a multiple of 8 from the
+        base: K is a multiple of 32); every scale fp32 (N,), contiguous and on the device."""
+        for i, (name, N, K, si) in gemm_at.items():
+            t, sc = weights[i], weights[si]
+            if not isinstance(t, torch.Tensor) or t.dtype not in WEIGHT_FP8_DTYPES:
+                raise TypeError(f"{name}: weight_fp8 is set, so the weight must be torch.float8_e4m3fn (or uint8), "
+                                f"got {getattr(t, 'dtype', type(t))}")
+            _check(t, t.dtype, name, dev)
+            if tuple(t.shape) != (N, K):
+                raise ValueError(f"{name}: shape {tuple(t.shape)} != ({N}, {K})")
+            if t.data_ptr() % 8:
+                raise ValueError(f"{name}: an FP8 weight must be 8-byte aligned (the kernels load 8 bytes per lane)")
+            _check(sc, torch.float32, f"{name} scale", dev)
+            if tuple(sc.shape) != (N,):
+                raise ValueError(f"{name} scale: shape {tuple(sc.shape)} != ({N},), one fp32 scale per output row")
 
     # Workspace buffers in the order p2pt_llama_ws_layout reports them.
     _WS_BUFFERS = (("resid", torch.bfloat16), ("q", torch.bfloat16), ("attn", torch.bfloat16), ("h", torch.bfloat16),
@@ -904,6 +1010,12 @@ class FusedLlamaDecoder:
             raise ValueError(f"rows must be 1..{limit} with matching pos/ids")
         if logits.shape != (B, d.vocab):
             raise ValueError("logits must be [B, vocab]")
+        if self.weight_fp8:
+            _ok(lib().p2pt_llama_decode_w(ctypes.byref(d), ctypes.byref(self._wplan), self._wptr, _p(self.k_cache),
+                                          _p(self.v_cache), _p(tokens), _p(pos), _p(slots), B, emit_rows,
+                                          _p(self.ws), self.ws.numel(), _p(logits), _p(ids), _stream(tokens)),
+                "llama_decode")
+            return
         _ok(lib().p2pt_llama_decode(ctypes.byref(d), self._wptr, _p(self.k_cache), _p(self.v_cache), _p(tokens),
                                     _p(pos), _p(slots), B, emit_rows, _p(self.ws), self.ws.numel(), _p(logits),
                                     _p(ids), _stream(tokens)), "llama_decode")

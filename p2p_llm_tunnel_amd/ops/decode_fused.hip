@@ -55,6 +55,13 @@ struct KvPlan {
   int qk_norm_kv8;  // k_qknorm_rope<D, TAB, true>: k and v appended as e4m3 (a QK-norm model with an FP8 cache)
 };
 KvPlan plan_kv(const LlamaDims& d) { return {d.kv_fp8, d.qk_norm ? d.kv_fp8 : 0}; }
+// The weight format of a step, beside StepPlan for the same reason. It is no field of LlamaDims either (whose
+// layout is pinned too): it travels as an argument of its own through the _w entry points. StepPlan does not
+// depend on it: FP8 weights change no grid, wave count, load batch or K part.
+struct WeightPlan {
+  int w8;  // k_skinny<.., 1>: the five GEMM weights are e4m3 bytes with an fp32 scale per output row
+};
+bool weights_ok(const WeightPlan& w) { return w.w8 == 0 || w.w8 == 1; }
 
 // One workgroup per tn subtiles of 16 >> kpl columns of one 16-row tile.
 //  - K parts (GemmArgs::kpl), where asked for (the d_model-wide O and down
@@ -199,9 +206,11 @@ GemmArgs operator+(GemmArgs a, Set set) {
   set(a);
   return a;
 }
-GemmArgs gemm(const void* x, const void* w) {  // M, N, K and kpl are the plan's: launch() fills them in
+// M, N, K and kpl are the plan's: launch() fills them in. wscale: the row scales of an FP8 weight (nullptr: bf16).
+GemmArgs gemm(const void* x, const void* w, const void* wscale = nullptr) {
   GemmArgs a{};
   a.x = static_cast<const uint16_t*>(x), a.w = static_cast<const uint16_t*>(w);
+  a.wscale = static_cast<const float*>(wscale);
   return a;
 }
 auto norm(const float* ss, int parts, float eps) {
@@ -237,15 +246,21 @@ using HeadDims = Ints<64, 128>;  // D of k_attn and k_qknorm_rope
 // G of k_attn, the GQA ratio H / Hkv (models/checkpoint.py mirrors it as _GQA_RATIOS). 5, 6 and 7 are the Qwen2 /
 // Qwen2.5 family's (40/8, 12/2, 14/2 and 28/4). 3 is absent: no checkpoint the loader accepts uses it.
 using GqaRatios = Ints<1, 2, 4, 5, 6, 7, 8>;
-using Flags = Ints<0, 1>;  // KV8 of k_attn; TAB and KV8 of k_qknorm_rope
+using Flags = Ints<0, 1>;  // KV8 of k_attn; TAB and KV8 of k_qknorm_rope; W8 of k_skinny
 using SkinnyWaves = Ints<4, 8>;
 using SkinnyTiles = Ints<1, 2>;
 using SkinnyBatches = Ints<1, 2, 4>;
 using SkinnyEpis = Ints<EPI_STORE, EPI_ROPE, EPI_SILU, EPI_RESID, EPI_ARGMAX, EPI_ROPE_BIAS, EPI_ROPE_TAB,
                         EPI_ROPE_BIAS_TAB, EPI_ROPE_KV8, EPI_ROPE_BIAS_KV8, EPI_ROPE_TAB_KV8, EPI_ROPE_BIAS_TAB_KV8>;
-constexpr bool skinny_exists(int nw, int tn, int epi, int um) {
+constexpr bool skinny_exists(int nw, int tn, int epi, int um, int w8) {
   // Two subtiles for the LM head and the standalone GEMM (plain STORE has both), one for every other epilogue.
   if (tn != (epi == EPI_ARGMAX ? 2 : 1) && !(epi == EPI_STORE && tn == 2)) return false;
+  // FP8 weights run the five GEMMs of a step only (the standalone GEMM stays bf16), so they carry what plan_gemm
+  // can give those: the LM head's fixed 4 waves with any load batch, and for the others the (nw, um) pairs of
+  // fixed_nw == 0 below. 47 instantiations beside the 66 of bf16.
+  if (w8 && epi == EPI_STORE && tn == 2) return false;
+  if (w8 && epi == EPI_ARGMAX) return nw == 4;
+  if (w8) return nw == 4 || um == 4;
   // The table and FP8-cache epilogues run QKV projections only, so they carry just the (nw, um) pairs plan_gemm
   // can give one (fixed_nw == 0): 4 waves up to 16 k-steps with um 1, 2 or 4, and 8 waves from 17 on, where a
   // wave's share is at least 3 k-steps and um is 4.
@@ -270,11 +285,11 @@ void pick(F&& f, int v, Ints<V...>, Rest... rest) {
 
 // The kernel a plan names, or nullptr where it is not instantiated.
 using SkinnyKernel = void (*)(GemmArgs);
-SkinnyKernel skinny_kernel(const GemmPlan& p) {
+SkinnyKernel skinny_kernel(const GemmPlan& p, int w8 = 0) {
   SkinnyKernel k = nullptr;
-  pick([&](auto nw, auto tn, auto epi, auto um) {
-    if constexpr (skinny_exists(nw, tn, epi, um)) k = k_skinny<nw, tn, epi, um>;
-  }, p.nw, SkinnyWaves{}, p.tn, SkinnyTiles{}, p.epi, SkinnyEpis{}, p.um, SkinnyBatches{});
+  pick([&](auto nw, auto tn, auto epi, auto um, auto f8) {
+    if constexpr (skinny_exists(nw, tn, epi, um, f8)) k = k_skinny<nw, tn, epi, um, f8>;
+  }, p.nw, SkinnyWaves{}, p.tn, SkinnyTiles{}, p.epi, SkinnyEpis{}, p.um, SkinnyBatches{}, w8, Flags{});
   return k;
 }
 using AttnKernel = decltype(&k_attn<64, 1, false>);
@@ -293,14 +308,16 @@ QkNormKernel qknorm_kernel(int D, int table, int kv8) {
 
 // ------------------------------------------------------------ launches
 // Each checks its arguments, looks its kernel up and launches it; a plan that names no kernel is hipErrorInvalidValue.
-hipError_t launch(const GemmPlan& p, GemmArgs a, hipStream_t s) {
+// w8: the FP8-weight instantiation (WeightPlan::w8), which reads a.wscale and is refused without it.
+hipError_t launch(const GemmPlan& p, GemmArgs a, hipStream_t s, int w8 = 0) {
+  if ((w8 != 0) != (a.wscale != nullptr)) return hipErrorInvalidValue;
   if (p.kpl < 0 || p.kpl > kMaxKpl || (p.ss_in > 0) != (a.ss_part != nullptr)) return hipErrorInvalidValue;
   if (p.kpl && (p.tn != 1 || (p.M << p.kpl) > 16 || p.K % (32 << p.kpl))) return hipErrorInvalidValue;
   // The bias is added once, after the K-split reduction: never with K parts, never without a bias.
   if (epi_has_bias(p.epi) && (p.kpl != 0 || a.bias == nullptr)) return hipErrorInvalidValue;
   // A table epilogue reads its table unconditionally: never without one.
   if (epi_has_table(p.epi) && a.inv_freq == nullptr) return hipErrorInvalidValue;
-  const SkinnyKernel k = skinny_kernel(p);
+  const SkinnyKernel k = skinny_kernel(p, w8);
   if (!k) return hipErrorInvalidValue;
   a.M = p.M, a.N = p.N, a.K = p.K, a.kpl = p.kpl;
   hipLaunchKernelGGL(k, dim3(p.grid_x, p.grid_y), dim3(p.nw * 64), 0, s, a);
@@ -401,20 +418,33 @@ int p2pt_llama_kv_plan(const LlamaDims* d, KvPlan* out) {
 // Whether every stage of the plans above names a kernel that exists, by the launchers' own lookups (host only).
 // 0: all do; 1 + n: stage n, counting qkv_first, qkv, qk_norm, attn, o, gate_up, down, lm_head, is the first that
 // does not; -1: dims or row count refused.
-int p2pt_llama_plan_kernels(const LlamaDims* d, int B, int emit_rows) {
-  if (!dims_ok(*d) || !rows_ok(B)) return -1;
+int p2pt_llama_plan_kernels_w(const LlamaDims* d, int B, int emit_rows, const WeightPlan* wp) {
+  if (!dims_ok(*d) || !rows_ok(B) || !weights_ok(*wp)) return -1;
   const StepPlan P = plan_step(*d, B, emit_rows);
   const KvPlan KV = plan_kv(*d);
-  const bool found[] = {skinny_kernel(P.qkv_first) != nullptr,
-                        skinny_kernel(P.qkv) != nullptr,
+  const int w8 = wp->w8;
+  const bool found[] = {skinny_kernel(P.qkv_first, w8) != nullptr,
+                        skinny_kernel(P.qkv, w8) != nullptr,
                         !P.qk_norm_grid || qknorm_kernel(d->D, P.qk_norm_table, KV.qk_norm_kv8) != nullptr,
                         attn_kernel(P.attn.D, P.attn.G, KV.attn_kv8) != nullptr,
-                        skinny_kernel(P.o) != nullptr,
-                        skinny_kernel(P.gate_up) != nullptr,
-                        skinny_kernel(P.down) != nullptr,
-                        skinny_kernel(P.lm_head) != nullptr};
+                        skinny_kernel(P.o, w8) != nullptr,
+                        skinny_kernel(P.gate_up, w8) != nullptr,
+                        skinny_kernel(P.down, w8) != nullptr,
+                        skinny_kernel(P.lm_head, w8) != nullptr};
   for (int n = 0; n < 8; n++)
     if (!found[n]) return 1 + n;
+  return 0;
+}
+int p2pt_llama_plan_kernels(const LlamaDims* d, int B, int emit_rows) {
+  const WeightPlan bf16{0};
+  return p2pt_llama_plan_kernels_w(d, B, emit_rows, &bf16);
+}
+
+// The weight format of a step for weight_fp8 in {0, 1} (host only), beside the plans above.
+int p2pt_llama_weight_plan(const LlamaDims* d, int weight_fp8, WeightPlan* out) {
+  const WeightPlan w{weight_fp8};
+  if (!dims_ok(*d) || !weights_ok(w)) return int(hipErrorInvalidValue);
+  *out = w;
   return 0;
 }
 
@@ -443,11 +473,16 @@ int p2pt_max_rows() { return kMaxM; }
 //   slots int32 [B] or nullptr: cache slot of each row (< max_batch). Rows of one
 //     slot at consecutive positions form a prefill chunk: every row's K/V is
 //     appended before attention runs, and each row attends up to its own position.
-int p2pt_llama_decode(const LlamaDims* dp, const void* const* w, void* k_cache, void* v_cache, const int64_t* tokens,
-                      const int* pos, const int* slots, int B, int emit_rows, void* ws, size_t ws_bytes, void* logits,
-                      int64_t* ids, void* stream) {
+//   FP8 weights (p2pt_llama_decode_w with WeightPlan::w8): the same table with lm_head, wqkv, wo, w_gate_up and
+//      w_down as e4m3 bytes [N][K] (8-byte aligned), quantised after the fold and the interleave, followed by the
+//      fp32 row scales: lm_head's [vocab], then per layer wqkv's, wo's, w_gate_up's and w_down's, each [N] in the
+//      row order of its weight. Every other entry (embed, norms, inv_freq, bqkv, q_norm, k_norm) is as above.
+int p2pt_llama_decode_w(const LlamaDims* dp, const WeightPlan* wp, const void* const* w, void* k_cache, void* v_cache,
+                        const int64_t* tokens, const int* pos, const int* slots, int B, int emit_rows, void* ws,
+                        size_t ws_bytes, void* logits, int64_t* ids, void* stream) {
   const LlamaDims d = *dp;
-  if (!dims_ok(d) || !rows_ok(B) || (!slots && B > d.max_batch)) return int(hipErrorInvalidValue);
+  if (!dims_ok(d) || !rows_ok(B) || (!slots && B > d.max_batch) || !weights_ok(*wp)) return int(hipErrorInvalidValue);
+  const int w8 = wp->w8;
   const Workspace W = carve(d, static_cast<uint8_t*>(ws));
   if (ws_bytes < W.bytes) return int(hipErrorInvalidValue);
   const StepPlan P = plan_step(d, B, emit_rows);
@@ -461,20 +496,25 @@ int p2pt_llama_decode(const LlamaDims* dp, const void* const* w, void* k_cache, 
   hipLaunchKernelGGL(k_embed, dim3(B), dim3(256), 0, s, static_cast<const uint16_t*>(w[0]), tokens, W.resid, W.ss,
                      d.dim, d.vocab);
   if (failed(hipGetLastError())) return int(e);
+  const int per_layer = d.qk_norm ? 8 : d.qkv_bias ? 7 : 6;
+  // FP8 weights: the row scales follow the table. nullptr for bf16, where launch() wants none.
+  const void* const* sc = w + 3 + d.rope_table + per_layer * d.n_layers;
+  auto scale = [&](int i) { return w8 ? sc[i] : nullptr; };  // 0: lm_head; 1 + 4 L + j: wqkv, wo, w_gate_up, w_down
   for (int L = 0; L < d.n_layers; L++) {
     // attn_norm, wqkv, wo, ffn_norm, w_gate_up, w_down (+ q_norm, k_norm, or + bqkv)
-    const void* const* wl = w + 3 + d.rope_table + (d.qk_norm ? 8 : d.qkv_bias ? 7 : 6) * L;
+    const void* const* wl = w + 3 + d.rope_table + per_layer * L;
     uint16_t* kc = reinterpret_cast<uint16_t*>(static_cast<uint8_t*>(k_cache) + L * layer_cache);
     uint16_t* vc = reinterpret_cast<uint16_t*>(static_cast<uint8_t*>(v_cache) + L * layer_cache);
     const GemmPlan& qkv = L ? P.qkv : P.qkv_first;
-    const GemmArgs qkv_in = gemm(W.resid, wl[1]) + norm(W.ss, qkv.ss_in, d.eps);
+    const GemmArgs qkv_in = gemm(W.resid, wl[1], scale(1 + 4 * L)) + norm(W.ss, qkv.ss_in, d.eps);
     const GemmArgs to_qkv =
         d.qk_norm ? qkv_in + store(W.qkv)
                   : qkv_in + rope(d, pos, slots, W.q, kc, vc, d.qkv_bias ? wl[6] : nullptr, inv_freq);
-    const GemmArgs to_o = gemm(W.attn, wl[2]) + resid(W.resid, W.ss);
-    const GemmArgs to_gate_up = gemm(W.resid, wl[4]) + norm(W.ss, P.gate_up.ss_in, d.eps) + store(W.h);
-    const GemmArgs to_down = gemm(W.h, wl[5]) + resid(W.resid, W.ss);
-    if (failed(launch(qkv, to_qkv, s))) return int(e);
+    const GemmArgs to_o = gemm(W.attn, wl[2], scale(2 + 4 * L)) + resid(W.resid, W.ss);
+    const GemmArgs to_gate_up =
+        gemm(W.resid, wl[4], scale(3 + 4 * L)) + norm(W.ss, P.gate_up.ss_in, d.eps) + store(W.h);
+    const GemmArgs to_down = gemm(W.h, wl[5], scale(4 + 4 * L)) + resid(W.resid, W.ss);
+    if (failed(launch(qkv, to_qkv, s, w8))) return int(e);
     if (P.qk_norm_grid) {
       const QkNormArgs qn{W.qkv, static_cast<const uint16_t*>(wl[6]), static_cast<const uint16_t*>(wl[7]), pos, slots,
                           d.max_batch, W.q, kc, vc, d.H, d.Hkv, d.max_seq, d.eps, log2f(d.theta),
@@ -485,15 +525,22 @@ int p2pt_llama_decode(const LlamaDims* dp, const void* const* w, void* k_cache, 
     if (failed(launch_attn(P.attn, KV.attn_kv8, W.q, kc, vc, pos, slots, d.max_batch, W.part_o, W.part_ml, W.counters, W.attn, d.H,
                            d.Hkv, d.max_seq, s)))
       return int(e);
-    if (failed(launch(P.o, to_o, s))) return int(e);
-    if (failed(launch(P.gate_up, to_gate_up, s))) return int(e);
-    if (failed(launch(P.down, to_down, s))) return int(e);
+    if (failed(launch(P.o, to_o, s, w8))) return int(e);
+    if (failed(launch(P.gate_up, to_gate_up, s, w8))) return int(e);
+    if (failed(launch(P.down, to_down, s, w8))) return int(e);
   }
   const GemmArgs to_logits =
-      gemm(W.resid, w[2]) + norm(W.ss, P.lm_head.ss_in, d.eps) + argmax(logits, W.am_val, W.am_idx);
-  if (failed(launch(P.lm_head, to_logits, s))) return int(e);
+      gemm(W.resid, w[2], scale(0)) + norm(W.ss, P.lm_head.ss_in, d.eps) + argmax(logits, W.am_val, W.am_idx);
+  if (failed(launch(P.lm_head, to_logits, s, w8))) return int(e);
   hipLaunchKernelGGL(k_argmax_merge, dim3(P.emit_rows), dim3(256), 0, s, W.am_val, W.am_idx, P.am_parts, ids);
   return int(hipGetLastError());
+}
+int p2pt_llama_decode(const LlamaDims* dp, const void* const* w, void* k_cache, void* v_cache, const int64_t* tokens,
+                      const int* pos, const int* slots, int B, int emit_rows, void* ws, size_t ws_bytes, void* logits,
+                      int64_t* ids, void* stream) {
+  const WeightPlan bf16{0};
+  return p2pt_llama_decode_w(dp, &bf16, w, k_cache, v_cache, tokens, pos, slots, B, emit_rows, ws, ws_bytes, logits,
+                             ids, stream);
 }
 
 // Standalone skinny GEMM (tests/benchmarks): out[M][N] = bf16(x[M][K] @ w[N][K]^T), M <= 64.

@@ -19,6 +19,8 @@
 //                        and k_attn<D, G, true> reads them: the same kernel count)
 //     k_attn            GQA flash-decoding split-K; the last split to finish
 //                        for a (sequence, KV head) merges the partials in-kernel
+//     (FP8 weights:      every k_skinny is its W8 instantiation: e4m3 weight bytes, 8-byte loads, and the
+//                        column's fp32 scale on the accumulator ahead of 1/rms: the same kernel count)
 //     k_skinny<RESID>    O projection -> residual add -> per-row sum-of-squares
 //                        partials for the next norm
 //     k_skinny<SILU>     RMSNorm (ffn_norm) -> gate/up GEMM -> SwiGLU
@@ -27,7 +29,7 @@
 //                        per-block greedy winners
 //   k_argmax_merge       one block per row merges the winners
 //
-// k_skinny<NW, TN, EPI, UM>, k_attn<D, G, KV8> and k_qknorm_rope<D, TAB, KV8> are templates; which instantiations
+// k_skinny<NW, TN, EPI, UM, W8>, k_attn<D, G, KV8> and k_qknorm_rope<D, TAB, KV8> are templates; which instantiations
 // exist is stated once, as lists of parameter values and one predicate, in decode_fused.hip, and a plan that names
 // any other is refused there. The RoPE epilogue of a model is rope_epi(bias, table, kv8) below.
 //
@@ -59,6 +61,7 @@
 #include "bf16_common.h"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace {
 
@@ -142,6 +145,9 @@ struct GemmArgs {
   // blocks of the 16 x 16 accumulator are summed in the epilogue. It needs
   // spare MFMA rows: a decode step of <= 16 / P tokens.
   int kpl;
+  // FP8 weights (k_skinny<.., W8 = 1>): w holds N * K e4m3 bytes and wscale the fp32 scale of each output row,
+  // [N] in the row order of w (interleaved like its rows). Not read by the bf16 kernels.
+  const float* wscale;
 };
 
 // log2 of the output columns per 16-lane subtile: 16, 8 or 4 for 1, 2 or 4 K parts.
@@ -223,48 +229,62 @@ __device__ __forceinline__ __amdgpu_buffer_rsrc_t rsrc(const void* p, uint32_t b
 __device__ __forceinline__ uint4 buf_ld16(__amdgpu_buffer_rsrc_t r, uint32_t off) {
   return __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(r, off, 0, 0));
 }
+__device__ __forceinline__ uint2 buf_ld8(__amdgpu_buffer_rsrc_t r, uint32_t off) {
+  return __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, 0));
+}
 
 // One batch of up to UM consecutive 32-wide k-steps [s, min(s + UM, s1)):
 // every load of the batch is issued before any of it is used.
-template <int UM, int TN>
+// W8 (FP8 weights): the lane's B fragment of a k-step is its 8 k-values as 8 e4m3 bytes, one 8-byte load at a
+// k-step stride of 32 bytes, decoded to the bf16 fragment (e4m3x8_to_bf16x8: exact) just ahead of its MFMA. The A
+// operand, the order of the k-steps and the MFMA are the bf16 kernel's, so on the decoded weights the accumulator
+// is the bf16 kernel's bit for bit.
+template <int UM, int TN, int W8>
 struct Batch {
-  uint4 b[UM][TN];
+  std::conditional_t<W8 != 0, uint2, uint4> b[UM][TN];
   uint4 a[UM];
 };
 
-template <int UM, int TN>
-__device__ __forceinline__ void load_batch(Batch<UM, TN>& bt, __amdgpu_buffer_rsrc_t ra, uint32_t xoff,
+template <int UM, int TN, int W8>
+__device__ __forceinline__ void load_batch(Batch<UM, TN, W8>& bt, __amdgpu_buffer_rsrc_t ra, uint32_t xoff,
                                            __amdgpu_buffer_rsrc_t rw, const uint32_t (&woff)[TN], int s, int s1) {
 #pragma unroll
   for (int u = 0; u < UM; u++) {
     const bool in = s + u < s1;
-    const uint32_t su = uint32_t(s + u) * 64u;  // bytes per 32-wide k-step
+    const uint32_t su = uint32_t(s + u) * 64u;  // bytes per 32-wide k-step (bf16; half that for e4m3 weights)
 #pragma unroll
-    for (int t = 0; t < TN; t++) bt.b[u][t] = buf_ld16(rw, in ? woff[t] + su : kOob);
+    for (int t = 0; t < TN; t++) {
+      if constexpr (W8) bt.b[u][t] = buf_ld8(rw, in ? woff[t] + (su >> 1) : kOob);
+      else bt.b[u][t] = buf_ld16(rw, in ? woff[t] + su : kOob);
+    }
     bt.a[u] = buf_ld16(ra, in ? xoff + su : kOob);
   }
 }
 
-template <int UM, int TN>
-__device__ __forceinline__ void mma_apply(frag4 (&acc)[TN], const Batch<UM, TN>& bt) {
+template <int UM, int TN, int W8>
+__device__ __forceinline__ void mma_apply(frag4 (&acc)[TN], const Batch<UM, TN, W8>& bt) {
 #pragma unroll
   for (int u = 0; u < UM; u++)
 #pragma unroll
-    for (int t = 0; t < TN; t++)
-      acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(bt.a[u]), as_frag(bt.b[u][t]), acc[t], 0, 0, 0);
+    for (int t = 0; t < TN; t++) {
+      uint4 b;
+      if constexpr (W8) b = e4m3x8_to_bf16x8(bt.b[u][t]);
+      else b = bt.b[u][t];
+      acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(bt.a[u]), as_frag(b), acc[t], 0, 0, 0);
+    }
 }
 
 // The wave's k-steps [s0, s1), one batch at a time.
-template <int UM, int TN>
+template <int UM, int TN, int W8>
 __device__ __forceinline__ void mma_stream(frag4 (&acc)[TN], __amdgpu_buffer_rsrc_t ra, uint32_t xoff,
                                            __amdgpu_buffer_rsrc_t rw, const uint32_t (&woff)[TN], int s0, int s1) {
   for (int s = s0; s < s1; s += UM) {
-    Batch<UM, TN> p;
-    load_batch<UM, TN>(p, ra, xoff, rw, woff, s, s1);
+    Batch<UM, TN, W8> p;
+    load_batch<UM, TN, W8>(p, ra, xoff, rw, woff, s, s1);
     // Keep every load of the batch ahead of the first MFMA: left alone, the
     // scheduler interleaves them and the batch pays several memory latencies.
     __builtin_amdgcn_sched_barrier(0);
-    mma_apply<UM, TN>(acc, p);
+    mma_apply<UM, TN, W8>(acc, p);
   }
 }
 
@@ -274,7 +294,12 @@ __device__ __forceinline__ void mma_stream(frag4 (&acc)[TN], __amdgpu_buffer_rsr
 // workgroup (blockIdx.y). ROPE and SILU take weights whose rows are
 // interleaved in pairs (RoPE partners d, d + D/2 of a head; gate_j, up_j), so
 // a pair sits in lanes c, c^1.
-template <int NW, int TN, int EPI, int UM>
+// W8: the weight is N * K e4m3 bytes with one fp32 scale per output row (GemmArgs::wscale). The stream is as above
+// with 8-byte B loads (Batch); the scale of the lane's column multiplies the accumulator once, in fp32, after the
+// K-split reduction and the K-parts diagonal sum and ahead of 1/rms: v = (v * s[col]) * rs. Everything after that
+// is the bf16 kernel's epilogue. With power-of-two scales the product is exact, so the kernel matches the bf16
+// kernel on the weights decode(q) * s bit for bit.
+template <int NW, int TN, int EPI, int UM, int W8 = 0>
 __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
   __shared__ float red[NW][TN][4][kWave];
   __shared__ float red_ss[NW][kWave];
@@ -313,13 +338,14 @@ __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
   // Byte offsets of this lane's A row and weight rows at k-step 0; rows past
   // M read as zeros (kOob).
   const __amdgpu_buffer_rsrc_t ra = rsrc(a.x, uint32_t(a.M) * uint32_t(a.K) * 2u);
-  const __amdgpu_buffer_rsrc_t rw = rsrc(a.w, uint32_t(a.N) * uint32_t(a.K) * 2u);
+  constexpr uint32_t kWb = W8 ? 1u : 2u;  // bytes per weight element
+  const __amdgpu_buffer_rsrc_t rw = rsrc(a.w, uint32_t(a.N) * uint32_t(a.K) * kWb);
   const uint32_t xoff = a_ok ? (uint32_t(m0 + m_a) * uint32_t(a.K) + uint32_t(p_a * Kp + kq)) * 2u : kOob;
   const int p_b = (lane & 15) >> cwl;  // K part of this lane's weight column
   uint32_t woff[TN];
 #pragma unroll
   for (int t = 0; t < TN; t++)
-    woff[t] = (uint32_t(tile_col<TN>(bx, t, lane & 15, cwl)) * uint32_t(a.K) + uint32_t(p_b * Kp + kq)) * 2u;
+    woff[t] = (uint32_t(tile_col<TN>(bx, t, lane & 15, cwl)) * uint32_t(a.K) + uint32_t(p_b * Kp + kq)) * kWb;
 
   // C layout: row m = m0 + 4*(lane>>4) + r, column = tile_col(.., lane & 15).
   const int lrow0 = (lane >> 4) << 2, mrow0 = m0 + lrow0;
@@ -361,10 +387,21 @@ __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
     if (wv == 0) tab_freq = a.inv_freq[(tile_col<TN>(bx, 0, c, cwl) % a.D) >> 1];
   }
 
+  // W8: this lane's column scales, loaded by wave 0 ahead of the weight stream like bias and tab_freq. tile_col
+  // masks the lane column to the tile width, so under K parts the lanes past it index their own column's scale,
+  // below N like every column of the grid (grid_x * TN * 2^cwl == N).
+  float wsc[W8 ? TN : 1];
+  if constexpr (W8) {
+    if (wv == 0) {
+#pragma unroll
+      for (int t = 0; t < TN; t++) wsc[t] = a.wscale[tile_col<TN>(bx, t, c, cwl)];
+    }
+  }
+
   frag4 acc[TN];
 #pragma unroll
   for (int t = 0; t < TN; t++) acc[t] = frag4{0.f, 0.f, 0.f, 0.f};
-  mma_stream<UM, TN>(acc, ra, xoff, rw, woff, s0, s1);
+  mma_stream<UM, TN, W8>(acc, ra, xoff, rw, woff, s0, s1);
 
   if (norm) {
     float ssum = 0.f;
@@ -409,6 +446,13 @@ __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
         for (int p = 0; p < kparts; p++) sum += cbuf[(row * kparts + p) * 17 + c + (p << cwl)];
       v[0][r] = sum;
     }
+  }
+
+  if constexpr (W8) {
+#pragma unroll
+    for (int t = 0; t < TN; t++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) v[t][r] *= wsc[t];
   }
 
   if (norm) {
@@ -1040,6 +1084,12 @@ int attn_slots(int B, int Hkv, int max_seq) {
 //    (<128,4> 184 VGPRs, <128,8> 72 bytes). A layout with 16-byte loads (D / 16 lanes per row) was not tried.
 //    What ships, against bf16 (profiles/kv_fp8.json): batch 16 at 32k tokens 1.987 -> 1.479 ms (small) and
 //    4.298 -> 3.701 (Llama-3.2-1B's shape); batch 1 0.2-0.6 % slower at every context.
+//  - FP8 weights, k_skinny<.., W8 = 1>: what ships is 8-byte B loads at a 32-byte k-step stride, decoded to the bf16
+//    fragment ahead of the MFMA (at most 88 VGPRs, no spills; the bf16 instantiations keep their register counts).
+//    Against bf16 (profiles/weight_fp8.json, ctx 1024): Llama-3.1-8B's shape 3.210 -> 2.835 ms at batch 1 and
+//    4.713 -> 4.338 at 16, small 0.368 -> 0.339 and 0.521 -> 0.498, tiny 0.140 -> 0.136: never slower, far from 2x.
+//    A weight layout with K permuted offline so that one 16-byte load feeds two k-steps was not tried and not
+//    measured; neither was decoding through FP8 or scaled MFMA (the activation stays bf16).
 //  - A two-deep load-batch pipeline (every projection +0.5-1.8 us) and one
 //    workgroup per CU forced through padded LDS (QKV 5.9 -> 9.9 us)
 //    (profiles/r02/decode/decode_sweep_s8.log).

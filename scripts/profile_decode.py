@@ -45,13 +45,17 @@ def main():
                          "\"low_freq_factor\": 1, \"high_freq_factor\": 4, \"original_max_seq\": 8192}")
     ap.add_argument("--name", default=None, help="label of a --cfg model in the result line")
     ap.add_argument("--checkpoint", default=None, help="load this HF Llama checkpoint instead of a random --config")
+    ap.add_argument("--weight-dtype", choices=("bf16", "fp8"), default="bf16",
+                    help="format of the GEMM weights: bf16, or fp8 (e4m3 with per-row scales, docs/WEIGHT_FP8.md; "
+                         "the fused step only)")
     ap.add_argument("--loop", action="store_true",
                     help="device-side autoregression: one graph = the fused step (ids feed the next step's "
                          "tokens in place) + pos += 1, no host copies per step")
     a = ap.parse_args()
     if a.checkpoint:
         from p2p_llm_tunnel_amd.models.checkpoint import load_llama
-        m = load_llama(a.checkpoint, device="cuda", max_batch=a.batch, fused=not a.unfused)
+        m = load_llama(a.checkpoint, device="cuda", max_batch=a.batch, fused=not a.unfused,
+                       weight_dtype=a.weight_dtype)
         a.config = os.path.basename(os.path.normpath(a.checkpoint))
     else:
         if a.cfg:
@@ -65,7 +69,7 @@ def main():
         if a.set:
             cfg = dataclasses.replace(cfg, **{k: int(v) for k, v in (x.split("=", 1) for x in a.set)})
             a.config += "[" + ",".join(a.set) + "]"
-        m = TinyLlama(cfg, device="cuda", max_batch=a.batch, fused=not a.unfused)
+        m = TinyLlama(cfg, device="cuda", max_batch=a.batch, fused=not a.unfused, weight_dtype=a.weight_dtype)
     m.k_cache.normal_()
     m.v_cache.normal_()
     if a.loop:
@@ -88,6 +92,7 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     print(json.dumps({"config": a.config, "batch": B, "ctx": a.ctx, "steps": a.steps, "graph": not a.eager, "fused": not a.unfused,
+                      "weight_dtype": a.weight_dtype, "weight_bytes": m.weight_bytes()["total"],
                       "ms_per_step": dt * 1e3 / a.steps, "tokens_per_s": B * a.steps / dt}))
 
 
@@ -117,6 +122,7 @@ def loop(m, a):
     dt = time.perf_counter() - t0
     nbytes = sum(t.numel() * t.element_size() for t in dec.weights[2:]) + m.embed.shape[1] * 2 * B
     print(json.dumps({"config": a.config, "batch": B, "ctx": a.ctx, "steps": a.steps, "graph": True, "loop": True,
+                      "weight_dtype": a.weight_dtype,
                       "ms_per_step": dt * 1e3 / a.steps, "tokens_per_s": B * a.steps / dt,
                       "weight_TBps": nbytes / (dt / a.steps) / 1e12}))
 
