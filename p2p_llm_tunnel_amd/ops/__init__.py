@@ -140,6 +140,7 @@ MAX_EMBED_JOBS = 16  # jobs per launch of embed_pool_ (embed_pool.hip's kMaxJobs
 MAX_LOGIT_BIAS = 300  # entries of a slot's logit_bias list (penalty.hip's kMaxBias; the OpenAI API's limit)
 KV_FP8_DTYPES = (torch.float8_e4m3fn, torch.uint8)  # cache dtypes of a decoder with dims.kv_fp8 (the same bytes)
 WEIGHT_FP8_DTYPES = KV_FP8_DTYPES  # GEMM-weight dtypes of a decoder with weight_fp8 (the same bytes)
+GEMM_OPERAND_LIMIT = 1 << 31  # bytes: every k_skinny operand stays below it (decode_fused_kernels.h's kOob)
 E4M3_MAX = 448.0  # the largest finite e4m3fn value: a row's largest magnitude quantises to it
 MAX_TOP_LOGPROBS = 20  # top (id, logprob) pairs per row of logprobs_ (logprobs.hip's kMaxTop; the OpenAI API's limit)
 
@@ -783,15 +784,21 @@ def pack_sampling(temperature: float, top_k: int, top_p: float, seed: int, count
 
 
 def skinny_gemm(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
-    """bf16(x @ w.T) for a few rows on MFMA (decode-shaped GEMM). x: [M<=64, K]; w: [N, K]."""
-    _check(x, torch.bfloat16, "x")
-    _check(w, torch.bfloat16, "w", x.device)
+    """bf16(x @ w.T) for a few rows on MFMA (decode-shaped GEMM). x: [M<=64, K]; w: [N, K], each below 2 GiB:
+    the kernel addresses both with 32-bit byte offsets, and a larger operand would read as zeros without a fault.
+    The shapes are judged first, from the shapes alone, so a refusal needs no device."""
+    if not isinstance(x, torch.Tensor) or not isinstance(w, torch.Tensor):
+        raise TypeError("x and w must be tensors")
     if x.dim() != 2 or w.dim() != 2 or x.shape[1] != w.shape[1]:
         raise ValueError("shapes must be x [M, K], w [N, K]")
     M, K = x.shape
     N = w.shape[0]
     if not 1 <= M <= MAX_ROWS or N % 32 or K % 32:
         raise ValueError(f"need 1 <= M <= {MAX_ROWS}, N % 32 == 0, K % 32 == 0")
+    if max(M, N) * K * 2 >= GEMM_OPERAND_LIMIT:
+        raise ValueError(f"x [{M}, {K}] and w [{N}, {K}] must each stay below 2 GiB (32-bit byte offsets)")
+    _check(x, torch.bfloat16, "x")
+    _check(w, torch.bfloat16, "w", x.device)
     out = torch.empty(M, N, dtype=x.dtype, device=x.device)
     _ok(lib().p2pt_skinny_gemm(_p(x), _p(w), _p(out), M, N, K, _stream(x)), "skinny_gemm")
     return out

@@ -545,7 +545,10 @@ int p2pt_llama_decode(const LlamaDims* dp, const void* const* w, void* k_cache, 
 
 // Standalone skinny GEMM (tests/benchmarks): out[M][N] = bf16(x[M][K] @ w[N][K]^T), M <= 64.
 int p2pt_skinny_gemm(const void* x, const void* w, void* out, int M, int N, int K, void* stream) {
-  if (!rows_ok(M) || N % 32 || K <= 0 || K % 32) return int(hipErrorInvalidValue);
+  if (!rows_ok(M) || N <= 0 || N % 32 || K <= 0 || K % 32) return int(hipErrorInvalidValue);
+  // k_skinny's 32-bit byte offsets and descriptor sizes: both operands below kOob (2 GiB), as dims_ok keeps
+  // the step's. A larger one would wrap its descriptor's size and read as zeros, without a fault.
+  if (size_t(N) * size_t(K) * 2 >= kOob || size_t(M) * size_t(K) * 2 >= kOob) return int(hipErrorInvalidValue);
   const GemmPlan p = plan_gemm(EPI_STORE, 2, M, N, K);
   return int(launch(p, gemm(x, w) + store(out), static_cast<hipStream_t>(stream)));
 }

@@ -405,12 +405,14 @@ def worst(got, ref_bound):
     return torch.where(torch.isnan(r), torch.full_like(r, float("inf")), r).max().item()
 
 
-def stage_ratios(case, W, obs, layer=0, qkv_stage=stage_qkv):
+def stage_ratios(case, W, obs, layer=0, qkv_stage=stage_qkv, inp=None):
     """Largest |observed - reference| / bound of every stage of ``layer``, each reference computed from the
     observed inputs of that stage alone. Layer 0 starts from embed[token]; a later layer from its observed input
     rows ``obs["x0"]``, and ``obs`` then holds that layer's q, attn, r1, h, r2 and its own cache as kc, vc.
-    ``qkv_stage(case, W, x0, pos, layer)`` gives the (q, k, v) references of the model's family."""
-    inp = inputs(case)
+    ``qkv_stage(case, W, x0, pos, layer)`` gives the (q, k, v) references of the model's family. ``inp``: the
+    tokens, pos and slots of a case whose inputs are not ``inputs(case)``'s (tests/test_gpu_fused_served.py builds
+    its wide layers on the device, and runs this under ``torch.device("cuda")`` with every tensor there)."""
+    inp = inp if inp is not None else inputs(case)
     c, B = case.cfg, case.rows
     emit = case.emit_rows or B
     rows = torch.arange(B)
