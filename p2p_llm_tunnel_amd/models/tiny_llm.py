@@ -59,7 +59,8 @@ CONFIGS = {
 
 KV_DTYPES = {"bf16": torch.bfloat16, "fp8": torch.float8_e4m3fn}  # TinyLlama(kv_dtype=): the caches' dtype
 WEIGHT_DTYPES = ("bf16", "fp8")  # TinyLlama(weight_dtype=): the format of the five GEMM weights
-GEMM_WEIGHTS = ("wqkv", "wo", "w_gate_up", "w_down")  # a layer's GEMM weights, in the order of their scales
+GEMM_WEIGHTS = ops.LAYER_GEMMS  # a layer's GEMM weights, in the order of their scales
+FOLDED_NORM = {"wqkv": "attn_norm", "w_gate_up": "ffn_norm", "lm_head": "final_norm"}  # GEMM: the norm in its columns
 
 
 def _pairs(n, device):  # [0, n, 1, n + 1, ...]
@@ -67,9 +68,10 @@ def _pairs(n, device):  # [0, n, 1, n + 1, ...]
 
 
 def fused_row_perm(cfg: "LlamaConfig", name: str, device) -> torch.Tensor | None:
-    """The row order of GEMM weight ``name`` in the fused table: row i of the table is row perm[i] of the plain
-    weight (RoPE partners of a head, gate_j / up_j, in pairs); None where the table keeps the plain order."""
-    if name == "wqkv" and not cfg.qk_norm:
+    """The row order of entry ``name`` in the fused table: row i of the table is row perm[i] of the plain weight
+    (RoPE partners of a head, for wqkv and its bias; gate_j / up_j, in pairs); None where the table keeps the plain
+    order."""
+    if name in ("wqkv", "bqkv") and not cfg.qk_norm:
         heads = cfg.n_heads + 2 * cfg.n_kv_heads
         return (torch.arange(heads, device=device)[:, None] * cfg.head_dim
                 + _pairs(cfg.head_dim // 2, device)[None, :]).flatten()
@@ -93,14 +95,23 @@ def quantize_layer_(cfg: "LlamaConfig", L: dict) -> dict:
     """One layer's four GEMM weights to FP8 in place: ``L[name]`` (bf16) gives way to ``L[name + "_q"]`` (e4m3,
     folded and interleaved as the fused table wants it) and ``L[name + "_s"]`` (fp32 row scales). The loader calls
     it layer by layer, so the bf16 and FP8 copies of all layers are never resident together."""
-    for name, norm in zip(GEMM_WEIGHTS, ("attn_norm", None, "ffn_norm", None)):
+    for name in GEMM_WEIGHTS:
         if name + "_q" in L:
             continue
         w = L.pop(name)
-        L[name + "_q"], L[name + "_s"] = quantize_gemm_weight(w, L[norm] if norm else None,
+        L[name + "_q"], L[name + "_s"] = quantize_gemm_weight(w, L.get(FOLDED_NORM.get(name)),
                                                               fused_row_perm(cfg, name, w.device))
         del w
     return L
+
+
+def llama_dims(cfg: "LlamaConfig", max_batch: int, kv_fp8: bool = False) -> ops.LlamaDims:
+    """The fused step's ``LlamaDims`` of a model of ``cfg`` with ``max_batch`` cache slots."""
+    c = cfg
+    return ops.LlamaDims(vocab=c.vocab, dim=c.dim, n_layers=c.n_layers, H=c.n_heads, Hkv=c.n_kv_heads, D=c.head_dim,
+                         ffn=c.ffn, max_seq=c.max_seq, max_batch=max_batch, eps=c.eps, theta=c.rope_theta,
+                         qk_norm=int(c.qk_norm), qkv_bias=int(c.qkv_bias), rope_table=int(c.rope_scaling is not None),
+                         kv_fp8=int(kv_fp8))
 
 
 def e4m3_round(x: torch.Tensor) -> torch.Tensor:
@@ -324,51 +335,33 @@ class TinyLlama:
         # QKV-bias model appends bqkv, interleaved like wqkv's rows (the fold
         # touches only wqkv). A model with scaled RoPE carries its frequency table (fp32)
         # as a fourth global entry, between lm_head and the layers.
-        def fold(w, g):
-            return (w.float() * g.float()[None, :]).to(torch.bfloat16)
+        # With FP8 weights the five GEMM weights are e4m3 bytes, quantised after the fold and the
+        # interleave (_quantize_weights), and their row scales follow the table.
+        fp8 = self.weight_dtype == "fp8"
+        top = {"embed": self.embed, "final_norm": self.final_norm, "lm_head": self.lm_head,
+               "lm_head_q": self.lm_head_q, "lm_head_s": self.lm_head_s, "inv_freq": self.rope_inv_freq()}
 
-        def pairs(n):  # [0, n, 1, n + 1, ...]
-            return _pairs(n, self.device)
+        def entry(name, layer):
+            src = top if layer is None else self.layers[layer]
+            if name.endswith(" scale"):
+                return src[name[:-len(" scale")] + "_s"]
+            if fp8 and (name in GEMM_WEIGHTS or name == "lm_head"):
+                return src[name + "_q"]
+            w = src[name]
+            if name in FOLDED_NORM:
+                w = (w.float() * src[FOLDED_NORM[name]].float()[None, :]).to(torch.bfloat16)
+            perm = fused_row_perm(c, name, self.device)
+            return w[perm].contiguous() if perm is not None else w.contiguous() if name.endswith("_norm") else w
 
-        heads = c.n_heads + 2 * c.n_kv_heads
-        head_perm = (torch.arange(heads, device=self.device)[:, None] * c.head_dim
-                     + pairs(c.head_dim // 2)[None, :]).flatten()
-        if self.weight_dtype == "fp8":
-            # The same layout with the five GEMM weights as e4m3 bytes (quantised after the fold and the
-            # interleave: _quantize_weights), followed by their row scales: lm_head's, then four per layer.
-            ws = [self.embed, self.final_norm, self.lm_head_q]
-            if c.rope_scaling is not None:
-                ws.append(self.rope_inv_freq())
-            scales = [self.lm_head_s]
-            for L in self.layers:
-                ws += [L["attn_norm"], L["wqkv_q"], L["wo_q"], L["ffn_norm"], L["w_gate_up_q"], L["w_down_q"]]
-                if c.qk_norm:
-                    ws += [L["q_norm"].contiguous(), L["k_norm"].contiguous()]
-                if c.qkv_bias:
-                    ws += [L["bqkv"][head_perm].contiguous()]
-                scales += [L[n + "_s"] for n in GEMM_WEIGHTS]
-            return ws + scales
-        ws = [self.embed, self.final_norm, fold(self.lm_head, self.final_norm)]
-        if c.rope_scaling is not None:
-            ws.append(self.rope_inv_freq())
-        for L in self.layers:
-            wqkv = fold(L["wqkv"], L["attn_norm"])
-            ws += [L["attn_norm"], wqkv.contiguous() if c.qk_norm else wqkv[head_perm].contiguous(), L["wo"],
-                   L["ffn_norm"], fold(L["w_gate_up"], L["ffn_norm"])[pairs(c.ffn)].contiguous(), L["w_down"]]
-            if c.qk_norm:
-                ws += [L["q_norm"].contiguous(), L["k_norm"].contiguous()]
-            if c.qkv_bias:
-                ws += [L["bqkv"][head_perm].contiguous()]
-        return ws
+        return [entry(e.name, e.layer) for e in ops.WeightTable(self.dims(), fp8)]
+
+    def dims(self) -> ops.LlamaDims:
+        """The fused step's dims of this model: one cache slot per sequence and the scratch slot."""
+        return llama_dims(self.cfg, self.max_batch + 1, self.kv_dtype == "fp8")
 
     def fused_decoder(self) -> ops.FusedLlamaDecoder:
         if self._fused is None:
-            c = self.cfg
-            dims = ops.LlamaDims(vocab=c.vocab, dim=c.dim, n_layers=c.n_layers, H=c.n_heads, Hkv=c.n_kv_heads,
-                                 D=c.head_dim, ffn=c.ffn, max_seq=c.max_seq, max_batch=self.max_batch + 1, eps=c.eps,
-                                 theta=c.rope_theta, qk_norm=int(c.qk_norm), qkv_bias=int(c.qkv_bias),
-                                 rope_table=int(c.rope_scaling is not None), kv_fp8=int(self.kv_dtype == "fp8"))
-            self._fused = ops.FusedLlamaDecoder(dims, self.fused_weights(), self.k_cache, self.v_cache,
+            self._fused = ops.FusedLlamaDecoder(self.dims(), self.fused_weights(), self.k_cache, self.v_cache,
                                                 weight_fp8=self.weight_dtype == "fp8")
         return self._fused
 

@@ -9,6 +9,7 @@ PyTorch fallback: if the library is missing on a GPU host, ``lib()`` raises.
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import math
 import os
@@ -107,6 +108,8 @@ def lib() -> ctypes.CDLL:
         _LIB.p2pt_llama_plan_kernels_w.argtypes = [ctypes.POINTER(LlamaDims), i, i, ctypes.POINTER(WeightPlan)]
         _LIB.p2pt_llama_decode_w.argtypes = [ctypes.POINTER(LlamaDims), ctypes.POINTER(WeightPlan), ctypes.POINTER(vp),
                                              vp, vp, vp, vp, vp, i, i, vp, ctypes.c_size_t, vp, vp, vp]
+        ip = ctypes.POINTER(ctypes.c_int)
+        _LIB.p2pt_llama_weight_layout.argtypes = [ctypes.POINTER(LlamaDims), ctypes.POINTER(WeightPlan), ip, ip, i]
         _LIB.p2pt_attn_span.argtypes = [i, i]
         _LIB.p2pt_max_rows.argtypes = []
         # microbenchmark hooks (scripts/bench_skinny.py)
@@ -115,7 +118,7 @@ def lib() -> ctypes.CDLL:
         for fn in ("p2pt_rmsnorm", "p2pt_silu_mul", "p2pt_rope_qkv_cache", "p2pt_decode_attention", "p2pt_argmax",
                    "p2pt_skinny_gemm", "p2pt_llama_decode", "p2pt_sample", "p2pt_logprobs", "p2pt_llama_plan", "p2pt_attn_span",
                    "p2pt_llama_kv_plan", "p2pt_llama_plan_kernels", "p2pt_llama_weight_plan",
-                   "p2pt_llama_plan_kernels_w", "p2pt_llama_decode_w",
+                   "p2pt_llama_plan_kernels_w", "p2pt_llama_decode_w", "p2pt_llama_weight_layout",
                    "p2pt_max_rows", "p2pt_skinny_bench", "p2pt_attn_bench", "p2pt_kv_copy", "p2pt_max_kv_copy_jobs",
                    "p2pt_embed_pool", "p2pt_max_embed_jobs", "p2pt_qk_norm_rope_cache", "p2pt_penalize",
                    "p2pt_penalty_reset", "p2pt_max_logit_bias", "p2pt_guide", "p2pt_guide_reset"):
@@ -183,6 +186,58 @@ def plan_kernels_ok(dims: LlamaDims, B: int, emit_rows: int = 0, weight_fp8: boo
     if rc < 0:
         raise ValueError("dims or row count not supported by the fused decode kernels")
     return rc == 0
+
+
+WeightEntry = collections.namedtuple("WeightEntry", "name layer dtypes shape align")  # layer None: global; align: bytes
+LAYER_GEMMS = ("wqkv", "wo", "w_gate_up", "w_down")  # a layer's GEMM weights, in the order of their scales
+
+
+class WeightTable(list):
+    """The fused step's weight table for ``(dims, weight_fp8)``: its ``WeightEntry`` list, in order (host only: no
+    device, no library). The one Python statement of the layout; decode_fused.hip's ``WeightTable`` is the C one,
+    and ``p2pt_llama_weight_layout`` reports that for comparison (tests/test_weight_table.py).
+
+    embed, final_norm, lm_head; inv_freq (fp32 (D / 2,), 8-byte aligned) with ``dims.rope_table``; then per layer
+    attn_norm, wqkv, wo, ffn_norm, w_gate_up, w_down, plus q_norm, k_norm with ``dims.qk_norm`` or bqkv with
+    ``dims.qkv_bias``. With ``weight_fp8`` the five GEMM weights are e4m3 (or uint8) bytes, 8-byte aligned (a lane
+    loads 8 bytes at a multiple of 8 from the base), and their fp32 row scales follow the table: lm_head's, then
+    each layer's four, named ``"<weight> scale"``."""
+
+    def __init__(self, dims: LlamaDims, weight_fp8: bool = False):
+        d, bf, f32 = dims, (torch.bfloat16,), (torch.float32,)
+        gemm, ga = (WEIGHT_FP8_DTYPES, 8) if weight_fp8 else (bf, 2)
+        n_qkv, norm = (d.H + 2 * d.Hkv) * d.D, (bf, (d.dim,), 2)
+        top = {"embed": (bf, (d.vocab, d.dim), 2), "final_norm": norm, "lm_head": (gemm, (d.vocab, d.dim), ga)}
+        if d.rope_table:
+            top["inv_freq"] = (f32, (d.D // 2,), 8)
+        layer = {"attn_norm": norm, "wqkv": (gemm, (n_qkv, d.dim), ga), "wo": (gemm, (d.dim, d.H * d.D), ga),
+                 "ffn_norm": norm, "w_gate_up": (gemm, (2 * d.ffn, d.dim), ga), "w_down": (gemm, (d.dim, d.ffn), ga)}
+        if d.qk_norm:
+            layer.update(q_norm=(bf, (d.D,), 2), k_norm=(bf, (d.D,), 2))
+        elif d.qkv_bias:
+            layer["bqkv"] = (bf, (n_qkv,), 2)
+        groups = [(None, top)] + [(L, layer) for L in range(d.n_layers)]
+        super().__init__(WeightEntry(n, L, *v) for L, group in groups for n, v in group.items())
+        if weight_fp8:
+            self += [WeightEntry(n + " scale", L, f32, v[1][:1], 4) for L, group in groups for n, v in group.items()
+                     if v[0] is gemm]
+        self.per_layer = len(layer)
+        self._at = {(e.name, e.layer): i for i, e in enumerate(self)}
+
+    def index(self, name: str, layer: int | None = None) -> int:
+        """Where ``name`` (of ``layer``; None for a global entry) sits; a role this table lacks is a KeyError."""
+        if (name, layer) not in self._at:
+            raise KeyError(f"this weight table has no {label(name, layer)}")
+        return self._at[name, layer]
+
+    def scale_index(self, name: str, layer: int | None = None) -> int:
+        """Where the fp32 row scales of GEMM weight ``name`` sit (FP8 tables only)."""
+        return self.index(name + " scale", layer)
+
+
+def label(name: str, layer: int | None) -> str:
+    """How messages name a table entry: ``lm_head``, ``layer 1: bqkv``."""
+    return name if layer is None else f"layer {layer}: {name}"
 
 
 def attn_span(length: int, slots: int) -> int:
@@ -834,19 +889,15 @@ class FusedLlamaDecoder:
     """Host handle for the fused decode step (decode_fused.hip): 5 kernels per layer + 3
     (6 per layer with ``dims.qk_norm``: the per-head q/k RMSNorm of Qwen3 runs in a kernel of its own;
     with ``dims.qkv_bias`` the q/k/v bias of Qwen2 is added in the QKV GEMM's epilogue, still 5; with
-    ``dims.rope_table`` the kernel that rotates reads its frequencies from ``weights[3]``, an fp32 (D / 2,)
-    table that sits between lm_head and the layers, and the kernel count does not change; with
-    ``dims.kv_fp8`` the caches are ``torch.float8_e4m3fn`` (or uint8), one OCP e4m3 byte per element at scale 1,
-    written by the _KV8 epilogues / ``k_qknorm_rope`` variant and read by ``k_attn<D, G, true>``: the same
-    kernel count again).
+    ``dims.rope_table`` the kernel that rotates reads its frequencies from the table's ``inv_freq`` entry, and the
+    kernel count does not change; with ``dims.kv_fp8`` the caches are ``torch.float8_e4m3fn`` (or uint8), one OCP
+    e4m3 byte per element at scale 1, written by the _KV8 epilogues / ``k_qknorm_rope`` variant and read by
+    ``k_attn<D, G, true>``: the same kernel count again).
 
-    ``weight_fp8``: the five GEMM weights as OCP e4m3 bytes with one fp32 scale per output row
-    (docs/WEIGHT_FP8.md, ``quantize_weight_fp8``). The table keeps the layout above, 6, 7 or 8 entries per layer
-    behind the 3 or 4 global ones, with lm_head, wqkv, wo, w_gate_up and w_down as ``torch.float8_e4m3fn`` (or
-    uint8) [N, K] instead of bf16, and is followed by the scales: lm_head's (vocab,), then per layer wqkv's, wo's,
-    w_gate_up's and w_down's, each fp32 (N,) in the row order of its weight: 1 + 4 * n_layers more entries. Every
-    ``k_skinny`` is then its FP8-weight instantiation; the kernel count, ``step_plan`` and the workspace are the
-    same. The bf16 table is unchanged.
+    ``weights`` is laid out as ``WeightTable(dims, weight_fp8)`` says, and every entry is checked against it.
+    ``weight_fp8``: the five GEMM weights as OCP e4m3 bytes with one fp32 scale per output row, each (N,) in the
+    row order of its weight (docs/WEIGHT_FP8.md, ``quantize_weight_fp8``). Every ``k_skinny`` is then its FP8-weight
+    instantiation; the kernel count, ``step_plan`` and the workspace are the same.
 
     Holds the weight pointer table and a zero-initialised workspace; ``step``
     validates the per-call tensors and launches on the current stream (capturable
@@ -871,46 +922,45 @@ class FusedLlamaDecoder:
                 raise TypeError(f"{name}: a {c.dtype} cache needs dims.kv_fp8 = 1")
         if dims.rope_table not in (0, 1):
             raise ValueError("dims.rope_table must be 0 or 1")
-        g0 = 3 + dims.rope_table  # global entries ahead of the layers
-        per_layer = 8 if dims.qk_norm else 7 if dims.qkv_bias else 6
-        n_table = g0 + per_layer * dims.n_layers  # entries of the bf16 layout; the FP8 scales follow them
-        gemm_at = self._gemm_entries(dims, g0, per_layer) if self.weight_fp8 else {}
-        for i, t in enumerate(weights):
-            if dims.rope_table and i == 3:
-                _check_inv_freq(t, dims.D, dev)
-            elif i in gemm_at or (self.weight_fp8 and i >= n_table):
-                continue  # checked below, once the table's length is known to be the FP8 layout's
-            elif isinstance(t, torch.Tensor) and t.dtype in WEIGHT_FP8_DTYPES and t.dtype != torch.uint8:
-                raise TypeError(f"weight[{i}] is {t.dtype}: an FP8 weight table needs weight_fp8=True")
-            else:
-                _check(t, torch.bfloat16, f"weight[{i}]", dev)
-        L, Bmax, S, Hkv, D = k_cache.shape
-        if (L, Bmax, S, Hkv, D) != (dims.n_layers, dims.max_batch, dims.max_seq, dims.Hkv, dims.D):
-            raise ValueError("cache shape does not match dims")
-        for name, c in (("k_cache", k_cache), ("v_cache", v_cache)):
-            _check(c, c.dtype if dims.kv_fp8 else torch.bfloat16, name, dev)
-        if v_cache.shape != k_cache.shape or v_cache.dtype != k_cache.dtype:
-            raise ValueError("k_cache and v_cache must have the same shape and dtype")
-        if len(weights) != n_table + (1 + 4 * dims.n_layers if self.weight_fp8 else 0):
+        self.table = table = WeightTable(dims, self.weight_fp8)
+        if len(weights) != len(table):
             raise ValueError(f"weight table: embed, final_norm, lm_head, "
-                             + ("inv_freq, " if dims.rope_table else "") + f"then {per_layer} per layer "
+                             + ("inv_freq, " if dims.rope_table else "") + f"then {table.per_layer} per layer "
                              "(wqkv, w_gate_up and lm_head with the preceding norm weight folded in"
                              + ("; q_norm and k_norm last)" if dims.qk_norm else
                                 "; bqkv last)" if dims.qkv_bias else ")")
                              + ("; weight_fp8: then the fp32 row scales, lm_head's and four per layer"
                                 if self.weight_fp8 else ""))
-        if self.weight_fp8:
-            self._check_fp8_table(weights, gemm_at, n_table, dev)
-        if dims.qk_norm:
-            for L in range(dims.n_layers):
-                for j in (6, 7):
-                    if weights[g0 + 8 * L + j].shape != (dims.D,):
-                        raise ValueError(f"layer {L}: q_norm and k_norm must be ({dims.D},)")
-        elif dims.qkv_bias:
-            n_qkv = (dims.H + 2 * dims.Hkv) * dims.D
-            for L in range(dims.n_layers):
-                if weights[g0 + 7 * L + 6].shape != (n_qkv,):
-                    raise ValueError(f"layer {L}: bqkv must be ({n_qkv},)")
+        # Every entry's dtype and shape, from the description alone: a refusal here needs no device. A weight shorter
+        # than dims says would be read past its end (k_skinny sizes its descriptors from dims, k_embed indexes vocab
+        # rows). The norm slots the kernels do not read are held to (dim,) too.
+        for e, t in zip(table, weights):
+            name = label(e.name, e.layer)
+            if not isinstance(t, torch.Tensor) or t.dtype not in e.dtypes:
+                got = getattr(t, "dtype", type(t))
+                if len(e.dtypes) > 1:
+                    raise TypeError(f"{name}: weight_fp8 is set, so the weight must be torch.float8_e4m3fn (or uint8), "
+                                    f"got {got}")
+                if got == torch.float8_e4m3fn:
+                    raise TypeError(f"{name} is {got}: an FP8 weight table needs weight_fp8=True")
+                raise TypeError(f"{name}: expected {e.dtypes[0]}, got {got}")
+            if tuple(t.shape) != e.shape:
+                raise ValueError(f"{name} has shape {tuple(t.shape)}, not {e.shape}"
+                                 + (": one fp32 scale per output row" if e.name.endswith(" scale") else ""))
+        L, Bmax, S, Hkv, D = k_cache.shape
+        if (L, Bmax, S, Hkv, D) != (dims.n_layers, dims.max_batch, dims.max_seq, dims.Hkv, dims.D):
+            raise ValueError("cache shape does not match dims")
+        if v_cache.shape != k_cache.shape or v_cache.dtype != k_cache.dtype:
+            raise ValueError("k_cache and v_cache must have the same shape and dtype")
+        # From here on the device: where every tensor lives, contiguity, alignment, the RoPE table's values.
+        for e, t in zip(table, weights):
+            _check(t, t.dtype, label(e.name, e.layer), dev)
+            if t.data_ptr() % e.align:
+                raise ValueError(f"{label(e.name, e.layer)} must be {e.align}-byte aligned")
+        if dims.rope_table:
+            _check_inv_freq(weights[table.index("inv_freq")], dims.D, dev)
+        for name, c in (("k_cache", k_cache), ("v_cache", v_cache)):
+            _check(c, c.dtype if dims.kv_fp8 else torch.bfloat16, name, dev)
         nbytes = lib().p2pt_llama_ws_bytes(ctypes.byref(dims))
         if nbytes == 0:
             raise ValueError("model dims not supported by the fused decode kernels")
@@ -920,37 +970,6 @@ class FusedLlamaDecoder:
         self.k_cache, self.v_cache = k_cache, v_cache
         self.device = dev
         self._resid = None  # embed_pool's view of the workspace's resid buffer
-
-    @staticmethod
-    def _gemm_entries(dims, g0, per_layer) -> dict:
-        """Index in the weight table -> (name, N, K, index of its scale behind the table) of the five GEMMs."""
-        n_table = g0 + per_layer * dims.n_layers
-        at = {2: ("lm_head", dims.vocab, dims.dim, n_table)}
-        shapes = (("wqkv", 1, (dims.H + 2 * dims.Hkv) * dims.D, dims.dim), ("wo", 2, dims.dim, dims.H * dims.D),
-                  ("w_gate_up", 4, 2 * dims.ffn, dims.dim), ("w_down", 5, dims.dim, dims.ffn))
-        for L in range(dims.n_layers):
-            for j, (name, k, N, K) in enumerate(shapes):
-                at[g0 + per_layer * L + k] = (f"layer {L} {name}", N, K, n_table + 1 + 4 * L + j)
-        return at
-
-    @staticmethod
-    def _check_fp8_table(weights, gemm_at, n_table, dev) -> None:
-        """The FP8 entries of a weight table, on the host before any launch: every GEMM weight e4m3 (or uint8)
-        [N, K], contiguous, on the device and 8-byte aligned (a lane loads 8 bytes at a multiple of 8 from the
-        base: K is a multiple of 32); every scale fp32 (N,), contiguous and on the device."""
-        for i, (name, N, K, si) in gemm_at.items():
-            t, sc = weights[i], weights[si]
-            if not isinstance(t, torch.Tensor) or t.dtype not in WEIGHT_FP8_DTYPES:
-                raise TypeError(f"{name}: weight_fp8 is set, so the weight must be torch.float8_e4m3fn (or uint8), "
-                                f"got {getattr(t, 'dtype', type(t))}")
-            _check(t, t.dtype, name, dev)
-            if tuple(t.shape) != (N, K):
-                raise ValueError(f"{name}: shape {tuple(t.shape)} != ({N}, {K})")
-            if t.data_ptr() % 8:
-                raise ValueError(f"{name}: an FP8 weight must be 8-byte aligned (the kernels load 8 bytes per lane)")
-            _check(sc, torch.float32, f"{name} scale", dev)
-            if tuple(sc.shape) != (N,):
-                raise ValueError(f"{name} scale: shape {tuple(sc.shape)} != ({N},), one fp32 scale per output row")
 
     # Workspace buffers in the order p2pt_llama_ws_layout reports them.
     _WS_BUFFERS = (("resid", torch.bfloat16), ("q", torch.bfloat16), ("attn", torch.bfloat16), ("h", torch.bfloat16),
@@ -991,7 +1010,7 @@ class FusedLlamaDecoder:
         weight and this model's eps."""
         if self._resid is None:
             self._resid = self.workspace_views()["resid"]
-        embed_pool_(self._resid, self.weights[1], acc, out, jobs, self.dims.eps)
+        embed_pool_(self._resid, self.weights[self.table.index("final_norm")], acc, out, jobs, self.dims.eps)
 
     def step(self, tokens: torch.Tensor, pos: torch.Tensor, logits: torch.Tensor, ids: torch.Tensor,
              slots: torch.Tensor | None = None, emit_rows: int = 0) -> None:

@@ -16,7 +16,7 @@ struct LlamaDims {
   // The KV cache holds OCP e4m3fn bytes (scale 1) instead of bf16: the _KV8 epilogues and k_attn<D, G, true>. It sits
   // ahead of the three family flags, whose order (qkv_bias last) the plan tests of those families pin.
   int kv_fp8;
-  int rope_table;  // RoPE frequencies from an fp32 table [D/2] (llama3 / linear scaling): w[3] points at it
+  int rope_table;  // RoPE frequencies from an fp32 table [D/2] (llama3 / linear scaling): the table's inv_freq entry
   int qk_norm;  // per-head RMSNorm on q and k before RoPE (Qwen3): a sixth kernel per layer
   int qkv_bias;  // a bias on the q, k and v projections (Qwen2): added in the QKV GEMM's epilogue
 };
@@ -196,6 +196,39 @@ Workspace carve(const LlamaDims& d, uint8_t* base) {
   w.bytes = l.bytes;
   return w;
 }
+
+// ------------------------------------------------------------ weight table
+// The one place in C that knows the layout of the pointer list w (ops/__init__.py's WeightTable is the Python one;
+// p2pt_llama_weight_layout reports this one so that the two can be compared): embed, final_norm, lm_head, inv_freq
+// if rope_table, then per layer the six, + q_norm, k_norm (qk_norm) or + bqkv (qkv_bias), then with FP8 weights the
+// fp32 row scales: lm_head's, then per layer wqkv's, wo's, w_gate_up's and w_down's.
+enum Role : int { R_EMBED, R_FINAL_NORM, R_LM_HEAD, R_INV_FREQ, R_ATTN_NORM, R_WQKV, R_WO, R_FFN_NORM, R_W_GATE_UP,
+                  R_W_DOWN, R_BQKV, R_Q_NORM, R_K_NORM, R_NROLES };
+struct WeightTable {
+  LlamaDims d;
+  int w8;
+  const void* const* w;
+  int per_layer() const { return d.qk_norm ? 8 : d.qkv_bias ? 7 : 6; }
+  int scales0() const { return 3 + d.rope_table + per_layer() * d.n_layers; }
+  int size() const { return scales0() + (w8 ? 1 + 4 * d.n_layers : 0); }
+  // Index of a role (of layer L, which the four global roles ignore); -1: this table has none.
+  int index(Role r, int L = 0) const {
+    if (r <= R_LM_HEAD) return r;
+    if (r == R_INV_FREQ) return d.rope_table ? 3 : -1;
+    const int base = 3 + d.rope_table + per_layer() * L;
+    if (r <= R_W_DOWN) return base + (r - R_ATTN_NORM);
+    if (r == R_BQKV) return d.qkv_bias && !d.qk_norm ? base + 6 : -1;
+    return d.qk_norm ? base + 6 + (r - R_Q_NORM) : -1;
+  }
+  // Index of the row scales of a GEMM weight; -1 for a bf16 table (where launch() wants none) or another role.
+  int scale_index(Role r, int L = 0) const {
+    const int j = r == R_WQKV ? 1 : r == R_WO ? 2 : r == R_W_GATE_UP ? 3 : r == R_W_DOWN ? 4 : 0;
+    return !w8 || (!j && r != R_LM_HEAD) ? -1 : scales0() + (j ? 4 * L + j : 0);
+  }
+  const void* get(Role r, int L = 0) const { return at(index(r, L)); }  // nullptr where the table has none
+  const void* scale(Role r, int L = 0) const { return at(scale_index(r, L)); }
+  const void* at(int i) const { return i < 0 ? nullptr : w[i]; }
+};
 
 // ------------------------------------------------------------ kernel arguments
 // A stage's GemmArgs is one expression: gemm(x, w) + norm(...) + its
@@ -448,6 +481,20 @@ int p2pt_llama_weight_plan(const LlamaDims* d, int weight_fp8, WeightPlan* out) 
   return 0;
 }
 
+// The weight table of (dims, weight plan) as the step reads it (host only): its length, and into index[L * 13 + r]
+// and scale_index[L * 13 + r] where role r (enum Role) of layer L and its row scales sit, -1 where there is none.
+// n: ints each array holds, at least 13 * n_layers. -1: dims or plan refused, or n too small.
+int p2pt_llama_weight_layout(const LlamaDims* d, const WeightPlan* wp, int* index, int* scale_index, int n) {
+  if (!dims_ok(*d) || !weights_ok(*wp) || n < R_NROLES * d->n_layers) return -1;
+  const WeightTable T{*d, wp->w8, nullptr};
+  for (int L = 0; L < d->n_layers; L++)
+    for (int r = 0; r < R_NROLES; r++) {
+      index[L * R_NROLES + r] = T.index(Role(r), L);
+      scale_index[L * R_NROLES + r] = T.scale_index(Role(r), L);
+    }
+  return T.size();
+}
+
 // k_attn's span rule: tokens per span slot for a row of `len` tokens.
 int p2pt_attn_span(int len, int slots) { return len > 0 && slots > 0 ? attn_span(len, unsigned(slots)) : 0; }
 
@@ -455,12 +502,11 @@ int p2pt_max_rows() { return kMaxM; }
 
 // One decode step over B <= 64 token rows. The grids depend on B alone (the
 // context enters through pos), so a captured step serves every position.
-//   w: embed, final_norm, lm_head, then per layer
+//   w: the weight table, in WeightTable's order: embed, final_norm, lm_head, then per layer
 //      attn_norm, wqkv [(H+2Hkv)*D, dim], wo [dim, H*D], ffn_norm, w_gate_up [2*ffn, dim], w_down [dim, ffn]
 //      where wqkv, w_gate_up and lm_head carry the preceding RMSNorm weight folded
 //      into their columns (W[n][k] * g[k]); the norm-weight slots are not read.
-//      wqkv rows are interleaved per head (dim i, dim i + D/2, ...) and w_gate_up
-//      rows per pair (gate_j, up_j, ...).
+//      wqkv rows are interleaved per head (dim i, dim i + D/2, ...) and w_gate_up rows per pair (gate_j, up_j, ...).
 //      With dims.qk_norm each layer has 8 entries, q_norm [D] and k_norm [D] appended, and
 //      wqkv rows stay in plain order (k_qknorm_rope pairs the RoPE partners itself).
 //      With dims.qkv_bias each layer has 7 entries: the six, then bqkv [(H+2Hkv)*D], interleaved like wqkv's rows.
@@ -492,33 +538,27 @@ int p2pt_llama_decode_w(const LlamaDims* dp, const WeightPlan* wp, const void* c
   hipError_t e;
   auto failed = [&](hipError_t r) { return (e = r) != hipSuccess; };
 
-  const void* inv_freq = d.rope_table ? w[3] : nullptr;
-  hipLaunchKernelGGL(k_embed, dim3(B), dim3(256), 0, s, static_cast<const uint16_t*>(w[0]), tokens, W.resid, W.ss,
-                     d.dim, d.vocab);
+  const WeightTable T{d, w8, w};
+  const void* inv_freq = T.get(R_INV_FREQ);
+  hipLaunchKernelGGL(k_embed, dim3(B), dim3(256), 0, s, static_cast<const uint16_t*>(T.get(R_EMBED)), tokens, W.resid,
+                     W.ss, d.dim, d.vocab);
   if (failed(hipGetLastError())) return int(e);
-  const int per_layer = d.qk_norm ? 8 : d.qkv_bias ? 7 : 6;
-  // FP8 weights: the row scales follow the table. nullptr for bf16, where launch() wants none.
-  const void* const* sc = w + 3 + d.rope_table + per_layer * d.n_layers;
-  auto scale = [&](int i) { return w8 ? sc[i] : nullptr; };  // 0: lm_head; 1 + 4 L + j: wqkv, wo, w_gate_up, w_down
   for (int L = 0; L < d.n_layers; L++) {
-    // attn_norm, wqkv, wo, ffn_norm, w_gate_up, w_down (+ q_norm, k_norm, or + bqkv)
-    const void* const* wl = w + 3 + d.rope_table + per_layer * L;
     uint16_t* kc = reinterpret_cast<uint16_t*>(static_cast<uint8_t*>(k_cache) + L * layer_cache);
     uint16_t* vc = reinterpret_cast<uint16_t*>(static_cast<uint8_t*>(v_cache) + L * layer_cache);
     const GemmPlan& qkv = L ? P.qkv : P.qkv_first;
-    const GemmArgs qkv_in = gemm(W.resid, wl[1], scale(1 + 4 * L)) + norm(W.ss, qkv.ss_in, d.eps);
+    const GemmArgs qkv_in = gemm(W.resid, T.get(R_WQKV, L), T.scale(R_WQKV, L)) + norm(W.ss, qkv.ss_in, d.eps);
     const GemmArgs to_qkv =
-        d.qk_norm ? qkv_in + store(W.qkv)
-                  : qkv_in + rope(d, pos, slots, W.q, kc, vc, d.qkv_bias ? wl[6] : nullptr, inv_freq);
-    const GemmArgs to_o = gemm(W.attn, wl[2], scale(2 + 4 * L)) + resid(W.resid, W.ss);
-    const GemmArgs to_gate_up =
-        gemm(W.resid, wl[4], scale(3 + 4 * L)) + norm(W.ss, P.gate_up.ss_in, d.eps) + store(W.h);
-    const GemmArgs to_down = gemm(W.h, wl[5], scale(4 + 4 * L)) + resid(W.resid, W.ss);
+        d.qk_norm ? qkv_in + store(W.qkv) : qkv_in + rope(d, pos, slots, W.q, kc, vc, T.get(R_BQKV, L), inv_freq);
+    const GemmArgs to_o = gemm(W.attn, T.get(R_WO, L), T.scale(R_WO, L)) + resid(W.resid, W.ss);
+    const GemmArgs to_gate_up = gemm(W.resid, T.get(R_W_GATE_UP, L), T.scale(R_W_GATE_UP, L)) +
+                                norm(W.ss, P.gate_up.ss_in, d.eps) + store(W.h);
+    const GemmArgs to_down = gemm(W.h, T.get(R_W_DOWN, L), T.scale(R_W_DOWN, L)) + resid(W.resid, W.ss);
     if (failed(launch(qkv, to_qkv, s, w8))) return int(e);
     if (P.qk_norm_grid) {
-      const QkNormArgs qn{W.qkv, static_cast<const uint16_t*>(wl[6]), static_cast<const uint16_t*>(wl[7]), pos, slots,
-                          d.max_batch, W.q, kc, vc, d.H, d.Hkv, d.max_seq, d.eps, log2f(d.theta),
-                          static_cast<const float*>(inv_freq)};
+      const QkNormArgs qn{W.qkv, static_cast<const uint16_t*>(T.get(R_Q_NORM, L)),
+                          static_cast<const uint16_t*>(T.get(R_K_NORM, L)), pos, slots, d.max_batch, W.q, kc, vc, d.H,
+                          d.Hkv, d.max_seq, d.eps, log2f(d.theta), static_cast<const float*>(inv_freq)};
       if (failed(launch_qknorm(P.qk_norm_grid, B, d.D, P.qk_norm_table != 0, KV.qk_norm_kv8 != 0, qn, s)))
         return int(e);
     }
@@ -530,7 +570,8 @@ int p2pt_llama_decode_w(const LlamaDims* dp, const WeightPlan* wp, const void* c
     if (failed(launch(P.down, to_down, s, w8))) return int(e);
   }
   const GemmArgs to_logits =
-      gemm(W.resid, w[2], scale(0)) + norm(W.ss, P.lm_head.ss_in, d.eps) + argmax(logits, W.am_val, W.am_idx);
+      gemm(W.resid, T.get(R_LM_HEAD), T.scale(R_LM_HEAD)) + norm(W.ss, P.lm_head.ss_in, d.eps) +
+      argmax(logits, W.am_val, W.am_idx);
   if (failed(launch(P.lm_head, to_logits, s, w8))) return int(e);
   hipLaunchKernelGGL(k_argmax_merge, dim3(P.emit_rows), dim3(256), 0, s, W.am_val, W.am_idx, P.am_parts, ids);
   return int(hipGetLastError());

@@ -120,7 +120,7 @@ def loop(m, a):
         g.replay()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    nbytes = sum(t.numel() * t.element_size() for t in dec.weights[2:]) + m.embed.shape[1] * 2 * B
+    nbytes = sum(t.numel() * t.element_size() for t in dec.weights[dec.table.index("lm_head"):]) + m.embed.shape[1] * 2 * B
     print(json.dumps({"config": a.config, "batch": B, "ctx": a.ctx, "steps": a.steps, "graph": True, "loop": True,
                       "weight_dtype": a.weight_dtype,
                       "ms_per_step": dt * 1e3 / a.steps, "tokens_per_s": B * a.steps / dt,

@@ -48,7 +48,7 @@ import test_gpu_qk_norm as qk3
 import test_gpu_qwen2 as qw2
 from test_gpu_fused_stages import (BF, CASES as STEP_CASES, EPI_NAMES, F64, LAYER_SLIPS, SENTINEL_BITS, SENTINEL_ID, U,
                                    Case, emulate, gemm_ref, inputs, layer_w, plan_strings, rounded, stage_qkv,
-                                   stage_ratios, step_plan, table_stride, worst)
+                                   stage_ratios, step_plan, table_layout, table_stride, worst)
 
 cuda = pytest.mark.skipif(not torch.cuda.is_available(), reason="needs a HIP device")
 
@@ -95,11 +95,11 @@ def qkv_stage_of(case, obs):
     """The (q, k, v) references of layer ``layer`` for the case's family, as ``stage_ratios`` calls them."""
     c = case.cfg
     if c.qkv_bias:
-        return lambda case, W, x0, pos, layer: qw2.stage_qkv_bias(c, layer_w(c, W, layer, 1), layer_w(c, W, layer, 6),
+        return lambda case, W, x0, pos, layer: qw2.stage_qkv_bias(c, layer_w(c, W, layer, "wqkv"), layer_w(c, W, layer, "bqkv"),
                                                                   x0, pos)
     if c.qk_norm:  # k_qknorm_rope, from the raw projection it read; v is copied: bound 0, bit equality
         def stage(case, W, x0, pos, layer):
-            qr, kr, v = qk3.reference(obs["qkv"], layer_w(c, W, layer, 6), layer_w(c, W, layer, 7), pos, c.n_heads,
+            qr, kr, v = qk3.reference(obs["qkv"], layer_w(c, W, layer, "q_norm"), layer_w(c, W, layer, "k_norm"), pos, c.n_heads,
                                       c.n_kv_heads, c.head_dim, c.eps, c.rope_theta)
             return qr, kr, (v.to(F64), torch.zeros(v.shape, dtype=F64))
         return stage
@@ -120,7 +120,7 @@ def layer1_ratios(case, W, obs):
     c = case.cfg
     out = stage_ratios(case, W, obs, layer=1, qkv_stage=qkv_stage_of(case, obs))
     if c.qk_norm:
-        y, E = gemm_ref(obs["x0"], layer_w(c, W, 1, 1), c.eps)
+        y, E = gemm_ref(obs["x0"], layer_w(c, W, 1, "wqkv"), c.eps)
         out["qkv"] = worst(obs["qkv"], (y, rounded(y, E)))
     parts = step_plan(case).down.grid_x
     out["ss_r1"] = ss_ratio(obs["ss2"], obs["r1"], parts)
@@ -152,8 +152,8 @@ def cache_problems(case, caches):
 
 def layers_differ(case, W):
     """Layer 1's table entries are not layer 0's: a kernel that reads the wrong one computes something else."""
-    n = table_stride(case.cfg)
-    return all(not torch.equal(W[3 + k], W[3 + n + k]) for k in range(n))
+    T = table_layout(case.cfg)
+    return all(not torch.equal(W[T.index(e.name, 0)], W[T.index(e.name, 1)]) for e in T if e.layer == 0)
 
 
 def show(ratios):
@@ -290,7 +290,7 @@ def observe_gpu(case):
             w.copy_(s)
         return {k: (views[k] if k == "ss" else views[k][:B]).cpu() for k in names}
 
-    wo, w_down = layer_w(c, dec.weights, 1, 2), layer_w(c, dec.weights, 1, 5)
+    wo, w_down = layer_w(c, dec.weights, 1, "wo"), layer_w(c, dec.weights, 1, "w_down")
     p1, p2, p3 = run([wo, w_down]), run([w_down]), run([])
     for k in names[:2] + names[5:]:  # q, attn (and qkv) depend on x1 alone: the same bits in every pass
         assert torch.equal(p1[k], p3[k]) and torch.equal(p2[k], p3[k]), k

@@ -666,7 +666,7 @@ def observe_layer(case, table, inp):
         torch.cuda.synchronize()
         return {k: views[k][:B].clone() for k in ("q", "attn", "h", "resid")}
 
-    w_down = table[8]
+    w_down = table[dec.table.index("w_down", 0)]
     saved = w_down.clone()
     w_down.zero_()
     first = run()

@@ -50,7 +50,7 @@ import pytest
 import torch
 
 from p2p_llm_tunnel_amd import ops
-from p2p_llm_tunnel_amd.models.tiny_llm import LlamaConfig, TinyLlama
+from p2p_llm_tunnel_amd.models.tiny_llm import LlamaConfig, TinyLlama, llama_dims
 
 cuda = pytest.mark.skipif(not torch.cuda.is_available(), reason="needs a HIP device")
 
@@ -269,14 +269,21 @@ def rope_tables(cfg, pos):
     return torch.cos(ang), torch.sin(ang), dsc
 
 
+@functools.lru_cache(maxsize=None)
+def table_layout(cfg, weight_fp8=False):
+    """The layout of the fused weight table of a model of ``cfg`` (``ops.WeightTable``: the one description)."""
+    return ops.WeightTable(llama_dims(cfg, 1), weight_fp8)
+
+
 def table_stride(cfg):
     """Entries per layer of the fused weight table: the six, + bqkv (Qwen2), or + q_norm, k_norm (Qwen3)."""
-    return 8 if cfg.qk_norm else 7 if cfg.qkv_bias else 6
+    return table_layout(cfg).per_layer
 
 
-def layer_w(cfg, W, layer, k):
-    """Entry k of ``layer`` in the table W: attn_norm, wqkv, wo, ffn_norm, w_gate_up, w_down (, bqkv | q_norm, k_norm)."""
-    return W[3 + table_stride(cfg) * layer + k]
+def layer_w(cfg, W, layer, name):
+    """Entry ``name`` of ``layer`` in the table W: attn_norm, wqkv, wo, ffn_norm, w_gate_up, w_down (, bqkv | q_norm,
+    k_norm)."""
+    return W[table_layout(cfg).index(name, layer)]
 
 
 def stage_qkv(case, W, x0, pos, layer=0):
@@ -290,7 +297,7 @@ def stage_qkv(case, W, x0, pos, layer=0):
     """
     c = case.cfg
     H, Hkv, D, half = c.n_heads, c.n_kv_heads, c.head_dim, c.head_dim // 2
-    y, E = gemm_ref(x0, layer_w(c, W, layer, 1), c.eps)
+    y, E = gemm_ref(x0, layer_w(c, W, layer, "wqkv"), c.eps)
     M = y.shape[0]
     y, E = y.view(M, H + 2 * Hkv, half, 2), E.view(M, H + 2 * Hkv, half, 2)  # pairs (dim i, dim i + D/2)
     vy, vE = y[:, H + Hkv:], E[:, H + Hkv:]
@@ -371,7 +378,7 @@ def stage_swiglu(case, W, r1, layer=0):
     fp32: __expf(-g) is off by (2 |g| + 2) U relatively, which 1 / (1 + e) damps to at most as much; the add,
     the divide (correctly rounded: no fast-math flag) and the multiply add 3 U.
     """
-    y, E = gemm_ref(r1, layer_w(case.cfg, W, layer, 4), case.cfg.eps)
+    y, E = gemm_ref(r1, layer_w(case.cfg, W, layer, "w_gate_up"), case.cfg.eps)
     M = y.shape[0]
     y, E = y.view(M, -1, 2), E.view(M, -1, 2)  # pairs (gate_j, up_j)
     g, u = bf64(y[..., 0]), bf64(y[..., 1])
@@ -425,9 +432,9 @@ def stage_ratios(case, W, obs, layer=0, qkv_stage=stage_qkv, inp=None):
     out["k"] = worst(obs["kc"][sl, inp.pos.long()], kr)
     out["v"] = worst(obs["vc"][sl, inp.pos.long()], vr)
     out["attn"] = worst(obs["attn"], stage_attn(case, obs["q"], obs["kc"], obs["vc"], inp.pos, inp.slots))
-    out["o"] = worst(obs["r1"], stage_resid(obs["attn"], layer_w(c, W, layer, 2), x0))
+    out["o"] = worst(obs["r1"], stage_resid(obs["attn"], layer_w(c, W, layer, "wo"), x0))
     out["h"] = worst(obs["h"], stage_swiglu(case, W, obs["r1"], layer))
-    out["down"] = worst(obs["r2"], stage_resid(obs["h"], layer_w(c, W, layer, 5), obs["r1"]))
+    out["down"] = worst(obs["r2"], stage_resid(obs["h"], layer_w(c, W, layer, "w_down"), obs["r1"]))
     out["logits"] = worst(obs["logits"][:emit], stage_lm_head(case, W, obs["r2"][:emit]))
     want = first_argmax(obs["logits"][:emit])
     out["ids"] = 0.0 if torch.equal(obs["ids"][:emit], want) else float("inf")
@@ -503,8 +510,8 @@ def emulate(case, mut=None, slip=None):
     for L in range(c.n_layers):
         late = L > 0
 
-        def entry(k, slipped):  # this layer's table entry k, or layer 0's under the slip that names it
-            return layer_w(c, W, 0 if late and slip == slipped else L, k)
+        def entry(name, slipped):  # this layer's table entry, or layer 0's under the slip that names it
+            return layer_w(c, W, 0 if late and slip == slipped else L, name)
 
         x0 = r2
         ss = sumsq(x0)  # layer 0: k_embed's one partial
@@ -512,13 +519,13 @@ def emulate(case, mut=None, slip=None):
             ss = (ss_down[:, :32 * plan.qkv.nw] if slip == "late_loop" else ss_down).sum(1)
             if slip == "stale_ss":
                 ss = ss_o
-        y = gemm("qkv", x0, entry(1, "table:wqkv"), ss)
+        y = gemm("qkv", x0, entry("wqkv", "table:wqkv"), ss)
         if c.qkv_bias:
-            y = y + entry(6, "table:bias").float()[None, :]
+            y = y + entry("bqkv", "table:bias").float()[None, :]
         if c.qk_norm:  # STORE, then k_qknorm_rope: plain row order, RoPE partners d and d + D/2
             raw = y.to(BF)
             xh = raw.float().view(B, H + 2 * Hkv, D)
-            g = torch.cat([entry(6, "table:qk_norm").float().expand(H, D), entry(7, "table:qk_norm").float().expand(Hkv, D)])
+            g = torch.cat([entry("q_norm", "table:qk_norm").float().expand(H, D), entry("k_norm", "table:qk_norm").float().expand(Hkv, D)])
             n = xh[:, :H + Hkv] * torch.rsqrt(xh[:, :H + Hkv].pow(2).sum(-1, keepdim=True) / D + c.eps) * g[None]
             x1, x2 = n[..., :half], n[..., half:]
             v = xh[:, H + Hkv:].to(BF)
@@ -533,12 +540,12 @@ def emulate(case, mut=None, slip=None):
         kc, vc = caches[0 if late and slip == "attend_layer0" else L]
         attn = _emulate_attn(case, q, kc, vc, mut)
 
-        r1 = bf32(x0.float() + bf32(gemm("o", attn, layer_w(c, W, L, 2)))).to(BF)
+        r1 = bf32(x0.float() + bf32(gemm("o", attn, layer_w(c, W, L, "wo")))).to(BF)
         ss_o = sumsq(r1)
-        gu = bf32(gemm("gate_up", r1, layer_w(c, W, L, 4), ss_o)).view(B, c.ffn, 2)
+        gu = bf32(gemm("gate_up", r1, layer_w(c, W, L, "w_gate_up"), ss_o)).view(B, c.ffn, 2)
         g_, u_ = (gu[..., 1], gu[..., 0]) if mut == "swap_gate_up" else (gu[..., 0], gu[..., 1])
         h = (g_ / (1 + torch.exp(-g_)) * u_).to(BF)
-        r2 = bf32(r1.float() + bf32(gemm("down", h, layer_w(c, W, L, 5)))).to(BF)
+        r2 = bf32(r1.float() + bf32(gemm("down", h, layer_w(c, W, L, "w_down")))).to(BF)
         ss_down = partials(r2)
     logits = gemm("lm_head", r2[:emit], W[2], sumsq(r2[:emit])).to(BF)
     kc, vc = caches[-1]
@@ -848,7 +855,7 @@ def observe_gpu(case):
         return {k: views[k][:B].cpu() for k in ("q", "attn", "h", "resid")}
 
     # Pass 1 with w_down (passed to the kernel as is) zeroed: the final residual is the post-O residual.
-    w_down = dec.weights[8]
+    w_down = dec.weights[dec.table.index("w_down", 0)]
     saved = w_down.clone()
     w_down.zero_()
     first = run()

@@ -51,7 +51,8 @@ from p2p_llm_tunnel_amd import ops
 from p2p_llm_tunnel_amd.models import rope
 from p2p_llm_tunnel_amd.models.rope import RopeScaling
 from p2p_llm_tunnel_amd.models.tiny_llm import CONFIGS, LlamaConfig, TinyLlama
-from test_gpu_fused_stages import BF, F64, U, bf64, flip, gemm_ref, rope_tables, rounded, stage_attn, worst
+from test_gpu_fused_stages import (BF, F64, U, bf64, flip, gemm_ref, rope_tables, rounded, stage_attn, table_layout,
+                                   worst)
 from test_gpu_qk_norm import RN
 from test_kv_fp8 import judge
 
@@ -220,21 +221,21 @@ def appended_reference(case, W, x0, pos, raw):
     observed bf16 projection of a QK-norm model."""
     c = case.cfg
     H, Hkv, D, half = c.n_heads, c.n_kv_heads, c.head_dim, c.head_dim // 2
-    g0 = 3 + int(c.rope_scaling is not None)
-    table = W[3] if c.rope_scaling is not None else None
+    at = lambda name: W[table_layout(c).index(name, 0)]
+    table = W[table_layout(c).index("inv_freq")] if c.rope_scaling is not None else None
     cs, sn, dsc = angles(c, pos, table)
     if c.qk_norm:
         x = raw.view(-1, H + 2 * Hkv, D)
         xd = x[:, :H + Hkv].to(F64)
-        g = torch.cat([W[g0 + 6].to(F64).expand(H, D), W[g0 + 7].to(F64).expand(Hkv, D)])[None]
+        g = torch.cat([at("q_norm").to(F64).expand(H, D), at("k_norm").to(F64).expand(Hkv, D)])[None]
         n = xd * torch.rsqrt(xd.pow(2).mean(-1, keepdim=True) + c.eps) * g
         zero = torch.zeros_like(n[..., :half])
         o, E = rotate(n[..., :half], n[..., half:], zero, zero, RN + 3 * U, cs, sn, dsc)
         v = x[:, H + Hkv:].to(F64)
         return (o[:, :H], rounded(o, E)[:, :H]), (o[:, H:], E[:, H:]), (v, torch.zeros_like(v))
-    y, E = gemm_ref(x0, W[g0 + 1], c.eps)
+    y, E = gemm_ref(x0, at("wqkv"), c.eps)
     if c.qkv_bias:
-        y = y + W[g0 + 6].to(F64)[None, :]
+        y = y + at("bqkv").to(F64)[None, :]
         E = E + U * y.abs()
     M = y.shape[0]
     y, E = y.view(M, H + 2 * Hkv, half, 2), E.view(M, H + 2 * Hkv, half, 2)  # pairs (dim i, dim i + D/2)

@@ -47,9 +47,9 @@ import pytest
 import torch
 
 from p2p_llm_tunnel_amd import ops
-from p2p_llm_tunnel_amd.models.tiny_llm import LlamaConfig, TinyLlama
+from p2p_llm_tunnel_amd.models.tiny_llm import LlamaConfig, TinyLlama, llama_dims
 from p2p_llm_tunnel_amd.utils import kv_fp8_ref as ref
-from test_gpu_fused_stages import BF, F64, U, bf64, flip, layer_w, rounded, stage_attn, worst
+from test_gpu_fused_stages import BF, F64, U, bf64, flip, layer_w, rounded, stage_attn, table_layout, worst
 from test_gpu_kv_fp8 import (EPS, F8, N_SLOTS, NAN_BYTE, PLANTS, SCALING, angles, appended_reference, decoded,
                              judge_rows, layout, rotate)
 from test_gpu_qk_norm import RN
@@ -120,11 +120,7 @@ IDS = [c.name for c in ALL]
 
 def dims_of(case):
     """The LlamaDims ``TinyLlama.fused_decoder`` builds for the case's model (max_batch = N_SLOTS, an FP8 cache)."""
-    c = case.cfg
-    return ops.LlamaDims(vocab=c.vocab, dim=c.dim, n_layers=c.n_layers, H=c.n_heads, Hkv=c.n_kv_heads, D=c.head_dim,
-                         ffn=c.ffn, max_seq=c.max_seq, max_batch=N_SLOTS + 1, eps=c.eps, theta=c.rope_theta,
-                         qk_norm=int(c.qk_norm), qkv_bias=int(c.qkv_bias), rope_table=int(c.rope_scaling is not None),
-                         kv_fp8=1)
+    return llama_dims(case.cfg, N_SLOTS + 1, kv_fp8=True)
 
 
 def plan_of(case):
@@ -356,10 +352,9 @@ def gemm_ref_exact(x, w, eps):
     return y, 8 * U * y.abs()
 
 
-def table_of(cfg, W):
-    """(the layers' part of the weight table W, shifted so that ``layer_w`` indexes it; the RoPE table or None)."""
-    shift = int(cfg.rope_scaling is not None)
-    return W[shift:], (W[3] if shift else None)
+def rope_table_of(cfg, W):
+    """The RoPE frequency table in the weight table W of a scaled model, or None."""
+    return W[table_layout(cfg).index("inv_freq")] if cfg.rope_scaling is not None else None
 
 
 def reference(case, W, layer, x0, pos, raw=None):
@@ -369,15 +364,15 @@ def reference(case, W, layer, x0, pos, raw=None):
     reference here as "qkv": (y, bound)."""
     c = case.cfg
     H, Hkv, D, half = c.n_heads, c.n_kv_heads, c.head_dim, c.head_dim // 2
-    Wl, table = table_of(c, W)
+    table = rope_table_of(c, W)
     cs, sn, dsc = angles(c, pos, table)
-    y, E = gemm_ref_exact(x0, layer_w(c, Wl, layer, 1), c.eps)
+    y, E = gemm_ref_exact(x0, layer_w(c, W, layer, "wqkv"), c.eps)
     if c.qk_norm:
         if raw is None:
             return {"qkv": (y, rounded(y, E))}
         x = raw.view(-1, H + 2 * Hkv, D)
         xd = x[:, :H + Hkv].to(F64)
-        g = torch.cat([layer_w(c, Wl, layer, 6).to(F64).expand(H, D), layer_w(c, Wl, layer, 7).to(F64).expand(Hkv, D)])[None]
+        g = torch.cat([layer_w(c, W, layer, "q_norm").to(F64).expand(H, D), layer_w(c, W, layer, "k_norm").to(F64).expand(Hkv, D)])[None]
         n = xd * torch.rsqrt(xd.pow(2).mean(-1, keepdim=True) + c.eps) * g
         zero = torch.zeros_like(n[..., :half])
         o, Eo = rotate(n[..., :half], n[..., half:], zero, zero, RN + 3 * U, cs, sn, dsc)
@@ -385,7 +380,7 @@ def reference(case, W, layer, x0, pos, raw=None):
         return {"q": (o[:, :H], rounded(o, Eo)[:, :H]), "k": (o[:, H:], Eo[:, H:]), "v": (v, torch.zeros_like(v)),
                 "qkv": (y, rounded(y, E))}
     if c.qkv_bias:
-        y = y + layer_w(c, Wl, layer, 6).to(F64)[None, :]
+        y = y + layer_w(c, W, layer, "bqkv").to(F64)[None, :]
         E = E + U * y.abs()
     M = y.shape[0]
     y, E = y.view(M, H + 2 * Hkv, half, 2), E.view(M, H + 2 * Hkv, half, 2)  # pairs (dim i, dim i + D/2)
@@ -496,8 +491,8 @@ def emulate_rows(case, W, layer, x0, pos, slip=None, order=None):
     the products are summed in."""
     c = case.cfg
     H, Hkv, D, half, K = c.n_heads, c.n_kv_heads, c.head_dim, c.head_dim // 2, c.dim
-    Wl, table = table_of(c, W)
-    x, w = x0.to(F32), layer_w(c, Wl, layer, 1).to(F32)
+    table = rope_table_of(c, W)
+    x, w = x0.to(F32), layer_w(c, W, layer, "wqkv").to(F32)
     M = x.shape[0]
     p = ops.step_plan(dims_of(case), case.rows).qkv
     S = K // 32
@@ -523,7 +518,7 @@ def emulate_rows(case, W, layer, x0, pos, slip=None, order=None):
     rs = torch.rsqrt(ss * (torch.tensor(1.0, dtype=F32) / K) + torch.tensor(c.eps, dtype=F32))
     y = acc * rs[:, None]
     if c.qkv_bias:
-        y = y + layer_w(c, Wl, layer, 6).to(F32)[None, :]
+        y = y + layer_w(c, W, layer, "bqkv").to(F32)[None, :]
     inv = table if table is not None else torch.exp2(-math.log2(c.rope_theta) * 2 * torch.arange(half, dtype=F32) / D)
     ang = pos.to(F32)[:, None, None] * inv.to(F32)[None, None, :]
     cs, sn = torch.cos(ang), torch.sin(ang)
@@ -531,7 +526,7 @@ def emulate_rows(case, W, layer, x0, pos, slip=None, order=None):
     if c.qk_norm:  # STORE, then k_qknorm_rope: plain row order, RoPE partners d and d + D/2
         raw = y.to(BF)
         xh = raw.to(F32).view(M, H + 2 * Hkv, D)
-        g = torch.cat([layer_w(c, Wl, layer, 6).to(F32).expand(H, D), layer_w(c, Wl, layer, 7).to(F32).expand(Hkv, D)])
+        g = torch.cat([layer_w(c, W, layer, "q_norm").to(F32).expand(H, D), layer_w(c, W, layer, "k_norm").to(F32).expand(Hkv, D)])
         n = xh[:, :H + Hkv] * torch.rsqrt(xh[:, :H + Hkv].pow(2).sum(-1, keepdim=True) / D + c.eps) * g[None]
         x1, x2 = n[..., :half], n[..., half:]
         vf = xh[:, H + Hkv:]
@@ -583,7 +578,7 @@ def test_fp32_emulation_passes_and_the_cap_holds_by_the_reference_alone(case):
     b = emulate(case, order=torch.randperm(case.dim, generator=torch.Generator().manual_seed(7)))
     assert all(torch.equal(a[k], b[k]) for k in ("kc", "vc")) and torch.equal(a["q"].view(torch.int16), b["q"].view(torch.int16))
     inp = inputs(case)
-    x, w = inp.weights[0][inp.tokens].to(F32), layer_w(case.cfg, table_of(case.cfg, inp.weights)[0], 0, 1).to(F32)
+    x, w = inp.weights[0][inp.tokens].to(F32), layer_w(case.cfg, inp.weights, 0, "wqkv").to(F32)
     order = torch.randperm(case.dim, generator=torch.Generator().manual_seed(8))
     assert torch.equal(x @ w.T, x[:, order] @ w[:, order].T) and torch.equal((x @ w.T).to(F64), x.to(F64) @ w.to(F64).T)
 
@@ -659,8 +654,7 @@ def observe_gpu(case):
 
     obs = {}
     if c.n_layers == 2:
-        Wl = table_of(c, dec.weights)[0]
-        zeroed = [layer_w(c, Wl, 1, 2), layer_w(c, Wl, 1, 5)]
+        zeroed = [layer_w(c, dec.weights, 1, "wo"), layer_w(c, dec.weights, 1, "w_down")]
         saved = [t.clone() for t in zeroed]
         for t in zeroed:
             t.zero_()

@@ -25,9 +25,9 @@ import pytest
 import torch
 
 from p2p_llm_tunnel_amd import ops
-from p2p_llm_tunnel_amd.models.tiny_llm import CONFIGS, GEMM_WEIGHTS, TinyLlama
+from p2p_llm_tunnel_amd.models.tiny_llm import CONFIGS, GEMM_WEIGHTS, TinyLlama, llama_dims
 from test_gpu_fused_stages import (BF, CASES, F64, SENTINEL_BITS, SENTINEL_ID, Case, _cfg, fmt, inputs, stage_ratios,
-                                   step_plan, table_stride)
+                                   step_plan, table_layout)
 from test_gpu_kv_fp8 import LOGIT_BOUND, N_NEW, SCALING, _ids, collect, reference_generation
 
 cuda = pytest.mark.skipif(not torch.cuda.is_available(), reason="needs a HIP device")
@@ -99,8 +99,8 @@ def test_the_cases_cover_the_plans_they_claim():
 # ---------------------------------------------------------------- tables
 def gemm_indices(cfg):
     """Indices of the five GEMM weights in the fused table, in the order of their scales."""
-    g0 = 3 + (cfg.rope_scaling is not None)
-    return [2] + [g0 + table_stride(cfg) * L + k for L in range(cfg.n_layers) for k in (1, 2, 4, 5)]
+    T = table_layout(cfg)
+    return [T.index("lm_head")] + [T.index(n, L) for L in range(cfg.n_layers) for n in GEMM_WEIGHTS]
 
 
 def pow2_scales(n, salt):
@@ -127,11 +127,7 @@ def tables(case, kind):
 
 
 def dims_of(case, kv8):
-    c = case.cfg
-    return ops.LlamaDims(vocab=c.vocab, dim=c.dim, n_layers=c.n_layers, H=c.n_heads, Hkv=c.n_kv_heads, D=c.head_dim,
-                         ffn=c.ffn, max_seq=c.max_seq, max_batch=case.max_batch + 1, eps=c.eps, theta=c.rope_theta,
-                         qk_norm=int(c.qk_norm), qkv_bias=int(c.qkv_bias), rope_table=int(c.rope_scaling is not None),
-                         kv_fp8=kv8)
+    return llama_dims(case.cfg, case.max_batch + 1, kv8)
 
 
 def as_bytes(t):
@@ -196,10 +192,10 @@ def quantized_model(case):
 
 def dequantized_table(table, cfg):
     """The FP8 table as the references read it: every GEMM weight q * s in fp64 (exact), everything else as is."""
-    n = len(table) - (1 + 4 * cfg.n_layers)
-    W = list(table[:n])
-    for j, i in enumerate(gemm_indices(cfg)):
-        W[i] = table[i].to(F64) * table[n + j].to(F64)[:, None]
+    T = table_layout(cfg, True)
+    W = list(table[:len(table_layout(cfg))])
+    for name, L in [("lm_head", None)] + [(n, L) for L in range(cfg.n_layers) for n in GEMM_WEIGHTS]:
+        W[T.index(name, L)] = table[T.index(name, L)].to(F64) * table[T.scale_index(name, L)].to(F64)[:, None]
     return W
 
 
@@ -240,7 +236,7 @@ def test_general_scales_match_fp64(case):
         torch.cuda.synchronize()
         return {k: views[k][:B].cpu() for k in ("q", "attn", "h", "resid")}
 
-    w_down = dec.weights[8]  # zero bytes: the final residual of the first pass is the residual after O
+    w_down = dec.weights[dec.table.index("w_down", 0)]  # zero bytes: the final residual of the first pass is the residual after O
     saved = w_down.clone()
     w_down.view(torch.uint8).zero_()
     first = run()
@@ -262,7 +258,7 @@ def test_reads_stay_inside_the_weights_and_scales(case, kv8):
     """Every FP8 weight is a uint8 view into the middle of a buffer of 0x7F (the e4m3 NaN) and every scale a view
     into a buffer of NaN: a byte or a scale read from outside reaches the outputs as NaN."""
     f8, _ = tables(case, "pow2")
-    n = len(f8) - (1 + 4 * case.cfg.n_layers)
+    n = len(table_layout(case.cfg))
     pad = 4096
     wrapped, bufs = [t.cuda() for t in f8], []
     for j, i in enumerate(gemm_indices(case.cfg)):
@@ -302,7 +298,8 @@ def test_the_decoder_validates_an_fp8_table_on_the_host():
         return good[:i] + [t] + good[i + 1:]
 
     build(good)
-    wq, sq = 4, n + 1  # layer 0's wqkv and its scale
+    T = table_layout(case.cfg, True)
+    wq, sq = T.index("wqkv", 0), T.scale_index("wqkv", 0)  # layer 0's wqkv and its scale
     with pytest.raises(TypeError, match="weight_fp8 is set"):
         build(with_(wq, bf[wq].cuda()))  # a bf16 weight in an FP8 table
     with pytest.raises(TypeError, match="weight_fp8 is set"):

@@ -352,8 +352,8 @@ def emu_ratios(obs):
     D64 = list(W[:n])
     for j, i in enumerate((2, 4, 5, 7, 8)):
         D64[i] = W[i].to(F64) * W[n + j].to(F64)[:, None]
-    stage = lambda case, W, x0, pos, layer: stage_qkv_bias(case.cfg, layer_w(case.cfg, W, layer, 1),
-                                                           layer_w(case.cfg, W, layer, 6), x0, pos)
+    stage = lambda case, W, x0, pos, layer: stage_qkv_bias(case.cfg, layer_w(case.cfg, W, layer, "wqkv"),
+                                                           layer_w(case.cfg, W, layer, "bqkv"), x0, pos)
     return stage_ratios(EMU, D64, obs, qkv_stage=stage)
 
 
