@@ -163,16 +163,20 @@ class _Reader:
 
 def load_llama(path: str, device="cuda", max_batch: int = 8, max_seq: int | None = None,
                fused: bool = True, prefix: str = "model.", kv_dtype: str = "bf16",
-               weight_dtype: str = "bf16") -> TinyLlama:
+               weight_dtype: str = "bf16", kv_scales=None) -> TinyLlama:
     """A TinyLlama with the checkpoint's weights (bf16 on ``device``). ``kv_dtype``: "bf16" or "fp8", the KV
-    cache's format (``TinyLlama``), for every family alike; ``k_scale`` / ``v_scale`` tensors a checkpoint may
-    carry are not read (the FP8 cache's scale is 1). ``weight_dtype``: "bf16" or "fp8" (docs/WEIGHT_FP8.md): each
+    cache's format (``TinyLlama``), for every family alike. ``kv_scales`` ("fp8" only): None (scale 1: ``k_scale`` /
+    ``v_scale`` tensors a checkpoint may carry are then not read), a ``KvScales``, or "checkpoint": the per-layer
+    ``self_attn.k_scale`` / ``.v_scale`` (or ``kv_scale``) tensors of the checkpoint, each a scalar broadcast over
+    the layer's KV heads; a checkpoint that lacks them for any layer is refused. ``weight_dtype``: "bf16" or "fp8" (docs/WEIGHT_FP8.md): each
     layer's GEMM weights are quantised on ``device`` as soon as the layer is read and its bf16 tensors dropped, so
     the device never holds the bf16 and the FP8 copies of all layers together. The checkpoint itself is bf16 / fp16
     / fp32 either way: one that is already quantised on disk is treated as before."""
     from p2p_llm_tunnel_amd.models.tiny_llm import WEIGHT_DTYPES, quantize_layer_
     if weight_dtype not in WEIGHT_DTYPES:
         raise ValueError(f"weight_dtype must be one of {list(WEIGHT_DTYPES)}, got {weight_dtype!r}")
+    from p2p_llm_tunnel_amd.models import kv_scales as kvs
+    kv_scales = kvs.parse_kv_scales(kv_scales, kv_dtype)  # refused with a bf16 cache before anything is read
     cfg, raw = read_config(path, max_seq)
     c = cfg
     rd = _Reader(path)
@@ -194,6 +198,8 @@ def load_llama(path: str, device="cuda", max_batch: int = 8, max_seq: int | None
             w["lm_head"] = w["embed"]
         else:
             raise KeyError("checkpoint has no lm_head.weight and does not tie embeddings")
+        if kv_scales == kvs.CHECKPOINT:
+            kv_scales = kvs.read_checkpoint(rd.has, rd.get, c.n_layers, c.n_kv_heads, prefix)
         for i in range(c.n_layers):
             p = f"{prefix}layers.{i}."
             q = t(p + "self_attn.q_proj.weight", (q_out, c.dim))
@@ -236,7 +242,7 @@ def load_llama(path: str, device="cuda", max_batch: int = 8, max_seq: int | None
     finally:
         rd.close()
     return TinyLlama.from_weights(cfg, w, device=dev, max_batch=max_batch, fused=fused, kv_dtype=kv_dtype,
-                                  weight_dtype=weight_dtype)
+                                  weight_dtype=weight_dtype, kv_scales=kv_scales)
 
 
 class Detokenizer:

@@ -415,11 +415,15 @@ class Engine:
 
     def __init__(self, device="cuda:0", config="tiny", max_batch=8, seed=0, use_graph=True, rows=64, model=None,
                  small_rows=16, prefix_cache=False, prefix_min=16, penalties=False, kv_dtype="bf16",
-                 guided=False, guided_states=1024, weight_dtype="bf16"):
+                 guided=False, guided_states=1024, weight_dtype="bf16", kv_scales=None):
+        if kv_scales is not None and kv_dtype != "fp8" and getattr(model, "kv_dtype", "bf16") != "fp8":
+            raise ValueError("kv_scales need kv_dtype='fp8' (--kv-dtype fp8): a bf16 KV cache has no scales")
         if model is None:
             from p2p_llm_tunnel_amd.models.tiny_llm import TinyLlama
             model = TinyLlama(config, device=device, max_batch=max_batch, seed=seed, fused=True, kv_dtype=kv_dtype,
-                              weight_dtype=weight_dtype)
+                              weight_dtype=weight_dtype, kv_scales=kv_scales)
+        elif kv_scales is not None and getattr(model, "kv_scales", None) != kv_scales:
+            raise ValueError("kv_scales given, but the injected model was built with other scales or none")
         elif kv_dtype != "bf16" and getattr(model, "kv_dtype", "bf16") != kv_dtype:
             raise ValueError(f"kv_dtype={kv_dtype!r}, but the injected model was built with "
                              f"{getattr(model, 'kv_dtype', 'bf16')!r} caches")

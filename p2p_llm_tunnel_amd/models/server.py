@@ -693,7 +693,7 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
                  engine: Engine | None = None, checkpoint: str | None = None, max_seq: int | None = None,
                  tokenizer=None, default_temperature: float = 0.0, prefix_cache: bool = False, prefix_min: int = 16,
                  embed_pooling: str = "mean", penalties: bool = False, kv_dtype: str = "bf16",
-                 guided: bool = False, guided_states: int = 1024, weight_dtype: str = "bf16"):
+                 guided: bool = False, guided_states: int = 1024, weight_dtype: str = "bf16", kv_scales=None):
     """Engine + HTTP front-end; returns (server, port, engine). ``server.shutdown()``
     stops the HTTP side, ``engine.stop()`` the GPU side. ``checkpoint``: serve a
     Hugging Face Llama checkpoint directory (weights + tokenizer) instead of
@@ -708,8 +708,17 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
     describes instead of answering 400; with ``guided`` /v1/chat/completions and
     /v1/completions act on what ``guided_params`` describes, which is ignored
     without the switch. ``weight_dtype`` ("bf16" or "fp8", the format of the GEMM weights:
-    docs/WEIGHT_FP8.md) is ``Engine``'s and ``load_llama``'s, and an injected engine's model must have it."""
+    docs/WEIGHT_FP8.md) is ``Engine``'s and ``load_llama``'s, and an injected engine's model must have it.
+    ``kv_scales`` (``kv_dtype="fp8"`` only): a ``KvScales``, the path of a JSON file ``{"k": [[..]], "v": [[..]]}``
+    or "checkpoint" (the checkpoint's own ``k_scale`` / ``v_scale`` tensors): per-layer, per-KV-head scales of the
+    FP8 cache (docs/KV_FP8.md); an injected engine's model must carry the same."""
     kv_dtype = parse_kv_dtype(kv_dtype)
+    from p2p_llm_tunnel_amd.models import kv_scales as kvs
+    kv_scales = kvs.parse_kv_scales(kv_scales, kv_dtype)
+    if kv_scales == kvs.CHECKPOINT and not (checkpoint and engine is None):
+        raise ValueError("kv_scales='checkpoint' (--kv-scales checkpoint) needs a checkpoint to read them from")
+    if engine is not None and kv_scales is not None and getattr(engine.model, "kv_scales", None) != kv_scales:
+        raise ValueError("kv_scales given, but the injected engine's model was built with other scales or none")
     weight_dtype = parse_weight_dtype(weight_dtype)
     if engine is not None and getattr(engine.model, "weight_dtype", "bf16") != weight_dtype:
         raise ValueError(f"weight_dtype={weight_dtype!r}, but the injected engine's model has "
@@ -729,14 +738,14 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
         import os
         from p2p_llm_tunnel_amd.models.checkpoint import Tokenizer, load_llama
         model = load_llama(checkpoint, device=device, max_batch=max_batch, max_seq=max_seq, kv_dtype=kv_dtype,
-                           weight_dtype=weight_dtype)
+                           weight_dtype=weight_dtype, kv_scales=kv_scales)
         tok = tok or Tokenizer.for_checkpoint(checkpoint)
         engine = Engine(device=device, max_batch=max_batch, model=model, prefix_cache=prefix_cache,
                         prefix_min=prefix_min, penalties=penalties, guided=guided, guided_states=guided_states)
         model_name = model_name or os.path.basename(os.path.normpath(checkpoint))
     engine = engine or Engine(device=device, config=config, max_batch=max_batch, prefix_cache=prefix_cache,
                               prefix_min=prefix_min, penalties=penalties, kv_dtype=kv_dtype, guided=guided,
-                              guided_states=guided_states, weight_dtype=weight_dtype)
+                              guided_states=guided_states, weight_dtype=weight_dtype, kv_scales=kv_scales)
     srv = FrontEnd(engine, host, port, model_name or f"p2pt-{config}", tokenizer=tok,
                    default_temperature=default_temperature, embed_pooling=embed_pooling)
     return srv, srv.server_address[1], engine
@@ -776,7 +785,9 @@ def kv_cache_line(model, kv_dtype: str) -> str:
     k, v = getattr(model, "k_cache", None), getattr(model, "v_cache", None)
     nbytes = sum(t.numel() * t.element_size() for t in (k, v) if t is not None)
     shape = "x".join(str(n) for n in k.shape) if k is not None else "?"
-    return f"kv cache: {nbytes} bytes ({kv_dtype}, K and V of {shape})"
+    scales = getattr(model, "kv_scales", None)
+    return (f"kv cache: {nbytes} bytes ({kv_dtype}, K and V of {shape})"
+            + (f"; scales in use: {scales.describe()}" if scales is not None else ""))
 
 
 def replica_cmd(a, i: int) -> list[str]:
@@ -795,6 +806,8 @@ def replica_cmd(a, i: int) -> list[str]:
         cmd += ["--penalties"]
     if getattr(a, "kv_dtype", "bf16") != "bf16":
         cmd += ["--kv-dtype", a.kv_dtype]
+    if getattr(a, "kv_scales", None):
+        cmd += ["--kv-scales", a.kv_scales]
     if getattr(a, "guided", False):
         cmd += ["--guided", "--guided-states", str(a.guided_states)]
     if getattr(a, "weight_dtype", "bf16") != "bf16":
@@ -863,9 +876,14 @@ def arg_parser() -> argparse.ArgumentParser:
                          "everything generated (repeat_last_n: only -1, or 0 = off). Costs a [max_batch + 1, vocab] "
                          "int32 count table and four more captured graphs")
     ap.add_argument("--kv-dtype", choices=KV_DTYPE_CHOICES, default="bf16",
-                    help="format of the KV cache: bf16, or fp8 (OCP e4m3, scale 1, no calibration): half the bytes "
-                         "per cached token, so the same memory holds twice the context or slots; values beyond "
-                         "+-448 saturate (docs/KV_FP8.md)")
+                    help="format of the KV cache: bf16, or fp8 (OCP e4m3; scale 1 unless --kv-scales gives scales): half "
+                         "the bytes per cached token, so the same memory holds twice the context or slots; values "
+                         "beyond +-448 times the scale saturate (docs/KV_FP8.md)")
+    ap.add_argument("--kv-scales", default=None, metavar="checkpoint|FILE",
+                    help="per-layer, per-KV-head scales of the fp8 KV cache (with --kv-dtype fp8): 'checkpoint' reads "
+                         "the checkpoint's self_attn.k_scale / .v_scale (or kv_scale) tensors; FILE is JSON "
+                         '{"k": [[...]], "v": [[...]]}, one row per layer and one number per KV head, as '
+                         "scripts/calibrate_kv.py writes it (docs/KV_FP8.md)")
     ap.add_argument("--weight-dtype", choices=WEIGHT_DTYPE_CHOICES, default="bf16",
                     help="format of the GEMM weights (QKV, O, gate/up, down and the LM head): bf16, or fp8 (OCP e4m3 "
                          "with one fp32 scale per output row, per-row absmax, no calibration; the activations stay "
@@ -884,13 +902,16 @@ def arg_parser() -> argparse.ArgumentParser:
 
 def main(argv=None):
     a = arg_parser().parse_args(argv)
+    if a.kv_scales and a.kv_dtype != "fp8":
+        raise SystemExit("--kv-scales needs --kv-dtype fp8: a bf16 KV cache has no scales")
     if a.gpus > 0:
         raise SystemExit(_replicas(a))
     srv, port, engine = start_server(a.host, a.port, a.device, a.config, a.max_batch, checkpoint=a.checkpoint,
                                      max_seq=a.max_seq, default_temperature=a.default_temperature,
                                      prefix_cache=a.prefix_cache, prefix_min=a.prefix_min,
                                      embed_pooling=a.embed_pooling, penalties=a.penalties, kv_dtype=a.kv_dtype,
-                                     guided=a.guided, guided_states=a.guided_states, weight_dtype=a.weight_dtype)
+                                     guided=a.guided, guided_states=a.guided_states, weight_dtype=a.weight_dtype,
+                                     kv_scales=a.kv_scales)
     print(weights_line(engine.model, a.weight_dtype), flush=True)
     print(kv_cache_line(engine.model, a.kv_dtype), flush=True)
     print(f"inference endpoint on http://{a.host}:{port} ({a.checkpoint or a.config}, {a.device})", flush=True)

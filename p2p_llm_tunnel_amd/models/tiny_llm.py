@@ -28,6 +28,7 @@ import torch.nn.functional as F
 
 from p2p_llm_tunnel_amd import ops
 from p2p_llm_tunnel_amd.models import rope as rope_mod
+from p2p_llm_tunnel_amd.models.kv_scales import KvScales
 from p2p_llm_tunnel_amd.models.rope import RopeScaling
 
 
@@ -140,9 +141,11 @@ def capture(fn, device, warmup: int = 2):
 class TinyLlama:
     def __init__(self, cfg: LlamaConfig | str = "tiny", device="cuda", max_batch: int = 8, seed: int = 0,
                  fused: bool = True, weights: dict | None = None, kv_dtype: str = "bf16",
-                 weight_dtype: str = "bf16"):
-        """``kv_dtype``: "bf16" (default) or "fp8": the K/V caches as ``torch.float8_e4m3fn`` (OCP e4m3, scale 1,
-        half the bytes; docs/KV_FP8.md), which only the fused step reads and writes.
+                 weight_dtype: str = "bf16", kv_scales: KvScales | None = None):
+        """``kv_dtype``: "bf16" (default) or "fp8": the K/V caches as ``torch.float8_e4m3fn`` (OCP e4m3, half the
+        bytes; docs/KV_FP8.md), which only the fused step reads and writes. ``kv_scales`` (a ``KvScales``; "fp8"
+        only): fp32 scales per layer and KV head, so the stored byte is e4m3(x / s) and attention undoes the scale;
+        None is scale 1.
 
         ``weight_dtype``: "bf16" (default) or "fp8": wqkv, wo, w_gate_up, w_down and lm_head as e4m3 bytes with
         one fp32 scale per output row (docs/WEIGHT_FP8.md), quantised here layer by layer (the bf16 tensor of each
@@ -161,6 +164,11 @@ class TinyLlama:
         if weight_dtype not in WEIGHT_DTYPES:
             raise ValueError(f"weight_dtype must be one of {list(WEIGHT_DTYPES)}, got {weight_dtype!r}")
         self.kv_dtype = kv_dtype
+        if kv_scales is not None:
+            if not isinstance(kv_scales, KvScales):
+                raise TypeError(f"kv_scales must be a KvScales, got {type(kv_scales).__name__}")
+            kv_scales.check(self.cfg.n_layers, self.cfg.n_kv_heads, kv_dtype)
+        self.kv_scales = kv_scales
         self.weight_dtype = weight_dtype
         self.lm_head_q = self.lm_head_s = None  # weight_dtype "fp8": the LM head's bytes and row scales
         self.fused = fused
@@ -219,9 +227,9 @@ class TinyLlama:
 
     @classmethod
     def from_weights(cls, cfg: LlamaConfig, weights: dict, device="cuda", max_batch: int = 8, fused: bool = True,
-                     kv_dtype: str = "bf16", weight_dtype: str = "bf16"):
+                     kv_dtype: str = "bf16", weight_dtype: str = "bf16", kv_scales: KvScales | None = None):
         return cls(cfg, device=device, max_batch=max_batch, fused=fused, weights=weights, kv_dtype=kv_dtype,
-                   weight_dtype=weight_dtype)
+                   weight_dtype=weight_dtype, kv_scales=kv_scales)
 
     def _quantize_weights(self):
         """``weight_dtype`` "fp8": every layer's GEMM weights and the LM head to e4m3 + row scales, one tensor at
@@ -362,7 +370,9 @@ class TinyLlama:
     def fused_decoder(self) -> ops.FusedLlamaDecoder:
         if self._fused is None:
             self._fused = ops.FusedLlamaDecoder(self.dims(), self.fused_weights(), self.k_cache, self.v_cache,
-                                                weight_fp8=self.weight_dtype == "fp8")
+                                                weight_fp8=self.weight_dtype == "fp8",
+                                                kv_scales=(self.kv_scales.table(self.device)
+                                                           if self.kv_scales is not None else None))
         return self._fused
 
     def step_rows(self, tokens, pos, slots=None, emit_rows=0, pos_range=None):
@@ -484,9 +494,18 @@ class TinyLlama:
         """fp32 forward of full sequences [B, T]; returns the final normed hidden
         state of every position [B, T, dim] (what the LM head multiplies).
         ``kv_round``: how K and V rows are stored, a function of the fp32 rows. None: the model's own cache
-        format, bf16 rounding or ``e4m3_round`` (one rounding from fp32, not through bf16)."""
+        format, bf16 rounding or ``e4m3_round`` (one rounding from fp32, not through bf16). With ``kv_scales`` (and
+        no ``kv_round``) a row of layer i and KV head h is stored as the kernels store it, e4m3_round(x * fp32(1 / s)),
+        and read back times s."""
+        scaled = kv_round is None and self.kv_scales is not None
         if kv_round is None:
             kv_round = e4m3_round if self.kv_dtype == "fp8" else (lambda t: t.to(torch.bfloat16).float())
+
+        def kv_store(t, which, layer):  # t: [B, T, Hkv, D]
+            if not scaled:
+                return kv_round(t)
+            s = (self.kv_scales.k if which == "k" else self.kv_scales.v)[layer].to(t.device)[None, None, :, None]
+            return e4m3_round(t.float() * (1.0 / s)) * s
         c = self.cfg
         B, T = seqs.shape
         f32 = lambda t: t.float()
@@ -526,11 +545,11 @@ class TinyLlama:
                 B, T, c.n_kv_heads, c.head_dim)
             # V is stored from the fp32 projection (the bf16 rounding of it is the bf16 store itself; the FP8 store
             # rounds the fp32 value once). A QK-norm model's V passes through the bf16 projection buffer first.
-            v = kv_round((qkv if c.qk_norm else raw)[..., (c.n_heads + c.n_kv_heads) * c.head_dim:]).view(
-                B, T, c.n_kv_heads, c.head_dim)
+            v = kv_store((qkv if c.qk_norm else raw)[..., (c.n_heads + c.n_kv_heads) * c.head_dim:].view(
+                B, T, c.n_kv_heads, c.head_dim), "v", i)
             if c.qk_norm:
                 q, k = rms(q, L["q_norm"]), rms(k, L["k_norm"])
-            q, k = bf(rope(q)), kv_round(rope(k))
+            q, k = bf(rope(q)), kv_store(rope(k), "k", i)
             k = k.repeat_interleave(G, dim=2)
             v = v.repeat_interleave(G, dim=2)
             s = torch.einsum("bqhd,bkhd->bhqk", q, k) / math.sqrt(c.head_dim) + mask

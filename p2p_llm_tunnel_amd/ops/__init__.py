@@ -108,6 +108,9 @@ def lib() -> ctypes.CDLL:
         _LIB.p2pt_llama_plan_kernels_w.argtypes = [ctypes.POINTER(LlamaDims), i, i, ctypes.POINTER(WeightPlan)]
         _LIB.p2pt_llama_decode_w.argtypes = [ctypes.POINTER(LlamaDims), ctypes.POINTER(WeightPlan), ctypes.POINTER(vp),
                                              vp, vp, vp, vp, vp, i, i, vp, ctypes.c_size_t, vp, vp, vp]
+        _LIB.p2pt_llama_decode_kv.argtypes = [ctypes.POINTER(LlamaDims), ctypes.POINTER(WeightPlan), vp,
+                                              ctypes.POINTER(vp), vp, vp, vp, vp, vp, i, i, vp, ctypes.c_size_t, vp,
+                                              vp, vp]
         ip = ctypes.POINTER(ctypes.c_int)
         _LIB.p2pt_llama_weight_layout.argtypes = [ctypes.POINTER(LlamaDims), ctypes.POINTER(WeightPlan), ip, ip, i]
         _LIB.p2pt_attn_span.argtypes = [i, i]
@@ -118,7 +121,7 @@ def lib() -> ctypes.CDLL:
         for fn in ("p2pt_rmsnorm", "p2pt_silu_mul", "p2pt_rope_qkv_cache", "p2pt_decode_attention", "p2pt_argmax",
                    "p2pt_skinny_gemm", "p2pt_llama_decode", "p2pt_sample", "p2pt_logprobs", "p2pt_llama_plan", "p2pt_attn_span",
                    "p2pt_llama_kv_plan", "p2pt_llama_plan_kernels", "p2pt_llama_weight_plan",
-                   "p2pt_llama_plan_kernels_w", "p2pt_llama_decode_w", "p2pt_llama_weight_layout",
+                   "p2pt_llama_plan_kernels_w", "p2pt_llama_decode_w", "p2pt_llama_decode_kv", "p2pt_llama_weight_layout",
                    "p2pt_max_rows", "p2pt_skinny_bench", "p2pt_attn_bench", "p2pt_kv_copy", "p2pt_max_kv_copy_jobs",
                    "p2pt_embed_pool", "p2pt_max_embed_jobs", "p2pt_qk_norm_rope_cache", "p2pt_penalize",
                    "p2pt_penalty_reset", "p2pt_max_logit_bias", "p2pt_guide", "p2pt_guide_reset"):
@@ -891,7 +894,7 @@ class FusedLlamaDecoder:
     with ``dims.qkv_bias`` the q/k/v bias of Qwen2 is added in the QKV GEMM's epilogue, still 5; with
     ``dims.rope_table`` the kernel that rotates reads its frequencies from the table's ``inv_freq`` entry, and the
     kernel count does not change; with ``dims.kv_fp8`` the caches are ``torch.float8_e4m3fn`` (or uint8), one OCP
-    e4m3 byte per element at scale 1, written by the _KV8 epilogues / ``k_qknorm_rope`` variant and read by
+    e4m3 byte per element at scale 1 (or with ``kv_scales``, below), written by the _KV8 epilogues / ``k_qknorm_rope`` variant and read by
     ``k_attn<D, G, true>``: the same kernel count again).
 
     ``weights`` is laid out as ``WeightTable(dims, weight_fp8)`` says, and every entry is checked against it.
@@ -899,13 +902,20 @@ class FusedLlamaDecoder:
     row order of its weight (docs/WEIGHT_FP8.md, ``quantize_weight_fp8``). Every ``k_skinny`` is then its FP8-weight
     instantiation; the kernel count, ``step_plan`` and the workspace are the same.
 
+    ``kv_scales`` (with ``dims.kv_fp8`` only): fp32 ``[4, n_layers, Hkv]`` on the caches' device, the reciprocals
+    1 / k_scale and 1 / v_scale, then k_scale and v_scale (``models.kv_scales.KvScales.table``), every entry finite
+    and > 0. A stored byte is then ``e4m3(clamp(x * (1 / s)))`` of its layer's and KV head's scale, and ``k_attn``
+    undoes the scale (K's in the score scale, V's in the final normalisation). It is no part of ``dims`` or of the
+    weight table: the plans, the table and the workspace are those of the model without scales, and None runs the
+    step exactly as before.
+
     Holds the weight pointer table and a zero-initialised workspace; ``step``
     validates the per-call tensors and launches on the current stream (capturable
     into a hipGraph: no host sync, no allocation, grids sized by the row count).
     """
 
     def __init__(self, dims: LlamaDims, weights: list, k_cache: torch.Tensor, v_cache: torch.Tensor,
-                 weight_fp8: bool = False):
+                 weight_fp8: bool = False, kv_scales: torch.Tensor | None = None):
         self.dims = dims
         self.weight_fp8 = bool(weight_fp8)
         self._wplan = WeightPlan(w8=int(self.weight_fp8))
@@ -922,6 +932,14 @@ class FusedLlamaDecoder:
                 raise TypeError(f"{name}: a {c.dtype} cache needs dims.kv_fp8 = 1")
         if dims.rope_table not in (0, 1):
             raise ValueError("dims.rope_table must be 0 or 1")
+        if kv_scales is not None:
+            if not dims.kv_fp8:
+                raise ValueError("kv_scales need an FP8 cache (dims.kv_fp8 = 1): a bf16 KV cache has no scales")
+            if not isinstance(kv_scales, torch.Tensor) or kv_scales.dtype != torch.float32 or \
+                    tuple(kv_scales.shape) != (4, dims.n_layers, dims.Hkv):
+                raise ValueError(f"kv_scales must be fp32 [4, {dims.n_layers}, {dims.Hkv}] (1 / k, 1 / v, k, v per layer "
+                                 f"and KV head), got {getattr(kv_scales, 'dtype', type(kv_scales))} "
+                                 f"{tuple(getattr(kv_scales, 'shape', ()))}")
         self.table = table = WeightTable(dims, self.weight_fp8)
         if len(weights) != len(table):
             raise ValueError(f"weight table: embed, final_norm, lm_head, "
@@ -961,6 +979,11 @@ class FusedLlamaDecoder:
             _check_inv_freq(weights[table.index("inv_freq")], dims.D, dev)
         for name, c in (("k_cache", k_cache), ("v_cache", v_cache)):
             _check(c, c.dtype if dims.kv_fp8 else torch.bfloat16, name, dev)
+        if kv_scales is not None:
+            _check(kv_scales, torch.float32, "kv_scales", dev)
+            if not bool((torch.isfinite(kv_scales) & (kv_scales > 0)).all().item()):
+                raise ValueError("kv_scales entries (and their reciprocals) must be finite and > 0")
+        self.kv_scales = kv_scales  # keep alive
         nbytes = lib().p2pt_llama_ws_bytes(ctypes.byref(dims))
         if nbytes == 0:
             raise ValueError("model dims not supported by the fused decode kernels")
@@ -1036,6 +1059,12 @@ class FusedLlamaDecoder:
             raise ValueError(f"rows must be 1..{limit} with matching pos/ids")
         if logits.shape != (B, d.vocab):
             raise ValueError("logits must be [B, vocab]")
+        if self.kv_scales is not None:
+            _ok(lib().p2pt_llama_decode_kv(ctypes.byref(d), ctypes.byref(self._wplan), _p(self.kv_scales), self._wptr,
+                                           _p(self.k_cache), _p(self.v_cache), _p(tokens), _p(pos), _p(slots), B,
+                                           emit_rows, _p(self.ws), self.ws.numel(), _p(logits), _p(ids),
+                                           _stream(tokens)), "llama_decode")
+            return
         if self.weight_fp8:
             _ok(lib().p2pt_llama_decode_w(ctypes.byref(d), ctypes.byref(self._wplan), self._wptr, _p(self.k_cache),
                                           _p(self.v_cache), _p(tokens), _p(pos), _p(slots), B, emit_rows,

@@ -13,9 +13,9 @@ namespace {
 struct LlamaDims {
   int vocab, dim, n_layers, H, Hkv, D, ffn, max_seq, max_batch;
   float eps, theta;
-  // The KV cache holds OCP e4m3fn bytes (scale 1) instead of bf16: the _KV8 epilogues and k_attn<D, G, true>. It sits
+  // The KV cache holds OCP e4m3fn bytes (scale 1, or per-head scales: KvScales) instead of bf16: the _KV8 epilogues and k_attn<D, G, true>. It sits
   // ahead of the three family flags, whose order (qkv_bias last) the plan tests of those families pin.
-  int kv_fp8;
+  int kv_fp8;  // per-head scales, where a model has them, travel beside the plans (KvScales), not here
   int rope_table;  // RoPE frequencies from an fp32 table [D/2] (llama3 / linear scaling): the table's inv_freq entry
   int qk_norm;  // per-head RMSNorm on q and k before RoPE (Qwen3): a sixth kernel per layer
   int qkv_bias;  // a bias on the q, k and v projections (Qwen2): added in the QKV GEMM's epilogue
@@ -62,6 +62,19 @@ struct WeightPlan {
   int w8;  // k_skinny<.., 1>: the five GEMM weights are e4m3 bytes with an fp32 scale per output row
 };
 bool weights_ok(const WeightPlan& w) { return w.w8 == 0 || w.w8 == 1; }
+// The scales of an FP8 cache, beside the plans as WeightPlan is and for the same reason: no field of LlamaDims, no
+// entry of the weight table, so a model without scales plans, lays out and launches what it did. One device buffer,
+// fp32 [4][n_layers][Hkv]: 1 / k_scale, 1 / v_scale (what the writers multiply by, computed once on the host),
+// then k_scale, v_scale (what k_attn undoes them with). nullptr: scale 1. It changes no plan: the kernels are the
+// same instantiations with or without it.
+struct KvScales {
+  const float* table;
+  enum Part : int { K_RECIP, V_RECIP, K, V };
+  // [Hkv] of one part for layer L; nullptr without scales.
+  const float* at(const LlamaDims& d, Part p, int L) const {
+    return table ? table + (size_t(p) * d.n_layers + L) * d.Hkv : nullptr;
+  }
+};
 
 // One workgroup per tn subtiles of 16 >> kpl columns of one 16-row tile.
 //  - K parts (GemmArgs::kpl), where asked for (the d_model-wide O and down
@@ -254,10 +267,12 @@ auto store(void* out) {  // STORE, SILU
 }
 // Every RoPE epilogue. bias and inv_freq: nullptr where the epilogue reads none (launch() refuses a bias or
 // table epilogue without its pointer).
+// k_rscale, v_rscale: the layer's reciprocal cache scales (KvScales), nullptr for scale 1 and for a bf16 cache.
 auto rope(const LlamaDims& d, const int* pos, const int* slot, uint16_t* q, uint16_t* kc, uint16_t* vc,
-          const void* bias, const void* inv_freq) {
+          const void* bias, const void* inv_freq, const float* k_rscale, const float* v_rscale) {
   return [=](GemmArgs& a) {
     a.pos = pos, a.slot = slot, a.nslots = d.max_batch, a.q_out = q, a.kc = kc, a.vc = vc;
+    a.k_rscale = k_rscale, a.v_rscale = v_rscale;
     a.bias = static_cast<const uint16_t*>(bias), a.inv_freq = static_cast<const float*>(inv_freq);
     a.H = d.H, a.Hkv = d.Hkv, a.D = d.D, a.Smax = d.max_seq, a.log2_theta = log2f(d.theta);
   };
@@ -350,6 +365,8 @@ hipError_t launch(const GemmPlan& p, GemmArgs a, hipStream_t s, int w8 = 0) {
   if (epi_has_bias(p.epi) && (p.kpl != 0 || a.bias == nullptr)) return hipErrorInvalidValue;
   // A table epilogue reads its table unconditionally: never without one.
   if (epi_has_table(p.epi) && a.inv_freq == nullptr) return hipErrorInvalidValue;
+  // Cache scales come in pairs, and only to the epilogues that write an FP8 cache.
+  if ((a.k_rscale != nullptr) != (a.v_rscale != nullptr) || (a.k_rscale && !epi_kv8(p.epi))) return hipErrorInvalidValue;
   const SkinnyKernel k = skinny_kernel(p, w8);
   if (!k) return hipErrorInvalidValue;
   a.M = p.M, a.N = p.N, a.K = p.K, a.kpl = p.kpl;
@@ -358,15 +375,19 @@ hipError_t launch(const GemmPlan& p, GemmArgs a, hipStream_t s, int w8 = 0) {
 }
 
 // (span slot, row, KV head) workgroups of 8 waves. Row b reads cache slot
-// slot[b] (nullptr: slot b) of nslots. kv8: the caches hold e4m3 bytes (KvPlan::attn_kv8).
+// slot[b] (nullptr: slot b) of nslots. kv8: the caches hold e4m3 bytes (KvPlan::attn_kv8). k_scale, v_scale: the
+// layer's cache scales [Hkv] (KvScales), both nullptr for scale 1; refused with a bf16 cache.
 hipError_t launch_attn(const AttnPlan& p, int kv8, const void* q, const void* kc, const void* vc, const int* pos,
                        const int* slot, int nslots, float* part_o, float* part_ml, unsigned* counters, void* out,
-                       int H, int Hkv, int Smax, hipStream_t s) {
+                       int H, int Hkv, int Smax, hipStream_t s, const float* k_scale = nullptr,
+                       const float* v_scale = nullptr) {
   const AttnKernel k = attn_kernel(p.D, p.G, kv8);
   if (!k) return hipErrorInvalidValue;
+  if ((k_scale != nullptr) != (v_scale != nullptr) || (k_scale && !kv8)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k, dim3(p.slots, p.grid_y), dim3(512), 0, s, static_cast<const uint16_t*>(q),
                      static_cast<const uint16_t*>(kc), static_cast<const uint16_t*>(vc), pos, slot, nslots, part_o,
-                     part_ml, counters, static_cast<uint16_t*>(out), H, Hkv, Smax, p.stride, 1.f / sqrtf(float(p.D)));
+                     part_ml, counters, static_cast<uint16_t*>(out), H, Hkv, Smax, p.stride, 1.f / sqrtf(float(p.D)),
+                     k_scale, v_scale);
   return hipGetLastError();
 }
 
@@ -378,6 +399,7 @@ hipError_t launch_qknorm(int grid_x, int rows, int D, bool table, bool kv8, cons
   if (!k) return hipErrorInvalidValue;
   if (grid_x <= 0 || rows <= 0 || grid_x * qknorm_heads_per_wg(D) < a.H + 2 * a.Hkv) return hipErrorInvalidValue;
   if (table && (a.inv_freq == nullptr || reinterpret_cast<uintptr_t>(a.inv_freq) % 8)) return hipErrorInvalidValue;
+  if ((a.k_rscale != nullptr) != (a.v_rscale != nullptr) || (a.k_rscale && !kv8)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k, dim3(grid_x, rows), dim3(kQkNormWaves * 64), 0, s, a);
   return hipGetLastError();
 }
@@ -523,11 +545,17 @@ int p2pt_max_rows() { return kMaxM; }
 //      w_down as e4m3 bytes [N][K] (8-byte aligned), quantised after the fold and the interleave, followed by the
 //      fp32 row scales: lm_head's [vocab], then per layer wqkv's, wo's, w_gate_up's and w_down's, each [N] in the
 //      row order of its weight. Every other entry (embed, norms, inv_freq, bqkv, q_norm, k_norm) is as above.
-int p2pt_llama_decode_w(const LlamaDims* dp, const WeightPlan* wp, const void* const* w, void* k_cache, void* v_cache,
-                        const int64_t* tokens, const int* pos, const int* slots, int B, int emit_rows, void* ws,
-                        size_t ws_bytes, void* logits, int64_t* ids, void* stream) {
+//   FP8 cache with scales (p2pt_llama_decode_kv with dims.kv_fp8): kv_scales is a device buffer, fp32
+//      [4][n_layers][Hkv]: 1 / k_scale, 1 / v_scale, k_scale, v_scale, every entry finite and > 0 (the caller's
+//      check). A stored byte is e4m3(clamp(x * (1 / s))) of the head's scale and k_attn undoes it (KvScales).
+//      nullptr: scale 1, which is p2pt_llama_decode_w. Refused with a bf16 cache.
+int p2pt_llama_decode_kv(const LlamaDims* dp, const WeightPlan* wp, const float* kv_scales, const void* const* w,
+                         void* k_cache, void* v_cache, const int64_t* tokens, const int* pos, const int* slots, int B,
+                         int emit_rows, void* ws, size_t ws_bytes, void* logits, int64_t* ids, void* stream) {
   const LlamaDims d = *dp;
   if (!dims_ok(d) || !rows_ok(B) || (!slots && B > d.max_batch) || !weights_ok(*wp)) return int(hipErrorInvalidValue);
+  if (kv_scales && !d.kv_fp8) return int(hipErrorInvalidValue);
+  const KvScales KS{kv_scales};
   const int w8 = wp->w8;
   const Workspace W = carve(d, static_cast<uint8_t*>(ws));
   if (ws_bytes < W.bytes) return int(hipErrorInvalidValue);
@@ -549,7 +577,9 @@ int p2pt_llama_decode_w(const LlamaDims* dp, const WeightPlan* wp, const void* c
     const GemmPlan& qkv = L ? P.qkv : P.qkv_first;
     const GemmArgs qkv_in = gemm(W.resid, T.get(R_WQKV, L), T.scale(R_WQKV, L)) + norm(W.ss, qkv.ss_in, d.eps);
     const GemmArgs to_qkv =
-        d.qk_norm ? qkv_in + store(W.qkv) : qkv_in + rope(d, pos, slots, W.q, kc, vc, T.get(R_BQKV, L), inv_freq);
+        d.qk_norm ? qkv_in + store(W.qkv)
+                  : qkv_in + rope(d, pos, slots, W.q, kc, vc, T.get(R_BQKV, L), inv_freq,
+                                  KS.at(d, KvScales::K_RECIP, L), KS.at(d, KvScales::V_RECIP, L));
     const GemmArgs to_o = gemm(W.attn, T.get(R_WO, L), T.scale(R_WO, L)) + resid(W.resid, W.ss);
     const GemmArgs to_gate_up = gemm(W.resid, T.get(R_W_GATE_UP, L), T.scale(R_W_GATE_UP, L)) +
                                 norm(W.ss, P.gate_up.ss_in, d.eps) + store(W.h);
@@ -558,12 +588,13 @@ int p2pt_llama_decode_w(const LlamaDims* dp, const WeightPlan* wp, const void* c
     if (P.qk_norm_grid) {
       const QkNormArgs qn{W.qkv, static_cast<const uint16_t*>(T.get(R_Q_NORM, L)),
                           static_cast<const uint16_t*>(T.get(R_K_NORM, L)), pos, slots, d.max_batch, W.q, kc, vc, d.H,
-                          d.Hkv, d.max_seq, d.eps, log2f(d.theta), static_cast<const float*>(inv_freq)};
+                          d.Hkv, d.max_seq, d.eps, log2f(d.theta), static_cast<const float*>(inv_freq),
+                          KS.at(d, KvScales::K_RECIP, L), KS.at(d, KvScales::V_RECIP, L)};
       if (failed(launch_qknorm(P.qk_norm_grid, B, d.D, P.qk_norm_table != 0, KV.qk_norm_kv8 != 0, qn, s)))
         return int(e);
     }
     if (failed(launch_attn(P.attn, KV.attn_kv8, W.q, kc, vc, pos, slots, d.max_batch, W.part_o, W.part_ml, W.counters, W.attn, d.H,
-                           d.Hkv, d.max_seq, s)))
+                           d.Hkv, d.max_seq, s, KS.at(d, KvScales::K, L), KS.at(d, KvScales::V, L))))
       return int(e);
     if (failed(launch(P.o, to_o, s, w8))) return int(e);
     if (failed(launch(P.gate_up, to_gate_up, s, w8))) return int(e);
@@ -575,6 +606,12 @@ int p2pt_llama_decode_w(const LlamaDims* dp, const WeightPlan* wp, const void* c
   if (failed(launch(P.lm_head, to_logits, s, w8))) return int(e);
   hipLaunchKernelGGL(k_argmax_merge, dim3(P.emit_rows), dim3(256), 0, s, W.am_val, W.am_idx, P.am_parts, ids);
   return int(hipGetLastError());
+}
+int p2pt_llama_decode_w(const LlamaDims* dp, const WeightPlan* wp, const void* const* w, void* k_cache, void* v_cache,
+                        const int64_t* tokens, const int* pos, const int* slots, int B, int emit_rows, void* ws,
+                        size_t ws_bytes, void* logits, int64_t* ids, void* stream) {
+  return p2pt_llama_decode_kv(dp, wp, nullptr, w, k_cache, v_cache, tokens, pos, slots, B, emit_rows, ws, ws_bytes,
+                              logits, ids, stream);
 }
 int p2pt_llama_decode(const LlamaDims* dp, const void* const* w, void* k_cache, void* v_cache, const int64_t* tokens,
                       const int* pos, const int* slots, int B, int emit_rows, void* ws, size_t ws_bytes, void* logits,
@@ -607,7 +644,7 @@ int p2pt_qk_norm_rope_cache(const void* qkv, const int* pos, const int* slots, c
   const QkNormArgs a{static_cast<const uint16_t*>(qkv), static_cast<const uint16_t*>(q_weight),
                      static_cast<const uint16_t*>(k_weight), pos, slots, nslots, static_cast<uint16_t*>(q),
                      static_cast<uint16_t*>(k_cache), static_cast<uint16_t*>(v_cache), H, Hkv, Smax, eps, log2f(theta),
-                     inv_freq};
+                     inv_freq, nullptr, nullptr};
   const int per_wg = qknorm_heads_per_wg(D);
   return int(launch_qknorm((H + 2 * Hkv + per_wg - 1) / per_wg, B, D, inv_freq != nullptr, false, a,
                            static_cast<hipStream_t>(stream)));

@@ -78,7 +78,7 @@ typedef float frag4 __attribute__((ext_vector_type(4)));
 // memory (llama3 / linear RoPE scaling: the host computes the table once per model). Variants of their own for
 // the same reason: models with default RoPE keep the inline exp2f and launch exactly what they did.
 // EPI_ROPE_KV8, EPI_ROPE_BIAS_KV8, EPI_ROPE_TAB_KV8, EPI_ROPE_BIAS_TAB_KV8: the four RoPE epilogues for an FP8
-// (OCP e4m3fn, scale 1) KV cache: q is written as before, the K and V rows as one byte per element, rounded once
+// (OCP e4m3fn; scale 1, or per-head scales: GemmArgs::k_rscale) KV cache: q is written as before, the K and V rows as one byte per element, rounded once
 // from the epilogue's fp32 value (f32_to_e4m3x2). Variants of their own, kEpiKv8 above their bf16 counterparts, so
 // that a bf16 cache launches exactly the kernels it did.
 constexpr int kEpiKv8 = 8;
@@ -148,6 +148,10 @@ struct GemmArgs {
   // FP8 weights (k_skinny<.., W8 = 1>): w holds N * K e4m3 bytes and wscale the fp32 scale of each output row,
   // [N] in the row order of w (interleaved like its rows). Not read by the bf16 kernels.
   const float* wscale;
+  // FP8 cache with scales (the _KV8 epilogues): fp32 [Hkv] each, the reciprocals 1 / k_scale and 1 / v_scale of this
+  // layer's KV heads, which multiply the value ahead of its one rounding. Both nullptr: scale 1. Not read otherwise.
+  const float* k_rscale;
+  const float* v_rscale;
 };
 
 // log2 of the output columns per 16-lane subtile: 16, 8 or 4 for 1, 2 or 4 K parts.
@@ -398,6 +402,15 @@ __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
     }
   }
 
+  // _KV8 with scales: the reciprocal scale of this workgroup's head, loaded ahead of the weight stream like bias
+  // and tab_freq. A tile's 16 columns lie in one head (D is a multiple of 16 and QKV has no K parts), so the head
+  // and the load are uniform: one scalar load per workgroup. q heads, and a model without scales, keep 1.
+  float kv_rs = 1.f;
+  if constexpr (epi_kv8(EPI)) {
+    const int kvh = tile_col<TN>(bx, 0, 0, cwl) / a.D - a.H;  // < 2 Hkv: every column of the grid is below N
+    if (wv == 0 && kvh >= 0 && a.k_rscale != nullptr) kv_rs = kvh < a.Hkv ? a.k_rscale[kvh] : a.v_rscale[kvh - a.Hkv];
+  }
+
   frag4 acc[TN];
 #pragma unroll
   for (int t = 0; t < TN; t++) acc[t] = frag4{0.f, 0.f, 0.f, 0.f};
@@ -546,14 +559,16 @@ __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
           const float x1 = second ? other : mine, x2 = second ? mine : other;
           val = second ? x2 * cs + x1 * sn : x1 * cs - x2 * sn;
         }
-        const float next = dpp<kDppXor2>(val);
+        // K and V: times the head's reciprocal scale (exactly val at scale 1), still ahead of the one rounding.
+        const float sval = val * kv_rs;
+        const float next = dpp<kDppXor2>(sval);
         if (head < a.H) {
           a.q_out[(size_t(m) * a.H + head) * a.D + d] = uint16_t(f2bf_bits(val));
         } else if (!(c & 2)) {
           const bool is_k = head < a.H + a.Hkv;
           uint8_t* row = reinterpret_cast<uint8_t*>(is_k ? a.kc : a.vc) +
                          ((size_t(sl) * a.Smax + p) * a.Hkv + (head - a.H - (is_k ? 0 : a.Hkv))) * a.D;
-          *reinterpret_cast<uint16_t*>(row + d) = f32_to_e4m3x2(val, next);
+          *reinterpret_cast<uint16_t*>(row + d) = f32_to_e4m3x2(sval, next);
         }
       } else if (head < a.H + a.Hkv) {
         float sn, cs;
@@ -680,6 +695,9 @@ struct QkNormArgs {
   int H, Hkv, Smax;
   float eps, log2_theta;
   const float* inv_freq;  // k_qknorm_rope<D, true>: [D / 2] RoPE frequencies, 8-byte aligned
+  // k_qknorm_rope<D, TAB, true> with scales: [Hkv] each, 1 / k_scale and 1 / v_scale (GemmArgs); both nullptr: scale 1.
+  const float* k_rscale;
+  const float* v_rscale;
 };
 
 constexpr int kQkNormWaves = 4;  // waves per workgroup of k_qknorm_rope
@@ -691,7 +709,8 @@ __host__ __device__ __forceinline__ int qknorm_heads_per_wg(int D) { return kQkN
 // of exp2f; 2j + 1 < D / 2 for every lane.
 // KV8: an FP8 (e4m3) cache. q is written as bf16 as before; k goes from the rotated fp32 value to e4m3 in one
 // rounding, v from the bf16 value read (exactly an fp32 value) likewise: two 2-byte stores per lane instead of two
-// 4-byte ones.
+// 4-byte ones. With scales, k and v are multiplied by their head's reciprocal scale ahead of that rounding (a lane
+// group's own head: one 4-byte load per lane, issued with the norm weights).
 template <int D, bool TAB = false, bool KV8 = false>
 __global__ __launch_bounds__(kQkNormWaves * 64) void k_qknorm_rope(QkNormArgs a) {
   constexpr int LPH = D / 4, half = D / 2;  // lanes per head
@@ -710,6 +729,10 @@ __global__ __launch_bounds__(kQkNormWaves * 64) void k_qknorm_rope(QkNormArgs a)
   const uint16_t* g = (is_q ? a.gq : a.gk) + 2 * j;
   const uint32_t glo = *reinterpret_cast<const uint32_t*>(g);
   const uint32_t ghi = *reinterpret_cast<const uint32_t*>(g + half);
+  float kv_rs = 1.f;
+  if constexpr (KV8) {
+    if (!is_q && a.k_rscale != nullptr) kv_rs = is_v ? a.v_rscale[hc - a.H - a.Hkv] : a.k_rscale[hc - a.H];
+  }
   float2 tab_freq = make_float2(0.f, 0.f);
   if constexpr (TAB) tab_freq = *reinterpret_cast<const float2*>(a.inv_freq + 2 * j);
   // Host validates; clamped anyway so a bad index can never write outside the cache.
@@ -746,8 +769,8 @@ __global__ __launch_bounds__(kQkNormWaves * 64) void k_qknorm_rope(QkNormArgs a)
   if constexpr (KV8) {
     if (!is_q) {
       uint8_t* dst8 = reinterpret_cast<uint8_t*>(is_v ? a.vc : a.kc) + (row + (hc - a.H - (is_v ? a.Hkv : 0))) * D;
-      *reinterpret_cast<uint16_t*>(dst8 + 2 * j) = f32_to_e4m3x2(o1[0], o1[1]);
-      *reinterpret_cast<uint16_t*>(dst8 + 2 * j + half) = f32_to_e4m3x2(o2[0], o2[1]);
+      *reinterpret_cast<uint16_t*>(dst8 + 2 * j) = f32_to_e4m3x2(o1[0] * kv_rs, o1[1] * kv_rs);
+      *reinterpret_cast<uint16_t*>(dst8 + 2 * j + half) = f32_to_e4m3x2(o2[0] * kv_rs, o2[1] * kv_rs);
       return;
     }
   }
@@ -798,17 +821,21 @@ __host__ __device__ __forceinline__ int attn_span(int len, unsigned slots) {
   return std::max(kAttnMinSpan, (span + kAttnPiece - 1) / kAttnPiece * kAttnPiece);
 }
 
-// KV8: an FP8 (e4m3, scale 1) cache. The same lane -> (token, 8-dim group) map and the same reductions; a lane
+// KV8: an FP8 (e4m3) cache. The same lane -> (token, 8-dim group) map and the same reductions; a lane
 // loads its 8 dims as 8 bytes instead of 16 and decodes them with v_cvt_pk_f32_fp8 (exact). For the scores the
 // decoded K is packed to bf16 pairs (exact too: 3 mantissa bits, and e4m3's exponents lie inside bf16's), so the
 // dot products are the bf16 kernel's v_dot2_f32_bf16 chain against the packed q, product and sum in fp32; P.V
 // takes the decoded V in fp32. The softmax and everything after the span loop are the bf16 kernel's code.
+// Scales (k_scale, v_scale: fp32 [Hkv] of this layer, both nullptr for scale 1; the bf16 kernels never read them):
+// the bytes hold x / s, and the KV head's two scalars undo that where it is free. K's joins the score scale
+// (scale * k_scale[kvh]), V's the final normalisation (v_scale[kvh] / L for 1.f / L) at the single-slot exit and in
+// the cross-slot merge, and nowhere else. At scale 1 both expressions are the unscaled ones bit for bit.
 template <int D, int G, bool KV8 = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1))) void k_attn(
     const uint16_t* __restrict__ q, const uint16_t* __restrict__ kc, const uint16_t* __restrict__ vc,
     const int* __restrict__ pos, const int* __restrict__ slot, int nslots, float* __restrict__ part_o,
     float* __restrict__ part_ml, unsigned* __restrict__ counters, uint16_t* __restrict__ out, int H, int Hkv, int Smax,
-    int nsplit, float scale) {
+    int nsplit, float scale, const float* __restrict__ k_scale, const float* __restrict__ v_scale) {
   constexpr int NWV = 8;
   constexpr int TOK = kAttnPiece;
   constexpr int DPL = D / kWave;  // merges: dims per lane
@@ -828,6 +855,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1))) void k
   const int sb = slot ? min(max(slot[b], 0), nslots - 1) : b;
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int dg = lane % LPR, ri = lane / LPR;
+  float vnum = 1.f;  // the numerator of the final normalisation
+  if constexpr (KV8) {
+    if (k_scale != nullptr) {
+      scale *= k_scale[kvh];
+      vnum = v_scale[kvh];
+    }
+  }
 
   const size_t tok_stride = size_t(Hkv) * D;
   const uint16_t* kbase = kc + size_t(sb) * Smax * tok_stride + size_t(kvh) * D + 8 * dg;
@@ -968,7 +1002,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1))) void k
     }
     const size_t hb = hb0 + g;
     if (nact == 1) {
-      const float inv = 1.f / L;
+      const float inv = KV8 ? vnum / L : 1.f / L;
 #pragma unroll
       for (int k = 0; k < DPL; k++) out[hb * D + lane + k * kWave] = uint16_t(f2bf_bits(o[k] * inv));
     } else {
@@ -1028,7 +1062,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1))) void k
         for (int k = 0; k < DPL; k++) o[k] += ww * pv[j][k];
       }
     }
-    const float inv = 1.f / L;
+    const float inv = KV8 ? vnum / L : 1.f / L;
 #pragma unroll
     for (int k = 0; k < DPL; k++) out[hb * D + lane + k * kWave] = uint16_t(f2bf_bits(o[k] * inv));
   }

@@ -14,7 +14,13 @@ is 448 (0x7e); subnormals are the multiples of 2^-9 below 2^-6.
               values), for tests that ask which inputs a bound decides.
 ``half_ulp``  the issue's hu: half the e4m3 spacing at a magnitude.
 
-Everything is integer arithmetic on the fp32 bit pattern: no library cast
+With per-head scales (``models/kv_scales.py``) the byte of head h is ``encode(x * fp32(1 / s[h]))``
+(``encode_scaled``: the reciprocal once, the product rounded to fp32 as the kernel's multiply rounds it, then the one
+rounding to e4m3) and the value it stands for is ``decode(byte) * s[h]`` (``decode_scaled``). ``attend`` is the
+scaled read as ``k_attn<D, G, true>`` does it, in fp32: the bytes themselves enter the dot products, K's scale joins
+the score scale and V's the final normalisation, at the single-slot exit or in the cross-slot merge.
+
+Everything in ``encode`` is integer arithmetic on the fp32 bit pattern: no library cast
 decides a rounding here.
 """
 from __future__ import annotations
@@ -96,3 +102,52 @@ def boundary_distance(x: np.ndarray) -> np.ndarray:
     b = boundaries()
     i = np.clip(np.searchsorted(b, a), 1, len(b) - 1)
     return np.minimum(np.abs(a - b[i - 1]), np.abs(a - b[i]))
+
+
+# ---------------------------------------------------------------- per-head scales
+def recip(s) -> np.ndarray:
+    """fp32(1 / s): what the host computes once and the writers multiply by."""
+    return (np.float32(1.0) / np.asarray(s, dtype=np.float32)).astype(np.float32)
+
+
+def encode_scaled(x: np.ndarray, s) -> np.ndarray:
+    """Rows ``x`` [..., Hkv, D] (fp32) to bytes under the head scales ``s`` [Hkv]: encode(x * fp32(1 / s))."""
+    x = np.asarray(x, dtype=np.float32)
+    return encode((x * recip(s)[..., :, None]).astype(np.float32))
+
+
+def decode_scaled(b: np.ndarray, s) -> np.ndarray:
+    """Bytes [..., Hkv, D] to the values they stand for under the head scales ``s`` [Hkv] (fp64)."""
+    return decode(b).astype(np.float64) * np.asarray(s, dtype=np.float64)[..., :, None]
+
+
+def attend(q: np.ndarray, kb: np.ndarray, vb: np.ndarray, k_scale: float, v_scale: float, slots: int = 1,
+           span: int = 64) -> np.ndarray:
+    """One KV head's attention as ``k_attn<D, G, true>`` computes it, in fp32: ``q`` [G, D] (bf16 values), ``kb`` /
+    ``vb`` [T, D] bytes of that head, its two scales. The tokens are cut into ``slots`` spans of ``span``; each
+    span's running maximum, sum and unnormalised output are kept, and with one span the exit is o * (v_scale / L),
+    with several the merge rescales the partials and ends with the same expression. Returns fp32 [G, D]."""
+    f = np.float32
+    D = q.shape[1]
+    sc = f(f(1.0) / np.sqrt(f(D))) * f(k_scale)  # K's scale joins the score scale, once
+    k, v = decode(kb).astype(f), decode(vb).astype(f)
+    T = k.shape[0]
+    nact = max(1, min(slots, -(-T // span)))
+    parts = []
+    for i in range(nact):
+        lo, hi = i * span, T if i == nact - 1 else min(T, (i + 1) * span)
+        s = (q.astype(f) @ k[lo:hi].T).astype(f) * sc
+        m = s.max(1, keepdims=True)
+        p = np.exp(s - m).astype(f)
+        parts.append((m[:, 0], p.sum(1, dtype=f), (p @ v[lo:hi]).astype(f)))
+    if nact == 1:  # the single-slot exit
+        m, l, o = parts[0]
+        return (o * (f(v_scale) / l)[:, None]).astype(f)
+    M = np.max([m for m, _, _ in parts], axis=0)
+    L = np.zeros_like(M)
+    o = np.zeros_like(parts[0][2])
+    for m, l, po in parts:  # the cross-slot merge
+        w = np.exp(m - M).astype(f)
+        L += l * w
+        o += w[:, None] * po
+    return (o * (f(v_scale) / L)[:, None]).astype(f)

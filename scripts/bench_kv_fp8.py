@@ -6,6 +6,11 @@ Two models share one set of random weights and differ in ``kv_dtype`` alone. For
 timed in alternating windows (bf16, fp8, bf16, ...), ``--rounds`` windows of ``--steps`` replays each, every
 window ending in a device synchronise; the result line carries each window's ms per step and the medians. Caches
 are filled with N(0, 1) values up to ctx. ``llama1b`` is Llama-3.2-1B's shape with random weights.
+
+``--scales`` adds a third model to the alternation, "fp8+scales": the FP8 cache with per-layer, per-KV-head scales
+(powers of two between 1/4 and 4, all different within a layer: the kernels take the same path whatever the values).
+``--no-bf16`` leaves the bf16 model out. The parent commit's own FP8 path is timed by running the parent's copy of
+this script in a process of its own, alternating with this one (profiles/kv_scale.json says how).
 """
 from __future__ import annotations
 
@@ -46,6 +51,8 @@ def main():
     ap.add_argument("--batch", type=int, nargs="+", default=[1, 16])
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--scales", action="store_true", help="also time the FP8 cache with per-head scales")
+    ap.add_argument("--no-bf16", action="store_true", help="leave the bf16-cache model out of the alternation")
     ap.add_argument("--out", default=None, help="append the JSON result lines to this file as well")
     a = ap.parse_args()
     max_batch = max(a.batch)
@@ -54,6 +61,14 @@ def main():
     w = dict(embed=models["bf16"].embed, final_norm=models["bf16"].final_norm, lm_head=models["bf16"].lm_head,
              layers=models["bf16"].layers)
     models["fp8"] = TinyLlama.from_weights(cfg, w, device="cuda", max_batch=max_batch, kv_dtype="fp8")
+    if a.scales:
+        from p2p_llm_tunnel_amd.models.kv_scales import KvScales
+        exps = torch.arange(cfg.n_layers * cfg.n_kv_heads).view(cfg.n_layers, cfg.n_kv_heads) % 5 - 2
+        models["fp8+scales"] = TinyLlama.from_weights(cfg, w, device="cuda", max_batch=max_batch, kv_dtype="fp8",
+                                                      kv_scales=KvScales(torch.exp2(exps.float()),
+                                                                         torch.exp2(-exps.float())))
+    if a.no_bf16:
+        del models["bf16"]
     for m in models.values():
         fill(m.k_cache)
         fill(m.v_cache)
@@ -62,7 +77,7 @@ def main():
     for ctx in a.ctx:
         for B in a.batch:
             tok = torch.randint(0, cfg.vocab, (B,), device="cuda")
-            ms = {"bf16": [], "fp8": []}
+            ms = {name: [] for name in models}
             q = ctx
 
             def window(m, q0, n):
