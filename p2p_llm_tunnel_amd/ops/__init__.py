@@ -66,6 +66,50 @@ class WeightPlan(ctypes.Structure):
     _fields_ = [("w8", _INT)]
 
 
+def _signatures() -> dict:
+    """Every symbol ``lib()`` binds -> its argtypes. The restype is ``c_int`` unless ``_RESTYPES`` names another."""
+    vp, i, f, sz, ptr = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.POINTER
+    dims, wp, ip, szp = ptr(LlamaDims), ptr(WeightPlan), ptr(i), ptr(sz)
+    return {
+        "p2pt_rmsnorm": [vp, vp, vp, vp, vp, i, i, f, vp],
+        "p2pt_silu_mul": [vp, vp, i, i, vp],
+        "p2pt_rope_qkv_cache": [vp, vp, vp, vp, vp, i, i, i, i, i, f, vp, vp],
+        "p2pt_qk_norm_rope_cache": [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, f, f, vp, vp],
+        "p2pt_decode_attention": [vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, f, vp],
+        "p2pt_argmax": [vp, vp, i, i, vp],
+        "p2pt_skinny_gemm": [vp, vp, vp, i, i, i, vp],
+        "p2pt_sample": [vp, vp, vp, i, i, i, vp],
+        "p2pt_logprobs": [vp, vp, vp, vp, vp, i, i, vp],
+        "p2pt_kv_copy": [vp, vp, i, i, i, i, i, ip, vp],
+        "p2pt_max_kv_copy_jobs": [],
+        "p2pt_embed_pool": [vp, i, i, vp, vp, i, vp, i, f, i, ip, vp],
+        "p2pt_max_embed_jobs": [],
+        "p2pt_penalize": [vp, vp, vp, vp, vp, vp, vp, i, vp, i, vp, vp, vp, i, i, vp],
+        "p2pt_penalty_reset": [vp, i, i, i, vp, i, vp, vp, vp, vp, i, vp],
+        "p2pt_max_logit_bias": [],
+        "p2pt_guide": [vp, vp, vp, vp, vp, vp, vp, vp, i, vp, i, i, i, vp],
+        "p2pt_guide_reset": [vp, vp, i, i, i, i, vp],
+        "p2pt_llama_ws_bytes": [dims],
+        "p2pt_llama_ws_layout": [dims, szp, szp, i],
+        "p2pt_llama_decode": [dims, ptr(vp), vp, vp, vp, vp, vp, i, i, vp, sz, vp, vp, vp],
+        "p2pt_llama_plan": [dims, i, i, ptr(StepPlan)],
+        "p2pt_llama_kv_plan": [dims, ptr(KvPlan)],
+        "p2pt_llama_plan_kernels": [dims, i, i],
+        "p2pt_llama_weight_plan": [dims, i, wp],
+        "p2pt_llama_plan_kernels_w": [dims, i, i, wp],
+        "p2pt_llama_decode_w": [dims, wp, ptr(vp), vp, vp, vp, vp, vp, i, i, vp, sz, vp, vp, vp],
+        "p2pt_llama_decode_kv": [dims, wp, vp, ptr(vp), vp, vp, vp, vp, vp, i, i, vp, sz, vp, vp, vp],
+        "p2pt_llama_weight_layout": [dims, wp, ip, ip, i],
+        "p2pt_attn_span": [i, i],
+        "p2pt_max_rows": [],
+        "p2pt_skinny_bench": [vp, vp, vp, i, i, i, i, i, i, vp],  # microbenchmark hooks (scripts/bench_skinny.py)
+        "p2pt_attn_bench": [vp, vp, vp, vp, i, i, i, i, i, vp, vp, vp, vp, i, vp],
+    }
+
+
+_RESTYPES = {"p2pt_llama_ws_bytes": ctypes.c_size_t}
+
+
 def lib() -> ctypes.CDLL:
     global _LIB
     if _LIB is None:
@@ -75,57 +119,9 @@ def lib() -> ctypes.CDLL:
             from . import build as _b
             _b.build()
         _LIB = ctypes.CDLL(path)
-        vp, i, f = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-        _LIB.p2pt_rmsnorm.argtypes = [vp, vp, vp, vp, vp, i, i, f, vp]
-        _LIB.p2pt_silu_mul.argtypes = [vp, vp, i, i, vp]
-        _LIB.p2pt_rope_qkv_cache.argtypes = [vp, vp, vp, vp, vp, i, i, i, i, i, f, vp, vp]
-        _LIB.p2pt_qk_norm_rope_cache.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, f, f, vp, vp]
-        _LIB.p2pt_decode_attention.argtypes = [vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, i, f, vp]
-        _LIB.p2pt_argmax.argtypes = [vp, vp, i, i, vp]
-        _LIB.p2pt_skinny_gemm.argtypes = [vp, vp, vp, i, i, i, vp]
-        _LIB.p2pt_sample.argtypes = [vp, vp, vp, i, i, i, vp]
-        _LIB.p2pt_logprobs.argtypes = [vp, vp, vp, vp, vp, i, i, vp]
-        _LIB.p2pt_kv_copy.argtypes = [vp, vp, i, i, i, i, i, ctypes.POINTER(ctypes.c_int), vp]
-        _LIB.p2pt_max_kv_copy_jobs.argtypes = []
-        _LIB.p2pt_embed_pool.argtypes = [vp, i, i, vp, vp, i, vp, i, f, i, ctypes.POINTER(ctypes.c_int), vp]
-        _LIB.p2pt_max_embed_jobs.argtypes = []
-        _LIB.p2pt_penalize.argtypes = [vp, vp, vp, vp, vp, vp, vp, i, vp, i, vp, vp, vp, i, i, vp]
-        _LIB.p2pt_penalty_reset.argtypes = [vp, i, i, i, vp, i, vp, vp, vp, vp, i, vp]
-        _LIB.p2pt_max_logit_bias.argtypes = []
-        _LIB.p2pt_guide.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, i, vp, i, i, i, vp]
-        _LIB.p2pt_guide_reset.argtypes = [vp, vp, i, i, i, i, vp]
-        _LIB.p2pt_llama_ws_bytes.argtypes = [ctypes.POINTER(LlamaDims)]
-        _LIB.p2pt_llama_ws_bytes.restype = ctypes.c_size_t
-        szp = ctypes.POINTER(ctypes.c_size_t)
-        _LIB.p2pt_llama_ws_layout.argtypes = [ctypes.POINTER(LlamaDims), szp, szp, i]
-        _LIB.p2pt_llama_ws_layout.restype = ctypes.c_int
-        _LIB.p2pt_llama_decode.argtypes = [ctypes.POINTER(LlamaDims), ctypes.POINTER(vp), vp, vp, vp, vp, vp, i, i,
-                                           vp, ctypes.c_size_t, vp, vp, vp]
-        _LIB.p2pt_llama_plan.argtypes = [ctypes.POINTER(LlamaDims), i, i, ctypes.POINTER(StepPlan)]
-        _LIB.p2pt_llama_kv_plan.argtypes = [ctypes.POINTER(LlamaDims), ctypes.POINTER(KvPlan)]
-        _LIB.p2pt_llama_plan_kernels.argtypes = [ctypes.POINTER(LlamaDims), i, i]
-        _LIB.p2pt_llama_weight_plan.argtypes = [ctypes.POINTER(LlamaDims), i, ctypes.POINTER(WeightPlan)]
-        _LIB.p2pt_llama_plan_kernels_w.argtypes = [ctypes.POINTER(LlamaDims), i, i, ctypes.POINTER(WeightPlan)]
-        _LIB.p2pt_llama_decode_w.argtypes = [ctypes.POINTER(LlamaDims), ctypes.POINTER(WeightPlan), ctypes.POINTER(vp),
-                                             vp, vp, vp, vp, vp, i, i, vp, ctypes.c_size_t, vp, vp, vp]
-        _LIB.p2pt_llama_decode_kv.argtypes = [ctypes.POINTER(LlamaDims), ctypes.POINTER(WeightPlan), vp,
-                                              ctypes.POINTER(vp), vp, vp, vp, vp, vp, i, i, vp, ctypes.c_size_t, vp,
-                                              vp, vp]
-        ip = ctypes.POINTER(ctypes.c_int)
-        _LIB.p2pt_llama_weight_layout.argtypes = [ctypes.POINTER(LlamaDims), ctypes.POINTER(WeightPlan), ip, ip, i]
-        _LIB.p2pt_attn_span.argtypes = [i, i]
-        _LIB.p2pt_max_rows.argtypes = []
-        # microbenchmark hooks (scripts/bench_skinny.py)
-        _LIB.p2pt_skinny_bench.argtypes = [vp, vp, vp, i, i, i, i, i, i, vp]
-        _LIB.p2pt_attn_bench.argtypes = [vp, vp, vp, vp, i, i, i, i, i, vp, vp, vp, vp, i, vp]
-        for fn in ("p2pt_rmsnorm", "p2pt_silu_mul", "p2pt_rope_qkv_cache", "p2pt_decode_attention", "p2pt_argmax",
-                   "p2pt_skinny_gemm", "p2pt_llama_decode", "p2pt_sample", "p2pt_logprobs", "p2pt_llama_plan", "p2pt_attn_span",
-                   "p2pt_llama_kv_plan", "p2pt_llama_plan_kernels", "p2pt_llama_weight_plan",
-                   "p2pt_llama_plan_kernels_w", "p2pt_llama_decode_w", "p2pt_llama_decode_kv", "p2pt_llama_weight_layout",
-                   "p2pt_max_rows", "p2pt_skinny_bench", "p2pt_attn_bench", "p2pt_kv_copy", "p2pt_max_kv_copy_jobs",
-                   "p2pt_embed_pool", "p2pt_max_embed_jobs", "p2pt_qk_norm_rope_cache", "p2pt_penalize",
-                   "p2pt_penalty_reset", "p2pt_max_logit_bias", "p2pt_guide", "p2pt_guide_reset"):
-            getattr(_LIB, fn).restype = ctypes.c_int
+        for name, argtypes in _signatures().items():
+            fn = getattr(_LIB, name)
+            fn.argtypes, fn.restype = argtypes, _RESTYPES.get(name, ctypes.c_int)
         if _LIB.p2pt_max_rows() != MAX_ROWS:
             raise RuntimeError(f"MAX_ROWS = {MAX_ROWS}, but {path} was built for {_LIB.p2pt_max_rows()} rows")
         if _LIB.p2pt_max_kv_copy_jobs() != MAX_KV_COPY_JOBS:
@@ -270,6 +266,11 @@ def _check(t: torch.Tensor, dtype, name: str, device=None):
         raise ValueError(f"{name} must be contiguous")
 
 
+def _int_in(v, lo, hi) -> bool:
+    """``v`` is an int, no bool, with lo <= v < hi."""
+    return isinstance(v, int) and not isinstance(v, bool) and lo <= v < hi
+
+
 def _ok(rc: int, what: str):
     if rc != 0:
         raise RuntimeError(f"{what}: HIP launch failed (hipError {rc})")
@@ -390,7 +391,7 @@ def qk_norm_rope_cache(qkv: torch.Tensor, pos: torch.Tensor, k_cache: torch.Tens
     _check(q_weight, torch.bfloat16, "q_weight", dev)
     _check(k_weight, torch.bfloat16, "k_weight", dev)
     for name, v in (("n_heads", n_heads), ("n_kv_heads", n_kv_heads), ("head_dim", head_dim)):
-        if isinstance(v, bool) or not isinstance(v, int) or v <= 0:
+        if not _int_in(v, 1, math.inf):
             raise ValueError(f"{name} must be a positive int, got {v!r}")
     if head_dim not in (64, 128):
         raise ValueError("head_dim must be 64 or 128")
@@ -457,7 +458,7 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
         raise ValueError("n_heads / n_kv_heads must be an integer <= 8")
     if lens.shape != (B,):
         raise ValueError("lens must be [B]")
-    if isinstance(chunk, bool) or not isinstance(chunk, int) or chunk <= 0:
+    if not _int_in(chunk, 1, math.inf):
         raise ValueError(f"chunk must be a positive int, got {chunk!r}")
     if max_len is None:
         max_len = int(lens.max().item())
@@ -554,6 +555,28 @@ def _penalty_tables(state, bias_n, bias_ids, bias_val):
     return n_slots, V
 
 
+def _check_rows(name: str, in_place: bool, x, work, ids, tok, dec, slot) -> None:
+    """The row arguments ``penalize_`` and ``guide_`` share, against their checked first argument ``x`` (bf16
+    [B, V], called ``name``): ``work`` bf16 of x's shape, apart from x (``in_place``: or x itself), both 16-byte
+    aligned when V % 8 == 0; ``ids`` and ``tok`` int64 [B]; ``dec`` and ``slot`` int64 [>= B]."""
+    dev, (B, V) = x.device, x.shape
+    _check(work, torch.bfloat16, "work", dev)
+    for n, t in (("ids", ids), ("tok", tok), ("dec", dec), ("slot", slot)):
+        _check(t, torch.int64, n, dev)
+    if work.shape != x.shape:
+        raise ValueError(f"work must be {tuple(x.shape)}, got {tuple(work.shape)}")
+    lo, hi = x.data_ptr(), x.data_ptr() + x.numel() * 2
+    if not (in_place and work.data_ptr() == lo) and work.data_ptr() < hi and lo < work.data_ptr() + work.numel() * 2:
+        raise ValueError(f"work must be {name} itself or must not overlap it" if in_place else
+                         f"work must not overlap {name} (the raw {name} are never written)")
+    if ids.shape != (B,) or tok.shape != (B,):
+        raise ValueError("ids and tok must be [B]")
+    if dec.dim() != 1 or slot.dim() != 1 or dec.shape[0] < B or slot.shape[0] < B:
+        raise ValueError("dec and slot need an entry per row")
+    if V % 8 == 0 and (x.data_ptr() % 16 or work.data_ptr() % 16):
+        raise ValueError(f"{name} and work must be 16-byte aligned")
+
+
 PENALTY_ON = 1  # flags word of a ``penalize_`` params column: bit 0 = the row is on
 
 
@@ -585,28 +608,16 @@ def penalize_(logits: torch.Tensor, work: torch.Tensor, ids: torch.Tensor, tok: 
     winner). Returns ``work``."""
     _check(logits, torch.bfloat16, "logits")
     dev = logits.device
-    _check(work, torch.bfloat16, "work", dev)
-    for name, t in (("ids", ids), ("tok", tok), ("dec", dec), ("slot", slot), ("params", params)):
-        _check(t, torch.int64, name, dev)
+    _check(params, torch.int64, "params", dev)
     n_slots, V = _penalty_tables(state, bias_n, bias_ids, bias_val)
     if state.device != dev:
         raise ValueError(f"state on {state.device}, expected {dev}")
     if logits.dim() != 2 or logits.shape[0] < 1 or logits.shape[1] != V:
         raise ValueError(f"logits must be [B >= 1, {V}] (state's vocabulary), got {tuple(logits.shape)}")
     B = logits.shape[0]
-    if work.shape != logits.shape:
-        raise ValueError(f"work must be {tuple(logits.shape)}, got {tuple(work.shape)}")
-    lo, hi = logits.data_ptr(), logits.data_ptr() + logits.numel() * 2
-    if work.data_ptr() < hi and lo < work.data_ptr() + work.numel() * 2:
-        raise ValueError("work must not overlap logits (the raw logits are never written)")
-    if ids.shape != (B,) or tok.shape != (B,):
-        raise ValueError("ids and tok must be [B]")
-    if dec.dim() != 1 or slot.dim() != 1 or dec.shape[0] < B or slot.shape[0] < B:
-        raise ValueError("dec and slot need an entry per row")
     if params.dim() != 2 or params.shape[0] != 4 or params.shape[1] < B:
         raise ValueError("params must be [4, >= B]")
-    if V % 8 == 0 and (logits.data_ptr() % 16 or work.data_ptr() % 16):
-        raise ValueError("logits and work must be 16-byte aligned")
+    _check_rows("logits", False, logits, work, ids, tok, dec, slot)
     _ok(lib().p2pt_penalize(_p(logits), _p(work), _p(ids), _p(tok), _p(dec), _p(slot), _p(params), params.shape[1],
                             _p(state), n_slots, _p(bias_n), _p(bias_ids), _p(bias_val), B, V, _stream(logits)),
         "penalize")
@@ -625,7 +636,7 @@ def penalty_reset_(state: torch.Tensor, slot: int, prompt_ids: torch.Tensor, bia
     slots untouched. Never captured."""
     n_slots, V = _penalty_tables(state, bias_n, bias_ids, bias_val)
     dev = state.device
-    if isinstance(slot, bool) or not isinstance(slot, int) or not 0 <= slot < n_slots:
+    if not _int_in(slot, 0, n_slots):
         raise ValueError(f"slot must be an int in [0, {n_slots}), got {slot!r}")
     _check(prompt_ids, torch.int32, "prompt_ids", dev)
     if prompt_ids.dim() != 1 or prompt_ids.shape[0] < 1:
@@ -677,27 +688,13 @@ def guide_(x: torch.Tensor, work: torch.Tensor, ids: torch.Tensor, tok: torch.Te
     id on ties, NaN never wins, 0 without a winner). Rows that are on must
     belong to different slots. Returns ``work``."""
     _check(x, torch.bfloat16, "x")
-    dev = x.device
-    _check(work, torch.bfloat16, "work", dev)
-    for name, t in (("ids", ids), ("tok", tok), ("dec", dec), ("slot", slot)):
-        _check(t, torch.int64, name, dev)
     n_slots, n_states, V = _guide_tables(base, cur, arena)
-    if arena.device != dev:
-        raise ValueError(f"arena on {arena.device}, expected {dev}")
+    if arena.device != x.device:
+        raise ValueError(f"arena on {arena.device}, expected {x.device}")
     if x.dim() != 2 or x.shape[0] < 1 or x.shape[1] != V:
         raise ValueError(f"x must be [B >= 1, {V}] (the arena's vocabulary), got {tuple(x.shape)}")
     B = x.shape[0]
-    if work.shape != x.shape:
-        raise ValueError(f"work must be {tuple(x.shape)}, got {tuple(work.shape)}")
-    lo, hi = x.data_ptr(), x.data_ptr() + x.numel() * 2
-    if work.data_ptr() != lo and work.data_ptr() < hi and lo < work.data_ptr() + work.numel() * 2:
-        raise ValueError("work must be x itself or must not overlap it")
-    if ids.shape != (B,) or tok.shape != (B,):
-        raise ValueError("ids and tok must be [B]")
-    if dec.dim() != 1 or slot.dim() != 1 or dec.shape[0] < B or slot.shape[0] < B:
-        raise ValueError("dec and slot need an entry per row")
-    if V % 8 == 0 and (x.data_ptr() % 16 or work.data_ptr() % 16):
-        raise ValueError("x and work must be 16-byte aligned")
+    _check_rows("x", True, x, work, ids, tok, dec, slot)
     _ok(lib().p2pt_guide(_p(x), _p(work), _p(ids), _p(tok), _p(dec), _p(slot), _p(base), _p(cur), n_slots, _p(arena),
                          n_states, B, V, _stream(x)), "guide")
     return work
@@ -711,7 +708,7 @@ def guide_reset_(base: torch.Tensor, cur: torch.Tensor, arena: torch.Tensor, slo
     captured."""
     n_slots, n_states, _ = _guide_tables(base, cur, arena)
     for name, v, lo, hi in (("slot", slot, 0, n_slots), ("first", first, -1, n_states)):
-        if isinstance(v, bool) or not isinstance(v, int) or not lo <= v < hi:
+        if not _int_in(v, lo, hi):
             raise ValueError(f"{name} must be an int in [{lo}, {hi}), got {v!r}")
     _ok(lib().p2pt_guide_reset(_p(base), _p(cur), n_slots, slot, first, n_states, _stream(base)), "guide_reset")
 

@@ -15,7 +15,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRCS = [os.path.join(HERE, f) for f in ("kernels.hip", "decode_fused.hip", "sample.hip", "logprobs.hip",
                                           "kv_copy.hip", "embed_pool.hip", "penalty.hip", "guide.hip")]
-DEPS = SRCS + [os.path.join(HERE, h) for h in ("bf16_common.h", "decode_fused_kernels.h")]
+DEPS = SRCS + [os.path.join(HERE, h) for h in ("bf16_common.h", "row_common.h", "decode_fused_kernels.h")]
 OUT = os.path.join(HERE, "_hip_ops.so")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950").split(";")[0]
 

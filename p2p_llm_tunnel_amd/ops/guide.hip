@@ -22,17 +22,18 @@
 //       2. mask: work[v] = arena[base + cur][v] >= 0 ? x[v] : -inf, the kept
 //          elements bit for bit. x may be work itself (the penalty kernel's
 //          output, masked in place): each lane stores only elements it loaded.
-//       3. ids[r] = argmax of the stored row by k_argmax_merge's rules (lowest id
-//          on ties, NaN never wins, a row with nothing above -inf gives 0), kept
-//          in registers while storing. The sampler reads work, so greedy decoding
-//          and sampling see the same numbers.
+//       3. ids[r] = argmax of the stored row by row_common.h's rules (take_bits,
+//          block_argmax; k_argmax_merge's too: lowest id on ties, NaN never wins,
+//          a row with nothing above -inf gives 0), kept in registers while
+//          storing. The sampler reads work, so greedy decoding and sampling see
+//          the same numbers.
 //     16-byte loads of x with ONE 16-byte load of the table row per 8 elements
 //     when V % 8 == 0 (every row of x, work and the arena then starts on a
 //     16-byte boundary); any other V runs element by element.
 //
 //   p2pt_guide_reset   admission of a request into a slot, never captured: one
 //     lane stores base[slot] (-1 switches the slot off) and cur[slot] = 0.
-#include "bf16_common.h"
+#include "row_common.h"
 
 namespace {
 
@@ -41,28 +42,19 @@ using namespace p2pt_gpu;
 constexpr int kThreads = 1024, kWaves = kThreads / 64;
 constexpr uint32_t kNegInf = 0xFF80u;  // bf16 -inf
 
-__device__ __forceinline__ void take(float& b, int& bi, uint32_t bits, int i) {
-  const float v = bf2f(uint16_t(bits));
-  if (v > b) {  // ascending i within a lane: the first of equals stays
-    b = v;
-    bi = i;
-  }
-}
-
 // 8 elements from loaded vectors: mask, store, keep the lane's argmax. A table entry is allowed when its sign
 // bit is clear.
 __device__ __forceinline__ void mask_chunk(int c, const uint4& lv, const uint4& tv, uint4* w4, float& b, int& bi) {
-  const uint32_t raw[8] = {lv.x & 0xffffu, lv.x >> 16, lv.y & 0xffffu, lv.y >> 16,
-                           lv.z & 0xffffu, lv.z >> 16, lv.w & 0xffffu, lv.w >> 16};
+  uint32_t raw[8], o[8];
+  bits8(lv, raw);
   const uint32_t neg[8] = {tv.x & 0x8000u, tv.x & 0x80000000u, tv.y & 0x8000u, tv.y & 0x80000000u,
                            tv.z & 0x8000u, tv.z & 0x80000000u, tv.w & 0x8000u, tv.w & 0x80000000u};
-  uint32_t o[8];
 #pragma unroll
   for (int j = 0; j < 8; j++) {
     o[j] = neg[j] ? kNegInf : raw[j];
-    take(b, bi, o[j], c * 8 + j);
+    take_bits(b, bi, o[j], c * 8 + j);
   }
-  w4[c] = make_uint4(o[0] | (o[1] << 16), o[2] | (o[3] << 16), o[4] | (o[5] << 16), o[6] | (o[7] << 16));
+  w4[c] = pack_bits8(o);
 }
 
 __global__ __launch_bounds__(kThreads) void k_guide(const uint16_t* x, uint16_t* work, int64_t* __restrict__ ids,
@@ -84,13 +76,7 @@ __global__ __launch_bounds__(kThreads) void k_guide(const uint16_t* x, uint16_t*
   }
   if (b0 < 0 || c < 0 || b0 >= arena_states || c >= arena_states - b0) {  // off: copy the row
     if (lr == wr) return;
-    if (vec) {
-      const uint4* l4 = reinterpret_cast<const uint4*>(lr);
-      uint4* w4 = reinterpret_cast<uint4*>(wr);
-      for (int i = threadIdx.x; i < nvec; i += kThreads) w4[i] = l4[i];
-    } else {
-      for (int i = threadIdx.x; i < V; i += kThreads) wr[i] = lr[i];
-    }
+    copy_row(lr, wr, V, kThreads);
     return;
   }
   const int64_t t64 = tok[row];
@@ -124,22 +110,14 @@ __global__ __launch_bounds__(kThreads) void k_guide(const uint16_t* x, uint16_t*
     for (int i = threadIdx.x; i < V; i += kThreads) {
       const uint32_t o = tr[i] < 0 ? kNegInf : uint32_t(lr[i]);
       wr[i] = uint16_t(o);
-      take(b, bi, o, i);
+      take_bits(b, bi, o, i);
     }
   }
 
   __shared__ float s_b[kWaves];
   __shared__ int s_i[kWaves];
-  wave_argmax(b, bi);
-  if ((threadIdx.x & 63) == 0) {
-    s_b[threadIdx.x >> 6] = b;
-    s_i[threadIdx.x >> 6] = bi;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < kWaves; w++) am_take(b, bi, s_b[w], s_i[w]);
-    ids[row] = bi == 0x7fffffff ? 0 : bi;  // no winner (all -inf / NaN): id 0, never out of range
-  }
+  block_argmax<kWaves>(b, bi, s_b, s_i);
+  if (threadIdx.x == 0) ids[row] = bi == 0x7fffffff ? 0 : bi;  // no winner (all -inf / NaN): id 0, never out of range
 }
 
 __global__ void k_guide_reset(int* __restrict__ base, int* __restrict__ cur, int first) {
@@ -148,8 +126,6 @@ __global__ void k_guide_reset(int* __restrict__ base, int* __restrict__ cur, int
     *cur = 0;
   }
 }
-
-bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
 

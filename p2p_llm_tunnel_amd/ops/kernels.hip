@@ -11,11 +11,12 @@
 //                          tiles staged in LDS once per workgroup and shared by
 //                          the group's query heads (one wave per head)
 //   p2pt_argmax            greedy sampling: per-row argmax over the vocabulary
+//                          (row_common.h's take_bits and block_argmax)
 //
 // All tensors are bf16 (raw uint16 storage) with fp32 accumulation. Waves are
 // 64 lanes; every block is a multiple of 64 threads. Launchers are extern "C"
 // (loaded with ctypes, no torch headers) and return the hipError_t of the launch.
-#include "bf16_common.h"
+#include "row_common.h"
 
 namespace {
 
@@ -277,40 +278,18 @@ __global__ __launch_bounds__(256) void k_argmax(const uint16_t* __restrict__ log
   const int vv = V / 8;
   const uint4* x4 = reinterpret_cast<const uint4*>(x);
   for (int i = threadIdx.x; i < vv; i += 256) {
-    float f[8];
-    unpack8(x4[i], f);
+    uint32_t h[8];
+    bits8(x4[i], h);
 #pragma unroll
-    for (int k = 0; k < 8; k++)
-      if (f[k] > best) {  // strict: keeps the first index within a thread
-        best = f[k];
-        bi = i * 8 + k;
-      }
+    for (int k = 0; k < 8; k++) take_bits(best, bi, h[k], i * 8 + k);
   }
-  for (int i = vv * 8 + threadIdx.x; i < V; i += 256) {
-    float f = bf2f(x[i]);
-    // Strict here too: a thread's tail indices ascend and lie past its vector ones, and an
-    // equality clause would let a -inf entry "win" against the initial -inf.
-    if (f > best) {
-      best = f;
-      bi = i;
-    }
-  }
-  wave_argmax(best, bi);
+  // take_bits is strict for the tail too: a thread's tail indices ascend and lie past its vector ones.
+  for (int i = vv * 8 + threadIdx.x; i < V; i += 256) take_bits(best, bi, x[i], i);
   __shared__ float sb[4];
   __shared__ int si[4];
-  if ((threadIdx.x & 63) == 0) {
-    sb[threadIdx.x >> 6] = best;
-    si[threadIdx.x >> 6] = bi;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < 4; w++)
-      if (sb[w] > best || (sb[w] == best && si[w] < bi)) {
-        best = sb[w];
-        bi = si[w];
-      }
-    out[row] = bi == 0x7fffffff ? 0 : bi;  // no entry above -inf (all -inf and/or NaN): id 0, never out of range
-  }
+  block_argmax<4>(best, bi, sb, si);
+  // no entry above -inf (all -inf and/or NaN): id 0, never out of range
+  if (threadIdx.x == 0) out[row] = bi == 0x7fffffff ? 0 : bi;
 }
 
 }  // namespace

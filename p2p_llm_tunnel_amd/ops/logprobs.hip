@@ -22,8 +22,9 @@
 //   decides which ids are returned or in what order.
 //
 //   Rows with want == 0 return before touching memory. -inf logits give -inf
-//   logprobs (never NaN); -0 orders as +0.
-#include "bf16_common.h"
+//   logprobs (never NaN); -0 orders as +0. The block reductions, the radix
+//   select's bucket scan (find_bucket) and the uint4 unpack are row_common.h's.
+#include "row_common.h"
 
 namespace {
 
@@ -42,75 +43,10 @@ __device__ __forceinline__ float key_value(uint32_t key) {
   return bf2f(uint16_t((key & 0x8000u) ? (key & 0x7FFFu) : (~key & 0xFFFFu)));
 }
 
-__device__ __forceinline__ float block_max(float v, float* red) {
-  v = wave_max(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float m = red[0];
-#pragma unroll
-  for (int w = 1; w < kWaves; w++) m = fmaxf(m, red[w]);
-  return m;
-}
-
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float s = 0.f;
-#pragma unroll
-  for (int w = 0; w < kWaves; w++) s += red[w];
-  return s;
-}
-
-// Among 256 buckets (descending digit order), the digit where the running
-// count from the top first reaches `need`; out[0] = that digit, out[1] = the
-// count in the buckets above it, out[2] = the count in all buckets. One wave:
-// lane j holds digits 255-4j .. 252-4j.
-__device__ __forceinline__ void find_bucket(const uint32_t* hist, uint32_t need, uint32_t* out) {
-  const int lane = threadIdx.x & 63;
-  uint32_t v[4], s = 0;
-#pragma unroll
-  for (int q = 0; q < 4; q++) {
-    v[q] = hist[255 - 4 * lane - q];
-    s += v[q];
-  }
-  uint32_t incl = s;  // inclusive prefix over lanes
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t o = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += o;
-  }
-  const uint32_t excl = incl - s;
-  const bool hit = excl < need && incl >= need;
-  const uint64_t b = __ballot(hit);
-  const int first = b ? __ffsll((unsigned long long)b) - 1 : 63;
-  if (lane == first) {
-    uint32_t run = excl, dg = 255 - 4 * lane - 3, ab = run;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      if (run + v[q] >= need || q == 3) {
-        dg = 255 - 4 * lane - q;
-        ab = run;
-        break;
-      }
-      run += v[q];
-    }
-    out[0] = dg;
-    out[1] = ab;
-  }
-  if (lane == 63) out[2] = incl;
-}
-
 // Elements i .. i+7 of the row as bf16 bit patterns; returns how many lie inside the row (i < V).
 __device__ __forceinline__ int load8(const uint16_t* __restrict__ lr, int i, int V, bool aligned, uint32_t (&h)[8]) {
   if (aligned && i + 8 <= V) {
-    const uint4 v = *reinterpret_cast<const uint4*>(lr + i);
-    h[0] = v.x & 0xFFFFu; h[1] = v.x >> 16;
-    h[2] = v.y & 0xFFFFu; h[3] = v.y >> 16;
-    h[4] = v.z & 0xFFFFu; h[5] = v.z >> 16;
-    h[6] = v.w & 0xFFFFu; h[7] = v.w >> 16;
+    bits8(*reinterpret_cast<const uint4*>(lr + i), h);
     return 8;
   }
   const int n = V - i < 8 ? V - i : 8;
@@ -149,7 +85,7 @@ __global__ __launch_bounds__(kThreads) void k_logprobs(const uint16_t* __restric
     for (int e = 0; e < 8; e++)
       if (e < n) m = fmaxf(m, bf2f(uint16_t(h[e])));
   }
-  m = block_max(m, red);
+  m = block_max<kWaves>(m, red);
   const float mm = m == -INFINITY ? 0.f : m;  // an all -inf row: exp(-inf - 0) = 0, lse = -inf
 
   // ---- pass 2: sum of exp(z - m), and the histogram of the keys' high bytes
@@ -173,7 +109,7 @@ __global__ __launch_bounds__(kThreads) void k_logprobs(const uint16_t* __restric
     }
     __syncthreads();
     if (N == 0) break;
-    if (tid < 64) find_bucket(hist, uint32_t(N), s_find);
+    if (tid < 64) find_bucket<uint32_t>(hist, uint32_t(N), &s_find[0], &s_find[1], &s_find[2]);
     __syncthreads();
     d1 = s_find[0];
     above = s_find[1];
@@ -181,7 +117,7 @@ __global__ __launch_bounds__(kThreads) void k_logprobs(const uint16_t* __restric
     lo = 0;
     __syncthreads();
   }
-  const float lse = mm + logf(block_sum(s, red));
+  const float lse = mm + logf(block_sum<kWaves>(s, red));
 
   if (tid == 0) {  // the chosen token: wherever it ranks
     const int64_t c = ids[row];
@@ -206,7 +142,7 @@ __global__ __launch_bounds__(kThreads) void k_logprobs(const uint16_t* __restric
     }
   }
   __syncthreads();
-  if (tid < 64) find_bucket(hist, uint32_t(N) - above, s_find);
+  if (tid < 64) find_bucket<uint32_t>(hist, uint32_t(N) - above, &s_find[0], &s_find[1], &s_find[2]);
   __syncthreads();
   const uint32_t kth = (d1 << 8) | s_find[0];
   const uint32_t n_above = above + s_find[1];          // keys > kth: all taken, < N of them

@@ -20,7 +20,9 @@
 // params: int64 [5, ld] — float32 bits of T, top_k (<= 0: off), float32 bits
 // of top_p (>= 1: off), seed, counter (the request's token index, so each
 // draw of a request uses fresh noise and a fixed seed replays the same text).
-#include "bf16_common.h"
+// The block reductions, the radix select's bucket scan (find_bucket) and the
+// argmax tail of the draw are row_common.h's.
+#include "row_common.h"
 
 namespace {
 
@@ -49,75 +51,6 @@ __device__ __forceinline__ float gumbel(uint64_t seed, uint64_t ctr, uint32_t i)
   return float(-log(-log(u)));
 }
 
-__device__ __forceinline__ float block_max(float v, float* red) {
-  v = wave_max(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float m = red[0];
-#pragma unroll
-  for (int w = 1; w < kWaves; w++) m = fmaxf(m, red[w]);
-  return m;
-}
-
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float s = 0.f;
-#pragma unroll
-  for (int w = 0; w < kWaves; w++) s += red[w];
-  return s;
-}
-
-// Among 256 buckets (descending digit order), the digit where the running sum
-// from the top first reaches `need`; *above = the sum of the buckets above it.
-// One wave: lane j holds digits 255-4j .. 252-4j.
-template <class T>
-__device__ __forceinline__ void find_bucket(const T* hist, T need, int* digit_out, T* above_out) {
-  const int lane = threadIdx.x & 63;
-  T v[4], s = 0;
-#pragma unroll
-  for (int q = 0; q < 4; q++) {
-    v[q] = hist[255 - 4 * lane - q];
-    s += v[q];
-  }
-  T incl = s;  // inclusive prefix over lanes
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    T o = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += o;
-  }
-  const T excl = incl - s;
-  const bool hit = excl < need && incl >= need;
-  const uint64_t b = __ballot(hit);
-  // No hit: the integer select always has one (need <= k < V = the level's total). The float select can miss
-  // when the totals, re-accumulated at this level by unordered atomics, fall short of the `need` carried down,
-  // i.e. when p * Z lies within rounding of the enclosing bucket's end. Lane 63 then takes digit 0 (q == 3
-  // below) with everything else above it, and so on down: the cut ends at the bottom of the enclosing bucket's
-  // key range. No key lies between that and the bucket's lowest token, so the kept set is the bucket and all
-  // above it, whose mass is `need` to within those roundings: the cut an exact sum could have chosen. At the
-  // first level the same reasoning keeps everything (p * Z within rounding of Z).
-  const int first = b ? __ffsll((unsigned long long)b) - 1 : 63;
-  if (lane == first) {
-    T run = excl;
-    int dg = 255 - 4 * lane - 3;
-    T ab = run;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      if (run + v[q] >= need || q == 3) {
-        dg = 255 - 4 * lane - q;
-        ab = run;
-        break;
-      }
-      run += v[q];
-    }
-    *digit_out = dg;
-    *above_out = ab;
-  }
-}
-
 __global__ __launch_bounds__(kThreads) void k_sample(const uint16_t* __restrict__ logits, int64_t* __restrict__ ids,
                                                      const int64_t* __restrict__ params, int ld, int V) {
   const int row = blockIdx.x;
@@ -135,7 +68,7 @@ __global__ __launch_bounds__(kThreads) void k_sample(const uint16_t* __restrict_
   __shared__ float red[kWaves];
   __shared__ uint32_t hist_u[256];
   __shared__ float hist_f[256];
-  __shared__ int s_digit;
+  __shared__ uint32_t s_digit;
   __shared__ uint32_t s_above_u;
   __shared__ float s_above_f;
   __shared__ float s_best[kWaves];
@@ -143,7 +76,7 @@ __global__ __launch_bounds__(kThreads) void k_sample(const uint16_t* __restrict_
 
   float m = -INFINITY;
   for (int i = threadIdx.x; i < V; i += kThreads) m = fmaxf(m, bf2f(lr[i]) * invT);
-  m = block_max(m, red);
+  m = block_max<kWaves>(m, red);
 
   // ---- top-k: the k-th largest key
   uint32_t kth = 0;  // keep key >= kth (0: everything)
@@ -157,10 +90,10 @@ __global__ __launch_bounds__(kThreads) void k_sample(const uint16_t* __restrict_
         if ((key & mask) == prefix) atomicAdd(&hist_u[(key >> shift) & 0xFF], 1u);
       }
       __syncthreads();
-      if (threadIdx.x < 64) find_bucket<uint32_t>(hist_u, need, &s_digit, &s_above_u);
+      if (threadIdx.x < 64) find_bucket<uint32_t>(hist_u, need, &s_digit, &s_above_u, nullptr);
       __syncthreads();
       need -= s_above_u;
-      prefix |= uint32_t(s_digit) << shift;
+      prefix |= s_digit << shift;
       mask |= 0xFFu << shift;
       __syncthreads();
     }
@@ -175,7 +108,7 @@ __global__ __launch_bounds__(kThreads) void k_sample(const uint16_t* __restrict_
       const float zi = bf2f(lr[i]) * invT;
       if (okey(zi) >= kth) z += __expf(zi - m);
     }
-    float need = p * block_sum(z, red);
+    float need = p * block_sum<kWaves>(z, red);
     uint32_t prefix = 0, mask = 0;
     for (int shift = 24; shift >= 0; shift -= 8) {
       for (int d = threadIdx.x; d < 256; d += kThreads) hist_f[d] = 0.f;
@@ -186,10 +119,10 @@ __global__ __launch_bounds__(kThreads) void k_sample(const uint16_t* __restrict_
         if (key >= kth && (key & mask) == prefix) atomicAdd(&hist_f[(key >> shift) & 0xFF], __expf(zi - m));
       }
       __syncthreads();
-      if (threadIdx.x < 64) find_bucket<float>(hist_f, need, &s_digit, &s_above_f);
+      if (threadIdx.x < 64) find_bucket<float>(hist_f, need, &s_digit, &s_above_f, nullptr);
       __syncthreads();
       need -= s_above_f;
-      prefix |= uint32_t(s_digit) << shift;
+      prefix |= s_digit << shift;
       mask |= 0xFFu << shift;
       __syncthreads();
     }
@@ -205,16 +138,8 @@ __global__ __launch_bounds__(kThreads) void k_sample(const uint16_t* __restrict_
     if (okey(zi) < cut) continue;
     am_take(best, bi, zi + gumbel(seed, ctr, uint32_t(i)), i);
   }
-  wave_argmax(best, bi);
-  if ((threadIdx.x & 63) == 0) {
-    s_best[threadIdx.x >> 6] = best;
-    s_bi[threadIdx.x >> 6] = bi;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    for (int w = 1; w < kWaves; w++) am_take(best, bi, s_best[w], s_bi[w]);
-    if (bi != 0x7fffffff) ids[row] = bi;
-  }
+  block_argmax<kWaves>(best, bi, s_best, s_bi);
+  if (threadIdx.x == 0 && bi != 0x7fffffff) ids[row] = bi;  // no winner: the greedy id stands
 }
 
 }  // namespace
