@@ -43,6 +43,12 @@ long-context fine-tunes (``LlamaConfig.rope_scaling``, ``models/rope.py``).
 Every key the type needs must be in the config; ``yarn``, ``dynamic``,
 ``longrope`` and any other type are refused.
 
+A checkpoint that declares a sliding attention window (Mistral-7B-v0.1 and its fine-tunes; Qwen2 / Qwen3 configs
+with ``use_sliding_window``) is served in one of two ways (docs/SLIDING_WINDOW.md). By default the context is capped
+at the window, below which sliding and full attention are the same function, and a ``sliding_attention`` entry in
+``layer_types`` is refused. With ``sliding_window=True`` the layers that slide get their window
+(``LlamaConfig.windows``) and the context is the usual one.
+
 HF Llama q/k projections are already laid out for the rotate-half RoPE
 convention our kernels use (``reference_logits``), so no head permutation is
 needed here; the fused decoder applies its own interleaving at setup.
@@ -63,9 +69,48 @@ _QKV_BIAS = {"Qwen2ForCausalLM"}  # bias on q_proj, k_proj and v_proj, always (t
 _GQA_RATIOS = (1, 2, 4, 5, 6, 7, 8)  # the fused step's attention instantiations (decode_fused.hip: GqaRatios)
 
 
-def read_config(path: str, max_seq: int | None = None) -> tuple[LlamaConfig, dict]:
+_LAYER_TYPES = ("full_attention", "sliding_attention")  # what layer_types may hold with sliding_window=True
+
+
+def layer_windows(raw: dict) -> tuple:
+    """The sliding window of every layer of an HF config that declares one (``read_config(sliding_window=True)``):
+    one int per layer, 0 for a layer with full attention. ``layer_types`` decides per layer where the config has
+    it; otherwise every layer slides, except that a config with ``use_sliding_window`` (Qwen2, Qwen3) follows
+    transformers' ``max_window_layers`` rule: layers with index >= ``max_window_layers`` slide. Refused: a config
+    that declares no window (none set, ``use_sliding_window`` false, or no layer that slides), a window below 1, a
+    ``layer_types`` list of another length than ``num_hidden_layers`` or with any other entry."""
+    n = int(raw["num_hidden_layers"])
+    sw = raw.get("sliding_window")
+    use = raw.get("use_sliding_window")  # Qwen2 / Qwen3 only; absent (or null) elsewhere
+    if sw is None or use is False:
+        raise ValueError("sliding_window=True (--sliding-window), but the checkpoint declares no sliding window "
+                         "(config.json has no sliding_window, or use_sliding_window is false)")
+    if isinstance(sw, bool) or not isinstance(sw, int) or sw < 1:
+        raise ValueError(f"sliding_window {sw!r}: a window must be an int >= 1")
+    types = raw.get("layer_types")
+    if types is not None:
+        other = sorted({str(t) for t in types} - set(_LAYER_TYPES))
+        if other:
+            raise ValueError(f"layer_types {other}: only full_attention and sliding_attention layers are supported "
+                             "by the decode kernels")
+        if len(types) != n:
+            raise ValueError(f"layer_types has {len(types)} entries, but num_hidden_layers is {n}")
+        slides = [t == "sliding_attention" for t in types]
+    elif use is not None:
+        first = int(raw["max_window_layers"]) if raw.get("max_window_layers") is not None else n
+        slides = [i >= first for i in range(n)]
+    else:
+        slides = [True] * n
+    if not any(slides):
+        raise ValueError("sliding_window=True (--sliding-window), but the checkpoint declares no sliding window: "
+                         "none of its layers slides (layer_types / max_window_layers)")
+    return tuple(int(sw) if s else 0 for s in slides)
+
+
+def read_config(path: str, max_seq: int | None = None, sliding_window: bool = False) -> tuple[LlamaConfig, dict]:
     """LlamaConfig from an HF ``config.json`` (file or checkpoint directory);
-    also returns the raw dict (tokenizer ids, tie flag)."""
+    also returns the raw dict (tokenizer ids, tie flag). ``sliding_window``: serve the checkpoint's sliding window
+    (``layer_windows``) instead of capping the context at it."""
     f = os.path.join(path, "config.json") if os.path.isdir(path) else path
     with open(f) as fh:
         raw = json.load(fh)
@@ -88,12 +133,18 @@ def read_config(path: str, max_seq: int | None = None) -> tuple[LlamaConfig, dic
     if raw.get("attention_bias") or raw.get("mlp_bias"):
         raise ValueError("projection biases are not supported by the decode kernels"
                          + (" (Qwen2: on q, k and v only, without a config flag)" if arch in _QKV_BIAS else ""))
-    other = sorted({str(t) for t in raw.get("layer_types") or []} - {"full_attention"})
-    if other:
-        raise ValueError(f"layer_types {other}: only full_attention layers are supported by the decode kernels")
-    sw = raw.get("sliding_window")
-    if sw and raw.get("use_sliding_window", True):  # full attention == sliding attention up to the window
-        max_seq = min(int(max_seq or sw), int(sw))
+    windows = None
+    if sliding_window:  # the layers that slide get their window; the context is not capped
+        windows = layer_windows(raw)
+    else:
+        other = sorted({str(t) for t in raw.get("layer_types") or []} - {"full_attention"})
+        if other:
+            raise ValueError(f"layer_types {other}: only full_attention layers are supported by the decode kernels"
+                             + (" (sliding_attention: with sliding_window=True / --sliding-window)"
+                                if "sliding_attention" in other else ""))
+        sw = raw.get("sliding_window")
+        if sw and raw.get("use_sliding_window", True):  # full attention == sliding attention up to the window
+            max_seq = min(int(max_seq or sw), int(sw))
     heads = int(raw["num_attention_heads"])
     dim = int(raw["hidden_size"])
     kv_heads = int(raw.get("num_key_value_heads", heads))
@@ -108,7 +159,7 @@ def read_config(path: str, max_seq: int | None = None) -> tuple[LlamaConfig, dic
         ffn=int(raw["intermediate_size"]),
         max_seq=int(max_seq or min(int(raw.get("max_position_embeddings", 2048)), 8192)),
         eps=float(raw.get("rms_norm_eps", 1e-5)), rope_theta=float(theta), qk_norm=arch in _QK_NORM,
-        qkv_bias=arch in _QKV_BIAS, rope_scaling=scaling)
+        qkv_bias=arch in _QKV_BIAS, rope_scaling=scaling, windows=windows)
     return cfg, raw
 
 
@@ -163,7 +214,7 @@ class _Reader:
 
 def load_llama(path: str, device="cuda", max_batch: int = 8, max_seq: int | None = None,
                fused: bool = True, prefix: str = "model.", kv_dtype: str = "bf16",
-               weight_dtype: str = "bf16", kv_scales=None) -> TinyLlama:
+               weight_dtype: str = "bf16", kv_scales=None, sliding_window: bool = False) -> TinyLlama:
     """A TinyLlama with the checkpoint's weights (bf16 on ``device``). ``kv_dtype``: "bf16" or "fp8", the KV
     cache's format (``TinyLlama``), for every family alike. ``kv_scales`` ("fp8" only): None (scale 1: ``k_scale`` /
     ``v_scale`` tensors a checkpoint may carry are then not read), a ``KvScales``, or "checkpoint": the per-layer
@@ -171,13 +222,17 @@ def load_llama(path: str, device="cuda", max_batch: int = 8, max_seq: int | None
     the layer's KV heads; a checkpoint that lacks them for any layer is refused. ``weight_dtype``: "bf16" or "fp8" (docs/WEIGHT_FP8.md): each
     layer's GEMM weights are quantised on ``device`` as soon as the layer is read and its bf16 tensors dropped, so
     the device never holds the bf16 and the FP8 copies of all layers together. The checkpoint itself is bf16 / fp16
-    / fp32 either way: one that is already quantised on disk is treated as before."""
+    / fp32 either way: one that is already quantised on disk is treated as before. ``sliding_window``: serve the
+    checkpoint's sliding attention window (``read_config``, docs/SLIDING_WINDOW.md), fused step only; a checkpoint
+    that declares none is refused."""
     from p2p_llm_tunnel_amd.models.tiny_llm import WEIGHT_DTYPES, quantize_layer_
     if weight_dtype not in WEIGHT_DTYPES:
         raise ValueError(f"weight_dtype must be one of {list(WEIGHT_DTYPES)}, got {weight_dtype!r}")
     from p2p_llm_tunnel_amd.models import kv_scales as kvs
     kv_scales = kvs.parse_kv_scales(kv_scales, kv_dtype)  # refused with a bf16 cache before anything is read
-    cfg, raw = read_config(path, max_seq)
+    cfg, raw = read_config(path, max_seq, sliding_window)
+    if cfg.windowed and not fused:
+        raise ValueError("a sliding window runs the fused step only: load with fused=True")
     c = cfg
     rd = _Reader(path)
     dev = torch.device(device)

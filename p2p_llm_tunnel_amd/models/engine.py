@@ -452,8 +452,9 @@ class Engine:
         lp_dev = self.device if use_graph else None
         fp8 = getattr(model, "kv_dtype", "bf16") != "bf16"  # read and written by the fused HIP step alone
         w8 = getattr(model, "weight_dtype", "bf16") != "bf16"  # multiplied by the fused HIP step alone
+        windowed = bool(getattr(getattr(model, "cfg", None), "windowed", False))  # attended by the fused HIP step alone
         for on, what in ((penalties, "penalties need"), (fp8, "an fp8 KV cache needs"), (w8, "fp8 weights need"),
-                         (guided, "guided decoding needs")):
+                         (guided, "guided decoding needs"), (windowed, "a sliding window needs")):
             if on and not use_graph:
                 raise ValueError(f"{what} the graph-captured HIP step; this engine runs eagerly")
         self.penalties = bool(penalties)

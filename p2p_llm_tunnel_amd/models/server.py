@@ -693,7 +693,8 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
                  engine: Engine | None = None, checkpoint: str | None = None, max_seq: int | None = None,
                  tokenizer=None, default_temperature: float = 0.0, prefix_cache: bool = False, prefix_min: int = 16,
                  embed_pooling: str = "mean", penalties: bool = False, kv_dtype: str = "bf16",
-                 guided: bool = False, guided_states: int = 1024, weight_dtype: str = "bf16", kv_scales=None):
+                 guided: bool = False, guided_states: int = 1024, weight_dtype: str = "bf16", kv_scales=None,
+                 sliding_window: bool = False):
     """Engine + HTTP front-end; returns (server, port, engine). ``server.shutdown()``
     stops the HTTP side, ``engine.stop()`` the GPU side. ``checkpoint``: serve a
     Hugging Face Llama checkpoint directory (weights + tokenizer) instead of
@@ -711,7 +712,14 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
     docs/WEIGHT_FP8.md) is ``Engine``'s and ``load_llama``'s, and an injected engine's model must have it.
     ``kv_scales`` (``kv_dtype="fp8"`` only): a ``KvScales``, the path of a JSON file ``{"k": [[..]], "v": [[..]]}``
     or "checkpoint" (the checkpoint's own ``k_scale`` / ``v_scale`` tensors): per-layer, per-KV-head scales of the
-    FP8 cache (docs/KV_FP8.md); an injected engine's model must carry the same."""
+    FP8 cache (docs/KV_FP8.md); an injected engine's model must carry the same.
+    ``sliding_window``: serve the checkpoint's sliding attention window instead of capping the context at it
+    (``load_llama``, docs/SLIDING_WINDOW.md); it needs a checkpoint that declares one, or an injected engine whose
+    model has windowed layers."""
+    if sliding_window and engine is None and not checkpoint:
+        raise ValueError("sliding_window=True (--sliding-window) needs a checkpoint that declares a sliding window")
+    if sliding_window and engine is not None and not getattr(getattr(engine.model, "cfg", None), "windowed", False):
+        raise ValueError("sliding_window=True, but the injected engine's model has no windowed layer")
     kv_dtype = parse_kv_dtype(kv_dtype)
     from p2p_llm_tunnel_amd.models import kv_scales as kvs
     kv_scales = kvs.parse_kv_scales(kv_scales, kv_dtype)
@@ -738,7 +746,7 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
         import os
         from p2p_llm_tunnel_amd.models.checkpoint import Tokenizer, load_llama
         model = load_llama(checkpoint, device=device, max_batch=max_batch, max_seq=max_seq, kv_dtype=kv_dtype,
-                           weight_dtype=weight_dtype, kv_scales=kv_scales)
+                           weight_dtype=weight_dtype, kv_scales=kv_scales, sliding_window=sliding_window)
         tok = tok or Tokenizer.for_checkpoint(checkpoint)
         engine = Engine(device=device, max_batch=max_batch, model=model, prefix_cache=prefix_cache,
                         prefix_min=prefix_min, penalties=penalties, guided=guided, guided_states=guided_states)
@@ -790,6 +798,15 @@ def kv_cache_line(model, kv_dtype: str) -> str:
             + (f"; scales in use: {scales.describe()}" if scales is not None else ""))
 
 
+def window_line(model) -> str:
+    """The start-up log line of ``--sliding-window``: the window, how many layers have one, and the context."""
+    cfg = model.cfg
+    windows = [w for w in (cfg.windows or ()) if w]
+    sizes = sorted(set(windows))
+    return (f"sliding window: {'/'.join(str(w) for w in sizes) or 'none'} tokens on {len(windows)} of {cfg.n_layers} "
+            f"layers; context {cfg.max_seq} tokens (the cache keeps every row: no ring buffer)")
+
+
 def replica_cmd(a, i: int) -> list[str]:
     """The command line of replica ``i`` of ``--gpus``: this process's own switches, on device ``cuda:i`` and port
     ``a.port + i``."""
@@ -812,6 +829,8 @@ def replica_cmd(a, i: int) -> list[str]:
         cmd += ["--guided", "--guided-states", str(a.guided_states)]
     if getattr(a, "weight_dtype", "bf16") != "bf16":
         cmd += ["--weight-dtype", a.weight_dtype]
+    if getattr(a, "sliding_window", False):
+        cmd += ["--sliding-window"]
     return cmd
 
 
@@ -889,6 +908,12 @@ def arg_parser() -> argparse.ArgumentParser:
                          "with one fp32 scale per output row, per-row absmax, no calibration; the activations stay "
                          "bf16): half the weight bytes per decode step; the embedding table stays bf16 "
                          "(docs/WEIGHT_FP8.md)")
+    ap.add_argument("--sliding-window", action="store_true",
+                    help="serve the checkpoint's sliding attention window (Mistral-7B-v0.1 and its fine-tunes; Qwen2 / "
+                         "Qwen3 with use_sliding_window) instead of capping the context at it: the layers that slide "
+                         "attend to their last sliding_window tokens and the context follows --max-seq / "
+                         "max_position_embeddings. Needs --checkpoint; one that declares no window is refused "
+                         "(docs/SLIDING_WINDOW.md)")
     ap.add_argument("--guided", action="store_true",
                     help="guided decoding on the device: /v1/chat/completions and /v1/completions act on "
                          "guided_regex, guided_choice and structured_outputs {regex | choice} (a checkpoint with a "
@@ -904,6 +929,8 @@ def main(argv=None):
     a = arg_parser().parse_args(argv)
     if a.kv_scales and a.kv_dtype != "fp8":
         raise SystemExit("--kv-scales needs --kv-dtype fp8: a bf16 KV cache has no scales")
+    if a.sliding_window and not a.checkpoint:
+        raise SystemExit("--sliding-window needs --checkpoint: the window is the checkpoint's own")
     if a.gpus > 0:
         raise SystemExit(_replicas(a))
     srv, port, engine = start_server(a.host, a.port, a.device, a.config, a.max_batch, checkpoint=a.checkpoint,
@@ -911,9 +938,11 @@ def main(argv=None):
                                      prefix_cache=a.prefix_cache, prefix_min=a.prefix_min,
                                      embed_pooling=a.embed_pooling, penalties=a.penalties, kv_dtype=a.kv_dtype,
                                      guided=a.guided, guided_states=a.guided_states, weight_dtype=a.weight_dtype,
-                                     kv_scales=a.kv_scales)
+                                     kv_scales=a.kv_scales, sliding_window=a.sliding_window)
     print(weights_line(engine.model, a.weight_dtype), flush=True)
     print(kv_cache_line(engine.model, a.kv_dtype), flush=True)
+    if a.sliding_window:
+        print(window_line(engine.model), flush=True)
     print(f"inference endpoint on http://{a.host}:{port} ({a.checkpoint or a.config}, {a.device})", flush=True)
     try:
         threading.Event().wait()

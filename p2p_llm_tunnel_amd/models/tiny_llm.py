@@ -21,7 +21,7 @@ causal attention over the whole sequence) for numerics tests.
 from __future__ import annotations
 
 import math
-from dataclasses import dataclass
+from dataclasses import InitVar, dataclass
 
 import torch
 import torch.nn.functional as F
@@ -48,6 +48,31 @@ class LlamaConfig:
     qkv_bias: bool = False  # bias on the q, k and v projections (Qwen2): layers carry bqkv [(H + 2 Hkv) * head_dim]
     # llama3 / linear RoPE scaling (Llama 3.1+): the kernels read inv_freq from a table instead of computing it
     rope_scaling: RopeScaling | None = None
+    # Sliding-window attention (docs/SLIDING_WINDOW.md): None, or one int per layer, 0 for full attention and W >= 1
+    # for a layer whose token at position p attends to positions (p - W, p]: W tokens, its own included. None and all
+    # zeros are the decoder without windows.
+    windows: tuple | None = None
+    sliding_window: InitVar[int | None] = None  # shorthand: the same window on every layer (it sets ``windows``)
+
+    def __post_init__(self, sliding_window):
+        if sliding_window is not None:
+            if isinstance(sliding_window, bool) or not isinstance(sliding_window, int) or sliding_window < 1:
+                raise ValueError(f"sliding_window must be an int >= 1, got {sliding_window!r}")
+            if self.windows is not None:
+                raise ValueError("give sliding_window (every layer) or windows (per layer), not both")
+            object.__setattr__(self, "windows", (sliding_window,) * self.n_layers)
+        elif self.windows is not None:
+            w = tuple(self.windows)
+            if len(w) != self.n_layers:
+                raise ValueError(f"windows must hold one entry per layer ({self.n_layers}), got {len(w)}")
+            if any(isinstance(x, bool) or not isinstance(x, int) or x < 0 for x in w):
+                raise ValueError(f"windows must be ints >= 0 (0: full attention), got {w!r}")
+            object.__setattr__(self, "windows", w)
+
+    @property
+    def windowed(self) -> bool:
+        """Whether any layer has a sliding window."""
+        return bool(self.windows) and any(self.windows)
 
 
 CONFIGS = {
@@ -372,7 +397,8 @@ class TinyLlama:
             self._fused = ops.FusedLlamaDecoder(self.dims(), self.fused_weights(), self.k_cache, self.v_cache,
                                                 weight_fp8=self.weight_dtype == "fp8",
                                                 kv_scales=(self.kv_scales.table(self.device)
-                                                           if self.kv_scales is not None else None))
+                                                           if self.kv_scales is not None else None),
+                                                windows=self.cfg.windows if self.cfg.windowed else None)
         return self._fused
 
     def step_rows(self, tokens, pos, slots=None, emit_rows=0, pos_range=None):
@@ -394,6 +420,9 @@ class TinyLlama:
         if self.weight_dtype != "bf16":
             raise ValueError(f"{self.weight_dtype} weights run the fused step only (at most {ops.MAX_ROWS} rows, "
                              "fused=True): the unfused path multiplies bf16 weights")
+        if self.cfg.windowed:
+            raise ValueError(f"a sliding window runs the fused step only (at most {ops.MAX_ROWS} rows, fused=True): "
+                             "the unfused attention kernel reads every cached position")
         return self._decode_unfused(tokens, pos, pos_range or (0, self.cfg.max_seq - 1))
 
     def _decode_unfused(self, tokens, pos, pos_range):
@@ -493,6 +522,8 @@ class TinyLlama:
     def reference_hidden(self, seqs: torch.Tensor, kv_round=None) -> torch.Tensor:
         """fp32 forward of full sequences [B, T]; returns the final normed hidden
         state of every position [B, T, dim] (what the LM head multiplies).
+        A layer with a sliding window W (``cfg.windows``) masks, besides the future, every key at or below q - W:
+        position q attends to (q - W, q], transformers' ``kv_idx > q_idx - sliding_window``.
         ``kv_round``: how K and V rows are stored, a function of the fp32 rows. None: the model's own cache
         format, bf16 rounding or ``e4m3_round`` (one rounding from fp32, not through bf16). With ``kv_scales`` (and
         no ``kv_round``) a row of layer i and KV head h is stored as the kernels store it, e4m3_round(x * fp32(1 / s)),
@@ -535,8 +566,11 @@ class TinyLlama:
         residual = x
         h = bf(rms(x, self._ref_norm(self.layers[0]["attn_norm"])))
         G = c.n_heads // c.n_kv_heads
-        mask = torch.full((T, T), float("-inf"), device=seqs.device).triu(1)
+        causal = torch.full((T, T), float("-inf"), device=seqs.device).triu(1)
         for i, L in enumerate(self.layers):
+            mask = causal
+            if c.windowed and c.windows[i]:  # keys at or below q - W as well
+                mask = causal + torch.full((T, T), float("-inf"), device=seqs.device).tril(-c.windows[i])
             raw = h @ self.reference_weight("wqkv", i).T
             raw = raw + f32(L["bqkv"]) if c.qkv_bias else raw
             qkv = bf(raw)

@@ -66,6 +66,14 @@ class WeightPlan(ctypes.Structure):
     _fields_ = [("w8", _INT)]
 
 
+class WindowPlan(ctypes.Structure):
+    """Mirror of ``WindowPlan``: what one layer's sliding window changes of a step, beside its ``StepPlan`` as
+    ``KvPlan`` and ``WeightPlan`` are (docs/SLIDING_WINDOW.md). ``win``: 1 for ``k_attn<D, G, KV8, true>``;
+    ``window``: its launch argument; ``slots``: its gridDim.x, the span slots of a cache of ``min(max_seq, window)``
+    rows. A layer without a window has ``win`` 0, ``window`` 0 and ``StepPlan.attn.slots``."""
+    _fields_ = [("win", _INT), ("window", _INT), ("slots", _INT)]
+
+
 def _signatures() -> dict:
     """Every symbol ``lib()`` binds -> its argtypes. The restype is ``c_int`` unless ``_RESTYPES`` names another."""
     vp, i, f, sz, ptr = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.POINTER
@@ -100,6 +108,9 @@ def _signatures() -> dict:
         "p2pt_llama_decode_w": [dims, wp, ptr(vp), vp, vp, vp, vp, vp, i, i, vp, sz, vp, vp, vp],
         "p2pt_llama_decode_kv": [dims, wp, vp, ptr(vp), vp, vp, vp, vp, vp, i, i, vp, sz, vp, vp, vp],
         "p2pt_llama_weight_layout": [dims, wp, ip, ip, i],
+        "p2pt_llama_window_plan": [dims, i, i, ptr(WindowPlan)],
+        "p2pt_llama_plan_kernels_win": [dims, i, i, wp, ip],
+        "p2pt_llama_decode_win": [dims, wp, vp, ip, ptr(vp), vp, vp, vp, vp, vp, i, i, vp, sz, vp, vp, vp],
         "p2pt_attn_span": [i, i],
         "p2pt_max_rows": [],
         "p2pt_skinny_bench": [vp, vp, vp, i, i, i, i, i, i, vp],  # microbenchmark hooks (scripts/bench_skinny.py)
@@ -173,11 +184,42 @@ def weight_plan(dims: LlamaDims, weight_fp8: bool = False) -> WeightPlan:
     return plan
 
 
-def plan_kernels_ok(dims: LlamaDims, B: int, emit_rows: int = 0, weight_fp8: bool = False) -> bool:
+def check_windows(windows, n_layers: int) -> tuple | None:
+    """``windows`` as the fused step takes them: None, or one int per layer, 0 for full attention and W >= 1 for a
+    sliding window of W positions. Returns None when no layer has a window (None and all zeros alike)."""
+    if windows is None:
+        return None
+    windows = tuple(windows)
+    if len(windows) != n_layers:
+        raise ValueError(f"windows must hold one entry per layer ({n_layers}), got {len(windows)}")
+    for L, w in enumerate(windows):
+        if not _int_in(w, 0, 1 << 31):
+            raise ValueError(f"layer {L}: a window must be an int >= 0 (0: full attention), got {w!r}")
+    return windows if any(windows) else None
+
+
+def window_plan(dims: LlamaDims, B: int, window: int) -> WindowPlan:
+    """What a layer with sliding window ``window`` (0: none) launches for attention at B rows, beside
+    ``step_plan(dims, B)`` (host only): the ``k_attn`` variant, its window argument and its span slots. The
+    partials' stride is ``step_plan(dims, B).attn.stride`` for every layer."""
+    plan = WindowPlan()
+    if not _int_in(window, 0, 1 << 31) or \
+            lib().p2pt_llama_window_plan(ctypes.byref(dims), B, window, ctypes.byref(plan)) != 0:
+        raise ValueError("dims, row count or window not supported by the fused decode kernels")
+    return plan
+
+
+def plan_kernels_ok(dims: LlamaDims, B: int, emit_rows: int = 0, weight_fp8: bool = False, windows=None) -> bool:
     """Whether every stage of ``step_plan(dims, B, emit_rows)``, ``kv_plan(dims)`` and
     ``weight_plan(dims, weight_fp8)`` names a kernel the library instantiates, by the lookups its launchers use
-    (host only)."""
-    if weight_fp8:
+    (host only). ``windows``: the per-layer sliding windows (``check_windows``); every layer's ``window_plan`` is
+    then looked up too."""
+    windows = check_windows(windows, dims.n_layers)
+    if windows is not None:
+        wp = WeightPlan(w8=int(bool(weight_fp8)))
+        rc = lib().p2pt_llama_plan_kernels_win(ctypes.byref(dims), B, emit_rows, ctypes.byref(wp),
+                                               (ctypes.c_int * len(windows))(*windows))
+    elif weight_fp8:
         wp = WeightPlan(w8=1)
         rc = lib().p2pt_llama_plan_kernels_w(ctypes.byref(dims), B, emit_rows, ctypes.byref(wp))
     else:
@@ -906,14 +948,21 @@ class FusedLlamaDecoder:
     weight table: the plans, the table and the workspace are those of the model without scales, and None runs the
     step exactly as before.
 
+    ``windows``: None, or one int per layer: 0 for full attention, W >= 1 for a sliding window (the layer's rows
+    attend to their last W positions, their own included: docs/SLIDING_WINDOW.md). Such a layer runs
+    ``k_attn<D, G, KV8, true>`` on ``window_plan``'s slots. Like the scales it is no part of ``dims``, of a plan or of
+    the weight table, and None or all zeros runs the step exactly as before.
+
     Holds the weight pointer table and a zero-initialised workspace; ``step``
     validates the per-call tensors and launches on the current stream (capturable
     into a hipGraph: no host sync, no allocation, grids sized by the row count).
     """
 
     def __init__(self, dims: LlamaDims, weights: list, k_cache: torch.Tensor, v_cache: torch.Tensor,
-                 weight_fp8: bool = False, kv_scales: torch.Tensor | None = None):
+                 weight_fp8: bool = False, kv_scales: torch.Tensor | None = None, windows=None):
         self.dims = dims
+        self.windows = check_windows(windows, dims.n_layers)
+        self._windows = (ctypes.c_int * dims.n_layers)(*self.windows) if self.windows is not None else None
         self.weight_fp8 = bool(weight_fp8)
         self._wplan = WeightPlan(w8=int(self.weight_fp8))
         dev = k_cache.device
@@ -1056,6 +1105,12 @@ class FusedLlamaDecoder:
             raise ValueError(f"rows must be 1..{limit} with matching pos/ids")
         if logits.shape != (B, d.vocab):
             raise ValueError("logits must be [B, vocab]")
+        if self._windows is not None:
+            _ok(lib().p2pt_llama_decode_win(ctypes.byref(d), ctypes.byref(self._wplan), _p(self.kv_scales),
+                                            self._windows, self._wptr, _p(self.k_cache), _p(self.v_cache), _p(tokens),
+                                            _p(pos), _p(slots), B, emit_rows, _p(self.ws), self.ws.numel(),
+                                            _p(logits), _p(ids), _stream(tokens)), "llama_decode")
+            return
         if self.kv_scales is not None:
             _ok(lib().p2pt_llama_decode_kv(ctypes.byref(d), ctypes.byref(self._wplan), _p(self.kv_scales), self._wptr,
                                            _p(self.k_cache), _p(self.v_cache), _p(tokens), _p(pos), _p(slots), B,

@@ -76,6 +76,31 @@ struct KvScales {
   }
 };
 
+// The sliding windows of a model's layers, beside the plans as WeightPlan and KvScales are and for the same reason: no
+// field of LlamaDims or of a plan struct, so a model without windows plans, lays out and launches what it did. A host
+// array of n_layers ints: 0 is full attention, W >= 1 attends to the last W positions, the row's own included
+// (docs/SLIDING_WINDOW.md). nullptr: no layer has a window.
+struct Windows {
+  const int* per_layer;
+  int at(int L) const { return per_layer ? per_layer[L] : 0; }
+};
+bool windows_ok(const LlamaDims& d, const Windows& w) {
+  for (int L = 0; w.per_layer && L < d.n_layers; L++)
+    if (w.per_layer[L] < 0) return false;
+  return true;
+}
+// What one layer's window changes of a step (mirrored with ctypes): the attention variant, its launch argument and
+// its span slots. Everything else of the layer is StepPlan's, and a layer with window 0 is StepPlan's attn as it is.
+struct WindowPlan {
+  int win;     // k_attn<D, G, KV8, true>
+  int window;  // its launch argument (0 without)
+  int slots;   // gridDim.x: those of a cache of min(max_seq, window) rows; the partials' stride stays AttnPlan's
+};
+WindowPlan plan_window(const LlamaDims& d, int B, int window) {
+  if (window <= 0) return {0, 0, attn_slots(B, d.Hkv, d.max_seq)};
+  return {1, window, attn_window_slots(B, d.Hkv, d.max_seq, window)};
+}
+
 // One workgroup per tn subtiles of 16 >> kpl columns of one 16-row tile.
 //  - K parts (GemmArgs::kpl), where asked for (the d_model-wide O and down
 //    projections): the widest tile (16, 8 or 4 columns) whose column tiles
@@ -294,7 +319,7 @@ using HeadDims = Ints<64, 128>;  // D of k_attn and k_qknorm_rope
 // G of k_attn, the GQA ratio H / Hkv (models/checkpoint.py mirrors it as _GQA_RATIOS). 5, 6 and 7 are the Qwen2 /
 // Qwen2.5 family's (40/8, 12/2, 14/2 and 28/4). 3 is absent: no checkpoint the loader accepts uses it.
 using GqaRatios = Ints<1, 2, 4, 5, 6, 7, 8>;
-using Flags = Ints<0, 1>;  // KV8 of k_attn; TAB and KV8 of k_qknorm_rope; W8 of k_skinny
+using Flags = Ints<0, 1>;  // KV8 and WIN of k_attn; TAB and KV8 of k_qknorm_rope; W8 of k_skinny
 using SkinnyWaves = Ints<4, 8>;
 using SkinnyTiles = Ints<1, 2>;
 using SkinnyBatches = Ints<1, 2, 4>;
@@ -341,9 +366,10 @@ SkinnyKernel skinny_kernel(const GemmPlan& p, int w8 = 0) {
   return k;
 }
 using AttnKernel = decltype(&k_attn<64, 1, false>);
-AttnKernel attn_kernel(int D, int G, int kv8) {
+AttnKernel attn_kernel(int D, int G, int kv8, int win = 0) {
   AttnKernel k = nullptr;
-  pick([&](auto d, auto g, auto f8) { k = k_attn<d, g, f8 != 0>; }, D, HeadDims{}, G, GqaRatios{}, kv8, Flags{});
+  pick([&](auto d, auto g, auto f8, auto wn) { k = k_attn<d, g, f8 != 0, wn != 0>; }, D, HeadDims{}, G, GqaRatios{},
+       kv8, Flags{}, win, Flags{});
   return k;
 }
 using QkNormKernel = void (*)(QkNormArgs);
@@ -376,18 +402,22 @@ hipError_t launch(const GemmPlan& p, GemmArgs a, hipStream_t s, int w8 = 0) {
 
 // (span slot, row, KV head) workgroups of 8 waves. Row b reads cache slot
 // slot[b] (nullptr: slot b) of nslots. kv8: the caches hold e4m3 bytes (KvPlan::attn_kv8). k_scale, v_scale: the
-// layer's cache scales [Hkv] (KvScales), both nullptr for scale 1; refused with a bf16 cache.
+// layer's cache scales [Hkv] (KvScales), both nullptr for scale 1; refused with a bf16 cache. wp: the layer's
+// window (WindowPlan); nullptr, or one without a window, launches the plan's own slots and the kernel without WIN.
+// A windowed layer's slots must fit the partials' stride.
 hipError_t launch_attn(const AttnPlan& p, int kv8, const void* q, const void* kc, const void* vc, const int* pos,
                        const int* slot, int nslots, float* part_o, float* part_ml, unsigned* counters, void* out,
                        int H, int Hkv, int Smax, hipStream_t s, const float* k_scale = nullptr,
-                       const float* v_scale = nullptr) {
-  const AttnKernel k = attn_kernel(p.D, p.G, kv8);
+                       const float* v_scale = nullptr, const WindowPlan* wp = nullptr) {
+  const bool win = wp && wp->win;
+  const AttnKernel k = attn_kernel(p.D, p.G, kv8, win);
   if (!k) return hipErrorInvalidValue;
   if ((k_scale != nullptr) != (v_scale != nullptr) || (k_scale && !kv8)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k, dim3(p.slots, p.grid_y), dim3(512), 0, s, static_cast<const uint16_t*>(q),
+  if (win && (wp->window < 1 || wp->slots < 1 || wp->slots > p.stride)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k, dim3(win ? wp->slots : p.slots, p.grid_y), dim3(512), 0, s, static_cast<const uint16_t*>(q),
                      static_cast<const uint16_t*>(kc), static_cast<const uint16_t*>(vc), pos, slot, nslots, part_o,
                      part_ml, counters, static_cast<uint16_t*>(out), H, Hkv, Smax, p.stride, 1.f / sqrtf(float(p.D)),
-                     k_scale, v_scale);
+                     k_scale, v_scale, win ? wp->window : 0);
   return hipGetLastError();
 }
 
@@ -473,21 +503,39 @@ int p2pt_llama_kv_plan(const LlamaDims* d, KvPlan* out) {
 // Whether every stage of the plans above names a kernel that exists, by the launchers' own lookups (host only).
 // 0: all do; 1 + n: stage n, counting qkv_first, qkv, qk_norm, attn, o, gate_up, down, lm_head, is the first that
 // does not; -1: dims or row count refused.
-int p2pt_llama_plan_kernels_w(const LlamaDims* d, int B, int emit_rows, const WeightPlan* wp) {
-  if (!dims_ok(*d) || !rows_ok(B) || !weights_ok(*wp)) return -1;
+// windows: the per-layer windows (Windows), nullptr for none: every layer's attention variant must exist, and a
+// windowed layer's slots must fit the partials' stride. A negative window is refused (-1).
+int p2pt_llama_plan_kernels_win(const LlamaDims* d, int B, int emit_rows, const WeightPlan* wp, const int* windows) {
+  if (!dims_ok(*d) || !rows_ok(B) || !weights_ok(*wp) || !windows_ok(*d, Windows{windows})) return -1;
   const StepPlan P = plan_step(*d, B, emit_rows);
   const KvPlan KV = plan_kv(*d);
   const int w8 = wp->w8;
+  bool attn = true;
+  for (int L = 0; L < d->n_layers; L++) {
+    const WindowPlan wn = plan_window(*d, B, Windows{windows}.at(L));
+    attn = attn && attn_kernel(P.attn.D, P.attn.G, KV.attn_kv8, wn.win) != nullptr && wn.slots >= 1 &&
+           wn.slots <= P.attn.stride;
+  }
   const bool found[] = {skinny_kernel(P.qkv_first, w8) != nullptr,
                         skinny_kernel(P.qkv, w8) != nullptr,
                         !P.qk_norm_grid || qknorm_kernel(d->D, P.qk_norm_table, KV.qk_norm_kv8) != nullptr,
-                        attn_kernel(P.attn.D, P.attn.G, KV.attn_kv8) != nullptr,
+                        attn,
                         skinny_kernel(P.o, w8) != nullptr,
                         skinny_kernel(P.gate_up, w8) != nullptr,
                         skinny_kernel(P.down, w8) != nullptr,
                         skinny_kernel(P.lm_head, w8) != nullptr};
   for (int n = 0; n < 8; n++)
     if (!found[n]) return 1 + n;
+  return 0;
+}
+int p2pt_llama_plan_kernels_w(const LlamaDims* d, int B, int emit_rows, const WeightPlan* wp) {
+  return p2pt_llama_plan_kernels_win(d, B, emit_rows, wp, nullptr);
+}
+// What a layer with sliding window `window` (0: none) launches for attention at B rows, beside the plans above
+// (host only).
+int p2pt_llama_window_plan(const LlamaDims* d, int B, int window, WindowPlan* out) {
+  if (!dims_ok(*d) || !rows_ok(B) || window < 0) return int(hipErrorInvalidValue);
+  *out = plan_window(*d, B, window);
   return 0;
 }
 int p2pt_llama_plan_kernels(const LlamaDims* d, int B, int emit_rows) {
@@ -549,12 +597,20 @@ int p2pt_max_rows() { return kMaxM; }
 //      [4][n_layers][Hkv]: 1 / k_scale, 1 / v_scale, k_scale, v_scale, every entry finite and > 0 (the caller's
 //      check). A stored byte is e4m3(clamp(x * (1 / s))) of the head's scale and k_attn undoes it (KvScales).
 //      nullptr: scale 1, which is p2pt_llama_decode_w. Refused with a bf16 cache.
-int p2pt_llama_decode_kv(const LlamaDims* dp, const WeightPlan* wp, const float* kv_scales, const void* const* w,
-                         void* k_cache, void* v_cache, const int64_t* tokens, const int* pos, const int* slots, int B,
-                         int emit_rows, void* ws, size_t ws_bytes, void* logits, int64_t* ids, void* stream) {
+//   Sliding windows (p2pt_llama_decode_win): windows is a host array of n_layers ints, read during the call only:
+//      0 for a layer with full attention, W >= 1 for one whose rows attend to their last W positions, their own
+//      included. Such a layer runs k_attn<D, G, KV8, true> on the slots of a cache of min(max_seq, W) rows; a layer
+//      with 0 launches what it did. The cache keeps max_seq rows per slot and appends go to pos as before.
+//      nullptr: no windows, which is p2pt_llama_decode_kv. A negative entry is refused.
+int p2pt_llama_decode_win(const LlamaDims* dp, const WeightPlan* wp, const float* kv_scales, const int* windows,
+                          const void* const* w, void* k_cache, void* v_cache, const int64_t* tokens, const int* pos,
+                          const int* slots, int B, int emit_rows, void* ws, size_t ws_bytes, void* logits,
+                          int64_t* ids, void* stream) {
   const LlamaDims d = *dp;
   if (!dims_ok(d) || !rows_ok(B) || (!slots && B > d.max_batch) || !weights_ok(*wp)) return int(hipErrorInvalidValue);
   if (kv_scales && !d.kv_fp8) return int(hipErrorInvalidValue);
+  const Windows WN{windows};
+  if (!windows_ok(d, WN)) return int(hipErrorInvalidValue);
   const KvScales KS{kv_scales};
   const int w8 = wp->w8;
   const Workspace W = carve(d, static_cast<uint8_t*>(ws));
@@ -593,8 +649,9 @@ int p2pt_llama_decode_kv(const LlamaDims* dp, const WeightPlan* wp, const float*
       if (failed(launch_qknorm(P.qk_norm_grid, B, d.D, P.qk_norm_table != 0, KV.qk_norm_kv8 != 0, qn, s)))
         return int(e);
     }
+    const WindowPlan wn = plan_window(d, B, WN.at(L));
     if (failed(launch_attn(P.attn, KV.attn_kv8, W.q, kc, vc, pos, slots, d.max_batch, W.part_o, W.part_ml, W.counters, W.attn, d.H,
-                           d.Hkv, d.max_seq, s, KS.at(d, KvScales::K, L), KS.at(d, KvScales::V, L))))
+                           d.Hkv, d.max_seq, s, KS.at(d, KvScales::K, L), KS.at(d, KvScales::V, L), &wn)))
       return int(e);
     if (failed(launch(P.o, to_o, s, w8))) return int(e);
     if (failed(launch(P.gate_up, to_gate_up, s, w8))) return int(e);
@@ -606,6 +663,12 @@ int p2pt_llama_decode_kv(const LlamaDims* dp, const WeightPlan* wp, const float*
   if (failed(launch(P.lm_head, to_logits, s, w8))) return int(e);
   hipLaunchKernelGGL(k_argmax_merge, dim3(P.emit_rows), dim3(256), 0, s, W.am_val, W.am_idx, P.am_parts, ids);
   return int(hipGetLastError());
+}
+int p2pt_llama_decode_kv(const LlamaDims* dp, const WeightPlan* wp, const float* kv_scales, const void* const* w,
+                         void* k_cache, void* v_cache, const int64_t* tokens, const int* pos, const int* slots, int B,
+                         int emit_rows, void* ws, size_t ws_bytes, void* logits, int64_t* ids, void* stream) {
+  return p2pt_llama_decode_win(dp, wp, kv_scales, nullptr, w, k_cache, v_cache, tokens, pos, slots, B, emit_rows, ws,
+                               ws_bytes, logits, ids, stream);
 }
 int p2pt_llama_decode_w(const LlamaDims* dp, const WeightPlan* wp, const void* const* w, void* k_cache, void* v_cache,
                         const int64_t* tokens, const int* pos, const int* slots, int B, int emit_rows, void* ws,

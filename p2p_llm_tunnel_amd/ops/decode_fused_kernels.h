@@ -19,6 +19,7 @@
 //                        and k_attn<D, G, true> reads them: the same kernel count)
 //     k_attn            GQA flash-decoding split-K; the last split to finish
 //                        for a (sequence, KV head) merges the partials in-kernel
+//     (sliding window:   a layer with a window runs k_attn<D, G, KV8, true> over its last W positions)
 //     (FP8 weights:      every k_skinny is its W8 instantiation: e4m3 weight bytes, 8-byte loads, and the
 //                        column's fp32 scale on the accumulator ahead of 1/rms: the same kernel count)
 //     k_skinny<RESID>    O projection -> residual add -> per-row sum-of-squares
@@ -29,7 +30,7 @@
 //                        per-block greedy winners
 //   k_argmax_merge       one block per row merges the winners
 //
-// k_skinny<NW, TN, EPI, UM, W8>, k_attn<D, G, KV8> and k_qknorm_rope<D, TAB, KV8> are templates; which instantiations
+// k_skinny<NW, TN, EPI, UM, W8>, k_attn<D, G, KV8, WIN> and k_qknorm_rope<D, TAB, KV8> are templates; which instantiations
 // exist is stated once, as lists of parameter values and one predicate, in decode_fused.hip, and a plan that names
 // any other is refused there. The RoPE epilogue of a model is rope_epi(bias, table, kv8) below.
 //
@@ -830,12 +831,18 @@ __host__ __device__ __forceinline__ int attn_span(int len, unsigned slots) {
 // the bytes hold x / s, and the KV head's two scalars undo that where it is free. K's joins the score scale
 // (scale * k_scale[kvh]), V's the final normalisation (v_scale[kvh] / L for 1.f / L) at the single-slot exit and in
 // the cross-slot merge, and nowhere else. At scale 1 both expressions are the unscaled ones bit for bit.
-template <int D, int G, bool KV8 = false>
+// WIN: sliding-window attention (docs/SLIDING_WINDOW.md). Row b attends to positions [lo, len) with lo = max(0, len -
+// window): `window` tokens, its own included (kv_idx > q_idx - window). The span geometry is that of a row of
+// len - lo tokens shifted up by lo: span and nact from len - lo, s0 = lo + sl * span. Rows below lo are never loaded
+// (the piece loop starts at s0 >= lo and a lane past a piece's end re-reads that piece's last row), so what they
+// hold is of no account; lo need be a multiple of nothing, since every load is a whole row's own 16 (or 8) bytes.
+// Everything after the span loop is the code below, unchanged. Without WIN `window` is not read.
+template <int D, int G, bool KV8 = false, bool WIN = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1))) void k_attn(
     const uint16_t* __restrict__ q, const uint16_t* __restrict__ kc, const uint16_t* __restrict__ vc,
     const int* __restrict__ pos, const int* __restrict__ slot, int nslots, float* __restrict__ part_o,
     float* __restrict__ part_ml, unsigned* __restrict__ counters, uint16_t* __restrict__ out, int H, int Hkv, int Smax,
-    int nsplit, float scale, const float* __restrict__ k_scale, const float* __restrict__ v_scale) {
+    int nsplit, float scale, const float* __restrict__ k_scale, const float* __restrict__ v_scale, int window) {
   constexpr int NWV = 8;
   constexpr int TOK = kAttnPiece;
   constexpr int DPL = D / kWave;  // merges: dims per lane
@@ -847,11 +854,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(1))) void k
 
   const int b = blockIdx.y / Hkv, kvh = blockIdx.y % Hkv;
   const int len = min(max(pos[b], 0), Smax - 1) + 1;
-  const int span = attn_span(len, gridDim.x);
-  const int nact = (len + span - 1) / span;  // slots with tokens
+  int lo = 0;  // first position the row attends to
+  if constexpr (WIN) lo = max(0, len - max(window, 1));
+  const int span = attn_span(len - lo, gridDim.x);
+  const int nact = (len - lo + span - 1) / span;  // slots with tokens
   const int sl = blockIdx.x;
   if (sl >= nact) return;
-  const int s0 = sl * span, s1 = min(len, s0 + span);
+  const int s0 = lo + sl * span, s1 = min(len, s0 + span);
   const int sb = slot ? min(max(slot[b], 0), nslots - 1) : b;
   const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int dg = lane % LPR, ri = lane / LPR;
@@ -1079,6 +1088,12 @@ int attn_part_stride(int max_seq) { return std::min(kAttnSlotCap, (max_seq + kAt
 // workgroups on the chip. Sized by the batch; the context enters through pos.
 int attn_slots(int B, int Hkv, int max_seq) {
   return std::max(1, std::min(kAttnTargetWgs / std::max(1, B * Hkv), attn_part_stride(max_seq)));
+}
+// ... of a layer with a sliding window: a row has min(max_seq, window) tokens at most, so the slots are those of a
+// cache that long. Never more than attn_slots(B, Hkv, max_seq), so within kAttnSlotCap and the partials' stride,
+// which stays attn_part_stride(max_seq) for every layer.
+int attn_window_slots(int B, int Hkv, int max_seq, int window) {
+  return attn_slots(B, Hkv, std::min(max_seq, std::max(window, 1)));
 }
 
 // Measured on MI355X and rejected; the code is gone, the findings stay. This
