@@ -103,6 +103,13 @@ _IN_ROWS = _LP + 1
 _PEN = slice(_IN_ROWS, _IN_ROWS + 4)
 
 
+def _layout(min_p: bool) -> tuple:
+    """(sampler rows, logprobs row, penalty rows) of the staging block. An engine built with min_p=True stages
+    one more sampler row, the float32 bits of ln(min_p), right behind the five (ops.sample_minp_ reads its six
+    rows as one block), and what follows moves down by one; without it, the rows named above."""
+    return (slice(5, 11), _LP + 1, slice(_PEN.start + 1, _PEN.stop + 1)) if min_p else (_SMP, _LP, _PEN)
+
+
 class _StepBuf:
     """Host staging of one in-flight step (two alternate: step k+1 is planned
     and launched while step k runs); ``h_in`` has the rows named above.
@@ -135,7 +142,8 @@ class _StepBuf:
 # in the order they run: ops.penalize_ writes the penalised logits of the rows that sample into ``work`` and replaces
 # their greedy ids by its argmax; ops.guide_ advances each slot's automaton by the row's input token, masks what the
 # state does not allow to -inf in ``work`` (a copy of the logits when nothing was penalised) and takes the argmax
-# again; ops.sample_ draws from ``work`` when either ran, else from the logits; ops.logprobs_ reads the RAW logits
+# again; ops.sample_ (ops.sample_minp_ in an engine built with min_p=True) draws from ``work`` when either ran, else
+# from the logits; ops.logprobs_ reads the RAW logits
 # (log-probabilities stay the model's own) and its outputs go back to pinned memory. A step replays the lowest post
 # that runs every stage an emitting row needs; rows that need less are off in their staging columns (``work`` is a
 # copy of their logits, their ids stand).
@@ -411,11 +419,17 @@ class Engine:
     request's first step (``_PenaltyState.reset``, ``_GuideState.bind``); a
     guided request whose table has no room yet waits at the head of the
     admission queue (``_take``, ``GuideTables``).
+
+    ``min_p`` (off by default, and then nothing above changes): the staging
+    block holds a sixth sampler row (``_layout``), every captured post that
+    samples launches ``ops.sample_minp_`` in place of ``ops.sample_``, and
+    ``Sampling(min_p=)`` is honoured (docs/MIN_P.md). The number of graphs is
+    what it is without the switch.
     """
 
     def __init__(self, device="cuda:0", config="tiny", max_batch=8, seed=0, use_graph=True, rows=64, model=None,
                  small_rows=16, prefix_cache=False, prefix_min=16, penalties=False, kv_dtype="bf16",
-                 guided=False, guided_states=1024, weight_dtype="bf16", kv_scales=None):
+                 guided=False, guided_states=1024, weight_dtype="bf16", kv_scales=None, min_p=False):
         if kv_scales is not None and kv_dtype != "fp8" and getattr(model, "kv_dtype", "bf16") != "fp8":
             raise ValueError("kv_scales need kv_dtype='fp8' (--kv-dtype fp8): a bf16 KV cache has no scales")
         if model is None:
@@ -454,13 +468,16 @@ class Engine:
         w8 = getattr(model, "weight_dtype", "bf16") != "bf16"  # multiplied by the fused HIP step alone
         windowed = bool(getattr(getattr(model, "cfg", None), "windowed", False))  # attended by the fused HIP step alone
         for on, what in ((penalties, "penalties need"), (fp8, "an fp8 KV cache needs"), (w8, "fp8 weights need"),
-                         (guided, "guided decoding needs"), (windowed, "a sliding window needs")):
+                         (guided, "guided decoding needs"), (windowed, "a sliding window needs"),
+                         (min_p, "min_p needs")):
             if on and not use_graph:
                 raise ValueError(f"{what} the graph-captured HIP step; this engine runs eagerly")
         self.penalties = bool(penalties)
         self.guided = bool(guided)
         self._held = None  # a guided request that waits for room in the arena (the head of the admission queue)
-        in_rows = _PEN.stop if self.penalties else _IN_ROWS
+        self.min_p = bool(min_p)
+        self._smp, self._lp, self._pen_rows = _layout(self.min_p)
+        in_rows = self._pen_rows.stop if self.penalties else self._lp + 1
         self._bufs = {R: [_StepBuf(R, cuda, lp_dev, in_rows), _StepBuf(R, cuda, lp_dev, in_rows)] for R in sizes}
         self._d_in = {R: torch.zeros((in_rows, R), dtype=torch.int64, device=self.device) for R in sizes}
         cfg = model.cfg
@@ -514,6 +531,8 @@ class Engine:
                              "graph-captured HIP step")
         if req.penalties is not None and any(t >= self.model.cfg.vocab for t in req.penalties.logit_bias):
             raise ValueError(f"logit_bias ids must be in [0, {self.model.cfg.vocab})")
+        if req.sampling.min_p > 0.0 and not self.min_p:
+            raise ValueError("min_p needs an engine built with min_p=True (--min-p) on the graph-captured HIP step")
         if req.guide is not None:
             if self._gd is None:
                 raise ValueError("a guide needs an engine built with guided=True (--guided) on the graph-captured "
@@ -709,14 +728,14 @@ class Engine:
             drawn = logits[:sample_rows]
             if penalize:
                 drawn = ops.penalize_(drawn, self._work[b.rows], ids[:sample_rows], tok[:sample_rows], din[_DEC],
-                                      din[_SLOT], din[_PEN], self._pen.state, self._pen.bias_n, self._pen.bias_ids,
+                                      din[_SLOT], din[self._pen_rows], self._pen.state, self._pen.bias_n, self._pen.bias_ids,
                                       self._pen.bias_val)
             if guide:
                 drawn = ops.guide_(drawn, self._work[b.rows], ids[:sample_rows], tok[:sample_rows], din[_DEC],
                                    din[_SLOT], self._gd.base, self._gd.cur, self._gd.arena)
-            ops.sample_(drawn, ids[:sample_rows], din[_SMP])
+            (ops.sample_minp_ if self.min_p else ops.sample_)(drawn, ids[:sample_rows], din[self._smp])
             if logprobs:
-                ops.logprobs_(logits[:sample_rows], ids[:sample_rows], din[_LP], b.d_lp[:sample_rows],
+                ops.logprobs_(logits[:sample_rows], ids[:sample_rows], din[self._lp], b.d_lp[:sample_rows],
                               b.d_lp_ids[:sample_rows])
                 b.h_lp.copy_(b.d_lp, non_blocking=True)
                 b.h_lp_ids.copy_(b.d_lp_ids, non_blocking=True)
@@ -749,21 +768,22 @@ class Engine:
         h[_SLOT, :n] = [r.slot for r in rows]
         h[_DEC, :n] = [r.decode for r in rows]
         h[_REC, :n] = [r.slot if r.emit else scratch for r in rows]
-        h[_SMP, :] = 0  # greedy unless an emitting row samples
-        h[_LP, :] = 0  # no logprobs unless an emitting row's request asks
+        smp, lp = self._smp, self._lp
+        h[smp, :] = 0  # greedy unless an emitting row samples
+        h[lp, :] = 0  # no logprobs unless an emitting row's request asks
         need = 0  # the stages this step's emitting rows need: its post is the lowest that runs them all
         for r, req, _, ctr in emits:
             if not req.sampling.greedy:
-                h[_SMP, r] = req.sampling.column(ctr)
+                h[smp, r] = req.sampling.column(ctr, self.min_p)
                 need |= _SAMPLE
             if req.logprobs is not None:
-                h[_LP, r] = 1 + req.logprobs
+                h[lp, r] = 1 + req.logprobs
                 need |= _LOGPROBS
         if self._pen is not None:
-            h[_PEN, :] = 0  # every row off unless its request has penalties
+            h[self._pen_rows, :] = 0  # every row off unless its request has penalties
             for r, req, _, _ in emits:
                 if req.penalties is not None:
-                    h[_PEN, r] = req.penalties.column()
+                    h[self._pen_rows, r] = req.penalties.column()
                     need |= _PENALIZE
         if self._gd is not None and any(req.guide is not None for _, req, _, _ in emits):
             need |= _GUIDE

@@ -10,22 +10,31 @@ class Sampling:
     """How a request picks its tokens: temperature (0 = greedy argmax, the
     fused LM head's own result), then top-k (0 = off) and top-p (1 = off),
     drawn on device by ``ops.sample_`` (sample.hip) from a per-request seed
-    and the token's index, so a fixed seed replays the same completion."""
-    __slots__ = ("temperature", "top_k", "top_p", "seed")
+    and the token's index, so a fixed seed replays the same completion.
+    ``min_p`` (0 = off; an engine built with ``min_p=True``, docs/MIN_P.md)
+    then drops every token less likely than min_p times the most likely one
+    (``ops.sample_minp_``)."""
+    __slots__ = ("temperature", "top_k", "top_p", "seed", "min_p")
 
-    def __init__(self, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int | None = None):
+    def __init__(self, temperature: float = 0.0, top_k: int = 0, top_p: float = 1.0, seed: int | None = None,
+                 min_p: float = 0.0):
         self.temperature = float(temperature)
         self.top_k = int(top_k)
         self.top_p = float(top_p)
         self.seed = int.from_bytes(os.urandom(8), "little") >> 1 if seed is None else int(seed) & ((1 << 63) - 1)
+        if isinstance(min_p, bool) or not isinstance(min_p, (int, float)) or not 0.0 <= min_p <= 1.0:
+            raise ValueError(f"min_p must be a number in [0, 1], got {min_p!r}")
+        self.min_p = float(min_p)
 
     @property
     def greedy(self) -> bool:
         return not self.temperature >= 1e-4 or self.top_k == 1  # the kernel's own greedy rule (+ top-1)
 
-    def column(self, counter: int) -> list[int]:
+    def column(self, counter: int, min_p: bool = False) -> list[int]:
+        """The sampler's params column: five values, or six for an engine built with ``min_p=True``."""
         from p2p_llm_tunnel_amd.ops import pack_sampling
-        return pack_sampling(0.0 if self.greedy else self.temperature, self.top_k, self.top_p, self.seed, counter)
+        return pack_sampling(0.0 if self.greedy else self.temperature, self.top_k, self.top_p, self.seed, counter,
+                             self.min_p if min_p else None)
 
 
 class Penalties:
@@ -150,7 +159,7 @@ def penalty_params(body: dict, ollama: bool, vocab: int | None = None) -> Penalt
 
 
 def sampling_params(body: dict, ollama: bool, default_temperature: float = 0.0, penalties: bool = False,
-                    vocab: int | None = None) -> Sampling:
+                    vocab: int | None = None, min_p: bool = False) -> Sampling:
     """Sampling of an OpenAI request (top-level temperature / top_p / seed, and
     the common top_k extension) or an Ollama one ("options"). Raises
     SamplingError for values out of range or parameters not implemented,
@@ -160,13 +169,21 @@ def sampling_params(body: dict, ollama: bool, default_temperature: float = 0.0, 
     ``penalties`` (a server started with --penalties; ``vocab``: the model's):
     the penalty parameters and logit_bias are then checked by
     ``penalty_params`` — whose result the caller takes from there — instead of
-    being refused unless neutral; everything else is as without the switch."""
+    being refused unless neutral; everything else is as without the switch.
+
+    ``min_p`` (a server started with --min-p): Ollama's "options.min_p" and
+    the top-level "min_p" of an OpenAI request (vLLM's extension) are taken, a
+    number in [0, 1], 0 = off. Without the switch an Ollama value other than 0
+    is refused like the other unimplemented options, and the OpenAI key, which
+    is no part of that API, is not looked at."""
     src = body.get("options", {}) if ollama else body
     if src is None:
         src = {}
     if not isinstance(src, dict):
         raise SamplingError("options must be an object")
     taken = () if not penalties else _OLLAMA_PENALTY_KEYS if ollama else _OPENAI_PENALTY_KEYS
+    if min_p:
+        taken += ("min_p",)
     for key, neutral in (_OLLAMA_NEUTRAL if ollama else _OPENAI_NEUTRAL).items():
         if key in taken:
             continue
@@ -179,7 +196,7 @@ def sampling_params(body: dict, ollama: bool, default_temperature: float = 0.0, 
     top_p = _number(src, "top_p", 0.0, 1.0, 1.0, lo_open=True)
     top_k = _number(src, "top_k", 0, 1 << 30, 0, integer=True)
     seed = _number(src, "seed", -(1 << 63), (1 << 64) - 1, None, integer=True)
-    return Sampling(t, top_k, top_p, seed)
+    return Sampling(t, top_k, top_p, seed, _number(src, "min_p", 0.0, 1.0, 0.0) if min_p else 0.0)
 
 
 _GUIDE_KEYS = ("guided_regex", "guided_choice", "structured_outputs")

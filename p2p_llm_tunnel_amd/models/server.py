@@ -20,6 +20,7 @@ profiles/bench_gpu_upstream_r01.json.)
   POST /v1/chat/completions  (SSE when "stream": true; JSON otherwise)
   POST /v1/completions       (same, "prompt" instead of "messages")
   POST /api/generate         (Ollama NDJSON stream)
+  POST /api/chat             (Ollama chat: NDJSON stream, or one JSON object; see "Ollama chat" below)
   POST /v1/embeddings, /api/embed, /api/embeddings  (see "Embeddings" below)
 
 Sampling: temperature / top_p / seed (and the common top_k extension) from an
@@ -31,8 +32,30 @@ to 4; Ollama "options.stop") end a completion at the first match in the
 detokenised text, which is left out (finish_reason "stop"); a streamed
 response holds back only a tail that could still begin one. Parameters that
 would change the output and are not implemented (n > 1, penalties,
-logit_bias, Ollama's repeat_penalty, mirostat, ...) are answered
+logit_bias, Ollama's repeat_penalty, min_p, mirostat, ...) are answered
 with 400, as is sampling on an engine without the captured HIP step.
+
+min_p (--min-p, off by default: Ollama's "options.min_p" other than 0 is then
+answered with 400 and a top-level "min_p" of an OpenAI request, which that API
+does not have, is not looked at): Ollama "options.min_p" and the vLLM extension
+"min_p" on the OpenAI routes, a number in [0, 1]. Tokens less likely than min_p
+times the most likely one are dropped after top-k and top-p (HF's order), on
+device inside the captured step (ops.sample_minp_, sample.hip). See
+docs/MIN_P.md.
+
+Ollama chat: /api/chat takes "model", "messages" ("role" system / user /
+assistant, string "content"), "stream" (default true), "options" (the sampling
+options, "num_predict" and "stop" of /api/generate) and "keep_alive", which is
+ignored. The messages go through the chat template of /v1/chat/completions. A
+streamed response is NDJSON, one {"model", "created_at", "message": {"role":
+"assistant", "content": piece}, "done": false} per token batch from a byte
+template rendered once per request (so "created_at" is the request's), then a
+final object with an empty content, "done": true, "done_reason" ("stop" or
+"length"), "prompt_eval_count", "eval_count" and "total_duration",
+"prompt_eval_duration" (up to the first token) and "eval_duration" in ns; a
+non-streamed one is that final object with the whole content. Non-empty
+"tools" or "format", "images" on a message, a content that is no string, an
+unknown role and an empty "messages" are answered with 400.
 
 Penalties (--penalties, off by default: the 400s above stand): OpenAI
 "presence_penalty", "frequency_penalty", "logit_bias" and the vLLM extension
@@ -42,8 +65,8 @@ on device inside the captured step, ahead of the sampler (ops.penalize_,
 penalty.hip; the arithmetic: ``params.Penalties``). The repetition penalty has
 HF / vLLM semantics — every id seen in the prompt or generated, NOT Ollama's
 window of the last 64 tokens: "repeat_last_n" is accepted only as -1, or 0 =
-repeat penalty off. n > 1, best_of, mirostat, tfs_z, typical_p and min_p stay
-refused. See docs/PENALTIES.md.
+repeat penalty off. n > 1, best_of, mirostat, tfs_z and typical_p stay
+refused (min_p too, unless --min-p). See docs/PENALTIES.md.
 
 Guided decoding (--guided, off by default: the keys below are then not acted
 on): /v1/chat/completions and /v1/completions take "guided_regex" (the whole
@@ -145,6 +168,34 @@ def chat_template_kwargs(body: dict) -> dict | None:
     return kw
 
 
+_OLLAMA_ROLES = ("system", "user", "assistant")
+
+
+def ollama_chat_body(body: dict) -> None:
+    """What /api/chat refuses of a request body, beside its sampling options:
+    raises SamplingError (answered with 400) naming the field. "messages" is a
+    non-empty list of objects with a "role" of system, user or assistant and a
+    string "content"; "images" on a message, non-empty "tools" and a non-empty
+    "format" (tool calls, vision and JSON output are not served) are refused,
+    not ignored."""
+    if body.get("tools"):
+        raise SamplingError("tools are not supported by this server")
+    if body.get("format"):
+        raise SamplingError(f"format={body['format']!r} is not supported by this server")
+    msgs = body.get("messages")
+    if not isinstance(msgs, list) or not msgs:
+        raise SamplingError("messages must be a non-empty list")
+    for n, m in enumerate(msgs):
+        if not isinstance(m, dict):
+            raise SamplingError(f"messages[{n}] must be an object")
+        if m.get("role") not in _OLLAMA_ROLES:
+            raise SamplingError(f"messages[{n}].role must be one of {list(_OLLAMA_ROLES)}, got {m.get('role')!r}")
+        if m.get("images"):
+            raise SamplingError(f"messages[{n}].images is not supported by this server")
+        if not isinstance(m.get("content"), str):
+            raise SamplingError(f"messages[{n}].content must be a string, got {m.get('content')!r}")
+
+
 def _prompt_ids(body: dict, tok=None, template_kwargs: dict | None = None) -> list[int]:
     msgs = body.get("messages")
     if tok is not None:
@@ -174,14 +225,18 @@ class _Stream:
     template around each token piece (token ids render as " t<id>": no JSON
     escaping needed)."""
     __slots__ = ("writer", "stream", "kind", "rid", "pre", "post", "toks", "done", "detok", "reason", "stop",
-                 "stop_hit", "lp_toks", "lp_off")
+                 "stop_hit", "lp_toks", "lp_off", "t0", "t_first", "created", "n_tok")
 
     def __init__(self, writer, stream, kind, rid, model, detok=None, stop=None, logprobs=False):
+        self.t0 = time.perf_counter_ns()  # /api/chat's durations: the request's start, and its first token's arrival
+        self.t_first = 0
+        self.n_tok = 0  # tokens taken from the engine (the EOS token or a matched stop's included)
+        self.created = None  # /api/chat: "created_at", one per request
         self.lp_toks = [] if logprobs else None  # with logprobs: the delivered ids; Request.lp[k] belongs to the k-th
         self.lp_off = 0  # legacy completions, streamed: text_offset of the next token
         self.writer = writer
         self.stream = stream
-        self.kind = kind  # "chat" | "text" | "ollama"
+        self.kind = kind  # "chat" | "text" | "ollama" (/api/generate) | "ollama_chat" (/api/chat)
         self.rid = rid
         self.toks = []  # non-streamed: rendered pieces (bytes, JSON-escaped when detokenised)
         self.detok = detok  # checkpoint tokenizer: incremental text of this request
@@ -198,6 +253,12 @@ class _Stream:
             self.pre = ('data: {"id": "%s", "object": "text_completion", "model": %s, "choices": '
                         '[{"index": 0, "text": "' % (rid, m)).encode()
             self.post = b'", "finish_reason": null}]}\n\n'
+        elif kind == "ollama_chat":
+            now = time.time()
+            self.created = time.strftime("%Y-%m-%dT%H:%M:%S", time.gmtime(now)) + ".%06dZ" % (now % 1 * 1e6)
+            self.pre = ('{"model": %s, "created_at": "%s", "message": {"role": "assistant", "content": "'
+                        % (m, self.created)).encode()
+            self.post = b'"}, "done": false}\n'
         else:
             self.pre = ('{"model": %s, "response": "' % m).encode()
             self.post = b'", "done": false}\n'
@@ -306,9 +367,12 @@ class FrontEnd:
                 req.cancelled = True
                 st.done.set_result(False)
                 continue
+            if not st.t_first:
+                st.t_first = time.perf_counter_ns()
             if tok is None:
                 self._finish(req, st)
                 continue
+            st.n_tok += 1
             if tok in self.eos:  # stop: the engine frees the slot on its next step
                 req.cancelled = True
                 st.reason = "stop"
@@ -378,6 +442,15 @@ class FrontEnd:
         else:
             st.toks.append(body)
 
+    def _ollama_chat_final(self, req, st, content: str) -> dict:
+        """The last object of an /api/chat response (the only one when it is not streamed)."""
+        now = time.perf_counter_ns()
+        first = st.t_first or now
+        return {"model": self.model_name, "created_at": st.created,
+                "message": {"role": "assistant", "content": content}, "done": True, "done_reason": st.reason,
+                "total_duration": now - st.t0, "prompt_eval_count": len(req.prompt),
+                "prompt_eval_duration": first - st.t0, "eval_count": st.n_tok, "eval_duration": now - first}
+
     def _finish(self, req, st):
         w = st.writer
         if st.stop is not None and not st.stop_hit:
@@ -390,6 +463,8 @@ class FrontEnd:
         if st.stream:
             if st.kind == "ollama":
                 tail = _chunk((json.dumps({"model": self.model_name, "response": "", "done": True}) + "\n").encode())
+            elif st.kind == "ollama_chat":
+                tail = _chunk((json.dumps(self._ollama_chat_final(req, st, "")) + "\n").encode())
             else:
                 fin = {"index": 0, "delta": {}, "finish_reason": st.reason} if st.kind == "chat" else \
                     {"index": 0, "text": "", "finish_reason": st.reason}
@@ -401,6 +476,8 @@ class FrontEnd:
             text = json.loads(b'"' + b"".join(st.toks) + b'"')
             if st.kind == "ollama":
                 obj = {"model": self.model_name, "response": text, "done": True}
+            elif st.kind == "ollama_chat":
+                obj = self._ollama_chat_final(req, st, text)
             elif st.kind == "chat":
                 obj = {"id": st.rid, "object": "chat.completion", "model": self.model_name,
                        "choices": [{"index": 0, "message": {"role": "assistant", "content": text},
@@ -627,7 +704,7 @@ class FrontEnd:
         if method == "POST" and path in _EMBED_PATHS:
             return await self._embeddings(path, body, writer, reader)
         if method != "POST" or path not in ("/v1/chat/completions", "/chat/completions", "/v1/completions",
-                                            "/api/generate"):
+                                            "/api/generate", "/api/chat"):
             writer.write(self._json_response({"error": "not found"}, 404))
             return True
         try:
@@ -637,23 +714,34 @@ class FrontEnd:
         except ValueError:
             req_body = {}
         raw_max = req_body.get("max_tokens", req_body.get("num_predict", 16))
+        if path == "/api/chat":
+            try:
+                ollama_chat_body(req_body)
+            except SamplingError as e:
+                writer.write(self._json_response({"error": {"message": str(e), "type": "invalid_request_error"}}, 400))
+                return True
+            opts = req_body.get("options")
+            if isinstance(opts, dict) and opts.get("num_predict") is not None:  # where Ollama's clients put it
+                raw_max = opts["num_predict"]
         try:
             max_new = int(raw_max if raw_max is not None else 16)
         except (TypeError, ValueError):
             writer.write(self._json_response({"error": f"max_tokens must be an integer, got {raw_max!r}"}, 400))
             return True
-        ollama = path == "/api/generate"
-        kind = "ollama" if ollama else ("chat" if "chat" in path else "text")
+        ollama = path in ("/api/generate", "/api/chat")
+        kind = ("ollama_chat" if path == "/api/chat" else "ollama") if ollama else \
+            ("chat" if "chat" in path else "text")
         try:
             # Logprobs first; sampling_params refuses both keys, so the OpenAI
             # endpoints hand it the body without them.
-            logprobs = logprob_params(req_body, kind)
+            logprobs = logprob_params(req_body, "ollama" if ollama else kind)
             if logprobs is not None and not self.engine.use_graph:
                 raise SamplingError("logprobs need the graph-captured HIP step; this engine runs eagerly")
             rest = req_body if ollama else {k: v for k, v in req_body.items() if k not in _LOGPROB_KEYS}
             pen_on = getattr(self.engine, "penalties", False)
             sampling = sampling_params(rest, ollama, self.default_temperature, penalties=pen_on,
-                                       vocab=self.engine.model.cfg.vocab)
+                                       vocab=self.engine.model.cfg.vocab,
+                                       min_p=getattr(self.engine, "min_p", False))
             penalties = penalty_params(rest, ollama, self.engine.model.cfg.vocab) if pen_on else None
             stops = stop_sequences(req_body, ollama)
             template_kwargs = chat_template_kwargs(req_body)
@@ -694,7 +782,7 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
                  tokenizer=None, default_temperature: float = 0.0, prefix_cache: bool = False, prefix_min: int = 16,
                  embed_pooling: str = "mean", penalties: bool = False, kv_dtype: str = "bf16",
                  guided: bool = False, guided_states: int = 1024, weight_dtype: str = "bf16", kv_scales=None,
-                 sliding_window: bool = False):
+                 sliding_window: bool = False, min_p: bool = False):
     """Engine + HTTP front-end; returns (server, port, engine). ``server.shutdown()``
     stops the HTTP side, ``engine.stop()`` the GPU side. ``checkpoint``: serve a
     Hugging Face Llama checkpoint directory (weights + tokenizer) instead of
@@ -715,7 +803,12 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
     FP8 cache (docs/KV_FP8.md); an injected engine's model must carry the same.
     ``sliding_window``: serve the checkpoint's sliding attention window instead of capping the context at it
     (``load_llama``, docs/SLIDING_WINDOW.md); it needs a checkpoint that declares one, or an injected engine whose
-    model has windowed layers."""
+    model has windowed layers.
+    ``min_p`` is ``Engine``'s: the endpoint then takes Ollama's "options.min_p" and a top-level "min_p" on the OpenAI
+    routes (``sampling_params``, docs/MIN_P.md) instead of refusing the first and ignoring the second; an injected
+    engine must have been built with it."""
+    if engine is not None and min_p and not getattr(engine, "min_p", False):
+        raise ValueError("min_p=True, but the injected engine was built without it")
     if sliding_window and engine is None and not checkpoint:
         raise ValueError("sliding_window=True (--sliding-window) needs a checkpoint that declares a sliding window")
     if sliding_window and engine is not None and not getattr(getattr(engine.model, "cfg", None), "windowed", False):
@@ -749,11 +842,13 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
                            weight_dtype=weight_dtype, kv_scales=kv_scales, sliding_window=sliding_window)
         tok = tok or Tokenizer.for_checkpoint(checkpoint)
         engine = Engine(device=device, max_batch=max_batch, model=model, prefix_cache=prefix_cache,
-                        prefix_min=prefix_min, penalties=penalties, guided=guided, guided_states=guided_states)
+                        prefix_min=prefix_min, penalties=penalties, guided=guided, guided_states=guided_states,
+                        min_p=min_p)
         model_name = model_name or os.path.basename(os.path.normpath(checkpoint))
     engine = engine or Engine(device=device, config=config, max_batch=max_batch, prefix_cache=prefix_cache,
                               prefix_min=prefix_min, penalties=penalties, kv_dtype=kv_dtype, guided=guided,
-                              guided_states=guided_states, weight_dtype=weight_dtype, kv_scales=kv_scales)
+                              guided_states=guided_states, weight_dtype=weight_dtype, kv_scales=kv_scales,
+                              min_p=min_p)
     srv = FrontEnd(engine, host, port, model_name or f"p2pt-{config}", tokenizer=tok,
                    default_temperature=default_temperature, embed_pooling=embed_pooling)
     return srv, srv.server_address[1], engine
@@ -798,6 +893,13 @@ def kv_cache_line(model, kv_dtype: str) -> str:
             + (f"; scales in use: {scales.describe()}" if scales is not None else ""))
 
 
+def min_p_line(engine) -> str:
+    """The start-up log line of ``--min-p``."""
+    if getattr(engine, "min_p", False):
+        return "min_p: on (options.min_p and min_p are applied on the device after top-k and top-p)"
+    return "min_p: off (options.min_p other than 0 is answered with 400; start with --min-p)"
+
+
 def window_line(model) -> str:
     """The start-up log line of ``--sliding-window``: the window, how many layers have one, and the context."""
     cfg = model.cfg
@@ -831,6 +933,8 @@ def replica_cmd(a, i: int) -> list[str]:
         cmd += ["--weight-dtype", a.weight_dtype]
     if getattr(a, "sliding_window", False):
         cmd += ["--sliding-window"]
+    if getattr(a, "min_p", False):
+        cmd += ["--min-p"]
     return cmd
 
 
@@ -914,6 +1018,11 @@ def arg_parser() -> argparse.ArgumentParser:
                          "attend to their last sliding_window tokens and the context follows --max-seq / "
                          "max_position_embeddings. Needs --checkpoint; one that declares no window is refused "
                          "(docs/SLIDING_WINDOW.md)")
+    ap.add_argument("--min-p", action="store_true",
+                    help="take min_p (Ollama options.min_p; a top-level min_p on the OpenAI routes, vLLM's extension) "
+                         "instead of answering 400 / ignoring it: tokens less likely than min_p times the most likely "
+                         "one are dropped on the device after top-k and top-p. Costs one more staged row per step; "
+                         "the number of captured graphs stays (docs/MIN_P.md)")
     ap.add_argument("--guided", action="store_true",
                     help="guided decoding on the device: /v1/chat/completions and /v1/completions act on "
                          "guided_regex, guided_choice and structured_outputs {regex | choice} (a checkpoint with a "
@@ -938,11 +1047,12 @@ def main(argv=None):
                                      prefix_cache=a.prefix_cache, prefix_min=a.prefix_min,
                                      embed_pooling=a.embed_pooling, penalties=a.penalties, kv_dtype=a.kv_dtype,
                                      guided=a.guided, guided_states=a.guided_states, weight_dtype=a.weight_dtype,
-                                     kv_scales=a.kv_scales, sliding_window=a.sliding_window)
+                                     kv_scales=a.kv_scales, sliding_window=a.sliding_window, min_p=a.min_p)
     print(weights_line(engine.model, a.weight_dtype), flush=True)
     print(kv_cache_line(engine.model, a.kv_dtype), flush=True)
     if a.sliding_window:
         print(window_line(engine.model), flush=True)
+    print(min_p_line(engine), flush=True)
     print(f"inference endpoint on http://{a.host}:{port} ({a.checkpoint or a.config}, {a.device})", flush=True)
     try:
         threading.Event().wait()

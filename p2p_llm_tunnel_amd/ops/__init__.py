@@ -87,6 +87,7 @@ def _signatures() -> dict:
         "p2pt_argmax": [vp, vp, i, i, vp],
         "p2pt_skinny_gemm": [vp, vp, vp, i, i, i, vp],
         "p2pt_sample": [vp, vp, vp, i, i, i, vp],
+        "p2pt_sample_minp": [vp, vp, vp, i, i, i, vp],
         "p2pt_logprobs": [vp, vp, vp, vp, vp, i, i, vp],
         "p2pt_kv_copy": [vp, vp, i, i, i, i, i, ip, vp],
         "p2pt_max_kv_copy_jobs": [],
@@ -539,15 +540,31 @@ def sample_(logits: torch.Tensor, ids: torch.Tensor, params: torch.Tensor) -> to
     keep the id already there. ``params``: int64 [5, >= B] (contiguous; column
     b for row b) — float32 bits of T, top_k (<= 0 off), float32 bits of top_p
     (>= 1 off), seed, counter (see ``pack_sampling``)."""
+    return _sample(logits, ids, params, 5)
+
+
+def sample_minp_(logits: torch.Tensor, ids: torch.Tensor, params: torch.Tensor) -> torch.Tensor:
+    """``sample_`` with a min_p cut after top-k and top-p (sample.hip's
+    ``MINP`` instantiation): ``params`` is int64 [6, >= B], rows 0..4 as
+    ``sample_`` takes them and row 5 the float32 bits of ln(min_p) (-inf: off;
+    see ``pack_sampling``'s ``min_p``). With z = logits / T and m its row
+    maximum, a token stays iff z >= fl32(m + ln(min_p)), i.e. iff its
+    probability is at least min_p times the most likely token's."""
+    return _sample(logits, ids, params, 6)
+
+
+def _sample(logits, ids, params, n_params: int):
+    """The checks and the launch of ``sample_`` (5 params rows) and ``sample_minp_`` (6)."""
     _check(logits, torch.bfloat16, "logits")
     _check(ids, torch.int64, "ids", logits.device)
     _check(params, torch.int64, "params", logits.device)
-    if logits.dim() != 2 or ids.shape != (logits.shape[0],) or params.dim() != 2 or params.shape[0] != 5:
-        raise ValueError("need logits [B, V], ids [B], params [5, >= B]")
+    if logits.dim() != 2 or ids.shape != (logits.shape[0],) or params.dim() != 2 or params.shape[0] != n_params:
+        raise ValueError(f"need logits [B, V], ids [B], params [{n_params}, >= B]")
     B, V = logits.shape
     if params.shape[1] < B:
         raise ValueError("params need a column per row")
-    _ok(lib().p2pt_sample(_p(logits), _p(ids), _p(params), B, params.shape[1], V, _stream(logits)), "sample")
+    fn = lib().p2pt_sample if n_params == 5 else lib().p2pt_sample_minp
+    _ok(fn(_p(logits), _p(ids), _p(params), B, params.shape[1], V, _stream(logits)), "sample")
     return ids
 
 
@@ -874,10 +891,22 @@ def f32_bits(x: float) -> int:
     return struct.unpack("<I", struct.pack("<f", float(x)))[0]
 
 
-def pack_sampling(temperature: float, top_k: int, top_p: float, seed: int, counter: int) -> list[int]:
-    """One params column for ``sample_``."""
-    return [f32_bits(temperature), int(top_k), f32_bits(top_p), int(seed) & 0x7FFFFFFFFFFFFFFF,
-            int(counter) & 0x7FFFFFFFFFFFFFFF]
+def ln_min_p(min_p: float) -> float:
+    """ln(min_p) as ``sample_minp_`` takes it: computed in float64 (the caller rounds it to float32 once, in
+    ``f32_bits``); 0 maps to -inf, which switches the cut off. ``min_p`` outside [0, 1] (NaN and bools included)
+    raises."""
+    if isinstance(min_p, bool) or not isinstance(min_p, (int, float)) or not 0.0 <= min_p <= 1.0:
+        raise ValueError(f"min_p must be a number in [0, 1], got {min_p!r}")
+    return math.log(min_p) if min_p > 0.0 else -math.inf
+
+
+def pack_sampling(temperature: float, top_k: int, top_p: float, seed: int, counter: int,
+                  min_p: float | None = None) -> list[int]:
+    """One params column for ``sample_``; with ``min_p`` (a number in [0, 1], 0 = off) the six values of a
+    ``sample_minp_`` column: the float32 bits of ln(min_p) follow."""
+    col = [f32_bits(temperature), int(top_k), f32_bits(top_p), int(seed) & 0x7FFFFFFFFFFFFFFF,
+           int(counter) & 0x7FFFFFFFFFFFFFFF]
+    return col if min_p is None else col + [f32_bits(ln_min_p(min_p))]
 
 
 def skinny_gemm(x: torch.Tensor, w: torch.Tensor) -> torch.Tensor:

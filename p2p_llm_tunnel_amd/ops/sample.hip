@@ -20,6 +20,21 @@
 // params: int64 [5, ld] — float32 bits of T, top_k (<= 0: off), float32 bits
 // of top_p (>= 1: off), seed, counter (the request's token index, so each
 // draw of a request uses fresh noise and a fixed seed replays the same text).
+//
+//   p2pt_sample_minp   the same kernel's MINP instantiation, params int64
+//     [6, ld]: row 5 holds the float32 bits of ln(min_p), computed on the host
+//     in fp64 and rounded once (-inf: off), so the device takes no
+//     transcendental at this cut:
+//     min_p: t = m + ln(min_p), one fp32 add on the block maximum m of z that
+//            the kernel already holds                     -> keep z >= t
+//     (a token whose z equals t is kept, as at the other cuts). The final cut
+//     is max(top-k, top-p, min_p): HF's order, temperature, top-k, top-p, then
+//     min_p. p_i / p_max = exp(z_i - m) does not depend on the set the softmax
+//     is normalised over, so after top-k and top-p the min_p filter is exactly
+//     this threshold; the top-p mass is taken over the top-k set as without
+//     min_p, not narrowed by it. One add and one key per row: no pass over the
+//     logits and no LDS beyond p2pt_sample's. p2pt_sample launches the
+//     MINP = false instantiation, whose code the flag does not touch.
 // The block reductions, the radix select's bucket scan (find_bucket) and the
 // argmax tail of the draw are row_common.h's.
 #include "row_common.h"
@@ -51,6 +66,7 @@ __device__ __forceinline__ float gumbel(uint64_t seed, uint64_t ctr, uint32_t i)
   return float(-log(-log(u)));
 }
 
+template <bool MINP>
 __global__ __launch_bounds__(kThreads) void k_sample(const uint16_t* __restrict__ logits, int64_t* __restrict__ ids,
                                                      const int64_t* __restrict__ params, int ld, int V) {
   const int row = blockIdx.x;
@@ -128,7 +144,14 @@ __global__ __launch_bounds__(kThreads) void k_sample(const uint16_t* __restrict_
     }
     pth = prefix;
   }
-  const uint32_t cut = kth > pth ? kth : pth;
+  uint32_t cut = kth > pth ? kth : pth;
+  if constexpr (MINP) {
+    const float lnp = __uint_as_float(uint32_t(params[5 * B + row]));
+    if (lnp != -INFINITY) {  // -inf: off (the cut stays what it is without min_p)
+      const uint32_t mth = okey(m + lnp);
+      cut = cut > mth ? cut : mth;
+    }
+  }
 
   // ---- Gumbel-max over the kept set
   float best = -INFINITY;
@@ -151,7 +174,15 @@ extern "C" {
 // logits: bf16 [B, V] rows contiguous.
 int p2pt_sample(const void* logits, int64_t* ids, const int64_t* params, int B, int ld, int V, void* stream) {
   if (B <= 0 || V <= 0 || ld < B) return int(hipErrorInvalidValue);
-  hipLaunchKernelGGL(k_sample, dim3(B), dim3(kThreads), 0, static_cast<hipStream_t>(stream),
+  hipLaunchKernelGGL(k_sample<false>, dim3(B), dim3(kThreads), 0, static_cast<hipStream_t>(stream),
+                     static_cast<const uint16_t*>(logits), ids, params, ld, V);
+  return int(hipGetLastError());
+}
+
+// As p2pt_sample with params: int64 [6, ld], whose row 5 holds the float32 bits of ln(min_p) (-inf: off).
+int p2pt_sample_minp(const void* logits, int64_t* ids, const int64_t* params, int B, int ld, int V, void* stream) {
+  if (B <= 0 || V <= 0 || ld < B) return int(hipErrorInvalidValue);
+  hipLaunchKernelGGL(k_sample<true>, dim3(B), dim3(kThreads), 0, static_cast<hipStream_t>(stream),
                      static_cast<const uint16_t*>(logits), ids, params, ld, V);
   return int(hipGetLastError());
 }
