@@ -219,9 +219,10 @@ def load_llama(path: str, device="cuda", max_batch: int = 8, max_seq: int | None
     cache's format (``TinyLlama``), for every family alike. ``kv_scales`` ("fp8" only): None (scale 1: ``k_scale`` /
     ``v_scale`` tensors a checkpoint may carry are then not read), a ``KvScales``, or "checkpoint": the per-layer
     ``self_attn.k_scale`` / ``.v_scale`` (or ``kv_scale``) tensors of the checkpoint, each a scalar broadcast over
-    the layer's KV heads; a checkpoint that lacks them for any layer is refused. ``weight_dtype``: "bf16" or "fp8" (docs/WEIGHT_FP8.md): each
+    the layer's KV heads; a checkpoint that lacks them for any layer is refused. ``weight_dtype``: "bf16", "fp8"
+    (docs/WEIGHT_FP8.md) or "mxfp4" (docs/WEIGHT_MXFP4.md: the layers' GEMM weights as MXFP4, the LM head as FP8): each
     layer's GEMM weights are quantised on ``device`` as soon as the layer is read and its bf16 tensors dropped, so
-    the device never holds the bf16 and the FP8 copies of all layers together. The checkpoint itself is bf16 / fp16
+    the device never holds the bf16 and the quantised copies of all layers together. The checkpoint itself is bf16 / fp16
     / fp32 either way: one that is already quantised on disk is treated as before. ``sliding_window``: serve the
     checkpoint's sliding attention window (``read_config``, docs/SLIDING_WINDOW.md), fused step only; a checkpoint
     that declares none is refused."""
@@ -292,8 +293,8 @@ def load_llama(path: str, device="cuda", max_batch: int = 8, max_seq: int | None
                                  f"{(raw.get('architectures') or ['LlamaForCausalLM'])[0]!r} applies no QK-norm: refusing "
                                  "to load it without them")
             del q, k, v, gate, up
-            if weight_dtype == "fp8":  # this layer's bf16 GEMM weights give way to e4m3 + scales before the next is read
-                quantize_layer_(c, w["layers"][-1])
+            if weight_dtype != "bf16":  # this layer's bf16 GEMM weights give way to the quantised ones before the next is read
+                quantize_layer_(c, w["layers"][-1], weight_dtype)
     finally:
         rd.close()
     return TinyLlama.from_weights(cfg, w, device=dev, max_batch=max_batch, fused=fused, kv_dtype=kv_dtype,

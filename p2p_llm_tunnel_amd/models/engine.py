@@ -467,7 +467,7 @@ class Engine:
         fp8 = getattr(model, "kv_dtype", "bf16") != "bf16"  # read and written by the fused HIP step alone
         w8 = getattr(model, "weight_dtype", "bf16") != "bf16"  # multiplied by the fused HIP step alone
         windowed = bool(getattr(getattr(model, "cfg", None), "windowed", False))  # attended by the fused HIP step alone
-        for on, what in ((penalties, "penalties need"), (fp8, "an fp8 KV cache needs"), (w8, "fp8 weights need"),
+        for on, what in ((penalties, "penalties need"), (fp8, "an fp8 KV cache needs"), (w8, f"{getattr(model, 'weight_dtype', 'bf16')} weights need"),
                          (guided, "guided decoding needs"), (windowed, "a sliding window needs"),
                          (min_p, "min_p needs")):
             if on and not use_graph:

@@ -796,8 +796,8 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
     With ``penalties`` the endpoint takes the parameters ``penalty_params``
     describes instead of answering 400; with ``guided`` /v1/chat/completions and
     /v1/completions act on what ``guided_params`` describes, which is ignored
-    without the switch. ``weight_dtype`` ("bf16" or "fp8", the format of the GEMM weights:
-    docs/WEIGHT_FP8.md) is ``Engine``'s and ``load_llama``'s, and an injected engine's model must have it.
+    without the switch. ``weight_dtype`` ("bf16", "fp8" or "mxfp4", the format of the GEMM weights:
+    docs/WEIGHT_FP8.md, docs/WEIGHT_MXFP4.md) is ``Engine``'s and ``load_llama``'s, and an injected engine's model must have it.
     ``kv_scales`` (``kv_dtype="fp8"`` only): a ``KvScales``, the path of a JSON file ``{"k": [[..]], "v": [[..]]}``
     or "checkpoint" (the checkpoint's own ``k_scale`` / ``v_scale`` tensors): per-layer, per-KV-head scales of the
     FP8 cache (docs/KV_FP8.md); an injected engine's model must carry the same.
@@ -864,11 +864,11 @@ def parse_kv_dtype(v) -> str:
     return v
 
 
-WEIGHT_DTYPE_CHOICES = ("bf16", "fp8")
+WEIGHT_DTYPE_CHOICES = ("bf16", "fp8", "mxfp4")
 
 
 def parse_weight_dtype(v) -> str:
-    """--weight-dtype / ``start_server(weight_dtype=)``: "bf16" (the default) or "fp8"; anything else is refused."""
+    """--weight-dtype / ``start_server(weight_dtype=)``: "bf16" (the default), "fp8" or "mxfp4"; anything else is refused."""
     if v not in WEIGHT_DTYPE_CHOICES:
         raise ValueError(f"weight_dtype must be one of {list(WEIGHT_DTYPE_CHOICES)}, got {v!r}")
     return v
@@ -1011,7 +1011,9 @@ def arg_parser() -> argparse.ArgumentParser:
                     help="format of the GEMM weights (QKV, O, gate/up, down and the LM head): bf16, or fp8 (OCP e4m3 "
                          "with one fp32 scale per output row, per-row absmax, no calibration; the activations stay "
                          "bf16): half the weight bytes per decode step; the embedding table stays bf16 "
-                         "(docs/WEIGHT_FP8.md)")
+                         "(docs/WEIGHT_FP8.md); or mxfp4 (OCP Microscaling FP4 for the four GEMM weights of every "
+                         "layer: e2m1 values in blocks of 32 with a power-of-two scale, round to nearest, no "
+                         "calibration; the LM head is fp8): about a quarter of their bytes (docs/WEIGHT_MXFP4.md)")
     ap.add_argument("--sliding-window", action="store_true",
                     help="serve the checkpoint's sliding attention window (Mistral-7B-v0.1 and its fine-tunes; Qwen2 / "
                          "Qwen3 with use_sliding_window) instead of capping the context at it: the layers that slide "

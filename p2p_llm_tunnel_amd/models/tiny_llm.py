@@ -84,7 +84,8 @@ CONFIGS = {
 
 
 KV_DTYPES = {"bf16": torch.bfloat16, "fp8": torch.float8_e4m3fn}  # TinyLlama(kv_dtype=): the caches' dtype
-WEIGHT_DTYPES = ("bf16", "fp8")  # TinyLlama(weight_dtype=): the format of the five GEMM weights
+# TinyLlama(weight_dtype=): the format of the GEMM weights. "mxfp4": a layer's four as MXFP4, the LM head as FP8.
+WEIGHT_DTYPES = ("bf16", "fp8", "mxfp4")
 GEMM_WEIGHTS = ops.LAYER_GEMMS  # a layer's GEMM weights, in the order of their scales
 FOLDED_NORM = {"wqkv": "attn_norm", "w_gate_up": "ffn_norm", "lm_head": "final_norm"}  # GEMM: the norm in its columns
 
@@ -106,29 +107,45 @@ def fused_row_perm(cfg: "LlamaConfig", name: str, device) -> torch.Tensor | None
     return None
 
 
-def quantize_gemm_weight(w: torch.Tensor, g: torch.Tensor | None, perm: torch.Tensor | None):
+def quantize_gemm_weight(w: torch.Tensor, g: torch.Tensor | None, perm: torch.Tensor | None,
+                         weight_dtype: str = "fp8"):
     """A GEMM weight as the fused table holds it, W'[n][k] = w[perm[n]][k] * g[k] with the fold in fp32, quantised
-    from that fp32 value (``ops.quantize_weight_fp8``), not through bf16: ``(q, scale)`` in the table's row order."""
+    from that fp32 value (``ops.quantize_weight_fp8``, or ``ops.quantize_weight_mxfp4`` for ``weight_dtype`` "mxfp4"),
+    not through bf16: ``(q, scale)`` in the table's row order."""
     wf = w.float()
     if g is not None:
         wf = wf * g.float()[None, :]
     if perm is not None:
         wf = wf[perm]
-    return ops.quantize_weight_fp8(wf.contiguous())
+    quantize = ops.quantize_weight_mxfp4 if weight_dtype == "mxfp4" else ops.quantize_weight_fp8
+    return quantize(wf.contiguous())
 
 
-def quantize_layer_(cfg: "LlamaConfig", L: dict) -> dict:
-    """One layer's four GEMM weights to FP8 in place: ``L[name]`` (bf16) gives way to ``L[name + "_q"]`` (e4m3,
-    folded and interleaved as the fused table wants it) and ``L[name + "_s"]`` (fp32 row scales). The loader calls
-    it layer by layer, so the bf16 and FP8 copies of all layers are never resident together."""
+def layer_weight_dtype(L: dict) -> str:
+    """The format of a layer's GEMM weights, read off its tensors: "bf16", or what ``quantize_layer_`` made of them
+    ("fp8": fp32 row scales; "mxfp4": e8m0 block-scale bytes)."""
+    s = next((L[n + "_s"] for n in GEMM_WEIGHTS if n + "_s" in L), None)
+    return "bf16" if s is None else "mxfp4" if s.dtype == torch.uint8 else "fp8"
+
+
+def quantize_layer_(cfg: "LlamaConfig", L: dict, weight_dtype: str = "fp8") -> dict:
+    """One layer's four GEMM weights to FP8 (or, ``weight_dtype`` "mxfp4", to MXFP4) in place: ``L[name]`` (bf16)
+    gives way to ``L[name + "_q"]`` (e4m3, or MXFP4 nibble bytes; folded and interleaved as the fused table wants
+    it) and ``L[name + "_s"]`` (fp32 row scales, or e8m0 block-scale bytes). The loader calls it layer by layer, so
+    the bf16 and quantised copies of all layers are never resident together."""
     for name in GEMM_WEIGHTS:
         if name + "_q" in L:
             continue
         w = L.pop(name)
         L[name + "_q"], L[name + "_s"] = quantize_gemm_weight(w, L.get(FOLDED_NORM.get(name)),
-                                                              fused_row_perm(cfg, name, w.device))
+                                                              fused_row_perm(cfg, name, w.device), weight_dtype)
         del w
     return L
+
+
+def dequantize_gemm_weight(q: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
+    """``(q, s)`` of ``quantize_gemm_weight`` back in fp32, whichever format made them."""
+    return ops.dequantize_weight_mxfp4(q, s) if s.dtype == torch.uint8 else ops.dequantize_weight_fp8(q, s)
 
 
 def llama_dims(cfg: "LlamaConfig", max_batch: int, kv_fp8: bool = False) -> ops.LlamaDims:
@@ -176,6 +193,8 @@ class TinyLlama:
         one fp32 scale per output row (docs/WEIGHT_FP8.md), quantised here layer by layer (the bf16 tensor of each
         is dropped as it goes; ``weights`` may bring layers ``quantize_layer_`` has already seen). Only the fused
         step reads them. The embedding stays bf16, so a tied model keeps it and gets an FP8 copy for the LM head.
+        "mxfp4": a layer's four GEMM weights as OCP Microscaling FP4 (e2m1 nibbles, one e8m0 scale byte per block of
+        32; docs/WEIGHT_MXFP4.md) and the LM head in the FP8 format above.
 
         Random-init weights from ``seed``, or ``weights`` (embed, final_norm,
         lm_head, layers[{attn_norm, wqkv, wo, ffn_norm, w_gate_up, w_down}, plus
@@ -259,11 +278,14 @@ class TinyLlama:
     def _quantize_weights(self):
         """``weight_dtype`` "fp8": every layer's GEMM weights and the LM head to e4m3 + row scales, one tensor at
         a time. The bf16 LM head is dropped unless it is the embedding itself (a tied model)."""
-        if self.weight_dtype != "fp8":
-            if any(n + "_q" in L for L in self.layers for n in GEMM_WEIGHTS):
-                raise ValueError("the weights hold FP8 layers: pass weight_dtype='fp8'")
+        for L in self.layers:
+            have = layer_weight_dtype(L)
+            if have != "bf16" and have != self.weight_dtype:
+                raise ValueError(f"the weights hold {'FP8' if have == 'fp8' else 'MXFP4'} layers: "
+                                 f"pass weight_dtype='{have}'")
+        if self.weight_dtype == "bf16":
             return
-        self.layers = [quantize_layer_(self.cfg, dict(L)) for L in self.layers]
+        self.layers = [quantize_layer_(self.cfg, dict(L), self.weight_dtype) for L in self.layers]
         self.lm_head_q, self.lm_head_s = quantize_gemm_weight(self.lm_head, self.final_norm, None)
         self.lm_head = None
 
@@ -279,7 +301,7 @@ class TinyLlama:
                     gemm += nb(t)
                 else:
                     other += nb(t)
-        if self.weight_dtype == "fp8":
+        if self.weight_dtype != "bf16":
             gemm += nb(self.lm_head_q) + nb(self.lm_head_s)
         elif self.lm_head is not self.embed and self.lm_head.data_ptr() != self.embed.data_ptr():
             gemm += nb(self.lm_head)
@@ -369,8 +391,9 @@ class TinyLlama:
         # touches only wqkv). A model with scaled RoPE carries its frequency table (fp32)
         # as a fourth global entry, between lm_head and the layers.
         # With FP8 weights the five GEMM weights are e4m3 bytes, quantised after the fold and the
-        # interleave (_quantize_weights), and their row scales follow the table.
-        fp8 = self.weight_dtype == "fp8"
+        # interleave (_quantize_weights), and their row scales follow the table. With MXFP4 weights a layer's four
+        # are nibble bytes and their scales the blocks' e8m0 bytes; the LM head is the FP8 one.
+        fp8 = self.weight_dtype != "bf16"
         top = {"embed": self.embed, "final_norm": self.final_norm, "lm_head": self.lm_head,
                "lm_head_q": self.lm_head_q, "lm_head_s": self.lm_head_s, "inv_freq": self.rope_inv_freq()}
 
@@ -386,7 +409,7 @@ class TinyLlama:
             perm = fused_row_perm(c, name, self.device)
             return w[perm].contiguous() if perm is not None else w.contiguous() if name.endswith("_norm") else w
 
-        return [entry(e.name, e.layer) for e in ops.WeightTable(self.dims(), fp8)]
+        return [entry(e.name, e.layer) for e in ops.WeightTable(self.dims(), weight_format=self.weight_dtype)]
 
     def dims(self) -> ops.LlamaDims:
         """The fused step's dims of this model: one cache slot per sequence and the scratch slot."""
@@ -395,7 +418,7 @@ class TinyLlama:
     def fused_decoder(self) -> ops.FusedLlamaDecoder:
         if self._fused is None:
             self._fused = ops.FusedLlamaDecoder(self.dims(), self.fused_weights(), self.k_cache, self.v_cache,
-                                                weight_fp8=self.weight_dtype == "fp8",
+                                                weight_format=self.weight_dtype,
                                                 kv_scales=(self.kv_scales.table(self.device)
                                                            if self.kv_scales is not None else None),
                                                 windows=self.cfg.windows if self.cfg.windowed else None)
@@ -503,12 +526,12 @@ class TinyLlama:
         multiplies it. bf16 weights: the tensor itself. FP8 weights: the dequantised ``q * s`` (the function the
         kernels compute; the quantisation error against the original is a separate quantity), which carries the
         preceding norm's weight folded in, so the reference then norms with a weight of one (``_ref_norm``)."""
-        if self.weight_dtype != "fp8":
+        if self.weight_dtype == "bf16":
             return (self.lm_head if layer is None else self.layers[layer][name]).float()
         if layer is None:
             return ops.dequantize_weight_fp8(self.lm_head_q, self.lm_head_s)
         L = self.layers[layer]
-        w = ops.dequantize_weight_fp8(L[name + "_q"], L[name + "_s"])
+        w = dequantize_gemm_weight(L[name + "_q"], L[name + "_s"])
         perm = fused_row_perm(self.cfg, name, w.device)
         if perm is not None:
             w = w[torch.argsort(perm)]
@@ -516,7 +539,7 @@ class TinyLlama:
 
     def _ref_norm(self, g: torch.Tensor) -> torch.Tensor:
         """The weight the reference's RMSNorm ahead of a folded GEMM applies: g, or one where g is in the weight."""
-        return torch.ones_like(g) if self.weight_dtype == "fp8" else g
+        return torch.ones_like(g) if self.weight_dtype != "bf16" else g
 
     @torch.no_grad()
     def reference_hidden(self, seqs: torch.Tensor, kv_round=None) -> torch.Tensor:

@@ -66,6 +66,39 @@ class WeightPlan(ctypes.Structure):
     _fields_ = [("w8", _INT)]
 
 
+class WeightFormat(ctypes.Structure):
+    """Mirror of ``WeightFormat``: the weight formats of a step, beside its ``StepPlan`` as ``WeightPlan`` is, and what
+    the ``_fmt`` entry points take. ``layers``: the format of a layer's four GEMM weights (wqkv, wo, w_gate_up,
+    w_down); ``lm_head``: the LM head's. 0 bf16, 1 FP8 (docs/WEIGHT_FP8.md), 2 MXFP4 (docs/WEIGHT_MXFP4.md: the layers
+    only, with an FP8 LM head). The supported pairs are ``WEIGHT_FORMATS``' values."""
+    _fields_ = [("layers", _INT), ("lm_head", _INT)]
+
+    def __repr__(self):
+        return f"WeightFormat(layers={self.layers}, lm_head={self.lm_head})"
+
+
+WEIGHT_FORMATS = {"bf16": (0, 0), "fp8": (1, 1), "mxfp4": (2, 1)}  # weight dtype -> (layers, lm_head) of WeightFormat
+
+
+def as_weight_format(weight_fp8: bool = False, weight_format=None) -> WeightFormat:
+    """The ``WeightFormat`` a caller means: ``weight_format`` (a ``WeightFormat``, or one of "bf16", "fp8", "mxfp4")
+    where given, else FP8 throughout for ``weight_fp8`` and bf16 without. Both at once, an unknown name or a pair of
+    formats the step does not run are refused (host only: no library)."""
+    if weight_format is None:
+        return WeightFormat(*WEIGHT_FORMATS["fp8" if weight_fp8 else "bf16"])
+    if weight_fp8:
+        raise ValueError("give weight_fp8 or weight_format, not both")
+    if isinstance(weight_format, str):
+        if weight_format not in WEIGHT_FORMATS:
+            raise ValueError(f"weight_format must be one of {sorted(WEIGHT_FORMATS)}, got {weight_format!r}")
+        return WeightFormat(*WEIGHT_FORMATS[weight_format])
+    if not isinstance(weight_format, WeightFormat) or \
+            (weight_format.layers, weight_format.lm_head) not in WEIGHT_FORMATS.values():
+        raise ValueError(f"weight_format must be a WeightFormat of (layers, lm_head) in "
+                         f"{sorted(WEIGHT_FORMATS.values())} or one of {sorted(WEIGHT_FORMATS)}, got {weight_format!r}")
+    return WeightFormat(weight_format.layers, weight_format.lm_head)
+
+
 class WindowPlan(ctypes.Structure):
     """Mirror of ``WindowPlan``: what one layer's sliding window changes of a step, beside its ``StepPlan`` as
     ``KvPlan`` and ``WeightPlan`` are (docs/SLIDING_WINDOW.md). ``win``: 1 for ``k_attn<D, G, KV8, true>``;
@@ -77,7 +110,7 @@ class WindowPlan(ctypes.Structure):
 def _signatures() -> dict:
     """Every symbol ``lib()`` binds -> its argtypes. The restype is ``c_int`` unless ``_RESTYPES`` names another."""
     vp, i, f, sz, ptr = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.POINTER
-    dims, wp, ip, szp = ptr(LlamaDims), ptr(WeightPlan), ptr(i), ptr(sz)
+    dims, wp, ip, szp, wf = ptr(LlamaDims), ptr(WeightPlan), ptr(i), ptr(sz), ptr(WeightFormat)
     return {
         "p2pt_rmsnorm": [vp, vp, vp, vp, vp, i, i, f, vp],
         "p2pt_silu_mul": [vp, vp, i, i, vp],
@@ -112,6 +145,10 @@ def _signatures() -> dict:
         "p2pt_llama_window_plan": [dims, i, i, ptr(WindowPlan)],
         "p2pt_llama_plan_kernels_win": [dims, i, i, wp, ip],
         "p2pt_llama_decode_win": [dims, wp, vp, ip, ptr(vp), vp, vp, vp, vp, vp, i, i, vp, sz, vp, vp, vp],
+        "p2pt_llama_weight_format": [dims, i, i, wf],
+        "p2pt_llama_plan_kernels_fmt": [dims, i, i, wf, ip],
+        "p2pt_llama_weight_layout_fmt": [dims, wf, ip, ip, i],
+        "p2pt_llama_decode_fmt": [dims, wf, vp, ip, ptr(vp), vp, vp, vp, vp, vp, i, i, vp, sz, vp, vp, vp],
         "p2pt_attn_span": [i, i],
         "p2pt_max_rows": [],
         "p2pt_skinny_bench": [vp, vp, vp, i, i, i, i, i, i, vp],  # microbenchmark hooks (scripts/bench_skinny.py)
@@ -156,6 +193,9 @@ KV_FP8_DTYPES = (torch.float8_e4m3fn, torch.uint8)  # cache dtypes of a decoder 
 WEIGHT_FP8_DTYPES = KV_FP8_DTYPES  # GEMM-weight dtypes of a decoder with weight_fp8 (the same bytes)
 GEMM_OPERAND_LIMIT = 1 << 31  # bytes: every k_skinny operand stays below it (decode_fused_kernels.h's kOob)
 E4M3_MAX = 448.0  # the largest finite e4m3fn value: a row's largest magnitude quantises to it
+MXFP4_BLOCK = 32  # K elements per MXFP4 block: one e8m0 scale byte each (one k-step of k_skinny)
+MXFP4_EXP_MIN, MXFP4_EXP_MAX = 2, 252  # the e8m0 bytes quantize_weight_mxfp4 emits (its docstring derives them)
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)  # the magnitudes of an e2m1 nibble's low three bits; bit 3: sign
 MAX_TOP_LOGPROBS = 20  # top (id, logprob) pairs per row of logprobs_ (logprobs.hip's kMaxTop; the OpenAI API's limit)
 
 
@@ -176,9 +216,16 @@ def kv_plan(dims: LlamaDims) -> KvPlan:
     return plan
 
 
-def weight_plan(dims: LlamaDims, weight_fp8: bool = False) -> WeightPlan:
+def weight_plan(dims: LlamaDims, weight_fp8: bool = False, weight_format=None):
     """The weight format ``p2pt_llama_decode_w`` launches for (host only): ``w8`` 1 with FP8 weights, 0 without.
-    ``step_plan(dims, B)`` is the same either way: the format changes no grid, wave count or load batch."""
+    ``step_plan(dims, B)`` is the same either way: the format changes no grid, wave count or load batch.
+    With ``weight_format`` (see ``as_weight_format``) the answer is the library's ``WeightFormat`` instead, which an
+    MXFP4 model needs: its layers and its LM head differ."""
+    if weight_format is not None:
+        f, out = as_weight_format(weight_fp8, weight_format), WeightFormat()
+        if lib().p2pt_llama_weight_format(ctypes.byref(dims), f.layers, f.lm_head, ctypes.byref(out)) != 0:
+            raise ValueError("dims not supported by the fused decode kernels")
+        return out
     plan = WeightPlan()
     if lib().p2pt_llama_weight_plan(ctypes.byref(dims), int(bool(weight_fp8)), ctypes.byref(plan)) != 0:
         raise ValueError("dims not supported by the fused decode kernels")
@@ -210,13 +257,18 @@ def window_plan(dims: LlamaDims, B: int, window: int) -> WindowPlan:
     return plan
 
 
-def plan_kernels_ok(dims: LlamaDims, B: int, emit_rows: int = 0, weight_fp8: bool = False, windows=None) -> bool:
+def plan_kernels_ok(dims: LlamaDims, B: int, emit_rows: int = 0, weight_fp8: bool = False, windows=None,
+                    weight_format=None) -> bool:
     """Whether every stage of ``step_plan(dims, B, emit_rows)``, ``kv_plan(dims)`` and
     ``weight_plan(dims, weight_fp8)`` names a kernel the library instantiates, by the lookups its launchers use
     (host only). ``windows``: the per-layer sliding windows (``check_windows``); every layer's ``window_plan`` is
-    then looked up too."""
+    then looked up too. ``weight_format`` (see ``as_weight_format``): the formats instead of ``weight_fp8``."""
     windows = check_windows(windows, dims.n_layers)
-    if windows is not None:
+    if weight_format is not None:
+        f = as_weight_format(weight_fp8, weight_format)
+        rc = lib().p2pt_llama_plan_kernels_fmt(ctypes.byref(dims), B, emit_rows, ctypes.byref(f),
+                                               (ctypes.c_int * len(windows))(*windows) if windows is not None else None)
+    elif windows is not None:
         wp = WeightPlan(w8=int(bool(weight_fp8)))
         rc = lib().p2pt_llama_plan_kernels_win(ctypes.byref(dims), B, emit_rows, ctypes.byref(wp),
                                                (ctypes.c_int * len(windows))(*windows))
@@ -243,26 +295,44 @@ class WeightTable(list):
     attn_norm, wqkv, wo, ffn_norm, w_gate_up, w_down, plus q_norm, k_norm with ``dims.qk_norm`` or bqkv with
     ``dims.qkv_bias``. With ``weight_fp8`` the five GEMM weights are e4m3 (or uint8) bytes, 8-byte aligned (a lane
     loads 8 bytes at a multiple of 8 from the base), and their fp32 row scales follow the table: lm_head's, then
-    each layer's four, named ``"<weight> scale"``."""
+    each layer's four, named ``"<weight> scale"``.
 
-    def __init__(self, dims: LlamaDims, weight_fp8: bool = False):
-        d, bf, f32 = dims, (torch.bfloat16,), (torch.float32,)
-        gemm, ga = (WEIGHT_FP8_DTYPES, 8) if weight_fp8 else (bf, 2)
+    ``weight_format`` (``as_weight_format``) in place of ``weight_fp8``; "mxfp4" (docs/WEIGHT_MXFP4.md) is the FP8
+    table with each layer's four GEMM weights as uint8 ``(N, K / 2)`` and, where the FP8 table has their row scales,
+    their e8m0 block scales, uint8 ``(N, K / 32)``: byte ``[n][b]`` is the scale of elements ``32 b .. 32 b + 31`` of
+    row n. The physical byte order of an MXFP4 row is the natural one, stated here once: byte ``[n][j]`` holds
+    elements ``k = 2 j`` (low nibble, bits 0..3) and ``k = 2 j + 1`` (high nibble), rows in the row order of the
+    weight. A lane of ``k_skinny<.., W8 = 2>`` loads its 8 k-values of a k-step as the 4 bytes at
+    ``n K / 2 + 16 s + 4 (lane >> 4)`` and the block's scale as the byte at ``n K / 32 + s``, so a weight is 4-byte
+    aligned and its scales need no alignment. ``pack_weight_mxfp4`` makes this order from nibble codes ``[N][K]``,
+    ``unpack_weight_mxfp4`` undoes it, and decode_fused.hip's accessor and the kernel's offsets mirror it."""
+
+    def __init__(self, dims: LlamaDims, weight_fp8: bool = False, weight_format=None):
+        self.format = fmt = as_weight_format(weight_fp8, weight_format)
+        d, bf, f32, u8 = dims, (torch.bfloat16,), (torch.float32,), (torch.uint8,)
+        gemm, ga = (WEIGHT_FP8_DTYPES, 8) if fmt.lm_head else (bf, 2)
         n_qkv, norm = (d.H + 2 * d.Hkv) * d.D, (bf, (d.dim,), 2)
         top = {"embed": (bf, (d.vocab, d.dim), 2), "final_norm": norm, "lm_head": (gemm, (d.vocab, d.dim), ga)}
         if d.rope_table:
             top["inv_freq"] = (f32, (d.D // 2,), 8)
-        layer = {"attn_norm": norm, "wqkv": (gemm, (n_qkv, d.dim), ga), "wo": (gemm, (d.dim, d.H * d.D), ga),
-                 "ffn_norm": norm, "w_gate_up": (gemm, (2 * d.ffn, d.dim), ga), "w_down": (gemm, (d.dim, d.ffn), ga)}
+        shapes = {"wqkv": (n_qkv, d.dim), "wo": (d.dim, d.H * d.D), "w_gate_up": (2 * d.ffn, d.dim),
+                  "w_down": (d.dim, d.ffn)}
+        if fmt.layers == 2:  # nibbles, two to a byte
+            lg = {n: (u8, (N, K // 2), 4) for n, (N, K) in shapes.items()}
+        else:
+            lg = {n: (gemm, shape, ga) for n, shape in shapes.items()}
+        layer = {"attn_norm": norm, "wqkv": lg["wqkv"], "wo": lg["wo"], "ffn_norm": norm, "w_gate_up": lg["w_gate_up"],
+                 "w_down": lg["w_down"]}
         if d.qk_norm:
             layer.update(q_norm=(bf, (d.D,), 2), k_norm=(bf, (d.D,), 2))
         elif d.qkv_bias:
             layer["bqkv"] = (bf, (n_qkv,), 2)
         groups = [(None, top)] + [(L, layer) for L in range(d.n_layers)]
         super().__init__(WeightEntry(n, L, *v) for L, group in groups for n, v in group.items())
-        if weight_fp8:
-            self += [WeightEntry(n + " scale", L, f32, v[1][:1], 4) for L, group in groups for n, v in group.items()
-                     if v[0] is gemm]
+        if fmt.lm_head:  # the scales, in the order of their weights: fp32 per row, or MXFP4's e8m0 byte per block
+            self += [WeightEntry(n + " scale", L, u8, (shapes[n][0], shapes[n][1] // MXFP4_BLOCK), 1)
+                     if L is not None and fmt.layers == 2 else WeightEntry(n + " scale", L, f32, v[1][:1], 4)
+                     for L, group in groups for n, v in group.items() if n == "lm_head" or n in LAYER_GEMMS]
         self.per_layer = len(layer)
         self._at = {(e.name, e.layer): i for i, e in enumerate(self)}
 
@@ -273,7 +343,8 @@ class WeightTable(list):
         return self._at[name, layer]
 
     def scale_index(self, name: str, layer: int | None = None) -> int:
-        """Where the fp32 row scales of GEMM weight ``name`` sit (FP8 tables only)."""
+        """Where the scales of GEMM weight ``name`` sit (FP8 and MXFP4 tables only): fp32 row scales, or the e8m0
+        block scales of an MXFP4 weight."""
         return self.index(name + " scale", layer)
 
 
@@ -956,6 +1027,82 @@ def dequantize_weight_fp8(q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
     return q.float() * scale.float()[:, None]
 
 
+def _check_mxfp4_input(w):
+    if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or w.dim() != 2 or w.shape[1] % MXFP4_BLOCK:
+        raise TypeError(f"quantize_weight_mxfp4 takes an fp32 [N, K] tensor with K a multiple of {MXFP4_BLOCK} (fold and "
+                        "quantise in fp32, not through bf16)")
+    if not bool(torch.isfinite(w).all()):
+        raise ValueError("non-finite weight (NaN or inf): refusing to quantise it to MXFP4")
+
+
+def pack_weight_mxfp4(codes: torch.Tensor) -> torch.Tensor:
+    """Nibble codes ``[N][K]`` (uint8, 0..15: bit 3 the sign, bits 0..2 the index into ``E2M1_VALUES``) to the bytes
+    ``[N][K / 2]`` the kernel loads, in the physical order ``WeightTable`` states: byte j of a row holds element 2 j in
+    its low nibble and element 2 j + 1 in its high nibble. The one function that makes that order."""
+    if not isinstance(codes, torch.Tensor) or codes.dtype != torch.uint8 or codes.dim() != 2 or codes.shape[1] % 2:
+        raise TypeError("pack_weight_mxfp4 takes uint8 nibble codes [N, K] with K even")
+    if codes.numel() and int(codes.max()) > 15:
+        raise ValueError("a nibble code is 0..15")
+    return (codes[:, 0::2] | (codes[:, 1::2] << 4)).contiguous()
+
+
+def unpack_weight_mxfp4(packed: torch.Tensor) -> torch.Tensor:
+    """The inverse of ``pack_weight_mxfp4``: bytes ``[N][K / 2]`` to nibble codes ``[N][K]``."""
+    if not isinstance(packed, torch.Tensor) or packed.dtype != torch.uint8 or packed.dim() != 2:
+        raise TypeError("unpack_weight_mxfp4 takes uint8 bytes [N, K / 2]")
+    return torch.stack([packed & 15, packed >> 4], 2).reshape(packed.shape[0], -1).contiguous()
+
+
+def quantize_weight_mxfp4(w: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """One GEMM weight ``w`` (fp32 [N, K], K a multiple of 32, as it sits in the fused table: folded and interleaved)
+    to OCP Microscaling MXFP4 (docs/WEIGHT_MXFP4.md): ``(bytes, scales)``, uint8 ``[N][K / 2]`` in
+    ``pack_weight_mxfp4``'s order and uint8 ``[N][K / 32]``. Plain torch on ``w``'s device: runs without a GPU.
+
+    Blocks are 32 consecutive elements of a row. A block's scale byte E (e8m0: the scale is 2^(E - 127)) is
+    ``E - 127 = floor(log2(amax)) - 2`` of the block's largest magnitude, so amax / 2^(E - 127) lies in [4, 8) and
+    the largest e2m1 magnitude, 6 = 1.5 * 2^2, shares amax's binade. E is clamped to [2, 252], the range in which
+    every decoded value is a normal bf16 number: the smallest non-zero one is 0.5 * 2^(E - 127) >= 2^-126 (bf16's
+    smallest normal) iff E >= 2, and the largest, 6 * 2^(E - 127) < 2^(E - 124), is below 2^128 iff E <= 252. The
+    upper end binds for no fp32 input (amax < 2^128 gives E <= 252 by the rule itself); the lower one holds blocks
+    with amax < 2^-123 at E = 2, where their elements round towards zero like any small element. 255 (e8m0's NaN) is
+    never emitted. An all-zero block (-0.0 included) gets E = 127 and zero nibbles.
+
+    An element is x / 2^(E - 127) (exact in fp32: a power-of-two factor, and the quotient of anything that does not
+    round to zero is normal) rounded to the nearest e2m1 magnitude {0, 0.5, 1, 1.5, 2, 3, 4, 6}, ties to the even
+    mantissa (0.25 -> 0, 0.75 -> 1, 1.25 -> 1, 1.75 -> 2, 2.5 -> 2, 3.5 -> 4, 5 -> 4), saturating at 6, with the sign
+    in bit 3; what rounds to zero is the nibble 0, never 8.
+
+    Error, per element, with s = 2^(E - 127) and y = |x| / s < 8: |dequant - x| <= s / 4 for y <= 2 (steps of 0.5),
+    s / 2 for y <= 4 (steps of 1), s for y <= 6 (steps of 2), and y - 6 < 2 in units of s above 6, where the value
+    saturates: the top binade is the worst case, and |dequant - x| < 2 s <= amax / 2 in every block whose E the lower
+    clamp did not raise (s <= amax / 4 there; a block held at E = 2 has y <= 2 and so the s / 4 bound, 2^-127).
+    Non-finite weights are refused."""
+    _check_mxfp4_input(w)
+    N, K = w.shape
+    blocks = w.reshape(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = blocks.abs().amax(2)
+    _, e = torch.frexp(amax)  # amax = m 2^e with m in [0.5, 1): floor(log2(amax)) = e - 1, subnormals included
+    E = torch.where(amax > 0, (e - 3 + 127).clamp(MXFP4_EXP_MIN, MXFP4_EXP_MAX), torch.full_like(e, 127))
+    y = torch.ldexp(blocks, (127 - E)[:, :, None].to(torch.int32)).abs()
+    code = ((y > 0.25).to(torch.uint8) + (y >= 0.75) + (y > 1.25) + (y >= 1.75) + (y > 2.5) + (y >= 3.5) + (y > 5.0))
+    code = code.to(torch.uint8)
+    code = code | (((blocks < 0) & (code > 0)).to(torch.uint8) << 3)
+    return pack_weight_mxfp4(code.reshape(N, K)), E.to(torch.uint8).contiguous()
+
+
+def dequantize_weight_mxfp4(packed: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """``e2m1(nibble) * 2^(E - 127)`` in fp32 ``[N][K]``: the weight the MXFP4 kernels compute with. Exact, and for
+    the scales ``quantize_weight_mxfp4`` emits every value is a bf16 number, so ``.to(torch.bfloat16)`` is exact too."""
+    codes = unpack_weight_mxfp4(packed)
+    N, K = codes.shape
+    if not isinstance(scales, torch.Tensor) or scales.dtype != torch.uint8 or \
+            tuple(scales.shape) != (N, K // MXFP4_BLOCK) or K % MXFP4_BLOCK:
+        raise TypeError(f"scales must be uint8 [N, K / {MXFP4_BLOCK}] e8m0 bytes of the weight's blocks")
+    mag = torch.tensor(E2M1_VALUES, dtype=torch.float32, device=codes.device)[(codes & 7).long()]
+    val = torch.where((codes & 8) != 0, -mag, mag).reshape(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    return torch.ldexp(val, (scales.to(torch.int32) - 127)[:, :, None]).reshape(N, K)
+
+
 class FusedLlamaDecoder:
     """Host handle for the fused decode step (decode_fused.hip): 5 kernels per layer + 3
     (6 per layer with ``dims.qk_norm``: the per-head q/k RMSNorm of Qwen3 runs in a kernel of its own;
@@ -965,7 +1112,10 @@ class FusedLlamaDecoder:
     e4m3 byte per element at scale 1 (or with ``kv_scales``, below), written by the _KV8 epilogues / ``k_qknorm_rope`` variant and read by
     ``k_attn<D, G, true>``: the same kernel count again).
 
-    ``weights`` is laid out as ``WeightTable(dims, weight_fp8)`` says, and every entry is checked against it.
+    ``weights`` is laid out as ``WeightTable(dims, weight_fp8, weight_format)`` says, and every entry is checked
+    against it. ``weight_format`` (``as_weight_format``: a ``WeightFormat`` or "bf16", "fp8", "mxfp4") in place of
+    ``weight_fp8``; "mxfp4" (docs/WEIGHT_MXFP4.md, ``quantize_weight_mxfp4``) has each layer's four GEMM weights as
+    MXFP4 bytes with e8m0 block scales, run by the ``k_skinny<.., W8 = 2>`` instantiations, and an FP8 LM head.
     ``weight_fp8``: the five GEMM weights as OCP e4m3 bytes with one fp32 scale per output row, each (N,) in the
     row order of its weight (docs/WEIGHT_FP8.md, ``quantize_weight_fp8``). Every ``k_skinny`` is then its FP8-weight
     instantiation; the kernel count, ``step_plan`` and the workspace are the same.
@@ -988,11 +1138,12 @@ class FusedLlamaDecoder:
     """
 
     def __init__(self, dims: LlamaDims, weights: list, k_cache: torch.Tensor, v_cache: torch.Tensor,
-                 weight_fp8: bool = False, kv_scales: torch.Tensor | None = None, windows=None):
+                 weight_fp8: bool = False, kv_scales: torch.Tensor | None = None, windows=None, weight_format=None):
         self.dims = dims
         self.windows = check_windows(windows, dims.n_layers)
         self._windows = (ctypes.c_int * dims.n_layers)(*self.windows) if self.windows is not None else None
-        self.weight_fp8 = bool(weight_fp8)
+        self.weight_format = fmt = as_weight_format(weight_fp8, weight_format)
+        self.weight_fp8 = fmt.layers == 1  # FP8 throughout
         self._wplan = WeightPlan(w8=int(self.weight_fp8))
         dev = k_cache.device
         # The cache dtype against dims.kv_fp8 first (a host-only check): a mismatch would have every kernel read
@@ -1015,7 +1166,7 @@ class FusedLlamaDecoder:
                 raise ValueError(f"kv_scales must be fp32 [4, {dims.n_layers}, {dims.Hkv}] (1 / k, 1 / v, k, v per layer "
                                  f"and KV head), got {getattr(kv_scales, 'dtype', type(kv_scales))} "
                                  f"{tuple(getattr(kv_scales, 'shape', ()))}")
-        self.table = table = WeightTable(dims, self.weight_fp8)
+        self.table = table = WeightTable(dims, weight_format=fmt)
         if len(weights) != len(table):
             raise ValueError(f"weight table: embed, final_norm, lm_head, "
                              + ("inv_freq, " if dims.rope_table else "") + f"then {table.per_layer} per layer "
@@ -1023,7 +1174,9 @@ class FusedLlamaDecoder:
                              + ("; q_norm and k_norm last)" if dims.qk_norm else
                                 "; bqkv last)" if dims.qkv_bias else ")")
                              + ("; weight_fp8: then the fp32 row scales, lm_head's and four per layer"
-                                if self.weight_fp8 else ""))
+                                if self.weight_fp8 else "")
+                             + ("; mxfp4: then lm_head's fp32 row scales and four e8m0 block-scale tensors per layer"
+                                if fmt.layers == 2 else ""))
         # Every entry's dtype and shape, from the description alone: a refusal here needs no device. A weight shorter
         # than dims says would be read past its end (k_skinny sizes its descriptors from dims, k_embed indexes vocab
         # rows). The norm slots the kernels do not read are held to (dim,) too.
@@ -1031,6 +1184,10 @@ class FusedLlamaDecoder:
             name = label(e.name, e.layer)
             if not isinstance(t, torch.Tensor) or t.dtype not in e.dtypes:
                 got = getattr(t, "dtype", type(t))
+                if fmt.layers == 2 and e.dtypes == (torch.uint8,):
+                    raise TypeError(f"{name}: the weight format is mxfp4, so "
+                                    + ("the block scales must be e8m0 bytes (torch.uint8)" if e.name.endswith(" scale")
+                                       else "the weight must be nibble bytes (torch.uint8)") + f", got {got}")
                 if len(e.dtypes) > 1:
                     raise TypeError(f"{name}: weight_fp8 is set, so the weight must be torch.float8_e4m3fn (or uint8), "
                                     f"got {got}")
@@ -1039,17 +1196,23 @@ class FusedLlamaDecoder:
                 raise TypeError(f"{name}: expected {e.dtypes[0]}, got {got}")
             if tuple(t.shape) != e.shape:
                 raise ValueError(f"{name} has shape {tuple(t.shape)}, not {e.shape}"
-                                 + (": one fp32 scale per output row" if e.name.endswith(" scale") else ""))
+                                 + ("" if not e.name.endswith(" scale") else
+                                    f": one e8m0 byte per {MXFP4_BLOCK}-element block" if e.dtypes == (torch.uint8,)
+                                    else ": one fp32 scale per output row")
+                                 + (": two nibbles per byte" if fmt.layers == 2 and e.name in LAYER_GEMMS else ""))
         L, Bmax, S, Hkv, D = k_cache.shape
         if (L, Bmax, S, Hkv, D) != (dims.n_layers, dims.max_batch, dims.max_seq, dims.Hkv, dims.D):
             raise ValueError("cache shape does not match dims")
         if v_cache.shape != k_cache.shape or v_cache.dtype != k_cache.dtype:
             raise ValueError("k_cache and v_cache must have the same shape and dtype")
         # From here on the device: where every tensor lives, contiguity, alignment, the RoPE table's values.
+        # Alignment first (an address needs no device to be judged), then the device: where every tensor lives,
+        # contiguity, the RoPE table's values.
         for e, t in zip(table, weights):
-            _check(t, t.dtype, label(e.name, e.layer), dev)
             if t.data_ptr() % e.align:
                 raise ValueError(f"{label(e.name, e.layer)} must be {e.align}-byte aligned")
+        for e, t in zip(table, weights):
+            _check(t, t.dtype, label(e.name, e.layer), dev)
         if dims.rope_table:
             _check_inv_freq(weights[table.index("inv_freq")], dims.D, dev)
         for name, c in (("k_cache", k_cache), ("v_cache", v_cache)):
@@ -1134,6 +1297,12 @@ class FusedLlamaDecoder:
             raise ValueError(f"rows must be 1..{limit} with matching pos/ids")
         if logits.shape != (B, d.vocab):
             raise ValueError("logits must be [B, vocab]")
+        if self.weight_format.layers != self.weight_format.lm_head:  # MXFP4: only the _fmt entry point says so
+            _ok(lib().p2pt_llama_decode_fmt(ctypes.byref(d), ctypes.byref(self.weight_format), _p(self.kv_scales),
+                                            self._windows, self._wptr, _p(self.k_cache), _p(self.v_cache), _p(tokens),
+                                            _p(pos), _p(slots), B, emit_rows, _p(self.ws), self.ws.numel(),
+                                            _p(logits), _p(ids), _stream(tokens)), "llama_decode")
+            return
         if self._windows is not None:
             _ok(lib().p2pt_llama_decode_win(ctypes.byref(d), ctypes.byref(self._wplan), _p(self.kv_scales),
                                             self._windows, self._wptr, _p(self.k_cache), _p(self.v_cache), _p(tokens),

@@ -62,6 +62,19 @@ struct WeightPlan {
   int w8;  // k_skinny<.., 1>: the five GEMM weights are e4m3 bytes with an fp32 scale per output row
 };
 bool weights_ok(const WeightPlan& w) { return w.w8 == 0 || w.w8 == 1; }
+// The weight formats of a step, beside the plans as WeightPlan is, and what the step itself follows: WeightPlan's one
+// field (pinned by tests, as is its refusal of w8 = 2) cannot say that the layers and the LM head differ, so the _fmt
+// entry points take this and the WeightPlan ones are the same call with {w8, w8}. 0 bf16, 1 FP8 (e4m3 bytes, an fp32
+// scale per output row), 2 MXFP4 (OCP Microscaling: e2m1 nibbles, an e8m0 scale byte per 32-element block). MXFP4
+// is a format of the four layer GEMMs only, and its LM head is FP8 (docs/WEIGHT_MXFP4.md). StepPlan does not depend
+// on it: no format changes a grid, wave count, load batch or K part.
+struct WeightFormat {
+  int layers;   // wqkv, wo, w_gate_up, w_down: k_skinny<.., layers>
+  int lm_head;  // k_skinny<.., EPI_ARGMAX, .., lm_head>
+};
+bool format_ok(const WeightFormat& f) {
+  return (f.layers == 0 && f.lm_head == 0) || (f.layers == 1 && f.lm_head == 1) || (f.layers == 2 && f.lm_head == 1);
+}
 // The scales of an FP8 cache, beside the plans as WeightPlan is and for the same reason: no field of LlamaDims, no
 // entry of the weight table, so a model without scales plans, lays out and launches what it did. One device buffer,
 // fp32 [4][n_layers][Hkv]: 1 / k_scale, 1 / v_scale (what the writers multiply by, computed once on the host),
@@ -239,16 +252,22 @@ Workspace carve(const LlamaDims& d, uint8_t* base) {
 // The one place in C that knows the layout of the pointer list w (ops/__init__.py's WeightTable is the Python one;
 // p2pt_llama_weight_layout reports this one so that the two can be compared): embed, final_norm, lm_head, inv_freq
 // if rope_table, then per layer the six, + q_norm, k_norm (qk_norm) or + bqkv (qkv_bias), then with FP8 weights the
-// fp32 row scales: lm_head's, then per layer wqkv's, wo's, w_gate_up's and w_down's.
+// fp32 row scales: lm_head's, then per layer wqkv's, wo's, w_gate_up's and w_down's. An MXFP4 table has the same
+// entries: lm_head as in an FP8 table, each layer GEMM as N * K / 2 bytes, and after the table lm_head's fp32 row
+// scales, then per layer the four e8m0 scale tensors [N][K / 32] where the FP8 table has row scales.
 enum Role : int { R_EMBED, R_FINAL_NORM, R_LM_HEAD, R_INV_FREQ, R_ATTN_NORM, R_WQKV, R_WO, R_FFN_NORM, R_W_GATE_UP,
                   R_W_DOWN, R_BQKV, R_Q_NORM, R_K_NORM, R_NROLES };
 struct WeightTable {
   LlamaDims d;
-  int w8;
+  WeightFormat f;
   const void* const* w;
   int per_layer() const { return d.qk_norm ? 8 : d.qkv_bias ? 7 : 6; }
   int scales0() const { return 3 + d.rope_table + per_layer() * d.n_layers; }
-  int size() const { return scales0() + (w8 ? 1 + 4 * d.n_layers : 0); }
+  int size() const { return scales0() + (f.lm_head ? 1 + 4 * d.n_layers : 0); }
+  // The format of a GEMM weight's role (0 for every other role).
+  int format(Role r) const {
+    return r == R_LM_HEAD ? f.lm_head : r == R_WQKV || r == R_WO || r == R_W_GATE_UP || r == R_W_DOWN ? f.layers : 0;
+  }
   // Index of a role (of layer L, which the four global roles ignore); -1: this table has none.
   int index(Role r, int L = 0) const {
     if (r <= R_LM_HEAD) return r;
@@ -258,10 +277,11 @@ struct WeightTable {
     if (r == R_BQKV) return d.qkv_bias && !d.qk_norm ? base + 6 : -1;
     return d.qk_norm ? base + 6 + (r - R_Q_NORM) : -1;
   }
-  // Index of the row scales of a GEMM weight; -1 for a bf16 table (where launch() wants none) or another role.
+  // Index of the scales of a GEMM weight (fp32 row scales, or an MXFP4 weight's e8m0 block scales); -1 for a bf16
+  // table (where launch() wants none) or another role.
   int scale_index(Role r, int L = 0) const {
     const int j = r == R_WQKV ? 1 : r == R_WO ? 2 : r == R_W_GATE_UP ? 3 : r == R_W_DOWN ? 4 : 0;
-    return !w8 || (!j && r != R_LM_HEAD) ? -1 : scales0() + (j ? 4 * L + j : 0);
+    return !format(r) ? -1 : scales0() + (j ? 4 * L + j : 0);
   }
   const void* get(Role r, int L = 0) const { return at(index(r, L)); }  // nullptr where the table has none
   const void* scale(Role r, int L = 0) const { return at(scale_index(r, L)); }
@@ -277,11 +297,13 @@ GemmArgs operator+(GemmArgs a, Set set) {
   set(a);
   return a;
 }
-// M, N, K and kpl are the plan's: launch() fills them in. wscale: the row scales of an FP8 weight (nullptr: bf16).
-GemmArgs gemm(const void* x, const void* w, const void* wscale = nullptr) {
+// M, N, K and kpl are the plan's: launch() fills them in. scale: what the table holds for the weight's scales, the
+// fp32 row scales of an FP8 weight (fmt 1) or the e8m0 block scales of an MXFP4 one (fmt 2); nullptr: bf16.
+GemmArgs gemm(const void* x, const void* w, const void* scale = nullptr, int fmt = 1) {
   GemmArgs a{};
   a.x = static_cast<const uint16_t*>(x), a.w = static_cast<const uint16_t*>(w);
-  a.wscale = static_cast<const float*>(wscale);
+  if (fmt == 2) a.wexp = static_cast<const uint8_t*>(scale);
+  else a.wscale = static_cast<const float*>(scale);
   return a;
 }
 auto norm(const float* ss, int parts, float eps) {
@@ -319,7 +341,8 @@ using HeadDims = Ints<64, 128>;  // D of k_attn and k_qknorm_rope
 // G of k_attn, the GQA ratio H / Hkv (models/checkpoint.py mirrors it as _GQA_RATIOS). 5, 6 and 7 are the Qwen2 /
 // Qwen2.5 family's (40/8, 12/2, 14/2 and 28/4). 3 is absent: no checkpoint the loader accepts uses it.
 using GqaRatios = Ints<1, 2, 4, 5, 6, 7, 8>;
-using Flags = Ints<0, 1>;  // KV8 and WIN of k_attn; TAB and KV8 of k_qknorm_rope; W8 of k_skinny
+using Flags = Ints<0, 1>;  // KV8 and WIN of k_attn; TAB and KV8 of k_qknorm_rope
+using SkinnyFormats = Ints<0, 1, 2>;  // W8 of k_skinny: bf16, FP8, MXFP4
 using SkinnyWaves = Ints<4, 8>;
 using SkinnyTiles = Ints<1, 2>;
 using SkinnyBatches = Ints<1, 2, 4>;
@@ -332,6 +355,10 @@ constexpr bool skinny_exists(int nw, int tn, int epi, int um, int w8) {
   // can give those: the LM head's fixed 4 waves with any load batch, and for the others the (nw, um) pairs of
   // fixed_nw == 0 below. 47 instantiations beside the 66 of bf16.
   if (w8 && epi == EPI_STORE && tn == 2) return false;
+  // MXFP4 weights run a layer's four GEMMs only (the LM head stays FP8): every epilogue those can be planned with,
+  // the eight RoPE ones, SILU, RESID and, for QK-norm models, STORE with one subtile, never ARGMAX, each with the
+  // (nw, um) pairs of fixed_nw == 0. 44 instantiations beside the 47 of FP8 and the 66 of bf16.
+  if (w8 == 2 && epi == EPI_ARGMAX) return false;
   if (w8 && epi == EPI_ARGMAX) return nw == 4;
   if (w8) return nw == 4 || um == 4;
   // The table and FP8-cache epilogues run QKV projections only, so they carry just the (nw, um) pairs plan_gemm
@@ -362,7 +389,7 @@ SkinnyKernel skinny_kernel(const GemmPlan& p, int w8 = 0) {
   SkinnyKernel k = nullptr;
   pick([&](auto nw, auto tn, auto epi, auto um, auto f8) {
     if constexpr (skinny_exists(nw, tn, epi, um, f8)) k = k_skinny<nw, tn, epi, um, f8>;
-  }, p.nw, SkinnyWaves{}, p.tn, SkinnyTiles{}, p.epi, SkinnyEpis{}, p.um, SkinnyBatches{}, w8, Flags{});
+  }, p.nw, SkinnyWaves{}, p.tn, SkinnyTiles{}, p.epi, SkinnyEpis{}, p.um, SkinnyBatches{}, w8, SkinnyFormats{});
   return k;
 }
 using AttnKernel = decltype(&k_attn<64, 1, false>);
@@ -382,9 +409,10 @@ QkNormKernel qknorm_kernel(int D, int table, int kv8) {
 
 // ------------------------------------------------------------ launches
 // Each checks its arguments, looks its kernel up and launches it; a plan that names no kernel is hipErrorInvalidValue.
-// w8: the FP8-weight instantiation (WeightPlan::w8), which reads a.wscale and is refused without it.
+// w8: the weight's format (WeightFormat): 1, the FP8-weight instantiation, reads a.wscale and is refused without it;
+// 2, the MXFP4 one, reads a.wexp likewise. A scale pointer the format does not read is refused too.
 hipError_t launch(const GemmPlan& p, GemmArgs a, hipStream_t s, int w8 = 0) {
-  if ((w8 != 0) != (a.wscale != nullptr)) return hipErrorInvalidValue;
+  if ((w8 == 1) != (a.wscale != nullptr) || (w8 == 2) != (a.wexp != nullptr)) return hipErrorInvalidValue;
   if (p.kpl < 0 || p.kpl > kMaxKpl || (p.ss_in > 0) != (a.ss_part != nullptr)) return hipErrorInvalidValue;
   if (p.kpl && (p.tn != 1 || (p.M << p.kpl) > 16 || p.K % (32 << p.kpl))) return hipErrorInvalidValue;
   // The bias is added once, after the K-split reduction: never with K parts, never without a bias.
@@ -505,11 +533,12 @@ int p2pt_llama_kv_plan(const LlamaDims* d, KvPlan* out) {
 // does not; -1: dims or row count refused.
 // windows: the per-layer windows (Windows), nullptr for none: every layer's attention variant must exist, and a
 // windowed layer's slots must fit the partials' stride. A negative window is refused (-1).
-int p2pt_llama_plan_kernels_win(const LlamaDims* d, int B, int emit_rows, const WeightPlan* wp, const int* windows) {
-  if (!dims_ok(*d) || !rows_ok(B) || !weights_ok(*wp) || !windows_ok(*d, Windows{windows})) return -1;
+// fmt: the weight formats (WeightFormat); one that is no supported pair is refused (-1).
+int p2pt_llama_plan_kernels_fmt(const LlamaDims* d, int B, int emit_rows, const WeightFormat* fmt, const int* windows) {
+  if (!dims_ok(*d) || !rows_ok(B) || !format_ok(*fmt) || !windows_ok(*d, Windows{windows})) return -1;
   const StepPlan P = plan_step(*d, B, emit_rows);
   const KvPlan KV = plan_kv(*d);
-  const int w8 = wp->w8;
+  const int w8 = fmt->layers;
   bool attn = true;
   for (int L = 0; L < d->n_layers; L++) {
     const WindowPlan wn = plan_window(*d, B, Windows{windows}.at(L));
@@ -523,10 +552,16 @@ int p2pt_llama_plan_kernels_win(const LlamaDims* d, int B, int emit_rows, const 
                         skinny_kernel(P.o, w8) != nullptr,
                         skinny_kernel(P.gate_up, w8) != nullptr,
                         skinny_kernel(P.down, w8) != nullptr,
-                        skinny_kernel(P.lm_head, w8) != nullptr};
+                        skinny_kernel(P.lm_head, fmt->lm_head) != nullptr};
   for (int n = 0; n < 8; n++)
     if (!found[n]) return 1 + n;
   return 0;
+}
+// The same with one format for the five GEMMs (WeightPlan: bf16 or FP8; anything else is refused).
+int p2pt_llama_plan_kernels_win(const LlamaDims* d, int B, int emit_rows, const WeightPlan* wp, const int* windows) {
+  if (!weights_ok(*wp)) return -1;
+  const WeightFormat f{wp->w8, wp->w8};
+  return p2pt_llama_plan_kernels_fmt(d, B, emit_rows, &f, windows);
 }
 int p2pt_llama_plan_kernels_w(const LlamaDims* d, int B, int emit_rows, const WeightPlan* wp) {
   return p2pt_llama_plan_kernels_win(d, B, emit_rows, wp, nullptr);
@@ -551,18 +586,33 @@ int p2pt_llama_weight_plan(const LlamaDims* d, int weight_fp8, WeightPlan* out) 
   return 0;
 }
 
-// The weight table of (dims, weight plan) as the step reads it (host only): its length, and into index[L * 13 + r]
-// and scale_index[L * 13 + r] where role r (enum Role) of layer L and its row scales sit, -1 where there is none.
-// n: ints each array holds, at least 13 * n_layers. -1: dims or plan refused, or n too small.
-int p2pt_llama_weight_layout(const LlamaDims* d, const WeightPlan* wp, int* index, int* scale_index, int n) {
-  if (!dims_ok(*d) || !weights_ok(*wp) || n < R_NROLES * d->n_layers) return -1;
-  const WeightTable T{*d, wp->w8, nullptr};
+// The weight formats of a step for (layers, lm_head) in {(0, 0), (1, 1), (2, 1)} (host only), beside the plans above.
+int p2pt_llama_weight_format(const LlamaDims* d, int layers, int lm_head, WeightFormat* out) {
+  const WeightFormat f{layers, lm_head};
+  if (!dims_ok(*d) || !format_ok(f)) return int(hipErrorInvalidValue);
+  *out = f;
+  return 0;
+}
+
+// The weight table of (dims, weight formats) as the step reads it (host only): its length, and into index[L * 13 + r]
+// and scale_index[L * 13 + r] where role r (enum Role) of layer L and its scales (fp32 row scales, or the e8m0 block
+// scales of an MXFP4 weight) sit, -1 where there is none.
+// n: ints each array holds, at least 13 * n_layers. -1: dims or formats refused, or n too small.
+int p2pt_llama_weight_layout_fmt(const LlamaDims* d, const WeightFormat* fmt, int* index, int* scale_index, int n) {
+  if (!dims_ok(*d) || !format_ok(*fmt) || n < R_NROLES * d->n_layers) return -1;
+  const WeightTable T{*d, *fmt, nullptr};
   for (int L = 0; L < d->n_layers; L++)
     for (int r = 0; r < R_NROLES; r++) {
       index[L * R_NROLES + r] = T.index(Role(r), L);
       scale_index[L * R_NROLES + r] = T.scale_index(Role(r), L);
     }
   return T.size();
+}
+// The same for a WeightPlan (bf16 or FP8 throughout; anything else is refused).
+int p2pt_llama_weight_layout(const LlamaDims* d, const WeightPlan* wp, int* index, int* scale_index, int n) {
+  if (!weights_ok(*wp)) return -1;
+  const WeightFormat f{wp->w8, wp->w8};
+  return p2pt_llama_weight_layout_fmt(d, &f, index, scale_index, n);
 }
 
 // k_attn's span rule: tokens per span slot for a row of `len` tokens.
@@ -602,17 +652,22 @@ int p2pt_max_rows() { return kMaxM; }
 //      included. Such a layer runs k_attn<D, G, KV8, true> on the slots of a cache of min(max_seq, W) rows; a layer
 //      with 0 launches what it did. The cache keeps max_seq rows per slot and appends go to pos as before.
 //      nullptr: no windows, which is p2pt_llama_decode_kv. A negative entry is refused.
-int p2pt_llama_decode_win(const LlamaDims* dp, const WeightPlan* wp, const float* kv_scales, const int* windows,
+//   MXFP4 weights (p2pt_llama_decode_fmt with WeightFormat{2, 1}): the FP8 table with each layer's wqkv, wo, w_gate_up
+//      and w_down as bytes [N][K / 2] (4-byte aligned), two e2m1 nibbles each with the lower k in the low nibble,
+//      quantised after the fold and the interleave, and where the FP8 table has their row scales the e8m0 scale
+//      bytes [N][K / 32] of their 32-element blocks. lm_head and its fp32 row scales are the FP8 table's.
+//      p2pt_llama_decode_win is this call with {w8, w8}.
+int p2pt_llama_decode_fmt(const LlamaDims* dp, const WeightFormat* fmt, const float* kv_scales, const int* windows,
                           const void* const* w, void* k_cache, void* v_cache, const int64_t* tokens, const int* pos,
                           const int* slots, int B, int emit_rows, void* ws, size_t ws_bytes, void* logits,
                           int64_t* ids, void* stream) {
   const LlamaDims d = *dp;
-  if (!dims_ok(d) || !rows_ok(B) || (!slots && B > d.max_batch) || !weights_ok(*wp)) return int(hipErrorInvalidValue);
+  if (!dims_ok(d) || !rows_ok(B) || (!slots && B > d.max_batch) || !format_ok(*fmt)) return int(hipErrorInvalidValue);
   if (kv_scales && !d.kv_fp8) return int(hipErrorInvalidValue);
   const Windows WN{windows};
   if (!windows_ok(d, WN)) return int(hipErrorInvalidValue);
   const KvScales KS{kv_scales};
-  const int w8 = wp->w8;
+  const int w8 = fmt->layers;
   const Workspace W = carve(d, static_cast<uint8_t*>(ws));
   if (ws_bytes < W.bytes) return int(hipErrorInvalidValue);
   const StepPlan P = plan_step(d, B, emit_rows);
@@ -622,7 +677,7 @@ int p2pt_llama_decode_win(const LlamaDims* dp, const WeightPlan* wp, const float
   hipError_t e;
   auto failed = [&](hipError_t r) { return (e = r) != hipSuccess; };
 
-  const WeightTable T{d, w8, w};
+  const WeightTable T{d, *fmt, w};
   const void* inv_freq = T.get(R_INV_FREQ);
   hipLaunchKernelGGL(k_embed, dim3(B), dim3(256), 0, s, static_cast<const uint16_t*>(T.get(R_EMBED)), tokens, W.resid,
                      W.ss, d.dim, d.vocab);
@@ -631,15 +686,15 @@ int p2pt_llama_decode_win(const LlamaDims* dp, const WeightPlan* wp, const float
     uint16_t* kc = reinterpret_cast<uint16_t*>(static_cast<uint8_t*>(k_cache) + L * layer_cache);
     uint16_t* vc = reinterpret_cast<uint16_t*>(static_cast<uint8_t*>(v_cache) + L * layer_cache);
     const GemmPlan& qkv = L ? P.qkv : P.qkv_first;
-    const GemmArgs qkv_in = gemm(W.resid, T.get(R_WQKV, L), T.scale(R_WQKV, L)) + norm(W.ss, qkv.ss_in, d.eps);
+    const GemmArgs qkv_in = gemm(W.resid, T.get(R_WQKV, L), T.scale(R_WQKV, L), w8) + norm(W.ss, qkv.ss_in, d.eps);
     const GemmArgs to_qkv =
         d.qk_norm ? qkv_in + store(W.qkv)
                   : qkv_in + rope(d, pos, slots, W.q, kc, vc, T.get(R_BQKV, L), inv_freq,
                                   KS.at(d, KvScales::K_RECIP, L), KS.at(d, KvScales::V_RECIP, L));
-    const GemmArgs to_o = gemm(W.attn, T.get(R_WO, L), T.scale(R_WO, L)) + resid(W.resid, W.ss);
-    const GemmArgs to_gate_up = gemm(W.resid, T.get(R_W_GATE_UP, L), T.scale(R_W_GATE_UP, L)) +
+    const GemmArgs to_o = gemm(W.attn, T.get(R_WO, L), T.scale(R_WO, L), w8) + resid(W.resid, W.ss);
+    const GemmArgs to_gate_up = gemm(W.resid, T.get(R_W_GATE_UP, L), T.scale(R_W_GATE_UP, L), w8) +
                                 norm(W.ss, P.gate_up.ss_in, d.eps) + store(W.h);
-    const GemmArgs to_down = gemm(W.h, T.get(R_W_DOWN, L), T.scale(R_W_DOWN, L)) + resid(W.resid, W.ss);
+    const GemmArgs to_down = gemm(W.h, T.get(R_W_DOWN, L), T.scale(R_W_DOWN, L), w8) + resid(W.resid, W.ss);
     if (failed(launch(qkv, to_qkv, s, w8))) return int(e);
     if (P.qk_norm_grid) {
       const QkNormArgs qn{W.qkv, static_cast<const uint16_t*>(T.get(R_Q_NORM, L)),
@@ -658,11 +713,20 @@ int p2pt_llama_decode_win(const LlamaDims* dp, const WeightPlan* wp, const float
     if (failed(launch(P.down, to_down, s, w8))) return int(e);
   }
   const GemmArgs to_logits =
-      gemm(W.resid, T.get(R_LM_HEAD), T.scale(R_LM_HEAD)) + norm(W.ss, P.lm_head.ss_in, d.eps) +
+      gemm(W.resid, T.get(R_LM_HEAD), T.scale(R_LM_HEAD), fmt->lm_head) + norm(W.ss, P.lm_head.ss_in, d.eps) +
       argmax(logits, W.am_val, W.am_idx);
-  if (failed(launch(P.lm_head, to_logits, s, w8))) return int(e);
+  if (failed(launch(P.lm_head, to_logits, s, fmt->lm_head))) return int(e);
   hipLaunchKernelGGL(k_argmax_merge, dim3(P.emit_rows), dim3(256), 0, s, W.am_val, W.am_idx, P.am_parts, ids);
   return int(hipGetLastError());
+}
+int p2pt_llama_decode_win(const LlamaDims* dp, const WeightPlan* wp, const float* kv_scales, const int* windows,
+                          const void* const* w, void* k_cache, void* v_cache, const int64_t* tokens, const int* pos,
+                          const int* slots, int B, int emit_rows, void* ws, size_t ws_bytes, void* logits,
+                          int64_t* ids, void* stream) {
+  if (!weights_ok(*wp)) return int(hipErrorInvalidValue);
+  const WeightFormat f{wp->w8, wp->w8};
+  return p2pt_llama_decode_fmt(dp, &f, kv_scales, windows, w, k_cache, v_cache, tokens, pos, slots, B, emit_rows, ws,
+                               ws_bytes, logits, ids, stream);
 }
 int p2pt_llama_decode_kv(const LlamaDims* dp, const WeightPlan* wp, const float* kv_scales, const void* const* w,
                          void* k_cache, void* v_cache, const int64_t* tokens, const int* pos, const int* slots, int B,

@@ -22,6 +22,10 @@
 //     (sliding window:   a layer with a window runs k_attn<D, G, KV8, true> over its last W positions)
 //     (FP8 weights:      every k_skinny is its W8 instantiation: e4m3 weight bytes, 8-byte loads, and the
 //                        column's fp32 scale on the accumulator ahead of 1/rms: the same kernel count)
+//     (MXFP4 weights:    a layer's four k_skinny are their W8 = 2 instantiations: OCP Microscaling FP4, 32-element
+//                        blocks of e2m1 nibbles with one e8m0 scale byte, 4-byte loads and a 1-byte scale load per
+//                        k-step, decoded exactly by v_cvt_scalef32_pk_bf16_fp4 ahead of the MFMA; no scale in the
+//                        epilogue. The LM head stays FP8. The same kernel count: docs/WEIGHT_MXFP4.md)
 //     k_skinny<RESID>    O projection -> residual add -> per-row sum-of-squares
 //                        partials for the next norm
 //     k_skinny<SILU>     RMSNorm (ffn_norm) -> gate/up GEMM -> SwiGLU
@@ -153,6 +157,10 @@ struct GemmArgs {
   // layer's KV heads, which multiply the value ahead of its one rounding. Both nullptr: scale 1. Not read otherwise.
   const float* k_rscale;
   const float* v_rscale;
+  // MXFP4 weights (k_skinny<.., W8 = 2>): w holds N * K / 2 bytes, two e2m1 nibbles each (the lower k in the low
+  // nibble), and wexp the e8m0 scale byte of every 32-element block, [N][K / 32] in the row order of w. Not read by
+  // the other kernels.
+  const uint8_t* wexp;
 };
 
 // log2 of the output columns per 16-lane subtile: 16, 8 or 4 for 1, 2 or 4 K parts.
@@ -237,6 +245,25 @@ __device__ __forceinline__ uint4 buf_ld16(__amdgpu_buffer_rsrc_t r, uint32_t off
 __device__ __forceinline__ uint2 buf_ld8(__amdgpu_buffer_rsrc_t r, uint32_t off) {
   return __builtin_bit_cast(uint2, __builtin_amdgcn_raw_buffer_load_b64(r, off, 0, 0));
 }
+__device__ __forceinline__ uint32_t buf_ld4(__amdgpu_buffer_rsrc_t r, uint32_t off) {
+  return __builtin_amdgcn_raw_buffer_load_b32(r, off, 0, 0);
+}
+__device__ __forceinline__ uint32_t buf_ld1(__amdgpu_buffer_rsrc_t r, uint32_t off) {
+  return __builtin_amdgcn_raw_buffer_load_b8(r, off, 0, 0);
+}
+
+// MXFP4: four bytes (eight e2m1 nibbles, the lower k in the low nibble of its byte) and the block's e8m0 scale byte E
+// as eight bf16, by v_cvt_scalef32_pk_bf16_fp4 with the scale 2^(E - 127) passed as the fp32 of bits E << 23. Exact:
+// every e2m1 value has at most one mantissa bit, and the quantiser keeps E where 0.5 * 2^(E - 127) and 6 * 2^(E - 127)
+// are normal bf16 numbers. E = 0 with zero nibbles (what a load past the buffer returns) decodes to zeros.
+__device__ __forceinline__ uint4 fp4x8_to_bf16x8(uint32_t v, uint32_t e) {
+  const float sc = __uint_as_float(e << 23);
+  auto cv = [&](auto sel) {
+    return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(v, sc, decltype(sel)::value));
+  };
+  return make_uint4(cv(std::integral_constant<int, 0>{}), cv(std::integral_constant<int, 1>{}),
+                    cv(std::integral_constant<int, 2>{}), cv(std::integral_constant<int, 3>{}));
+}
 
 // One batch of up to UM consecutive 32-wide k-steps [s, min(s + UM, s1)):
 // every load of the batch is issued before any of it is used.
@@ -244,22 +271,32 @@ __device__ __forceinline__ uint2 buf_ld8(__amdgpu_buffer_rsrc_t r, uint32_t off)
 // k-step stride of 32 bytes, decoded to the bf16 fragment (e4m3x8_to_bf16x8: exact) just ahead of its MFMA. The A
 // operand, the order of the k-steps and the MFMA are the bf16 kernel's, so on the decoded weights the accumulator
 // is the bf16 kernel's bit for bit.
+// W8 = 2 (MXFP4 weights): the 8 k-values are 4 bytes, one 4-byte load at a k-step stride of 16 bytes, and the k-step
+// is one 32-element block, so its scale is one byte at a stride of 1 (soff, through the descriptor rs; the four
+// k-groups of a column read the same byte). Both are decoded together just ahead of the MFMA (fp4x8_to_bf16x8: exact
+// for every scale), and nothing after the MFMA knows the format: on the dequantised weights the whole kernel is the
+// bf16 kernel's bit for bit. soff and rs are not read otherwise.
 template <int UM, int TN, int W8>
 struct Batch {
-  std::conditional_t<W8 != 0, uint2, uint4> b[UM][TN];
+  std::conditional_t<W8 == 2, uint32_t, std::conditional_t<W8 == 1, uint2, uint4>> b[UM][TN];
+  uint32_t e[W8 == 2 ? UM : 1][TN];  // W8 = 2: the block's e8m0 scale byte
   uint4 a[UM];
 };
 
 template <int UM, int TN, int W8>
 __device__ __forceinline__ void load_batch(Batch<UM, TN, W8>& bt, __amdgpu_buffer_rsrc_t ra, uint32_t xoff,
-                                           __amdgpu_buffer_rsrc_t rw, const uint32_t (&woff)[TN], int s, int s1) {
+                                           __amdgpu_buffer_rsrc_t rw, const uint32_t (&woff)[TN],
+                                           __amdgpu_buffer_rsrc_t rs, const uint32_t (&soff)[TN], int s, int s1) {
 #pragma unroll
   for (int u = 0; u < UM; u++) {
     const bool in = s + u < s1;
-    const uint32_t su = uint32_t(s + u) * 64u;  // bytes per 32-wide k-step (bf16; half that for e4m3 weights)
+    const uint32_t su = uint32_t(s + u) * 64u;  // bytes per 32-wide k-step (bf16; half for e4m3, a quarter for MXFP4)
 #pragma unroll
     for (int t = 0; t < TN; t++) {
-      if constexpr (W8) bt.b[u][t] = buf_ld8(rw, in ? woff[t] + (su >> 1) : kOob);
+      if constexpr (W8 == 2) {
+        bt.b[u][t] = buf_ld4(rw, in ? woff[t] + (su >> 2) : kOob);
+        bt.e[u][t] = buf_ld1(rs, in ? soff[t] + uint32_t(s + u) : kOob);
+      } else if constexpr (W8 == 1) bt.b[u][t] = buf_ld8(rw, in ? woff[t] + (su >> 1) : kOob);
       else bt.b[u][t] = buf_ld16(rw, in ? woff[t] + su : kOob);
     }
     bt.a[u] = buf_ld16(ra, in ? xoff + su : kOob);
@@ -273,7 +310,8 @@ __device__ __forceinline__ void mma_apply(frag4 (&acc)[TN], const Batch<UM, TN, 
 #pragma unroll
     for (int t = 0; t < TN; t++) {
       uint4 b;
-      if constexpr (W8) b = e4m3x8_to_bf16x8(bt.b[u][t]);
+      if constexpr (W8 == 2) b = fp4x8_to_bf16x8(bt.b[u][t], bt.e[u][t]);
+      else if constexpr (W8 == 1) b = e4m3x8_to_bf16x8(bt.b[u][t]);
       else b = bt.b[u][t];
       acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(bt.a[u]), as_frag(b), acc[t], 0, 0, 0);
     }
@@ -282,10 +320,11 @@ __device__ __forceinline__ void mma_apply(frag4 (&acc)[TN], const Batch<UM, TN, 
 // The wave's k-steps [s0, s1), one batch at a time.
 template <int UM, int TN, int W8>
 __device__ __forceinline__ void mma_stream(frag4 (&acc)[TN], __amdgpu_buffer_rsrc_t ra, uint32_t xoff,
-                                           __amdgpu_buffer_rsrc_t rw, const uint32_t (&woff)[TN], int s0, int s1) {
+                                           __amdgpu_buffer_rsrc_t rw, const uint32_t (&woff)[TN],
+                                           __amdgpu_buffer_rsrc_t rs, const uint32_t (&soff)[TN], int s0, int s1) {
   for (int s = s0; s < s1; s += UM) {
     Batch<UM, TN, W8> p;
-    load_batch<UM, TN, W8>(p, ra, xoff, rw, woff, s, s1);
+    load_batch<UM, TN, W8>(p, ra, xoff, rw, woff, rs, soff, s, s1);
     // Keep every load of the batch ahead of the first MFMA: left alone, the
     // scheduler interleaves them and the batch pays several memory latencies.
     __builtin_amdgcn_sched_barrier(0);
@@ -304,6 +343,10 @@ __device__ __forceinline__ void mma_stream(frag4 (&acc)[TN], __amdgpu_buffer_rsr
 // K-split reduction and the K-parts diagonal sum and ahead of 1/rms: v = (v * s[col]) * rs. Everything after that
 // is the bf16 kernel's epilogue. With power-of-two scales the product is exact, so the kernel matches the bf16
 // kernel on the weights decode(q) * s bit for bit.
+// W8 = 2: the weight is N * K / 2 bytes of e2m1 nibbles with one e8m0 byte per 32-element block (GemmArgs::wexp,
+// N * K / 32 bytes). The stream is as above with 4-byte B loads and a 1-byte scale load per k-step (Batch); under K
+// parts both offsets carry the part. There is no scale in the epilogue: the decoded fragment is the dequantised
+// weight itself, so the kernel matches the bf16 kernel on those weights bit for bit, for every scale.
 template <int NW, int TN, int EPI, int UM, int W8 = 0>
 __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
   __shared__ float red[NW][TN][4][kWave];
@@ -343,14 +386,20 @@ __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
   // Byte offsets of this lane's A row and weight rows at k-step 0; rows past
   // M read as zeros (kOob).
   const __amdgpu_buffer_rsrc_t ra = rsrc(a.x, uint32_t(a.M) * uint32_t(a.K) * 2u);
-  constexpr uint32_t kWb = W8 ? 1u : 2u;  // bytes per weight element
-  const __amdgpu_buffer_rsrc_t rw = rsrc(a.w, uint32_t(a.N) * uint32_t(a.K) * kWb);
+  constexpr uint32_t kWb = W8 ? 1u : 2u;   // bytes per weight element ...
+  constexpr uint32_t kWs = W8 == 2 ? 1u : 0u;  // ... halved once more for MXFP4's nibbles
+  const __amdgpu_buffer_rsrc_t rw = rsrc(a.w, (uint32_t(a.N) * uint32_t(a.K) * kWb) >> kWs);
+  // MXFP4: the scale bytes, [N][K / 32]; the other formats never load through it.
+  const __amdgpu_buffer_rsrc_t rs = W8 == 2 ? rsrc(a.wexp, uint32_t(a.N) * uint32_t(a.K >> 5)) : rw;
   const uint32_t xoff = a_ok ? (uint32_t(m0 + m_a) * uint32_t(a.K) + uint32_t(p_a * Kp + kq)) * 2u : kOob;
   const int p_b = (lane & 15) >> cwl;  // K part of this lane's weight column
-  uint32_t woff[TN];
+  uint32_t woff[TN], soff[TN];
 #pragma unroll
-  for (int t = 0; t < TN; t++)
-    woff[t] = (uint32_t(tile_col<TN>(bx, t, lane & 15, cwl)) * uint32_t(a.K) + uint32_t(p_b * Kp + kq)) * kWb;
+  for (int t = 0; t < TN; t++) {
+    const uint32_t col = uint32_t(tile_col<TN>(bx, t, lane & 15, cwl));
+    woff[t] = ((col * uint32_t(a.K) + uint32_t(p_b * Kp + kq)) * kWb) >> kWs;
+    soff[t] = col * uint32_t(a.K >> 5) + uint32_t(p_b * (Kp >> 5));  // the block of k-step 0 of this lane's K part
+  }
 
   // C layout: row m = m0 + 4*(lane>>4) + r, column = tile_col(.., lane & 15).
   const int lrow0 = (lane >> 4) << 2, mrow0 = m0 + lrow0;
@@ -395,8 +444,8 @@ __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
   // W8: this lane's column scales, loaded by wave 0 ahead of the weight stream like bias and tab_freq. tile_col
   // masks the lane column to the tile width, so under K parts the lanes past it index their own column's scale,
   // below N like every column of the grid (grid_x * TN * 2^cwl == N).
-  float wsc[W8 ? TN : 1];
-  if constexpr (W8) {
+  float wsc[W8 == 1 ? TN : 1];
+  if constexpr (W8 == 1) {
     if (wv == 0) {
 #pragma unroll
       for (int t = 0; t < TN; t++) wsc[t] = a.wscale[tile_col<TN>(bx, t, c, cwl)];
@@ -415,7 +464,7 @@ __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
   frag4 acc[TN];
 #pragma unroll
   for (int t = 0; t < TN; t++) acc[t] = frag4{0.f, 0.f, 0.f, 0.f};
-  mma_stream<UM, TN, W8>(acc, ra, xoff, rw, woff, s0, s1);
+  mma_stream<UM, TN, W8>(acc, ra, xoff, rw, woff, rs, soff, s0, s1);
 
   if (norm) {
     float ssum = 0.f;
@@ -462,7 +511,7 @@ __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
     }
   }
 
-  if constexpr (W8) {
+  if constexpr (W8 == 1) {
 #pragma unroll
     for (int t = 0; t < TN; t++)
 #pragma unroll
@@ -1139,6 +1188,15 @@ int attn_window_slots(int B, int Hkv, int max_seq, int window) {
 //    4.713 -> 4.338 at 16, small 0.368 -> 0.339 and 0.521 -> 0.498, tiny 0.140 -> 0.136: never slower, far from 2x.
 //    A weight layout with K permuted offline so that one 16-byte load feeds two k-steps was not tried and not
 //    measured; neither was decoding through FP8 or scaled MFMA (the activation stays bf16).
+//  - MXFP4 weights, k_skinny<.., W8 = 2>: what ships is the natural byte order, one 4-byte B load and one 1-byte scale
+//    load per lane, k-step and subtile, decoded by v_cvt_scalef32_pk_bf16_fp4 ahead of the MFMA. It is correct bit for
+//    bit and it is slow: a quarter of the bytes in twice the load instructions of bf16, each fetching a quarter of a
+//    16-byte one. Against bf16 and FP8 (docs/WEIGHT_MXFP4_raw.json, ctx 1024, ms per step): Llama-3.1-8B's shape
+//    3.193 / 2.839 / 4.291 at batch 1 and 4.764 / 4.356 / 5.864 at 16, Llama-3.2-1B's 0.816 / 0.737 / 0.940 and
+//    1.191 / 1.133 / 1.410, small 0.368 / 0.339 / 0.393 and 0.523 / 0.502 / 0.595, tiny 0.140 / 0.136 / 0.147 and
+//    0.187 / 0.177 / 0.196: slower than both at every shape measured. The blocked order (K permuted offline so that one
+//    16-byte load feeds a lane's four k-steps, and the four scale bytes one 4-byte load) was not built and not
+//    measured; it is the first thing to try, and the format's bytes on the device would be the same.
 //  - A two-deep load-batch pipeline (every projection +0.5-1.8 us) and one
 //    workgroup per CU forced through padded LDS (QKV 5.9 -> 9.9 us)
 //    (profiles/r02/decode/decode_sweep_s8.log).

@@ -45,13 +45,23 @@ def main():
                          "\"low_freq_factor\": 1, \"high_freq_factor\": 4, \"original_max_seq\": 8192}")
     ap.add_argument("--name", default=None, help="label of a --cfg model in the result line")
     ap.add_argument("--checkpoint", default=None, help="load this HF Llama checkpoint instead of a random --config")
-    ap.add_argument("--weight-dtype", choices=("bf16", "fp8"), default="bf16",
-                    help="format of the GEMM weights: bf16, or fp8 (e4m3 with per-row scales, docs/WEIGHT_FP8.md; "
-                         "the fused step only)")
+    ap.add_argument("--weight-dtype", choices=("bf16", "fp8", "mxfp4"), default="bf16",
+                    help="format of the GEMM weights: bf16, fp8 (e4m3 with per-row scales, docs/WEIGHT_FP8.md) or "
+                         "mxfp4 (block-scaled FP4 layers with an fp8 LM head, docs/WEIGHT_MXFP4.md); the fused step "
+                         "only")
+    ap.add_argument("--compare", default=None, metavar="DTYPES",
+                    help="weight formats to compare in this one process, e.g. bf16,fp8,mxfp4: one model per format "
+                         "from the same bf16 weights, then --windows alternating windows of --steps graph replays "
+                         "for every format and every batch of --batches; one JSON line per (format, batch) with the "
+                         "windows and their median, and the share of rows whose greedy token is the bf16 model's")
+    ap.add_argument("--windows", type=int, default=5, help="windows per format and batch (with --compare)")
+    ap.add_argument("--batches", default="1,16", help="comma-separated batch sizes (with --compare)")
     ap.add_argument("--loop", action="store_true",
                     help="device-side autoregression: one graph = the fused step (ids feed the next step's "
                          "tokens in place) + pos += 1, no host copies per step")
     a = ap.parse_args()
+    if a.compare:
+        return compare(a)
     if a.checkpoint:
         from p2p_llm_tunnel_amd.models.checkpoint import load_llama
         m = load_llama(a.checkpoint, device="cuda", max_batch=a.batch, fused=not a.unfused,
@@ -94,6 +104,59 @@ def main():
     print(json.dumps({"config": a.config, "batch": B, "ctx": a.ctx, "steps": a.steps, "graph": not a.eager, "fused": not a.unfused,
                       "weight_dtype": a.weight_dtype, "weight_bytes": m.weight_bytes()["total"],
                       "ms_per_step": dt * 1e3 / a.steps, "tokens_per_s": B * a.steps / dt}))
+
+
+def compare(a):
+    """--compare: every format on the same weights in one process, the windows alternating between the formats so
+    that clock and temperature drift fall on all of them alike."""
+    import statistics
+    cfg = LlamaConfig(**json.loads(a.cfg)) if a.cfg else CONFIGS[a.config]
+    name = a.name or (a.config if not a.cfg else "custom")
+    formats, batches = a.compare.split(","), [int(b) for b in a.batches.split(",")]
+    B = max(batches)
+    base = TinyLlama(cfg, device="cuda", max_batch=B)
+    weights = dict(embed=base.embed, final_norm=base.final_norm, lm_head=base.lm_head, layers=base.layers)
+    models = {f: base if f == "bf16" else TinyLlama.from_weights(cfg, weights, device="cuda", max_batch=B,
+                                                                  weight_dtype=f) for f in formats}
+    g = torch.Generator(device="cuda").manual_seed(0)
+    kc = torch.randn(base.k_cache.shape, generator=g, device="cuda", dtype=torch.bfloat16)
+    vc = torch.randn(base.v_cache.shape, generator=g, device="cuda", dtype=torch.bfloat16)
+    for m in models.values():
+        m.k_cache.copy_(kc)
+        m.v_cache.copy_(vc)
+        for b in batches:
+            m.capture_graph(rows=b)
+    agree = {}
+    for f, m in models.items():  # greedy tokens of 4 steps of B rows on identical inputs, against the first format's
+        ids = []
+        for i in range(4):
+            tok = torch.randint(0, cfg.vocab, (B,), generator=g, device="cuda") if f == formats[0] else agree["tok"][i]
+            agree.setdefault("tok", []).append(tok)
+            p = torch.full((B,), a.ctx + i, dtype=torch.int32, device="cuda")
+            ids.append(m.graph_step(tok, p).clone())
+        agree[f] = torch.cat(ids)
+    times = {(f, b): [] for f in formats for b in batches}
+    for w in range(a.windows):
+        for b in batches:
+            for f in formats:
+                m = models[f]
+                tok = torch.randint(0, cfg.vocab, (b,), device="cuda")
+                for i in range(a.warmup + a.steps):
+                    if i == a.warmup:
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                    q = a.ctx + 8 + i
+                    tok = m.graph_step(tok, torch.full((b,), q, dtype=torch.int32, device="cuda"))
+                torch.cuda.synchronize()
+                times[f, b].append((time.perf_counter() - t0) * 1e3 / a.steps)
+    for (f, b), t in times.items():
+        print(json.dumps({"config": name, "batch": b, "ctx": a.ctx, "steps": a.steps, "graph": True, "fused": True,
+                          "weight_dtype": f, "weight_bytes": models[f].weight_bytes()["total"],
+                          "gemm_weight_bytes": models[f].weight_bytes()["gemm"],
+                          "ms_per_step_windows": [round(x, 4) for x in t],
+                          "ms_per_step": round(statistics.median(t), 4),
+                          "greedy_agreement_with_" + formats[0]: float((agree[f] == agree[formats[0]]).float().mean()),
+                          "lib": os.path.basename(__import__("p2p_llm_tunnel_amd").ops.loaded_path())}), flush=True)
 
 
 def loop(m, a):
