@@ -214,7 +214,8 @@ class _Reader:
 
 def load_llama(path: str, device="cuda", max_batch: int = 8, max_seq: int | None = None,
                fused: bool = True, prefix: str = "model.", kv_dtype: str = "bf16",
-               weight_dtype: str = "bf16", kv_scales=None, sliding_window: bool = False) -> TinyLlama:
+               weight_dtype: str = "bf16", kv_scales=None, sliding_window: bool = False,
+               chunk_attn: bool = False) -> TinyLlama:
     """A TinyLlama with the checkpoint's weights (bf16 on ``device``). ``kv_dtype``: "bf16" or "fp8", the KV
     cache's format (``TinyLlama``), for every family alike. ``kv_scales`` ("fp8" only): None (scale 1: ``k_scale`` /
     ``v_scale`` tensors a checkpoint may carry are then not read), a ``KvScales``, or "checkpoint": the per-layer
@@ -223,7 +224,8 @@ def load_llama(path: str, device="cuda", max_batch: int = 8, max_seq: int | None
     (docs/WEIGHT_FP8.md) or "mxfp4" (docs/WEIGHT_MXFP4.md: the layers' GEMM weights as MXFP4, the LM head as FP8): each
     layer's GEMM weights are quantised on ``device`` as soon as the layer is read and its bf16 tensors dropped, so
     the device never holds the bf16 and the quantised copies of all layers together. The checkpoint itself is bf16 / fp16
-    / fp32 either way: one that is already quantised on disk is treated as before. ``sliding_window``: serve the
+    / fp32 either way: one that is already quantised on disk is treated as before. ``chunk_attn``: ``TinyLlama``'s
+    (docs/CHUNK_ATTN.md). ``sliding_window``: serve the
     checkpoint's sliding attention window (``read_config``, docs/SLIDING_WINDOW.md), fused step only; a checkpoint
     that declares none is refused."""
     from p2p_llm_tunnel_amd.models.tiny_llm import WEIGHT_DTYPES, quantize_layer_
@@ -298,7 +300,7 @@ def load_llama(path: str, device="cuda", max_batch: int = 8, max_seq: int | None
     finally:
         rd.close()
     return TinyLlama.from_weights(cfg, w, device=dev, max_batch=max_batch, fused=fused, kv_dtype=kv_dtype,
-                                  weight_dtype=weight_dtype, kv_scales=kv_scales)
+                                  weight_dtype=weight_dtype, kv_scales=kv_scales, chunk_attn=chunk_attn)
 
 
 class Detokenizer:

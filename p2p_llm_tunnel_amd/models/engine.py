@@ -425,17 +425,26 @@ class Engine:
     samples launches ``ops.sample_minp_`` in place of ``ops.sample_``, and
     ``Sampling(min_p=)`` is honoured (docs/MIN_P.md). The number of graphs is
     what it is without the switch.
+
+    ``chunk_attn`` (off by default, and then nothing above changes; docs/CHUNK_ATTN.md):
+    the model's fused step attends with ``k_attn_chunk`` in steps of more than 16
+    rows, so the 64-row graphs capture that kernel and the 16-row ones what they
+    did. The number of graphs is what it is without the switch. A prompt row's
+    attention then sums in an order that depends on its tile-mates.
     """
 
     def __init__(self, device="cuda:0", config="tiny", max_batch=8, seed=0, use_graph=True, rows=64, model=None,
                  small_rows=16, prefix_cache=False, prefix_min=16, penalties=False, kv_dtype="bf16",
-                 guided=False, guided_states=1024, weight_dtype="bf16", kv_scales=None, min_p=False):
+                 guided=False, guided_states=1024, weight_dtype="bf16", kv_scales=None, min_p=False,
+                 chunk_attn=False):
         if kv_scales is not None and kv_dtype != "fp8" and getattr(model, "kv_dtype", "bf16") != "fp8":
             raise ValueError("kv_scales need kv_dtype='fp8' (--kv-dtype fp8): a bf16 KV cache has no scales")
         if model is None:
             from p2p_llm_tunnel_amd.models.tiny_llm import TinyLlama
             model = TinyLlama(config, device=device, max_batch=max_batch, seed=seed, fused=True, kv_dtype=kv_dtype,
-                              weight_dtype=weight_dtype, kv_scales=kv_scales)
+                              weight_dtype=weight_dtype, kv_scales=kv_scales, chunk_attn=bool(chunk_attn))
+        elif chunk_attn and not getattr(model, "chunk_attn", False):
+            raise ValueError("chunk_attn=True, but the injected model was built without it")
         elif kv_scales is not None and getattr(model, "kv_scales", None) != kv_scales:
             raise ValueError("kv_scales given, but the injected model was built with other scales or none")
         elif kv_dtype != "bf16" and getattr(model, "kv_dtype", "bf16") != kv_dtype:
@@ -469,13 +478,14 @@ class Engine:
         windowed = bool(getattr(getattr(model, "cfg", None), "windowed", False))  # attended by the fused HIP step alone
         for on, what in ((penalties, "penalties need"), (fp8, "an fp8 KV cache needs"), (w8, f"{getattr(model, 'weight_dtype', 'bf16')} weights need"),
                          (guided, "guided decoding needs"), (windowed, "a sliding window needs"),
-                         (min_p, "min_p needs")):
+                         (min_p, "min_p needs"), (getattr(model, "chunk_attn", False), "chunk_attn needs")):
             if on and not use_graph:
                 raise ValueError(f"{what} the graph-captured HIP step; this engine runs eagerly")
         self.penalties = bool(penalties)
         self.guided = bool(guided)
         self._held = None  # a guided request that waits for room in the arena (the head of the admission queue)
         self.min_p = bool(min_p)
+        self.chunk_attn = bool(getattr(model, "chunk_attn", False))
         self._smp, self._lp, self._pen_rows = _layout(self.min_p)
         in_rows = self._pen_rows.stop if self.penalties else self._lp + 1
         self._bufs = {R: [_StepBuf(R, cuda, lp_dev, in_rows), _StepBuf(R, cuda, lp_dev, in_rows)] for R in sizes}

@@ -782,7 +782,7 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
                  tokenizer=None, default_temperature: float = 0.0, prefix_cache: bool = False, prefix_min: int = 16,
                  embed_pooling: str = "mean", penalties: bool = False, kv_dtype: str = "bf16",
                  guided: bool = False, guided_states: int = 1024, weight_dtype: str = "bf16", kv_scales=None,
-                 sliding_window: bool = False, min_p: bool = False):
+                 sliding_window: bool = False, min_p: bool = False, chunk_attn: bool = False):
     """Engine + HTTP front-end; returns (server, port, engine). ``server.shutdown()``
     stops the HTTP side, ``engine.stop()`` the GPU side. ``checkpoint``: serve a
     Hugging Face Llama checkpoint directory (weights + tokenizer) instead of
@@ -806,7 +806,11 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
     model has windowed layers.
     ``min_p`` is ``Engine``'s: the endpoint then takes Ollama's "options.min_p" and a top-level "min_p" on the OpenAI
     routes (``sampling_params``, docs/MIN_P.md) instead of refusing the first and ignoring the second; an injected
-    engine must have been built with it."""
+    engine must have been built with it.
+    ``chunk_attn`` is ``Engine``'s and ``load_llama``'s (docs/CHUNK_ATTN.md): steps of more than 16 rows attend with
+    ``k_attn_chunk``; an injected engine's model must have been built with it."""
+    if engine is not None and chunk_attn and not getattr(engine, "chunk_attn", False):
+        raise ValueError("chunk_attn=True, but the injected engine was built without it")
     if engine is not None and min_p and not getattr(engine, "min_p", False):
         raise ValueError("min_p=True, but the injected engine was built without it")
     if sliding_window and engine is None and not checkpoint:
@@ -839,7 +843,8 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
         import os
         from p2p_llm_tunnel_amd.models.checkpoint import Tokenizer, load_llama
         model = load_llama(checkpoint, device=device, max_batch=max_batch, max_seq=max_seq, kv_dtype=kv_dtype,
-                           weight_dtype=weight_dtype, kv_scales=kv_scales, sliding_window=sliding_window)
+                           weight_dtype=weight_dtype, kv_scales=kv_scales, sliding_window=sliding_window,
+                           chunk_attn=chunk_attn)
         tok = tok or Tokenizer.for_checkpoint(checkpoint)
         engine = Engine(device=device, max_batch=max_batch, model=model, prefix_cache=prefix_cache,
                         prefix_min=prefix_min, penalties=penalties, guided=guided, guided_states=guided_states,
@@ -848,7 +853,7 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
     engine = engine or Engine(device=device, config=config, max_batch=max_batch, prefix_cache=prefix_cache,
                               prefix_min=prefix_min, penalties=penalties, kv_dtype=kv_dtype, guided=guided,
                               guided_states=guided_states, weight_dtype=weight_dtype, kv_scales=kv_scales,
-                              min_p=min_p)
+                              min_p=min_p, chunk_attn=chunk_attn)
     srv = FrontEnd(engine, host, port, model_name or f"p2pt-{config}", tokenizer=tok,
                    default_temperature=default_temperature, embed_pooling=embed_pooling)
     return srv, srv.server_address[1], engine
@@ -900,6 +905,12 @@ def min_p_line(engine) -> str:
     return "min_p: off (options.min_p other than 0 is answered with 400; start with --min-p)"
 
 
+def chunk_attn_line() -> str:
+    """The start-up log line of ``--chunk-attn``."""
+    return ("chunk attention: on (steps of more than 16 rows attend with k_attn_chunk, one K/V pass per 16-row tile; "
+            "a prompt row's attention sums in an order that depends on its tile-mates)")
+
+
 def window_line(model) -> str:
     """The start-up log line of ``--sliding-window``: the window, how many layers have one, and the context."""
     cfg = model.cfg
@@ -935,6 +946,8 @@ def replica_cmd(a, i: int) -> list[str]:
         cmd += ["--sliding-window"]
     if getattr(a, "min_p", False):
         cmd += ["--min-p"]
+    if getattr(a, "chunk_attn", False):
+        cmd += ["--chunk-attn"]
     return cmd
 
 
@@ -1025,6 +1038,12 @@ def arg_parser() -> argparse.ArgumentParser:
                          "instead of answering 400 / ignoring it: tokens less likely than min_p times the most likely "
                          "one are dropped on the device after top-k and top-p. Costs one more staged row per step; "
                          "the number of captured graphs stays (docs/MIN_P.md)")
+    ap.add_argument("--chunk-attn", action="store_true",
+                    help="prefill attention on MFMA: steps of more than 16 rows attend with k_attn_chunk, which reads "
+                         "a prompt chunk's K/V history once per 16-row tile instead of once per row. Off by default: "
+                         "a prompt row's attention then sums in an order that depends on the rows it shares a tile "
+                         "with, so batching can change its last fp32 bits. Decode-only steps are untouched and the "
+                         "number of captured graphs stays (docs/CHUNK_ATTN.md)")
     ap.add_argument("--guided", action="store_true",
                     help="guided decoding on the device: /v1/chat/completions and /v1/completions act on "
                          "guided_regex, guided_choice and structured_outputs {regex | choice} (a checkpoint with a "
@@ -1049,12 +1068,15 @@ def main(argv=None):
                                      prefix_cache=a.prefix_cache, prefix_min=a.prefix_min,
                                      embed_pooling=a.embed_pooling, penalties=a.penalties, kv_dtype=a.kv_dtype,
                                      guided=a.guided, guided_states=a.guided_states, weight_dtype=a.weight_dtype,
-                                     kv_scales=a.kv_scales, sliding_window=a.sliding_window, min_p=a.min_p)
+                                     kv_scales=a.kv_scales, sliding_window=a.sliding_window, min_p=a.min_p,
+                                     chunk_attn=a.chunk_attn)
     print(weights_line(engine.model, a.weight_dtype), flush=True)
     print(kv_cache_line(engine.model, a.kv_dtype), flush=True)
     if a.sliding_window:
         print(window_line(engine.model), flush=True)
     print(min_p_line(engine), flush=True)
+    if a.chunk_attn:
+        print(chunk_attn_line(), flush=True)
     print(f"inference endpoint on http://{a.host}:{port} ({a.checkpoint or a.config}, {a.device})", flush=True)
     try:
         threading.Event().wait()

@@ -183,8 +183,11 @@ def capture(fn, device, warmup: int = 2):
 class TinyLlama:
     def __init__(self, cfg: LlamaConfig | str = "tiny", device="cuda", max_batch: int = 8, seed: int = 0,
                  fused: bool = True, weights: dict | None = None, kv_dtype: str = "bf16",
-                 weight_dtype: str = "bf16", kv_scales: KvScales | None = None):
-        """``kv_dtype``: "bf16" (default) or "fp8": the K/V caches as ``torch.float8_e4m3fn`` (OCP e4m3, half the
+                 weight_dtype: str = "bf16", kv_scales: KvScales | None = None, chunk_attn: bool = False):
+        """``chunk_attn`` (off by default; docs/CHUNK_ATTN.md): steps of more than 16 rows attend with
+        ``k_attn_chunk``, one K/V pass per 16-row tile, on every layer without a window. Only the fused step has it.
+
+        ``kv_dtype``: "bf16" (default) or "fp8": the K/V caches as ``torch.float8_e4m3fn`` (OCP e4m3, half the
         bytes; docs/KV_FP8.md), which only the fused step reads and writes. ``kv_scales`` (a ``KvScales``; "fp8"
         only): fp32 scales per layer and KV head, so the stored byte is e4m3(x / s) and attention undoes the scale;
         None is scale 1.
@@ -214,6 +217,12 @@ class TinyLlama:
             kv_scales.check(self.cfg.n_layers, self.cfg.n_kv_heads, kv_dtype)
         self.kv_scales = kv_scales
         self.weight_dtype = weight_dtype
+        if not isinstance(chunk_attn, bool):
+            raise TypeError(f"chunk_attn must be a bool, got {chunk_attn!r}")
+        if chunk_attn and not fused:
+            raise ValueError("chunk_attn runs the fused step only (fused=True): the unfused path has no chunk "
+                             "attention kernel")
+        self.chunk_attn = chunk_attn
         self.lm_head_q = self.lm_head_s = None  # weight_dtype "fp8": the LM head's bytes and row scales
         self.fused = fused
         self._fused = None
@@ -271,9 +280,10 @@ class TinyLlama:
 
     @classmethod
     def from_weights(cls, cfg: LlamaConfig, weights: dict, device="cuda", max_batch: int = 8, fused: bool = True,
-                     kv_dtype: str = "bf16", weight_dtype: str = "bf16", kv_scales: KvScales | None = None):
+                     kv_dtype: str = "bf16", weight_dtype: str = "bf16", kv_scales: KvScales | None = None,
+                     chunk_attn: bool = False):
         return cls(cfg, device=device, max_batch=max_batch, fused=fused, weights=weights, kv_dtype=kv_dtype,
-                   weight_dtype=weight_dtype, kv_scales=kv_scales)
+                   weight_dtype=weight_dtype, kv_scales=kv_scales, chunk_attn=chunk_attn)
 
     def _quantize_weights(self):
         """``weight_dtype`` "fp8": every layer's GEMM weights and the LM head to e4m3 + row scales, one tensor at
@@ -421,7 +431,8 @@ class TinyLlama:
                                                 weight_format=self.weight_dtype,
                                                 kv_scales=(self.kv_scales.table(self.device)
                                                            if self.kv_scales is not None else None),
-                                                windows=self.cfg.windows if self.cfg.windowed else None)
+                                                windows=self.cfg.windows if self.cfg.windowed else None,
+                                                **({"chunk_attn": True} if self.chunk_attn else {}))
         return self._fused
 
     def step_rows(self, tokens, pos, slots=None, emit_rows=0, pos_range=None):
@@ -443,6 +454,9 @@ class TinyLlama:
         if self.weight_dtype != "bf16":
             raise ValueError(f"{self.weight_dtype} weights run the fused step only (at most {ops.MAX_ROWS} rows, "
                              "fused=True): the unfused path multiplies bf16 weights")
+        if self.chunk_attn:
+            raise ValueError(f"chunk_attn runs the fused step only (at most {ops.MAX_ROWS} rows, fused=True): "
+                             "the unfused path has no chunk attention kernel")
         if self.cfg.windowed:
             raise ValueError(f"a sliding window runs the fused step only (at most {ops.MAX_ROWS} rows, fused=True): "
                              "the unfused attention kernel reads every cached position")

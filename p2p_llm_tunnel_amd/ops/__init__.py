@@ -107,6 +107,13 @@ class WindowPlan(ctypes.Structure):
     _fields_ = [("win", _INT), ("window", _INT), ("slots", _INT)]
 
 
+class ChunkPlan(ctypes.Structure):
+    """Mirror of ``ChunkPlan``: what ``k_attn_chunk<D, G, KV8>`` launches for B rows (docs/CHUNK_ATTN.md), beside the
+    step's ``StepPlan`` as ``WindowPlan`` is: ``slots`` x ``grid_y`` workgroups of ``waves`` waves, ``grid_y`` =
+    ``tiles`` (16-row tiles) x Hkv; ``stride`` partial slots per head in part_o / part_ml, ``StepPlan.attn.stride``."""
+    _fields_ = [(n, _INT) for n in ("D", "G", "tiles", "slots", "stride", "grid_y", "waves")]
+
+
 def _signatures() -> dict:
     """Every symbol ``lib()`` binds -> its argtypes. The restype is ``c_int`` unless ``_RESTYPES`` names another."""
     vp, i, f, sz, ptr = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.POINTER
@@ -149,6 +156,10 @@ def _signatures() -> dict:
         "p2pt_llama_plan_kernels_fmt": [dims, i, i, wf, ip],
         "p2pt_llama_weight_layout_fmt": [dims, wf, ip, ip, i],
         "p2pt_llama_decode_fmt": [dims, wf, vp, ip, ptr(vp), vp, vp, vp, vp, vp, i, i, vp, sz, vp, vp, vp],
+        "p2pt_llama_chunk_plan": [dims, i, ptr(ChunkPlan)],
+        "p2pt_llama_plan_kernels_chunk": [dims, i, i, wf, ip, i],
+        "p2pt_llama_decode_chunk": [dims, wf, vp, ip, ptr(vp), vp, vp, vp, vp, vp, i, i, vp, sz, vp, vp, vp, i],
+        "p2pt_chunk_attention": [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, vp, vp, vp, vp, vp, vp, vp],
         "p2pt_attn_span": [i, i],
         "p2pt_max_rows": [],
         "p2pt_skinny_bench": [vp, vp, vp, i, i, i, i, i, i, vp],  # microbenchmark hooks (scripts/bench_skinny.py)
@@ -257,14 +268,30 @@ def window_plan(dims: LlamaDims, B: int, window: int) -> WindowPlan:
     return plan
 
 
+def chunk_plan(dims: LlamaDims, B: int) -> ChunkPlan:
+    """What a layer that runs chunk attention launches for attention at B rows (host only): ``k_attn_chunk``'s grid
+    and span slots. A decoder built with ``chunk_attn=True`` follows it on every layer without a window in steps of
+    more than 16 rows; everything else of the step is ``step_plan(dims, B)``."""
+    plan = ChunkPlan()
+    if lib().p2pt_llama_chunk_plan(ctypes.byref(dims), B, ctypes.byref(plan)) != 0:
+        raise ValueError("dims or row count not supported by the fused decode kernels")
+    return plan
+
+
 def plan_kernels_ok(dims: LlamaDims, B: int, emit_rows: int = 0, weight_fp8: bool = False, windows=None,
-                    weight_format=None) -> bool:
+                    weight_format=None, chunk_attn: bool = False) -> bool:
     """Whether every stage of ``step_plan(dims, B, emit_rows)``, ``kv_plan(dims)`` and
     ``weight_plan(dims, weight_fp8)`` names a kernel the library instantiates, by the lookups its launchers use
     (host only). ``windows``: the per-layer sliding windows (``check_windows``); every layer's ``window_plan`` is
-    then looked up too. ``weight_format`` (see ``as_weight_format``): the formats instead of ``weight_fp8``."""
+    then looked up too. ``weight_format`` (see ``as_weight_format``): the formats instead of ``weight_fp8``.
+    ``chunk_attn``: the layers that then run ``k_attn_chunk`` (``chunk_plan``) are looked up as that."""
     windows = check_windows(windows, dims.n_layers)
-    if weight_format is not None:
+    if chunk_attn:
+        f = as_weight_format(weight_fp8, weight_format)
+        rc = lib().p2pt_llama_plan_kernels_chunk(ctypes.byref(dims), B, emit_rows, ctypes.byref(f),
+                                                 (ctypes.c_int * len(windows))(*windows) if windows is not None else None,
+                                                 1)
+    elif weight_format is not None:
         f = as_weight_format(weight_fp8, weight_format)
         rc = lib().p2pt_llama_plan_kernels_fmt(ctypes.byref(dims), B, emit_rows, ctypes.byref(f),
                                                (ctypes.c_int * len(windows))(*windows) if windows is not None else None)
@@ -586,6 +613,59 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
     scale = 1.0 / math.sqrt(D) if scale is None else scale
     _ok(lib().p2pt_decode_attention(_p(q), _p(k_cache), _p(v_cache), _p(lens), _p(out), _p(ws), B, H, Hkv, D, Smax,
                                     nsplit, chunk, scale, _stream(q)), "decode_attention")
+    return out
+
+
+def chunk_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pos: torch.Tensor,
+                    slots: torch.Tensor | None = None, k_scale: torch.Tensor | None = None,
+                    v_scale: torch.Tensor | None = None) -> torch.Tensor:
+    """GQA attention of B <= 64 token rows over the KV cache with ``k_attn_chunk`` (docs/CHUNK_ATTN.md): one K/V pass
+    per 16-row tile and distinct slot in it. q: bf16 [B, H, D]; caches [nslots, Smax, Hkv, D], bf16 or FP8
+    (``KV_FP8_DTYPES``); row b reads slot ``slots[b]`` (int32 [B]; None: slot b) and attends to positions
+    0..``pos[b]`` (int32 [B]), both clamped into range by the kernel as ``k_attn`` clamps them. ``k_scale`` /
+    ``v_scale``: fp32 [Hkv] scales of an FP8 cache, both or neither. Returns bf16 [B, H, D]."""
+    _check(q, torch.bfloat16, "q")
+    kv8 = isinstance(k_cache, torch.Tensor) and k_cache.dtype in KV_FP8_DTYPES
+    _check(k_cache, k_cache.dtype if kv8 else torch.bfloat16, "k_cache", q.device)
+    _check(v_cache, k_cache.dtype, "v_cache", q.device)
+    _check(pos, torch.int32, "pos", q.device)
+    if q.dim() != 3 or k_cache.dim() != 4:
+        raise ValueError("q must be [B, H, D] and the caches [nslots, Smax, Hkv, D]")
+    B, H, D = q.shape
+    nslots, Smax, Hkv = k_cache.shape[:3]
+    if k_cache.shape != (nslots, Smax, Hkv, D) or v_cache.shape != k_cache.shape:
+        raise ValueError("cache shape mismatch")
+    if D not in (64, 128):
+        raise ValueError("head_dim must be 64 or 128")
+    if not 1 <= B <= MAX_ROWS:
+        raise ValueError(f"rows must be 1..{MAX_ROWS}")
+    if Hkv < 1 or H % Hkv or H // Hkv not in (1, 2, 4, 5, 6, 7, 8):
+        raise ValueError("n_heads / n_kv_heads must be one of 1, 2, 4, 5, 6, 7, 8")
+    if nslots < 1 or Smax < 1:
+        raise ValueError("the caches must hold at least one row")
+    if pos.shape != (B,):
+        raise ValueError("pos must be [B]")
+    if slots is not None:
+        _check(slots, torch.int32, "slots", q.device)
+        if slots.shape != (B,):
+            raise ValueError("slots must be [B]")
+    elif B > nslots:
+        raise ValueError("without slots, row b reads slot b: B must be <= nslots")
+    if (k_scale is None) != (v_scale is None) or (k_scale is not None and not kv8):
+        raise ValueError("k_scale and v_scale come together, and with an FP8 cache only")
+    for name, t in (("k_scale", k_scale), ("v_scale", v_scale)):
+        if t is not None:
+            _check(t, torch.float32, name, q.device)
+            if t.shape != (Hkv,):
+                raise ValueError(f"{name} must be [Hkv]")
+    stride = min(16, (Smax + 63) // 64)  # attn_part_stride: the most span slots a launch can have
+    part_o = torch.empty(B * H * stride * D, dtype=torch.float32, device=q.device)
+    part_ml = torch.empty(B * H * stride * 2, dtype=torch.float32, device=q.device)
+    counters = torch.zeros(((B + 15) // 16) * Hkv, dtype=torch.int32, device=q.device)
+    out = torch.empty_like(q)
+    _ok(lib().p2pt_chunk_attention(_p(q), _p(k_cache), _p(v_cache), _p(pos), _p(slots), B, H, Hkv, D, nslots, Smax,
+                                   int(kv8), _p(k_scale), _p(v_scale), _p(part_o), _p(part_ml), _p(counters), _p(out),
+                                   _stream(q)), "chunk_attention")
     return out
 
 
@@ -1132,14 +1212,23 @@ class FusedLlamaDecoder:
     ``k_attn<D, G, KV8, true>`` on ``window_plan``'s slots. Like the scales it is no part of ``dims``, of a plan or of
     the weight table, and None or all zeros runs the step exactly as before.
 
+    ``chunk_attn`` (docs/CHUNK_ATTN.md; off by default, and then nothing above changes): in a step of more than 16
+    rows, every layer without a window attends with ``k_attn_chunk`` on ``chunk_plan``'s grid, one K/V pass per 16-row
+    tile and distinct slot in it, instead of ``k_attn``'s one per row. Steps of up to 16 rows and windowed layers
+    launch what they did; ``step_plan`` and the workspace are the same.
+
     Holds the weight pointer table and a zero-initialised workspace; ``step``
     validates the per-call tensors and launches on the current stream (capturable
     into a hipGraph: no host sync, no allocation, grids sized by the row count).
     """
 
     def __init__(self, dims: LlamaDims, weights: list, k_cache: torch.Tensor, v_cache: torch.Tensor,
-                 weight_fp8: bool = False, kv_scales: torch.Tensor | None = None, windows=None, weight_format=None):
+                 weight_fp8: bool = False, kv_scales: torch.Tensor | None = None, windows=None, weight_format=None,
+                 chunk_attn: bool = False):
         self.dims = dims
+        if not isinstance(chunk_attn, bool):
+            raise TypeError(f"chunk_attn must be a bool, got {chunk_attn!r}")
+        self.chunk_attn = chunk_attn
         self.windows = check_windows(windows, dims.n_layers)
         self._windows = (ctypes.c_int * dims.n_layers)(*self.windows) if self.windows is not None else None
         self.weight_format = fmt = as_weight_format(weight_fp8, weight_format)
@@ -1297,6 +1386,12 @@ class FusedLlamaDecoder:
             raise ValueError(f"rows must be 1..{limit} with matching pos/ids")
         if logits.shape != (B, d.vocab):
             raise ValueError("logits must be [B, vocab]")
+        if self.chunk_attn:
+            _ok(lib().p2pt_llama_decode_chunk(ctypes.byref(d), ctypes.byref(self.weight_format), _p(self.kv_scales),
+                                              self._windows, self._wptr, _p(self.k_cache), _p(self.v_cache),
+                                              _p(tokens), _p(pos), _p(slots), B, emit_rows, _p(self.ws),
+                                              self.ws.numel(), _p(logits), _p(ids), _stream(tokens), 1), "llama_decode")
+            return
         if self.weight_format.layers != self.weight_format.lm_head:  # MXFP4: only the _fmt entry point says so
             _ok(lib().p2pt_llama_decode_fmt(ctypes.byref(d), ctypes.byref(self.weight_format), _p(self.kv_scales),
                                             self._windows, self._wptr, _p(self.k_cache), _p(self.v_cache), _p(tokens),

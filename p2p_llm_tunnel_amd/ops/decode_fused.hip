@@ -114,6 +114,26 @@ WindowPlan plan_window(const LlamaDims& d, int B, int window) {
   return {1, window, attn_window_slots(B, d.Hkv, d.max_seq, window)};
 }
 
+// Chunk attention (docs/CHUNK_ATTN.md), beside the plans as WindowPlan is and for the same reason: an opt-in that is no
+// field of LlamaDims or of a plan struct, so a step without it plans, lays out and launches what it did. What
+// k_attn_chunk<D, G, KV8> launches for B rows (mirrored with ctypes): (slots, tiles * Hkv) workgroups of `waves` waves.
+// The span slots are attn_slots' of the tile count in place of the row count, so within the partials' stride, which
+// stays AttnPlan's; the grid depends on (B, dims) alone.
+struct ChunkPlan {
+  int D, G;
+  int tiles;   // 16-row tiles: (B + 15) / 16
+  int slots;   // gridDim.x
+  int stride;  // partial slots per head in part_o / part_ml (attn_part_stride)
+  int grid_y;  // tiles * Hkv: counters[grid_y] are the tickets
+  int waves;   // per workgroup: one per query head of the KV head, 4 at least
+};
+ChunkPlan plan_attn_chunk(int B, int H, int Hkv, int D, int max_seq) {
+  const int tiles = (B + 15) >> 4, G = Hkv > 0 ? H / Hkv : 0;
+  return {D, G, tiles, attn_slots(tiles, Hkv, max_seq), attn_part_stride(max_seq), tiles * Hkv, chunk_waves(G)};
+}
+// Which layers of a step run it: the flag is set, the step has more than one row tile and the layer has no window.
+bool chunk_layer(int chunk_attn, int B, const WindowPlan& wn) { return chunk_attn && B > 16 && !wn.win; }
+
 // One workgroup per tn subtiles of 16 >> kpl columns of one 16-row tile.
 //  - K parts (GemmArgs::kpl), where asked for (the d_model-wide O and down
 //    projections): the widest tile (16, 8 or 4 columns) whose column tiles
@@ -399,6 +419,12 @@ AttnKernel attn_kernel(int D, int G, int kv8, int win = 0) {
        kv8, Flags{}, win, Flags{});
   return k;
 }
+using ChunkKernel = decltype(&k_attn_chunk<64, 1, false>);
+ChunkKernel chunk_kernel(int D, int G, int kv8) {
+  ChunkKernel k = nullptr;
+  pick([&](auto d, auto g, auto f8) { k = k_attn_chunk<d, g, f8 != 0>; }, D, HeadDims{}, G, GqaRatios{}, kv8, Flags{});
+  return k;
+}
 using QkNormKernel = void (*)(QkNormArgs);
 QkNormKernel qknorm_kernel(int D, int table, int kv8) {
   QkNormKernel k = nullptr;
@@ -406,6 +432,8 @@ QkNormKernel qknorm_kernel(int D, int table, int kv8) {
        kv8, Flags{});
   return k;
 }
+
+bool rows_ok(int B) { return B > 0 && B <= kMaxM; }
 
 // ------------------------------------------------------------ launches
 // Each checks its arguments, looks its kernel up and launches it; a plan that names no kernel is hipErrorInvalidValue.
@@ -449,6 +477,25 @@ hipError_t launch_attn(const AttnPlan& p, int kv8, const void* q, const void* kc
   return hipGetLastError();
 }
 
+// (span slot, 16-row tile x KV head) workgroups of k_attn_chunk for B rows; the arguments are launch_attn's. The
+// partials' stride must hold the slots, and the counters (kMaxM * H of them) the tickets.
+hipError_t launch_attn_chunk(const ChunkPlan& p, int kv8, const void* q, const void* kc, const void* vc, const int* pos,
+                             const int* slot, int B, int nslots, float* part_o, float* part_ml, unsigned* counters,
+                             void* out, int H, int Hkv, int Smax, hipStream_t s, const float* k_scale = nullptr,
+                             const float* v_scale = nullptr) {
+  const ChunkKernel k = chunk_kernel(p.D, p.G, kv8);
+  if (!k) return hipErrorInvalidValue;
+  if ((k_scale != nullptr) != (v_scale != nullptr) || (k_scale && !kv8)) return hipErrorInvalidValue;
+  if (!rows_ok(B) || p.tiles != (B + 15) >> 4 || p.grid_y != p.tiles * Hkv || p.G * Hkv != H) return hipErrorInvalidValue;
+  if (p.slots < 1 || p.slots > p.stride || p.waves != chunk_waves(p.G)) return hipErrorInvalidValue;
+  if ((!slot && B > nslots) || nslots < 1 || Smax < 1) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k, dim3(p.slots, p.grid_y), dim3(p.waves * 64), 0, s, static_cast<const uint16_t*>(q),
+                     static_cast<const uint16_t*>(kc), static_cast<const uint16_t*>(vc), pos, slot, B, nslots, part_o,
+                     part_ml, counters, static_cast<uint16_t*>(out), H, Hkv, Smax, p.stride, 1.f / sqrtf(float(p.D)),
+                     k_scale, v_scale);
+  return hipGetLastError();
+}
+
 // (row, head group) workgroups of k_qknorm_rope: grid_x groups of qknorm_heads_per_wg(D) heads.
 // table: the k_qknorm_rope<D, true> variant, which reads a.inv_freq (8-byte loads) and is refused without it.
 // kv8: the variants that append k and v to an e4m3 cache.
@@ -485,8 +532,6 @@ bool dims_ok(const LlamaDims& d) {
   if (d.max_batch <= 0 || d.max_seq <= 0 || d.n_layers <= 0) return false;
   return true;
 }
-
-bool rows_ok(int B) { return B > 0 && B <= kMaxM; }
 
 }  // namespace
 
@@ -534,7 +579,10 @@ int p2pt_llama_kv_plan(const LlamaDims* d, KvPlan* out) {
 // windows: the per-layer windows (Windows), nullptr for none: every layer's attention variant must exist, and a
 // windowed layer's slots must fit the partials' stride. A negative window is refused (-1).
 // fmt: the weight formats (WeightFormat); one that is no supported pair is refused (-1).
-int p2pt_llama_plan_kernels_fmt(const LlamaDims* d, int B, int emit_rows, const WeightFormat* fmt, const int* windows) {
+// chunk_attn (p2pt_llama_plan_kernels_chunk): the layers chunk_layer names need their k_attn_chunk instead, with its
+// slots inside the stride. p2pt_llama_plan_kernels_fmt is the call without it.
+int p2pt_llama_plan_kernels_chunk(const LlamaDims* d, int B, int emit_rows, const WeightFormat* fmt, const int* windows,
+                                  int chunk_attn) {
   if (!dims_ok(*d) || !rows_ok(B) || !format_ok(*fmt) || !windows_ok(*d, Windows{windows})) return -1;
   const StepPlan P = plan_step(*d, B, emit_rows);
   const KvPlan KV = plan_kv(*d);
@@ -542,6 +590,11 @@ int p2pt_llama_plan_kernels_fmt(const LlamaDims* d, int B, int emit_rows, const 
   bool attn = true;
   for (int L = 0; L < d->n_layers; L++) {
     const WindowPlan wn = plan_window(*d, B, Windows{windows}.at(L));
+    if (chunk_layer(chunk_attn, B, wn)) {
+      const ChunkPlan cp = plan_attn_chunk(B, d->H, d->Hkv, d->D, d->max_seq);
+      attn = attn && chunk_kernel(cp.D, cp.G, KV.attn_kv8) != nullptr && cp.slots >= 1 && cp.slots <= cp.stride;
+      continue;
+    }
     attn = attn && attn_kernel(P.attn.D, P.attn.G, KV.attn_kv8, wn.win) != nullptr && wn.slots >= 1 &&
            wn.slots <= P.attn.stride;
   }
@@ -555,6 +608,15 @@ int p2pt_llama_plan_kernels_fmt(const LlamaDims* d, int B, int emit_rows, const 
                         skinny_kernel(P.lm_head, fmt->lm_head) != nullptr};
   for (int n = 0; n < 8; n++)
     if (!found[n]) return 1 + n;
+  return 0;
+}
+int p2pt_llama_plan_kernels_fmt(const LlamaDims* d, int B, int emit_rows, const WeightFormat* fmt, const int* windows) {
+  return p2pt_llama_plan_kernels_chunk(d, B, emit_rows, fmt, windows, 0);
+}
+// What k_attn_chunk launches for B rows, beside the plans above (host only).
+int p2pt_llama_chunk_plan(const LlamaDims* d, int B, ChunkPlan* out) {
+  if (!dims_ok(*d) || !rows_ok(B)) return int(hipErrorInvalidValue);
+  *out = plan_attn_chunk(B, d->H, d->Hkv, d->D, d->max_seq);
   return 0;
 }
 // The same with one format for the five GEMMs (WeightPlan: bf16 or FP8; anything else is refused).
@@ -657,10 +719,14 @@ int p2pt_max_rows() { return kMaxM; }
 //      quantised after the fold and the interleave, and where the FP8 table has their row scales the e8m0 scale
 //      bytes [N][K / 32] of their 32-element blocks. lm_head and its fp32 row scales are the FP8 table's.
 //      p2pt_llama_decode_win is this call with {w8, w8}.
-int p2pt_llama_decode_fmt(const LlamaDims* dp, const WeightFormat* fmt, const float* kv_scales, const int* windows,
-                          const void* const* w, void* k_cache, void* v_cache, const int64_t* tokens, const int* pos,
-                          const int* slots, int B, int emit_rows, void* ws, size_t ws_bytes, void* logits,
-                          int64_t* ids, void* stream) {
+//   Chunk attention (p2pt_llama_decode_chunk with chunk_attn != 0; docs/CHUNK_ATTN.md): in a step of more than 16 rows,
+//      every layer without a window runs k_attn_chunk on ChunkPlan's grid instead of k_attn: one K/V pass per 16-row
+//      tile and distinct slot in it. Steps of up to 16 rows and windowed layers launch what they did, and so does
+//      chunk_attn = 0, which is p2pt_llama_decode_fmt. The workspace is the same.
+int p2pt_llama_decode_chunk(const LlamaDims* dp, const WeightFormat* fmt, const float* kv_scales, const int* windows,
+                            const void* const* w, void* k_cache, void* v_cache, const int64_t* tokens, const int* pos,
+                            const int* slots, int B, int emit_rows, void* ws, size_t ws_bytes, void* logits,
+                            int64_t* ids, void* stream, int chunk_attn) {
   const LlamaDims d = *dp;
   if (!dims_ok(d) || !rows_ok(B) || (!slots && B > d.max_batch) || !format_ok(*fmt)) return int(hipErrorInvalidValue);
   if (kv_scales && !d.kv_fp8) return int(hipErrorInvalidValue);
@@ -672,6 +738,7 @@ int p2pt_llama_decode_fmt(const LlamaDims* dp, const WeightFormat* fmt, const fl
   if (ws_bytes < W.bytes) return int(hipErrorInvalidValue);
   const StepPlan P = plan_step(d, B, emit_rows);
   const KvPlan KV = plan_kv(d);
+  const ChunkPlan CP = plan_attn_chunk(B, d.H, d.Hkv, d.D, d.max_seq);
   auto s = static_cast<hipStream_t>(stream);
   const size_t layer_cache = size_t(d.max_batch) * d.max_seq * d.Hkv * d.D * (d.kv_fp8 ? 1 : 2);  // bytes
   hipError_t e;
@@ -705,8 +772,13 @@ int p2pt_llama_decode_fmt(const LlamaDims* dp, const WeightFormat* fmt, const fl
         return int(e);
     }
     const WindowPlan wn = plan_window(d, B, WN.at(L));
-    if (failed(launch_attn(P.attn, KV.attn_kv8, W.q, kc, vc, pos, slots, d.max_batch, W.part_o, W.part_ml, W.counters, W.attn, d.H,
-                           d.Hkv, d.max_seq, s, KS.at(d, KvScales::K, L), KS.at(d, KvScales::V, L), &wn)))
+    if (chunk_layer(chunk_attn, B, wn)) {
+      if (failed(launch_attn_chunk(CP, KV.attn_kv8, W.q, kc, vc, pos, slots, B, d.max_batch, W.part_o, W.part_ml,
+                                   W.counters, W.attn, d.H, d.Hkv, d.max_seq, s, KS.at(d, KvScales::K, L),
+                                   KS.at(d, KvScales::V, L))))
+        return int(e);
+    } else if (failed(launch_attn(P.attn, KV.attn_kv8, W.q, kc, vc, pos, slots, d.max_batch, W.part_o, W.part_ml, W.counters, W.attn, d.H,
+                                  d.Hkv, d.max_seq, s, KS.at(d, KvScales::K, L), KS.at(d, KvScales::V, L), &wn)))
       return int(e);
     if (failed(launch(P.o, to_o, s, w8))) return int(e);
     if (failed(launch(P.gate_up, to_gate_up, s, w8))) return int(e);
@@ -718,6 +790,13 @@ int p2pt_llama_decode_fmt(const LlamaDims* dp, const WeightFormat* fmt, const fl
   if (failed(launch(P.lm_head, to_logits, s, fmt->lm_head))) return int(e);
   hipLaunchKernelGGL(k_argmax_merge, dim3(P.emit_rows), dim3(256), 0, s, W.am_val, W.am_idx, P.am_parts, ids);
   return int(hipGetLastError());
+}
+int p2pt_llama_decode_fmt(const LlamaDims* dp, const WeightFormat* fmt, const float* kv_scales, const int* windows,
+                          const void* const* w, void* k_cache, void* v_cache, const int64_t* tokens, const int* pos,
+                          const int* slots, int B, int emit_rows, void* ws, size_t ws_bytes, void* logits,
+                          int64_t* ids, void* stream) {
+  return p2pt_llama_decode_chunk(dp, fmt, kv_scales, windows, w, k_cache, v_cache, tokens, pos, slots, B, emit_rows, ws,
+                                 ws_bytes, logits, ids, stream, 0);
 }
 int p2pt_llama_decode_win(const LlamaDims* dp, const WeightPlan* wp, const float* kv_scales, const int* windows,
                           const void* const* w, void* k_cache, void* v_cache, const int64_t* tokens, const int* pos,
@@ -775,6 +854,20 @@ int p2pt_qk_norm_rope_cache(const void* qkv, const int* pos, const int* slots, c
   const int per_wg = qknorm_heads_per_wg(D);
   return int(launch_qknorm((H + 2 * Hkv + per_wg - 1) / per_wg, B, D, inv_freq != nullptr, false, a,
                            static_cast<hipStream_t>(stream)));
+}
+
+// Standalone chunk attention (ops.chunk_attention; tests, benchmarks): k_attn_chunk on caller tensors, for any B in
+// 1..64. q [B][H*D] bf16, caches [nslots][Smax][Hkv][D] (bf16, or e4m3 bytes with kv8), pos / slots int32 [B] (slots
+// nullptr: row b reads slot b, B <= nslots), k_scale / v_scale fp32 [Hkv] or both nullptr. part_o [B * H * stride * D]
+// and part_ml [B * H * stride * 2] fp32 with stride = attn_part_stride(Smax), counters [ceil(B / 16) * Hkv] zeroed;
+// out [B][H*D] bf16.
+int p2pt_chunk_attention(const void* q, const void* kc, const void* vc, const int* pos, const int* slots, int B, int H,
+                         int Hkv, int D, int nslots, int Smax, int kv8, const float* k_scale, const float* v_scale,
+                         float* part_o, float* part_ml, unsigned* counters, void* out, void* stream) {
+  if (!rows_ok(B) || Hkv <= 0 || H <= 0 || H % Hkv || Smax <= 0 || nslots <= 0) return int(hipErrorInvalidValue);
+  const ChunkPlan p = plan_attn_chunk(B, H, Hkv, D, Smax);
+  return int(launch_attn_chunk(p, kv8, q, kc, vc, pos, slots, B, nslots, part_o, part_ml, counters, out, H, Hkv, Smax,
+                               static_cast<hipStream_t>(stream), k_scale, v_scale));
 }
 
 // Microbenchmark hook (scripts/bench_skinny.py --attn): `reps` back-to-back

@@ -59,7 +59,15 @@ def main():
     ap.add_argument("--loop", action="store_true",
                     help="device-side autoregression: one graph = the fused step (ids feed the next step's "
                          "tokens in place) + pos += 1, no host copies per step")
+    ap.add_argument("--chunk-attn", action="store_true",
+                    help="chunk attention (docs/CHUNK_ATTN.md) on and off in this one process: a 64-row step whose "
+                         "rows are one slot's prefill chunk ending at --ctx, captured once per side, --windows "
+                         "alternating windows of --steps replays timed with device events; one JSON line per side "
+                         "with the K/V bytes attention must read per step")
+    ap.add_argument("--kv-dtype", choices=("bf16", "fp8"), default="bf16", help="KV cache format (with --chunk-attn)")
     a = ap.parse_args()
+    if a.chunk_attn:
+        return chunk_compare(a)
     if a.compare:
         return compare(a)
     if a.checkpoint:
@@ -157,6 +165,56 @@ def compare(a):
                           "ms_per_step": round(statistics.median(t), 4),
                           "greedy_agreement_with_" + formats[0]: float((agree[f] == agree[formats[0]]).float().mean()),
                           "lib": os.path.basename(__import__("p2p_llm_tunnel_amd").ops.loaded_path())}), flush=True)
+
+
+def chunk_compare(a):
+    """--chunk-attn: the 64-row prefill step with k_attn and with k_attn_chunk, same weights and caches, windows
+    alternating so that clock and temperature drift fall on both alike."""
+    import statistics
+    cfg = LlamaConfig(**json.loads(a.cfg)) if a.cfg else CONFIGS[a.config]
+    if a.set:
+        cfg = dataclasses.replace(cfg, **{k: int(v) for k, v in (x.split("=", 1) for x in a.set)})
+    cfg = dataclasses.replace(cfg, max_seq=max(cfg.max_seq, a.ctx))
+    name, R = a.name or (a.config if not a.cfg else "custom"), 64
+    base = TinyLlama(cfg, device="cuda", max_batch=1, kv_dtype=a.kv_dtype)
+    weights = dict(embed=base.embed, final_norm=base.final_norm, lm_head=base.lm_head, layers=base.layers)
+    models = {"off": base, "on": TinyLlama.from_weights(cfg, weights, device="cuda", max_batch=1, kv_dtype=a.kv_dtype,
+                                                         chunk_attn=True)}
+    models["on"].k_cache, models["on"].v_cache = base.k_cache, base.v_cache  # one cache: the step rewrites its own rows
+    for c in (base.k_cache, base.v_cache):
+        for layer in c:  # layer by layer: the fp32 draw of a whole 32k cache is large
+            layer.copy_((torch.randn(layer.shape, device="cuda") * 0.5).to(c.dtype))
+    tok = torch.randint(0, cfg.vocab, (R,), device="cuda")
+    pos = torch.arange(a.ctx - R, a.ctx, dtype=torch.int32, device="cuda")
+    slots = torch.zeros(R, dtype=torch.int32, device="cuda")
+    logits = torch.empty(R, cfg.vocab, dtype=torch.bfloat16, device="cuda")
+    ids = torch.empty(R, dtype=torch.int64, device="cuda")
+    graphs = {}
+    for side, m in models.items():
+        dec = m.fused_decoder()
+        graphs[side], _ = capture(lambda dec=dec: dec.step(tok, pos, logits, ids, slots, 1), m.device, warmup=1)
+    times = {side: [] for side in graphs}
+    for w in range(a.windows):
+        for side, g in graphs.items():
+            for _ in range(a.warmup):
+                g.replay()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(a.steps):
+                g.replay()
+            e1.record()
+            e1.synchronize()
+            times[side].append(e0.elapsed_time(e1) / a.steps)
+    # K and V bytes attention must read per step: every row's own history with k_attn, every 16-row tile's with the
+    # chunk kernel (the longest row's), over all KV heads and layers.
+    row_bytes = 2 * cfg.n_kv_heads * cfg.head_dim * (1 if a.kv_dtype == "fp8" else 2) * cfg.n_layers
+    need = {"off": sum(int(p) + 1 for p in pos.tolist()) * row_bytes,
+            "on": sum(int(pos[t + 15]) + 1 for t in range(0, R, 16)) * row_bytes}
+    for side, t in times.items():
+        ms = statistics.median(t)
+        print(json.dumps({"config": name, "rows": R, "ctx": a.ctx, "kv_dtype": a.kv_dtype, "chunk_attn": side == "on",
+                          "steps": a.steps, "ms_per_step_windows": [round(x, 4) for x in t], "ms_per_step": round(ms, 4),
+                          "attn_kv_bytes_per_step": need[side]}), flush=True)
 
 
 def loop(m, a):
