@@ -23,7 +23,15 @@ Name mapping (HF ``LlamaForCausalLM`` → ours, see ``tiny_llm.py``):
 ``...self_attn.q_norm.weight`` (Qwen3 only)              ``layers[i]["q_norm"]``
 ``...self_attn.k_norm.weight`` (Qwen3 only)              ``layers[i]["k_norm"]``
 ``...self_attn.{q,k,v}_proj.bias`` (Qwen2, concatenated)  ``layers[i]["bqkv"]``
+``...block_sparse_moe.gate.weight`` (Mixtral)            ``layers[i]["router"]``
+``...block_sparse_moe.experts.e.{w1,w3}.weight`` (cat.)  ``layers[i]["w_gate_up"][e]``
+``...block_sparse_moe.experts.e.w2.weight``              ``layers[i]["w_down"][e]``
 =====================================================  ===========================
+
+``MixtralForCausalLM`` is the Mistral layout with the MLP replaced by ``num_local_experts`` experts, of which a
+softmax router picks ``num_experts_per_tok`` per token and renormalises their probabilities
+(``LlamaConfig.n_experts``, ``top_k``; docs/MOE.md). Its experts are read and stacked one layer at a time. bf16
+expert weights and the fused step only. The Qwen MoE architectures stay refused.
 
 ``Qwen3ForCausalLM`` (dense) is the Llama layout plus a per-head RMSNorm over
 ``head_dim`` on q and k before RoPE (``LlamaConfig.qk_norm``); its ``head_dim``
@@ -60,10 +68,12 @@ import os
 
 import torch
 
+from p2p_llm_tunnel_amd import ops
 from p2p_llm_tunnel_amd.models import rope as rope_mod
 from p2p_llm_tunnel_amd.models.tiny_llm import LlamaConfig, TinyLlama
 
-_SUPPORTED = {"LlamaForCausalLM", "MistralForCausalLM", "Qwen2ForCausalLM", "Qwen3ForCausalLM"}
+_SUPPORTED = {"LlamaForCausalLM", "MistralForCausalLM", "Qwen2ForCausalLM", "Qwen3ForCausalLM", "MixtralForCausalLM"}
+_MOE = {"MixtralForCausalLM"}  # a routed-expert FFN: softmax over all experts, top-k, renormalised (docs/MOE.md)
 _QK_NORM = {"Qwen3ForCausalLM"}  # per-head RMSNorm on q and k before RoPE
 _QKV_BIAS = {"Qwen2ForCausalLM"}  # bias on q_proj, k_proj and v_proj, always (the config has no flag for it)
 _GQA_RATIOS = (1, 2, 4, 5, 6, 7, 8)  # the fused step's attention instantiations (decode_fused.hip: GqaRatios)
@@ -153,13 +163,25 @@ def read_config(path: str, max_seq: int | None = None, sliding_window: bool = Fa
                          + (f" = {heads // kv_heads}" if kv_heads > 0 and heads % kv_heads == 0 else "")
                          + f" is not supported by the decode kernels (num_attention_heads / num_key_value_heads "
                            f"must be one of {list(_GQA_RATIOS)})")
+    moe = {}
+    if arch in _MOE:
+        E, k = raw.get("num_local_experts"), raw.get("num_experts_per_tok")
+        for key, v in (("num_local_experts", E), ("num_experts_per_tok", k)):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError(f"{key} {v!r}: an MoE checkpoint needs an int >= 1")
+        if E > ops.MAX_EXPERTS:
+            raise ValueError(f"num_local_experts {E}: the routed-expert kernels serve at most {ops.MAX_EXPERTS} experts")
+        if k > min(ops.MAX_TOP_K, E):
+            raise ValueError(f"num_experts_per_tok {k}: the routed-expert kernels serve at most "
+                             f"min({ops.MAX_TOP_K}, num_local_experts) experts per token")
+        moe = {"n_experts": E, "top_k": k, "norm_topk": True}
     cfg = LlamaConfig(
         vocab=int(raw["vocab_size"]), dim=dim, n_layers=int(raw["num_hidden_layers"]), n_heads=heads,
         n_kv_heads=kv_heads, head_dim=int(raw.get("head_dim") or dim // heads),
         ffn=int(raw["intermediate_size"]),
         max_seq=int(max_seq or min(int(raw.get("max_position_embeddings", 2048)), 8192)),
         eps=float(raw.get("rms_norm_eps", 1e-5)), rope_theta=float(theta), qk_norm=arch in _QK_NORM,
-        qkv_bias=arch in _QKV_BIAS, rope_scaling=scaling, windows=windows)
+        qkv_bias=arch in _QKV_BIAS, rope_scaling=scaling, windows=windows, **moe)
     return cfg, raw
 
 
@@ -236,6 +258,9 @@ def load_llama(path: str, device="cuda", max_batch: int = 8, max_seq: int | None
     cfg, raw = read_config(path, max_seq, sliding_window)
     if cfg.windowed and not fused:
         raise ValueError("a sliding window runs the fused step only: load with fused=True")
+    if cfg.n_experts and weight_dtype != "bf16":
+        raise ValueError(f"an MoE checkpoint's expert weights are served as bf16 only: weight_dtype {weight_dtype!r} "
+                         "is not supported with a routed-expert FFN")
     c = cfg
     rd = _Reader(path)
     dev = torch.device(device)
@@ -275,16 +300,43 @@ def load_llama(path: str, device="cuda", max_batch: int = 8, max_seq: int | None
                 raise ValueError(f"{p}self_attn has q/k/v projection biases, but the architecture "
                                  f"{(raw.get('architectures') or ['LlamaForCausalLM'])[0]!r} applies none: attention "
                                  "projection biases are not supported for it, refusing to load it without them")
-            gate = t(p + "mlp.gate_proj.weight", (c.ffn, c.dim))
-            up = t(p + "mlp.up_proj.weight", (c.ffn, c.dim))
+            router = None
+            if c.n_experts:
+                # This layer's experts into two preallocated stacks on the device, one expert at a time: the host
+                # holds one expert's tensors, the device never two layers' worth of loose ones.
+                m = p + "block_sparse_moe."
+                router = t(m + "gate.weight", (c.n_experts, c.dim))
+                gate_up = torch.empty(c.n_experts, 2 * c.ffn, c.dim, dtype=torch.bfloat16, device=dev)
+                down = torch.empty(c.n_experts, c.dim, c.ffn, dtype=torch.bfloat16, device=dev)
+                for e in range(c.n_experts):
+                    x = f"{m}experts.{e}."
+                    for n in ("w1", "w2", "w3"):
+                        if not rd.has(x + n + ".weight"):
+                            raise KeyError(f"checkpoint has no tensor {x + n + '.weight'!r}: expert {e} of "
+                                           f"{c.n_experts} is missing")
+                        if rd.has(x + n + ".bias"):
+                            raise ValueError(f"{x}{n}.bias: expert biases are not supported by the decode kernels")
+                    gate_up[e, : c.ffn] = t(x + "w1.weight", (c.ffn, c.dim))
+                    gate_up[e, c.ffn:] = t(x + "w3.weight", (c.ffn, c.dim))
+                    down[e] = t(x + "w2.weight", (c.dim, c.ffn))
+                if rd.has(f"{m}experts.{c.n_experts}.w1.weight"):
+                    raise ValueError(f"{m}experts.{c.n_experts}: the checkpoint has more experts than "
+                                     f"num_local_experts ({c.n_experts})")
+                gate = up = None
+            else:
+                gate = t(p + "mlp.gate_proj.weight", (c.ffn, c.dim))
+                up = t(p + "mlp.up_proj.weight", (c.ffn, c.dim))
+                gate_up, down = torch.cat([gate, up], 0).contiguous(), t(p + "mlp.down_proj.weight", (c.dim, c.ffn))
             w["layers"].append({
                 "attn_norm": t(p + "input_layernorm.weight", (c.dim,)),
                 "wqkv": torch.cat([q, k, v], 0).contiguous(),
                 "wo": t(p + "self_attn.o_proj.weight", (c.dim, q_out)),
                 "ffn_norm": t(p + "post_attention_layernorm.weight", (c.dim,)),
-                "w_gate_up": torch.cat([gate, up], 0).contiguous(),
-                "w_down": t(p + "mlp.down_proj.weight", (c.dim, c.ffn)),
+                "w_gate_up": gate_up,
+                "w_down": down,
             })
+            if router is not None:
+                w["layers"][-1]["router"] = router
             if bqkv is not None:
                 w["layers"][-1]["bqkv"] = bqkv
             if c.qk_norm:

@@ -478,7 +478,8 @@ class Engine:
         windowed = bool(getattr(getattr(model, "cfg", None), "windowed", False))  # attended by the fused HIP step alone
         for on, what in ((penalties, "penalties need"), (fp8, "an fp8 KV cache needs"), (w8, f"{getattr(model, 'weight_dtype', 'bf16')} weights need"),
                          (guided, "guided decoding needs"), (windowed, "a sliding window needs"),
-                         (min_p, "min_p needs"), (getattr(model, "chunk_attn", False), "chunk_attn needs")):
+                         (min_p, "min_p needs"), (getattr(model, "chunk_attn", False), "chunk_attn needs"),
+                         (bool(getattr(getattr(model, "cfg", None), "n_experts", 0)), "an MoE model needs")):
             if on and not use_graph:
                 raise ValueError(f"{what} the graph-captured HIP step; this engine runs eagerly")
         self.penalties = bool(penalties)

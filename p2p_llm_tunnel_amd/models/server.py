@@ -885,7 +885,13 @@ def weights_line(model, weight_dtype: str) -> str:
     if not callable(sizes):
         return f"weights: ? bytes ({weight_dtype})"
     b = sizes()
-    return (f"weights: {b['total']} bytes ({weight_dtype} GEMM weights {b['gemm']}, bf16 embedding {b['embed']})")
+    line = f"weights: {b['total']} bytes ({weight_dtype} GEMM weights {b['gemm']}, bf16 embedding {b['embed']})"
+    c = getattr(model, "cfg", None)
+    if getattr(c, "n_experts", 0):  # the expert bytes one token reads: top_k of every layer's n_experts
+        expert = (2 * c.ffn * c.dim + c.dim * c.ffn) * 2
+        active = b["gemm"] - c.n_layers * (c.n_experts - c.top_k) * expert
+        line += f"; MoE: {c.n_experts} experts, top-{c.top_k}, {active} GEMM bytes active per token"
+    return line
 
 
 def kv_cache_line(model, kv_dtype: str) -> str:

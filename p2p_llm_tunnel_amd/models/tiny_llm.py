@@ -52,9 +52,17 @@ class LlamaConfig:
     # for a layer whose token at position p attends to positions (p - W, p]: W tokens, its own included. None and all
     # zeros are the decoder without windows.
     windows: tuple | None = None
+    # Routed-expert FFN (Mixtral; docs/MOE.md): n_experts > 0 makes every layer's FFN a mixture of n_experts experts
+    # of intermediate size ``ffn`` each, top_k of them per token by a softmax router; norm_topk renormalises the
+    # top_k probabilities to sum to one. 0 experts: the dense FFN.
+    n_experts: int = 0
+    top_k: int = 0
+    norm_topk: bool = True
     sliding_window: InitVar[int | None] = None  # shorthand: the same window on every layer (it sets ``windows``)
 
     def __post_init__(self, sliding_window):
+        if self.n_experts or self.top_k:
+            ops.check_moe(ops.MoeDims(self.n_experts, self.top_k, int(bool(self.norm_topk))), self.dim, self.ffn)
         if sliding_window is not None:
             if isinstance(sliding_window, bool) or not isinstance(sliding_window, int) or sliding_window < 1:
                 raise ValueError(f"sliding_window must be an int >= 1, got {sliding_window!r}")
@@ -70,6 +78,11 @@ class LlamaConfig:
             object.__setattr__(self, "windows", w)
 
     @property
+    def moe(self) -> "ops.MoeDims | None":
+        """The fused step's ``MoeDims`` of this model; None for a dense one."""
+        return ops.MoeDims(self.n_experts, self.top_k, int(bool(self.norm_topk))) if self.n_experts else None
+
+    @property
     def windowed(self) -> bool:
         """Whether any layer has a sliding window."""
         return bool(self.windows) and any(self.windows)
@@ -80,6 +93,8 @@ CONFIGS = {
     "micro": LlamaConfig(vocab=4096, dim=256, n_layers=2, n_heads=4, n_kv_heads=2, head_dim=64, ffn=512, max_seq=512),
     "small": LlamaConfig(vocab=32000, dim=2048, n_layers=8, n_heads=16, n_kv_heads=4, head_dim=128, ffn=5632,
                          max_seq=4096),
+    # tiny's attention with a Mixtral-style FFN: 8 experts of 1408, two per token (the FFN bytes a token reads: tiny's)
+    "tiny-moe": LlamaConfig(ffn=1408, n_experts=8, top_k=2),
 }
 
 
@@ -102,7 +117,7 @@ def fused_row_perm(cfg: "LlamaConfig", name: str, device) -> torch.Tensor | None
         heads = cfg.n_heads + 2 * cfg.n_kv_heads
         return (torch.arange(heads, device=device)[:, None] * cfg.head_dim
                 + _pairs(cfg.head_dim // 2, device)[None, :]).flatten()
-    if name == "w_gate_up":
+    if name == "w_gate_up":  # an MoE model's: the same order within every expert (dim 1 of the stack)
         return _pairs(cfg.ffn, device)
     return None
 
@@ -217,6 +232,12 @@ class TinyLlama:
             kv_scales.check(self.cfg.n_layers, self.cfg.n_kv_heads, kv_dtype)
         self.kv_scales = kv_scales
         self.weight_dtype = weight_dtype
+        if self.cfg.n_experts and weight_dtype != "bf16":
+            raise ValueError(f"an MoE model's expert weights are bf16 only: weight_dtype {weight_dtype!r} is not "
+                             "supported with a routed-expert FFN")
+        if self.cfg.n_experts and not fused:
+            raise ValueError("an MoE model runs the fused step only (fused=True): the unfused path has no "
+                             "routed-expert kernels")
         if not isinstance(chunk_attn, bool):
             raise TypeError(f"chunk_attn must be a bool, got {chunk_attn!r}")
         if chunk_attn and not fused:
@@ -245,6 +266,13 @@ class TinyLlama:
                 for i, L in enumerate(self.layers):
                     if "bqkv" not in L or tuple(L["bqkv"].shape) != (n_qkv,):
                         raise ValueError(f"layer {i}: a QKV-bias model needs bqkv of shape ({n_qkv},)")
+            if c.n_experts:
+                want = {"router": (c.n_experts, c.dim), "w_gate_up": (c.n_experts, 2 * c.ffn, c.dim),
+                        "w_down": (c.n_experts, c.dim, c.ffn)}
+                for i, L in enumerate(self.layers):
+                    for n, shape in want.items():
+                        if n not in L or tuple(L[n].shape) != shape:
+                            raise ValueError(f"layer {i}: an MoE model needs {n} of shape {shape}")
             self._quantize_weights()
             self._alloc_caches()
             return
@@ -257,6 +285,7 @@ class TinyLlama:
             return (1.0 + 0.1 * torch.randn(n, generator=g)).to(torch.bfloat16).to(self.device)
 
         qkv_out = (c.n_heads + 2 * c.n_kv_heads) * c.head_dim
+        experts = (c.n_experts,) if c.n_experts else ()  # an MoE model's FFN weights are stacked per expert
         self.embed = w(c.vocab, c.dim, scale=1.0)
         self.layers = []
         for _ in range(c.n_layers):
@@ -265,9 +294,11 @@ class TinyLlama:
                 "wqkv": w(qkv_out, c.dim, scale=1 / math.sqrt(c.dim)),
                 "wo": w(c.dim, c.n_heads * c.head_dim, scale=1 / math.sqrt(c.n_heads * c.head_dim)),
                 "ffn_norm": norm_w(c.dim),
-                "w_gate_up": w(2 * c.ffn, c.dim, scale=1 / math.sqrt(c.dim)),
-                "w_down": w(c.dim, c.ffn, scale=1 / math.sqrt(c.ffn)),
+                "w_gate_up": w(*experts, 2 * c.ffn, c.dim, scale=1 / math.sqrt(c.dim)),
+                "w_down": w(*experts, c.dim, c.ffn, scale=1 / math.sqrt(c.ffn)),
             })
+            if c.n_experts:  # logits of a few units, so that the routes of random tokens differ and are decided
+                self.layers[-1]["router"] = w(c.n_experts, c.dim, scale=2 / math.sqrt(c.dim))
             if c.qk_norm:  # drawn well away from 1 and from each other: a missing or swapped weight shows
                 for n in ("q_norm", "k_norm"):
                     self.layers[-1][n] = (0.5 + torch.rand(c.head_dim, generator=g)).to(torch.bfloat16).to(self.device)
@@ -414,12 +445,15 @@ class TinyLlama:
             if fp8 and (name in GEMM_WEIGHTS or name == "lm_head"):
                 return src[name + "_q"]
             w = src[name]
-            if name in FOLDED_NORM:
-                w = (w.float() * src[FOLDED_NORM[name]].float()[None, :]).to(torch.bfloat16)
+            if name in FOLDED_NORM or name == "router":  # the router reads the FFN-normed activation too
+                w = (w.float() * src[FOLDED_NORM.get(name, "ffn_norm")].float()[None, :]).to(torch.bfloat16)
             perm = fused_row_perm(c, name, self.device)
+            if perm is not None and w.dim() == 3:  # stacked experts: the row order within each
+                return w[:, perm].contiguous()
             return w[perm].contiguous() if perm is not None else w.contiguous() if name.endswith("_norm") else w
 
-        return [entry(e.name, e.layer) for e in ops.WeightTable(self.dims(), weight_format=self.weight_dtype)]
+        return [entry(e.name, e.layer)
+                for e in ops.WeightTable(self.dims(), weight_format=self.weight_dtype, moe=c.moe)]
 
     def dims(self) -> ops.LlamaDims:
         """The fused step's dims of this model: one cache slot per sequence and the scratch slot."""
@@ -432,7 +466,8 @@ class TinyLlama:
                                                 kv_scales=(self.kv_scales.table(self.device)
                                                            if self.kv_scales is not None else None),
                                                 windows=self.cfg.windows if self.cfg.windowed else None,
-                                                **({"chunk_attn": True} if self.chunk_attn else {}))
+                                                **({"chunk_attn": True} if self.chunk_attn else {}),
+                                                **({"moe": self.cfg.moe} if self.cfg.n_experts else {}))
         return self._fused
 
     def step_rows(self, tokens, pos, slots=None, emit_rows=0, pos_range=None):
@@ -628,10 +663,27 @@ class TinyLlama:
             o = bf(a @ self.reference_weight("wo", i).T)
             residual = bf(residual + o)
             h = bf(rms(residual, self._ref_norm(L["ffn_norm"])))
-            gu = bf(h @ self.reference_weight("w_gate_up", i).T)
-            g_, u_ = gu[..., : c.ffn], gu[..., c.ffn:]
-            m = bf(bf(F.silu(g_) * u_) @ self.reference_weight("w_down", i).T)
-            residual = bf(residual + m)
+            if c.n_experts:
+                # Softmax over all experts, top-k, renormalise, weighted sum: every expert on every token (these are
+                # small models), then each token's top_k gathered. The experts' outputs and their sum stay fp32,
+                # as k_moe_down and k_moe_combine keep them; the residual is rounded once.
+                probs = (h @ f32(L["router"]).T).softmax(-1)
+                tw, ti = probs.topk(c.top_k, dim=-1)
+                if c.norm_topk:
+                    tw = tw / tw.sum(-1, keepdim=True)
+                gu = bf(torch.einsum("btk,enk->bten", h, f32(L["w_gate_up"])))
+                act = bf(F.silu(gu[..., : c.ffn]) * gu[..., c.ffn:])
+                y = torch.einsum("btef,edf->bted", act, f32(L["w_down"]))
+                y = torch.gather(y, 2, ti[..., None].expand(-1, -1, -1, c.dim)) * tw[..., None]
+                m = y[:, :, 0]
+                for j in range(1, c.top_k):
+                    m = m + y[:, :, j]
+                residual = bf(residual + m)
+            else:
+                gu = bf(h @ self.reference_weight("w_gate_up", i).T)
+                g_, u_ = gu[..., : c.ffn], gu[..., c.ffn:]
+                m = bf(bf(F.silu(g_) * u_) @ self.reference_weight("w_down", i).T)
+                residual = bf(residual + m)
             nxt = self.layers[i + 1]["attn_norm"] if i + 1 < len(self.layers) else self.final_norm
             h = bf(rms(residual, self._ref_norm(nxt)))
         return h

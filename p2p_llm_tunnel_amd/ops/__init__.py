@@ -114,10 +114,56 @@ class ChunkPlan(ctypes.Structure):
     _fields_ = [(n, _INT) for n in ("D", "G", "tiles", "slots", "stride", "grid_y", "waves")]
 
 
+class MoeDims(ctypes.Structure):
+    """Mirror of ``MoeDims`` (decode_moe.h): the routed-expert FFN of a model, beside ``LlamaDims`` and the plans as
+    ``WeightFormat`` is (docs/MOE.md). ``n_experts`` E <= 128, ``top_k`` experts per token (<= min(8, E)),
+    ``norm_topk``: 1 when the top-k probabilities are renormalised to sum to one. With it ``dims.ffn`` is the
+    per-expert intermediate size."""
+    _fields_ = [("n_experts", _INT), ("top_k", _INT), ("norm_topk", _INT)]
+
+    def __repr__(self):
+        return f"MoeDims(n_experts={self.n_experts}, top_k={self.top_k}, norm_topk={self.norm_topk})"
+
+
+class MoePlan(ctypes.Structure):
+    """Mirror of ``MoePlan``: what the four kernels of an MoE layer launch for B rows. ``k_moe_route`` on
+    ``route_grid`` workgroups; ``k_moe_gate_up<gu_nw, gu_rt, gu_um>`` on ``gu_grid_x`` x ``gu_grid_y`` (column tiles x
+    experts), ``k_moe_down`` likewise; ``k_moe_combine`` on ``cb_grid`` workgroups of ``cb_cols`` columns, ``cb_grid``
+    being the ``ss_in`` of the next QKV GEMM and of the LM head."""
+    _fields_ = [(n, _INT) for n in ("route_grid", "route_waves", "gu_grid_x", "gu_grid_y", "gu_nw", "gu_rt", "gu_um",
+                                    "dn_grid_x", "dn_grid_y", "dn_nw", "dn_rt", "dn_um", "cb_grid", "cb_cols",
+                                    "cb_waves")]
+
+
+MAX_EXPERTS, MAX_TOP_K = 128, 8  # decode_moe.h's kMaxExperts and kMaxTopK
+
+
+def check_moe(moe, dim: int, ffn: int) -> "MoeDims | None":
+    """``moe`` as the fused step takes it: None (a dense model), or a ``MoeDims`` the kernels run for per-expert
+    shapes ``[2 * ffn, dim]`` and ``[dim, ffn]``. Every refusal says why (host only: no library)."""
+    if moe is None:
+        return None
+    if not isinstance(moe, MoeDims):
+        raise TypeError(f"moe must be an ops.MoeDims or None, got {type(moe).__name__}")
+    E, k = moe.n_experts, moe.top_k
+    if not 1 <= E <= MAX_EXPERTS:
+        raise ValueError(f"n_experts must be 1..{MAX_EXPERTS}, got {E}")
+    if not 1 <= k <= min(MAX_TOP_K, E):
+        raise ValueError(f"top_k must be 1..min({MAX_TOP_K}, n_experts), got {k} with {E} experts")
+    if moe.norm_topk not in (0, 1):
+        raise ValueError(f"norm_topk must be 0 or 1, got {moe.norm_topk}")
+    if dim % 32 or ffn % 32 or dim <= 0 or ffn <= 0:
+        raise ValueError(f"an expert's shapes must be multiples of 32 (whole k-steps), got dim {dim}, ffn {ffn}")
+    if 2 * ffn * dim * 2 >= GEMM_OPERAND_LIMIT:
+        raise ValueError(f"one expert's gate/up slice ({2 * ffn} x {dim} bf16) must stay below 2 GiB")
+    return MoeDims(E, k, moe.norm_topk)
+
+
 def _signatures() -> dict:
     """Every symbol ``lib()`` binds -> its argtypes. The restype is ``c_int`` unless ``_RESTYPES`` names another."""
     vp, i, f, sz, ptr = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.POINTER
     dims, wp, ip, szp, wf = ptr(LlamaDims), ptr(WeightPlan), ptr(i), ptr(sz), ptr(WeightFormat)
+    moe = ptr(MoeDims)
     return {
         "p2pt_rmsnorm": [vp, vp, vp, vp, vp, i, i, f, vp],
         "p2pt_silu_mul": [vp, vp, i, i, vp],
@@ -160,6 +206,14 @@ def _signatures() -> dict:
         "p2pt_llama_plan_kernels_chunk": [dims, i, i, wf, ip, i],
         "p2pt_llama_decode_chunk": [dims, wf, vp, ip, ptr(vp), vp, vp, vp, vp, vp, i, i, vp, sz, vp, vp, vp, i],
         "p2pt_chunk_attention": [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, vp, vp, vp, vp, vp, vp, vp],
+        "p2pt_llama_ws_bytes_moe": [dims, moe],
+        "p2pt_llama_ws_layout_moe": [dims, moe, szp, szp, i],
+        "p2pt_llama_moe_plan": [dims, moe, i, ptr(MoePlan)],
+        "p2pt_llama_plan_kernels_moe": [dims, i, i, wf, ip, i, moe],
+        "p2pt_llama_weight_layout_moe": [dims, moe, ip, i],
+        "p2pt_llama_decode_moe": [dims, wf, vp, ip, ptr(vp), vp, vp, vp, vp, vp, i, i, vp, sz, vp, vp, vp, i, moe],
+        "p2pt_moe_ffn": [vp, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, f, vp],
+        "p2pt_moe_ffn_plan": [i, i, i, i, i, i, ptr(MoePlan)],
         "p2pt_attn_span": [i, i],
         "p2pt_max_rows": [],
         "p2pt_skinny_bench": [vp, vp, vp, i, i, i, i, i, i, vp],  # microbenchmark hooks (scripts/bench_skinny.py)
@@ -167,7 +221,7 @@ def _signatures() -> dict:
     }
 
 
-_RESTYPES = {"p2pt_llama_ws_bytes": ctypes.c_size_t}
+_RESTYPES = {"p2pt_llama_ws_bytes": ctypes.c_size_t, "p2pt_llama_ws_bytes_moe": ctypes.c_size_t}
 
 
 def lib() -> ctypes.CDLL:
@@ -278,15 +332,31 @@ def chunk_plan(dims: LlamaDims, B: int) -> ChunkPlan:
     return plan
 
 
+def moe_plan(dims: LlamaDims, moe: MoeDims, B: int) -> MoePlan:
+    """What the routed-expert FFN's four kernels launch for B rows, beside ``step_plan(dims, B)`` (host only: the
+    library, no GPU). A function of (B, dims, moe) alone."""
+    plan = MoePlan()
+    moe = check_moe(moe, dims.dim, dims.ffn)
+    if moe is None or lib().p2pt_llama_moe_plan(ctypes.byref(dims), ctypes.byref(moe), B, ctypes.byref(plan)) != 0:
+        raise ValueError("dims, MoE dims or row count not supported by the fused decode kernels")
+    return plan
+
+
 def plan_kernels_ok(dims: LlamaDims, B: int, emit_rows: int = 0, weight_fp8: bool = False, windows=None,
-                    weight_format=None, chunk_attn: bool = False) -> bool:
+                    weight_format=None, chunk_attn: bool = False, moe: MoeDims | None = None) -> bool:
     """Whether every stage of ``step_plan(dims, B, emit_rows)``, ``kv_plan(dims)`` and
     ``weight_plan(dims, weight_fp8)`` names a kernel the library instantiates, by the lookups its launchers use
     (host only). ``windows``: the per-layer sliding windows (``check_windows``); every layer's ``window_plan`` is
     then looked up too. ``weight_format`` (see ``as_weight_format``): the formats instead of ``weight_fp8``.
     ``chunk_attn``: the layers that then run ``k_attn_chunk`` (``chunk_plan``) are looked up as that."""
     windows = check_windows(windows, dims.n_layers)
-    if chunk_attn:
+    moe = check_moe(moe, dims.dim, dims.ffn)
+    if moe is not None:  # the gate_up and down stages are then the four MoE kernels (``moe_plan``), bf16 layers only
+        f = as_weight_format(weight_fp8, weight_format)
+        rc = lib().p2pt_llama_plan_kernels_moe(ctypes.byref(dims), B, emit_rows, ctypes.byref(f),
+                                               (ctypes.c_int * len(windows))(*windows) if windows is not None else None,
+                                               int(chunk_attn), ctypes.byref(moe))
+    elif chunk_attn:
         f = as_weight_format(weight_fp8, weight_format)
         rc = lib().p2pt_llama_plan_kernels_chunk(ctypes.byref(dims), B, emit_rows, ctypes.byref(f),
                                                  (ctypes.c_int * len(windows))(*windows) if windows is not None else None,
@@ -332,10 +402,18 @@ class WeightTable(list):
     weight. A lane of ``k_skinny<.., W8 = 2>`` loads its 8 k-values of a k-step as the 4 bytes at
     ``n K / 2 + 16 s + 4 (lane >> 4)`` and the block's scale as the byte at ``n K / 32 + s``, so a weight is 4-byte
     aligned and its scales need no alignment. ``pack_weight_mxfp4`` makes this order from nibble codes ``[N][K]``,
-    ``unpack_weight_mxfp4`` undoes it, and decode_fused.hip's accessor and the kernel's offsets mirror it."""
+    ``unpack_weight_mxfp4`` undoes it, and decode_fused.hip's accessor and the kernel's offsets mirror it.
 
-    def __init__(self, dims: LlamaDims, weight_fp8: bool = False, weight_format=None):
+    ``moe`` (a ``MoeDims``; bf16 only, docs/MOE.md): ``dims.ffn`` is the per-expert size, w_gate_up is
+    ``(E, 2 * ffn, dim)``, folded and pair-interleaved per expert, w_down ``(E, dim, ffn)``, and every layer ends with
+    router, bf16 ``(E, dim)`` with the FFN norm folded in, 16-byte aligned. None: the dense table, unchanged."""
+
+    def __init__(self, dims: LlamaDims, weight_fp8: bool = False, weight_format=None, moe: MoeDims | None = None):
         self.format = fmt = as_weight_format(weight_fp8, weight_format)
+        self.moe = moe = check_moe(moe, dims.dim, dims.ffn)
+        if moe is not None and fmt.layers != 0:
+            raise ValueError("an MoE model's expert weights are bf16 only: weight_dtype fp8 and mxfp4 are not "
+                             "supported with a routed-expert FFN")
         d, bf, f32, u8 = dims, (torch.bfloat16,), (torch.float32,), (torch.uint8,)
         gemm, ga = (WEIGHT_FP8_DTYPES, 8) if fmt.lm_head else (bf, 2)
         n_qkv, norm = (d.H + 2 * d.Hkv) * d.D, (bf, (d.dim,), 2)
@@ -354,6 +432,10 @@ class WeightTable(list):
             layer.update(q_norm=(bf, (d.D,), 2), k_norm=(bf, (d.D,), 2))
         elif d.qkv_bias:
             layer["bqkv"] = (bf, (n_qkv,), 2)
+        if moe is not None:  # stacked experts (16-byte loads of a router row) and the router, after every other entry
+            layer["w_gate_up"] = (bf, (moe.n_experts, 2 * d.ffn, d.dim), 2)
+            layer["w_down"] = (bf, (moe.n_experts, d.dim, d.ffn), 2)
+            layer["router"] = (bf, (moe.n_experts, d.dim), 16)
         groups = [(None, top)] + [(L, layer) for L in range(d.n_layers)]
         super().__init__(WeightEntry(n, L, *v) for L, group in groups for n, v in group.items())
         if fmt.lm_head:  # the scales, in the order of their weights: fp32 per row, or MXFP4's e8m0 byte per block
@@ -667,6 +749,72 @@ def chunk_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tenso
                                    int(kv8), _p(k_scale), _p(v_scale), _p(part_o), _p(part_ml), _p(counters), _p(out),
                                    _stream(q)), "chunk_attention")
     return out
+
+
+def moe_ffn_plan(B: int, dim: int, ffn: int, moe: MoeDims) -> MoePlan:
+    """``moe_plan`` for the standalone op's shapes (host only)."""
+    plan, moe = MoePlan(), check_moe(moe, dim, ffn)
+    if moe is None or lib().p2pt_moe_ffn_plan(B, dim, ffn, moe.n_experts, moe.top_k, moe.norm_topk,
+                                              ctypes.byref(plan)) != 0:
+        raise ValueError("shapes, MoE dims or row count not supported by the MoE kernels")
+    return plan
+
+
+def moe_ffn(resid: torch.Tensor, ss: torch.Tensor, router: torch.Tensor, w_gate_up: torch.Tensor,
+            w_down: torch.Tensor, top_k: int, norm_topk: bool = True, eps: float = 1e-5, out: dict | None = None,
+            ss_in: int | None = None) -> dict:
+    """One routed-expert FFN layer on caller tensors, with the fused step's four kernels (docs/MOE.md):
+    ``resid += sum_j route_w[j] * down_e(SwiGLU(gate_up_e(rmsnorm(resid))))`` over each row's ``top_k`` experts.
+
+    resid: bf16 [B <= 64, dim], updated in place. ss: fp32 [parts, 64], partial sums of squares of resid's rows
+    (row b's sum is ``ss[:ss_in, b].sum()``; ``ss_in`` None: every row of ss), as the producer of the residual leaves
+    them; replaced by those of the new rows, ``ss[:cb_grid]`` of ``moe_ffn_plan``, so it needs at least ``cb_grid`` rows. router: bf16 [E, dim];
+    w_gate_up: bf16 [E, 2 * ffn, dim], rows interleaved (gate_j, up_j); w_down: bf16 [E, dim, ffn]; the router and
+    w_gate_up carry the norm weight folded into their columns. Returns the intermediates, each written in every slot
+    a (row, choice) pair owns: route_id int32 [B, top_k] (descending probability, ties to the lower id), route_w fp32
+    [B, top_k], route_rs fp32 [B], moe_h bf16 [B * top_k, ffn], moe_part fp32 [B, top_k, dim]. ``out``: tensors to
+    use for them instead of fresh ones (tests poison them)."""
+    _check(resid, torch.bfloat16, "resid")
+    dev = resid.device
+    for name, t in (("router", router), ("w_gate_up", w_gate_up), ("w_down", w_down)):
+        _check(t, torch.bfloat16, name, dev)
+    _check(ss, torch.float32, "ss", dev)
+    if resid.dim() != 2 or router.dim() != 2:
+        raise ValueError("resid must be [B, dim] and router [E, dim]")
+    (B, dim), E = resid.shape, router.shape[0]
+    if w_down.dim() != 3:
+        raise ValueError("w_down must be [E, dim, ffn]")
+    ffn = w_down.shape[2]
+    if not 1 <= B <= MAX_ROWS:
+        raise ValueError(f"rows must be 1..{MAX_ROWS}")
+    if not _int_in(top_k, 1, MAX_TOP_K + 1):
+        raise ValueError(f"top_k must be an int in 1..{MAX_TOP_K}, got {top_k!r}")
+    moe = check_moe(MoeDims(E, top_k, int(bool(norm_topk))), dim, ffn)
+    if router.shape != (E, dim) or w_gate_up.shape != (E, 2 * ffn, dim) or w_down.shape != (E, dim, ffn):
+        raise ValueError(f"expected router [{E}, {dim}], w_gate_up [{E}, {2 * ffn}, {dim}], w_down [{E}, {dim}, {ffn}]")
+    for name, t in (("resid", resid), ("router", router), ("w_gate_up", w_gate_up), ("w_down", w_down)):
+        if t.data_ptr() % 16:
+            raise ValueError(f"{name} must be 16-byte aligned")
+    plan = moe_ffn_plan(B, dim, ffn, moe)
+    if ss.dim() != 2 or ss.shape[1] != MAX_ROWS or ss.shape[0] < plan.cb_grid or ss.shape[0] < 1:
+        raise ValueError(f"ss must be fp32 [parts >= {plan.cb_grid}, {MAX_ROWS}]")
+    ss_in = ss.shape[0] if ss_in is None else ss_in
+    if not _int_in(ss_in, 1, ss.shape[0] + 1):
+        raise ValueError(f"ss_in must be an int in 1..{ss.shape[0]}, got {ss_in!r}")
+    want = {"route_id": (torch.int32, (B, top_k)), "route_w": (torch.float32, (B, top_k)),
+            "route_rs": (torch.float32, (B,)), "moe_h": (torch.bfloat16, (B * top_k, ffn)),
+            "moe_part": (torch.float32, (B, top_k, dim))}
+    res = {}
+    for name, (dtype, shape) in want.items():
+        t = out[name] if out is not None else torch.empty(shape, dtype=dtype, device=dev)
+        _check(t, dtype, name, dev)
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+        res[name] = t
+    _ok(lib().p2pt_moe_ffn(_p(resid), _p(ss), ss_in, _p(router), _p(w_gate_up), _p(w_down), _p(res["route_id"]),
+                           _p(res["route_w"]), _p(res["route_rs"]), _p(res["moe_h"]), _p(res["moe_part"]), B, dim, ffn,
+                           E, top_k, moe.norm_topk, eps, _stream(resid)), "moe_ffn")
+    return res
 
 
 def argmax(logits: torch.Tensor) -> torch.Tensor:
@@ -1217,6 +1365,11 @@ class FusedLlamaDecoder:
     tile and distinct slot in it, instead of ``k_attn``'s one per row. Steps of up to 16 rows and windowed layers
     launch what they did; ``step_plan`` and the workspace are the same.
 
+    ``moe`` (a ``MoeDims``; docs/MOE.md; None, and then nothing above changes): a routed-expert FFN. ``dims.ffn`` is
+    the per-expert size, the table is ``WeightTable(.., moe=moe)`` (stacked experts and a router per layer, bf16
+    only), and each layer's gate/up and down kernels give way to ``k_moe_route``, ``k_moe_gate_up``, ``k_moe_down`` and
+    ``k_moe_combine`` on ``moe_plan``'s grids: 7 kernels per layer, still one capturable call.
+
     Holds the weight pointer table and a zero-initialised workspace; ``step``
     validates the per-call tensors and launches on the current stream (capturable
     into a hipGraph: no host sync, no allocation, grids sized by the row count).
@@ -1224,8 +1377,9 @@ class FusedLlamaDecoder:
 
     def __init__(self, dims: LlamaDims, weights: list, k_cache: torch.Tensor, v_cache: torch.Tensor,
                  weight_fp8: bool = False, kv_scales: torch.Tensor | None = None, windows=None, weight_format=None,
-                 chunk_attn: bool = False):
+                 chunk_attn: bool = False, moe: MoeDims | None = None):
         self.dims = dims
+        self.moe = check_moe(moe, dims.dim, dims.ffn)
         if not isinstance(chunk_attn, bool):
             raise TypeError(f"chunk_attn must be a bool, got {chunk_attn!r}")
         self.chunk_attn = chunk_attn
@@ -1255,7 +1409,7 @@ class FusedLlamaDecoder:
                 raise ValueError(f"kv_scales must be fp32 [4, {dims.n_layers}, {dims.Hkv}] (1 / k, 1 / v, k, v per layer "
                                  f"and KV head), got {getattr(kv_scales, 'dtype', type(kv_scales))} "
                                  f"{tuple(getattr(kv_scales, 'shape', ()))}")
-        self.table = table = WeightTable(dims, weight_format=fmt)
+        self.table = table = WeightTable(dims, weight_format=fmt, moe=self.moe)
         if len(weights) != len(table):
             raise ValueError(f"weight table: embed, final_norm, lm_head, "
                              + ("inv_freq, " if dims.rope_table else "") + f"then {table.per_layer} per layer "
@@ -1265,7 +1419,9 @@ class FusedLlamaDecoder:
                              + ("; weight_fp8: then the fp32 row scales, lm_head's and four per layer"
                                 if self.weight_fp8 else "")
                              + ("; mxfp4: then lm_head's fp32 row scales and four e8m0 block-scale tensors per layer"
-                                if fmt.layers == 2 else ""))
+                                if fmt.layers == 2 else "")
+                             + ("; MoE: w_gate_up and w_down stacked per expert, and router last in every layer"
+                                if self.moe is not None else ""))
         # Every entry's dtype and shape, from the description alone: a refusal here needs no device. A weight shorter
         # than dims says would be read past its end (k_skinny sizes its descriptors from dims, k_embed indexes vocab
         # rows). The norm slots the kernels do not read are held to (dim,) too.
@@ -1311,9 +1467,19 @@ class FusedLlamaDecoder:
             if not bool((torch.isfinite(kv_scales) & (kv_scales > 0)).all().item()):
                 raise ValueError("kv_scales entries (and their reciprocals) must be finite and > 0")
         self.kv_scales = kv_scales  # keep alive
-        nbytes = lib().p2pt_llama_ws_bytes(ctypes.byref(dims))
+        if self.moe is not None:
+            nbytes = lib().p2pt_llama_ws_bytes_moe(ctypes.byref(dims), ctypes.byref(self.moe))
+        else:
+            nbytes = lib().p2pt_llama_ws_bytes(ctypes.byref(dims))
         if nbytes == 0:
             raise ValueError("model dims not supported by the fused decode kernels")
+        # The MoE kernels a step can name (RT follows the row count; waves and load batch the per-expert shapes): a
+        # plan without its instantiation is refused here with a message, not at the first launch with an error code.
+        for B in (1, 17, 33):
+            if self.moe is not None and not plan_kernels_ok(dims, B, windows=self.windows, weight_format=fmt,
+                                                            chunk_attn=chunk_attn, moe=self.moe):
+                raise ValueError(f"the fused decode kernels have no instantiation for a step of {B} rows of this "
+                                 f"MoE model ({self.moe!r}, dim {dims.dim}, ffn {dims.ffn})")
         self.weights = weights  # keep alive
         self._wptr = (ctypes.c_void_p * len(weights))(*[t.data_ptr() for t in weights])
         self.ws = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
@@ -1326,6 +1492,9 @@ class FusedLlamaDecoder:
                    ("ss", torch.float32), ("part_o", torch.float32), ("part_ml", torch.float32),
                    ("am_val", torch.float32), ("am_idx", torch.int32), ("counters", torch.int32),
                    ("qkv", torch.bfloat16))
+    # ... and those of an MoE model, which follow them (p2pt_llama_ws_layout_moe).
+    _WS_MOE_BUFFERS = (("route_id", torch.int32), ("route_w", torch.float32), ("route_rs", torch.float32),
+                       ("moe_h", torch.bfloat16), ("moe_part", torch.float32))
 
     def workspace_views(self) -> dict:
         """Typed, shaped views into the workspace (no copies; the layout comes from
@@ -1336,14 +1505,21 @@ class FusedLlamaDecoder:
         am_val [blocks, 64] (fp32); am_idx [blocks, 64], counters [64*H] (int32);
         qkv [64, (H+2*Hkv)*D] (bf16): the raw QKV projection of a QK-norm model's
         last layer, as ``k_qknorm_rope`` read it ([0, ...] for other models).
+        An MoE model adds its last layer's route_id, route_w [64, top_k], route_rs [64], moe_h [64 * top_k, ffn]
+        and moe_part [64, top_k, dim] (``moe_ffn``), and its h stays unwritten.
         Read them after a stream sync; only the first B rows of a step are defined."""
         d = self.dims
-        n = len(self._WS_BUFFERS)
+        buffers = self._WS_BUFFERS + (self._WS_MOE_BUFFERS if self.moe is not None else ())
+        n = len(buffers)
         off, cnt = (ctypes.c_size_t * n)(), (ctypes.c_size_t * n)()
-        if lib().p2pt_llama_ws_layout(ctypes.byref(d), off, cnt, n) != n:
+        if self.moe is not None:
+            got = lib().p2pt_llama_ws_layout_moe(ctypes.byref(d), ctypes.byref(self.moe), off, cnt, n)
+        else:
+            got = lib().p2pt_llama_ws_layout(ctypes.byref(d), off, cnt, n)
+        if got != n:
             raise RuntimeError("workspace layout: buffer list out of step with decode_fused.hip")
         views = {}
-        for (name, dtype), o, c in zip(self._WS_BUFFERS, off, cnt):
+        for (name, dtype), o, c in zip(buffers, off, cnt):
             size = torch.empty(0, dtype=dtype).element_size()
             if o % size or o + c * size > self.ws.numel():
                 raise RuntimeError(f"workspace layout: {name} lies outside the workspace")
@@ -1352,6 +1528,9 @@ class FusedLlamaDecoder:
         shapes = {"resid": (M, d.dim), "q": (M, d.H, d.D), "attn": (M, d.H * d.D), "h": (M, d.ffn), "ss": (-1, M),
                   "part_o": (M, d.H, -1, d.D), "part_ml": (M, d.H, -1, 2), "am_val": (-1, M), "am_idx": (-1, M),
                   "counters": (M * d.H,), "qkv": (M if d.qk_norm else 0, (d.H + 2 * d.Hkv) * d.D)}
+        if self.moe is not None:
+            k = self.moe.top_k
+            shapes.update(route_id=(M, k), route_w=(M, k), route_rs=(M,), moe_h=(M * k, d.ffn), moe_part=(M, k, d.dim))
         return {name: v.view(*shapes[name]) for name, v in views.items()}
 
     def embed_pool(self, acc: torch.Tensor, out: torch.Tensor, jobs) -> None:
@@ -1386,6 +1565,13 @@ class FusedLlamaDecoder:
             raise ValueError(f"rows must be 1..{limit} with matching pos/ids")
         if logits.shape != (B, d.vocab):
             raise ValueError("logits must be [B, vocab]")
+        if self.moe is not None:
+            _ok(lib().p2pt_llama_decode_moe(ctypes.byref(d), ctypes.byref(self.weight_format), _p(self.kv_scales),
+                                            self._windows, self._wptr, _p(self.k_cache), _p(self.v_cache), _p(tokens),
+                                            _p(pos), _p(slots), B, emit_rows, _p(self.ws), self.ws.numel(), _p(logits),
+                                            _p(ids), _stream(tokens), int(self.chunk_attn), ctypes.byref(self.moe)),
+                "llama_decode")
+            return
         if self.chunk_attn:
             _ok(lib().p2pt_llama_decode_chunk(ctypes.byref(d), ctypes.byref(self.weight_format), _p(self.kv_scales),
                                               self._windows, self._wptr, _p(self.k_cache), _p(self.v_cache),

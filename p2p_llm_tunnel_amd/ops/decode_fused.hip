@@ -4,6 +4,7 @@
 // lookups and launches that follow a plan into that set, and the C entry
 // points. The kernels and the design notes are in decode_fused_kernels.h.
 #include "decode_fused_kernels.h"
+#include "decode_moe.h"
 
 #include <type_traits>
 #include <utility>
@@ -134,6 +135,19 @@ ChunkPlan plan_attn_chunk(int B, int H, int Hkv, int D, int max_seq) {
 // Which layers of a step run it: the flag is set, the step has more than one row tile and the layer has no window.
 bool chunk_layer(int chunk_attn, int B, const WindowPlan& wn) { return chunk_attn && B > 16 && !wn.win; }
 
+// The routed-expert FFN (docs/MOE.md), beside the plans as WeightFormat, KvScales, Windows and ChunkPlan are and for the
+// same reason: MoeDims is no field of LlamaDims or of a plan struct, so a dense model (moe == nullptr everywhere below)
+// plans, lays out and launches what it did. With it, LlamaDims::ffn is the per-expert intermediate size.
+using p2pt_moe::MoeDims;
+using p2pt_moe::MoePlan;
+bool moe_ok(const LlamaDims& d, const MoeDims& m) {
+  if (m.n_experts < 1 || m.n_experts > p2pt_moe::kMaxExperts) return false;
+  if (m.top_k < 1 || m.top_k > std::min(p2pt_moe::kMaxTopK, m.n_experts)) return false;
+  if (m.norm_topk != 0 && m.norm_topk != 1) return false;
+  // Per-expert shapes are k_skinny's: whole k-steps of dim and ffn_e, 16-column tiles of [2 ffn_e] and [dim], and
+  // each expert's slice below kOob (dims_ok holds d.ffn, the per-expert size, to exactly these).
+  return d.dim % 32 == 0 && d.ffn % 32 == 0 && size_t(2) * d.ffn * d.dim * 2 < kOob;
+}
 // One workgroup per tn subtiles of 16 >> kpl columns of one 16-row tile.
 //  - K parts (GemmArgs::kpl), where asked for (the d_model-wide O and down
 //    projections): the widest tile (16, 8 or 4 columns) whose column tiles
@@ -166,6 +180,22 @@ GemmPlan plan_gemm(int epi, int tn, int M, int N, int K, bool k_parts = false, i
 // 4 waves x 2 subtiles: the fastest LM-head shape measured (vocab 32000, K 2048: 22.6 vs 29.6 us).
 GemmPlan plan_lm_head(const LlamaDims& d, int rows) {
   return plan_gemm(EPI_ARGMAX, kTnStore, rows, d.vocab, d.dim, false, 4);
+}
+
+// What the four kernels launch for B rows: a pure function of (B, dims, moe). Waves and load batch follow plan_gemm's
+// rule for the expert's own K; the row tiles held per weight pass cover B pairs, the most one expert gets when a row
+// names it once; k_moe_combine's grid is the dense down projection's, so the next norm's readers keep their ss_in.
+MoePlan plan_moe(const LlamaDims& d, const MoeDims& m, int B) {
+  MoePlan p{};
+  const GemmPlan gu = plan_gemm(EPI_SILU, 1, B, 2 * d.ffn, d.dim), dn = plan_gemm(EPI_RESID, 1, B, d.dim, d.ffn);
+  const GemmPlan dense_down = plan_gemm(EPI_RESID, kTnResid, B, d.dim, d.ffn, true);
+  const int rt = B <= 16 ? 1 : B <= 32 ? 2 : 4;
+  p.route_grid = B, p.route_waves = p2pt_moe::kRouteWaves;
+  p.gu_grid_x = gu.grid_x, p.gu_grid_y = m.n_experts, p.gu_nw = gu.nw, p.gu_rt = rt, p.gu_um = gu.um;
+  p.dn_grid_x = dn.grid_x, p.dn_grid_y = m.n_experts, p.dn_nw = dn.nw, p.dn_rt = rt, p.dn_um = dn.um;
+  p.cb_grid = dense_down.grid_x, p.cb_cols = dense_down.grid_x > 0 ? d.dim / dense_down.grid_x : 0;
+  p.cb_waves = p2pt_moe::kCombineWaves;
+  return p;
 }
 
 AttnPlan plan_attn(int B, int H, int Hkv, int D, int max_seq) {
@@ -204,25 +234,30 @@ StepPlan plan_step(const LlamaDims& d, int B, int emit_rows) {
 size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
 struct Workspace {
-  uint16_t *resid, *q, *attn, *h, *qkv;
-  float *ss, *part_o, *part_ml, *am_val;
-  int* am_idx;
+  uint16_t *resid, *q, *attn, *h, *qkv, *moe_h;
+  float *ss, *part_o, *part_ml, *am_val, *route_w, *route_rs, *moe_part;
+  int *am_idx, *route_id;
   unsigned* counters;  // [kMaxM * H] attention split tickets (self-resetting)
   size_t bytes;
 };
 
 // The workspace buffers in layout order (p2pt_llama_ws_layout reports them in this order).
-enum WsBuf : int { WS_RESID, WS_Q, WS_ATTN, WS_H, WS_SS, WS_PART_O, WS_PART_ML, WS_AM_VAL, WS_AM_IDX, WS_COUNTERS, WS_QKV, WS_NBUF };
+// The routed-expert FFN's buffers follow WS_QKV and are empty without MoeDims; WS_NDENSE counts the buffers
+// p2pt_llama_ws_layout reports, WS_NBUF those of p2pt_llama_ws_layout_moe.
+enum WsBuf : int { WS_RESID, WS_Q, WS_ATTN, WS_H, WS_SS, WS_PART_O, WS_PART_ML, WS_AM_VAL, WS_AM_IDX, WS_COUNTERS, WS_QKV,
+                   WS_NDENSE, WS_ROUTE_ID = WS_NDENSE, WS_ROUTE_W, WS_ROUTE_RS, WS_MOE_H, WS_MOE_PART, WS_NBUF };
 
 struct WsLayout {
   size_t off[WS_NBUF];    // byte offset from the workspace base (256-byte aligned)
-  size_t count[WS_NBUF];  // elements: bf16 resid/q/attn/h/qkv, fp32 ss/part_o/part_ml/am_val, int32 am_idx, uint32 counters
+  // elements: bf16 resid/q/attn/h/qkv/moe_h, fp32 ss/part_o/part_ml/am_val/route_w/route_rs/moe_part, int32 am_idx/route_id,
+  // uint32 counters
+  size_t count[WS_NBUF];
   size_t bytes;
 };
 
 // The one place that knows the workspace layout. The counts that depend on a
 // grid are the plan's own, at their worst case over the row count.
-WsLayout ws_layout(const LlamaDims& d) {
+WsLayout ws_layout(const LlamaDims& d, const MoeDims* moe = nullptr) {
   WsLayout l{};
   size_t off = 0;
   auto take = [&](WsBuf b, size_t count, size_t elem) {
@@ -245,12 +280,20 @@ WsLayout ws_layout(const LlamaDims& d) {
   take(WS_COUNTERS, size_t(kMaxM * d.H), 4);
   // The raw QKV projection of a QK-norm model; empty otherwise (the layout of other models is unchanged).
   take(WS_QKV, d.qk_norm ? size_t(kMaxM) * (d.H + 2 * d.Hkv) * d.D : 0, 2);
+  // The routed-expert FFN: the route of every row, one moe_h row and one moe_part row per (row, choice) pair. Empty
+  // without MoeDims, and after everything else, so the offsets and the size of a dense model are unchanged.
+  const size_t pairs = moe ? size_t(kMaxM) * moe->top_k : 0;
+  take(WS_ROUTE_ID, pairs, 4);
+  take(WS_ROUTE_W, pairs, 4);
+  take(WS_ROUTE_RS, moe ? kMaxM : 0, 4);
+  take(WS_MOE_H, pairs * d.ffn, 2);
+  take(WS_MOE_PART, pairs * d.dim, 4);
   l.bytes = off;
   return l;
 }
 
-Workspace carve(const LlamaDims& d, uint8_t* base) {
-  const WsLayout l = ws_layout(d);
+Workspace carve(const LlamaDims& d, uint8_t* base, const MoeDims* moe = nullptr) {
+  const WsLayout l = ws_layout(d, moe);
   Workspace w{};
   auto at = [&](WsBuf b) { return base ? base + l.off[b] : nullptr; };
   w.resid = reinterpret_cast<uint16_t*>(at(WS_RESID));
@@ -264,6 +307,11 @@ Workspace carve(const LlamaDims& d, uint8_t* base) {
   w.am_idx = reinterpret_cast<int*>(at(WS_AM_IDX));
   w.counters = reinterpret_cast<unsigned*>(at(WS_COUNTERS));
   w.qkv = reinterpret_cast<uint16_t*>(at(WS_QKV));
+  w.route_id = reinterpret_cast<int*>(at(WS_ROUTE_ID));
+  w.route_w = reinterpret_cast<float*>(at(WS_ROUTE_W));
+  w.route_rs = reinterpret_cast<float*>(at(WS_ROUTE_RS));
+  w.moe_h = reinterpret_cast<uint16_t*>(at(WS_MOE_H));
+  w.moe_part = reinterpret_cast<float*>(at(WS_MOE_PART));
   w.bytes = l.bytes;
   return w;
 }
@@ -275,13 +323,17 @@ Workspace carve(const LlamaDims& d, uint8_t* base) {
 // fp32 row scales: lm_head's, then per layer wqkv's, wo's, w_gate_up's and w_down's. An MXFP4 table has the same
 // entries: lm_head as in an FP8 table, each layer GEMM as N * K / 2 bytes, and after the table lm_head's fp32 row
 // scales, then per layer the four e8m0 scale tensors [N][K / 32] where the FP8 table has row scales.
+// An MoE table (moe set; bf16 only) has one more entry per layer, after every other: router, bf16 [E][dim] with the FFN
+// norm folded in; its w_gate_up is [E][2 ffn_e][dim], folded and pair-interleaved per expert, and its w_down
+// [E][dim][ffn_e]. R_ROUTER follows R_NROLES so that p2pt_llama_weight_layout's 13 roles per layer stay what they are.
 enum Role : int { R_EMBED, R_FINAL_NORM, R_LM_HEAD, R_INV_FREQ, R_ATTN_NORM, R_WQKV, R_WO, R_FFN_NORM, R_W_GATE_UP,
-                  R_W_DOWN, R_BQKV, R_Q_NORM, R_K_NORM, R_NROLES };
+                  R_W_DOWN, R_BQKV, R_Q_NORM, R_K_NORM, R_NROLES, R_ROUTER = R_NROLES, R_NROLES_MOE };
 struct WeightTable {
   LlamaDims d;
   WeightFormat f;
   const void* const* w;
-  int per_layer() const { return d.qk_norm ? 8 : d.qkv_bias ? 7 : 6; }
+  int moe = 0;  // the layers carry a router
+  int per_layer() const { return (d.qk_norm ? 8 : d.qkv_bias ? 7 : 6) + moe; }
   int scales0() const { return 3 + d.rope_table + per_layer() * d.n_layers; }
   int size() const { return scales0() + (f.lm_head ? 1 + 4 * d.n_layers : 0); }
   // The format of a GEMM weight's role (0 for every other role).
@@ -294,6 +346,7 @@ struct WeightTable {
     if (r == R_INV_FREQ) return d.rope_table ? 3 : -1;
     const int base = 3 + d.rope_table + per_layer() * L;
     if (r <= R_W_DOWN) return base + (r - R_ATTN_NORM);
+    if (r == R_ROUTER) return moe ? base + per_layer() - 1 : -1;
     if (r == R_BQKV) return d.qkv_bias && !d.qk_norm ? base + 6 : -1;
     return d.qk_norm ? base + 6 + (r - R_Q_NORM) : -1;
   }
@@ -549,13 +602,34 @@ size_t p2pt_llama_ws_bytes(const LlamaDims* d) {
 // part_ml, am_val, am_idx, counters, qkv (empty unless qk_norm), in that order, into off[n] / count[n].
 // Returns the number of buffers, or 0 for unsupported dims or n too small.
 int p2pt_llama_ws_layout(const LlamaDims* d, size_t* off, size_t* count, int n) {
-  if (!dims_ok(*d) || n < WS_NBUF) return 0;
+  if (!dims_ok(*d) || n < WS_NDENSE) return 0;
   const WsLayout l = ws_layout(*d);
+  for (int b = 0; b < WS_NDENSE; b++) {
+    off[b] = l.off[b];
+    count[b] = l.count[b];
+  }
+  return WS_NDENSE;
+}
+// The same for a step with a routed-expert FFN (moe; nullptr: a dense model, whose first eleven buffers and size are
+// those above): route_id, route_w, route_rs, moe_h, moe_part follow qkv. Returns the number of buffers (16), or 0.
+size_t p2pt_llama_ws_bytes_moe(const LlamaDims* d, const MoeDims* moe) {
+  if (!dims_ok(*d) || (moe && !moe_ok(*d, *moe))) return 0;
+  return ws_layout(*d, moe).bytes;
+}
+int p2pt_llama_ws_layout_moe(const LlamaDims* d, const MoeDims* moe, size_t* off, size_t* count, int n) {
+  if (!dims_ok(*d) || (moe && !moe_ok(*d, *moe)) || n < WS_NBUF) return 0;
+  const WsLayout l = ws_layout(*d, moe);
   for (int b = 0; b < WS_NBUF; b++) {
     off[b] = l.off[b];
     count[b] = l.count[b];
   }
   return WS_NBUF;
+}
+// What the routed-expert FFN's four kernels launch for B rows, beside the plans below (host only).
+int p2pt_llama_moe_plan(const LlamaDims* d, const MoeDims* moe, int B, MoePlan* out) {
+  if (!dims_ok(*d) || !moe_ok(*d, *moe) || !rows_ok(B)) return int(hipErrorInvalidValue);
+  *out = plan_moe(*d, *moe, B);
+  return 0;
 }
 
 // What p2pt_llama_decode launches for B rows (host only: no device is touched).
@@ -581,9 +655,13 @@ int p2pt_llama_kv_plan(const LlamaDims* d, KvPlan* out) {
 // fmt: the weight formats (WeightFormat); one that is no supported pair is refused (-1).
 // chunk_attn (p2pt_llama_plan_kernels_chunk): the layers chunk_layer names need their k_attn_chunk instead, with its
 // slots inside the stride. p2pt_llama_plan_kernels_fmt is the call without it.
-int p2pt_llama_plan_kernels_chunk(const LlamaDims* d, int B, int emit_rows, const WeightFormat* fmt, const int* windows,
-                                  int chunk_attn) {
+// moe (p2pt_llama_plan_kernels_moe): stages gate_up and down are then the routed-expert FFN's kernels (all four must
+// exist), bf16 layers only; a MoeDims the step refuses, or FP8 / MXFP4 layers with it, are -1. nullptr: the call without.
+int p2pt_llama_plan_kernels_moe(const LlamaDims* d, int B, int emit_rows, const WeightFormat* fmt, const int* windows,
+                                int chunk_attn, const MoeDims* moe) {
   if (!dims_ok(*d) || !rows_ok(B) || !format_ok(*fmt) || !windows_ok(*d, Windows{windows})) return -1;
+  if (moe && (!moe_ok(*d, *moe) || fmt->layers != 0)) return -1;
+  const bool moe_found = !moe || p2pt_moe::moe_kernels_exist(plan_moe(*d, *moe, B));
   const StepPlan P = plan_step(*d, B, emit_rows);
   const KvPlan KV = plan_kv(*d);
   const int w8 = fmt->layers;
@@ -603,12 +681,16 @@ int p2pt_llama_plan_kernels_chunk(const LlamaDims* d, int B, int emit_rows, cons
                         !P.qk_norm_grid || qknorm_kernel(d->D, P.qk_norm_table, KV.qk_norm_kv8) != nullptr,
                         attn,
                         skinny_kernel(P.o, w8) != nullptr,
-                        skinny_kernel(P.gate_up, w8) != nullptr,
-                        skinny_kernel(P.down, w8) != nullptr,
+                        moe ? moe_found : skinny_kernel(P.gate_up, w8) != nullptr,
+                        moe ? moe_found : skinny_kernel(P.down, w8) != nullptr,
                         skinny_kernel(P.lm_head, fmt->lm_head) != nullptr};
   for (int n = 0; n < 8; n++)
     if (!found[n]) return 1 + n;
   return 0;
+}
+int p2pt_llama_plan_kernels_chunk(const LlamaDims* d, int B, int emit_rows, const WeightFormat* fmt, const int* windows,
+                                  int chunk_attn) {
+  return p2pt_llama_plan_kernels_moe(d, B, emit_rows, fmt, windows, chunk_attn, nullptr);
 }
 int p2pt_llama_plan_kernels_fmt(const LlamaDims* d, int B, int emit_rows, const WeightFormat* fmt, const int* windows) {
   return p2pt_llama_plan_kernels_chunk(d, B, emit_rows, fmt, windows, 0);
@@ -670,6 +752,14 @@ int p2pt_llama_weight_layout_fmt(const LlamaDims* d, const WeightFormat* fmt, in
     }
   return T.size();
 }
+// The same for an MoE table (bf16 only): 14 roles per layer, router (enum Role's R_ROUTER) last; no scales.
+int p2pt_llama_weight_layout_moe(const LlamaDims* d, const MoeDims* moe, int* index, int n) {
+  if (!dims_ok(*d) || !moe_ok(*d, *moe) || n < R_NROLES_MOE * d->n_layers) return -1;
+  const WeightTable T{*d, WeightFormat{0, 0}, nullptr, 1};
+  for (int L = 0; L < d->n_layers; L++)
+    for (int r = 0; r < R_NROLES_MOE; r++) index[L * R_NROLES_MOE + r] = T.index(Role(r), L);
+  return T.size();
+}
 // The same for a WeightPlan (bf16 or FP8 throughout; anything else is refused).
 int p2pt_llama_weight_layout(const LlamaDims* d, const WeightPlan* wp, int* index, int* scale_index, int n) {
   if (!weights_ok(*wp)) return -1;
@@ -723,20 +813,28 @@ int p2pt_max_rows() { return kMaxM; }
 //      every layer without a window runs k_attn_chunk on ChunkPlan's grid instead of k_attn: one K/V pass per 16-row
 //      tile and distinct slot in it. Steps of up to 16 rows and windowed layers launch what they did, and so does
 //      chunk_attn = 0, which is p2pt_llama_decode_fmt. The workspace is the same.
-int p2pt_llama_decode_chunk(const LlamaDims* dp, const WeightFormat* fmt, const float* kv_scales, const int* windows,
-                            const void* const* w, void* k_cache, void* v_cache, const int64_t* tokens, const int* pos,
-                            const int* slots, int B, int emit_rows, void* ws, size_t ws_bytes, void* logits,
-                            int64_t* ids, void* stream, int chunk_attn) {
+//   Routed-expert FFN (p2pt_llama_decode_moe with moe != nullptr; docs/MOE.md): dims.ffn is the per-expert
+//      intermediate size, and every layer has a seventh (with q_norm / k_norm or bqkv: last) entry, router, bf16
+//      [E][dim] with the FFN norm folded in; w_gate_up is [E][2 * ffn][dim], folded and pair-interleaved per expert,
+//      w_down [E][dim][ffn]. The layer's gate/up and down kernels give way to k_moe_route, k_moe_gate_up, k_moe_down
+//      and k_moe_combine on MoePlan's grids; every other launch is the dense step's. bf16 layers only. The workspace
+//      is p2pt_llama_ws_bytes_moe's. moe == nullptr is p2pt_llama_decode_chunk, launch for launch.
+int p2pt_llama_decode_moe(const LlamaDims* dp, const WeightFormat* fmt, const float* kv_scales, const int* windows,
+                          const void* const* w, void* k_cache, void* v_cache, const int64_t* tokens, const int* pos,
+                          const int* slots, int B, int emit_rows, void* ws, size_t ws_bytes, void* logits,
+                          int64_t* ids, void* stream, int chunk_attn, const MoeDims* moe) {
   const LlamaDims d = *dp;
   if (!dims_ok(d) || !rows_ok(B) || (!slots && B > d.max_batch) || !format_ok(*fmt)) return int(hipErrorInvalidValue);
+  if (moe && (!moe_ok(d, *moe) || fmt->layers != 0)) return int(hipErrorInvalidValue);
   if (kv_scales && !d.kv_fp8) return int(hipErrorInvalidValue);
   const Windows WN{windows};
   if (!windows_ok(d, WN)) return int(hipErrorInvalidValue);
   const KvScales KS{kv_scales};
   const int w8 = fmt->layers;
-  const Workspace W = carve(d, static_cast<uint8_t*>(ws));
+  const Workspace W = carve(d, static_cast<uint8_t*>(ws), moe);
   if (ws_bytes < W.bytes) return int(hipErrorInvalidValue);
   const StepPlan P = plan_step(d, B, emit_rows);
+  const MoePlan MP = moe ? plan_moe(d, *moe, B) : MoePlan{};
   const KvPlan KV = plan_kv(d);
   const ChunkPlan CP = plan_attn_chunk(B, d.H, d.Hkv, d.D, d.max_seq);
   auto s = static_cast<hipStream_t>(stream);
@@ -744,7 +842,7 @@ int p2pt_llama_decode_chunk(const LlamaDims* dp, const WeightFormat* fmt, const 
   hipError_t e;
   auto failed = [&](hipError_t r) { return (e = r) != hipSuccess; };
 
-  const WeightTable T{d, *fmt, w};
+  const WeightTable T{d, *fmt, w, moe ? 1 : 0};
   const void* inv_freq = T.get(R_INV_FREQ);
   hipLaunchKernelGGL(k_embed, dim3(B), dim3(256), 0, s, static_cast<const uint16_t*>(T.get(R_EMBED)), tokens, W.resid,
                      W.ss, d.dim, d.vocab);
@@ -781,6 +879,15 @@ int p2pt_llama_decode_chunk(const LlamaDims* dp, const WeightFormat* fmt, const 
                                   d.Hkv, d.max_seq, s, KS.at(d, KvScales::K, L), KS.at(d, KvScales::V, L), &wn)))
       return int(e);
     if (failed(launch(P.o, to_o, s, w8))) return int(e);
+    if (moe) {
+      // resid and ss as the O projection left them; k_moe_combine leaves them as the down projection would.
+      const p2pt_moe::MoeArgs ma{W.resid, W.ss, P.gate_up.ss_in, static_cast<const uint16_t*>(T.get(R_ROUTER, L)),
+                                 static_cast<const uint16_t*>(T.get(R_W_GATE_UP, L)),
+                                 static_cast<const uint16_t*>(T.get(R_W_DOWN, L)), W.route_id, W.route_w, W.route_rs,
+                                 W.moe_h, W.moe_part, B, d.dim, d.ffn, moe->n_experts, moe->top_k, moe->norm_topk, d.eps};
+      if (failed(p2pt_moe::launch_moe(MP, ma, s))) return int(e);
+      continue;
+    }
     if (failed(launch(P.gate_up, to_gate_up, s, w8))) return int(e);
     if (failed(launch(P.down, to_down, s, w8))) return int(e);
   }
@@ -790,6 +897,13 @@ int p2pt_llama_decode_chunk(const LlamaDims* dp, const WeightFormat* fmt, const 
   if (failed(launch(P.lm_head, to_logits, s, fmt->lm_head))) return int(e);
   hipLaunchKernelGGL(k_argmax_merge, dim3(P.emit_rows), dim3(256), 0, s, W.am_val, W.am_idx, P.am_parts, ids);
   return int(hipGetLastError());
+}
+int p2pt_llama_decode_chunk(const LlamaDims* dp, const WeightFormat* fmt, const float* kv_scales, const int* windows,
+                            const void* const* w, void* k_cache, void* v_cache, const int64_t* tokens, const int* pos,
+                            const int* slots, int B, int emit_rows, void* ws, size_t ws_bytes, void* logits,
+                            int64_t* ids, void* stream, int chunk_attn) {
+  return p2pt_llama_decode_moe(dp, fmt, kv_scales, windows, w, k_cache, v_cache, tokens, pos, slots, B, emit_rows, ws,
+                               ws_bytes, logits, ids, stream, chunk_attn, nullptr);
 }
 int p2pt_llama_decode_fmt(const LlamaDims* dp, const WeightFormat* fmt, const float* kv_scales, const int* windows,
                           const void* const* w, void* k_cache, void* v_cache, const int64_t* tokens, const int* pos,
@@ -868,6 +982,37 @@ int p2pt_chunk_attention(const void* q, const void* kc, const void* vc, const in
   const ChunkPlan p = plan_attn_chunk(B, H, Hkv, D, Smax);
   return int(launch_attn_chunk(p, kv8, q, kc, vc, pos, slots, B, nslots, part_o, part_ml, counters, out, H, Hkv, Smax,
                                static_cast<hipStream_t>(stream), k_scale, v_scale));
+}
+
+// Standalone routed-expert FFN (ops.moe_ffn; tests, benchmarks): the four kernels of one MoE layer on caller
+// tensors. resid bf16 [B][dim], updated in place; ss fp32 [>= max(ss_in, cb_grid)][64]: rows [0, ss_in) hold the
+// partial sums of squares of resid's rows on entry, rows [0, cb_grid) those of the new rows on return
+// (cb_grid: p2pt_llama_moe_plan's); router bf16 [E][dim], w_gate_up bf16 [E][2 * ffn][dim] and w_down bf16
+// [E][dim][ffn] as the step's weight table holds them; route_id int32 and route_w fp32 [B][top_k], route_rs fp32 [B],
+// moe_h bf16 [B * top_k][ffn], moe_part fp32 [B][top_k][dim]: outputs, every slot a pair owns written.
+int p2pt_moe_ffn(void* resid, float* ss, int ss_in, const void* router, const void* w_gate_up, const void* w_down,
+                 int* route_id, float* route_w, float* route_rs, void* moe_h, float* moe_part, int B, int dim, int ffn,
+                 int E, int top_k, int norm_topk, float eps, void* stream) {
+  if (!rows_ok(B) || dim <= 0 || ffn <= 0 || dim % 32 || ffn % 32) return int(hipErrorInvalidValue);
+  LlamaDims d{};
+  d.dim = dim, d.ffn = ffn;
+  const MoeDims m{E, top_k, norm_topk};
+  if (!moe_ok(d, m)) return int(hipErrorInvalidValue);
+  const p2pt_moe::MoeArgs a{static_cast<uint16_t*>(resid), ss, ss_in, static_cast<const uint16_t*>(router),
+                            static_cast<const uint16_t*>(w_gate_up), static_cast<const uint16_t*>(w_down), route_id,
+                            route_w, route_rs, static_cast<uint16_t*>(moe_h), moe_part, B, dim, ffn, E, top_k, norm_topk,
+                            eps};
+  return int(p2pt_moe::launch_moe(plan_moe(d, m, B), a, static_cast<hipStream_t>(stream)));
+}
+// plan_moe for the standalone op's shapes (host only).
+int p2pt_moe_ffn_plan(int B, int dim, int ffn, int E, int top_k, int norm_topk, MoePlan* out) {
+  if (!rows_ok(B) || dim <= 0 || ffn <= 0 || dim % 32 || ffn % 32) return int(hipErrorInvalidValue);
+  LlamaDims d{};
+  d.dim = dim, d.ffn = ffn;
+  const MoeDims m{E, top_k, norm_topk};
+  if (!moe_ok(d, m)) return int(hipErrorInvalidValue);
+  *out = plan_moe(d, m, B);
+  return 0;
 }
 
 // Microbenchmark hook (scripts/bench_skinny.py --attn): `reps` back-to-back

@@ -1,0 +1,57 @@
+// Routed-expert FFN of the fused decode step (docs/MOE.md): what decode_fused.hip (planning, workspace, entry points)
+// and decode_moe.hip (the four kernels' instantiations and launches) share. The kernels themselves are in
+// decode_moe_kernels.h. decode_moe.hip is a translation unit of its own because it is compiled without packed fp32
+// instructions (build.py), which the rest of the library keeps.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace p2pt_moe {
+
+constexpr int kMaxExperts = 128;  // E: a lane of k_moe_route holds experts lane and lane + 64
+constexpr int kMaxTopK = 8;       // experts per token: route_id holds at most kMaxM * 8 ints
+constexpr int kRouteWaves = 4, kCombineWaves = 4;  // waves per workgroup of k_moe_route and k_moe_combine
+
+// The mixture-of-experts shape of a model, beside the plans as WeightFormat and Windows are (mirrored with ctypes).
+// With it, LlamaDims::ffn is the per-expert intermediate size.
+struct MoeDims {
+  int n_experts;  // E
+  int top_k;      // experts per token
+  int norm_topk;  // 1: the top-k probabilities are renormalised to sum to one (Mixtral)
+};
+
+// What the four kernels launch for B rows (mirrored with ctypes): every field a function of (B, dims, MoeDims).
+struct MoePlan {
+  int route_grid, route_waves;      // k_moe_route: one workgroup per row
+  int gu_grid_x, gu_grid_y;         // k_moe_gate_up<gu_nw, gu_rt, gu_um>: (16-column tiles of [2 ffn_e], expert)
+  int gu_nw, gu_rt, gu_um;
+  int dn_grid_x, dn_grid_y;         // k_moe_down<dn_nw, dn_rt, dn_um>: (16-column tiles of [dim], expert)
+  int dn_nw, dn_rt, dn_um;
+  int cb_grid, cb_cols, cb_waves;   // k_moe_combine: cb_grid workgroups of cb_cols columns; cb_grid is the ss_in of
+                                    // the next layer's QKV GEMM and of the LM head
+};
+
+// One layer's pointers. Shapes: dims of the model, E / top_k of MoeDims, B rows.
+struct MoeArgs {
+  uint16_t* resid;          // bf16 [B][dim], updated in place by k_moe_combine
+  float* ss;                // fp32 [parts][kMaxM]: read (ss_in partials) by k_moe_route, rewritten (cb_grid) by combine
+  int ss_in;                // partials the residual's producer left
+  const uint16_t* router;   // bf16 [E][dim], the FFN norm weight folded in
+  const uint16_t* w_gate_up;  // bf16 [E][2 ffn_e][dim], folded, rows interleaved (gate_j, up_j) per expert
+  const uint16_t* w_down;     // bf16 [E][dim][ffn_e]
+  int* route_id;            // int32 [B][top_k], descending probability
+  float* route_w;           // fp32 [B][top_k]
+  float* route_rs;          // fp32 [B]: 1 / rms of the row, as the router used it
+  uint16_t* moe_h;          // bf16 [B * top_k][ffn_e]
+  float* moe_part;          // fp32 [B][top_k][dim]
+  int B, dim, ffn, E, top_k, norm_topk;
+  float eps;
+};
+
+// The four launches of one MoE layer, in order, on stream s; a plan that names a kernel which is not instantiated, or
+// arguments outside what the kernels index, are hipErrorInvalidValue and nothing is launched.
+hipError_t launch_moe(const MoePlan& p, const MoeArgs& a, hipStream_t s);
+// Whether the plan's kernels exist (host only).
+bool moe_kernels_exist(const MoePlan& p);
+
+}  // namespace p2pt_moe
