@@ -237,7 +237,7 @@ class _Reader:
 def load_llama(path: str, device="cuda", max_batch: int = 8, max_seq: int | None = None,
                fused: bool = True, prefix: str = "model.", kv_dtype: str = "bf16",
                weight_dtype: str = "bf16", kv_scales=None, sliding_window: bool = False,
-               chunk_attn: bool = False) -> TinyLlama:
+               chunk_attn: bool = False, expert_dtype: str = "bf16") -> TinyLlama:
     """A TinyLlama with the checkpoint's weights (bf16 on ``device``). ``kv_dtype``: "bf16" or "fp8", the KV
     cache's format (``TinyLlama``), for every family alike. ``kv_scales`` ("fp8" only): None (scale 1: ``k_scale`` /
     ``v_scale`` tensors a checkpoint may carry are then not read), a ``KvScales``, or "checkpoint": the per-layer
@@ -246,13 +246,18 @@ def load_llama(path: str, device="cuda", max_batch: int = 8, max_seq: int | None
     (docs/WEIGHT_FP8.md) or "mxfp4" (docs/WEIGHT_MXFP4.md: the layers' GEMM weights as MXFP4, the LM head as FP8): each
     layer's GEMM weights are quantised on ``device`` as soon as the layer is read and its bf16 tensors dropped, so
     the device never holds the bf16 and the quantised copies of all layers together. The checkpoint itself is bf16 / fp16
-    / fp32 either way: one that is already quantised on disk is treated as before. ``chunk_attn``: ``TinyLlama``'s
+    / fp32 either way: one that is already quantised on disk is treated as before. ``expert_dtype``: "bf16" or "fp8"
+    (docs/MOE_FP8.md; MoE checkpoints only): the stacked experts as e4m3 bytes with per-row scales, each layer's stack
+    quantised as soon as it is read (``quantize_experts_``), every other weight bf16. ``chunk_attn``: ``TinyLlama``'s
     (docs/CHUNK_ATTN.md). ``sliding_window``: serve the
     checkpoint's sliding attention window (``read_config``, docs/SLIDING_WINDOW.md), fused step only; a checkpoint
     that declares none is refused."""
-    from p2p_llm_tunnel_amd.models.tiny_llm import WEIGHT_DTYPES, quantize_layer_
+    from p2p_llm_tunnel_amd.models.tiny_llm import (EXPERT_DTYPES, WEIGHT_DTYPES, check_expert_scales, quantize_experts_,
+                                                    quantize_layer_)
     if weight_dtype not in WEIGHT_DTYPES:
         raise ValueError(f"weight_dtype must be one of {list(WEIGHT_DTYPES)}, got {weight_dtype!r}")
+    if expert_dtype not in EXPERT_DTYPES:
+        raise ValueError(f"expert_dtype must be one of {list(EXPERT_DTYPES)}, got {expert_dtype!r}")
     from p2p_llm_tunnel_amd.models import kv_scales as kvs
     kv_scales = kvs.parse_kv_scales(kv_scales, kv_dtype)  # refused with a bf16 cache before anything is read
     cfg, raw = read_config(path, max_seq, sliding_window)
@@ -260,7 +265,11 @@ def load_llama(path: str, device="cuda", max_batch: int = 8, max_seq: int | None
         raise ValueError("a sliding window runs the fused step only: load with fused=True")
     if cfg.n_experts and weight_dtype != "bf16":
         raise ValueError(f"an MoE checkpoint's expert weights are served as bf16 only: weight_dtype {weight_dtype!r} "
-                         "is not supported with a routed-expert FFN")
+                         "is not supported with a routed-expert FFN (expert_dtype='fp8' quantises the experts)")
+    from p2p_llm_tunnel_amd import ops
+    ops.as_expert_format(expert_dtype, cfg.moe, cfg.dim, cfg.ffn)  # a dense checkpoint, or shapes that do not block
+    if expert_dtype != "bf16" and not fused:
+        raise ValueError("FP8 experts run the fused step only: load with fused=True")
     c = cfg
     rd = _Reader(path)
     dev = torch.device(device)
@@ -349,10 +358,15 @@ def load_llama(path: str, device="cuda", max_batch: int = 8, max_seq: int | None
             del q, k, v, gate, up
             if weight_dtype != "bf16":  # this layer's bf16 GEMM weights give way to the quantised ones before the next is read
                 quantize_layer_(c, w["layers"][-1], weight_dtype)
+            if expert_dtype == "fp8":  # likewise this layer's expert stacks
+                quantize_experts_(c, w["layers"][-1])
+                check_expert_scales(w["layers"][-1], i)
+                del gate_up, down
     finally:
         rd.close()
     return TinyLlama.from_weights(cfg, w, device=dev, max_batch=max_batch, fused=fused, kv_dtype=kv_dtype,
-                                  weight_dtype=weight_dtype, kv_scales=kv_scales, chunk_attn=chunk_attn)
+                                  weight_dtype=weight_dtype, kv_scales=kv_scales, chunk_attn=chunk_attn,
+                                  expert_dtype=expert_dtype)
 
 
 class Detokenizer:

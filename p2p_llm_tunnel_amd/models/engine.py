@@ -431,18 +431,26 @@ class Engine:
     rows, so the 64-row graphs capture that kernel and the 16-row ones what they
     did. The number of graphs is what it is without the switch. A prompt row's
     attention then sums in an order that depends on its tile-mates.
+
+    ``expert_dtype`` ("bf16" by default, and then nothing above changes; docs/MOE_FP8.md):
+    "fp8" builds an MoE model with FP8 expert matrices, which only the
+    graph-captured HIP step multiplies. The number of graphs is what it is without.
     """
 
     def __init__(self, device="cuda:0", config="tiny", max_batch=8, seed=0, use_graph=True, rows=64, model=None,
                  small_rows=16, prefix_cache=False, prefix_min=16, penalties=False, kv_dtype="bf16",
                  guided=False, guided_states=1024, weight_dtype="bf16", kv_scales=None, min_p=False,
-                 chunk_attn=False):
+                 chunk_attn=False, expert_dtype="bf16"):
         if kv_scales is not None and kv_dtype != "fp8" and getattr(model, "kv_dtype", "bf16") != "fp8":
             raise ValueError("kv_scales need kv_dtype='fp8' (--kv-dtype fp8): a bf16 KV cache has no scales")
         if model is None:
             from p2p_llm_tunnel_amd.models.tiny_llm import TinyLlama
             model = TinyLlama(config, device=device, max_batch=max_batch, seed=seed, fused=True, kv_dtype=kv_dtype,
-                              weight_dtype=weight_dtype, kv_scales=kv_scales, chunk_attn=bool(chunk_attn))
+                              weight_dtype=weight_dtype, kv_scales=kv_scales, chunk_attn=bool(chunk_attn),
+                              **({"expert_dtype": expert_dtype} if expert_dtype != "bf16" else {}))
+        elif expert_dtype != "bf16" and getattr(model, "expert_dtype", "bf16") != expert_dtype:
+            raise ValueError(f"expert_dtype={expert_dtype!r}, but the injected model was built with "
+                             f"{getattr(model, 'expert_dtype', 'bf16')!r} experts")
         elif chunk_attn and not getattr(model, "chunk_attn", False):
             raise ValueError("chunk_attn=True, but the injected model was built without it")
         elif kv_scales is not None and getattr(model, "kv_scales", None) != kv_scales:
@@ -479,6 +487,7 @@ class Engine:
         for on, what in ((penalties, "penalties need"), (fp8, "an fp8 KV cache needs"), (w8, f"{getattr(model, 'weight_dtype', 'bf16')} weights need"),
                          (guided, "guided decoding needs"), (windowed, "a sliding window needs"),
                          (min_p, "min_p needs"), (getattr(model, "chunk_attn", False), "chunk_attn needs"),
+                         (getattr(model, "expert_dtype", "bf16") != "bf16", "fp8 experts need"),
                          (bool(getattr(getattr(model, "cfg", None), "n_experts", 0)), "an MoE model needs")):
             if on and not use_graph:
                 raise ValueError(f"{what} the graph-captured HIP step; this engine runs eagerly")

@@ -782,7 +782,8 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
                  tokenizer=None, default_temperature: float = 0.0, prefix_cache: bool = False, prefix_min: int = 16,
                  embed_pooling: str = "mean", penalties: bool = False, kv_dtype: str = "bf16",
                  guided: bool = False, guided_states: int = 1024, weight_dtype: str = "bf16", kv_scales=None,
-                 sliding_window: bool = False, min_p: bool = False, chunk_attn: bool = False):
+                 sliding_window: bool = False, min_p: bool = False, chunk_attn: bool = False,
+                 expert_dtype: str = "bf16"):
     """Engine + HTTP front-end; returns (server, port, engine). ``server.shutdown()``
     stops the HTTP side, ``engine.stop()`` the GPU side. ``checkpoint``: serve a
     Hugging Face Llama checkpoint directory (weights + tokenizer) instead of
@@ -808,7 +809,13 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
     routes (``sampling_params``, docs/MIN_P.md) instead of refusing the first and ignoring the second; an injected
     engine must have been built with it.
     ``chunk_attn`` is ``Engine``'s and ``load_llama``'s (docs/CHUNK_ATTN.md): steps of more than 16 rows attend with
-    ``k_attn_chunk``; an injected engine's model must have been built with it."""
+    ``k_attn_chunk``; an injected engine's model must have been built with it.
+    ``expert_dtype`` ("bf16" or "fp8": docs/MOE_FP8.md) is ``Engine``'s and ``load_llama``'s: the format of an MoE
+    model's stacked expert matrices alone; a dense model refuses "fp8", and an injected engine's model must have it."""
+    expert_dtype = parse_expert_dtype(expert_dtype)
+    if engine is not None and getattr(engine.model, "expert_dtype", "bf16") != expert_dtype:
+        raise ValueError(f"expert_dtype={expert_dtype!r}, but the injected engine's model has "
+                         f"{getattr(engine.model, 'expert_dtype', 'bf16')!r} experts")
     if engine is not None and chunk_attn and not getattr(engine, "chunk_attn", False):
         raise ValueError("chunk_attn=True, but the injected engine was built without it")
     if engine is not None and min_p and not getattr(engine, "min_p", False):
@@ -844,7 +851,7 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
         from p2p_llm_tunnel_amd.models.checkpoint import Tokenizer, load_llama
         model = load_llama(checkpoint, device=device, max_batch=max_batch, max_seq=max_seq, kv_dtype=kv_dtype,
                            weight_dtype=weight_dtype, kv_scales=kv_scales, sliding_window=sliding_window,
-                           chunk_attn=chunk_attn)
+                           chunk_attn=chunk_attn, expert_dtype=expert_dtype)
         tok = tok or Tokenizer.for_checkpoint(checkpoint)
         engine = Engine(device=device, max_batch=max_batch, model=model, prefix_cache=prefix_cache,
                         prefix_min=prefix_min, penalties=penalties, guided=guided, guided_states=guided_states,
@@ -853,7 +860,7 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
     engine = engine or Engine(device=device, config=config, max_batch=max_batch, prefix_cache=prefix_cache,
                               prefix_min=prefix_min, penalties=penalties, kv_dtype=kv_dtype, guided=guided,
                               guided_states=guided_states, weight_dtype=weight_dtype, kv_scales=kv_scales,
-                              min_p=min_p, chunk_attn=chunk_attn)
+                              min_p=min_p, chunk_attn=chunk_attn, expert_dtype=expert_dtype)
     srv = FrontEnd(engine, host, port, model_name or f"p2pt-{config}", tokenizer=tok,
                    default_temperature=default_temperature, embed_pooling=embed_pooling)
     return srv, srv.server_address[1], engine
@@ -879,6 +886,16 @@ def parse_weight_dtype(v) -> str:
     return v
 
 
+EXPERT_DTYPE_CHOICES = ("bf16", "fp8")
+
+
+def parse_expert_dtype(v) -> str:
+    """--expert-dtype / ``start_server(expert_dtype=)``: "bf16" (the default) or "fp8"; anything else is refused."""
+    if v not in EXPERT_DTYPE_CHOICES:
+        raise ValueError(f"expert_dtype must be one of {list(EXPERT_DTYPE_CHOICES)}, got {v!r}")
+    return v
+
+
 def weights_line(model, weight_dtype: str) -> str:
     """The start-up log line with the weights' size."""
     sizes = getattr(model, "weight_bytes", None)
@@ -889,8 +906,13 @@ def weights_line(model, weight_dtype: str) -> str:
     c = getattr(model, "cfg", None)
     if getattr(c, "n_experts", 0):  # the expert bytes one token reads: top_k of every layer's n_experts
         expert = (2 * c.ffn * c.dim + c.dim * c.ffn) * 2
+        fp8 = getattr(model, "expert_dtype", "bf16") == "fp8"
+        if fp8:  # a byte per weight and an fp32 scale per output row
+            expert = (2 * c.ffn * c.dim + c.dim * c.ffn) + (2 * c.ffn + c.dim) * 4
         active = b["gemm"] - c.n_layers * (c.n_experts - c.top_k) * expert
         line += f"; MoE: {c.n_experts} experts, top-{c.top_k}, {active} GEMM bytes active per token"
+        if fp8:
+            line += f"; fp8 experts {c.n_layers * c.n_experts * expert} bytes with their row scales"
     return line
 
 
@@ -954,6 +976,8 @@ def replica_cmd(a, i: int) -> list[str]:
         cmd += ["--min-p"]
     if getattr(a, "chunk_attn", False):
         cmd += ["--chunk-attn"]
+    if getattr(a, "expert_dtype", "bf16") != "bf16":
+        cmd += ["--expert-dtype", a.expert_dtype]
     return cmd
 
 
@@ -1033,6 +1057,12 @@ def arg_parser() -> argparse.ArgumentParser:
                          "(docs/WEIGHT_FP8.md); or mxfp4 (OCP Microscaling FP4 for the four GEMM weights of every "
                          "layer: e2m1 values in blocks of 32 with a power-of-two scale, round to nearest, no "
                          "calibration; the LM head is fp8): about a quarter of their bytes (docs/WEIGHT_MXFP4.md)")
+    ap.add_argument("--expert-dtype", choices=EXPERT_DTYPE_CHOICES, default="bf16",
+                    help="format of an MoE model's stacked expert matrices (Mixtral checkpoints, tiny-moe): bf16, or "
+                         "fp8 (OCP e4m3 with one fp32 scale per expert and output row, per-row absmax, nothing "
+                         "calibrated; activations, router, attention projections and LM head stay bf16): half the "
+                         "expert bytes in memory and per step. A dense model refuses it, and --weight-dtype stays "
+                         "bf16 on an MoE model (docs/MOE_FP8.md)")
     ap.add_argument("--sliding-window", action="store_true",
                     help="serve the checkpoint's sliding attention window (Mistral-7B-v0.1 and its fine-tunes; Qwen2 / "
                          "Qwen3 with use_sliding_window) instead of capping the context at it: the layers that slide "
@@ -1075,7 +1105,7 @@ def main(argv=None):
                                      embed_pooling=a.embed_pooling, penalties=a.penalties, kv_dtype=a.kv_dtype,
                                      guided=a.guided, guided_states=a.guided_states, weight_dtype=a.weight_dtype,
                                      kv_scales=a.kv_scales, sliding_window=a.sliding_window, min_p=a.min_p,
-                                     chunk_attn=a.chunk_attn)
+                                     chunk_attn=a.chunk_attn, expert_dtype=a.expert_dtype)
     print(weights_line(engine.model, a.weight_dtype), flush=True)
     print(kv_cache_line(engine.model, a.kv_dtype), flush=True)
     if a.sliding_window:

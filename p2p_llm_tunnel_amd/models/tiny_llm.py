@@ -101,6 +101,9 @@ CONFIGS = {
 KV_DTYPES = {"bf16": torch.bfloat16, "fp8": torch.float8_e4m3fn}  # TinyLlama(kv_dtype=): the caches' dtype
 # TinyLlama(weight_dtype=): the format of the GEMM weights. "mxfp4": a layer's four as MXFP4, the LM head as FP8.
 WEIGHT_DTYPES = ("bf16", "fp8", "mxfp4")
+# TinyLlama(expert_dtype=): the format of an MoE model's stacked expert matrices alone (docs/MOE_FP8.md).
+EXPERT_DTYPES = tuple(ops.EXPERT_FORMATS)
+EXPERT_WEIGHTS = ("w_gate_up", "w_down")  # the stacked expert matrices of an MoE layer
 GEMM_WEIGHTS = ops.LAYER_GEMMS  # a layer's GEMM weights, in the order of their scales
 FOLDED_NORM = {"wqkv": "attn_norm", "w_gate_up": "ffn_norm", "lm_head": "final_norm"}  # GEMM: the norm in its columns
 
@@ -158,6 +161,35 @@ def quantize_layer_(cfg: "LlamaConfig", L: dict, weight_dtype: str = "fp8") -> d
     return L
 
 
+def quantize_experts_(cfg: "LlamaConfig", L: dict) -> dict:
+    """One MoE layer's stacked experts to FP8 in place (docs/MOE_FP8.md): ``L["w_gate_up"]`` and ``L["w_down"]`` (bf16
+    ``[E, N, K]``) give way to ``L[name + "_q"]`` (e4m3 ``[E, N, K]``, folded and interleaved as the fused table wants
+    it, natural K order) and ``L[name + "_s"]`` (fp32 ``[E, N]``), by ``ops.quantize_weight_fp8`` expert by expert: per
+    row absmax / 448, in fp32 after the fold and the interleave. The loader calls it layer by layer, as it does
+    ``quantize_layer_``, so the bf16 and FP8 stacks of all layers are never resident together."""
+    for name in EXPERT_WEIGHTS:
+        if name + "_q" in L:
+            continue
+        w = L.pop(name)
+        q = torch.empty(w.shape, dtype=torch.float8_e4m3fn, device=w.device)
+        sc = torch.empty(w.shape[:2], dtype=torch.float32, device=w.device)
+        g, perm = L.get(FOLDED_NORM.get(name)), fused_row_perm(cfg, name, w.device)
+        for e in range(w.shape[0]):
+            q[e], sc[e] = quantize_gemm_weight(w[e], g, perm)
+        L[name + "_q"], L[name + "_s"] = q, sc
+        del w
+    return L
+
+
+def check_expert_scales(L: dict, layer: int) -> None:
+    """The row scales of a layer's FP8 experts must be finite and > 0: anything else would poison every row."""
+    for name in EXPERT_WEIGHTS:
+        sc = L[name + "_s"]
+        if not bool((torch.isfinite(sc) & (sc > 0)).all()):
+            raise ValueError(f"layer {layer}: {name}_s holds a non-finite or non-positive scale: FP8 expert scales "
+                             "must be finite and > 0")
+
+
 def dequantize_gemm_weight(q: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
     """``(q, s)`` of ``quantize_gemm_weight`` back in fp32, whichever format made them."""
     return ops.dequantize_weight_mxfp4(q, s) if s.dtype == torch.uint8 else ops.dequantize_weight_fp8(q, s)
@@ -198,8 +230,16 @@ def capture(fn, device, warmup: int = 2):
 class TinyLlama:
     def __init__(self, cfg: LlamaConfig | str = "tiny", device="cuda", max_batch: int = 8, seed: int = 0,
                  fused: bool = True, weights: dict | None = None, kv_dtype: str = "bf16",
-                 weight_dtype: str = "bf16", kv_scales: KvScales | None = None, chunk_attn: bool = False):
-        """``chunk_attn`` (off by default; docs/CHUNK_ATTN.md): steps of more than 16 rows attend with
+                 weight_dtype: str = "bf16", kv_scales: KvScales | None = None, chunk_attn: bool = False,
+                 expert_dtype: str = "bf16"):
+        """``expert_dtype`` ("bf16", the default, or "fp8"; MoE models and the fused step only; docs/MOE_FP8.md): the
+        stacked expert matrices as e4m3 bytes with one fp32 scale per (expert, output row), per-row absmax, nothing
+        calibrated; quantised here layer by layer, or brought by ``weights`` as ``w_gate_up_q`` / ``w_gate_up_s`` /
+        ``w_down_q`` / ``w_down_s`` (e4m3 or uint8 ``[E, N, K]`` in natural K order and the fused table's row order,
+        fp32 ``[E, N]``). Everything else of the model, the router included, stays bf16; ``weight_dtype`` stays
+        "bf16" on an MoE model.
+
+        ``chunk_attn`` (off by default; docs/CHUNK_ATTN.md): steps of more than 16 rows attend with
         ``k_attn_chunk``, one K/V pass per 16-row tile, on every layer without a window. Only the fused step has it.
 
         ``kv_dtype``: "bf16" (default) or "fp8": the K/V caches as ``torch.float8_e4m3fn`` (OCP e4m3, half the
@@ -232,6 +272,13 @@ class TinyLlama:
             kv_scales.check(self.cfg.n_layers, self.cfg.n_kv_heads, kv_dtype)
         self.kv_scales = kv_scales
         self.weight_dtype = weight_dtype
+        if expert_dtype not in EXPERT_DTYPES:
+            raise ValueError(f"expert_dtype must be one of {list(EXPERT_DTYPES)}, got {expert_dtype!r}")
+        self.expert_dtype = expert_dtype
+        ops.as_expert_format(expert_dtype, self.cfg.moe, self.cfg.dim, self.cfg.ffn)  # dense, or no multiple of 64
+        if expert_dtype != "bf16" and not fused:
+            raise ValueError("FP8 experts run the fused step only (fused=True): the unfused path has no "
+                             "routed-expert kernels")
         if self.cfg.n_experts and weight_dtype != "bf16":
             raise ValueError(f"an MoE model's expert weights are bf16 only: weight_dtype {weight_dtype!r} is not "
                              "supported with a routed-expert FFN")
@@ -244,6 +291,7 @@ class TinyLlama:
             raise ValueError("chunk_attn runs the fused step only (fused=True): the unfused path has no chunk "
                              "attention kernel")
         self.chunk_attn = chunk_attn
+        self._experts_blocked = False  # FP8 experts: fused_weights() has put their bytes into the device order
         self.lm_head_q = self.lm_head_s = None  # weight_dtype "fp8": the LM head's bytes and row scales
         self.fused = fused
         self._fused = None
@@ -271,7 +319,15 @@ class TinyLlama:
                         "w_down": (c.n_experts, c.dim, c.ffn)}
                 for i, L in enumerate(self.layers):
                     for n, shape in want.items():
-                        if n not in L or tuple(L[n].shape) != shape:
+                        if n + "_q" in L:  # experts that are FP8 already
+                            q, sc = L[n + "_q"], L.get(n + "_s")
+                            if expert_dtype != "fp8":
+                                raise ValueError(f"layer {i}: the weights hold FP8 experts: pass expert_dtype='fp8'")
+                            if q.dtype not in ops.WEIGHT_FP8_DTYPES or tuple(q.shape) != shape or sc is None or \
+                                    sc.dtype != torch.float32 or tuple(sc.shape) != shape[:2]:
+                                raise ValueError(f"layer {i}: FP8 experts need {n}_q, e4m3 or uint8 of shape {shape}, "
+                                                 f"and {n}_s, fp32 of shape {shape[:2]}")
+                        elif n not in L or tuple(L[n].shape) != shape:
                             raise ValueError(f"layer {i}: an MoE model needs {n} of shape {shape}")
             self._quantize_weights()
             self._alloc_caches()
@@ -312,15 +368,20 @@ class TinyLlama:
     @classmethod
     def from_weights(cls, cfg: LlamaConfig, weights: dict, device="cuda", max_batch: int = 8, fused: bool = True,
                      kv_dtype: str = "bf16", weight_dtype: str = "bf16", kv_scales: KvScales | None = None,
-                     chunk_attn: bool = False):
+                     chunk_attn: bool = False, expert_dtype: str = "bf16"):
         return cls(cfg, device=device, max_batch=max_batch, fused=fused, weights=weights, kv_dtype=kv_dtype,
-                   weight_dtype=weight_dtype, kv_scales=kv_scales, chunk_attn=chunk_attn)
+                   weight_dtype=weight_dtype, kv_scales=kv_scales, chunk_attn=chunk_attn, expert_dtype=expert_dtype)
 
     def _quantize_weights(self):
         """``weight_dtype`` "fp8": every layer's GEMM weights and the LM head to e4m3 + row scales, one tensor at
         a time. The bf16 LM head is dropped unless it is the embedding itself (a tied model)."""
+        if self.expert_dtype == "fp8":  # the experts alone, a layer at a time; every other weight stays bf16
+            self.layers = [quantize_experts_(self.cfg, dict(L)) for L in self.layers]
+            for i, L in enumerate(self.layers):
+                check_expert_scales(L, i)
         for L in self.layers:
-            have = layer_weight_dtype(L)
+            have = layer_weight_dtype({k: t for k, t in L.items() if k[:-2] not in EXPERT_WEIGHTS}
+                                      if self.cfg.n_experts else L)
             if have != "bf16" and have != self.weight_dtype:
                 raise ValueError(f"the weights hold {'FP8' if have == 'fp8' else 'MXFP4'} layers: "
                                  f"pass weight_dtype='{have}'")
@@ -330,8 +391,23 @@ class TinyLlama:
         self.lm_head_q, self.lm_head_s = quantize_gemm_weight(self.lm_head, self.final_norm, None)
         self.lm_head = None
 
+    def expert_weight(self, name: str, layer: int) -> torch.Tensor:
+        """An MoE layer's stacked ``name`` ("w_gate_up" or "w_down") in fp32 as the kernels compute with it, in the
+        fused table's row order and natural K order: with FP8 experts the dequantised ``q * s`` (the FFN norm folded
+        in), else the bf16 tensor folded and interleaved the same way."""
+        L = self.layers[layer]
+        if self.expert_dtype == "fp8":
+            q = L[name + "_q"]
+            q = ops.unblock_expert_fp8(q) if self._experts_blocked else q
+            return q.view(torch.float8_e4m3fn).float() * L[name + "_s"][:, :, None]
+        w, g = L[name].float(), L.get(FOLDED_NORM.get(name))
+        w = w * g.float()[None, None, :] if g is not None else w
+        perm = fused_row_perm(self.cfg, name, w.device)
+        return w[:, perm] if perm is not None else w
+
     def weight_bytes(self) -> dict:
-        """Bytes of the weights on the device: ``gemm`` (the five GEMM weights, with their scales when FP8),
+        """Bytes of the weights on the device: ``gemm`` (the five GEMM weights, with their scales when FP8; an MoE
+        model's stacked experts, in ``expert_dtype``'s format with their scales, are its w_gate_up and w_down),
         ``embed`` (the bf16 embedding table, which FP8 weights leave alone) and ``total`` (those and the norms,
         biases and QK-norm weights). A tied bf16 model counts its one shared table under ``embed`` only."""
         nb = lambda t: t.numel() * t.element_size()
@@ -438,10 +514,20 @@ class TinyLlama:
         top = {"embed": self.embed, "final_norm": self.final_norm, "lm_head": self.lm_head,
                "lm_head_q": self.lm_head_q, "lm_head_s": self.lm_head_s, "inv_freq": self.rope_inv_freq()}
 
+        # FP8 experts go into the kernels' k-step-pair order here (ops.block_expert_fp8), a layer at a time and in
+        # place of the natural-order bytes, so a second copy of the stacks never stays resident.
+        if self.expert_dtype == "fp8" and not self._experts_blocked:
+            for L in self.layers:
+                for n in EXPERT_WEIGHTS:
+                    L[n + "_q"] = ops.block_expert_fp8(L[n + "_q"])
+            self._experts_blocked = True
+
         def entry(name, layer):
             src = top if layer is None else self.layers[layer]
             if name.endswith(" scale"):
                 return src[name[:-len(" scale")] + "_s"]
+            if self.expert_dtype == "fp8" and name in EXPERT_WEIGHTS:
+                return src[name + "_q"]
             if fp8 and (name in GEMM_WEIGHTS or name == "lm_head"):
                 return src[name + "_q"]
             w = src[name]
@@ -453,7 +539,8 @@ class TinyLlama:
             return w[perm].contiguous() if perm is not None else w.contiguous() if name.endswith("_norm") else w
 
         return [entry(e.name, e.layer)
-                for e in ops.WeightTable(self.dims(), weight_format=self.weight_dtype, moe=c.moe)]
+                for e in ops.WeightTable(self.dims(), weight_format=self.weight_dtype, moe=c.moe,
+                                         **({"expert_format": "fp8"} if self.expert_dtype == "fp8" else {}))]
 
     def dims(self) -> ops.LlamaDims:
         """The fused step's dims of this model: one cache slot per sequence and the scratch slot."""
@@ -467,7 +554,8 @@ class TinyLlama:
                                                            if self.kv_scales is not None else None),
                                                 windows=self.cfg.windows if self.cfg.windowed else None,
                                                 **({"chunk_attn": True} if self.chunk_attn else {}),
-                                                **({"moe": self.cfg.moe} if self.cfg.n_experts else {}))
+                                                **({"moe": self.cfg.moe} if self.cfg.n_experts else {}),
+                                                **({"expert_format": "fp8"} if self.expert_dtype == "fp8" else {}))
         return self._fused
 
     def step_rows(self, tokens, pos, slots=None, emit_rows=0, pos_range=None):
@@ -671,9 +759,16 @@ class TinyLlama:
                 tw, ti = probs.topk(c.top_k, dim=-1)
                 if c.norm_topk:
                     tw = tw / tw.sum(-1, keepdim=True)
-                gu = bf(torch.einsum("btk,enk->bten", h, f32(L["w_gate_up"])))
+                if self.expert_dtype == "fp8":  # the dequantised experts: the norm is in them, the rows interleaved
+                    gu = bf(torch.einsum("btk,enk->bten", bf(rms(residual, torch.ones_like(L["ffn_norm"]))),
+                                         self.expert_weight("w_gate_up", i)))
+                    gu = torch.cat([gu[..., 0::2], gu[..., 1::2]], -1)
+                    w_down = self.expert_weight("w_down", i)
+                else:
+                    gu = bf(torch.einsum("btk,enk->bten", h, f32(L["w_gate_up"])))
+                    w_down = f32(L["w_down"])
                 act = bf(F.silu(gu[..., : c.ffn]) * gu[..., c.ffn:])
-                y = torch.einsum("btef,edf->bted", act, f32(L["w_down"]))
+                y = torch.einsum("btef,edf->bted", act, w_down)
                 y = torch.gather(y, 2, ti[..., None].expand(-1, -1, -1, c.dim)) * tw[..., None]
                 m = y[:, :, 0]
                 for j in range(1, c.top_k):

@@ -138,6 +138,76 @@ class MoePlan(ctypes.Structure):
 MAX_EXPERTS, MAX_TOP_K = 128, 8  # decode_moe.h's kMaxExperts and kMaxTopK
 
 
+class ExpertFormat(ctypes.Structure):
+    """Mirror of ``ExpertFormat`` (decode_moe.h): the format of an MoE model's stacked expert matrices, beside
+    ``MoeDims`` as ``WeightFormat`` is beside the plans (docs/MOE_FP8.md). ``w8``: 0 bf16; 1 OCP e4m3fn bytes in
+    k-step-pair order (``block_expert_fp8``) with one fp32 scale per (expert, output row)."""
+    _fields_ = [("w8", _INT)]
+
+    def __repr__(self):
+        return f"ExpertFormat(w8={self.w8})"
+
+
+EXPERT_FORMATS = {"bf16": 0, "fp8": 1}  # expert dtype -> ExpertFormat.w8
+EXPERT_BLOCK = 64  # K elements per block of the FP8 experts' byte order: a pair of k-steps
+
+
+def as_expert_format(expert_format=None, moe=None, dim: int = 0, ffn: int = 0) -> ExpertFormat:
+    """The ``ExpertFormat`` a caller means: None or "bf16", "fp8", or an ``ExpertFormat`` of w8 0 or 1. FP8 experts
+    need a routed-expert FFN (``moe``) whose ``dim`` and per-expert ``ffn`` are multiples of 64: every refusal says
+    why (host only: no library)."""
+    f = expert_format
+    if f is None:
+        return ExpertFormat(0)
+    if isinstance(f, str):
+        if f not in EXPERT_FORMATS:
+            raise ValueError(f"expert_dtype must be one of {sorted(EXPERT_FORMATS)}, got {f!r}")
+        f = ExpertFormat(EXPERT_FORMATS[f])
+    if not isinstance(f, ExpertFormat) or f.w8 not in EXPERT_FORMATS.values():
+        raise ValueError(f"expert_format must be an ExpertFormat of w8 0 or 1 or one of {sorted(EXPERT_FORMATS)}, "
+                         f"got {expert_format!r}")
+    if f.w8:
+        if moe is None:
+            raise ValueError("expert_dtype fp8 needs a routed-expert FFN: a dense model has no experts "
+                             "(its GEMM weights follow weight_dtype)")
+        if dim % EXPERT_BLOCK or ffn % EXPERT_BLOCK:
+            raise ValueError(f"FP8 experts are stored in blocks of {EXPERT_BLOCK} (pairs of k-steps): dim and the "
+                             f"per-expert ffn must be multiples of {EXPERT_BLOCK}, got dim {dim}, ffn {ffn}")
+    return ExpertFormat(f.w8)
+
+
+def _expert_perm(K: int, device=None) -> torch.Tensor:
+    """``perm[i]``: the natural k of byte i of a row in k-step-pair order."""
+    i = torch.arange(K, device=device)
+    j, g, half = i % EXPERT_BLOCK, (i % EXPERT_BLOCK) // 16, (i % 16) // 8
+    return i - j + 32 * half + 8 * g + i % 8
+
+
+def _check_expert_bytes(q, what: str):
+    if not isinstance(q, torch.Tensor) or q.dtype not in KV_FP8_DTYPES or q.dim() != 3:
+        raise TypeError(f"{what} takes e4m3 (or uint8) bytes [E, N, K]")
+    if q.shape[2] % EXPERT_BLOCK:
+        raise ValueError(f"K must be a multiple of {EXPERT_BLOCK} (a pair of k-steps), got {q.shape[2]}")
+
+
+def block_expert_fp8(q: torch.Tensor) -> torch.Tensor:
+    """FP8 expert bytes ``[E, N, K]`` from natural K order to the device order ``k_moe_gate_up`` / ``k_moe_down``
+    stream (docs/MOE_FP8.md): inside every 64-element block of a row, lane group g = 0..3 owns 16 contiguous bytes,
+    bytes ``16 g .. 16 g + 7`` the natural bytes ``8 g .. 8 g + 7`` (the even k-step of the pair) and bytes
+    ``16 g + 8 .. 16 g + 15`` the natural bytes ``32 + 8 g .. 32 + 8 g + 7`` (the odd one), so one 16-byte load feeds
+    two k-steps. A new contiguous tensor of ``q``'s dtype; plain torch on ``q``'s device."""
+    _check_expert_bytes(q, "block_expert_fp8")
+    return q.view(torch.uint8)[..., _expert_perm(q.shape[2], q.device)].contiguous().view(q.dtype)
+
+
+def unblock_expert_fp8(q: torch.Tensor) -> torch.Tensor:
+    """The inverse of ``block_expert_fp8``: device order back to natural K order."""
+    _check_expert_bytes(q, "unblock_expert_fp8")
+    out = torch.empty_like(q.view(torch.uint8))
+    out[..., _expert_perm(q.shape[2], q.device)] = q.view(torch.uint8)
+    return out.view(q.dtype)
+
+
 def check_moe(moe, dim: int, ffn: int) -> "MoeDims | None":
     """``moe`` as the fused step takes it: None (a dense model), or a ``MoeDims`` the kernels run for per-expert
     shapes ``[2 * ffn, dim]`` and ``[dim, ffn]``. Every refusal says why (host only: no library)."""
@@ -163,7 +233,7 @@ def _signatures() -> dict:
     """Every symbol ``lib()`` binds -> its argtypes. The restype is ``c_int`` unless ``_RESTYPES`` names another."""
     vp, i, f, sz, ptr = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.POINTER
     dims, wp, ip, szp, wf = ptr(LlamaDims), ptr(WeightPlan), ptr(i), ptr(sz), ptr(WeightFormat)
-    moe = ptr(MoeDims)
+    moe, ef = ptr(MoeDims), ptr(ExpertFormat)
     return {
         "p2pt_rmsnorm": [vp, vp, vp, vp, vp, i, i, f, vp],
         "p2pt_silu_mul": [vp, vp, i, i, vp],
@@ -214,6 +284,11 @@ def _signatures() -> dict:
         "p2pt_llama_decode_moe": [dims, wf, vp, ip, ptr(vp), vp, vp, vp, vp, vp, i, i, vp, sz, vp, vp, vp, i, moe],
         "p2pt_moe_ffn": [vp, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, f, vp],
         "p2pt_moe_ffn_plan": [i, i, i, i, i, i, ptr(MoePlan)],
+        "p2pt_llama_plan_kernels_experts": [dims, i, i, wf, ip, i, moe, ef],
+        "p2pt_llama_weight_layout_experts": [dims, moe, ef, ip, ip, i],
+        "p2pt_llama_decode_experts": [dims, wf, vp, ip, ptr(vp), vp, vp, vp, vp, vp, i, i, vp, sz, vp, vp, vp, i, moe,
+                                      ef],
+        "p2pt_moe_ffn_experts": [vp, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, f, vp, ef, vp, vp],
         "p2pt_attn_span": [i, i],
         "p2pt_max_rows": [],
         "p2pt_skinny_bench": [vp, vp, vp, i, i, i, i, i, i, vp],  # microbenchmark hooks (scripts/bench_skinny.py)
@@ -343,15 +418,25 @@ def moe_plan(dims: LlamaDims, moe: MoeDims, B: int) -> MoePlan:
 
 
 def plan_kernels_ok(dims: LlamaDims, B: int, emit_rows: int = 0, weight_fp8: bool = False, windows=None,
-                    weight_format=None, chunk_attn: bool = False, moe: MoeDims | None = None) -> bool:
+                    weight_format=None, chunk_attn: bool = False, moe: MoeDims | None = None,
+                    expert_format=None) -> bool:
     """Whether every stage of ``step_plan(dims, B, emit_rows)``, ``kv_plan(dims)`` and
     ``weight_plan(dims, weight_fp8)`` names a kernel the library instantiates, by the lookups its launchers use
     (host only). ``windows``: the per-layer sliding windows (``check_windows``); every layer's ``window_plan`` is
     then looked up too. ``weight_format`` (see ``as_weight_format``): the formats instead of ``weight_fp8``.
-    ``chunk_attn``: the layers that then run ``k_attn_chunk`` (``chunk_plan``) are looked up as that."""
+    ``chunk_attn``: the layers that then run ``k_attn_chunk`` (``chunk_plan``) are looked up as that.
+    ``expert_format`` (``as_expert_format``; with ``moe`` only): the experts' format, whose ``k_moe_gate_up`` /
+    ``k_moe_down`` instantiations are then the ones looked up."""
     windows = check_windows(windows, dims.n_layers)
     moe = check_moe(moe, dims.dim, dims.ffn)
-    if moe is not None:  # the gate_up and down stages are then the four MoE kernels (``moe_plan``), bf16 layers only
+    experts = as_expert_format(expert_format, moe, dims.dim, dims.ffn)
+    if moe is not None and experts.w8:
+        f = as_weight_format(weight_fp8, weight_format)
+        rc = lib().p2pt_llama_plan_kernels_experts(
+            ctypes.byref(dims), B, emit_rows, ctypes.byref(f),
+            (ctypes.c_int * len(windows))(*windows) if windows is not None else None, int(chunk_attn),
+            ctypes.byref(moe), ctypes.byref(experts))
+    elif moe is not None:  # the gate_up and down stages are then the four MoE kernels (``moe_plan``), bf16 layers only
         f = as_weight_format(weight_fp8, weight_format)
         rc = lib().p2pt_llama_plan_kernels_moe(ctypes.byref(dims), B, emit_rows, ctypes.byref(f),
                                                (ctypes.c_int * len(windows))(*windows) if windows is not None else None,
@@ -404,16 +489,22 @@ class WeightTable(list):
     aligned and its scales need no alignment. ``pack_weight_mxfp4`` makes this order from nibble codes ``[N][K]``,
     ``unpack_weight_mxfp4`` undoes it, and decode_fused.hip's accessor and the kernel's offsets mirror it.
 
-    ``moe`` (a ``MoeDims``; bf16 only, docs/MOE.md): ``dims.ffn`` is the per-expert size, w_gate_up is
+    ``moe`` (a ``MoeDims``; docs/MOE.md): ``dims.ffn`` is the per-expert size, w_gate_up is
     ``(E, 2 * ffn, dim)``, folded and pair-interleaved per expert, w_down ``(E, dim, ffn)``, and every layer ends with
-    router, bf16 ``(E, dim)`` with the FFN norm folded in, 16-byte aligned. None: the dense table, unchanged."""
+    router, bf16 ``(E, dim)`` with the FFN norm folded in, 16-byte aligned. None: the dense table, unchanged.
+    ``weight_format`` stays bf16 with it; ``expert_format`` (``as_expert_format``; docs/MOE_FP8.md) "fp8" makes
+    w_gate_up and w_down e4m3 (or uint8) bytes of the same shapes, 16-byte aligned, rows in ``block_expert_fp8``'s
+    order, and appends after every other entry, per layer, their fp32 row scales ``(E, 2 * ffn)`` and ``(E, dim)``,
+    named ``"w_gate_up scale"`` and ``"w_down scale"``. None or "bf16": the bf16 MoE table, unchanged."""
 
-    def __init__(self, dims: LlamaDims, weight_fp8: bool = False, weight_format=None, moe: MoeDims | None = None):
+    def __init__(self, dims: LlamaDims, weight_fp8: bool = False, weight_format=None, moe: MoeDims | None = None,
+                 expert_format=None):
         self.format = fmt = as_weight_format(weight_fp8, weight_format)
         self.moe = moe = check_moe(moe, dims.dim, dims.ffn)
+        self.expert_format = experts = as_expert_format(expert_format, moe, dims.dim, dims.ffn)
         if moe is not None and fmt.layers != 0:
             raise ValueError("an MoE model's expert weights are bf16 only: weight_dtype fp8 and mxfp4 are not "
-                             "supported with a routed-expert FFN")
+                             "supported with a routed-expert FFN (expert_format='fp8' quantises the experts alone)")
         d, bf, f32, u8 = dims, (torch.bfloat16,), (torch.float32,), (torch.uint8,)
         gemm, ga = (WEIGHT_FP8_DTYPES, 8) if fmt.lm_head else (bf, 2)
         n_qkv, norm = (d.H + 2 * d.Hkv) * d.D, (bf, (d.dim,), 2)
@@ -436,12 +527,18 @@ class WeightTable(list):
             layer["w_gate_up"] = (bf, (moe.n_experts, 2 * d.ffn, d.dim), 2)
             layer["w_down"] = (bf, (moe.n_experts, d.dim, d.ffn), 2)
             layer["router"] = (bf, (moe.n_experts, d.dim), 16)
+            if experts.w8:  # one 16-byte load per lane and k-step pair
+                layer["w_gate_up"] = (WEIGHT_FP8_DTYPES, (moe.n_experts, 2 * d.ffn, d.dim), 16)
+                layer["w_down"] = (WEIGHT_FP8_DTYPES, (moe.n_experts, d.dim, d.ffn), 16)
         groups = [(None, top)] + [(L, layer) for L in range(d.n_layers)]
         super().__init__(WeightEntry(n, L, *v) for L, group in groups for n, v in group.items())
         if fmt.lm_head:  # the scales, in the order of their weights: fp32 per row, or MXFP4's e8m0 byte per block
             self += [WeightEntry(n + " scale", L, u8, (shapes[n][0], shapes[n][1] // MXFP4_BLOCK), 1)
                      if L is not None and fmt.layers == 2 else WeightEntry(n + " scale", L, f32, v[1][:1], 4)
                      for L, group in groups for n, v in group.items() if n == "lm_head" or n in LAYER_GEMMS]
+        if experts.w8:  # the experts' row scales, after every other entry
+            self += [WeightEntry(n + " scale", L, f32, layer[n][1][:2], 4)
+                     for L in range(d.n_layers) for n in ("w_gate_up", "w_down")]
         self.per_layer = len(layer)
         self._at = {(e.name, e.layer): i for i, e in enumerate(self)}
 
@@ -762,7 +859,8 @@ def moe_ffn_plan(B: int, dim: int, ffn: int, moe: MoeDims) -> MoePlan:
 
 def moe_ffn(resid: torch.Tensor, ss: torch.Tensor, router: torch.Tensor, w_gate_up: torch.Tensor,
             w_down: torch.Tensor, top_k: int, norm_topk: bool = True, eps: float = 1e-5, out: dict | None = None,
-            ss_in: int | None = None) -> dict:
+            ss_in: int | None = None, gate_up_scale: torch.Tensor | None = None,
+            down_scale: torch.Tensor | None = None) -> dict:
     """One routed-expert FFN layer on caller tensors, with the fused step's four kernels (docs/MOE.md):
     ``resid += sum_j route_w[j] * down_e(SwiGLU(gate_up_e(rmsnorm(resid))))`` over each row's ``top_k`` experts.
 
@@ -773,11 +871,28 @@ def moe_ffn(resid: torch.Tensor, ss: torch.Tensor, router: torch.Tensor, w_gate_
     w_gate_up carry the norm weight folded into their columns. Returns the intermediates, each written in every slot
     a (row, choice) pair owns: route_id int32 [B, top_k] (descending probability, ties to the lower id), route_w fp32
     [B, top_k], route_rs fp32 [B], moe_h bf16 [B * top_k, ffn], moe_part fp32 [B, top_k, dim]. ``out``: tensors to
-    use for them instead of fresh ones (tests poison them)."""
+    use for them instead of fresh ones (tests poison them).
+
+    FP8 experts (docs/MOE_FP8.md): with ``gate_up_scale`` (fp32 [E, 2 * ffn]) and ``down_scale`` (fp32 [E, dim]) both
+    given, w_gate_up and w_down are e4m3 (or uint8) bytes of the same shapes in ``block_expert_fp8``'s order, and the
+    two GEMMs run their FP8 instantiations; dim and ffn must be multiples of 64. One scale without the other is
+    refused. The router stays bf16."""
+    if (gate_up_scale is None) != (down_scale is None):
+        raise ValueError("FP8 experts need both gate_up_scale and down_scale; bf16 experts take neither")
+    w8 = gate_up_scale is not None
+    for name, t, w in (("gate_up_scale", gate_up_scale, w_gate_up), ("down_scale", down_scale, w_down)):
+        shape = tuple(getattr(w, "shape", ()))[:2]  # one scale per expert and output row (host only: no device yet)
+        if w8 and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != shape):
+            raise ValueError(f"{name} must be fp32 {shape}: one scale per expert and output row, got "
+                             f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
     _check(resid, torch.bfloat16, "resid")
     dev = resid.device
-    for name, t in (("router", router), ("w_gate_up", w_gate_up), ("w_down", w_down)):
-        _check(t, torch.bfloat16, name, dev)
+    _check(router, torch.bfloat16, "router", dev)
+    for name, t in (("w_gate_up", w_gate_up), ("w_down", w_down)):
+        if w8 and (not isinstance(t, torch.Tensor) or t.dtype not in WEIGHT_FP8_DTYPES):
+            raise TypeError(f"{name}: with scales the experts are FP8, so it must be torch.float8_e4m3fn (or uint8), "
+                            f"got {getattr(t, 'dtype', type(t))}")
+        _check(t, t.dtype if w8 else torch.bfloat16, name, dev)
     _check(ss, torch.float32, "ss", dev)
     if resid.dim() != 2 or router.dim() != 2:
         raise ValueError("resid must be [B, dim] and router [E, dim]")
@@ -790,6 +905,10 @@ def moe_ffn(resid: torch.Tensor, ss: torch.Tensor, router: torch.Tensor, w_gate_
     if not _int_in(top_k, 1, MAX_TOP_K + 1):
         raise ValueError(f"top_k must be an int in 1..{MAX_TOP_K}, got {top_k!r}")
     moe = check_moe(MoeDims(E, top_k, int(bool(norm_topk))), dim, ffn)
+    experts = as_expert_format("fp8" if w8 else None, moe, dim, ffn)
+    for name, t in (("gate_up_scale", gate_up_scale), ("down_scale", down_scale)):
+        if w8:
+            _check(t, torch.float32, name, dev)
     if router.shape != (E, dim) or w_gate_up.shape != (E, 2 * ffn, dim) or w_down.shape != (E, dim, ffn):
         raise ValueError(f"expected router [{E}, {dim}], w_gate_up [{E}, {2 * ffn}, {dim}], w_down [{E}, {dim}, {ffn}]")
     for name, t in (("resid", resid), ("router", router), ("w_gate_up", w_gate_up), ("w_down", w_down)):
@@ -811,6 +930,12 @@ def moe_ffn(resid: torch.Tensor, ss: torch.Tensor, router: torch.Tensor, w_gate_
         if tuple(t.shape) != shape:
             raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
         res[name] = t
+    if w8:
+        _ok(lib().p2pt_moe_ffn_experts(_p(resid), _p(ss), ss_in, _p(router), _p(w_gate_up), _p(w_down),
+                                       _p(res["route_id"]), _p(res["route_w"]), _p(res["route_rs"]), _p(res["moe_h"]),
+                                       _p(res["moe_part"]), B, dim, ffn, E, top_k, moe.norm_topk, eps, _stream(resid),
+                                       ctypes.byref(experts), _p(gate_up_scale), _p(down_scale)), "moe_ffn")
+        return res
     _ok(lib().p2pt_moe_ffn(_p(resid), _p(ss), ss_in, _p(router), _p(w_gate_up), _p(w_down), _p(res["route_id"]),
                            _p(res["route_w"]), _p(res["route_rs"]), _p(res["moe_h"]), _p(res["moe_part"]), B, dim, ffn,
                            E, top_k, moe.norm_topk, eps, _stream(resid)), "moe_ffn")
@@ -1369,6 +1494,10 @@ class FusedLlamaDecoder:
     the per-expert size, the table is ``WeightTable(.., moe=moe)`` (stacked experts and a router per layer, bf16
     only), and each layer's gate/up and down kernels give way to ``k_moe_route``, ``k_moe_gate_up``, ``k_moe_down`` and
     ``k_moe_combine`` on ``moe_plan``'s grids: 7 kernels per layer, still one capturable call.
+    ``expert_format`` (``as_expert_format``; with ``moe`` only; docs/MOE_FP8.md): "fp8" has the stacked experts as
+    e4m3 bytes in ``block_expert_fp8``'s order with fp32 row scales after the table
+    (``WeightTable(.., expert_format=)``), run by the FP8 instantiations of ``k_moe_gate_up`` and ``k_moe_down`` on the
+    same plan; everything else of the model stays bf16. None or "bf16": nothing above changes.
 
     Holds the weight pointer table and a zero-initialised workspace; ``step``
     validates the per-call tensors and launches on the current stream (capturable
@@ -1377,9 +1506,10 @@ class FusedLlamaDecoder:
 
     def __init__(self, dims: LlamaDims, weights: list, k_cache: torch.Tensor, v_cache: torch.Tensor,
                  weight_fp8: bool = False, kv_scales: torch.Tensor | None = None, windows=None, weight_format=None,
-                 chunk_attn: bool = False, moe: MoeDims | None = None):
+                 chunk_attn: bool = False, moe: MoeDims | None = None, expert_format=None):
         self.dims = dims
         self.moe = check_moe(moe, dims.dim, dims.ffn)
+        self.expert_format = as_expert_format(expert_format, self.moe, dims.dim, dims.ffn)
         if not isinstance(chunk_attn, bool):
             raise TypeError(f"chunk_attn must be a bool, got {chunk_attn!r}")
         self.chunk_attn = chunk_attn
@@ -1409,7 +1539,7 @@ class FusedLlamaDecoder:
                 raise ValueError(f"kv_scales must be fp32 [4, {dims.n_layers}, {dims.Hkv}] (1 / k, 1 / v, k, v per layer "
                                  f"and KV head), got {getattr(kv_scales, 'dtype', type(kv_scales))} "
                                  f"{tuple(getattr(kv_scales, 'shape', ()))}")
-        self.table = table = WeightTable(dims, weight_format=fmt, moe=self.moe)
+        self.table = table = WeightTable(dims, weight_format=fmt, moe=self.moe, expert_format=self.expert_format)
         if len(weights) != len(table):
             raise ValueError(f"weight table: embed, final_norm, lm_head, "
                              + ("inv_freq, " if dims.rope_table else "") + f"then {table.per_layer} per layer "
@@ -1421,7 +1551,9 @@ class FusedLlamaDecoder:
                              + ("; mxfp4: then lm_head's fp32 row scales and four e8m0 block-scale tensors per layer"
                                 if fmt.layers == 2 else "")
                              + ("; MoE: w_gate_up and w_down stacked per expert, and router last in every layer"
-                                if self.moe is not None else ""))
+                                if self.moe is not None else "")
+                             + ("; FP8 experts: then their fp32 row scales, w_gate_up's and w_down's per layer"
+                                if self.expert_format.w8 else ""))
         # Every entry's dtype and shape, from the description alone: a refusal here needs no device. A weight shorter
         # than dims says would be read past its end (k_skinny sizes its descriptors from dims, k_embed indexes vocab
         # rows). The norm slots the kernels do not read are held to (dim,) too.
@@ -1433,6 +1565,9 @@ class FusedLlamaDecoder:
                     raise TypeError(f"{name}: the weight format is mxfp4, so "
                                     + ("the block scales must be e8m0 bytes (torch.uint8)" if e.name.endswith(" scale")
                                        else "the weight must be nibble bytes (torch.uint8)") + f", got {got}")
+                if len(e.dtypes) > 1 and self.expert_format.w8:
+                    raise TypeError(f"{name}: the experts are FP8, so the weight must be torch.float8_e4m3fn (or "
+                                    f"uint8), got {got}")
                 if len(e.dtypes) > 1:
                     raise TypeError(f"{name}: weight_fp8 is set, so the weight must be torch.float8_e4m3fn (or uint8), "
                                     f"got {got}")
@@ -1443,6 +1578,7 @@ class FusedLlamaDecoder:
                 raise ValueError(f"{name} has shape {tuple(t.shape)}, not {e.shape}"
                                  + ("" if not e.name.endswith(" scale") else
                                     f": one e8m0 byte per {MXFP4_BLOCK}-element block" if e.dtypes == (torch.uint8,)
+                                    else ": one fp32 scale per expert and output row" if self.expert_format.w8
                                     else ": one fp32 scale per output row")
                                  + (": two nibbles per byte" if fmt.layers == 2 and e.name in LAYER_GEMMS else ""))
         L, Bmax, S, Hkv, D = k_cache.shape
@@ -1477,7 +1613,8 @@ class FusedLlamaDecoder:
         # plan without its instantiation is refused here with a message, not at the first launch with an error code.
         for B in (1, 17, 33):
             if self.moe is not None and not plan_kernels_ok(dims, B, windows=self.windows, weight_format=fmt,
-                                                            chunk_attn=chunk_attn, moe=self.moe):
+                                                            chunk_attn=chunk_attn, moe=self.moe,
+                                                            expert_format=self.expert_format):
                 raise ValueError(f"the fused decode kernels have no instantiation for a step of {B} rows of this "
                                  f"MoE model ({self.moe!r}, dim {dims.dim}, ffn {dims.ffn})")
         self.weights = weights  # keep alive
@@ -1565,6 +1702,14 @@ class FusedLlamaDecoder:
             raise ValueError(f"rows must be 1..{limit} with matching pos/ids")
         if logits.shape != (B, d.vocab):
             raise ValueError("logits must be [B, vocab]")
+        if self.expert_format.w8:
+            _ok(lib().p2pt_llama_decode_experts(ctypes.byref(d), ctypes.byref(self.weight_format), _p(self.kv_scales),
+                                                self._windows, self._wptr, _p(self.k_cache), _p(self.v_cache),
+                                                _p(tokens), _p(pos), _p(slots), B, emit_rows, _p(self.ws),
+                                                self.ws.numel(), _p(logits), _p(ids), _stream(tokens),
+                                                int(self.chunk_attn), ctypes.byref(self.moe),
+                                                ctypes.byref(self.expert_format)), "llama_decode")
+            return
         if self.moe is not None:
             _ok(lib().p2pt_llama_decode_moe(ctypes.byref(d), ctypes.byref(self.weight_format), _p(self.kv_scales),
                                             self._windows, self._wptr, _p(self.k_cache), _p(self.v_cache), _p(tokens),

@@ -140,6 +140,13 @@ bool chunk_layer(int chunk_attn, int B, const WindowPlan& wn) { return chunk_att
 // plans, lays out and launches what it did. With it, LlamaDims::ffn is the per-expert intermediate size.
 using p2pt_moe::MoeDims;
 using p2pt_moe::MoePlan;
+using p2pt_moe::ExpertFormat;
+// The experts' format beside MoeDims (docs/MOE_FP8.md): bf16, or FP8 in k-step-pair order, whose rows are whole pairs.
+// nullptr everywhere below is bf16, and then nothing changes.
+bool experts_ok(const LlamaDims& d, const ExpertFormat* f) {
+  return !f || f->w8 == 0 || (f->w8 == 1 && d.dim % 64 == 0 && d.ffn % 64 == 0);
+}
+int expert_w8(const ExpertFormat* f) { return f ? f->w8 : 0; }
 bool moe_ok(const LlamaDims& d, const MoeDims& m) {
   if (m.n_experts < 1 || m.n_experts > p2pt_moe::kMaxExperts) return false;
   if (m.top_k < 1 || m.top_k > std::min(p2pt_moe::kMaxTopK, m.n_experts)) return false;
@@ -185,6 +192,9 @@ GemmPlan plan_lm_head(const LlamaDims& d, int rows) {
 // What the four kernels launch for B rows: a pure function of (B, dims, moe). Waves and load batch follow plan_gemm's
 // rule for the expert's own K; the row tiles held per weight pass cover B pairs, the most one expert gets when a row
 // names it once; k_moe_combine's grid is the dense down projection's, so the next norm's readers keep their ss_in.
+// FP8 experts (ExpertFormat) run this plan int for int. Their kernels count K in pairs of k-steps, so a load batch um
+// means max(um / 2, 1) pairs: 1 -> 2 k-steps in flight, 2 -> 2, 4 -> 4, the bf16 kernel's registers in flight except
+// at um = 1; and gu_nw / dn_nw waves split K / 64 pairs, so waves past K / 64 (a K of 64 or 128 with 4 waves) stay idle.
 MoePlan plan_moe(const LlamaDims& d, const MoeDims& m, int B) {
   MoePlan p{};
   const GemmPlan gu = plan_gemm(EPI_SILU, 1, B, 2 * d.ffn, d.dim), dn = plan_gemm(EPI_RESID, 1, B, d.dim, d.ffn);
@@ -323,7 +333,10 @@ Workspace carve(const LlamaDims& d, uint8_t* base, const MoeDims* moe = nullptr)
 // fp32 row scales: lm_head's, then per layer wqkv's, wo's, w_gate_up's and w_down's. An MXFP4 table has the same
 // entries: lm_head as in an FP8 table, each layer GEMM as N * K / 2 bytes, and after the table lm_head's fp32 row
 // scales, then per layer the four e8m0 scale tensors [N][K / 32] where the FP8 table has row scales.
-// An MoE table (moe set; bf16 only) has one more entry per layer, after every other: router, bf16 [E][dim] with the FFN
+// With FP8 experts (ew8; docs/MOE_FP8.md) w_gate_up and w_down are e4m3 bytes of the same shapes, 16-byte aligned, rows
+// in k-step-pair order, and their fp32 row scales [E][2 ffn_e] and [E][dim] follow every other entry, per layer in that
+// order; scale(R_W_GATE_UP / R_W_DOWN, L) reaches them, and no role is added.
+// An MoE table (moe set; bf16 apart from the experts) has one more entry per layer, after every other: router, bf16 [E][dim] with the FFN
 // norm folded in; its w_gate_up is [E][2 ffn_e][dim], folded and pair-interleaved per expert, and its w_down
 // [E][dim][ffn_e]. R_ROUTER follows R_NROLES so that p2pt_llama_weight_layout's 13 roles per layer stay what they are.
 enum Role : int { R_EMBED, R_FINAL_NORM, R_LM_HEAD, R_INV_FREQ, R_ATTN_NORM, R_WQKV, R_WO, R_FFN_NORM, R_W_GATE_UP,
@@ -333,9 +346,10 @@ struct WeightTable {
   WeightFormat f;
   const void* const* w;
   int moe = 0;  // the layers carry a router
+  int ew8 = 0;  // the experts are FP8 (moe only): two scale entries per layer after the table
   int per_layer() const { return (d.qk_norm ? 8 : d.qkv_bias ? 7 : 6) + moe; }
   int scales0() const { return 3 + d.rope_table + per_layer() * d.n_layers; }
-  int size() const { return scales0() + (f.lm_head ? 1 + 4 * d.n_layers : 0); }
+  int size() const { return scales0() + (f.lm_head ? 1 + 4 * d.n_layers : 0) + (ew8 ? 2 * d.n_layers : 0); }
   // The format of a GEMM weight's role (0 for every other role).
   int format(Role r) const {
     return r == R_LM_HEAD ? f.lm_head : r == R_WQKV || r == R_WO || r == R_W_GATE_UP || r == R_W_DOWN ? f.layers : 0;
@@ -353,6 +367,8 @@ struct WeightTable {
   // Index of the scales of a GEMM weight (fp32 row scales, or an MXFP4 weight's e8m0 block scales); -1 for a bf16
   // table (where launch() wants none) or another role.
   int scale_index(Role r, int L = 0) const {
+    // FP8 experts: the layers are bf16 (an MoE model's only format), so the experts' scales are all there is.
+    if (ew8 && (r == R_W_GATE_UP || r == R_W_DOWN)) return scales0() + 2 * L + (r == R_W_DOWN);
     const int j = r == R_WQKV ? 1 : r == R_WO ? 2 : r == R_W_GATE_UP ? 3 : r == R_W_DOWN ? 4 : 0;
     return !format(r) ? -1 : scales0() + (j ? 4 * L + j : 0);
   }
@@ -657,11 +673,16 @@ int p2pt_llama_kv_plan(const LlamaDims* d, KvPlan* out) {
 // slots inside the stride. p2pt_llama_plan_kernels_fmt is the call without it.
 // moe (p2pt_llama_plan_kernels_moe): stages gate_up and down are then the routed-expert FFN's kernels (all four must
 // exist), bf16 layers only; a MoeDims the step refuses, or FP8 / MXFP4 layers with it, are -1. nullptr: the call without.
-int p2pt_llama_plan_kernels_moe(const LlamaDims* d, int B, int emit_rows, const WeightFormat* fmt, const int* windows,
-                                int chunk_attn, const MoeDims* moe) {
+// experts (p2pt_llama_plan_kernels_experts): the format of an MoE model's experts; the gate_up and down stages are then
+// that format's instantiations. FP8 without moe, or with a dim or ffn that is no multiple of 64, is -1. nullptr: bf16.
+int p2pt_llama_plan_kernels_experts(const LlamaDims* d, int B, int emit_rows, const WeightFormat* fmt,
+                                    const int* windows, int chunk_attn, const MoeDims* moe,
+                                    const ExpertFormat* experts) {
   if (!dims_ok(*d) || !rows_ok(B) || !format_ok(*fmt) || !windows_ok(*d, Windows{windows})) return -1;
   if (moe && (!moe_ok(*d, *moe) || fmt->layers != 0)) return -1;
-  const bool moe_found = !moe || p2pt_moe::moe_kernels_exist(plan_moe(*d, *moe, B));
+  if (!experts_ok(*d, experts) || (!moe && expert_w8(experts))) return -1;
+  const bool moe_found =
+      !moe || p2pt_moe::moe_kernels_exist(plan_moe(*d, *moe, B), ExpertFormat{expert_w8(experts)});
   const StepPlan P = plan_step(*d, B, emit_rows);
   const KvPlan KV = plan_kv(*d);
   const int w8 = fmt->layers;
@@ -687,6 +708,10 @@ int p2pt_llama_plan_kernels_moe(const LlamaDims* d, int B, int emit_rows, const 
   for (int n = 0; n < 8; n++)
     if (!found[n]) return 1 + n;
   return 0;
+}
+int p2pt_llama_plan_kernels_moe(const LlamaDims* d, int B, int emit_rows, const WeightFormat* fmt, const int* windows,
+                                int chunk_attn, const MoeDims* moe) {
+  return p2pt_llama_plan_kernels_experts(d, B, emit_rows, fmt, windows, chunk_attn, moe, nullptr);
 }
 int p2pt_llama_plan_kernels_chunk(const LlamaDims* d, int B, int emit_rows, const WeightFormat* fmt, const int* windows,
                                   int chunk_attn) {
@@ -760,6 +785,19 @@ int p2pt_llama_weight_layout_moe(const LlamaDims* d, const MoeDims* moe, int* in
     for (int r = 0; r < R_NROLES_MOE; r++) index[L * R_NROLES_MOE + r] = T.index(Role(r), L);
   return T.size();
 }
+// The same with the experts' format (nullptr: bf16, the call above with no scales): scale_index[L * 14 + r] is where the
+// fp32 row scales of role r sit, -1 for every role but w_gate_up and w_down of an FP8-expert table.
+int p2pt_llama_weight_layout_experts(const LlamaDims* d, const MoeDims* moe, const ExpertFormat* experts, int* index,
+                                     int* scale_index, int n) {
+  if (!dims_ok(*d) || !moe_ok(*d, *moe) || !experts_ok(*d, experts) || n < R_NROLES_MOE * d->n_layers) return -1;
+  const WeightTable T{*d, WeightFormat{0, 0}, nullptr, 1, expert_w8(experts)};
+  for (int L = 0; L < d->n_layers; L++)
+    for (int r = 0; r < R_NROLES_MOE; r++) {
+      index[L * R_NROLES_MOE + r] = T.index(Role(r), L);
+      scale_index[L * R_NROLES_MOE + r] = T.scale_index(Role(r), L);
+    }
+  return T.size();
+}
 // The same for a WeightPlan (bf16 or FP8 throughout; anything else is refused).
 int p2pt_llama_weight_layout(const LlamaDims* d, const WeightPlan* wp, int* index, int* scale_index, int n) {
   if (!weights_ok(*wp)) return -1;
@@ -819,13 +857,22 @@ int p2pt_max_rows() { return kMaxM; }
 //      w_down [E][dim][ffn]. The layer's gate/up and down kernels give way to k_moe_route, k_moe_gate_up, k_moe_down
 //      and k_moe_combine on MoePlan's grids; every other launch is the dense step's. bf16 layers only. The workspace
 //      is p2pt_llama_ws_bytes_moe's. moe == nullptr is p2pt_llama_decode_chunk, launch for launch.
-int p2pt_llama_decode_moe(const LlamaDims* dp, const WeightFormat* fmt, const float* kv_scales, const int* windows,
-                          const void* const* w, void* k_cache, void* v_cache, const int64_t* tokens, const int* pos,
-                          const int* slots, int B, int emit_rows, void* ws, size_t ws_bytes, void* logits,
-                          int64_t* ids, void* stream, int chunk_attn, const MoeDims* moe) {
+//   FP8 experts (p2pt_llama_decode_experts with ExpertFormat::w8; docs/MOE_FP8.md): w_gate_up and w_down are e4m3 bytes
+//      of the same shapes, 16-byte aligned, quantised after the fold and the interleave, every row in k-step-pair
+//      order, and after every other entry of the table come, per layer, their fp32 row scales [E][2 * ffn] and
+//      [E][dim]. k_moe_gate_up and k_moe_down are then their FP8 instantiations on the same MoePlan; every other
+//      launch, the router's included, is unchanged. dim and ffn must be multiples of 64. experts == nullptr (or w8 = 0)
+//      is p2pt_llama_decode_moe, launch for launch; FP8 experts without moe are refused.
+int p2pt_llama_decode_experts(const LlamaDims* dp, const WeightFormat* fmt, const float* kv_scales, const int* windows,
+                              const void* const* w, void* k_cache, void* v_cache, const int64_t* tokens,
+                              const int* pos, const int* slots, int B, int emit_rows, void* ws, size_t ws_bytes,
+                              void* logits, int64_t* ids, void* stream, int chunk_attn, const MoeDims* moe,
+                              const ExpertFormat* experts) {
   const LlamaDims d = *dp;
   if (!dims_ok(d) || !rows_ok(B) || (!slots && B > d.max_batch) || !format_ok(*fmt)) return int(hipErrorInvalidValue);
   if (moe && (!moe_ok(d, *moe) || fmt->layers != 0)) return int(hipErrorInvalidValue);
+  if (!experts_ok(d, experts) || (!moe && expert_w8(experts))) return int(hipErrorInvalidValue);
+  const ExpertFormat EF{expert_w8(experts)};
   if (kv_scales && !d.kv_fp8) return int(hipErrorInvalidValue);
   const Windows WN{windows};
   if (!windows_ok(d, WN)) return int(hipErrorInvalidValue);
@@ -842,7 +889,7 @@ int p2pt_llama_decode_moe(const LlamaDims* dp, const WeightFormat* fmt, const fl
   hipError_t e;
   auto failed = [&](hipError_t r) { return (e = r) != hipSuccess; };
 
-  const WeightTable T{d, *fmt, w, moe ? 1 : 0};
+  const WeightTable T{d, *fmt, w, moe ? 1 : 0, EF.w8};
   const void* inv_freq = T.get(R_INV_FREQ);
   hipLaunchKernelGGL(k_embed, dim3(B), dim3(256), 0, s, static_cast<const uint16_t*>(T.get(R_EMBED)), tokens, W.resid,
                      W.ss, d.dim, d.vocab);
@@ -882,10 +929,11 @@ int p2pt_llama_decode_moe(const LlamaDims* dp, const WeightFormat* fmt, const fl
     if (moe) {
       // resid and ss as the O projection left them; k_moe_combine leaves them as the down projection would.
       const p2pt_moe::MoeArgs ma{W.resid, W.ss, P.gate_up.ss_in, static_cast<const uint16_t*>(T.get(R_ROUTER, L)),
-                                 static_cast<const uint16_t*>(T.get(R_W_GATE_UP, L)),
-                                 static_cast<const uint16_t*>(T.get(R_W_DOWN, L)), W.route_id, W.route_w, W.route_rs,
-                                 W.moe_h, W.moe_part, B, d.dim, d.ffn, moe->n_experts, moe->top_k, moe->norm_topk, d.eps};
-      if (failed(p2pt_moe::launch_moe(MP, ma, s))) return int(e);
+                                 T.get(R_W_GATE_UP, L), T.get(R_W_DOWN, L), W.route_id, W.route_w, W.route_rs,
+                                 W.moe_h, W.moe_part, B, d.dim, d.ffn, moe->n_experts, moe->top_k, moe->norm_topk, d.eps,
+                                 static_cast<const float*>(T.scale(R_W_GATE_UP, L)),
+                                 static_cast<const float*>(T.scale(R_W_DOWN, L))};
+      if (failed(p2pt_moe::launch_moe(MP, ma, s, EF))) return int(e);
       continue;
     }
     if (failed(launch(P.gate_up, to_gate_up, s, w8))) return int(e);
@@ -897,6 +945,13 @@ int p2pt_llama_decode_moe(const LlamaDims* dp, const WeightFormat* fmt, const fl
   if (failed(launch(P.lm_head, to_logits, s, fmt->lm_head))) return int(e);
   hipLaunchKernelGGL(k_argmax_merge, dim3(P.emit_rows), dim3(256), 0, s, W.am_val, W.am_idx, P.am_parts, ids);
   return int(hipGetLastError());
+}
+int p2pt_llama_decode_moe(const LlamaDims* dp, const WeightFormat* fmt, const float* kv_scales, const int* windows,
+                          const void* const* w, void* k_cache, void* v_cache, const int64_t* tokens, const int* pos,
+                          const int* slots, int B, int emit_rows, void* ws, size_t ws_bytes, void* logits,
+                          int64_t* ids, void* stream, int chunk_attn, const MoeDims* moe) {
+  return p2pt_llama_decode_experts(dp, fmt, kv_scales, windows, w, k_cache, v_cache, tokens, pos, slots, B, emit_rows,
+                                   ws, ws_bytes, logits, ids, stream, chunk_attn, moe, nullptr);
 }
 int p2pt_llama_decode_chunk(const LlamaDims* dp, const WeightFormat* fmt, const float* kv_scales, const int* windows,
                             const void* const* w, void* k_cache, void* v_cache, const int64_t* tokens, const int* pos,
@@ -990,19 +1045,30 @@ int p2pt_chunk_attention(const void* q, const void* kc, const void* vc, const in
 // (cb_grid: p2pt_llama_moe_plan's); router bf16 [E][dim], w_gate_up bf16 [E][2 * ffn][dim] and w_down bf16
 // [E][dim][ffn] as the step's weight table holds them; route_id int32 and route_w fp32 [B][top_k], route_rs fp32 [B],
 // moe_h bf16 [B * top_k][ffn], moe_part fp32 [B][top_k][dim]: outputs, every slot a pair owns written.
-int p2pt_moe_ffn(void* resid, float* ss, int ss_in, const void* router, const void* w_gate_up, const void* w_down,
-                 int* route_id, float* route_w, float* route_rs, void* moe_h, float* moe_part, int B, int dim, int ffn,
-                 int E, int top_k, int norm_topk, float eps, void* stream) {
+// FP8 experts (p2pt_moe_ffn_experts with ExpertFormat::w8): w_gate_up and w_down are e4m3 bytes of the same shapes in
+// k-step-pair order, gate_up_scale fp32 [E][2 * ffn] and down_scale fp32 [E][dim] their row scales; dim and ffn
+// multiples of 64. experts == nullptr (or w8 = 0) wants both scales nullptr and is p2pt_moe_ffn.
+int p2pt_moe_ffn_experts(void* resid, float* ss, int ss_in, const void* router, const void* w_gate_up,
+                         const void* w_down, int* route_id, float* route_w, float* route_rs, void* moe_h,
+                         float* moe_part, int B, int dim, int ffn, int E, int top_k, int norm_topk, float eps,
+                         void* stream, const ExpertFormat* experts, const float* gate_up_scale,
+                         const float* down_scale) {
   if (!rows_ok(B) || dim <= 0 || ffn <= 0 || dim % 32 || ffn % 32) return int(hipErrorInvalidValue);
   LlamaDims d{};
   d.dim = dim, d.ffn = ffn;
   const MoeDims m{E, top_k, norm_topk};
-  if (!moe_ok(d, m)) return int(hipErrorInvalidValue);
-  const p2pt_moe::MoeArgs a{static_cast<uint16_t*>(resid), ss, ss_in, static_cast<const uint16_t*>(router),
-                            static_cast<const uint16_t*>(w_gate_up), static_cast<const uint16_t*>(w_down), route_id,
-                            route_w, route_rs, static_cast<uint16_t*>(moe_h), moe_part, B, dim, ffn, E, top_k, norm_topk,
-                            eps};
-  return int(p2pt_moe::launch_moe(plan_moe(d, m, B), a, static_cast<hipStream_t>(stream)));
+  if (!moe_ok(d, m) || !experts_ok(d, experts)) return int(hipErrorInvalidValue);
+  const p2pt_moe::MoeArgs a{static_cast<uint16_t*>(resid), ss, ss_in, static_cast<const uint16_t*>(router), w_gate_up,
+                            w_down, route_id, route_w, route_rs, static_cast<uint16_t*>(moe_h), moe_part, B, dim, ffn,
+                            E, top_k, norm_topk, eps, gate_up_scale, down_scale};
+  return int(p2pt_moe::launch_moe(plan_moe(d, m, B), a, static_cast<hipStream_t>(stream),
+                                  ExpertFormat{expert_w8(experts)}));
+}
+int p2pt_moe_ffn(void* resid, float* ss, int ss_in, const void* router, const void* w_gate_up, const void* w_down,
+                 int* route_id, float* route_w, float* route_rs, void* moe_h, float* moe_part, int B, int dim, int ffn,
+                 int E, int top_k, int norm_topk, float eps, void* stream) {
+  return p2pt_moe_ffn_experts(resid, ss, ss_in, router, w_gate_up, w_down, route_id, route_w, route_rs, moe_h, moe_part,
+                              B, dim, ffn, E, top_k, norm_topk, eps, stream, nullptr, nullptr, nullptr);
 }
 // plan_moe for the standalone op's shapes (host only).
 int p2pt_moe_ffn_plan(int B, int dim, int ffn, int E, int top_k, int norm_topk, MoePlan* out) {

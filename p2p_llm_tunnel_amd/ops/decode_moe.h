@@ -20,6 +20,14 @@ struct MoeDims {
   int norm_topk;  // 1: the top-k probabilities are renormalised to sum to one (Mixtral)
 };
 
+// The format of the stacked expert matrices (w_gate_up, w_down), beside MoeDims as WeightFormat is beside the plans
+// (mirrored with ctypes; docs/MOE_FP8.md). 0: bf16. 1: OCP e4m3fn bytes in k-step-pair order with one fp32 scale per
+// (expert, output row). It changes no field of MoePlan: the grids, wave counts, row tiles and load batches are the
+// bf16 kernels'. The router, the attention projections and the LM head are bf16 either way.
+struct ExpertFormat {
+  int w8;
+};
+
 // What the four kernels launch for B rows (mirrored with ctypes): every field a function of (B, dims, MoeDims).
 struct MoePlan {
   int route_grid, route_waves;      // k_moe_route: one workgroup per row
@@ -37,8 +45,9 @@ struct MoeArgs {
   float* ss;                // fp32 [parts][kMaxM]: read (ss_in partials) by k_moe_route, rewritten (cb_grid) by combine
   int ss_in;                // partials the residual's producer left
   const uint16_t* router;   // bf16 [E][dim], the FFN norm weight folded in
-  const uint16_t* w_gate_up;  // bf16 [E][2 ffn_e][dim], folded, rows interleaved (gate_j, up_j) per expert
-  const uint16_t* w_down;     // bf16 [E][dim][ffn_e]
+  const void* w_gate_up;    // bf16 [E][2 ffn_e][dim], folded, rows interleaved (gate_j, up_j) per expert; with
+                            // ExpertFormat::w8 e4m3 bytes of the same shape, every row in k-step-pair order
+  const void* w_down;       // bf16 (or e4m3 bytes, likewise) [E][dim][ffn_e]
   int* route_id;            // int32 [B][top_k], descending probability
   float* route_w;           // fp32 [B][top_k]
   float* route_rs;          // fp32 [B]: 1 / rms of the row, as the router used it
@@ -46,12 +55,15 @@ struct MoeArgs {
   float* moe_part;          // fp32 [B][top_k][dim]
   int B, dim, ffn, E, top_k, norm_topk;
   float eps;
+  const float* gate_up_scale;  // ExpertFormat::w8: fp32 [E][2 ffn_e], the row scales of w_gate_up; nullptr for bf16
+  const float* down_scale;     // ExpertFormat::w8: fp32 [E][dim]; nullptr for bf16
 };
 
 // The four launches of one MoE layer, in order, on stream s; a plan that names a kernel which is not instantiated, or
-// arguments outside what the kernels index, are hipErrorInvalidValue and nothing is launched.
-hipError_t launch_moe(const MoePlan& p, const MoeArgs& a, hipStream_t s);
-// Whether the plan's kernels exist (host only).
-bool moe_kernels_exist(const MoePlan& p);
+// arguments outside what the kernels index, are hipErrorInvalidValue and nothing is launched. f: the experts' format;
+// the GEMM kernels are then its instantiations, and the scales must be there exactly when it is FP8.
+hipError_t launch_moe(const MoePlan& p, const MoeArgs& a, hipStream_t s, ExpertFormat f = ExpertFormat{0});
+// Whether the plan's kernels exist in format f (host only).
+bool moe_kernels_exist(const MoePlan& p, ExpertFormat f = ExpertFormat{0});
 
 }  // namespace p2pt_moe

@@ -13,29 +13,36 @@ namespace {
 using p2pt_moe::MoePlan;
 using MoeKernel = void (*)(MoeArgs);
 
-// k_moe_gate_up / k_moe_down<NW, RT, UM> exist for NW in {4, 8}, RT in {1, 2, 4}, UM in {1, 2, 4}: what plan_moe
-// can name. nullptr for anything else.
-template <bool DOWN, int NW, int RT>
+// k_moe_gate_up / k_moe_down<NW, RT, UM, W8> exist for NW in {4, 8}, RT in {1, 2, 4}, UM in {1, 2, 4}, W8 in {0, 1}:
+// what plan_moe can name, in either expert format. nullptr for anything else. An FP8 kernel's load batch is counted in
+// k-step pairs (decode_moe_kernels.h), so a plan's um of 1 runs 2 k-steps a batch: the <.., 2, 1> instantiation.
+template <bool DOWN, int NW, int RT, int W8>
 MoeKernel by_um(int um) {
   switch (um) {
-    case 1: return DOWN ? k_moe_down<NW, RT, 1> : k_moe_gate_up<NW, RT, 1>;
-    case 2: return DOWN ? k_moe_down<NW, RT, 2> : k_moe_gate_up<NW, RT, 2>;
-    case 4: return DOWN ? k_moe_down<NW, RT, 4> : k_moe_gate_up<NW, RT, 4>;
+    case 1:
+      if constexpr (W8 != 0) return DOWN ? k_moe_down<NW, RT, 2, W8> : k_moe_gate_up<NW, RT, 2, W8>;
+      else return DOWN ? k_moe_down<NW, RT, 1> : k_moe_gate_up<NW, RT, 1>;
+    case 2: return DOWN ? k_moe_down<NW, RT, 2, W8> : k_moe_gate_up<NW, RT, 2, W8>;
+    case 4: return DOWN ? k_moe_down<NW, RT, 4, W8> : k_moe_gate_up<NW, RT, 4, W8>;
   }
   return nullptr;
 }
-template <bool DOWN, int NW>
+template <bool DOWN, int NW, int W8>
 MoeKernel by_rt(int rt, int um) {
   switch (rt) {
-    case 1: return by_um<DOWN, NW, 1>(um);
-    case 2: return by_um<DOWN, NW, 2>(um);
-    case 4: return by_um<DOWN, NW, 4>(um);
+    case 1: return by_um<DOWN, NW, 1, W8>(um);
+    case 2: return by_um<DOWN, NW, 2, W8>(um);
+    case 4: return by_um<DOWN, NW, 4, W8>(um);
   }
   return nullptr;
 }
+template <bool DOWN, int W8>
+MoeKernel by_nw(int nw, int rt, int um) {
+  return nw == 4 ? by_rt<DOWN, 4, W8>(rt, um) : nw == 8 ? by_rt<DOWN, 8, W8>(rt, um) : nullptr;
+}
 template <bool DOWN>
-MoeKernel moe_kernel(int nw, int rt, int um) {
-  return nw == 4 ? by_rt<DOWN, 4>(rt, um) : nw == 8 ? by_rt<DOWN, 8>(rt, um) : nullptr;
+MoeKernel moe_kernel(int nw, int rt, int um, int w8 = 0) {
+  return w8 == 0 ? by_nw<DOWN, 0>(nw, rt, um) : w8 == 1 ? by_nw<DOWN, 1>(nw, rt, um) : nullptr;
 }
 
 int log2_exact(int v) { return v == 4 ? 2 : v == 8 ? 3 : v == 16 ? 4 : -1; }
@@ -44,13 +51,13 @@ int log2_exact(int v) { return v == 4 ? 2 : v == 8 ? 3 : v == 16 ? 4 : -1; }
 
 namespace p2pt_moe {
 
-bool moe_kernels_exist(const MoePlan& p) {
-  return moe_kernel<false>(p.gu_nw, p.gu_rt, p.gu_um) && moe_kernel<true>(p.dn_nw, p.dn_rt, p.dn_um) &&
+bool moe_kernels_exist(const MoePlan& p, ExpertFormat f) {
+  return moe_kernel<false>(p.gu_nw, p.gu_rt, p.gu_um, f.w8) && moe_kernel<true>(p.dn_nw, p.dn_rt, p.dn_um, f.w8) &&
          p.route_waves == kRouteWaves && p.cb_waves == kCombineWaves && log2_exact(p.cb_cols) > 0;
 }
 
-hipError_t launch_moe(const MoePlan& p, const MoeArgs& a, hipStream_t s) {
-  if (!moe_kernels_exist(p)) return hipErrorInvalidValue;
+hipError_t launch_moe(const MoePlan& p, const MoeArgs& a, hipStream_t s, ExpertFormat f) {
+  if (!moe_kernels_exist(p, f)) return hipErrorInvalidValue;
   // What the kernels index without a test of their own.
   if (a.B < 1 || a.B > kMaxM || a.E < 1 || a.E > kMaxExperts || a.top_k < 1 || a.top_k > kMaxTopK || a.top_k > a.E)
     return hipErrorInvalidValue;
@@ -64,10 +71,15 @@ hipError_t launch_moe(const MoePlan& p, const MoeArgs& a, hipStream_t s) {
   if (!a.resid || !a.ss || !a.router || !a.w_gate_up || !a.w_down || !a.route_id || !a.route_w || !a.route_rs ||
       !a.moe_h || !a.moe_part)
     return hipErrorInvalidValue;
+  // FP8 experts: whole k-step pairs of both K (the kernels split and load K by the pair), each expert's slice in bytes
+  // below kOob (half the bf16 slice above, tested on its own all the same), and the row scales there exactly then.
+  if (f.w8 && (a.dim % 64 || a.ffn % 64 || size_t(2) * a.ffn * a.dim >= kOob)) return hipErrorInvalidValue;
+  if ((f.w8 != 0) != (a.gate_up_scale != nullptr) || (f.w8 != 0) != (a.down_scale != nullptr))
+    return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_moe_route, dim3(p.route_grid), dim3(kRouteWaves * 64), 0, s, a);
-  hipLaunchKernelGGL(moe_kernel<false>(p.gu_nw, p.gu_rt, p.gu_um), dim3(p.gu_grid_x, p.gu_grid_y), dim3(p.gu_nw * 64), 0,
+  hipLaunchKernelGGL(moe_kernel<false>(p.gu_nw, p.gu_rt, p.gu_um, f.w8), dim3(p.gu_grid_x, p.gu_grid_y), dim3(p.gu_nw * 64), 0,
                      s, a);
-  hipLaunchKernelGGL(moe_kernel<true>(p.dn_nw, p.dn_rt, p.dn_um), dim3(p.dn_grid_x, p.dn_grid_y), dim3(p.dn_nw * 64), 0,
+  hipLaunchKernelGGL(moe_kernel<true>(p.dn_nw, p.dn_rt, p.dn_um, f.w8), dim3(p.dn_grid_x, p.dn_grid_y), dim3(p.dn_nw * 64), 0,
                      s, a);
   hipLaunchKernelGGL(k_moe_combine, dim3(p.cb_grid), dim3(kCombineWaves * 64), 0, s, a, log2_exact(p.cb_cols));
   return hipGetLastError();

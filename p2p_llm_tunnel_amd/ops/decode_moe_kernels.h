@@ -119,7 +119,17 @@ __device__ __forceinline__ int moe_pairs(const MoeArgs& a, int e, uint16_t* pair
 // SwiGLU, bf16 to moe_h[p]) and k_moe_down (A rows from moe_h by the pair, N = dim, K = ffn_e, epilogue fp32
 // route_w[p] * y to moe_part[p]). NW waves split K and are summed through LDS in wave order; wave 0 runs the
 // epilogue. C layout as k_skinny: pair 16 t + 4 (lane >> 4) + r of the pass, column lane & 15 of the tile.
-template <int NW, int RT, int UM, bool DOWN>
+//
+// W8 = 1 (docs/MOE_FP8.md): the expert's weights are e4m3 bytes with an fp32 scale per output row, and every row is
+// stored in k-step pairs: inside a 64-byte block, the 16 bytes of lane group g = lane >> 4 are its 8 k-values of the
+// even k-step, then its 8 of the odd one. One 16-byte load per lane therefore feeds two k-steps (where the natural
+// order allows 8-byte loads only), its halves decoded to two bf16 B fragments (e4m3x8_to_bf16x8: exact) just ahead of
+// their MFMAs, which run in k-step order on the same accumulators, so the MFMA sequence of a K range is the bf16
+// kernel's. The unit of everything that splits K is the pair: the waves' K ranges (whole pairs; they are the bf16
+// kernel's ranges exactly when NW divides K / 64) and the load batch, max(UM / 2, 1) pairs, i.e. UM k-steps in flight
+// as in the bf16 kernel but never fewer than 2. The row scale is no part of the K loop: wave 0 loads its column's
+// scale ahead of the stream and multiplies the reduced accumulator once, before the pair factor.
+template <int NW, int RT, int UM, bool DOWN, int W8 = 0>
 __device__ __forceinline__ void moe_gemm(const MoeArgs& a) {
   __shared__ float red[NW][RT][4][kWave];
   __shared__ uint16_t pairs[kMaxPairs];
@@ -127,17 +137,25 @@ __device__ __forceinline__ void moe_gemm(const MoeArgs& a) {
   const int lane = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int bx = blockIdx.x, e = blockIdx.y;
   const int count = moe_pairs(a, e, pairs, &cnt);
-  if (count == 0) return;  // no pair: no weight byte is read
+  if (count == 0) return;  // no pair: no weight or scale byte is read
   const int K = DOWN ? a.ffn : a.dim, N = DOWN ? a.dim : 2 * a.ffn;
-  const int S = K >> 5, s0 = wv * S / NW, s1 = (wv + 1) * S / NW;
+  // k-steps of 32 (bf16), or pairs of them (W8: K is a multiple of 64, the host's check).
+  const int S = K >> (W8 ? 6 : 5), s0 = wv * S / NW, s1 = (wv + 1) * S / NW;
   const int kq = (lane >> 4) << 3, c = lane & 15, lrow0 = (lane >> 4) << 2;
   const __amdgpu_buffer_rsrc_t ra =
       rsrc(DOWN ? a.moe_h : a.resid, uint32_t(DOWN ? a.B * a.top_k : a.B) * uint32_t(K) * 2u);
   // This expert's slice of the stack: the descriptor's base and size are the slice's.
-  const uint16_t* we = (DOWN ? a.w_down : a.w_gate_up) + size_t(e) * size_t(N) * size_t(K);
-  const __amdgpu_buffer_rsrc_t rw = rsrc(we, uint32_t(N) * uint32_t(K) * 2u);
+  constexpr uint32_t kWb = W8 ? 1u : 2u;  // bytes per weight element
+  const uint8_t* we =
+      static_cast<const uint8_t*>(DOWN ? a.w_down : a.w_gate_up) + size_t(e) * size_t(N) * size_t(K) * kWb;
+  const __amdgpu_buffer_rsrc_t rw = rsrc(we, uint32_t(N) * uint32_t(K) * kWb);
   const int col = bx * 16 + c;
-  const uint32_t woff = (uint32_t(col) * uint32_t(K) + uint32_t(kq)) * 2u;
+  // bf16: the lane's 8 k-values of a k-step, 16 bytes. W8: its 16 bytes of a pair, at 16 g inside the 64-byte block.
+  const uint32_t woff = W8 ? uint32_t(col) * uint32_t(K) + uint32_t(kq) * 2u
+                           : (uint32_t(col) * uint32_t(K) + uint32_t(kq)) * 2u;
+  float wscale = 0.f;  // W8: the column's row scale, wave 0's, ahead of the weight stream like sc below
+  if constexpr (W8 != 0)
+    if (wv == 0) wscale = (DOWN ? a.down_scale : a.gate_up_scale)[size_t(e) * size_t(N) + size_t(col)];
   const int tiles = (count + 15) >> 4;  // <= RT: the host's choice of RT for B rows
   uint32_t xoff[RT];
 #pragma unroll
@@ -162,6 +180,34 @@ __device__ __forceinline__ void moe_gemm(const MoeArgs& a) {
   frag4 acc[RT];
 #pragma unroll
   for (int t = 0; t < RT; t++) acc[t] = frag4{0.f, 0.f, 0.f, 0.f};
+  if constexpr (W8 != 0) {
+    constexpr int UP = UM >= 2 ? UM / 2 : 1;  // pairs per load batch: UM k-steps in flight, 2 at least
+    for (int s = s0; s < s1; s += UP) {
+      uint4 bq[UP], af[UP][2][RT];
+#pragma unroll
+      for (int u = 0; u < UP; u++) {
+        const bool in = s + u < s1;
+        const uint32_t su = uint32_t(s + u) * 128u;  // A bytes of a pair: two k-steps of 32 bf16
+        bq[u] = buf_ld16(rw, in ? woff + (su >> 1) : kOob);
+#pragma unroll
+        for (int t = 0; t < RT; t++) {
+          af[u][0][t] = buf_ld16(ra, in ? xoff[t] + su : kOob);
+          af[u][1][t] = buf_ld16(ra, in ? xoff[t] + su + 64u : kOob);
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int u = 0; u < UP; u++)
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+          const uint4 b = e4m3x8_to_bf16x8(h ? make_uint2(bq[u].z, bq[u].w) : make_uint2(bq[u].x, bq[u].y));
+#pragma unroll
+          for (int t = 0; t < RT; t++)
+            if (t == 0 || t < tiles)
+              acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(af[u][h][t]), as_frag(b), acc[t], 0, 0, 0);
+        }
+    }
+  } else
   for (int s = s0; s < s1; s += UM) {
     uint4 bf[UM], af[UM][RT];
 #pragma unroll
@@ -193,6 +239,7 @@ __device__ __forceinline__ void moe_gemm(const MoeArgs& a) {
         float v = 0.f;
 #pragma unroll
         for (int w = 0; w < NW; w++) v += red[w][t][r][lane];
+        if constexpr (W8 != 0) v *= wscale;  // once, on the reduced sum, before the pair factor
         const int p = pr[t][r];
         if constexpr (DOWN) {
           if (p >= 0) a.moe_part[size_t(p) * a.dim + col] = sc[t][r] * v;
@@ -207,13 +254,13 @@ __device__ __forceinline__ void moe_gemm(const MoeArgs& a) {
   }
 }
 
-template <int NW, int RT, int UM>
+template <int NW, int RT, int UM, int W8 = 0>
 __global__ __launch_bounds__(NW * 64) void k_moe_gate_up(MoeArgs a) {
-  moe_gemm<NW, RT, UM, false>(a);
+  moe_gemm<NW, RT, UM, false, W8>(a);
 }
-template <int NW, int RT, int UM>
+template <int NW, int RT, int UM, int W8 = 0>
 __global__ __launch_bounds__(NW * 64) void k_moe_down(MoeArgs a) {
-  moe_gemm<NW, RT, UM, true>(a);
+  moe_gemm<NW, RT, UM, true, W8>(a);
 }
 
 // resid[b] = bf16(resid[b] + (part[b][0] + ... + part[b][top_k - 1])), the sum fp32 in j order, and the new row's
