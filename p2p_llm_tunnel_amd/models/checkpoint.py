@@ -246,9 +246,10 @@ def load_llama(path: str, device="cuda", max_batch: int = 8, max_seq: int | None
     (docs/WEIGHT_FP8.md) or "mxfp4" (docs/WEIGHT_MXFP4.md: the layers' GEMM weights as MXFP4, the LM head as FP8): each
     layer's GEMM weights are quantised on ``device`` as soon as the layer is read and its bf16 tensors dropped, so
     the device never holds the bf16 and the quantised copies of all layers together. The checkpoint itself is bf16 / fp16
-    / fp32 either way: one that is already quantised on disk is treated as before. ``expert_dtype``: "bf16" or "fp8"
+    / fp32 either way: one that is already quantised on disk is treated as before. ``expert_dtype``: "bf16", "fp8"
     (docs/MOE_FP8.md; MoE checkpoints only): the stacked experts as e4m3 bytes with per-row scales, each layer's stack
-    quantised as soon as it is read (``quantize_experts_``), every other weight bf16. ``chunk_attn``: ``TinyLlama``'s
+    quantised as soon as it is read (``quantize_experts_``), every other weight bf16; or "mxfp4" (docs/MOE_MXFP4.md):
+    the stacks as MXFP4 nibble bytes with e8m0 block scales, quantised layer by layer in the same place. ``chunk_attn``: ``TinyLlama``'s
     (docs/CHUNK_ATTN.md). ``sliding_window``: serve the
     checkpoint's sliding attention window (``read_config``, docs/SLIDING_WINDOW.md), fused step only; a checkpoint
     that declares none is refused."""
@@ -269,7 +270,7 @@ def load_llama(path: str, device="cuda", max_batch: int = 8, max_seq: int | None
     from p2p_llm_tunnel_amd import ops
     ops.as_expert_format(expert_dtype, cfg.moe, cfg.dim, cfg.ffn)  # a dense checkpoint, or shapes that do not block
     if expert_dtype != "bf16" and not fused:
-        raise ValueError("FP8 experts run the fused step only: load with fused=True")
+        raise ValueError(f"{expert_dtype.upper()} experts run the fused step only: load with fused=True")
     c = cfg
     rd = _Reader(path)
     dev = torch.device(device)
@@ -361,6 +362,9 @@ def load_llama(path: str, device="cuda", max_batch: int = 8, max_seq: int | None
             if expert_dtype == "fp8":  # likewise this layer's expert stacks
                 quantize_experts_(c, w["layers"][-1])
                 check_expert_scales(w["layers"][-1], i)
+                del gate_up, down
+            if expert_dtype == "mxfp4":
+                quantize_experts_(c, w["layers"][-1], "mxfp4")
                 del gate_up, down
     finally:
         rd.close()

@@ -434,7 +434,8 @@ class Engine:
 
     ``expert_dtype`` ("bf16" by default, and then nothing above changes; docs/MOE_FP8.md):
     "fp8" builds an MoE model with FP8 expert matrices, which only the
-    graph-captured HIP step multiplies. The number of graphs is what it is without.
+    graph-captured HIP step multiplies; "mxfp4" one with MXFP4 expert matrices (docs/MOE_MXFP4.md), likewise. The
+    number of graphs is what it is without.
     """
 
     def __init__(self, device="cuda:0", config="tiny", max_batch=8, seed=0, use_graph=True, rows=64, model=None,
@@ -487,7 +488,8 @@ class Engine:
         for on, what in ((penalties, "penalties need"), (fp8, "an fp8 KV cache needs"), (w8, f"{getattr(model, 'weight_dtype', 'bf16')} weights need"),
                          (guided, "guided decoding needs"), (windowed, "a sliding window needs"),
                          (min_p, "min_p needs"), (getattr(model, "chunk_attn", False), "chunk_attn needs"),
-                         (getattr(model, "expert_dtype", "bf16") != "bf16", "fp8 experts need"),
+                         (getattr(model, "expert_dtype", "bf16") != "bf16",
+                          f"{getattr(model, 'expert_dtype', 'bf16')} experts need"),
                          (bool(getattr(getattr(model, "cfg", None), "n_experts", 0)), "an MoE model needs")):
             if on and not use_graph:
                 raise ValueError(f"{what} the graph-captured HIP step; this engine runs eagerly")

@@ -810,8 +810,9 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
     engine must have been built with it.
     ``chunk_attn`` is ``Engine``'s and ``load_llama``'s (docs/CHUNK_ATTN.md): steps of more than 16 rows attend with
     ``k_attn_chunk``; an injected engine's model must have been built with it.
-    ``expert_dtype`` ("bf16" or "fp8": docs/MOE_FP8.md) is ``Engine``'s and ``load_llama``'s: the format of an MoE
-    model's stacked expert matrices alone; a dense model refuses "fp8", and an injected engine's model must have it."""
+    ``expert_dtype`` ("bf16", "fp8": docs/MOE_FP8.md, or "mxfp4": docs/MOE_MXFP4.md) is ``Engine``'s and
+    ``load_llama``'s: the format of an MoE model's stacked expert matrices alone; a dense model refuses "fp8" and
+    "mxfp4", and an injected engine's model must have it."""
     expert_dtype = parse_expert_dtype(expert_dtype)
     if engine is not None and getattr(engine.model, "expert_dtype", "bf16") != expert_dtype:
         raise ValueError(f"expert_dtype={expert_dtype!r}, but the injected engine's model has "
@@ -886,11 +887,12 @@ def parse_weight_dtype(v) -> str:
     return v
 
 
-EXPERT_DTYPE_CHOICES = ("bf16", "fp8")
+EXPERT_DTYPE_CHOICES = ("bf16", "fp8", "mxfp4")
 
 
 def parse_expert_dtype(v) -> str:
-    """--expert-dtype / ``start_server(expert_dtype=)``: "bf16" (the default) or "fp8"; anything else is refused."""
+    """--expert-dtype / ``start_server(expert_dtype=)``: "bf16" (the default), "fp8" or "mxfp4"; anything else is
+    refused."""
     if v not in EXPERT_DTYPE_CHOICES:
         raise ValueError(f"expert_dtype must be one of {list(EXPERT_DTYPE_CHOICES)}, got {v!r}")
     return v
@@ -909,10 +911,15 @@ def weights_line(model, weight_dtype: str) -> str:
         fp8 = getattr(model, "expert_dtype", "bf16") == "fp8"
         if fp8:  # a byte per weight and an fp32 scale per output row
             expert = (2 * c.ffn * c.dim + c.dim * c.ffn) + (2 * c.ffn + c.dim) * 4
+        mxfp4 = getattr(model, "expert_dtype", "bf16") == "mxfp4"
+        if mxfp4:  # a nibble per weight and an e8m0 byte per block of 32
+            expert = (2 * c.ffn * c.dim + c.dim * c.ffn) // 2 + (2 * c.ffn * c.dim + c.dim * c.ffn) // 32
         active = b["gemm"] - c.n_layers * (c.n_experts - c.top_k) * expert
         line += f"; MoE: {c.n_experts} experts, top-{c.top_k}, {active} GEMM bytes active per token"
         if fp8:
             line += f"; fp8 experts {c.n_layers * c.n_experts * expert} bytes with their row scales"
+        if mxfp4:
+            line += f"; mxfp4 experts {c.n_layers * c.n_experts * expert} bytes with their block scales"
     return line
 
 
@@ -1061,8 +1068,10 @@ def arg_parser() -> argparse.ArgumentParser:
                     help="format of an MoE model's stacked expert matrices (Mixtral checkpoints, tiny-moe): bf16, or "
                          "fp8 (OCP e4m3 with one fp32 scale per expert and output row, per-row absmax, nothing "
                          "calibrated; activations, router, attention projections and LM head stay bf16): half the "
-                         "expert bytes in memory and per step. A dense model refuses it, and --weight-dtype stays "
-                         "bf16 on an MoE model (docs/MOE_FP8.md)")
+                         "expert bytes in memory and per step; or mxfp4 (OCP Microscaling FP4: e2m1 values in blocks "
+                         "of 32 with a power-of-two scale, round to nearest, nothing calibrated): about 0.27 of the "
+                         "bf16 expert bytes. A dense model refuses both, and --weight-dtype stays "
+                         "bf16 on an MoE model (docs/MOE_FP8.md, docs/MOE_MXFP4.md)")
     ap.add_argument("--sliding-window", action="store_true",
                     help="serve the checkpoint's sliding attention window (Mistral-7B-v0.1 and its fine-tunes; Qwen2 / "
                          "Qwen3 with use_sliding_window) instead of capping the context at it: the layers that slide "

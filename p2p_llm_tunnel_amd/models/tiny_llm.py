@@ -101,7 +101,8 @@ CONFIGS = {
 KV_DTYPES = {"bf16": torch.bfloat16, "fp8": torch.float8_e4m3fn}  # TinyLlama(kv_dtype=): the caches' dtype
 # TinyLlama(weight_dtype=): the format of the GEMM weights. "mxfp4": a layer's four as MXFP4, the LM head as FP8.
 WEIGHT_DTYPES = ("bf16", "fp8", "mxfp4")
-# TinyLlama(expert_dtype=): the format of an MoE model's stacked expert matrices alone (docs/MOE_FP8.md).
+# TinyLlama(expert_dtype=): the format of an MoE model's stacked expert matrices alone (docs/MOE_FP8.md,
+# docs/MOE_MXFP4.md).
 EXPERT_DTYPES = tuple(ops.EXPERT_FORMATS)
 EXPERT_WEIGHTS = ("w_gate_up", "w_down")  # the stacked expert matrices of an MoE layer
 GEMM_WEIGHTS = ops.LAYER_GEMMS  # a layer's GEMM weights, in the order of their scales
@@ -161,16 +162,30 @@ def quantize_layer_(cfg: "LlamaConfig", L: dict, weight_dtype: str = "fp8") -> d
     return L
 
 
-def quantize_experts_(cfg: "LlamaConfig", L: dict) -> dict:
+def quantize_experts_(cfg: "LlamaConfig", L: dict, expert_dtype: str = "fp8") -> dict:
     """One MoE layer's stacked experts to FP8 in place (docs/MOE_FP8.md): ``L["w_gate_up"]`` and ``L["w_down"]`` (bf16
     ``[E, N, K]``) give way to ``L[name + "_q"]`` (e4m3 ``[E, N, K]``, folded and interleaved as the fused table wants
     it, natural K order) and ``L[name + "_s"]`` (fp32 ``[E, N]``), by ``ops.quantize_weight_fp8`` expert by expert: per
     row absmax / 448, in fp32 after the fold and the interleave. The loader calls it layer by layer, as it does
-    ``quantize_layer_``, so the bf16 and FP8 stacks of all layers are never resident together."""
+    ``quantize_layer_``, so the bf16 and FP8 stacks of all layers are never resident together.
+
+    ``expert_dtype`` "mxfp4" (docs/MOE_MXFP4.md): to MXFP4 instead, by ``ops.quantize_weight_mxfp4`` on the same folded,
+    interleaved fp32 rows: ``L[name + "_q"]`` (uint8 nibble bytes ``[E, N, K / 2]``, natural order) and
+    ``L[name + "_e"]`` (uint8 e8m0 ``[E, N, K / 32]``)."""
     for name in EXPERT_WEIGHTS:
         if name + "_q" in L:
             continue
         w = L.pop(name)
+        if expert_dtype == "mxfp4":
+            E, N, K = w.shape
+            q = torch.empty((E, N, K // 2), dtype=torch.uint8, device=w.device)
+            ex = torch.empty((E, N, K // ops.MXFP4_BLOCK), dtype=torch.uint8, device=w.device)
+            g, perm = L.get(FOLDED_NORM.get(name)), fused_row_perm(cfg, name, w.device)
+            for e in range(E):
+                q[e], ex[e] = quantize_gemm_weight(w[e], g, perm, "mxfp4")
+            L[name + "_q"], L[name + "_e"] = q, ex
+            del w
+            continue
         q = torch.empty(w.shape, dtype=torch.float8_e4m3fn, device=w.device)
         sc = torch.empty(w.shape[:2], dtype=torch.float32, device=w.device)
         g, perm = L.get(FOLDED_NORM.get(name)), fused_row_perm(cfg, name, w.device)
@@ -232,7 +247,11 @@ class TinyLlama:
                  fused: bool = True, weights: dict | None = None, kv_dtype: str = "bf16",
                  weight_dtype: str = "bf16", kv_scales: KvScales | None = None, chunk_attn: bool = False,
                  expert_dtype: str = "bf16"):
-        """``expert_dtype`` ("bf16", the default, or "fp8"; MoE models and the fused step only; docs/MOE_FP8.md): the
+        """``expert_dtype`` ("bf16", the default, "fp8" or "mxfp4"; MoE models and the fused step only;
+        docs/MOE_FP8.md, docs/MOE_MXFP4.md). "mxfp4": the stacked expert matrices as OCP MXFP4 (e2m1 nibbles in blocks
+        of 32 with an e8m0 scale, round to nearest, nothing calibrated), quantised here layer by layer, or brought by
+        ``weights`` as ``w_gate_up_q`` / ``w_gate_up_e`` / ``w_down_q`` / ``w_down_e`` (uint8 ``[E, N, K / 2]`` and
+        ``[E, N, K / 32]`` in natural order and the fused table's row order). "fp8": the
         stacked expert matrices as e4m3 bytes with one fp32 scale per (expert, output row), per-row absmax, nothing
         calibrated; quantised here layer by layer, or brought by ``weights`` as ``w_gate_up_q`` / ``w_gate_up_s`` /
         ``w_down_q`` / ``w_down_s`` (e4m3 or uint8 ``[E, N, K]`` in natural K order and the fused table's row order,
@@ -277,8 +296,8 @@ class TinyLlama:
         self.expert_dtype = expert_dtype
         ops.as_expert_format(expert_dtype, self.cfg.moe, self.cfg.dim, self.cfg.ffn)  # dense, or no multiple of 64
         if expert_dtype != "bf16" and not fused:
-            raise ValueError("FP8 experts run the fused step only (fused=True): the unfused path has no "
-                             "routed-expert kernels")
+            raise ValueError(f"{expert_dtype.upper()} experts run the fused step only (fused=True): the unfused path "
+                             "has no routed-expert kernels")
         if self.cfg.n_experts and weight_dtype != "bf16":
             raise ValueError(f"an MoE model's expert weights are bf16 only: weight_dtype {weight_dtype!r} is not "
                              "supported with a routed-expert FFN")
@@ -291,7 +310,7 @@ class TinyLlama:
             raise ValueError("chunk_attn runs the fused step only (fused=True): the unfused path has no chunk "
                              "attention kernel")
         self.chunk_attn = chunk_attn
-        self._experts_blocked = False  # FP8 experts: fused_weights() has put their bytes into the device order
+        self._experts_blocked = False  # FP8 / MXFP4 experts: fused_weights() has put their bytes into the device order
         self.lm_head_q = self.lm_head_s = None  # weight_dtype "fp8": the LM head's bytes and row scales
         self.fused = fused
         self._fused = None
@@ -319,7 +338,17 @@ class TinyLlama:
                         "w_down": (c.n_experts, c.dim, c.ffn)}
                 for i, L in enumerate(self.layers):
                     for n, shape in want.items():
-                        if n + "_q" in L:  # experts that are FP8 already
+                        if n + "_e" in L or (n + "_q" in L and expert_dtype == "mxfp4"):  # MXFP4 already
+                            q, ex = L.get(n + "_q"), L.get(n + "_e")
+                            if expert_dtype != "mxfp4":
+                                raise ValueError(f"layer {i}: the weights hold MXFP4 experts: pass "
+                                                 "expert_dtype='mxfp4'")
+                            qs, es = shape[:2] + (shape[2] // 2,), shape[:2] + (shape[2] // ops.MXFP4_BLOCK,)
+                            if q is None or ex is None or q.dtype != torch.uint8 or ex.dtype != torch.uint8 or \
+                                    tuple(q.shape) != qs or tuple(ex.shape) != es:
+                                raise ValueError(f"layer {i}: MXFP4 experts need {n}_q, uint8 nibble bytes of shape "
+                                                 f"{qs}, and {n}_e, uint8 e8m0 bytes of shape {es}")
+                        elif n + "_q" in L:  # experts that are FP8 already
                             q, sc = L[n + "_q"], L.get(n + "_s")
                             if expert_dtype != "fp8":
                                 raise ValueError(f"layer {i}: the weights hold FP8 experts: pass expert_dtype='fp8'")
@@ -375,6 +404,8 @@ class TinyLlama:
     def _quantize_weights(self):
         """``weight_dtype`` "fp8": every layer's GEMM weights and the LM head to e4m3 + row scales, one tensor at
         a time. The bf16 LM head is dropped unless it is the embedding itself (a tied model)."""
+        if self.expert_dtype == "mxfp4":  # likewise; an e8m0 byte is valid whatever it holds, so nothing to check
+            self.layers = [quantize_experts_(self.cfg, dict(L), "mxfp4") for L in self.layers]
         if self.expert_dtype == "fp8":  # the experts alone, a layer at a time; every other weight stays bf16
             self.layers = [quantize_experts_(self.cfg, dict(L)) for L in self.layers]
             for i, L in enumerate(self.layers):
@@ -394,8 +425,13 @@ class TinyLlama:
     def expert_weight(self, name: str, layer: int) -> torch.Tensor:
         """An MoE layer's stacked ``name`` ("w_gate_up" or "w_down") in fp32 as the kernels compute with it, in the
         fused table's row order and natural K order: with FP8 experts the dequantised ``q * s`` (the FFN norm folded
-        in), else the bf16 tensor folded and interleaved the same way."""
+        in), with MXFP4 experts ``ops.dequantize_weight_mxfp4`` of every expert, else the bf16 tensor folded and
+        interleaved the same way."""
         L = self.layers[layer]
+        if self.expert_dtype == "mxfp4":
+            q = L[name + "_q"]
+            q = ops.unblock_expert_mxfp4(q) if self._experts_blocked else q
+            return torch.stack([ops.dequantize_weight_mxfp4(q[e], L[name + "_e"][e]) for e in range(q.shape[0])])
         if self.expert_dtype == "fp8":
             q = L[name + "_q"]
             q = ops.unblock_expert_fp8(q) if self._experts_blocked else q
@@ -516,17 +552,18 @@ class TinyLlama:
 
         # FP8 experts go into the kernels' k-step-pair order here (ops.block_expert_fp8), a layer at a time and in
         # place of the natural-order bytes, so a second copy of the stacks never stays resident.
-        if self.expert_dtype == "fp8" and not self._experts_blocked:
+        if self.expert_dtype != "bf16" and not self._experts_blocked:
+            block = ops.block_expert_mxfp4 if self.expert_dtype == "mxfp4" else ops.block_expert_fp8
             for L in self.layers:
                 for n in EXPERT_WEIGHTS:
-                    L[n + "_q"] = ops.block_expert_fp8(L[n + "_q"])
+                    L[n + "_q"] = block(L[n + "_q"])
             self._experts_blocked = True
 
         def entry(name, layer):
             src = top if layer is None else self.layers[layer]
             if name.endswith(" scale"):
-                return src[name[:-len(" scale")] + "_s"]
-            if self.expert_dtype == "fp8" and name in EXPERT_WEIGHTS:
+                return src[name[:-len(" scale")] + ("_e" if self.expert_dtype == "mxfp4" else "_s")]
+            if self.expert_dtype != "bf16" and name in EXPERT_WEIGHTS:
                 return src[name + "_q"]
             if fp8 and (name in GEMM_WEIGHTS or name == "lm_head"):
                 return src[name + "_q"]
@@ -540,7 +577,8 @@ class TinyLlama:
 
         return [entry(e.name, e.layer)
                 for e in ops.WeightTable(self.dims(), weight_format=self.weight_dtype, moe=c.moe,
-                                         **({"expert_format": "fp8"} if self.expert_dtype == "fp8" else {}))]
+                                         **({"expert_format": self.expert_dtype} if self.expert_dtype != "bf16"
+                                            else {}))]
 
     def dims(self) -> ops.LlamaDims:
         """The fused step's dims of this model: one cache slot per sequence and the scratch slot."""
@@ -555,7 +593,8 @@ class TinyLlama:
                                                 windows=self.cfg.windows if self.cfg.windowed else None,
                                                 **({"chunk_attn": True} if self.chunk_attn else {}),
                                                 **({"moe": self.cfg.moe} if self.cfg.n_experts else {}),
-                                                **({"expert_format": "fp8"} if self.expert_dtype == "fp8" else {}))
+                                                **({"expert_format": self.expert_dtype}
+                                                   if self.expert_dtype != "bf16" else {}))
         return self._fused
 
     def step_rows(self, tokens, pos, slots=None, emit_rows=0, pos_range=None):
@@ -759,7 +798,7 @@ class TinyLlama:
                 tw, ti = probs.topk(c.top_k, dim=-1)
                 if c.norm_topk:
                     tw = tw / tw.sum(-1, keepdim=True)
-                if self.expert_dtype == "fp8":  # the dequantised experts: the norm is in them, the rows interleaved
+                if self.expert_dtype != "bf16":  # the dequantised experts: the norm is in them, the rows interleaved
                     gu = bf(torch.einsum("btk,enk->bten", bf(rms(residual, torch.ones_like(L["ffn_norm"]))),
                                          self.expert_weight("w_gate_up", i)))
                     gu = torch.cat([gu[..., 0::2], gu[..., 1::2]], -1)

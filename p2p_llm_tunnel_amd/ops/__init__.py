@@ -141,21 +141,23 @@ MAX_EXPERTS, MAX_TOP_K = 128, 8  # decode_moe.h's kMaxExperts and kMaxTopK
 class ExpertFormat(ctypes.Structure):
     """Mirror of ``ExpertFormat`` (decode_moe.h): the format of an MoE model's stacked expert matrices, beside
     ``MoeDims`` as ``WeightFormat`` is beside the plans (docs/MOE_FP8.md). ``w8``: 0 bf16; 1 OCP e4m3fn bytes in
-    k-step-pair order (``block_expert_fp8``) with one fp32 scale per (expert, output row)."""
+    k-step-pair order (``block_expert_fp8``) with one fp32 scale per (expert, output row); 2 OCP MXFP4 nibble bytes in
+    k-step-quad order (``block_expert_mxfp4``) with one e8m0 byte per 32-element block (docs/MOE_MXFP4.md)."""
     _fields_ = [("w8", _INT)]
 
     def __repr__(self):
         return f"ExpertFormat(w8={self.w8})"
 
 
-EXPERT_FORMATS = {"bf16": 0, "fp8": 1}  # expert dtype -> ExpertFormat.w8
+EXPERT_FORMATS = {"bf16": 0, "fp8": 1, "mxfp4": 2}  # expert dtype -> ExpertFormat.w8
 EXPERT_BLOCK = 64  # K elements per block of the FP8 experts' byte order: a pair of k-steps
+EXPERT_QUAD = 128  # K elements per block of the MXFP4 experts' byte order: a quad of k-steps, 64 nibble bytes
 
 
 def as_expert_format(expert_format=None, moe=None, dim: int = 0, ffn: int = 0) -> ExpertFormat:
-    """The ``ExpertFormat`` a caller means: None or "bf16", "fp8", or an ``ExpertFormat`` of w8 0 or 1. FP8 experts
-    need a routed-expert FFN (``moe``) whose ``dim`` and per-expert ``ffn`` are multiples of 64: every refusal says
-    why (host only: no library)."""
+    """The ``ExpertFormat`` a caller means: None or "bf16", "fp8", "mxfp4", or an ``ExpertFormat`` of w8 0, 1 or 2.
+    FP8 experts need a routed-expert FFN (``moe``) whose ``dim`` and per-expert ``ffn`` are multiples of 64, MXFP4
+    experts one whose two are multiples of 128: every refusal says why (host only: no library)."""
     f = expert_format
     if f is None:
         return ExpertFormat(0)
@@ -164,9 +166,16 @@ def as_expert_format(expert_format=None, moe=None, dim: int = 0, ffn: int = 0) -
             raise ValueError(f"expert_dtype must be one of {sorted(EXPERT_FORMATS)}, got {f!r}")
         f = ExpertFormat(EXPERT_FORMATS[f])
     if not isinstance(f, ExpertFormat) or f.w8 not in EXPERT_FORMATS.values():
-        raise ValueError(f"expert_format must be an ExpertFormat of w8 0 or 1 or one of {sorted(EXPERT_FORMATS)}, "
+        raise ValueError(f"expert_format must be an ExpertFormat of w8 0, 1 or 2 or one of {sorted(EXPERT_FORMATS)}, "
                          f"got {expert_format!r}")
-    if f.w8:
+    if f.w8 == 2:
+        if moe is None:
+            raise ValueError("expert_dtype mxfp4 needs a routed-expert FFN: a dense model has no experts "
+                             "(its GEMM weights follow weight_dtype)")
+        if dim % EXPERT_QUAD or ffn % EXPERT_QUAD:
+            raise ValueError(f"MXFP4 experts are stored in blocks of {EXPERT_QUAD} (quads of k-steps): dim and the "
+                             f"per-expert ffn must be multiples of {EXPERT_QUAD}, got dim {dim}, ffn {ffn}")
+    elif f.w8:
         if moe is None:
             raise ValueError("expert_dtype fp8 needs a routed-expert FFN: a dense model has no experts "
                              "(its GEMM weights follow weight_dtype)")
@@ -206,6 +215,41 @@ def unblock_expert_fp8(q: torch.Tensor) -> torch.Tensor:
     out = torch.empty_like(q.view(torch.uint8))
     out[..., _expert_perm(q.shape[2], q.device)] = q.view(torch.uint8)
     return out.view(q.dtype)
+
+
+def _expert_perm_mxfp4(Kb: int, device=None) -> torch.Tensor:
+    """``perm[i]``: the natural byte of byte i of a row of ``Kb`` nibble bytes in k-step-quad order."""
+    i = torch.arange(Kb, device=device)
+    j = i % (EXPERT_QUAD // 2)
+    g, h, b = j // 16, (j % 16) // 4, j % 4
+    return i - j + 16 * h + 4 * g + b
+
+
+def _check_expert_nibbles(packed, what: str):
+    if not isinstance(packed, torch.Tensor) or packed.dtype != torch.uint8 or packed.dim() != 3:
+        raise TypeError(f"{what} takes uint8 nibble bytes [E, N, K / 2]")
+    if packed.shape[2] % (EXPERT_QUAD // 2):
+        raise ValueError(f"K must be a multiple of {EXPERT_QUAD} (a quad of k-steps, {EXPERT_QUAD // 2} nibble bytes), "
+                         f"got {2 * packed.shape[2]}")
+
+
+def block_expert_mxfp4(packed: torch.Tensor) -> torch.Tensor:
+    """MXFP4 expert nibble bytes ``[E, N, K / 2]`` from ``pack_weight_mxfp4``'s natural order to the device order
+    ``k_moe_gate_up`` / ``k_moe_down`` stream (docs/MOE_MXFP4.md): inside every 64-byte block of a row (128 K elements)
+    device byte ``16 g + 4 h + b`` is natural byte ``16 h + 4 g + b``, for lane group g, k-step h of the quad and byte
+    b, each 0..3. The 16 contiguous bytes of lane group g are then its 8 k-values of the quad's four k-steps in
+    order, so one 16-byte load feeds four k-steps. Nibble order inside a byte and the e8m0 scale bytes do not move. A
+    new contiguous tensor; plain torch on ``packed``'s device."""
+    _check_expert_nibbles(packed, "block_expert_mxfp4")
+    return packed[..., _expert_perm_mxfp4(packed.shape[2], packed.device)].contiguous()
+
+
+def unblock_expert_mxfp4(packed: torch.Tensor) -> torch.Tensor:
+    """The inverse of ``block_expert_mxfp4``: device order back to natural order."""
+    _check_expert_nibbles(packed, "unblock_expert_mxfp4")
+    out = torch.empty_like(packed)
+    out[..., _expert_perm_mxfp4(packed.shape[2], packed.device)] = packed
+    return out
 
 
 def check_moe(moe, dim: int, ffn: int) -> "MoeDims | None":
@@ -289,6 +333,7 @@ def _signatures() -> dict:
         "p2pt_llama_decode_experts": [dims, wf, vp, ip, ptr(vp), vp, vp, vp, vp, vp, i, i, vp, sz, vp, vp, vp, i, moe,
                                       ef],
         "p2pt_moe_ffn_experts": [vp, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, f, vp, ef, vp, vp],
+        "p2pt_moe_ffn_mxfp4": [vp, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, f, vp, vp, vp],
         "p2pt_attn_span": [i, i],
         "p2pt_max_rows": [],
         "p2pt_skinny_bench": [vp, vp, vp, i, i, i, i, i, i, vp],  # microbenchmark hooks (scripts/bench_skinny.py)
@@ -495,7 +540,10 @@ class WeightTable(list):
     ``weight_format`` stays bf16 with it; ``expert_format`` (``as_expert_format``; docs/MOE_FP8.md) "fp8" makes
     w_gate_up and w_down e4m3 (or uint8) bytes of the same shapes, 16-byte aligned, rows in ``block_expert_fp8``'s
     order, and appends after every other entry, per layer, their fp32 row scales ``(E, 2 * ffn)`` and ``(E, dim)``,
-    named ``"w_gate_up scale"`` and ``"w_down scale"``. None or "bf16": the bf16 MoE table, unchanged."""
+    named ``"w_gate_up scale"`` and ``"w_down scale"``. "mxfp4" (docs/MOE_MXFP4.md) makes them uint8 nibble bytes
+    ``(E, 2 * ffn, dim / 2)`` and ``(E, dim, ffn / 2)``, 16-byte aligned, rows in ``block_expert_mxfp4``'s order, and the
+    two appended entries their e8m0 bytes ``(E, 2 * ffn, dim / 32)`` and ``(E, dim, ffn / 32)``, uint8, natural order,
+    4-byte aligned. None or "bf16": the bf16 MoE table, unchanged."""
 
     def __init__(self, dims: LlamaDims, weight_fp8: bool = False, weight_format=None, moe: MoeDims | None = None,
                  expert_format=None):
@@ -527,17 +575,23 @@ class WeightTable(list):
             layer["w_gate_up"] = (bf, (moe.n_experts, 2 * d.ffn, d.dim), 2)
             layer["w_down"] = (bf, (moe.n_experts, d.dim, d.ffn), 2)
             layer["router"] = (bf, (moe.n_experts, d.dim), 16)
-            if experts.w8:  # one 16-byte load per lane and k-step pair
+            if experts.w8 == 1:  # one 16-byte load per lane and k-step pair
                 layer["w_gate_up"] = (WEIGHT_FP8_DTYPES, (moe.n_experts, 2 * d.ffn, d.dim), 16)
                 layer["w_down"] = (WEIGHT_FP8_DTYPES, (moe.n_experts, d.dim, d.ffn), 16)
+            if experts.w8 == 2:  # one 16-byte load per lane and k-step quad
+                layer["w_gate_up"] = (u8, (moe.n_experts, 2 * d.ffn, d.dim // 2), 16)
+                layer["w_down"] = (u8, (moe.n_experts, d.dim, d.ffn // 2), 16)
         groups = [(None, top)] + [(L, layer) for L in range(d.n_layers)]
         super().__init__(WeightEntry(n, L, *v) for L, group in groups for n, v in group.items())
         if fmt.lm_head:  # the scales, in the order of their weights: fp32 per row, or MXFP4's e8m0 byte per block
             self += [WeightEntry(n + " scale", L, u8, (shapes[n][0], shapes[n][1] // MXFP4_BLOCK), 1)
                      if L is not None and fmt.layers == 2 else WeightEntry(n + " scale", L, f32, v[1][:1], 4)
                      for L, group in groups for n, v in group.items() if n == "lm_head" or n in LAYER_GEMMS]
-        if experts.w8:  # the experts' row scales, after every other entry
+        if experts.w8 == 1:  # the experts' row scales, after every other entry
             self += [WeightEntry(n + " scale", L, f32, layer[n][1][:2], 4)
+                     for L in range(d.n_layers) for n in ("w_gate_up", "w_down")]
+        if experts.w8 == 2:  # in their place the e8m0 byte of every 32-element block: a 4-byte load per k-step quad
+            self += [WeightEntry(n + " scale", L, u8, layer[n][1][:2] + (layer[n][1][2] // (MXFP4_BLOCK // 2),), 4)
                      for L in range(d.n_layers) for n in ("w_gate_up", "w_down")]
         self.per_layer = len(layer)
         self._at = {(e.name, e.layer): i for i, e in enumerate(self)}
@@ -860,7 +914,8 @@ def moe_ffn_plan(B: int, dim: int, ffn: int, moe: MoeDims) -> MoePlan:
 def moe_ffn(resid: torch.Tensor, ss: torch.Tensor, router: torch.Tensor, w_gate_up: torch.Tensor,
             w_down: torch.Tensor, top_k: int, norm_topk: bool = True, eps: float = 1e-5, out: dict | None = None,
             ss_in: int | None = None, gate_up_scale: torch.Tensor | None = None,
-            down_scale: torch.Tensor | None = None) -> dict:
+            down_scale: torch.Tensor | None = None, gate_up_exp: torch.Tensor | None = None,
+            down_exp: torch.Tensor | None = None) -> dict:
     """One routed-expert FFN layer on caller tensors, with the fused step's four kernels (docs/MOE.md):
     ``resid += sum_j route_w[j] * down_e(SwiGLU(gate_up_e(rmsnorm(resid))))`` over each row's ``top_k`` experts.
 
@@ -876,9 +931,27 @@ def moe_ffn(resid: torch.Tensor, ss: torch.Tensor, router: torch.Tensor, w_gate_
     FP8 experts (docs/MOE_FP8.md): with ``gate_up_scale`` (fp32 [E, 2 * ffn]) and ``down_scale`` (fp32 [E, dim]) both
     given, w_gate_up and w_down are e4m3 (or uint8) bytes of the same shapes in ``block_expert_fp8``'s order, and the
     two GEMMs run their FP8 instantiations; dim and ffn must be multiples of 64. One scale without the other is
-    refused. The router stays bf16."""
+    refused. The router stays bf16.
+
+    MXFP4 experts (docs/MOE_MXFP4.md): with ``gate_up_exp`` (uint8 e8m0 [E, 2 * ffn, dim / 32]) and ``down_exp`` (uint8
+    [E, dim, ffn / 32]) both given, w_gate_up and w_down are uint8 nibble bytes [E, 2 * ffn, dim / 2] and
+    [E, dim, ffn / 2] in ``block_expert_mxfp4``'s order (the scale bytes in natural order), and the two GEMMs run their
+    MXFP4 instantiations; dim and ffn must be multiples of 128. One without the other, or either together with the
+    fp32 scales, is refused."""
     if (gate_up_scale is None) != (down_scale is None):
         raise ValueError("FP8 experts need both gate_up_scale and down_scale; bf16 experts take neither")
+    if (gate_up_exp is None) != (down_exp is None):
+        raise ValueError("MXFP4 experts need both gate_up_exp and down_exp; bf16 and FP8 experts take neither")
+    w4 = gate_up_exp is not None
+    if w4 and gate_up_scale is not None:
+        raise ValueError("MXFP4 experts take no fp32 row scales: pass gate_up_exp and down_exp (e8m0 block scales) or "
+                         "gate_up_scale and down_scale (FP8 experts), not both")
+    for name, t, w in (("gate_up_exp", gate_up_exp, w_gate_up), ("down_exp", down_exp, w_down)):
+        shape = tuple(getattr(w, "shape", ()))  # one e8m0 byte per 32 elements, i.e. 16 nibble bytes (host only)
+        shape = shape[:2] + (shape[2] // 16,) if len(shape) == 3 else shape
+        if w4 and (not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or tuple(t.shape) != shape):
+            raise ValueError(f"{name} must be uint8 {shape}: one e8m0 byte per expert, output row and 32-element block, "
+                             f"got {getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
     w8 = gate_up_scale is not None
     for name, t, w in (("gate_up_scale", gate_up_scale, w_gate_up), ("down_scale", down_scale, w_down)):
         shape = tuple(getattr(w, "shape", ()))[:2]  # one scale per expert and output row (host only: no device yet)
@@ -892,25 +965,35 @@ def moe_ffn(resid: torch.Tensor, ss: torch.Tensor, router: torch.Tensor, w_gate_
         if w8 and (not isinstance(t, torch.Tensor) or t.dtype not in WEIGHT_FP8_DTYPES):
             raise TypeError(f"{name}: with scales the experts are FP8, so it must be torch.float8_e4m3fn (or uint8), "
                             f"got {getattr(t, 'dtype', type(t))}")
-        _check(t, t.dtype if w8 else torch.bfloat16, name, dev)
+        if w4 and (not isinstance(t, torch.Tensor) or t.dtype != torch.uint8):
+            raise TypeError(f"{name}: with e8m0 scales the experts are MXFP4, so it must be nibble bytes (torch.uint8), "
+                            f"got {getattr(t, 'dtype', type(t))}")
+        _check(t, t.dtype if w8 or w4 else torch.bfloat16, name, dev)
     _check(ss, torch.float32, "ss", dev)
     if resid.dim() != 2 or router.dim() != 2:
         raise ValueError("resid must be [B, dim] and router [E, dim]")
     (B, dim), E = resid.shape, router.shape[0]
     if w_down.dim() != 3:
         raise ValueError("w_down must be [E, dim, ffn]")
-    ffn = w_down.shape[2]
+    ffn = w_down.shape[2] * (2 if w4 else 1)
     if not 1 <= B <= MAX_ROWS:
         raise ValueError(f"rows must be 1..{MAX_ROWS}")
     if not _int_in(top_k, 1, MAX_TOP_K + 1):
         raise ValueError(f"top_k must be an int in 1..{MAX_TOP_K}, got {top_k!r}")
     moe = check_moe(MoeDims(E, top_k, int(bool(norm_topk))), dim, ffn)
-    experts = as_expert_format("fp8" if w8 else None, moe, dim, ffn)
+    experts = as_expert_format("fp8" if w8 else "mxfp4" if w4 else None, moe, dim, ffn)
     for name, t in (("gate_up_scale", gate_up_scale), ("down_scale", down_scale)):
         if w8:
             _check(t, torch.float32, name, dev)
-    if router.shape != (E, dim) or w_gate_up.shape != (E, 2 * ffn, dim) or w_down.shape != (E, dim, ffn):
-        raise ValueError(f"expected router [{E}, {dim}], w_gate_up [{E}, {2 * ffn}, {dim}], w_down [{E}, {dim}, {ffn}]")
+    for name, t in (("gate_up_exp", gate_up_exp), ("down_exp", down_exp)):
+        if w4:
+            _check(t, torch.uint8, name, dev)
+            if t.data_ptr() % 4:
+                raise ValueError(f"{name} must be 4-byte aligned")
+    kd = 2 if w4 else 1  # K elements per weight byte or element
+    if router.shape != (E, dim) or w_gate_up.shape != (E, 2 * ffn, dim // kd) or w_down.shape != (E, dim, ffn // kd):
+        raise ValueError(f"expected router [{E}, {dim}], w_gate_up [{E}, {2 * ffn}, {dim // kd}], "
+                         f"w_down [{E}, {dim}, {ffn // kd}]")
     for name, t in (("resid", resid), ("router", router), ("w_gate_up", w_gate_up), ("w_down", w_down)):
         if t.data_ptr() % 16:
             raise ValueError(f"{name} must be 16-byte aligned")
@@ -930,6 +1013,12 @@ def moe_ffn(resid: torch.Tensor, ss: torch.Tensor, router: torch.Tensor, w_gate_
         if tuple(t.shape) != shape:
             raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
         res[name] = t
+    if w4:
+        _ok(lib().p2pt_moe_ffn_mxfp4(_p(resid), _p(ss), ss_in, _p(router), _p(w_gate_up), _p(w_down),
+                                     _p(res["route_id"]), _p(res["route_w"]), _p(res["route_rs"]), _p(res["moe_h"]),
+                                     _p(res["moe_part"]), B, dim, ffn, E, top_k, moe.norm_topk, eps, _stream(resid),
+                                     _p(gate_up_exp), _p(down_exp)), "moe_ffn")
+        return res
     if w8:
         _ok(lib().p2pt_moe_ffn_experts(_p(resid), _p(ss), ss_in, _p(router), _p(w_gate_up), _p(w_down),
                                        _p(res["route_id"]), _p(res["route_w"]), _p(res["route_rs"]), _p(res["moe_h"]),
@@ -1497,7 +1586,9 @@ class FusedLlamaDecoder:
     ``expert_format`` (``as_expert_format``; with ``moe`` only; docs/MOE_FP8.md): "fp8" has the stacked experts as
     e4m3 bytes in ``block_expert_fp8``'s order with fp32 row scales after the table
     (``WeightTable(.., expert_format=)``), run by the FP8 instantiations of ``k_moe_gate_up`` and ``k_moe_down`` on the
-    same plan; everything else of the model stays bf16. None or "bf16": nothing above changes.
+    same plan; "mxfp4" (docs/MOE_MXFP4.md) has them as nibble bytes in ``block_expert_mxfp4``'s order with their e8m0
+    block scales after the table, run by the MXFP4 instantiations; everything else of the model stays bf16. None or
+    "bf16": nothing above changes.
 
     Holds the weight pointer table and a zero-initialised workspace; ``step``
     validates the per-call tensors and launches on the current stream (capturable
@@ -1553,7 +1644,9 @@ class FusedLlamaDecoder:
                              + ("; MoE: w_gate_up and w_down stacked per expert, and router last in every layer"
                                 if self.moe is not None else "")
                              + ("; FP8 experts: then their fp32 row scales, w_gate_up's and w_down's per layer"
-                                if self.expert_format.w8 else ""))
+                                if self.expert_format.w8 == 1 else "")
+                             + ("; MXFP4 experts: then their e8m0 block scales, w_gate_up's and w_down's per layer"
+                                if self.expert_format.w8 == 2 else ""))
         # Every entry's dtype and shape, from the description alone: a refusal here needs no device. A weight shorter
         # than dims says would be read past its end (k_skinny sizes its descriptors from dims, k_embed indexes vocab
         # rows). The norm slots the kernels do not read are held to (dim,) too.
@@ -1563,6 +1656,10 @@ class FusedLlamaDecoder:
                 got = getattr(t, "dtype", type(t))
                 if fmt.layers == 2 and e.dtypes == (torch.uint8,):
                     raise TypeError(f"{name}: the weight format is mxfp4, so "
+                                    + ("the block scales must be e8m0 bytes (torch.uint8)" if e.name.endswith(" scale")
+                                       else "the weight must be nibble bytes (torch.uint8)") + f", got {got}")
+                if self.expert_format.w8 == 2 and e.dtypes == (torch.uint8,):
+                    raise TypeError(f"{name}: the experts are MXFP4, so "
                                     + ("the block scales must be e8m0 bytes (torch.uint8)" if e.name.endswith(" scale")
                                        else "the weight must be nibble bytes (torch.uint8)") + f", got {got}")
                 if len(e.dtypes) > 1 and self.expert_format.w8:
@@ -1580,7 +1677,8 @@ class FusedLlamaDecoder:
                                     f": one e8m0 byte per {MXFP4_BLOCK}-element block" if e.dtypes == (torch.uint8,)
                                     else ": one fp32 scale per expert and output row" if self.expert_format.w8
                                     else ": one fp32 scale per output row")
-                                 + (": two nibbles per byte" if fmt.layers == 2 and e.name in LAYER_GEMMS else ""))
+                                 + (": two nibbles per byte" if e.name in LAYER_GEMMS and e.dtypes == (torch.uint8,) and
+                                    (fmt.layers == 2 or self.expert_format.w8 == 2) else ""))
         L, Bmax, S, Hkv, D = k_cache.shape
         if (L, Bmax, S, Hkv, D) != (dims.n_layers, dims.max_batch, dims.max_seq, dims.Hkv, dims.D):
             raise ValueError("cache shape does not match dims")

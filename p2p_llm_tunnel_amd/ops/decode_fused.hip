@@ -141,10 +141,12 @@ bool chunk_layer(int chunk_attn, int B, const WindowPlan& wn) { return chunk_att
 using p2pt_moe::MoeDims;
 using p2pt_moe::MoePlan;
 using p2pt_moe::ExpertFormat;
-// The experts' format beside MoeDims (docs/MOE_FP8.md): bf16, or FP8 in k-step-pair order, whose rows are whole pairs.
-// nullptr everywhere below is bf16, and then nothing changes.
+// The experts' format beside MoeDims (docs/MOE_FP8.md, docs/MOE_MXFP4.md): bf16, FP8 in k-step-pair order, whose rows
+// are whole pairs, or MXFP4 in k-step-quad order, whose rows are whole quads. nullptr everywhere below is bf16, and
+// then nothing changes.
 bool experts_ok(const LlamaDims& d, const ExpertFormat* f) {
-  return !f || f->w8 == 0 || (f->w8 == 1 && d.dim % 64 == 0 && d.ffn % 64 == 0);
+  return !f || f->w8 == 0 || (f->w8 == 1 && d.dim % 64 == 0 && d.ffn % 64 == 0) ||
+         (f->w8 == 2 && d.dim % 128 == 0 && d.ffn % 128 == 0);
 }
 int expert_w8(const ExpertFormat* f) { return f ? f->w8 : 0; }
 bool moe_ok(const LlamaDims& d, const MoeDims& m) {
@@ -195,6 +197,10 @@ GemmPlan plan_lm_head(const LlamaDims& d, int rows) {
 // FP8 experts (ExpertFormat) run this plan int for int. Their kernels count K in pairs of k-steps, so a load batch um
 // means max(um / 2, 1) pairs: 1 -> 2 k-steps in flight, 2 -> 2, 4 -> 4, the bf16 kernel's registers in flight except
 // at um = 1; and gu_nw / dn_nw waves split K / 64 pairs, so waves past K / 64 (a K of 64 or 128 with 4 waves) stay idle.
+// MXFP4 experts run it int for int too. Their kernels count K in quads of k-steps and a load batch is one quad at every
+// um: 1 -> 4 k-steps in flight, 2 -> 4, 4 -> 4; and gu_nw / dn_nw waves split K / 128 quads, wave wv taking quads
+// [wv (K / 128) / nw, (wv + 1) (K / 128) / nw): the bf16 kernel's K ranges where nw divides K / 128, otherwise some
+// waves get fewer quads or none (a K of 128 or 256 with 4 waves leaves three or two idle).
 MoePlan plan_moe(const LlamaDims& d, const MoeDims& m, int B) {
   MoePlan p{};
   const GemmPlan gu = plan_gemm(EPI_SILU, 1, B, 2 * d.ffn, d.dim), dn = plan_gemm(EPI_RESID, 1, B, d.dim, d.ffn);
@@ -336,6 +342,9 @@ Workspace carve(const LlamaDims& d, uint8_t* base, const MoeDims* moe = nullptr)
 // With FP8 experts (ew8; docs/MOE_FP8.md) w_gate_up and w_down are e4m3 bytes of the same shapes, 16-byte aligned, rows
 // in k-step-pair order, and their fp32 row scales [E][2 ffn_e] and [E][dim] follow every other entry, per layer in that
 // order; scale(R_W_GATE_UP / R_W_DOWN, L) reaches them, and no role is added.
+// With MXFP4 experts (ew8 = 2; docs/MOE_MXFP4.md) w_gate_up and w_down are nibble bytes [E][2 ffn_e][dim / 2] and
+// [E][dim][ffn_e / 2], 16-byte aligned, rows in k-step-quad order, and where the FP8-expert table has the row scales it
+// has their e8m0 bytes [E][2 ffn_e][dim / 32] and [E][dim][ffn_e / 32], 4-byte aligned: expert_exp() reaches them.
 // An MoE table (moe set; bf16 apart from the experts) has one more entry per layer, after every other: router, bf16 [E][dim] with the FFN
 // norm folded in; its w_gate_up is [E][2 ffn_e][dim], folded and pair-interleaved per expert, and its w_down
 // [E][dim][ffn_e]. R_ROUTER follows R_NROLES so that p2pt_llama_weight_layout's 13 roles per layer stay what they are.
@@ -346,7 +355,7 @@ struct WeightTable {
   WeightFormat f;
   const void* const* w;
   int moe = 0;  // the layers carry a router
-  int ew8 = 0;  // the experts are FP8 (moe only): two scale entries per layer after the table
+  int ew8 = 0;  // ExpertFormat::w8 (moe only): FP8 or MXFP4 experts have two scale entries per layer after the table
   int per_layer() const { return (d.qk_norm ? 8 : d.qkv_bias ? 7 : 6) + moe; }
   int scales0() const { return 3 + d.rope_table + per_layer() * d.n_layers; }
   int size() const { return scales0() + (f.lm_head ? 1 + 4 * d.n_layers : 0) + (ew8 ? 2 * d.n_layers : 0); }
@@ -374,6 +383,9 @@ struct WeightTable {
   }
   const void* get(Role r, int L = 0) const { return at(index(r, L)); }  // nullptr where the table has none
   const void* scale(Role r, int L = 0) const { return at(scale_index(r, L)); }
+  // The experts' scales by their type: fp32 row scales (FP8 experts) or e8m0 block scales (MXFP4 experts), else nullptr.
+  const float* expert_scale(Role r, int L) const { return ew8 == 1 ? static_cast<const float*>(scale(r, L)) : nullptr; }
+  const uint8_t* expert_exp(Role r, int L) const { return ew8 == 2 ? static_cast<const uint8_t*>(scale(r, L)) : nullptr; }
   const void* at(int i) const { return i < 0 ? nullptr : w[i]; }
 };
 
@@ -674,7 +686,8 @@ int p2pt_llama_kv_plan(const LlamaDims* d, KvPlan* out) {
 // moe (p2pt_llama_plan_kernels_moe): stages gate_up and down are then the routed-expert FFN's kernels (all four must
 // exist), bf16 layers only; a MoeDims the step refuses, or FP8 / MXFP4 layers with it, are -1. nullptr: the call without.
 // experts (p2pt_llama_plan_kernels_experts): the format of an MoE model's experts; the gate_up and down stages are then
-// that format's instantiations. FP8 without moe, or with a dim or ffn that is no multiple of 64, is -1. nullptr: bf16.
+// that format's instantiations. FP8 or MXFP4 without moe, or with a dim or ffn that is no multiple of 64 (FP8) or 128
+// (MXFP4), is -1. nullptr: bf16.
 int p2pt_llama_plan_kernels_experts(const LlamaDims* d, int B, int emit_rows, const WeightFormat* fmt,
                                     const int* windows, int chunk_attn, const MoeDims* moe,
                                     const ExpertFormat* experts) {
@@ -786,7 +799,8 @@ int p2pt_llama_weight_layout_moe(const LlamaDims* d, const MoeDims* moe, int* in
   return T.size();
 }
 // The same with the experts' format (nullptr: bf16, the call above with no scales): scale_index[L * 14 + r] is where the
-// fp32 row scales of role r sit, -1 for every role but w_gate_up and w_down of an FP8-expert table.
+// fp32 row scales (FP8) or e8m0 block scales (MXFP4) of role r sit, -1 for every role but w_gate_up and w_down of an
+// FP8- or MXFP4-expert table.
 int p2pt_llama_weight_layout_experts(const LlamaDims* d, const MoeDims* moe, const ExpertFormat* experts, int* index,
                                      int* scale_index, int n) {
   if (!dims_ok(*d) || !moe_ok(*d, *moe) || !experts_ok(*d, experts) || n < R_NROLES_MOE * d->n_layers) return -1;
@@ -863,6 +877,10 @@ int p2pt_max_rows() { return kMaxM; }
 //      [E][dim]. k_moe_gate_up and k_moe_down are then their FP8 instantiations on the same MoePlan; every other
 //      launch, the router's included, is unchanged. dim and ffn must be multiples of 64. experts == nullptr (or w8 = 0)
 //      is p2pt_llama_decode_moe, launch for launch; FP8 experts without moe are refused.
+//   MXFP4 experts (ExpertFormat::w8 = 2; docs/MOE_MXFP4.md): w_gate_up and w_down are nibble bytes of half the element
+//      count, 16-byte aligned, every row in k-step-quad order, and where the FP8-expert table has row scales come their
+//      e8m0 block scales [E][2 * ffn][dim / 32] and [E][dim][ffn / 32], natural order, 4-byte aligned. The MXFP4
+//      instantiations run on the same MoePlan. dim and ffn must be multiples of 128.
 int p2pt_llama_decode_experts(const LlamaDims* dp, const WeightFormat* fmt, const float* kv_scales, const int* windows,
                               const void* const* w, void* k_cache, void* v_cache, const int64_t* tokens,
                               const int* pos, const int* slots, int B, int emit_rows, void* ws, size_t ws_bytes,
@@ -931,8 +949,8 @@ int p2pt_llama_decode_experts(const LlamaDims* dp, const WeightFormat* fmt, cons
       const p2pt_moe::MoeArgs ma{W.resid, W.ss, P.gate_up.ss_in, static_cast<const uint16_t*>(T.get(R_ROUTER, L)),
                                  T.get(R_W_GATE_UP, L), T.get(R_W_DOWN, L), W.route_id, W.route_w, W.route_rs,
                                  W.moe_h, W.moe_part, B, d.dim, d.ffn, moe->n_experts, moe->top_k, moe->norm_topk, d.eps,
-                                 static_cast<const float*>(T.scale(R_W_GATE_UP, L)),
-                                 static_cast<const float*>(T.scale(R_W_DOWN, L))};
+                                 T.expert_scale(R_W_GATE_UP, L), T.expert_scale(R_W_DOWN, L),
+                                 T.expert_exp(R_W_GATE_UP, L), T.expert_exp(R_W_DOWN, L)};
       if (failed(p2pt_moe::launch_moe(MP, ma, s, EF))) return int(e);
       continue;
     }
@@ -1048,6 +1066,24 @@ int p2pt_chunk_attention(const void* q, const void* kc, const void* vc, const in
 // FP8 experts (p2pt_moe_ffn_experts with ExpertFormat::w8): w_gate_up and w_down are e4m3 bytes of the same shapes in
 // k-step-pair order, gate_up_scale fp32 [E][2 * ffn] and down_scale fp32 [E][dim] their row scales; dim and ffn
 // multiples of 64. experts == nullptr (or w8 = 0) wants both scales nullptr and is p2pt_moe_ffn.
+// MXFP4 experts (p2pt_moe_ffn_mxfp4; w8 = 2): w_gate_up and w_down are nibble bytes [E][2 * ffn][dim / 2] and
+// [E][dim][ffn / 2] in k-step-quad order, gate_up_exp [E][2 * ffn][dim / 32] and down_exp [E][dim][ffn / 32] their e8m0
+// block scales in natural order; dim and ffn multiples of 128; no fp32 scales.
+int p2pt_moe_ffn_mxfp4(void* resid, float* ss, int ss_in, const void* router, const void* w_gate_up, const void* w_down,
+                       int* route_id, float* route_w, float* route_rs, void* moe_h, float* moe_part, int B, int dim,
+                       int ffn, int E, int top_k, int norm_topk, float eps, void* stream, const uint8_t* gate_up_exp,
+                       const uint8_t* down_exp) {
+  if (!rows_ok(B) || dim <= 0 || ffn <= 0) return int(hipErrorInvalidValue);
+  LlamaDims d{};
+  d.dim = dim, d.ffn = ffn;
+  const MoeDims m{E, top_k, norm_topk};
+  const ExpertFormat f{2};
+  if (!moe_ok(d, m) || !experts_ok(d, &f)) return int(hipErrorInvalidValue);
+  const p2pt_moe::MoeArgs a{static_cast<uint16_t*>(resid), ss, ss_in, static_cast<const uint16_t*>(router), w_gate_up,
+                            w_down, route_id, route_w, route_rs, static_cast<uint16_t*>(moe_h), moe_part, B, dim, ffn,
+                            E, top_k, norm_topk, eps, nullptr, nullptr, gate_up_exp, down_exp};
+  return int(p2pt_moe::launch_moe(plan_moe(d, m, B), a, static_cast<hipStream_t>(stream), f));
+}
 int p2pt_moe_ffn_experts(void* resid, float* ss, int ss_in, const void* router, const void* w_gate_up,
                          const void* w_down, int* route_id, float* route_w, float* route_rs, void* moe_h,
                          float* moe_part, int B, int dim, int ffn, int E, int top_k, int norm_topk, float eps,
@@ -1060,7 +1096,7 @@ int p2pt_moe_ffn_experts(void* resid, float* ss, int ss_in, const void* router, 
   if (!moe_ok(d, m) || !experts_ok(d, experts)) return int(hipErrorInvalidValue);
   const p2pt_moe::MoeArgs a{static_cast<uint16_t*>(resid), ss, ss_in, static_cast<const uint16_t*>(router), w_gate_up,
                             w_down, route_id, route_w, route_rs, static_cast<uint16_t*>(moe_h), moe_part, B, dim, ffn,
-                            E, top_k, norm_topk, eps, gate_up_scale, down_scale};
+                            E, top_k, norm_topk, eps, gate_up_scale, down_scale, nullptr, nullptr};
   return int(p2pt_moe::launch_moe(plan_moe(d, m, B), a, static_cast<hipStream_t>(stream),
                                   ExpertFormat{expert_w8(experts)}));
 }

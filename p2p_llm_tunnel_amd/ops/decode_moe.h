@@ -22,8 +22,10 @@ struct MoeDims {
 
 // The format of the stacked expert matrices (w_gate_up, w_down), beside MoeDims as WeightFormat is beside the plans
 // (mirrored with ctypes; docs/MOE_FP8.md). 0: bf16. 1: OCP e4m3fn bytes in k-step-pair order with one fp32 scale per
-// (expert, output row). It changes no field of MoePlan: the grids, wave counts, row tiles and load batches are the
-// bf16 kernels'. The router, the attention projections and the LM head are bf16 either way.
+// (expert, output row). 2 (docs/MOE_MXFP4.md): OCP MXFP4, e2m1 nibbles two to a byte in k-step-quad order with one
+// e8m0 scale byte per 32-element block of a row, and no fp32 scale. It changes no field of MoePlan: the grids, wave
+// counts, row tiles and load batches are the bf16 kernels'. The router, the attention projections and the LM head are
+// bf16 either way.
 struct ExpertFormat {
   int w8;
 };
@@ -46,8 +48,9 @@ struct MoeArgs {
   int ss_in;                // partials the residual's producer left
   const uint16_t* router;   // bf16 [E][dim], the FFN norm weight folded in
   const void* w_gate_up;    // bf16 [E][2 ffn_e][dim], folded, rows interleaved (gate_j, up_j) per expert; with
-                            // ExpertFormat::w8 e4m3 bytes of the same shape, every row in k-step-pair order
-  const void* w_down;       // bf16 (or e4m3 bytes, likewise) [E][dim][ffn_e]
+                            // ExpertFormat::w8 = 1 e4m3 bytes of the same shape, every row in k-step-pair order;
+                            // with w8 = 2 nibble bytes [E][2 ffn_e][dim / 2], every row in k-step-quad order
+  const void* w_down;       // bf16 (or e4m3 bytes, or nibble bytes of half the count, likewise) [E][dim][ffn_e]
   int* route_id;            // int32 [B][top_k], descending probability
   float* route_w;           // fp32 [B][top_k]
   float* route_rs;          // fp32 [B]: 1 / rms of the row, as the router used it
@@ -55,13 +58,16 @@ struct MoeArgs {
   float* moe_part;          // fp32 [B][top_k][dim]
   int B, dim, ffn, E, top_k, norm_topk;
   float eps;
-  const float* gate_up_scale;  // ExpertFormat::w8: fp32 [E][2 ffn_e], the row scales of w_gate_up; nullptr for bf16
-  const float* down_scale;     // ExpertFormat::w8: fp32 [E][dim]; nullptr for bf16
+  const float* gate_up_scale;  // ExpertFormat::w8 = 1: fp32 [E][2 ffn_e], the row scales of w_gate_up; else nullptr
+  const float* down_scale;     // ExpertFormat::w8 = 1: fp32 [E][dim]; else nullptr
+  const uint8_t* gate_up_exp;  // ExpertFormat::w8 = 2: e8m0 [E][2 ffn_e][dim / 32], natural order; else nullptr
+  const uint8_t* down_exp;     // ExpertFormat::w8 = 2: e8m0 [E][dim][ffn_e / 32]; else nullptr
 };
 
 // The four launches of one MoE layer, in order, on stream s; a plan that names a kernel which is not instantiated, or
 // arguments outside what the kernels index, are hipErrorInvalidValue and nothing is launched. f: the experts' format;
-// the GEMM kernels are then its instantiations, and the scales must be there exactly when it is FP8.
+// the GEMM kernels are then its instantiations, the fp32 scales must be there exactly when it is FP8 and the e8m0
+// scales exactly when it is MXFP4.
 hipError_t launch_moe(const MoePlan& p, const MoeArgs& a, hipStream_t s, ExpertFormat f = ExpertFormat{0});
 // Whether the plan's kernels exist in format f (host only).
 bool moe_kernels_exist(const MoePlan& p, ExpertFormat f = ExpertFormat{0});

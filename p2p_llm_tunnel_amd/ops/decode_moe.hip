@@ -13,19 +13,25 @@ namespace {
 using p2pt_moe::MoePlan;
 using MoeKernel = void (*)(MoeArgs);
 
-// k_moe_gate_up / k_moe_down<NW, RT, UM, W8> exist for NW in {4, 8}, RT in {1, 2, 4}, UM in {1, 2, 4}, W8 in {0, 1}:
-// what plan_moe can name, in either expert format. nullptr for anything else. An FP8 kernel's load batch is counted in
-// k-step pairs (decode_moe_kernels.h), so a plan's um of 1 runs 2 k-steps a batch: the <.., 2, 1> instantiation.
+// k_moe_gate_up / k_moe_down<NW, RT, UM, W8> exist for NW in {4, 8}, RT in {1, 2, 4}, UM in {1, 2, 4}, W8 in {0, 1, 2}:
+// what plan_moe can name, in every expert format. nullptr for anything else. An FP8 kernel's load batch is counted in
+// k-step pairs (decode_moe_kernels.h), so a plan's um of 1 runs 2 k-steps a batch: the <.., 2, 1> instantiation. An
+// MXFP4 kernel's is one k-step quad at every um, so every um the plan can name runs the <.., 1, 2> instantiation.
 template <bool DOWN, int NW, int RT, int W8>
 MoeKernel by_um(int um) {
-  switch (um) {
-    case 1:
-      if constexpr (W8 != 0) return DOWN ? k_moe_down<NW, RT, 2, W8> : k_moe_gate_up<NW, RT, 2, W8>;
-      else return DOWN ? k_moe_down<NW, RT, 1> : k_moe_gate_up<NW, RT, 1>;
-    case 2: return DOWN ? k_moe_down<NW, RT, 2, W8> : k_moe_gate_up<NW, RT, 2, W8>;
-    case 4: return DOWN ? k_moe_down<NW, RT, 4, W8> : k_moe_gate_up<NW, RT, 4, W8>;
+  if constexpr (W8 == 2) {
+    if (um == 1 || um == 2 || um == 4) return DOWN ? k_moe_down<NW, RT, 1, 2> : k_moe_gate_up<NW, RT, 1, 2>;
+    return nullptr;
+  } else {
+    switch (um) {
+      case 1:
+        if constexpr (W8 != 0) return DOWN ? k_moe_down<NW, RT, 2, W8> : k_moe_gate_up<NW, RT, 2, W8>;
+        else return DOWN ? k_moe_down<NW, RT, 1> : k_moe_gate_up<NW, RT, 1>;
+      case 2: return DOWN ? k_moe_down<NW, RT, 2, W8> : k_moe_gate_up<NW, RT, 2, W8>;
+      case 4: return DOWN ? k_moe_down<NW, RT, 4, W8> : k_moe_gate_up<NW, RT, 4, W8>;
+    }
+    return nullptr;
   }
-  return nullptr;
 }
 template <bool DOWN, int NW, int W8>
 MoeKernel by_rt(int rt, int um) {
@@ -42,7 +48,10 @@ MoeKernel by_nw(int nw, int rt, int um) {
 }
 template <bool DOWN>
 MoeKernel moe_kernel(int nw, int rt, int um, int w8 = 0) {
-  return w8 == 0 ? by_nw<DOWN, 0>(nw, rt, um) : w8 == 1 ? by_nw<DOWN, 1>(nw, rt, um) : nullptr;
+  return w8 == 0   ? by_nw<DOWN, 0>(nw, rt, um)
+         : w8 == 1 ? by_nw<DOWN, 1>(nw, rt, um)
+         : w8 == 2 ? by_nw<DOWN, 2>(nw, rt, um)
+                   : nullptr;
 }
 
 int log2_exact(int v) { return v == 4 ? 2 : v == 8 ? 3 : v == 16 ? 4 : -1; }
@@ -73,8 +82,13 @@ hipError_t launch_moe(const MoePlan& p, const MoeArgs& a, hipStream_t s, ExpertF
     return hipErrorInvalidValue;
   // FP8 experts: whole k-step pairs of both K (the kernels split and load K by the pair), each expert's slice in bytes
   // below kOob (half the bf16 slice above, tested on its own all the same), and the row scales there exactly then.
-  if (f.w8 && (a.dim % 64 || a.ffn % 64 || size_t(2) * a.ffn * a.dim >= kOob)) return hipErrorInvalidValue;
-  if ((f.w8 != 0) != (a.gate_up_scale != nullptr) || (f.w8 != 0) != (a.down_scale != nullptr))
+  if (f.w8 == 1 && (a.dim % 64 || a.ffn % 64 || size_t(2) * a.ffn * a.dim >= kOob)) return hipErrorInvalidValue;
+  if ((f.w8 == 1) != (a.gate_up_scale != nullptr) || (f.w8 == 1) != (a.down_scale != nullptr))
+    return hipErrorInvalidValue;
+  // MXFP4 experts: whole k-step quads of both K, each expert's nibble slice (and so its scale slice, a sixteenth of
+  // it) below kOob, the e8m0 scales there exactly then, and no fp32 scales (the test above).
+  if (f.w8 == 2 && (a.dim % 128 || a.ffn % 128 || size_t(a.ffn) * a.dim >= kOob)) return hipErrorInvalidValue;
+  if ((f.w8 == 2) != (a.gate_up_exp != nullptr) || (f.w8 == 2) != (a.down_exp != nullptr))
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_moe_route, dim3(p.route_grid), dim3(kRouteWaves * 64), 0, s, a);
   hipLaunchKernelGGL(moe_kernel<false>(p.gu_nw, p.gu_rt, p.gu_um, f.w8), dim3(p.gu_grid_x, p.gu_grid_y), dim3(p.gu_nw * 64), 0,

@@ -129,6 +129,19 @@ __device__ __forceinline__ int moe_pairs(const MoeArgs& a, int e, uint16_t* pair
 // kernel's ranges exactly when NW divides K / 64) and the load batch, max(UM / 2, 1) pairs, i.e. UM k-steps in flight
 // as in the bf16 kernel but never fewer than 2. The row scale is no part of the K loop: wave 0 loads its column's
 // scale ahead of the stream and multiplies the reduced accumulator once, before the pair factor.
+//
+// W8 = 2 (docs/MOE_MXFP4.md): the expert's weights are MXFP4, e2m1 nibbles two to a byte with an e8m0 scale byte per
+// 32-element block, i.e. per k-step, and no fp32 scale. Every row is stored in k-step quads: inside a 64-byte block
+// (128 K elements) the 16 bytes of lane group g are its 8 k-values (4 bytes) of k-steps 4 q, 4 q + 1, 4 q + 2 and
+// 4 q + 3, in that order. One 16-byte load per lane therefore feeds four k-steps, where the natural order allows one
+// 4-byte load a k-step, and one 4-byte load fetches the quad's four scale bytes, which are contiguous in the natural
+// scale order (a second descriptor, over this expert's N K / 32 scale bytes). Word h of the 16 bytes and byte h of
+// the scale word are decoded together (fp4x8_to_bf16x8: exact for every scale) just ahead of MFMA h; the four MFMAs of
+// a quad run in k-step order on the same accumulators, so the MFMA sequence of a K range is the bf16 kernel's on the
+// dequantised weights and nothing after the K loop knows the format. The unit of everything that splits K is the quad:
+// the waves' K ranges (whole quads; the bf16 kernel's ranges exactly when NW divides K / 128) and the load batch, one
+// quad at every UM: four k-steps in flight (UM is not read; the launcher runs the <.., 1, 2> instantiation). A row
+// tile past the expert's pairs loads at kOob, and a load past the buffer returns zeros.
 template <int NW, int RT, int UM, bool DOWN, int W8 = 0>
 __device__ __forceinline__ void moe_gemm(const MoeArgs& a) {
   __shared__ float red[NW][RT][4][kWave];
@@ -139,22 +152,24 @@ __device__ __forceinline__ void moe_gemm(const MoeArgs& a) {
   const int count = moe_pairs(a, e, pairs, &cnt);
   if (count == 0) return;  // no pair: no weight or scale byte is read
   const int K = DOWN ? a.ffn : a.dim, N = DOWN ? a.dim : 2 * a.ffn;
-  // k-steps of 32 (bf16), or pairs of them (W8: K is a multiple of 64, the host's check).
-  const int S = K >> (W8 ? 6 : 5), s0 = wv * S / NW, s1 = (wv + 1) * S / NW;
+  // k-steps of 32 (bf16), pairs of them (W8 = 1: K is a multiple of 64, the host's check) or quads (W8 = 2: of 128).
+  const int S = K >> (W8 == 2 ? 7 : W8 ? 6 : 5), s0 = wv * S / NW, s1 = (wv + 1) * S / NW;
   const int kq = (lane >> 4) << 3, c = lane & 15, lrow0 = (lane >> 4) << 2;
   const __amdgpu_buffer_rsrc_t ra =
       rsrc(DOWN ? a.moe_h : a.resid, uint32_t(DOWN ? a.B * a.top_k : a.B) * uint32_t(K) * 2u);
   // This expert's slice of the stack: the descriptor's base and size are the slice's.
-  constexpr uint32_t kWb = W8 ? 1u : 2u;  // bytes per weight element
+  constexpr uint32_t kWb = W8 ? 1u : 2u;  // bytes per weight element (W8 = 2: per two, see kWs)
+  constexpr int kWs = W8 == 2 ? 1 : 0;    // W8 = 2: two elements a byte
   const uint8_t* we =
-      static_cast<const uint8_t*>(DOWN ? a.w_down : a.w_gate_up) + size_t(e) * size_t(N) * size_t(K) * kWb;
-  const __amdgpu_buffer_rsrc_t rw = rsrc(we, uint32_t(N) * uint32_t(K) * kWb);
+      static_cast<const uint8_t*>(DOWN ? a.w_down : a.w_gate_up) + ((size_t(e) * size_t(N) * size_t(K) * kWb) >> kWs);
+  const __amdgpu_buffer_rsrc_t rw = rsrc(we, (uint32_t(N) * uint32_t(K) * kWb) >> kWs);
   const int col = bx * 16 + c;
-  // bf16: the lane's 8 k-values of a k-step, 16 bytes. W8: its 16 bytes of a pair, at 16 g inside the 64-byte block.
-  const uint32_t woff = W8 ? uint32_t(col) * uint32_t(K) + uint32_t(kq) * 2u
+  // bf16: the lane's 8 k-values of a k-step, 16 bytes. W8 = 1: its 16 bytes of a pair, at 16 g inside the 64-byte
+  // block. W8 = 2: its 16 bytes of a quad, at 16 g inside the 64-byte block of a row of K / 2 bytes.
+  const uint32_t woff = W8 ? ((uint32_t(col) * uint32_t(K)) >> kWs) + uint32_t(kq) * 2u
                            : (uint32_t(col) * uint32_t(K) + uint32_t(kq)) * 2u;
-  float wscale = 0.f;  // W8: the column's row scale, wave 0's, ahead of the weight stream like sc below
-  if constexpr (W8 != 0)
+  float wscale = 0.f;  // W8 = 1: the column's row scale, wave 0's, ahead of the weight stream like sc below
+  if constexpr (W8 == 1)
     if (wv == 0) wscale = (DOWN ? a.down_scale : a.gate_up_scale)[size_t(e) * size_t(N) + size_t(col)];
   const int tiles = (count + 15) >> 4;  // <= RT: the host's choice of RT for B rows
   uint32_t xoff[RT];
@@ -180,7 +195,33 @@ __device__ __forceinline__ void moe_gemm(const MoeArgs& a) {
   frag4 acc[RT];
 #pragma unroll
   for (int t = 0; t < RT; t++) acc[t] = frag4{0.f, 0.f, 0.f, 0.f};
-  if constexpr (W8 != 0) {
+  if constexpr (W8 == 2) {
+    // This expert's e8m0 bytes [N][K / 32], natural order: the four of quad q are the 4 bytes at col K / 32 + 4 q.
+    const __amdgpu_buffer_rsrc_t rs =
+        rsrc((DOWN ? a.down_exp : a.gate_up_exp) + ((size_t(e) * size_t(N) * size_t(K)) >> 5),
+             (uint32_t(N) * uint32_t(K)) >> 5);
+    const uint32_t soff = (uint32_t(col) * uint32_t(K)) >> 5;
+    for (int s = s0; s < s1; s++) {  // one quad per load batch, whatever UM: its range is never past s1
+      const uint32_t su = uint32_t(s) * 256u;  // A bytes of a quad: four k-steps of 32 bf16
+      const uint4 bq = buf_ld16(rw, woff + (su >> 2));
+      const uint32_t eq = buf_ld4(rs, soff + (su >> 6));
+      uint4 af[4][RT];
+#pragma unroll
+      for (int h = 0; h < 4; h++)
+#pragma unroll
+        for (int t = 0; t < RT; t++) af[h][t] = buf_ld16(ra, xoff[t] + su + 64u * h);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int h = 0; h < 4; h++) {
+        const uint32_t w = h == 0 ? bq.x : h == 1 ? bq.y : h == 2 ? bq.z : bq.w;
+        const uint4 b = fp4x8_to_bf16x8(w, (eq >> (8 * h)) & 0xffu);
+#pragma unroll
+        for (int t = 0; t < RT; t++)
+          if (t == 0 || t < tiles)
+            acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(af[h][t]), as_frag(b), acc[t], 0, 0, 0);
+      }
+    }
+  } else if constexpr (W8 != 0) {
     constexpr int UP = UM >= 2 ? UM / 2 : 1;  // pairs per load batch: UM k-steps in flight, 2 at least
     for (int s = s0; s < s1; s += UP) {
       uint4 bq[UP], af[UP][2][RT];
@@ -239,7 +280,7 @@ __device__ __forceinline__ void moe_gemm(const MoeArgs& a) {
         float v = 0.f;
 #pragma unroll
         for (int w = 0; w < NW; w++) v += red[w][t][r][lane];
-        if constexpr (W8 != 0) v *= wscale;  // once, on the reduced sum, before the pair factor
+        if constexpr (W8 == 1) v *= wscale;  // once, on the reduced sum, before the pair factor
         const int p = pr[t][r];
         if constexpr (DOWN) {
           if (p >= 0) a.moe_part[size_t(p) * a.dim + col] = sc[t][r] * v;
