@@ -234,6 +234,112 @@ class _Reader:
         self._handles.clear()
 
 
+# ---------------------------------------------------------------- GPTQ / AWQ 4-bit checkpoints (docs/WEIGHT_INT4.md)
+# The tensor layouts below are the published ones (AutoGPTQ's and AutoAWQ's "gemm" packing); they were not checked
+# against those libraries, which this project does not depend on.
+_AWQ_ORDER = (0, 2, 4, 6, 1, 3, 5, 7)  # nibble i of an AWQ word is column 8 c + _AWQ_ORDER[i]
+_INT4_GROUP = 128
+
+
+def read_quantization(raw: dict) -> dict | None:
+    """The ``quantization_config`` of a checkpoint's config.json as the loader serves it: None without one, else
+    ``{"method": "gptq" | "awq", "zero_offset": 0 | 1}``; everything the int4 kernels do not run is refused."""
+    qc = raw.get("quantization_config")
+    if qc is None:
+        return None
+    method = qc.get("quant_method")
+    if method not in ("gptq", "awq"):
+        raise ValueError(f"quantization_config: quant_method {method!r} is not supported (gptq and awq are)")
+    bits, group = qc.get("bits", qc.get("w_bit")), qc.get("group_size", qc.get("q_group_size"))
+    if bits != 4:
+        raise ValueError(f"quantization_config: bits {bits!r} is not supported: the int4 kernels run 4-bit weights")
+    if group != _INT4_GROUP:
+        raise ValueError(f"quantization_config: group_size {group!r} is not supported: the int4 kernels run groups of "
+                         f"{_INT4_GROUP}")
+    if raw.get("num_local_experts") or raw.get("num_experts"):
+        raise ValueError("quantization_config: a quantised MoE checkpoint is not supported")
+    if method == "gptq":
+        if qc.get("desc_act"):
+            raise ValueError("quantization_config: desc_act true (activation-ordered groups) is not supported: a "
+                             "group must be 128 consecutive input features")
+        fmt = qc.get("checkpoint_format", "gptq")
+        if fmt not in ("gptq", "gptq_v2"):
+            raise ValueError(f"quantization_config: checkpoint_format {fmt!r} is not supported (gptq and gptq_v2 are)")
+        return {"method": "gptq", "zero_offset": 1 if fmt == "gptq" else 0}
+    if str(qc.get("version", "gemm")).lower() != "gemm":
+        raise ValueError(f"quantization_config: AWQ version {qc.get('version')!r} is not supported (gemm is)")
+    if qc.get("zero_point", True) is False:
+        raise ValueError("quantization_config: AWQ with zero_point false (symmetric) is not supported")
+    return {"method": "awq", "zero_offset": 0}
+
+
+def _nibbles(x: torch.Tensor) -> torch.Tensor:
+    """int32 [..., C] to uint8 [..., C, 8]: nibble i (bits 4 i .. 4 i + 3) of every word."""
+    return ((x.to(torch.int32).unsqueeze(-1) >> (4 * torch.arange(8, dtype=torch.int32))) & 15).to(torch.uint8)
+
+
+def unpack_int4_linear(quant: dict, get, has, name: str, N: int, K: int):
+    """One quantised linear layer ``name`` (``.qweight`` / ``.qzeros`` / ``.scales``) as ``(q, z, s)`` of
+    ``ops.pack_weight_w4g``: uint8 [N, K], uint8 [N, K / 128] (the true zero point, 0..16) and fp16 [N, K / 128]."""
+    G = K // _INT4_GROUP
+    qw, qz, sc = get(name + ".qweight"), get(name + ".qzeros"), get(name + ".scales")
+    gptq = quant["method"] == "gptq"
+    want = ((K // 8, N) if gptq else (K, N // 8), (G, N // 8), (G, N))
+    for t, shape, what in zip((qw, qz, sc), want, ("qweight", "qzeros", "scales")):
+        if tuple(t.shape) != shape:
+            raise ValueError(f"{name}.{what}: shape {tuple(t.shape)} != expected {shape}")
+    if qw.dtype != torch.int32 or qz.dtype != torch.int32 or sc.dtype != torch.float16:
+        raise ValueError(f"{name}: qweight and qzeros must be int32 and scales fp16")
+    if gptq:
+        if has(name + ".g_idx") and not torch.equal(get(name + ".g_idx").long(), torch.arange(K) // _INT4_GROUP):
+            raise ValueError(f"{name}.g_idx is permuted: only g_idx[k] == k // {_INT4_GROUP} is supported")
+        q = _nibbles(qw).permute(1, 0, 2).reshape(N, K)  # [K / 8, N, 8]: nibble i of row r is k = 8 r + i
+        z = _nibbles(qz).reshape(G, N)                                        # nibble j of word c: n = 8 c + j
+    else:
+        order = torch.tensor(_AWQ_ORDER)
+        q = torch.empty(K, N // 8, 8, dtype=torch.uint8)
+        q[..., order] = _nibbles(qw)  # nibble i of word c: n = 8 c + order[i]
+        z = torch.empty(G, N // 8, 8, dtype=torch.uint8)
+        z[..., order] = _nibbles(qz)
+        q, z = q.reshape(K, N).T, z.reshape(G, N)
+    z = z.T + quant["zero_offset"]
+    return q.contiguous(), z.contiguous().to(torch.uint8), sc.T.contiguous()
+
+
+def _int4_layer(c, quant, rd, p, t, dev) -> dict:
+    """One layer of a GPTQ / AWQ checkpoint as ``TinyLlama`` takes int4 weights: ``name_q`` / ``name_s`` of each of the
+    four GEMMs (q|k|v and gate|up stacked by rows, rows in the fused table's order, ``ops.pack_weight_w4g``), the norm
+    weights and a q / k / v bias as bf16."""
+    from p2p_llm_tunnel_amd import ops
+    from p2p_llm_tunnel_amd.models.tiny_llm import fused_row_perm
+    q_out, kv_out = c.n_heads * c.head_dim, c.n_kv_heads * c.head_dim
+    parts = {"wqkv": [("self_attn.q_proj", q_out, c.dim), ("self_attn.k_proj", kv_out, c.dim),
+                      ("self_attn.v_proj", kv_out, c.dim)],
+             "wo": [("self_attn.o_proj", c.dim, q_out)],
+             "w_gate_up": [("mlp.gate_proj", c.ffn, c.dim), ("mlp.up_proj", c.ffn, c.dim)],
+             "w_down": [("mlp.down_proj", c.dim, c.ffn)]}
+    L = {"attn_norm": t(p + "input_layernorm.weight", (c.dim,)),
+         "ffn_norm": t(p + "post_attention_layernorm.weight", (c.dim,))}
+    for name, srcs in parts.items():
+        qzs = [unpack_int4_linear(quant, rd.get, rd.has, p + n, N, K) for n, N, K in srcs]
+        q, z, s = (torch.cat([x[j] for x in qzs], 0) for j in range(3))
+        perm = fused_row_perm(c, name, "cpu")
+        if perm is not None:
+            q, z, s = q[perm], z[perm], s[perm]
+        nib, grp = ops.pack_weight_w4g(q.contiguous(), z.contiguous(), s.contiguous())
+        L[name + "_q"], L[name + "_s"] = nib.to(dev), grp.to(dev)
+    for n in ("self_attn.o_proj", "mlp.gate_proj", "mlp.up_proj", "mlp.down_proj"):
+        if rd.has(p + n + ".bias"):
+            raise ValueError(f"{p}{n}.bias: only q, k and v projection biases are supported by the decode kernels")
+    if c.qkv_bias:
+        L["bqkv"] = torch.cat([t(p + "self_attn.q_proj.bias", (q_out,)), t(p + "self_attn.k_proj.bias", (kv_out,)),
+                               t(p + "self_attn.v_proj.bias", (kv_out,))], 0).contiguous()
+    if c.qk_norm:
+        L["q_norm"] = t(p + "self_attn.q_norm.weight", (c.head_dim,))
+        L["k_norm"] = t(p + "self_attn.k_norm.weight", (c.head_dim,))
+    return L
+
+
 def load_llama(path: str, device="cuda", max_batch: int = 8, max_seq: int | None = None,
                fused: bool = True, prefix: str = "model.", kv_dtype: str = "bf16",
                weight_dtype: str = "bf16", kv_scales=None, sliding_window: bool = False,
@@ -246,7 +352,9 @@ def load_llama(path: str, device="cuda", max_batch: int = 8, max_seq: int | None
     (docs/WEIGHT_FP8.md) or "mxfp4" (docs/WEIGHT_MXFP4.md: the layers' GEMM weights as MXFP4, the LM head as FP8): each
     layer's GEMM weights are quantised on ``device`` as soon as the layer is read and its bf16 tensors dropped, so
     the device never holds the bf16 and the quantised copies of all layers together. The checkpoint itself is bf16 / fp16
-    / fp32 either way: one that is already quantised on disk is treated as before. ``expert_dtype``: "bf16", "fp8"
+    / fp32 either way, except that a ``quantization_config`` of ``quant_method`` gptq or awq (4 bits, groups of 128)
+    is detected and its layers are served as they are, as "int4g128" (docs/WEIGHT_INT4.md), with no flag; "int4g128"
+    on a bf16 checkpoint quantises it round-to-nearest. ``expert_dtype``: "bf16", "fp8"
     (docs/MOE_FP8.md; MoE checkpoints only): the stacked experts as e4m3 bytes with per-row scales, each layer's stack
     quantised as soon as it is read (``quantize_experts_``), every other weight bf16; or "mxfp4" (docs/MOE_MXFP4.md):
     the stacks as MXFP4 nibble bytes with e8m0 block scales, quantised layer by layer in the same place. ``chunk_attn``: ``TinyLlama``'s
@@ -262,6 +370,15 @@ def load_llama(path: str, device="cuda", max_batch: int = 8, max_seq: int | None
     from p2p_llm_tunnel_amd.models import kv_scales as kvs
     kv_scales = kvs.parse_kv_scales(kv_scales, kv_dtype)  # refused with a bf16 cache before anything is read
     cfg, raw = read_config(path, max_seq, sliding_window)
+    # A GPTQ / AWQ checkpoint is served as int4g128 without a flag; another weight format on it is refused.
+    quant = read_quantization(raw)
+    if quant is not None:
+        if weight_dtype not in ("bf16", "int4g128"):
+            raise ValueError(f"weight_dtype {weight_dtype!r} on a {quant['method']} checkpoint: its 4-bit weights are "
+                             "served as they are (int4g128)")
+        if not fused:
+            raise ValueError(f"a {quant['method']} checkpoint runs the fused step only: load with fused=True")
+        weight_dtype = "int4g128"
     if cfg.windowed and not fused:
         raise ValueError("a sliding window runs the fused step only: load with fused=True")
     if cfg.n_experts and weight_dtype != "bf16":
@@ -293,8 +410,13 @@ def load_llama(path: str, device="cuda", max_batch: int = 8, max_seq: int | None
             raise KeyError("checkpoint has no lm_head.weight and does not tie embeddings")
         if kv_scales == kvs.CHECKPOINT:
             kv_scales = kvs.read_checkpoint(rd.has, rd.get, c.n_layers, c.n_kv_heads, prefix)
+        if quant is not None and (rd.has("lm_head.qweight") or rd.has(prefix + "embed_tokens.qweight")):
+            raise ValueError("a quantised lm_head or embedding is not supported: GPTQ and AWQ leave them fp16")
         for i in range(c.n_layers):
             p = f"{prefix}layers.{i}."
+            if quant is not None:
+                w["layers"].append(_int4_layer(c, quant, rd, p, t, dev))
+                continue
             q = t(p + "self_attn.q_proj.weight", (q_out, c.dim))
             k = t(p + "self_attn.k_proj.weight", (kv_out, c.dim))
             v = t(p + "self_attn.v_proj.weight", (kv_out, c.dim))

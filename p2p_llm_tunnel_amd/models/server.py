@@ -877,11 +877,12 @@ def parse_kv_dtype(v) -> str:
     return v
 
 
-WEIGHT_DTYPE_CHOICES = ("bf16", "fp8", "mxfp4")
+WEIGHT_DTYPE_CHOICES = ("bf16", "fp8", "mxfp4", "int4g128")
 
 
 def parse_weight_dtype(v) -> str:
-    """--weight-dtype / ``start_server(weight_dtype=)``: "bf16" (the default), "fp8" or "mxfp4"; anything else is refused."""
+    """--weight-dtype / ``start_server(weight_dtype=)``: "bf16" (the default), "fp8", "mxfp4" or "int4g128" (grouped int4,
+    docs/WEIGHT_INT4.md); anything else is refused."""
     if v not in WEIGHT_DTYPE_CHOICES:
         raise ValueError(f"weight_dtype must be one of {list(WEIGHT_DTYPE_CHOICES)}, got {v!r}")
     return v
@@ -1063,7 +1064,10 @@ def arg_parser() -> argparse.ArgumentParser:
                          "bf16): half the weight bytes per decode step; the embedding table stays bf16 "
                          "(docs/WEIGHT_FP8.md); or mxfp4 (OCP Microscaling FP4 for the four GEMM weights of every "
                          "layer: e2m1 values in blocks of 32 with a power-of-two scale, round to nearest, no "
-                         "calibration; the LM head is fp8): about a quarter of their bytes (docs/WEIGHT_MXFP4.md)")
+                         "calibration; the LM head is fp8): about a quarter of their bytes (docs/WEIGHT_MXFP4.md); or "
+                         "int4g128 (uint4 with an fp16 scale and a zero point per group of 128 input features for "
+                         "the four GEMM weights of every layer, GPTQ / AWQ style, round to nearest; the LM head "
+                         "stays bf16; docs/WEIGHT_INT4.md)")
     ap.add_argument("--expert-dtype", choices=EXPERT_DTYPE_CHOICES, default="bf16",
                     help="format of an MoE model's stacked expert matrices (Mixtral checkpoints, tiny-moe): bf16, or "
                          "fp8 (OCP e4m3 with one fp32 scale per expert and output row, per-row absmax, nothing "

@@ -100,7 +100,8 @@ CONFIGS = {
 
 KV_DTYPES = {"bf16": torch.bfloat16, "fp8": torch.float8_e4m3fn}  # TinyLlama(kv_dtype=): the caches' dtype
 # TinyLlama(weight_dtype=): the format of the GEMM weights. "mxfp4": a layer's four as MXFP4, the LM head as FP8.
-WEIGHT_DTYPES = ("bf16", "fp8", "mxfp4")
+# "int4g128" (docs/WEIGHT_INT4.md): a layer's four as grouped uint4 (GPTQ / AWQ style), the LM head bf16.
+WEIGHT_DTYPES = ("bf16", "fp8", "mxfp4", "int4g128")
 # TinyLlama(expert_dtype=): the format of an MoE model's stacked expert matrices alone (docs/MOE_FP8.md,
 # docs/MOE_MXFP4.md).
 EXPERT_DTYPES = tuple(ops.EXPERT_FORMATS)
@@ -136,15 +137,17 @@ def quantize_gemm_weight(w: torch.Tensor, g: torch.Tensor | None, perm: torch.Te
         wf = wf * g.float()[None, :]
     if perm is not None:
         wf = wf[perm]
+    if weight_dtype == "int4g128":  # no fold (the caller passes no g): a group's one scale cannot carry g[k]
+        return ops.pack_weight_w4g(*ops.quantize_weight_w4g(wf.contiguous()))
     quantize = ops.quantize_weight_mxfp4 if weight_dtype == "mxfp4" else ops.quantize_weight_fp8
     return quantize(wf.contiguous())
 
 
 def layer_weight_dtype(L: dict) -> str:
     """The format of a layer's GEMM weights, read off its tensors: "bf16", or what ``quantize_layer_`` made of them
-    ("fp8": fp32 row scales; "mxfp4": e8m0 block-scale bytes)."""
+    ("fp8": fp32 row scales; "mxfp4": e8m0 block-scale bytes; "int4g128": int32 group words)."""
     s = next((L[n + "_s"] for n in GEMM_WEIGHTS if n + "_s" in L), None)
-    return "bf16" if s is None else "mxfp4" if s.dtype == torch.uint8 else "fp8"
+    return "bf16" if s is None else "mxfp4" if s.dtype == torch.uint8 else "int4g128" if s.dtype == torch.int32 else "fp8"
 
 
 def quantize_layer_(cfg: "LlamaConfig", L: dict, weight_dtype: str = "fp8") -> dict:
@@ -156,8 +159,8 @@ def quantize_layer_(cfg: "LlamaConfig", L: dict, weight_dtype: str = "fp8") -> d
         if name + "_q" in L:
             continue
         w = L.pop(name)
-        L[name + "_q"], L[name + "_s"] = quantize_gemm_weight(w, L.get(FOLDED_NORM.get(name)),
-                                                              fused_row_perm(cfg, name, w.device), weight_dtype)
+        g = L.get(FOLDED_NORM.get(name)) if weight_dtype != "int4g128" else None  # int4 keeps the norm weights apart
+        L[name + "_q"], L[name + "_s"] = quantize_gemm_weight(w, g, fused_row_perm(cfg, name, w.device), weight_dtype)
         del w
     return L
 
@@ -207,6 +210,8 @@ def check_expert_scales(L: dict, layer: int) -> None:
 
 def dequantize_gemm_weight(q: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
     """``(q, s)`` of ``quantize_gemm_weight`` back in fp32, whichever format made them."""
+    if s.dtype == torch.int32:
+        return ops.dequantize_weight_w4g(*ops.unpack_weight_w4g(q, s)).float()
     return ops.dequantize_weight_mxfp4(q, s) if s.dtype == torch.uint8 else ops.dequantize_weight_fp8(q, s)
 
 
@@ -270,6 +275,10 @@ class TinyLlama:
         one fp32 scale per output row (docs/WEIGHT_FP8.md), quantised here layer by layer (the bf16 tensor of each
         is dropped as it goes; ``weights`` may bring layers ``quantize_layer_`` has already seen). Only the fused
         step reads them. The embedding stays bf16, so a tied model keeps it and gets an FP8 copy for the LM head.
+        "int4g128" (docs/WEIGHT_INT4.md): a layer's four GEMM weights as grouped uint4, GPTQ / AWQ style (an fp16 scale
+        and a zero point per 128 input features; ``ops.quantize_weight_w4g`` where the weights are bf16, or
+        ``name_q`` / ``name_s`` as ``ops.pack_weight_w4g`` makes them, in the fused table's row order), no norm weight
+        folded in, and a bf16 LM head. dim, ffn and n_heads * head_dim must be multiples of 128; fused step only.
         "mxfp4": a layer's four GEMM weights as OCP Microscaling FP4 (e2m1 nibbles, one e8m0 scale byte per block of
         32; docs/WEIGHT_MXFP4.md) and the LM head in the FP8 format above.
 
@@ -291,6 +300,11 @@ class TinyLlama:
             kv_scales.check(self.cfg.n_layers, self.cfg.n_kv_heads, kv_dtype)
         self.kv_scales = kv_scales
         self.weight_dtype = weight_dtype
+        if weight_dtype == "int4g128":
+            if not fused:
+                raise ValueError("int4 weights run the fused step only (fused=True): the unfused path multiplies bf16 "
+                                 "weights")
+            ops.check_w4g_dims(llama_dims(self.cfg, 1))
         if expert_dtype not in EXPERT_DTYPES:
             raise ValueError(f"expert_dtype must be one of {list(EXPERT_DTYPES)}, got {expert_dtype!r}")
         self.expert_dtype = expert_dtype
@@ -414,11 +428,13 @@ class TinyLlama:
             have = layer_weight_dtype({k: t for k, t in L.items() if k[:-2] not in EXPERT_WEIGHTS}
                                       if self.cfg.n_experts else L)
             if have != "bf16" and have != self.weight_dtype:
-                raise ValueError(f"the weights hold {'FP8' if have == 'fp8' else 'MXFP4'} layers: "
+                raise ValueError(f"the weights hold {'FP8' if have == 'fp8' else have.upper()} layers: "
                                  f"pass weight_dtype='{have}'")
         if self.weight_dtype == "bf16":
             return
         self.layers = [quantize_layer_(self.cfg, dict(L), self.weight_dtype) for L in self.layers]
+        if self.weight_dtype == "int4g128":  # the LM head stays bf16, as GPTQ and AWQ checkpoints leave it
+            return
         self.lm_head_q, self.lm_head_s = quantize_gemm_weight(self.lm_head, self.final_norm, None)
         self.lm_head = None
 
@@ -454,7 +470,7 @@ class TinyLlama:
                     gemm += nb(t)
                 else:
                     other += nb(t)
-        if self.weight_dtype != "bf16":
+        if self.weight_dtype not in ("bf16", "int4g128"):
             gemm += nb(self.lm_head_q) + nb(self.lm_head_s)
         elif self.lm_head is not self.embed and self.lm_head.data_ptr() != self.embed.data_ptr():
             gemm += nb(self.lm_head)
@@ -547,6 +563,7 @@ class TinyLlama:
         # interleave (_quantize_weights), and their row scales follow the table. With MXFP4 weights a layer's four
         # are nibble bytes and their scales the blocks' e8m0 bytes; the LM head is the FP8 one.
         fp8 = self.weight_dtype != "bf16"
+        int4 = self.weight_dtype == "int4g128"  # bf16 LM head with its fold; the layers' four unfolded, norms read as they are
         top = {"embed": self.embed, "final_norm": self.final_norm, "lm_head": self.lm_head,
                "lm_head_q": self.lm_head_q, "lm_head_s": self.lm_head_s, "inv_freq": self.rope_inv_freq()}
 
@@ -565,7 +582,7 @@ class TinyLlama:
                 return src[name[:-len(" scale")] + ("_e" if self.expert_dtype == "mxfp4" else "_s")]
             if self.expert_dtype != "bf16" and name in EXPERT_WEIGHTS:
                 return src[name + "_q"]
-            if fp8 and (name in GEMM_WEIGHTS or name == "lm_head"):
+            if fp8 and (name in GEMM_WEIGHTS or (name == "lm_head" and not int4)):
                 return src[name + "_q"]
             w = src[name]
             if name in FOLDED_NORM or name == "router":  # the router reads the FFN-normed activation too
@@ -702,7 +719,7 @@ class TinyLlama:
         multiplies it. bf16 weights: the tensor itself. FP8 weights: the dequantised ``q * s`` (the function the
         kernels compute; the quantisation error against the original is a separate quantity), which carries the
         preceding norm's weight folded in, so the reference then norms with a weight of one (``_ref_norm``)."""
-        if self.weight_dtype == "bf16":
+        if self.weight_dtype == "bf16" or (layer is None and self.weight_dtype == "int4g128"):
             return (self.lm_head if layer is None else self.layers[layer][name]).float()
         if layer is None:
             return ops.dequantize_weight_fp8(self.lm_head_q, self.lm_head_s)
@@ -762,8 +779,16 @@ class TinyLlama:
             cc, ss = cos[None, :, None, :], sin[None, :, None, :]
             return torch.cat([t1 * cc - t2 * ss, t2 * cc + t1 * ss], -1)
 
+        def normed(v, g, final=False):
+            if self.weight_dtype != "int4g128":
+                return bf(rms(v, self._ref_norm(g)))
+            if final:  # the bf16 LM head keeps its fold
+                return bf(rms(v, g))
+            # int4: the GEMM's A operand is bf16(v * g), one rounding, and 1/rms scales the accumulator in fp32.
+            return bf(v * f32(g)) * torch.rsqrt(v.pow(2).mean(-1, keepdim=True) + c.eps)
+
         residual = x
-        h = bf(rms(x, self._ref_norm(self.layers[0]["attn_norm"])))
+        h = normed(x, self.layers[0]["attn_norm"])
         G = c.n_heads // c.n_kv_heads
         causal = torch.full((T, T), float("-inf"), device=seqs.device).triu(1)
         for i, L in enumerate(self.layers):
@@ -789,7 +814,7 @@ class TinyLlama:
             a = bf(torch.einsum("bhqk,bkhd->bqhd", s.softmax(-1), v).reshape(B, T, -1))
             o = bf(a @ self.reference_weight("wo", i).T)
             residual = bf(residual + o)
-            h = bf(rms(residual, self._ref_norm(L["ffn_norm"])))
+            h = normed(residual, L["ffn_norm"])
             if c.n_experts:
                 # Softmax over all experts, top-k, renormalise, weighted sum: every expert on every token (these are
                 # small models), then each token's top_k gathered. The experts' outputs and their sum stay fp32,
@@ -819,7 +844,7 @@ class TinyLlama:
                 m = bf(bf(F.silu(g_) * u_) @ self.reference_weight("w_down", i).T)
                 residual = bf(residual + m)
             nxt = self.layers[i + 1]["attn_norm"] if i + 1 < len(self.layers) else self.final_norm
-            h = bf(rms(residual, self._ref_norm(nxt)))
+            h = normed(residual, nxt, final=i + 1 == len(self.layers))
         return h
 
     @torch.no_grad()

@@ -70,18 +70,20 @@ class WeightFormat(ctypes.Structure):
     """Mirror of ``WeightFormat``: the weight formats of a step, beside its ``StepPlan`` as ``WeightPlan`` is, and what
     the ``_fmt`` entry points take. ``layers``: the format of a layer's four GEMM weights (wqkv, wo, w_gate_up,
     w_down); ``lm_head``: the LM head's. 0 bf16, 1 FP8 (docs/WEIGHT_FP8.md), 2 MXFP4 (docs/WEIGHT_MXFP4.md: the layers
-    only, with an FP8 LM head). The supported pairs are ``WEIGHT_FORMATS``' values."""
+    only, with an FP8 LM head), 3 grouped int4 (docs/WEIGHT_INT4.md: the layers only, with a bf16 LM head). The supported pairs are ``WEIGHT_FORMATS``' values."""
     _fields_ = [("layers", _INT), ("lm_head", _INT)]
 
     def __repr__(self):
         return f"WeightFormat(layers={self.layers}, lm_head={self.lm_head})"
 
 
-WEIGHT_FORMATS = {"bf16": (0, 0), "fp8": (1, 1), "mxfp4": (2, 1)}  # weight dtype -> (layers, lm_head) of WeightFormat
+# weight dtype -> (layers, lm_head) of WeightFormat. "int4g128" (docs/WEIGHT_INT4.md): grouped uint4 layers, GPTQ / AWQ
+# style, groups of 128, with a bf16 LM head. The name says the group size: plain "int4" stays an unknown dtype.
+WEIGHT_FORMATS = {"bf16": (0, 0), "fp8": (1, 1), "mxfp4": (2, 1), "int4g128": (3, 0)}
 
 
 def as_weight_format(weight_fp8: bool = False, weight_format=None) -> WeightFormat:
-    """The ``WeightFormat`` a caller means: ``weight_format`` (a ``WeightFormat``, or one of "bf16", "fp8", "mxfp4")
+    """The ``WeightFormat`` a caller means: ``weight_format`` (a ``WeightFormat``, or one of "bf16", "fp8", "mxfp4", "int4g128")
     where given, else FP8 throughout for ``weight_fp8`` and bf16 without. Both at once, an unknown name or a pair of
     formats the step does not run are refused (host only: no library)."""
     if weight_format is None:
@@ -313,6 +315,9 @@ def _signatures() -> dict:
         "p2pt_llama_plan_kernels_win": [dims, i, i, wp, ip],
         "p2pt_llama_decode_win": [dims, wp, vp, ip, ptr(vp), vp, vp, vp, vp, vp, i, i, vp, sz, vp, vp, vp],
         "p2pt_llama_weight_format": [dims, i, i, wf],
+        "p2pt_llama_plan_fmt": [dims, wf, i, i, ptr(StepPlan)],
+        "p2pt_llama_ws_bytes_fmt": [dims, wf],
+        "p2pt_llama_ws_layout_fmt": [dims, wf, szp, szp, i],
         "p2pt_llama_plan_kernels_fmt": [dims, i, i, wf, ip],
         "p2pt_llama_weight_layout_fmt": [dims, wf, ip, ip, i],
         "p2pt_llama_decode_fmt": [dims, wf, vp, ip, ptr(vp), vp, vp, vp, vp, vp, i, i, vp, sz, vp, vp, vp],
@@ -341,7 +346,8 @@ def _signatures() -> dict:
     }
 
 
-_RESTYPES = {"p2pt_llama_ws_bytes": ctypes.c_size_t, "p2pt_llama_ws_bytes_moe": ctypes.c_size_t}
+_RESTYPES = {"p2pt_llama_ws_bytes": ctypes.c_size_t, "p2pt_llama_ws_bytes_moe": ctypes.c_size_t,
+             "p2pt_llama_ws_bytes_fmt": ctypes.c_size_t}
 
 
 def lib() -> ctypes.CDLL:
@@ -380,14 +386,23 @@ GEMM_OPERAND_LIMIT = 1 << 31  # bytes: every k_skinny operand stays below it (de
 E4M3_MAX = 448.0  # the largest finite e4m3fn value: a row's largest magnitude quantises to it
 MXFP4_BLOCK = 32  # K elements per MXFP4 block: one e8m0 scale byte each (one k-step of k_skinny)
 MXFP4_EXP_MIN, MXFP4_EXP_MAX = 2, 252  # the e8m0 bytes quantize_weight_mxfp4 emits (its docstring derives them)
+W4G_GROUP = 128  # K elements per group of an int4 weight: one scale and zero point each (a quad of k_skinny's k-steps)
+W4G_ZERO_MAX = 16  # the largest zero point a group word may carry (GPTQ v1 stores z - 1 in a nibble)
 E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)  # the magnitudes of an e2m1 nibble's low three bits; bit 3: sign
 MAX_TOP_LOGPROBS = 20  # top (id, logprob) pairs per row of logprobs_ (logprobs.hip's kMaxTop; the OpenAI API's limit)
 
 
-def step_plan(dims: LlamaDims, B: int, emit_rows: int = 0) -> StepPlan:
+def step_plan(dims: LlamaDims, B: int, emit_rows: int = 0, weight_format=None) -> StepPlan:
     """What ``p2pt_llama_decode`` launches for B rows: the kernel variant, grid and partial counts of every
-    stage, from the library's own planning function (host only: needs the library, not a GPU)."""
+    stage, from the library's own planning function (host only: needs the library, not a GPU).
+    ``weight_format`` (``as_weight_format``): the plan of a step in those formats. Only "int4g128" differs from the plan
+    without it: its K parts carry whole groups of 128 (docs/WEIGHT_INT4.md)."""
     plan = StepPlan()
+    if weight_format is not None:
+        f = as_weight_format(False, weight_format)
+        if lib().p2pt_llama_plan_fmt(ctypes.byref(dims), ctypes.byref(f), B, emit_rows, ctypes.byref(plan)) != 0:
+            raise ValueError("dims, row count or weight format not supported by the fused decode kernels")
+        return plan
     if lib().p2pt_llama_plan(ctypes.byref(dims), B, emit_rows, ctypes.byref(plan)) != 0:
         raise ValueError("dims or row count not supported by the fused decode kernels")
     return plan
@@ -534,6 +549,11 @@ class WeightTable(list):
     aligned and its scales need no alignment. ``pack_weight_mxfp4`` makes this order from nibble codes ``[N][K]``,
     ``unpack_weight_mxfp4`` undoes it, and decode_fused.hip's accessor and the kernel's offsets mirror it.
 
+    "int4g128" (docs/WEIGHT_INT4.md): embed, the norms and lm_head (final_norm folded in) are the bf16 table's; each
+    layer's four GEMM weights are uint8 ``(N, K / 2)`` in ``pack_weight_w4g``'s order, 16-byte aligned, with no norm
+    weight folded in, and after the table come, per layer, their group words, int32 ``(N, K / 128)``, named
+    ``"<weight> scale"`` too. attn_norm and ffn_norm are read by this format: the residual's producers multiply by them.
+
     ``moe`` (a ``MoeDims``; docs/MOE.md): ``dims.ffn`` is the per-expert size, w_gate_up is
     ``(E, 2 * ffn, dim)``, folded and pair-interleaved per expert, w_down ``(E, dim, ffn)``, and every layer ends with
     router, bf16 ``(E, dim)`` with the FFN norm folded in, 16-byte aligned. None: the dense table, unchanged.
@@ -555,14 +575,19 @@ class WeightTable(list):
                              "supported with a routed-expert FFN (expert_format='fp8' quantises the experts alone)")
         d, bf, f32, u8 = dims, (torch.bfloat16,), (torch.float32,), (torch.uint8,)
         gemm, ga = (WEIGHT_FP8_DTYPES, 8) if fmt.lm_head else (bf, 2)
-        n_qkv, norm = (d.H + 2 * d.Hkv) * d.D, (bf, (d.dim,), 2)
+        # int4: the embedding kernel reads layer 0's attn_norm with 16-byte loads
+        n_qkv, norm = (d.H + 2 * d.Hkv) * d.D, (bf, (d.dim,), 16 if fmt.layers == 3 else 2)
         top = {"embed": (bf, (d.vocab, d.dim), 2), "final_norm": norm, "lm_head": (gemm, (d.vocab, d.dim), ga)}
         if d.rope_table:
             top["inv_freq"] = (f32, (d.D // 2,), 8)
         shapes = {"wqkv": (n_qkv, d.dim), "wo": (d.dim, d.H * d.D), "w_gate_up": (2 * d.ffn, d.dim),
                   "w_down": (d.dim, d.ffn)}
+        if fmt.layers == 3:
+            check_w4g_dims(d)
         if fmt.layers == 2:  # nibbles, two to a byte
             lg = {n: (u8, (N, K // 2), 4) for n, (N, K) in shapes.items()}
+        elif fmt.layers == 3:  # nibbles in k-step-quad order: one 16-byte load per lane and quad
+            lg = {n: (u8, (N, K // 2), 16) for n, (N, K) in shapes.items()}
         else:
             lg = {n: (gemm, shape, ga) for n, shape in shapes.items()}
         layer = {"attn_norm": norm, "wqkv": lg["wqkv"], "wo": lg["wo"], "ffn_norm": norm, "w_gate_up": lg["w_gate_up"],
@@ -587,6 +612,9 @@ class WeightTable(list):
             self += [WeightEntry(n + " scale", L, u8, (shapes[n][0], shapes[n][1] // MXFP4_BLOCK), 1)
                      if L is not None and fmt.layers == 2 else WeightEntry(n + " scale", L, f32, v[1][:1], 4)
                      for L, group in groups for n, v in group.items() if n == "lm_head" or n in LAYER_GEMMS]
+        if fmt.layers == 3:  # the group words of each layer's four; the LM head is bf16 and has none
+            self += [WeightEntry(n + " scale", L, (torch.int32,), (shapes[n][0], shapes[n][1] // W4G_GROUP), 4)
+                     for L in range(d.n_layers) for n in LAYER_GEMMS]
         if experts.w8 == 1:  # the experts' row scales, after every other entry
             self += [WeightEntry(n + " scale", L, f32, layer[n][1][:2], 4)
                      for L in range(d.n_layers) for n in ("w_gate_up", "w_down")]
@@ -606,6 +634,14 @@ class WeightTable(list):
         """Where the scales of GEMM weight ``name`` sit (FP8 and MXFP4 tables only): fp32 row scales, or the e8m0
         block scales of an MXFP4 weight."""
         return self.index(name + " scale", layer)
+
+
+def check_w4g_dims(dims: LlamaDims) -> None:
+    """Grouped int4 weights need every K of a layer GEMM in whole groups of 128 (host only)."""
+    if dims.dim % W4G_GROUP or dims.ffn % W4G_GROUP or (dims.H * dims.D) % W4G_GROUP:
+        raise ValueError(f"int4 weights are stored in groups of {W4G_GROUP} (quads of k-steps): dim, ffn and "
+                         f"n_heads * head_dim must be multiples of {W4G_GROUP}, got dim {dims.dim}, ffn {dims.ffn}, "
+                         f"n_heads * head_dim {dims.H * dims.D}")
 
 
 def label(name: str, layer: int | None) -> str:
@@ -1545,6 +1581,91 @@ def dequantize_weight_mxfp4(packed: torch.Tensor, scales: torch.Tensor) -> torch
     return torch.ldexp(val, (scales.to(torch.int32) - 127)[:, :, None]).reshape(N, K)
 
 
+def _check_w4g(q, z, s, what: str):
+    if not isinstance(q, torch.Tensor) or q.dtype != torch.uint8 or q.dim() != 2 or q.shape[1] % W4G_GROUP or \
+            not q.shape[1]:
+        raise TypeError(f"{what}: q must be uint8 [N, K] with K a multiple of {W4G_GROUP} (the group size)")
+    groups = (q.shape[0], q.shape[1] // W4G_GROUP)
+    if not isinstance(z, torch.Tensor) or z.dtype != torch.uint8 or tuple(z.shape) != groups:
+        raise TypeError(f"{what}: z must be uint8 [N, K / {W4G_GROUP}], one zero point per group")
+    if not isinstance(s, torch.Tensor) or s.dtype != torch.float16 or tuple(s.shape) != groups:
+        raise TypeError(f"{what}: s must be fp16 [N, K / {W4G_GROUP}], one scale per group")
+    if q.numel() and (int(q.max()) > 15 or int(z.max()) > W4G_ZERO_MAX):
+        raise ValueError(f"{what}: q must be 0..15 and z 0..{W4G_ZERO_MAX}")
+    if not bool(torch.isfinite(s).all()):
+        raise ValueError(f"{what}: non-finite group scale")
+
+
+def pack_weight_w4g(q: torch.Tensor, z: torch.Tensor, s: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """A grouped int4 weight ``W[n][k] = (q[n][k] - z[n][k // 128]) * s[n][k // 128]`` (``q`` uint8 [N, K] in 0..15,
+    ``z`` uint8 [N, K / 128] in 0..16, ``s`` fp16 [N, K / 128]) to what ``k_skinny<.., W8 = 3>`` loads
+    (docs/WEIGHT_INT4.md): ``(nibbles, groups)``.
+
+    ``nibbles`` uint8 [N, K / 2], every row in k-step-quad order: byte ``64 Q + 16 kq + 4 u + b`` holds
+    ``k = 128 Q + 32 u + 8 kq + 2 b`` in its low nibble and ``k + 1`` in its high one, for quad Q, lane group kq,
+    k-step u of the quad and byte b, each of the last three 0..3 (``block_expert_mxfp4``'s order). The 16 bytes of a
+    lane group are then its 8 k-values of the quad's four k-steps: one load. ``groups`` int32 [N, K / 128]: the fp16
+    bits of ``s`` in bits 0..15 and ``z`` in bits 16..23. The one function that makes this order."""
+    _check_w4g(q, z, s, "pack_weight_w4g")
+    natural = q[:, 0::2] | (q[:, 1::2] << 4)
+    nibbles = natural[:, _expert_perm_mxfp4(natural.shape[1], q.device)].contiguous()
+    groups = (s.view(torch.int16).to(torch.int32) & 0xffff) | (z.to(torch.int32) << 16)
+    return nibbles, groups.contiguous()
+
+
+def unpack_weight_w4g(nibbles: torch.Tensor, groups: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The inverse of ``pack_weight_w4g``: ``(q, z, s)``."""
+    if not isinstance(nibbles, torch.Tensor) or nibbles.dtype != torch.uint8 or nibbles.dim() != 2 or \
+            nibbles.shape[1] % (W4G_GROUP // 2) or not isinstance(groups, torch.Tensor) or \
+            groups.dtype != torch.int32 or tuple(groups.shape) != (nibbles.shape[0], nibbles.shape[1] * 2 // W4G_GROUP):
+        raise TypeError(f"unpack_weight_w4g takes uint8 nibble bytes [N, K / 2] and int32 group words "
+                        f"[N, K / {W4G_GROUP}]")
+    natural = torch.empty_like(nibbles)
+    natural[:, _expert_perm_mxfp4(nibbles.shape[1], nibbles.device)] = nibbles
+    q = torch.stack([natural & 15, natural >> 4], 2).reshape(nibbles.shape[0], -1).contiguous()
+    s = (groups & 0xffff).to(torch.int16).view(torch.float16)
+    return q, ((groups >> 16) & 0xff).to(torch.uint8), s
+
+
+def quantize_weight_w4g(w: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """One GEMM weight ``w`` (fp32 [N, K], K a multiple of 128, in the fused table's row order, no norm weight folded
+    in) to grouped int4 by asymmetric round-to-nearest, nothing calibrated: ``(q, z, s)`` as ``pack_weight_w4g`` takes
+    them. Plain torch on ``w``'s device: runs without a GPU.
+
+    Per group of 128 consecutive k of a row, with lo = min(group, 0) and hi = max(group, 0) (zero lies in the range, as
+    in GPTQ's and AWQ's own quantisers, so a zero point in 0..15 always reaches lo): ``s = fp16((hi - lo) / 15)``,
+    ``z = clamp(round(-lo / s), 0, 15)`` and ``q = clamp(round(w / s) + z, 0, 15)``. z is 0 for a group without negative
+    values and 15 for one without positive ones. A group whose s would round below fp16's smallest normal, 2^-14 (an
+    all-zero group among them), gets s = 2^-14: every element then still lies within 15 steps. A scale beyond fp16's range is
+    refused, as are non-finite weights. Error: |w - (q - z) s| <= s / 2 + 16 * 2^-11 * s per element (the second term
+    is the fp16 rounding of s, which can push the largest element just past step 15), before bf16's own rounding of
+    the dequantised value."""
+    if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or w.dim() != 2 or w.shape[1] % W4G_GROUP or \
+            not w.shape[1]:
+        raise TypeError(f"quantize_weight_w4g takes an fp32 [N, K] tensor with K a multiple of {W4G_GROUP}")
+    if not bool(torch.isfinite(w).all()):
+        raise ValueError("non-finite weight (NaN or inf): refusing to quantise it to int4")
+    N, K = w.shape
+    g = w.reshape(N, K // W4G_GROUP, W4G_GROUP)
+    lo, hi = g.amin(2).clamp(max=0.0), g.amax(2).clamp(min=0.0)
+    s32 = (hi - lo) / 15.0
+    if bool((s32 > 65504.0).any()):
+        raise ValueError("a group's scale exceeds fp16's range: refusing to quantise it to int4")
+    s = s32.to(torch.float16).clamp(min=2.0 ** -14)
+    sf = s.float()
+    z = torch.round(-lo / sf).clamp(0, 15)
+    q = (torch.round(g / sf[:, :, None]) + z[:, :, None]).clamp(0, 15)
+    return q.to(torch.uint8).reshape(N, K), z.to(torch.uint8), s
+
+
+def dequantize_weight_w4g(q: torch.Tensor, z: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
+    """``W_deq = bf16_rne(fp32(q - z) * fp32(s))``, bf16 [N, K]: the weight the int4 kernels compute with, by
+    definition. The fp32 product is exact (at most 5 + 11 significand bits), so there is one rounding."""
+    _check_w4g(q, z, s, "dequantize_weight_w4g")
+    d = q.float() - z.float().repeat_interleave(W4G_GROUP, 1)
+    return (d * s.float().repeat_interleave(W4G_GROUP, 1)).to(torch.bfloat16)
+
+
 class FusedLlamaDecoder:
     """Host handle for the fused decode step (decode_fused.hip): 5 kernels per layer + 3
     (6 per layer with ``dims.qk_norm``: the per-head q/k RMSNorm of Qwen3 runs in a kernel of its own;
@@ -1557,7 +1678,10 @@ class FusedLlamaDecoder:
     ``weights`` is laid out as ``WeightTable(dims, weight_fp8, weight_format)`` says, and every entry is checked
     against it. ``weight_format`` (``as_weight_format``: a ``WeightFormat`` or "bf16", "fp8", "mxfp4") in place of
     ``weight_fp8``; "mxfp4" (docs/WEIGHT_MXFP4.md, ``quantize_weight_mxfp4``) has each layer's four GEMM weights as
-    MXFP4 bytes with e8m0 block scales, run by the ``k_skinny<.., W8 = 2>`` instantiations, and an FP8 LM head.
+    MXFP4 bytes with e8m0 block scales, run by the ``k_skinny<.., W8 = 2>`` instantiations, and an FP8 LM head;
+    "int4g128" (docs/WEIGHT_INT4.md, ``pack_weight_w4g``) has them as grouped uint4 with an fp16 scale and a zero point per
+    128 k, run by the ``W8 = 3`` instantiations on ``step_plan(.., weight_format="int4g128")``, with a bf16 LM head; its
+    workspace has one more buffer, xg.
     ``weight_fp8``: the five GEMM weights as OCP e4m3 bytes with one fp32 scale per output row, each (N,) in the
     row order of its weight (docs/WEIGHT_FP8.md, ``quantize_weight_fp8``). Every ``k_skinny`` is then its FP8-weight
     instantiation; the kernel count, ``step_plan`` and the workspace are the same.
@@ -1641,6 +1765,8 @@ class FusedLlamaDecoder:
                                 if self.weight_fp8 else "")
                              + ("; mxfp4: then lm_head's fp32 row scales and four e8m0 block-scale tensors per layer"
                                 if fmt.layers == 2 else "")
+                             + ("; int4: no norm weight folded into a layer's four, and then four group-word tensors "
+                                "per layer" if fmt.layers == 3 else "")
                              + ("; MoE: w_gate_up and w_down stacked per expert, and router last in every layer"
                                 if self.moe is not None else "")
                              + ("; FP8 experts: then their fp32 row scales, w_gate_up's and w_down's per layer"
@@ -1654,6 +1780,10 @@ class FusedLlamaDecoder:
             name = label(e.name, e.layer)
             if not isinstance(t, torch.Tensor) or t.dtype not in e.dtypes:
                 got = getattr(t, "dtype", type(t))
+                if fmt.layers == 3 and e.dtypes in ((torch.uint8,), (torch.int32,)):
+                    raise TypeError(f"{name}: the weight format is int4, so "
+                                    + ("the group words must be torch.int32" if e.name.endswith(" scale")
+                                       else "the weight must be nibble bytes (torch.uint8)") + f", got {got}")
                 if fmt.layers == 2 and e.dtypes == (torch.uint8,):
                     raise TypeError(f"{name}: the weight format is mxfp4, so "
                                     + ("the block scales must be e8m0 bytes (torch.uint8)" if e.name.endswith(" scale")
@@ -1674,11 +1804,12 @@ class FusedLlamaDecoder:
             if tuple(t.shape) != e.shape:
                 raise ValueError(f"{name} has shape {tuple(t.shape)}, not {e.shape}"
                                  + ("" if not e.name.endswith(" scale") else
+                                    f": one group word per {W4G_GROUP} k" if e.dtypes == (torch.int32,) else
                                     f": one e8m0 byte per {MXFP4_BLOCK}-element block" if e.dtypes == (torch.uint8,)
                                     else ": one fp32 scale per expert and output row" if self.expert_format.w8
                                     else ": one fp32 scale per output row")
                                  + (": two nibbles per byte" if e.name in LAYER_GEMMS and e.dtypes == (torch.uint8,) and
-                                    (fmt.layers == 2 or self.expert_format.w8 == 2) else ""))
+                                    (fmt.layers in (2, 3) or self.expert_format.w8 == 2) else ""))
         L, Bmax, S, Hkv, D = k_cache.shape
         if (L, Bmax, S, Hkv, D) != (dims.n_layers, dims.max_batch, dims.max_seq, dims.Hkv, dims.D):
             raise ValueError("cache shape does not match dims")
@@ -1703,6 +1834,8 @@ class FusedLlamaDecoder:
         self.kv_scales = kv_scales  # keep alive
         if self.moe is not None:
             nbytes = lib().p2pt_llama_ws_bytes_moe(ctypes.byref(dims), ctypes.byref(self.moe))
+        elif fmt.layers == 3:  # the xg buffer after the others
+            nbytes = lib().p2pt_llama_ws_bytes_fmt(ctypes.byref(dims), ctypes.byref(fmt))
         else:
             nbytes = lib().p2pt_llama_ws_bytes(ctypes.byref(dims))
         if nbytes == 0:
@@ -1740,15 +1873,20 @@ class FusedLlamaDecoder:
         am_val [blocks, 64] (fp32); am_idx [blocks, 64], counters [64*H] (int32);
         qkv [64, (H+2*Hkv)*D] (bf16): the raw QKV projection of a QK-norm model's
         last layer, as ``k_qknorm_rope`` read it ([0, ...] for other models).
+        An int4 model adds xg [64, dim] (bf16): the last residual times the norm weight its producer was given.
         An MoE model adds its last layer's route_id, route_w [64, top_k], route_rs [64], moe_h [64 * top_k, ffn]
         and moe_part [64, top_k, dim] (``moe_ffn``), and its h stays unwritten.
         Read them after a stream sync; only the first B rows of a step are defined."""
         d = self.dims
-        buffers = self._WS_BUFFERS + (self._WS_MOE_BUFFERS if self.moe is not None else ())
+        w4g = self.weight_format.layers == 3
+        buffers = self._WS_BUFFERS + (self._WS_MOE_BUFFERS if self.moe is not None else ()) + \
+            ((("xg", torch.bfloat16),) if w4g else ())
         n = len(buffers)
         off, cnt = (ctypes.c_size_t * n)(), (ctypes.c_size_t * n)()
         if self.moe is not None:
             got = lib().p2pt_llama_ws_layout_moe(ctypes.byref(d), ctypes.byref(self.moe), off, cnt, n)
+        elif w4g:
+            got = lib().p2pt_llama_ws_layout_fmt(ctypes.byref(d), ctypes.byref(self.weight_format), off, cnt, n)
         else:
             got = lib().p2pt_llama_ws_layout(ctypes.byref(d), off, cnt, n)
         if got != n:
@@ -1763,6 +1901,8 @@ class FusedLlamaDecoder:
         shapes = {"resid": (M, d.dim), "q": (M, d.H, d.D), "attn": (M, d.H * d.D), "h": (M, d.ffn), "ss": (-1, M),
                   "part_o": (M, d.H, -1, d.D), "part_ml": (M, d.H, -1, 2), "am_val": (-1, M), "am_idx": (-1, M),
                   "counters": (M * d.H,), "qkv": (M if d.qk_norm else 0, (d.H + 2 * d.Hkv) * d.D)}
+        if w4g:
+            shapes["xg"] = (M, d.dim)
         if self.moe is not None:
             k = self.moe.top_k
             shapes.update(route_id=(M, k), route_w=(M, k), route_rs=(M,), moe_h=(M * k, d.ffn), moe_part=(M, k, d.dim))

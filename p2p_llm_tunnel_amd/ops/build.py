@@ -1,10 +1,11 @@
 """Compile the HIP kernels in-tree for gfx950 (CDNA4 / MI355X).
 
-    hipcc -O3 --offload-arch=gfx950 -shared -fPIC decode_moe.o kernels.hip decode_fused.hip sample.hip \
+    hipcc -O3 --offload-arch=gfx950 -shared -fPIC decode_moe.o decode_w4g.o kernels.hip decode_fused.hip sample.hip \
           logprobs.hip kv_copy.hip embed_pool.hip penalty.hip guide.hip -o _hip_ops.so
 
 decode_moe.hip (the routed-expert FFN's kernels) is compiled to an object first, with the same flags and without packed
-fp32 instructions (``NO_PK_F32``); every other source is compiled as it always was, so their code does not change.
+fp32 instructions (``NO_PK_F32``), and so is decode_w4g.hip (the grouped int4 instantiations of the fused GEMM, whose
+decode is scalar fp32 arithmetic); every other source is compiled as it always was, so their code does not change.
 
 Cross-compiles on a CPU-only host; the .so travels with the repo snapshot to
 the GPU box.
@@ -20,8 +21,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SRCS = [os.path.join(HERE, f) for f in ("kernels.hip", "decode_fused.hip", "sample.hip", "logprobs.hip",
                                           "kv_copy.hip", "embed_pool.hip", "penalty.hip", "guide.hip")]
 MOE_SRC = os.path.join(HERE, "decode_moe.hip")
-DEPS = SRCS + [MOE_SRC] + [os.path.join(HERE, h) for h in ("bf16_common.h", "row_common.h", "decode_fused_kernels.h",
-                                                           "decode_moe.h", "decode_moe_kernels.h")]
+W4G_SRC = os.path.join(HERE, "decode_w4g.hip")
+DEPS = SRCS + [MOE_SRC, W4G_SRC] + [os.path.join(HERE, h) for h in (
+    "bf16_common.h", "row_common.h", "decode_fused_kernels.h", "decode_fused_set.h", "decode_moe.h",
+    "decode_moe_kernels.h", "decode_w4g.h")]
 NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 OUT = os.path.join(HERE, "_hip_ops.so")
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950").split(";")[0]
@@ -43,10 +46,11 @@ def build(verbose: bool = False, force: bool = False) -> str:
         return OUT
     flags = ["-O3", f"--offload-arch={ARCH}", "-std=c++17", "-fPIC"]
     with tempfile.TemporaryDirectory(prefix="p2pt_hip_ops_") as tmp:
-        moe_obj = os.path.join(tmp, "decode_moe.o")
-        # The object goes ahead of the sources: hipcc's "-x hip" holds for every input after a .hip file.
+        moe_obj, w4g_obj = os.path.join(tmp, "decode_moe.o"), os.path.join(tmp, "decode_w4g.o")
+        # The objects go ahead of the sources: hipcc's "-x hip" holds for every input after a .hip file.
         for cmd in ([hipcc(), *flags, *NO_PK_F32, "-c", MOE_SRC, "-o", moe_obj],
-                    [hipcc(), *flags, "-shared", "-o", OUT + ".tmp", moe_obj, *SRCS]):
+                    [hipcc(), *flags, *NO_PK_F32, "-c", W4G_SRC, "-o", w4g_obj],
+                    [hipcc(), *flags, "-shared", "-o", OUT + ".tmp", moe_obj, w4g_obj, *SRCS]):
             if verbose:
                 print(" ".join(cmd), flush=True)
             r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)

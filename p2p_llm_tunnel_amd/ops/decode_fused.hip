@@ -4,7 +4,9 @@
 // lookups and launches that follow a plan into that set, and the C entry
 // points. The kernels and the design notes are in decode_fused_kernels.h.
 #include "decode_fused_kernels.h"
+#include "decode_fused_set.h"
 #include "decode_moe.h"
+#include "decode_w4g.h"
 
 #include <type_traits>
 #include <utility>
@@ -73,9 +75,16 @@ struct WeightFormat {
   int layers;   // wqkv, wo, w_gate_up, w_down: k_skinny<.., layers>
   int lm_head;  // k_skinny<.., EPI_ARGMAX, .., lm_head>
 };
+// 3 (docs/WEIGHT_INT4.md): grouped int4, GPTQ / AWQ style: uint4 nibbles in k-step-quad order with one word (fp16 scale,
+// zero point) per group of 128 k, the layers only, with a bf16 LM head. Unlike the others it does change the step: the
+// norm weight cannot be folded into a group, so the residual's producers also store xg = bf16(resid * g_next) into a
+// workspace buffer of its own and the QKV and gate/up GEMMs read that (plan_step, ws_layout and the table take the
+// format for it), and K parts carry whole quads.
 bool format_ok(const WeightFormat& f) {
-  return (f.layers == 0 && f.lm_head == 0) || (f.layers == 1 && f.lm_head == 1) || (f.layers == 2 && f.lm_head == 1);
+  return (f.layers == 0 && f.lm_head == 0) || (f.layers == 1 && f.lm_head == 1) || (f.layers == 2 && f.lm_head == 1) ||
+         (f.layers == kW4g && f.lm_head == 0);
 }
+constexpr int kW4gGroup = 128;  // k per group: one quad of k-steps
 // The scales of an FP8 cache, beside the plans as WeightPlan is and for the same reason: no field of LlamaDims, no
 // entry of the weight table, so a model without scales plans, lays out and launches what it did. One device buffer,
 // fp32 [4][n_layers][Hkv]: 1 / k_scale, 1 / v_scale (what the writers multiply by, computed once on the host),
@@ -169,11 +178,16 @@ bool moe_ok(const LlamaDims& d, const MoeDims& m) {
 //  - Load batch um: each wave's share of k-steps, rounded up to a power of two,
 //    at most 4 (fewer registers, more resident waves).
 // A K without a whole k-step leaves nw = 0, which launch() refuses.
-GemmPlan plan_gemm(int epi, int tn, int M, int N, int K, bool k_parts = false, int fixed_nw = 0) {
+// quads (grouped int4 weights): a K part must hold whole quads of k-steps, so where K / 128 does not split into the P
+// parts the rule above picks, the next smaller P that does is taken (bf16 gives up K parts there: it never happens
+// for a K that is a multiple of 128 * P). The waves then split K / 128 quads, not K / 32 k-steps; nw and um keep
+// their rule, so where nw does not divide the quads some waves get fewer or none.
+GemmPlan plan_gemm(int epi, int tn, int M, int N, int K, bool k_parts = false, int fixed_nw = 0, bool quads = false) {
   GemmPlan p{};
   p.epi = epi, p.tn = tn, p.M = M, p.N = N, p.K = K;
   if (k_parts && tn == 1 && (N >> 4) < kCUs) {
-    const int kpl = std::min((N >> 3) >= kCUs ? 1 : 2, kMaxKpl);
+    int kpl = std::min((N >> 3) >= kCUs ? 1 : 2, kMaxKpl);
+    while (quads && kpl > 0 && K % (kW4gGroup << kpl)) kpl--;
     if ((M << kpl) <= 16 && K % (32 << kpl) == 0) p.kpl = kpl;
   }
   const int steps = (K >> p.kpl) >> 5;
@@ -218,7 +232,8 @@ AttnPlan plan_attn(int B, int H, int Hkv, int D, int max_seq) {
   return {D, Hkv > 0 ? H / Hkv : 0, attn_slots(B, Hkv, max_seq), attn_part_stride(max_seq), B * Hkv};
 }
 
-StepPlan plan_step(const LlamaDims& d, int B, int emit_rows) {
+StepPlan plan_step(const LlamaDims& d, int B, int emit_rows, const WeightFormat& f = WeightFormat{0, 0}) {
+  const bool quads = f.layers == kW4g;
   StepPlan p{};
   p.rows = B;
   p.emit_rows = emit_rows <= 0 || emit_rows > B ? B : emit_rows;
@@ -227,16 +242,16 @@ StepPlan plan_step(const LlamaDims& d, int B, int emit_rows) {
   // Scaled RoPE (rope_table): the table counterpart of whichever kernel rotates; nothing else moves.
   // FP8 cache (kv_fp8): the _KV8 counterpart of whichever kernel appends, and of k_attn; nothing else moves.
   const int qkv_epi = d.qk_norm ? EPI_STORE : rope_epi(d.qkv_bias, d.rope_table, d.kv_fp8);
-  p.qkv = plan_gemm(qkv_epi, 1, B, (d.H + 2 * d.Hkv) * d.D, d.dim);
+  p.qkv = plan_gemm(qkv_epi, 1, B, (d.H + 2 * d.Hkv) * d.D, d.dim, false, 0, quads);
   if (d.qk_norm) {
     const int per_wg = qknorm_heads_per_wg(d.D);
     p.qk_norm_grid = (d.H + 2 * d.Hkv + per_wg - 1) / per_wg;
     p.qk_norm_table = d.rope_table;
   }
   p.attn = plan_attn(B, d.H, d.Hkv, d.D, d.max_seq);
-  p.o = plan_gemm(EPI_RESID, kTnResid, B, d.dim, d.H * d.D, true);
-  p.gate_up = plan_gemm(EPI_SILU, 1, B, 2 * d.ffn, d.dim);
-  p.down = plan_gemm(EPI_RESID, kTnResid, B, d.dim, d.ffn, true);
+  p.o = plan_gemm(EPI_RESID, kTnResid, B, d.dim, d.H * d.D, true, 0, quads);
+  p.gate_up = plan_gemm(EPI_SILU, 1, B, 2 * d.ffn, d.dim, false, 0, quads);
+  p.down = plan_gemm(EPI_RESID, kTnResid, B, d.dim, d.ffn, true, 0, quads);
   p.lm_head = plan_lm_head(d, p.emit_rows);
   p.qkv_first = p.qkv;
   p.qkv_first.ss_in = 1;
@@ -250,7 +265,7 @@ StepPlan plan_step(const LlamaDims& d, int B, int emit_rows) {
 size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
 struct Workspace {
-  uint16_t *resid, *q, *attn, *h, *qkv, *moe_h;
+  uint16_t *resid, *q, *attn, *h, *qkv, *moe_h, *xg;
   float *ss, *part_o, *part_ml, *am_val, *route_w, *route_rs, *moe_part;
   int *am_idx, *route_id;
   unsigned* counters;  // [kMaxM * H] attention split tickets (self-resetting)
@@ -261,19 +276,20 @@ struct Workspace {
 // The routed-expert FFN's buffers follow WS_QKV and are empty without MoeDims; WS_NDENSE counts the buffers
 // p2pt_llama_ws_layout reports, WS_NBUF those of p2pt_llama_ws_layout_moe.
 enum WsBuf : int { WS_RESID, WS_Q, WS_ATTN, WS_H, WS_SS, WS_PART_O, WS_PART_ML, WS_AM_VAL, WS_AM_IDX, WS_COUNTERS, WS_QKV,
-                   WS_NDENSE, WS_ROUTE_ID = WS_NDENSE, WS_ROUTE_W, WS_ROUTE_RS, WS_MOE_H, WS_MOE_PART, WS_NBUF };
+                   WS_NDENSE, WS_ROUTE_ID = WS_NDENSE, WS_ROUTE_W, WS_ROUTE_RS, WS_MOE_H, WS_MOE_PART, WS_NBUF,
+                   WS_XG = WS_NBUF, WS_NALL };  // WS_XG: grouped int4 only, after every buffer the other layouts report
 
 struct WsLayout {
-  size_t off[WS_NBUF];    // byte offset from the workspace base (256-byte aligned)
+  size_t off[WS_NALL];    // byte offset from the workspace base (256-byte aligned)
   // elements: bf16 resid/q/attn/h/qkv/moe_h, fp32 ss/part_o/part_ml/am_val/route_w/route_rs/moe_part, int32 am_idx/route_id,
   // uint32 counters
-  size_t count[WS_NBUF];
+  size_t count[WS_NALL];
   size_t bytes;
 };
 
 // The one place that knows the workspace layout. The counts that depend on a
 // grid are the plan's own, at their worst case over the row count.
-WsLayout ws_layout(const LlamaDims& d, const MoeDims* moe = nullptr) {
+WsLayout ws_layout(const LlamaDims& d, const MoeDims* moe = nullptr, const WeightFormat& f = WeightFormat{0, 0}) {
   WsLayout l{};
   size_t off = 0;
   auto take = [&](WsBuf b, size_t count, size_t elem) {
@@ -304,12 +320,16 @@ WsLayout ws_layout(const LlamaDims& d, const MoeDims* moe = nullptr) {
   take(WS_ROUTE_RS, moe ? kMaxM : 0, 4);
   take(WS_MOE_H, pairs * d.ffn, 2);
   take(WS_MOE_PART, pairs * d.dim, 4);
+  // Grouped int4 weights: xg = bf16(resid * g_next), what the QKV and gate/up GEMMs read. Empty otherwise, and last, so
+  // the offsets and the size of every other format are unchanged.
+  take(WS_XG, f.layers == kW4g ? size_t(kMaxM) * d.dim : 0, 2);
   l.bytes = off;
   return l;
 }
 
-Workspace carve(const LlamaDims& d, uint8_t* base, const MoeDims* moe = nullptr) {
-  const WsLayout l = ws_layout(d, moe);
+Workspace carve(const LlamaDims& d, uint8_t* base, const MoeDims* moe = nullptr,
+                const WeightFormat& f = WeightFormat{0, 0}) {
+  const WsLayout l = ws_layout(d, moe, f);
   Workspace w{};
   auto at = [&](WsBuf b) { return base ? base + l.off[b] : nullptr; };
   w.resid = reinterpret_cast<uint16_t*>(at(WS_RESID));
@@ -328,6 +348,7 @@ Workspace carve(const LlamaDims& d, uint8_t* base, const MoeDims* moe = nullptr)
   w.route_rs = reinterpret_cast<float*>(at(WS_ROUTE_RS));
   w.moe_h = reinterpret_cast<uint16_t*>(at(WS_MOE_H));
   w.moe_part = reinterpret_cast<float*>(at(WS_MOE_PART));
+  w.xg = reinterpret_cast<uint16_t*>(at(WS_XG));
   w.bytes = l.bytes;
   return w;
 }
@@ -345,6 +366,10 @@ Workspace carve(const LlamaDims& d, uint8_t* base, const MoeDims* moe = nullptr)
 // With MXFP4 experts (ew8 = 2; docs/MOE_MXFP4.md) w_gate_up and w_down are nibble bytes [E][2 ffn_e][dim / 2] and
 // [E][dim][ffn_e / 2], 16-byte aligned, rows in k-step-quad order, and where the FP8-expert table has the row scales it
 // has their e8m0 bytes [E][2 ffn_e][dim / 32] and [E][dim][ffn_e / 32], 4-byte aligned: expert_exp() reaches them.
+// A grouped int4 table (docs/WEIGHT_INT4.md) has bf16 embed, norms and lm_head (final_norm folded in), each layer GEMM as
+// N * K / 2 nibble bytes in k-step-quad order, 16-byte aligned, with no norm weight folded in, and after the table per
+// layer the four group-word tensors [N][K / 128] uint32 where the FP8 table has row scales (no lm_head entry ahead of
+// them). Its attn_norm and ffn_norm entries are read: they are the g of the xg stores.
 // An MoE table (moe set; bf16 apart from the experts) has one more entry per layer, after every other: router, bf16 [E][dim] with the FFN
 // norm folded in; its w_gate_up is [E][2 ffn_e][dim], folded and pair-interleaved per expert, and its w_down
 // [E][dim][ffn_e]. R_ROUTER follows R_NROLES so that p2pt_llama_weight_layout's 13 roles per layer stay what they are.
@@ -358,7 +383,9 @@ struct WeightTable {
   int ew8 = 0;  // ExpertFormat::w8 (moe only): FP8 or MXFP4 experts have two scale entries per layer after the table
   int per_layer() const { return (d.qk_norm ? 8 : d.qkv_bias ? 7 : 6) + moe; }
   int scales0() const { return 3 + d.rope_table + per_layer() * d.n_layers; }
-  int size() const { return scales0() + (f.lm_head ? 1 + 4 * d.n_layers : 0) + (ew8 ? 2 * d.n_layers : 0); }
+  int size() const {
+    return scales0() + (f.lm_head ? 1 + 4 * d.n_layers : f.layers == kW4g ? 4 * d.n_layers : 0) + (ew8 ? 2 * d.n_layers : 0);
+  }
   // The format of a GEMM weight's role (0 for every other role).
   int format(Role r) const {
     return r == R_LM_HEAD ? f.lm_head : r == R_WQKV || r == R_WO || r == R_W_GATE_UP || r == R_W_DOWN ? f.layers : 0;
@@ -379,6 +406,7 @@ struct WeightTable {
     // FP8 experts: the layers are bf16 (an MoE model's only format), so the experts' scales are all there is.
     if (ew8 && (r == R_W_GATE_UP || r == R_W_DOWN)) return scales0() + 2 * L + (r == R_W_DOWN);
     const int j = r == R_WQKV ? 1 : r == R_WO ? 2 : r == R_W_GATE_UP ? 3 : r == R_W_DOWN ? 4 : 0;
+    if (f.layers == kW4g) return j ? scales0() + 4 * L + j - 1 : -1;  // no lm_head scales ahead of the layers'
     return !format(r) ? -1 : scales0() + (j ? 4 * L + j : 0);
   }
   const void* get(Role r, int L = 0) const { return at(index(r, L)); }  // nullptr where the table has none
@@ -399,11 +427,13 @@ GemmArgs operator+(GemmArgs a, Set set) {
   return a;
 }
 // M, N, K and kpl are the plan's: launch() fills them in. scale: what the table holds for the weight's scales, the
-// fp32 row scales of an FP8 weight (fmt 1) or the e8m0 block scales of an MXFP4 one (fmt 2); nullptr: bf16.
+// fp32 row scales of an FP8 weight (fmt 1), the e8m0 block scales of an MXFP4 one (fmt 2) or the group words of a
+// grouped int4 one (fmt 3); nullptr: bf16.
 GemmArgs gemm(const void* x, const void* w, const void* scale = nullptr, int fmt = 1) {
   GemmArgs a{};
   a.x = static_cast<const uint16_t*>(x), a.w = static_cast<const uint16_t*>(w);
   if (fmt == 2) a.wexp = static_cast<const uint8_t*>(scale);
+  else if (fmt == kW4g) a.wgrp = static_cast<const uint32_t*>(scale);
   else a.wscale = static_cast<const float*>(scale);
   return a;
 }
@@ -425,68 +455,19 @@ auto rope(const LlamaDims& d, const int* pos, const int* slot, uint16_t* q, uint
     a.H = d.H, a.Hkv = d.Hkv, a.D = d.D, a.Smax = d.max_seq, a.log2_theta = log2f(d.theta);
   };
 }
-auto resid(uint16_t* r, float* ss_out) {
-  return [=](GemmArgs& a) { a.out = r, a.ss_out = ss_out; };
+// gnext, xg: grouped int4 only (the next norm's weight and the buffer its product with the new residual goes to).
+auto resid(uint16_t* r, float* ss_out, const void* gnext = nullptr, uint16_t* xg = nullptr) {
+  return [=](GemmArgs& a) { a.out = r, a.ss_out = ss_out, a.gnext = static_cast<const uint16_t*>(gnext), a.xg = xg; };
 }
 auto argmax(void* logits, float* am_val, int* am_idx) {
   return [=](GemmArgs& a) { a.out = static_cast<uint16_t*>(logits), a.am_val = am_val, a.am_idx = am_idx; };
 }
 
-// ------------------------------------------------------------ the kernels that exist
-// Stated once: a list of values per template parameter and, for k_skinny, one predicate over their product. The
-// three *_kernel() lookups instantiate exactly this set; the launchers, p2pt_llama_plan_kernels and dims_ok read
-// nothing else.
-template <int... V>
-using Ints = std::integer_sequence<int, V...>;
-using HeadDims = Ints<64, 128>;  // D of k_attn and k_qknorm_rope
-// G of k_attn, the GQA ratio H / Hkv (models/checkpoint.py mirrors it as _GQA_RATIOS). 5, 6 and 7 are the Qwen2 /
-// Qwen2.5 family's (40/8, 12/2, 14/2 and 28/4). 3 is absent: no checkpoint the loader accepts uses it.
-using GqaRatios = Ints<1, 2, 4, 5, 6, 7, 8>;
-using Flags = Ints<0, 1>;  // KV8 and WIN of k_attn; TAB and KV8 of k_qknorm_rope
-using SkinnyFormats = Ints<0, 1, 2>;  // W8 of k_skinny: bf16, FP8, MXFP4
-using SkinnyWaves = Ints<4, 8>;
-using SkinnyTiles = Ints<1, 2>;
-using SkinnyBatches = Ints<1, 2, 4>;
-using SkinnyEpis = Ints<EPI_STORE, EPI_ROPE, EPI_SILU, EPI_RESID, EPI_ARGMAX, EPI_ROPE_BIAS, EPI_ROPE_TAB,
-                        EPI_ROPE_BIAS_TAB, EPI_ROPE_KV8, EPI_ROPE_BIAS_KV8, EPI_ROPE_TAB_KV8, EPI_ROPE_BIAS_TAB_KV8>;
-constexpr bool skinny_exists(int nw, int tn, int epi, int um, int w8) {
-  // Two subtiles for the LM head and the standalone GEMM (plain STORE has both), one for every other epilogue.
-  if (tn != (epi == EPI_ARGMAX ? 2 : 1) && !(epi == EPI_STORE && tn == 2)) return false;
-  // FP8 weights run the five GEMMs of a step only (the standalone GEMM stays bf16), so they carry what plan_gemm
-  // can give those: the LM head's fixed 4 waves with any load batch, and for the others the (nw, um) pairs of
-  // fixed_nw == 0 below. 47 instantiations beside the 66 of bf16.
-  if (w8 && epi == EPI_STORE && tn == 2) return false;
-  // MXFP4 weights run a layer's four GEMMs only (the LM head stays FP8): every epilogue those can be planned with,
-  // the eight RoPE ones, SILU, RESID and, for QK-norm models, STORE with one subtile, never ARGMAX, each with the
-  // (nw, um) pairs of fixed_nw == 0. 44 instantiations beside the 47 of FP8 and the 66 of bf16.
-  if (w8 == 2 && epi == EPI_ARGMAX) return false;
-  if (w8 && epi == EPI_ARGMAX) return nw == 4;
-  if (w8) return nw == 4 || um == 4;
-  // The table and FP8-cache epilogues run QKV projections only, so they carry just the (nw, um) pairs plan_gemm
-  // can give one (fixed_nw == 0): 4 waves up to 16 k-steps with um 1, 2 or 4, and 8 waves from 17 on, where a
-  // wave's share is at least 3 k-steps and um is 4.
-  if (epi_has_table(epi) || epi_kv8(epi)) return nw == 4 || um == 4;
-  return true;
-}
-template <int... V>
-constexpr bool contains(Ints<V...>, int v) {
-  return ((v == V) || ...);
-}
-
-// pick(f, v0, Ints<...>{}, v1, Ints<...>{}, ...) calls f(c0, c1, ...), each c a std::integral_constant equal to
-// its run-time v, and calls nothing when some v is in no list.
-template <typename F>
-void pick(F&& f) {
-  f();
-}
-template <typename F, int... V, typename... Rest>
-void pick(F&& f, int v, Ints<V...>, Rest... rest) {
-  ((v == V ? pick([&](auto... c) { f(std::integral_constant<int, V>{}, c...); }, rest...) : void()), ...);
-}
-
 // The kernel a plan names, or nullptr where it is not instantiated.
 using SkinnyKernel = void (*)(GemmArgs);
 SkinnyKernel skinny_kernel(const GemmPlan& p, int w8 = 0) {
+  // Grouped int4: the same lists and predicate, instantiated in decode_w4g.hip.
+  if (w8 == kW4g) return reinterpret_cast<SkinnyKernel>(const_cast<void*>(p2pt_w4g::skinny_kernel(p.nw, p.tn, p.epi, p.um)));
   SkinnyKernel k = nullptr;
   pick([&](auto nw, auto tn, auto epi, auto um, auto f8) {
     if constexpr (skinny_exists(nw, tn, epi, um, f8)) k = k_skinny<nw, tn, epi, um, f8>;
@@ -519,9 +500,14 @@ bool rows_ok(int B) { return B > 0 && B <= kMaxM; }
 // ------------------------------------------------------------ launches
 // Each checks its arguments, looks its kernel up and launches it; a plan that names no kernel is hipErrorInvalidValue.
 // w8: the weight's format (WeightFormat): 1, the FP8-weight instantiation, reads a.wscale and is refused without it;
-// 2, the MXFP4 one, reads a.wexp likewise. A scale pointer the format does not read is refused too.
+// 2, the MXFP4 one, reads a.wexp likewise; 3, the grouped int4 one, a.wgrp. A scale pointer the format does not read is
+// refused too.
 hipError_t launch(const GemmPlan& p, GemmArgs a, hipStream_t s, int w8 = 0) {
   if ((w8 == 1) != (a.wscale != nullptr) || (w8 == 2) != (a.wexp != nullptr)) return hipErrorInvalidValue;
+  // Grouped int4: the group words, K parts of whole quads, and for a residual producer the xg store's two pointers.
+  if ((w8 == kW4g) != (a.wgrp != nullptr) || (w8 == kW4g && p.K % (kW4gGroup << p.kpl))) return hipErrorInvalidValue;
+  if ((w8 == kW4g && p.epi == EPI_RESID) != (a.gnext != nullptr) || (a.gnext != nullptr) != (a.xg != nullptr))
+    return hipErrorInvalidValue;
   if (p.kpl < 0 || p.kpl > kMaxKpl || (p.ss_in > 0) != (a.ss_part != nullptr)) return hipErrorInvalidValue;
   if (p.kpl && (p.tn != 1 || (p.M << p.kpl) > 16 || p.K % (32 << p.kpl))) return hipErrorInvalidValue;
   // The bias is added once, after the K-split reduction: never with K parts, never without a bias.
@@ -614,6 +600,11 @@ bool dims_ok(const LlamaDims& d) {
   return true;
 }
 
+// Grouped int4 weights: every K of a layer GEMM (dim, H * D, ffn) in whole groups of 128.
+bool format_dims_ok(const LlamaDims& d, const WeightFormat& f) {
+  return f.layers != kW4g || (d.dim % kW4gGroup == 0 && (d.H * d.D) % kW4gGroup == 0 && d.ffn % kW4gGroup == 0);
+}
+
 }  // namespace
 
 extern "C" {
@@ -668,6 +659,27 @@ int p2pt_llama_plan(const LlamaDims* d, int B, int emit_rows, StepPlan* out) {
   return 0;
 }
 
+// The same for a step in weight formats fmt (p2pt_llama_decode_fmt): grouped int4 layers plan their K parts in whole
+// quads; every other format is the plan above, int for int.
+int p2pt_llama_plan_fmt(const LlamaDims* d, const WeightFormat* fmt, int B, int emit_rows, StepPlan* out) {
+  if (!dims_ok(*d) || !rows_ok(B) || !format_ok(*fmt) || !format_dims_ok(*d, *fmt)) return int(hipErrorInvalidValue);
+  *out = plan_step(*d, B, emit_rows, *fmt);
+  return 0;
+}
+// The workspace of a step in weight formats fmt: p2pt_llama_ws_bytes' and p2pt_llama_ws_layout's eleven buffers at
+// their offsets, and with grouped int4 layers a twelfth, xg bf16 [64][dim], after them (empty otherwise).
+size_t p2pt_llama_ws_bytes_fmt(const LlamaDims* d, const WeightFormat* fmt) {
+  if (!dims_ok(*d) || !format_ok(*fmt) || !format_dims_ok(*d, *fmt)) return 0;
+  return ws_layout(*d, nullptr, *fmt).bytes;
+}
+int p2pt_llama_ws_layout_fmt(const LlamaDims* d, const WeightFormat* fmt, size_t* off, size_t* count, int n) {
+  if (!dims_ok(*d) || !format_ok(*fmt) || !format_dims_ok(*d, *fmt) || n < WS_NDENSE + 1) return 0;
+  const WsLayout l = ws_layout(*d, nullptr, *fmt);
+  for (int b = 0; b < WS_NDENSE; b++) off[b] = l.off[b], count[b] = l.count[b];
+  off[WS_NDENSE] = l.off[WS_XG], count[WS_NDENSE] = l.count[WS_XG];
+  return WS_NDENSE + 1;
+}
+
 // The FP8-cache variants p2pt_llama_decode launches beside the plan above (host only); both 0 for a bf16 cache.
 int p2pt_llama_kv_plan(const LlamaDims* d, KvPlan* out) {
   if (!dims_ok(*d)) return int(hipErrorInvalidValue);
@@ -692,11 +704,12 @@ int p2pt_llama_plan_kernels_experts(const LlamaDims* d, int B, int emit_rows, co
                                     const int* windows, int chunk_attn, const MoeDims* moe,
                                     const ExpertFormat* experts) {
   if (!dims_ok(*d) || !rows_ok(B) || !format_ok(*fmt) || !windows_ok(*d, Windows{windows})) return -1;
+  if (!format_dims_ok(*d, *fmt)) return -1;
   if (moe && (!moe_ok(*d, *moe) || fmt->layers != 0)) return -1;
   if (!experts_ok(*d, experts) || (!moe && expert_w8(experts))) return -1;
   const bool moe_found =
       !moe || p2pt_moe::moe_kernels_exist(plan_moe(*d, *moe, B), ExpertFormat{expert_w8(experts)});
-  const StepPlan P = plan_step(*d, B, emit_rows);
+  const StepPlan P = plan_step(*d, B, emit_rows, *fmt);
   const KvPlan KV = plan_kv(*d);
   const int w8 = fmt->layers;
   bool attn = true;
@@ -768,10 +781,10 @@ int p2pt_llama_weight_plan(const LlamaDims* d, int weight_fp8, WeightPlan* out) 
   return 0;
 }
 
-// The weight formats of a step for (layers, lm_head) in {(0, 0), (1, 1), (2, 1)} (host only), beside the plans above.
+// The weight formats of a step for (layers, lm_head) in {(0, 0), (1, 1), (2, 1), (3, 0)} (host only), beside the plans above.
 int p2pt_llama_weight_format(const LlamaDims* d, int layers, int lm_head, WeightFormat* out) {
   const WeightFormat f{layers, lm_head};
-  if (!dims_ok(*d) || !format_ok(f)) return int(hipErrorInvalidValue);
+  if (!dims_ok(*d) || !format_ok(f) || !format_dims_ok(*d, f)) return int(hipErrorInvalidValue);
   *out = f;
   return 0;
 }
@@ -781,7 +794,7 @@ int p2pt_llama_weight_format(const LlamaDims* d, int layers, int lm_head, Weight
 // scales of an MXFP4 weight) sit, -1 where there is none.
 // n: ints each array holds, at least 13 * n_layers. -1: dims or formats refused, or n too small.
 int p2pt_llama_weight_layout_fmt(const LlamaDims* d, const WeightFormat* fmt, int* index, int* scale_index, int n) {
-  if (!dims_ok(*d) || !format_ok(*fmt) || n < R_NROLES * d->n_layers) return -1;
+  if (!dims_ok(*d) || !format_ok(*fmt) || !format_dims_ok(*d, *fmt) || n < R_NROLES * d->n_layers) return -1;
   const WeightTable T{*d, *fmt, nullptr};
   for (int L = 0; L < d->n_layers; L++)
     for (int r = 0; r < R_NROLES; r++) {
@@ -888,6 +901,7 @@ int p2pt_llama_decode_experts(const LlamaDims* dp, const WeightFormat* fmt, cons
                               const ExpertFormat* experts) {
   const LlamaDims d = *dp;
   if (!dims_ok(d) || !rows_ok(B) || (!slots && B > d.max_batch) || !format_ok(*fmt)) return int(hipErrorInvalidValue);
+  if (!format_dims_ok(d, *fmt)) return int(hipErrorInvalidValue);
   if (moe && (!moe_ok(d, *moe) || fmt->layers != 0)) return int(hipErrorInvalidValue);
   if (!experts_ok(d, experts) || (!moe && expert_w8(experts))) return int(hipErrorInvalidValue);
   const ExpertFormat EF{expert_w8(experts)};
@@ -896,9 +910,12 @@ int p2pt_llama_decode_experts(const LlamaDims* dp, const WeightFormat* fmt, cons
   if (!windows_ok(d, WN)) return int(hipErrorInvalidValue);
   const KvScales KS{kv_scales};
   const int w8 = fmt->layers;
-  const Workspace W = carve(d, static_cast<uint8_t*>(ws), moe);
+  const Workspace W = carve(d, static_cast<uint8_t*>(ws), moe, *fmt);
   if (ws_bytes < W.bytes) return int(hipErrorInvalidValue);
-  const StepPlan P = plan_step(d, B, emit_rows);
+  const StepPlan P = plan_step(d, B, emit_rows, *fmt);
+  // Grouped int4: the normed GEMMs read xg, which the residual's producers store with the next norm's weight.
+  const bool w4g = w8 == kW4g;
+  const uint16_t* normed_in = w4g ? W.xg : W.resid;
   const MoePlan MP = moe ? plan_moe(d, *moe, B) : MoePlan{};
   const KvPlan KV = plan_kv(d);
   const ChunkPlan CP = plan_attn_chunk(B, d.H, d.Hkv, d.D, d.max_seq);
@@ -909,22 +926,34 @@ int p2pt_llama_decode_experts(const LlamaDims* dp, const WeightFormat* fmt, cons
 
   const WeightTable T{d, *fmt, w, moe ? 1 : 0, EF.w8};
   const void* inv_freq = T.get(R_INV_FREQ);
-  hipLaunchKernelGGL(k_embed, dim3(B), dim3(256), 0, s, static_cast<const uint16_t*>(T.get(R_EMBED)), tokens, W.resid,
-                     W.ss, d.dim, d.vocab);
-  if (failed(hipGetLastError())) return int(e);
+  if (w4g) {
+    if (failed(p2pt_w4g::launch_embed_xg(static_cast<const uint16_t*>(T.get(R_EMBED)), tokens, W.resid, W.ss, d.dim,
+                                         d.vocab, static_cast<const uint16_t*>(T.get(R_ATTN_NORM, 0)), W.xg, B, s)))
+      return int(e);
+  } else {
+    hipLaunchKernelGGL(k_embed, dim3(B), dim3(256), 0, s, static_cast<const uint16_t*>(T.get(R_EMBED)), tokens,
+                       W.resid, W.ss, d.dim, d.vocab);
+    if (failed(hipGetLastError())) return int(e);
+  }
   for (int L = 0; L < d.n_layers; L++) {
     uint16_t* kc = reinterpret_cast<uint16_t*>(static_cast<uint8_t*>(k_cache) + L * layer_cache);
     uint16_t* vc = reinterpret_cast<uint16_t*>(static_cast<uint8_t*>(v_cache) + L * layer_cache);
     const GemmPlan& qkv = L ? P.qkv : P.qkv_first;
-    const GemmArgs qkv_in = gemm(W.resid, T.get(R_WQKV, L), T.scale(R_WQKV, L), w8) + norm(W.ss, qkv.ss_in, d.eps);
+    const GemmArgs qkv_in = gemm(normed_in, T.get(R_WQKV, L), T.scale(R_WQKV, L), w8) + norm(W.ss, qkv.ss_in, d.eps);
     const GemmArgs to_qkv =
         d.qk_norm ? qkv_in + store(W.qkv)
                   : qkv_in + rope(d, pos, slots, W.q, kc, vc, T.get(R_BQKV, L), inv_freq,
                                   KS.at(d, KvScales::K_RECIP, L), KS.at(d, KvScales::V_RECIP, L));
-    const GemmArgs to_o = gemm(W.attn, T.get(R_WO, L), T.scale(R_WO, L), w8) + resid(W.resid, W.ss);
-    const GemmArgs to_gate_up = gemm(W.resid, T.get(R_W_GATE_UP, L), T.scale(R_W_GATE_UP, L), w8) +
+    // The norm weight the GEMM after each residual producer would have folded: ffn_norm after O, the next layer's
+    // attn_norm after down (the last layer's: final_norm, whose xg nothing reads; the LM head keeps its fold).
+    const void* g_o = w4g ? T.get(R_FFN_NORM, L) : nullptr;
+    const void* g_down = !w4g ? nullptr : L + 1 < d.n_layers ? T.get(R_ATTN_NORM, L + 1) : T.get(R_FINAL_NORM);
+    const GemmArgs to_o = gemm(W.attn, T.get(R_WO, L), T.scale(R_WO, L), w8) +
+                          resid(W.resid, W.ss, g_o, w4g ? W.xg : nullptr);
+    const GemmArgs to_gate_up = gemm(normed_in, T.get(R_W_GATE_UP, L), T.scale(R_W_GATE_UP, L), w8) +
                                 norm(W.ss, P.gate_up.ss_in, d.eps) + store(W.h);
-    const GemmArgs to_down = gemm(W.h, T.get(R_W_DOWN, L), T.scale(R_W_DOWN, L), w8) + resid(W.resid, W.ss);
+    const GemmArgs to_down = gemm(W.h, T.get(R_W_DOWN, L), T.scale(R_W_DOWN, L), w8) +
+                             resid(W.resid, W.ss, g_down, w4g ? W.xg : nullptr);
     if (failed(launch(qkv, to_qkv, s, w8))) return int(e);
     if (P.qk_norm_grid) {
       const QkNormArgs qn{W.qkv, static_cast<const uint16_t*>(T.get(R_Q_NORM, L)),

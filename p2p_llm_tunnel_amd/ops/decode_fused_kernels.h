@@ -28,6 +28,12 @@
 //                        blocks of e2m1 nibbles with one e8m0 scale byte, 4-byte loads and a 1-byte scale load per
 //                        k-step, decoded exactly by v_cvt_scalef32_pk_bf16_fp4 ahead of the MFMA; no scale in the
 //                        epilogue. The LM head stays FP8. The same kernel count: docs/WEIGHT_MXFP4.md)
+//     (int4 weights:     a layer's four k_skinny are their W8 = 3 instantiations: GPTQ / AWQ style uint4 with an fp16
+//                        scale and a zero point per group of 128, one 16-byte nibble load and one 4-byte group-word
+//                        load per quad of k-steps, decoded by an fma and v_cvt_pk_bf16_f32 ahead of the MFMA. The norm
+//                        weight cannot be folded into a group, so the residual's producers also store bf16(resid * g)
+//                        and QKV and gate/up read that. The LM head stays bf16. The same kernel count:
+//                        docs/WEIGHT_INT4.md)
 //     k_skinny<RESID>    O projection -> residual add -> per-row sum-of-squares
 //                        partials for the next norm
 //     k_skinny<SILU>     RMSNorm (ffn_norm) -> gate/up GEMM -> SwiGLU
@@ -37,7 +43,7 @@
 //   k_argmax_merge       one block per row merges the winners
 //
 // k_skinny<NW, TN, EPI, UM, W8>, k_attn<D, G, KV8, WIN> and k_qknorm_rope<D, TAB, KV8> are templates; which instantiations
-// exist is stated once, as lists of parameter values and one predicate, in decode_fused.hip, and a plan that names
+// exist is stated once, as lists of parameter values and one predicate, in decode_fused_set.h, and a plan that names
 // any other is refused there. The RoPE epilogue of a model is rope_epi(bias, table, kv8) below.
 //
 // Skinny GEMM (M <= 64 tokens): Y[M,N] = A[M,K] * W[N,K]^T on
@@ -163,6 +169,14 @@ struct GemmArgs {
   // nibble), and wexp the e8m0 scale byte of every 32-element block, [N][K / 32] in the row order of w. Not read by
   // the other kernels.
   const uint8_t* wexp;
+  // Grouped int4 weights (k_skinny<.., W8 = 3>; docs/WEIGHT_INT4.md): w holds N * K / 2 nibble bytes, every row in
+  // k-step-quad order, and wgrp one word per group of 128 k, [N][K / 128] in the row order of w: the fp16 bits of the
+  // group's scale in the low half, its zero point (0..16) in byte 2. Not read by the other kernels.
+  const uint32_t* wgrp;
+  // W8 = 3, EPI_RESID: the residual's producer also stores xg[m][n] = bf16(resid_new[m][n] * gnext[n]), the A operand
+  // of the next normed GEMM (a group's scale cannot carry the norm weight, which varies inside it). gnext: bf16 [N].
+  const uint16_t* gnext;
+  uint16_t* xg;
 };
 
 // log2 of the output columns per 16-lane subtile: 16, 8 or 4 for 1, 2 or 4 K parts.
@@ -267,6 +281,66 @@ __device__ __forceinline__ uint4 fp4x8_to_bf16x8(uint32_t v, uint32_t e) {
                     cv(std::integral_constant<int, 2>{}), cv(std::integral_constant<int, 3>{}));
 }
 
+// Grouped int4: one word (eight nibbles q in 0..15, the lower k in the lower nibble) as eight bf16 of (q - z) * s, for
+// the group's scale s and nzs = -z * s (w4g_group). fma(float(q), s, nzs) is (q - z) * s rounded once to fp32, and that
+// product is exact (5 + 11 significand bits), so the one rounding is v_cvt_pk_bf16_f32's, to nearest even: the bits of
+// bf16_rne(fp32(q - z) * fp32(s)). Scalar fmas only: this code is compiled without packed fp32 instructions. A load
+// past the buffer (zero nibbles, zero group word) decodes to zeros.
+typedef float float2v_w4g __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint4 w4g_to_bf16x8(uint32_t w, float s, float nzs) {
+  auto cv = [&](uint32_t lo, uint32_t hi) {
+    const float2v_w4g f = {__builtin_fmaf(float(lo), s, nzs), __builtin_fmaf(float(hi), s, nzs)};
+    return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, bf16x2_t));
+  };
+  return make_uint4(cv(w & 15u, (w >> 4) & 15u), cv((w >> 8) & 15u, (w >> 12) & 15u),
+                    cv((w >> 16) & 15u, (w >> 20) & 15u), cv((w >> 24) & 15u, w >> 28));
+}
+// A group word to (s, -z * s): the product is exact (z <= 16, s an fp16 value).
+__device__ __forceinline__ void w4g_group(uint32_t g, float& s, float& nzs) {
+  s = float(__builtin_bit_cast(_Float16, uint16_t(g)));
+  nzs = -float((g >> 16) & 0xffu) * s;
+}
+
+// The wave's quads of k-steps [q0, q1) of grouped int4 weights, QB quads per load batch. A quad is one group of 128 k:
+// per subtile one 16-byte load holds the lane's 8 k-values of its four k-steps (word u: k-step 4 q + u) and one 4-byte
+// load the group word, beside the bf16 kernel's four 16-byte A loads. Each word is decoded just ahead of its MFMA, in
+// the bf16 kernel's k order, so on the dequantised weights the accumulator is the bf16 kernel's bit for bit where the
+// two split K over the waves alike.
+template <int QB, int TN>
+__device__ __forceinline__ void mma_stream_w4g(frag4 (&acc)[TN], __amdgpu_buffer_rsrc_t ra, uint32_t xoff,
+                                               __amdgpu_buffer_rsrc_t rw, const uint32_t (&woff)[TN],
+                                               __amdgpu_buffer_rsrc_t rg, const uint32_t (&goff)[TN], int q0, int q1) {
+  for (int q = q0; q < q1; q += QB) {
+    uint4 b[QB][TN], x[QB][4];
+    uint32_t g[QB][TN];
+#pragma unroll
+    for (int i = 0; i < QB; i++) {
+      const bool in = q + i < q1;
+      const uint32_t qi = uint32_t(q + i);
+#pragma unroll
+      for (int t = 0; t < TN; t++) {
+        b[i][t] = buf_ld16(rw, in ? woff[t] + qi * 64u : kOob);
+        g[i][t] = buf_ld4(rg, in ? goff[t] + qi * 4u : kOob);
+      }
+#pragma unroll
+      for (int u = 0; u < 4; u++) x[i][u] = buf_ld16(ra, in ? xoff + (qi * 4u + u) * 64u : kOob);
+    }
+    __builtin_amdgcn_sched_barrier(0);  // every load of the batch ahead of the first MFMA, as in mma_stream
+#pragma unroll
+    for (int i = 0; i < QB; i++)
+#pragma unroll
+      for (int u = 0; u < 4; u++)
+#pragma unroll
+        for (int t = 0; t < TN; t++) {
+          float s, nzs;
+          w4g_group(g[i][t], s, nzs);
+          const uint32_t w = u == 0 ? b[i][t].x : u == 1 ? b[i][t].y : u == 2 ? b[i][t].z : b[i][t].w;
+          acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(x[i][u]), as_frag(w4g_to_bf16x8(w, s, nzs)), acc[t],
+                                                           0, 0, 0);
+        }
+  }
+}
+
 // One batch of up to UM consecutive 32-wide k-steps [s, min(s + UM, s1)):
 // every load of the batch is issued before any of it is used.
 // W8 (FP8 weights): the lane's B fragment of a k-step is its 8 k-values as 8 e4m3 bytes, one 8-byte load at a
@@ -349,6 +423,10 @@ __device__ __forceinline__ void mma_stream(frag4 (&acc)[TN], __amdgpu_buffer_rsr
 // N * K / 32 bytes). The stream is as above with 4-byte B loads and a 1-byte scale load per k-step (Batch); under K
 // parts both offsets carry the part. There is no scale in the epilogue: the decoded fragment is the dequantised
 // weight itself, so the kernel matches the bf16 kernel on those weights bit for bit, for every scale.
+// W8 = 3: grouped int4 (docs/WEIGHT_INT4.md): N * K / 2 nibble bytes in k-step-quad order and one group word per 128 k
+// (GemmArgs::wgrp). The waves split K in quads and K parts carry whole quads (the host plans kpl so); a load batch is
+// one quad for UM 1 and 2 and two quads for UM 4 (mma_stream_w4g). Nothing after the MFMA knows the format. With
+// EPI_RESID the epilogue also stores xg = bf16(resid_new * gnext[col]), the next normed GEMM's A operand.
 template <int NW, int TN, int EPI, int UM, int W8 = 0>
 __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
   __shared__ float red[NW][TN][4][kWave];
@@ -385,14 +463,18 @@ __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
   const int kq = (lane >> 4) << 3;
   const int S = Kp >> 5;
   const int s0 = wv * S / NW, s1 = (wv + 1) * S / NW;
+  const int Sq = Kp >> 7, q0 = wv * Sq / NW, q1 = (wv + 1) * Sq / NW;  // W8 = 3: the wave's quads
   // Byte offsets of this lane's A row and weight rows at k-step 0; rows past
   // M read as zeros (kOob).
   const __amdgpu_buffer_rsrc_t ra = rsrc(a.x, uint32_t(a.M) * uint32_t(a.K) * 2u);
   constexpr uint32_t kWb = W8 ? 1u : 2u;   // bytes per weight element ...
-  constexpr uint32_t kWs = W8 == 2 ? 1u : 0u;  // ... halved once more for MXFP4's nibbles
+  constexpr uint32_t kWs = W8 >= 2 ? 1u : 0u;  // ... halved once more for MXFP4's and int4's nibbles
   const __amdgpu_buffer_rsrc_t rw = rsrc(a.w, (uint32_t(a.N) * uint32_t(a.K) * kWb) >> kWs);
   // MXFP4: the scale bytes, [N][K / 32]; the other formats never load through it.
-  const __amdgpu_buffer_rsrc_t rs = W8 == 2 ? rsrc(a.wexp, uint32_t(a.N) * uint32_t(a.K >> 5)) : rw;
+  // Grouped int4: the group words, [N][K / 128] of 4 bytes, through the same descriptor slot.
+  const __amdgpu_buffer_rsrc_t rs = W8 == 2   ? rsrc(a.wexp, uint32_t(a.N) * uint32_t(a.K >> 5))
+                                    : W8 == 3 ? rsrc(a.wgrp, uint32_t(a.N) * uint32_t(a.K >> 7) * 4u)
+                                              : rw;
   const uint32_t xoff = a_ok ? (uint32_t(m0 + m_a) * uint32_t(a.K) + uint32_t(p_a * Kp + kq)) * 2u : kOob;
   const int p_b = (lane & 15) >> cwl;  // K part of this lane's weight column
   uint32_t woff[TN], soff[TN];
@@ -401,6 +483,11 @@ __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
     const uint32_t col = uint32_t(tile_col<TN>(bx, t, lane & 15, cwl));
     woff[t] = ((col * uint32_t(a.K) + uint32_t(p_b * Kp + kq)) * kWb) >> kWs;
     soff[t] = col * uint32_t(a.K >> 5) + uint32_t(p_b * (Kp >> 5));  // the block of k-step 0 of this lane's K part
+    if constexpr (W8 == 3) {
+      // Quad order: the lane group's 16 bytes of quad 0 of this lane's K part, and that quad's group word.
+      woff[t] = ((col * uint32_t(a.K) + uint32_t(p_b * Kp)) >> 1) + (uint32_t(lane >> 4) << 4);
+      soff[t] = (col * uint32_t(a.K >> 7) + uint32_t(p_b * (Kp >> 7))) * 4u;
+    }
   }
 
   // C layout: row m = m0 + 4*(lane>>4) + r, column = tile_col(.., lane & 15).
@@ -454,6 +541,15 @@ __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
     }
   }
 
+  // W8 = 3, RESID: the next norm's weight at this lane's columns (below N like wsc's), loaded ahead of the stream.
+  float gnx[W8 == 3 && EPI == EPI_RESID ? TN : 1];
+  if constexpr (W8 == 3 && EPI == EPI_RESID) {
+    if (wv == 0) {
+#pragma unroll
+      for (int t = 0; t < TN; t++) gnx[t] = bf2f(a.gnext[tile_col<TN>(bx, t, c, cwl)]);
+    }
+  }
+
   // _KV8 with scales: the reciprocal scale of this workgroup's head, loaded ahead of the weight stream like bias
   // and tab_freq. A tile's 16 columns lie in one head (D is a multiple of 16 and QKV has no K parts), so the head
   // and the load are uniform: one scalar load per workgroup. q heads, and a model without scales, keep 1.
@@ -466,7 +562,8 @@ __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
   frag4 acc[TN];
 #pragma unroll
   for (int t = 0; t < TN; t++) acc[t] = frag4{0.f, 0.f, 0.f, 0.f};
-  mma_stream<UM, TN, W8>(acc, ra, xoff, rw, woff, rs, soff, s0, s1);
+  if constexpr (W8 == 3) mma_stream_w4g<(UM == 4 ? 2 : 1), TN>(acc, ra, xoff, rw, woff, rs, soff, q0, q1);
+  else mma_stream<UM, TN, W8>(acc, ra, xoff, rw, woff, rs, soff, s0, s1);
 
   if (norm) {
     float ssum = 0.f;
@@ -645,6 +742,7 @@ __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
         if (m >= a.M || !col_ok) continue;
         const float nv = bf_round(rprev[t][r] + bf_round(v[t][r]));
         a.out[size_t(m) * a.N + n] = uint16_t(f2bf_bits(nv));
+        if constexpr (W8 == 3) a.xg[size_t(m) * a.N + n] = uint16_t(f2bf_bits(nv * gnx[t]));  // exact product, one rounding
         sq[r] += nv * nv;
       }
     }
@@ -699,9 +797,12 @@ __global__ __launch_bounds__(256) void k_argmax_merge(const float* __restrict__ 
 
 // ------------------------------------------------------------ embedding gather
 // One block per token: residual row = embed[token]; ss_out[0][b] = sum of squares.
-__global__ __launch_bounds__(256) void k_embed(const uint16_t* __restrict__ embed, const int64_t* __restrict__ tok,
-                                               uint16_t* __restrict__ resid, float* __restrict__ ss_out, int dim,
-                                               int vocab) {
+// XG (k_embed_xg: grouped int4 weights): also xg row = bf16(embed[token] * g), g layer 0's attn_norm weight [dim]: the
+// exact fp32 product of two bf16 values, rounded once.
+template <bool XG>
+__device__ __forceinline__ void embed_row(const uint16_t* __restrict__ embed, const int64_t* __restrict__ tok,
+                                          uint16_t* __restrict__ resid, float* __restrict__ ss_out, int dim, int vocab,
+                                          const uint16_t* __restrict__ g, uint16_t* __restrict__ xg) {
   const int b = blockIdx.x;
   int64_t t = tok[b];
   t = t < 0 ? 0 : (t >= vocab ? vocab - 1 : t);
@@ -715,12 +816,31 @@ __global__ __launch_bounds__(256) void k_embed(const uint16_t* __restrict__ embe
     unpack8(v, f);
 #pragma unroll
     for (int j = 0; j < 8; j++) ss += f[j] * f[j];
+    if constexpr (XG) {
+      float gf[8];
+      unpack8(reinterpret_cast<const uint4*>(g)[i], gf);
+#pragma unroll
+      for (int j = 0; j < 8; j++) gf[j] *= f[j];
+      reinterpret_cast<uint4*>(xg + size_t(b) * dim)[i] = pack8(gf);
+    }
   }
   __shared__ float red[4];
   ss = wave_sum(ss);
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ss;
   __syncthreads();
   if (threadIdx.x == 0) ss_out[b] = red[0] + red[1] + red[2] + red[3];
+}
+__global__ __launch_bounds__(256) void k_embed(const uint16_t* __restrict__ embed, const int64_t* __restrict__ tok,
+                                               uint16_t* __restrict__ resid, float* __restrict__ ss_out, int dim,
+                                               int vocab) {
+  embed_row<false>(embed, tok, resid, ss_out, dim, vocab, nullptr, nullptr);
+}
+// A template only so that the one translation unit that launches it (decode_w4g.hip) emits it.
+template <int = 0>
+__global__ __launch_bounds__(256) void k_embed_xg(const uint16_t* __restrict__ embed, const int64_t* __restrict__ tok,
+                                                  uint16_t* __restrict__ resid, float* __restrict__ ss_out, int dim,
+                                                  int vocab, const uint16_t* __restrict__ g, uint16_t* __restrict__ xg) {
+  embed_row<true>(embed, tok, resid, ss_out, dim, vocab, g, xg);
 }
 
 // ------------------------------------------------------------ per-head QK RMSNorm + RoPE + cache append
