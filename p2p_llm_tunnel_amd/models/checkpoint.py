@@ -64,6 +64,7 @@ needed here; the fused decoder applies its own interleaving at setup.
 from __future__ import annotations
 
 import json
+import math
 import os
 
 import torch
@@ -343,7 +344,7 @@ def _int4_layer(c, quant, rd, p, t, dev) -> dict:
 def load_llama(path: str, device="cuda", max_batch: int = 8, max_seq: int | None = None,
                fused: bool = True, prefix: str = "model.", kv_dtype: str = "bf16",
                weight_dtype: str = "bf16", kv_scales=None, sliding_window: bool = False,
-               chunk_attn: bool = False, expert_dtype: str = "bf16") -> TinyLlama:
+               chunk_attn: bool = False, expert_dtype: str = "bf16", loras: dict | None = None) -> TinyLlama:
     """A TinyLlama with the checkpoint's weights (bf16 on ``device``). ``kv_dtype``: "bf16" or "fp8", the KV
     cache's format (``TinyLlama``), for every family alike. ``kv_scales`` ("fp8" only): None (scale 1: ``k_scale`` /
     ``v_scale`` tensors a checkpoint may carry are then not read), a ``KvScales``, or "checkpoint": the per-layer
@@ -360,7 +361,8 @@ def load_llama(path: str, device="cuda", max_batch: int = 8, max_seq: int | None
     the stacks as MXFP4 nibble bytes with e8m0 block scales, quantised layer by layer in the same place. ``chunk_attn``: ``TinyLlama``'s
     (docs/CHUNK_ATTN.md). ``sliding_window``: serve the
     checkpoint's sliding attention window (``read_config``, docs/SLIDING_WINDOW.md), fused step only; a checkpoint
-    that declares none is refused."""
+    that declares none is refused. ``loras``: name -> PEFT adapter directory (or a ``LoraAdapter``), at most 8, served
+    beside the base weights (``load_lora``, docs/LORA.md)."""
     from p2p_llm_tunnel_amd.models.tiny_llm import (EXPERT_DTYPES, WEIGHT_DTYPES, check_expert_scales, quantize_experts_,
                                                     quantize_layer_)
     if weight_dtype not in WEIGHT_DTYPES:
@@ -388,6 +390,8 @@ def load_llama(path: str, device="cuda", max_batch: int = 8, max_seq: int | None
     ops.as_expert_format(expert_dtype, cfg.moe, cfg.dim, cfg.ffn)  # a dense checkpoint, or shapes that do not block
     if expert_dtype != "bf16" and not fused:
         raise ValueError(f"{expert_dtype.upper()} experts run the fused step only: load with fused=True")
+    if loras:  # refused before any base weight is read
+        loras = {n: a if isinstance(a, LoraAdapter) else load_lora(a, cfg, weight_dtype, fused) for n, a in loras.items()}
     c = cfg
     rd = _Reader(path)
     dev = torch.device(device)
@@ -492,7 +496,84 @@ def load_llama(path: str, device="cuda", max_batch: int = 8, max_seq: int | None
         rd.close()
     return TinyLlama.from_weights(cfg, w, device=dev, max_batch=max_batch, fused=fused, kv_dtype=kv_dtype,
                                   weight_dtype=weight_dtype, kv_scales=kv_scales, chunk_attn=chunk_attn,
-                                  expert_dtype=expert_dtype)
+                                  expert_dtype=expert_dtype, **({"loras": loras} if loras else {}))
+
+
+LORA_MODULES = {"q_proj": "self_attn", "k_proj": "self_attn", "v_proj": "self_attn", "o_proj": "self_attn",
+                "gate_proj": "mlp", "up_proj": "mlp", "down_proj": "mlp"}  # PEFT target module -> its block
+
+
+class LoraAdapter:
+    """One PEFT LoRA adapter as ``load_lora`` read it: ``r``, ``scaling`` (``lora_alpha / r``, or ``/ sqrt(r)`` with
+    ``use_rslora``), ``modules`` (the target modules, sorted) and ``layers[L][module] = (lora_A [r, K], lora_B
+    [n, r])``, bf16 on the CPU. ``nbytes``: the bytes of those tensors."""
+
+    def __init__(self, r: int, scaling: float, modules: tuple, layers: list):
+        self.r, self.scaling, self.modules, self.layers = r, scaling, modules, layers
+        self.nbytes = sum(t.numel() * t.element_size() for L in layers for ab in L.values() for t in ab)
+
+
+def load_lora(path: str, cfg: LlamaConfig, weight_dtype: str = "bf16", fused: bool = True) -> LoraAdapter:
+    """A PEFT adapter directory (``adapter_config.json`` + ``adapter_model.safetensors``, read weights-only through
+    ``safetensors``) for a base model of ``cfg`` (docs/LORA.md). Target modules: any subset of ``LORA_MODULES``; a
+    module the adapter leaves out contributes nothing. Everything the kernels do not serve is refused with a message
+    that names the key."""
+    if cfg.n_experts:
+        raise ValueError("lora: adapters on an MoE model are not supported")
+    if cfg.qk_norm:
+        raise ValueError("lora: adapters on a QK-norm model (Qwen3) are not supported")
+    if weight_dtype != "bf16":
+        raise ValueError(f"lora: adapters need bf16 weights, not weight_dtype {weight_dtype!r}")
+    if not fused:
+        raise ValueError("lora: adapters run the fused step only (fused=True), not the eager or unfused path")
+    with open(os.path.join(path, "adapter_config.json")) as fh:
+        raw = json.load(fh)
+    if raw.get("peft_type", "LORA") != "LORA":
+        raise ValueError(f"lora: peft_type {raw.get('peft_type')!r} is not LORA")
+    for key in ("use_dora", "fan_in_fan_out"):
+        if raw.get(key):
+            raise ValueError(f"lora: {key} is not supported")
+    if raw.get("bias", "none") != "none":
+        raise ValueError(f"lora: bias {raw['bias']!r} is not supported (only \"none\")")
+    for key in ("modules_to_save", "rank_pattern", "alpha_pattern"):
+        if raw.get(key):
+            raise ValueError(f"lora: a non-empty {key} is not supported")
+    modules = raw.get("target_modules") or []
+    modules = (modules,) if isinstance(modules, str) else tuple(sorted(modules))
+    for m in modules:
+        if m not in LORA_MODULES:
+            raise ValueError(f"lora: target module {m!r} is not supported (only {', '.join(LORA_MODULES)})")
+    r = raw.get("r")
+    if isinstance(r, bool) or not isinstance(r, int) or not 1 <= r <= 64:
+        raise ValueError(f"lora: r must be an int in 1..64, got {r!r}")
+    alpha = float(raw.get("lora_alpha", r))
+    scaling = alpha / math.sqrt(r) if raw.get("use_rslora") else alpha / r
+    q, kv = cfg.n_heads * cfg.head_dim, cfg.n_kv_heads * cfg.head_dim
+    shapes = {"q_proj": (q, cfg.dim), "k_proj": (kv, cfg.dim), "v_proj": (kv, cfg.dim), "o_proj": (cfg.dim, q),
+              "gate_proj": (cfg.ffn, cfg.dim), "up_proj": (cfg.ffn, cfg.dim), "down_proj": (cfg.dim, cfg.ffn)}
+    from safetensors import safe_open
+    layers = []
+    with safe_open(os.path.join(path, "adapter_model.safetensors"), framework="pt", device="cpu") as f:
+        names = set(f.keys())
+        for i in range(cfg.n_layers):
+            layer = {}
+            for m in modules:
+                ab = []
+                for part, shape in (("lora_A", (r, shapes[m][1])), ("lora_B", (shapes[m][0], r))):
+                    name = f"base_model.model.model.layers.{i}.{LORA_MODULES[m]}.{m}.{part}.weight"
+                    if name not in names:
+                        raise KeyError(f"lora: the adapter has no tensor {name!r}")
+                    t = f.get_tensor(name)
+                    if tuple(t.shape) != shape:
+                        raise ValueError(f"lora: {name} has shape {tuple(t.shape)}, which does not match the base "
+                                         f"model ({shape})")
+                    names.discard(name)
+                    ab.append(t.to(torch.bfloat16))
+                layer[m] = tuple(ab)
+            layers.append(layer)
+        if names:
+            raise ValueError(f"lora: the adapter has a tensor the base model has no place for: {sorted(names)[0]!r}")
+    return LoraAdapter(r, scaling, modules, layers)
 
 
 class Detokenizer:

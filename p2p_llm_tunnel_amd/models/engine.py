@@ -35,7 +35,8 @@ class Request:
 
     def __init__(self, prompt_ids: list[int], max_new: int, batched: bool = False, sampling: Sampling | None = None,
                  logprobs: int | None = None, embed: str | None = None, penalties: Penalties | None = None,
-                 guide=None):
+                 guide=None, adapter: str | None = None):
+        self.adapter = adapter  # the name of a LoRA adapter the engine was built with (docs/LORA.md); None: the base
         if embed not in (None, "mean", "last"):
             raise ValueError(f'embed must be None, "mean" or "last", got {embed!r}')
         if guide is not None:
@@ -441,14 +442,17 @@ class Engine:
     def __init__(self, device="cuda:0", config="tiny", max_batch=8, seed=0, use_graph=True, rows=64, model=None,
                  small_rows=16, prefix_cache=False, prefix_min=16, penalties=False, kv_dtype="bf16",
                  guided=False, guided_states=1024, weight_dtype="bf16", kv_scales=None, min_p=False,
-                 chunk_attn=False, expert_dtype="bf16"):
+                 chunk_attn=False, expert_dtype="bf16", loras=None):
         if kv_scales is not None and kv_dtype != "fp8" and getattr(model, "kv_dtype", "bf16") != "fp8":
             raise ValueError("kv_scales need kv_dtype='fp8' (--kv-dtype fp8): a bf16 KV cache has no scales")
         if model is None:
             from p2p_llm_tunnel_amd.models.tiny_llm import TinyLlama
             model = TinyLlama(config, device=device, max_batch=max_batch, seed=seed, fused=True, kv_dtype=kv_dtype,
                               weight_dtype=weight_dtype, kv_scales=kv_scales, chunk_attn=bool(chunk_attn),
-                              **({"expert_dtype": expert_dtype} if expert_dtype != "bf16" else {}))
+                              **({"expert_dtype": expert_dtype} if expert_dtype != "bf16" else {}),
+                              **({"loras": loras} if loras else {}))
+        elif loras and tuple(getattr(model, "lora_names", ())) != tuple(loras):
+            raise ValueError("loras given, but the injected model was built with other adapters or none")
         elif expert_dtype != "bf16" and getattr(model, "expert_dtype", "bf16") != expert_dtype:
             raise ValueError(f"expert_dtype={expert_dtype!r}, but the injected model was built with "
                              f"{getattr(model, 'expert_dtype', 'bf16')!r} experts")
@@ -490,7 +494,8 @@ class Engine:
                          (min_p, "min_p needs"), (getattr(model, "chunk_attn", False), "chunk_attn needs"),
                          (getattr(model, "expert_dtype", "bf16") != "bf16",
                           f"{getattr(model, 'expert_dtype', 'bf16')} experts need"),
-                         (bool(getattr(getattr(model, "cfg", None), "n_experts", 0)), "an MoE model needs")):
+                         (bool(getattr(getattr(model, "cfg", None), "n_experts", 0)), "an MoE model needs"),
+                         (bool(getattr(model, "lora_names", ())), "LoRA adapters need")):
             if on and not use_graph:
                 raise ValueError(f"{what} the graph-captured HIP step; this engine runs eagerly")
         self.penalties = bool(penalties)
@@ -500,6 +505,10 @@ class Engine:
         self.chunk_attn = bool(getattr(model, "chunk_attn", False))
         self._smp, self._lp, self._pen_rows = _layout(self.min_p)
         in_rows = self._pen_rows.stop if self.penalties else self._lp + 1
+        # LoRA adapters (docs/LORA.md): each row's adapter index travels in one more staging row, after every other.
+        self.lora_names = tuple(getattr(model, "lora_names", ()))
+        self._aid = in_rows if self.lora_names else None
+        in_rows += bool(self.lora_names)
         self._bufs = {R: [_StepBuf(R, cuda, lp_dev, in_rows), _StepBuf(R, cuda, lp_dev, in_rows)] for R in sizes}
         self._d_in = {R: torch.zeros((in_rows, R), dtype=torch.int64, device=self.device) for R in sizes}
         cfg = model.cfg
@@ -516,6 +525,10 @@ class Engine:
                           for need in range(16)]
         self._graphs = {(R, par, post): self._capture(self._bufs[R][par], 0 if R == small_rows else max_batch, post)
                         for R in sizes if use_graph for par in (0, 1) for post in self._posts}
+        # With adapters one more set, whose steps run the LoRA kernels: replayed only when some row names an adapter.
+        self._lora_graphs = {(R, par, post): self._capture(self._bufs[R][par], 0 if R == small_rows else max_batch,
+                                                           post, lora=True)
+                             for R in sizes if self.lora_names for par in (0, 1) for post in self._posts}
         self.max_batch = max_batch
         self.pending: queue.Queue = queue.Queue()
         self.slots: list[dict | None] = [None] * max_batch
@@ -537,6 +550,7 @@ class Engine:
         # freed), whether the slot was busy at the last admission pass, and the pass-ordered tick at which it was seen
         # free (least recently freed = smallest).
         self._kv: list[dict | None] = [None] * max_batch
+        self._slot_aid = [-1] * max_batch  # the adapter index of the request that last took each slot (-1: the base)
         self._was_busy = [False] * max_batch
         self._freed = [0] * max_batch
         self._tick = 0
@@ -555,6 +569,8 @@ class Engine:
             raise ValueError(f"logit_bias ids must be in [0, {self.model.cfg.vocab})")
         if req.sampling.min_p > 0.0 and not self.min_p:
             raise ValueError("min_p needs an engine built with min_p=True (--min-p) on the graph-captured HIP step")
+        if req.adapter is not None and req.adapter not in self.lora_names:
+            raise ValueError(f"adapter {req.adapter!r} is none of the engine's ({', '.join(self.lora_names) or 'none'})")
         if req.guide is not None:
             if self._gd is None:
                 raise ValueError("a guide needs an engine built with guided=True (--guided) on the graph-captured "
@@ -608,6 +624,8 @@ class Engine:
         for i, s in enumerate(self._kv):
             if s is None or req.embed is not None:  # an embed request pools every row: it takes no prefix
                 continue
+            if s["req"].adapter != req.adapter:  # a slot's rows belong to the adapter that wrote them
+                continue
             n = min(_common_prefix(ids, self._resident(s)), len(ids) - 1)
             if n >= self.prefix_min and (n > m or (n == m and self.slots[i] is None and self.slots[src] is not None)):
                 m, src = n, i
@@ -643,6 +661,7 @@ class Engine:
             if src is not None:
                 jobs.append((src, slot, m))
             self.slots[slot] = s = {"req": req, "pos": m, "ids": ids, "gen": 0, "embed": req.embed}
+            self._slot_aid[slot] = self.lora_names.index(req.adapter) if req.adapter is not None else -1
             if self.prefix_cache:  # the slot's residency (``_resident``): ``_drain`` adds the outputs to ``known``
                 s["known"] = list(ids)
                 self._kv[slot] = req.kv = s
@@ -734,7 +753,7 @@ class Engine:
         return rows, emits
 
     def _step_body(self, b: _StepBuf, n: int, run, sample_rows: int = 0, logprobs: bool = False,
-                   penalize: bool = False, guide: bool = False):
+                   penalize: bool = False, guide: bool = False, lora: bool = False):
         """One step on the first ``n`` rows of ``b``: staging -> device, decode
         rows' tokens gathered from ``last``, the model through ``run(tokens, pos,
         slots) -> (ids, logits)``, the stages of ``_posts`` that the flags name
@@ -744,7 +763,11 @@ class Engine:
         din.copy_(b.h_in, non_blocking=True)
         d = din[:, :n]
         tok = torch.where(d[_DEC] != 0, self._d_last[d[_SLOT]], d[_TOK])
-        ids, logits = run(tok, d[_POS].to(torch.int32), d[_SLOT].to(torch.int32))
+        if lora:
+            ids, logits = run(tok, d[_POS].to(torch.int32), d[_SLOT].to(torch.int32),
+                              adapters=d[self._aid].to(torch.int32))
+        else:
+            ids, logits = run(tok, d[_POS].to(torch.int32), d[_SLOT].to(torch.int32))
         if sample_rows:
             from p2p_llm_tunnel_amd import ops
             drawn = logits[:sample_rows]
@@ -764,17 +787,19 @@ class Engine:
         self._d_last.index_copy_(0, d[_REC], ids)
         b.h_out[:n].copy_(ids, non_blocking=True)
 
-    def _capture(self, b: _StepBuf, emit_rows: int, post: int):
+    def _capture(self, b: _StepBuf, emit_rows: int, post: int, lora: bool = False):
         """The step on all of ``b``'s rows through ``step_rows``, as a hipGraph;
         ``post``: what follows the fused step (see ``_posts``)."""
         from p2p_llm_tunnel_amd.models.tiny_llm import capture
         b.np[:] = 0
         b.np[_SLOT, :] = b.np[_REC, :] = self.model.scratch_slot  # warm-up and capture touch the scratch slot only
+        if lora:
+            b.np[self._aid, :] = -1
         run = functools.partial(self.model.step_rows, emit_rows=emit_rows)
         st = self._posts[post]
         sample_rows = (emit_rows or b.rows) if st & _SAMPLE else 0
         graph, _ = capture(lambda: self._step_body(b, b.rows, run, sample_rows, bool(st & _LOGPROBS),
-                                                   bool(st & _PENALIZE), bool(st & _GUIDE)), self.device)
+                                                   bool(st & _PENALIZE), bool(st & _GUIDE), lora), self.device)
         torch.cuda.synchronize(self.device)
         return graph
 
@@ -813,8 +838,13 @@ class Engine:
             h[_TOK, n:R] = h[_POS, n:R] = h[_DEC, n:R] = 0
             h[_SLOT, n:R] = h[_REC, n:R] = scratch
         b.n, b.emits = n, emits
+        lora = False
+        if self._aid is not None:
+            h[self._aid, :] = -1
+            h[self._aid, :n] = aid = [self._slot_aid[r.slot] for r in rows]
+            lora = max(aid) >= 0
         if self.use_graph:
-            self._graphs[(R, par, self._post_for[need])].replay()
+            (self._lora_graphs if lora else self._graphs)[(R, par, self._post_for[need])].replay()
         else:  # injected model (tests): the same step, eagerly, on its n rows; no sampler
             rng = (min(r.pos for r in rows), max(r.pos for r in rows))
             self._step_body(b, n, lambda tok, pos, slots: (

@@ -246,6 +246,18 @@ _LEGACY_MAX_LOGPROBS = 5  # /v1/completions: the OpenAI API's limit for the lega
 _LOGPROB_KEYS = ("logprobs", "top_logprobs")
 
 
+def adapter_param(body: dict, lora_names) -> str | None:
+    """The LoRA adapter a request runs under (docs/LORA.md): its "model" when that equals one of the configured
+    adapter names, on every route alike; any other value, a missing one included, is the base model as before."""
+    m = body.get("model")
+    return m if isinstance(m, str) and m in tuple(lora_names) else None
+
+
+def model_names(base: str, lora_names) -> list:
+    """What /v1/models and /api/tags list: the base model, then the adapters in their order."""
+    return [base] + [n for n in lora_names if n != base]
+
+
 def logprob_params(body: dict, kind: str) -> int | None:
     """How many top log-probabilities a request wants beside each chosen
     token's own: None = no logprobs at all, N in 0..20 = the chosen token's plus

@@ -146,9 +146,9 @@ import uuid
 # names stay importable from here.
 from p2p_llm_tunnel_amd.models.engine import Engine, Request
 from p2p_llm_tunnel_amd.models.params import (_LOGPROB_KEYS, Penalties, Sampling, SamplingError,  # noqa: F401
-                                              StopMatcher, chat_logprob_entry, chat_logprobs, completion_logprobs,
-                                              guided_params, logprob_params, penalty_params, sampling_params,
-                                              stop_sequences)
+                                              StopMatcher, adapter_param, chat_logprob_entry, chat_logprobs,
+                                              completion_logprobs, guided_params, logprob_params, model_names,
+                                              penalty_params, sampling_params, stop_sequences)
 
 
 def chat_template_kwargs(body: dict) -> dict | None:
@@ -687,14 +687,15 @@ class FrontEnd:
 
     async def _dispatch(self, method, path, body, writer, reader=None) -> bool:
         name = self.model_name
+        names = model_names(name, getattr(self.engine, "lora_names", ()))  # the base, then the adapters
         if method in ("GET", "HEAD"):
             if path in ("/v1/models", "/models"):
                 resp = self._json_response({"object": "list", "data": [
-                    {"id": name, "object": "model", "owned_by": "p2p_llm_tunnel_amd"}]})
+                    {"id": n, "object": "model", "owned_by": "p2p_llm_tunnel_amd"} for n in names]})
             elif path == "/health":
                 resp = self._response(200, "text/plain", b"ok")
             elif path == "/api/tags":
-                resp = self._json_response({"models": [{"name": name, "model": name}]})
+                resp = self._json_response({"models": [{"name": n, "model": n} for n in names]})
             else:
                 resp = self._json_response({"error": "not found"}, 404)
             if method == "HEAD":
@@ -713,6 +714,7 @@ class FrontEnd:
                 req_body = {}
         except ValueError:
             req_body = {}
+        adapter = adapter_param(req_body, getattr(self.engine, "lora_names", ()))
         raw_max = req_body.get("max_tokens", req_body.get("num_predict", 16))
         if path == "/api/chat":
             try:
@@ -765,7 +767,7 @@ class FrontEnd:
         rid = ("chatcmpl-" if kind == "chat" else "cmpl-") + uuid.uuid4().hex[:12]
         prompt = _prompt_ids(req_body, self.tok, template_kwargs)
         req = Request(prompt, max(1, min(max_new, 1024)), batched=True, sampling=sampling, logprobs=logprobs,
-                      penalties=penalties, guide=guide)
+                      penalties=penalties, guide=guide, adapter=adapter)
         st = _Stream(writer, stream, kind, rid, name, self.tok.detokenizer(prompt) if self.tok is not None else None,
                      StopMatcher(stops) if stops else None, logprobs is not None)
         req.state = st
@@ -783,7 +785,7 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
                  embed_pooling: str = "mean", penalties: bool = False, kv_dtype: str = "bf16",
                  guided: bool = False, guided_states: int = 1024, weight_dtype: str = "bf16", kv_scales=None,
                  sliding_window: bool = False, min_p: bool = False, chunk_attn: bool = False,
-                 expert_dtype: str = "bf16"):
+                 expert_dtype: str = "bf16", loras: dict | None = None):
     """Engine + HTTP front-end; returns (server, port, engine). ``server.shutdown()``
     stops the HTTP side, ``engine.stop()`` the GPU side. ``checkpoint``: serve a
     Hugging Face Llama checkpoint directory (weights + tokenizer) instead of
@@ -812,8 +814,13 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
     ``k_attn_chunk``; an injected engine's model must have been built with it.
     ``expert_dtype`` ("bf16", "fp8": docs/MOE_FP8.md, or "mxfp4": docs/MOE_MXFP4.md) is ``Engine``'s and
     ``load_llama``'s: the format of an MoE model's stacked expert matrices alone; a dense model refuses "fp8" and
-    "mxfp4", and an injected engine's model must have it."""
+    "mxfp4", and an injected engine's model must have it.
+    ``loras`` (docs/LORA.md): name -> PEFT adapter directory, at most 8, served beside the base model; a request
+    whose "model" is one of the names runs under that adapter. Refused with an injected engine."""
     expert_dtype = parse_expert_dtype(expert_dtype)
+    loras = check_loras(loras)
+    if loras and engine is not None:
+        raise ValueError("loras: an injected engine brings its own adapters (Engine(loras=))")
     if engine is not None and getattr(engine.model, "expert_dtype", "bf16") != expert_dtype:
         raise ValueError(f"expert_dtype={expert_dtype!r}, but the injected engine's model has "
                          f"{getattr(engine.model, 'expert_dtype', 'bf16')!r} experts")
@@ -852,13 +859,18 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
         from p2p_llm_tunnel_amd.models.checkpoint import Tokenizer, load_llama
         model = load_llama(checkpoint, device=device, max_batch=max_batch, max_seq=max_seq, kv_dtype=kv_dtype,
                            weight_dtype=weight_dtype, kv_scales=kv_scales, sliding_window=sliding_window,
-                           chunk_attn=chunk_attn, expert_dtype=expert_dtype)
+                           chunk_attn=chunk_attn, expert_dtype=expert_dtype, loras=loras)
         tok = tok or Tokenizer.for_checkpoint(checkpoint)
         engine = Engine(device=device, max_batch=max_batch, model=model, prefix_cache=prefix_cache,
                         prefix_min=prefix_min, penalties=penalties, guided=guided, guided_states=guided_states,
                         min_p=min_p)
         model_name = model_name or os.path.basename(os.path.normpath(checkpoint))
-    engine = engine or Engine(device=device, config=config, max_batch=max_batch, prefix_cache=prefix_cache,
+    if loras and engine is None:  # a random-init config: the adapters are read against its shapes
+        from p2p_llm_tunnel_amd.models.checkpoint import load_lora
+        from p2p_llm_tunnel_amd.models.tiny_llm import CONFIGS
+        cfg = CONFIGS[config] if isinstance(config, str) else config
+        loras = {n: load_lora(d, cfg, weight_dtype) for n, d in loras.items()}
+    engine = engine or Engine(device=device, config=config, **({"loras": loras} if loras else {}), max_batch=max_batch, prefix_cache=prefix_cache,
                               prefix_min=prefix_min, penalties=penalties, kv_dtype=kv_dtype, guided=guided,
                               guided_states=guided_states, weight_dtype=weight_dtype, kv_scales=kv_scales,
                               min_p=min_p, chunk_attn=chunk_attn, expert_dtype=expert_dtype)
@@ -868,6 +880,31 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
 
 
 KV_DTYPE_CHOICES = ("bf16", "fp8")
+
+
+def check_loras(loras) -> dict | None:
+    """--lora NAME=DIR (repeatable) / ``start_server(loras=)``: a dict name -> directory, or the list of NAME=DIR
+    strings; at most ``ops.LORA_MAX_ADAPTERS``, names unique and non-empty. None or empty: no adapters."""
+    if not loras:
+        return None
+    if not isinstance(loras, dict):
+        pairs = [str(x).partition("=") for x in loras]
+        for n, eq, d in pairs:
+            if not n or not eq or not d:
+                raise ValueError(f"--lora takes NAME=DIR, got {n + eq + d!r}")
+        if len({n for n, _, _ in pairs}) != len(pairs):
+            raise ValueError("--lora: adapter names must be unique")
+        loras = {n: d for n, _, d in pairs}
+    from p2p_llm_tunnel_amd.ops import LORA_MAX_ADAPTERS
+    if len(loras) > LORA_MAX_ADAPTERS:
+        raise ValueError(f"--lora: at most {LORA_MAX_ADAPTERS} adapters, got {len(loras)}")
+    return dict(loras)
+
+
+def lora_lines(model) -> list:
+    """What the server logs per adapter at start: rank, modules and bytes."""
+    return [f"lora {n}: r {a.r}, modules {','.join(a.modules)}, {a.nbytes} bytes"
+            for n, a in (getattr(model, "loras", None) or {}).items()]
 
 
 def parse_kv_dtype(v) -> str:
@@ -986,6 +1023,8 @@ def replica_cmd(a, i: int) -> list[str]:
         cmd += ["--chunk-attn"]
     if getattr(a, "expert_dtype", "bf16") != "bf16":
         cmd += ["--expert-dtype", a.expert_dtype]
+    for spec in getattr(a, "lora", None) or ():
+        cmd += ["--lora", spec]
     return cmd
 
 
@@ -1093,6 +1132,11 @@ def arg_parser() -> argparse.ArgumentParser:
                          "a prompt row's attention then sums in an order that depends on the rows it shares a tile "
                          "with, so batching can change its last fp32 bits. Decode-only steps are untouched and the "
                          "number of captured graphs stays (docs/CHUNK_ATTN.md)")
+    ap.add_argument("--lora", action="append", default=None, metavar="NAME=DIR",
+                    help="serve the PEFT LoRA adapter in DIR (adapter_config.json, adapter_model.safetensors) beside "
+                         "the base model; repeatable, at most 8. A request whose model is NAME runs under it, batched "
+                         "with requests for the base and for other adapters. Dense bf16 models without QK-norm only; "
+                         "costs the adapter tables and a second set of captured graphs (docs/LORA.md)")
     ap.add_argument("--guided", action="store_true",
                     help="guided decoding on the device: /v1/chat/completions and /v1/completions act on "
                          "guided_regex, guided_choice and structured_outputs {regex | choice} (a checkpoint with a "
@@ -1118,7 +1162,9 @@ def main(argv=None):
                                      embed_pooling=a.embed_pooling, penalties=a.penalties, kv_dtype=a.kv_dtype,
                                      guided=a.guided, guided_states=a.guided_states, weight_dtype=a.weight_dtype,
                                      kv_scales=a.kv_scales, sliding_window=a.sliding_window, min_p=a.min_p,
-                                     chunk_attn=a.chunk_attn, expert_dtype=a.expert_dtype)
+                                     chunk_attn=a.chunk_attn, expert_dtype=a.expert_dtype, loras=a.lora)
+    for line in lora_lines(engine.model):
+        print(line, flush=True)
     print(weights_line(engine.model, a.weight_dtype), flush=True)
     print(kv_cache_line(engine.model, a.kv_dtype), flush=True)
     if a.sliding_window:

@@ -251,8 +251,11 @@ class TinyLlama:
     def __init__(self, cfg: LlamaConfig | str = "tiny", device="cuda", max_batch: int = 8, seed: int = 0,
                  fused: bool = True, weights: dict | None = None, kv_dtype: str = "bf16",
                  weight_dtype: str = "bf16", kv_scales: KvScales | None = None, chunk_attn: bool = False,
-                 expert_dtype: str = "bf16"):
-        """``expert_dtype`` ("bf16", the default, "fp8" or "mxfp4"; MoE models and the fused step only;
+                 expert_dtype: str = "bf16", loras: dict | None = None):
+        """``loras`` (docs/LORA.md): name -> LoRA adapter (``checkpoint.load_lora``'s ``LoraAdapter``), at most 8, served
+        beside the base weights by the fused step: ``step_rows(.., adapters=)`` names each row's adapter by its index
+        in ``lora_names``, -1 for none. Dense bf16 models without QK-norm and the fused step only.
+        ``expert_dtype`` ("bf16", the default, "fp8" or "mxfp4"; MoE models and the fused step only;
         docs/MOE_FP8.md, docs/MOE_MXFP4.md). "mxfp4": the stacked expert matrices as OCP MXFP4 (e2m1 nibbles in blocks
         of 32 with an e8m0 scale, round to nearest, nothing calibrated), quantised here layer by layer, or brought by
         ``weights`` as ``w_gate_up_q`` / ``w_gate_up_e`` / ``w_down_q`` / ``w_down_e`` (uint8 ``[E, N, K / 2]`` and
@@ -324,6 +327,14 @@ class TinyLlama:
             raise ValueError("chunk_attn runs the fused step only (fused=True): the unfused path has no chunk "
                              "attention kernel")
         self.chunk_attn = chunk_attn
+        self.loras = dict(loras) if loras else None
+        self.lora_names = tuple(self.loras) if self.loras else ()
+        if self.loras:
+            if len(self.loras) > ops.LORA_MAX_ADAPTERS:
+                raise ValueError(f"lora: at most {ops.LORA_MAX_ADAPTERS} adapters, got {len(self.loras)}")
+            if self.cfg.n_experts or self.cfg.qk_norm or weight_dtype != "bf16" or not fused:
+                raise ValueError("lora: adapters need a dense bf16 model without QK-norm on the fused step (no MoE, no "
+                                 "weight_dtype, fused=True)")
         self._experts_blocked = False  # FP8 / MXFP4 experts: fused_weights() has put their bytes into the device order
         self.lm_head_q = self.lm_head_s = None  # weight_dtype "fp8": the LM head's bytes and row scales
         self.fused = fused
@@ -411,9 +422,10 @@ class TinyLlama:
     @classmethod
     def from_weights(cls, cfg: LlamaConfig, weights: dict, device="cuda", max_batch: int = 8, fused: bool = True,
                      kv_dtype: str = "bf16", weight_dtype: str = "bf16", kv_scales: KvScales | None = None,
-                     chunk_attn: bool = False, expert_dtype: str = "bf16"):
+                     chunk_attn: bool = False, expert_dtype: str = "bf16", loras: dict | None = None):
         return cls(cfg, device=device, max_batch=max_batch, fused=fused, weights=weights, kv_dtype=kv_dtype,
-                   weight_dtype=weight_dtype, kv_scales=kv_scales, chunk_attn=chunk_attn, expert_dtype=expert_dtype)
+                   weight_dtype=weight_dtype, kv_scales=kv_scales, chunk_attn=chunk_attn, expert_dtype=expert_dtype,
+                   loras=loras)
 
     def _quantize_weights(self):
         """``weight_dtype`` "fp8": every layer's GEMM weights and the LM head to e4m3 + row scales, one tensor at
@@ -601,6 +613,24 @@ class TinyLlama:
         """The fused step's dims of this model: one cache slot per sequence and the scratch slot."""
         return llama_dims(self.cfg, self.max_batch + 1, self.kv_dtype == "fp8")
 
+    def lora_tables(self) -> list:
+        """The adapters as ``ops.FusedLlamaDecoder(lora=)`` takes them: per layer and projection every adapter's
+        ``ops.pack_lora`` tables, with this model's norm weights folded in, stacked in ``lora_names``' order and padded
+        to the widest adapter's rank."""
+        out = []
+        for L in self.layers:
+            layer = {}
+            for name, parts in ops.LORA_PARTS.items():
+                R = max(ops.lora_rank(*[a.r if m in a.modules else 0 for m in parts]) for a in self.loras.values())
+                packed = []
+                for a, src in ((a, a.layers[len(out)]) for a in self.loras.values()):
+                    ab = [src.get(m, (None, None)) for m in parts]
+                    packed.append(ops.pack_lora(self.cfg, name, [x[0] for x in ab], [x[1] for x in ab], a.scaling,
+                                                L.get(FOLDED_NORM.get(name)), rank=R))
+                layer[name] = tuple(torch.stack([p[j].to(self.device) for p in packed]).contiguous() for j in (0, 1))
+            out.append(layer)
+        return out
+
     def fused_decoder(self) -> ops.FusedLlamaDecoder:
         if self._fused is None:
             self._fused = ops.FusedLlamaDecoder(self.dims(), self.fused_weights(), self.k_cache, self.v_cache,
@@ -611,10 +641,11 @@ class TinyLlama:
                                                 **({"chunk_attn": True} if self.chunk_attn else {}),
                                                 **({"moe": self.cfg.moe} if self.cfg.n_experts else {}),
                                                 **({"expert_format": self.expert_dtype}
-                                                   if self.expert_dtype != "bf16" else {}))
+                                                   if self.expert_dtype != "bf16" else {}),
+                                                **({"lora": self.lora_tables()} if self.loras else {}))
         return self._fused
 
-    def step_rows(self, tokens, pos, slots=None, emit_rows=0, pos_range=None):
+    def step_rows(self, tokens, pos, slots=None, emit_rows=0, pos_range=None, adapters=None):
         """``decode_step`` without host validation (the fused path: without host
         sync either, so capturable); returns (ids, logits). ``pos_range``: (min,
         max) of ``pos`` for the unfused kernels' bounds check and attention
@@ -625,8 +656,11 @@ class TinyLlama:
             slots = slots.contiguous() if slots is not None else None
             logits = torch.empty(B, self.cfg.vocab, dtype=torch.bfloat16, device=self.device)
             ids = torch.empty(B, dtype=torch.int64, device=self.device)
-            self.fused_decoder().step(tokens, pos, logits, ids, slots, emit_rows)
+            self.fused_decoder().step(tokens, pos, logits, ids, slots, emit_rows,
+                                      **({} if adapters is None else {"adapters": adapters.contiguous()}))
             return ids, logits
+        if adapters is not None:
+            raise ValueError(f"adapters run the fused step only (at most {ops.MAX_ROWS} rows, fused=True)")
         if self.kv_dtype != "bf16":
             raise ValueError(f"an {self.kv_dtype} KV cache runs the fused step only (at most {ops.MAX_ROWS} rows, "
                              "fused=True): the unfused kernels read and write bf16 caches")

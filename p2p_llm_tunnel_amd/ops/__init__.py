@@ -151,6 +151,17 @@ class ExpertFormat(ctypes.Structure):
         return f"ExpertFormat(w8={self.w8})"
 
 
+class LoraPlan(ctypes.Structure):
+    """decode_lora.h's LoraPlan: what ``k_lora_delta`` launches for one projection (docs/LORA.md)."""
+    _fields_ = [(n, _INT) for n in ("grid_x", "grid_y", "waves", "cols", "passes")]
+
+
+class LoraTable(ctypes.Structure):
+    """decode_fused.hip's LoraTable: the adapters of a decoder. ``rank``: the padded R of wqkv, wo, w_gate_up, w_down;
+    ``tables``: per layer eight device pointers, A' then B' of each of the four."""
+    _fields_ = [("n_adapters", _INT), ("rank", _INT * 4), ("tables", ctypes.POINTER(ctypes.c_void_p))]
+
+
 EXPERT_FORMATS = {"bf16": 0, "fp8": 1, "mxfp4": 2}  # expert dtype -> ExpertFormat.w8
 EXPERT_BLOCK = 64  # K elements per block of the FP8 experts' byte order: a pair of k-steps
 EXPERT_QUAD = 128  # K elements per block of the MXFP4 experts' byte order: a quad of k-steps, 64 nibble bytes
@@ -339,6 +350,15 @@ def _signatures() -> dict:
                                       ef],
         "p2pt_moe_ffn_experts": [vp, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, f, vp, ef, vp, vp],
         "p2pt_moe_ffn_mxfp4": [vp, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, f, vp, vp, vp],
+        "p2pt_lora_delta": [vp, vp, vp, vp, vp, i, i, i, i, i, vp],
+        "p2pt_lora_plan": [i, i, i, i, i, ptr(LoraPlan)],
+        "p2pt_lora_max_adapters": [],
+        "p2pt_lora_max_rank": [],
+        "p2pt_llama_ws_bytes_lora": [dims],
+        "p2pt_llama_ws_layout_lora": [dims, szp, szp, i],
+        "p2pt_llama_plan_kernels_lora": [dims, i, i, ip, i, ptr(LoraTable)],
+        "p2pt_llama_decode_lora": [dims, vp, ip, ptr(vp), vp, vp, vp, vp, vp, i, i, vp, sz, vp, vp, vp, i,
+                                   ptr(LoraTable), vp],
         "p2pt_attn_span": [i, i],
         "p2pt_max_rows": [],
         "p2pt_skinny_bench": [vp, vp, vp, i, i, i, i, i, i, vp],  # microbenchmark hooks (scripts/bench_skinny.py)
@@ -347,7 +367,7 @@ def _signatures() -> dict:
 
 
 _RESTYPES = {"p2pt_llama_ws_bytes": ctypes.c_size_t, "p2pt_llama_ws_bytes_moe": ctypes.c_size_t,
-             "p2pt_llama_ws_bytes_fmt": ctypes.c_size_t}
+             "p2pt_llama_ws_bytes_fmt": ctypes.c_size_t, "p2pt_llama_ws_bytes_lora": ctypes.c_size_t}
 
 
 def lib() -> ctypes.CDLL:
@@ -373,6 +393,9 @@ def lib() -> ctypes.CDLL:
         if _LIB.p2pt_max_logit_bias() != MAX_LOGIT_BIAS:
             raise RuntimeError(f"MAX_LOGIT_BIAS = {MAX_LOGIT_BIAS}, but {path} was built for "
                                f"{_LIB.p2pt_max_logit_bias()} entries")
+        if (_LIB.p2pt_lora_max_adapters(), _LIB.p2pt_lora_max_rank()) != (LORA_MAX_ADAPTERS, LORA_MAX_RANK):
+            raise RuntimeError(f"LORA_MAX_ADAPTERS, LORA_MAX_RANK = {LORA_MAX_ADAPTERS}, {LORA_MAX_RANK}, but {path} "
+                               f"was built for {_LIB.p2pt_lora_max_adapters()}, {_LIB.p2pt_lora_max_rank()}")
     return _LIB
 
 
@@ -390,6 +413,12 @@ W4G_GROUP = 128  # K elements per group of an int4 weight: one scale and zero po
 W4G_ZERO_MAX = 16  # the largest zero point a group word may carry (GPTQ v1 stores z - 1 in a nibble)
 E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)  # the magnitudes of an e2m1 nibble's low three bits; bit 3: sign
 MAX_TOP_LOGPROBS = 20  # top (id, logprob) pairs per row of logprobs_ (logprobs.hip's kMaxTop; the OpenAI API's limit)
+LORA_MAX_ADAPTERS = 8  # adapters beside one base model (decode_lora.h's kMaxAdapters)
+LORA_MAX_RANK = 192  # padded rank R of one projection: three stacked parts of PEFT rank <= 64 (kMaxRank)
+LORA_MODULE_MAX_RANK = 64  # PEFT r of one target module
+# A fused projection's PEFT target modules, in the order their parts are stacked in A' and B' (docs/LORA.md).
+LORA_PARTS = {"wqkv": ("q_proj", "k_proj", "v_proj"), "wo": ("o_proj",), "w_gate_up": ("gate_proj", "up_proj"),
+              "w_down": ("down_proj",)}
 
 
 def step_plan(dims: LlamaDims, B: int, emit_rows: int = 0, weight_format=None) -> StepPlan:
@@ -479,18 +508,28 @@ def moe_plan(dims: LlamaDims, moe: MoeDims, B: int) -> MoePlan:
 
 def plan_kernels_ok(dims: LlamaDims, B: int, emit_rows: int = 0, weight_fp8: bool = False, windows=None,
                     weight_format=None, chunk_attn: bool = False, moe: MoeDims | None = None,
-                    expert_format=None) -> bool:
+                    expert_format=None, lora=None) -> bool:
     """Whether every stage of ``step_plan(dims, B, emit_rows)``, ``kv_plan(dims)`` and
     ``weight_plan(dims, weight_fp8)`` names a kernel the library instantiates, by the lookups its launchers use
     (host only). ``windows``: the per-layer sliding windows (``check_windows``); every layer's ``window_plan`` is
     then looked up too. ``weight_format`` (see ``as_weight_format``): the formats instead of ``weight_fp8``.
     ``chunk_attn``: the layers that then run ``k_attn_chunk`` (``chunk_plan``) are looked up as that.
     ``expert_format`` (``as_expert_format``; with ``moe`` only): the experts' format, whose ``k_moe_gate_up`` /
-    ``k_moe_down`` instantiations are then the ones looked up."""
+    ``k_moe_down`` instantiations are then the ones looked up.
+    ``lora`` (docs/LORA.md): the padded ranks of wqkv, wo, w_gate_up and w_down (``lora_rank``); the four layer stages
+    are then looked up as their LoRA-delta variants, which exist for bf16 dense models without QK-norm."""
     windows = check_windows(windows, dims.n_layers)
     moe = check_moe(moe, dims.dim, dims.ffn)
     experts = as_expert_format(expert_format, moe, dims.dim, dims.ffn)
-    if moe is not None and experts.w8:
+    if lora is not None:
+        f = as_weight_format(weight_fp8, weight_format)
+        if moe is not None or (f.layers, f.lm_head) != (0, 0) or dims.qk_norm:
+            raise ValueError("LoRA adapters need a dense bf16 model without QK-norm")
+        table = LoraTable(n_adapters=1, rank=(_INT * 4)(*lora))
+        rc = lib().p2pt_llama_plan_kernels_lora(
+            ctypes.byref(dims), B, emit_rows, (ctypes.c_int * len(windows))(*windows) if windows is not None else None,
+            int(chunk_attn), ctypes.byref(table))
+    elif moe is not None and experts.w8:
         f = as_weight_format(weight_fp8, weight_format)
         rc = lib().p2pt_llama_plan_kernels_experts(
             ctypes.byref(dims), B, emit_rows, ctypes.byref(f),
@@ -1666,6 +1705,173 @@ def dequantize_weight_w4g(q: torch.Tensor, z: torch.Tensor, s: torch.Tensor) -> 
     return (d * s.float().repeat_interleave(W4G_GROUP, 1)).to(torch.bfloat16)
 
 
+# ------------------------------------------------------------ LoRA adapters (docs/LORA.md)
+def lora_rank(*ranks: int) -> int:
+    """The padded rank R of a projection whose stacked parts have PEFT ranks ``ranks`` (0: the adapter leaves the
+    module out): their sum rounded up to a whole 16-rank MFMA tile, 16 at least."""
+    for r in ranks:
+        if not _int_in(r, 0, LORA_MODULE_MAX_RANK + 1):
+            raise ValueError(f"a LoRA module's rank must be an int in 0..{LORA_MODULE_MAX_RANK}, got {r!r}")
+    return max(16, (sum(ranks) + 15) // 16 * 16)
+
+
+def lora_shapes(cfg) -> dict:
+    """name -> (part output sizes, K) of the four projections of a model of ``cfg`` (a ``LlamaConfig``), parts in
+    ``LORA_PARTS``' order."""
+    q, kv = cfg.n_heads * cfg.head_dim, cfg.n_kv_heads * cfg.head_dim
+    return {"wqkv": ((q, kv, kv), cfg.dim), "wo": ((cfg.dim,), q), "w_gate_up": ((cfg.ffn, cfg.ffn), cfg.dim),
+            "w_down": ((cfg.dim,), cfg.ffn)}
+
+
+def pack_lora(cfg, name: str, lora_A, lora_B, scaling, norm_weight: torch.Tensor | None = None,
+              rank: int | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """One adapter's tables for projection ``name`` ("wqkv", "wo", "w_gate_up", "w_down") as ``k_lora_delta`` reads
+    them: ``(A' [R, K], B' [N, R])``, bf16, on the parts' device. Plain torch: runs without a GPU.
+
+    ``lora_A`` / ``lora_B``: per part of ``LORA_PARTS[name]`` PEFT's ``lora_A.weight [r, K]`` and ``lora_B.weight
+    [n_part, r]``, or None for a module the adapter leaves out (a bare tensor for a one-part projection).
+    ``scaling``: PEFT's ``lora_alpha / r`` (``lora_alpha / sqrt(r)`` with ``use_rslora``), one float or one per part;
+    it is folded into B'. The parts are stacked: A' = [A_0; A_1; ..] and B' block-structured (part i's rows times part
+    i's ranks, zeros elsewhere), so B' A' x is each part's own B_i A_i x. ``norm_weight``: the RMSNorm weight [K] that
+    the base weight has folded into its columns (wqkv: attn_norm, w_gate_up: ffn_norm; required there, refused
+    elsewhere): folded into A's columns likewise, since the kernel reads the raw residual. B' rows go through
+    ``fused_row_perm``, the base weight's row order. ``rank``: the R to pad to with zero rows of A' and zero columns
+    of B' (default ``lora_rank`` of the parts' ranks); every adapter of a decoder shares it. The products are formed
+    in fp32 and rounded to bf16 once."""
+    from p2p_llm_tunnel_amd.models.tiny_llm import FOLDED_NORM, fused_row_perm
+    if name not in LORA_PARTS:
+        raise ValueError(f"pack_lora: {name!r} is no projection of a layer ({', '.join(LORA_PARTS)})")
+    parts = LORA_PARTS[name]
+    sizes, K = lora_shapes(cfg)[name]
+    if isinstance(lora_A, torch.Tensor) or lora_A is None:
+        lora_A, lora_B = [lora_A], [lora_B]
+    if len(lora_A) != len(parts) or len(lora_B) != len(parts):
+        raise ValueError(f"{name}: one lora_A and one lora_B per part {parts} (None for a module left out)")
+    scal = [float(scaling)] * len(parts) if isinstance(scaling, (int, float)) else [float(s) for s in scaling]
+    if (norm_weight is not None) != (name in FOLDED_NORM):
+        raise ValueError(f"{name}: " + ("the preceding norm's weight is folded into A' (norm_weight is required)"
+                                       if name in FOLDED_NORM else "no norm precedes this projection"))
+    ranks = []
+    for mod, A, B, n in zip(parts, lora_A, lora_B, sizes):
+        if (A is None) != (B is None):
+            raise ValueError(f"{mod}: lora_A and lora_B come together")
+        if A is not None and (A.dim() != 2 or B.dim() != 2 or A.shape[1] != K or tuple(B.shape) != (n, A.shape[0])):
+            raise ValueError(f"{mod}: lora_A {tuple(A.shape)} and lora_B {tuple(B.shape)} do not match the base model "
+                             f"(lora_A [r, {K}], lora_B [{n}, r])")
+        ranks.append(0 if A is None else A.shape[0])
+    R = lora_rank(*ranks) if rank is None else rank
+    if R % 16 or not sum(ranks) <= R <= LORA_MAX_RANK:
+        raise ValueError(f"{name}: rank must be a multiple of 16 in {max(16, sum(ranks))}..{LORA_MAX_RANK}, got {R}")
+    dev = next((A.device for A in lora_A if A is not None), "cpu")
+    Ap = torch.zeros(R, K, dtype=torch.float32, device=dev)
+    Bp = torch.zeros(sum(sizes), R, dtype=torch.float32, device=dev)
+    r0 = n0 = 0
+    for A, B, n, s in zip(lora_A, lora_B, sizes, scal):
+        if A is not None:
+            r = A.shape[0]
+            Ap[r0:r0 + r] = A.float() if norm_weight is None else A.float() * norm_weight.float().to(dev)[None, :]
+            Bp[n0:n0 + n, r0:r0 + r] = B.float() * s
+            r0 += r
+        n0 += n
+    if not bool(torch.isfinite(Ap).all()) or not bool(torch.isfinite(Bp).all()):
+        raise ValueError(f"{name}: non-finite adapter weight (NaN or inf)")
+    perm = fused_row_perm(cfg, name, dev)
+    if perm is not None:
+        Bp = Bp[perm]
+    return Ap.to(torch.bfloat16).contiguous(), Bp.to(torch.bfloat16).contiguous()
+
+
+def unpack_lora(cfg, name: str, A: torch.Tensor, B: torch.Tensor,
+                norm_weight: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """``pack_lora``'s inverse, in fp64: ``(A [R, K], B [N, R])`` with the norm weight divided out of A's columns and
+    B's rows back in the plain order of the stacked parts, so that ``B @ A`` is the delta of the plain weight."""
+    from p2p_llm_tunnel_amd.models.tiny_llm import fused_row_perm
+    A64, B64 = A.double(), B.double()
+    if norm_weight is not None:
+        A64 = A64 / norm_weight.double().to(A.device)[None, :]
+    perm = fused_row_perm(cfg, name, B.device)
+    if perm is not None:
+        plain = torch.empty_like(B64)
+        plain[perm] = B64
+        B64 = plain
+    return A64, B64
+
+
+def _check_lora_shapes(M: int, N: int, K: int, R: int, n: int) -> None:
+    if not 1 <= M <= MAX_ROWS or N < 16 or N % 16 or K < 32 or K % 32:
+        raise ValueError(f"lora: need 1 <= M <= {MAX_ROWS}, N % 16 == 0, K % 32 == 0, got M {M}, N {N}, K {K}")
+    if R < 16 or R % 16 or R > LORA_MAX_RANK:
+        raise ValueError(f"lora: the padded rank must be a multiple of 16 up to {LORA_MAX_RANK}, got {R}")
+    if not 1 <= n <= LORA_MAX_ADAPTERS:
+        raise ValueError(f"lora: 1..{LORA_MAX_ADAPTERS} adapters, got {n}")
+    if max(M * K, R * K, N * R) * 2 >= GEMM_OPERAND_LIMIT:
+        raise ValueError("lora: x, one adapter's A' and one adapter's B' must each stay below 2 GiB")
+
+
+def lora_plan(M: int, N: int, K: int, R: int, n_adapters: int = 1) -> LoraPlan:
+    """What ``k_lora_delta`` launches for M rows of a projection [N, K] at padded rank R (host only: the library, no
+    GPU): (column tiles of delta, 16-row tiles) workgroups of ``waves`` waves, ``cols`` delta columns each, and
+    ``passes`` shrink passes per distinct adapter of a row tile."""
+    _check_lora_shapes(M, N, K, R, n_adapters)
+    plan = LoraPlan()
+    _ok(lib().p2pt_lora_plan(M, N, K, R, n_adapters, ctypes.byref(plan)), "lora_plan")
+    return plan
+
+
+def lora_delta(x: torch.Tensor, A: torch.Tensor, B: torch.Tensor, aid: torch.Tensor) -> torch.Tensor:
+    """``k_lora_delta`` alone: fp32 ``delta[m] = B[aid[m]] @ bf16(A[aid[m]] @ x[m])`` for every row, exactly 0 where
+    ``aid[m]`` is -1. x bf16 [M <= 64, K]; A bf16 [n, R, K]; B bf16 [n, N, R]; aid int32 [M]. The shapes are judged
+    first, from the shapes alone, so a refusal needs no device."""
+    for name, t in (("x", x), ("A", A), ("B", B), ("aid", aid)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a tensor")
+    if x.dim() != 2 or A.dim() != 3 or B.dim() != 3 or A.shape[2] != x.shape[1] or B.shape[0] != A.shape[0] or \
+            B.shape[2] != A.shape[1] or tuple(aid.shape) != (x.shape[0],):
+        raise ValueError("shapes must be x [M, K], A [n, R, K], B [n, N, R], aid [M]")
+    (M, K), (n, R, _), N = x.shape, A.shape, B.shape[1]
+    _check_lora_shapes(M, N, K, R, n)
+    _check(x, torch.bfloat16, "x")
+    _check(A, torch.bfloat16, "A", x.device)
+    _check(B, torch.bfloat16, "B", x.device)
+    _check(aid, torch.int32, "aid", x.device)
+    delta = torch.empty(M, N, dtype=torch.float32, device=x.device)
+    _ok(lib().p2pt_lora_delta(_p(x), _p(aid), _p(A), _p(B), _p(delta), M, N, K, R, n, _stream(x)), "lora_delta")
+    return delta
+
+
+def check_lora(cfg_dims: LlamaDims, lora, device=None) -> tuple[int, tuple]:
+    """``lora`` as ``FusedLlamaDecoder`` takes it: one dict per layer, name -> ``(A [n, R, K], B [n, N, R])`` (bf16,
+    the adapters stacked on dim 0) for each of ``LAYER_GEMMS``, the same n and the same R per projection in every
+    layer. Returns (n, the four ranks). Shapes and dtypes only unless ``device`` is given."""
+    d = cfg_dims
+    shapes = {"wqkv": ((d.H + 2 * d.Hkv) * d.D, d.dim), "wo": (d.dim, d.H * d.D), "w_gate_up": (2 * d.ffn, d.dim),
+              "w_down": (d.dim, d.ffn)}
+    if not isinstance(lora, (list, tuple)) or len(lora) != d.n_layers:
+        raise ValueError(f"lora must hold one dict per layer ({d.n_layers})")
+    n, ranks = None, {}
+    for L, layer in enumerate(lora):
+        if set(layer) != set(LAYER_GEMMS):
+            raise ValueError(f"layer {L}: lora needs exactly {', '.join(LAYER_GEMMS)}")
+        for name in LAYER_GEMMS:
+            A, B = layer[name]
+            N, K = shapes[name]
+            for what, t in (("A'", A), ("B'", B)):
+                if not isinstance(t, torch.Tensor) or t.dtype != torch.bfloat16 or t.dim() != 3:
+                    raise TypeError(f"{label(name, L)} lora {what}: expected a bf16 tensor with the adapters on dim 0")
+            n = A.shape[0] if n is None else n
+            R = ranks.setdefault(name, A.shape[1])
+            if tuple(A.shape) != (n, R, K) or tuple(B.shape) != (n, N, R):
+                raise ValueError(f"{label(name, L)} lora: A' {tuple(A.shape)} and B' {tuple(B.shape)}, not "
+                                 f"({n}, {R}, {K}) and ({n}, {N}, {R})")
+            _check_lora_shapes(MAX_ROWS, N, K, R, n)
+            if device is not None:
+                _check(A, torch.bfloat16, f"{label(name, L)} lora A'", device)
+                _check(B, torch.bfloat16, f"{label(name, L)} lora B'", device)
+                if A.data_ptr() % 16 or B.data_ptr() % 16:
+                    raise ValueError(f"{label(name, L)} lora: A' and B' must be 16-byte aligned")
+    return n, tuple(ranks[name] for name in LAYER_GEMMS)
+
+
 class FusedLlamaDecoder:
     """Host handle for the fused decode step (decode_fused.hip): 5 kernels per layer + 3
     (6 per layer with ``dims.qk_norm``: the per-head q/k RMSNorm of Qwen3 runs in a kernel of its own;
@@ -1714,6 +1920,13 @@ class FusedLlamaDecoder:
     block scales after the table, run by the MXFP4 instantiations; everything else of the model stays bf16. None or
     "bf16": nothing above changes.
 
+    ``lora`` (docs/LORA.md; None, and then nothing above changes): up to 8 LoRA adapters beside the base weights, as
+    ``check_lora`` describes them (``pack_lora`` builds one adapter's tables). Dense bf16 models without QK-norm only.
+    The workspace grows by one buffer, delta, and ``step(.., adapters=)`` names each row's adapter: ahead of each of a
+    layer's four projections ``k_lora_delta`` writes the rows' fp32 low-rank term there and the projection runs as
+    its ``k_skinny<.., LORA = 1>`` variant on the same ``step_plan``, which adds it to the accumulator ahead of its
+    epilogue. ``adapters=None`` launches the base step, kernel for kernel.
+
     Holds the weight pointer table and a zero-initialised workspace; ``step``
     validates the per-call tensors and launches on the current stream (capturable
     into a hipGraph: no host sync, no allocation, grids sized by the row count).
@@ -1721,7 +1934,7 @@ class FusedLlamaDecoder:
 
     def __init__(self, dims: LlamaDims, weights: list, k_cache: torch.Tensor, v_cache: torch.Tensor,
                  weight_fp8: bool = False, kv_scales: torch.Tensor | None = None, windows=None, weight_format=None,
-                 chunk_attn: bool = False, moe: MoeDims | None = None, expert_format=None):
+                 chunk_attn: bool = False, moe: MoeDims | None = None, expert_format=None, lora=None):
         self.dims = dims
         self.moe = check_moe(moe, dims.dim, dims.ffn)
         self.expert_format = as_expert_format(expert_format, self.moe, dims.dim, dims.ffn)
@@ -1832,7 +2045,26 @@ class FusedLlamaDecoder:
             if not bool((torch.isfinite(kv_scales) & (kv_scales > 0)).all().item()):
                 raise ValueError("kv_scales entries (and their reciprocals) must be finite and > 0")
         self.kv_scales = kv_scales  # keep alive
-        if self.moe is not None:
+        self.lora = self._lora = None
+        if lora is not None:
+            if self.moe is not None or (fmt.layers, fmt.lm_head) != (0, 0):
+                raise ValueError("lora: adapters need a dense model with bf16 weights (no MoE, no --weight-dtype)")
+            if dims.qk_norm:
+                raise ValueError("lora: adapters on a QK-norm model (Qwen3) are not supported: its QKV projection "
+                                 "has no LoRA-delta kernel variant")
+            n, ranks = check_lora(dims, lora, dev)
+            ptrs = [layer[name][j].data_ptr() for layer in lora for name in LAYER_GEMMS for j in (0, 1)]
+            self._lora_ptrs = (ctypes.c_void_p * len(ptrs))(*ptrs)
+            self._lora = LoraTable(n_adapters=n, rank=(_INT * 4)(*ranks), tables=self._lora_ptrs)
+            self.lora = lora  # keep alive
+            # Every row count: K parts, and with them waves and load batch, change with it (host-only lookups).
+            for B in range(1, MAX_ROWS + 1):
+                if not plan_kernels_ok(dims, B, windows=self.windows, chunk_attn=chunk_attn, lora=ranks):
+                    raise ValueError(f"the fused decode kernels have no LoRA variant for a step of {B} rows of this "
+                                     "model")
+        if self._lora is not None:
+            nbytes = lib().p2pt_llama_ws_bytes_lora(ctypes.byref(dims))
+        elif self.moe is not None:
             nbytes = lib().p2pt_llama_ws_bytes_moe(ctypes.byref(dims), ctypes.byref(self.moe))
         elif fmt.layers == 3:  # the xg buffer after the others
             nbytes = lib().p2pt_llama_ws_bytes_fmt(ctypes.byref(dims), ctypes.byref(fmt))
@@ -1874,16 +2106,20 @@ class FusedLlamaDecoder:
         qkv [64, (H+2*Hkv)*D] (bf16): the raw QKV projection of a QK-norm model's
         last layer, as ``k_qknorm_rope`` read it ([0, ...] for other models).
         An int4 model adds xg [64, dim] (bf16): the last residual times the norm weight its producer was given.
+        A decoder with ``lora`` adds delta [64, widest projection] (fp32): row m of the last ``k_lora_delta`` launch,
+        the last layer's down projection, lies in ``delta.view(-1)[m * dim:(m + 1) * dim]``.
         An MoE model adds its last layer's route_id, route_w [64, top_k], route_rs [64], moe_h [64 * top_k, ffn]
         and moe_part [64, top_k, dim] (``moe_ffn``), and its h stays unwritten.
         Read them after a stream sync; only the first B rows of a step are defined."""
         d = self.dims
         w4g = self.weight_format.layers == 3
         buffers = self._WS_BUFFERS + (self._WS_MOE_BUFFERS if self.moe is not None else ()) + \
-            ((("xg", torch.bfloat16),) if w4g else ())
+            ((("xg", torch.bfloat16),) if w4g else ()) + ((("delta", torch.float32),) if self._lora is not None else ())
         n = len(buffers)
         off, cnt = (ctypes.c_size_t * n)(), (ctypes.c_size_t * n)()
-        if self.moe is not None:
+        if self._lora is not None:
+            got = lib().p2pt_llama_ws_layout_lora(ctypes.byref(d), off, cnt, n)
+        elif self.moe is not None:
             got = lib().p2pt_llama_ws_layout_moe(ctypes.byref(d), ctypes.byref(self.moe), off, cnt, n)
         elif w4g:
             got = lib().p2pt_llama_ws_layout_fmt(ctypes.byref(d), ctypes.byref(self.weight_format), off, cnt, n)
@@ -1903,6 +2139,8 @@ class FusedLlamaDecoder:
                   "counters": (M * d.H,), "qkv": (M if d.qk_norm else 0, (d.H + 2 * d.Hkv) * d.D)}
         if w4g:
             shapes["xg"] = (M, d.dim)
+        if self._lora is not None:
+            shapes["delta"] = (M, -1)
         if self.moe is not None:
             k = self.moe.top_k
             shapes.update(route_id=(M, k), route_w=(M, k), route_rs=(M,), moe_h=(M * k, d.ffn), moe_part=(M, k, d.dim))
@@ -1917,12 +2155,14 @@ class FusedLlamaDecoder:
         embed_pool_(self._resid, self.weights[self.table.index("final_norm")], acc, out, jobs, self.dims.eps)
 
     def step(self, tokens: torch.Tensor, pos: torch.Tensor, logits: torch.Tensor, ids: torch.Tensor,
-             slots: torch.Tensor | None = None, emit_rows: int = 0) -> None:
+             slots: torch.Tensor | None = None, emit_rows: int = 0, adapters: torch.Tensor | None = None) -> None:
         """One step over B <= 64 token rows (16-row MFMA tiles). Row b is token
         ``tokens[b]`` at cache position ``pos[b]`` of cache slot ``slots[b]``
         (default: slot b). Rows of one slot at consecutive positions are a prefill
         chunk (causal within the step). Only rows [0, emit_rows) get logits and
-        ids (0: all): the LM head skips prefill rows that sample nothing."""
+        ids (0: all): the LM head skips prefill rows that sample nothing.
+        ``adapters`` (a decoder with ``lora`` only): int32 [B], the adapter of each row, -1 for none. None runs the
+        base step."""
         d = self.dims
         _check(tokens, torch.int64, "tokens", self.device)
         _check(pos, torch.int32, "pos", self.device)
@@ -1940,6 +2180,19 @@ class FusedLlamaDecoder:
             raise ValueError(f"rows must be 1..{limit} with matching pos/ids")
         if logits.shape != (B, d.vocab):
             raise ValueError("logits must be [B, vocab]")
+        if adapters is not None:
+            if self._lora is None:
+                raise ValueError("adapters: this decoder was built without lora")
+            _check(adapters, torch.int32, "adapters", self.device)
+            if adapters.shape != (B,):
+                raise ValueError("adapters must be [B]")
+        if self._lora is not None:
+            _ok(lib().p2pt_llama_decode_lora(ctypes.byref(d), _p(self.kv_scales), self._windows, self._wptr,
+                                             _p(self.k_cache), _p(self.v_cache), _p(tokens), _p(pos), _p(slots), B,
+                                             emit_rows, _p(self.ws), self.ws.numel(), _p(logits), _p(ids),
+                                             _stream(tokens), int(self.chunk_attn), ctypes.byref(self._lora),
+                                             _p(adapters)), "llama_decode")
+            return
         if self.expert_format.w8:
             _ok(lib().p2pt_llama_decode_experts(ctypes.byref(d), ctypes.byref(self.weight_format), _p(self.kv_scales),
                                                 self._windows, self._wptr, _p(self.k_cache), _p(self.v_cache),

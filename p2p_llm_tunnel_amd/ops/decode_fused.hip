@@ -5,6 +5,7 @@
 // points. The kernels and the design notes are in decode_fused_kernels.h.
 #include "decode_fused_kernels.h"
 #include "decode_fused_set.h"
+#include "decode_lora.h"
 #include "decode_moe.h"
 #include "decode_w4g.h"
 
@@ -166,6 +167,26 @@ bool moe_ok(const LlamaDims& d, const MoeDims& m) {
   // each expert's slice below kOob (dims_ok holds d.ffn, the per-expert size, to exactly these).
   return d.dim % 32 == 0 && d.ffn % 32 == 0 && size_t(2) * d.ffn * d.dim * 2 < kOob;
 }
+// LoRA adapters (docs/LORA.md), beside the plans as MoeDims is and for the same reason: no field of LlamaDims or of a
+// plan struct, so a model without adapters (lora == nullptr everywhere below) plans, lays out and launches what it did.
+// Mirrored with ctypes. rank: the padded R of wqkv, wo, w_gate_up and w_down (a multiple of 16 up to 192, the same in
+// every layer and adapter). tables: per layer eight device pointers, A' then B' of each of the four in that order;
+// A' bf16 [n_adapters][R][K] with the preceding norm weight folded into its columns where the base weight has it,
+// B' bf16 [n_adapters][N][R] in the row order of the base weight with the PEFT scaling folded in; 16-byte aligned.
+struct LoraTable {
+  int n_adapters;
+  int rank[4];
+  const void* const* tables;
+};
+enum LoraProj : int { LP_QKV, LP_O, LP_GATE_UP, LP_DOWN };
+// bf16 dense layers without QK-norm (whose EPI_STORE route has no LORA variant: refused, not served).
+bool lora_ok(const LlamaDims& d, const LoraTable& t) {
+  if (d.qk_norm) return false;
+  const int N[4] = {(d.H + 2 * d.Hkv) * d.D, d.dim, 2 * d.ffn, d.dim}, K[4] = {d.dim, d.H * d.D, d.dim, d.ffn};
+  for (int j = 0; j < 4; j++)
+    if (!p2pt_lora::shapes_ok(kMaxM, N[j], K[j], t.rank[j], t.n_adapters)) return false;
+  return true;
+}
 // One workgroup per tn subtiles of 16 >> kpl columns of one 16-row tile.
 //  - K parts (GemmArgs::kpl), where asked for (the d_model-wide O and down
 //    projections): the widest tile (16, 8 or 4 columns) whose column tiles
@@ -266,7 +287,7 @@ size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
 struct Workspace {
   uint16_t *resid, *q, *attn, *h, *qkv, *moe_h, *xg;
-  float *ss, *part_o, *part_ml, *am_val, *route_w, *route_rs, *moe_part;
+  float *ss, *part_o, *part_ml, *am_val, *route_w, *route_rs, *moe_part, *delta;
   int *am_idx, *route_id;
   unsigned* counters;  // [kMaxM * H] attention split tickets (self-resetting)
   size_t bytes;
@@ -277,19 +298,21 @@ struct Workspace {
 // p2pt_llama_ws_layout reports, WS_NBUF those of p2pt_llama_ws_layout_moe.
 enum WsBuf : int { WS_RESID, WS_Q, WS_ATTN, WS_H, WS_SS, WS_PART_O, WS_PART_ML, WS_AM_VAL, WS_AM_IDX, WS_COUNTERS, WS_QKV,
                    WS_NDENSE, WS_ROUTE_ID = WS_NDENSE, WS_ROUTE_W, WS_ROUTE_RS, WS_MOE_H, WS_MOE_PART, WS_NBUF,
-                   WS_XG = WS_NBUF, WS_NALL };  // WS_XG: grouped int4 only, after every buffer the other layouts report
+                   WS_XG = WS_NBUF,  // WS_XG: grouped int4 only, after every buffer the other layouts report
+                   WS_DELTA, WS_NALL };  // WS_DELTA: LoRA adapters only, after every other buffer
 
 struct WsLayout {
   size_t off[WS_NALL];    // byte offset from the workspace base (256-byte aligned)
   // elements: bf16 resid/q/attn/h/qkv/moe_h, fp32 ss/part_o/part_ml/am_val/route_w/route_rs/moe_part, int32 am_idx/route_id,
-  // uint32 counters
+  // uint32 counters, fp32 delta
   size_t count[WS_NALL];
   size_t bytes;
 };
 
 // The one place that knows the workspace layout. The counts that depend on a
 // grid are the plan's own, at their worst case over the row count.
-WsLayout ws_layout(const LlamaDims& d, const MoeDims* moe = nullptr, const WeightFormat& f = WeightFormat{0, 0}) {
+WsLayout ws_layout(const LlamaDims& d, const MoeDims* moe = nullptr, const WeightFormat& f = WeightFormat{0, 0},
+                   bool lora = false) {
   WsLayout l{};
   size_t off = 0;
   auto take = [&](WsBuf b, size_t count, size_t elem) {
@@ -323,13 +346,17 @@ WsLayout ws_layout(const LlamaDims& d, const MoeDims* moe = nullptr, const Weigh
   // Grouped int4 weights: xg = bf16(resid * g_next), what the QKV and gate/up GEMMs read. Empty otherwise, and last, so
   // the offsets and the size of every other format are unchanged.
   take(WS_XG, f.layers == kW4g ? size_t(kMaxM) * d.dim : 0, 2);
+  // LoRA adapters: delta fp32 [64][the widest projection], what k_lora_delta leaves for the next k_skinny. One buffer
+  // serves a layer's four projections in turn (one stream). Empty otherwise, and last, so nothing else moves.
+  const size_t widest = std::max(std::max(size_t(d.H + 2 * d.Hkv) * d.D, size_t(d.dim)), size_t(2) * d.ffn);
+  take(WS_DELTA, lora ? size_t(kMaxM) * widest : 0, 4);
   l.bytes = off;
   return l;
 }
 
 Workspace carve(const LlamaDims& d, uint8_t* base, const MoeDims* moe = nullptr,
-                const WeightFormat& f = WeightFormat{0, 0}) {
-  const WsLayout l = ws_layout(d, moe, f);
+                const WeightFormat& f = WeightFormat{0, 0}, bool lora = false) {
+  const WsLayout l = ws_layout(d, moe, f, lora);
   Workspace w{};
   auto at = [&](WsBuf b) { return base ? base + l.off[b] : nullptr; };
   w.resid = reinterpret_cast<uint16_t*>(at(WS_RESID));
@@ -349,6 +376,7 @@ Workspace carve(const LlamaDims& d, uint8_t* base, const MoeDims* moe = nullptr,
   w.moe_h = reinterpret_cast<uint16_t*>(at(WS_MOE_H));
   w.moe_part = reinterpret_cast<float*>(at(WS_MOE_PART));
   w.xg = reinterpret_cast<uint16_t*>(at(WS_XG));
+  w.delta = reinterpret_cast<float*>(at(WS_DELTA));
   w.bytes = l.bytes;
   return w;
 }
@@ -465,7 +493,11 @@ auto argmax(void* logits, float* am_val, int* am_idx) {
 
 // The kernel a plan names, or nullptr where it is not instantiated.
 using SkinnyKernel = void (*)(GemmArgs);
-SkinnyKernel skinny_kernel(const GemmPlan& p, int w8 = 0) {
+SkinnyKernel skinny_kernel(const GemmPlan& p, int w8 = 0, bool lora = false) {
+  // The LoRA-delta variants (bf16 weights only): the same lists and their own predicate, in decode_lora.hip.
+  if (lora)
+    return w8 ? nullptr
+              : reinterpret_cast<SkinnyKernel>(const_cast<void*>(p2pt_lora::skinny_kernel(p.nw, p.tn, p.epi, p.um)));
   // Grouped int4: the same lists and predicate, instantiated in decode_w4g.hip.
   if (w8 == kW4g) return reinterpret_cast<SkinnyKernel>(const_cast<void*>(p2pt_w4g::skinny_kernel(p.nw, p.tn, p.epi, p.um)));
   SkinnyKernel k = nullptr;
@@ -501,8 +533,10 @@ bool rows_ok(int B) { return B > 0 && B <= kMaxM; }
 // Each checks its arguments, looks its kernel up and launches it; a plan that names no kernel is hipErrorInvalidValue.
 // w8: the weight's format (WeightFormat): 1, the FP8-weight instantiation, reads a.wscale and is refused without it;
 // 2, the MXFP4 one, reads a.wexp likewise; 3, the grouped int4 one, a.wgrp. A scale pointer the format does not read is
-// refused too.
-hipError_t launch(const GemmPlan& p, GemmArgs a, hipStream_t s, int w8 = 0) {
+// refused too. lora: the LORA instantiation of the plan's kernel, which reads a.delta: refused without it, as is a
+// delta without the flag.
+hipError_t launch(const GemmPlan& p, GemmArgs a, hipStream_t s, int w8 = 0, bool lora = false) {
+  if (lora != (a.delta != nullptr)) return hipErrorInvalidValue;
   if ((w8 == 1) != (a.wscale != nullptr) || (w8 == 2) != (a.wexp != nullptr)) return hipErrorInvalidValue;
   // Grouped int4: the group words, K parts of whole quads, and for a residual producer the xg store's two pointers.
   if ((w8 == kW4g) != (a.wgrp != nullptr) || (w8 == kW4g && p.K % (kW4gGroup << p.kpl))) return hipErrorInvalidValue;
@@ -516,7 +550,7 @@ hipError_t launch(const GemmPlan& p, GemmArgs a, hipStream_t s, int w8 = 0) {
   if (epi_has_table(p.epi) && a.inv_freq == nullptr) return hipErrorInvalidValue;
   // Cache scales come in pairs, and only to the epilogues that write an FP8 cache.
   if ((a.k_rscale != nullptr) != (a.v_rscale != nullptr) || (a.k_rscale && !epi_kv8(p.epi))) return hipErrorInvalidValue;
-  const SkinnyKernel k = skinny_kernel(p, w8);
+  const SkinnyKernel k = skinny_kernel(p, w8, lora);
   if (!k) return hipErrorInvalidValue;
   a.M = p.M, a.N = p.N, a.K = p.K, a.kpl = p.kpl;
   hipLaunchKernelGGL(k, dim3(p.grid_x, p.grid_y), dim3(p.nw * 64), 0, s, a);
@@ -700,9 +734,12 @@ int p2pt_llama_kv_plan(const LlamaDims* d, KvPlan* out) {
 // experts (p2pt_llama_plan_kernels_experts): the format of an MoE model's experts; the gate_up and down stages are then
 // that format's instantiations. FP8 or MXFP4 without moe, or with a dim or ffn that is no multiple of 64 (FP8) or 128
 // (MXFP4), is -1. nullptr: bf16.
-int p2pt_llama_plan_kernels_experts(const LlamaDims* d, int B, int emit_rows, const WeightFormat* fmt,
-                                    const int* windows, int chunk_attn, const MoeDims* moe,
-                                    const ExpertFormat* experts) {
+// lora (p2pt_llama_plan_kernels_lora): the four layer stages are then their LORA variants; bf16 dense layers without
+// QK-norm only, anything else is -1. nullptr: the call without.
+static int plan_kernels(const LlamaDims* d, int B, int emit_rows, const WeightFormat* fmt, const int* windows,
+                        int chunk_attn, const MoeDims* moe, const ExpertFormat* experts, const LoraTable* lora) {
+  if (lora && (moe || fmt->layers != 0 || !dims_ok(*d) || !lora_ok(*d, *lora))) return -1;
+  const bool lr = lora != nullptr;
   if (!dims_ok(*d) || !rows_ok(B) || !format_ok(*fmt) || !windows_ok(*d, Windows{windows})) return -1;
   if (!format_dims_ok(*d, *fmt)) return -1;
   if (moe && (!moe_ok(*d, *moe) || fmt->layers != 0)) return -1;
@@ -723,17 +760,40 @@ int p2pt_llama_plan_kernels_experts(const LlamaDims* d, int B, int emit_rows, co
     attn = attn && attn_kernel(P.attn.D, P.attn.G, KV.attn_kv8, wn.win) != nullptr && wn.slots >= 1 &&
            wn.slots <= P.attn.stride;
   }
-  const bool found[] = {skinny_kernel(P.qkv_first, w8) != nullptr,
-                        skinny_kernel(P.qkv, w8) != nullptr,
+  const bool found[] = {skinny_kernel(P.qkv_first, w8, lr) != nullptr,
+                        skinny_kernel(P.qkv, w8, lr) != nullptr,
                         !P.qk_norm_grid || qknorm_kernel(d->D, P.qk_norm_table, KV.qk_norm_kv8) != nullptr,
                         attn,
-                        skinny_kernel(P.o, w8) != nullptr,
-                        moe ? moe_found : skinny_kernel(P.gate_up, w8) != nullptr,
-                        moe ? moe_found : skinny_kernel(P.down, w8) != nullptr,
+                        skinny_kernel(P.o, w8, lr) != nullptr,
+                        moe ? moe_found : skinny_kernel(P.gate_up, w8, lr) != nullptr,
+                        moe ? moe_found : skinny_kernel(P.down, w8, lr) != nullptr,
                         skinny_kernel(P.lm_head, fmt->lm_head) != nullptr};
   for (int n = 0; n < 8; n++)
     if (!found[n]) return 1 + n;
   return 0;
+}
+int p2pt_llama_plan_kernels_experts(const LlamaDims* d, int B, int emit_rows, const WeightFormat* fmt,
+                                    const int* windows, int chunk_attn, const MoeDims* moe,
+                                    const ExpertFormat* experts) {
+  return plan_kernels(d, B, emit_rows, fmt, windows, chunk_attn, moe, experts, nullptr);
+}
+int p2pt_llama_plan_kernels_lora(const LlamaDims* d, int B, int emit_rows, const int* windows, int chunk_attn,
+                                 const LoraTable* lora) {
+  const WeightFormat bf16{0, 0};
+  return lora ? plan_kernels(d, B, emit_rows, &bf16, windows, chunk_attn, nullptr, nullptr, lora) : -1;
+}
+// The workspace of a decoder with adapters: p2pt_llama_ws_layout's eleven buffers at their offsets and a twelfth,
+// delta fp32 [64][widest projection], after them.
+size_t p2pt_llama_ws_bytes_lora(const LlamaDims* d) {
+  if (!dims_ok(*d) || d->qk_norm) return 0;
+  return ws_layout(*d, nullptr, WeightFormat{0, 0}, true).bytes;
+}
+int p2pt_llama_ws_layout_lora(const LlamaDims* d, size_t* off, size_t* count, int n) {
+  if (!dims_ok(*d) || d->qk_norm || n < WS_NDENSE + 1) return 0;
+  const WsLayout l = ws_layout(*d, nullptr, WeightFormat{0, 0}, true);
+  for (int b = 0; b < WS_NDENSE; b++) off[b] = l.off[b], count[b] = l.count[b];
+  off[WS_NDENSE] = l.off[WS_DELTA], count[WS_NDENSE] = l.count[WS_DELTA];
+  return WS_NDENSE + 1;
 }
 int p2pt_llama_plan_kernels_moe(const LlamaDims* d, int B, int emit_rows, const WeightFormat* fmt, const int* windows,
                                 int chunk_attn, const MoeDims* moe) {
@@ -894,12 +954,21 @@ int p2pt_max_rows() { return kMaxM; }
 //      count, 16-byte aligned, every row in k-step-quad order, and where the FP8-expert table has row scales come their
 //      e8m0 block scales [E][2 * ffn][dim / 32] and [E][dim][ffn / 32], natural order, 4-byte aligned. The MXFP4
 //      instantiations run on the same MoePlan. dim and ffn must be multiples of 128.
-int p2pt_llama_decode_experts(const LlamaDims* dp, const WeightFormat* fmt, const float* kv_scales, const int* windows,
-                              const void* const* w, void* k_cache, void* v_cache, const int64_t* tokens,
-                              const int* pos, const int* slots, int B, int emit_rows, void* ws, size_t ws_bytes,
-                              void* logits, int64_t* ids, void* stream, int chunk_attn, const MoeDims* moe,
-                              const ExpertFormat* experts) {
+//   LoRA adapters (p2pt_llama_decode_lora with lora != nullptr; docs/LORA.md): bf16 dense layers without QK-norm. The
+//      workspace is p2pt_llama_ws_bytes_lora's. adapters: int32 [B] on the device, the adapter of each row, -1 for
+//      none. Ahead of each of a layer's four projections k_lora_delta writes the rows' low-rank term into the
+//      workspace's delta, and the projection runs as its LORA variant on the same plan: 9 kernels per layer, one
+//      stream. adapters == nullptr launches the base step on the larger workspace, launch for launch.
+static int decode_step(const LlamaDims* dp, const WeightFormat* fmt, const float* kv_scales, const int* windows,
+                       const void* const* w, void* k_cache, void* v_cache, const int64_t* tokens, const int* pos,
+                       const int* slots, int B, int emit_rows, void* ws, size_t ws_bytes, void* logits, int64_t* ids,
+                       void* stream, int chunk_attn, const MoeDims* moe, const ExpertFormat* experts,
+                       const LoraTable* lora, const int* adapters) {
   const LlamaDims d = *dp;
+  if (lora && (moe || fmt->layers != 0 || fmt->lm_head != 0 || !dims_ok(d) || !lora_ok(d, *lora)))
+    return int(hipErrorInvalidValue);
+  if ((adapters && !lora) || (lora && !lora->tables)) return int(hipErrorInvalidValue);
+  const bool lr = lora && adapters;
   if (!dims_ok(d) || !rows_ok(B) || (!slots && B > d.max_batch) || !format_ok(*fmt)) return int(hipErrorInvalidValue);
   if (!format_dims_ok(d, *fmt)) return int(hipErrorInvalidValue);
   if (moe && (!moe_ok(d, *moe) || fmt->layers != 0)) return int(hipErrorInvalidValue);
@@ -910,9 +979,20 @@ int p2pt_llama_decode_experts(const LlamaDims* dp, const WeightFormat* fmt, cons
   if (!windows_ok(d, WN)) return int(hipErrorInvalidValue);
   const KvScales KS{kv_scales};
   const int w8 = fmt->layers;
-  const Workspace W = carve(d, static_cast<uint8_t*>(ws), moe, *fmt);
+  const Workspace W = carve(d, static_cast<uint8_t*>(ws), moe, *fmt, lora != nullptr);
   if (ws_bytes < W.bytes) return int(hipErrorInvalidValue);
   const StepPlan P = plan_step(d, B, emit_rows, *fmt);
+  // k_lora_delta for projection j of layer L on the operand its k_skinny reads, and that k_skinny's delta argument.
+  auto with_delta = [&](GemmArgs a) {
+    a.delta = lr ? W.delta : nullptr;
+    return a;
+  };
+  auto lora_delta = [&](int L, int j, const GemmPlan& p, const void* x) {
+    const void* const* t = lora->tables + size_t(L) * 8 + 2 * j;
+    return p2pt_lora::launch_delta({static_cast<const uint16_t*>(x), adapters, static_cast<const uint16_t*>(t[0]),
+                                    static_cast<const uint16_t*>(t[1]), W.delta, B, p.N, p.K, lora->rank[j],
+                                    lora->n_adapters}, static_cast<hipStream_t>(stream));
+  };
   // Grouped int4: the normed GEMMs read xg, which the residual's producers store with the next norm's weight.
   const bool w4g = w8 == kW4g;
   const uint16_t* normed_in = w4g ? W.xg : W.resid;
@@ -954,7 +1034,8 @@ int p2pt_llama_decode_experts(const LlamaDims* dp, const WeightFormat* fmt, cons
                                 norm(W.ss, P.gate_up.ss_in, d.eps) + store(W.h);
     const GemmArgs to_down = gemm(W.h, T.get(R_W_DOWN, L), T.scale(R_W_DOWN, L), w8) +
                              resid(W.resid, W.ss, g_down, w4g ? W.xg : nullptr);
-    if (failed(launch(qkv, to_qkv, s, w8))) return int(e);
+    if (lr && failed(lora_delta(L, LP_QKV, qkv, normed_in))) return int(e);
+    if (failed(launch(qkv, with_delta(to_qkv), s, w8, lr))) return int(e);
     if (P.qk_norm_grid) {
       const QkNormArgs qn{W.qkv, static_cast<const uint16_t*>(T.get(R_Q_NORM, L)),
                           static_cast<const uint16_t*>(T.get(R_K_NORM, L)), pos, slots, d.max_batch, W.q, kc, vc, d.H,
@@ -972,7 +1053,8 @@ int p2pt_llama_decode_experts(const LlamaDims* dp, const WeightFormat* fmt, cons
     } else if (failed(launch_attn(P.attn, KV.attn_kv8, W.q, kc, vc, pos, slots, d.max_batch, W.part_o, W.part_ml, W.counters, W.attn, d.H,
                                   d.Hkv, d.max_seq, s, KS.at(d, KvScales::K, L), KS.at(d, KvScales::V, L), &wn)))
       return int(e);
-    if (failed(launch(P.o, to_o, s, w8))) return int(e);
+    if (lr && failed(lora_delta(L, LP_O, P.o, W.attn))) return int(e);
+    if (failed(launch(P.o, with_delta(to_o), s, w8, lr))) return int(e);
     if (moe) {
       // resid and ss as the O projection left them; k_moe_combine leaves them as the down projection would.
       const p2pt_moe::MoeArgs ma{W.resid, W.ss, P.gate_up.ss_in, static_cast<const uint16_t*>(T.get(R_ROUTER, L)),
@@ -983,8 +1065,10 @@ int p2pt_llama_decode_experts(const LlamaDims* dp, const WeightFormat* fmt, cons
       if (failed(p2pt_moe::launch_moe(MP, ma, s, EF))) return int(e);
       continue;
     }
-    if (failed(launch(P.gate_up, to_gate_up, s, w8))) return int(e);
-    if (failed(launch(P.down, to_down, s, w8))) return int(e);
+    if (lr && failed(lora_delta(L, LP_GATE_UP, P.gate_up, normed_in))) return int(e);
+    if (failed(launch(P.gate_up, with_delta(to_gate_up), s, w8, lr))) return int(e);
+    if (lr && failed(lora_delta(L, LP_DOWN, P.down, W.h))) return int(e);
+    if (failed(launch(P.down, with_delta(to_down), s, w8, lr))) return int(e);
   }
   const GemmArgs to_logits =
       gemm(W.resid, T.get(R_LM_HEAD), T.scale(R_LM_HEAD), fmt->lm_head) + norm(W.ss, P.lm_head.ss_in, d.eps) +
@@ -992,6 +1076,23 @@ int p2pt_llama_decode_experts(const LlamaDims* dp, const WeightFormat* fmt, cons
   if (failed(launch(P.lm_head, to_logits, s, fmt->lm_head))) return int(e);
   hipLaunchKernelGGL(k_argmax_merge, dim3(P.emit_rows), dim3(256), 0, s, W.am_val, W.am_idx, P.am_parts, ids);
   return int(hipGetLastError());
+}
+int p2pt_llama_decode_experts(const LlamaDims* dp, const WeightFormat* fmt, const float* kv_scales, const int* windows,
+                              const void* const* w, void* k_cache, void* v_cache, const int64_t* tokens,
+                              const int* pos, const int* slots, int B, int emit_rows, void* ws, size_t ws_bytes,
+                              void* logits, int64_t* ids, void* stream, int chunk_attn, const MoeDims* moe,
+                              const ExpertFormat* experts) {
+  return decode_step(dp, fmt, kv_scales, windows, w, k_cache, v_cache, tokens, pos, slots, B, emit_rows, ws, ws_bytes,
+                     logits, ids, stream, chunk_attn, moe, experts, nullptr, nullptr);
+}
+int p2pt_llama_decode_lora(const LlamaDims* dp, const float* kv_scales, const int* windows, const void* const* w,
+                           void* k_cache, void* v_cache, const int64_t* tokens, const int* pos, const int* slots, int B,
+                           int emit_rows, void* ws, size_t ws_bytes, void* logits, int64_t* ids, void* stream,
+                           int chunk_attn, const LoraTable* lora, const int* adapters) {
+  const WeightFormat bf16{0, 0};
+  if (!lora) return int(hipErrorInvalidValue);
+  return decode_step(dp, &bf16, kv_scales, windows, w, k_cache, v_cache, tokens, pos, slots, B, emit_rows, ws,
+                     ws_bytes, logits, ids, stream, chunk_attn, nullptr, nullptr, lora, adapters);
 }
 int p2pt_llama_decode_moe(const LlamaDims* dp, const WeightFormat* fmt, const float* kv_scales, const int* windows,
                           const void* const* w, void* k_cache, void* v_cache, const int64_t* tokens, const int* pos,

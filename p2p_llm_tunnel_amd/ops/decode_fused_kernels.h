@@ -177,6 +177,10 @@ struct GemmArgs {
   // of the next normed GEMM (a group's scale cannot carry the norm weight, which varies inside it). gnext: bf16 [N].
   const uint16_t* gnext;
   uint16_t* xg;
+  // LoRA adapters (k_skinny<.., LORA = 1>; docs/LORA.md): fp32 [M][N], the low-rank delta of every row and output
+  // column of this projection, in the row order of w, written by k_lora_delta ahead of this launch. It joins the
+  // accumulator ahead of everything else the epilogue does. Not read by the other kernels.
+  const float* delta;
 };
 
 // log2 of the output columns per 16-lane subtile: 16, 8 or 4 for 1, 2 or 4 K parts.
@@ -427,7 +431,11 @@ __device__ __forceinline__ void mma_stream(frag4 (&acc)[TN], __amdgpu_buffer_rsr
 // (GemmArgs::wgrp). The waves split K in quads and K parts carry whole quads (the host plans kpl so); a load batch is
 // one quad for UM 1 and 2 and two quads for UM 4 (mma_stream_w4g). Nothing after the MFMA knows the format. With
 // EPI_RESID the epilogue also stores xg = bf16(resid_new * gnext[col]), the next normed GEMM's A operand.
-template <int NW, int TN, int EPI, int UM, int W8 = 0>
+// LORA (bf16 weights, a layer's four projections; docs/LORA.md): wave 0 adds GemmArgs::delta[m][n], the fp32 low-rank
+// term k_lora_delta left for this projection, to the reduced accumulator: after the K-parts diagonal sum and ahead of
+// 1/rms, the bias and everything else, so (W' + B'A') x is scaled, rotated, gated or added to the residual exactly as
+// W' x is. A variant of its own: a decoder without adapters launches the instantiations it always did.
+template <int NW, int TN, int EPI, int UM, int W8 = 0, int LORA = 0>
 __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
   __shared__ float red[NW][TN][4][kWave];
   __shared__ float red_ss[NW][kWave];
@@ -508,6 +516,19 @@ __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
           const int m = min(mrow0 + r, a.M - 1);
           rprev[t][r] = bf2f(a.out[size_t(m) * a.N + tile_col<TN>(bx, t, c, cwl)]);
         }
+    }
+  }
+
+  // LORA: the delta of this lane's outputs, loaded by wave 0 ahead of the weight stream like rprev (k_lora_delta
+  // ran ahead of this kernel on the same stream). Rows past M read row M - 1 and are never stored.
+  float dlt[LORA ? TN : 1][4];
+  if constexpr (LORA != 0) {
+    if (wv == 0) {
+#pragma unroll
+      for (int t = 0; t < TN; t++)
+#pragma unroll
+        for (int r = 0; r < 4; r++)
+          dlt[t][r] = a.delta[size_t(min(mrow0 + r, a.M - 1)) * a.N + tile_col<TN>(bx, t, c, cwl)];
     }
   }
 
@@ -608,6 +629,13 @@ __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
         for (int p = 0; p < kparts; p++) sum += cbuf[(row * kparts + p) * 17 + c + (p << cwl)];
       v[0][r] = sum;
     }
+  }
+
+  if constexpr (LORA != 0) {
+#pragma unroll
+    for (int t = 0; t < TN; t++)
+#pragma unroll
+      for (int r = 0; r < 4; r++) v[t][r] += dlt[t][r];
   }
 
   if constexpr (W8 == 1) {

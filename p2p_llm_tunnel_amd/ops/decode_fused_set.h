@@ -1,6 +1,6 @@
 // The set of kernel instantiations of the fused decode step, stated once: decode_fused.hip (every format but grouped
-// int4) and decode_w4g.hip (grouped int4, compiled without packed fp32 instructions) both instantiate from these lists
-// and this predicate, and nothing else.
+// int4), decode_w4g.hip (grouped int4, compiled without packed fp32 instructions) and decode_lora.hip (the LoRA-delta
+// variants) all instantiate from these lists and these predicates, and nothing else.
 #pragma once
 #include "decode_fused_kernels.h"
 
@@ -46,6 +46,12 @@ constexpr bool skinny_exists(int nw, int tn, int epi, int um, int w8) {
   // wave's share is at least 3 k-steps and um is 4.
   if (epi_has_table(epi) || epi_kv8(epi)) return nw == 4 || um == 4;
   return true;
+}
+// k_skinny<.., W8 = 0, LORA = 1> in decode_lora.hip (docs/LORA.md): bf16 weights and the epilogues a layer's four
+// projections of a model without QK-norm can be planned with, the eight RoPE ones, SILU and RESID, one subtile, each
+// with the (nw, um) pairs its base kernel has: 48 instantiations.
+constexpr bool skinny_lora_exists(int nw, int tn, int epi, int um) {
+  return tn == 1 && (epi_is_rope(epi) || epi == EPI_SILU || epi == EPI_RESID) && skinny_exists(nw, tn, epi, um, 0);
 }
 template <int... V>
 constexpr bool contains(Ints<V...>, int v) {
