@@ -20,6 +20,7 @@ causal attention over the whole sequence) for numerics tests.
 """
 from __future__ import annotations
 
+import gc
 import math
 from dataclasses import InitVar, dataclass
 
@@ -242,8 +243,18 @@ def capture(fn, device, warmup: int = 2):
             fn()
     torch.cuda.current_stream(device).wait_stream(side)
     graph = torch.cuda.CUDAGraph()
-    with torch.no_grad(), torch.cuda.graph(graph):
-        out = fn()
+    # No cyclic collection may start inside the capture: it can destroy dead objects of earlier models and engines
+    # (CUDAGraphs, pinned staging buffers), whose destructors synchronise or query the device, which a capturing
+    # stream forbids and the destructor turns into an abort. torch.cuda.graph no longer collects on entry itself.
+    gc.collect()
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.no_grad(), torch.cuda.graph(graph):
+            out = fn()
+    finally:
+        if was_enabled:
+            gc.enable()
     return graph, out
 
 

@@ -162,6 +162,31 @@ class LoraTable(ctypes.Structure):
     _fields_ = [("n_adapters", _INT), ("rank", _INT * 4), ("tables", ctypes.POINTER(ctypes.c_void_p))]
 
 
+class StepOptions(ctypes.Structure):
+    """Mirror of ``StepOptions``: every option of a fused step, as ``p2pt_llama_step``, ``p2pt_llama_step_kernels``,
+    ``p2pt_llama_step_ws`` and ``p2pt_llama_step_weights`` take them. All zero: the bf16 dense step. ``kv_scales``: a
+    device address; ``windows``: a host array of ``n_layers`` ints. Build one with ``step_options``."""
+    _fields_ = [("fmt", WeightFormat), ("kv_scales", ctypes.c_void_p), ("windows", ctypes.POINTER(_INT)),
+                ("chunk_attn", _INT), ("moe", ctypes.POINTER(MoeDims)), ("experts", ctypes.POINTER(ExpertFormat)),
+                ("lora", ctypes.POINTER(LoraTable))]
+
+
+def step_options(fmt: WeightFormat, kv_scales: torch.Tensor | None = None, windows=None, chunk_attn: bool = False,
+                 moe: MoeDims | None = None, experts: ExpertFormat | None = None,
+                 lora: LoraTable | None = None) -> StepOptions:
+    """A ``StepOptions`` of checked values (``as_weight_format``, ``check_windows``, ``check_moe``,
+    ``as_expert_format``); None leaves a pointer null. The struct keeps the ctypes objects it points to alive; the
+    ``kv_scales`` tensor is the caller's to keep."""
+    o = StepOptions(fmt=fmt, kv_scales=kv_scales.data_ptr() if kv_scales is not None else None,
+                    chunk_attn=int(chunk_attn))
+    if windows is not None:
+        o.windows = (_INT * len(windows))(*windows)
+    for name, value in (("moe", moe), ("experts", experts), ("lora", lora)):
+        if value is not None:
+            setattr(o, name, ctypes.pointer(value))
+    return o
+
+
 EXPERT_FORMATS = {"bf16": 0, "fp8": 1, "mxfp4": 2}  # expert dtype -> ExpertFormat.w8
 EXPERT_BLOCK = 64  # K elements per block of the FP8 experts' byte order: a pair of k-steps
 EXPERT_QUAD = 128  # K elements per block of the MXFP4 experts' byte order: a quad of k-steps, 64 nibble bytes
@@ -290,7 +315,7 @@ def _signatures() -> dict:
     """Every symbol ``lib()`` binds -> its argtypes. The restype is ``c_int`` unless ``_RESTYPES`` names another."""
     vp, i, f, sz, ptr = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.POINTER
     dims, wp, ip, szp, wf = ptr(LlamaDims), ptr(WeightPlan), ptr(i), ptr(sz), ptr(WeightFormat)
-    moe, ef = ptr(MoeDims), ptr(ExpertFormat)
+    moe, ef, opts = ptr(MoeDims), ptr(ExpertFormat), ptr(StepOptions)
     return {
         "p2pt_rmsnorm": [vp, vp, vp, vp, vp, i, i, f, vp],
         "p2pt_silu_mul": [vp, vp, i, i, vp],
@@ -320,7 +345,6 @@ def _signatures() -> dict:
         "p2pt_llama_weight_plan": [dims, i, wp],
         "p2pt_llama_plan_kernels_w": [dims, i, i, wp],
         "p2pt_llama_decode_w": [dims, wp, ptr(vp), vp, vp, vp, vp, vp, i, i, vp, sz, vp, vp, vp],
-        "p2pt_llama_decode_kv": [dims, wp, vp, ptr(vp), vp, vp, vp, vp, vp, i, i, vp, sz, vp, vp, vp],
         "p2pt_llama_weight_layout": [dims, wp, ip, ip, i],
         "p2pt_llama_window_plan": [dims, i, i, ptr(WindowPlan)],
         "p2pt_llama_plan_kernels_win": [dims, i, i, wp, ip],
@@ -333,32 +357,27 @@ def _signatures() -> dict:
         "p2pt_llama_weight_layout_fmt": [dims, wf, ip, ip, i],
         "p2pt_llama_decode_fmt": [dims, wf, vp, ip, ptr(vp), vp, vp, vp, vp, vp, i, i, vp, sz, vp, vp, vp],
         "p2pt_llama_chunk_plan": [dims, i, ptr(ChunkPlan)],
-        "p2pt_llama_plan_kernels_chunk": [dims, i, i, wf, ip, i],
         "p2pt_llama_decode_chunk": [dims, wf, vp, ip, ptr(vp), vp, vp, vp, vp, vp, i, i, vp, sz, vp, vp, vp, i],
         "p2pt_chunk_attention": [vp, vp, vp, vp, vp, i, i, i, i, i, i, i, vp, vp, vp, vp, vp, vp, vp],
         "p2pt_llama_ws_bytes_moe": [dims, moe],
         "p2pt_llama_ws_layout_moe": [dims, moe, szp, szp, i],
         "p2pt_llama_moe_plan": [dims, moe, i, ptr(MoePlan)],
-        "p2pt_llama_plan_kernels_moe": [dims, i, i, wf, ip, i, moe],
         "p2pt_llama_weight_layout_moe": [dims, moe, ip, i],
         "p2pt_llama_decode_moe": [dims, wf, vp, ip, ptr(vp), vp, vp, vp, vp, vp, i, i, vp, sz, vp, vp, vp, i, moe],
         "p2pt_moe_ffn": [vp, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, f, vp],
         "p2pt_moe_ffn_plan": [i, i, i, i, i, i, ptr(MoePlan)],
         "p2pt_llama_plan_kernels_experts": [dims, i, i, wf, ip, i, moe, ef],
         "p2pt_llama_weight_layout_experts": [dims, moe, ef, ip, ip, i],
-        "p2pt_llama_decode_experts": [dims, wf, vp, ip, ptr(vp), vp, vp, vp, vp, vp, i, i, vp, sz, vp, vp, vp, i, moe,
-                                      ef],
         "p2pt_moe_ffn_experts": [vp, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, f, vp, ef, vp, vp],
         "p2pt_moe_ffn_mxfp4": [vp, vp, i, vp, vp, vp, vp, vp, vp, vp, vp, i, i, i, i, i, i, f, vp, vp, vp],
         "p2pt_lora_delta": [vp, vp, vp, vp, vp, i, i, i, i, i, vp],
         "p2pt_lora_plan": [i, i, i, i, i, ptr(LoraPlan)],
         "p2pt_lora_max_adapters": [],
         "p2pt_lora_max_rank": [],
-        "p2pt_llama_ws_bytes_lora": [dims],
-        "p2pt_llama_ws_layout_lora": [dims, szp, szp, i],
-        "p2pt_llama_plan_kernels_lora": [dims, i, i, ip, i, ptr(LoraTable)],
-        "p2pt_llama_decode_lora": [dims, vp, ip, ptr(vp), vp, vp, vp, vp, vp, i, i, vp, sz, vp, vp, vp, i,
-                                   ptr(LoraTable), vp],
+        "p2pt_llama_step": [dims, opts, ptr(vp), vp, vp, vp, vp, vp, i, i, vp, sz, vp, vp, vp, vp],
+        "p2pt_llama_step_kernels": [dims, opts, i, i],
+        "p2pt_llama_step_ws": [dims, opts, szp, szp, i],
+        "p2pt_llama_step_weights": [dims, opts, ip, ip, i],
         "p2pt_attn_span": [i, i],
         "p2pt_max_rows": [],
         "p2pt_skinny_bench": [vp, vp, vp, i, i, i, i, i, i, vp],  # microbenchmark hooks (scripts/bench_skinny.py)
@@ -367,7 +386,7 @@ def _signatures() -> dict:
 
 
 _RESTYPES = {"p2pt_llama_ws_bytes": ctypes.c_size_t, "p2pt_llama_ws_bytes_moe": ctypes.c_size_t,
-             "p2pt_llama_ws_bytes_fmt": ctypes.c_size_t, "p2pt_llama_ws_bytes_lora": ctypes.c_size_t}
+             "p2pt_llama_ws_bytes_fmt": ctypes.c_size_t, "p2pt_llama_step_ws": ctypes.c_size_t}
 
 
 def lib() -> ctypes.CDLL:
@@ -521,43 +540,14 @@ def plan_kernels_ok(dims: LlamaDims, B: int, emit_rows: int = 0, weight_fp8: boo
     windows = check_windows(windows, dims.n_layers)
     moe = check_moe(moe, dims.dim, dims.ffn)
     experts = as_expert_format(expert_format, moe, dims.dim, dims.ffn)
+    f = as_weight_format(weight_fp8, weight_format)
+    table = None
     if lora is not None:
-        f = as_weight_format(weight_fp8, weight_format)
         if moe is not None or (f.layers, f.lm_head) != (0, 0) or dims.qk_norm:
             raise ValueError("LoRA adapters need a dense bf16 model without QK-norm")
         table = LoraTable(n_adapters=1, rank=(_INT * 4)(*lora))
-        rc = lib().p2pt_llama_plan_kernels_lora(
-            ctypes.byref(dims), B, emit_rows, (ctypes.c_int * len(windows))(*windows) if windows is not None else None,
-            int(chunk_attn), ctypes.byref(table))
-    elif moe is not None and experts.w8:
-        f = as_weight_format(weight_fp8, weight_format)
-        rc = lib().p2pt_llama_plan_kernels_experts(
-            ctypes.byref(dims), B, emit_rows, ctypes.byref(f),
-            (ctypes.c_int * len(windows))(*windows) if windows is not None else None, int(chunk_attn),
-            ctypes.byref(moe), ctypes.byref(experts))
-    elif moe is not None:  # the gate_up and down stages are then the four MoE kernels (``moe_plan``), bf16 layers only
-        f = as_weight_format(weight_fp8, weight_format)
-        rc = lib().p2pt_llama_plan_kernels_moe(ctypes.byref(dims), B, emit_rows, ctypes.byref(f),
-                                               (ctypes.c_int * len(windows))(*windows) if windows is not None else None,
-                                               int(chunk_attn), ctypes.byref(moe))
-    elif chunk_attn:
-        f = as_weight_format(weight_fp8, weight_format)
-        rc = lib().p2pt_llama_plan_kernels_chunk(ctypes.byref(dims), B, emit_rows, ctypes.byref(f),
-                                                 (ctypes.c_int * len(windows))(*windows) if windows is not None else None,
-                                                 1)
-    elif weight_format is not None:
-        f = as_weight_format(weight_fp8, weight_format)
-        rc = lib().p2pt_llama_plan_kernels_fmt(ctypes.byref(dims), B, emit_rows, ctypes.byref(f),
-                                               (ctypes.c_int * len(windows))(*windows) if windows is not None else None)
-    elif windows is not None:
-        wp = WeightPlan(w8=int(bool(weight_fp8)))
-        rc = lib().p2pt_llama_plan_kernels_win(ctypes.byref(dims), B, emit_rows, ctypes.byref(wp),
-                                               (ctypes.c_int * len(windows))(*windows))
-    elif weight_fp8:
-        wp = WeightPlan(w8=1)
-        rc = lib().p2pt_llama_plan_kernels_w(ctypes.byref(dims), B, emit_rows, ctypes.byref(wp))
-    else:
-        rc = lib().p2pt_llama_plan_kernels(ctypes.byref(dims), B, emit_rows)
+    opts = step_options(f, None, windows, chunk_attn, moe, experts, table)
+    rc = lib().p2pt_llama_step_kernels(ctypes.byref(dims), ctypes.byref(opts), B, emit_rows)
     if rc < 0:
         raise ValueError("dims or row count not supported by the fused decode kernels")
     return rc == 0
@@ -1872,6 +1862,36 @@ def check_lora(cfg_dims: LlamaDims, lora, device=None) -> tuple[int, tuple]:
     return n, tuple(ranks[name] for name in LAYER_GEMMS)
 
 
+# Every workspace buffer in the order of decode_fused.hip's WsBuf, which p2pt_llama_step_ws reports them in. The first
+# WS_DENSE every step has (qkv empty without QK-norm); then an MoE model's five, an int4 model's xg, the adapters' delta.
+WS_BUFFERS = (("resid", torch.bfloat16), ("q", torch.bfloat16), ("attn", torch.bfloat16), ("h", torch.bfloat16),
+              ("ss", torch.float32), ("part_o", torch.float32), ("part_ml", torch.float32), ("am_val", torch.float32),
+              ("am_idx", torch.int32), ("counters", torch.int32), ("qkv", torch.bfloat16), ("route_id", torch.int32),
+              ("route_w", torch.float32), ("route_rs", torch.float32), ("moe_h", torch.bfloat16),
+              ("moe_part", torch.float32), ("xg", torch.bfloat16), ("delta", torch.float32))
+WS_DENSE = 11
+
+
+def workspace_layout(dims: LlamaDims, opts: StepOptions) -> tuple:
+    """The workspace of a step with ``opts`` (host only): its bytes, and ``{name: (dtype, byte offset, elements)}`` of
+    the buffers it has, in ``WS_BUFFERS``' order: the dense ones always, a later one when it is not empty."""
+    n = len(WS_BUFFERS)
+    off, cnt = (ctypes.c_size_t * n)(), (ctypes.c_size_t * n)()
+    nbytes = lib().p2pt_llama_step_ws(ctypes.byref(dims), ctypes.byref(opts), off, cnt, n)
+    if nbytes == 0:
+        raise ValueError("model dims not supported by the fused decode kernels")
+    # Each buffer starts where the 256-byte-aligned one before it ends: a list that differs from WsBuf fails here.
+    end = 0
+    for (name, dtype), o, c in zip(WS_BUFFERS, off, cnt):
+        if o != end:
+            raise RuntimeError(f"workspace layout: buffer list out of step with decode_fused.hip at {name}")
+        end = o + (c * dtype.itemsize + 255) // 256 * 256
+    if end != nbytes:
+        raise RuntimeError("workspace layout: buffer list out of step with decode_fused.hip")
+    return nbytes, {name: (dtype, o, c) for i, ((name, dtype), o, c) in enumerate(zip(WS_BUFFERS, off, cnt))
+                    if i < WS_DENSE or c}
+
+
 class FusedLlamaDecoder:
     """Host handle for the fused decode step (decode_fused.hip): 5 kernels per layer + 3
     (6 per layer with ``dims.qk_norm``: the per-head q/k RMSNorm of Qwen3 runs in a kernel of its own;
@@ -1942,10 +1962,8 @@ class FusedLlamaDecoder:
             raise TypeError(f"chunk_attn must be a bool, got {chunk_attn!r}")
         self.chunk_attn = chunk_attn
         self.windows = check_windows(windows, dims.n_layers)
-        self._windows = (ctypes.c_int * dims.n_layers)(*self.windows) if self.windows is not None else None
         self.weight_format = fmt = as_weight_format(weight_fp8, weight_format)
         self.weight_fp8 = fmt.layers == 1  # FP8 throughout
-        self._wplan = WeightPlan(w8=int(self.weight_fp8))
         dev = k_cache.device
         # The cache dtype against dims.kv_fp8 first (a host-only check): a mismatch would have every kernel read
         # and write rows of the wrong width.
@@ -2062,16 +2080,9 @@ class FusedLlamaDecoder:
                 if not plan_kernels_ok(dims, B, windows=self.windows, chunk_attn=chunk_attn, lora=ranks):
                     raise ValueError(f"the fused decode kernels have no LoRA variant for a step of {B} rows of this "
                                      "model")
-        if self._lora is not None:
-            nbytes = lib().p2pt_llama_ws_bytes_lora(ctypes.byref(dims))
-        elif self.moe is not None:
-            nbytes = lib().p2pt_llama_ws_bytes_moe(ctypes.byref(dims), ctypes.byref(self.moe))
-        elif fmt.layers == 3:  # the xg buffer after the others
-            nbytes = lib().p2pt_llama_ws_bytes_fmt(ctypes.byref(dims), ctypes.byref(fmt))
-        else:
-            nbytes = lib().p2pt_llama_ws_bytes(ctypes.byref(dims))
-        if nbytes == 0:
-            raise ValueError("model dims not supported by the fused decode kernels")
+        # What every call into the library takes beside dims. It points into kv_scales and the adapters, kept alive above.
+        self._opts = step_options(fmt, kv_scales, self.windows, chunk_attn, self.moe, self.expert_format, self._lora)
+        nbytes, _ = workspace_layout(dims, self._opts)
         # The MoE kernels a step can name (RT follows the row count; waves and load batch the per-expert shapes): a
         # plan without its instantiation is refused here with a message, not at the first launch with an error code.
         for B in (1, 17, 33):
@@ -2087,18 +2098,11 @@ class FusedLlamaDecoder:
         self.device = dev
         self._resid = None  # embed_pool's view of the workspace's resid buffer
 
-    # Workspace buffers in the order p2pt_llama_ws_layout reports them.
-    _WS_BUFFERS = (("resid", torch.bfloat16), ("q", torch.bfloat16), ("attn", torch.bfloat16), ("h", torch.bfloat16),
-                   ("ss", torch.float32), ("part_o", torch.float32), ("part_ml", torch.float32),
-                   ("am_val", torch.float32), ("am_idx", torch.int32), ("counters", torch.int32),
-                   ("qkv", torch.bfloat16))
-    # ... and those of an MoE model, which follow them (p2pt_llama_ws_layout_moe).
-    _WS_MOE_BUFFERS = (("route_id", torch.int32), ("route_w", torch.float32), ("route_rs", torch.float32),
-                       ("moe_h", torch.bfloat16), ("moe_part", torch.float32))
+    _WS_BUFFERS = WS_BUFFERS[:WS_DENSE]  # the buffers p2pt_llama_ws_layout reports
 
     def workspace_views(self) -> dict:
         """Typed, shaped views into the workspace (no copies; the layout comes from
-        ``p2pt_llama_ws_layout``): what the last ``step`` left in each buffer.
+        ``p2pt_llama_step_ws``): what the last ``step`` left in each buffer.
 
         resid [64, dim], q [64, H, D], attn [64, H*D], h [64, ffn] (bf16);
         ss [parts, 64], part_o [64, H, nsplit, D], part_ml [64, H, nsplit, 2],
@@ -2112,39 +2116,17 @@ class FusedLlamaDecoder:
         and moe_part [64, top_k, dim] (``moe_ffn``), and its h stays unwritten.
         Read them after a stream sync; only the first B rows of a step are defined."""
         d = self.dims
-        w4g = self.weight_format.layers == 3
-        buffers = self._WS_BUFFERS + (self._WS_MOE_BUFFERS if self.moe is not None else ()) + \
-            ((("xg", torch.bfloat16),) if w4g else ()) + ((("delta", torch.float32),) if self._lora is not None else ())
-        n = len(buffers)
-        off, cnt = (ctypes.c_size_t * n)(), (ctypes.c_size_t * n)()
-        if self._lora is not None:
-            got = lib().p2pt_llama_ws_layout_lora(ctypes.byref(d), off, cnt, n)
-        elif self.moe is not None:
-            got = lib().p2pt_llama_ws_layout_moe(ctypes.byref(d), ctypes.byref(self.moe), off, cnt, n)
-        elif w4g:
-            got = lib().p2pt_llama_ws_layout_fmt(ctypes.byref(d), ctypes.byref(self.weight_format), off, cnt, n)
-        else:
-            got = lib().p2pt_llama_ws_layout(ctypes.byref(d), off, cnt, n)
-        if got != n:
-            raise RuntimeError("workspace layout: buffer list out of step with decode_fused.hip")
-        views = {}
-        for (name, dtype), o, c in zip(buffers, off, cnt):
-            size = torch.empty(0, dtype=dtype).element_size()
-            if o % size or o + c * size > self.ws.numel():
-                raise RuntimeError(f"workspace layout: {name} lies outside the workspace")
-            views[name] = self.ws[o:o + c * size].view(dtype)
-        M = MAX_ROWS
+        nbytes, layout = workspace_layout(d, self._opts)
+        if nbytes != self.ws.numel():
+            raise RuntimeError("workspace layout: the buffers would lie outside the workspace")
+        M, k = MAX_ROWS, self.moe.top_k if self.moe is not None else 0
         shapes = {"resid": (M, d.dim), "q": (M, d.H, d.D), "attn": (M, d.H * d.D), "h": (M, d.ffn), "ss": (-1, M),
                   "part_o": (M, d.H, -1, d.D), "part_ml": (M, d.H, -1, 2), "am_val": (-1, M), "am_idx": (-1, M),
-                  "counters": (M * d.H,), "qkv": (M if d.qk_norm else 0, (d.H + 2 * d.Hkv) * d.D)}
-        if w4g:
-            shapes["xg"] = (M, d.dim)
-        if self._lora is not None:
-            shapes["delta"] = (M, -1)
-        if self.moe is not None:
-            k = self.moe.top_k
-            shapes.update(route_id=(M, k), route_w=(M, k), route_rs=(M,), moe_h=(M * k, d.ffn), moe_part=(M, k, d.dim))
-        return {name: v.view(*shapes[name]) for name, v in views.items()}
+                  "counters": (M * d.H,), "qkv": (M if d.qk_norm else 0, (d.H + 2 * d.Hkv) * d.D),
+                  "route_id": (M, k), "route_w": (M, k), "route_rs": (M,), "moe_h": (M * k, d.ffn),
+                  "moe_part": (M, k, d.dim), "xg": (M, d.dim), "delta": (M, -1)}
+        return {name: self.ws[o:o + c * dtype.itemsize].view(dtype).view(*shapes[name])
+                for name, (dtype, o, c) in layout.items()}
 
     def embed_pool(self, acc: torch.Tensor, out: torch.Tensor, jobs) -> None:
         """``embed_pool_`` over the rows the last ``step`` left in ``resid`` (the
@@ -2186,58 +2168,6 @@ class FusedLlamaDecoder:
             _check(adapters, torch.int32, "adapters", self.device)
             if adapters.shape != (B,):
                 raise ValueError("adapters must be [B]")
-        if self._lora is not None:
-            _ok(lib().p2pt_llama_decode_lora(ctypes.byref(d), _p(self.kv_scales), self._windows, self._wptr,
-                                             _p(self.k_cache), _p(self.v_cache), _p(tokens), _p(pos), _p(slots), B,
-                                             emit_rows, _p(self.ws), self.ws.numel(), _p(logits), _p(ids),
-                                             _stream(tokens), int(self.chunk_attn), ctypes.byref(self._lora),
-                                             _p(adapters)), "llama_decode")
-            return
-        if self.expert_format.w8:
-            _ok(lib().p2pt_llama_decode_experts(ctypes.byref(d), ctypes.byref(self.weight_format), _p(self.kv_scales),
-                                                self._windows, self._wptr, _p(self.k_cache), _p(self.v_cache),
-                                                _p(tokens), _p(pos), _p(slots), B, emit_rows, _p(self.ws),
-                                                self.ws.numel(), _p(logits), _p(ids), _stream(tokens),
-                                                int(self.chunk_attn), ctypes.byref(self.moe),
-                                                ctypes.byref(self.expert_format)), "llama_decode")
-            return
-        if self.moe is not None:
-            _ok(lib().p2pt_llama_decode_moe(ctypes.byref(d), ctypes.byref(self.weight_format), _p(self.kv_scales),
-                                            self._windows, self._wptr, _p(self.k_cache), _p(self.v_cache), _p(tokens),
-                                            _p(pos), _p(slots), B, emit_rows, _p(self.ws), self.ws.numel(), _p(logits),
-                                            _p(ids), _stream(tokens), int(self.chunk_attn), ctypes.byref(self.moe)),
-                "llama_decode")
-            return
-        if self.chunk_attn:
-            _ok(lib().p2pt_llama_decode_chunk(ctypes.byref(d), ctypes.byref(self.weight_format), _p(self.kv_scales),
-                                              self._windows, self._wptr, _p(self.k_cache), _p(self.v_cache),
-                                              _p(tokens), _p(pos), _p(slots), B, emit_rows, _p(self.ws),
-                                              self.ws.numel(), _p(logits), _p(ids), _stream(tokens), 1), "llama_decode")
-            return
-        if self.weight_format.layers != self.weight_format.lm_head:  # MXFP4: only the _fmt entry point says so
-            _ok(lib().p2pt_llama_decode_fmt(ctypes.byref(d), ctypes.byref(self.weight_format), _p(self.kv_scales),
-                                            self._windows, self._wptr, _p(self.k_cache), _p(self.v_cache), _p(tokens),
-                                            _p(pos), _p(slots), B, emit_rows, _p(self.ws), self.ws.numel(),
-                                            _p(logits), _p(ids), _stream(tokens)), "llama_decode")
-            return
-        if self._windows is not None:
-            _ok(lib().p2pt_llama_decode_win(ctypes.byref(d), ctypes.byref(self._wplan), _p(self.kv_scales),
-                                            self._windows, self._wptr, _p(self.k_cache), _p(self.v_cache), _p(tokens),
-                                            _p(pos), _p(slots), B, emit_rows, _p(self.ws), self.ws.numel(),
-                                            _p(logits), _p(ids), _stream(tokens)), "llama_decode")
-            return
-        if self.kv_scales is not None:
-            _ok(lib().p2pt_llama_decode_kv(ctypes.byref(d), ctypes.byref(self._wplan), _p(self.kv_scales), self._wptr,
-                                           _p(self.k_cache), _p(self.v_cache), _p(tokens), _p(pos), _p(slots), B,
-                                           emit_rows, _p(self.ws), self.ws.numel(), _p(logits), _p(ids),
-                                           _stream(tokens)), "llama_decode")
-            return
-        if self.weight_fp8:
-            _ok(lib().p2pt_llama_decode_w(ctypes.byref(d), ctypes.byref(self._wplan), self._wptr, _p(self.k_cache),
-                                          _p(self.v_cache), _p(tokens), _p(pos), _p(slots), B, emit_rows,
-                                          _p(self.ws), self.ws.numel(), _p(logits), _p(ids), _stream(tokens)),
-                "llama_decode")
-            return
-        _ok(lib().p2pt_llama_decode(ctypes.byref(d), self._wptr, _p(self.k_cache), _p(self.v_cache), _p(tokens),
-                                    _p(pos), _p(slots), B, emit_rows, _p(self.ws), self.ws.numel(), _p(logits),
-                                    _p(ids), _stream(tokens)), "llama_decode")
+        _ok(lib().p2pt_llama_step(ctypes.byref(d), ctypes.byref(self._opts), self._wptr, _p(self.k_cache),
+                                  _p(self.v_cache), _p(tokens), _p(pos), _p(slots), B, emit_rows, _p(self.ws),
+                                  self.ws.numel(), _p(logits), _p(ids), _stream(tokens), _p(adapters)), "llama_decode")

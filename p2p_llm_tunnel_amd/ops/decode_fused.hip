@@ -60,7 +60,7 @@ struct KvPlan {
 };
 KvPlan plan_kv(const LlamaDims& d) { return {d.kv_fp8, d.qk_norm ? d.kv_fp8 : 0}; }
 // The weight format of a step, beside StepPlan for the same reason. It is no field of LlamaDims either (whose
-// layout is pinned too): it travels as an argument of its own through the _w entry points. StepPlan does not
+// layout is pinned too): the _w entry points take it as an argument of its own. StepPlan does not
 // depend on it: FP8 weights change no grid, wave count, load batch or K part.
 struct WeightPlan {
   int w8;  // k_skinny<.., 1>: the five GEMM weights are e4m3 bytes with an fp32 scale per output row
@@ -187,6 +187,18 @@ bool lora_ok(const LlamaDims& d, const LoraTable& t) {
     if (!p2pt_lora::shapes_ok(kMaxM, N[j], K[j], t.rank[j], t.n_adapters)) return false;
   return true;
 }
+// Every option of a step, beside the plans as each of its fields is (mirrored with ctypes): how they travel from the
+// entry points to decode_step(), step_kernels(), the workspace and the weight layout. An all-zero struct is the bf16
+// dense step without scales, windows, chunk attention or adapters. options_ok() is the one list of what is refused.
+struct StepOptions {
+  WeightFormat fmt;             // {0, 0}: bf16
+  const float* kv_scales;       // device (KvScales), or nullptr
+  const int* windows;           // host [n_layers] (Windows), or nullptr
+  int chunk_attn;
+  const MoeDims* moe;           // or nullptr
+  const ExpertFormat* experts;  // or nullptr
+  const LoraTable* lora;        // or nullptr
+};
 // One workgroup per tn subtiles of 16 >> kpl columns of one 16-row tile.
 //  - K parts (GemmArgs::kpl), where asked for (the d_model-wide O and down
 //    projections): the widest tile (16, 8 or 4 columns) whose column tiles
@@ -293,7 +305,7 @@ struct Workspace {
   size_t bytes;
 };
 
-// The workspace buffers in layout order (p2pt_llama_ws_layout reports them in this order).
+// The workspace buffers in layout order (p2pt_llama_step_ws reports all WS_NALL of them in this order).
 // The routed-expert FFN's buffers follow WS_QKV and are empty without MoeDims; WS_NDENSE counts the buffers
 // p2pt_llama_ws_layout reports, WS_NBUF those of p2pt_llama_ws_layout_moe.
 enum WsBuf : int { WS_RESID, WS_Q, WS_ATTN, WS_H, WS_SS, WS_PART_O, WS_PART_ML, WS_AM_VAL, WS_AM_IDX, WS_COUNTERS, WS_QKV,
@@ -311,8 +323,8 @@ struct WsLayout {
 
 // The one place that knows the workspace layout. The counts that depend on a
 // grid are the plan's own, at their worst case over the row count.
-WsLayout ws_layout(const LlamaDims& d, const MoeDims* moe = nullptr, const WeightFormat& f = WeightFormat{0, 0},
-                   bool lora = false) {
+WsLayout ws_layout(const LlamaDims& d, const StepOptions& o) {
+  const MoeDims* moe = o.moe;
   WsLayout l{};
   size_t off = 0;
   auto take = [&](WsBuf b, size_t count, size_t elem) {
@@ -345,18 +357,17 @@ WsLayout ws_layout(const LlamaDims& d, const MoeDims* moe = nullptr, const Weigh
   take(WS_MOE_PART, pairs * d.dim, 4);
   // Grouped int4 weights: xg = bf16(resid * g_next), what the QKV and gate/up GEMMs read. Empty otherwise, and last, so
   // the offsets and the size of every other format are unchanged.
-  take(WS_XG, f.layers == kW4g ? size_t(kMaxM) * d.dim : 0, 2);
+  take(WS_XG, o.fmt.layers == kW4g ? size_t(kMaxM) * d.dim : 0, 2);
   // LoRA adapters: delta fp32 [64][the widest projection], what k_lora_delta leaves for the next k_skinny. One buffer
   // serves a layer's four projections in turn (one stream). Empty otherwise, and last, so nothing else moves.
   const size_t widest = std::max(std::max(size_t(d.H + 2 * d.Hkv) * d.D, size_t(d.dim)), size_t(2) * d.ffn);
-  take(WS_DELTA, lora ? size_t(kMaxM) * widest : 0, 4);
+  take(WS_DELTA, o.lora ? size_t(kMaxM) * widest : 0, 4);
   l.bytes = off;
   return l;
 }
 
-Workspace carve(const LlamaDims& d, uint8_t* base, const MoeDims* moe = nullptr,
-                const WeightFormat& f = WeightFormat{0, 0}, bool lora = false) {
-  const WsLayout l = ws_layout(d, moe, f, lora);
+Workspace carve(const LlamaDims& d, uint8_t* base, const StepOptions& o) {
+  const WsLayout l = ws_layout(d, o);
   Workspace w{};
   auto at = [&](WsBuf b) { return base ? base + l.off[b] : nullptr; };
   w.resid = reinterpret_cast<uint16_t*>(at(WS_RESID));
@@ -639,44 +650,77 @@ bool format_dims_ok(const LlamaDims& d, const WeightFormat& f) {
   return f.layers != kW4g || (d.dim % kW4gGroup == 0 && (d.H * d.D) % kW4gGroup == 0 && d.ffn % kW4gGroup == 0);
 }
 
+// Every refusal that needs no per-call value, in one place: what the step refuses, the kernel lookup, the workspace
+// and the weight layout refuse as well. The row count, slots, adapters, lora->tables and the workspace size are the
+// step's own checks.
+bool options_ok(const LlamaDims& d, const StepOptions& o) {
+  if (!dims_ok(d) || !format_ok(o.fmt) || !format_dims_ok(d, o.fmt)) return false;
+  if (!windows_ok(d, Windows{o.windows})) return false;
+  if (o.moe && (!moe_ok(d, *o.moe) || o.fmt.layers != 0)) return false;  // an MoE model's layers are bf16
+  if (!experts_ok(d, o.experts) || (!o.moe && expert_w8(o.experts))) return false;
+  if (o.lora && (o.moe || o.fmt.layers != 0 || o.fmt.lm_head != 0 || !lora_ok(d, *o.lora))) return false;
+  return !o.kv_scales || d.kv_fp8;  // a bf16 cache has no scales
+}
+// The one format of a WeightPlan for the five GEMMs. format_ok passes {w8, w8} for 0 and 1 alone, so every entry point
+// that takes a WeightPlan refuses w8 = 2 as weights_ok does.
+StepOptions plan_options(const WeightPlan& wp, const float* kv_scales = nullptr, const int* windows = nullptr) {
+  return {{wp.w8, wp.w8}, kv_scales, windows};
+}
+StepOptions moe_options(const MoeDims* moe, const ExpertFormat* experts = nullptr) {
+  return {{0, 0}, nullptr, nullptr, 0, moe, experts};
+}
+
+size_t ws_bytes(const LlamaDims& d, const StepOptions& o) { return options_ok(d, o) ? ws_layout(d, o).bytes : 0; }
+// Offsets and counts of the first `prefix` buffers of WsBuf, then of buffer `extra` where one is named (the kept layout
+// exports report such subsets). Returns how many were written; 0: options refused or n too small, nothing written.
+int ws_report(const LlamaDims& d, const StepOptions& o, size_t* off, size_t* count, int n, int prefix, int extra = -1) {
+  const int total = prefix + (extra >= 0);
+  if (!options_ok(d, o) || n < total) return 0;
+  const WsLayout l = ws_layout(d, o);
+  for (int b = 0; b < total; b++) {
+    const int from = b < prefix ? b : extra;
+    off[b] = l.off[from], count[b] = l.count[from];
+  }
+  return total;
+}
+
+// The weight table of (dims, options) as the step reads it (host only): its length, and into index[L * roles + r] and,
+// where asked for, scale_index[L * roles + r] where role r (enum Role) of layer L and its scales sit, -1 where there is
+// none. roles: R_NROLES, or R_NROLES_MOE to include the router's. -1: options refused, or n < roles * n_layers.
+int weight_layout(const LlamaDims& d, const StepOptions& o, int roles, int* index, int* scale_index, int n) {
+  if (!options_ok(d, o) || n < roles * d.n_layers) return -1;
+  const WeightTable T{d, o.fmt, nullptr, o.moe ? 1 : 0, expert_w8(o.experts)};
+  for (int L = 0; L < d.n_layers; L++)
+    for (int r = 0; r < roles; r++) {
+      index[L * roles + r] = T.index(Role(r), L);
+      if (scale_index) scale_index[L * roles + r] = T.scale_index(Role(r), L);
+    }
+  return T.size();
+}
+
 }  // namespace
 
 extern "C" {
 
-// Workspace bytes for p2pt_llama_decode; it must be zero-filled once before first use
-// (the in-kernel arrival counters reset themselves afterwards).
-size_t p2pt_llama_ws_bytes(const LlamaDims* d) {
-  if (!dims_ok(*d)) return 0;
-  return carve(*d, nullptr).bytes;
+// The workspace of a step with options o: its bytes (0: refused); it must be zero-filled once before first use (the
+// in-kernel arrival counters reset themselves afterwards). Where off and count are given and n >= WS_NALL, also where
+// each buffer lies (tests read the step's intermediates through this): byte offsets and element counts of all WS_NALL
+// buffers in WsBuf order, those the options do not use with count 0.
+size_t p2pt_llama_step_ws(const LlamaDims* d, const StepOptions* o, size_t* off, size_t* count, int n) {
+  if (off && count) ws_report(*d, *o, off, count, n, WS_NALL);
+  return ws_bytes(*d, *o);
 }
-
-// Where each workspace buffer lies (tests read the step's intermediates through
-// this): byte offsets and element counts of resid, q, attn, h, ss, part_o,
-// part_ml, am_val, am_idx, counters, qkv (empty unless qk_norm), in that order, into off[n] / count[n].
+// The bf16 dense step's: resid, q, attn, h, ss, part_o, part_ml, am_val, am_idx, counters, qkv (empty unless qk_norm).
 // Returns the number of buffers, or 0 for unsupported dims or n too small.
+size_t p2pt_llama_ws_bytes(const LlamaDims* d) { return ws_bytes(*d, StepOptions{}); }
 int p2pt_llama_ws_layout(const LlamaDims* d, size_t* off, size_t* count, int n) {
-  if (!dims_ok(*d) || n < WS_NDENSE) return 0;
-  const WsLayout l = ws_layout(*d);
-  for (int b = 0; b < WS_NDENSE; b++) {
-    off[b] = l.off[b];
-    count[b] = l.count[b];
-  }
-  return WS_NDENSE;
+  return ws_report(*d, StepOptions{}, off, count, n, WS_NDENSE);
 }
 // The same for a step with a routed-expert FFN (moe; nullptr: a dense model, whose first eleven buffers and size are
 // those above): route_id, route_w, route_rs, moe_h, moe_part follow qkv. Returns the number of buffers (16), or 0.
-size_t p2pt_llama_ws_bytes_moe(const LlamaDims* d, const MoeDims* moe) {
-  if (!dims_ok(*d) || (moe && !moe_ok(*d, *moe))) return 0;
-  return ws_layout(*d, moe).bytes;
-}
+size_t p2pt_llama_ws_bytes_moe(const LlamaDims* d, const MoeDims* moe) { return ws_bytes(*d, moe_options(moe)); }
 int p2pt_llama_ws_layout_moe(const LlamaDims* d, const MoeDims* moe, size_t* off, size_t* count, int n) {
-  if (!dims_ok(*d) || (moe && !moe_ok(*d, *moe)) || n < WS_NBUF) return 0;
-  const WsLayout l = ws_layout(*d, moe);
-  for (int b = 0; b < WS_NBUF; b++) {
-    off[b] = l.off[b];
-    count[b] = l.count[b];
-  }
-  return WS_NBUF;
+  return ws_report(*d, moe_options(moe), off, count, n, WS_NBUF);
 }
 // What the routed-expert FFN's four kernels launch for B rows, beside the plans below (host only).
 int p2pt_llama_moe_plan(const LlamaDims* d, const MoeDims* moe, int B, MoePlan* out) {
@@ -702,16 +746,9 @@ int p2pt_llama_plan_fmt(const LlamaDims* d, const WeightFormat* fmt, int B, int 
 }
 // The workspace of a step in weight formats fmt: p2pt_llama_ws_bytes' and p2pt_llama_ws_layout's eleven buffers at
 // their offsets, and with grouped int4 layers a twelfth, xg bf16 [64][dim], after them (empty otherwise).
-size_t p2pt_llama_ws_bytes_fmt(const LlamaDims* d, const WeightFormat* fmt) {
-  if (!dims_ok(*d) || !format_ok(*fmt) || !format_dims_ok(*d, *fmt)) return 0;
-  return ws_layout(*d, nullptr, *fmt).bytes;
-}
+size_t p2pt_llama_ws_bytes_fmt(const LlamaDims* d, const WeightFormat* fmt) { return ws_bytes(*d, StepOptions{*fmt}); }
 int p2pt_llama_ws_layout_fmt(const LlamaDims* d, const WeightFormat* fmt, size_t* off, size_t* count, int n) {
-  if (!dims_ok(*d) || !format_ok(*fmt) || !format_dims_ok(*d, *fmt) || n < WS_NDENSE + 1) return 0;
-  const WsLayout l = ws_layout(*d, nullptr, *fmt);
-  for (int b = 0; b < WS_NDENSE; b++) off[b] = l.off[b], count[b] = l.count[b];
-  off[WS_NDENSE] = l.off[WS_XG], count[WS_NDENSE] = l.count[WS_XG];
-  return WS_NDENSE + 1;
+  return ws_report(*d, StepOptions{*fmt}, off, count, n, WS_NDENSE, WS_XG);
 }
 
 // The FP8-cache variants p2pt_llama_decode launches beside the plan above (host only); both 0 for a bf16 cache.
@@ -723,36 +760,25 @@ int p2pt_llama_kv_plan(const LlamaDims* d, KvPlan* out) {
 
 // Whether every stage of the plans above names a kernel that exists, by the launchers' own lookups (host only).
 // 0: all do; 1 + n: stage n, counting qkv_first, qkv, qk_norm, attn, o, gate_up, down, lm_head, is the first that
-// does not; -1: dims or row count refused.
-// windows: the per-layer windows (Windows), nullptr for none: every layer's attention variant must exist, and a
-// windowed layer's slots must fit the partials' stride. A negative window is refused (-1).
-// fmt: the weight formats (WeightFormat); one that is no supported pair is refused (-1).
-// chunk_attn (p2pt_llama_plan_kernels_chunk): the layers chunk_layer names need their k_attn_chunk instead, with its
-// slots inside the stride. p2pt_llama_plan_kernels_fmt is the call without it.
-// moe (p2pt_llama_plan_kernels_moe): stages gate_up and down are then the routed-expert FFN's kernels (all four must
-// exist), bf16 layers only; a MoeDims the step refuses, or FP8 / MXFP4 layers with it, are -1. nullptr: the call without.
-// experts (p2pt_llama_plan_kernels_experts): the format of an MoE model's experts; the gate_up and down stages are then
-// that format's instantiations. FP8 or MXFP4 without moe, or with a dim or ffn that is no multiple of 64 (FP8) or 128
-// (MXFP4), is -1. nullptr: bf16.
-// lora (p2pt_llama_plan_kernels_lora): the four layer stages are then their LORA variants; bf16 dense layers without
-// QK-norm only, anything else is -1. nullptr: the call without.
-static int plan_kernels(const LlamaDims* d, int B, int emit_rows, const WeightFormat* fmt, const int* windows,
-                        int chunk_attn, const MoeDims* moe, const ExpertFormat* experts, const LoraTable* lora) {
-  if (lora && (moe || fmt->layers != 0 || !dims_ok(*d) || !lora_ok(*d, *lora))) return -1;
-  const bool lr = lora != nullptr;
-  if (!dims_ok(*d) || !rows_ok(B) || !format_ok(*fmt) || !windows_ok(*d, Windows{windows})) return -1;
-  if (!format_dims_ok(*d, *fmt)) return -1;
-  if (moe && (!moe_ok(*d, *moe) || fmt->layers != 0)) return -1;
-  if (!experts_ok(*d, experts) || (!moe && expert_w8(experts))) return -1;
+// does not; -1: the options (options_ok) or the row count refused.
+// windows: every layer's attention variant must exist, and a windowed layer's slots must fit the partials' stride.
+// chunk_attn: the layers chunk_layer names need their k_attn_chunk instead, with its slots inside the stride.
+// moe: stages gate_up and down are then the routed-expert FFN's kernels in the experts' format (all four must exist).
+// lora: the four layer stages are then their LORA variants.
+static int step_kernels(const LlamaDims* d, const StepOptions& o, int B, int emit_rows) {
+  if (!options_ok(*d, o) || !rows_ok(B)) return -1;
+  const WeightFormat* fmt = &o.fmt;
+  const MoeDims* moe = o.moe;
+  const bool lr = o.lora != nullptr;
   const bool moe_found =
-      !moe || p2pt_moe::moe_kernels_exist(plan_moe(*d, *moe, B), ExpertFormat{expert_w8(experts)});
+      !moe || p2pt_moe::moe_kernels_exist(plan_moe(*d, *moe, B), ExpertFormat{expert_w8(o.experts)});
   const StepPlan P = plan_step(*d, B, emit_rows, *fmt);
   const KvPlan KV = plan_kv(*d);
   const int w8 = fmt->layers;
   bool attn = true;
   for (int L = 0; L < d->n_layers; L++) {
-    const WindowPlan wn = plan_window(*d, B, Windows{windows}.at(L));
-    if (chunk_layer(chunk_attn, B, wn)) {
+    const WindowPlan wn = plan_window(*d, B, Windows{o.windows}.at(L));
+    if (chunk_layer(o.chunk_attn, B, wn)) {
       const ChunkPlan cp = plan_attn_chunk(B, d->H, d->Hkv, d->D, d->max_seq);
       attn = attn && chunk_kernel(cp.D, cp.G, KV.attn_kv8) != nullptr && cp.slots >= 1 && cp.slots <= cp.stride;
       continue;
@@ -772,39 +798,18 @@ static int plan_kernels(const LlamaDims* d, int B, int emit_rows, const WeightFo
     if (!found[n]) return 1 + n;
   return 0;
 }
+int p2pt_llama_step_kernels(const LlamaDims* d, const StepOptions* o, int B, int emit_rows) {
+  return step_kernels(d, *o, B, emit_rows);
+}
+// The entry points from before StepOptions that tests and scripts call: each is the call above with its arguments as
+// options.
 int p2pt_llama_plan_kernels_experts(const LlamaDims* d, int B, int emit_rows, const WeightFormat* fmt,
                                     const int* windows, int chunk_attn, const MoeDims* moe,
                                     const ExpertFormat* experts) {
-  return plan_kernels(d, B, emit_rows, fmt, windows, chunk_attn, moe, experts, nullptr);
-}
-int p2pt_llama_plan_kernels_lora(const LlamaDims* d, int B, int emit_rows, const int* windows, int chunk_attn,
-                                 const LoraTable* lora) {
-  const WeightFormat bf16{0, 0};
-  return lora ? plan_kernels(d, B, emit_rows, &bf16, windows, chunk_attn, nullptr, nullptr, lora) : -1;
-}
-// The workspace of a decoder with adapters: p2pt_llama_ws_layout's eleven buffers at their offsets and a twelfth,
-// delta fp32 [64][widest projection], after them.
-size_t p2pt_llama_ws_bytes_lora(const LlamaDims* d) {
-  if (!dims_ok(*d) || d->qk_norm) return 0;
-  return ws_layout(*d, nullptr, WeightFormat{0, 0}, true).bytes;
-}
-int p2pt_llama_ws_layout_lora(const LlamaDims* d, size_t* off, size_t* count, int n) {
-  if (!dims_ok(*d) || d->qk_norm || n < WS_NDENSE + 1) return 0;
-  const WsLayout l = ws_layout(*d, nullptr, WeightFormat{0, 0}, true);
-  for (int b = 0; b < WS_NDENSE; b++) off[b] = l.off[b], count[b] = l.count[b];
-  off[WS_NDENSE] = l.off[WS_DELTA], count[WS_NDENSE] = l.count[WS_DELTA];
-  return WS_NDENSE + 1;
-}
-int p2pt_llama_plan_kernels_moe(const LlamaDims* d, int B, int emit_rows, const WeightFormat* fmt, const int* windows,
-                                int chunk_attn, const MoeDims* moe) {
-  return p2pt_llama_plan_kernels_experts(d, B, emit_rows, fmt, windows, chunk_attn, moe, nullptr);
-}
-int p2pt_llama_plan_kernels_chunk(const LlamaDims* d, int B, int emit_rows, const WeightFormat* fmt, const int* windows,
-                                  int chunk_attn) {
-  return p2pt_llama_plan_kernels_moe(d, B, emit_rows, fmt, windows, chunk_attn, nullptr);
+  return step_kernels(d, StepOptions{*fmt, nullptr, windows, chunk_attn, moe, experts}, B, emit_rows);
 }
 int p2pt_llama_plan_kernels_fmt(const LlamaDims* d, int B, int emit_rows, const WeightFormat* fmt, const int* windows) {
-  return p2pt_llama_plan_kernels_chunk(d, B, emit_rows, fmt, windows, 0);
+  return step_kernels(d, StepOptions{*fmt, nullptr, windows}, B, emit_rows);
 }
 // What k_attn_chunk launches for B rows, beside the plans above (host only).
 int p2pt_llama_chunk_plan(const LlamaDims* d, int B, ChunkPlan* out) {
@@ -814,12 +819,10 @@ int p2pt_llama_chunk_plan(const LlamaDims* d, int B, ChunkPlan* out) {
 }
 // The same with one format for the five GEMMs (WeightPlan: bf16 or FP8; anything else is refused).
 int p2pt_llama_plan_kernels_win(const LlamaDims* d, int B, int emit_rows, const WeightPlan* wp, const int* windows) {
-  if (!weights_ok(*wp)) return -1;
-  const WeightFormat f{wp->w8, wp->w8};
-  return p2pt_llama_plan_kernels_fmt(d, B, emit_rows, &f, windows);
+  return step_kernels(d, plan_options(*wp, nullptr, windows), B, emit_rows);
 }
 int p2pt_llama_plan_kernels_w(const LlamaDims* d, int B, int emit_rows, const WeightPlan* wp) {
-  return p2pt_llama_plan_kernels_win(d, B, emit_rows, wp, nullptr);
+  return step_kernels(d, plan_options(*wp), B, emit_rows);
 }
 // What a layer with sliding window `window` (0: none) launches for attention at B rows, beside the plans above
 // (host only).
@@ -829,8 +832,7 @@ int p2pt_llama_window_plan(const LlamaDims* d, int B, int window, WindowPlan* ou
   return 0;
 }
 int p2pt_llama_plan_kernels(const LlamaDims* d, int B, int emit_rows) {
-  const WeightPlan bf16{0};
-  return p2pt_llama_plan_kernels_w(d, B, emit_rows, &bf16);
+  return step_kernels(d, StepOptions{}, B, emit_rows);
 }
 
 // The weight format of a step for weight_fp8 in {0, 1} (host only), beside the plans above.
@@ -854,42 +856,26 @@ int p2pt_llama_weight_format(const LlamaDims* d, int layers, int lm_head, Weight
 // scales of an MXFP4 weight) sit, -1 where there is none.
 // n: ints each array holds, at least 13 * n_layers. -1: dims or formats refused, or n too small.
 int p2pt_llama_weight_layout_fmt(const LlamaDims* d, const WeightFormat* fmt, int* index, int* scale_index, int n) {
-  if (!dims_ok(*d) || !format_ok(*fmt) || !format_dims_ok(*d, *fmt) || n < R_NROLES * d->n_layers) return -1;
-  const WeightTable T{*d, *fmt, nullptr};
-  for (int L = 0; L < d->n_layers; L++)
-    for (int r = 0; r < R_NROLES; r++) {
-      index[L * R_NROLES + r] = T.index(Role(r), L);
-      scale_index[L * R_NROLES + r] = T.scale_index(Role(r), L);
-    }
-  return T.size();
+  return weight_layout(*d, StepOptions{*fmt}, R_NROLES, index, scale_index, n);
 }
-// The same for an MoE table (bf16 only): 14 roles per layer, router (enum Role's R_ROUTER) last; no scales.
+// The same for every option: 14 roles per layer, router (enum Role's R_ROUTER) last and -1 without moe.
+int p2pt_llama_step_weights(const LlamaDims* d, const StepOptions* o, int* index, int* scale_index, int n) {
+  return weight_layout(*d, *o, R_NROLES_MOE, index, scale_index, n);
+}
+// The same for an MoE table (bf16 only): 14 roles per layer; no scales.
 int p2pt_llama_weight_layout_moe(const LlamaDims* d, const MoeDims* moe, int* index, int n) {
-  if (!dims_ok(*d) || !moe_ok(*d, *moe) || n < R_NROLES_MOE * d->n_layers) return -1;
-  const WeightTable T{*d, WeightFormat{0, 0}, nullptr, 1};
-  for (int L = 0; L < d->n_layers; L++)
-    for (int r = 0; r < R_NROLES_MOE; r++) index[L * R_NROLES_MOE + r] = T.index(Role(r), L);
-  return T.size();
+  return weight_layout(*d, moe_options(moe), R_NROLES_MOE, index, nullptr, n);
 }
 // The same with the experts' format (nullptr: bf16, the call above with no scales): scale_index[L * 14 + r] is where the
 // fp32 row scales (FP8) or e8m0 block scales (MXFP4) of role r sit, -1 for every role but w_gate_up and w_down of an
 // FP8- or MXFP4-expert table.
 int p2pt_llama_weight_layout_experts(const LlamaDims* d, const MoeDims* moe, const ExpertFormat* experts, int* index,
                                      int* scale_index, int n) {
-  if (!dims_ok(*d) || !moe_ok(*d, *moe) || !experts_ok(*d, experts) || n < R_NROLES_MOE * d->n_layers) return -1;
-  const WeightTable T{*d, WeightFormat{0, 0}, nullptr, 1, expert_w8(experts)};
-  for (int L = 0; L < d->n_layers; L++)
-    for (int r = 0; r < R_NROLES_MOE; r++) {
-      index[L * R_NROLES_MOE + r] = T.index(Role(r), L);
-      scale_index[L * R_NROLES_MOE + r] = T.scale_index(Role(r), L);
-    }
-  return T.size();
+  return weight_layout(*d, moe_options(moe, experts), R_NROLES_MOE, index, scale_index, n);
 }
 // The same for a WeightPlan (bf16 or FP8 throughout; anything else is refused).
 int p2pt_llama_weight_layout(const LlamaDims* d, const WeightPlan* wp, int* index, int* scale_index, int n) {
-  if (!weights_ok(*wp)) return -1;
-  const WeightFormat f{wp->w8, wp->w8};
-  return p2pt_llama_weight_layout_fmt(d, &f, index, scale_index, n);
+  return weight_layout(*d, plan_options(*wp), R_NROLES, index, scale_index, n);
 }
 
 // k_attn's span rule: tokens per span slot for a row of `len` tokens.
@@ -916,70 +902,60 @@ int p2pt_max_rows() { return kMaxM; }
 //   slots int32 [B] or nullptr: cache slot of each row (< max_batch). Rows of one
 //     slot at consecutive positions form a prefill chunk: every row's K/V is
 //     appended before attention runs, and each row attends up to its own position.
-//   FP8 weights (p2pt_llama_decode_w with WeightPlan::w8): the same table with lm_head, wqkv, wo, w_gate_up and
-//      w_down as e4m3 bytes [N][K] (8-byte aligned), quantised after the fold and the interleave, followed by the
-//      fp32 row scales: lm_head's [vocab], then per layer wqkv's, wo's, w_gate_up's and w_down's, each [N] in the
-//      row order of its weight. Every other entry (embed, norms, inv_freq, bqkv, q_norm, k_norm) is as above.
-//   FP8 cache with scales (p2pt_llama_decode_kv with dims.kv_fp8): kv_scales is a device buffer, fp32
-//      [4][n_layers][Hkv]: 1 / k_scale, 1 / v_scale, k_scale, v_scale, every entry finite and > 0 (the caller's
-//      check). A stored byte is e4m3(clamp(x * (1 / s))) of the head's scale and k_attn undoes it (KvScales).
-//      nullptr: scale 1, which is p2pt_llama_decode_w. Refused with a bf16 cache.
-//   Sliding windows (p2pt_llama_decode_win): windows is a host array of n_layers ints, read during the call only:
-//      0 for a layer with full attention, W >= 1 for one whose rows attend to their last W positions, their own
-//      included. Such a layer runs k_attn<D, G, KV8, true> on the slots of a cache of min(max_seq, W) rows; a layer
-//      with 0 launches what it did. The cache keeps max_seq rows per slot and appends go to pos as before.
-//      nullptr: no windows, which is p2pt_llama_decode_kv. A negative entry is refused.
-//   MXFP4 weights (p2pt_llama_decode_fmt with WeightFormat{2, 1}): the FP8 table with each layer's wqkv, wo, w_gate_up
-//      and w_down as bytes [N][K / 2] (4-byte aligned), two e2m1 nibbles each with the lower k in the low nibble,
-//      quantised after the fold and the interleave, and where the FP8 table has their row scales the e8m0 scale
-//      bytes [N][K / 32] of their 32-element blocks. lm_head and its fp32 row scales are the FP8 table's.
-//      p2pt_llama_decode_win is this call with {w8, w8}.
-//   Chunk attention (p2pt_llama_decode_chunk with chunk_attn != 0; docs/CHUNK_ATTN.md): in a step of more than 16 rows,
-//      every layer without a window runs k_attn_chunk on ChunkPlan's grid instead of k_attn: one K/V pass per 16-row
-//      tile and distinct slot in it. Steps of up to 16 rows and windowed layers launch what they did, and so does
-//      chunk_attn = 0, which is p2pt_llama_decode_fmt. The workspace is the same.
-//   Routed-expert FFN (p2pt_llama_decode_moe with moe != nullptr; docs/MOE.md): dims.ffn is the per-expert
-//      intermediate size, and every layer has a seventh (with q_norm / k_norm or bqkv: last) entry, router, bf16
-//      [E][dim] with the FFN norm folded in; w_gate_up is [E][2 * ffn][dim], folded and pair-interleaved per expert,
-//      w_down [E][dim][ffn]. The layer's gate/up and down kernels give way to k_moe_route, k_moe_gate_up, k_moe_down
-//      and k_moe_combine on MoePlan's grids; every other launch is the dense step's. bf16 layers only. The workspace
-//      is p2pt_llama_ws_bytes_moe's. moe == nullptr is p2pt_llama_decode_chunk, launch for launch.
-//   FP8 experts (p2pt_llama_decode_experts with ExpertFormat::w8; docs/MOE_FP8.md): w_gate_up and w_down are e4m3 bytes
-//      of the same shapes, 16-byte aligned, quantised after the fold and the interleave, every row in k-step-pair
-//      order, and after every other entry of the table come, per layer, their fp32 row scales [E][2 * ffn] and
-//      [E][dim]. k_moe_gate_up and k_moe_down are then their FP8 instantiations on the same MoePlan; every other
-//      launch, the router's included, is unchanged. dim and ffn must be multiples of 64. experts == nullptr (or w8 = 0)
-//      is p2pt_llama_decode_moe, launch for launch; FP8 experts without moe are refused.
-//   MXFP4 experts (ExpertFormat::w8 = 2; docs/MOE_MXFP4.md): w_gate_up and w_down are nibble bytes of half the element
-//      count, 16-byte aligned, every row in k-step-quad order, and where the FP8-expert table has row scales come their
-//      e8m0 block scales [E][2 * ffn][dim / 32] and [E][dim][ffn / 32], natural order, 4-byte aligned. The MXFP4
-//      instantiations run on the same MoePlan. dim and ffn must be multiples of 128.
-//   LoRA adapters (p2pt_llama_decode_lora with lora != nullptr; docs/LORA.md): bf16 dense layers without QK-norm. The
-//      workspace is p2pt_llama_ws_bytes_lora's. adapters: int32 [B] on the device, the adapter of each row, -1 for
-//      none. Ahead of each of a layer's four projections k_lora_delta writes the rows' low-rank term into the
-//      workspace's delta, and the projection runs as its LORA variant on the same plan: 9 kernels per layer, one
-//      stream. adapters == nullptr launches the base step on the larger workspace, launch for launch.
-static int decode_step(const LlamaDims* dp, const WeightFormat* fmt, const float* kv_scales, const int* windows,
-                       const void* const* w, void* k_cache, void* v_cache, const int64_t* tokens, const int* pos,
-                       const int* slots, int B, int emit_rows, void* ws, size_t ws_bytes, void* logits, int64_t* ids,
-                       void* stream, int chunk_attn, const MoeDims* moe, const ExpertFormat* experts,
-                       const LoraTable* lora, const int* adapters) {
+//   ws, ws_bytes: the workspace, p2pt_llama_step_ws' bytes of the same options at least
+//   adapters int32 [B] on the device or nullptr (with o.lora only): the adapter of each row, -1 for none
+// The options (StepOptions; options_ok refuses what is not served). The all-zero struct launches the bf16 dense step,
+// and each field left zero leaves every launch, the table and the workspace what they are without it.
+//   fmt, the weight formats. {1, 1}, FP8: the same table with lm_head, wqkv, wo, w_gate_up and w_down as e4m3 bytes
+//      [N][K] (8-byte aligned), quantised after the fold and the interleave, followed by the fp32 row scales: lm_head's
+//      [vocab], then per layer wqkv's, wo's, w_gate_up's and w_down's, each [N] in the row order of its weight. Every
+//      other entry (embed, norms, inv_freq, bqkv, q_norm, k_norm) is as above. {2, 1}, MXFP4: the FP8 table with each
+//      layer's four as bytes [N][K / 2] (4-byte aligned), two e2m1 nibbles each with the lower k in the low nibble,
+//      quantised after the fold and the interleave, and where the FP8 table has their row scales the e8m0 scale bytes
+//      [N][K / 32] of their 32-element blocks; lm_head and its row scales are the FP8 table's. {3, 0}, grouped int4:
+//      the table above WeightTable and docs/WEIGHT_INT4.md describe, and one more workspace buffer, xg.
+//   kv_scales (with dims.kv_fp8; refused with a bf16 cache): a device buffer, fp32 [4][n_layers][Hkv]: 1 / k_scale,
+//      1 / v_scale, k_scale, v_scale, every entry finite and > 0 (the caller's check). A stored byte is
+//      e4m3(clamp(x * (1 / s))) of the head's scale and k_attn undoes it (KvScales). nullptr: scale 1.
+//   windows: a host array of n_layers ints, read during the call only: 0 for a layer with full attention, W >= 1 for
+//      one whose rows attend to their last W positions, their own included. Such a layer runs k_attn<D, G, KV8, true>
+//      on the slots of a cache of min(max_seq, W) rows; a layer with 0 launches what it did. The cache keeps max_seq
+//      rows per slot and appends go to pos as before. nullptr: no windows. A negative entry is refused.
+//   chunk_attn (docs/CHUNK_ATTN.md): in a step of more than 16 rows, every layer without a window runs k_attn_chunk on
+//      ChunkPlan's grid instead of k_attn: one K/V pass per 16-row tile and distinct slot in it. Steps of up to 16 rows
+//      and windowed layers launch what they did. The workspace is the same.
+//   moe (docs/MOE.md; bf16 layers only): dims.ffn is the per-expert intermediate size, and every layer has a seventh
+//      (with q_norm / k_norm or bqkv: last) entry, router, bf16 [E][dim] with the FFN norm folded in; w_gate_up is
+//      [E][2 * ffn][dim], folded and pair-interleaved per expert, w_down [E][dim][ffn]. The layer's gate/up and down
+//      kernels give way to k_moe_route, k_moe_gate_up, k_moe_down and k_moe_combine on MoePlan's grids; every other
+//      launch is the dense step's. The workspace has the five route and expert buffers.
+//   experts (with moe only; nullptr or w8 = 0: bf16). w8 = 1, FP8 (docs/MOE_FP8.md): w_gate_up and w_down are e4m3
+//      bytes of the same shapes, 16-byte aligned, quantised after the fold and the interleave, every row in
+//      k-step-pair order, and after every other entry of the table come, per layer, their fp32 row scales
+//      [E][2 * ffn] and [E][dim]; dim and ffn must be multiples of 64. w8 = 2, MXFP4 (docs/MOE_MXFP4.md): nibble bytes
+//      of half the element count, 16-byte aligned, every row in k-step-quad order, and where the FP8-expert table has
+//      row scales their e8m0 block scales [E][2 * ffn][dim / 32] and [E][dim][ffn / 32], natural order, 4-byte
+//      aligned; dim and ffn must be multiples of 128. k_moe_gate_up and k_moe_down are then that format's
+//      instantiations on the same MoePlan; every other launch, the router's included, is unchanged.
+//   lora (docs/LORA.md; bf16 dense layers without QK-norm): the workspace has one more buffer, delta. Ahead of each of
+//      a layer's four projections k_lora_delta writes the rows' low-rank term there, and the projection runs as its
+//      LORA variant on the same plan: 9 kernels per layer, one stream. adapters == nullptr launches the base step on
+//      the larger workspace, launch for launch.
+static int decode_step(const LlamaDims* dp, const StepOptions& o, const void* const* w, void* k_cache, void* v_cache,
+                       const int64_t* tokens, const int* pos, const int* slots, int B, int emit_rows, void* ws,
+                       size_t ws_bytes, void* logits, int64_t* ids, void* stream, const int* adapters) {
   const LlamaDims d = *dp;
-  if (lora && (moe || fmt->layers != 0 || fmt->lm_head != 0 || !dims_ok(d) || !lora_ok(d, *lora)))
-    return int(hipErrorInvalidValue);
+  const WeightFormat* fmt = &o.fmt;
+  const MoeDims* moe = o.moe;
+  const LoraTable* lora = o.lora;
+  if (!options_ok(d, o) || !rows_ok(B) || (!slots && B > d.max_batch)) return int(hipErrorInvalidValue);
   if ((adapters && !lora) || (lora && !lora->tables)) return int(hipErrorInvalidValue);
   const bool lr = lora && adapters;
-  if (!dims_ok(d) || !rows_ok(B) || (!slots && B > d.max_batch) || !format_ok(*fmt)) return int(hipErrorInvalidValue);
-  if (!format_dims_ok(d, *fmt)) return int(hipErrorInvalidValue);
-  if (moe && (!moe_ok(d, *moe) || fmt->layers != 0)) return int(hipErrorInvalidValue);
-  if (!experts_ok(d, experts) || (!moe && expert_w8(experts))) return int(hipErrorInvalidValue);
-  const ExpertFormat EF{expert_w8(experts)};
-  if (kv_scales && !d.kv_fp8) return int(hipErrorInvalidValue);
-  const Windows WN{windows};
-  if (!windows_ok(d, WN)) return int(hipErrorInvalidValue);
-  const KvScales KS{kv_scales};
+  const ExpertFormat EF{expert_w8(o.experts)};
+  const Windows WN{o.windows};
+  const KvScales KS{o.kv_scales};
   const int w8 = fmt->layers;
-  const Workspace W = carve(d, static_cast<uint8_t*>(ws), moe, *fmt, lora != nullptr);
+  const Workspace W = carve(d, static_cast<uint8_t*>(ws), o);
   if (ws_bytes < W.bytes) return int(hipErrorInvalidValue);
   const StepPlan P = plan_step(d, B, emit_rows, *fmt);
   // k_lora_delta for projection j of layer L on the operand its k_skinny reads, and that k_skinny's delta argument.
@@ -1045,7 +1021,7 @@ static int decode_step(const LlamaDims* dp, const WeightFormat* fmt, const float
         return int(e);
     }
     const WindowPlan wn = plan_window(d, B, WN.at(L));
-    if (chunk_layer(chunk_attn, B, wn)) {
+    if (chunk_layer(o.chunk_attn, B, wn)) {
       if (failed(launch_attn_chunk(CP, KV.attn_kv8, W.q, kc, vc, pos, slots, B, d.max_batch, W.part_o, W.part_ml,
                                    W.counters, W.attn, d.H, d.Hkv, d.max_seq, s, KS.at(d, KvScales::K, L),
                                    KS.at(d, KvScales::V, L))))
@@ -1077,71 +1053,53 @@ static int decode_step(const LlamaDims* dp, const WeightFormat* fmt, const float
   hipLaunchKernelGGL(k_argmax_merge, dim3(P.emit_rows), dim3(256), 0, s, W.am_val, W.am_idx, P.am_parts, ids);
   return int(hipGetLastError());
 }
-int p2pt_llama_decode_experts(const LlamaDims* dp, const WeightFormat* fmt, const float* kv_scales, const int* windows,
-                              const void* const* w, void* k_cache, void* v_cache, const int64_t* tokens,
-                              const int* pos, const int* slots, int B, int emit_rows, void* ws, size_t ws_bytes,
-                              void* logits, int64_t* ids, void* stream, int chunk_attn, const MoeDims* moe,
-                              const ExpertFormat* experts) {
-  return decode_step(dp, fmt, kv_scales, windows, w, k_cache, v_cache, tokens, pos, slots, B, emit_rows, ws, ws_bytes,
-                     logits, ids, stream, chunk_attn, moe, experts, nullptr, nullptr);
+int p2pt_llama_step(const LlamaDims* dp, const StepOptions* o, const void* const* w, void* k_cache, void* v_cache,
+                    const int64_t* tokens, const int* pos, const int* slots, int B, int emit_rows, void* ws,
+                    size_t ws_bytes, void* logits, int64_t* ids, void* stream, const int* adapters) {
+  return decode_step(dp, *o, w, k_cache, v_cache, tokens, pos, slots, B, emit_rows, ws, ws_bytes, logits, ids, stream,
+                     adapters);
 }
-int p2pt_llama_decode_lora(const LlamaDims* dp, const float* kv_scales, const int* windows, const void* const* w,
-                           void* k_cache, void* v_cache, const int64_t* tokens, const int* pos, const int* slots, int B,
-                           int emit_rows, void* ws, size_t ws_bytes, void* logits, int64_t* ids, void* stream,
-                           int chunk_attn, const LoraTable* lora, const int* adapters) {
-  const WeightFormat bf16{0, 0};
-  if (!lora) return int(hipErrorInvalidValue);
-  return decode_step(dp, &bf16, kv_scales, windows, w, k_cache, v_cache, tokens, pos, slots, B, emit_rows, ws,
-                     ws_bytes, logits, ids, stream, chunk_attn, nullptr, nullptr, lora, adapters);
-}
+// The entry points from before StepOptions that tests and scripts call: each is the step above with its arguments as
+// options.
 int p2pt_llama_decode_moe(const LlamaDims* dp, const WeightFormat* fmt, const float* kv_scales, const int* windows,
                           const void* const* w, void* k_cache, void* v_cache, const int64_t* tokens, const int* pos,
                           const int* slots, int B, int emit_rows, void* ws, size_t ws_bytes, void* logits,
                           int64_t* ids, void* stream, int chunk_attn, const MoeDims* moe) {
-  return p2pt_llama_decode_experts(dp, fmt, kv_scales, windows, w, k_cache, v_cache, tokens, pos, slots, B, emit_rows,
-                                   ws, ws_bytes, logits, ids, stream, chunk_attn, moe, nullptr);
+  return decode_step(dp, StepOptions{*fmt, kv_scales, windows, chunk_attn, moe}, w, k_cache, v_cache, tokens, pos, slots,
+                     B, emit_rows, ws, ws_bytes, logits, ids, stream, nullptr);
 }
 int p2pt_llama_decode_chunk(const LlamaDims* dp, const WeightFormat* fmt, const float* kv_scales, const int* windows,
                             const void* const* w, void* k_cache, void* v_cache, const int64_t* tokens, const int* pos,
                             const int* slots, int B, int emit_rows, void* ws, size_t ws_bytes, void* logits,
                             int64_t* ids, void* stream, int chunk_attn) {
-  return p2pt_llama_decode_moe(dp, fmt, kv_scales, windows, w, k_cache, v_cache, tokens, pos, slots, B, emit_rows, ws,
-                               ws_bytes, logits, ids, stream, chunk_attn, nullptr);
+  return decode_step(dp, StepOptions{*fmt, kv_scales, windows, chunk_attn}, w, k_cache, v_cache, tokens, pos, slots, B,
+                     emit_rows, ws, ws_bytes, logits, ids, stream, nullptr);
 }
 int p2pt_llama_decode_fmt(const LlamaDims* dp, const WeightFormat* fmt, const float* kv_scales, const int* windows,
                           const void* const* w, void* k_cache, void* v_cache, const int64_t* tokens, const int* pos,
                           const int* slots, int B, int emit_rows, void* ws, size_t ws_bytes, void* logits,
                           int64_t* ids, void* stream) {
-  return p2pt_llama_decode_chunk(dp, fmt, kv_scales, windows, w, k_cache, v_cache, tokens, pos, slots, B, emit_rows, ws,
-                                 ws_bytes, logits, ids, stream, 0);
+  return decode_step(dp, StepOptions{*fmt, kv_scales, windows}, w, k_cache, v_cache, tokens, pos, slots, B, emit_rows,
+                     ws, ws_bytes, logits, ids, stream, nullptr);
 }
 int p2pt_llama_decode_win(const LlamaDims* dp, const WeightPlan* wp, const float* kv_scales, const int* windows,
                           const void* const* w, void* k_cache, void* v_cache, const int64_t* tokens, const int* pos,
                           const int* slots, int B, int emit_rows, void* ws, size_t ws_bytes, void* logits,
                           int64_t* ids, void* stream) {
-  if (!weights_ok(*wp)) return int(hipErrorInvalidValue);
-  const WeightFormat f{wp->w8, wp->w8};
-  return p2pt_llama_decode_fmt(dp, &f, kv_scales, windows, w, k_cache, v_cache, tokens, pos, slots, B, emit_rows, ws,
-                               ws_bytes, logits, ids, stream);
-}
-int p2pt_llama_decode_kv(const LlamaDims* dp, const WeightPlan* wp, const float* kv_scales, const void* const* w,
-                         void* k_cache, void* v_cache, const int64_t* tokens, const int* pos, const int* slots, int B,
-                         int emit_rows, void* ws, size_t ws_bytes, void* logits, int64_t* ids, void* stream) {
-  return p2pt_llama_decode_win(dp, wp, kv_scales, nullptr, w, k_cache, v_cache, tokens, pos, slots, B, emit_rows, ws,
-                               ws_bytes, logits, ids, stream);
+  return decode_step(dp, plan_options(*wp, kv_scales, windows), w, k_cache, v_cache, tokens, pos, slots, B, emit_rows,
+                     ws, ws_bytes, logits, ids, stream, nullptr);
 }
 int p2pt_llama_decode_w(const LlamaDims* dp, const WeightPlan* wp, const void* const* w, void* k_cache, void* v_cache,
                         const int64_t* tokens, const int* pos, const int* slots, int B, int emit_rows, void* ws,
                         size_t ws_bytes, void* logits, int64_t* ids, void* stream) {
-  return p2pt_llama_decode_kv(dp, wp, nullptr, w, k_cache, v_cache, tokens, pos, slots, B, emit_rows, ws, ws_bytes,
-                              logits, ids, stream);
+  return decode_step(dp, plan_options(*wp), w, k_cache, v_cache, tokens, pos, slots, B, emit_rows, ws, ws_bytes, logits,
+                     ids, stream, nullptr);
 }
 int p2pt_llama_decode(const LlamaDims* dp, const void* const* w, void* k_cache, void* v_cache, const int64_t* tokens,
                       const int* pos, const int* slots, int B, int emit_rows, void* ws, size_t ws_bytes, void* logits,
                       int64_t* ids, void* stream) {
-  const WeightPlan bf16{0};
-  return p2pt_llama_decode_w(dp, &bf16, w, k_cache, v_cache, tokens, pos, slots, B, emit_rows, ws, ws_bytes, logits,
-                             ids, stream);
+  return decode_step(dp, StepOptions{}, w, k_cache, v_cache, tokens, pos, slots, B, emit_rows, ws, ws_bytes, logits, ids,
+                     stream, nullptr);
 }
 
 // Standalone skinny GEMM (tests/benchmarks): out[M][N] = bf16(x[M][K] @ w[N][K]^T), M <= 64.
