@@ -240,15 +240,30 @@ class _Reader:
 # against those libraries, which this project does not depend on.
 _AWQ_ORDER = (0, 2, 4, 6, 1, 3, 5, 7)  # nibble i of an AWQ word is column 8 c + _AWQ_ORDER[i]
 _INT4_GROUP = 128
+_FP8_BLOCK = 128  # block-FP8 checkpoints (docs/WEIGHT_FP8G128.md): one weight_scale_inv entry per 128 x 128 block
 
 
 def read_quantization(raw: dict) -> dict | None:
     """The ``quantization_config`` of a checkpoint's config.json as the loader serves it: None without one, else
-    ``{"method": "gptq" | "awq", "zero_offset": 0 | 1}``; everything the int4 kernels do not run is refused."""
+    ``{"method": "gptq" | "awq", "zero_offset": 0 | 1}``; everything the int4 kernels do not run is refused. A block-FP8
+    checkpoint (``quant_method`` "fp8" with ``weight_block_size`` [128, 128]; docs/WEIGHT_FP8G128.md) gives
+    ``{"method": "fp8", "skip": modules_to_not_convert}``; its ``activation_scheme`` is not read (activations stay
+    bf16 here)."""
     qc = raw.get("quantization_config")
     if qc is None:
         return None
     method = qc.get("quant_method")
+    if method == "fp8":
+        block = qc.get("weight_block_size")
+        if block is None:
+            raise ValueError("quantization_config: quant_method 'fp8' without weight_block_size (one scale per tensor) "
+                             f"is not supported: the block-FP8 kernels run blocks of [{_FP8_BLOCK}, {_FP8_BLOCK}]")
+        if list(block) != [_FP8_BLOCK, _FP8_BLOCK]:
+            raise ValueError(f"quantization_config: weight_block_size {block!r} is not supported: the block-FP8 kernels "
+                             f"run blocks of [{_FP8_BLOCK}, {_FP8_BLOCK}]")
+        if raw.get("num_local_experts") or raw.get("num_experts"):
+            raise ValueError("quantization_config: a quantised MoE checkpoint is not supported")
+        return {"method": "fp8", "skip": tuple(qc.get("modules_to_not_convert") or ())}
     if method not in ("gptq", "awq"):
         raise ValueError(f"quantization_config: quant_method {method!r} is not supported (gptq and awq are)")
     bits, group = qc.get("bits", qc.get("w_bit")), qc.get("group_size", qc.get("q_group_size"))
@@ -307,10 +322,41 @@ def unpack_int4_linear(quant: dict, get, has, name: str, N: int, K: int):
     return q.contiguous(), z.contiguous().to(torch.uint8), sc.T.contiguous()
 
 
-def _int4_layer(c, quant, rd, p, t, dev) -> dict:
-    """One layer of a GPTQ / AWQ checkpoint as ``TinyLlama`` takes int4 weights: ``name_q`` / ``name_s`` of each of the
-    four GEMMs (q|k|v and gate|up stacked by rows, rows in the fused table's order, ``ops.pack_weight_w4g``), the norm
-    weights and a q / k / v bias as bf16."""
+def _not_converted(skip: tuple, module: str) -> str | None:
+    """The entry of ``modules_to_not_convert`` that names ``module`` (a full name such as
+    ``model.layers.0.mlp.up_proj``), or None: the name itself, a suffix of it from a dot on (``up_proj``,
+    ``mlp.up_proj``) or a prefix of it up to one (``model.layers.0``)."""
+    return next((e for e in skip if module == e or module.endswith("." + e) or module.startswith(e + ".")), None)
+
+
+def unpack_fp8_linear(quant: dict, get, has, name: str, N: int, K: int):
+    """One block-FP8 linear layer ``name`` (``.weight`` e4m3 [N, K] and ``.weight_scale_inv`` fp32 or bf16
+    [ceil(N / 128), ceil(K / 128)]; the dequantised weight is their product) as ``(q, s)``: the bytes as they are and
+    the scales expanded to one per row and 128 input features, fp32 [N, K / 128]. K is a multiple of 128 (the model's
+    dims are checked ahead of this); N need not be."""
+    entry = _not_converted(quant["skip"], name)
+    if entry is not None:
+        raise ValueError(f"{name}: modules_to_not_convert ({entry!r}) keeps it out of FP8, but a layer's GEMM weights are "
+                         "served in one format: a block-FP8 checkpoint with bf16 layer projections is not supported")
+    if not has(name + ".weight_scale_inv"):
+        raise KeyError(f"checkpoint has no tensor {name + '.weight_scale_inv'!r}: a block-FP8 checkpoint ships one "
+                       "beside every linear weight")
+    w, s = get(name + ".weight"), get(name + ".weight_scale_inv")
+    if w.dtype != torch.float8_e4m3fn or tuple(w.shape) != (N, K):
+        raise ValueError(f"{name}.weight: {w.dtype} {tuple(w.shape)} != expected torch.float8_e4m3fn {(N, K)}")
+    want = (-(-N // _FP8_BLOCK), -(-K // _FP8_BLOCK))
+    if tuple(s.shape) != want:
+        raise ValueError(f"{name}.weight_scale_inv: shape {tuple(s.shape)} != expected {want}")
+    if s.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"{name}.weight_scale_inv: {s.dtype} is not supported (fp32 and bf16 are)")
+    return w, s.float().repeat_interleave(_FP8_BLOCK, 0)[:N].contiguous()
+
+
+def _quantised_layer(c, quant, rd, p, t, dev) -> dict:
+    """One layer of a quantised checkpoint as ``TinyLlama`` takes it: ``name_q`` / ``name_s`` of each of the four GEMMs
+    (q|k|v and gate|up stacked by rows, rows in the fused table's order), the norm weights and a q / k / v bias as bf16.
+    GPTQ / AWQ: int4 weights by ``ops.pack_weight_w4g``. Block-FP8: fp8g128 weights, bytes and expanded scales stacked
+    and reordered by rows together, bytes by ``ops.pack_weight_fp8g128``."""
     from p2p_llm_tunnel_amd import ops
     from p2p_llm_tunnel_amd.models.tiny_llm import fused_row_perm
     q_out, kv_out = c.n_heads * c.head_dim, c.n_kv_heads * c.head_dim
@@ -321,14 +367,19 @@ def _int4_layer(c, quant, rd, p, t, dev) -> dict:
              "w_down": [("mlp.down_proj", c.dim, c.ffn)]}
     L = {"attn_norm": t(p + "input_layernorm.weight", (c.dim,)),
          "ffn_norm": t(p + "post_attention_layernorm.weight", (c.dim,))}
+    fp8 = quant["method"] == "fp8"
+    unpack = unpack_fp8_linear if fp8 else unpack_int4_linear
     for name, srcs in parts.items():
-        qzs = [unpack_int4_linear(quant, rd.get, rd.has, p + n, N, K) for n, N, K in srcs]
-        q, z, s = (torch.cat([x[j] for x in qzs], 0) for j in range(3))
+        # (q, s) of a block-FP8 linear, (q, z, s) of an int4 one: stacked and reordered by rows alike
+        parts_ = [unpack(quant, rd.get, rd.has, p + n, N, K) for n, N, K in srcs]
+        stacked = [torch.cat([x[j] for x in parts_], 0) for j in range(len(parts_[0]))]
         perm = fused_row_perm(c, name, "cpu")
         if perm is not None:
-            q, z, s = q[perm], z[perm], s[perm]
-        nib, grp = ops.pack_weight_w4g(q.contiguous(), z.contiguous(), s.contiguous())
-        L[name + "_q"], L[name + "_s"] = nib.to(dev), grp.to(dev)
+            stacked = [x.view(torch.uint8)[perm].view(x.dtype) if x.dtype == torch.float8_e4m3fn else x[perm]
+                       for x in stacked]
+        stacked = [x.contiguous() for x in stacked]
+        wq, ws = (ops.pack_weight_fp8g128(stacked[0]), stacked[1]) if fp8 else ops.pack_weight_w4g(*stacked)
+        L[name + "_q"], L[name + "_s"] = wq.to(dev), ws.to(dev)
     for n in ("self_attn.o_proj", "mlp.gate_proj", "mlp.up_proj", "mlp.down_proj"):
         if rd.has(p + n + ".bias"):
             raise ValueError(f"{p}{n}.bias: only q, k and v projection biases are supported by the decode kernels")
@@ -355,7 +406,9 @@ def load_llama(path: str, device="cuda", max_batch: int = 8, max_seq: int | None
     the device never holds the bf16 and the quantised copies of all layers together. The checkpoint itself is bf16 / fp16
     / fp32 either way, except that a ``quantization_config`` of ``quant_method`` gptq or awq (4 bits, groups of 128)
     is detected and its layers are served as they are, as "int4g128" (docs/WEIGHT_INT4.md), with no flag; "int4g128"
-    on a bf16 checkpoint quantises it round-to-nearest. ``expert_dtype``: "bf16", "fp8"
+    on a bf16 checkpoint quantises it round-to-nearest. A ``quant_method`` of fp8 with ``weight_block_size`` [128, 128]
+    (e4m3 weights with a ``weight_scale_inv`` per linear) is served as it is too, as "fp8g128"
+    (docs/WEIGHT_FP8G128.md); "fp8g128" on a bf16 checkpoint quantises it per 1 x 128 group. ``expert_dtype``: "bf16", "fp8"
     (docs/MOE_FP8.md; MoE checkpoints only): the stacked experts as e4m3 bytes with per-row scales, each layer's stack
     quantised as soon as it is read (``quantize_experts_``), every other weight bf16; or "mxfp4" (docs/MOE_MXFP4.md):
     the stacks as MXFP4 nibble bytes with e8m0 block scales, quantised layer by layer in the same place. ``chunk_attn``: ``TinyLlama``'s
@@ -374,19 +427,28 @@ def load_llama(path: str, device="cuda", max_batch: int = 8, max_seq: int | None
     cfg, raw = read_config(path, max_seq, sliding_window)
     # A GPTQ / AWQ checkpoint is served as int4g128 without a flag; another weight format on it is refused.
     quant = read_quantization(raw)
-    if quant is not None:
+    if quant is not None and quant["method"] == "fp8":  # a block-FP8 checkpoint, as fp8g128, likewise
+        if weight_dtype not in ("bf16", "fp8g128"):
+            raise ValueError(f"weight_dtype {weight_dtype!r} on a block-FP8 checkpoint: its e4m3 weights are served as "
+                             "they are (fp8g128)")
+        if not fused:
+            raise ValueError("a block-FP8 checkpoint runs the fused step only: load with fused=True")
+        weight_dtype = "fp8g128"
+    elif quant is not None:
         if weight_dtype not in ("bf16", "int4g128"):
             raise ValueError(f"weight_dtype {weight_dtype!r} on a {quant['method']} checkpoint: its 4-bit weights are "
                              "served as they are (int4g128)")
         if not fused:
             raise ValueError(f"a {quant['method']} checkpoint runs the fused step only: load with fused=True")
         weight_dtype = "int4g128"
+    if weight_dtype == "fp8g128":  # ahead of any tensor: every K in whole groups of 128
+        from p2p_llm_tunnel_amd.models.tiny_llm import llama_dims
+        ops.check_w4g_dims(llama_dims(cfg, 1), "fp8g128")
     if cfg.windowed and not fused:
         raise ValueError("a sliding window runs the fused step only: load with fused=True")
     if cfg.n_experts and weight_dtype != "bf16":
         raise ValueError(f"an MoE checkpoint's expert weights are served as bf16 only: weight_dtype {weight_dtype!r} "
                          "is not supported with a routed-expert FFN (expert_dtype='fp8' quantises the experts)")
-    from p2p_llm_tunnel_amd import ops
     ops.as_expert_format(expert_dtype, cfg.moe, cfg.dim, cfg.ffn)  # a dense checkpoint, or shapes that do not block
     if expert_dtype != "bf16" and not fused:
         raise ValueError(f"{expert_dtype.upper()} experts run the fused step only: load with fused=True")
@@ -416,10 +478,13 @@ def load_llama(path: str, device="cuda", max_batch: int = 8, max_seq: int | None
             kv_scales = kvs.read_checkpoint(rd.has, rd.get, c.n_layers, c.n_kv_heads, prefix)
         if quant is not None and (rd.has("lm_head.qweight") or rd.has(prefix + "embed_tokens.qweight")):
             raise ValueError("a quantised lm_head or embedding is not supported: GPTQ and AWQ leave them fp16")
+        if quant is not None and (rd.has("lm_head.weight_scale_inv") or rd.has(prefix + "embed_tokens.weight_scale_inv")):
+            raise ValueError("a quantised lm_head or embedding is not supported: the block-FP8 kernels run a layer's "
+                             "four GEMM weights, and the LM head stays bf16")
         for i in range(c.n_layers):
             p = f"{prefix}layers.{i}."
             if quant is not None:
-                w["layers"].append(_int4_layer(c, quant, rd, p, t, dev))
+                w["layers"].append(_quantised_layer(c, quant, rd, p, t, dev))
                 continue
             q = t(p + "self_attn.q_proj.weight", (q_out, c.dim))
             k = t(p + "self_attn.k_proj.weight", (kv_out, c.dim))

@@ -799,8 +799,8 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
     With ``penalties`` the endpoint takes the parameters ``penalty_params``
     describes instead of answering 400; with ``guided`` /v1/chat/completions and
     /v1/completions act on what ``guided_params`` describes, which is ignored
-    without the switch. ``weight_dtype`` ("bf16", "fp8" or "mxfp4", the format of the GEMM weights:
-    docs/WEIGHT_FP8.md, docs/WEIGHT_MXFP4.md) is ``Engine``'s and ``load_llama``'s, and an injected engine's model must have it.
+    without the switch. ``weight_dtype`` ("bf16", "fp8", "mxfp4", "int4g128" or "fp8g128", the format of the GEMM
+    weights: docs/WEIGHT_FP8.md, docs/WEIGHT_MXFP4.md, docs/WEIGHT_INT4.md, docs/WEIGHT_FP8G128.md) is ``Engine``'s and ``load_llama``'s, and an injected engine's model must have it.
     ``kv_scales`` (``kv_dtype="fp8"`` only): a ``KvScales``, the path of a JSON file ``{"k": [[..]], "v": [[..]]}``
     or "checkpoint" (the checkpoint's own ``k_scale`` / ``v_scale`` tensors): per-layer, per-KV-head scales of the
     FP8 cache (docs/KV_FP8.md); an injected engine's model must carry the same.
@@ -914,12 +914,12 @@ def parse_kv_dtype(v) -> str:
     return v
 
 
-WEIGHT_DTYPE_CHOICES = ("bf16", "fp8", "mxfp4", "int4g128")
+WEIGHT_DTYPE_CHOICES = ("bf16", "fp8", "mxfp4", "int4g128", "fp8g128")
 
 
 def parse_weight_dtype(v) -> str:
-    """--weight-dtype / ``start_server(weight_dtype=)``: "bf16" (the default), "fp8", "mxfp4" or "int4g128" (grouped int4,
-    docs/WEIGHT_INT4.md); anything else is refused."""
+    """--weight-dtype / ``start_server(weight_dtype=)``: "bf16" (the default), "fp8", "mxfp4", "int4g128" (grouped int4,
+    docs/WEIGHT_INT4.md) or "fp8g128" (block-scaled FP8, docs/WEIGHT_FP8G128.md); anything else is refused."""
     if v not in WEIGHT_DTYPE_CHOICES:
         raise ValueError(f"weight_dtype must be one of {list(WEIGHT_DTYPE_CHOICES)}, got {v!r}")
     return v
@@ -1106,7 +1106,10 @@ def arg_parser() -> argparse.ArgumentParser:
                          "calibration; the LM head is fp8): about a quarter of their bytes (docs/WEIGHT_MXFP4.md); or "
                          "int4g128 (uint4 with an fp16 scale and a zero point per group of 128 input features for "
                          "the four GEMM weights of every layer, GPTQ / AWQ style, round to nearest; the LM head "
-                         "stays bf16; docs/WEIGHT_INT4.md)")
+                         "stays bf16; docs/WEIGHT_INT4.md); or fp8g128 (OCP e4m3 with one fp32 scale per output row and "
+                         "group of 128 input features for the four GEMM weights of every layer, absmax per group, no "
+                         "calibration; the LM head stays bf16; the format a block-FP8 checkpoint, weight_block_size "
+                         "[128, 128], is served in without this flag; docs/WEIGHT_FP8G128.md)")
     ap.add_argument("--expert-dtype", choices=EXPERT_DTYPE_CHOICES, default="bf16",
                     help="format of an MoE model's stacked expert matrices (Mixtral checkpoints, tiny-moe): bf16, or "
                          "fp8 (OCP e4m3 with one fp32 scale per expert and output row, per-row absmax, nothing "

@@ -102,7 +102,10 @@ CONFIGS = {
 KV_DTYPES = {"bf16": torch.bfloat16, "fp8": torch.float8_e4m3fn}  # TinyLlama(kv_dtype=): the caches' dtype
 # TinyLlama(weight_dtype=): the format of the GEMM weights. "mxfp4": a layer's four as MXFP4, the LM head as FP8.
 # "int4g128" (docs/WEIGHT_INT4.md): a layer's four as grouped uint4 (GPTQ / AWQ style), the LM head bf16.
-WEIGHT_DTYPES = ("bf16", "fp8", "mxfp4", "int4g128")
+# "fp8g128" (docs/WEIGHT_FP8G128.md): a layer's four as e4m3 with an fp32 scale per row and 128 input features (what
+# block-FP8 checkpoints expand to), the LM head bf16.
+WEIGHT_DTYPES = ("bf16", "fp8", "mxfp4", "int4g128", "fp8g128")
+UNFOLDED_DTYPES = ("int4g128", "fp8g128")  # group-scaled layers: no norm weight folded in, a bf16 LM head, fused only
 # TinyLlama(expert_dtype=): the format of an MoE model's stacked expert matrices alone (docs/MOE_FP8.md,
 # docs/MOE_MXFP4.md).
 EXPERT_DTYPES = tuple(ops.EXPERT_FORMATS)
@@ -140,14 +143,20 @@ def quantize_gemm_weight(w: torch.Tensor, g: torch.Tensor | None, perm: torch.Te
         wf = wf[perm]
     if weight_dtype == "int4g128":  # no fold (the caller passes no g): a group's one scale cannot carry g[k]
         return ops.pack_weight_w4g(*ops.quantize_weight_w4g(wf.contiguous()))
+    if weight_dtype == "fp8g128":  # no fold either: per 1 x 128 group, absmax / 448, bytes in the kernel's order
+        q, s = ops.quantize_weight_fp8g128(wf.contiguous())
+        return ops.pack_weight_fp8g128(q), s
     quantize = ops.quantize_weight_mxfp4 if weight_dtype == "mxfp4" else ops.quantize_weight_fp8
     return quantize(wf.contiguous())
 
 
 def layer_weight_dtype(L: dict) -> str:
     """The format of a layer's GEMM weights, read off its tensors: "bf16", or what ``quantize_layer_`` made of them
-    ("fp8": fp32 row scales; "mxfp4": e8m0 block-scale bytes; "int4g128": int32 group words)."""
+    ("fp8": fp32 row scales; "mxfp4": e8m0 block-scale bytes; "int4g128": int32 group words; "fp8g128": fp32 scales
+    per row and group, two dimensions)."""
     s = next((L[n + "_s"] for n in GEMM_WEIGHTS if n + "_s" in L), None)
+    if s is not None and s.dtype == torch.float32 and s.dim() == 2:
+        return "fp8g128"
     return "bf16" if s is None else "mxfp4" if s.dtype == torch.uint8 else "int4g128" if s.dtype == torch.int32 else "fp8"
 
 
@@ -160,7 +169,7 @@ def quantize_layer_(cfg: "LlamaConfig", L: dict, weight_dtype: str = "fp8") -> d
         if name + "_q" in L:
             continue
         w = L.pop(name)
-        g = L.get(FOLDED_NORM.get(name)) if weight_dtype != "int4g128" else None  # int4 keeps the norm weights apart
+        g = L.get(FOLDED_NORM.get(name)) if weight_dtype not in UNFOLDED_DTYPES else None  # those keep the norm weights apart
         L[name + "_q"], L[name + "_s"] = quantize_gemm_weight(w, g, fused_row_perm(cfg, name, w.device), weight_dtype)
         del w
     return L
@@ -213,6 +222,8 @@ def dequantize_gemm_weight(q: torch.Tensor, s: torch.Tensor) -> torch.Tensor:
     """``(q, s)`` of ``quantize_gemm_weight`` back in fp32, whichever format made them."""
     if s.dtype == torch.int32:
         return ops.dequantize_weight_w4g(*ops.unpack_weight_w4g(q, s)).float()
+    if s.dtype == torch.float32 and s.dim() == 2:
+        return ops.dequantize_weight_fp8g128(ops.unpack_weight_fp8g128(q), s)
     return ops.dequantize_weight_mxfp4(q, s) if s.dtype == torch.uint8 else ops.dequantize_weight_fp8(q, s)
 
 
@@ -293,6 +304,11 @@ class TinyLlama:
         and a zero point per 128 input features; ``ops.quantize_weight_w4g`` where the weights are bf16, or
         ``name_q`` / ``name_s`` as ``ops.pack_weight_w4g`` makes them, in the fused table's row order), no norm weight
         folded in, and a bf16 LM head. dim, ffn and n_heads * head_dim must be multiples of 128; fused step only.
+        "fp8g128" (docs/WEIGHT_FP8G128.md): a layer's four GEMM weights as e4m3 bytes with one fp32 scale per output row
+        and 128 input features (``ops.quantize_weight_fp8g128`` where the weights are bf16: absmax / 448 per 1 x 128
+        group; or ``name_q`` / ``name_s`` as ``ops.pack_weight_fp8g128`` orders the bytes, fp32 ``[N, K / 128]``, in the
+        fused table's row order, which is how a block-FP8 checkpoint arrives), no norm weight folded in, and a bf16 LM
+        head. The same multiples of 128; dense models and the fused step only.
         "mxfp4": a layer's four GEMM weights as OCP Microscaling FP4 (e2m1 nibbles, one e8m0 scale byte per block of
         32; docs/WEIGHT_MXFP4.md) and the LM head in the FP8 format above.
 
@@ -319,6 +335,11 @@ class TinyLlama:
                 raise ValueError("int4 weights run the fused step only (fused=True): the unfused path multiplies bf16 "
                                  "weights")
             ops.check_w4g_dims(llama_dims(self.cfg, 1))
+        if weight_dtype == "fp8g128":
+            if not fused:
+                raise ValueError("fp8g128 weights run the fused step only (fused=True): the unfused path multiplies "
+                                 "bf16 weights")
+            ops.check_w4g_dims(llama_dims(self.cfg, 1), "fp8g128")
         if expert_dtype not in EXPERT_DTYPES:
             raise ValueError(f"expert_dtype must be one of {list(EXPERT_DTYPES)}, got {expert_dtype!r}")
         self.expert_dtype = expert_dtype
@@ -456,7 +477,7 @@ class TinyLlama:
         if self.weight_dtype == "bf16":
             return
         self.layers = [quantize_layer_(self.cfg, dict(L), self.weight_dtype) for L in self.layers]
-        if self.weight_dtype == "int4g128":  # the LM head stays bf16, as GPTQ and AWQ checkpoints leave it
+        if self.weight_dtype in UNFOLDED_DTYPES:  # the LM head stays bf16, as GPTQ, AWQ and block-FP8 checkpoints leave it
             return
         self.lm_head_q, self.lm_head_s = quantize_gemm_weight(self.lm_head, self.final_norm, None)
         self.lm_head = None
@@ -493,7 +514,7 @@ class TinyLlama:
                     gemm += nb(t)
                 else:
                     other += nb(t)
-        if self.weight_dtype not in ("bf16", "int4g128"):
+        if self.weight_dtype not in ("bf16",) + UNFOLDED_DTYPES:
             gemm += nb(self.lm_head_q) + nb(self.lm_head_s)
         elif self.lm_head is not self.embed and self.lm_head.data_ptr() != self.embed.data_ptr():
             gemm += nb(self.lm_head)
@@ -586,7 +607,8 @@ class TinyLlama:
         # interleave (_quantize_weights), and their row scales follow the table. With MXFP4 weights a layer's four
         # are nibble bytes and their scales the blocks' e8m0 bytes; the LM head is the FP8 one.
         fp8 = self.weight_dtype != "bf16"
-        int4 = self.weight_dtype == "int4g128"  # bf16 LM head with its fold; the layers' four unfolded, norms read as they are
+        # int4 and fp8g128: bf16 LM head with its fold; the layers' four unfolded, norms read as they are
+        unfolded = self.weight_dtype in UNFOLDED_DTYPES
         top = {"embed": self.embed, "final_norm": self.final_norm, "lm_head": self.lm_head,
                "lm_head_q": self.lm_head_q, "lm_head_s": self.lm_head_s, "inv_freq": self.rope_inv_freq()}
 
@@ -605,7 +627,7 @@ class TinyLlama:
                 return src[name[:-len(" scale")] + ("_e" if self.expert_dtype == "mxfp4" else "_s")]
             if self.expert_dtype != "bf16" and name in EXPERT_WEIGHTS:
                 return src[name + "_q"]
-            if fp8 and (name in GEMM_WEIGHTS or (name == "lm_head" and not int4)):
+            if fp8 and (name in GEMM_WEIGHTS or (name == "lm_head" and not unfolded)):
                 return src[name + "_q"]
             w = src[name]
             if name in FOLDED_NORM or name == "router":  # the router reads the FFN-normed activation too
@@ -764,7 +786,7 @@ class TinyLlama:
         multiplies it. bf16 weights: the tensor itself. FP8 weights: the dequantised ``q * s`` (the function the
         kernels compute; the quantisation error against the original is a separate quantity), which carries the
         preceding norm's weight folded in, so the reference then norms with a weight of one (``_ref_norm``)."""
-        if self.weight_dtype == "bf16" or (layer is None and self.weight_dtype == "int4g128"):
+        if self.weight_dtype == "bf16" or (layer is None and self.weight_dtype in UNFOLDED_DTYPES):
             return (self.lm_head if layer is None else self.layers[layer][name]).float()
         if layer is None:
             return ops.dequantize_weight_fp8(self.lm_head_q, self.lm_head_s)
@@ -825,11 +847,11 @@ class TinyLlama:
             return torch.cat([t1 * cc - t2 * ss, t2 * cc + t1 * ss], -1)
 
         def normed(v, g, final=False):
-            if self.weight_dtype != "int4g128":
+            if self.weight_dtype not in UNFOLDED_DTYPES:
                 return bf(rms(v, self._ref_norm(g)))
             if final:  # the bf16 LM head keeps its fold
                 return bf(rms(v, g))
-            # int4: the GEMM's A operand is bf16(v * g), one rounding, and 1/rms scales the accumulator in fp32.
+            # int4 and fp8g128: the GEMM's A operand is bf16(v * g), one rounding, and 1/rms scales the accumulator in fp32.
             return bf(v * f32(g)) * torch.rsqrt(v.pow(2).mean(-1, keepdim=True) + c.eps)
 
         residual = x

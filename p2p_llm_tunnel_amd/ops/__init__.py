@@ -70,7 +70,8 @@ class WeightFormat(ctypes.Structure):
     """Mirror of ``WeightFormat``: the weight formats of a step, beside its ``StepPlan`` as ``WeightPlan`` is, and what
     the ``_fmt`` entry points take. ``layers``: the format of a layer's four GEMM weights (wqkv, wo, w_gate_up,
     w_down); ``lm_head``: the LM head's. 0 bf16, 1 FP8 (docs/WEIGHT_FP8.md), 2 MXFP4 (docs/WEIGHT_MXFP4.md: the layers
-    only, with an FP8 LM head), 3 grouped int4 (docs/WEIGHT_INT4.md: the layers only, with a bf16 LM head). The supported pairs are ``WEIGHT_FORMATS``' values."""
+    only, with an FP8 LM head), 3 grouped int4 (docs/WEIGHT_INT4.md: the layers only, with a bf16 LM head), 4 block-scaled FP8
+    (docs/WEIGHT_FP8G128.md: the layers only, with a bf16 LM head). The supported pairs are ``WEIGHT_FORMATS``' values."""
     _fields_ = [("layers", _INT), ("lm_head", _INT)]
 
     def __repr__(self):
@@ -79,12 +80,14 @@ class WeightFormat(ctypes.Structure):
 
 # weight dtype -> (layers, lm_head) of WeightFormat. "int4g128" (docs/WEIGHT_INT4.md): grouped uint4 layers, GPTQ / AWQ
 # style, groups of 128, with a bf16 LM head. The name says the group size: plain "int4" stays an unknown dtype.
-WEIGHT_FORMATS = {"bf16": (0, 0), "fp8": (1, 1), "mxfp4": (2, 1), "int4g128": (3, 0)}
+# "fp8g128" (docs/WEIGHT_FP8G128.md): e4m3 layers with one fp32 scale per output row and 128 input features, what
+# block-FP8 checkpoints (weight_block_size [128, 128]) expand to, with a bf16 LM head.
+WEIGHT_FORMATS = {"bf16": (0, 0), "fp8": (1, 1), "mxfp4": (2, 1), "int4g128": (3, 0), "fp8g128": (4, 0)}
 
 
 def as_weight_format(weight_fp8: bool = False, weight_format=None) -> WeightFormat:
-    """The ``WeightFormat`` a caller means: ``weight_format`` (a ``WeightFormat``, or one of "bf16", "fp8", "mxfp4", "int4g128")
-    where given, else FP8 throughout for ``weight_fp8`` and bf16 without. Both at once, an unknown name or a pair of
+    """The ``WeightFormat`` a caller means: ``weight_format`` (a ``WeightFormat``, or one of "bf16", "fp8", "mxfp4", "int4g128",
+    "fp8g128") where given, else FP8 throughout for ``weight_fp8`` and bf16 without. Both at once, an unknown name or a pair of
     formats the step does not run are refused (host only: no library)."""
     if weight_format is None:
         return WeightFormat(*WEIGHT_FORMATS["fp8" if weight_fp8 else "bf16"])
@@ -429,6 +432,7 @@ E4M3_MAX = 448.0  # the largest finite e4m3fn value: a row's largest magnitude q
 MXFP4_BLOCK = 32  # K elements per MXFP4 block: one e8m0 scale byte each (one k-step of k_skinny)
 MXFP4_EXP_MIN, MXFP4_EXP_MAX = 2, 252  # the e8m0 bytes quantize_weight_mxfp4 emits (its docstring derives them)
 W4G_GROUP = 128  # K elements per group of an int4 weight: one scale and zero point each (a quad of k_skinny's k-steps)
+F8G_GROUP = 128  # K elements per scale of a block-scaled FP8 weight row (a quad of k-steps, two 64-byte k-step pairs)
 W4G_ZERO_MAX = 16  # the largest zero point a group word may carry (GPTQ v1 stores z - 1 in a nibble)
 E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)  # the magnitudes of an e2m1 nibble's low three bits; bit 3: sign
 MAX_TOP_LOGPROBS = 20  # top (id, logprob) pairs per row of logprobs_ (logprobs.hip's kMaxTop; the OpenAI API's limit)
@@ -443,8 +447,8 @@ LORA_PARTS = {"wqkv": ("q_proj", "k_proj", "v_proj"), "wo": ("o_proj",), "w_gate
 def step_plan(dims: LlamaDims, B: int, emit_rows: int = 0, weight_format=None) -> StepPlan:
     """What ``p2pt_llama_decode`` launches for B rows: the kernel variant, grid and partial counts of every
     stage, from the library's own planning function (host only: needs the library, not a GPU).
-    ``weight_format`` (``as_weight_format``): the plan of a step in those formats. Only "int4g128" differs from the plan
-    without it: its K parts carry whole groups of 128 (docs/WEIGHT_INT4.md)."""
+    ``weight_format`` (``as_weight_format``): the plan of a step in those formats. Only "int4g128" and "fp8g128" differ from
+    the plan without it: their K parts carry whole groups of 128 (docs/WEIGHT_INT4.md, docs/WEIGHT_FP8G128.md)."""
     plan = StepPlan()
     if weight_format is not None:
         f = as_weight_format(False, weight_format)
@@ -583,6 +587,16 @@ class WeightTable(list):
     weight folded in, and after the table come, per layer, their group words, int32 ``(N, K / 128)``, named
     ``"<weight> scale"`` too. attn_norm and ffn_norm are read by this format: the residual's producers multiply by them.
 
+    "fp8g128" (docs/WEIGHT_FP8G128.md): embed, the norms and lm_head (final_norm folded in) are the bf16 table's; each
+    layer's four GEMM weights are e4m3 (or uint8) bytes ``(N, K)``, 16-byte aligned, with no norm weight folded in, and
+    after the table come, per layer, their scales, fp32 ``(N, K / 128)``, 4-byte aligned, named ``"<weight> scale"``:
+    ``W[n][k] = e4m3(byte) * scale[n][k // 128]``. The physical byte order of a row is k-step-pair order, stated here
+    once: inside every 64 bytes, byte ``16 g + 8 h + j`` holds ``k = 32 h + 8 g + j`` of that block, for lane group
+    g = 0..3, k-step h = 0..1 of the pair and j = 0..7 (``block_expert_fp8``'s order), so the 16 bytes at
+    ``n K + 64 P + 16 (lane >> 4)`` are a lane's 8 k-values of k-steps 2 P and 2 P + 1. ``pack_weight_fp8g128`` makes
+    this order from natural bytes, ``unpack_weight_fp8g128`` undoes it. attn_norm and ffn_norm (16-byte aligned) are
+    read by this format: the QKV and gate/up kernels multiply their A fragments by them.
+
     ``moe`` (a ``MoeDims``; docs/MOE.md): ``dims.ffn`` is the per-expert size, w_gate_up is
     ``(E, 2 * ffn, dim)``, folded and pair-interleaved per expert, w_down ``(E, dim, ffn)``, and every layer ends with
     router, bf16 ``(E, dim)`` with the FFN norm folded in, 16-byte aligned. None: the dense table, unchanged.
@@ -604,19 +618,21 @@ class WeightTable(list):
                              "supported with a routed-expert FFN (expert_format='fp8' quantises the experts alone)")
         d, bf, f32, u8 = dims, (torch.bfloat16,), (torch.float32,), (torch.uint8,)
         gemm, ga = (WEIGHT_FP8_DTYPES, 8) if fmt.lm_head else (bf, 2)
-        # int4: the embedding kernel reads layer 0's attn_norm with 16-byte loads
-        n_qkv, norm = (d.H + 2 * d.Hkv) * d.D, (bf, (d.dim,), 16 if fmt.layers == 3 else 2)
+        # int4: the embedding kernel reads layer 0's attn_norm with 16-byte loads; fp8g128: the normed GEMMs do
+        n_qkv, norm = (d.H + 2 * d.Hkv) * d.D, (bf, (d.dim,), 16 if fmt.layers in (3, 4) else 2)
         top = {"embed": (bf, (d.vocab, d.dim), 2), "final_norm": norm, "lm_head": (gemm, (d.vocab, d.dim), ga)}
         if d.rope_table:
             top["inv_freq"] = (f32, (d.D // 2,), 8)
         shapes = {"wqkv": (n_qkv, d.dim), "wo": (d.dim, d.H * d.D), "w_gate_up": (2 * d.ffn, d.dim),
                   "w_down": (d.dim, d.ffn)}
-        if fmt.layers == 3:
-            check_w4g_dims(d)
+        if fmt.layers in (3, 4):
+            check_w4g_dims(d, "int4" if fmt.layers == 3 else "fp8g128")
         if fmt.layers == 2:  # nibbles, two to a byte
             lg = {n: (u8, (N, K // 2), 4) for n, (N, K) in shapes.items()}
         elif fmt.layers == 3:  # nibbles in k-step-quad order: one 16-byte load per lane and quad
             lg = {n: (u8, (N, K // 2), 16) for n, (N, K) in shapes.items()}
+        elif fmt.layers == 4:  # e4m3 bytes in k-step-pair order: one 16-byte load per lane and pair
+            lg = {n: (WEIGHT_FP8_DTYPES, shape, 16) for n, shape in shapes.items()}
         else:
             lg = {n: (gemm, shape, ga) for n, shape in shapes.items()}
         layer = {"attn_norm": norm, "wqkv": lg["wqkv"], "wo": lg["wo"], "ffn_norm": norm, "w_gate_up": lg["w_gate_up"],
@@ -644,6 +660,9 @@ class WeightTable(list):
         if fmt.layers == 3:  # the group words of each layer's four; the LM head is bf16 and has none
             self += [WeightEntry(n + " scale", L, (torch.int32,), (shapes[n][0], shapes[n][1] // W4G_GROUP), 4)
                      for L in range(d.n_layers) for n in LAYER_GEMMS]
+        if fmt.layers == 4:  # one fp32 scale per row and 128 k of each layer's four; the LM head is bf16 and has none
+            self += [WeightEntry(n + " scale", L, f32, (shapes[n][0], shapes[n][1] // F8G_GROUP), 4)
+                     for L in range(d.n_layers) for n in LAYER_GEMMS]
         if experts.w8 == 1:  # the experts' row scales, after every other entry
             self += [WeightEntry(n + " scale", L, f32, layer[n][1][:2], 4)
                      for L in range(d.n_layers) for n in ("w_gate_up", "w_down")]
@@ -665,10 +684,11 @@ class WeightTable(list):
         return self.index(name + " scale", layer)
 
 
-def check_w4g_dims(dims: LlamaDims) -> None:
-    """Grouped int4 weights need every K of a layer GEMM in whole groups of 128 (host only)."""
+def check_w4g_dims(dims: LlamaDims, what: str = "int4") -> None:
+    """Grouped int4 weights, and ``what`` "fp8g128" block-scaled FP8 ones, need every K of a layer GEMM in whole groups
+    of 128 (host only)."""
     if dims.dim % W4G_GROUP or dims.ffn % W4G_GROUP or (dims.H * dims.D) % W4G_GROUP:
-        raise ValueError(f"int4 weights are stored in groups of {W4G_GROUP} (quads of k-steps): dim, ffn and "
+        raise ValueError(f"{what} weights are stored in groups of {W4G_GROUP} (quads of k-steps): dim, ffn and "
                          f"n_heads * head_dim must be multiples of {W4G_GROUP}, got dim {dims.dim}, ffn {dims.ffn}, "
                          f"n_heads * head_dim {dims.H * dims.D}")
 
@@ -1892,6 +1912,52 @@ def workspace_layout(dims: LlamaDims, opts: StepOptions) -> tuple:
                     if i < WS_DENSE or c}
 
 
+def _check_fp8g128(q, scale, what: str):
+    if not isinstance(q, torch.Tensor) or q.dtype not in WEIGHT_FP8_DTYPES or q.dim() != 2 or \
+            q.shape[1] % F8G_GROUP or not q.shape[1]:
+        raise TypeError(f"{what}: q must be e4m3 (or uint8) bytes [N, K] with K a multiple of {F8G_GROUP}")
+    if scale is not None and (not isinstance(scale, torch.Tensor) or scale.dtype != torch.float32 or
+                              tuple(scale.shape) != (q.shape[0], q.shape[1] // F8G_GROUP)):
+        raise TypeError(f"{what}: scale must be fp32 [N, K / {F8G_GROUP}], one per output row and {F8G_GROUP} k")
+
+
+def pack_weight_fp8g128(q: torch.Tensor) -> torch.Tensor:
+    """The e4m3 bytes ``[N, K]`` of a block-scaled FP8 weight from natural K order to what ``k_skinny<.., W8 = 4>`` loads
+    (docs/WEIGHT_FP8G128.md): every row in the k-step-pair order ``WeightTable`` states. The scales do not move. The one
+    function that makes this order; a new contiguous tensor of ``q``'s dtype."""
+    _check_fp8g128(q, None, "pack_weight_fp8g128")
+    return q.view(torch.uint8)[:, _expert_perm(q.shape[1], q.device)].contiguous().view(q.dtype)
+
+
+def unpack_weight_fp8g128(q: torch.Tensor) -> torch.Tensor:
+    """The inverse of ``pack_weight_fp8g128``: device order back to natural K order."""
+    _check_fp8g128(q, None, "unpack_weight_fp8g128")
+    out = torch.empty_like(q.view(torch.uint8))
+    out[:, _expert_perm(q.shape[1], q.device)] = q.view(torch.uint8)
+    return out.view(q.dtype)
+
+
+def quantize_weight_fp8g128(w: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """One GEMM weight ``w`` (fp32 [N, K], K a multiple of 128, in the fused table's row order, no norm weight folded
+    in) to block-scaled FP8 per 1 x 128 group, nothing calibrated: ``(q, scale)``, e4m3 ``[N, K]`` in natural K order and
+    fp32 ``[N, K / 128]`` with ``scale = max |group| / 448`` (1.0 for a group whose maximum is zero or so small that the
+    division underflows to zero) and ``q`` the e4m3fn byte, round to nearest even, of ``w / scale`` (the division in
+    fp32): ``quantize_weight_fp8``'s rule on every group. Plain torch on ``w``'s device: runs without a GPU."""
+    if not isinstance(w, torch.Tensor) or w.dtype != torch.float32 or w.dim() != 2 or w.shape[1] % F8G_GROUP or \
+            not w.shape[1]:
+        raise TypeError(f"quantize_weight_fp8g128 takes an fp32 [N, K] tensor with K a multiple of {F8G_GROUP}")
+    N, K = w.shape
+    q, scale = quantize_weight_fp8(w.reshape(N * (K // F8G_GROUP), F8G_GROUP))
+    return q.reshape(N, K), scale.reshape(N, K // F8G_GROUP)
+
+
+def dequantize_weight_fp8g128(q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """``e4m3(q) * scale[n][k // 128]`` in fp32 ``[N, K]`` (``q`` in natural K order): the weight the block-scaled FP8
+    kernels compute with. One fp32 rounding per element, none when the scales are powers of two."""
+    _check_fp8g128(q, scale, "dequantize_weight_fp8g128")
+    return q.view(torch.float8_e4m3fn).float() * scale.repeat_interleave(F8G_GROUP, 1)
+
+
 class FusedLlamaDecoder:
     """Host handle for the fused decode step (decode_fused.hip): 5 kernels per layer + 3
     (6 per layer with ``dims.qk_norm``: the per-head q/k RMSNorm of Qwen3 runs in a kernel of its own;
@@ -1907,7 +1973,10 @@ class FusedLlamaDecoder:
     MXFP4 bytes with e8m0 block scales, run by the ``k_skinny<.., W8 = 2>`` instantiations, and an FP8 LM head;
     "int4g128" (docs/WEIGHT_INT4.md, ``pack_weight_w4g``) has them as grouped uint4 with an fp16 scale and a zero point per
     128 k, run by the ``W8 = 3`` instantiations on ``step_plan(.., weight_format="int4g128")``, with a bf16 LM head; its
-    workspace has one more buffer, xg.
+    workspace has one more buffer, xg;
+    "fp8g128" (docs/WEIGHT_FP8G128.md, ``pack_weight_fp8g128``) has them as e4m3 bytes with one fp32 scale per row and
+    128 k, run by the ``W8 = 4`` instantiations on ``step_plan(.., weight_format="fp8g128")``, with a bf16 LM head and
+    the dense bf16 workspace.
     ``weight_fp8``: the five GEMM weights as OCP e4m3 bytes with one fp32 scale per output row, each (N,) in the
     row order of its weight (docs/WEIGHT_FP8.md, ``quantize_weight_fp8``). Every ``k_skinny`` is then its FP8-weight
     instantiation; the kernel count, ``step_plan`` and the workspace are the same.
@@ -1998,6 +2067,8 @@ class FusedLlamaDecoder:
                                 if fmt.layers == 2 else "")
                              + ("; int4: no norm weight folded into a layer's four, and then four group-word tensors "
                                 "per layer" if fmt.layers == 3 else "")
+                             + ("; fp8g128: no norm weight folded into a layer's four, and then four fp32 group-scale "
+                                "tensors per layer" if fmt.layers == 4 else "")
                              + ("; MoE: w_gate_up and w_down stacked per expert, and router last in every layer"
                                 if self.moe is not None else "")
                              + ("; FP8 experts: then their fp32 row scales, w_gate_up's and w_down's per layer"
@@ -2015,6 +2086,10 @@ class FusedLlamaDecoder:
                     raise TypeError(f"{name}: the weight format is int4, so "
                                     + ("the group words must be torch.int32" if e.name.endswith(" scale")
                                        else "the weight must be nibble bytes (torch.uint8)") + f", got {got}")
+                if fmt.layers == 4 and (len(e.dtypes) > 1 or e.name.endswith(" scale")):
+                    raise TypeError(f"{name}: the weight format is fp8g128, so "
+                                    + ("the group scales must be torch.float32" if e.name.endswith(" scale")
+                                       else "the weight must be torch.float8_e4m3fn (or uint8)") + f", got {got}")
                 if fmt.layers == 2 and e.dtypes == (torch.uint8,):
                     raise TypeError(f"{name}: the weight format is mxfp4, so "
                                     + ("the block scales must be e8m0 bytes (torch.uint8)" if e.name.endswith(" scale")
@@ -2037,6 +2112,7 @@ class FusedLlamaDecoder:
                                  + ("" if not e.name.endswith(" scale") else
                                     f": one group word per {W4G_GROUP} k" if e.dtypes == (torch.int32,) else
                                     f": one e8m0 byte per {MXFP4_BLOCK}-element block" if e.dtypes == (torch.uint8,)
+                                    else f": one fp32 scale per output row and {F8G_GROUP} k" if fmt.layers == 4
                                     else ": one fp32 scale per expert and output row" if self.expert_format.w8
                                     else ": one fp32 scale per output row")
                                  + (": two nibbles per byte" if e.name in LAYER_GEMMS and e.dtypes == (torch.uint8,) and

@@ -4,6 +4,7 @@
 // lookups and launches that follow a plan into that set, and the C entry
 // points. The kernels and the design notes are in decode_fused_kernels.h.
 #include "decode_fused_kernels.h"
+#include "decode_f8g.h"
 #include "decode_fused_set.h"
 #include "decode_lora.h"
 #include "decode_moe.h"
@@ -81,11 +82,17 @@ struct WeightFormat {
 // norm weight cannot be folded into a group, so the residual's producers also store xg = bf16(resid * g_next) into a
 // workspace buffer of its own and the QKV and gate/up GEMMs read that (plan_step, ws_layout and the table take the
 // format for it), and K parts carry whole quads.
+// 4 (docs/WEIGHT_FP8G128.md): block-scaled FP8, what block-FP8 checkpoints expand to: e4m3 bytes in k-step-pair order
+// with one fp32 scale per output row and group of 128 k, the layers only, with a bf16 LM head. The norm weight cannot
+// be folded into a group here either, but the format adds no buffer: the QKV and gate/up kernels read the table's
+// attn_norm / ffn_norm entries and multiply their A fragments in registers. It plans K in whole groups as 3 does; the
+// workspace is the bf16 one.
 bool format_ok(const WeightFormat& f) {
   return (f.layers == 0 && f.lm_head == 0) || (f.layers == 1 && f.lm_head == 1) || (f.layers == 2 && f.lm_head == 1) ||
-         (f.layers == kW4g && f.lm_head == 0);
+         (f.layers == kW4g && f.lm_head == 0) || (f.layers == kF8g && f.lm_head == 0);
 }
 constexpr int kW4gGroup = 128;  // k per group: one quad of k-steps
+bool grouped(int w8) { return w8 == kW4g || w8 == kF8g; }  // the formats whose scales change every kW4gGroup k
 // The scales of an FP8 cache, beside the plans as WeightPlan is and for the same reason: no field of LlamaDims, no
 // entry of the weight table, so a model without scales plans, lays out and launches what it did. One device buffer,
 // fp32 [4][n_layers][Hkv]: 1 / k_scale, 1 / v_scale (what the writers multiply by, computed once on the host),
@@ -211,7 +218,7 @@ struct StepOptions {
 //  - Load batch um: each wave's share of k-steps, rounded up to a power of two,
 //    at most 4 (fewer registers, more resident waves).
 // A K without a whole k-step leaves nw = 0, which launch() refuses.
-// quads (grouped int4 weights): a K part must hold whole quads of k-steps, so where K / 128 does not split into the P
+// quads (grouped int4 and block-scaled FP8 weights): a K part must hold whole quads of k-steps, so where K / 128 does not split into the P
 // parts the rule above picks, the next smaller P that does is taken (bf16 gives up K parts there: it never happens
 // for a K that is a multiple of 128 * P). The waves then split K / 128 quads, not K / 32 k-steps; nw and um keep
 // their rule, so where nw does not divide the quads some waves get fewer or none.
@@ -266,7 +273,7 @@ AttnPlan plan_attn(int B, int H, int Hkv, int D, int max_seq) {
 }
 
 StepPlan plan_step(const LlamaDims& d, int B, int emit_rows, const WeightFormat& f = WeightFormat{0, 0}) {
-  const bool quads = f.layers == kW4g;
+  const bool quads = grouped(f.layers);
   StepPlan p{};
   p.rows = B;
   p.emit_rows = emit_rows <= 0 || emit_rows > B ? B : emit_rows;
@@ -409,6 +416,9 @@ Workspace carve(const LlamaDims& d, uint8_t* base, const StepOptions& o) {
 // N * K / 2 nibble bytes in k-step-quad order, 16-byte aligned, with no norm weight folded in, and after the table per
 // layer the four group-word tensors [N][K / 128] uint32 where the FP8 table has row scales (no lm_head entry ahead of
 // them). Its attn_norm and ffn_norm entries are read: they are the g of the xg stores.
+// A block-scaled FP8 table (docs/WEIGHT_FP8G128.md) has the same entries as the grouped int4 one: each layer GEMM as
+// N * K e4m3 bytes in k-step-pair order, 16-byte aligned, with no norm weight folded in, and after the table per layer
+// the four scale tensors [N][K / 128] fp32. Its attn_norm and ffn_norm entries are read by the QKV and gate/up kernels.
 // An MoE table (moe set; bf16 apart from the experts) has one more entry per layer, after every other: router, bf16 [E][dim] with the FFN
 // norm folded in; its w_gate_up is [E][2 ffn_e][dim], folded and pair-interleaved per expert, and its w_down
 // [E][dim][ffn_e]. R_ROUTER follows R_NROLES so that p2pt_llama_weight_layout's 13 roles per layer stay what they are.
@@ -423,7 +433,7 @@ struct WeightTable {
   int per_layer() const { return (d.qk_norm ? 8 : d.qkv_bias ? 7 : 6) + moe; }
   int scales0() const { return 3 + d.rope_table + per_layer() * d.n_layers; }
   int size() const {
-    return scales0() + (f.lm_head ? 1 + 4 * d.n_layers : f.layers == kW4g ? 4 * d.n_layers : 0) + (ew8 ? 2 * d.n_layers : 0);
+    return scales0() + (f.lm_head ? 1 + 4 * d.n_layers : grouped(f.layers) ? 4 * d.n_layers : 0) + (ew8 ? 2 * d.n_layers : 0);
   }
   // The format of a GEMM weight's role (0 for every other role).
   int format(Role r) const {
@@ -445,7 +455,7 @@ struct WeightTable {
     // FP8 experts: the layers are bf16 (an MoE model's only format), so the experts' scales are all there is.
     if (ew8 && (r == R_W_GATE_UP || r == R_W_DOWN)) return scales0() + 2 * L + (r == R_W_DOWN);
     const int j = r == R_WQKV ? 1 : r == R_WO ? 2 : r == R_W_GATE_UP ? 3 : r == R_W_DOWN ? 4 : 0;
-    if (f.layers == kW4g) return j ? scales0() + 4 * L + j - 1 : -1;  // no lm_head scales ahead of the layers'
+    if (grouped(f.layers)) return j ? scales0() + 4 * L + j - 1 : -1;  // no lm_head scales ahead of the layers'
     return !format(r) ? -1 : scales0() + (j ? 4 * L + j : 0);
   }
   const void* get(Role r, int L = 0) const { return at(index(r, L)); }  // nullptr where the table has none
@@ -466,8 +476,8 @@ GemmArgs operator+(GemmArgs a, Set set) {
   return a;
 }
 // M, N, K and kpl are the plan's: launch() fills them in. scale: what the table holds for the weight's scales, the
-// fp32 row scales of an FP8 weight (fmt 1), the e8m0 block scales of an MXFP4 one (fmt 2) or the group words of a
-// grouped int4 one (fmt 3); nullptr: bf16.
+// fp32 row scales of an FP8 weight (fmt 1), the e8m0 block scales of an MXFP4 one (fmt 2), the group words of a
+// grouped int4 one (fmt 3) or the fp32 group scales of a block-scaled FP8 one (fmt 4); nullptr: bf16.
 GemmArgs gemm(const void* x, const void* w, const void* scale = nullptr, int fmt = 1) {
   GemmArgs a{};
   a.x = static_cast<const uint16_t*>(x), a.w = static_cast<const uint16_t*>(w);
@@ -476,8 +486,9 @@ GemmArgs gemm(const void* x, const void* w, const void* scale = nullptr, int fmt
   else a.wscale = static_cast<const float*>(scale);
   return a;
 }
-auto norm(const float* ss, int parts, float eps) {
-  return [=](GemmArgs& a) { a.ss_part = ss, a.ss_parts = parts, a.eps = eps; };
+// g: block-scaled FP8 only (the norm's weight, which the kernel multiplies into its A fragments).
+auto norm(const float* ss, int parts, float eps, const void* g = nullptr) {
+  return [=](GemmArgs& a) { a.ss_part = ss, a.ss_parts = parts, a.eps = eps, a.gin = static_cast<const uint16_t*>(g); };
 }
 auto store(void* out) {  // STORE, SILU
   return [=](GemmArgs& a) { a.out = static_cast<uint16_t*>(out); };
@@ -511,6 +522,8 @@ SkinnyKernel skinny_kernel(const GemmPlan& p, int w8 = 0, bool lora = false) {
               : reinterpret_cast<SkinnyKernel>(const_cast<void*>(p2pt_lora::skinny_kernel(p.nw, p.tn, p.epi, p.um)));
   // Grouped int4: the same lists and predicate, instantiated in decode_w4g.hip.
   if (w8 == kW4g) return reinterpret_cast<SkinnyKernel>(const_cast<void*>(p2pt_w4g::skinny_kernel(p.nw, p.tn, p.epi, p.um)));
+  // Block-scaled FP8: likewise, in decode_f8g.hip.
+  if (w8 == kF8g) return reinterpret_cast<SkinnyKernel>(const_cast<void*>(p2pt_f8g::skinny_kernel(p.nw, p.tn, p.epi, p.um)));
   SkinnyKernel k = nullptr;
   pick([&](auto nw, auto tn, auto epi, auto um, auto f8) {
     if constexpr (skinny_exists(nw, tn, epi, um, f8)) k = k_skinny<nw, tn, epi, um, f8>;
@@ -543,14 +556,19 @@ bool rows_ok(int B) { return B > 0 && B <= kMaxM; }
 // ------------------------------------------------------------ launches
 // Each checks its arguments, looks its kernel up and launches it; a plan that names no kernel is hipErrorInvalidValue.
 // w8: the weight's format (WeightFormat): 1, the FP8-weight instantiation, reads a.wscale and is refused without it;
-// 2, the MXFP4 one, reads a.wexp likewise; 3, the grouped int4 one, a.wgrp. A scale pointer the format does not read is
+// 2, the MXFP4 one, reads a.wexp likewise; 3, the grouped int4 one, a.wgrp; 4, the block-scaled FP8 one, a.wscale as
+// [N][K / 128] and with a normed input a.gin. A scale pointer the format does not read is
 // refused too. lora: the LORA instantiation of the plan's kernel, which reads a.delta: refused without it, as is a
 // delta without the flag.
 hipError_t launch(const GemmPlan& p, GemmArgs a, hipStream_t s, int w8 = 0, bool lora = false) {
   if (lora != (a.delta != nullptr)) return hipErrorInvalidValue;
-  if ((w8 == 1) != (a.wscale != nullptr) || (w8 == 2) != (a.wexp != nullptr)) return hipErrorInvalidValue;
+  if ((w8 == 1 || w8 == kF8g) != (a.wscale != nullptr) || (w8 == 2) != (a.wexp != nullptr)) return hipErrorInvalidValue;
   // Grouped int4: the group words, K parts of whole quads, and for a residual producer the xg store's two pointers.
-  if ((w8 == kW4g) != (a.wgrp != nullptr) || (w8 == kW4g && p.K % (kW4gGroup << p.kpl))) return hipErrorInvalidValue;
+  if ((w8 == kW4g) != (a.wgrp != nullptr) || (grouped(w8) && p.K % (kW4gGroup << p.kpl))) return hipErrorInvalidValue;
+  // Block-scaled FP8: the norm weight with a normed input and never otherwise; the kernels norm every epilogue but
+  // RESID, so a plan that differs is refused.
+  if ((w8 == kF8g && p.ss_in > 0) != (a.gin != nullptr) || (w8 == kF8g && (p.ss_in > 0) == (p.epi == EPI_RESID)))
+    return hipErrorInvalidValue;
   if ((w8 == kW4g && p.epi == EPI_RESID) != (a.gnext != nullptr) || (a.gnext != nullptr) != (a.xg != nullptr))
     return hipErrorInvalidValue;
   if (p.kpl < 0 || p.kpl > kMaxKpl || (p.ss_in > 0) != (a.ss_part != nullptr)) return hipErrorInvalidValue;
@@ -645,9 +663,9 @@ bool dims_ok(const LlamaDims& d) {
   return true;
 }
 
-// Grouped int4 weights: every K of a layer GEMM (dim, H * D, ffn) in whole groups of 128.
+// Grouped int4 and block-scaled FP8 weights: every K of a layer GEMM (dim, H * D, ffn) in whole groups of 128.
 bool format_dims_ok(const LlamaDims& d, const WeightFormat& f) {
-  return f.layers != kW4g || (d.dim % kW4gGroup == 0 && (d.H * d.D) % kW4gGroup == 0 && d.ffn % kW4gGroup == 0);
+  return !grouped(f.layers) || (d.dim % kW4gGroup == 0 && (d.H * d.D) % kW4gGroup == 0 && d.ffn % kW4gGroup == 0);
 }
 
 // Every refusal that needs no per-call value, in one place: what the step refuses, the kernel lookup, the workspace
@@ -737,8 +755,8 @@ int p2pt_llama_plan(const LlamaDims* d, int B, int emit_rows, StepPlan* out) {
   return 0;
 }
 
-// The same for a step in weight formats fmt (p2pt_llama_decode_fmt): grouped int4 layers plan their K parts in whole
-// quads; every other format is the plan above, int for int.
+// The same for a step in weight formats fmt (p2pt_llama_decode_fmt): grouped int4 and block-scaled FP8 layers plan
+// their K parts in whole quads; every other format is the plan above, int for int.
 int p2pt_llama_plan_fmt(const LlamaDims* d, const WeightFormat* fmt, int B, int emit_rows, StepPlan* out) {
   if (!dims_ok(*d) || !rows_ok(B) || !format_ok(*fmt) || !format_dims_ok(*d, *fmt)) return int(hipErrorInvalidValue);
   *out = plan_step(*d, B, emit_rows, *fmt);
@@ -843,7 +861,8 @@ int p2pt_llama_weight_plan(const LlamaDims* d, int weight_fp8, WeightPlan* out) 
   return 0;
 }
 
-// The weight formats of a step for (layers, lm_head) in {(0, 0), (1, 1), (2, 1), (3, 0)} (host only), beside the plans above.
+// The weight formats of a step for (layers, lm_head) in {(0, 0), (1, 1), (2, 1), (3, 0), (4, 0)} (host only), beside the
+// plans above.
 int p2pt_llama_weight_format(const LlamaDims* d, int layers, int lm_head, WeightFormat* out) {
   const WeightFormat f{layers, lm_head};
   if (!dims_ok(*d) || !format_ok(f) || !format_dims_ok(*d, f)) return int(hipErrorInvalidValue);
@@ -913,7 +932,8 @@ int p2pt_max_rows() { return kMaxM; }
 //      layer's four as bytes [N][K / 2] (4-byte aligned), two e2m1 nibbles each with the lower k in the low nibble,
 //      quantised after the fold and the interleave, and where the FP8 table has their row scales the e8m0 scale bytes
 //      [N][K / 32] of their 32-element blocks; lm_head and its row scales are the FP8 table's. {3, 0}, grouped int4:
-//      the table above WeightTable and docs/WEIGHT_INT4.md describe, and one more workspace buffer, xg.
+//      the table above WeightTable and docs/WEIGHT_INT4.md describe, and one more workspace buffer, xg. {4, 0},
+//      block-scaled FP8: the table above WeightTable and docs/WEIGHT_FP8G128.md describe, on the bf16 workspace.
 //   kv_scales (with dims.kv_fp8; refused with a bf16 cache): a device buffer, fp32 [4][n_layers][Hkv]: 1 / k_scale,
 //      1 / v_scale, k_scale, v_scale, every entry finite and > 0 (the caller's check). A stored byte is
 //      e4m3(clamp(x * (1 / s))) of the head's scale and k_attn undoes it (KvScales). nullptr: scale 1.
@@ -995,7 +1015,10 @@ static int decode_step(const LlamaDims* dp, const StepOptions& o, const void* co
     uint16_t* kc = reinterpret_cast<uint16_t*>(static_cast<uint8_t*>(k_cache) + L * layer_cache);
     uint16_t* vc = reinterpret_cast<uint16_t*>(static_cast<uint8_t*>(v_cache) + L * layer_cache);
     const GemmPlan& qkv = L ? P.qkv : P.qkv_first;
-    const GemmArgs qkv_in = gemm(normed_in, T.get(R_WQKV, L), T.scale(R_WQKV, L), w8) + norm(W.ss, qkv.ss_in, d.eps);
+    // Block-scaled FP8: the normed GEMMs read the residual and multiply by the norm weight themselves.
+    const bool f8g = w8 == kF8g;
+    const GemmArgs qkv_in = gemm(normed_in, T.get(R_WQKV, L), T.scale(R_WQKV, L), w8) +
+                            norm(W.ss, qkv.ss_in, d.eps, f8g ? T.get(R_ATTN_NORM, L) : nullptr);
     const GemmArgs to_qkv =
         d.qk_norm ? qkv_in + store(W.qkv)
                   : qkv_in + rope(d, pos, slots, W.q, kc, vc, T.get(R_BQKV, L), inv_freq,
@@ -1007,7 +1030,7 @@ static int decode_step(const LlamaDims* dp, const StepOptions& o, const void* co
     const GemmArgs to_o = gemm(W.attn, T.get(R_WO, L), T.scale(R_WO, L), w8) +
                           resid(W.resid, W.ss, g_o, w4g ? W.xg : nullptr);
     const GemmArgs to_gate_up = gemm(normed_in, T.get(R_W_GATE_UP, L), T.scale(R_W_GATE_UP, L), w8) +
-                                norm(W.ss, P.gate_up.ss_in, d.eps) + store(W.h);
+                                norm(W.ss, P.gate_up.ss_in, d.eps, f8g ? T.get(R_FFN_NORM, L) : nullptr) + store(W.h);
     const GemmArgs to_down = gemm(W.h, T.get(R_W_DOWN, L), T.scale(R_W_DOWN, L), w8) +
                              resid(W.resid, W.ss, g_down, w4g ? W.xg : nullptr);
     if (lr && failed(lora_delta(L, LP_QKV, qkv, normed_in))) return int(e);

@@ -34,6 +34,11 @@
 //                        weight cannot be folded into a group, so the residual's producers also store bf16(resid * g)
 //                        and QKV and gate/up read that. The LM head stays bf16. The same kernel count:
 //                        docs/WEIGHT_INT4.md)
+//     (block FP8:        a layer's four k_skinny are their W8 = 4 instantiations: e4m3 bytes with one fp32 scale per
+//                        output row and 128 input features, as block-FP8 checkpoints expand to; each group of four
+//                        k-steps accumulates apart and joins the running sum by an FMA with its scale, and QKV and
+//                        gate/up multiply the norm weight into their A fragments in registers. The LM head stays bf16.
+//                        The same kernel count and workspace: docs/WEIGHT_FP8G128.md)
 //     k_skinny<RESID>    O projection -> residual add -> per-row sum-of-squares
 //                        partials for the next norm
 //     k_skinny<SILU>     RMSNorm (ffn_norm) -> gate/up GEMM -> SwiGLU
@@ -181,6 +186,12 @@ struct GemmArgs {
   // column of this projection, in the row order of w, written by k_lora_delta ahead of this launch. It joins the
   // accumulator ahead of everything else the epilogue does. Not read by the other kernels.
   const float* delta;
+  // Block-scaled FP8 weights (k_skinny<.., W8 = 4>; docs/WEIGHT_FP8G128.md): w holds N * K e4m3 bytes, every row in
+  // k-step-pair order, and wscale (the W8 = 1 field, another shape) one fp32 scale per row and group of 128 k,
+  // [N][K / 128] in the row order of w. gin: with a normed input, the norm weight g, bf16 [K], which no group scale
+  // can carry: the A fragment of a k-step is bf16(x[k] * g[k]), multiplied in registers. Not read by the other
+  // kernels; last, so that every other field stays where those read it.
+  const uint16_t* gin;
 };
 
 // log2 of the output columns per 16-lane subtile: 16, 8 or 4 for 1, 2 or 4 K parts.
@@ -345,6 +356,78 @@ __device__ __forceinline__ void mma_stream_w4g(frag4 (&acc)[TN], __amdgpu_buffer
   }
 }
 
+// Two bf16 pairs multiplied lane-wise and rounded once, to nearest even (v_cvt_pk_bf16_f32): the fp32 product of two
+// bf16 values is exact (8 + 8 significand bits), so the result is bf16_rne(x * g) of the real product.
+__device__ __forceinline__ uint32_t mul_bf16x2(uint32_t x, uint32_t g) {
+  const float2v f = {__uint_as_float(x << 16) * __uint_as_float(g << 16),
+                     __uint_as_float(x & 0xffff0000u) * __uint_as_float(g & 0xffff0000u)};
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, bf16x2_t));
+}
+__device__ __forceinline__ uint4 mul_bf16x8(const uint4& x, const uint4& g) {
+  return make_uint4(mul_bf16x2(x.x, g.x), mul_bf16x2(x.y, g.y), mul_bf16x2(x.z, g.z), mul_bf16x2(x.w, g.w));
+}
+
+// The wave's groups [q0, q1) of block-scaled FP8 weights (docs/WEIGHT_FP8G128.md), QB groups per load batch. A group is
+// 128 k, a quad of k-steps, with one fp32 scale per output row. Per subtile and group the lane issues one 4-byte load,
+// its column's scale (the B fragment's weight row and the accumulator's column are both lane & 15, K part included),
+// ahead of two 16-byte loads, its 8 k-values of the group's two k-step pairs (bytes 0..7 of a load: the even k-step,
+// 8..15: the odd one), beside the bf16 kernel's four 16-byte A loads. NORM: four more 16-byte loads, the norm weight g
+// at the A fragments' k (the 16 lanes of a lane group read the same 16 bytes), and the A fragment is bf16(x * g).
+// The bytes are decoded exactly (e4m3x8_to_bf16x8) just ahead of their MFMA into a fresh group accumulator, in the bf16
+// kernel's k order, and that joins the running one by one fp32 FMA per register, acc = fma(s, group, acc): one rounding
+// per group where the bf16 kernel has none, and none at all for a scale that is a power of two. A group past the
+// wave's share loads zeros through the descriptors' range check (scale 0, bytes 0) and adds fma(0, 0, acc) = acc.
+template <int QB, int TN, bool NORM>
+__device__ __forceinline__ void mma_stream_f8g(frag4 (&acc)[TN], __amdgpu_buffer_rsrc_t ra, uint32_t xoff,
+                                               __amdgpu_buffer_rsrc_t rw, const uint32_t (&woff)[TN],
+                                               __amdgpu_buffer_rsrc_t rs, const uint32_t (&soff)[TN],
+                                               __amdgpu_buffer_rsrc_t rg, uint32_t goff, int q0, int q1) {
+  for (int q = q0; q < q1; q += QB) {
+    float sc[QB][TN];
+    uint4 b[QB][2][TN], x[QB][4], g[NORM ? QB : 1][4];
+#pragma unroll
+    for (int i = 0; i < QB; i++)
+#pragma unroll
+      for (int t = 0; t < TN; t++) sc[i][t] = __uint_as_float(buf_ld4(rs, q + i < q1 ? soff[t] + uint32_t(q + i) * 4u : kOob));
+#pragma unroll
+    for (int i = 0; i < QB; i++) {
+      const bool in = q + i < q1;
+      const uint32_t qi = uint32_t(q + i);
+#pragma unroll
+      for (int t = 0; t < TN; t++)
+#pragma unroll
+        for (int h = 0; h < 2; h++) b[i][h][t] = buf_ld16(rw, in ? woff[t] + (qi * 2u + h) * 64u : kOob);
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        x[i][u] = buf_ld16(ra, in ? xoff + (qi * 4u + u) * 64u : kOob);
+        if constexpr (NORM) g[i][u] = buf_ld16(rg, in ? goff + (qi * 4u + u) * 64u : kOob);
+      }
+    }
+    __builtin_amdgcn_sched_barrier(0);  // every load of the batch ahead of the first MFMA, as in mma_stream
+#pragma unroll
+    for (int i = 0; i < QB; i++) {
+      uint4 af[4];
+#pragma unroll
+      for (int u = 0; u < 4; u++) {
+        if constexpr (NORM) af[u] = mul_bf16x8(x[i][u], g[i][u]);
+        else af[u] = x[i][u];
+      }
+#pragma unroll
+      for (int t = 0; t < TN; t++) {
+        frag4 ga = frag4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+          const uint4& p = b[i][u >> 1][t];
+          const uint2 bytes = (u & 1) ? make_uint2(p.z, p.w) : make_uint2(p.x, p.y);
+          ga = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_frag(af[u]), as_frag(e4m3x8_to_bf16x8(bytes)), ga, 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; r++) acc[t][r] = __builtin_fmaf(sc[i][t], ga[r], acc[t][r]);
+      }
+    }
+  }
+}
+
 // One batch of up to UM consecutive 32-wide k-steps [s, min(s + UM, s1)):
 // every load of the batch is issued before any of it is used.
 // W8 (FP8 weights): the lane's B fragment of a k-step is its 8 k-values as 8 e4m3 bytes, one 8-byte load at a
@@ -431,6 +514,13 @@ __device__ __forceinline__ void mma_stream(frag4 (&acc)[TN], __amdgpu_buffer_rsr
 // (GemmArgs::wgrp). The waves split K in quads and K parts carry whole quads (the host plans kpl so); a load batch is
 // one quad for UM 1 and 2 and two quads for UM 4 (mma_stream_w4g). Nothing after the MFMA knows the format. With
 // EPI_RESID the epilogue also stores xg = bf16(resid_new * gnext[col]), the next normed GEMM's A operand.
+// W8 = 4: block-scaled FP8 (docs/WEIGHT_FP8G128.md): N * K e4m3 bytes in k-step-pair order and one fp32 scale per row
+// and 128 k (GemmArgs::wscale, [N][K / 128]). A scale that changes along K cannot wait for the epilogue: the waves
+// split K in groups as W8 = 3 does (K parts carry whole groups), each group runs its four MFMAs into an accumulator of
+// its own and joins the running one by an fp32 FMA with its scale (mma_stream_f8g); a load batch is one group for UM 1
+// and 2 and two for UM 4. No group scale can carry the norm weight either, and this format adds no buffer: with a
+// normed input (every epilogue but RESID) the A fragment is bf16(x * g), g read from GemmArgs::gin. Nothing after the
+// stream knows the format.
 // LORA (bf16 weights, a layer's four projections; docs/LORA.md): wave 0 adds GemmArgs::delta[m][n], the fp32 low-rank
 // term k_lora_delta left for this projection, to the reduced accumulator: after the K-parts diagonal sum and ahead of
 // 1/rms, the bias and everything else, so (W' + B'A') x is scaled, rotated, gated or added to the residual exactly as
@@ -471,17 +561,18 @@ __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
   const int kq = (lane >> 4) << 3;
   const int S = Kp >> 5;
   const int s0 = wv * S / NW, s1 = (wv + 1) * S / NW;
-  const int Sq = Kp >> 7, q0 = wv * Sq / NW, q1 = (wv + 1) * Sq / NW;  // W8 = 3: the wave's quads
+  const int Sq = Kp >> 7, q0 = wv * Sq / NW, q1 = (wv + 1) * Sq / NW;  // W8 = 3 and 4: the wave's quads (groups)
   // Byte offsets of this lane's A row and weight rows at k-step 0; rows past
   // M read as zeros (kOob).
   const __amdgpu_buffer_rsrc_t ra = rsrc(a.x, uint32_t(a.M) * uint32_t(a.K) * 2u);
   constexpr uint32_t kWb = W8 ? 1u : 2u;   // bytes per weight element ...
-  constexpr uint32_t kWs = W8 >= 2 ? 1u : 0u;  // ... halved once more for MXFP4's and int4's nibbles
+  constexpr uint32_t kWs = W8 == 2 || W8 == 3 ? 1u : 0u;  // ... halved once more for MXFP4's and int4's nibbles
   const __amdgpu_buffer_rsrc_t rw = rsrc(a.w, (uint32_t(a.N) * uint32_t(a.K) * kWb) >> kWs);
   // MXFP4: the scale bytes, [N][K / 32]; the other formats never load through it.
   // Grouped int4: the group words, [N][K / 128] of 4 bytes, through the same descriptor slot.
   const __amdgpu_buffer_rsrc_t rs = W8 == 2   ? rsrc(a.wexp, uint32_t(a.N) * uint32_t(a.K >> 5))
                                     : W8 == 3 ? rsrc(a.wgrp, uint32_t(a.N) * uint32_t(a.K >> 7) * 4u)
+                                    : W8 == 4 ? rsrc(a.wscale, uint32_t(a.N) * uint32_t(a.K >> 7) * 4u)
                                               : rw;
   const uint32_t xoff = a_ok ? (uint32_t(m0 + m_a) * uint32_t(a.K) + uint32_t(p_a * Kp + kq)) * 2u : kOob;
   const int p_b = (lane & 15) >> cwl;  // K part of this lane's weight column
@@ -496,7 +587,16 @@ __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
       woff[t] = ((col * uint32_t(a.K) + uint32_t(p_b * Kp)) >> 1) + (uint32_t(lane >> 4) << 4);
       soff[t] = (col * uint32_t(a.K >> 7) + uint32_t(p_b * (Kp >> 7))) * 4u;
     }
+    if constexpr (W8 == 4) {
+      // Pair order: the lane group's 16 bytes of pair 0 of this lane's K part, and the scale of that part's group 0.
+      woff[t] = col * uint32_t(a.K) + uint32_t(p_b * Kp) + (uint32_t(lane >> 4) << 4);
+      soff[t] = (col * uint32_t(a.K >> 7) + uint32_t(p_b * (Kp >> 7))) * 4u;
+    }
   }
+  // W8 = 4 with a normed input: the norm weight at this lane's A fragment of k-step 0 (rows past M read zeros anyway).
+  const bool f8g_norm = W8 == 4 && EPI != EPI_RESID;
+  const __amdgpu_buffer_rsrc_t rg = f8g_norm ? rsrc(a.gin, uint32_t(a.K) * 2u) : ra;
+  const uint32_t goff = a_ok ? uint32_t(p_a * Kp + kq) * 2u : kOob;
 
   // C layout: row m = m0 + 4*(lane>>4) + r, column = tile_col(.., lane & 15).
   const int lrow0 = (lane >> 4) << 2, mrow0 = m0 + lrow0;
@@ -584,6 +684,8 @@ __global__ __launch_bounds__(NW * 64) void k_skinny(GemmArgs a) {
 #pragma unroll
   for (int t = 0; t < TN; t++) acc[t] = frag4{0.f, 0.f, 0.f, 0.f};
   if constexpr (W8 == 3) mma_stream_w4g<(UM == 4 ? 2 : 1), TN>(acc, ra, xoff, rw, woff, rs, soff, q0, q1);
+  else if constexpr (W8 == 4)
+    mma_stream_f8g<(UM == 4 ? 2 : 1), TN, EPI != EPI_RESID>(acc, ra, xoff, rw, woff, rs, soff, rg, goff, q0, q1);
   else mma_stream<UM, TN, W8>(acc, ra, xoff, rw, woff, rs, soff, s0, s1);
 
   if (norm) {

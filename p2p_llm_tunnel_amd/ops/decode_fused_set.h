@@ -1,6 +1,6 @@
 // The set of kernel instantiations of the fused decode step, stated once: decode_fused.hip (every format but grouped
-// int4), decode_w4g.hip (grouped int4, compiled without packed fp32 instructions) and decode_lora.hip (the LoRA-delta
-// variants) all instantiate from these lists and these predicates, and nothing else.
+// int4 and block-scaled FP8), decode_w4g.hip (grouped int4, compiled without packed fp32 instructions), decode_f8g.hip
+// (block-scaled FP8) and decode_lora.hip (the LoRA-delta variants) all instantiate from these lists and these predicates, and nothing else.
 #pragma once
 #include "decode_fused_kernels.h"
 
@@ -22,6 +22,7 @@ using GqaRatios = Ints<1, 2, 4, 5, 6, 7, 8>;
 using Flags = Ints<0, 1>;  // KV8 and WIN of k_attn; TAB and KV8 of k_qknorm_rope
 using SkinnyFormats = Ints<0, 1, 2>;  // W8 of k_skinny in decode_fused.hip: bf16, FP8, MXFP4
 constexpr int kW4g = 3;  // W8 of k_skinny in decode_w4g.hip: grouped int4 (docs/WEIGHT_INT4.md)
+constexpr int kF8g = 4;  // W8 of k_skinny in decode_f8g.hip: block-scaled FP8 (docs/WEIGHT_FP8G128.md)
 using SkinnyWaves = Ints<4, 8>;
 using SkinnyTiles = Ints<1, 2>;
 using SkinnyBatches = Ints<1, 2, 4>;
@@ -37,7 +38,8 @@ constexpr bool skinny_exists(int nw, int tn, int epi, int um, int w8) {
   // MXFP4 weights run a layer's four GEMMs only (the LM head stays FP8): every epilogue those can be planned with,
   // the eight RoPE ones, SILU, RESID and, for QK-norm models, STORE with one subtile, never ARGMAX, each with the
   // (nw, um) pairs of fixed_nw == 0. 44 instantiations beside the 47 of FP8 and the 66 of bf16.
-  // Grouped int4 weights likewise (the LM head stays bf16): the same 44, in decode_w4g.hip.
+  // Grouped int4 weights likewise (the LM head stays bf16): the same 44, in decode_w4g.hip. Block-scaled FP8 weights
+  // likewise: the same 44, in decode_f8g.hip.
   if (w8 >= 2 && epi == EPI_ARGMAX) return false;
   if (w8 && epi == EPI_ARGMAX) return nw == 4;
   if (w8) return nw == 4 || um == 4;

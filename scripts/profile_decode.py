@@ -45,10 +45,11 @@ def main():
                          "\"low_freq_factor\": 1, \"high_freq_factor\": 4, \"original_max_seq\": 8192}")
     ap.add_argument("--name", default=None, help="label of a --cfg model in the result line")
     ap.add_argument("--checkpoint", default=None, help="load this HF Llama checkpoint instead of a random --config")
-    ap.add_argument("--weight-dtype", choices=("bf16", "fp8", "mxfp4", "int4g128"), default="bf16",
-                    help="format of the GEMM weights: bf16, fp8 (e4m3 with per-row scales, docs/WEIGHT_FP8.md) or "
-                         "mxfp4 (block-scaled FP4 layers with an fp8 LM head, docs/WEIGHT_MXFP4.md); the fused step "
-                         "only")
+    ap.add_argument("--weight-dtype", choices=("bf16", "fp8", "mxfp4", "int4g128", "fp8g128"), default="bf16",
+                    help="format of the GEMM weights: bf16, fp8 (e4m3 with per-row scales, docs/WEIGHT_FP8.md), "
+                         "mxfp4 (block-scaled FP4 layers with an fp8 LM head, docs/WEIGHT_MXFP4.md), int4g128 (grouped "
+                         "uint4 layers, docs/WEIGHT_INT4.md) or fp8g128 (e4m3 layers with a scale per row and 128 "
+                         "input features, docs/WEIGHT_FP8G128.md); the fused step only")
     ap.add_argument("--compare", default=None, metavar="DTYPES",
                     help="weight formats to compare in this one process, e.g. bf16,fp8,mxfp4,int4g128: one model per format "
                          "from the same bf16 weights, then --windows alternating windows of --steps graph replays "
