@@ -31,12 +31,25 @@ class Request:
     engine built with ``penalties=True``, and an embedding request takes none.
     ``guide``: a ``guided.Guide`` compiled for the model's vocabulary (None is
     off): every token is then one the guide's automaton allows; needs an engine
-    built with ``guided=True``, and an embedding request takes none."""
+    built with ``guided=True``, and an embedding request takes none.
+    ``score``: True asks for the log-probability of every prompt token after
+    the first (docs/PROMPT_LOGPROBS.md); needs an engine built with
+    ``prompt_logprobs=True``. ``prompt_lp`` then holds one entry per admitted
+    prompt token, None for the first and ``(logprob, top id, top logprob)``
+    for the others, complete before the first generated token is handed over.
+    Such a request may have ``max_new`` 0: it then samples nothing and ends
+    with its last prompt row."""
 
     def __init__(self, prompt_ids: list[int], max_new: int, batched: bool = False, sampling: Sampling | None = None,
                  logprobs: int | None = None, embed: str | None = None, penalties: Penalties | None = None,
-                 guide=None, adapter: str | None = None):
+                 guide=None, adapter: str | None = None, score: bool = False):
         self.adapter = adapter  # the name of a LoRA adapter the engine was built with (docs/LORA.md); None: the base
+        if not isinstance(score, bool):
+            raise TypeError(f"score must be a bool, got {score!r}")
+        if score and embed is not None:
+            raise ValueError("an embedding request scores no prompt tokens")
+        self.score = score
+        self.prompt_lp: list = []
         if embed not in (None, "mean", "last"):
             raise ValueError(f'embed must be None, "mean" or "last", got {embed!r}')
         if guide is not None:
@@ -137,6 +150,11 @@ class _StepBuf:
         # buffers ([max_batch, dim] fp32, device and pinned) come with the first such step.
         self.embeds = []
         self.d_emb = self.h_emb = None
+        # Scoring rows of this step: (row, req, index of the scored prompt token), and the scoring requests without
+        # generation that end in it. The buffers (targets in, three floats and an id per row out; device and pinned)
+        # come with the first such step.
+        self.scores, self.scored = [], []
+        self.h_tgt = self.d_tgt = self.d_sc = self.d_sc_id = self.h_sc = self.h_sc_id = None
 
 
 # What follows the fused step inside a captured graph, its ``post``, is described here and nowhere else. The stages,
@@ -437,12 +455,25 @@ class Engine:
     "fp8" builds an MoE model with FP8 expert matrices, which only the
     graph-captured HIP step multiplies; "mxfp4" one with MXFP4 expert matrices (docs/MOE_MXFP4.md), likewise. The
     number of graphs is what it is without.
+
+    ``prompt_logprobs`` (off by default, and then nothing above changes; docs/PROMPT_LOGPROBS.md):
+    serves ``Request(score=True)``. A scoring request prefills its whole prompt
+    (it takes no cached prefix), and the prompt row at position p is scored for
+    the prompt's token p + 1. Like the embed rows, these rows are served from
+    the decoder's ``resid`` buffer right after the replay of their step:
+    ``model.lm_score`` (lm_score.hip; never captured, one call per step) writes
+    log-sum-exp, target logit, top logit and top id of every scoring row, and
+    they come back through pinned memory with the step's event. A row's result
+    depends on the row alone, so it is the same however the prompt is split
+    over steps and whatever else the steps carry. A scoring request with
+    ``max_new`` 0 samples nothing and ends with its last prompt row. The number
+    of graphs is what it is without the switch.
     """
 
     def __init__(self, device="cuda:0", config="tiny", max_batch=8, seed=0, use_graph=True, rows=64, model=None,
                  small_rows=16, prefix_cache=False, prefix_min=16, penalties=False, kv_dtype="bf16",
                  guided=False, guided_states=1024, weight_dtype="bf16", kv_scales=None, min_p=False,
-                 chunk_attn=False, expert_dtype="bf16", loras=None):
+                 chunk_attn=False, expert_dtype="bf16", loras=None, prompt_logprobs=False):
         if kv_scales is not None and kv_dtype != "fp8" and getattr(model, "kv_dtype", "bf16") != "fp8":
             raise ValueError("kv_scales need kv_dtype='fp8' (--kv-dtype fp8): a bf16 KV cache has no scales")
         if model is None:
@@ -544,6 +575,11 @@ class Engine:
         self.cached_tokens = 0  # prompt rows not run, over all requests
         self.kv_copies = 0  # slot-to-slot copy jobs issued
         self.can_embed = callable(getattr(model, "embed_pool", None))
+        if prompt_logprobs and not (use_graph and callable(getattr(model, "lm_score", None))):
+            raise ValueError("prompt_logprobs needs the graph-captured HIP step and a model with lm_score(...)")
+        self.prompt_logprobs = bool(prompt_logprobs)
+        self.scored_tokens = 0  # prompt tokens scored
+        self._scores, self._scored = [], []  # _plan -> _launch: the step's scoring rows, and the requests that end
         self.embeddings = 0  # embedding requests finished
         self._pools = []  # _plan -> _launch: the step's (slot, first row, rows, first piece, req when it finishes)
         # Prefix cache: per slot the state of the request that last took it (its residency; kept after the slot is
@@ -560,6 +596,8 @@ class Engine:
     def submit(self, req: Request) -> Request:
         if req.logprobs is not None and not self.use_graph:
             raise ValueError("logprobs need the graph-captured HIP step; this engine runs eagerly")
+        if req.score and not self.prompt_logprobs:
+            raise ValueError("score needs an engine built with prompt_logprobs=True (--prompt-logprobs)")
         if req.embed is not None and not self.can_embed:
             raise ValueError("embeddings need a model with embed_pool(jobs, out) (pooling of the final hidden state)")
         if req.penalties is not None and self._pen is None:
@@ -622,7 +660,7 @@ class Engine:
             return free[0], 0, None
         m, src = 0, None
         for i, s in enumerate(self._kv):
-            if s is None or req.embed is not None:  # an embed request pools every row: it takes no prefix
+            if s is None or req.embed is not None or req.score:  # every row is pooled, or scored: no prefix
                 continue
             if s["req"].adapter != req.adapter:  # a slot's rows belong to the adapter that wrote them
                 continue
@@ -653,14 +691,17 @@ class Engine:
             # max_new is clamped so prompt + generated rows fit max_seq; a prompt too long for the rest keeps its end
             # (for a chat, the latest turns and the generation prompt). An embed request generates nothing: the
             # prompt's head, up to the cache's rows.
-            req.max_new = max(1, min(req.max_new, max_seq - 2))
+            quiet = req.embed is not None or (req.score and req.max_new == 0)  # it samples nothing
+            req.max_new = 0 if quiet and req.score else max(1, min(req.max_new, max_seq - 2))
             cut = req.prompt[:max_seq - 1] if req.embed is not None else req.prompt[-(max_seq - req.max_new - 1):]
             ids = [t % V for t in cut] or [0]
             slot, m, src = self._choose(free, ids, req)
             free.remove(slot)
             if src is not None:
                 jobs.append((src, slot, m))
-            self.slots[slot] = s = {"req": req, "pos": m, "ids": ids, "gen": 0, "embed": req.embed}
+            self.slots[slot] = s = {"req": req, "pos": m, "ids": ids, "gen": 0, "embed": req.embed, "quiet": quiet}
+            if req.score:
+                req.prompt_lp = [None] * len(ids)
             self._slot_aid[slot] = self.lora_names.index(req.adapter) if req.adapter is not None else -1
             if self.prefix_cache:  # the slot's residency (``_resident``): ``_drain`` adds the outputs to ``known``
                 s["known"] = list(ids)
@@ -702,13 +743,13 @@ class Engine:
         for i, s in enumerate(self.slots):  # then prompt chunks
             if s is None or s["pos"] >= len(s["ids"]):
                 continue
-            if s["embed"] and s["req"].cancelled:  # it never reaches a decode row: dropped here
+            if s["quiet"] and s["req"].cancelled:  # it never reaches a decode row: dropped here
                 self._emit(s["req"], None, batch)
                 self.slots[i] = None
                 continue
             take = min(self.rows - len(rows), len(s["ids"]) - s["pos"])
             for p in range(s["pos"], s["pos"] + take):
-                rows.append(_Row(i, s["ids"][p], p, 0, p == len(s["ids"]) - 1 and not s["embed"]))
+                rows.append(_Row(i, s["ids"][p], p, 0, p == len(s["ids"]) - 1 and not s["quiet"]))
             if len(rows) >= self.rows:
                 break
         # Rows that sample go first: the 64-row graph's LM head covers only the
@@ -724,6 +765,14 @@ class Engine:
                     pools[-1][2] += 1
                 else:
                     pools.append([row.slot, r, 1, row.pos == 0, None])
+        # Scoring rows: a prompt row at position p is scored for the prompt's token p + 1.
+        self._scores = scores = []
+        self._scored = scored = []
+        if self.prompt_logprobs:
+            for r, row in enumerate(rows):
+                s = self.slots[row.slot]
+                if s["req"].score and not row.decode and row.pos + 1 < len(s["ids"]):
+                    scores.append((r, s["req"], row.pos + 1, s["ids"][row.pos + 1]))
         # Advance every row's slot first: after the sort a slot's sampling row
         # can precede its other prompt rows, so slots are only freed once all
         # rows of the step are accounted for.
@@ -748,6 +797,11 @@ class Engine:
             if s["pos"] >= len(s["ids"]):
                 pool[4] = s["req"]
                 done.append(pool[0])
+        for i in {row.slot for row in rows}:  # a scoring request without generation is done with its last prompt row
+            s = self.slots[i]
+            if s["quiet"] and s["req"].score and s["pos"] >= len(s["ids"]):
+                scored.append(s["req"])
+                done.append(i)
         for i in done:
             self.slots[i] = None
         return rows, emits
@@ -852,6 +906,9 @@ class Engine:
         b.embeds = []
         if self._pools:
             self._pool(b, self._pools)
+        b.scores, b.scored = self._scores, self._scored
+        if b.scores:
+            self._score(b, n)
         if b.ev is not None:
             b.ev.record()
         self.steps += 1
@@ -879,9 +936,36 @@ class Engine:
         if b.embeds:
             b.h_emb[:len(b.embeds)].copy_(b.d_emb[:len(b.embeds)], non_blocking=True)
 
+    def _score(self, b: _StepBuf, n: int):
+        """Score the scoring rows of the step just queued (see the class docstring)."""
+        if b.h_tgt is None:
+            pin = self.device.type == "cuda"
+            b.h_tgt = torch.zeros(b.rows, dtype=torch.int32, pin_memory=pin)
+            b.d_tgt = torch.zeros(b.rows, dtype=torch.int32, device=self.device)
+            b.d_sc = torch.zeros((3, b.rows), dtype=torch.float32, device=self.device)
+            b.d_sc_id = torch.zeros(b.rows, dtype=torch.int32, device=self.device)
+            b.h_sc = torch.zeros((3, b.rows), dtype=torch.float32, pin_memory=pin)
+            b.h_sc_id = torch.zeros(b.rows, dtype=torch.int32, pin_memory=pin)
+        t = b.h_tgt.numpy()
+        t[:] = -1
+        for r, _, _, tok in b.scores:
+            t[r] = tok  # below the vocabulary: _admit reduced every id
+        b.d_tgt.copy_(b.h_tgt, non_blocking=True)
+        self.model.lm_score(b.d_tgt[:n], b.d_sc[0, :n], b.d_sc[1, :n], b.d_sc[2, :n], b.d_sc_id[:n])
+        b.h_sc.copy_(b.d_sc, non_blocking=True)
+        b.h_sc_id.copy_(b.d_sc_id, non_blocking=True)
+
     def _drain(self, b: _StepBuf, batch: list):
         if b.ev is not None:
             b.ev.synchronize()  # GIL released: the HTTP thread writes meanwhile
+        if b.scores:  # ahead of the tokens: the prompt's record is complete when the first one is handed over
+            lse, zt, ztop = b.h_sc.tolist()
+            top = b.h_sc_id.tolist()
+            for r, req, at, _ in b.scores:
+                req.prompt_lp[at] = (zt[r] - lse[r], top[r], ztop[r] - lse[r])
+            self.scored_tokens += len(b.scores)
+        for req in b.scored:
+            self._emit(req, None, batch)
         out = b.h_out[: b.n].tolist() if b.emits else []
         for r, req, fin, _ in b.emits:
             if self.prefix_cache:  # drained: the id is known (a cancelled request's too: its row may have been fed)

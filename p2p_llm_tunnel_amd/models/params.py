@@ -289,6 +289,70 @@ def logprob_params(body: dict, kind: str) -> int | None:
     return n or None
 
 
+def prompt_logprob_params(body: dict, kind: str, enabled: bool) -> tuple:
+    """What a request wants of its own prompt (docs/PROMPT_LOGPROBS.md): ``(echo, legacy, vllm)``. ``echo``: the
+    prompt's text leads the completion's; ``legacy``: None, or N in 0..1 when /v1/completions (``kind`` "text") has
+    "echo": true beside its integer "logprobs", whose lists then start with the prompt's tokens; ``vllm``: None, or
+    vLLM's "prompt_logprobs" N in 0..1 (every OpenAI route). N is how many top tokens go with each prompt token's
+    own log-probability. Without ``enabled`` (a server started without --prompt-logprobs), and on the Ollama routes,
+    neither key is looked at: (False, None, None). Raises SamplingError (answered with 400) for anything else, top-N
+    above 1 included."""
+    if not enabled or kind not in ("chat", "text"):
+        return False, None, None
+
+    def top_n(key, v):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 0:
+            raise SamplingError(f"{key} must be an integer >= 0, got {v!r}")
+        if v > 1:
+            raise SamplingError(f"{key}={v!r} with the prompt's tokens is not supported: a prompt token comes with "
+                                "its own log-probability and at most the top 1")
+        return v
+
+    vllm = body.get("prompt_logprobs")
+    vllm = None if vllm is None else top_n("prompt_logprobs", vllm)
+    echo = body.get("echo")
+    if echo is not None and not isinstance(echo, bool):
+        raise SamplingError(f"echo must be a boolean, got {echo!r}")
+    if echo and kind != "text":
+        raise SamplingError("echo belongs to /v1/completions")
+    lp = body.get("logprobs")
+    legacy = top_n("logprobs (with echo)", lp) if echo and lp is not None and lp is not False else None
+    return bool(echo), legacy, vllm
+
+
+def prompt_logprobs_legacy(tokens: list[int], records: list, text_of, top: int) -> dict:
+    """The prompt's share of a legacy completion's ``choices[0].logprobs`` under "echo": ``completion_logprobs``'
+    four lists over the prompt's tokens. ``records`` is ``Request.prompt_lp``: None for the first token, whose
+    ``token_logprobs`` and ``top_logprobs`` are null, then ``(logprob, top id, top logprob)``; ``top`` 1 puts the
+    top token into ``top_logprobs``, 0 leaves those objects empty."""
+    out = {"tokens": [], "token_logprobs": [], "top_logprobs": [], "text_offset": []}
+    offset = 0
+    for t, rec in zip(tokens, records):
+        text = text_of(t)
+        out["tokens"].append(text)
+        out["token_logprobs"].append(None if rec is None else _finite(rec[0]))
+        out["top_logprobs"].append(None if rec is None else {text_of(rec[1]): _finite(rec[2])} if top else {})
+        out["text_offset"].append(offset)
+        offset += len(text)
+    return out
+
+
+def prompt_logprobs_vllm(tokens: list[int], records: list, text_of, top: int) -> list:
+    """vLLM's ``prompt_logprobs``: null for the first prompt token, then one object per token that maps a token id
+    to ``{"logprob", "decoded_token"}``: the prompt token's own and, with ``top`` 1, the most likely one's (which
+    carries "rank": 1)."""
+    out = []
+    for t, rec in zip(tokens, records):
+        if rec is None:
+            out.append(None)
+            continue
+        entry = {str(t): {"logprob": _finite(rec[0]), "decoded_token": text_of(t)}}
+        if top:
+            entry.setdefault(str(rec[1]), {"logprob": _finite(rec[2]), "decoded_token": text_of(rec[1])})["rank"] = 1
+        out.append(entry)
+    return out
+
+
 def _finite(x: float) -> float:
     """JSON has no -inf: a non-finite logprob is sent as -9999.0, as the OpenAI API does."""
     return x if -float("inf") < x < float("inf") else -9999.0

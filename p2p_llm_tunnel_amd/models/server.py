@@ -101,6 +101,13 @@ is "" when the detokeniser or the stop matcher holds the text back).
 Non-finite values are sent as -9999.0. The eager engine has no logits and
 answers such a request with 400; /api/generate has no logprobs.
 
+Prompt log-probabilities (--prompt-logprobs, off by default: "echo" and
+"prompt_logprobs" are then not looked at): /v1/completions takes "echo": true
+with "logprobs" 0 or 1, "max_tokens": 0 included, and the OpenAI routes vLLM's
+"prompt_logprobs" 0 or 1 (``params.prompt_logprob_params``). The prompt's rows
+are scored after their step by ops.lm_score_ (lm_score.hip), outside the
+captured graphs. See docs/PROMPT_LOGPROBS.md.
+
 Prefix cache (--prefix-cache, off by default): a request whose prompt begins
 like the K/V rows a cache slot already holds — the next turn of a chat, a
 second stream with the same system prompt — takes those rows instead of
@@ -148,6 +155,7 @@ from p2p_llm_tunnel_amd.models.engine import Engine, Request
 from p2p_llm_tunnel_amd.models.params import (_LOGPROB_KEYS, Penalties, Sampling, SamplingError,  # noqa: F401
                                               StopMatcher, adapter_param, chat_logprob_entry, chat_logprobs,
                                               completion_logprobs, guided_params, logprob_params, model_names,
+                                              prompt_logprob_params, prompt_logprobs_legacy, prompt_logprobs_vllm,
                                               penalty_params, sampling_params, stop_sequences)
 
 
@@ -225,9 +233,13 @@ class _Stream:
     template around each token piece (token ids render as " t<id>": no JSON
     escaping needed)."""
     __slots__ = ("writer", "stream", "kind", "rid", "pre", "post", "toks", "done", "detok", "reason", "stop",
-                 "stop_hit", "lp_toks", "lp_off", "t0", "t_first", "created", "n_tok")
+                 "stop_hit", "lp_toks", "lp_off", "t0", "t_first", "created", "n_tok", "prompt_part", "echoed")
 
-    def __init__(self, writer, stream, kind, rid, model, detok=None, stop=None, logprobs=False):
+    def __init__(self, writer, stream, kind, rid, model, detok=None, stop=None, logprobs=False, prompt_part=None):
+        # --prompt-logprobs: (echo, legacy N or None, vLLM N or None) of a request that wants its prompt back, until
+        # the prompt's share of the response has been rendered; ``echoed`` is that share of a non-streamed response.
+        self.prompt_part = prompt_part
+        self.echoed = None
         self.t0 = time.perf_counter_ns()  # /api/chat's durations: the request's start, and its first token's arrival
         self.t_first = 0
         self.n_tok = 0  # tokens taken from the engine (the EOS token or a matched stop's included)
@@ -369,6 +381,8 @@ class FrontEnd:
                 continue
             if not st.t_first:
                 st.t_first = time.perf_counter_ns()
+            if st.prompt_part is not None:  # the engine has scored the whole prompt by now
+                self._prompt_part(req, st)
             if tok is None:
                 self._finish(req, st)
                 continue
@@ -403,6 +417,29 @@ class FrontEnd:
 
     def _token_text(self, tid: int) -> str:
         return self.tok.decode([tid]) if self.tok is not None else " t%d" % tid
+
+    def _prompt_part(self, req, st):
+        """The prompt's share of a response (--prompt-logprobs): its text under "echo", its tokens' entries at the
+        head of the legacy "logprobs" lists, vLLM's "prompt_logprobs". Streamed, it is the first chunk; otherwise
+        ``_finish`` joins it with the completion's."""
+        echo, legacy, vllm = st.prompt_part
+        st.prompt_part = None
+        text = "".join(self._token_text(t) for t in req.prompt) if echo else ""
+        lp = prompt_logprobs_legacy(req.prompt, req.prompt_lp, self._token_text, legacy) if legacy is not None else None
+        plp = prompt_logprobs_vllm(req.prompt, req.prompt_lp, self._token_text, vllm) if vllm is not None else None
+        st.lp_off = len(text)
+        if not st.stream:
+            st.echoed = (text, lp, plp)
+            return
+        choice = {"index": 0, "delta": {"content": ""}} if st.kind == "chat" else {"index": 0, "text": text}
+        if lp is not None:
+            choice["logprobs"] = lp
+        if plp is not None:
+            choice["prompt_logprobs"] = plp
+        choice["finish_reason"] = None
+        obj = {"id": st.rid, "object": "chat.completion.chunk" if st.kind == "chat" else "text_completion",
+               "model": self.model_name, "choices": [choice]}
+        st.writer.write(_chunk(f"data: {json.dumps(obj, ensure_ascii=False)}\n\n".encode()))
 
     def _on_token_logprobs(self, req, st, tok):
         """A token of a request with logprobs: its entry goes out with it. A
@@ -491,7 +528,17 @@ class FrontEnd:
                        "choices": [{"index": 0, "text": text, "finish_reason": st.reason}]}
             if st.lp_toks is not None:  # (never an Ollama request)
                 render = chat_logprobs if st.kind == "chat" else completion_logprobs
-                obj["choices"][0]["logprobs"] = render(st.lp_toks, req.lp[:len(st.lp_toks)], self._token_text)
+                obj["choices"][0]["logprobs"] = render(st.lp_toks, req.lp[:len(st.lp_toks)], self._token_text,
+                                                       **({"offset": st.lp_off} if st.kind == "text" else {}))
+            if st.echoed is not None:  # the prompt first: its text, its tokens' entries, vLLM's field
+                head, lp, plp = st.echoed
+                choice = obj["choices"][0]
+                if st.kind == "text":
+                    choice["text"] = head + choice["text"]
+                if lp is not None:
+                    choice["logprobs"] = {k: v + choice["logprobs"][k] for k, v in lp.items()}
+                if plp is not None:
+                    choice["prompt_logprobs"] = plp
             w.write(self._json_response(obj))
         st.done.set_result(True)
 
@@ -747,6 +794,9 @@ class FrontEnd:
             penalties = penalty_params(rest, ollama, self.engine.model.cfg.vocab) if pen_on else None
             stops = stop_sequences(req_body, ollama)
             template_kwargs = chat_template_kwargs(req_body)
+            prompt_part = prompt_logprob_params(req_body, kind, getattr(self.engine, "prompt_logprobs", False))
+            if prompt_part[1] is not None:  # "echo" with "logprobs" 0 or 1: the completion's tokens get the same
+                logprobs = prompt_part[1]
             guide = None
             if getattr(self.engine, "guided", False) and not ollama:
                 want = guided_params(req_body)
@@ -766,10 +816,23 @@ class FrontEnd:
         stream = bool(req_body.get("stream", ollama))
         rid = ("chatcmpl-" if kind == "chat" else "cmpl-") + uuid.uuid4().hex[:12]
         prompt = _prompt_ids(req_body, self.tok, template_kwargs)
-        req = Request(prompt, max(1, min(max_new, 1024)), batched=True, sampling=sampling, logprobs=logprobs,
-                      penalties=penalties, guide=guide, adapter=adapter)
+        score = prompt_part[1] is not None or prompt_part[2] is not None
+        # "max_tokens": 0 is a scoring request's alone (lm-eval's log-likelihood call): it samples nothing.
+        use_new = 0 if score and max_new == 0 else max(1, min(max_new, 1024))
+        if prompt_part == (False, None, None):
+            prompt_part = None
+        elif max_new < 0 or len(prompt) + use_new + 1 > self.engine.model.cfg.max_seq:
+            # The engine would keep the prompt's end only: the response could not give the prompt back whole.
+            writer.write(self._json_response({"error": {
+                "message": f"a request that echoes or scores its prompt must fit the context: {len(prompt)} prompt "
+                           f"tokens and max_tokens {max_new} exceed {self.engine.model.cfg.max_seq - 1}",
+                "type": "invalid_request_error"}}, 400))
+            return True
+        req = Request(prompt, use_new, batched=True,
+                      sampling=sampling, logprobs=logprobs, penalties=penalties, guide=guide, adapter=adapter,
+                      **({"score": True} if score else {}))
         st = _Stream(writer, stream, kind, rid, name, self.tok.detokenizer(prompt) if self.tok is not None else None,
-                     StopMatcher(stops) if stops else None, logprobs is not None)
+                     StopMatcher(stops) if stops else None, logprobs is not None, prompt_part)
         req.state = st
         if stream:
             writer.write(b"HTTP/1.1 200 OK\r\nContent-Type: %s\r\nCache-Control: no-cache\r\n"
@@ -785,7 +848,7 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
                  embed_pooling: str = "mean", penalties: bool = False, kv_dtype: str = "bf16",
                  guided: bool = False, guided_states: int = 1024, weight_dtype: str = "bf16", kv_scales=None,
                  sliding_window: bool = False, min_p: bool = False, chunk_attn: bool = False,
-                 expert_dtype: str = "bf16", loras: dict | None = None):
+                 expert_dtype: str = "bf16", loras: dict | None = None, prompt_logprobs: bool = False):
     """Engine + HTTP front-end; returns (server, port, engine). ``server.shutdown()``
     stops the HTTP side, ``engine.stop()`` the GPU side. ``checkpoint``: serve a
     Hugging Face Llama checkpoint directory (weights + tokenizer) instead of
@@ -816,7 +879,12 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
     ``load_llama``'s: the format of an MoE model's stacked expert matrices alone; a dense model refuses "fp8" and
     "mxfp4", and an injected engine's model must have it.
     ``loras`` (docs/LORA.md): name -> PEFT adapter directory, at most 8, served beside the base model; a request
-    whose "model" is one of the names runs under that adapter. Refused with an injected engine."""
+    whose "model" is one of the names runs under that adapter. Refused with an injected engine.
+    ``prompt_logprobs`` is ``Engine``'s (docs/PROMPT_LOGPROBS.md): /v1/completions then takes "echo": true with
+    "logprobs" 0 or 1, and the OpenAI routes vLLM's "prompt_logprobs" 0 or 1 (``prompt_logprob_params``); without it
+    neither key is looked at. An injected engine must have been built with it."""
+    if engine is not None and prompt_logprobs and not getattr(engine, "prompt_logprobs", False):
+        raise ValueError("prompt_logprobs=True, but the injected engine was built without it")
     expert_dtype = parse_expert_dtype(expert_dtype)
     loras = check_loras(loras)
     if loras and engine is not None:
@@ -863,7 +931,7 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
         tok = tok or Tokenizer.for_checkpoint(checkpoint)
         engine = Engine(device=device, max_batch=max_batch, model=model, prefix_cache=prefix_cache,
                         prefix_min=prefix_min, penalties=penalties, guided=guided, guided_states=guided_states,
-                        min_p=min_p)
+                        min_p=min_p, **({"prompt_logprobs": True} if prompt_logprobs else {}))
         model_name = model_name or os.path.basename(os.path.normpath(checkpoint))
     if loras and engine is None:  # a random-init config: the adapters are read against its shapes
         from p2p_llm_tunnel_amd.models.checkpoint import load_lora
@@ -873,7 +941,8 @@ def start_server(host="127.0.0.1", port=0, device="cuda:0", config="tiny", max_b
     engine = engine or Engine(device=device, config=config, **({"loras": loras} if loras else {}), max_batch=max_batch, prefix_cache=prefix_cache,
                               prefix_min=prefix_min, penalties=penalties, kv_dtype=kv_dtype, guided=guided,
                               guided_states=guided_states, weight_dtype=weight_dtype, kv_scales=kv_scales,
-                              min_p=min_p, chunk_attn=chunk_attn, expert_dtype=expert_dtype)
+                              min_p=min_p, chunk_attn=chunk_attn, expert_dtype=expert_dtype,
+                              **({"prompt_logprobs": True} if prompt_logprobs else {}))
     srv = FrontEnd(engine, host, port, model_name or f"p2pt-{config}", tokenizer=tok,
                    default_temperature=default_temperature, embed_pooling=embed_pooling)
     return srv, srv.server_address[1], engine
@@ -1025,6 +1094,8 @@ def replica_cmd(a, i: int) -> list[str]:
         cmd += ["--expert-dtype", a.expert_dtype]
     for spec in getattr(a, "lora", None) or ():
         cmd += ["--lora", spec]
+    if getattr(a, "prompt_logprobs", False):
+        cmd += ["--prompt-logprobs"]
     return cmd
 
 
@@ -1140,6 +1211,12 @@ def arg_parser() -> argparse.ArgumentParser:
                          "the base model; repeatable, at most 8. A request whose model is NAME runs under it, batched "
                          "with requests for the base and for other adapters. Dense bf16 models without QK-norm only; "
                          "costs the adapter tables and a second set of captured graphs (docs/LORA.md)")
+    ap.add_argument("--prompt-logprobs", action="store_true",
+                    help="score prompts on the device: /v1/completions takes echo: true with logprobs 0 or 1 "
+                         "(max_tokens 0 included: lm-eval's log-likelihood call) and the OpenAI routes vLLM's "
+                         "prompt_logprobs 0 or 1, instead of ignoring both. A scoring request prefills its whole "
+                         "prompt; its rows are scored by an fp32 LM-head kernel after their step, outside the "
+                         "captured graphs, whose number stays (docs/PROMPT_LOGPROBS.md)")
     ap.add_argument("--guided", action="store_true",
                     help="guided decoding on the device: /v1/chat/completions and /v1/completions act on "
                          "guided_regex, guided_choice and structured_outputs {regex | choice} (a checkpoint with a "
@@ -1165,7 +1242,8 @@ def main(argv=None):
                                      embed_pooling=a.embed_pooling, penalties=a.penalties, kv_dtype=a.kv_dtype,
                                      guided=a.guided, guided_states=a.guided_states, weight_dtype=a.weight_dtype,
                                      kv_scales=a.kv_scales, sliding_window=a.sliding_window, min_p=a.min_p,
-                                     chunk_attn=a.chunk_attn, expert_dtype=a.expert_dtype, loras=a.lora)
+                                     chunk_attn=a.chunk_attn, expert_dtype=a.expert_dtype, loras=a.lora,
+                                     **({"prompt_logprobs": True} if a.prompt_logprobs else {}))
     for line in lora_lines(engine.model):
         print(line, flush=True)
     print(weights_line(engine.model, a.weight_dtype), flush=True)

@@ -557,6 +557,15 @@ class TinyLlama:
             self._embed_acc = torch.zeros(self.max_batch + 1, self.cfg.dim, dtype=torch.float32, device=self.device)
         self.fused_decoder().embed_pool(self._embed_acc, out, jobs)
 
+    def lm_score(self, target: torch.Tensor, lse: torch.Tensor, z_target: torch.Tensor, z_top: torch.Tensor,
+                 id_top: torch.Tensor) -> None:
+        """Score the first ``len(target)`` rows of the last fused step against the LM head on the current stream
+        (``ops.lm_score_``; docs/PROMPT_LOGPROBS.md): ``target`` int32, the token each row is scored for (negative:
+        the row is off and its outputs stay), the outputs fp32, fp32, fp32 and int32 of the same length."""
+        if not self.fused:
+            raise ValueError("lm_score needs the fused path (it reads the fused step's workspace)")
+        self.fused_decoder().lm_score(target, lse, z_target, z_top, id_top)
+
     # ------------------------------------------------------------------ HIP path
     @torch.no_grad()
     def decode_step(self, tokens: torch.Tensor, pos: torch.Tensor, pos_range: tuple[int, int],

@@ -165,6 +165,13 @@ class LoraTable(ctypes.Structure):
     _fields_ = [("n_adapters", _INT), ("rank", _INT * 4), ("tables", ctypes.POINTER(ctypes.c_void_p))]
 
 
+class LmScorePlan(ctypes.Structure):
+    """What ``lm_score_`` launches (lm_score.hip): ``k_lm_score`` on ``slabs * tiles`` workgroups of ``threads``, each
+    a slab of ``slab`` vocabulary columns of one 16-row tile, then the merge on one wave per row; ``work_words``
+    4-byte words of scratch."""
+    _fields_ = [(n, _INT) for n in ("slab", "slabs", "tiles", "threads", "work_words")]
+
+
 class StepOptions(ctypes.Structure):
     """Mirror of ``StepOptions``: every option of a fused step, as ``p2pt_llama_step``, ``p2pt_llama_step_kernels``,
     ``p2pt_llama_step_ws`` and ``p2pt_llama_step_weights`` take them. All zero: the bf16 dense step. ``kv_scales``: a
@@ -334,6 +341,8 @@ def _signatures() -> dict:
         "p2pt_max_kv_copy_jobs": [],
         "p2pt_embed_pool": [vp, i, i, vp, vp, i, vp, i, f, i, ip, vp],
         "p2pt_max_embed_jobs": [],
+        "p2pt_lm_score": [vp, i, i, vp, vp, i, i, f, vp, vp, sz, vp, vp, vp, vp, vp],
+        "p2pt_lm_score_plan": [i, i, i, ptr(LmScorePlan)],
         "p2pt_penalize": [vp, vp, vp, vp, vp, vp, vp, i, vp, i, vp, vp, vp, i, i, vp],
         "p2pt_penalty_reset": [vp, i, i, i, vp, i, vp, vp, vp, vp, i, vp],
         "p2pt_max_logit_bias": [],
@@ -1483,6 +1492,70 @@ def embed_pool_(resid: torch.Tensor, norm_weight: torch.Tensor, acc: torch.Tenso
                               float(eps), len(jobs), arr, _stream(resid)), "embed_pool")
 
 
+def lm_score_plan(V: int, dim: int, rows: int) -> LmScorePlan:
+    """The grids of ``lm_score_`` for a ``[V, dim]`` LM head and ``rows`` rows of resid (host only: the library, no
+    GPU). A function of the shapes alone."""
+    plan = LmScorePlan()
+    if not all(_int_in(v, 1, 1 << 31) for v in (V, dim, rows)) or \
+            lib().p2pt_lm_score_plan(V, dim, rows, ctypes.byref(plan)) != 0:
+        raise ValueError(f"lm_score needs V >= 1, dim a multiple of 32 up to 16384 and 1..{MAX_ROWS} rows, got V {V!r}, "
+                         f"dim {dim!r}, rows {rows!r}")
+    return plan
+
+
+def lm_score_(resid: torch.Tensor, lm_head: torch.Tensor, scale: torch.Tensor | None, eps: float,
+              target: torch.Tensor, lse: torch.Tensor, z_target: torch.Tensor, z_top: torch.Tensor,
+              id_top: torch.Tensor, work: torch.Tensor | None = None, check_targets: bool = True) -> None:
+    """Score rows of the fused step's final residual against the LM head without writing a logit (lm_score.hip;
+    docs/PROMPT_LOGPROBS.md). ``resid`` is bf16 [rows <= 64, dim]; ``lm_head`` the fused table's entry, [V, dim] with
+    the final-norm weight folded in, bf16 with ``scale`` None or e4m3 (or uint8) bytes with ``scale`` fp32 (V,);
+    ``target`` int32 (rows,), a negative entry turns its row off. For every other row, with
+    ``z[v] = ((x . W'[v]) * scale[v]) / rms(x)`` held in fp32 from the MFMA accumulator on, ``lse`` = log sum exp z,
+    ``z_target`` = z[target], ``z_top`` = max z and ``id_top`` its lowest id (fp32, fp32, fp32, int32, each (rows,));
+    the token's log-probability is ``z_target - lse``. A row that is off touches no output. ``work``: int32 scratch
+    of ``lm_score_plan(..).work_words`` words (allocated when None). ``check_targets=False`` skips the one check
+    that reads the device (``target < V``; a target past V matches no column and leaves ``z_target`` at -inf): a
+    caller that built the targets on the host, as the engine does, has checked them there."""
+    _check(resid, torch.bfloat16, "resid")
+    dev = resid.device
+    if resid.dim() != 2 or not 1 <= resid.shape[0] <= MAX_ROWS:
+        raise ValueError(f"resid must be [rows <= {MAX_ROWS}, dim], got {tuple(resid.shape)}")
+    rows, dim = resid.shape
+    if not isinstance(lm_head, torch.Tensor) or lm_head.dim() != 2 or lm_head.shape[1] != dim or lm_head.shape[0] < 1:
+        raise ValueError(f"lm_head must be [V >= 1, {dim}], got {tuple(getattr(lm_head, 'shape', ()))}")
+    V = lm_head.shape[0]
+    plan = lm_score_plan(V, dim, rows)
+    w8 = lm_head.dtype in WEIGHT_FP8_DTYPES
+    _check(lm_head, lm_head.dtype if w8 else torch.bfloat16, "lm_head", dev)
+    if w8:
+        if scale is None:
+            raise ValueError("an FP8 lm_head needs its fp32 row scales")
+        _check(scale, torch.float32, "scale", dev)
+        if scale.shape != (V,):
+            raise ValueError(f"scale shape {tuple(scale.shape)} != ({V},)")
+    elif scale is not None:
+        raise ValueError("a bf16 lm_head has no scales")
+    _check(target, torch.int32, "target", dev)
+    for name, t, dt in (("lse", lse, torch.float32), ("z_target", z_target, torch.float32),
+                        ("z_top", z_top, torch.float32), ("id_top", id_top, torch.int32)):
+        _check(t, dt, name, dev)
+    if any(t.shape != (rows,) for t in (target, lse, z_target, z_top, id_top)):
+        raise ValueError(f"target, lse, z_target, z_top and id_top must be ({rows},)")
+    if isinstance(eps, bool) or not isinstance(eps, (int, float)) or not 0.0 <= eps < float("inf"):
+        raise ValueError(f"eps must be a finite number >= 0, got {eps!r}")
+    if work is None:
+        work = torch.empty(plan.work_words, dtype=torch.int32, device=dev)
+    _check(work, torch.int32, "work", dev)
+    if work.numel() < plan.work_words:
+        raise ValueError(f"work holds {work.numel()} words, lm_score_plan asks for {plan.work_words}")
+    if resid.data_ptr() % 16 or work.data_ptr() % 16 or lm_head.data_ptr() % (8 if w8 else 16):
+        raise ValueError("resid, work and a bf16 lm_head must be 16-byte aligned, an FP8 lm_head 8-byte aligned")
+    if check_targets and int(target.max().item()) >= V:
+        raise ValueError(f"target ids must be below V = {V}")
+    _ok(lib().p2pt_lm_score(_p(resid), rows, dim, _p(lm_head), _p(scale), int(w8), V, float(eps), _p(target), _p(work),
+                            work.numel(), _p(lse), _p(z_target), _p(z_top), _p(id_top), _stream(resid)), "lm_score")
+
+
 def f32_bits(x: float) -> int:
     """The float32 bit pattern of x as a non-negative int (the sampler's params encoding)."""
     import struct
@@ -2172,7 +2245,8 @@ class FusedLlamaDecoder:
         self.ws = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
         self.k_cache, self.v_cache = k_cache, v_cache
         self.device = dev
-        self._resid = None  # embed_pool's view of the workspace's resid buffer
+        self._resid = None  # embed_pool's and lm_score's view of the workspace's resid buffer
+        self._score_work = None  # lm_score's partials, allocated on first use
 
     _WS_BUFFERS = WS_BUFFERS[:WS_DENSE]  # the buffers p2pt_llama_ws_layout reports
 
@@ -2211,6 +2285,20 @@ class FusedLlamaDecoder:
         if self._resid is None:
             self._resid = self.workspace_views()["resid"]
         embed_pool_(self._resid, self.weights[self.table.index("final_norm")], acc, out, jobs, self.dims.eps)
+
+    def lm_score(self, target: torch.Tensor, lse: torch.Tensor, z_target: torch.Tensor, z_top: torch.Tensor,
+                 id_top: torch.Tensor) -> None:
+        """``lm_score_`` over the first ``len(target)`` rows the last ``step`` left in ``resid``, with this model's
+        LM head (and its row scales when it is FP8) and eps. The targets are the caller's, built on the host and
+        below ``dims.vocab``: nothing here reads the device, so the call can follow a graph replay on the stream."""
+        if self._resid is None:
+            self._resid = self.workspace_views()["resid"]
+        if self._score_work is None:
+            words = lm_score_plan(self.dims.vocab, self.dims.dim, MAX_ROWS).work_words
+            self._score_work = torch.empty(words, dtype=torch.int32, device=self.device)
+        scale = self.weights[self.table.scale_index("lm_head")] if self.weight_format.lm_head else None
+        lm_score_(self._resid[:target.shape[0]], self.weights[self.table.index("lm_head")], scale, self.dims.eps,
+                  target, lse, z_target, z_top, id_top, self._score_work, check_targets=False)
 
     def step(self, tokens: torch.Tensor, pos: torch.Tensor, logits: torch.Tensor, ids: torch.Tensor,
              slots: torch.Tensor | None = None, emit_rows: int = 0, adapters: torch.Tensor | None = None) -> None:

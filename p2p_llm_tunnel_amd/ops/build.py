@@ -2,14 +2,14 @@
 
     hipcc -O3 --offload-arch=gfx950 -shared -fPIC decode_moe.o decode_w4g.o kernels.hip decode_fused.hip sample.hip \
           logprobs.hip kv_copy.hip embed_pool.hip penalty.hip guide.hip decode_lora.hip lora_delta.hip decode_f8g.hip \
-          -o _hip_ops.so
+          lm_score.hip -o _hip_ops.so
 
 decode_moe.hip (the routed-expert FFN's kernels) is compiled to an object first, with the same flags and without packed
 fp32 instructions (``NO_PK_F32``), and so is decode_w4g.hip (the grouped int4 instantiations of the fused GEMM, whose
 decode is scalar fp32 arithmetic); every other source is compiled as it always was, so their code does not change.
 decode_lora.hip (the LoRA-delta instantiations of the fused GEMM) and lora_delta.hip (k_lora_delta) are translation
 units of their own with the common flags (docs/LORA.md), and so is decode_f8g.hip (the block-scaled FP8 instantiations
-of the fused GEMM; docs/WEIGHT_FP8G128.md).
+of the fused GEMM; docs/WEIGHT_FP8G128.md), and lm_score.hip (the prompt scorer's LM head; docs/PROMPT_LOGPROBS.md).
 
 Cross-compiles on a CPU-only host; the .so travels with the repo snapshot to
 the GPU box.
@@ -24,7 +24,7 @@ import tempfile
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRCS = [os.path.join(HERE, f) for f in ("kernels.hip", "decode_fused.hip", "sample.hip", "logprobs.hip",
                                           "kv_copy.hip", "embed_pool.hip", "penalty.hip", "guide.hip",
-                                          "decode_lora.hip", "lora_delta.hip", "decode_f8g.hip")]
+                                          "decode_lora.hip", "lora_delta.hip", "decode_f8g.hip", "lm_score.hip")]
 MOE_SRC = os.path.join(HERE, "decode_moe.hip")
 W4G_SRC = os.path.join(HERE, "decode_w4g.hip")
 DEPS = SRCS + [MOE_SRC, W4G_SRC] + [os.path.join(HERE, h) for h in (
